@@ -7,8 +7,13 @@
 
 A "step" is one LeapFrogSimulator.step() (kick-drift, one all-pairs force evaluation, kick) on a
 seeded Plummer sphere already resident in HBM. EXACTLY --steps steps are timed per window (barrier +
-synchronize on both sides, MAX over ranks); the window is repeated >= --repeats times (>= 1 s of timed
-steps in all) and `value` / `ms_per_step` are the MEDIAN window's. Workload: 65 536 particles PER GPU, i.e.
+synchronize on both sides, MAX over ranks), every window starting from the same seeded initial state.
+A plain run times ONE window: it sets up, pre-warms and warms up, times the --steps steps, writes the
+last step's positions / velocities / accelerations if --dump-outputs DIR is given, and prints the line.
+--full repeats the window >= --repeats (5) times (>= 1 s of timed steps in all; `value` / `ms_per_step`
+are then the MEDIAN window's) and adds everything else: the roofline leg (HIP events around the force
+kernel), the general-mass kernel, the sharded step's phases, the strong-scaling leg, the CPU baseline
+and the surrogate / training legs. Workload: 65 536 particles PER GPU, i.e.
 BASELINE.json configs[1] at N=1 (65 536 bodies, one MI355X) and configs[4] at N=8 (524 288 bodies
 range-sharded over 8 GPUs with one RCCL all-gather of positions per step). pairs/step = n_total^2
 (the reference evaluates every (i,j) incl. i=j, simulation.py:80-88), one force evaluation per step.
@@ -118,6 +123,29 @@ def cpu_baseline(n, seed, budget_s):
     return out
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(sim, out_dir, rank):
+    """What a caller of the timed path holds after its last step: positions, velocities, accelerations (global
+    order, fp32) as out_dir/<name>.npy. Above DUMP_MAX_BYTES in all, a fixed seeded sample of rows is written,
+    its global row indices in sample_rows.npy. Sharded runs gather first: every rank must call this."""
+    import numpy as np
+    names = ("positions", "velocities", "accelerations")
+    arrays = [sim.gather(name) for name in names]
+    if rank != 0:
+        return
+    host = {name: a.detach().cpu().numpy().astype(np.float32) for name, a in zip(names, arrays)}
+    n = sim.n
+    if sum(a.nbytes for a in host.values()) > DUMP_MAX_BYTES:
+        rows = np.sort(np.random.default_rng(0).choice(n, DUMP_MAX_BYTES // (len(names) * 3 * 4 + 8), replace=False))
+        host = {name: a[rows] for name, a in host.items()}
+        host["sample_rows"] = rows.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in host.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -126,15 +154,26 @@ def main():
     ap.add_argument("--particles-per-gpu", type=int, default=PARTICLES_PER_GPU)
     ap.add_argument("--n-total", type=int, default=0, help="fix the TOTAL particle count (strong scaling)")
     ap.add_argument("--cpu-seconds", type=float, default=75.0,
-                    help="CPU baseline budget for the N = 65 536 leg (one whole step if it fits 0.75 x this, else a row sample); 0 disables")
+                    help="--full: CPU baseline budget for the N = 65 536 leg (one whole step if it fits 0.75 x this, else a row sample); 0 disables")
     ap.add_argument("--prewarm-seconds", type=float, default=0.5,
                     help="untimed steps run for this long before --warmup (clock ramp); 0 disables")
-    ap.add_argument("--repeats", type=int, default=5, help="minimum number of timed windows of --steps steps each")
-    ap.add_argument("--min-timed-seconds", type=float, default=1.0,
-                    help="keep adding windows until this much time has been spent in timed steps (<= 400 windows)")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="minimum number of timed windows of --steps steps each (default 1; --full: 5)")
+    ap.add_argument("--min-timed-seconds", type=float, default=None,
+                    help="keep adding windows until this much time has been spent in timed steps (<= 400 windows; "
+                         "default 0; --full: 1.0)")
     ap.add_argument("--seed", type=int, default=1234)
-    ap.add_argument("--no-surrogates", action="store_true", help="skip the secondary GNN / ContConv rollout timings")
+    ap.add_argument("--no-surrogates", action="store_true", help="--full: skip the secondary GNN / ContConv rollout timings")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary measurements (roofline, general-mass kernel, sharded phases, strong "
+                         "scaling, CPU baseline, surrogate and training legs); off: only the headline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's positions / velocities / accelerations as DIR/<name>.npy (fp32)")
     args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
+    if args.min_timed_seconds is None:
+        args.min_timed_seconds = 1.0 if args.full else 0.0
 
     import torch
     import torch.distributed as dist
@@ -169,6 +208,13 @@ def main():
     p, v, m = generate_plummer(n_total, seed=args.seed)
     sim = simulation.LeapFrogSimulator(positions=p, velocities=v, masses=m, g_const=1.0, softening=0.1,
                                        dt=0.01, calc_energy=False, device="cuda", process_group=group)
+    # every timed window starts from this state, so the last step's outputs do not depend on how many untimed
+    # steps (time-based pre-warm) or windows ran before it
+    start = (sim.positions.clone(), sim.velocities.clone(), sim.accelerations.clone())
+
+    def restore(s_, st):
+        # in place: a captured step replays on these very buffers
+        s_.positions.copy_(st[0]); s_.velocities.copy_(st[1]); s_.accelerations.copy_(st[2])
 
     def barrier():
         if group is not None:
@@ -206,7 +252,7 @@ def main():
     # fallback when the runtime refuses the capture (gloo rehearsals always do), and the JSON says which ran.
     sharded_info = None
     if sim._sharded:
-        sharded_info = {"host_enqueue_ms_eager": host_enqueue_ms(sim)}
+        sharded_info = {"host_enqueue_ms_eager": host_enqueue_ms(sim)} if args.full else {}
         want = os.environ.get("NBD_CAPTURE_SHARDED", "1") != "0" and (group is None or dist.get_backend() == "nccl")
         ok_t = torch.tensor([1 if (want and sim.capture_step()) else 0], dtype=torch.int32, device="cuda")
         if group is not None:                      # all ranks replay or none does
@@ -215,14 +261,17 @@ def main():
             sim._step_graph = None
         sharded_info["captured"] = bool(ok_t.item())
         sharded_info["step_ran"] = "hipGraph replay (kick-drift, all-gather, both force blocks)" if ok_t.item() else "eager launches"
-        if ok_t.item():
+        if ok_t.item() and args.full:
             sharded_info["host_enqueue_ms_captured"] = host_enqueue_ms(sim)
 
-    def timed_windows(s_, min_repeats, min_total_s):
+    def timed_windows(s_, min_repeats, min_total_s, start_state=None):
         """EXACTLY --steps steps per window, each window bracketed by barrier + synchronize on both sides and the MAX
         over ranks taken per window; repeated (median of >= 5 repeats) until >= min_total_s of timed
-        steps have run -- one 20 ms window is inside the 4 % box-to-box / clock noise it cannot report."""
+        steps have run -- one 20 ms window is inside the 4 % box-to-box / clock noise it cannot report.
+        start_state: restored (untimed) before every window."""
         def one():
+            if start_state is not None:
+                restore(s_, start_state)
             barrier()
             t_ = time.perf_counter()
             for _ in range(args.steps):
@@ -238,8 +287,11 @@ def main():
         if group is not None:
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
         return sorted(t.tolist())
-    windows = timed_windows(sim, args.repeats, args.min_timed_seconds)
+    windows = timed_windows(sim, args.repeats, args.min_timed_seconds, start)
     elapsed = windows[len(windows) // 2] if len(windows) % 2 else 0.5 * (windows[len(windows) // 2 - 1] + windows[len(windows) // 2])
+    assert torch.isfinite(sim.positions).all()
+    if args.dump_outputs:
+        dump_outputs(sim, args.dump_outputs, rank)
 
     # roofline leg (every rank runs it to stay in lock-step; rank 0 reports): HIP events on the
     # launch stream around the force kernel of K further steps
@@ -275,12 +327,14 @@ def main():
             evs.append((e0, e1))
         barrier()
         return sum(a.elapsed_time(b) for a, b in evs) / len(evs)
-    k_ms = kernel_event_ms(sim)
-    assert torch.isfinite(sim.positions).all()
+    k_ms = None
+    if args.full:
+        k_ms = kernel_event_ms(sim)
+        assert torch.isfinite(sim.positions).all()
 
     # where a rank's step goes (HIP events between the phases of EAGER steps, MAX over ranks): own x own block, launch
     # stream idle until the all-gather has landed, own x remote block; beside the host's enqueue time
-    if sharded_info is not None:
+    if sharded_info is not None and args.full:
         ph = [sim.step_phases() for _ in range(max(args.steps, 5))]
         keys = ("kick_drift_ms", "local_force_ms", "gather_wait_ms", "remote_force_ms", "host_enqueue_ms")
         t_ph = torch.tensor([sorted(x[k_] for x in ph)[len(ph) // 2] for k_ in keys], dtype=torch.float64, device="cuda")
@@ -294,7 +348,7 @@ def main():
     # the general-mass kernel beside the equal-mass headline (the reference multiplies by m_j per pair,
     # simulation.py:86-88; the Plummer set's equal masses let the headline kernel factor the mass out of the sum)
     general = None
-    if world == 1 and not strong and getattr(sim, "_uniform", None) is not None:
+    if args.full and world == 1 and not strong and getattr(sim, "_uniform", None) is not None:
         os.environ["NBD_UNIFORM_MASS"] = "0"
         try:
             sim_g = simulation.LeapFrogSimulator(positions=p, velocities=v, masses=m, g_const=1.0, softening=0.1,
@@ -316,7 +370,7 @@ def main():
     # BASELINE.json's metric string reads "N = 65 536 ... 1/2/4/8 MI355X": next to the weak series above
     # (fixed bodies per GPU, configs[4] at 8 GPUs), time the SAME 65 536-body problem split over all ranks.
     strong_leg = None
-    if world > 1 and not strong:
+    if args.full and world > 1 and not strong:
         n_s = args.particles_per_gpu
         p2, v2, m2 = generate_plummer(n_s, seed=args.seed)
         sim2 = simulation.LeapFrogSimulator(positions=p2, velocities=v2, masses=m2, g_const=1.0, softening=0.1,
@@ -339,15 +393,6 @@ def main():
     pairs_per_step = float(n_total) * float(n_total)
     value = pairs_per_step * args.steps / elapsed
     n_loc = sim.part.n_local
-    pairs_per_launch = float(n_loc) * float(n_total)
-    achieved = pairs_per_launch * FLOP_PER_PAIR / (k_ms * 1e-3) / 1e12
-    traffic, traffic_source = None, None
-    tpath = os.path.join(ROOT, "profiles", "traffic.json")
-    if os.path.exists(tpath) and world == 1 and not strong:
-        tj = json.load(open(tpath))
-        traffic = tj.get("accel_kernel_hbm_bytes_per_launch")
-        traffic_source = ("profiles/traffic.json (" + str(tj.get("source", "rocprofv3 --pmc FETCH_SIZE x 2 + WRITE_SIZE passes of an earlier run of this command")) +
-                          "): a constant read from the repository, NOT measured by this run")
     plan = direct.accel_plan(n_total, n_loc) if not sim._sharded else direct.shard_plan(n_total, sim.part.lo, n_loc)
     out = {
         "metric": "pair-interactions/sec, direct O(N^2) leapfrog N-body, fp32",
@@ -371,7 +416,19 @@ def main():
                            f"overlapped with the own-bodies force block",
             "launch_plan": plan,
         },
-        "roofline": {
+        "full": args.full,
+    }
+    if args.full:
+        pairs_per_launch = float(n_loc) * float(n_total)
+        achieved = pairs_per_launch * FLOP_PER_PAIR / (k_ms * 1e-3) / 1e12
+        traffic, traffic_source = None, None
+        tpath = os.path.join(ROOT, "profiles", "traffic.json")
+        if os.path.exists(tpath) and world == 1 and not strong:
+            tj = json.load(open(tpath))
+            traffic = tj.get("accel_kernel_hbm_bytes_per_launch")
+            traffic_source = ("profiles/traffic.json (" + str(tj.get("source", "rocprofv3 --pmc FETCH_SIZE x 2 + WRITE_SIZE passes of an earlier run of this command")) +
+                              "): a constant read from the repository, NOT measured by this run")
+        out["roofline"] = {
             # compute roofline ("mfma" in the harness's two-way hbm|mfma taxonomy): the kernel itself is fp32
             # VALU -- all-pairs gravity has no dense contraction for MFMA -- and on MI355X the fp32 vector
             # peak and the fp32 MFMA peak are the same 157.3 TFLOP/s, so the fraction is unambiguous
@@ -387,19 +444,18 @@ def main():
                     "fewer: equal masses factor out of the sum, 11 packed ops + 2 rsq per source and pair of targets). "
                     "The instruction stream's own ceiling is 128 pairs per 60 issue cycles per SIMD = 66% of this peak "
                     "at 2.4 GHz (general masses: 64 cycles, 62%)",
-        },
-    }
+        }
     if general is not None:
         out["roofline"]["general_mass"] = general
     if sharded_info is not None:
         out["sharded_step"] = sharded_info
     if strong_leg is not None:
         out["strong_scaling_n65536"] = strong_leg
-    if args.cpu_seconds > 0 and world == 1:
+    if args.full and args.cpu_seconds > 0 and world == 1:
         out["cpu_baseline"] = cpu_baseline(min(n_total, 65536), args.seed, args.cpu_seconds)
-    elif world > 1:
+    elif args.full and world > 1:
         out["cpu_baseline"] = None
-    if world == 1 and not strong and not args.no_surrogates:
+    if args.full and world == 1 and not strong and not args.no_surrogates:
         # secondary legs (BASELINE configs[2], [3]): ms per surrogate rollout step + rollout MSE
         sys.path.insert(0, os.path.join(ROOT, "tools"))
         import bench_surrogates

@@ -342,7 +342,7 @@ def test_bench_py_multi_rank_json_end_to_end(gpu_device, tmp_path):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={world}",
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", str(world),
            "--steps", "5", "--warmup", "2", "--particles-per-gpu", str(per), "--prewarm-seconds", "0.05",
-           "--min-timed-seconds", "0.05", "--repeats", "3", "--cpu-seconds", "0", "--no-surrogates"]
+           "--min-timed-seconds", "0.05", "--repeats", "3", "--cpu-seconds", "0", "--no-surrogates", "--full"]
     res = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
     assert res.returncode == 0, res.stderr[-3000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
@@ -362,6 +362,49 @@ def test_bench_py_multi_rank_json_end_to_end(gpu_device, tmp_path):
     for k in ("local_force_ms", "gather_wait_ms", "remote_force_ms", "host_enqueue_ms", "kick_drift_ms", "host_enqueue_ms_eager"):
         assert sh[k] >= 0.0, k
     assert sh["captured"] is False and sh["step_ran"] == "eager launches"      # gloo rehearsal: nothing to capture
+
+
+def test_bench_py_plain_run_times_exactly_steps_and_dumps_outputs(gpu_device, tmp_path):
+    """bench.py without --full: ONE window of exactly --steps timed steps, none of the secondary legs, and with
+    --dump-outputs the last step's positions / velocities / accelerations. Every window starts from the seeded initial
+    state, so two runs dump identical arrays and they equal --steps steps of a fresh simulator, however many untimed
+    pre-warm steps ran before."""
+    import json
+    import subprocess
+    import sys
+    from conftest import ROOT
+    from galaxify import simulation
+    from nbd.plummer import generate_plummer
+    n, steps, seed = 4096, 7, 99
+    dumps = []
+    for run in range(2):
+        out_dir = tmp_path / f"out{run}"
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", "2",
+               "--particles-per-gpu", str(n), "--seed", str(seed), "--prewarm-seconds", "0.05",
+               "--dump-outputs", str(out_dir)]
+        res = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
+        assert res.returncode == 0, res.stderr[-3000:]
+        lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, res.stdout[-2000:]
+        out = json.loads(lines[0])
+        assert out["steps"] == steps and out["repeats"] == 1 and out["full"] is False
+        assert abs(out["timed_seconds_total"] * 1e3 / steps - out["ms_per_step"]) < 1e-9 * out["ms_per_step"]
+        assert out["value"] > 0 and abs(out["value"] - float(n) ** 2 / (out["ms_per_step"] * 1e-3)) < 1e-6 * out["value"]
+        assert out["unit"] == "pair-interactions/s" and out["higher_is_better"] is True and out["dtype"] == "f32"
+        for key in ("roofline", "cpu_baseline", "secondary", "strong_scaling_n65536"):
+            assert key not in out, key
+        dumps.append({k: np.load(out_dir / f"{k}.npy") for k in ("positions", "velocities", "accelerations")})
+        assert sorted(os.listdir(out_dir)) == ["accelerations.npy", "positions.npy", "velocities.npy"]
+    p, v, m = generate_plummer(n, seed=seed)
+    sim = simulation.LeapFrogSimulator(positions=p, velocities=v, masses=m, g_const=1.0, softening=0.1, dt=0.01,
+                                       calc_energy=False, device="cuda")
+    for _ in range(steps):
+        sim.step()
+    for key, ref in (("positions", sim.positions), ("velocities", sim.velocities), ("accelerations", sim.accelerations)):
+        a, b = dumps[0][key], dumps[1][key]
+        assert a.dtype == np.float32 and a.shape == (n, 3), key
+        assert np.array_equal(a, b), key                            # same arguments, same outputs
+        assert row_rel(a, _np(ref)) < 1e-6, key
 
 
 def test_captured_sharded_step_is_bit_identical_to_eager_one_rank_rccl(gpu_device):
