@@ -158,11 +158,22 @@ int nbd_leapfrog_step_ev_f32(float* pos, float* vel, const float* acc_in, float*
  * multiply by m_j (11 packed fp32 ops + 2 v_rsq_f32 per source and pair of targets instead of 12 + 2) and g_const *
  * mass_value is applied once, to the finished sum. The differences r_j - r_i stay the exact fp32 subtractions of
  * simulation.py:80; one multiplication per sum rounds differently from one per term. The caller vouches that every
- * entry of `mass` equals mass_value. Workspace: nbd_step_workspace_bytes(n). */
+ * entry of `mass` equals mass_value. From n = 65 536 on (softening_sq >= 1e-24) the force evaluates each off-diagonal pair
+ * once and feeds both rows (Newton's third law; nbd_accel_sym_uniform_f32), same terms summed in another fixed order.
+ * Workspace: nbd_step_workspace_bytes(n). */
 int nbd_leapfrog_step_uniform_f32(float* pos, float* vel, const float* acc_in, float* acc_out, const float* mass,
                                   float mass_value, int n, float dt_half, float dt, float softening_sq, float g_const,
                                   float* posm, void* workspace, size_t workspace_bytes, nbd_stream_t stream,
                                   void* ev_force_begin, void* ev_force_end);
+
+/* The force of nbd_leapfrog_step_uniform_f32's symmetric path on its own (tests, profiling): acc = g_const * mass_value *
+ * sum_j d_ij s_ij^3 over all n bodies of posm, each off-diagonal pair evaluated once (Newton's third law). Needs
+ * n >= 2048 and softening_sq >= 1e-24 (else NBD_E_UNSUPPORTED). Deterministic. variant: the register shape (0: the
+ * step's, 4 source groups per tile pair; 1: 2 source groups), same sums in another order. Workspace:
+ * nbd_accel_sym_workspace_bytes(n). */
+size_t nbd_accel_sym_workspace_bytes(int n);
+int nbd_accel_sym_uniform_f32(const float* posm, int n, float softening_sq, float g_const, float mass_value,
+                              float* acc_out, void* workspace, size_t workspace_bytes, int variant, nbd_stream_t stream);
 
 /* One whole EulerSimulator.step (simulation.py:173-187): force -> kick(dt) -> drift(dt). */
 int nbd_euler_step_f32(float* pos, float* vel, float* acc_out, const float* mass, int n, float dt,

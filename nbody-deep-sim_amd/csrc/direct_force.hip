@@ -142,12 +142,19 @@ __device__ __forceinline__ void interact_block(const f4* __restrict__ buf, const
 // c_j r_j - c_j r_i rounds the product c_j r_j -- and a close pair amplifies that half-ulp shift of the source:
 // 1.8e-4 on one row of the Plummer N = 1000 golden, against the 1e-5 bar. Rejected; measured +2.9 %.) Padding entries
 // are no zeros without the mass factor: the chunk that holds them (sv.tail) takes the masked path.
+// out_rows: rows between slabs of `out` (n_tgt, or the system size when the launch fills rows of a wider slot array).
+// tile_len: gridDim.z > 1 runs independent diagonal blocks, block z taking targets AND sources [z*tile_len, +n_tgt)
+// (the diagonal blocks of the symmetric step, see accel_sym_kernel); 0 for every other launch.
 template <bool MASKED, int KU, bool UNI = false>
 __global__ __launch_bounds__(64 * kWaves, KU == 4 ? 8 : 5) void accel_kernel(
     const f4* __restrict__ src, const SrcView sv, const f4* __restrict__ tgt,
-    int n_tgt, int tgt_off, float eps2, float scale, float* __restrict__ out) {
+    int n_tgt, int tgt_off, float eps2, float scale, float* __restrict__ out, int out_rows, int tile_len) {
   // [wave][buffer][64] staging + [wave][6][64] partials, ONE object (keeps hipcc's waits sane)
   __shared__ f4 lds[kWaves * 2 * kChunk + kWaves * 6 * 64 / 4];
+  {
+    const int tz = blockIdx.z * tile_len;
+    src += tz; tgt += tz; out += (size_t)tz * 3;
+  }
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int t_base = blockIdx.x * kTgtPerWG;
@@ -195,7 +202,7 @@ __global__ __launch_bounds__(64 * kWaves, KU == 4 ? 8 : 5) void accel_kernel(
   mine[2 * 64 + lane] = ay.x; mine[3 * 64 + lane] = ay.y;
   mine[4 * 64 + lane] = az.x; mine[5 * 64 + lane] = az.y;
   __syncthreads();
-  float* dst = out + ((size_t)blockIdx.y * n_tgt + t_base) * 3;
+  float* dst = out + ((size_t)blockIdx.y * out_rows + t_base) * 3;
   const int n_valid = min(kTgtPerWG, n_tgt - t_base) * 3;
   for (int o = threadIdx.x; o < n_valid; o += 64 * kWaves) {
     const int lt = o / 3, comp = o - lt * 3;
@@ -205,6 +212,170 @@ __global__ __launch_bounds__(64 * kWaves, KU == 4 ? 8 : 5) void accel_kernel(
     for (int w = 1; w < kWaves; ++w) sum += red[w * 6 * 64 + idx];
     dst[o] = __fmul_rn(scale, sum);
   }
+}
+
+// ---- symmetric force for EQUAL masses: every off-diagonal pair evaluated once (Newton's third law).
+// The term of j on i is the exact negative of the term of i on j (r_j - r_i and r_i - r_j are exact negatives in fp32,
+// r^2 and rsq come out bit-identical), so one evaluation feeds both rows; only the order of summation changes.
+//
+// The first core = M * S bodies (M even) are cut into M super-tiles of S = 1024. The M (M - 1) / 2 off-diagonal tile
+// pairs are the M - 1 rounds of a round-robin tournament (circle method): round r pairs every tile with exactly one
+// other, so one round writes each core row exactly once. Round r writes slot (r + 1) % K of the float[K][n][3] partial
+// array (K = min(M, 16)); the diagonal blocks (accel_kernel, one launch) write slot 0. The rounds go in launches of at
+// most K: the first launch (rounds 0 .. K-2) stores, every later one adds to what an earlier launch stored, so no two
+// workgroups of one launch touch the same (slot, row) and the per-row sums have a fixed order: deterministic, no atomics,
+// every slot written every step (no zero fill: capturable), and the workspace is the 16 slots the all-pairs step needs.
+//
+// One workgroup = one tile pair (a, b): 4 target groups x SG source groups of waves. Wave (tg, sg) holds targets
+// a*S + tg*256 + 64 t + lane (t = 0..3, as the packed pairs {t0, t1}, {t2, t3}) and walks the 16 / SG 64-body chunks
+// of source group sg of tile b. Step k of a chunk: lane l takes source (l + k) & 63 (a lane-varying ds_read_b128 from a
+// chunk stored twice, so the address is the immediate offset k * 16 and never wraps), adds w d to its own sums and
+// -w d to the reaction registers of that source, then the 6 reaction VGPRs move one lane down (DPP wave_rol:1): after
+// 64 steps lane l holds the reaction on source l from the wave's 256 targets. At the end of a chunk the 4 target groups
+// add their reactions through LDS in wave order (one barrier per chunk); at the end of the tile pair the SG source
+// groups add their own sums through LDS in order. Per step and pair of targets: 14 packed ops + 2 v_rsq_f32; per step
+// 6 DPP moves for 4 targets.
+constexpr int kSymTile = 1024;                   // S
+constexpr int kSymChunks = kSymTile / kChunk;    // 16
+constexpr int kSymSlots = 16;                    // K at most: the workspace of the all-pairs step at N = 65 536
+
+__device__ __forceinline__ float rol1(float x) {  // lane l <- lane (l + 1) & 63
+  return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(x), 0x134 /* wave_rol:1 */, 0xf, 0xf, false));
+}
+
+// one source against two targets: own sums += w d, reaction -= w d (the neg modifier of v_pk_fma)
+__device__ __forceinline__ void sym_pair(const f4 p, const f2 xi, const f2 yi, const f2 zi, const f2 e2,
+                                         f2& ax, f2& ay, f2& az, f2& rx, f2& ry, f2& rz) {
+  const f2 dx = f2{p.x, p.x} - xi, dy = f2{p.y, p.y} - yi, dz = f2{p.z, p.z} - zi;  // r_j - r_i
+  f2 r2 = __builtin_elementwise_fma(dx, dx, e2);
+  r2 = __builtin_elementwise_fma(dy, dy, r2);
+  r2 = __builtin_elementwise_fma(dz, dz, r2);
+  const f2 s = {__builtin_amdgcn_rsqf(r2.x), __builtin_amdgcn_rsqf(r2.y)};
+  const f2 w = (s * s) * s;
+  ax = __builtin_elementwise_fma(w, dx, ax);
+  ay = __builtin_elementwise_fma(w, dy, ay);
+  az = __builtin_elementwise_fma(w, dz, az);
+  rx = __builtin_elementwise_fma(-w, dx, rx);
+  ry = __builtin_elementwise_fma(-w, dy, ry);
+  rz = __builtin_elementwise_fma(-w, dz, rz);
+}
+
+// grid = (rounds of this launch) x M/2 workgroups; block = 256 * SG. Unscaled sums (finish_kernel applies G m).
+template <int SG>
+__global__ __launch_bounds__(256 * SG, 2 * SG) void accel_sym_kernel(const f4* __restrict__ posm, int n, int m,
+                                                                     int r0, int n_slots, float eps2,
+                                                                     float* __restrict__ out) {
+  constexpr int CPS = kSymChunks / SG;           // chunks per source group
+  constexpr int kStageF4 = SG * 2 * 2 * kChunk;  // [sg][buffer][copy][64] f4
+  constexpr int kRedF = 2 * 4 * SG * 3 * 64;     // [parity][wave][comp][lane] floats
+  constexpr int kOwnF = SG * 4 * 12 * 64;        // [sg][tg][comp * 4 + t][lane] floats
+  constexpr int kLdsF = (kStageF4 * 4 + kRedF > kOwnF) ? kStageF4 * 4 + kRedF : kOwnF;
+  __shared__ f4 lds[kLdsF / 4];                  // ONE object (keeps hipcc's waits sane)
+  float* const ldsf = reinterpret_cast<float*>(lds);
+
+  // tile pair of this workgroup: round r of the circle method, match i
+  const int half = m >> 1, mm = m - 1;
+  const int rr = blockIdx.x / half, i = blockIdx.x - rr * half, r = r0 + rr;
+  const int ta = i == 0 ? r % mm : (r + i) % mm;
+  const int tb = i == 0 ? mm : (r - i + mm) % mm;
+  const int slot = (r + 1) % n_slots;
+  const bool init = r + 1 < n_slots;
+
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int tg = wave & 3, sg = wave >> 2;
+  const int row0 = ta * kSymTile + tg * 256 + lane;
+  const f4 q0 = posm[row0], q1 = posm[row0 + 64], q2 = posm[row0 + 128], q3 = posm[row0 + 192];
+  const f2 xa = {q0.x, q1.x}, ya = {q0.y, q1.y}, za = {q0.z, q1.z};
+  const f2 xb = {q2.x, q3.x}, yb = {q2.y, q3.y}, zb = {q2.z, q3.z};
+  f2 axa = {0.f, 0.f}, aya = {0.f, 0.f}, aza = {0.f, 0.f}, axb = {0.f, 0.f}, ayb = {0.f, 0.f}, azb = {0.f, 0.f};
+  f2 e2 = {eps2, eps2};
+  asm volatile("" : "+v"(e2));  // keep eps^2 in VGPRs: an SGPR operand halves v_pk_fma issue
+
+  // sources: the chunks of source group sg of tile b, staged by target group 3 (not a reducer: its vmcnt counts only
+  // the staging loads) into a buffer the 4 target groups share; the per-chunk barrier publishes and releases it
+  f4* const stage = &lds[sg * 4 * kChunk];
+  const int c0 = tb * kSymChunks + sg * CPS;
+  const f4* const s_lane = posm + lane + (size_t)c0 * kChunk;
+  auto fetch = [&](int c, int b) {
+    __builtin_amdgcn_global_load_lds(GPTR(s_lane + c * kChunk), LPTR(stage + b * 2 * kChunk), 16, 0, 0);
+    __builtin_amdgcn_global_load_lds(GPTR(s_lane + c * kChunk), LPTR(stage + b * 2 * kChunk + kChunk), 16, 0, 0);
+  };
+  if (tg == 3) {
+    fetch(0, 0);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  }
+  __syncthreads();
+
+  for (int c = 0; c < CPS; ++c) {
+    const int b = c & 1;
+    if (tg == 3 && c + 1 < CPS) fetch(c + 1, b ^ 1);
+    // reducer tg (< 3) adds component tg of this chunk's reaction to what an earlier launch stored: fetch it now
+    float* const o_react = out + ((size_t)slot * n + (size_t)(c0 + c) * kChunk + lane) * 3 + tg;
+    float old = 0.f;
+    if (!init && tg < 3) old = *o_react;
+    const f4* buf = stage + b * 2 * kChunk + lane;
+    f2 rx = {0.f, 0.f}, ry = {0.f, 0.f}, rz = {0.f, 0.f};
+#pragma unroll 2
+    for (int k = 0; k < kChunk; ++k) {
+      const f4 p = buf[k];
+      sym_pair(p, xa, ya, za, e2, axa, aya, aza, rx, ry, rz);
+      sym_pair(p, xb, yb, zb, e2, axb, ayb, azb, rx, ry, rz);
+      rx = f2{rol1(rx.x), rol1(rx.y)};
+      ry = f2{rol1(ry.x), rol1(ry.y)};
+      rz = f2{rol1(rz.x), rol1(rz.y)};
+    }
+    float* const red = ldsf + kStageF4 * 4 + b * (4 * SG * 3 * 64);
+    float* const mine = red + wave * 3 * 64;
+    mine[lane] = rx.x + rx.y;
+    mine[64 + lane] = ry.x + ry.y;
+    mine[128 + lane] = rz.x + rz.y;
+    if (tg == 3 && c + 1 < CPS) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // chunk c + 1 has landed
+    __syncthreads();
+    if (tg < 3) {
+      const float* rs = red + (sg * 4) * 3 * 64 + tg * 64 + lane;
+      const float v = ((rs[0] + rs[3 * 64]) + rs[6 * 64]) + rs[9 * 64];
+      *o_react = init ? v : old + v;
+    }
+  }
+
+  // own sums: the SG source groups of a target group in order, through LDS (staging and reaction space are free)
+  float* const o_own = out + ((size_t)slot * n + row0) * 3;
+  const f2 own[6] = {axa, aya, aza, axb, ayb, azb};
+  if (SG == 1) {
+#pragma unroll
+    for (int t = 0; t < 4; ++t)
+#pragma unroll
+      for (int comp = 0; comp < 3; ++comp) {
+        const f2 v2 = own[(t >> 1) * 3 + comp];
+        const float v = (t & 1) ? v2.y : v2.x;
+        float* o = o_own + t * 64 * 3 + comp;
+        *o = init ? v : *o + v;
+      }
+    return;
+  }
+  __syncthreads();  // every reduction read of the last chunk is done
+  float* const mo = ldsf + (sg * 4 + tg) * 12 * 64;
+#pragma unroll
+  for (int t = 0; t < 4; ++t)
+#pragma unroll
+    for (int comp = 0; comp < 3; ++comp) {
+      const f2 v2 = own[(t >> 1) * 3 + comp];
+      mo[(comp * 4 + t) * 64 + lane] = (t & 1) ? v2.y : v2.x;
+    }
+  __syncthreads();
+  if (sg != 0) return;
+#pragma unroll
+  for (int t = 0; t < 4; ++t)
+#pragma unroll
+    for (int comp = 0; comp < 3; ++comp) {
+      const float* src = ldsf + tg * 12 * 64 + (comp * 4 + t) * 64 + lane;
+      float v = src[0];
+#pragma unroll
+      for (int g = 1; g < SG; ++g) v += src[g * 4 * 12 * 64];
+      float* o = o_own + t * 64 * 3 + comp;
+      *o = init ? v : *o + v;
+    }
 }
 
 // acc = g * (slab_0 + slab_1 + ...), optional fused kick v += c * acc (simulation.py:88,170).
@@ -489,14 +660,15 @@ int excluded_view(int n_src, int ex_lo, int ex_hi, SrcView* v) {
 // force into slabs (or straight into acc_out when one slab), no finishing pass
 int launch_accel(const float* posm_src, SrcView sv, const float* posm_tgt, int n_tgt, int off,
                  float eps2, float direct_scale, float* slabs_or_acc, const AccelPlan& p,
-                 hipStream_t st, bool uniform = false) {
-  dim3 grid(p.groups, p.slabs), block(64 * kWaves);
+                 hipStream_t st, bool uniform = false, int out_rows = 0, int tiles = 1, int tile_len = 0) {
+  dim3 grid(p.groups, p.slabs, tiles), block(64 * kWaves);
+  if (out_rows <= 0) out_rows = n_tgt;
   const f4* s = reinterpret_cast<const f4*>(posm_src);
   const f4* t = reinterpret_cast<const f4*>(posm_tgt);
   sv.n_chunks = p.n_chunks;
   sv.cpw_q = p.n_chunks / (p.slabs * kWaves); sv.cpw_r = p.n_chunks % (p.slabs * kWaves);
   const bool masked = eps2 < kEps2Masked;
-#define NBD_LAUNCH(M, K, U) accel_kernel<M, K, U><<<grid, block, 0, st>>>(s, sv, t, n_tgt, off, eps2, direct_scale, slabs_or_acc)
+#define NBD_LAUNCH(M, K, U) accel_kernel<M, K, U><<<grid, block, 0, st>>>(s, sv, t, n_tgt, off, eps2, direct_scale, slabs_or_acc, out_rows, tile_len)
   if (uniform) {
     if (p.variant == 1) { if (masked) NBD_LAUNCH(true, 4, true); else NBD_LAUNCH(false, 4, true); }
     else                { if (masked) NBD_LAUNCH(true, 8, true); else NBD_LAUNCH(false, 8, true); }
@@ -509,6 +681,71 @@ int launch_accel(const float* posm_src, SrcView sv, const float* posm_tgt, int n
 }
 
 bool misaligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; }
+
+// ---- the symmetric force's launch plan (accel_sym_kernel): M even tiles of kSymTile, K slots, the remainder rows
+// [core, n) in one more slot
+struct SymPlan { int m, core, rem, slots, total_slots; };
+
+SymPlan plan_sym(int n) {
+  SymPlan p;
+  p.m = n / kSymTile;
+  p.m &= ~1;                                  // the circle method pairs an even number of tiles
+  p.core = p.m * kSymTile;
+  p.rem = n - p.core;
+  p.slots = p.m < kSymSlots ? p.m : kSymSlots;
+  p.total_slots = p.slots + (p.rem > 0 ? 1 : 0);
+  return p;
+}
+
+size_t sym_workspace_bytes(int n) {
+  const SymPlan p = plan_sym(n);
+  return p.m < 2 ? 0 : (size_t)p.total_slots * n * 3 * sizeof(float);
+}
+
+// the uniform-mass leapfrog step takes the symmetric force from this size on
+constexpr int kSymStepMinN = 65536;
+bool sym_step(int n, float eps2) { return n >= kSymStepMinN && eps2 >= kEps2Masked; }
+
+// unscaled sum_j d_ij s_ij^3 of every row into slots [0, total_slots) of float[total_slots][n][3]; needs m >= 2 and
+// eps2 >= kEps2Masked (the i == j term of a diagonal block is then an exact zero)
+// variant 0: 4 source groups (16-wave workgroups, 64 VGPRs, 2 per CU: 8 waves per SIMD); 1: 2 source groups (8 waves,
+// 86 VGPRs: 4 waves per SIMD)
+int launch_sym(const float* posm, int n, float eps2, float* slots, hipStream_t st, int variant = 0) {
+  const SymPlan sp = plan_sym(n);
+  const f4* pm = reinterpret_cast<const f4*>(posm);
+  // the diagonal blocks (a, a): the all-pairs kernel on each tile, slot 0
+  AccelPlan dp;
+  dp.groups = kSymTile / kTgtPerWG; dp.slabs = 1; dp.n_chunks = kSymChunks; dp.variant = 0;
+  dp.cpw = ceil_div(kSymChunks, kWaves);
+  int rc = launch_accel(posm, full_view(kSymTile, dp), posm, kSymTile, 0, eps2, 1.0f, slots, dp, st, true, n, sp.m,
+                        kSymTile);
+  if (rc) return rc;
+  // the off-diagonal rounds: [0, K-1) stores, then launches of K rounds add
+  const int rounds = sp.m - 1;
+  for (int r0 = 0; r0 < rounds;) {
+    const int r1 = r0 == 0 ? (sp.slots - 1 < rounds ? sp.slots - 1 : rounds) : (r0 + sp.slots < rounds ? r0 + sp.slots : rounds);
+    const int wgs = (r1 - r0) * (sp.m / 2);
+    if (variant == 1) accel_sym_kernel<2><<<wgs, 512, 0, st>>>(pm, n, sp.m, r0, sp.slots, eps2, slots);
+    else accel_sym_kernel<4><<<wgs, 1024, 0, st>>>(pm, n, sp.m, r0, sp.slots, eps2, slots);
+    if ((rc = launch_status())) return rc;
+    r0 = r1;
+  }
+  if (sp.rem == 0) return 0;
+  // remainder rows [core, n) against all n sources, split over every slot (the symmetric launches never write them)
+  AccelPlan tp;
+  tp.groups = ceil_div(sp.rem, kTgtPerWG); tp.slabs = sp.total_slots; tp.n_chunks = ceil_div(n, kChunk); tp.variant = 0;
+  tp.cpw = ceil_div(tp.n_chunks, tp.slabs * kWaves);
+  rc = launch_accel(posm, full_view(n, tp), posm + (size_t)sp.core * 4, sp.rem, sp.core, eps2, 1.0f,
+                    slots + (size_t)sp.core * 3, tp, st, true, n);
+  if (rc) return rc;
+  // core rows against the remainder sources: the last slot
+  SrcView sv;
+  AccelPlan cp;
+  cp.n_chunks = excluded_view(n, 0, sp.core, &sv);
+  cp.groups = sp.core / kTgtPerWG; cp.slabs = 1; cp.variant = 0; cp.cpw = ceil_div(cp.n_chunks, kWaves);
+  return launch_accel(posm, sv, posm, sp.core, 0, eps2, 1.0f, slots + (size_t)sp.slots * n * 3, cp, st, true, n);
+}
+
 
 }  // namespace
 
@@ -562,7 +799,27 @@ int nbd_accel_plan(int n_src, int n_tgt, int* groups, int* slabs, int* chunks_pe
 
 size_t nbd_step_workspace_bytes(int n) {
   if (n <= 0) return 0;
-  return (size_t)plan_accel(n, n).slabs * n * 3 * sizeof(float);
+  const size_t all_pairs = (size_t)plan_accel(n, n).slabs * n * 3 * sizeof(float);
+  const size_t sym = sym_step(n, kEps2Masked) ? sym_workspace_bytes(n) : 0;
+  return sym > all_pairs ? sym : all_pairs;
+}
+
+size_t nbd_accel_sym_workspace_bytes(int n) { return n <= 0 ? 0 : sym_workspace_bytes(n); }
+
+int nbd_accel_sym_uniform_f32(const float* posm, int n, float softening_sq, float g_const, float mass_value,
+                              float* acc_out, void* workspace, size_t workspace_bytes, int variant, nbd_stream_t stream) {
+  if (n < 0 || (n > 0 && (!posm || !acc_out)) || misaligned16(posm) || variant < 0 || variant > 1) return NBD_E_BADARG;
+  if (n == 0) return 0;
+  if (plan_sym(n).m < 2 || softening_sq < kEps2Masked) return NBD_E_UNSUPPORTED;
+  if (!workspace || workspace_bytes < sym_workspace_bytes(n)) return NBD_E_WORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  float* slots = static_cast<float*>(workspace);
+  int rc = launch_sym(posm, n, softening_sq, slots, st, variant);
+  if (rc) return rc;
+  const int n3 = 3 * n;
+  finish_kernel<<<ceil_div(n3, 64), 256, 0, st>>>(slots, plan_sym(n).total_slots, (size_t)n3, g_const * mass_value,
+                                                   acc_out, nullptr, 0.f, n3);
+  return launch_status();
 }
 
 int nbd_accel_f32(const float* posm_src, int n_src, const float* posm_tgt, int n_tgt,
@@ -818,18 +1075,21 @@ int nbd_leapfrog_step_uniform_f32(float* pos, float* vel, const float* acc_in, f
   if (n == 0) return 0;
   if (!pos || !vel || !acc_in || !acc_out || !mass || !posm || misaligned16(posm)) return NBD_E_BADARG;
   hipStream_t st = (hipStream_t)stream;
+  const bool sym = sym_step(n, softening_sq);   // large systems: every pair once (accel_sym_kernel)
   const AccelPlan p = plan_accel(n, n);
-  const size_t need = (size_t)p.slabs * n * 3 * sizeof(float);
+  const size_t need = sym ? sym_workspace_bytes(n) : (size_t)p.slabs * n * 3 * sizeof(float);
   if (!workspace || workspace_bytes < need) return NBD_E_WORKSPACE;
   int rc = nbd_kick_drift_f32(pos, vel, acc_in, mass, n, dt_half, dt, posm, stream);
   if (rc) return rc;
   float* slabs = static_cast<float*>(workspace);
   if (ev_force_begin && (rc = check(hipEventRecord((hipEvent_t)ev_force_begin, st)))) return rc;
-  rc = launch_accel(posm, full_view(n, p), posm, n, 0, softening_sq, 1.0f, slabs, p, st, true);
+  if (sym) rc = launch_sym(posm, n, softening_sq, slabs, st);
+  else rc = launch_accel(posm, full_view(n, p), posm, n, 0, softening_sq, 1.0f, slabs, p, st, true);
   if (rc) return rc;
   if (ev_force_end && (rc = check(hipEventRecord((hipEvent_t)ev_force_end, st)))) return rc;
   const int n3 = 3 * n;
-  finish_kernel<<<ceil_div(n3, 64), 256, 0, st>>>(slabs, p.slabs, (size_t)n3, g_const * mass_value, acc_out, vel,
+  const int n_slabs = sym ? plan_sym(n).total_slots : p.slabs;
+  finish_kernel<<<ceil_div(n3, 64), 256, 0, st>>>(slabs, n_slabs, (size_t)n3, g_const * mass_value, acc_out, vel,
                                                    dt_half, n3);
   return launch_status();
 }
