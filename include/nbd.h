@@ -189,6 +189,50 @@ size_t nbd_energy_workspace_bytes(int n);
 int nbd_energy_f32(const float* posm, const float* vel, int n, float softening, float g_const,
                    double* out_uk, void* workspace, size_t workspace_bytes, nbd_stream_t stream);
 
+/* ---------------------------------------------------------------- batched direct integrator
+ * An ensemble of S >= 1 independent systems ("scenes") in one set of arrays: scene s owns bodies
+ * [offsets[s], offsets[s + 1]) of pos / vel / acc (n,3) and mass (n,); offsets is a HOST int array of S + 1 entries,
+ * offsets[0] = 0, non-decreasing (zero-body scenes allowed). Each body feels only the bodies of its own scene, with
+ * that scene's G, softening and dt: the per-scene parameters are DEVICE fp32 arrays of S entries. The packed sources
+ * of a scene start at a multiple of NBD_SRC_PAD rows of `posm` (float4[posm_rows], 16-byte aligned). Each entry
+ * validates offsets on the host (negative / decreasing / S <= 0: NBD_E_BADARG) before it touches the device.
+ * A scene's work and summation order depend on its own size only: its results are bit-identical alone or with any
+ * other scenes, at any position, run to run (no float atomics). No host syncs, no memsets: capturable.
+ *
+ * Host-only plan query: work items (one per scene x 128-target group x slab), packed rows, and the bytes of the
+ * device plan and of the workspace. */
+int nbd_batch_plan(const int* offsets, int n_scenes, int* n_items, int* posm_rows, size_t* plan_bytes,
+                   size_t* workspace_bytes);
+/* Host-only: writes the plan (plan_bytes as nbd_batch_plan reported) into HOST memory; the caller copies it to a
+ * 16-byte-aligned device buffer once and passes that buffer, with the same offsets, to the entries below. */
+int nbd_batch_plan_fill(const int* offsets, int n_scenes, void* plan, size_t plan_bytes);
+/* posm = {x, y, z, m} of every scene (zeros in each scene's padding). */
+int nbd_batch_pack_posm_f32(const int* offsets, int n_scenes, const void* plan, size_t plan_bytes, const float* pos,
+                            const float* mass, float* posm, nbd_stream_t stream);
+/* BaseSimulator.compute_accelerations per scene (simulation.py:71-89): pack posm, then
+ * acc_i = G_s sum_{j != i, j in s} m_j d_ij (|d_ij|^2 + eps_s^2)^(-3/2) (i == j dropped by index). */
+int nbd_batch_accel_f32(const int* offsets, int n_scenes, const void* plan, size_t plan_bytes, const float* pos,
+                        const float* mass, const float* softening_sq, const float* g_const, float* acc_out,
+                        float* posm, void* workspace, size_t workspace_bytes, nbd_stream_t stream);
+/* LeapFrogSimulator.step per scene (simulation.py:153-170), three launches for all scenes: kick(dt_half_s) +
+ * drift(dt_s) + pack, the segmented force, the slab sum with G_s and the second kick fused. Leaves posm = the new
+ * positions. acc_in may alias acc_out. */
+int nbd_batch_leapfrog_step_f32(const int* offsets, int n_scenes, const void* plan, size_t plan_bytes, float* pos,
+                                float* vel, const float* acc_in, float* acc_out, const float* mass, const float* dt_half,
+                                const float* dt, const float* softening_sq, const float* g_const, float* posm,
+                                void* workspace, size_t workspace_bytes, nbd_stream_t stream);
+/* EulerSimulator.step per scene (simulation.py:173-187): force -> kick(dt_s) -> drift(dt_s); leaves posm = the
+ * moved positions. */
+int nbd_batch_euler_step_f32(const int* offsets, int n_scenes, const void* plan, size_t plan_bytes, float* pos,
+                             float* vel, float* acc_out, const float* mass, const float* dt, const float* softening_sq,
+                             const float* g_const, float* posm, void* workspace, size_t workspace_bytes,
+                             nbd_stream_t stream);
+/* compute_energies per scene (simulation.py:91-115) from posm (as packed by the entries above) and vel: out_uk is a
+ * device double[S][2] = {U_s, K_s}; a zero-body scene gives {0, 0}. */
+int nbd_batch_energies(const int* offsets, int n_scenes, const void* plan, size_t plan_bytes, const float* posm,
+                       const float* vel, const float* softening, const float* g_const, double* out_uk, void* workspace,
+                       size_t workspace_bytes, nbd_stream_t stream);
+
 /* ------------------------------------------------------------ surrogate models: graph build
  * Replace the torch_cluster kernels the reference reaches through PyG. Index-exact rule (the
  * reference delegates ties/truncation to torch_cluster; fixed here, see oracle/surrogate_oracle.py):

@@ -1,0 +1,511 @@
+// direct_batch.hip -- an ensemble of S independent systems ("scenes") advanced by one set of launches (gfx950).
+//
+// The scenes are stored back to back: bodies [off_s, off_s + n_s) of pos / vel / acc / mass belong to scene s, and
+// the packed sources {x, y, z, m} of scene s sit at rows [poff_s, poff_s + pad64(n_s)) of one posm array (every scene
+// padded to whole 64-body chunks with zero entries). Each body feels only the bodies of its own scene, with the
+// scene's own G, softening^2 and dt. C-ABI: include/nbd.h (nbd_batch_*).
+//
+// Work list (built once on the host, nbd_batch_plan / nbd_batch_plan_fill, uploaded by the caller): one item per
+// (scene, target group of 128, slab), a workgroup each. Item (s, g, k) runs the all-pairs inner loop of
+// accel_kernel (interact / interact_block of direct_kernels.h: two targets per lane, v_pk_fma_f32 + v_rsq_f32,
+// LDS-DMA staged 64-body chunks) on targets [128 g, 128 g + 128) of scene s against the chunks of ITS scene that
+// wave k * 4 + w owns. The slab count of a scene is the single-system plan for its size (nbd_accel_plan(n, n)), so
+// a scene's items, their split of the sources and the fixed-order slab sum depend on n_s alone: a scene's results
+// are bit-identical whether it runs alone or with any companions, at any position of the batch. Items are
+// dispatched largest first (the order of the work, never of any sum). No float atomics, no host syncs, no memset:
+// every launch here can be captured into a graph.
+#include <hip/hip_runtime.h>
+#include <limits.h>
+#include <stdint.h>
+#include <string.h>
+
+#include <algorithm>
+#include <vector>
+
+#include "../../include/nbd.h"
+#include "direct_kernels.h"
+
+namespace {
+
+// scene record of the device plan (8 ints, two int4 loads)
+struct SceneRec {
+  int off;      // first body of the scene in pos / vel / acc / mass
+  int n;        // bodies
+  int poff;     // first packed row (multiple of 64)
+  int ws_off;   // first float of the scene's slabs in the workspace: float[slabs][n][3]
+  int u_off;    // first fp64 energy partial of the scene: double[groups * slabs]
+  int slabs;
+  int n_chunks; // pad64(n) / 64
+  int groups;   // ceil(n / 128)
+};
+
+inline int bceil_div(int a, int b) { return (a + b - 1) / b; }
+
+// The slab count of a scene: the single-system launch plan for its size (depends on n alone).
+int scene_slabs(int n) {
+  struct Memo { int n, slabs; };
+  thread_local Memo memo[16] = {};
+  thread_local int next = 0;
+  for (const Memo& m : memo)
+    if (m.n == n && m.slabs > 0) return m.slabs;
+  int g = 0, s = 1, c = 0;
+  if (nbd_accel_plan(n, n, &g, &s, &c) != 0 || s < 1) s = 1;
+  memo[next] = {n, s};
+  next = (next + 1) & 15;
+  return s;
+}
+
+struct BatchTotals {
+  int n_scenes, n_items, n_total, n_rows;   // rows = packed rows (sum of pad64(n_s))
+  int64_t ws_floats, u_doubles;
+};
+
+// Validates host offsets (offsets[0] == 0, non-decreasing) and sums the plan's sizes. Returns 0 or NBD_E_*.
+int batch_totals(const int* offsets, int n_scenes, BatchTotals* t) {
+  if (!offsets || n_scenes <= 0 || offsets[0] != 0) return NBD_E_BADARG;
+  int64_t items = 0, rows = 0, ws = 0, ud = 0;
+  for (int s = 0; s < n_scenes; ++s) {
+    const int n = offsets[s + 1] - offsets[s];
+    if (offsets[s + 1] < offsets[s] || offsets[s + 1] < 0) return NBD_E_BADARG;
+    if (n == 0) continue;
+    const int slabs = scene_slabs(n), groups = bceil_div(n, kTgtPerWG);
+    items += (int64_t)groups * slabs;
+    rows += (int64_t)bceil_div(n, kChunk) * kChunk;
+    ws += (int64_t)slabs * n * 3;
+    ud += (int64_t)groups * slabs;
+  }
+  if (items > INT_MAX || rows > INT_MAX / 4 || ws > INT_MAX || ud > INT_MAX) return NBD_E_UNSUPPORTED;
+  t->n_scenes = n_scenes; t->n_items = (int)items; t->n_total = offsets[n_scenes]; t->n_rows = (int)rows;
+  t->ws_floats = ws; t->u_doubles = ud;
+  return 0;
+}
+
+// plan layout (int32): items int4[n_items] | scenes SceneRec[n_scenes] | row_scene int[n_rows]
+size_t plan_bytes_of(const BatchTotals& t) {
+  return (size_t)t.n_items * 16 + (size_t)t.n_scenes * sizeof(SceneRec) + (size_t)t.n_rows * 4;
+}
+// workspace: slabs (fp32) | energy partials (fp64, 8-byte aligned)
+size_t ws_u_offset(const BatchTotals& t) { return ((size_t)t.ws_floats * 4 + 15) & ~(size_t)15; }
+size_t ws_bytes_of(const BatchTotals& t) { return ws_u_offset(t) + (size_t)t.u_doubles * 8; }
+
+struct DevPlan {
+  const int4* items;
+  const SceneRec* scenes;
+  const int* row_scene;
+};
+DevPlan dev_plan(const void* plan, const BatchTotals& t) {
+  const char* p = static_cast<const char*>(plan);
+  DevPlan d;
+  d.items = reinterpret_cast<const int4*>(p);
+  d.scenes = reinterpret_cast<const SceneRec*>(p + (size_t)t.n_items * 16);
+  d.row_scene = reinterpret_cast<const int*>(p + (size_t)t.n_items * 16 + (size_t)t.n_scenes * sizeof(SceneRec));
+  return d;
+}
+
+__device__ __forceinline__ SceneRec load_scene(const SceneRec* scenes, int s) {
+  const int4* q = reinterpret_cast<const int4*>(scenes + s);
+  const int4 a = q[0], b = q[1];
+  return SceneRec{a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+}
+
+// ---- segmented force: one workgroup per item; the body of accel_kernel (KU = 8) on the item's scene. Unscaled
+// sums into slab k of the scene: ws[ws_off + (k * n + i) * 3 + c]. softening^2 < kEps2Masked takes the index-masked
+// path for the whole scene (fill_diagonal_, simulation.py:85: the i == j term and the padding are dropped by index,
+// coincident bodies give NaN in that scene only). Otherwise r^2 >= softening^2 >= 1e-24 keeps s^3 finite, and a
+// padding entry (m = 0) adds w d = 0 exactly, as in accel_kernel's general-mass path.
+__global__ __launch_bounds__(64 * kWaves, 5) void batch_accel_kernel(const f4* __restrict__ posm,
+                                                                     const int4* __restrict__ items,
+                                                                     const SceneRec* __restrict__ scenes,
+                                                                     const float* __restrict__ eps2_s,
+                                                                     float* __restrict__ ws) {
+  __shared__ f4 lds[kWaves * 2 * kChunk + kWaves * 6 * 64 / 4];
+  const int4 it = items[blockIdx.x];
+  const int s = __builtin_amdgcn_readfirstlane(it.x), grp = __builtin_amdgcn_readfirstlane(it.y);
+  const int slab = __builtin_amdgcn_readfirstlane(it.z);
+  const SceneRec sc = load_scene(scenes, s);
+  const int n = __builtin_amdgcn_readfirstlane(sc.n);
+  const int n_chunks = __builtin_amdgcn_readfirstlane(sc.n_chunks), slabs = __builtin_amdgcn_readfirstlane(sc.slabs);
+  const f4* src = posm + __builtin_amdgcn_readfirstlane(sc.poff);
+  const float eps2 = eps2_s[s];
+  const bool masked = eps2 < kEps2Masked;
+
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int t_base = grp * kTgtPerWG;
+  const int i0 = t_base + lane, i1 = t_base + 64 + lane;
+  const f4 t0 = src[min(i0, n - 1)], t1 = src[min(i1, n - 1)];
+  const f2 xi = {t0.x, t1.x}, yi = {t0.y, t1.y}, zi = {t0.z, t1.z};
+  f2 ax = {0.f, 0.f}, ay = {0.f, 0.f}, az = {0.f, 0.f};
+  f2 e2 = {eps2, eps2};
+  asm volatile("" : "+v"(e2));  // keep eps^2 in VGPRs: an SGPR operand halves v_pk_fma issue
+
+  SrcView sv;
+  sv.n_src = n; sv.n_chunks = n_chunks; sv.cpw_q = n_chunks / (slabs * kWaves); sv.cpw_r = n_chunks % (slabs * kWaves);
+  sv.skip_c0 = n_chunks; sv.skip_cn = 0; sv.ex_lo = 0; sv.ex_hi = 0; sv.edge0 = -1; sv.edge1 = -1;
+  sv.tail = (n % kChunk) ? n / kChunk : -1;
+
+  const int jw = slab * kWaves + wave;
+  const int c_begin = jw * sv.cpw_q + min(jw, sv.cpw_r), c_end = c_begin + sv.cpw_q + (jw < sv.cpw_r ? 1 : 0);
+  f4* stage = &lds[wave * 2 * kChunk];
+  const f4* s_lane = src + lane;
+  if (c_begin < c_end)
+    __builtin_amdgcn_global_load_lds(GPTR(s_lane + (size_t)c_begin * kChunk), LPTR(stage), 16, 0, 0);
+  for (int c = c_begin; c < c_end; ++c) {
+    const int b = (c - c_begin) & 1;
+    if (c + 1 < c_end) {
+      __builtin_amdgcn_global_load_lds(GPTR(s_lane + (size_t)(c + 1) * kChunk), LPTR(stage + (b ^ 1) * kChunk), 16, 0, 0);
+      asm volatile("s_waitcnt vmcnt(1)" ::: "memory");  // chunk c has landed, c+1 in flight
+    } else {
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
+    const f4* buf = stage + b * kChunk;
+    const int j0 = c * kChunk;
+    if (masked) {
+#pragma unroll 4
+      for (int j = 0; j < kChunk; ++j) interact<true>(buf[j], xi, yi, zi, e2, ax, ay, az, j0 + j, i0, i1, sv);
+    } else {
+#pragma unroll 1
+      for (int j = 0; j < kChunk; j += 8) interact_block<8>(buf + j, xi, yi, zi, e2, ax, ay, az);
+    }
+  }
+
+  // wavefront partials -> LDS -> one coalesced (128 x 3) store per workgroup, waves added in fixed order
+  float* red = reinterpret_cast<float*>(&lds[kWaves * 2 * kChunk]);
+  float* mine = red + wave * 6 * 64;
+  mine[0 * 64 + lane] = ax.x; mine[1 * 64 + lane] = ax.y;
+  mine[2 * 64 + lane] = ay.x; mine[3 * 64 + lane] = ay.y;
+  mine[4 * 64 + lane] = az.x; mine[5 * 64 + lane] = az.y;
+  __syncthreads();
+  float* dst = ws + sc.ws_off + ((size_t)slab * n + t_base) * 3;
+  const int n_valid = min(kTgtPerWG, n - t_base) * 3;
+  for (int o = threadIdx.x; o < n_valid; o += 64 * kWaves) {
+    const int lt = o / 3, comp = o - lt * 3;
+    const int idx = (comp * 2 + (lt >> 6)) * 64 + (lt & 63);
+    float sum = red[idx];
+#pragma unroll
+    for (int w = 1; w < kWaves; ++w) sum += red[w * 6 * 64 + idx];
+    dst[o] = sum;
+  }
+}
+
+// ---- per packed row r: scene s = row_scene[r], body i = r - poff_s. Optional kick v += ck_s a, optional drift
+// x += cd_s v, then posm[r] = {x, m} (zeros behind the scene's last body). mul and add round separately (the torch
+// eager order of kick_drift_kernel): given the same accelerations the update is bit-exact with the one-system step.
+__global__ __launch_bounds__(256) void batch_update_kernel(const int* __restrict__ row_scene,
+                                                           const SceneRec* __restrict__ scenes, int n_rows,
+                                                           float* __restrict__ pos, float* __restrict__ vel,
+                                                           const float* __restrict__ acc, const float* __restrict__ mass,
+                                                           const float* __restrict__ ck_s, const float* __restrict__ cd_s,
+                                                           f4* __restrict__ posm) {
+  const int r = blockIdx.x * 256 + threadIdx.x;
+  if (r >= n_rows) return;
+  const int s = row_scene[r];
+  const SceneRec sc = load_scene(scenes, s);
+  const int i = r - sc.poff;
+  f4 pm = {0.f, 0.f, 0.f, 0.f};
+  if (i < sc.n) {
+    const int b = sc.off + i;
+    const float ck = acc ? ck_s[s] : 0.f, cd = cd_s ? cd_s[s] : 0.f;
+    float x[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      x[k] = pos[3 * b + k];
+      if (vel) {
+        float v = vel[3 * b + k];
+        if (acc) { v = __fadd_rn(v, __fmul_rn(ck, acc[3 * b + k])); vel[3 * b + k] = v; }
+        if (cd_s) { x[k] = __fadd_rn(x[k], __fmul_rn(cd, v)); pos[3 * b + k] = x[k]; }
+      }
+    }
+    pm = f4{x[0], x[1], x[2], mass[b]};
+  }
+  posm[r] = pm;
+}
+
+// ---- fixed-order slab sum: acc = G_s * (slab_0 + slab_1 + ...) in slab order, optional fused kick v += ck_s acc.
+// One thread per (packed row, component): coalesced over the scene's rows of each slab.
+__global__ __launch_bounds__(256) void batch_finish_kernel(const int* __restrict__ row_scene,
+                                                           const SceneRec* __restrict__ scenes, int n_rows,
+                                                           const float* __restrict__ ws, const float* __restrict__ g_s,
+                                                           float* __restrict__ acc, float* __restrict__ vel,
+                                                           const float* __restrict__ ck_s) {
+  const int e = blockIdx.x * 256 + threadIdx.x;
+  if (e >= 3 * n_rows) return;
+  const int r = e / 3, comp = e - 3 * r;
+  const int s = row_scene[r];
+  const SceneRec sc = load_scene(scenes, s);
+  const int i = r - sc.poff;
+  if (i >= sc.n) return;
+  const float* p = ws + sc.ws_off + (size_t)i * 3 + comp;
+  const size_t stride = (size_t)sc.n * 3;
+  float sum = p[0];
+  for (int k = 1; k < sc.slabs; ++k) sum += p[k * stride];
+  const float a = __fmul_rn(g_s[s], sum);
+  const size_t o = (size_t)(sc.off + i) * 3 + comp;
+  acc[o] = a;
+  if (vel) vel[o] = __fadd_rn(vel[o], __fmul_rn(ck_s[s], a));
+}
+
+// ---- segmented potential energy: one workgroup per item, energy_kernel's body on the item's scene (upper triangle,
+// |r| + eps, fp32 lanes, fp64 across lanes); the item's partial goes to pu[u_off + g * slabs + k].
+__global__ __launch_bounds__(64 * kWaves) void batch_energy_kernel(const f4* __restrict__ posm,
+                                                                   const int4* __restrict__ items,
+                                                                   const SceneRec* __restrict__ scenes,
+                                                                   const float* __restrict__ soft_s,
+                                                                   double* __restrict__ pu) {
+  __shared__ f4 lds[kWaves * 2 * kChunk + 8];
+  const int4 it = items[blockIdx.x];
+  const int s = __builtin_amdgcn_readfirstlane(it.x), grp = __builtin_amdgcn_readfirstlane(it.y);
+  const int slab = __builtin_amdgcn_readfirstlane(it.z);
+  const SceneRec sc = load_scene(scenes, s);
+  const int n = __builtin_amdgcn_readfirstlane(sc.n), n_chunks = __builtin_amdgcn_readfirstlane(sc.n_chunks);
+  const int slabs = __builtin_amdgcn_readfirstlane(sc.slabs);
+  const f4* src = posm + __builtin_amdgcn_readfirstlane(sc.poff);
+  const float soft_ = soft_s[s];
+  const bool all_masked = !(soft_ > 0.f);
+
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int t_base = grp * kTgtPerWG;
+  const int i0 = t_base + lane, i1 = t_base + 64 + lane;
+  const f4 t0 = src[min(i0, n - 1)], t1 = src[min(i1, n - 1)];
+  const f2 xi = {t0.x, t1.x}, yi = {t0.y, t1.y}, zi = {t0.z, t1.z};
+  f2 u = {0.f, 0.f};
+  f2 soft = {soft_, soft_};
+  asm volatile("" : "+v"(soft));
+  const int c_lo = t_base / kChunk;
+  const int span = n_chunks - c_lo;
+  const int parts = slabs * kWaves;
+  const int cpw = (span + parts - 1) / parts;
+  const int jw = slab * kWaves + wave;
+  const int c_begin = min(c_lo + jw * cpw, n_chunks), c_end = min(c_begin + cpw, n_chunks);
+  const int c_diag_end = (t_base + kTgtPerWG + kChunk - 1) / kChunk;
+  f4* stage = &lds[wave * 2 * kChunk];
+  const f4* s_lane = src + lane;
+  if (c_begin < c_end)
+    __builtin_amdgcn_global_load_lds(GPTR(s_lane + (size_t)c_begin * kChunk), LPTR(stage), 16, 0, 0);
+  for (int c = c_begin; c < c_end; ++c) {
+    const int b = (c - c_begin) & 1;
+    if (c + 1 < c_end) {
+      __builtin_amdgcn_global_load_lds(GPTR(s_lane + (size_t)(c + 1) * kChunk), LPTR(stage + (b ^ 1) * kChunk), 16, 0, 0);
+      asm volatile("s_waitcnt vmcnt(1)" ::: "memory");
+    } else {
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
+    const f4* buf = stage + b * kChunk;
+    const int j0 = c * kChunk;
+    if (all_masked || c < c_diag_end || c == n_chunks - 1) {
+#pragma unroll 4
+      for (int j = 0; j < kChunk; ++j) energy_pair<true>(buf[j], xi, yi, zi, soft, u, j0 + j, i0, i1, n);
+    } else {
+#pragma unroll 4
+      for (int j = 0; j < kChunk; ++j) energy_pair<false>(buf[j], xi, yi, zi, soft, u, j0 + j, i0, i1, n);
+    }
+  }
+  double acc = 0.0;
+  if (i0 < n) acc += (double)t0.w * (double)u.x;
+  if (i1 < n) acc += (double)t1.w * (double)u.y;
+  for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off);
+  double* red = reinterpret_cast<double*>(&lds[kWaves * 2 * kChunk]);
+  if (lane == 0) red[wave] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) pu[(size_t)sc.u_off + (size_t)grp * slabs + slab] = (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+// one workgroup per scene: U_s = -G_s * (sum of its partials), K_s = sum 0.5 m v^2 (fp32 terms as kinetic_kernel,
+// fp64 sums); thread-strided then a fixed shuffle / LDS tree. out_uk[2 s] = U_s, out_uk[2 s + 1] = K_s.
+__global__ __launch_bounds__(256) void batch_energy_final_kernel(const SceneRec* __restrict__ scenes,
+                                                                 const f4* __restrict__ posm,
+                                                                 const float* __restrict__ vel,
+                                                                 const double* __restrict__ pu,
+                                                                 const float* __restrict__ g_s,
+                                                                 double* __restrict__ out_uk) {
+  __shared__ double ru[4], rk[4];
+  const int s = blockIdx.x;
+  const SceneRec sc = load_scene(scenes, s);
+  double u = 0.0, k = 0.0;
+  const int nu = sc.n > 0 ? sc.groups * sc.slabs : 0;
+  for (int b = threadIdx.x; b < nu; b += 256) u += pu[(size_t)sc.u_off + b];
+  for (int i = threadIdx.x; i < sc.n; i += 256) {
+    const size_t b = (size_t)(sc.off + i) * 3;
+    const float vx = vel[b], vy = vel[b + 1], vz = vel[b + 2];
+    const float v2 = __fadd_rn(__fadd_rn(__fmul_rn(vx, vx), __fmul_rn(vy, vy)), __fmul_rn(vz, vz));
+    k += (double)__fmul_rn(__fmul_rn(0.5f, posm[sc.poff + i].w), v2);       // 0.5 * m * |v|^2 (simulation.py:100)
+  }
+  for (int off = 32; off > 0; off >>= 1) { u += __shfl_down(u, off); k += __shfl_down(k, off); }
+  if ((threadIdx.x & 63) == 0) { ru[threadIdx.x >> 6] = u; rk[threadIdx.x >> 6] = k; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const double us = (ru[0] + ru[1]) + (ru[2] + ru[3]);
+    out_uk[2 * s] = sc.n > 0 ? -(double)g_s[s] * us : 0.0;
+    out_uk[2 * s + 1] = (rk[0] + rk[1]) + (rk[2] + rk[3]);
+  }
+}
+
+inline int bcheck() { const hipError_t e = hipGetLastError(); return e == hipSuccess ? 0 : (int)e; }
+bool bmisaligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; }
+
+// common argument checks of the launching entry points; fills t
+int batch_prologue(const int* offsets, int n_scenes, const void* plan, size_t plan_bytes, BatchTotals* t) {
+  int rc = batch_totals(offsets, n_scenes, t);
+  if (rc) return rc;
+  if (!plan || bmisaligned16(plan) || plan_bytes != plan_bytes_of(*t)) return NBD_E_BADARG;
+  return 0;
+}
+
+int launch_update(const DevPlan& d, const BatchTotals& t, float* pos, float* vel, const float* acc, const float* mass,
+                  const float* ck, const float* cd, float* posm, hipStream_t st) {
+  batch_update_kernel<<<bceil_div(t.n_rows, 256), 256, 0, st>>>(d.row_scene, d.scenes, t.n_rows, pos, vel, acc, mass,
+                                                               ck, cd, reinterpret_cast<f4*>(posm));
+  return bcheck();
+}
+
+int launch_force(const DevPlan& d, const BatchTotals& t, const float* posm, const float* eps2, const float* g,
+                 float* acc_out, float* vel, const float* ck, void* workspace, hipStream_t st) {
+  float* ws = static_cast<float*>(workspace);
+  batch_accel_kernel<<<t.n_items, 64 * kWaves, 0, st>>>(reinterpret_cast<const f4*>(posm), d.items, d.scenes, eps2, ws);
+  int rc = bcheck();
+  if (rc) return rc;
+  batch_finish_kernel<<<bceil_div(3 * t.n_rows, 256), 256, 0, st>>>(d.row_scene, d.scenes, t.n_rows, ws, g, acc_out,
+                                                                   vel, ck);
+  return bcheck();
+}
+
+}  // namespace
+
+extern "C" {
+
+int nbd_batch_plan(const int* offsets, int n_scenes, int* n_items, int* posm_rows, size_t* plan_bytes,
+                   size_t* workspace_bytes) {
+  BatchTotals t;
+  const int rc = batch_totals(offsets, n_scenes, &t);
+  if (rc) return rc;
+  if (n_items) *n_items = t.n_items;
+  if (posm_rows) *posm_rows = t.n_rows;
+  if (plan_bytes) *plan_bytes = plan_bytes_of(t);
+  if (workspace_bytes) *workspace_bytes = ws_bytes_of(t);
+  return 0;
+}
+
+int nbd_batch_plan_fill(const int* offsets, int n_scenes, void* plan, size_t plan_bytes) {
+  BatchTotals t;
+  const int rc = batch_totals(offsets, n_scenes, &t);
+  if (rc) return rc;
+  if (!plan || plan_bytes != plan_bytes_of(t)) return NBD_E_BADARG;
+  std::vector<int> items;             // (scene, group, slab, chunks per wave) before ordering
+  items.reserve((size_t)t.n_items * 4);
+  std::vector<SceneRec> scenes(n_scenes);
+  std::vector<int> rows((size_t)t.n_rows);
+  int poff = 0, ws_off = 0, u_off = 0;
+  for (int s = 0; s < n_scenes; ++s) {
+    SceneRec& r = scenes[s];
+    r.off = offsets[s]; r.n = offsets[s + 1] - offsets[s]; r.poff = poff; r.ws_off = ws_off; r.u_off = u_off;
+    r.slabs = r.n > 0 ? scene_slabs(r.n) : 0;
+    r.n_chunks = bceil_div(r.n, kChunk);
+    r.groups = bceil_div(r.n, kTgtPerWG);
+    const int cpw = r.n > 0 ? bceil_div(r.n_chunks, r.slabs * kWaves) : 0;
+    for (int g = 0; g < r.groups; ++g)
+      for (int k = 0; k < r.slabs; ++k) items.insert(items.end(), {s, g, k, cpw});
+    for (int i = 0; i < r.n_chunks * kChunk; ++i) rows[(size_t)poff + i] = s;
+    poff += r.n_chunks * kChunk; ws_off += r.slabs * r.n * 3; u_off += r.groups * r.slabs;
+  }
+  // dispatch order: longest items first (a stable order of the WORK; no sum depends on it)
+  std::vector<int> order(t.n_items);
+  for (int i = 0; i < t.n_items; ++i) order[i] = i;
+  std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return items[4 * a + 3] > items[4 * b + 3]; });
+  int* out = static_cast<int*>(plan);
+  for (int i = 0; i < t.n_items; ++i) {
+    const int* src = &items[4 * order[i]];
+    out[4 * i] = src[0]; out[4 * i + 1] = src[1]; out[4 * i + 2] = src[2]; out[4 * i + 3] = 0;
+  }
+  memcpy(out + 4 * (size_t)t.n_items, scenes.data(), scenes.size() * sizeof(SceneRec));
+  memcpy(reinterpret_cast<char*>(out + 4 * (size_t)t.n_items) + scenes.size() * sizeof(SceneRec), rows.data(),
+         rows.size() * sizeof(int));
+  return 0;
+}
+
+int nbd_batch_pack_posm_f32(const int* offsets, int n_scenes, const void* plan, size_t plan_bytes, const float* pos,
+                            const float* mass, float* posm, nbd_stream_t stream) {
+  BatchTotals t;
+  int rc = batch_prologue(offsets, n_scenes, plan, plan_bytes, &t);
+  if (rc) return rc;
+  if (t.n_total == 0) return 0;
+  if (!pos || !mass || !posm || bmisaligned16(posm)) return NBD_E_BADARG;
+  return launch_update(dev_plan(plan, t), t, const_cast<float*>(pos), nullptr, nullptr, mass, nullptr, nullptr, posm,
+                       (hipStream_t)stream);
+}
+
+int nbd_batch_accel_f32(const int* offsets, int n_scenes, const void* plan, size_t plan_bytes, const float* pos,
+                        const float* mass, const float* softening_sq, const float* g_const, float* acc_out,
+                        float* posm, void* workspace, size_t workspace_bytes, nbd_stream_t stream) {
+  BatchTotals t;
+  int rc = batch_prologue(offsets, n_scenes, plan, plan_bytes, &t);
+  if (rc) return rc;
+  if (t.n_total == 0) return 0;
+  if (!pos || !mass || !softening_sq || !g_const || !acc_out || !posm || bmisaligned16(posm)) return NBD_E_BADARG;
+  if (!workspace || workspace_bytes < ws_bytes_of(t)) return NBD_E_WORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  const DevPlan d = dev_plan(plan, t);
+  if ((rc = launch_update(d, t, const_cast<float*>(pos), nullptr, nullptr, mass, nullptr, nullptr, posm, st))) return rc;
+  return launch_force(d, t, posm, softening_sq, g_const, acc_out, nullptr, nullptr, workspace, st);
+}
+
+int nbd_batch_leapfrog_step_f32(const int* offsets, int n_scenes, const void* plan, size_t plan_bytes, float* pos,
+                                float* vel, const float* acc_in, float* acc_out, const float* mass, const float* dt_half,
+                                const float* dt, const float* softening_sq, const float* g_const, float* posm,
+                                void* workspace, size_t workspace_bytes, nbd_stream_t stream) {
+  BatchTotals t;
+  int rc = batch_prologue(offsets, n_scenes, plan, plan_bytes, &t);
+  if (rc) return rc;
+  if (t.n_total == 0) return 0;
+  if (!pos || !vel || !acc_in || !acc_out || !mass || !dt_half || !dt || !softening_sq || !g_const || !posm ||
+      bmisaligned16(posm))
+    return NBD_E_BADARG;
+  if (!workspace || workspace_bytes < ws_bytes_of(t)) return NBD_E_WORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  const DevPlan d = dev_plan(plan, t);
+  if ((rc = launch_update(d, t, pos, vel, acc_in, mass, dt_half, dt, posm, st))) return rc;
+  return launch_force(d, t, posm, softening_sq, g_const, acc_out, vel, dt_half, workspace, st);
+}
+
+int nbd_batch_euler_step_f32(const int* offsets, int n_scenes, const void* plan, size_t plan_bytes, float* pos,
+                             float* vel, float* acc_out, const float* mass, const float* dt, const float* softening_sq,
+                             const float* g_const, float* posm, void* workspace, size_t workspace_bytes,
+                             nbd_stream_t stream) {
+  BatchTotals t;
+  int rc = batch_prologue(offsets, n_scenes, plan, plan_bytes, &t);
+  if (rc) return rc;
+  if (t.n_total == 0) return 0;
+  if (!pos || !vel || !acc_out || !mass || !dt || !softening_sq || !g_const || !posm || bmisaligned16(posm))
+    return NBD_E_BADARG;
+  if (!workspace || workspace_bytes < ws_bytes_of(t)) return NBD_E_WORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  const DevPlan d = dev_plan(plan, t);
+  if ((rc = launch_update(d, t, pos, nullptr, nullptr, mass, nullptr, nullptr, posm, st))) return rc;
+  if ((rc = launch_force(d, t, posm, softening_sq, g_const, acc_out, vel, dt, workspace, st))) return rc;
+  // drift x += dt v, and posm = the moved bodies (what the energies of the new state read)
+  return launch_update(d, t, pos, vel, nullptr, mass, nullptr, dt, posm, st);
+}
+
+int nbd_batch_energies(const int* offsets, int n_scenes, const void* plan, size_t plan_bytes, const float* posm,
+                       const float* vel, const float* softening, const float* g_const, double* out_uk, void* workspace,
+                       size_t workspace_bytes, nbd_stream_t stream) {
+  BatchTotals t;
+  int rc = batch_prologue(offsets, n_scenes, plan, plan_bytes, &t);
+  if (rc) return rc;
+  if (!out_uk || !g_const || !softening) return NBD_E_BADARG;
+  if (t.n_total > 0 && (!posm || !vel || bmisaligned16(posm))) return NBD_E_BADARG;
+  if (!workspace || workspace_bytes < ws_bytes_of(t)) return NBD_E_WORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  const DevPlan d = dev_plan(plan, t);
+  double* pu = reinterpret_cast<double*>(static_cast<char*>(workspace) + ws_u_offset(t));
+  if (t.n_items > 0) {
+    batch_energy_kernel<<<t.n_items, 64 * kWaves, 0, st>>>(reinterpret_cast<const f4*>(posm), d.items, d.scenes,
+                                                          softening, pu);
+    if ((rc = bcheck())) return rc;
+  }
+  batch_energy_final_kernel<<<n_scenes, 256, 0, st>>>(d.scenes, reinterpret_cast<const f4*>(posm), vel, pu, g_const,
+                                                      out_uk);
+  return bcheck();
+}
+
+}  // extern "C"

@@ -25,109 +25,9 @@
 #include <stdint.h>
 
 #include "../../include/nbd.h"
-
-typedef float f2 __attribute__((ext_vector_type(2)));
-typedef float f4 __attribute__((ext_vector_type(4)));
-
-#define GPTR(p) ((const __attribute__((address_space(1))) void*)(p))
-#define LPTR(p) ((__attribute__((address_space(3))) void*)(p))
+#include "direct_kernels.h"
 
 namespace {
-
-constexpr int kWaves = 4;                  // waves per workgroup (J-split inside the workgroup)
-constexpr int kTgtPerLane = 2;             // packed pair of targets per lane
-constexpr int kTgtPerWG = 64 * kTgtPerLane;  // 128 targets per workgroup
-constexpr int kChunk = NBD_SRC_PAD;        // 64 sources = one 1-KiB LDS-DMA piece
-constexpr int kMaxSlabs = 64;
-// below this softening^2 the cube of rsq overflows fp32 for coincident bodies (and the i==j
-// term), so the index-masked kernel is used (fill_diagonal_ semantics, simulation.py:85)
-constexpr float kEps2Masked = 1e-24f;
-
-inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
-
-// Which sources a launch walks: the 64-source chunks of `src` minus a run of skipped physical chunks,
-// with an element-wise exclusion in the (at most two) chunks that hold a partial piece of the excluded
-// index range. The un-sharded force uses the trivial view; the range-sharded step (nbd_shard_*) walks
-// "all bodies except my own [lo, hi)" with it while its own block runs from a separate launch.
-struct SrcView {
-  int n_src;           // real entries; the padding behind them is zero-mass
-  int n_chunks;        // logical chunks walked (physical chunks minus the skipped run)
-  int cpw_q, cpw_r;    // balanced split: every wave walks cpw_q chunks, the first cpw_r waves one more
-  int skip_c0, skip_cn;  // physical chunks [skip_c0, skip_c0 + skip_cn) are not visited
-  int ex_lo, ex_hi;    // source indices [ex_lo, ex_hi) contribute nothing (checked only where needed)
-  int edge0, edge1;    // physical chunks that straddle ex_lo / ex_hi (-1: none): these take the masked path
-  int tail;            // uniform-mass kernels only: the physical chunk that holds padding behind n_src (-1: none); it takes
-                       // the masked path too (without the per-source mass factor a padding entry is not a zero any more)
-};
-
-// One source against the lane's two targets. 12 packed ops + 2 v_rsq_f32 (UNI: 11, see accel_kernel).
-template <bool MASKED, bool UNI = false>
-__device__ __forceinline__ void interact(const f4 p, const f2 xi, const f2 yi, const f2 zi,
-                                         const f2 e2, f2& ax, f2& ay, f2& az, int j, int i0,
-                                         int i1, const SrcView& sv) {
-  const f2 dx = f2{p.x, p.x} - xi, dy = f2{p.y, p.y} - yi, dz = f2{p.z, p.z} - zi;  // r_j - r_i
-  f2 r2 = __builtin_elementwise_fma(dx, dx, e2);
-  r2 = __builtin_elementwise_fma(dy, dy, r2);
-  r2 = __builtin_elementwise_fma(dz, dz, r2);
-  f2 s = {__builtin_amdgcn_rsqf(r2.x), __builtin_amdgcn_rsqf(r2.y)};
-  if (MASKED) {  // exact fill_diagonal_(0): only j == i is dropped; padding and the excluded range too
-    const bool live = j < sv.n_src && (unsigned)(j - sv.ex_lo) >= (unsigned)(sv.ex_hi - sv.ex_lo);
-    s.x = (live && j != i0) ? s.x : 0.0f;
-    s.y = (live && j != i1) ? s.y : 0.0f;
-  }
-  // w = m_j * s^3 with m_j broadcast from the HIGH half of the {z,m} register pair; hipcc does not
-  // fold that splat into op_sel by itself (it inserts a v_mov), hence the one asm line. The asm
-  // multiply takes s^3 (an ordinary VALU result), never s itself: gfx950 needs a wait state between
-  // a transcendental result and its VALU consumer, and hipcc pads that only for instructions it
-  // can see (an asm consumer right behind v_rsq_f32/v_rcp_f32 reads a stale register).
-  const f2 zm = {p.z, p.w};
-  const f2 s3 = (s * s) * s;
-  f2 w;  // m_j (r^2 + eps^2)^(-3/2)
-  if (UNI) w = s3;               // equal masses: the common factor is applied once, to the finished sum
-  else asm("v_pk_mul_f32 %0, %1, %2 op_sel:[1,0] op_sel_hi:[1,1]" : "=v"(w) : "v"(zm), "v"(s3));
-  ax = __builtin_elementwise_fma(w, dx, ax);
-  ay = __builtin_elementwise_fma(w, dy, ay);
-  az = __builtin_elementwise_fma(w, dz, az);
-}
-
-// KU sources at once for the un-masked path: same arithmetic as interact(), with the 2*KU v_rsq_f32
-// issued back to back (__builtin_amdgcn_sched_group_barrier on the TRANS class). Switching between the
-// quarter-rate transcendental unit and the packed-math stream costs issue cycles on gfx950 (3 fma : 1
-// rsq mixes run ~10 % under the sum of their parts, tools/ubench_valu.hip), so the switches are
-// batched; the rsq stays a compiler builtin so that hipcc fills the transcendental -> VALU wait state
-// with independent work instead of the s_nop it must put behind an opaque asm block. Measured
-// (tools/k1_variants.hip, N = 65 536): KU = 8 at 90 VGPRs / 5 waves per SIMD beats KU = 4 at 58 VGPRs /
-// 8 waves (1.004 vs 1.010 ms) and an inline-asm rsq block (1.021 ms).
-template <int KU, bool UNI = false>
-__device__ __forceinline__ void interact_block(const f4* __restrict__ buf, const f2 xi, const f2 yi, const f2 zi,
-                                               const f2 e2, f2& ax, f2& ay, f2& az) {
-  f4 p[KU];
-  f2 dx[KU], dy[KU], dz[KU], s[KU];
-#pragma unroll
-  for (int u = 0; u < KU; ++u) {
-    p[u] = buf[u];
-    if (UNI) asm("" : "+v"(p[u]));      // keep the source a whole 4-register tuple: with the mass unused hipcc loads 96 bits
-                                        // and then copies z out of its odd register to splat it (a v_mov per source)
-    dx[u] = f2{p[u].x, p[u].x} - xi; dy[u] = f2{p[u].y, p[u].y} - yi; dz[u] = f2{p[u].z, p[u].z} - zi;
-    f2 r2 = __builtin_elementwise_fma(dx[u], dx[u], e2);
-    r2 = __builtin_elementwise_fma(dy[u], dy[u], r2);
-    s[u] = __builtin_elementwise_fma(dz[u], dz[u], r2);
-  }
-#pragma unroll
-  for (int u = 0; u < KU; ++u) s[u] = f2{__builtin_amdgcn_rsqf(s[u].x), __builtin_amdgcn_rsqf(s[u].y)};
-  __builtin_amdgcn_sched_group_barrier(0x400, 2 * KU, 0);      // 0x400 = TRANS: keep the rsq's together
-#pragma unroll
-  for (int u = 0; u < KU; ++u) {
-    const f2 zm = {p[u].z, p[u].w};
-    const f2 s3 = (s[u] * s[u]) * s[u];          // compiler-visible consumers of the rsq results (hazard-padded)
-    f2 w;
-    if (UNI) w = s3;
-    else asm("v_pk_mul_f32 %0, %1, %2 op_sel:[1,0] op_sel_hi:[1,1]" : "=v"(w) : "v"(zm), "v"(s3));
-    ax = __builtin_elementwise_fma(w, dx[u], ax);
-    ay = __builtin_elementwise_fma(w, dy[u], ay);
-    az = __builtin_elementwise_fma(w, dz[u], az);
-  }
-}
 
 // grid = (target groups of 128, slabs); block = 256.
 // Wave jw = blockIdx.y*4 + w handles the logical source chunks [jw*q + min(jw, r), ... + q (+1 if jw < r)):
@@ -452,30 +352,6 @@ __global__ __launch_bounds__(256) void axpy_kernel(float* __restrict__ y, const 
                                                    float c, int n) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i < n) y[i] = __fadd_rn(y[i], __fmul_rn(c, x[i]));
-}
-
-// ---- energies (simulation.py:91-115). U = sum_{i<j} -G m_i m_j / (|r_ij| + eps), K = sum 0.5 m v^2.
-// Same streaming structure as K1 (two targets per lane in packed registers, wave-private LDS-DMA
-// chunks, J-split over waves and slabs) restricted to the upper triangle: a target group only
-// walks the source chunks at or above its own first index; the (at most three) chunks that
-// straddle the diagonal take the masked path (j > i), the rest run mask-free. Per pair
-// 8 packed ops + 1 v_mov + 2 v_sqrt_f32 + 2 v_rcp_f32. fp32 per-lane partial sums, fp64 across lanes/blocks.
-template <bool MASKED>
-__device__ __forceinline__ void energy_pair(const f4 p, const f2 xi, const f2 yi, const f2 zi, const f2 soft,
-                                            f2& u, int j, int i0, int i1, int n) {
-  const f2 dx = f2{p.x, p.x} - xi, dy = f2{p.y, p.y} - yi, dz = f2{p.z, p.z} - zi;
-  f2 d2 = dx * dx;
-  d2 = __builtin_elementwise_fma(dy, dy, d2);
-  d2 = __builtin_elementwise_fma(dz, dz, d2);
-  const f2 den = f2{__builtin_amdgcn_sqrtf(d2.x), __builtin_amdgcn_sqrtf(d2.y)} + soft;   // |r| + eps (:105)
-  const f2 inv = {__builtin_amdgcn_rcpf(den.x), __builtin_amdgcn_rcpf(den.y)};
-  f2 t = f2{p.w, p.w} * inv;                  // m_j / den (plain C: the consumer of v_rcp_f32 must be
-                                              // visible to hipcc's hazard padding -- see interact())
-  if (MASKED) {                               // triu(1): strictly above the diagonal (:113)
-    t.x = (j > i0 && j < n) ? t.x : 0.f;
-    t.y = (j > i1 && j < n) ? t.y : 0.f;
-  }
-  u += t;
 }
 
 __global__ __launch_bounds__(64 * kWaves) void energy_kernel(const f4* __restrict__ posm, int n, int n_chunks,

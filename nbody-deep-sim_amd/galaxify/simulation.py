@@ -11,6 +11,9 @@ Addition over the reference (which has no distributed code): `process_group=` ra
 the bodies over the ranks of a torch.distributed group (one process per GPU, RCCL over xGMI);
 positions/velocities/accelerations then hold the local shard [lo, hi) and `gather()` assembles
 the global arrays. See nbd/dist.py and DESIGN.md.
+
+Second addition: `BatchedSimulator` advances many independent systems with one set of launches per step
+(csrc/direct_batch.hip).
 """
 from __future__ import annotations
 
@@ -462,3 +465,240 @@ class EulerSimulator(BaseSimulator):
         self.accelerations = self._force_sharded(self.velocities, dt)        # a(t), v += dt a fused
         if self.part.n_local:
             direct.drift(self.positions, self.velocities, dt)
+
+
+def _per_scene(x, n_scenes: int, name: str) -> list:
+    """A scalar, or one value per scene -> list of S Python floats."""
+    if isinstance(x, torch.Tensor):
+        x = x.detach().cpu().tolist()
+    if np.ndim(x) == 0:
+        return [float(x)] * n_scenes
+    vals = [float(v) for v in np.asarray(x, dtype=np.float64).reshape(-1)]
+    if len(vals) != n_scenes:
+        raise ValueError(f"{name}: expected a scalar or {n_scenes} values, got {len(vals)}")
+    return vals
+
+
+class BatchedSimulator:
+    """S independent systems ("scenes") advanced together: one set of launches per step for all of them
+    (csrc/direct_batch.hip). Each body feels only the bodies of its own scene, with that scene's g_const, softening
+    and dt (scalars, or one value per scene). The scenes are stored back to back: `positions`, `velocities`,
+    `accelerations` are (N_total, 3) and `masses` (N_total,), scene s owning rows offsets[s]:offsets[s + 1];
+    `scene(s)` returns views of them. A scene's results do not depend on its companions or its position in the batch
+    (bit for bit). There is no CPU path and no multi-GPU sharding: the batch runs on one device."""
+
+    GRAPH_RUN_CHUNK = 32
+    RING_BYTES = 64 << 20                                # the eager run()'s staging cap, per chunk of states
+
+    def __init__(self, *, systems, integrator: str = "leapfrog", g_const=1.0, softening=0.1, dt=0.01,
+                 calc_energy: bool = True, device: str = None):
+        if integrator not in ("leapfrog", "euler"):
+            raise ValueError("integrator must be 'leapfrog' or 'euler'")
+        self.device = _resolve_device(device)
+        _lib.lib()
+        systems = list(systems)
+        if not systems:
+            raise ValueError("systems: need at least one (positions, velocities, masses) scene")
+        self.integrator = integrator
+        self.calc_energy = calc_energy
+        self.n_scenes = len(systems)
+        pos, vel, mass = [], [], []
+        for i, sysm in enumerate(systems):
+            p, v, m = (_to_f32(x, self.device) for x in sysm)
+            n = p.shape[0]
+            if p.shape != (n, 3) or v.shape != (n, 3) or m.shape != (n,):
+                raise ValueError(f"scene {i}: positions/velocities must be (n,3) and masses (n,)")
+            pos.append(p); vel.append(v); mass.append(m)
+        self.sizes = [p.shape[0] for p in pos]
+        self.positions = torch.cat(pos).contiguous()
+        self.velocities = torch.cat(vel).contiguous()
+        self.masses = torch.cat(mass).contiguous()
+        self.n = self.positions.shape[0]
+        self._plan = direct.BatchPlan(self.sizes, self.device)
+        self.offsets = torch.tensor(self._plan.offsets, dtype=torch.int64)
+        self.g_const, self.softening, self.dt = g_const, softening, dt
+        self._posm = self._plan.alloc_posm()
+        self._ws = self._plan.workspace()
+        self._params = torch.zeros((5, self.n_scenes), dtype=torch.float32, device=self.device)
+        self._params_key = None
+        self.accelerations = self.compute_accelerations()
+
+    # ------------------------------------------------------------------ per-scene parameters
+    def _sync_params(self):
+        """Rows g, eps^2, eps, dt / 2, dt of the device parameter table, as torch forms the fp32 scalars from the
+        Python doubles (simulation.py:82,88,164); rewritten IN PLACE when an attribute changed (captured graphs keep
+        reading the same buffer). Returns the per-scene values (the graph cache key)."""
+        S = self.n_scenes
+        g = _per_scene(self.g_const, S, "g_const")
+        eps = _per_scene(self.softening, S, "softening")
+        dt = _per_scene(self.dt, S, "dt")
+        key = (tuple(g), tuple(eps), tuple(dt))
+        if key != self._params_key:
+            rows = [[direct.f32(x) for x in g], [direct.f32(e ** 2) for e in eps], [direct.f32(e) for e in eps],
+                    [direct.f32(0.5 * d) for d in dt], [direct.f32(d) for d in dt]]
+            self._params.copy_(torch.tensor(rows, dtype=torch.float32))
+            self._params_key = key
+        return key
+
+    def scene(self, i: int):
+        """(positions, velocities, accelerations) views of scene i."""
+        if not -self.n_scenes <= i < self.n_scenes:
+            raise IndexError(f"scene {i} of {self.n_scenes}")
+        i %= self.n_scenes
+        lo, hi = int(self.offsets[i]), int(self.offsets[i + 1])
+        return self.positions[lo:hi], self.velocities[lo:hi], self.accelerations[lo:hi]
+
+    # ------------------------------------------------------------------ force, energies, step
+    def compute_accelerations(self) -> torch.Tensor:
+        """Force of every scene on its own bodies -> new (N_total, 3) tensor (simulation.py:71-89 per scene)."""
+        self._sync_params()
+        acc = torch.zeros((self.n, 3), dtype=torch.float32, device=self.device)
+        P = self._params
+        direct.batch_accel(self._plan, self.positions, self.masses, P[1], P[0], acc, self._posm, self._ws)
+        return acc
+
+    def _energies_into(self, out_uk):
+        P = self._params
+        direct.batch_energies(self._plan, self._posm, self.velocities, P[2], P[0], out_uk, self._ws)
+
+    def compute_energies(self):
+        """(u, k): two lists of S Python floats (simulation.py:91-115 per scene)."""
+        self._sync_params()
+        direct.batch_pack_posm(self._plan, self.positions, self.masses, self._posm)
+        uk = torch.empty((self.n_scenes, 2), dtype=torch.float64, device=self.device)
+        self._energies_into(uk)
+        uk = uk.cpu()
+        return uk[:, 0].tolist(), uk[:, 1].tolist()
+
+    def _step_into(self, acc_in, acc_out):
+        P = self._params
+        if self.integrator == "leapfrog":
+            direct.batch_leapfrog_step(self._plan, self.positions, self.velocities, acc_in, acc_out, self.masses,
+                                       P[3], P[4], P[1], P[0], self._posm, self._ws)
+        else:
+            direct.batch_euler_step(self._plan, self.positions, self.velocities, acc_out, self.masses, P[4], P[1],
+                                    P[0], self._posm, self._ws)
+
+    def step(self):
+        """One step of every scene; positions and velocities in place, `accelerations` rebound to a new tensor."""
+        if self.n == 0:
+            return
+        self._sync_params()
+        new_acc = torch.empty_like(self.accelerations)
+        self._step_into(self.accelerations, new_acc)
+        self.accelerations = new_acc
+
+    # ------------------------------------------------------------------ run()
+    def _chunk_buffers(self, m: int):
+        """One device buffer = ring (m, 3, N, 3) fp32 | energies (m, S, 2) fp64: ONE device->host copy per chunk."""
+        ring_b = (m * 9 * self.n * 4 + 15) // 16 * 16
+        buf = torch.empty(ring_b + m * self.n_scenes * 16, dtype=torch.uint8, device=self.device)
+        ring = buf[:m * 9 * self.n * 4].view(torch.float32).view(m, 3, self.n, 3)
+        uk = buf[ring_b:].view(torch.float64).view(m, self.n_scenes, 2)
+        return buf, ring, uk, ring_b
+
+    def _states(self, host, m, ring_b, first, t_steps, out):
+        """Append m states per scene to `out` from a host copy of a chunk buffer (views into it, no copies)."""
+        ring = host[:m * 9 * self.n * 4].view(torch.float32).view(m, 3, self.n, 3)
+        uk = host[ring_b:].view(torch.float64).view(m, self.n_scenes, 2).tolist() if self.calc_energy else None
+        off = self.offsets.tolist()
+        for s_ in range(m):
+            for i in range(self.n_scenes):
+                lo, hi = off[i], off[i + 1]
+                u, k = (uk[s_][i][0], uk[s_][i][1]) if self.calc_energy else (None, None)
+                out[i].append(SimulationState(step=first + s_, step_time=t_steps[s_], positions=ring[s_, 0, lo:hi],
+                                              velocities=ring[s_, 1, lo:hi], accelerations=ring[s_, 2, lo:hi],
+                                              u_energy=u, k_energy=k))
+
+    def _chunk_len(self) -> int:
+        return max(1, min(self.GRAPH_RUN_CHUNK, self.RING_BYTES // max(36 * self.n, 1)))
+
+    def run(self, steps: int) -> list[list[SimulationState]]:
+        """Run `steps` steps of every scene: S lists of reference-shaped SimulationState (simulation.py:117-146).
+        step_time is the GPU time of the batched step divided by S. Chunks of >= 8 steps replay a captured hipGraph
+        (the steps, the energies and one snapshot launch per step; one device->host copy per chunk); the last < 8 steps
+        run eagerly -- the same launches in the same order, so the states are bit-identical either way."""
+        out = [[] for _ in range(self.n_scenes)]
+        if steps <= 0:
+            return out
+        if self.n == 0:
+            uk = (0.0, 0.0) if self.calc_energy else (None, None)
+            empty = torch.zeros((0, 3), dtype=torch.float32)
+            for i in range(self.n_scenes):
+                out[i] = [SimulationState(step=s, step_time=0.0, positions=empty, velocities=empty, accelerations=empty,
+                                          u_energy=uk[0], k_energy=uk[1]) for s in range(steps)]
+            return out
+        self._sync_params()
+        done = 0
+        big = self._chunk_len()
+        if big >= 8 and os.environ.get("NBD_RUN_GRAPH", "1") != "0":
+            self._acc_g = getattr(self, "_acc_g", None)
+            if self._acc_g is None:
+                self._acc_g = torch.empty((self.n, 3), dtype=torch.float32, device=self.device)
+            first = True
+            while steps - done >= 8:
+                m = big if steps - done >= big else 8
+                graph, buf, ring_b = self._chunk_graph(m)
+                if first:                                    # a caller's handle on the old accelerations stays valid
+                    self._acc_g.copy_(self.accelerations)
+                    first = False
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                graph.replay()
+                e1.record()
+                host = buf.cpu()                             # one device->host copy per chunk (synchronises)
+                self._states(host, m, ring_b, done, [e0.elapsed_time(e1) * 1e-3 / m / self.n_scenes] * m, out)
+                done += m
+            if not first:
+                self.accelerations = self._acc_g.clone()
+        while done < steps:                                  # eager: the tail, or everything
+            m = min(self._chunk_len(), steps - done)
+            buf, ring, uk, ring_b = self._chunk_buffers(m)
+            events = []
+            for s_ in range(m):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                self.step()
+                e1.record()
+                events.append((e0, e1))
+                if self.calc_energy:
+                    self._energies_into(uk[s_])
+                direct.snapshot(self.positions, self.velocities, self.accelerations, ring[s_])
+            host = buf.cpu()
+            self._states(host, m, ring_b, done, [a.elapsed_time(b) * 1e-3 / self.n_scenes for a, b in events], out)
+            done += m
+        return out
+
+    def _chunk_graph(self, m: int):
+        """(graph, buffer, ring offset) for a chunk of m steps; captured once per key and kept."""
+        cache = self.__dict__.setdefault("_run_graphs", {})
+        # a graph bakes in buffer addresses and scalar arguments: anything the caller may have changed is in the key
+        key = (m, self.positions.data_ptr(), self.velocities.data_ptr(), self.masses.data_ptr(), self._acc_g.data_ptr(),
+               self._params_key, bool(self.calc_energy), self.integrator)
+        if key in cache:
+            return cache[key]
+        if len(cache) > 8:
+            cache.clear()
+        buf, ring, uk, ring_b = self._chunk_buffers(m)
+
+        def body(count=m):
+            for s_ in range(count):
+                self._step_into(self._acc_g, self._acc_g)
+                if self.calc_energy:
+                    self._energies_into(uk[s_])
+                direct.snapshot(self.positions, self.velocities, self._acc_g, ring[s_])
+        dev = self.device
+        # capture on a side stream; the state is saved and restored around the (executed) warm-up pass
+        keep = (self.positions.clone(), self.velocities.clone(), self._acc_g.clone())
+        side = torch.cuda.Stream(device=dev)
+        side.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(side):
+            body(1)
+        torch.cuda.current_stream(dev).wait_stream(side)
+        self.positions.copy_(keep[0]); self.velocities.copy_(keep[1]); self._acc_g.copy_(keep[2])
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph):
+            body()
+        self.positions.copy_(keep[0]); self.velocities.copy_(keep[1]); self._acc_g.copy_(keep[2])
+        cache[key] = (graph, buf, ring_b)
+        return cache[key]

@@ -174,6 +174,19 @@ SIGNATURES = {
     "nbd_energy_workspace_bytes": (c_size_t, [c_int]),
     "nbd_energy_f32": (c_int, [c_void_p, c_void_p, c_int, c_float, c_float, c_void_p, c_void_p,
                                c_size_t, c_void_p]),
+    # --- batched direct integrator (csrc/direct_batch.hip)
+    "nbd_batch_plan": (c_int, [c_void_p, c_int, POINTER(c_int), POINTER(c_int), POINTER(c_size_t), POINTER(c_size_t)]),
+    "nbd_batch_plan_fill": (c_int, [c_void_p, c_int, c_void_p, c_size_t]),
+    "nbd_batch_pack_posm_f32": (c_int, [c_void_p, c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "nbd_batch_accel_f32": (c_int, [c_void_p, c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p,
+                                    c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "nbd_batch_leapfrog_step_f32": (c_int, [c_void_p, c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p,
+                                            c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
+                                            c_void_p]),
+    "nbd_batch_euler_step_f32": (c_int, [c_void_p, c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p,
+                                         c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "nbd_batch_energies": (c_int, [c_void_p, c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                   c_void_p, c_size_t, c_void_p]),
     # --- generators on the device (csrc/generators.hip)
     "nbd_disk_workspace_bytes": (c_size_t, [c_int]),
     "nbd_disk_from_draws_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_double, c_double, c_double, c_double,

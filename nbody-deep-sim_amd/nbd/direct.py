@@ -265,3 +265,102 @@ def energy(posm, vel, n: int, softening: float, g_const: float, out_uk=None, wor
                                              out_uk.data_ptr(), workspace.data_ptr(), _nbytes(workspace),
                                              _lib.current_stream(dev)), "nbd_energy_f32")
     return out_uk
+
+
+# ---------------------------------------------------------------- batched direct integrator (csrc/direct_batch.hip)
+class BatchPlan:
+    """The host offsets of an ensemble of scenes and the device work list built from them (nbd_batch_plan /
+    nbd_batch_plan_fill): built once per set of scene sizes, passed to every batch_* call."""
+
+    def __init__(self, sizes, device):
+        sizes = [int(n) for n in sizes]
+        if not sizes or min(sizes) < 0:
+            raise _lib.NbdError("batch: need at least one scene and no negative size")
+        self.offsets = np.zeros(len(sizes) + 1, dtype=np.int32)
+        np.cumsum(sizes, out=self.offsets[1:])
+        self.n_scenes, self.n_total = len(sizes), int(self.offsets[-1])
+        items, rows = ctypes.c_int(), ctypes.c_int()
+        pb, wb = ctypes.c_size_t(), ctypes.c_size_t()
+        L = _lib.lib()
+        _lib.check(L.nbd_batch_plan(self._off(), self.n_scenes, items, rows, pb, wb), "nbd_batch_plan")
+        self.n_items, self.posm_rows, self.plan_bytes, self.workspace_bytes = items.value, rows.value, pb.value, wb.value
+        host = np.zeros((self.plan_bytes + 15) // 16 * 4, dtype=np.int32)
+        _lib.check(L.nbd_batch_plan_fill(self._off(), self.n_scenes, host.ctypes.data, self.plan_bytes),
+                   "nbd_batch_plan_fill")
+        self.plan = torch.from_numpy(host).to(device)
+        self.device = self.plan.device
+
+    def _off(self) -> int:
+        return self.offsets.ctypes.data
+
+    def head(self):
+        """The leading arguments of every batch entry point."""
+        return (self._off(), self.n_scenes, self.plan.data_ptr(), self.plan_bytes)
+
+    def workspace(self) -> torch.Tensor:
+        return alloc_bytes(self.workspace_bytes, self.device)
+
+    def alloc_posm(self) -> torch.Tensor:
+        return torch.zeros((max(self.posm_rows, 1), 4), dtype=torch.float32, device=self.device)
+
+    def check_state(self, posm, ws, *arrays):
+        n = self.n_total
+        for t, nm in arrays:
+            _chk(t, (n, 3) if nm != "mass" else (n,), nm)
+        _chk(posm, None, "posm")
+        if posm.dim() != 2 or posm.shape[1] != 4 or posm.shape[0] < self.posm_rows:
+            raise _lib.NbdError(f"posm: need >= {self.posm_rows} rows of 4, got {tuple(posm.shape)}")
+        if ws is not None and _nbytes(ws) < self.workspace_bytes:
+            raise _lib.NbdError("batch workspace too small")
+
+
+def _param(p: torch.Tensor, plan: BatchPlan, name: str) -> int:
+    _chk(p, (plan.n_scenes,), name)
+    return p.data_ptr()
+
+
+def batch_pack_posm(plan: BatchPlan, pos, mass, posm) -> None:
+    plan.check_state(posm, None, (pos, "pos"), (mass, "mass"))
+    with _lib.on_device(pos.device):
+        _lib.check(_lib.lib().nbd_batch_pack_posm_f32(*plan.head(), pos.data_ptr(), mass.data_ptr(), posm.data_ptr(),
+                                                      _lib.current_stream(pos.device)), "nbd_batch_pack_posm_f32")
+
+
+def batch_accel(plan: BatchPlan, pos, mass, eps2, g, acc_out, posm, ws) -> None:
+    """acc_out = the force of every scene on its own bodies (packs posm first). eps2, g: device fp32 (S,)."""
+    plan.check_state(posm, ws, (pos, "pos"), (mass, "mass"), (acc_out, "acc_out"))
+    with _lib.on_device(pos.device):
+        _lib.check(_lib.lib().nbd_batch_accel_f32(
+            *plan.head(), pos.data_ptr(), mass.data_ptr(), _param(eps2, plan, "softening_sq"), _param(g, plan, "g_const"),
+            acc_out.data_ptr(), posm.data_ptr(), ws.data_ptr(), _nbytes(ws), _lib.current_stream(pos.device)),
+            "nbd_batch_accel_f32")
+
+
+def batch_leapfrog_step(plan: BatchPlan, pos, vel, acc_in, acc_out, mass, dt_half, dt, eps2, g, posm, ws) -> None:
+    plan.check_state(posm, ws, (pos, "pos"), (vel, "vel"), (acc_in, "acc_in"), (acc_out, "acc_out"), (mass, "mass"))
+    with _lib.on_device(pos.device):
+        _lib.check(_lib.lib().nbd_batch_leapfrog_step_f32(
+            *plan.head(), pos.data_ptr(), vel.data_ptr(), acc_in.data_ptr(), acc_out.data_ptr(), mass.data_ptr(),
+            _param(dt_half, plan, "dt_half"), _param(dt, plan, "dt"), _param(eps2, plan, "softening_sq"),
+            _param(g, plan, "g_const"), posm.data_ptr(), ws.data_ptr(), _nbytes(ws), _lib.current_stream(pos.device)),
+            "nbd_batch_leapfrog_step_f32")
+
+
+def batch_euler_step(plan: BatchPlan, pos, vel, acc_out, mass, dt, eps2, g, posm, ws) -> None:
+    plan.check_state(posm, ws, (pos, "pos"), (vel, "vel"), (acc_out, "acc_out"), (mass, "mass"))
+    with _lib.on_device(pos.device):
+        _lib.check(_lib.lib().nbd_batch_euler_step_f32(
+            *plan.head(), pos.data_ptr(), vel.data_ptr(), acc_out.data_ptr(), mass.data_ptr(), _param(dt, plan, "dt"),
+            _param(eps2, plan, "softening_sq"), _param(g, plan, "g_const"), posm.data_ptr(), ws.data_ptr(), _nbytes(ws),
+            _lib.current_stream(pos.device)), "nbd_batch_euler_step_f32")
+
+
+def batch_energies(plan: BatchPlan, posm, vel, soft, g, out_uk, ws) -> torch.Tensor:
+    """out_uk (S, 2) float64 = {U_s, K_s} from posm (as the batch entries leave it) and vel; asynchronous."""
+    plan.check_state(posm, ws, (vel, "vel"))
+    _chk(out_uk, (plan.n_scenes, 2), "out_uk", torch.float64)
+    with _lib.on_device(vel.device):
+        _lib.check(_lib.lib().nbd_batch_energies(
+            *plan.head(), posm.data_ptr(), vel.data_ptr(), _param(soft, plan, "softening"), _param(g, plan, "g_const"),
+            out_uk.data_ptr(), ws.data_ptr(), _nbytes(ws), _lib.current_stream(vel.device)), "nbd_batch_energies")
+    return out_uk
