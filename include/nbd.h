@@ -233,6 +233,30 @@ int nbd_batch_energies(const int* offsets, int n_scenes, const void* plan, size_
                        const float* vel, const float* softening, const float* g_const, double* out_uk, void* workspace,
                        size_t workspace_bytes, nbd_stream_t stream);
 
+/* ------------------------------------------------------------ 4th-order Hermite integrator (csrc/direct_hermite.hip)
+ * An extension (the reference has Euler and leapfrog only): the shared-timestep predictor-corrector of Makino & Aarseth
+ * (1992), one acceleration + jerk evaluation per step, fp32 state. With r_ij = x_j - x_i, v_ij = v_j - v_i and
+ * s = (|r_ij|^2 + softening_sq)^(-1/2):  a_i = G sum_{j!=i} m_j r_ij s^3,
+ * j_i = G sum_{j!=i} m_j (v_ij s^3 - 3 (r_ij.v_ij) s^5 r_ij). Below softening_sq = 1e-24 the i == j term is dropped by
+ * index, as in nbd_accel_f32. The fp32 step constants (dt, dt/2, dt^2/2, dt^3/6, dt^2/12) are formed from the double dt
+ * and rounded once. Deterministic (fixed-order slab sums, no atomics) and capturable (no memsets, no host syncs).
+ * Workspace: nbd_hermite_workspace_bytes(n), 16-byte aligned. */
+size_t nbd_hermite_workspace_bytes(int n);
+/* posm = {x_p, m}, velp = {v_p, 0}: float4[nbd_posm_padded_len(n)] each, zero padding. With acc and jerk the predicted
+ * state x_p = x + v dt + a dt^2/2 + j dt^3/6, v_p = v + a dt + j dt^2/2; with both null a plain pack of (x, v). */
+int nbd_hermite_pack_f32(const float* pos, const float* vel, const float* acc, const float* jerk, const float* mass,
+                         int n, double dt, float* posm, float* velp, nbd_stream_t stream);
+/* The force alone (tests, profiling): acc_out and jerk_out (n,3) of all n bodies of posm / velp. variant: the register
+ * shape of the kernel (0: the step's, two sources in flight; 1: four), same sums. */
+int nbd_accel_jerk_f32(const float* posm, const float* velp, int n, float softening_sq, float g_const, float* acc_out,
+                       float* jerk_out, void* workspace, size_t workspace_bytes, int variant, nbd_stream_t stream);
+/* One step: predict + pack, acceleration + jerk at the predicted state, slab sum + corrector (three launches). Writes
+ * pos, vel (in place), acc_out, jerk_out (= a1, j1 at the predicted state, carried into the next step) and
+ * posm = {x1, m}. acc_in may alias acc_out and jerk_in may alias jerk_out. posm: float4[nbd_posm_padded_len(n)]. */
+int nbd_hermite_step_f32(float* pos, float* vel, const float* acc_in, const float* jerk_in, float* acc_out,
+                         float* jerk_out, const float* mass, int n, double dt, float softening_sq, float g_const,
+                         float* posm, void* workspace, size_t workspace_bytes, nbd_stream_t stream);
+
 /* ------------------------------------------------------------ surrogate models: graph build
  * Replace the torch_cluster kernels the reference reaches through PyG. Index-exact rule (the
  * reference delegates ties/truncation to torch_cluster; fixed here, see oracle/surrogate_oracle.py):

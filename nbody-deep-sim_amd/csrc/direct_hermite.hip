@@ -1,0 +1,358 @@
+// direct_hermite.hip -- shared-timestep 4th-order Hermite predictor-corrector (Makino & Aarseth 1992) for the direct
+// force path on gfx950 (MI355X). An extension: the reference has Euler and kick-drift-kick leapfrog only. C-ABI: the
+// nbd_hermite_* / nbd_accel_jerk_f32 entries of include/nbd.h; Python: galaxify.simulation.HermiteSimulator.
+//
+// One step is three launches (PEC form; a0, j0 carried from the previous step):
+//   predict  : x_p = x + v dt + a0 dt^2/2 + j0 dt^3/6, v_p = v + a0 dt + j0 dt^2/2 -> posm = {x_p, m}, velp = {v_p, 0}
+//              (64-source chunk layout, zero padding)
+//   evaluate : accel_jerk_kernel -- a_i = G sum_j m_j r_ij s^3, j_i = G sum_j m_j (v_ij s^3 - 3 (r_ij.v_ij) s^5 r_ij)
+//              into float[slabs][6][n] partial sums (unscaled)
+//   correct  : fixed-order slab sum, a1 = G sum, j1 = G sum, then
+//              v1 = v + (a0 + a1) dt/2 + (j0 - j1) dt^2/12,  x1 = x + (v + v1) dt/2 + (a0 - a1) dt^2/12,
+//              posm = {x1, m} (energies after the step need no extra pack)
+// No atomics, no memsets, no host syncs: deterministic and capturable.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "../../include/nbd.h"
+#include "direct_kernels.h"
+
+namespace {
+
+// One source against the lane's two targets, index-masked (softening^2 below kEps2Masked): accel_kernel's rule, only
+// j == i and the padding behind n are dropped. ja accumulates w dv, jb accumulates (r.v s^2) w dr; j = ja - 3 jb.
+__device__ __forceinline__ void jerk_pair_masked(const f4 p, const f4 q, const f2 xi, const f2 yi, const f2 zi,
+                                                 const f2 ui, const f2 vi, const f2 wi, const f2 e2, f2* acc, int j,
+                                                 int i0, int i1, int n) {
+  const f2 dx = f2{p.x, p.x} - xi, dy = f2{p.y, p.y} - yi, dz = f2{p.z, p.z} - zi;
+  const f2 du = f2{q.x, q.x} - ui, dv = f2{q.y, q.y} - vi, dw = f2{q.z, q.z} - wi;
+  f2 r2 = __builtin_elementwise_fma(dx, dx, e2);
+  r2 = __builtin_elementwise_fma(dy, dy, r2);
+  r2 = __builtin_elementwise_fma(dz, dz, r2);
+  f2 rv = dx * du;
+  rv = __builtin_elementwise_fma(dy, dv, rv);
+  rv = __builtin_elementwise_fma(dz, dw, rv);
+  f2 s = {__builtin_amdgcn_rsqf(r2.x), __builtin_amdgcn_rsqf(r2.y)};
+  const bool live = j < n;
+  s.x = (live && j != i0) ? s.x : 0.0f;
+  s.y = (live && j != i1) ? s.y : 0.0f;
+  const f2 s2 = s * s;
+  const f2 w = (s2 * s) * f2{p.w, p.w};
+  const f2 c = (rv * s2) * w;
+  acc[0] = __builtin_elementwise_fma(w, dx, acc[0]);
+  acc[1] = __builtin_elementwise_fma(w, dy, acc[1]);
+  acc[2] = __builtin_elementwise_fma(w, dz, acc[2]);
+  acc[3] = __builtin_elementwise_fma(w, du, acc[3]);
+  acc[4] = __builtin_elementwise_fma(w, dv, acc[4]);
+  acc[5] = __builtin_elementwise_fma(w, dw, acc[5]);
+  acc[6] = __builtin_elementwise_fma(c, dx, acc[6]);
+  acc[7] = __builtin_elementwise_fma(c, dy, acc[7]);
+  acc[8] = __builtin_elementwise_fma(c, dz, acc[8]);
+}
+
+// KU sources at once, un-masked: interact_block's shape (the 2 KU v_rsq_f32 issued back to back, the mass splat folded
+// into op_sel by one asm multiply that consumes s^3, never the rsq result itself -- see interact()). Per source and pair
+// of targets: 6 v_pk_add (differences), 5 v_pk_fma + 1 v_pk_mul (r^2, r.v), 2 v_rsq_f32, 5 v_pk_mul (s^2, s^3, w, r.v s^2,
+// c = (r.v s^2) w), 9 v_pk_fma (a, w dv, c dr): 26 packed ops (the factor -3 of the jerk's second sum is applied once, to
+// the finished per-lane sum).
+template <int KU>
+__device__ __forceinline__ void jerk_block(const f4* __restrict__ bp, const f4* __restrict__ bv, const f2 xi,
+                                           const f2 yi, const f2 zi, const f2 ui, const f2 vi, const f2 wi,
+                                           const f2 e2, f2* acc) {
+  f2 zm[KU], dx[KU], dy[KU], dz[KU], du[KU], dv[KU], dw[KU], s[KU], rv[KU];
+#pragma unroll
+  for (int u = 0; u < KU; ++u) {
+    const f4 p = bp[u], q = bv[u];
+    zm[u] = f2{p.z, p.w};
+    dx[u] = f2{p.x, p.x} - xi; dy[u] = f2{p.y, p.y} - yi; dz[u] = f2{p.z, p.z} - zi;
+    du[u] = f2{q.x, q.x} - ui; dv[u] = f2{q.y, q.y} - vi; dw[u] = f2{q.z, q.z} - wi;
+    f2 r2 = __builtin_elementwise_fma(dx[u], dx[u], e2);
+    r2 = __builtin_elementwise_fma(dy[u], dy[u], r2);
+    s[u] = __builtin_elementwise_fma(dz[u], dz[u], r2);
+    f2 t = dx[u] * du[u];
+    t = __builtin_elementwise_fma(dy[u], dv[u], t);
+    rv[u] = __builtin_elementwise_fma(dz[u], dw[u], t);
+  }
+#pragma unroll
+  for (int u = 0; u < KU; ++u) s[u] = f2{__builtin_amdgcn_rsqf(s[u].x), __builtin_amdgcn_rsqf(s[u].y)};
+  __builtin_amdgcn_sched_group_barrier(0x400, 2 * KU, 0);      // 0x400 = TRANS: keep the rsq's together
+#pragma unroll
+  for (int u = 0; u < KU; ++u) {
+    const f2 s2 = s[u] * s[u];
+    const f2 s3 = s2 * s[u];
+    f2 w;
+    asm("v_pk_mul_f32 %0, %1, %2 op_sel:[1,0] op_sel_hi:[1,1]" : "=v"(w) : "v"(zm[u]), "v"(s3));
+    const f2 c = (rv[u] * s2) * w;
+    acc[0] = __builtin_elementwise_fma(w, dx[u], acc[0]);
+    acc[1] = __builtin_elementwise_fma(w, dy[u], acc[1]);
+    acc[2] = __builtin_elementwise_fma(w, dz[u], acc[2]);
+    acc[3] = __builtin_elementwise_fma(w, du[u], acc[3]);
+    acc[4] = __builtin_elementwise_fma(w, dv[u], acc[4]);
+    acc[5] = __builtin_elementwise_fma(w, dw[u], acc[5]);
+    acc[6] = __builtin_elementwise_fma(c, dx[u], acc[6]);
+    acc[7] = __builtin_elementwise_fma(c, dy[u], acc[7]);
+    acc[8] = __builtin_elementwise_fma(c, dz[u], acc[8]);
+  }
+}
+
+// Acceleration + jerk of all n bodies under all n bodies. accel_kernel's structure: grid = (target groups of 128,
+// slabs), block = 4 waves; two targets per lane in packed fp32; every wave streams its own balanced slice of the chunks,
+// each chunk = 64 positions + 64 velocities (2 KiB) by LDS-DMA, double-buffered behind a counted vmcnt; the 4 waves'
+// partials are reduced through LDS into one coalesced store of 6 x 128 floats per workgroup. out: float[slab][6][n].
+// KU = 2 (the default): 76 VGPRs, 6 waves per SIMD, and hipcc issues each pair of rsq's back to back with no s_nop in
+// the loop; KU = 4: 88 VGPRs, 5 waves per SIMD, but hipcc interleaves the rsq's with their consumers and pads the
+// transcendental hazards with s_nop (14-19 per 4 sources). 16 KiB of LDS per workgroup (the partials reuse each wave's
+// own staging buffers), so LDS does not cap either below 10 workgroups per CU.
+template <bool MASKED, int KU>
+__global__ __launch_bounds__(64 * kWaves, KU == 2 ? 6 : 5) void accel_jerk_kernel(
+    const f4* __restrict__ posm, const f4* __restrict__ velp, int n, int cpw_q, int cpw_r, float eps2,
+    float* __restrict__ out) {
+  // [wave][buffer][pos | vel][64] staging; after its last chunk a wave puts its [12][64] partials into its own part
+  __shared__ f4 lds[kWaves * 4 * kChunk];
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int t_base = blockIdx.x * kTgtPerWG;
+  const int i0 = t_base + lane, i1 = t_base + 64 + lane;
+  const f4 t0 = posm[min(i0, n - 1)], t1 = posm[min(i1, n - 1)];
+  const f4 u0 = velp[min(i0, n - 1)], u1 = velp[min(i1, n - 1)];
+  const f2 xi = {t0.x, t1.x}, yi = {t0.y, t1.y}, zi = {t0.z, t1.z};
+  const f2 ui = {u0.x, u1.x}, vi = {u0.y, u1.y}, wi = {u0.z, u1.z};
+  f2 acc[9];
+#pragma unroll
+  for (int k = 0; k < 9; ++k) acc[k] = f2{0.f, 0.f};
+  f2 e2 = {eps2, eps2};
+  asm volatile("" : "+v"(e2));  // keep eps^2 in VGPRs: an SGPR operand halves v_pk_fma issue
+
+  const int jw = blockIdx.y * kWaves + wave;
+  const int c_begin = jw * cpw_q + min(jw, cpw_r), c_end = c_begin + cpw_q + (jw < cpw_r ? 1 : 0);
+  f4* stage = &lds[wave * 4 * kChunk];
+  const f4* p_lane = posm + lane;
+  const f4* v_lane = velp + lane;
+  auto fetch = [&](int c, int b) {
+    __builtin_amdgcn_global_load_lds(GPTR(p_lane + (size_t)c * kChunk), LPTR(stage + b * 2 * kChunk), 16, 0, 0);
+    __builtin_amdgcn_global_load_lds(GPTR(v_lane + (size_t)c * kChunk), LPTR(stage + b * 2 * kChunk + kChunk), 16, 0, 0);
+  };
+  if (c_begin < c_end) fetch(c_begin, 0);
+  for (int c = c_begin; c < c_end; ++c) {
+    const int b = (c - c_begin) & 1;
+    if (c + 1 < c_end) {
+      fetch(c + 1, b ^ 1);
+      asm volatile("s_waitcnt vmcnt(2)" ::: "memory");  // chunk c has landed, c+1 (two loads) in flight
+    } else {
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
+    const f4* bp = stage + b * 2 * kChunk;
+    const f4* bv = bp + kChunk;
+    if (MASKED) {
+      const int j0 = c * kChunk;
+#pragma unroll 2
+      for (int j = 0; j < kChunk; ++j)
+        jerk_pair_masked(bp[j], bv[j], xi, yi, zi, ui, vi, wi, e2, acc, j0 + j, i0, i1, n);
+    } else {
+#pragma unroll 1
+      for (int j = 0; j < kChunk; j += KU) jerk_block<KU>(bp + j, bv + j, xi, yi, zi, ui, vi, wi, e2, acc);
+    }
+  }
+
+  // j = (w dv) - 3 (r.v s^2 w dr); wavefront partials -> LDS -> one coalesced (6 x 128) store per workgroup. A wave's
+  // staging is free here: its loads have landed (vmcnt(0) on the last chunk) and its reads precede these writes.
+  constexpr int kPart = 4 * kChunk * 4;                              // floats per wave: [comp*2+half][64] in the first 768
+  float* red = reinterpret_cast<float*>(lds);
+  float* mine = red + wave * kPart;
+#pragma unroll
+  for (int k = 0; k < 6; ++k) {
+    const f2 v = k < 3 ? acc[k] : acc[k] - 3.0f * acc[k + 3];
+    mine[(2 * k) * 64 + lane] = v.x;
+    mine[(2 * k + 1) * 64 + lane] = v.y;
+  }
+  __syncthreads();
+  float* dst = out + (size_t)blockIdx.y * 6 * n + t_base;
+  const int n_valid = min(kTgtPerWG, n - t_base);
+  for (int o = threadIdx.x; o < 6 * kTgtPerWG; o += 64 * kWaves) {
+    const int comp = o >> 7, lt = o & 127;
+    if (lt >= n_valid) continue;
+    const int idx = (comp * 2 + (lt >> 6)) * 64 + (lt & 63);
+    float sum = red[idx];
+#pragma unroll
+    for (int w = 1; w < kWaves; ++w) sum += red[w * kPart + idx];
+    dst[(size_t)comp * n + lt] = sum;
+  }
+}
+
+// fp32 step constants, each formed in double and rounded once
+struct HermiteDt { float dt, dt_half, dt2_half, dt3_sixth, dt2_twelfth; };
+
+HermiteDt hermite_dt(double dt) {
+  return HermiteDt{(float)dt, (float)(0.5 * dt), (float)(0.5 * dt * dt), (float)(dt * dt * dt / 6.0),
+                   (float)(dt * dt / 12.0)};
+}
+
+// posm = {x_p, m}, velp = {v_p, 0} for rows [0, n_pad) (zero padding behind n). acc == nullptr: plain pack (x, v).
+__global__ __launch_bounds__(256) void hermite_predict_kernel(const float* __restrict__ pos, const float* __restrict__ vel,
+                                                              const float* __restrict__ acc, const float* __restrict__ jerk,
+                                                              const float* __restrict__ mass, int n, int n_pad, HermiteDt h,
+                                                              f4* __restrict__ posm, f4* __restrict__ velp) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n_pad) return;
+  f4 pm = {0.f, 0.f, 0.f, 0.f}, vp = {0.f, 0.f, 0.f, 0.f};
+  if (i < n) {
+    float x[3], v[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      x[k] = pos[3 * i + k];
+      v[k] = vel[3 * i + k];
+      if (acc) {
+        const float a = acc[3 * i + k], j = jerk[3 * i + k];
+        x[k] = ((x[k] + v[k] * h.dt) + a * h.dt2_half) + j * h.dt3_sixth;
+        v[k] = (v[k] + a * h.dt) + j * h.dt2_half;
+      }
+    }
+    pm = f4{x[0], x[1], x[2], mass[i]};
+    vp = f4{v[0], v[1], v[2], 0.f};
+  }
+  posm[i] = pm;
+  velp[i] = vp;
+}
+
+// a1 = g * sum of the slabs, j1 likewise, in a fixed order (finish_kernel's scheme: wave w of the block sums slabs
+// w, w+4, ... of 64 consecutive bodies, the four partials combined as (p0 + p1) + (p2 + p3)). pos == nullptr: write a1, j1
+// only (the force on its own). Else the corrector: reads a0, j0 (acc_in / jerk_in, which may alias acc_out / jerk_out:
+// each element is read before it is written, by the same thread), x, v; writes x1, v1, a1, j1 and posm = {x1, m}.
+__global__ __launch_bounds__(256) void hermite_correct_kernel(const float* __restrict__ slabs, int n_slabs, int n, float g,
+                                                              HermiteDt h, float* pos, float* vel, const float* acc_in,
+                                                              const float* jerk_in, float* acc_out, float* jerk_out,
+                                                              const float* __restrict__ mass, f4* __restrict__ posm) {
+  __shared__ float part[4][6][64];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int i = blockIdx.x * 64 + lane;
+  float sum[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  if (i < n)
+    for (int s = w; s < n_slabs; s += 4)
+#pragma unroll
+      for (int k = 0; k < 6; ++k) sum[k] += slabs[((size_t)s * 6 + k) * n + i];
+#pragma unroll
+  for (int k = 0; k < 6; ++k) part[w][k][lane] = sum[k];
+  __syncthreads();
+  if (w != 0 || i >= n) return;
+  float a1[3], j1[3];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    a1[k] = g * ((part[0][k][lane] + part[1][k][lane]) + (part[2][k][lane] + part[3][k][lane]));
+    j1[k] = g * ((part[0][k + 3][lane] + part[1][k + 3][lane]) + (part[2][k + 3][lane] + part[3][k + 3][lane]));
+  }
+  if (pos) {
+    float x1[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      const float a0 = acc_in[3 * i + k], j0 = jerk_in[3 * i + k];
+      const float x = pos[3 * i + k], v = vel[3 * i + k];
+      const float v1 = (v + (a0 + a1[k]) * h.dt_half) + (j0 - j1[k]) * h.dt2_twelfth;
+      x1[k] = (x + (v + v1) * h.dt_half) + (a0 - a1[k]) * h.dt2_twelfth;
+      vel[3 * i + k] = v1;
+      pos[3 * i + k] = x1[k];
+    }
+    posm[i] = f4{x1[0], x1[1], x1[2], mass[i]};
+  }
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    acc_out[3 * i + k] = a1[k];
+    jerk_out[3 * i + k] = j1[k];
+  }
+}
+
+bool misaligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; }
+
+// the all-pairs force's launch geometry (nbd_accel_plan): same targets, same chunks, the same balance problem
+struct JerkPlan { int groups, slabs, n_chunks; };
+
+JerkPlan plan_jerk(int n) {
+  JerkPlan p;
+  int cpw = 0;
+  nbd_accel_plan(n, n, &p.groups, &p.slabs, &cpw);
+  p.n_chunks = ceil_div(n, kChunk);
+  return p;
+}
+
+size_t velp_bytes(int n) { return (size_t)ceil_div(n, kChunk) * kChunk * sizeof(f4); }
+
+// the unscaled partial sums of every body into float[slabs][6][n]
+int launch_jerk(const float* posm, const float* velp, int n, float eps2, float* slabs, const JerkPlan& p, int variant,
+                hipStream_t st) {
+  dim3 grid(p.groups, p.slabs), block(64 * kWaves);
+  const int q = p.n_chunks / (p.slabs * kWaves), r = p.n_chunks % (p.slabs * kWaves);
+  const f4* pm = reinterpret_cast<const f4*>(posm);
+  const f4* vp = reinterpret_cast<const f4*>(velp);
+  const bool masked = eps2 < kEps2Masked;
+#define NBD_LAUNCH(M, K) accel_jerk_kernel<M, K><<<grid, block, 0, st>>>(pm, vp, n, q, r, eps2, slabs)
+  if (variant == 1) { if (masked) NBD_LAUNCH(true, 4); else NBD_LAUNCH(false, 4); }
+  else              { if (masked) NBD_LAUNCH(true, 2); else NBD_LAUNCH(false, 2); }
+#undef NBD_LAUNCH
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? 0 : (int)e;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t nbd_hermite_workspace_bytes(int n) {
+  if (n <= 0) return 0;
+  return velp_bytes(n) + (size_t)plan_jerk(n).slabs * 6 * n * sizeof(float);
+}
+
+int nbd_hermite_pack_f32(const float* pos, const float* vel, const float* acc, const float* jerk, const float* mass,
+                         int n, double dt, float* posm, float* velp, nbd_stream_t stream) {
+  if (n < 0 || (n > 0 && (!pos || !vel || !mass || !posm || !velp)) || (!acc != !jerk)) return NBD_E_BADARG;
+  if (misaligned16(posm) || misaligned16(velp)) return NBD_E_BADARG;
+  if (n == 0) return 0;
+  const int n_pad = nbd_posm_padded_len(n);
+  hermite_predict_kernel<<<ceil_div(n_pad, 256), 256, 0, (hipStream_t)stream>>>(
+      pos, vel, acc, jerk, mass, n, n_pad, hermite_dt(dt), reinterpret_cast<f4*>(posm), reinterpret_cast<f4*>(velp));
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? 0 : (int)e;
+}
+
+int nbd_accel_jerk_f32(const float* posm, const float* velp, int n, float softening_sq, float g_const, float* acc_out,
+                       float* jerk_out, void* workspace, size_t workspace_bytes, int variant, nbd_stream_t stream) {
+  if (n < 0 || variant < 0 || variant > 1) return NBD_E_BADARG;
+  if (n == 0) return 0;
+  if (!posm || !velp || !acc_out || !jerk_out || misaligned16(posm) || misaligned16(velp)) return NBD_E_BADARG;
+  if (!workspace || workspace_bytes < nbd_hermite_workspace_bytes(n)) return NBD_E_WORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  const JerkPlan p = plan_jerk(n);
+  float* slabs = static_cast<float*>(workspace);
+  int rc = launch_jerk(posm, velp, n, softening_sq, slabs, p, variant, st);
+  if (rc) return rc;
+  hermite_correct_kernel<<<ceil_div(n, 64), 256, 0, st>>>(slabs, p.slabs, n, g_const, hermite_dt(0.0), nullptr, nullptr,
+                                                          nullptr, nullptr, acc_out, jerk_out, nullptr, nullptr);
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? 0 : (int)e;
+}
+
+int nbd_hermite_step_f32(float* pos, float* vel, const float* acc_in, const float* jerk_in, float* acc_out,
+                         float* jerk_out, const float* mass, int n, double dt, float softening_sq, float g_const,
+                         float* posm, void* workspace, size_t workspace_bytes, nbd_stream_t stream) {
+  if (n < 0) return NBD_E_BADARG;
+  if (n == 0) return 0;
+  if (!pos || !vel || !acc_in || !jerk_in || !acc_out || !jerk_out || !mass || !posm || misaligned16(posm))
+    return NBD_E_BADARG;
+  if (!workspace || misaligned16(workspace) || workspace_bytes < nbd_hermite_workspace_bytes(n)) return NBD_E_WORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  const HermiteDt h = hermite_dt(dt);
+  const JerkPlan p = plan_jerk(n);
+  float* velp = static_cast<float*>(workspace);
+  float* slabs = reinterpret_cast<float*>(static_cast<char*>(workspace) + velp_bytes(n));
+  const int n_pad = nbd_posm_padded_len(n);
+  hermite_predict_kernel<<<ceil_div(n_pad, 256), 256, 0, st>>>(pos, vel, acc_in, jerk_in, mass, n, n_pad, h,
+                                                               reinterpret_cast<f4*>(posm), reinterpret_cast<f4*>(velp));
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return (int)e;
+  int rc = launch_jerk(posm, velp, n, softening_sq, slabs, p, 0, st);
+  if (rc) return rc;
+  hermite_correct_kernel<<<ceil_div(n, 64), 256, 0, st>>>(slabs, p.slabs, n, g_const, h, pos, vel, acc_in, jerk_in,
+                                                          acc_out, jerk_out, mass, reinterpret_cast<f4*>(posm));
+  e = hipGetLastError();
+  return e == hipSuccess ? 0 : (int)e;
+}
+
+}  // extern "C"

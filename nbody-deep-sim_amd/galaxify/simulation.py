@@ -14,6 +14,9 @@ the global arrays. See nbd/dist.py and DESIGN.md.
 
 Second addition: `BatchedSimulator` advances many independent systems with one set of launches per step
 (csrc/direct_batch.hip).
+
+Third addition: `HermiteSimulator`, the shared-timestep 4th-order Hermite predictor-corrector (one acceleration + jerk
+evaluation per step; csrc/direct_hermite.hip).
 """
 from __future__ import annotations
 
@@ -220,9 +223,9 @@ class BaseSimulator:
                 events.append((e0, e1))
                 if self.calc_energy:
                     if not self._sharded:
-                        # energies of the state AFTER the step (simulation.py:131-133). The leapfrog step
-                        # leaves posm = current positions; the Euler step packs before its drift, so repack.
-                        if not isinstance(self, LeapFrogSimulator):
+                        # energies of the state AFTER the step (simulation.py:131-133). The leapfrog and Hermite
+                        # steps leave posm = current positions; the Euler step packs before its drift, so repack.
+                        if not isinstance(self, (LeapFrogSimulator, HermiteSimulator)):
                             direct.pack_posm(self.positions, self.masses, out=self._posm)
                         direct.energy(self._posm, self.velocities, self.n, direct.f32(self.softening),
                                       self._g, out_uk=uk_dev[s])
@@ -259,7 +262,7 @@ class BaseSimulator:
 
     def _graph_run_ok(self, steps: int) -> bool:
         return (not self._sharded and 0 < self.n <= self.GRAPH_RUN_MAX_BODIES and steps >= 8 and
-                type(self).step in (LeapFrogSimulator.step, EulerSimulator.step) and
+                type(self).step in (LeapFrogSimulator.step, EulerSimulator.step, HermiteSimulator.step) and
                 os.environ.get("NBD_RUN_GRAPH", "1") != "0")
 
     def _step_in_place(self, acc):
@@ -268,6 +271,9 @@ class BaseSimulator:
         if isinstance(self, LeapFrogSimulator):
             direct.leapfrog_step(self.positions, self.velocities, acc, acc, self.masses, direct.f32(0.5 * self.dt), dt,
                                  self._eps2, self._g, self._posm, self._ws, uniform=self._uniform)
+        elif isinstance(self, HermiteSimulator):        # the jerks are carried in the simulator's own static buffer
+            direct.hermite_step(self.positions, self.velocities, acc, self._jerk_g, acc, self._jerk_g, self.masses,
+                                self.dt, self._eps2, self._g, self._posm, self._hws)
         else:
             direct.euler_step(self.positions, self.velocities, acc, self.masses, dt, self._eps2, self._g, self._posm,
                               self._ws)
@@ -286,10 +292,13 @@ class BaseSimulator:
         if getattr(self, "_acc_g", None) is None:
             self._acc_g = torch.empty((n, 3), dtype=torch.float32, device=dev)
             self._energy_ws = direct.alloc_bytes(_lib.lib().nbd_energy_workspace_bytes(n), dev)
+        hermite = isinstance(self, HermiteSimulator)
+        if hermite and getattr(self, "_jerk_g", None) is None:
+            self._jerk_g = torch.empty((n, 3), dtype=torch.float32, device=dev)
         ring = torch.empty((m, 3, n, 3), dtype=torch.float32, device=dev)
         uk = torch.zeros((m, 2), dtype=torch.float64, device=dev)
         soft = direct.f32(self.softening)
-        leap = isinstance(self, LeapFrogSimulator)
+        leap = isinstance(self, (LeapFrogSimulator, HermiteSimulator))      # steps that leave posm = {x, m}
 
         def body(count=m):
             for s_ in range(count):
@@ -300,17 +309,23 @@ class BaseSimulator:
                     direct.energy(self._posm, self.velocities, n, soft, self._g, out_uk=uk[s_], workspace=self._energy_ws)
                 direct.snapshot(self.positions, self.velocities, self._acc_g, ring[s_])
         # capture on a side stream; the state is saved and restored around the (executed) warm-up pass
-        keep = (self.positions.clone(), self.velocities.clone(), self._acc_g.clone())
+        keep = (self.positions.clone(), self.velocities.clone(), self._acc_g.clone(),
+                self._jerk_g.clone() if hermite else None)
+
+        def restore():
+            self.positions.copy_(keep[0]); self.velocities.copy_(keep[1]); self._acc_g.copy_(keep[2])
+            if hermite:
+                self._jerk_g.copy_(keep[3])
         side = torch.cuda.Stream(device=dev)
         side.wait_stream(torch.cuda.current_stream(dev))
         with torch.cuda.stream(side):
             body(1)                                          # every kernel of a step once (lazy initialisations)
         torch.cuda.current_stream(dev).wait_stream(side)
-        self.positions.copy_(keep[0]); self.velocities.copy_(keep[1]); self._acc_g.copy_(keep[2])
+        restore()
         graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(graph):
             body()
-        self.positions.copy_(keep[0]); self.velocities.copy_(keep[1]); self._acc_g.copy_(keep[2])
+        restore()
         cache[key] = (graph, ring, uk)
         return cache[key]
 
@@ -323,6 +338,8 @@ class BaseSimulator:
             graph, ring, uk = self._chunk_graph(m)          # (capture leaves the state untouched)
             if first:                                        # a caller's handle on the old accelerations stays valid
                 self._acc_g.copy_(self.accelerations)
+                if isinstance(self, HermiteSimulator):
+                    self._jerk_g.copy_(self.jerks)
                 first = False
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
@@ -337,6 +354,8 @@ class BaseSimulator:
                                               velocities=host[s_, 1], accelerations=host[s_, 2], u_energy=u, k_energy=k))
             done += m
         self.accelerations = self._acc_g.clone()             # rebound, as step() does (simulation.py:168)
+        if isinstance(self, HermiteSimulator):
+            self.jerks = self._jerk_g.clone()
         if done < steps:
             states += self._run_eager(steps - done, done)
         return states
@@ -466,6 +485,47 @@ class EulerSimulator(BaseSimulator):
         if self.part.n_local:
             direct.drift(self.positions, self.velocities, dt)
 
+
+
+class HermiteSimulator(BaseSimulator):
+    """Shared-timestep 4th-order Hermite predictor-corrector (Makino & Aarseth 1992), an extension the reference does not
+    have. With a0, j0 the acceleration and jerk carried from the previous step:
+        predict  x_p = x + v dt + a0 dt^2/2 + j0 dt^3/6,  v_p = v + a0 dt + j0 dt^2/2
+        evaluate a1, j1 at (x_p, v_p)
+        correct  v1 = v + (a0 + a1) dt/2 + (j0 - j1) dt^2/12,  x1 = x + (v + v1) dt/2 + (a0 - a1) dt^2/12
+    One acceleration + jerk evaluation per step (csrc/direct_hermite.hip), fp32 state. `jerks` (n,3) is public next to
+    `accelerations`; both hold the values evaluated at the last predicted state (PEC) and are rebound by step(). No
+    range-sharded form (process_group is refused) and no equal-mass specialisation."""
+
+    def __init__(self, *, positions, velocities, masses, g_const: float = 1.0, softening: float = 0.1,
+                 dt: float = 0.01, calc_energy: bool = True, device: str = None, process_group=None):
+        if process_group is not None:
+            raise ValueError("HermiteSimulator: there is no range-sharded Hermite step; process_group is not supported")
+        self.jerks = None
+        super().__init__(positions=positions, velocities=velocities, masses=masses, g_const=g_const,
+                         softening=softening, dt=dt, calc_energy=calc_energy, device=device)
+        self._velp = direct.alloc_posm(self.n, self.device)
+        self._hws = direct.hermite_workspace(max(self.n, 1), self.device)
+        self.accelerations, self.jerks = self.compute_accelerations_and_jerks()
+
+    def compute_accelerations_and_jerks(self):
+        """(a, j) of the current state as new (n,3) tensors: a_i = G sum_{j!=i} m_j r_ij s^3,
+        j_i = G sum_{j!=i} m_j (v_ij s^3 - 3 (r_ij.v_ij) s^5 r_ij), s = (|r_ij|^2 + eps^2)^(-1/2)."""
+        if self.n == 0:
+            z = torch.zeros((0, 3), dtype=torch.float32, device=self.device)
+            return z, z.clone()
+        direct.hermite_pack(self.positions, self.velocities, self.masses, self._posm, self._velp)
+        return direct.accel_jerk(self._posm, self._velp, self.n, self._eps2, self._g, workspace=self._hws)
+
+    def step(self):
+        """One predictor-corrector step: positions and velocities in place, `accelerations` and `jerks` rebound."""
+        if self.n == 0:
+            return
+        new_acc = torch.empty_like(self.accelerations)
+        new_jerk = torch.empty_like(self.jerks)
+        direct.hermite_step(self.positions, self.velocities, self.accelerations, self.jerks, new_acc, new_jerk,
+                            self.masses, self.dt, self._eps2, self._g, self._posm, self._hws)
+        self.accelerations, self.jerks = new_acc, new_jerk
 
 def _per_scene(x, n_scenes: int, name: str) -> list:
     """A scalar, or one value per scene -> list of S Python floats."""

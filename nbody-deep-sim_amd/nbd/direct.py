@@ -267,6 +267,65 @@ def energy(posm, vel, n: int, softening: float, g_const: float, out_uk=None, wor
     return out_uk
 
 
+
+# ---------------------------------------------------------------- 4th-order Hermite integrator (csrc/direct_hermite.hip)
+def hermite_workspace(n: int, device) -> torch.Tensor:
+    return alloc_bytes(_lib.lib().nbd_hermite_workspace_bytes(int(n)), device)
+
+
+def hermite_pack(pos, vel, mass, posm, velp, acc=None, jerk=None, dt: float = 0.0) -> None:
+    """posm = {x_p, m}, velp = {v_p, 0} (padded_len(n) rows each): the predicted state after dt from (acc, jerk), or a
+    plain pack of (pos, vel) when both are None."""
+    n = pos.shape[0]
+    _chk(pos, (n, 3), "pos"); _chk(vel, (n, 3), "vel"); _chk(mass, (n,), "mass")
+    _chk(posm, (padded_len(n), 4), "posm"); _chk(velp, (padded_len(n), 4), "velp")
+    if (acc is None) != (jerk is None):
+        raise _lib.NbdError("hermite_pack: give both acc and jerk, or neither")
+    if acc is not None:
+        _chk(acc, (n, 3), "acc"); _chk(jerk, (n, 3), "jerk")
+    with _lib.on_device(pos.device):
+        _lib.check(_lib.lib().nbd_hermite_pack_f32(
+            pos.data_ptr(), vel.data_ptr(), _lib.ptr(acc), _lib.ptr(jerk), mass.data_ptr(), n, float(dt),
+            posm.data_ptr(), velp.data_ptr(), _lib.current_stream(pos.device)), "nbd_hermite_pack_f32")
+
+
+def accel_jerk(posm, velp, n: int, softening_sq: float, g_const: float, acc_out=None, jerk_out=None, workspace=None,
+               variant: int = 0):
+    """(acc, jerk), each (n,3), of all n bodies of posm / velp (as hermite_pack leaves them):
+    a_i = G sum_j m_j r_ij s^3, j_i = G sum_j m_j (v_ij s^3 - 3 (r_ij.v_ij) s^5 r_ij), s = (|r_ij|^2 + eps^2)^(-1/2)."""
+    _chk(posm, (padded_len(n), 4), "posm"); _chk(velp, (padded_len(n), 4), "velp")
+    dev = posm.device
+    if acc_out is None:
+        acc_out = torch.empty((n, 3), dtype=torch.float32, device=dev)
+    if jerk_out is None:
+        jerk_out = torch.empty((n, 3), dtype=torch.float32, device=dev)
+    _chk(acc_out, (n, 3), "acc_out"); _chk(jerk_out, (n, 3), "jerk_out")
+    need = _lib.lib().nbd_hermite_workspace_bytes(n)
+    if workspace is None or _nbytes(workspace) < need:
+        workspace = alloc_bytes(need, dev)
+    with _lib.on_device(dev):
+        _lib.check(_lib.lib().nbd_accel_jerk_f32(
+            posm.data_ptr(), velp.data_ptr(), n, float(softening_sq), float(g_const), acc_out.data_ptr(),
+            jerk_out.data_ptr(), workspace.data_ptr(), _nbytes(workspace), int(variant), _lib.current_stream(dev)),
+            "nbd_accel_jerk_f32")
+    return acc_out, jerk_out
+
+
+def hermite_step(pos, vel, acc_in, jerk_in, acc_out, jerk_out, mass, dt: float, softening_sq: float, g_const: float,
+                 posm, workspace) -> None:
+    """One predictor-corrector step (three launches): pos, vel in place; acc_out, jerk_out = a, j at the predicted state
+    (may be acc_in, jerk_in); posm = {x1, m}. dt is the Python double: the fp32 step constants are formed from it."""
+    n = pos.shape[0]
+    for t, nm in ((pos, "pos"), (vel, "vel"), (acc_in, "acc_in"), (jerk_in, "jerk_in"), (acc_out, "acc_out"),
+                  (jerk_out, "jerk_out")):
+        _chk(t, (n, 3), nm)
+    _chk(mass, (n,), "mass"); _chk(posm, (padded_len(n), 4), "posm")
+    with _lib.on_device(pos.device):
+        _lib.check(_lib.lib().nbd_hermite_step_f32(
+            pos.data_ptr(), vel.data_ptr(), acc_in.data_ptr(), jerk_in.data_ptr(), acc_out.data_ptr(),
+            jerk_out.data_ptr(), mass.data_ptr(), n, float(dt), float(softening_sq), float(g_const), posm.data_ptr(),
+            workspace.data_ptr(), _nbytes(workspace), _lib.current_stream(pos.device)), "nbd_hermite_step_f32")
+
 # ---------------------------------------------------------------- batched direct integrator (csrc/direct_batch.hip)
 class BatchPlan:
     """The host offsets of an ensemble of scenes and the device work list built from them (nbd_batch_plan /
