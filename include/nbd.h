@@ -257,6 +257,49 @@ int nbd_hermite_step_f32(float* pos, float* vel, const float* acc_in, const floa
                          float* jerk_out, const float* mass, int n, double dt, float softening_sq, float g_const,
                          float* posm, void* workspace, size_t workspace_bytes, nbd_stream_t stream);
 
+/* ------------------------------------------------ block-timestep Hermite integrator (csrc/direct_hermite_block.hip)
+ * The scheme above with individual power-of-two steps (Makino & Aarseth 1992). One output interval dt is 2^K integer
+ * ticks, K = max_level in [0, 20]. Body i keeps x, v, a, j at its last correction tick ticks[i] (int32) and a level
+ * levels[i] in [0, K]; its step is d_i = 2^(K - k_i) ticks. sched is a device int[NBD_HBLOCK_SCHED_INTS] whose first
+ * three entries are {t_next, n_act, clamped}: schedule writes t_next and n_act, the clamp counter is cumulative (zero it
+ * once); the rest (current tick, level histogram) belongs to the entries. Every interval starts and ends with all
+ * ticks at 0. A block step is schedule, then predict, force and correct (or nbd_hblock_step_f32, all three). Levels
+ * come from the Aarseth criterion in fp64, quantised against the exact powers dt 2^-k; a level deeper than K (or a NaN
+ * criterion) is clamped to K and counted. Workspace: nbd_hblock_workspace_bytes(n), 16-byte aligned; it holds the active
+ * list and the partial sums between the calls of one block step. Eager-only (schedule reads back to the host). */
+#define NBD_HBLOCK_SCHED_INTS 32
+size_t nbd_hblock_workspace_bytes(int n);
+/* ticks = 0 and levels from dt_i = (eta / 2) |a| / |j| for all n bodies; starts a new interval. */
+int nbd_hblock_init_levels(const float* acc, const float* jerk, int n, double dt, double eta, int max_level, int* ticks,
+                           int* levels, int* sched, nbd_stream_t stream);
+/* t_next = min_i (ticks[i] + d_i) and the active list (in no fixed order) into the workspace. host_sched non-null:
+ * sched[0..4) is copied there and the stream synchronised (the one readback of a block step; pinned memory is
+ * fastest). */
+int nbd_hblock_schedule(const int* levels, int n, int max_level, int* sched, void* workspace, size_t workspace_bytes,
+                        int* host_sched, nbd_stream_t stream);
+/* posm = {x_p, m}, velp = {v_p, 0} of every body predicted to t_next = sched[0] over (t_next - ticks[i]) dt / 2^K;
+ * float4[nbd_posm_padded_len(n)] each, zero padding. */
+int nbd_hblock_predict_f32(const float* pos, const float* vel, const float* acc, const float* jerk, const float* mass,
+                           const int* ticks, int n, int max_level, double dt, int* sched, float* posm, float* velp,
+                           nbd_stream_t stream);
+/* Acceleration + jerk partial sums of the n_act listed bodies (n_act as schedule reported) under all n of posm / velp. */
+int nbd_hblock_force_f32(const float* posm, const float* velp, int n, int n_act, float softening_sq, void* workspace,
+                         size_t workspace_bytes, nbd_stream_t stream);
+/* Slab sum, corrector with each listed body's own step, new level, ticks[i] = t_next (0 at 2^K), posm[i] = {x1, m}. */
+int nbd_hblock_correct_f32(float* pos, float* vel, float* acc, float* jerk, const float* mass, int* ticks, int* levels,
+                           int n, int n_act, int max_level, double dt, double eta, float g_const, int* sched, float* posm,
+                           void* workspace, size_t workspace_bytes, nbd_stream_t stream);
+/* predict + force + correct of one block step (n_act >= 1). */
+int nbd_hblock_step_f32(float* pos, float* vel, float* acc, float* jerk, const float* mass, int* ticks, int* levels,
+                        int n, int n_act, int max_level, double dt, double eta, float softening_sq, float g_const,
+                        int* sched, float* posm, float* velp, void* workspace, size_t workspace_bytes,
+                        nbd_stream_t stream);
+/* The force alone (tests, profiling): acc_out, jerk_out (n_act,3) of the bodies act[0..n_act) (a device int32 list, any
+ * order, no repeats needed) under all n bodies of posm / velp. With n_act = n the sums are nbd_accel_jerk_f32's bits. */
+int nbd_accel_jerk_active_f32(const float* posm, const float* velp, int n, const int* act, int n_act,
+                              float softening_sq, float g_const, float* acc_out, float* jerk_out, void* workspace,
+                              size_t workspace_bytes, nbd_stream_t stream);
+
 /* ------------------------------------------------------------ surrogate models: graph build
  * Replace the torch_cluster kernels the reference reaches through PyG. Index-exact rule (the
  * reference delegates ties/truncation to torch_cluster; fixed here, see oracle/surrogate_oracle.py):

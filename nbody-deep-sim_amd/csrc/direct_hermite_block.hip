@@ -1,0 +1,495 @@
+// direct_hermite_block.hip -- block-timestep 4th-order Hermite integration (Makino & Aarseth 1992) for the direct force
+// path on gfx950 (MI355X). An extension: the reference has Euler and kick-drift-kick leapfrog only. C-ABI: the
+// nbd_hblock_* / nbd_accel_jerk_active_f32 entries of include/nbd.h; Python: galaxify.simulation.BlockHermiteSimulator.
+//
+// One output interval dt is 2^K integer ticks (K = max_level). Body i carries x, v, a, j at its last correction tick
+// t_i and a level k_i in [0, K]: its step is d_i = 2^(K - k_i) ticks, and t_i is always a multiple of d_i. One block step:
+//   schedule : t_next = min_i (t_i + d_i), the active list {i : t_i + d_i = t_next}. Under the block condition every
+//              body at level k is due at the first multiple of d_k after the current tick T, so t_next is the integer
+//              min of that over the levels present (a device histogram of the levels), and the active bodies are those
+//              whose d_i divides t_next: level >= K - ctz(t_next). A multi-block compaction writes the list.
+//   predict  : every body to t_next with its own Delta_i = t_next - t_i ticks -> posm = {x_p, m}, velp = {v_p, 0}
+//   evaluate : accel_jerk_active_kernel -- a1, j1 of the active targets under all n predicted sources, into
+//              float[slabs][6][n_act] partial sums (accel_jerk_kernel's arithmetic and source order)
+//   correct  : fixed-order slab sum, the corrector with the body's own step h = d_i, the Aarseth criterion in fp64 for the
+//              new level, t_i = t_next (0 at the end of the interval), posm = {x1, m}
+// The fp32 step constants are formed in fp64 from dt and the tick count and rounded once, exactly as hermite_dt() does:
+// a body whose Delta is the whole interval gets the shared step's bits. No float atomics (the clamp counter is an integer
+// atomic); the host reads {t_next, n_act} once per block step, so the path is eager-only.
+#include <hip/hip_runtime.h>
+#include <limits.h>
+#include <math.h>
+#include <stdint.h>
+
+#include "../../include/nbd.h"
+#include "direct_kernels.h"
+#include "hermite_kernels.h"
+
+namespace {
+
+constexpr int kMaxLevel = 20;        // 2^20 ticks per interval: the tick count fits an int32 with room for t_i + d_i
+constexpr int kActSlabTarget = 512;  // small active sets: raise the slab count until groups x slabs reaches ~2 per CU
+constexpr int kActMaxSlabs = 256;
+
+// sched[NBD_HBLOCK_SCHED_INTS]: t_next and n_act of the block step being taken, the cumulative clamp count, the tick T
+// every body has reached (the last t_next, 0 at the start of an interval), the compaction's write cursor and its count
+// of finished workgroups (both 0 between launches), and the level histogram (bin k: bodies at level k)
+enum { kTNext = 0, kNAct = 1, kClamped = 2, kTCur = 3, kCursor = 4, kDone = 5, kHist = 8 };
+static_assert(kHist + kMaxLevel + 1 <= NBD_HBLOCK_SCHED_INTS, "sched holds the level histogram");
+
+// Acceleration + jerk of the n_act targets act[0..n_act) under all n sources: accel_jerk_kernel with its targets gathered
+// through the index list. Grid = (ceil(n_act / 128), slabs), block = 4 waves; same LDS-DMA chunk stream, same fixed-order
+// wave reduction. The lanes behind n_act repeat the last target and store nothing. out: float[slab][6][n_act], in list
+// order. A target's sums depend only on n and the slab count, not on where it sits in the list.
+template <bool MASKED>
+__global__ __launch_bounds__(64 * kWaves, 6) void accel_jerk_active_kernel(
+    const f4* __restrict__ posm, const f4* __restrict__ velp, int n, const int* __restrict__ act, int n_act, int cpw_q,
+    int cpw_r, float eps2, float* __restrict__ out) {
+  constexpr int KU = 2;
+  __shared__ f4 lds[kWaves * 4 * kChunk];
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int t_base = blockIdx.x * kTgtPerWG;
+  const int i0 = act[min(t_base + lane, n_act - 1)], i1 = act[min(t_base + 64 + lane, n_act - 1)];
+  const f4 t0 = posm[i0], t1 = posm[i1];
+  const f4 u0 = velp[i0], u1 = velp[i1];
+  const f2 xi = {t0.x, t1.x}, yi = {t0.y, t1.y}, zi = {t0.z, t1.z};
+  const f2 ui = {u0.x, u1.x}, vi = {u0.y, u1.y}, wi = {u0.z, u1.z};
+  f2 acc[9];
+#pragma unroll
+  for (int k = 0; k < 9; ++k) acc[k] = f2{0.f, 0.f};
+  f2 e2 = {eps2, eps2};
+  asm volatile("" : "+v"(e2));  // keep eps^2 in VGPRs: an SGPR operand halves v_pk_fma issue
+
+  const int jw = blockIdx.y * kWaves + wave;
+  const int c_begin = jw * cpw_q + min(jw, cpw_r), c_end = c_begin + cpw_q + (jw < cpw_r ? 1 : 0);
+  f4* stage = &lds[wave * 4 * kChunk];
+  const f4* p_lane = posm + lane;
+  const f4* v_lane = velp + lane;
+  auto fetch = [&](int c, int b) {
+    __builtin_amdgcn_global_load_lds(GPTR(p_lane + (size_t)c * kChunk), LPTR(stage + b * 2 * kChunk), 16, 0, 0);
+    __builtin_amdgcn_global_load_lds(GPTR(v_lane + (size_t)c * kChunk), LPTR(stage + b * 2 * kChunk + kChunk), 16, 0, 0);
+  };
+  if (c_begin < c_end) fetch(c_begin, 0);
+  for (int c = c_begin; c < c_end; ++c) {
+    const int b = (c - c_begin) & 1;
+    if (c + 1 < c_end) {
+      fetch(c + 1, b ^ 1);
+      asm volatile("s_waitcnt vmcnt(2)" ::: "memory");  // chunk c has landed, c+1 (two loads) in flight
+    } else {
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
+    const f4* bp = stage + b * 2 * kChunk;
+    const f4* bv = bp + kChunk;
+    if (MASKED) {
+      const int j0 = c * kChunk;
+#pragma unroll 2
+      for (int j = 0; j < kChunk; ++j)
+        jerk_pair_masked(bp[j], bv[j], xi, yi, zi, ui, vi, wi, e2, acc, j0 + j, i0, i1, n);
+    } else {
+#pragma unroll 1
+      for (int j = 0; j < kChunk; j += KU) jerk_block<KU>(bp + j, bv + j, xi, yi, zi, ui, vi, wi, e2, acc);
+    }
+  }
+
+  constexpr int kPart = 4 * kChunk * 4;
+  float* red = reinterpret_cast<float*>(lds);
+  float* mine = red + wave * kPart;
+#pragma unroll
+  for (int k = 0; k < 6; ++k) {
+    const f2 v = k < 3 ? acc[k] : acc[k] - 3.0f * acc[k + 3];
+    mine[(2 * k) * 64 + lane] = v.x;
+    mine[(2 * k + 1) * 64 + lane] = v.y;
+  }
+  __syncthreads();
+  float* dst = out + (size_t)blockIdx.y * 6 * n_act + t_base;
+  const int n_valid = min(kTgtPerWG, n_act - t_base);
+  for (int o = threadIdx.x; o < 6 * kTgtPerWG; o += 64 * kWaves) {
+    const int comp = o >> 7, lt = o & 127;
+    if (lt >= n_valid) continue;
+    const int idx = (comp * 2 + (lt >> 6)) * 64 + (lt & 63);
+    float sum = red[idx];
+#pragma unroll
+    for (int w = 1; w < kWaves; ++w) sum += red[w * kPart + idx];
+    dst[(size_t)comp * n_act + lt] = sum;
+  }
+}
+
+// The Aarseth criterion sqrt(eta num / den). den = 0 (no jerk and no higher derivative: a lone body, or one in a
+// uniform field) allows any step: +inf, not the NaN of 0/0. A NaN that comes from NaN forces stays NaN (clamped).
+__device__ __forceinline__ double criterion(double eta, double num, double den) {
+  return den == 0.0 ? INFINITY : sqrt(eta * num / den);
+}
+
+// The level a criterion value asks for: the smallest k >= 0 with dt 2^-k <= crit, compared against the exact powers of
+// two. K + 1 means "deeper than K" (also for NaN, which no comparison accepts); +inf gives 0.
+__device__ __forceinline__ int wanted_level(double crit, double dt, int K) {
+  int k = 0;
+  double step = dt;
+  while (k <= K && !(step <= crit)) {
+    ++k;
+    step *= 0.5;
+  }
+  return k;
+}
+
+__device__ __forceinline__ double norm3(double x, double y, double z) { return sqrt(x * x + y * y + z * z); }
+
+// Initial levels from dt_i = (eta / 2) |a| / |j| in fp64 (+inf where j = 0); every tick to 0. Levels deeper than K are clamped and counted.
+__global__ __launch_bounds__(256) void hblock_init_kernel(const float* __restrict__ acc, const float* __restrict__ jerk,
+                                                          int n, int K, double dt, double eta, int* __restrict__ ticks,
+                                                          int* __restrict__ levels, int* __restrict__ sched) {
+  __shared__ int hist[kMaxLevel + 1];
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (threadIdx.x <= K) hist[threadIdx.x] = 0;
+  __syncthreads();
+  if (i < n) {
+    const double a = norm3(acc[3 * i], acc[3 * i + 1], acc[3 * i + 2]);
+    const double j = norm3(jerk[3 * i], jerk[3 * i + 1], jerk[3 * i + 2]);
+    int k = wanted_level(j == 0.0 ? INFINITY : 0.5 * eta * a / j, dt, K);
+    if (k > K) {
+      k = K;
+      atomicAdd(&sched[kClamped], 1);
+    }
+    ticks[i] = 0;
+    levels[i] = k;
+    atomicAdd(&hist[k], 1);
+  }
+  __syncthreads();
+  if (threadIdx.x <= K && hist[threadIdx.x]) atomicAdd(&sched[kHist + threadIdx.x], hist[threadIdx.x]);
+}
+
+// t_next from the level histogram and the current tick T = sched[kTCur]; every block derives it alike. Each wave appends
+// its active bodies at one integer atomic on the cursor, so the list order varies from run to run; a body's sums do not
+// depend on its place in the list. Block 0 publishes t_next and n_act. The last workgroup to finish sets the cursor and
+// the finished count back to 0, so every launch starts from a clean cursor.
+__global__ __launch_bounds__(256) void hblock_schedule_kernel(const int* __restrict__ levels, int n, int K,
+                                                              int* __restrict__ sched, int* __restrict__ act) {
+  const int T = sched[kTCur];
+  int t_next = INT_MAX;
+  for (int k = 0; k <= K; ++k)
+    if (sched[kHist + k] > 0) {
+      const int d = 1 << (K - k);
+      t_next = min(t_next, (T / d + 1) * d);
+    }
+  const int thr = max(0, K - __builtin_ctz(t_next));          // active: d_i divides t_next
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  const bool on = i < n && levels[i] >= thr;
+  const unsigned long long mask = __ballot(on);
+  if (mask) {
+    const int lane = threadIdx.x & 63, leader = __ffsll((long long)mask) - 1;
+    int base = 0;
+    if (lane == leader) base = atomicAdd(&sched[kCursor], __popcll(mask));
+    base = __shfl(base, leader);
+    if (on) act[base + __popcll(mask & __lanemask_lt())] = i;
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    int n_act = 0;
+    for (int k = thr; k <= K; ++k) n_act += sched[kHist + k];
+    sched[kTNext] = t_next;
+    sched[kNAct] = n_act;
+  }
+  __syncthreads();                                             // every wave of this workgroup has taken its places
+  if (threadIdx.x == 0) {
+    __threadfence();
+    if (atomicAdd(&sched[kDone], 1) == (int)gridDim.x - 1) {   // the last workgroup: no cursor update can follow
+      sched[kCursor] = 0;
+      sched[kDone] = 0;
+    }
+  }
+}
+
+// posm = {x_p, m}, velp = {v_p, 0} for rows [0, n_pad) (zero padding behind n): every body predicted from its last
+// correction to t_next = sched[0], over Delta_i = (t_next - t_i) dt / 2^K, the constants formed as hermite_dt() forms them.
+__global__ __launch_bounds__(256) void hblock_predict_kernel(const float* __restrict__ pos, const float* __restrict__ vel,
+                                                             const float* __restrict__ acc, const float* __restrict__ jerk,
+                                                             const float* __restrict__ mass, const int* __restrict__ ticks,
+                                                             int n, int n_pad, double dt, double tick,
+                                                             const int* __restrict__ sched, f4* __restrict__ posm,
+                                                             f4* __restrict__ velp) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n_pad) return;
+  f4 pm = {0.f, 0.f, 0.f, 0.f}, vp = {0.f, 0.f, 0.f, 0.f};
+  if (i < n) {
+    const double h = dt * (double)(sched[kTNext] - ticks[i]) * tick;
+    const float c1 = (float)h, c2 = (float)(0.5 * h * h), c3 = (float)(h * h * h / 6.0);
+    float x[3], v[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      x[k] = pos[3 * i + k];
+      v[k] = vel[3 * i + k];
+      const float a = acc[3 * i + k], j = jerk[3 * i + k];
+      x[k] = ((x[k] + v[k] * c1) + a * c2) + j * c3;
+      v[k] = (v[k] + a * c1) + j * c2;
+    }
+    pm = f4{x[0], x[1], x[2], mass[i]};
+    vp = f4{v[0], v[1], v[2], 0.f};
+  }
+  posm[i] = pm;
+  velp[i] = vp;
+}
+
+// The active bodies' corrector: a1 = g * sum of the slabs, j1 likewise, in hermite_correct_kernel's fixed order (wave w of
+// the block sums slabs w, w+4, ... of 64 consecutive list entries; the four partials combined as (p0 + p1) + (p2 + p3)).
+// pos == nullptr: write a1, j1 in list order only (the force on its own). Else, for body i = act[p] with its own step
+// h = dt 2^-k_i: the corrector, then the new level from the Aarseth criterion in fp64 (shrink freely; grow by one level
+// where t_next is a multiple of 2 d_i; deeper than K clamped and counted), t_i = t_next (0 at 2^K), posm = {x1, m}.
+__global__ __launch_bounds__(256) void hblock_correct_kernel(const float* __restrict__ slabs, int n_slabs,
+                                                             const int* __restrict__ act, int n_act, float g, int K,
+                                                             double dt, double tick, double eta, float* pos, float* vel,
+                                                             float* acc, float* jerk, const float* __restrict__ mass,
+                                                             int* __restrict__ ticks, int* __restrict__ levels,
+                                                             int* __restrict__ sched, f4* __restrict__ posm) {
+  __shared__ float part[4][6][64];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int p = blockIdx.x * 64 + lane;
+  float sum[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  if (p < n_act)
+    for (int s = w; s < n_slabs; s += 4)
+#pragma unroll
+      for (int k = 0; k < 6; ++k) sum[k] += slabs[((size_t)s * 6 + k) * n_act + p];
+#pragma unroll
+  for (int k = 0; k < 6; ++k) part[w][k][lane] = sum[k];
+  __syncthreads();
+  if (w != 0 || p >= n_act) return;
+  float a1[3], j1[3];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    a1[k] = g * ((part[0][k][lane] + part[1][k][lane]) + (part[2][k][lane] + part[3][k][lane]));
+    j1[k] = g * ((part[0][k + 3][lane] + part[1][k + 3][lane]) + (part[2][k + 3][lane] + part[3][k + 3][lane]));
+  }
+  if (!pos) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      acc[3 * p + k] = a1[k];
+      jerk[3 * p + k] = j1[k];
+    }
+    return;
+  }
+  const int i = act[p];
+  const int lev = levels[i];
+  const int d = 1 << (K - lev);
+  const double h = dt * (double)d * tick;
+  const float dt_half = (float)(0.5 * h), dt2_twelfth = (float)(h * h / 12.0);
+  float x1[3];
+  double a0d[3], j0d[3];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const float a0 = acc[3 * i + k], j0 = jerk[3 * i + k];
+    const float x = pos[3 * i + k], v = vel[3 * i + k];
+    const float v1 = (v + (a0 + a1[k]) * dt_half) + (j0 - j1[k]) * dt2_twelfth;
+    x1[k] = (x + (v + v1) * dt_half) + (a0 - a1[k]) * dt2_twelfth;
+    vel[3 * i + k] = v1;
+    pos[3 * i + k] = x1[k];
+    acc[3 * i + k] = a1[k];
+    jerk[3 * i + k] = j1[k];
+    a0d[k] = a0;
+    j0d[k] = j0;
+  }
+  posm[i] = f4{x1[0], x1[1], x1[2], mass[i]};
+
+  // Aarseth: a3 = (12 (a0 - a1) + 6 h (j0 + j1)) / h^3, a2(t1) = (-6 (a0 - a1) - h (4 j0 + 2 j1)) / h^2 + h a3
+  double a3[3], a2[3];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const double da = a0d[k] - (double)a1[k];
+    a3[k] = (12.0 * da + 6.0 * h * (j0d[k] + (double)j1[k])) / (h * h * h);
+    a2[k] = (-6.0 * da - h * (4.0 * j0d[k] + 2.0 * (double)j1[k])) / (h * h) + h * a3[k];
+  }
+  const double na1 = norm3(a1[0], a1[1], a1[2]), nj1 = norm3(j1[0], j1[1], j1[2]);
+  const double na2 = norm3(a2[0], a2[1], a2[2]), na3 = norm3(a3[0], a3[1], a3[2]);
+  const double crit = criterion(eta, na1 * na2 + nj1 * nj1, nj1 * na3 + na2 * na2);
+  const int want = wanted_level(crit, dt, K);
+  const int t_next = sched[kTNext];
+  int nl = lev;
+  if (want > lev) {
+    nl = want;
+    if (nl > K) {
+      nl = K;
+      atomicAdd(&sched[kClamped], 1);
+    }
+  } else if (want < lev && (t_next & (2 * d - 1)) == 0) {
+    nl = lev - 1;
+  }
+  if (nl != lev) {
+    atomicSub(&sched[kHist + lev], 1);
+    atomicAdd(&sched[kHist + nl], 1);
+  }
+  levels[i] = nl;
+  const int t_now = t_next == (1 << K) ? 0 : t_next;
+  ticks[i] = t_now;
+  if (p == 0) sched[kTCur] = t_now;
+}
+
+bool misaligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; }
+
+struct ActPlan { int groups, slabs, n_chunks; };
+
+// All targets active: the shared step's plan, nbd_accel_plan(n, n), so that the sums are bit-identical to it. Fewer: the
+// plan of n_act targets, with the slab count raised until groups x slabs reaches kActSlabTarget (at least one chunk per
+// wave, at most kActMaxSlabs).
+ActPlan plan_active(int n, int n_act) {
+  ActPlan p;
+  int cpw = 0;
+  nbd_accel_plan(n, n_act, &p.groups, &p.slabs, &cpw);
+  p.n_chunks = ceil_div(n, kChunk);
+  if (n_act < n && p.groups * p.slabs < kActSlabTarget) {
+    int s = ceil_div(kActSlabTarget, p.groups);
+    const int cap = p.n_chunks / kWaves < kActMaxSlabs ? p.n_chunks / kWaves : kActMaxSlabs;
+    if (s > cap) s = cap;
+    if (s > p.slabs) p.slabs = s;
+  }
+  return p;
+}
+
+size_t act_bytes(int n) { return (size_t)ceil_div(n, 4) * 4 * sizeof(int); }
+
+// what one block step with n_act targets uses of the workspace: the list and its partial sums (O(1): one plan)
+size_t step_bytes(int n, int n_act) {
+  return act_bytes(n) + (n_act > 0 ? (size_t)plan_active(n, n_act).slabs * 6 * n_act * sizeof(float) : 0);
+}
+
+// the largest slabs x n_act any active set of n sources can need
+size_t slab_floats(int n) {
+  size_t most = 0;
+  const int g_all = ceil_div(n, kTgtPerWG);
+  for (int g = 1; g <= g_all; ++g) {
+    const int n_act = g == g_all ? n : g * kTgtPerWG;
+    size_t rows = (size_t)plan_active(n, n_act).slabs * n_act;
+    if (g == g_all && n_act > 1) {                      // a ragged last group below n uses the n_act < n plan
+      const size_t r2 = (size_t)plan_active(n, n_act - 1).slabs * (n_act - 1);
+      if (r2 > rows) rows = r2;
+    }
+    if (rows > most) most = rows;
+  }
+  return most * 6;
+}
+
+inline int status() {
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? 0 : (int)e;
+}
+
+int launch_active(const float* posm, const float* velp, int n, const int* act, int n_act, float eps2, float* slabs,
+                  const ActPlan& p, hipStream_t st) {
+  dim3 grid(p.groups, p.slabs), block(64 * kWaves);
+  const int q = p.n_chunks / (p.slabs * kWaves), r = p.n_chunks % (p.slabs * kWaves);
+  const f4* pm = reinterpret_cast<const f4*>(posm);
+  const f4* vp = reinterpret_cast<const f4*>(velp);
+  if (eps2 < kEps2Masked) accel_jerk_active_kernel<true><<<grid, block, 0, st>>>(pm, vp, n, act, n_act, q, r, eps2, slabs);
+  else accel_jerk_active_kernel<false><<<grid, block, 0, st>>>(pm, vp, n, act, n_act, q, r, eps2, slabs);
+  return status();
+}
+
+bool bad_level(int K) { return K < 0 || K > kMaxLevel; }
+
+int* ws_act(void* ws) { return static_cast<int*>(ws); }
+float* ws_slabs(void* ws, int n) { return reinterpret_cast<float*>(static_cast<char*>(ws) + act_bytes(n)); }
+
+}  // namespace
+
+extern "C" {
+
+size_t nbd_hblock_workspace_bytes(int n) {
+  if (n <= 0) return 0;
+  return act_bytes(n) + slab_floats(n) * sizeof(float);
+}
+
+int nbd_hblock_init_levels(const float* acc, const float* jerk, int n, double dt, double eta, int max_level, int* ticks,
+                           int* levels, int* sched, nbd_stream_t stream) {
+  if (n < 0 || bad_level(max_level) || !(dt > 0.0) || !(eta > 0.0)) return NBD_E_BADARG;
+  if (!sched) return NBD_E_BADARG;
+  if (n == 0) return 0;
+  if (!acc || !jerk || !ticks || !levels) return NBD_E_BADARG;
+  hipStream_t st = (hipStream_t)stream;
+  // T, the cursor and the histogram start from zero; t_next, n_act and the clamp count are left as they are
+  hipError_t e = hipMemsetAsync(sched + kTCur, 0, (NBD_HBLOCK_SCHED_INTS - kTCur) * sizeof(int), st);
+  if (e != hipSuccess) return (int)e;
+  hblock_init_kernel<<<ceil_div(n, 256), 256, 0, st>>>(acc, jerk, n, max_level, dt, eta, ticks, levels, sched);
+  return status();
+}
+
+int nbd_hblock_schedule(const int* levels, int n, int max_level, int* sched, void* workspace, size_t workspace_bytes,
+                        int* host_sched, nbd_stream_t stream) {
+  if (n <= 0 || bad_level(max_level) || !levels || !sched) return NBD_E_BADARG;
+  if (!workspace || misaligned16(workspace) || workspace_bytes < act_bytes(n)) return NBD_E_WORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  hblock_schedule_kernel<<<ceil_div(n, 256), 256, 0, st>>>(levels, n, max_level, sched, ws_act(workspace));
+  int rc = status();
+  if (rc || !host_sched) return rc;
+  hipError_t e = hipMemcpyAsync(host_sched, sched, 4 * sizeof(int), hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  return e == hipSuccess ? 0 : (int)e;
+}
+
+int nbd_hblock_predict_f32(const float* pos, const float* vel, const float* acc, const float* jerk, const float* mass,
+                           const int* ticks, int n, int max_level, double dt, int* sched, float* posm, float* velp,
+                           nbd_stream_t stream) {
+  if (n <= 0 || bad_level(max_level) || !(dt > 0.0)) return NBD_E_BADARG;
+  if (!pos || !vel || !acc || !jerk || !mass || !ticks || !sched || !posm || !velp) return NBD_E_BADARG;
+  if (misaligned16(posm) || misaligned16(velp)) return NBD_E_BADARG;
+  const int n_pad = nbd_posm_padded_len(n);
+  hblock_predict_kernel<<<ceil_div(n_pad, 256), 256, 0, (hipStream_t)stream>>>(
+      pos, vel, acc, jerk, mass, ticks, n, n_pad, dt, ldexp(1.0, -max_level), sched, reinterpret_cast<f4*>(posm),
+      reinterpret_cast<f4*>(velp));
+  return status();
+}
+
+int nbd_hblock_force_f32(const float* posm, const float* velp, int n, int n_act, float softening_sq, void* workspace,
+                         size_t workspace_bytes, nbd_stream_t stream) {
+  if (n <= 0 || n_act < 0 || n_act > n || !posm || !velp || misaligned16(posm) || misaligned16(velp))
+    return NBD_E_BADARG;
+  if (!workspace || misaligned16(workspace) || workspace_bytes < step_bytes(n, n_act)) return NBD_E_WORKSPACE;
+  if (n_act == 0) return 0;
+  return launch_active(posm, velp, n, ws_act(workspace), n_act, softening_sq, ws_slabs(workspace, n),
+                       plan_active(n, n_act), (hipStream_t)stream);
+}
+
+int nbd_hblock_correct_f32(float* pos, float* vel, float* acc, float* jerk, const float* mass, int* ticks, int* levels,
+                           int n, int n_act, int max_level, double dt, double eta, float g_const, int* sched, float* posm,
+                           void* workspace, size_t workspace_bytes, nbd_stream_t stream) {
+  if (n <= 0 || n_act < 0 || n_act > n || bad_level(max_level) || !(dt > 0.0) || !(eta > 0.0)) return NBD_E_BADARG;
+  if (!pos || !vel || !acc || !jerk || !mass || !ticks || !levels || !sched || !posm || misaligned16(posm))
+    return NBD_E_BADARG;
+  if (!workspace || misaligned16(workspace) || workspace_bytes < step_bytes(n, n_act)) return NBD_E_WORKSPACE;
+  if (n_act == 0) return 0;
+  const ActPlan p = plan_active(n, n_act);
+  hblock_correct_kernel<<<ceil_div(n_act, 64), 256, 0, (hipStream_t)stream>>>(
+      ws_slabs(workspace, n), p.slabs, ws_act(workspace), n_act, g_const, max_level, dt, ldexp(1.0, -max_level), eta,
+      pos, vel, acc, jerk, mass, ticks, levels, sched, reinterpret_cast<f4*>(posm));
+  return status();
+}
+
+int nbd_hblock_step_f32(float* pos, float* vel, float* acc, float* jerk, const float* mass, int* ticks, int* levels,
+                        int n, int n_act, int max_level, double dt, double eta, float softening_sq, float g_const,
+                        int* sched, float* posm, float* velp, void* workspace, size_t workspace_bytes,
+                        nbd_stream_t stream) {
+  if (n <= 0 || n_act < 1 || n_act > n || bad_level(max_level) || !(dt > 0.0) || !(eta > 0.0)) return NBD_E_BADARG;
+  if (!velp || misaligned16(velp)) return NBD_E_BADARG;
+  int rc = nbd_hblock_predict_f32(pos, vel, acc, jerk, mass, ticks, n, max_level, dt, sched, posm, velp, stream);
+  if (rc) return rc;
+  rc = nbd_hblock_force_f32(posm, velp, n, n_act, softening_sq, workspace, workspace_bytes, stream);
+  if (rc) return rc;
+  return nbd_hblock_correct_f32(pos, vel, acc, jerk, mass, ticks, levels, n, n_act, max_level, dt, eta, g_const, sched,
+                                posm, workspace, workspace_bytes, stream);
+}
+
+int nbd_accel_jerk_active_f32(const float* posm, const float* velp, int n, const int* act, int n_act,
+                              float softening_sq, float g_const, float* acc_out, float* jerk_out, void* workspace,
+                              size_t workspace_bytes, nbd_stream_t stream) {
+  if (n < 0 || n_act < 0 || n_act > n) return NBD_E_BADARG;
+  if (n_act == 0) return 0;
+  if (!posm || !velp || !act || !acc_out || !jerk_out || misaligned16(posm) || misaligned16(velp)) return NBD_E_BADARG;
+  if (!workspace || misaligned16(workspace) || workspace_bytes < step_bytes(n, n_act)) return NBD_E_WORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  const ActPlan p = plan_active(n, n_act);
+  float* slabs = ws_slabs(workspace, n);
+  int rc = launch_active(posm, velp, n, act, n_act, softening_sq, slabs, p, st);
+  if (rc) return rc;
+  hblock_correct_kernel<<<ceil_div(n_act, 64), 256, 0, st>>>(slabs, p.slabs, act, n_act, g_const, 0, 1.0, 1.0, 1.0,
+                                                             nullptr, nullptr, acc_out, jerk_out, nullptr, nullptr,
+                                                             nullptr, nullptr, nullptr);
+  return status();
+}
+
+}  // extern "C"

@@ -1,0 +1,85 @@
+// hermite_kernels.h -- the acceleration-plus-jerk inner loop shared by the Hermite translation units
+// (direct_hermite.hip: all targets, shared timestep; direct_hermite_block.hip: an active list of targets, block timesteps).
+// The definitions sit in an anonymous namespace: every translation unit that includes this file gets its own inlined copies.
+#pragma once
+#include "direct_kernels.h"
+
+namespace {
+
+// One source against the lane's two targets, index-masked (softening^2 below kEps2Masked): accel_kernel's rule, only
+// j == i and the padding behind n are dropped. ja accumulates w dv, jb accumulates (r.v s^2) w dr; j = ja - 3 jb.
+__device__ __forceinline__ void jerk_pair_masked(const f4 p, const f4 q, const f2 xi, const f2 yi, const f2 zi,
+                                                 const f2 ui, const f2 vi, const f2 wi, const f2 e2, f2* acc, int j,
+                                                 int i0, int i1, int n) {
+  const f2 dx = f2{p.x, p.x} - xi, dy = f2{p.y, p.y} - yi, dz = f2{p.z, p.z} - zi;
+  const f2 du = f2{q.x, q.x} - ui, dv = f2{q.y, q.y} - vi, dw = f2{q.z, q.z} - wi;
+  f2 r2 = __builtin_elementwise_fma(dx, dx, e2);
+  r2 = __builtin_elementwise_fma(dy, dy, r2);
+  r2 = __builtin_elementwise_fma(dz, dz, r2);
+  f2 rv = dx * du;
+  rv = __builtin_elementwise_fma(dy, dv, rv);
+  rv = __builtin_elementwise_fma(dz, dw, rv);
+  f2 s = {__builtin_amdgcn_rsqf(r2.x), __builtin_amdgcn_rsqf(r2.y)};
+  const bool live = j < n;
+  s.x = (live && j != i0) ? s.x : 0.0f;
+  s.y = (live && j != i1) ? s.y : 0.0f;
+  const f2 s2 = s * s;
+  const f2 w = (s2 * s) * f2{p.w, p.w};
+  const f2 c = (rv * s2) * w;
+  acc[0] = __builtin_elementwise_fma(w, dx, acc[0]);
+  acc[1] = __builtin_elementwise_fma(w, dy, acc[1]);
+  acc[2] = __builtin_elementwise_fma(w, dz, acc[2]);
+  acc[3] = __builtin_elementwise_fma(w, du, acc[3]);
+  acc[4] = __builtin_elementwise_fma(w, dv, acc[4]);
+  acc[5] = __builtin_elementwise_fma(w, dw, acc[5]);
+  acc[6] = __builtin_elementwise_fma(c, dx, acc[6]);
+  acc[7] = __builtin_elementwise_fma(c, dy, acc[7]);
+  acc[8] = __builtin_elementwise_fma(c, dz, acc[8]);
+}
+
+// KU sources at once, un-masked: interact_block's shape (the 2 KU v_rsq_f32 issued back to back, the mass splat folded
+// into op_sel by one asm multiply that consumes s^3, never the rsq result itself -- see interact()). Per source and pair
+// of targets: 6 v_pk_add (differences), 5 v_pk_fma + 1 v_pk_mul (r^2, r.v), 2 v_rsq_f32, 5 v_pk_mul (s^2, s^3, w, r.v s^2,
+// c = (r.v s^2) w), 9 v_pk_fma (a, w dv, c dr): 26 packed ops (the factor -3 of the jerk's second sum is applied once, to
+// the finished per-lane sum).
+template <int KU>
+__device__ __forceinline__ void jerk_block(const f4* __restrict__ bp, const f4* __restrict__ bv, const f2 xi,
+                                           const f2 yi, const f2 zi, const f2 ui, const f2 vi, const f2 wi,
+                                           const f2 e2, f2* acc) {
+  f2 zm[KU], dx[KU], dy[KU], dz[KU], du[KU], dv[KU], dw[KU], s[KU], rv[KU];
+#pragma unroll
+  for (int u = 0; u < KU; ++u) {
+    const f4 p = bp[u], q = bv[u];
+    zm[u] = f2{p.z, p.w};
+    dx[u] = f2{p.x, p.x} - xi; dy[u] = f2{p.y, p.y} - yi; dz[u] = f2{p.z, p.z} - zi;
+    du[u] = f2{q.x, q.x} - ui; dv[u] = f2{q.y, q.y} - vi; dw[u] = f2{q.z, q.z} - wi;
+    f2 r2 = __builtin_elementwise_fma(dx[u], dx[u], e2);
+    r2 = __builtin_elementwise_fma(dy[u], dy[u], r2);
+    s[u] = __builtin_elementwise_fma(dz[u], dz[u], r2);
+    f2 t = dx[u] * du[u];
+    t = __builtin_elementwise_fma(dy[u], dv[u], t);
+    rv[u] = __builtin_elementwise_fma(dz[u], dw[u], t);
+  }
+#pragma unroll
+  for (int u = 0; u < KU; ++u) s[u] = f2{__builtin_amdgcn_rsqf(s[u].x), __builtin_amdgcn_rsqf(s[u].y)};
+  __builtin_amdgcn_sched_group_barrier(0x400, 2 * KU, 0);      // 0x400 = TRANS: keep the rsq's together
+#pragma unroll
+  for (int u = 0; u < KU; ++u) {
+    const f2 s2 = s[u] * s[u];
+    const f2 s3 = s2 * s[u];
+    f2 w;
+    asm("v_pk_mul_f32 %0, %1, %2 op_sel:[1,0] op_sel_hi:[1,1]" : "=v"(w) : "v"(zm[u]), "v"(s3));
+    const f2 c = (rv[u] * s2) * w;
+    acc[0] = __builtin_elementwise_fma(w, dx[u], acc[0]);
+    acc[1] = __builtin_elementwise_fma(w, dy[u], acc[1]);
+    acc[2] = __builtin_elementwise_fma(w, dz[u], acc[2]);
+    acc[3] = __builtin_elementwise_fma(w, du[u], acc[3]);
+    acc[4] = __builtin_elementwise_fma(w, dv[u], acc[4]);
+    acc[5] = __builtin_elementwise_fma(w, dw[u], acc[5]);
+    acc[6] = __builtin_elementwise_fma(c, dx[u], acc[6]);
+    acc[7] = __builtin_elementwise_fma(c, dy[u], acc[7]);
+    acc[8] = __builtin_elementwise_fma(c, dz[u], acc[8]);
+  }
+}
+
+}  // namespace

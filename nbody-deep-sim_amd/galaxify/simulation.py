@@ -17,6 +17,9 @@ Second addition: `BatchedSimulator` advances many independent systems with one s
 
 Third addition: `HermiteSimulator`, the shared-timestep 4th-order Hermite predictor-corrector (one acceleration + jerk
 evaluation per step; csrc/direct_hermite.hip).
+
+Fourth addition: `BlockHermiteSimulator`, the same scheme with individual block timesteps inside each output interval
+(csrc/direct_hermite_block.hip).
 """
 from __future__ import annotations
 
@@ -526,6 +529,95 @@ class HermiteSimulator(BaseSimulator):
         direct.hermite_step(self.positions, self.velocities, self.accelerations, self.jerks, new_acc, new_jerk,
                             self.masses, self.dt, self._eps2, self._g, self._posm, self._hws)
         self.accelerations, self.jerks = new_acc, new_jerk
+
+
+class BlockHermiteSimulator(HermiteSimulator):
+    """HermiteSimulator with individual block timesteps (Makino & Aarseth 1992), an extension the reference does not have.
+    `dt` is the output interval and the longest step: one step() advances every body by dt, in 2^max_level ticks. Body i
+    moves with its own step dt 2^-k_i, k_i = levels[i] in [0, max_level], chosen by the Aarseth criterion
+        dt_i = sqrt(eta (|a||a2| + |j|^2) / (|j||a3| + |a2|^2))
+    (levels may deepen at any block step and rise by one where the block allows). On each block step only the bodies that
+    are due are evaluated, against all bodies predicted to that time; every body is back in step at the end of the
+    interval, so run() keeps returning one state per dt. Initial levels (at construction, and after dt, eta or max_level
+    change) come from dt_i = (eta / 2) |a| / |j|.
+
+    Counters (cumulative Python ints): `block_steps`, `pair_interactions` (sum of n_act * n over block steps) and `clamped`
+    (levels the criterion wanted deeper than max_level, NaN criteria included). `accelerations` and `jerks` are updated in
+    place. Eager-only: every block step reads {t_next, n_act} back to the host (csrc/direct_hermite_block.hip). Setting
+    `level_history` to a list records a CPU copy of `levels` after every block step (tests, diagnostics)."""
+
+    MAX_LEVEL_LIMIT = 20
+
+    def __init__(self, *, positions, velocities, masses, g_const: float = 1.0, softening: float = 0.1,
+                 dt: float = 0.01, calc_energy: bool = True, device: str = None, process_group=None,
+                 eta: float = 0.02, max_level: int = 10):
+        if process_group is not None:
+            raise ValueError("BlockHermiteSimulator: there is no range-sharded Hermite step; process_group is not "
+                             "supported")
+        super().__init__(positions=positions, velocities=velocities, masses=masses, g_const=g_const,
+                         softening=softening, dt=dt, calc_energy=calc_energy, device=device)
+        self.eta = eta
+        self.max_level = max_level
+        self.levels = torch.zeros(self.n, dtype=torch.int32, device=self.device)
+        self._ticks = torch.zeros(self.n, dtype=torch.int32, device=self.device)
+        self._sched = torch.zeros(direct.HBLOCK_SCHED_INTS, dtype=torch.int32, device=self.device)
+        self._sched_host = torch.zeros(4, dtype=torch.int32).pin_memory()
+        self._bws = direct.hblock_workspace(max(self.n, 1), self.device)
+        self.block_steps = 0
+        self.pair_interactions = 0
+        self.clamped = 0
+        self.level_history = None
+        self._leveled_for = None
+        self._set_levels()
+
+    def _check_params(self):
+        if not (isinstance(self.max_level, int) and 0 <= self.max_level <= self.MAX_LEVEL_LIMIT):
+            raise ValueError(f"BlockHermiteSimulator: max_level must be an int in [0, {self.MAX_LEVEL_LIMIT}]")
+        if not (self.dt > 0 and self.eta > 0):
+            raise ValueError("BlockHermiteSimulator: dt and eta must be positive")
+
+    def _set_levels(self):
+        self._check_params()
+        self._leveled_for = (self.dt, self.eta, self.max_level)
+        if self.n == 0:
+            return
+        direct.hblock_init_levels(self.accelerations, self.jerks, self.dt, self.eta, self.max_level, self._ticks,
+                                  self.levels, self._sched)
+        self._read_clamped()
+
+    def _read_clamped(self):
+        self._sched_host.copy_(self._sched[:4])
+        self.clamped = int(self._sched_host[2])
+
+    def step(self):
+        """One output interval: block steps until every body is back at tick 2^max_level (at most 2^max_level of them)."""
+        if self.n == 0:
+            return
+        if self._leveled_for != (self.dt, self.eta, self.max_level):
+            self._set_levels()
+        K = self.max_level
+        end = 1 << K
+        host = self._sched_host
+        t_prev = 0
+        for _ in range(end):
+            direct.hblock_schedule(self.levels, K, self._sched, self._bws, host_sched=host)
+            t_next, n_act = int(host[0]), int(host[1])
+            if not (t_prev < t_next <= end and 1 <= n_act <= self.n):
+                raise RuntimeError(f"BlockHermiteSimulator: corrupt schedule (t_next={t_next}, n_act={n_act}, "
+                                   f"previous tick {t_prev})")
+            direct.hblock_step(self.positions, self.velocities, self.accelerations, self.jerks, self.masses,
+                               self._ticks, self.levels, n_act, K, self.dt, self.eta, self._eps2, self._g, self._sched,
+                               self._posm, self._velp, self._bws)
+            self.block_steps += 1
+            self.pair_interactions += n_act * self.n
+            if self.level_history is not None:
+                self.level_history.append(self.levels.cpu())
+            if t_next == end:
+                break
+            t_prev = t_next
+        else:
+            raise RuntimeError(f"BlockHermiteSimulator: interval not finished within {end} block steps")
+        self._read_clamped()
 
 def _per_scene(x, n_scenes: int, name: str) -> list:
     """A scalar, or one value per scene -> list of S Python floats."""

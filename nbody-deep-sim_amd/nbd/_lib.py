@@ -195,6 +195,22 @@ SIGNATURES = {
                                    c_int, c_void_p]),
     "nbd_hermite_step_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
                                      c_double, c_float, c_float, c_void_p, c_void_p, c_size_t, c_void_p]),
+    # --- block-timestep Hermite integrator (csrc/direct_hermite_block.hip)
+    "nbd_hblock_workspace_bytes": (c_size_t, [c_int]),
+    "nbd_hblock_init_levels": (c_int, [c_void_p, c_void_p, c_int, c_double, c_double, c_int, c_void_p, c_void_p,
+                                       c_void_p, c_void_p]),
+    "nbd_hblock_schedule": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
+    "nbd_hblock_predict_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
+                                       c_double, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "nbd_hblock_force_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_float, c_void_p, c_size_t, c_void_p]),
+    "nbd_hblock_correct_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                                       c_int, c_int, c_double, c_double, c_float, c_void_p, c_void_p, c_void_p,
+                                       c_size_t, c_void_p]),
+    "nbd_hblock_step_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
+                                    c_int, c_double, c_double, c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p,
+                                    c_size_t, c_void_p]),
+    "nbd_accel_jerk_active_f32": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_float, c_float, c_void_p,
+                                          c_void_p, c_void_p, c_size_t, c_void_p]),
     # --- generators on the device (csrc/generators.hip)
     "nbd_disk_workspace_bytes": (c_size_t, [c_int]),
     "nbd_disk_from_draws_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_double, c_double, c_double, c_double,

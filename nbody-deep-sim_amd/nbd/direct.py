@@ -326,6 +326,79 @@ def hermite_step(pos, vel, acc_in, jerk_in, acc_out, jerk_out, mass, dt: float, 
             jerk_out.data_ptr(), mass.data_ptr(), n, float(dt), float(softening_sq), float(g_const), posm.data_ptr(),
             workspace.data_ptr(), _nbytes(workspace), _lib.current_stream(pos.device)), "nbd_hermite_step_f32")
 
+
+# ---------------------------------------------------- block-timestep Hermite integrator (csrc/direct_hermite_block.hip)
+HBLOCK_SCHED_INTS = 32          # NBD_HBLOCK_SCHED_INTS: {t_next, n_act, clamped, ...} of the block schedule
+
+
+def hblock_workspace(n: int, device) -> torch.Tensor:
+    """Active list + partial sums of one block step (nbd_hblock_workspace_bytes)."""
+    return alloc_bytes(_lib.lib().nbd_hblock_workspace_bytes(int(n)), device)
+
+
+def hblock_init_levels(acc, jerk, dt: float, eta: float, max_level: int, ticks, levels, sched) -> None:
+    """ticks = 0, levels from dt_i = (eta / 2) |a| / |j| quantised to dt 2^-k (k in [0, max_level]; deeper ones are
+    clamped and counted in sched[2]); starts a new interval."""
+    n = acc.shape[0]
+    _chk(acc, (n, 3), "acc"); _chk(jerk, (n, 3), "jerk")
+    _chk(ticks, (n,), "ticks", torch.int32); _chk(levels, (n,), "levels", torch.int32)
+    _chk(sched, (HBLOCK_SCHED_INTS,), "sched", torch.int32)
+    with _lib.on_device(acc.device):
+        _lib.check(_lib.lib().nbd_hblock_init_levels(
+            acc.data_ptr(), jerk.data_ptr(), n, float(dt), float(eta), int(max_level), ticks.data_ptr(),
+            levels.data_ptr(), sched.data_ptr(), _lib.current_stream(acc.device)), "nbd_hblock_init_levels")
+
+
+def hblock_schedule(levels, max_level: int, sched, workspace, host_sched=None) -> None:
+    """t_next and the active list of the next block step (sched[0], sched[1]; the list into the workspace). host_sched: an
+    int32 CPU tensor of at least 4 elements (pinned is fastest) that receives sched[0..4) after a stream sync."""
+    n = levels.shape[0]
+    _chk(levels, (n,), "levels", torch.int32)
+    _chk(sched, (HBLOCK_SCHED_INTS,), "sched", torch.int32)
+    if host_sched is not None and (host_sched.is_cuda or host_sched.dtype != torch.int32 or host_sched.numel() < 4):
+        raise _lib.NbdError("hblock_schedule: host_sched must be an int32 CPU tensor of 4 elements")
+    with _lib.on_device(levels.device):
+        _lib.check(_lib.lib().nbd_hblock_schedule(
+            levels.data_ptr(), n, int(max_level), sched.data_ptr(), workspace.data_ptr(), _nbytes(workspace),
+            _lib.ptr(host_sched), _lib.current_stream(levels.device)), "nbd_hblock_schedule")
+
+
+def hblock_step(pos, vel, acc, jerk, mass, ticks, levels, n_act: int, max_level: int, dt: float, eta: float,
+                softening_sq: float, g_const: float, sched, posm, velp, workspace) -> None:
+    """Predict all bodies to t_next, evaluate the n_act listed ones, correct and re-level them (three launches). pos, vel,
+    acc, jerk, ticks, levels in place for the active bodies; posm = {x1, m} for them, predicted rows for the rest."""
+    n = pos.shape[0]
+    for t, nm in ((pos, "pos"), (vel, "vel"), (acc, "acc"), (jerk, "jerk")):
+        _chk(t, (n, 3), nm)
+    _chk(mass, (n,), "mass"); _chk(posm, (padded_len(n), 4), "posm"); _chk(velp, (padded_len(n), 4), "velp")
+    _chk(ticks, (n,), "ticks", torch.int32); _chk(levels, (n,), "levels", torch.int32)
+    _chk(sched, (HBLOCK_SCHED_INTS,), "sched", torch.int32)
+    with _lib.on_device(pos.device):
+        _lib.check(_lib.lib().nbd_hblock_step_f32(
+            pos.data_ptr(), vel.data_ptr(), acc.data_ptr(), jerk.data_ptr(), mass.data_ptr(), ticks.data_ptr(),
+            levels.data_ptr(), n, int(n_act), int(max_level), float(dt), float(eta), float(softening_sq),
+            float(g_const), sched.data_ptr(), posm.data_ptr(), velp.data_ptr(), workspace.data_ptr(),
+            _nbytes(workspace), _lib.current_stream(pos.device)), "nbd_hblock_step_f32")
+
+
+def accel_jerk_active(posm, velp, n: int, act, softening_sq: float, g_const: float, workspace=None):
+    """(acc, jerk), each (len(act), 3), of the bodies act (a device int32 list, any order) under all n bodies of posm /
+    velp, in list order. The all-bodies list gives accel_jerk's bits."""
+    _chk(posm, (padded_len(n), 4), "posm"); _chk(velp, (padded_len(n), 4), "velp")
+    _chk(act, None, "act", torch.int32)
+    n_act = act.numel()
+    dev = posm.device
+    acc_out = torch.empty((n_act, 3), dtype=torch.float32, device=dev)
+    jerk_out = torch.empty((n_act, 3), dtype=torch.float32, device=dev)
+    if workspace is None:                       # a given workspace is checked by the entry, against what this call uses
+        workspace = hblock_workspace(n, dev)
+    with _lib.on_device(dev):
+        _lib.check(_lib.lib().nbd_accel_jerk_active_f32(
+            posm.data_ptr(), velp.data_ptr(), n, act.data_ptr(), n_act, float(softening_sq), float(g_const),
+            acc_out.data_ptr(), jerk_out.data_ptr(), workspace.data_ptr(), _nbytes(workspace),
+            _lib.current_stream(dev)), "nbd_accel_jerk_active_f32")
+    return acc_out, jerk_out
+
 # ---------------------------------------------------------------- batched direct integrator (csrc/direct_batch.hip)
 class BatchPlan:
     """The host offsets of an ensemble of scenes and the device work list built from them (nbd_batch_plan /

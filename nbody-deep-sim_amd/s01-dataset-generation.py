@@ -3,8 +3,9 @@
 (src/s01-dataset-generation.py:12-91 flags, :93-104 cartesian product over list-valued flags,
 :108-125 columns, :218-241 one row per particle per step), running the simulation on the MI355X
 through galaxify.simulation. Rows are formatted state by state in native code (the reference builds one
-dict per particle per step and hands it to csv.DictWriter). Extensions: --sim-type plummer (the reference has disk | spiral only) and --integrator hermite
-(4th-order Hermite, galaxify.simulation.HermiteSimulator).
+dict per particle per step and hands it to csv.DictWriter). Extensions: --sim-type plummer (the reference has disk | spiral only), --integrator hermite
+(4th-order Hermite, galaxify.simulation.HermiteSimulator) and --integrator hermite-block (the same scheme with individual
+block timesteps inside each dt, galaxify.simulation.BlockHermiteSimulator with its default eta and max_level).
 
   python s01-dataset-generation.py --integrator leapfrog --n-bodies 3 25 50 --sim-type spiral \\
          --steps 1000 --seed 7 --output data/train/output_file_1.csv
@@ -61,8 +62,8 @@ def write_states(f, scene_id, scene_type, states, masses):
 def build_parser():
     p = argparse.ArgumentParser(description="Generación de dataset de simulaciones de galaxias (MI355X)")
     p.add_argument("--n-bodies", type=int, nargs="+", required=True)
-    p.add_argument("--integrator", type=str, default="leapfrog", choices=["leapfrog", "euler", "hermite"],
-                   required=True)
+    p.add_argument("--integrator", type=str, default="leapfrog", required=True,
+                   choices=["leapfrog", "euler", "hermite", "hermite-block"])
     p.add_argument("--output", type=str, required=True)
     p.add_argument("--sim-type", type=str, nargs="+", choices=["disk", "spiral", "plummer"], default=["disk"])
     p.add_argument("--steps", type=int, default=100)
@@ -99,14 +100,16 @@ def initial_conditions(c):
 def main(argv=None):
     parser = build_parser()
     args = parser.parse_args(argv)
-    if args.batch_scenes and args.integrator == "hermite":
-        parser.error("--integrator hermite cannot be combined with --batch-scenes (BatchedSimulator has no Hermite step)")
+    if args.batch_scenes and args.integrator in ("hermite", "hermite-block"):
+        parser.error(f"--integrator {args.integrator} cannot be combined with --batch-scenes (BatchedSimulator has no "
+                     "Hermite step)")
     params = {k: (v if isinstance(v, list) else [v]) for k, v in vars(args).items()
               if k not in ("output", "device", "batch_scenes")}
     keys = list(params)
     combos = list(itertools.product(*(params[k] for k in keys)))
     print(f"Generando {len(combos)} escenarios -> {args.output}")
-    cls = {"euler": simulation.EulerSimulator, "hermite": simulation.HermiteSimulator}.get(
+    cls = {"euler": simulation.EulerSimulator, "hermite": simulation.HermiteSimulator,
+           "hermite-block": simulation.BlockHermiteSimulator}.get(
         args.integrator, simulation.LeapFrogSimulator)
     with open(args.output, "wb") as f:
         f.write((",".join(FIELDNAMES) + "\r\n").encode())
