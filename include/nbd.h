@@ -233,6 +233,27 @@ int nbd_batch_energies(const int* offsets, int n_scenes, const void* plan, size_
                        const float* vel, const float* softening, const float* g_const, double* out_uk, void* workspace,
                        size_t workspace_bytes, nbd_stream_t stream);
 
+/* Hermite per scene (csrc/direct_batch_hermite.hip): the scheme of nbd_hermite_step_f32 below applied to every scene,
+ * three launches for all scenes, on the plan above. A scene's pos / vel / acc / jerk are bit-identical to
+ * nbd_hermite_step_f32 (nbd_accel_jerk_f32 after nbd_hermite_pack_f32) on that scene alone with the same parameters.
+ * Host-only: the bytes of the Hermite workspace (16-byte aligned: packed velocities float4[posm_rows], then the
+ * acceleration + jerk partial sums); NBD_E_UNSUPPORTED when those sums outgrow the kernels' int offsets. */
+int nbd_batch_hermite_workspace_bytes(const int* offsets, int n_scenes, size_t* bytes);
+/* acc_out, jerk_out (N, 3) of the current state of every scene: a plain pack of (x, v) into posm and the workspace, the
+ * acceleration + jerk, the fixed-order slab sum with G_s. Leaves posm = {x, m}. */
+int nbd_batch_accel_jerk_f32(const int* offsets, int n_scenes, const void* plan, size_t plan_bytes, const float* pos,
+                             const float* vel, const float* mass, const float* softening_sq, const float* g_const,
+                             float* acc_out, float* jerk_out, float* posm, void* workspace, size_t workspace_bytes,
+                             nbd_stream_t stream);
+/* One Hermite step of every scene: predict + pack, acceleration + jerk at the predicted state, slab sum + corrector.
+ * hdt: device fp32 [5][S] table of each scene's (dt, dt/2, dt^2/2, dt^3/6, dt^2/12), each formed from the double dt
+ * and rounded once. Writes pos, vel (in place), acc_out, jerk_out and posm = {x1, m}. acc_in may alias acc_out and
+ * jerk_in may alias jerk_out. */
+int nbd_batch_hermite_step_f32(const int* offsets, int n_scenes, const void* plan, size_t plan_bytes, float* pos,
+                               float* vel, const float* acc_in, const float* jerk_in, float* acc_out, float* jerk_out,
+                               const float* mass, const float* hdt, const float* softening_sq, const float* g_const,
+                               float* posm, void* workspace, size_t workspace_bytes, nbd_stream_t stream);
+
 /* ------------------------------------------------------------ 4th-order Hermite integrator (csrc/direct_hermite.hip)
  * An extension (the reference has Euler and leapfrog only): the shared-timestep predictor-corrector of Makino & Aarseth
  * (1992), one acceleration + jerk evaluation per step, fp32 state. With r_ij = x_j - x_i, v_ij = v_j - v_i and

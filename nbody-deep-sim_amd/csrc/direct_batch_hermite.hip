@@ -1,0 +1,320 @@
+// direct_batch_hermite.hip -- the shared-timestep 4th-order Hermite predictor-corrector of direct_hermite.hip, applied to
+// every scene of an ensemble of independent systems by one set of launches (gfx950). C-ABI: the nbd_batch_hermite_* /
+// nbd_batch_accel_jerk_f32 entries of include/nbd.h; Python: galaxify.simulation.BatchedSimulator(integrator="hermite").
+//
+// The scenes, the packed rows and the work list are those of direct_batch.hip (direct_batch_plan.h, unchanged): one item
+// per (scene, target group of 128, slab), the slab count of a scene being the single-system plan for its size. One step
+// is three launches for all scenes:
+//   predict  : one thread per packed row: posm = {x_p, m}, velp = {v_p, 0} (zeros in each scene's padding), the
+//              arithmetic of hermite_predict_kernel with the scene's own fp32 step constants
+//   evaluate : one workgroup per item: accel_jerk_kernel's body (KU = 2) on the item's scene, masked or not per scene
+//              from its softening^2; unscaled partial sums into float[slabs][6][n_s] at float 2 * ws_off of the slabs
+//   correct  : one workgroup per 64 packed rows (never across scenes): hermite_correct_kernel's fixed-order slab sum
+//              and corrector with the scene's G and constants; posm = {x1, m} for the energies after the step
+// A scene's work, its split of the sources, its slab sum and its arithmetic depend on n_s and its own parameters alone,
+// and each equals the single-system kernel's: its results are bit-identical to nbd_hermite_step_f32 on that scene alone.
+// No atomics, no memsets, no host syncs: deterministic and capturable.
+#include <hip/hip_runtime.h>
+#include <limits.h>
+#include <stdint.h>
+
+#include "../../include/nbd.h"
+#include "direct_batch_plan.h"
+#include "direct_kernels.h"
+#include "hermite_kernels.h"
+
+namespace {
+
+// rows of the per-scene step-constant table hdt[5][S] (each formed in double and rounded once, as hermite_dt())
+enum { kDt = 0, kDtHalf = 1, kDt2Half = 2, kDt3Sixth = 3, kDt2Twelfth = 4 };
+
+// posm[r] = {x_p, m}, velp[r] = {v_p, 0} for every packed row r (zeros behind each scene's last body). acc == nullptr:
+// a plain pack of (x, v).
+__global__ __launch_bounds__(256) void batch_hermite_predict_kernel(const int* __restrict__ row_scene,
+                                                                    const SceneRec* __restrict__ scenes, int n_rows,
+                                                                    const float* __restrict__ pos,
+                                                                    const float* __restrict__ vel,
+                                                                    const float* __restrict__ acc,
+                                                                    const float* __restrict__ jerk,
+                                                                    const float* __restrict__ mass,
+                                                                    const float* __restrict__ hdt, int n_scenes,
+                                                                    f4* __restrict__ posm, f4* __restrict__ velp) {
+  const int r = blockIdx.x * 256 + threadIdx.x;
+  if (r >= n_rows) return;
+  const int s = row_scene[r];
+  const SceneRec sc = load_scene(scenes, s);
+  const int i = r - sc.poff;
+  f4 pm = {0.f, 0.f, 0.f, 0.f}, vp = {0.f, 0.f, 0.f, 0.f};
+  if (i < sc.n) {
+    const int b = sc.off + i;
+    const float dt = acc ? hdt[kDt * n_scenes + s] : 0.f;
+    const float dt2_half = acc ? hdt[kDt2Half * n_scenes + s] : 0.f;
+    const float dt3_sixth = acc ? hdt[kDt3Sixth * n_scenes + s] : 0.f;
+    float x[3], v[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      x[k] = pos[3 * b + k];
+      v[k] = vel[3 * b + k];
+      if (acc) {
+        const float a = acc[3 * b + k], j = jerk[3 * b + k];
+        x[k] = ((x[k] + v[k] * dt) + a * dt2_half) + j * dt3_sixth;
+        v[k] = (v[k] + a * dt) + j * dt2_half;
+      }
+    }
+    pm = f4{x[0], x[1], x[2], mass[b]};
+    vp = f4{v[0], v[1], v[2], 0.f};
+  }
+  posm[r] = pm;
+  velp[r] = vp;
+}
+
+// Acceleration + jerk of targets [128 grp, 128 grp + 128) of one scene (src_p / src_v: its packed rows) against the chunks
+// that wave 4 slab + w owns: accel_jerk_kernel<MASKED, 2>'s body. out: the scene's float[slabs][6][n].
+template <bool MASKED>
+__device__ __forceinline__ void accel_jerk_item(const f4* __restrict__ src_p, const f4* __restrict__ src_v, int n,
+                                                int n_chunks, int slabs, int grp, int slab, float eps2, f4* lds,
+                                                float* __restrict__ out) {
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int t_base = grp * kTgtPerWG;
+  const int i0 = t_base + lane, i1 = t_base + 64 + lane;
+  const f4 t0 = src_p[min(i0, n - 1)], t1 = src_p[min(i1, n - 1)];
+  const f4 u0 = src_v[min(i0, n - 1)], u1 = src_v[min(i1, n - 1)];
+  const f2 xi = {t0.x, t1.x}, yi = {t0.y, t1.y}, zi = {t0.z, t1.z};
+  const f2 ui = {u0.x, u1.x}, vi = {u0.y, u1.y}, wi = {u0.z, u1.z};
+  f2 acc[9];
+#pragma unroll
+  for (int k = 0; k < 9; ++k) acc[k] = f2{0.f, 0.f};
+  f2 e2 = {eps2, eps2};
+  asm volatile("" : "+v"(e2));  // keep eps^2 in VGPRs: an SGPR operand halves v_pk_fma issue
+
+  const int cpw_q = n_chunks / (slabs * kWaves), cpw_r = n_chunks % (slabs * kWaves);
+  const int jw = slab * kWaves + wave;
+  const int c_begin = jw * cpw_q + min(jw, cpw_r), c_end = c_begin + cpw_q + (jw < cpw_r ? 1 : 0);
+  f4* stage = &lds[wave * 4 * kChunk];
+  const f4* p_lane = src_p + lane;
+  const f4* v_lane = src_v + lane;
+  auto fetch = [&](int c, int b) {
+    __builtin_amdgcn_global_load_lds(GPTR(p_lane + (size_t)c * kChunk), LPTR(stage + b * 2 * kChunk), 16, 0, 0);
+    __builtin_amdgcn_global_load_lds(GPTR(v_lane + (size_t)c * kChunk), LPTR(stage + b * 2 * kChunk + kChunk), 16, 0, 0);
+  };
+  if (c_begin < c_end) fetch(c_begin, 0);
+  for (int c = c_begin; c < c_end; ++c) {
+    const int b = (c - c_begin) & 1;
+    if (c + 1 < c_end) {
+      fetch(c + 1, b ^ 1);
+      asm volatile("s_waitcnt vmcnt(2)" ::: "memory");  // chunk c has landed, c+1 (two loads) in flight
+    } else {
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
+    const f4* bp = stage + b * 2 * kChunk;
+    const f4* bv = bp + kChunk;
+    if (MASKED) {
+      const int j0 = c * kChunk;
+#pragma unroll 2
+      for (int j = 0; j < kChunk; ++j)
+        jerk_pair_masked(bp[j], bv[j], xi, yi, zi, ui, vi, wi, e2, acc, j0 + j, i0, i1, n);
+    } else {
+#pragma unroll 1
+      for (int j = 0; j < kChunk; j += 2) jerk_block<2>(bp + j, bv + j, xi, yi, zi, ui, vi, wi, e2, acc);
+    }
+  }
+
+  // j = (w dv) - 3 (r.v s^2 w dr); wavefront partials -> LDS (each wave's own staging, its loads have landed) -> one
+  // coalesced (6 x 128) store per workgroup, the waves added in fixed order
+  constexpr int kPart = 4 * kChunk * 4;
+  float* red = reinterpret_cast<float*>(lds);
+  float* mine = red + wave * kPart;
+#pragma unroll
+  for (int k = 0; k < 6; ++k) {
+    const f2 v = k < 3 ? acc[k] : acc[k] - 3.0f * acc[k + 3];
+    mine[(2 * k) * 64 + lane] = v.x;
+    mine[(2 * k + 1) * 64 + lane] = v.y;
+  }
+  __syncthreads();
+  float* dst = out + (size_t)slab * 6 * n + t_base;
+  const int n_valid = min(kTgtPerWG, n - t_base);
+  for (int o = threadIdx.x; o < 6 * kTgtPerWG; o += 64 * kWaves) {
+    const int comp = o >> 7, lt = o & 127;
+    if (lt >= n_valid) continue;
+    const int idx = (comp * 2 + (lt >> 6)) * 64 + (lt & 63);
+    float sum = red[idx];
+#pragma unroll
+    for (int w = 1; w < kWaves; ++w) sum += red[w * kPart + idx];
+    dst[(size_t)comp * n + lt] = sum;
+  }
+}
+
+// One workgroup per item (s, g, k): the item's scene, its chunk split (cpw_q / cpw_r of the scene's own plan) and its
+// slab. softening^2 < kEps2Masked takes the index-masked loop for the whole scene; the branch is taken once, at the top,
+// so that each path keeps its own registers. out: the scene's float[slabs][6][n] at ws + 2 * ws_off (the leapfrog
+// plan's float[slabs][n][3] offsets, doubled).
+__global__ __launch_bounds__(64 * kWaves, 5) void batch_accel_jerk_kernel(const f4* __restrict__ posm,
+                                                                          const f4* __restrict__ velp,
+                                                                          const int4* __restrict__ items,
+                                                                          const SceneRec* __restrict__ scenes,
+                                                                          const float* __restrict__ eps2_s,
+                                                                          float* __restrict__ ws) {
+  // [wave][buffer][pos | vel][64] staging; after its last chunk a wave puts its [12][64] partials into its own part
+  __shared__ f4 lds[kWaves * 4 * kChunk];
+  const int4 it = items[blockIdx.x];
+  const int s = __builtin_amdgcn_readfirstlane(it.x), grp = __builtin_amdgcn_readfirstlane(it.y);
+  const int slab = __builtin_amdgcn_readfirstlane(it.z);
+  const SceneRec sc = load_scene(scenes, s);
+  const int n = __builtin_amdgcn_readfirstlane(sc.n);
+  const int n_chunks = __builtin_amdgcn_readfirstlane(sc.n_chunks), slabs = __builtin_amdgcn_readfirstlane(sc.slabs);
+  const int poff = __builtin_amdgcn_readfirstlane(sc.poff);
+  float* out = ws + 2 * (size_t)sc.ws_off;
+  const float eps2 = eps2_s[s];
+  if (eps2 < kEps2Masked)
+    accel_jerk_item<true>(posm + poff, velp + poff, n, n_chunks, slabs, grp, slab, eps2, lds, out);
+  else
+    accel_jerk_item<false>(posm + poff, velp + poff, n, n_chunks, slabs, grp, slab, eps2, lds, out);
+}
+
+// One workgroup per 64 packed rows (a scene's rows are whole chunks of 64, so a block never spans two scenes):
+// hermite_correct_kernel's fixed order -- wave w sums slabs w, w+4, ..., the partials combined as (p0 + p1) + (p2 + p3)
+// -- then a1 = G_s sum, j1 = G_s sum. pos == nullptr: write a1, j1 only. Else the corrector: reads a0, j0 (acc_in /
+// jerk_in may alias acc_out / jerk_out: each element is read before it is written, by the same thread), x, v; writes
+// x1, v1, a1, j1 and posm = {x1, m}.
+__global__ __launch_bounds__(256) void batch_hermite_correct_kernel(const int* __restrict__ row_scene,
+                                                                    const SceneRec* __restrict__ scenes,
+                                                                    const float* __restrict__ ws,
+                                                                    const float* __restrict__ g_s,
+                                                                    const float* __restrict__ hdt, int n_scenes,
+                                                                    float* pos, float* vel, const float* acc_in,
+                                                                    const float* jerk_in, float* acc_out,
+                                                                    float* jerk_out, const float* __restrict__ mass,
+                                                                    f4* __restrict__ posm) {
+  __shared__ float part[4][6][64];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int r0 = blockIdx.x * 64;
+  const int s = row_scene[r0];
+  const SceneRec sc = load_scene(scenes, s);
+  const int n = sc.n;
+  const int i = r0 - sc.poff + lane;
+  const float* slabs = ws + 2 * (size_t)sc.ws_off;
+  float sum[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  if (i < n)
+    for (int k = w; k < sc.slabs; k += 4)
+#pragma unroll
+      for (int c = 0; c < 6; ++c) sum[c] += slabs[((size_t)k * 6 + c) * n + i];
+#pragma unroll
+  for (int c = 0; c < 6; ++c) part[w][c][lane] = sum[c];
+  __syncthreads();
+  if (w != 0 || i >= n) return;
+  const float g = g_s[s];
+  float a1[3], j1[3];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    a1[k] = g * ((part[0][k][lane] + part[1][k][lane]) + (part[2][k][lane] + part[3][k][lane]));
+    j1[k] = g * ((part[0][k + 3][lane] + part[1][k + 3][lane]) + (part[2][k + 3][lane] + part[3][k + 3][lane]));
+  }
+  const size_t b = (size_t)sc.off + i;
+  if (pos) {
+    const float dt_half = hdt[kDtHalf * n_scenes + s], dt2_twelfth = hdt[kDt2Twelfth * n_scenes + s];
+    float x1[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      const float a0 = acc_in[3 * b + k], j0 = jerk_in[3 * b + k];
+      float x = pos[3 * b + k], v = vel[3 * b + k];
+      hermite_correct(x, v, a0, j0, a1[k], j1[k], dt_half, dt2_twelfth);
+      vel[3 * b + k] = v;
+      pos[3 * b + k] = x1[k] = x;
+    }
+    posm[r0 + lane] = f4{x1[0], x1[1], x1[2], mass[b]};
+  }
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    acc_out[3 * b + k] = a1[k];
+    jerk_out[3 * b + k] = j1[k];
+  }
+}
+
+// workspace: velp float4[posm_rows] | slabs fp32[2 * ws_floats] (16-byte aligned: posm_rows * 16 bytes come first)
+size_t hws_slab_offset(const BatchTotals& t) { return (size_t)t.n_rows * sizeof(f4); }
+size_t hws_bytes_of(const BatchTotals& t) { return hws_slab_offset(t) + (size_t)(2 * t.ws_floats) * sizeof(float); }
+// The slabs of a scene start at float 2 * ws_off; the whole slab area must stay within the int range the plan's own
+// offsets live in.
+bool hws_fits(const BatchTotals& t) { return 2 * t.ws_floats <= (int64_t)INT_MAX; }
+
+int launch_predict(const DevPlan& d, const BatchTotals& t, const float* pos, const float* vel, const float* acc,
+                   const float* jerk, const float* mass, const float* hdt, int n_scenes, float* posm, void* workspace,
+                   hipStream_t st) {
+  batch_hermite_predict_kernel<<<bceil_div(t.n_rows, 256), 256, 0, st>>>(
+      d.row_scene, d.scenes, t.n_rows, pos, vel, acc, jerk, mass, hdt, n_scenes, reinterpret_cast<f4*>(posm),
+      static_cast<f4*>(workspace));
+  return bcheck();
+}
+
+// the force of every scene at posm / velp, then the slab sum (+ the corrector when pos is given)
+int launch_force_correct(const DevPlan& d, const BatchTotals& t, float* posm, const float* eps2, const float* g,
+                         const float* hdt, int n_scenes, float* pos, float* vel, const float* acc_in,
+                         const float* jerk_in, float* acc_out, float* jerk_out, const float* mass, void* workspace,
+                         hipStream_t st) {
+  const f4* velp = static_cast<const f4*>(workspace);
+  float* slabs = reinterpret_cast<float*>(static_cast<char*>(workspace) + hws_slab_offset(t));
+  batch_accel_jerk_kernel<<<t.n_items, 64 * kWaves, 0, st>>>(reinterpret_cast<const f4*>(posm), velp, d.items,
+                                                             d.scenes, eps2, slabs);
+  int rc = bcheck();
+  if (rc) return rc;
+  batch_hermite_correct_kernel<<<t.n_rows / kChunk, 256, 0, st>>>(d.row_scene, d.scenes, slabs, g, hdt, n_scenes,
+                                                                   pos, vel, acc_in, jerk_in, acc_out, jerk_out, mass,
+                                                                   reinterpret_cast<f4*>(posm));
+  return bcheck();
+}
+
+}  // namespace
+
+extern "C" {
+
+int nbd_batch_hermite_workspace_bytes(const int* offsets, int n_scenes, size_t* bytes) {
+  BatchTotals t;
+  const int rc = batch_totals(offsets, n_scenes, &t);
+  if (rc) return rc;
+  if (!bytes) return NBD_E_BADARG;
+  if (!hws_fits(t)) return NBD_E_UNSUPPORTED;
+  *bytes = hws_bytes_of(t);
+  return 0;
+}
+
+int nbd_batch_accel_jerk_f32(const int* offsets, int n_scenes, const void* plan, size_t plan_bytes, const float* pos,
+                             const float* vel, const float* mass, const float* softening_sq, const float* g_const,
+                             float* acc_out, float* jerk_out, float* posm, void* workspace, size_t workspace_bytes,
+                             nbd_stream_t stream) {
+  BatchTotals t;
+  int rc = batch_prologue(offsets, n_scenes, plan, plan_bytes, &t);
+  if (rc) return rc;
+  if (!hws_fits(t)) return NBD_E_UNSUPPORTED;
+  if (t.n_total == 0) return 0;
+  if (!pos || !vel || !mass || !softening_sq || !g_const || !acc_out || !jerk_out || !posm || bmisaligned16(posm))
+    return NBD_E_BADARG;
+  if (!workspace || bmisaligned16(workspace) || workspace_bytes < hws_bytes_of(t)) return NBD_E_WORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  const DevPlan d = dev_plan(plan, t);
+  if ((rc = launch_predict(d, t, pos, vel, nullptr, nullptr, mass, nullptr, n_scenes, posm, workspace, st))) return rc;
+  return launch_force_correct(d, t, posm, softening_sq, g_const, nullptr, n_scenes, nullptr, nullptr, nullptr, nullptr,
+                              acc_out, jerk_out, nullptr, workspace, st);
+}
+
+int nbd_batch_hermite_step_f32(const int* offsets, int n_scenes, const void* plan, size_t plan_bytes, float* pos,
+                               float* vel, const float* acc_in, const float* jerk_in, float* acc_out, float* jerk_out,
+                               const float* mass, const float* hdt, const float* softening_sq, const float* g_const,
+                               float* posm, void* workspace, size_t workspace_bytes, nbd_stream_t stream) {
+  BatchTotals t;
+  int rc = batch_prologue(offsets, n_scenes, plan, plan_bytes, &t);
+  if (rc) return rc;
+  if (!hws_fits(t)) return NBD_E_UNSUPPORTED;
+  if (t.n_total == 0) return 0;
+  if (!pos || !vel || !acc_in || !jerk_in || !acc_out || !jerk_out || !mass || !hdt || !softening_sq || !g_const ||
+      !posm || bmisaligned16(posm))
+    return NBD_E_BADARG;
+  if (!workspace || bmisaligned16(workspace) || workspace_bytes < hws_bytes_of(t)) return NBD_E_WORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  const DevPlan d = dev_plan(plan, t);
+  if ((rc = launch_predict(d, t, pos, vel, acc_in, jerk_in, mass, hdt, n_scenes, posm, workspace, st))) return rc;
+  return launch_force_correct(d, t, posm, softening_sq, g_const, hdt, n_scenes, pos, vel, acc_in, jerk_in, acc_out,
+                              jerk_out, mass, workspace, st);
+}
+
+}  // extern "C"

@@ -170,11 +170,10 @@ __global__ __launch_bounds__(256) void hermite_correct_kernel(const float* __res
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
       const float a0 = acc_in[3 * i + k], j0 = jerk_in[3 * i + k];
-      const float x = pos[3 * i + k], v = vel[3 * i + k];
-      const float v1 = (v + (a0 + a1[k]) * h.dt_half) + (j0 - j1[k]) * h.dt2_twelfth;
-      x1[k] = (x + (v + v1) * h.dt_half) + (a0 - a1[k]) * h.dt2_twelfth;
-      vel[3 * i + k] = v1;
-      pos[3 * i + k] = x1[k];
+      float x = pos[3 * i + k], v = vel[3 * i + k];
+      hermite_correct(x, v, a0, j0, a1[k], j1[k], h.dt_half, h.dt2_twelfth);
+      vel[3 * i + k] = v;
+      pos[3 * i + k] = x1[k] = x;
     }
     posm[i] = f4{x1[0], x1[1], x1[2], mass[i]};
   }

@@ -1,5 +1,6 @@
-// hermite_kernels.h -- the acceleration-plus-jerk inner loop shared by the Hermite translation units
-// (direct_hermite.hip: all targets, shared timestep; direct_hermite_block.hip: an active list of targets, block timesteps).
+// hermite_kernels.h -- the acceleration-plus-jerk inner loop and the corrector arithmetic shared by the Hermite
+// translation units (direct_hermite.hip: all targets, shared timestep; direct_hermite_block.hip: an active list of
+// targets, block timesteps; direct_batch_hermite.hip: many independent systems, shared timestep per system).
 // The definitions sit in an anonymous namespace: every translation unit that includes this file gets its own inlined copies.
 #pragma once
 #include "direct_kernels.h"
@@ -80,6 +81,15 @@ __device__ __forceinline__ void jerk_block(const f4* __restrict__ bp, const f4* 
     acc[7] = __builtin_elementwise_fma(c, dy[u], acc[7]);
     acc[8] = __builtin_elementwise_fma(c, dz[u], acc[8]);
   }
+}
+
+// One component of the shared-timestep corrector, each product and sum rounded on its own (the build has
+// -ffp-contract=off): v1 = v + (a0 + a1) dt/2 + (j0 - j1) dt^2/12, x1 = x + (v + v1) dt/2 + (a0 - a1) dt^2/12.
+__device__ __forceinline__ void hermite_correct(float& x, float& v, const float a0, const float j0, const float a1,
+                                                const float j1, const float dt_half, const float dt2_twelfth) {
+  const float v1 = (v + (a0 + a1) * dt_half) + (j0 - j1) * dt2_twelfth;
+  x = (x + (v + v1) * dt_half) + (a0 - a1) * dt2_twelfth;
+  v = v1;
 }
 
 }  // namespace

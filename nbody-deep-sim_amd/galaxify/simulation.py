@@ -637,15 +637,21 @@ class BatchedSimulator:
     and dt (scalars, or one value per scene). The scenes are stored back to back: `positions`, `velocities`,
     `accelerations` are (N_total, 3) and `masses` (N_total,), scene s owning rows offsets[s]:offsets[s + 1];
     `scene(s)` returns views of them. A scene's results do not depend on its companions or its position in the batch
-    (bit for bit). There is no CPU path and no multi-GPU sharding: the batch runs on one device."""
+    (bit for bit). There is no CPU path and no multi-GPU sharding: the batch runs on one device.
+
+    integrator="hermite" is HermiteSimulator's shared-timestep predictor-corrector on every scene
+    (csrc/direct_batch_hermite.hip): `jerks` (N_total, 3) is public next to `accelerations`, both rebound by step(), and
+    each scene's positions, velocities, accelerations and jerks are bit-identical to a HermiteSimulator of that scene
+    alone. `jerks` is None for leapfrog and Euler. The integrator may switch between leapfrog and Euler after
+    construction, but not into or out of Hermite."""
 
     GRAPH_RUN_CHUNK = 32
     RING_BYTES = 64 << 20                                # the eager run()'s staging cap, per chunk of states
 
     def __init__(self, *, systems, integrator: str = "leapfrog", g_const=1.0, softening=0.1, dt=0.01,
                  calc_energy: bool = True, device: str = None):
-        if integrator not in ("leapfrog", "euler"):
-            raise ValueError("integrator must be 'leapfrog' or 'euler'")
+        if integrator not in ("leapfrog", "euler", "hermite"):
+            raise ValueError("integrator must be 'leapfrog', 'euler' or 'hermite'")
         self.device = _resolve_device(device)
         _lib.lib()
         systems = list(systems)
@@ -671,15 +677,22 @@ class BatchedSimulator:
         self.g_const, self.softening, self.dt = g_const, softening, dt
         self._posm = self._plan.alloc_posm()
         self._ws = self._plan.workspace()
-        self._params = torch.zeros((5, self.n_scenes), dtype=torch.float32, device=self.device)
+        self._params = torch.zeros((10, self.n_scenes), dtype=torch.float32, device=self.device)
         self._params_key = None
-        self.accelerations = self.compute_accelerations()
+        self._hermite = integrator == "hermite"          # fixed at construction: the state carries jerks or not
+        self._hws = None
+        self.jerks = None
+        if self._hermite:
+            self.accelerations, self.jerks = self.compute_accelerations_and_jerks()
+        else:
+            self.accelerations = self.compute_accelerations()
 
     # ------------------------------------------------------------------ per-scene parameters
     def _sync_params(self):
         """Rows g, eps^2, eps, dt / 2, dt of the device parameter table, as torch forms the fp32 scalars from the
-        Python doubles (simulation.py:82,88,164); rewritten IN PLACE when an attribute changed (captured graphs keep
-        reading the same buffer). Returns the per-scene values (the graph cache key)."""
+        Python doubles (simulation.py:82,88,164), then the Hermite step constants dt, dt/2, dt^2/2, dt^3/6, dt^2/12, each
+        formed in double and rounded once (as HermiteSimulator's); rewritten IN PLACE when an attribute changed
+        (captured graphs keep reading the same buffer). Returns the per-scene values (the graph cache key)."""
         S = self.n_scenes
         g = _per_scene(self.g_const, S, "g_const")
         eps = _per_scene(self.softening, S, "softening")
@@ -687,7 +700,9 @@ class BatchedSimulator:
         key = (tuple(g), tuple(eps), tuple(dt))
         if key != self._params_key:
             rows = [[direct.f32(x) for x in g], [direct.f32(e ** 2) for e in eps], [direct.f32(e) for e in eps],
-                    [direct.f32(0.5 * d) for d in dt], [direct.f32(d) for d in dt]]
+                    [direct.f32(0.5 * d) for d in dt], [direct.f32(d) for d in dt],
+                    [direct.f32(d) for d in dt], [direct.f32(0.5 * d) for d in dt], [direct.f32(0.5 * d * d) for d in dt],
+                    [direct.f32(d * d * d / 6.0) for d in dt], [direct.f32(d * d / 12.0) for d in dt]]
             self._params.copy_(torch.tensor(rows, dtype=torch.float32))
             self._params_key = key
         return key
@@ -709,6 +724,26 @@ class BatchedSimulator:
         direct.batch_accel(self._plan, self.positions, self.masses, P[1], P[0], acc, self._posm, self._ws)
         return acc
 
+    def _hermite_ws(self) -> torch.Tensor:
+        if self._hws is None:
+            self._hws = self._plan.hermite_workspace()
+        return self._hws
+
+    def compute_accelerations_and_jerks(self):
+        """(a, j) of every scene's current state as new (N_total, 3) tensors (HermiteSimulator's per scene)."""
+        self._sync_params()
+        acc = torch.zeros((self.n, 3), dtype=torch.float32, device=self.device)
+        jerk = torch.zeros((self.n, 3), dtype=torch.float32, device=self.device)
+        P = self._params
+        direct.batch_accel_jerk(self._plan, self.positions, self.velocities, self.masses, P[1], P[0], acc, jerk,
+                                self._posm, self._hermite_ws())
+        return acc, jerk
+
+    def _check_integrator(self):
+        if (self.integrator == "hermite") != self._hermite:
+            raise ValueError("BatchedSimulator: the integrator cannot change into or out of 'hermite' after "
+                             "construction (the state carries jerks only for Hermite); build a new simulator")
+
     def _energies_into(self, out_uk):
         P = self._params
         direct.batch_energies(self._plan, self._posm, self.velocities, P[2], P[0], out_uk, self._ws)
@@ -722,9 +757,12 @@ class BatchedSimulator:
         uk = uk.cpu()
         return uk[:, 0].tolist(), uk[:, 1].tolist()
 
-    def _step_into(self, acc_in, acc_out):
+    def _step_into(self, acc_in, acc_out, jerk_in=None, jerk_out=None):
         P = self._params
-        if self.integrator == "leapfrog":
+        if self._hermite:
+            direct.batch_hermite_step(self._plan, self.positions, self.velocities, acc_in, jerk_in, acc_out, jerk_out,
+                                      self.masses, P[5:10], P[1], P[0], self._posm, self._hws)
+        elif self.integrator == "leapfrog":
             direct.batch_leapfrog_step(self._plan, self.positions, self.velocities, acc_in, acc_out, self.masses,
                                        P[3], P[4], P[1], P[0], self._posm, self._ws)
         else:
@@ -732,11 +770,18 @@ class BatchedSimulator:
                                     P[0], self._posm, self._ws)
 
     def step(self):
-        """One step of every scene; positions and velocities in place, `accelerations` rebound to a new tensor."""
+        """One step of every scene; positions and velocities in place, `accelerations` (and for Hermite `jerks`)
+        rebound to new tensors."""
+        self._check_integrator()
         if self.n == 0:
             return
         self._sync_params()
         new_acc = torch.empty_like(self.accelerations)
+        if self._hermite:
+            new_jerk = torch.empty_like(self.jerks)
+            self._step_into(self.accelerations, new_acc, self.jerks, new_jerk)
+            self.accelerations, self.jerks = new_acc, new_jerk
+            return
         self._step_into(self.accelerations, new_acc)
         self.accelerations = new_acc
 
@@ -773,6 +818,7 @@ class BatchedSimulator:
         out = [[] for _ in range(self.n_scenes)]
         if steps <= 0:
             return out
+        self._check_integrator()
         if self.n == 0:
             uk = (0.0, 0.0) if self.calc_energy else (None, None)
             empty = torch.zeros((0, 3), dtype=torch.float32)
@@ -787,12 +833,16 @@ class BatchedSimulator:
             self._acc_g = getattr(self, "_acc_g", None)
             if self._acc_g is None:
                 self._acc_g = torch.empty((self.n, 3), dtype=torch.float32, device=self.device)
+            if self._hermite and getattr(self, "_jerk_g", None) is None:     # the jerks' stable buffer, beside _acc_g
+                self._jerk_g = torch.empty((self.n, 3), dtype=torch.float32, device=self.device)
             first = True
             while steps - done >= 8:
                 m = big if steps - done >= big else 8
                 graph, buf, ring_b = self._chunk_graph(m)
                 if first:                                    # a caller's handle on the old accelerations stays valid
                     self._acc_g.copy_(self.accelerations)
+                    if self._hermite:
+                        self._jerk_g.copy_(self.jerks)
                     first = False
                 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 e0.record()
@@ -803,6 +853,8 @@ class BatchedSimulator:
                 done += m
             if not first:
                 self.accelerations = self._acc_g.clone()
+                if self._hermite:
+                    self.jerks = self._jerk_g.clone()
         while done < steps:                                  # eager: the tail, or everything
             m = min(self._chunk_len(), steps - done)
             buf, ring, uk, ring_b = self._chunk_buffers(m)
@@ -825,8 +877,10 @@ class BatchedSimulator:
         """(graph, buffer, ring offset) for a chunk of m steps; captured once per key and kept."""
         cache = self.__dict__.setdefault("_run_graphs", {})
         # a graph bakes in buffer addresses and scalar arguments: anything the caller may have changed is in the key
+        jerk_g = self._jerk_g if self._hermite else None
         key = (m, self.positions.data_ptr(), self.velocities.data_ptr(), self.masses.data_ptr(), self._acc_g.data_ptr(),
-               self._params_key, bool(self.calc_energy), self.integrator)
+               jerk_g.data_ptr() if jerk_g is not None else None, self._params_key, bool(self.calc_energy),
+               self.integrator)
         if key in cache:
             return cache[key]
         if len(cache) > 8:
@@ -835,22 +889,28 @@ class BatchedSimulator:
 
         def body(count=m):
             for s_ in range(count):
-                self._step_into(self._acc_g, self._acc_g)
+                self._step_into(self._acc_g, self._acc_g, jerk_g, jerk_g)
                 if self.calc_energy:
                     self._energies_into(uk[s_])
                 direct.snapshot(self.positions, self.velocities, self._acc_g, ring[s_])
         dev = self.device
         # capture on a side stream; the state is saved and restored around the (executed) warm-up pass
-        keep = (self.positions.clone(), self.velocities.clone(), self._acc_g.clone())
+        keep = (self.positions.clone(), self.velocities.clone(), self._acc_g.clone(),
+                jerk_g.clone() if jerk_g is not None else None)
+
+        def restore():
+            self.positions.copy_(keep[0]); self.velocities.copy_(keep[1]); self._acc_g.copy_(keep[2])
+            if jerk_g is not None:
+                jerk_g.copy_(keep[3])
         side = torch.cuda.Stream(device=dev)
         side.wait_stream(torch.cuda.current_stream(dev))
         with torch.cuda.stream(side):
             body(1)
         torch.cuda.current_stream(dev).wait_stream(side)
-        self.positions.copy_(keep[0]); self.velocities.copy_(keep[1]); self._acc_g.copy_(keep[2])
+        restore()
         graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(graph):
             body()
-        self.positions.copy_(keep[0]); self.velocities.copy_(keep[1]); self._acc_g.copy_(keep[2])
+        restore()
         cache[key] = (graph, buf, ring_b)
         return cache[key]

@@ -187,6 +187,13 @@ SIGNATURES = {
                                          c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "nbd_batch_energies": (c_int, [c_void_p, c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                    c_void_p, c_size_t, c_void_p]),
+    # --- Hermite per scene (csrc/direct_batch_hermite.hip)
+    "nbd_batch_hermite_workspace_bytes": (c_int, [c_void_p, c_int, POINTER(c_size_t)]),
+    "nbd_batch_accel_jerk_f32": (c_int, [c_void_p, c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p,
+                                         c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "nbd_batch_hermite_step_f32": (c_int, [c_void_p, c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p,
+                                           c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                           c_size_t, c_void_p]),
     # --- 4th-order Hermite integrator (csrc/direct_hermite.hip)
     "nbd_hermite_workspace_bytes": (c_size_t, [c_int]),
     "nbd_hermite_pack_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_double, c_void_p,

@@ -435,6 +435,19 @@ class BatchPlan:
     def alloc_posm(self) -> torch.Tensor:
         return torch.zeros((max(self.posm_rows, 1), 4), dtype=torch.float32, device=self.device)
 
+    def hermite_workspace_bytes(self) -> int:
+        if getattr(self, "_hws_bytes", None) is None:          # asked on every step: one host query per plan
+            nb = ctypes.c_size_t()
+            _lib.check(_lib.lib().nbd_batch_hermite_workspace_bytes(self._off(), self.n_scenes, nb),
+                       "nbd_batch_hermite_workspace_bytes")
+            self._hws_bytes = nb.value
+        return self._hws_bytes
+
+    def hermite_workspace(self) -> torch.Tensor:
+        """Packed velocities + acceleration-and-jerk partial sums of the batch_hermite_* calls (the energies keep using
+        workspace())."""
+        return alloc_bytes(self.hermite_workspace_bytes(), self.device)
+
     def check_state(self, posm, ws, *arrays):
         n = self.n_total
         for t, nm in arrays:
@@ -496,3 +509,38 @@ def batch_energies(plan: BatchPlan, posm, vel, soft, g, out_uk, ws) -> torch.Ten
             *plan.head(), posm.data_ptr(), vel.data_ptr(), _param(soft, plan, "softening"), _param(g, plan, "g_const"),
             out_uk.data_ptr(), ws.data_ptr(), _nbytes(ws), _lib.current_stream(vel.device)), "nbd_batch_energies")
     return out_uk
+
+
+# ---------------------------------------------------------------- Hermite per scene (csrc/direct_batch_hermite.hip)
+def _hws(plan: BatchPlan, ws) -> None:
+    if _nbytes(ws) < plan.hermite_workspace_bytes():
+        raise _lib.NbdError("batch Hermite workspace too small")
+
+
+def batch_accel_jerk(plan: BatchPlan, pos, vel, mass, eps2, g, acc_out, jerk_out, posm, hws) -> None:
+    """acc_out, jerk_out = the acceleration and jerk of every scene's current state (a plain pack first; leaves
+    posm = {x, m}). eps2, g: device fp32 (S,); hws: plan.hermite_workspace()."""
+    plan.check_state(posm, None, (pos, "pos"), (vel, "vel"), (mass, "mass"), (acc_out, "acc_out"),
+                     (jerk_out, "jerk_out"))
+    _hws(plan, hws)
+    with _lib.on_device(pos.device):
+        _lib.check(_lib.lib().nbd_batch_accel_jerk_f32(
+            *plan.head(), pos.data_ptr(), vel.data_ptr(), mass.data_ptr(), _param(eps2, plan, "softening_sq"),
+            _param(g, plan, "g_const"), acc_out.data_ptr(), jerk_out.data_ptr(), posm.data_ptr(), hws.data_ptr(),
+            _nbytes(hws), _lib.current_stream(pos.device)), "nbd_batch_accel_jerk_f32")
+
+
+def batch_hermite_step(plan: BatchPlan, pos, vel, acc_in, jerk_in, acc_out, jerk_out, mass, hdt, eps2, g, posm,
+                       hws) -> None:
+    """One Hermite step of every scene: pos, vel in place; acc_out, jerk_out (may be acc_in, jerk_in); posm = {x1, m}.
+    hdt: device fp32 (5, S) rows dt, dt/2, dt^2/2, dt^3/6, dt^2/12, each formed from the double dt and rounded once."""
+    plan.check_state(posm, None, (pos, "pos"), (vel, "vel"), (acc_in, "acc_in"), (jerk_in, "jerk_in"),
+                     (acc_out, "acc_out"), (jerk_out, "jerk_out"), (mass, "mass"))
+    _chk(hdt, (5, plan.n_scenes), "hdt")
+    _hws(plan, hws)
+    with _lib.on_device(pos.device):
+        _lib.check(_lib.lib().nbd_batch_hermite_step_f32(
+            *plan.head(), pos.data_ptr(), vel.data_ptr(), acc_in.data_ptr(), jerk_in.data_ptr(), acc_out.data_ptr(),
+            jerk_out.data_ptr(), mass.data_ptr(), hdt.data_ptr(), _param(eps2, plan, "softening_sq"),
+            _param(g, plan, "g_const"), posm.data_ptr(), hws.data_ptr(), _nbytes(hws), _lib.current_stream(pos.device)),
+            "nbd_batch_hermite_step_f32")

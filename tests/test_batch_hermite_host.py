@@ -1,0 +1,164 @@
+"""Batched Hermite without a GPU: the new C-ABI entries reject bad arguments before anything reaches the device, the
+workspace query agrees with the plan, and the segmented acceleration-plus-jerk kernel (gfx950 assembly, hipcc
+cross-compiles) keeps the packed-fp32 inner loop of the one-system kernel with no scratch."""
+import ctypes
+import os
+import re
+import subprocess
+from collections import Counter
+
+import numpy as np
+import pytest
+
+from conftest import ROOT
+from nbd import _lib
+
+SRC = os.path.join(ROOT, "nbody-deep-sim_amd", "csrc", "direct_batch_hermite.hip")
+FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-ffp-contract=off", "--cuda-device-only", "-S"]
+E_BADARG, E_WORKSPACE = -1, -2
+# per source and pair of targets in the un-masked loop, as accel_jerk_kernel (tests/test_hermite_host.py): 26 packed ops
+PER_SOURCE = {"v_pk_add_f32": 6, "v_pk_fma_f32": 14, "v_pk_mul_f32": 6, "v_rsq_f32_e32": 2}
+
+
+def _off(sizes):
+    off = np.zeros(len(sizes) + 1, dtype=np.int32)
+    np.cumsum(sizes, out=off[1:])
+    return off
+
+
+def _plan(sizes):
+    L = _lib.lib()
+    off = _off(sizes)
+    items, rows, pb, wb = ctypes.c_int(), ctypes.c_int(), ctypes.c_size_t(), ctypes.c_size_t()
+    assert L.nbd_batch_plan(off.ctypes.data, len(sizes), items, rows, pb, wb) == 0
+    buf = np.zeros(pb.value // 4, dtype=np.int32)
+    assert L.nbd_batch_plan_fill(off.ctypes.data, len(sizes), buf.ctypes.data, pb.value) == 0
+    k = items.value
+    scenes = buf[4 * k:4 * k + 8 * len(sizes)].reshape(len(sizes), 8)
+    return off, rows.value, pb.value, scenes, buf
+
+
+def _hws_bytes(off, s):
+    nb = ctypes.c_size_t(0)
+    rc = _lib.lib().nbd_batch_hermite_workspace_bytes(None if off is None else off.ctypes.data, s, nb)
+    return rc, nb.value
+
+
+@pytest.mark.parametrize("sizes", [[3, 0, 25, 64, 65, 128, 129, 500, 1, 4097, 0, 1000, 16384, 2], [100] * 7, [0, 0]])
+def test_workspace_is_consistent_with_the_plan(sizes):
+    off, rows, _, scenes, _ = _plan(sizes)
+    rc, nb = _hws_bytes(off, len(sizes))
+    assert rc == 0
+    # velp float4[posm_rows], then each scene's float[slabs][6][n] at float 2 * ws_off, back to back
+    slab_floats = 0
+    for s, n in enumerate(sizes):
+        _, nn, _, ws_off, _, slabs, _, _ = scenes[s]
+        assert nn == n and 2 * ws_off == slab_floats
+        slab_floats += 6 * slabs * n
+    assert nb == rows * 16 + 4 * slab_floats
+    assert (rows * 16) % 16 == 0
+
+
+def test_bad_arguments_rejected_without_a_gpu():
+    L = _lib.lib()
+    off = _off([5, 7])
+    bad = np.array([0, 5, 2], dtype=np.int32)
+    assert _hws_bytes(bad, 2)[0] == E_BADARG
+    assert _hws_bytes(np.array([1, 5], dtype=np.int32), 1)[0] == E_BADARG
+    assert _hws_bytes(off, 0)[0] == E_BADARG
+    assert _hws_bytes(None, 1)[0] == E_BADARG
+    assert L.nbd_batch_hermite_workspace_bytes(off.ctypes.data, 2, None) == E_BADARG
+    _, _, good, _, host = _plan([5, 7])
+    p = host.ctypes.data
+    # every device pointer here is NULL or a host address that is never dereferenced
+    assert L.nbd_batch_accel_jerk_f32(bad.ctypes.data, 2, p, good, *[None] * 8, None, 0, None) == E_BADARG
+    assert L.nbd_batch_accel_jerk_f32(off.ctypes.data, 2, p, good + 16, *[None] * 8, None, 0, None) == E_BADARG
+    assert L.nbd_batch_accel_jerk_f32(off.ctypes.data, 2, None, good, *[None] * 8, None, 0, None) == E_BADARG
+    assert L.nbd_batch_accel_jerk_f32(off.ctypes.data, 2, p, good, *[None] * 8, None, 0, None) == E_BADARG
+    assert L.nbd_batch_hermite_step_f32(bad.ctypes.data, 2, p, good, *[None] * 11, None, 0, None) == E_BADARG
+    assert L.nbd_batch_hermite_step_f32(off.ctypes.data, 0, p, good, *[None] * 11, None, 0, None) == E_BADARG
+    assert L.nbd_batch_hermite_step_f32(off.ctypes.data, 2, p, good, *[None] * 11, None, 0, None) == E_BADARG
+    # one NULL array among the rest
+    for k in range(11):
+        args = [p] * 11
+        args[k] = None
+        assert L.nbd_batch_hermite_step_f32(off.ctypes.data, 2, p, good, *args, p, 1 << 20, None) == E_BADARG, k
+    # arrays given but no (or a too small) workspace: NBD_E_WORKSPACE, still before any launch
+    assert L.nbd_batch_accel_jerk_f32(off.ctypes.data, 2, p, good, *[p] * 8, None, 0, None) == E_WORKSPACE
+    _, need = _hws_bytes(off, 2)
+    assert L.nbd_batch_hermite_step_f32(off.ctypes.data, 2, p, good, *[p] * 11, p, need - 1, None) == E_WORKSPACE
+
+
+@pytest.fixture(scope="module")
+def asm(tmp_path_factory):
+    out = str(tmp_path_factory.mktemp("isa") / "direct_batch_hermite.s")
+    subprocess.run(["/opt/rocm/bin/hipcc", *FLAGS, "-o", out, SRC], check=True, capture_output=True)
+    return open(out).read()
+
+
+def _name(asm, kernel):
+    names = [m for m in re.findall(r"^(_Z\S+):", asm, flags=re.M) if kernel in m]
+    assert len(names) == 1, names
+    return names[0]
+
+
+def _function(asm, name):
+    i = asm.index(name + ":")
+    return asm[i:asm.index(".Lfunc_end", i)]
+
+
+def _meta(asm, name):
+    meta = asm[asm.index(".name:           " + name):]
+    return meta[:meta.index(".name:           ", 20) if ".name:           " in meta[20:] else len(meta)]
+
+
+def _resources(asm, name):
+    meta = _meta(asm, name)
+    return {k: int(re.search(r"\." + k + r":\s+(\d+)", meta).group(1))
+            for k in ("vgpr_count", "vgpr_spill_count", "private_segment_fixed_size")}
+
+
+def _rsq_loops(body):
+    out = []
+    for block in re.split(r"\n\.LBB\d+_\d+:", body)[1:]:
+        ins = [ln.strip() for ln in block.split("\n")]
+        ins = [ln for ln in ins if ln and not ln.startswith((";", "."))]
+        if any(ln.startswith("v_rsq_f32") for ln in ins):
+            out.append(ins)
+    return out
+
+
+def test_force_kernel_registers_and_scratch(asm):
+    name = _name(asm, "batch_accel_jerk_kernel")
+    r = _resources(asm, name)
+    assert r["private_segment_fixed_size"] == 0 and r["vgpr_spill_count"] == 0 and r["vgpr_count"] <= 96, r
+    body = _function(asm, name)
+    assert "global_load_lds_dwordx4" in body
+    assert not any("scratch_" in ln or "buffer_" in ln for ln in body.split("\n"))
+    desc = asm[asm.index(".amdhsa_kernel " + name):]
+    assert int(re.search(r"\.amdhsa_group_segment_fixed_size\s+(\d+)", desc).group(1)) == 16384
+
+
+def test_force_kernel_unmasked_inner_loop_instruction_mix(asm):
+    """Two source loops (masked and un-masked); the un-masked one -- no index compares -- runs the 26 packed ops and
+    2 v_rsq_f32 per source of accel_jerk_kernel, the mass splat folded into op_sel, no s_nop and no v_mov."""
+    loops = _rsq_loops(_function(asm, _name(asm, "batch_accel_jerk_kernel")))
+    assert len(loops) == 2
+    unmasked = [ins for ins in loops if not any(ln.startswith("v_cmp") for ln in ins)]
+    assert len(unmasked) == 1
+    ins = unmasked[0]
+    ops = Counter(ln.split()[0] for ln in ins)
+    sources = ops["v_rsq_f32_e32"] // 2
+    assert sources == 2
+    for op, n in PER_SOURCE.items():
+        assert ops[op] == n * sources, (op, ops[op], sources)
+    assert ops["s_nop"] == 0 and ops["v_mov_b32_e32"] == 0, ops
+    assert sum("op_sel:[1,0] op_sel_hi:[1,1]" in ln for ln in ins if ln.startswith("v_pk_mul_f32")) == sources
+    assert not any("scratch_" in ln or "buffer_" in ln for ln in ins)
+
+
+@pytest.mark.parametrize("kernel", ["batch_hermite_predict_kernel", "batch_hermite_correct_kernel"])
+def test_step_kernels_have_no_scratch(asm, kernel):
+    r = _resources(asm, _name(asm, kernel))
+    assert r["private_segment_fixed_size"] == 0 and r["vgpr_spill_count"] == 0, r
+    assert not any("scratch_" in ln or "buffer_" in ln for ln in _function(asm, _name(asm, kernel)).split("\n"))

@@ -6,8 +6,10 @@ direct integrator; prints ONE JSON line. Cases:
   large : 4 scenes x 16 384 bodies x 100 steps, energies off (pair rate: large scenes must not be penalised).
 Times are wall clock around run() after a warm-up run() of the same length (graph capture excluded on both sides), and
 GPU time = the sum of SimulationState.step_time (the batched step's GPU time is spread over its S scenes).
+--integrator hermite compares scene-by-scene HermiteSimulator.run() with one batched Hermite run(), and adds the batched
+leapfrog time of the same scenes from the same process (batched_leapfrog_*, hermite_over_leapfrog_gpu).
 
-  python tools/bench_direct_scenes.py [--sample 128] [--cases six,many,large]
+  python tools/bench_direct_scenes.py [--sample 128] [--cases six,many,large] [--integrator leapfrog|hermite]
 """
 import argparse
 import json
@@ -37,47 +39,62 @@ def timed(fn):
     return time.perf_counter() - t0, out
 
 
-def case(sizes, steps, energy, sample=None):
+def batched(systems, steps, energy, integrator):
+    """(wall s, GPU s) of one batched run() after a warm-up run() of the same length."""
+    bat = simulation.BatchedSimulator(systems=systems, integrator=integrator, g_const=G, softening=EPS, dt=DT,
+                                      calc_energy=energy, device="cuda")
+    bat.run(steps)
+    wall, runs = timed(lambda: bat.run(steps))
+    return wall, sum(st.step_time for r in runs for st in r)
+
+
+def case(sizes, steps, energy, sample=None, integrator="leapfrog"):
     systems = [spiral(n, 1 + i) for i, n in enumerate(sizes)]
     seq = systems if sample is None else systems[:sample]
-    sims = [simulation.LeapFrogSimulator(positions=p, velocities=v, masses=m, g_const=G, softening=EPS, dt=DT,
-                                         calc_energy=energy, device="cuda") for p, v, m in seq]
+    cls = simulation.HermiteSimulator if integrator == "hermite" else simulation.LeapFrogSimulator
+    sims = [cls(positions=p, velocities=v, masses=m, g_const=G, softening=EPS, dt=DT, calc_energy=energy, device="cuda")
+            for p, v, m in seq]
     for s in sims:
         s.run(steps)                                      # warm-up: captures
     wall_seq, runs = timed(lambda: [s.run(steps) for s in sims])
     gpu_seq = sum(st.step_time for r in runs for st in r)
     scale = len(systems) / len(seq)
-    bat = simulation.BatchedSimulator(systems=systems, integrator="leapfrog", g_const=G, softening=EPS, dt=DT,
-                                      calc_energy=energy, device="cuda")
-    bat.run(steps)
-    wall_bat, runs_b = timed(lambda: bat.run(steps))
-    gpu_bat = sum(st.step_time for r in runs_b for st in r)
+    wall_bat, gpu_bat = batched(systems, steps, energy, integrator)
     pairs = sum(n * n for n in sizes) * steps
-    return {"scenes": len(sizes), "bodies": sum(sizes), "steps": steps, "energy": energy,
-            "scene_by_scene_sampled": len(seq),
-            "scene_by_scene_wall_us_per_step": 1e6 * wall_seq * scale / steps,
-            "scene_by_scene_gpu_us_per_step": 1e6 * gpu_seq * scale / steps,
-            "batched_wall_us_per_step": 1e6 * wall_bat / steps,
-            "batched_gpu_us_per_step": 1e6 * gpu_bat / steps,
-            "speedup_wall": wall_seq * scale / wall_bat, "speedup_gpu": gpu_seq * scale / gpu_bat,
-            "batched_gpairs_per_s_gpu": pairs / gpu_bat * 1e-9,
-            "scene_by_scene_gpairs_per_s_gpu": pairs / (gpu_seq * scale) * 1e-9}
+    out = {} if integrator == "leapfrog" else {"integrator": integrator}
+    out.update({"scenes": len(sizes), "bodies": sum(sizes), "steps": steps, "energy": energy,
+                "scene_by_scene_sampled": len(seq),
+                "scene_by_scene_wall_us_per_step": 1e6 * wall_seq * scale / steps,
+                "scene_by_scene_gpu_us_per_step": 1e6 * gpu_seq * scale / steps,
+                "batched_wall_us_per_step": 1e6 * wall_bat / steps,
+                "batched_gpu_us_per_step": 1e6 * gpu_bat / steps,
+                "speedup_wall": wall_seq * scale / wall_bat, "speedup_gpu": gpu_seq * scale / gpu_bat,
+                "batched_gpairs_per_s_gpu": pairs / gpu_bat * 1e-9,
+                "scene_by_scene_gpairs_per_s_gpu": pairs / (gpu_seq * scale) * 1e-9})
+    if integrator != "leapfrog":
+        wall_lf, gpu_lf = batched(systems, steps, energy, "leapfrog")
+        out.update({"batched_leapfrog_wall_us_per_step": 1e6 * wall_lf / steps,
+                    "batched_leapfrog_gpu_us_per_step": 1e6 * gpu_lf / steps,
+                    "hermite_over_leapfrog_gpu": gpu_bat / gpu_lf})
+    return out
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sample", type=int, default=128)
     ap.add_argument("--cases", default="six,many,large")
+    ap.add_argument("--integrator", choices=("leapfrog", "hermite"), default="leapfrog")
     a = ap.parse_args()
+    it = a.integrator
     torch.cuda.set_device(0)
     out = {"device": torch.cuda.get_device_name(0)}
     todo = a.cases.split(",")
     if "six" in todo:
-        out["six"] = case([3, 25, 50, 100, 250, 500], 1000, True)
+        out["six"] = case([3, 25, 50, 100, 250, 500], 1000, True, integrator=it)
     if "many" in todo:
-        out["many"] = case([100] * 1024, 100, True, sample=a.sample)
+        out["many"] = case([100] * 1024, 100, True, sample=a.sample, integrator=it)
     if "large" in todo:
-        out["large"] = case([16384] * 4, 100, False)
+        out["large"] = case([16384] * 4, 100, False, integrator=it)
     print(json.dumps(out))
 
 
