@@ -168,8 +168,9 @@ int nbd_leapfrog_step_uniform_f32(float* pos, float* vel, const float* acc_in, f
 
 /* The force of nbd_leapfrog_step_uniform_f32's symmetric path on its own (tests, profiling): acc = g_const * mass_value *
  * sum_j d_ij s_ij^3 over all n bodies of posm, each off-diagonal pair evaluated once (Newton's third law). Needs
- * n >= 2048 and softening_sq >= 1e-24 (else NBD_E_UNSUPPORTED). Deterministic. variant: the register shape (0: the
- * step's, 4 source groups per tile pair; 1: 2 source groups), same sums in another order. Workspace:
+ * n >= 2048 and softening_sq >= 1e-24 (else NBD_E_UNSUPPORTED). Deterministic. variant: the register shape (0: 4 source
+ * groups per tile pair; 1: 2 source groups; 2: the step's, two sources per step packed by source), same sums in another
+ * order. Workspace:
  * nbd_accel_sym_workspace_bytes(n). */
 size_t nbd_accel_sym_workspace_bytes(int n);
 int nbd_accel_sym_uniform_f32(const float* posm, int n, float softening_sq, float g_const, float mass_value,

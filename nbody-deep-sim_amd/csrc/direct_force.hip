@@ -160,6 +160,17 @@ __device__ __forceinline__ void sym_pair(const f4 p, const f2 xi, const f2 yi, c
   rz = __builtin_elementwise_fma(-w, dz, rz);
 }
 
+// tile pair (ta, tb) of workgroup wg of the launch that starts at round r0: round r of the circle method, match i
+__device__ __forceinline__ void sym_round_match(int wg, int m, int r0, int n_slots, int& ta, int& tb, int& slot,
+                                                bool& init) {
+  const int half = m >> 1, mm = m - 1;
+  const int rr = wg / half, i = wg - rr * half, r = r0 + rr;
+  ta = i == 0 ? r % mm : (r + i) % mm;
+  tb = i == 0 ? mm : (r - i + mm) % mm;
+  slot = (r + 1) % n_slots;
+  init = r + 1 < n_slots;
+}
+
 // grid = (rounds of this launch) x M/2 workgroups; block = 256 * SG. Unscaled sums (finish_kernel applies G m).
 template <int SG>
 __global__ __launch_bounds__(256 * SG, 2 * SG) void accel_sym_kernel(const f4* __restrict__ posm, int n, int m,
@@ -173,13 +184,9 @@ __global__ __launch_bounds__(256 * SG, 2 * SG) void accel_sym_kernel(const f4* _
   __shared__ f4 lds[kLdsF / 4];                  // ONE object (keeps hipcc's waits sane)
   float* const ldsf = reinterpret_cast<float*>(lds);
 
-  // tile pair of this workgroup: round r of the circle method, match i
-  const int half = m >> 1, mm = m - 1;
-  const int rr = blockIdx.x / half, i = blockIdx.x - rr * half, r = r0 + rr;
-  const int ta = i == 0 ? r % mm : (r + i) % mm;
-  const int tb = i == 0 ? mm : (r - i + mm) % mm;
-  const int slot = (r + 1) % n_slots;
-  const bool init = r + 1 < n_slots;
+  int ta, tb, slot;
+  bool init;
+  sym_round_match(blockIdx.x, m, r0, n_slots, ta, tb, slot, init);
 
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -276,6 +283,165 @@ __global__ __launch_bounds__(256 * SG, 2 * SG) void accel_sym_kernel(const f4* _
       float* o = o_own + t * 64 * 3 + comp;
       *o = init ? v : *o + v;
     }
+}
+
+// ---- variant 2 of the symmetric force: the packed halves of the VALU hold two SOURCES instead of two targets.
+// accel_sym_kernel packs by target, so both halves of its reaction registers act on the one source of the step and each
+// source pays 6 DPP moves. Here a step takes source s of chunk c in the .x halves and source s of chunk c + 8 in the .y
+// halves; a target's coordinate is broadcast into both halves (op_sel), the own sums are {from c, from c + 8} (added once
+// at the end) and the reaction {R_c, R_c+8} covers both sources: 6 DPP moves per two sources.
+//
+// One workgroup = one tile pair (a, b) of the same circle-method rounds as accel_sym_kernel (same slots, store/add rule).
+// 8 waves: target group tg = wave & 1 holds the 512 targets a*S + tg*512 + 64 t + lane (t = 0..7) in registers, source
+// group sg = wave >> 1 walks the chunk pairs (p, p + 8), p = 2 sg, 2 sg + 1, of tile b. Tile b is staged once, at the
+// start, into an interleaved LDS image: per chunk pair, [128] {x_c, x_c+8, y_c, y_c+8} and [128] {z_c, z_c+8}, each chunk
+// stored twice so that step k of lane l reads entry l + k at immediate offset k (one ds_read_b128 + one ds_read_b64, no
+// wrap, no repacking). Per step and lane: 8 targets x 2 sources = 24 v_pk_add + 72 v_pk_fma + 16 v_pk_mul + 16 v_rsq +
+// 6 DPP moves (37.5 issue cycles per lane-pair against 42 for accel_sym_kernel). The reactions of a chunk pair go to LDS
+// without a barrier; after the walk the 2 target groups' reactions are added in order, then the 4 source groups' own
+// sums, each row written once per (slot, row). Unscaled sums; needs the tile pair in the core (m >= 2).
+constexpr int kSym2Pairs = kSymChunks / 2;   // chunk pairs (p, p + 8) of a tile
+constexpr int kSym2T = 8;                    // targets per lane
+constexpr int kSym2G = 2;                    // targets per scheduling group of the step (4: 128 VGPRs, 3 s_nop)
+
+__global__ __launch_bounds__(512, 4) void accel_sym2_kernel(const f4* __restrict__ posm, int n, int m, int r0,
+                                                            int n_slots, float eps2, float* __restrict__ out) {
+  constexpr int kXyF = kSym2Pairs * 128 * 4;      // [pair][128] {x, x', y, y'}
+  constexpr int kZF = kSym2Pairs * 128 * 2;       // [pair][128] {z, z'}
+  constexpr int kReactF = 2 * 8 * 6 * 64;         // [j][wave][comp * 2 + half][lane]
+  constexpr int kOwnF = 8 * 3 * kSym2T * 64;      // [sg][tg][comp][t][lane], over all of the above after the walk
+  static_assert(kXyF + kZF + kReactF == kOwnF, "one 48-KiB LDS image");
+  __shared__ f4 lds[kOwnF / 4];                   // ONE object (keeps hipcc's waits sane)
+  float* const ldsf = reinterpret_cast<float*>(lds);
+  f4* const xy = lds;
+  f2* const zz = reinterpret_cast<f2*>(ldsf + kXyF);
+  float* const react = ldsf + kXyF + kZF;
+
+  int ta, tb, slot;
+  bool init;
+  sym_round_match(blockIdx.x, m, r0, n_slots, ta, tb, slot, init);
+
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int tg = wave & 1, sg = wave >> 1;
+  {  // stage tile b: thread (p = wave, lane) takes source lane of chunks p and p + 8
+    const f4 u = posm[tb * kSymTile + wave * kChunk + lane];
+    const f4 v = posm[tb * kSymTile + (wave + kSym2Pairs) * kChunk + lane];
+    const f4 q = {u.x, v.x, u.y, v.y};
+    const f2 z = {u.z, v.z};
+    xy[wave * 128 + lane] = q; xy[wave * 128 + 64 + lane] = q;
+    zz[wave * 128 + lane] = z; zz[wave * 128 + 64 + lane] = z;
+  }
+  const int row0 = ta * kSymTile + tg * 512 + lane;
+  // targets as register pairs {x_t, y_t} and {z_t, z_t+1}: a coordinate reaches both halves of a packed op by op_sel
+  f2 txy[kSym2T], tzz[kSym2T / 2];
+  f2 ax[kSym2T], ay[kSym2T], az[kSym2T];
+#pragma unroll
+  for (int t = 0; t < kSym2T; ++t) {
+    const f4 q = posm[row0 + t * 64];
+    txy[t] = f2{q.x, q.y};
+    if (t & 1) tzz[t >> 1].y = q.z; else tzz[t >> 1].x = q.z;
+    ax[t] = ay[t] = az[t] = f2{0.f, 0.f};
+  }
+  f2 e2 = {eps2, eps2};
+  asm volatile("" : "+v"(e2));  // keep eps^2 in VGPRs: an SGPR operand halves v_pk_fma issue
+  __syncthreads();
+
+#pragma unroll 1
+  for (int j = 0; j < 2; ++j) {
+    const int p = sg * 2 + j;
+    const f4* const bxy = xy + p * 128 + lane;
+    const f2* const bz = zz + p * 128 + lane;
+    f2 rx = {0.f, 0.f}, ry = {0.f, 0.f}, rz = {0.f, 0.f};
+#pragma unroll 1
+    for (int k = 0; k < kChunk; ++k) {
+      const f4 a = bxy[k];
+      const f2 sx = {a.x, a.y}, sy = {a.z, a.w}, sz = bz[k];
+      // opaque per step, or hipcc hoists the splats {x_t, x_t} out of the loop (24 more VGPRs)
+#pragma unroll
+      for (int t = 0; t < kSym2T; ++t) asm volatile("" : "+v"(txy[t]));
+#pragma unroll
+      for (int t = 0; t < kSym2T / 2; ++t) asm volatile("" : "+v"(tzz[t]));
+#pragma unroll
+      for (int g = 0; g < kSym2T; g += kSym2G) {
+        // each stage over the whole group, fenced by sched_barrier: left alone, hipcc runs each target's chain back to back
+        // and pads a wait state (s_nop) between every dependent packed op or rsq and its producer, 31 per step
+        f2 dx[kSym2G], dy[kSym2G], dz[kSym2G], s[kSym2G], w[kSym2G];
+#pragma unroll
+        for (int u = 0; u < kSym2G; ++u) {
+          const int t = g + u;
+          const float tz = (t & 1) ? tzz[t >> 1].y : tzz[t >> 1].x;
+          dx[u] = sx - f2{txy[t].x, txy[t].x}; dy[u] = sy - f2{txy[t].y, txy[t].y}; dz[u] = sz - f2{tz, tz};  // r_j - r_i
+        }
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int u = 0; u < kSym2G; ++u) s[u] = __builtin_elementwise_fma(dx[u], dx[u], e2);
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int u = 0; u < kSym2G; ++u) s[u] = __builtin_elementwise_fma(dy[u], dy[u], s[u]);
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int u = 0; u < kSym2G; ++u) s[u] = __builtin_elementwise_fma(dz[u], dz[u], s[u]);
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int u = 0; u < kSym2G; ++u) s[u] = f2{__builtin_amdgcn_rsqf(s[u].x), __builtin_amdgcn_rsqf(s[u].y)};
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int u = 0; u < kSym2G; ++u) w[u] = s[u] * s[u];
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int u = 0; u < kSym2G; ++u) w[u] = w[u] * s[u];
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int u = 0; u < kSym2G; ++u) {
+          const int t = g + u;
+          ax[t] = __builtin_elementwise_fma(w[u], dx[u], ax[t]);
+          ay[t] = __builtin_elementwise_fma(w[u], dy[u], ay[t]);
+          az[t] = __builtin_elementwise_fma(w[u], dz[u], az[t]);
+          rx = __builtin_elementwise_fma(-w[u], dx[u], rx);
+          ry = __builtin_elementwise_fma(-w[u], dy[u], ry);
+          rz = __builtin_elementwise_fma(-w[u], dz[u], rz);
+        }
+      }
+      rx = f2{rol1(rx.x), rol1(rx.y)};
+      ry = f2{rol1(ry.x), rol1(ry.y)};
+      rz = f2{rol1(rz.x), rol1(rz.y)};
+    }
+    float* const mine = react + (j * 8 + wave) * 6 * 64 + lane;
+    mine[0 * 64] = rx.x; mine[1 * 64] = rx.y;
+    mine[2 * 64] = ry.x; mine[3 * 64] = ry.y;
+    mine[4 * 64] = rz.x; mine[5 * 64] = rz.y;
+  }
+  __syncthreads();
+
+  // reactions: rows of tile b, target group 0 + target group 1; one coalesced pass over the tile's 1024 x 3 floats
+  float* const o_b = out + ((size_t)slot * n + (size_t)tb * kSymTile) * 3;
+  for (int o = threadIdx.x; o < kSymTile * 3; o += 512) {
+    const int row = o / 3, comp = o - row * 3;
+    const int c = row >> 6, l = row & 63, p = c & (kSym2Pairs - 1), hf = c / kSym2Pairs;
+    const float* rs = react + ((p & 1) * 8 + (p >> 1) * 2) * 6 * 64 + (comp * 2 + hf) * 64 + l;
+    const float v = rs[0] + rs[6 * 64];
+    o_b[o] = init ? v : o_b[o] + v;
+  }
+  __syncthreads();  // every reaction read is done: the LDS image takes the own sums
+#pragma unroll
+  for (int t = 0; t < kSym2T; ++t) {
+    float* const mo = ldsf + ((sg * 2 + tg) * 3 * kSym2T + t) * 64 + lane;
+    mo[0 * kSym2T * 64] = ax[t].x + ax[t].y;
+    mo[1 * kSym2T * 64] = ay[t].x + ay[t].y;
+    mo[2 * kSym2T * 64] = az[t].x + az[t].y;
+  }
+  __syncthreads();
+  // own sums: rows of tile a, the 4 source groups in order
+  float* const o_a = out + ((size_t)slot * n + (size_t)ta * kSymTile) * 3;
+  for (int o = threadIdx.x; o < kSymTile * 3; o += 512) {
+    const int row = o / 3, comp = o - row * 3;
+    const int g = row >> 9, t = (row >> 6) & (kSym2T - 1), l = row & 63;
+    const float* os = ldsf + ((g * 3 + comp) * kSym2T + t) * 64 + l;
+    constexpr int kSg = 2 * 3 * kSym2T * 64;
+    const float v = ((os[0] + os[kSg]) + os[2 * kSg]) + os[3 * kSg];
+    o_a[o] = init ? v : o_a[o] + v;
+  }
 }
 
 // acc = g * (slab_0 + slab_1 + ...), optional fused kick v += c * acc (simulation.py:88,170).
@@ -585,7 +751,7 @@ bool sym_step(int n, float eps2) { return n >= kSymStepMinN && eps2 >= kEps2Mask
 // unscaled sum_j d_ij s_ij^3 of every row into slots [0, total_slots) of float[total_slots][n][3]; needs m >= 2 and
 // eps2 >= kEps2Masked (the i == j term of a diagonal block is then an exact zero)
 // variant 0: 4 source groups (16-wave workgroups, 64 VGPRs, 2 per CU: 8 waves per SIMD); 1: 2 source groups (8 waves,
-// 86 VGPRs: 4 waves per SIMD)
+// 86 VGPRs: 4 waves per SIMD); 2: accel_sym2_kernel (two sources per step, 8 waves, <= 128 VGPRs: 4 waves per SIMD)
 int launch_sym(const float* posm, int n, float eps2, float* slots, hipStream_t st, int variant = 0) {
   const SymPlan sp = plan_sym(n);
   const f4* pm = reinterpret_cast<const f4*>(posm);
@@ -601,7 +767,8 @@ int launch_sym(const float* posm, int n, float eps2, float* slots, hipStream_t s
   for (int r0 = 0; r0 < rounds;) {
     const int r1 = r0 == 0 ? (sp.slots - 1 < rounds ? sp.slots - 1 : rounds) : (r0 + sp.slots < rounds ? r0 + sp.slots : rounds);
     const int wgs = (r1 - r0) * (sp.m / 2);
-    if (variant == 1) accel_sym_kernel<2><<<wgs, 512, 0, st>>>(pm, n, sp.m, r0, sp.slots, eps2, slots);
+    if (variant == 2) accel_sym2_kernel<<<wgs, 512, 0, st>>>(pm, n, sp.m, r0, sp.slots, eps2, slots);
+    else if (variant == 1) accel_sym_kernel<2><<<wgs, 512, 0, st>>>(pm, n, sp.m, r0, sp.slots, eps2, slots);
     else accel_sym_kernel<4><<<wgs, 1024, 0, st>>>(pm, n, sp.m, r0, sp.slots, eps2, slots);
     if ((rc = launch_status())) return rc;
     r0 = r1;
@@ -684,7 +851,7 @@ size_t nbd_accel_sym_workspace_bytes(int n) { return n <= 0 ? 0 : sym_workspace_
 
 int nbd_accel_sym_uniform_f32(const float* posm, int n, float softening_sq, float g_const, float mass_value,
                               float* acc_out, void* workspace, size_t workspace_bytes, int variant, nbd_stream_t stream) {
-  if (n < 0 || (n > 0 && (!posm || !acc_out)) || misaligned16(posm) || variant < 0 || variant > 1) return NBD_E_BADARG;
+  if (n < 0 || (n > 0 && (!posm || !acc_out)) || misaligned16(posm) || variant < 0 || variant > 2) return NBD_E_BADARG;
   if (n == 0) return 0;
   if (plan_sym(n).m < 2 || softening_sq < kEps2Masked) return NBD_E_UNSUPPORTED;
   if (!workspace || workspace_bytes < sym_workspace_bytes(n)) return NBD_E_WORKSPACE;
@@ -951,7 +1118,7 @@ int nbd_leapfrog_step_uniform_f32(float* pos, float* vel, const float* acc_in, f
   if (n == 0) return 0;
   if (!pos || !vel || !acc_in || !acc_out || !mass || !posm || misaligned16(posm)) return NBD_E_BADARG;
   hipStream_t st = (hipStream_t)stream;
-  const bool sym = sym_step(n, softening_sq);   // large systems: every pair once (accel_sym_kernel)
+  const bool sym = sym_step(n, softening_sq);   // large systems: every pair once (accel_sym2_kernel)
   const AccelPlan p = plan_accel(n, n);
   const size_t need = sym ? sym_workspace_bytes(n) : (size_t)p.slabs * n * 3 * sizeof(float);
   if (!workspace || workspace_bytes < need) return NBD_E_WORKSPACE;
@@ -959,7 +1126,7 @@ int nbd_leapfrog_step_uniform_f32(float* pos, float* vel, const float* acc_in, f
   if (rc) return rc;
   float* slabs = static_cast<float*>(workspace);
   if (ev_force_begin && (rc = check(hipEventRecord((hipEvent_t)ev_force_begin, st)))) return rc;
-  if (sym) rc = launch_sym(posm, n, softening_sq, slabs, st);
+  if (sym) rc = launch_sym(posm, n, softening_sq, slabs, st, 2);
   else rc = launch_accel(posm, full_view(n, p), posm, n, 0, softening_sq, 1.0f, slabs, p, st, true);
   if (rc) return rc;
   if (ev_force_end && (rc = check(hipEventRecord((hipEvent_t)ev_force_end, st)))) return rc;
