@@ -6,9 +6,9 @@
 // scene's own G, softening^2 and dt. C-ABI: include/nbd.h (nbd_batch_*).
 //
 // Work list (built once on the host, nbd_batch_plan / nbd_batch_plan_fill, uploaded by the caller): one item per
-// (scene, target group of 128, slab), a workgroup each. Item (s, g, k) runs the all-pairs inner loop of
-// accel_kernel (interact / interact_block of direct_kernels.h: two targets per lane, v_pk_fma_f32 + v_rsq_f32,
-// LDS-DMA staged 64-body chunks) on targets [128 g, 128 g + 128) of scene s against the chunks of ITS scene that
+// (scene, target group of 128, slab), a workgroup each. Item (s, g, k) runs the wave body of
+// accel_kernel (accel_body of direct_kernels.h: two targets per lane, v_pk_fma_f32 + v_rsq_f32,
+// LDS-DMA staged 64-body chunks, the same code the one-system kernel calls) on targets [128 g, 128 g + 128) of scene s against the chunks of ITS scene that
 // wave k * 4 + w owns. The slab count of a scene is the single-system plan for its size (nbd_accel_plan(n, n)), so
 // a scene's items, their split of the sources and the fixed-order slab sum depend on n_s alone: a scene's results
 // are bit-identical whether it runs alone or with any companions, at any position of the batch. Items are
@@ -32,7 +32,8 @@ namespace {
 size_t ws_u_offset(const BatchTotals& t) { return ((size_t)t.ws_floats * 4 + 15) & ~(size_t)15; }
 size_t ws_bytes_of(const BatchTotals& t) { return ws_u_offset(t) + (size_t)t.u_doubles * 8; }
 
-// ---- segmented force: one workgroup per item; the body of accel_kernel (KU = 8) on the item's scene. Unscaled
+// ---- segmented force: one workgroup per item; accel_kernel's body (accel_body, KU = 8, the scene's full view) on the
+// item's scene, masked or not for the whole scene by an argument the compiler tests once per chunk. Unscaled
 // sums into slab k of the scene: ws[ws_off + (k * n + i) * 3 + c]. softening^2 < kEps2Masked takes the index-masked
 // path for the whole scene (fill_diagonal_, simulation.py:85: the i == j term and the padding are dropped by index,
 // coincident bodies give NaN in that scene only). Otherwise r^2 >= softening^2 >= 1e-24 keeps s^3 finite, and a
@@ -42,7 +43,7 @@ __global__ __launch_bounds__(64 * kWaves, 5) void batch_accel_kernel(const f4* _
                                                                      const SceneRec* __restrict__ scenes,
                                                                      const float* __restrict__ eps2_s,
                                                                      float* __restrict__ ws) {
-  __shared__ f4 lds[kWaves * 2 * kChunk + kWaves * 6 * 64 / 4];
+  __shared__ f4 lds[kAccelLdsF4];
   const int4 it = items[blockIdx.x];
   const int s = __builtin_amdgcn_readfirstlane(it.x), grp = __builtin_amdgcn_readfirstlane(it.y);
   const int slab = __builtin_amdgcn_readfirstlane(it.z);
@@ -51,65 +52,9 @@ __global__ __launch_bounds__(64 * kWaves, 5) void batch_accel_kernel(const f4* _
   const int n_chunks = __builtin_amdgcn_readfirstlane(sc.n_chunks), slabs = __builtin_amdgcn_readfirstlane(sc.slabs);
   const f4* src = posm + __builtin_amdgcn_readfirstlane(sc.poff);
   const float eps2 = eps2_s[s];
-  const bool masked = eps2 < kEps2Masked;
-
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int t_base = grp * kTgtPerWG;
-  const int i0 = t_base + lane, i1 = t_base + 64 + lane;
-  const f4 t0 = src[min(i0, n - 1)], t1 = src[min(i1, n - 1)];
-  const f2 xi = {t0.x, t1.x}, yi = {t0.y, t1.y}, zi = {t0.z, t1.z};
-  f2 ax = {0.f, 0.f}, ay = {0.f, 0.f}, az = {0.f, 0.f};
-  f2 e2 = {eps2, eps2};
-  asm volatile("" : "+v"(e2));  // keep eps^2 in VGPRs: an SGPR operand halves v_pk_fma issue
-
-  SrcView sv;
-  sv.n_src = n; sv.n_chunks = n_chunks; sv.cpw_q = n_chunks / (slabs * kWaves); sv.cpw_r = n_chunks % (slabs * kWaves);
-  sv.skip_c0 = n_chunks; sv.skip_cn = 0; sv.ex_lo = 0; sv.ex_hi = 0; sv.edge0 = -1; sv.edge1 = -1;
-  sv.tail = (n % kChunk) ? n / kChunk : -1;
-
-  const int jw = slab * kWaves + wave;
-  const int c_begin = jw * sv.cpw_q + min(jw, sv.cpw_r), c_end = c_begin + sv.cpw_q + (jw < sv.cpw_r ? 1 : 0);
-  f4* stage = &lds[wave * 2 * kChunk];
-  const f4* s_lane = src + lane;
-  if (c_begin < c_end)
-    __builtin_amdgcn_global_load_lds(GPTR(s_lane + (size_t)c_begin * kChunk), LPTR(stage), 16, 0, 0);
-  for (int c = c_begin; c < c_end; ++c) {
-    const int b = (c - c_begin) & 1;
-    if (c + 1 < c_end) {
-      __builtin_amdgcn_global_load_lds(GPTR(s_lane + (size_t)(c + 1) * kChunk), LPTR(stage + (b ^ 1) * kChunk), 16, 0, 0);
-      asm volatile("s_waitcnt vmcnt(1)" ::: "memory");  // chunk c has landed, c+1 in flight
-    } else {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-    const f4* buf = stage + b * kChunk;
-    const int j0 = c * kChunk;
-    if (masked) {
-#pragma unroll 4
-      for (int j = 0; j < kChunk; ++j) interact<true>(buf[j], xi, yi, zi, e2, ax, ay, az, j0 + j, i0, i1, sv);
-    } else {
-#pragma unroll 1
-      for (int j = 0; j < kChunk; j += 8) interact_block<8>(buf + j, xi, yi, zi, e2, ax, ay, az);
-    }
-  }
-
-  // wavefront partials -> LDS -> one coalesced (128 x 3) store per workgroup, waves added in fixed order
-  float* red = reinterpret_cast<float*>(&lds[kWaves * 2 * kChunk]);
-  float* mine = red + wave * 6 * 64;
-  mine[0 * 64 + lane] = ax.x; mine[1 * 64 + lane] = ax.y;
-  mine[2 * 64 + lane] = ay.x; mine[3 * 64 + lane] = ay.y;
-  mine[4 * 64 + lane] = az.x; mine[5 * 64 + lane] = az.y;
-  __syncthreads();
-  float* dst = ws + sc.ws_off + ((size_t)slab * n + t_base) * 3;
-  const int n_valid = min(kTgtPerWG, n - t_base) * 3;
-  for (int o = threadIdx.x; o < n_valid; o += 64 * kWaves) {
-    const int lt = o / 3, comp = o - lt * 3;
-    const int idx = (comp * 2 + (lt >> 6)) * 64 + (lt & 63);
-    float sum = red[idx];
-#pragma unroll
-    for (int w = 1; w < kWaves; ++w) sum += red[w * 6 * 64 + idx];
-    dst[o] = sum;
-  }
+  accel_body<8, false>(src, full_view(n, n_chunks, slabs), eps2 < kEps2Masked, src, n, 0, t_base, slab, eps2, 1.0f, lds,
+                       ws + sc.ws_off + ((size_t)slab * n + t_base) * 3);
 }
 
 // ---- per packed row r: scene s = row_scene[r], body i = r - poff_s. Optional kick v += ck_s a, optional drift
@@ -169,70 +114,23 @@ __global__ __launch_bounds__(256) void batch_finish_kernel(const int* __restrict
   if (vel) vel[o] = __fadd_rn(vel[o], __fmul_rn(ck_s[s], a));
 }
 
-// ---- segmented potential energy: one workgroup per item, energy_kernel's body on the item's scene (upper triangle,
+// ---- segmented potential energy: one workgroup per item, energy_kernel's body (energy_body) on the item's scene (upper triangle,
 // |r| + eps, fp32 lanes, fp64 across lanes); the item's partial goes to pu[u_off + g * slabs + k].
 __global__ __launch_bounds__(64 * kWaves) void batch_energy_kernel(const f4* __restrict__ posm,
                                                                    const int4* __restrict__ items,
                                                                    const SceneRec* __restrict__ scenes,
                                                                    const float* __restrict__ soft_s,
                                                                    double* __restrict__ pu) {
-  __shared__ f4 lds[kWaves * 2 * kChunk + 8];
+  __shared__ f4 lds[kEnergyLdsF4];
   const int4 it = items[blockIdx.x];
   const int s = __builtin_amdgcn_readfirstlane(it.x), grp = __builtin_amdgcn_readfirstlane(it.y);
   const int slab = __builtin_amdgcn_readfirstlane(it.z);
   const SceneRec sc = load_scene(scenes, s);
   const int n = __builtin_amdgcn_readfirstlane(sc.n), n_chunks = __builtin_amdgcn_readfirstlane(sc.n_chunks);
   const int slabs = __builtin_amdgcn_readfirstlane(sc.slabs);
-  const f4* src = posm + __builtin_amdgcn_readfirstlane(sc.poff);
-  const float soft_ = soft_s[s];
-  const bool all_masked = !(soft_ > 0.f);
-
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int t_base = grp * kTgtPerWG;
-  const int i0 = t_base + lane, i1 = t_base + 64 + lane;
-  const f4 t0 = src[min(i0, n - 1)], t1 = src[min(i1, n - 1)];
-  const f2 xi = {t0.x, t1.x}, yi = {t0.y, t1.y}, zi = {t0.z, t1.z};
-  f2 u = {0.f, 0.f};
-  f2 soft = {soft_, soft_};
-  asm volatile("" : "+v"(soft));
-  const int c_lo = t_base / kChunk;
-  const int span = n_chunks - c_lo;
-  const int parts = slabs * kWaves;
-  const int cpw = (span + parts - 1) / parts;
-  const int jw = slab * kWaves + wave;
-  const int c_begin = min(c_lo + jw * cpw, n_chunks), c_end = min(c_begin + cpw, n_chunks);
-  const int c_diag_end = (t_base + kTgtPerWG + kChunk - 1) / kChunk;
-  f4* stage = &lds[wave * 2 * kChunk];
-  const f4* s_lane = src + lane;
-  if (c_begin < c_end)
-    __builtin_amdgcn_global_load_lds(GPTR(s_lane + (size_t)c_begin * kChunk), LPTR(stage), 16, 0, 0);
-  for (int c = c_begin; c < c_end; ++c) {
-    const int b = (c - c_begin) & 1;
-    if (c + 1 < c_end) {
-      __builtin_amdgcn_global_load_lds(GPTR(s_lane + (size_t)(c + 1) * kChunk), LPTR(stage + (b ^ 1) * kChunk), 16, 0, 0);
-      asm volatile("s_waitcnt vmcnt(1)" ::: "memory");
-    } else {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-    const f4* buf = stage + b * kChunk;
-    const int j0 = c * kChunk;
-    if (all_masked || c < c_diag_end || c == n_chunks - 1) {
-#pragma unroll 4
-      for (int j = 0; j < kChunk; ++j) energy_pair<true>(buf[j], xi, yi, zi, soft, u, j0 + j, i0, i1, n);
-    } else {
-#pragma unroll 4
-      for (int j = 0; j < kChunk; ++j) energy_pair<false>(buf[j], xi, yi, zi, soft, u, j0 + j, i0, i1, n);
-    }
-  }
-  double acc = 0.0;
-  if (i0 < n) acc += (double)t0.w * (double)u.x;
-  if (i1 < n) acc += (double)t1.w * (double)u.y;
-  for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off);
-  double* red = reinterpret_cast<double*>(&lds[kWaves * 2 * kChunk]);
-  if (lane == 0) red[wave] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) pu[(size_t)sc.u_off + (size_t)grp * slabs + slab] = (red[0] + red[1]) + (red[2] + red[3]);
+  const float soft = soft_s[s];
+  energy_body(posm + __builtin_amdgcn_readfirstlane(sc.poff), n, n_chunks, grp * kTgtPerWG, slab, slabs, soft,
+              !(soft > 0.f), lds, pu + (size_t)sc.u_off + (size_t)grp * slabs + slab);
 }
 
 // one workgroup per scene: U_s = -G_s * (sum of its partials), K_s = sum 0.5 m v^2 (fp32 terms as kinetic_kernel,

@@ -7,7 +7,7 @@
 // is three launches for all scenes:
 //   predict  : one thread per packed row: posm = {x_p, m}, velp = {v_p, 0} (zeros in each scene's padding), the
 //              arithmetic of hermite_predict_kernel with the scene's own fp32 step constants
-//   evaluate : one workgroup per item: accel_jerk_kernel's body (KU = 2) on the item's scene, masked or not per scene
+//   evaluate : one workgroup per item: accel_jerk_body (hermite_kernels.h, KU = 2) on the item's scene, masked or not per scene
 //              from its softening^2; unscaled partial sums into float[slabs][6][n_s] at float 2 * ws_off of the slabs
 //   correct  : one workgroup per 64 packed rows (never across scenes): hermite_correct_kernel's fixed-order slab sum
 //              and corrector with the scene's G and constants; posm = {x1, m} for the energies after the step
@@ -68,94 +68,17 @@ __global__ __launch_bounds__(256) void batch_hermite_predict_kernel(const int* _
   velp[r] = vp;
 }
 
-// Acceleration + jerk of targets [128 grp, 128 grp + 128) of one scene (src_p / src_v: its packed rows) against the chunks
-// that wave 4 slab + w owns: accel_jerk_kernel<MASKED, 2>'s body. out: the scene's float[slabs][6][n].
-template <bool MASKED>
-__device__ __forceinline__ void accel_jerk_item(const f4* __restrict__ src_p, const f4* __restrict__ src_v, int n,
-                                                int n_chunks, int slabs, int grp, int slab, float eps2, f4* lds,
-                                                float* __restrict__ out) {
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int t_base = grp * kTgtPerWG;
-  const int i0 = t_base + lane, i1 = t_base + 64 + lane;
-  const f4 t0 = src_p[min(i0, n - 1)], t1 = src_p[min(i1, n - 1)];
-  const f4 u0 = src_v[min(i0, n - 1)], u1 = src_v[min(i1, n - 1)];
-  const f2 xi = {t0.x, t1.x}, yi = {t0.y, t1.y}, zi = {t0.z, t1.z};
-  const f2 ui = {u0.x, u1.x}, vi = {u0.y, u1.y}, wi = {u0.z, u1.z};
-  f2 acc[9];
-#pragma unroll
-  for (int k = 0; k < 9; ++k) acc[k] = f2{0.f, 0.f};
-  f2 e2 = {eps2, eps2};
-  asm volatile("" : "+v"(e2));  // keep eps^2 in VGPRs: an SGPR operand halves v_pk_fma issue
-
-  const int cpw_q = n_chunks / (slabs * kWaves), cpw_r = n_chunks % (slabs * kWaves);
-  const int jw = slab * kWaves + wave;
-  const int c_begin = jw * cpw_q + min(jw, cpw_r), c_end = c_begin + cpw_q + (jw < cpw_r ? 1 : 0);
-  f4* stage = &lds[wave * 4 * kChunk];
-  const f4* p_lane = src_p + lane;
-  const f4* v_lane = src_v + lane;
-  auto fetch = [&](int c, int b) {
-    __builtin_amdgcn_global_load_lds(GPTR(p_lane + (size_t)c * kChunk), LPTR(stage + b * 2 * kChunk), 16, 0, 0);
-    __builtin_amdgcn_global_load_lds(GPTR(v_lane + (size_t)c * kChunk), LPTR(stage + b * 2 * kChunk + kChunk), 16, 0, 0);
-  };
-  if (c_begin < c_end) fetch(c_begin, 0);
-  for (int c = c_begin; c < c_end; ++c) {
-    const int b = (c - c_begin) & 1;
-    if (c + 1 < c_end) {
-      fetch(c + 1, b ^ 1);
-      asm volatile("s_waitcnt vmcnt(2)" ::: "memory");  // chunk c has landed, c+1 (two loads) in flight
-    } else {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-    const f4* bp = stage + b * 2 * kChunk;
-    const f4* bv = bp + kChunk;
-    if (MASKED) {
-      const int j0 = c * kChunk;
-#pragma unroll 2
-      for (int j = 0; j < kChunk; ++j)
-        jerk_pair_masked(bp[j], bv[j], xi, yi, zi, ui, vi, wi, e2, acc, j0 + j, i0, i1, n);
-    } else {
-#pragma unroll 1
-      for (int j = 0; j < kChunk; j += 2) jerk_block<2>(bp + j, bv + j, xi, yi, zi, ui, vi, wi, e2, acc);
-    }
-  }
-
-  // j = (w dv) - 3 (r.v s^2 w dr); wavefront partials -> LDS (each wave's own staging, its loads have landed) -> one
-  // coalesced (6 x 128) store per workgroup, the waves added in fixed order
-  constexpr int kPart = 4 * kChunk * 4;
-  float* red = reinterpret_cast<float*>(lds);
-  float* mine = red + wave * kPart;
-#pragma unroll
-  for (int k = 0; k < 6; ++k) {
-    const f2 v = k < 3 ? acc[k] : acc[k] - 3.0f * acc[k + 3];
-    mine[(2 * k) * 64 + lane] = v.x;
-    mine[(2 * k + 1) * 64 + lane] = v.y;
-  }
-  __syncthreads();
-  float* dst = out + (size_t)slab * 6 * n + t_base;
-  const int n_valid = min(kTgtPerWG, n - t_base);
-  for (int o = threadIdx.x; o < 6 * kTgtPerWG; o += 64 * kWaves) {
-    const int comp = o >> 7, lt = o & 127;
-    if (lt >= n_valid) continue;
-    const int idx = (comp * 2 + (lt >> 6)) * 64 + (lt & 63);
-    float sum = red[idx];
-#pragma unroll
-    for (int w = 1; w < kWaves; ++w) sum += red[w * kPart + idx];
-    dst[(size_t)comp * n + lt] = sum;
-  }
-}
-
-// One workgroup per item (s, g, k): the item's scene, its chunk split (cpw_q / cpw_r of the scene's own plan) and its
-// slab. softening^2 < kEps2Masked takes the index-masked loop for the whole scene; the branch is taken once, at the top,
-// so that each path keeps its own registers. out: the scene's float[slabs][6][n] at ws + 2 * ws_off (the leapfrog
-// plan's float[slabs][n][3] offsets, doubled).
+// One workgroup per item (s, g, k): targets [128 g, 128 g + 128) of scene s (its packed rows of posm / velp) against the
+// chunks that wave 4 k + w owns in the scene's own plan: accel_jerk_kernel<MASKED, 2>'s geometry read from the scene
+// record, then the same accel_jerk_body. softening^2 < kEps2Masked takes the index-masked loop for the whole scene; the
+// branch is taken once, at the top, so that each path keeps its own registers. out: the scene's float[slabs][6][n] at
+// ws + 2 * ws_off (the leapfrog plan's float[slabs][n][3] offsets, doubled).
 __global__ __launch_bounds__(64 * kWaves, 5) void batch_accel_jerk_kernel(const f4* __restrict__ posm,
                                                                           const f4* __restrict__ velp,
                                                                           const int4* __restrict__ items,
                                                                           const SceneRec* __restrict__ scenes,
                                                                           const float* __restrict__ eps2_s,
                                                                           float* __restrict__ ws) {
-  // [wave][buffer][pos | vel][64] staging; after its last chunk a wave puts its [12][64] partials into its own part
   __shared__ f4 lds[kWaves * 4 * kChunk];
   const int4 it = items[blockIdx.x];
   const int s = __builtin_amdgcn_readfirstlane(it.x), grp = __builtin_amdgcn_readfirstlane(it.y);
@@ -164,12 +87,20 @@ __global__ __launch_bounds__(64 * kWaves, 5) void batch_accel_jerk_kernel(const 
   const int n = __builtin_amdgcn_readfirstlane(sc.n);
   const int n_chunks = __builtin_amdgcn_readfirstlane(sc.n_chunks), slabs = __builtin_amdgcn_readfirstlane(sc.slabs);
   const int poff = __builtin_amdgcn_readfirstlane(sc.poff);
-  float* out = ws + 2 * (size_t)sc.ws_off;
   const float eps2 = eps2_s[s];
+  const int t_base = grp * kTgtPerWG;
+  const int i0 = t_base + (threadIdx.x & 63), i1 = i0 + 64;
+  const int cpw_q = n_chunks / (slabs * kWaves), cpw_r = n_chunks % (slabs * kWaves);
+  const int jw = slab * kWaves + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int c_begin = jw * cpw_q + min(jw, cpw_r), c_end = c_begin + cpw_q + (jw < cpw_r ? 1 : 0);
+  float* dst = ws + 2 * (size_t)sc.ws_off + (size_t)slab * 6 * n + t_base;
+  const int n_valid = min(kTgtPerWG, n - t_base);
   if (eps2 < kEps2Masked)
-    accel_jerk_item<true>(posm + poff, velp + poff, n, n_chunks, slabs, grp, slab, eps2, lds, out);
+    accel_jerk_body<true, 2>(posm + poff, velp + poff, n, min(i0, n - 1), min(i1, n - 1), i0, i1, c_begin, c_end, eps2,
+                             lds, dst, n, n_valid);
   else
-    accel_jerk_item<false>(posm + poff, velp + poff, n, n_chunks, slabs, grp, slab, eps2, lds, out);
+    accel_jerk_body<false, 2>(posm + poff, velp + poff, n, min(i0, n - 1), min(i1, n - 1), i0, i1, c_begin, c_end, eps2,
+                              lds, dst, n, n_valid);
 }
 
 // One workgroup per 64 packed rows (a scene's rows are whole chunks of 64, so a block never spans two scenes):

@@ -9,7 +9,7 @@
 //     so everything is arranged to keep the four SIMDs of a CU issuing packed fp32 math:
 //     each lane owns TWO targets held as float2 register pairs, so one broadcast source feeds
 //     v_pk_add/v_pk_fma/v_pk_mul on both; two register shapes of the same code are built: eight
-//     sources in flight per wave (90 VGPRs, 5 waves/SIMD: best issue rate, the default) and four
+//     sources in flight per wave (86-96 VGPRs, 5 waves/SIMD: best issue rate, the default) and four
 //     (<=64 VGPRs, 8 waves/SIMD: more, smaller workgroup slots for launches with few targets);
 //   * every wave is autonomous: it streams its own slice of the source array in 64-body
 //     (1 KiB) chunks HBM/L2 -> LDS by LDS-DMA (global_load_lds_dwordx4: coalesced float4
@@ -24,15 +24,15 @@
 #include <string.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "../../include/nbd.h"
 #include "direct_kernels.h"
 
 namespace {
 
-// grid = (target groups of 128, slabs); block = 256.
-// Wave jw = blockIdx.y*4 + w handles the logical source chunks [jw*q + min(jw, r), ... + q (+1 if jw < r)):
-// all chunks are spread over all waves to within one chunk (no idle tail waves).
-// KU = 8: 90 VGPRs, 5 waves/SIMD. KU = 4: capped at 64 VGPRs, 8 waves/SIMD.
+// grid = (target groups of 128, slabs); block = 256: accel_body (direct_kernels.h) on group blockIdx.x, slab blockIdx.y.
+// KU = 8: 96 VGPRs (UNI: 86), 5 waves/SIMD. KU = 4: capped at 64 VGPRs, 8 waves/SIMD.
 // UNI (round 3): every body has the SAME mass -- the published configurations (Plummer, m = 1 / N) among them. The mass
 // then factors out of the whole sum, a = (G m) sum_j d_ij s_ij^3: the per-pair multiply by m_j goes (11 packed ops +
 // 2 v_rsq_f32 per source and pair of targets instead of 12 + 2: 60 issue cycles per 128 pairs instead of 64), the
@@ -49,69 +49,11 @@ template <bool MASKED, int KU, bool UNI = false>
 __global__ __launch_bounds__(64 * kWaves, KU == 4 ? 8 : 5) void accel_kernel(
     const f4* __restrict__ src, const SrcView sv, const f4* __restrict__ tgt,
     int n_tgt, int tgt_off, float eps2, float scale, float* __restrict__ out, int out_rows, int tile_len) {
-  // [wave][buffer][64] staging + [wave][6][64] partials, ONE object (keeps hipcc's waits sane)
-  __shared__ f4 lds[kWaves * 2 * kChunk + kWaves * 6 * 64 / 4];
-  {
-    const int tz = blockIdx.z * tile_len;
-    src += tz; tgt += tz; out += (size_t)tz * 3;
-  }
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  __shared__ f4 lds[kAccelLdsF4];
+  const int tz = blockIdx.z * tile_len;
   const int t_base = blockIdx.x * kTgtPerWG;
-  const int i0 = t_base + lane, i1 = t_base + 64 + lane;
-  const f4 t0 = tgt[min(i0, n_tgt - 1)], t1 = tgt[min(i1, n_tgt - 1)];
-  const f2 xi = {t0.x, t1.x}, yi = {t0.y, t1.y}, zi = {t0.z, t1.z};
-  f2 ax = {0.f, 0.f}, ay = {0.f, 0.f}, az = {0.f, 0.f};
-  f2 e2 = {eps2, eps2};
-  asm volatile("" : "+v"(e2));  // keep eps^2 in VGPRs: an SGPR operand halves v_pk_fma issue
-
-  const int jw = blockIdx.y * kWaves + wave;
-  const int c_begin = jw * sv.cpw_q + min(jw, sv.cpw_r), c_end = c_begin + sv.cpw_q + (jw < sv.cpw_r ? 1 : 0);
-  f4* stage = &lds[wave * 2 * kChunk];
-  const f4* s_lane = src + lane;
-  // logical -> physical chunk: hop over the skipped run
-  auto phys = [&](int c) { return c + (c >= sv.skip_c0 ? sv.skip_cn : 0); };
-  if (c_begin < c_end)
-    __builtin_amdgcn_global_load_lds(GPTR(s_lane + (size_t)phys(c_begin) * kChunk), LPTR(stage), 16, 0, 0);
-  for (int c = c_begin; c < c_end; ++c) {
-    const int b = (c - c_begin) & 1;
-    if (c + 1 < c_end) {
-      __builtin_amdgcn_global_load_lds(GPTR(s_lane + (size_t)phys(c + 1) * kChunk),
-                                       LPTR(stage + (b ^ 1) * kChunk), 16, 0, 0);
-      asm volatile("s_waitcnt vmcnt(1)" ::: "memory");  // chunk c has landed, c+1 in flight
-    } else {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-    const f4* buf = stage + b * kChunk;
-    const int pc = phys(c);
-    const int j0 = pc * kChunk;
-    if (MASKED || pc == sv.edge0 || pc == sv.edge1 || (UNI && pc == sv.tail)) {
-#pragma unroll 4
-      for (int j = 0; j < kChunk; ++j)
-        interact<true, UNI>(buf[j], xi, yi, zi, e2, ax, ay, az, j0 + j, tgt_off + i0, tgt_off + i1, sv);
-    } else {
-#pragma unroll 1
-      for (int j = 0; j < kChunk; j += KU) interact_block<KU, UNI>(buf + j, xi, yi, zi, e2, ax, ay, az);
-    }
-  }
-
-  // wavefront partials -> LDS -> one coalesced (128 x 3) store per workgroup
-  float* red = reinterpret_cast<float*>(&lds[kWaves * 2 * kChunk]);  // [wave][comp*2+half][64]
-  float* mine = red + wave * 6 * 64;
-  mine[0 * 64 + lane] = ax.x; mine[1 * 64 + lane] = ax.y;
-  mine[2 * 64 + lane] = ay.x; mine[3 * 64 + lane] = ay.y;
-  mine[4 * 64 + lane] = az.x; mine[5 * 64 + lane] = az.y;
-  __syncthreads();
-  float* dst = out + ((size_t)blockIdx.y * out_rows + t_base) * 3;
-  const int n_valid = min(kTgtPerWG, n_tgt - t_base) * 3;
-  for (int o = threadIdx.x; o < n_valid; o += 64 * kWaves) {
-    const int lt = o / 3, comp = o - lt * 3;
-    const int idx = (comp * 2 + (lt >> 6)) * 64 + (lt & 63);
-    float sum = red[idx];
-#pragma unroll
-    for (int w = 1; w < kWaves; ++w) sum += red[w * 6 * 64 + idx];
-    dst[o] = __fmul_rn(scale, sum);
-  }
+  accel_body<KU, UNI>(src + tz, sv, std::integral_constant<bool, MASKED>{}, tgt + tz, n_tgt, tgt_off, t_base, blockIdx.y, eps2, scale, lds,
+                      out + (size_t)tz * 3 + ((size_t)blockIdx.y * out_rows + t_base) * 3);
 }
 
 // ---- symmetric force for EQUAL masses: every off-diagonal pair evaluated once (Newton's third law).
@@ -523,56 +465,9 @@ __global__ __launch_bounds__(256) void axpy_kernel(float* __restrict__ y, const 
 __global__ __launch_bounds__(64 * kWaves) void energy_kernel(const f4* __restrict__ posm, int n, int n_chunks,
                                                              float soft_, int all_masked,
                                                              double* __restrict__ partial_u) {
-  __shared__ f4 lds[kWaves * 2 * kChunk + 8];
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int t_base = blockIdx.x * kTgtPerWG;
-  const int i0 = t_base + lane, i1 = t_base + 64 + lane;
-  const f4 t0 = posm[min(i0, n - 1)], t1 = posm[min(i1, n - 1)];
-  const f2 xi = {t0.x, t1.x}, yi = {t0.y, t1.y}, zi = {t0.z, t1.z};
-  f2 u = {0.f, 0.f};
-  f2 soft = {soft_, soft_};
-  asm volatile("" : "+v"(soft));
-  // this block's share of the chunks [first chunk of the group, n_chunks), split over slabs x waves
-  const int c_lo = t_base / kChunk;
-  const int span = n_chunks - c_lo;
-  const int parts = gridDim.y * kWaves;
-  const int cpw = (span + parts - 1) / parts;
-  const int jw = blockIdx.y * kWaves + wave;
-  const int c_begin = min(c_lo + jw * cpw, n_chunks), c_end = min(c_begin + cpw, n_chunks);
-  const int c_diag_end = (t_base + kTgtPerWG + kChunk - 1) / kChunk;      // chunks below this touch j <= i
-  f4* stage = &lds[wave * 2 * kChunk];
-  const f4* s_lane = posm + lane;
-  if (c_begin < c_end)
-    __builtin_amdgcn_global_load_lds(GPTR(s_lane + (size_t)c_begin * kChunk), LPTR(stage), 16, 0, 0);
-  for (int c = c_begin; c < c_end; ++c) {
-    const int b = (c - c_begin) & 1;
-    if (c + 1 < c_end) {
-      __builtin_amdgcn_global_load_lds(GPTR(s_lane + (size_t)(c + 1) * kChunk), LPTR(stage + (b ^ 1) * kChunk), 16, 0, 0);
-      asm volatile("s_waitcnt vmcnt(1)" ::: "memory");
-    } else {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-    const f4* buf = stage + b * kChunk;
-    const int j0 = c * kChunk;
-    if (all_masked || c < c_diag_end || c == n_chunks - 1) {     // diagonal chunks and the padded tail
-#pragma unroll 4
-      for (int j = 0; j < kChunk; ++j) energy_pair<true>(buf[j], xi, yi, zi, soft, u, j0 + j, i0, i1, n);
-    } else {
-#pragma unroll 4
-      for (int j = 0; j < kChunk; ++j) energy_pair<false>(buf[j], xi, yi, zi, soft, u, j0 + j, i0, i1, n);
-    }
-  }
-  // U contribution of this wave: sum_i m_i u_i  (the -G factor is applied by the final kernel)
-  double acc = 0.0;
-  if (i0 < n) acc += (double)t0.w * (double)u.x;
-  if (i1 < n) acc += (double)t1.w * (double)u.y;
-  for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off);
-  double* red = reinterpret_cast<double*>(&lds[kWaves * 2 * kChunk]);
-  if (lane == 0) red[wave] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0)
-    partial_u[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+  __shared__ f4 lds[kEnergyLdsF4];
+  energy_body(posm, n, n_chunks, blockIdx.x * kTgtPerWG, blockIdx.y, gridDim.y, soft_, all_masked, lds,
+              partial_u + (size_t)blockIdx.y * gridDim.x + blockIdx.x);
 }
 
 __global__ __launch_bounds__(256) void kinetic_kernel(const f4* __restrict__ posm, const float* __restrict__ vel,
@@ -613,6 +508,11 @@ inline int energy_slabs(int groups) {
 }
 
 struct AccelPlan { int groups, slabs, n_chunks, cpw, variant; };   // cpw = the LARGEST chunk count of a wave
+
+// an explicit geometry: groups x slabs workgroups on n_chunks logical source chunks
+AccelPlan make_plan(int groups, int slabs, int n_chunks, int variant = 0) {
+  return AccelPlan{groups, slabs, n_chunks, ceil_div(n_chunks, slabs * kWaves), variant};
+}
 
 // Launch geometry for `n_chunks` logical source chunks against n_tgt targets.
 //
@@ -673,14 +573,8 @@ AccelPlan plan_accel(int n_src, int n_tgt) { return plan_chunks(ceil_div(n_src, 
 inline int check(hipError_t e) { return e == hipSuccess ? 0 : (int)e; }
 inline int launch_status() { return check(hipGetLastError()); }
 
-// all sources of an n_src array
-SrcView full_view(int n_src, const AccelPlan& p) {
-  SrcView v;
-  v.n_src = n_src; v.n_chunks = p.n_chunks; v.cpw_q = 0; v.cpw_r = 0;
-  v.skip_c0 = p.n_chunks; v.skip_cn = 0; v.ex_lo = 0; v.ex_hi = 0; v.edge0 = -1; v.edge1 = -1;
-  v.tail = (n_src % kChunk) ? n_src / kChunk : -1;
-  return v;
-}
+// all sources of an n_src array, split as the plan says
+SrcView full_view(int n_src, const AccelPlan& p) { return full_view(n_src, p.n_chunks, p.slabs); }
 
 // logical chunk count of "n_src sources without the indices [ex_lo, ex_hi)": whole chunks inside the
 // excluded range are hopped over, chunks that straddle one of its ends are walked with the element mask
@@ -707,8 +601,7 @@ int launch_accel(const float* posm_src, SrcView sv, const float* posm_tgt, int n
   if (out_rows <= 0) out_rows = n_tgt;
   const f4* s = reinterpret_cast<const f4*>(posm_src);
   const f4* t = reinterpret_cast<const f4*>(posm_tgt);
-  sv.n_chunks = p.n_chunks;
-  sv.cpw_q = p.n_chunks / (p.slabs * kWaves); sv.cpw_r = p.n_chunks % (p.slabs * kWaves);
+  split_chunks(sv, p.n_chunks, p.slabs);
   const bool masked = eps2 < kEps2Masked;
 #define NBD_LAUNCH(M, K, U) accel_kernel<M, K, U><<<grid, block, 0, st>>>(s, sv, t, n_tgt, off, eps2, direct_scale, slabs_or_acc, out_rows, tile_len)
   if (uniform) {
@@ -756,9 +649,7 @@ int launch_sym(const float* posm, int n, float eps2, float* slots, hipStream_t s
   const SymPlan sp = plan_sym(n);
   const f4* pm = reinterpret_cast<const f4*>(posm);
   // the diagonal blocks (a, a): the all-pairs kernel on each tile, slot 0
-  AccelPlan dp;
-  dp.groups = kSymTile / kTgtPerWG; dp.slabs = 1; dp.n_chunks = kSymChunks; dp.variant = 0;
-  dp.cpw = ceil_div(kSymChunks, kWaves);
+  const AccelPlan dp = make_plan(kSymTile / kTgtPerWG, 1, kSymChunks);
   int rc = launch_accel(posm, full_view(kSymTile, dp), posm, kSymTile, 0, eps2, 1.0f, slots, dp, st, true, n, sp.m,
                         kSymTile);
   if (rc) return rc;
@@ -775,20 +666,15 @@ int launch_sym(const float* posm, int n, float eps2, float* slots, hipStream_t s
   }
   if (sp.rem == 0) return 0;
   // remainder rows [core, n) against all n sources, split over every slot (the symmetric launches never write them)
-  AccelPlan tp;
-  tp.groups = ceil_div(sp.rem, kTgtPerWG); tp.slabs = sp.total_slots; tp.n_chunks = ceil_div(n, kChunk); tp.variant = 0;
-  tp.cpw = ceil_div(tp.n_chunks, tp.slabs * kWaves);
+  const AccelPlan tp = make_plan(ceil_div(sp.rem, kTgtPerWG), sp.total_slots, ceil_div(n, kChunk));
   rc = launch_accel(posm, full_view(n, tp), posm + (size_t)sp.core * 4, sp.rem, sp.core, eps2, 1.0f,
                     slots + (size_t)sp.core * 3, tp, st, true, n);
   if (rc) return rc;
   // core rows against the remainder sources: the last slot
   SrcView sv;
-  AccelPlan cp;
-  cp.n_chunks = excluded_view(n, 0, sp.core, &sv);
-  cp.groups = sp.core / kTgtPerWG; cp.slabs = 1; cp.variant = 0; cp.cpw = ceil_div(cp.n_chunks, kWaves);
+  const AccelPlan cp = make_plan(sp.core / kTgtPerWG, 1, excluded_view(n, 0, sp.core, &sv));
   return launch_accel(posm, sv, posm, sp.core, 0, eps2, 1.0f, slots + (size_t)sp.slots * n * 3, cp, st, true, n);
 }
-
 
 }  // namespace
 
@@ -908,12 +794,8 @@ int nbd_accel_tuned_f32(const float* posm_src, int n_src, int exclude_lo, int ex
   if (!workspace || workspace_bytes < nbd_accel_tuned_workspace_bytes(n_tgt, slabs)) return NBD_E_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
   SrcView sv;
-  AccelPlan p;
-  p.n_chunks = excluded_view(n_src, exclude_lo, exclude_hi, &sv);
-  p.groups = ceil_div(n_tgt, kTgtPerWG);
-  p.slabs = slabs;
-  p.variant = variant;
-  p.cpw = ceil_div(p.n_chunks > 0 ? p.n_chunks : 1, slabs * kWaves);
+  const AccelPlan p =
+      make_plan(ceil_div(n_tgt, kTgtPerWG), slabs, excluded_view(n_src, exclude_lo, exclude_hi, &sv), variant);
   float* sl = static_cast<float*>(workspace);
   const int n3 = n_tgt * 3;
   if (p.n_chunks == 0) {
@@ -976,21 +858,22 @@ size_t nbd_shard_workspace_bytes(int n_total, int lo, int n_local) {
   return (size_t)(sp.local.slabs + sp.remote.slabs) * n_local * 3 * sizeof(float);
 }
 
-int nbd_shard_force_local_f32(const float* posm_local, int n_local, float softening_sq, void* workspace,
-                              size_t workspace_bytes, int n_total, int lo, nbd_stream_t stream) {
+// the rank's own block: targets and sources are the same array, the diagonal is at j == i (offset 0)
+static int shard_force_local(const float* posm_local, int n_local, float softening_sq, void* workspace,
+                             size_t workspace_bytes, int n_total, int lo, nbd_stream_t stream, bool uniform) {
   if (n_local < 0 || n_total < 0 || lo < 0 || lo + n_local > n_total) return NBD_E_BADARG;
   if (n_local == 0) return 0;
   if (!posm_local || misaligned16(posm_local)) return NBD_E_BADARG;
   if (!workspace || workspace_bytes < nbd_shard_workspace_bytes(n_total, lo, n_local)) return NBD_E_WORKSPACE;
   const ShardPlan sp = plan_shard(n_total, lo, n_local);
-  // targets and sources are the same array: the diagonal is at j == i (offset 0)
   return launch_accel(posm_local, full_view(n_local, sp.local), posm_local, n_local, 0, softening_sq, 1.0f,
-                      static_cast<float*>(workspace), sp.local, (hipStream_t)stream);
+                      static_cast<float*>(workspace), sp.local, (hipStream_t)stream, uniform);
 }
 
-int nbd_shard_force_remote_f32(const float* posm_all, int n_total, const float* posm_local, int n_local, int lo,
-                               float softening_sq, float g_const, float* acc_out, float* vel, float c_kick,
-                               void* workspace, size_t workspace_bytes, nbd_stream_t stream) {
+// every other rank's bodies, then acc = g_scale * (all slabs, local ones first) and the fused kick
+static int shard_force_remote(const float* posm_all, int n_total, const float* posm_local, int n_local, int lo,
+                              float softening_sq, float g_scale, float* acc_out, float* vel, float c_kick,
+                              void* workspace, size_t workspace_bytes, nbd_stream_t stream, bool uniform) {
   if (n_local < 0 || n_total < 0 || lo < 0 || lo + n_local > n_total) return NBD_E_BADARG;
   if (n_local == 0) return 0;
   if (!posm_all || !posm_local || !acc_out || misaligned16(posm_all) || misaligned16(posm_local)) return NBD_E_BADARG;
@@ -1004,48 +887,38 @@ int nbd_shard_force_remote_f32(const float* posm_all, int n_total, const float* 
     excluded_view(n_total, lo, lo + n_local, &sv);
     // the diagonal never occurs here (every j in [lo, lo + n_local) is excluded); lo keeps the index meaning
     int rc = launch_accel(posm_all, sv, posm_local, n_local, lo, softening_sq, 1.0f,
-                          slabs + (size_t)sp.local.slabs * n3, sp.remote, st);
+                          slabs + (size_t)sp.local.slabs * n3, sp.remote, st, uniform);
     if (rc) return rc;
   }
-  finish_kernel<<<ceil_div(n3, 64), 256, 0, st>>>(slabs, sp.local.slabs + sp.remote.slabs, (size_t)n3, g_const,
+  finish_kernel<<<ceil_div(n3, 64), 256, 0, st>>>(slabs, sp.local.slabs + sp.remote.slabs, (size_t)n3, g_scale,
                                                    acc_out, vel, c_kick, n3);
   return launch_status();
+}
+
+int nbd_shard_force_local_f32(const float* posm_local, int n_local, float softening_sq, void* workspace,
+                              size_t workspace_bytes, int n_total, int lo, nbd_stream_t stream) {
+  return shard_force_local(posm_local, n_local, softening_sq, workspace, workspace_bytes, n_total, lo, stream, false);
+}
+
+int nbd_shard_force_remote_f32(const float* posm_all, int n_total, const float* posm_local, int n_local, int lo,
+                               float softening_sq, float g_const, float* acc_out, float* vel, float c_kick,
+                               void* workspace, size_t workspace_bytes, nbd_stream_t stream) {
+  return shard_force_remote(posm_all, n_total, posm_local, n_local, lo, softening_sq, g_const, acc_out, vel, c_kick,
+                            workspace, workspace_bytes, stream, false);
 }
 
 // The two force launches of the range-sharded step for a system of EQUAL masses (see nbd_leapfrog_step_uniform_f32): the
 // kernels without their per-pair mass multiply, g_const * mass_value applied once by the finishing kernel.
 int nbd_shard_force_local_uniform_f32(const float* posm_local, int n_local, float softening_sq, void* workspace,
                                       size_t workspace_bytes, int n_total, int lo, nbd_stream_t stream) {
-  if (n_local < 0 || n_total < 0 || lo < 0 || lo + n_local > n_total) return NBD_E_BADARG;
-  if (n_local == 0) return 0;
-  if (!posm_local || misaligned16(posm_local)) return NBD_E_BADARG;
-  if (!workspace || workspace_bytes < nbd_shard_workspace_bytes(n_total, lo, n_local)) return NBD_E_WORKSPACE;
-  const ShardPlan sp = plan_shard(n_total, lo, n_local);
-  return launch_accel(posm_local, full_view(n_local, sp.local), posm_local, n_local, 0, softening_sq, 1.0f,
-                      static_cast<float*>(workspace), sp.local, (hipStream_t)stream, true);
+  return shard_force_local(posm_local, n_local, softening_sq, workspace, workspace_bytes, n_total, lo, stream, true);
 }
 
 int nbd_shard_force_remote_uniform_f32(const float* posm_all, int n_total, const float* posm_local, int n_local, int lo,
                                        float softening_sq, float g_const, float mass_value, float* acc_out, float* vel,
                                        float c_kick, void* workspace, size_t workspace_bytes, nbd_stream_t stream) {
-  if (n_local < 0 || n_total < 0 || lo < 0 || lo + n_local > n_total) return NBD_E_BADARG;
-  if (n_local == 0) return 0;
-  if (!posm_all || !posm_local || !acc_out || misaligned16(posm_all) || misaligned16(posm_local)) return NBD_E_BADARG;
-  if (!workspace || workspace_bytes < nbd_shard_workspace_bytes(n_total, lo, n_local)) return NBD_E_WORKSPACE;
-  hipStream_t st = (hipStream_t)stream;
-  const ShardPlan sp = plan_shard(n_total, lo, n_local);
-  float* slabs = static_cast<float*>(workspace);
-  const int n3 = 3 * n_local;
-  if (sp.remote.slabs > 0) {
-    SrcView sv;
-    excluded_view(n_total, lo, lo + n_local, &sv);
-    int rc = launch_accel(posm_all, sv, posm_local, n_local, lo, softening_sq, 1.0f,
-                          slabs + (size_t)sp.local.slabs * n3, sp.remote, st, true);
-    if (rc) return rc;
-  }
-  finish_kernel<<<ceil_div(n3, 64), 256, 0, st>>>(slabs, sp.local.slabs + sp.remote.slabs, (size_t)n3, g_const * mass_value,
-                                                   acc_out, vel, c_kick, n3);
-  return launch_status();
+  return shard_force_remote(posm_all, n_total, posm_local, n_local, lo, softening_sq, g_const * mass_value, acc_out, vel,
+                            c_kick, workspace, workspace_bytes, stream, true);
 }
 
 int nbd_kick_drift_f32(float* pos, float* vel, const float* acc, const float* mass, int n,
@@ -1079,28 +952,44 @@ int nbd_snapshot_f32(const float* pos, const float* vel, const float* acc, int n
   return launch_status();
 }
 
+// What the whole-system steps share: check, update the bodies and pack them (the kick-drift of a leapfrog step with
+// acc_in; euler: a plain pack), the force of all n bodies into slabs, then acc = g_scale * (slab sum) and the fused kick
+// v += c_kick acc. uniform: the kernels without the per-pair mass multiply (g_scale carries the mass), and from
+// kSymStepMinN bodies on every pair once (accel_sym2_kernel).
+static int step_force(float* pos, float* vel, const float* acc_in, float* acc_out, const float* mass, int n, bool euler,
+                      float c_kick, float c_drift, float softening_sq, float g_scale, bool uniform, float* posm,
+                      void* workspace, size_t workspace_bytes, nbd_stream_t stream, void* ev_force_begin,
+                      void* ev_force_end) {
+  if (n < 0) return NBD_E_BADARG;
+  if (n == 0) return 0;
+  if (!pos || !vel || (!euler && !acc_in) || !acc_out || !mass || !posm || misaligned16(posm)) return NBD_E_BADARG;
+  hipStream_t st = (hipStream_t)stream;
+  const bool sym = uniform && sym_step(n, softening_sq);
+  const AccelPlan p = plan_accel(n, n);
+  // one slab also goes to scratch
+  const size_t need = sym ? sym_workspace_bytes(n) : (size_t)p.slabs * n * 3 * sizeof(float);
+  if (!workspace || workspace_bytes < need) return NBD_E_WORKSPACE;
+  int rc = euler ? nbd_pack_posm_f32(pos, mass, n, posm, stream)
+                 : nbd_kick_drift_f32(pos, vel, acc_in, mass, n, c_kick, c_drift, posm, stream);
+  if (rc) return rc;
+  float* slabs = static_cast<float*>(workspace);
+  if (ev_force_begin && (rc = check(hipEventRecord((hipEvent_t)ev_force_begin, st)))) return rc;
+  if (sym) rc = launch_sym(posm, n, softening_sq, slabs, st, 2);
+  else rc = launch_accel(posm, full_view(n, p), posm, n, 0, softening_sq, 1.0f, slabs, p, st, uniform);
+  if (rc) return rc;
+  if (ev_force_end && (rc = check(hipEventRecord((hipEvent_t)ev_force_end, st)))) return rc;
+  const int n3 = 3 * n;
+  const int n_slabs = sym ? plan_sym(n).total_slots : p.slabs;
+  finish_kernel<<<ceil_div(n3, 64), 256, 0, st>>>(slabs, n_slabs, (size_t)n3, g_scale, acc_out, vel, c_kick, n3);
+  return launch_status();
+}
+
 int nbd_leapfrog_step_ev_f32(float* pos, float* vel, const float* acc_in, float* acc_out,
                           const float* mass, int n, float dt_half, float dt, float softening_sq,
                           float g_const, float* posm, void* workspace, size_t workspace_bytes,
                           nbd_stream_t stream, void* ev_force_begin, void* ev_force_end) {
-  if (n < 0) return NBD_E_BADARG;
-  if (n == 0) return 0;
-  if (!pos || !vel || !acc_in || !acc_out || !mass || !posm || misaligned16(posm)) return NBD_E_BADARG;
-  hipStream_t st = (hipStream_t)stream;
-  const AccelPlan p = plan_accel(n, n);
-  const size_t need = (size_t)p.slabs * n * 3 * sizeof(float);  // one slab also goes to scratch
-  if (!workspace || workspace_bytes < need) return NBD_E_WORKSPACE;
-  int rc = nbd_kick_drift_f32(pos, vel, acc_in, mass, n, dt_half, dt, posm, stream);
-  if (rc) return rc;
-  float* slabs = static_cast<float*>(workspace);
-  if (ev_force_begin && (rc = check(hipEventRecord((hipEvent_t)ev_force_begin, st)))) return rc;
-  rc = launch_accel(posm, full_view(n, p), posm, n, 0, softening_sq, 1.0f, slabs, p, st);
-  if (rc) return rc;
-  if (ev_force_end && (rc = check(hipEventRecord((hipEvent_t)ev_force_end, st)))) return rc;
-  const int n3 = 3 * n;
-  finish_kernel<<<ceil_div(n3, 64), 256, 0, st>>>(slabs, p.slabs, (size_t)n3, g_const, acc_out, vel,
-                                                   dt_half, n3);
-  return launch_status();
+  return step_force(pos, vel, acc_in, acc_out, mass, n, false, dt_half, dt, softening_sq, g_const, false, posm,
+                    workspace, workspace_bytes, stream, ev_force_begin, ev_force_end);
 }
 
 // LeapFrogSimulator.step (simulation.py:153-170) for a system whose bodies all have the SAME mass (the published
@@ -1114,27 +1003,8 @@ int nbd_leapfrog_step_uniform_f32(float* pos, float* vel, const float* acc_in, f
                                   float mass_value, int n, float dt_half, float dt, float softening_sq, float g_const,
                                   float* posm, void* workspace, size_t workspace_bytes, nbd_stream_t stream,
                                   void* ev_force_begin, void* ev_force_end) {
-  if (n < 0) return NBD_E_BADARG;
-  if (n == 0) return 0;
-  if (!pos || !vel || !acc_in || !acc_out || !mass || !posm || misaligned16(posm)) return NBD_E_BADARG;
-  hipStream_t st = (hipStream_t)stream;
-  const bool sym = sym_step(n, softening_sq);   // large systems: every pair once (accel_sym2_kernel)
-  const AccelPlan p = plan_accel(n, n);
-  const size_t need = sym ? sym_workspace_bytes(n) : (size_t)p.slabs * n * 3 * sizeof(float);
-  if (!workspace || workspace_bytes < need) return NBD_E_WORKSPACE;
-  int rc = nbd_kick_drift_f32(pos, vel, acc_in, mass, n, dt_half, dt, posm, stream);
-  if (rc) return rc;
-  float* slabs = static_cast<float*>(workspace);
-  if (ev_force_begin && (rc = check(hipEventRecord((hipEvent_t)ev_force_begin, st)))) return rc;
-  if (sym) rc = launch_sym(posm, n, softening_sq, slabs, st, 2);
-  else rc = launch_accel(posm, full_view(n, p), posm, n, 0, softening_sq, 1.0f, slabs, p, st, true);
-  if (rc) return rc;
-  if (ev_force_end && (rc = check(hipEventRecord((hipEvent_t)ev_force_end, st)))) return rc;
-  const int n3 = 3 * n;
-  const int n_slabs = sym ? plan_sym(n).total_slots : p.slabs;
-  finish_kernel<<<ceil_div(n3, 64), 256, 0, st>>>(slabs, n_slabs, (size_t)n3, g_const * mass_value, acc_out, vel,
-                                                   dt_half, n3);
-  return launch_status();
+  return step_force(pos, vel, acc_in, acc_out, mass, n, false, dt_half, dt, softening_sq, g_const * mass_value, true,
+                    posm, workspace, workspace_bytes, stream, ev_force_begin, ev_force_end);
 }
 
 int nbd_leapfrog_step_f32(float* pos, float* vel, const float* acc_in, float* acc_out,
@@ -1148,21 +1018,8 @@ int nbd_leapfrog_step_f32(float* pos, float* vel, const float* acc_in, float* ac
 int nbd_euler_step_f32(float* pos, float* vel, float* acc_out, const float* mass, int n, float dt,
                        float softening_sq, float g_const, float* posm, void* workspace,
                        size_t workspace_bytes, nbd_stream_t stream) {
-  if (n < 0) return NBD_E_BADARG;
-  if (n == 0) return 0;
-  if (!pos || !vel || !acc_out || !mass || !posm || misaligned16(posm)) return NBD_E_BADARG;
-  hipStream_t st = (hipStream_t)stream;
-  const AccelPlan p = plan_accel(n, n);
-  const size_t need = (size_t)p.slabs * n * 3 * sizeof(float);
-  if (!workspace || workspace_bytes < need) return NBD_E_WORKSPACE;
-  int rc = nbd_pack_posm_f32(pos, mass, n, posm, stream);
-  if (rc) return rc;
-  float* slabs = static_cast<float*>(workspace);
-  rc = launch_accel(posm, full_view(n, p), posm, n, 0, softening_sq, 1.0f, slabs, p, st);
-  if (rc) return rc;
-  const int n3 = 3 * n;
-  finish_kernel<<<ceil_div(n3, 64), 256, 0, st>>>(slabs, p.slabs, (size_t)n3, g_const, acc_out, vel, dt, n3);
-  rc = launch_status();
+  const int rc = step_force(pos, vel, nullptr, acc_out, mass, n, true, dt, 0.f, softening_sq, g_const, false, posm,
+                            workspace, workspace_bytes, stream, nullptr, nullptr);
   if (rc) return rc;
   return nbd_drift_f32(pos, vel, n, dt, stream);
 }

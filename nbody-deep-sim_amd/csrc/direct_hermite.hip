@@ -20,10 +20,8 @@
 
 namespace {
 
-// Acceleration + jerk of all n bodies under all n bodies. accel_kernel's structure: grid = (target groups of 128,
-// slabs), block = 4 waves; two targets per lane in packed fp32; every wave streams its own balanced slice of the chunks,
-// each chunk = 64 positions + 64 velocities (2 KiB) by LDS-DMA, double-buffered behind a counted vmcnt; the 4 waves'
-// partials are reduced through LDS into one coalesced store of 6 x 128 floats per workgroup. out: float[slab][6][n].
+// Acceleration + jerk of all n bodies under all n bodies: accel_jerk_body (hermite_kernels.h) with grid = (target groups
+// of 128, slabs), the chunks spread over all slabs x 4 waves to within one. out: float[slab][6][n].
 // KU = 2 (the default): 76 VGPRs, 6 waves per SIMD, and hipcc issues each pair of rsq's back to back with no s_nop in
 // the loop; KU = 4: 88 VGPRs, 5 waves per SIMD, but hipcc interleaves the rsq's with their consumers and pads the
 // transcendental hazards with s_nop (14-19 per 4 sources). 16 KiB of LDS per workgroup (the partials reuse each wave's
@@ -32,76 +30,13 @@ template <bool MASKED, int KU>
 __global__ __launch_bounds__(64 * kWaves, KU == 2 ? 6 : 5) void accel_jerk_kernel(
     const f4* __restrict__ posm, const f4* __restrict__ velp, int n, int cpw_q, int cpw_r, float eps2,
     float* __restrict__ out) {
-  // [wave][buffer][pos | vel][64] staging; after its last chunk a wave puts its [12][64] partials into its own part
   __shared__ f4 lds[kWaves * 4 * kChunk];
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int t_base = blockIdx.x * kTgtPerWG;
-  const int i0 = t_base + lane, i1 = t_base + 64 + lane;
-  const f4 t0 = posm[min(i0, n - 1)], t1 = posm[min(i1, n - 1)];
-  const f4 u0 = velp[min(i0, n - 1)], u1 = velp[min(i1, n - 1)];
-  const f2 xi = {t0.x, t1.x}, yi = {t0.y, t1.y}, zi = {t0.z, t1.z};
-  const f2 ui = {u0.x, u1.x}, vi = {u0.y, u1.y}, wi = {u0.z, u1.z};
-  f2 acc[9];
-#pragma unroll
-  for (int k = 0; k < 9; ++k) acc[k] = f2{0.f, 0.f};
-  f2 e2 = {eps2, eps2};
-  asm volatile("" : "+v"(e2));  // keep eps^2 in VGPRs: an SGPR operand halves v_pk_fma issue
-
-  const int jw = blockIdx.y * kWaves + wave;
+  const int i0 = t_base + (threadIdx.x & 63), i1 = i0 + 64;
+  const int jw = blockIdx.y * kWaves + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int c_begin = jw * cpw_q + min(jw, cpw_r), c_end = c_begin + cpw_q + (jw < cpw_r ? 1 : 0);
-  f4* stage = &lds[wave * 4 * kChunk];
-  const f4* p_lane = posm + lane;
-  const f4* v_lane = velp + lane;
-  auto fetch = [&](int c, int b) {
-    __builtin_amdgcn_global_load_lds(GPTR(p_lane + (size_t)c * kChunk), LPTR(stage + b * 2 * kChunk), 16, 0, 0);
-    __builtin_amdgcn_global_load_lds(GPTR(v_lane + (size_t)c * kChunk), LPTR(stage + b * 2 * kChunk + kChunk), 16, 0, 0);
-  };
-  if (c_begin < c_end) fetch(c_begin, 0);
-  for (int c = c_begin; c < c_end; ++c) {
-    const int b = (c - c_begin) & 1;
-    if (c + 1 < c_end) {
-      fetch(c + 1, b ^ 1);
-      asm volatile("s_waitcnt vmcnt(2)" ::: "memory");  // chunk c has landed, c+1 (two loads) in flight
-    } else {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-    const f4* bp = stage + b * 2 * kChunk;
-    const f4* bv = bp + kChunk;
-    if (MASKED) {
-      const int j0 = c * kChunk;
-#pragma unroll 2
-      for (int j = 0; j < kChunk; ++j)
-        jerk_pair_masked(bp[j], bv[j], xi, yi, zi, ui, vi, wi, e2, acc, j0 + j, i0, i1, n);
-    } else {
-#pragma unroll 1
-      for (int j = 0; j < kChunk; j += KU) jerk_block<KU>(bp + j, bv + j, xi, yi, zi, ui, vi, wi, e2, acc);
-    }
-  }
-
-  // j = (w dv) - 3 (r.v s^2 w dr); wavefront partials -> LDS -> one coalesced (6 x 128) store per workgroup. A wave's
-  // staging is free here: its loads have landed (vmcnt(0) on the last chunk) and its reads precede these writes.
-  constexpr int kPart = 4 * kChunk * 4;                              // floats per wave: [comp*2+half][64] in the first 768
-  float* red = reinterpret_cast<float*>(lds);
-  float* mine = red + wave * kPart;
-#pragma unroll
-  for (int k = 0; k < 6; ++k) {
-    const f2 v = k < 3 ? acc[k] : acc[k] - 3.0f * acc[k + 3];
-    mine[(2 * k) * 64 + lane] = v.x;
-    mine[(2 * k + 1) * 64 + lane] = v.y;
-  }
-  __syncthreads();
-  float* dst = out + (size_t)blockIdx.y * 6 * n + t_base;
-  const int n_valid = min(kTgtPerWG, n - t_base);
-  for (int o = threadIdx.x; o < 6 * kTgtPerWG; o += 64 * kWaves) {
-    const int comp = o >> 7, lt = o & 127;
-    if (lt >= n_valid) continue;
-    const int idx = (comp * 2 + (lt >> 6)) * 64 + (lt & 63);
-    float sum = red[idx];
-#pragma unroll
-    for (int w = 1; w < kWaves; ++w) sum += red[w * kPart + idx];
-    dst[(size_t)comp * n + lt] = sum;
-  }
+  accel_jerk_body<MASKED, KU>(posm, velp, n, min(i0, n - 1), min(i1, n - 1), i0, i1, c_begin, c_end, eps2, lds,
+                              out + (size_t)blockIdx.y * 6 * n + t_base, n, min(kTgtPerWG, n - t_base));
 }
 
 // fp32 step constants, each formed in double and rounded once

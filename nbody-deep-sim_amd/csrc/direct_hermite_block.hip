@@ -37,82 +37,23 @@ constexpr int kActMaxSlabs = 256;
 enum { kTNext = 0, kNAct = 1, kClamped = 2, kTCur = 3, kCursor = 4, kDone = 5, kHist = 8 };
 static_assert(kHist + kMaxLevel + 1 <= NBD_HBLOCK_SCHED_INTS, "sched holds the level histogram");
 
-// Acceleration + jerk of the n_act targets act[0..n_act) under all n sources: accel_jerk_kernel with its targets gathered
-// through the index list. Grid = (ceil(n_act / 128), slabs), block = 4 waves; same LDS-DMA chunk stream, same fixed-order
-// wave reduction. The lanes behind n_act repeat the last target and store nothing. out: float[slab][6][n_act], in list
-// order. A target's sums depend only on n and the slab count, not on where it sits in the list.
+// Acceleration + jerk of the n_act targets act[0..n_act) under all n sources: accel_jerk_kernel<MASKED, 2> with its
+// targets gathered through the index list (the same accel_jerk_body, so the same chunk stream and wave reduction).
+// Grid = (ceil(n_act / 128), slabs), block = 4 waves. The lanes behind n_act repeat the last target and store nothing.
+// out: float[slab][6][n_act], in list order. A target's sums depend only on n and the slab count, not on where it sits
+// in the list.
 template <bool MASKED>
 __global__ __launch_bounds__(64 * kWaves, 6) void accel_jerk_active_kernel(
     const f4* __restrict__ posm, const f4* __restrict__ velp, int n, const int* __restrict__ act, int n_act, int cpw_q,
     int cpw_r, float eps2, float* __restrict__ out) {
-  constexpr int KU = 2;
   __shared__ f4 lds[kWaves * 4 * kChunk];
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int t_base = blockIdx.x * kTgtPerWG;
-  const int i0 = act[min(t_base + lane, n_act - 1)], i1 = act[min(t_base + 64 + lane, n_act - 1)];
-  const f4 t0 = posm[i0], t1 = posm[i1];
-  const f4 u0 = velp[i0], u1 = velp[i1];
-  const f2 xi = {t0.x, t1.x}, yi = {t0.y, t1.y}, zi = {t0.z, t1.z};
-  const f2 ui = {u0.x, u1.x}, vi = {u0.y, u1.y}, wi = {u0.z, u1.z};
-  f2 acc[9];
-#pragma unroll
-  for (int k = 0; k < 9; ++k) acc[k] = f2{0.f, 0.f};
-  f2 e2 = {eps2, eps2};
-  asm volatile("" : "+v"(e2));  // keep eps^2 in VGPRs: an SGPR operand halves v_pk_fma issue
-
-  const int jw = blockIdx.y * kWaves + wave;
+  const int l0 = t_base + (threadIdx.x & 63);
+  const int i0 = act[min(l0, n_act - 1)], i1 = act[min(l0 + 64, n_act - 1)];
+  const int jw = blockIdx.y * kWaves + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int c_begin = jw * cpw_q + min(jw, cpw_r), c_end = c_begin + cpw_q + (jw < cpw_r ? 1 : 0);
-  f4* stage = &lds[wave * 4 * kChunk];
-  const f4* p_lane = posm + lane;
-  const f4* v_lane = velp + lane;
-  auto fetch = [&](int c, int b) {
-    __builtin_amdgcn_global_load_lds(GPTR(p_lane + (size_t)c * kChunk), LPTR(stage + b * 2 * kChunk), 16, 0, 0);
-    __builtin_amdgcn_global_load_lds(GPTR(v_lane + (size_t)c * kChunk), LPTR(stage + b * 2 * kChunk + kChunk), 16, 0, 0);
-  };
-  if (c_begin < c_end) fetch(c_begin, 0);
-  for (int c = c_begin; c < c_end; ++c) {
-    const int b = (c - c_begin) & 1;
-    if (c + 1 < c_end) {
-      fetch(c + 1, b ^ 1);
-      asm volatile("s_waitcnt vmcnt(2)" ::: "memory");  // chunk c has landed, c+1 (two loads) in flight
-    } else {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-    const f4* bp = stage + b * 2 * kChunk;
-    const f4* bv = bp + kChunk;
-    if (MASKED) {
-      const int j0 = c * kChunk;
-#pragma unroll 2
-      for (int j = 0; j < kChunk; ++j)
-        jerk_pair_masked(bp[j], bv[j], xi, yi, zi, ui, vi, wi, e2, acc, j0 + j, i0, i1, n);
-    } else {
-#pragma unroll 1
-      for (int j = 0; j < kChunk; j += KU) jerk_block<KU>(bp + j, bv + j, xi, yi, zi, ui, vi, wi, e2, acc);
-    }
-  }
-
-  constexpr int kPart = 4 * kChunk * 4;
-  float* red = reinterpret_cast<float*>(lds);
-  float* mine = red + wave * kPart;
-#pragma unroll
-  for (int k = 0; k < 6; ++k) {
-    const f2 v = k < 3 ? acc[k] : acc[k] - 3.0f * acc[k + 3];
-    mine[(2 * k) * 64 + lane] = v.x;
-    mine[(2 * k + 1) * 64 + lane] = v.y;
-  }
-  __syncthreads();
-  float* dst = out + (size_t)blockIdx.y * 6 * n_act + t_base;
-  const int n_valid = min(kTgtPerWG, n_act - t_base);
-  for (int o = threadIdx.x; o < 6 * kTgtPerWG; o += 64 * kWaves) {
-    const int comp = o >> 7, lt = o & 127;
-    if (lt >= n_valid) continue;
-    const int idx = (comp * 2 + (lt >> 6)) * 64 + (lt & 63);
-    float sum = red[idx];
-#pragma unroll
-    for (int w = 1; w < kWaves; ++w) sum += red[w * kPart + idx];
-    dst[(size_t)comp * n_act + lt] = sum;
-  }
+  accel_jerk_body<MASKED, 2>(posm, velp, n, i0, i1, i0, i1, c_begin, c_end, eps2, lds,
+                             out + (size_t)blockIdx.y * 6 * n_act + t_base, n_act, min(kTgtPerWG, n_act - t_base));
 }
 
 // The Aarseth criterion sqrt(eta num / den). den = 0 (no jerk and no higher derivative: a lone body, or one in a

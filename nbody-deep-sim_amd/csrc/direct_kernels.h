@@ -1,6 +1,10 @@
 // direct_kernels.h -- device building blocks shared by the direct-force translation units (direct_force.hip: one
-// system; direct_batch.hip: many independent systems back to back). The definitions sit in an anonymous namespace:
-// every translation unit that includes this file gets its own inlined copies.
+// system; direct_batch.hip: many independent systems back to back): the pair arithmetic (interact, interact_block,
+// energy_pair) and, one level up, the wave bodies that walk the source chunks with it (accel_body, energy_body: target
+// loads, LDS-DMA chunk walk, pair loop, four-wave reduction, store). A force or energy kernel of either unit is a
+// prologue that reads its geometry (from blockIdx and arguments, or from a scene record) and one call of the body: that
+// is what keeps a scene of a batch bit-identical to the same system run alone.
+// The definitions sit in an anonymous namespace: every translation unit that includes this file gets its own inlined copies.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -39,6 +43,22 @@ struct SrcView {
   int tail;            // uniform-mass kernels only: the physical chunk that holds padding behind n_src (-1: none); it takes
                        // the masked path too (without the per-source mass factor a padding entry is not a zero any more)
 };
+
+// the balanced split of a view's n_chunks logical chunks over slabs x 4 waves
+__host__ __device__ inline void split_chunks(SrcView& v, int n_chunks, int slabs) {
+  v.n_chunks = n_chunks;
+  v.cpw_q = n_chunks / (slabs * kWaves); v.cpw_r = n_chunks % (slabs * kWaves);
+}
+
+// all sources of an n_src array (n_chunks = ceil(n_src / 64)), split over `slabs` slabs
+__host__ __device__ inline SrcView full_view(int n_src, int n_chunks, int slabs) {
+  SrcView v;
+  v.n_src = n_src;
+  split_chunks(v, n_chunks, slabs);
+  v.skip_c0 = n_chunks; v.skip_cn = 0; v.ex_lo = 0; v.ex_hi = 0; v.edge0 = -1; v.edge1 = -1;
+  v.tail = (n_src % kChunk) ? n_src / kChunk : -1;
+  return v;
+}
 
 // One source against the lane's two targets. 12 packed ops + 2 v_rsq_f32 (UNI: 11, see accel_kernel).
 template <bool MASKED, bool UNI = false>
@@ -109,6 +129,78 @@ __device__ __forceinline__ void interact_block(const f4* __restrict__ buf, const
   }
 }
 
+// The wave body of the all-pairs force kernels. A workgroup is 4 waves on the 128 targets tgt[t_base ..] (two per lane in
+// packed fp32; global index tgt_off + row, what the masked loop takes for the lane's own source). Wave jw = slab * 4 + w
+// walks the logical source chunks [jw*q + min(jw, r), ... + q (+1 if jw < r)) of the view: all chunks are spread over all
+// waves to within one chunk (no idle tail waves). Each chunk comes HBM/L2 -> LDS by LDS-DMA, double-buffered behind a
+// counted vmcnt; `masked` (or an edge chunk of the view, or the padded tail of a UNI walk) takes the index-masked loop,
+// every other chunk interact_block<KU>. `masked` is a bool known at run time (a scene of a batch: tested once per chunk)
+// or a std::integral_constant where the kernel's template parameter decides (the dead loop is never emitted). The 4 waves' partials are reduced through LDS ([wave][comp*2+half][64]) in wave
+// order into one coalesced store dst[t * 3 + comp] = scale * sum for the valid targets. lds: the workgroup's
+// f4[kAccelLdsF4]: [wave][buffer][64] staging + [wave][6][64] partials, ONE object (keeps hipcc's waits sane).
+constexpr int kAccelLdsF4 = kWaves * 2 * kChunk + kWaves * 6 * 64 / 4;
+
+template <int KU, bool UNI, class Masked>
+__device__ __forceinline__ void accel_body(const f4* __restrict__ src, const SrcView& sv, const Masked masked,
+                                           const f4* __restrict__ tgt, int n_tgt, int tgt_off, int t_base, int slab,
+                                           float eps2, float scale, f4* lds, float* __restrict__ dst) {
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int i0 = t_base + lane, i1 = t_base + 64 + lane;
+  const f4 t0 = tgt[min(i0, n_tgt - 1)], t1 = tgt[min(i1, n_tgt - 1)];
+  const f2 xi = {t0.x, t1.x}, yi = {t0.y, t1.y}, zi = {t0.z, t1.z};
+  f2 ax = {0.f, 0.f}, ay = {0.f, 0.f}, az = {0.f, 0.f};
+  f2 e2 = {eps2, eps2};
+  asm volatile("" : "+v"(e2));  // keep eps^2 in VGPRs: an SGPR operand halves v_pk_fma issue
+
+  const int jw = slab * kWaves + wave;
+  const int c_begin = jw * sv.cpw_q + min(jw, sv.cpw_r), c_end = c_begin + sv.cpw_q + (jw < sv.cpw_r ? 1 : 0);
+  f4* stage = &lds[wave * 2 * kChunk];
+  const f4* s_lane = src + lane;
+  // logical -> physical chunk: hop over the skipped run
+  auto phys = [&](int c) { return c + (c >= sv.skip_c0 ? sv.skip_cn : 0); };
+  if (c_begin < c_end)
+    __builtin_amdgcn_global_load_lds(GPTR(s_lane + (size_t)phys(c_begin) * kChunk), LPTR(stage), 16, 0, 0);
+  for (int c = c_begin; c < c_end; ++c) {
+    const int b = (c - c_begin) & 1;
+    if (c + 1 < c_end) {
+      __builtin_amdgcn_global_load_lds(GPTR(s_lane + (size_t)phys(c + 1) * kChunk),
+                                       LPTR(stage + (b ^ 1) * kChunk), 16, 0, 0);
+      asm volatile("s_waitcnt vmcnt(1)" ::: "memory");  // chunk c has landed, c+1 in flight
+    } else {
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
+    const f4* buf = stage + b * kChunk;
+    const int pc = phys(c);
+    const int j0 = pc * kChunk;
+    if (masked || pc == sv.edge0 || pc == sv.edge1 || (UNI && pc == sv.tail)) {
+#pragma unroll 4
+      for (int j = 0; j < kChunk; ++j)
+        interact<true, UNI>(buf[j], xi, yi, zi, e2, ax, ay, az, j0 + j, tgt_off + i0, tgt_off + i1, sv);
+    } else {
+#pragma unroll 1
+      for (int j = 0; j < kChunk; j += KU) interact_block<KU, UNI>(buf + j, xi, yi, zi, e2, ax, ay, az);
+    }
+  }
+
+  // wavefront partials -> LDS -> one coalesced (128 x 3) store per workgroup, waves added in fixed order
+  float* red = reinterpret_cast<float*>(&lds[kWaves * 2 * kChunk]);  // [wave][comp*2+half][64]
+  float* mine = red + wave * 6 * 64;
+  mine[0 * 64 + lane] = ax.x; mine[1 * 64 + lane] = ax.y;
+  mine[2 * 64 + lane] = ay.x; mine[3 * 64 + lane] = ay.y;
+  mine[4 * 64 + lane] = az.x; mine[5 * 64 + lane] = az.y;
+  __syncthreads();
+  const int n_valid = min(kTgtPerWG, n_tgt - t_base) * 3;
+  for (int o = threadIdx.x; o < n_valid; o += 64 * kWaves) {
+    const int lt = o / 3, comp = o - lt * 3;
+    const int idx = (comp * 2 + (lt >> 6)) * 64 + (lt & 63);
+    float sum = red[idx];
+#pragma unroll
+    for (int w = 1; w < kWaves; ++w) sum += red[w * 6 * 64 + idx];
+    dst[o] = __fmul_rn(scale, sum);
+  }
+}
+
 // ---- energies (simulation.py:91-115). U = sum_{i<j} -G m_i m_j / (|r_ij| + eps), K = sum 0.5 m v^2.
 // Same streaming structure as K1 (two targets per lane in packed registers, wave-private LDS-DMA
 // chunks, J-split over waves and slabs) restricted to the upper triangle: a target group only
@@ -131,6 +223,62 @@ __device__ __forceinline__ void energy_pair(const f4 p, const f2 xi, const f2 yi
     t.y = (j > i1 && j < n) ? t.y : 0.f;
   }
   u += t;
+}
+
+// The wave body of the potential-energy kernels: targets [t_base, t_base + 128) of the n bodies in posm against this
+// workgroup's share of the chunks [first chunk of the group, n_chunks), split over slabs x 4 waves; the diagonal chunks
+// and the padded tail (every chunk when all_masked: no softening) take the masked pair. *dst = the workgroup's
+// sum_i m_i u_i in fp64 (the -G factor is applied by the final kernel). lds: the workgroup's f4[kEnergyLdsF4].
+constexpr int kEnergyLdsF4 = kWaves * 2 * kChunk + 8;
+
+__device__ __forceinline__ void energy_body(const f4* __restrict__ posm, int n, int n_chunks, int t_base, int slab,
+                                            int slabs, float soft_, const bool all_masked, f4* lds,
+                                            double* __restrict__ dst) {
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int i0 = t_base + lane, i1 = t_base + 64 + lane;
+  const f4 t0 = posm[min(i0, n - 1)], t1 = posm[min(i1, n - 1)];
+  const f2 xi = {t0.x, t1.x}, yi = {t0.y, t1.y}, zi = {t0.z, t1.z};
+  f2 u = {0.f, 0.f};
+  f2 soft = {soft_, soft_};
+  asm volatile("" : "+v"(soft));
+  const int c_lo = t_base / kChunk;
+  const int span = n_chunks - c_lo;
+  const int parts = slabs * kWaves;
+  const int cpw = (span + parts - 1) / parts;
+  const int jw = slab * kWaves + wave;
+  const int c_begin = min(c_lo + jw * cpw, n_chunks), c_end = min(c_begin + cpw, n_chunks);
+  const int c_diag_end = (t_base + kTgtPerWG + kChunk - 1) / kChunk;      // chunks below this touch j <= i
+  f4* stage = &lds[wave * 2 * kChunk];
+  const f4* s_lane = posm + lane;
+  if (c_begin < c_end)
+    __builtin_amdgcn_global_load_lds(GPTR(s_lane + (size_t)c_begin * kChunk), LPTR(stage), 16, 0, 0);
+  for (int c = c_begin; c < c_end; ++c) {
+    const int b = (c - c_begin) & 1;
+    if (c + 1 < c_end) {
+      __builtin_amdgcn_global_load_lds(GPTR(s_lane + (size_t)(c + 1) * kChunk), LPTR(stage + (b ^ 1) * kChunk), 16, 0, 0);
+      asm volatile("s_waitcnt vmcnt(1)" ::: "memory");  // chunk c has landed, c+1 in flight
+    } else {
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
+    const f4* buf = stage + b * kChunk;
+    const int j0 = c * kChunk;
+    if (all_masked || c < c_diag_end || c == n_chunks - 1) {     // diagonal chunks and the padded tail
+#pragma unroll 4
+      for (int j = 0; j < kChunk; ++j) energy_pair<true>(buf[j], xi, yi, zi, soft, u, j0 + j, i0, i1, n);
+    } else {
+#pragma unroll 4
+      for (int j = 0; j < kChunk; ++j) energy_pair<false>(buf[j], xi, yi, zi, soft, u, j0 + j, i0, i1, n);
+    }
+  }
+  double acc = 0.0;
+  if (i0 < n) acc += (double)t0.w * (double)u.x;
+  if (i1 < n) acc += (double)t1.w * (double)u.y;
+  for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off);
+  double* red = reinterpret_cast<double*>(&lds[kWaves * 2 * kChunk]);
+  if (lane == 0) red[wave] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) *dst = (red[0] + red[1]) + (red[2] + red[3]);
 }
 
 }  // namespace

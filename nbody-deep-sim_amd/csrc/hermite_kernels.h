@@ -1,6 +1,9 @@
-// hermite_kernels.h -- the acceleration-plus-jerk inner loop and the corrector arithmetic shared by the Hermite
-// translation units (direct_hermite.hip: all targets, shared timestep; direct_hermite_block.hip: an active list of
-// targets, block timesteps; direct_batch_hermite.hip: many independent systems, shared timestep per system).
+// hermite_kernels.h -- the acceleration-plus-jerk wave body (accel_jerk_body: target loads, LDS-DMA chunk walk, pair
+// loop, four-wave reduction, store) and the corrector arithmetic shared by the Hermite translation units
+// (direct_hermite.hip: all targets, shared timestep; direct_hermite_block.hip: an active list of targets, block
+// timesteps; direct_batch_hermite.hip: many independent systems, shared timestep per system). Their force kernels are a
+// prologue that says which targets, which chunks and which output rows, and one call of the body: that is what keeps a
+// scene of a batch, or a block step at level 0, bit-identical to the shared-timestep kernel.
 // The definitions sit in an anonymous namespace: every translation unit that includes this file gets its own inlined copies.
 #pragma once
 #include "direct_kernels.h"
@@ -80,6 +83,81 @@ __device__ __forceinline__ void jerk_block(const f4* __restrict__ bp, const f4* 
     acc[6] = __builtin_elementwise_fma(c, dx[u], acc[6]);
     acc[7] = __builtin_elementwise_fma(c, dy[u], acc[7]);
     acc[8] = __builtin_elementwise_fma(c, dz[u], acc[8]);
+  }
+}
+
+// The wave body of every acceleration-plus-jerk kernel. accel_kernel's structure: a workgroup is 4 waves on 128 targets,
+// two per lane in packed fp32 (rows r0, r1 of posm / velp; i0, i1 are the source indices the masked loop takes for the
+// lane's own); every wave streams its chunks [c_begin, c_end) of the n sources, each chunk = 64 positions + 64 velocities
+// (2 KiB) by LDS-DMA, double-buffered behind a counted vmcnt; the 4 waves' partials are reduced through LDS in wave order
+// into one coalesced store of 6 x n_valid floats: dst[comp * stride + t], t < n_valid. lds: the workgroup's
+// f4[kWaves * 4 * kChunk] (16 KiB), [wave][buffer][pos | vel][64] staging; after its last chunk a wave puts its [12][64]
+// partials into its own part.
+template <bool MASKED, int KU>
+__device__ __forceinline__ void accel_jerk_body(const f4* __restrict__ posm, const f4* __restrict__ velp, int n, int r0,
+                                                int r1, int i0, int i1, int c_begin, int c_end, float eps2, f4* lds,
+                                                float* __restrict__ dst, int stride, int n_valid) {
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const f4 t0 = posm[r0], t1 = posm[r1];
+  const f4 u0 = velp[r0], u1 = velp[r1];
+  const f2 xi = {t0.x, t1.x}, yi = {t0.y, t1.y}, zi = {t0.z, t1.z};
+  const f2 ui = {u0.x, u1.x}, vi = {u0.y, u1.y}, wi = {u0.z, u1.z};
+  f2 acc[9];
+#pragma unroll
+  for (int k = 0; k < 9; ++k) acc[k] = f2{0.f, 0.f};
+  f2 e2 = {eps2, eps2};
+  asm volatile("" : "+v"(e2));  // keep eps^2 in VGPRs: an SGPR operand halves v_pk_fma issue
+
+  f4* stage = &lds[wave * 4 * kChunk];
+  const f4* p_lane = posm + lane;
+  const f4* v_lane = velp + lane;
+  auto fetch = [&](int c, int b) {
+    __builtin_amdgcn_global_load_lds(GPTR(p_lane + (size_t)c * kChunk), LPTR(stage + b * 2 * kChunk), 16, 0, 0);
+    __builtin_amdgcn_global_load_lds(GPTR(v_lane + (size_t)c * kChunk), LPTR(stage + b * 2 * kChunk + kChunk), 16, 0, 0);
+  };
+  if (c_begin < c_end) fetch(c_begin, 0);
+  for (int c = c_begin; c < c_end; ++c) {
+    const int b = (c - c_begin) & 1;
+    if (c + 1 < c_end) {
+      fetch(c + 1, b ^ 1);
+      asm volatile("s_waitcnt vmcnt(2)" ::: "memory");  // chunk c has landed, c+1 (two loads) in flight
+    } else {
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
+    const f4* bp = stage + b * 2 * kChunk;
+    const f4* bv = bp + kChunk;
+    if (MASKED) {
+      const int j0 = c * kChunk;
+#pragma unroll 2
+      for (int j = 0; j < kChunk; ++j)
+        jerk_pair_masked(bp[j], bv[j], xi, yi, zi, ui, vi, wi, e2, acc, j0 + j, i0, i1, n);
+    } else {
+#pragma unroll 1
+      for (int j = 0; j < kChunk; j += KU) jerk_block<KU>(bp + j, bv + j, xi, yi, zi, ui, vi, wi, e2, acc);
+    }
+  }
+
+  // j = (w dv) - 3 (r.v s^2 w dr); wavefront partials -> LDS -> one coalesced (6 x 128) store per workgroup. A wave's
+  // staging is free here: its loads have landed (vmcnt(0) on the last chunk) and its reads precede these writes.
+  constexpr int kPart = 4 * kChunk * 4;                              // floats per wave: [comp*2+half][64] in the first 768
+  float* red = reinterpret_cast<float*>(lds);
+  float* mine = red + wave * kPart;
+#pragma unroll
+  for (int k = 0; k < 6; ++k) {
+    const f2 v = k < 3 ? acc[k] : acc[k] - 3.0f * acc[k + 3];
+    mine[(2 * k) * 64 + lane] = v.x;
+    mine[(2 * k + 1) * 64 + lane] = v.y;
+  }
+  __syncthreads();
+  for (int o = threadIdx.x; o < 6 * kTgtPerWG; o += 64 * kWaves) {
+    const int comp = o >> 7, lt = o & 127;
+    if (lt >= n_valid) continue;
+    const int idx = (comp * 2 + (lt >> 6)) * 64 + (lt & 63);
+    float sum = red[idx];
+#pragma unroll
+    for (int w = 1; w < kWaves; ++w) sum += red[w * kPart + idx];
+    dst[(size_t)comp * stride + lt] = sum;
   }
 }
 
