@@ -354,16 +354,30 @@ __global__ __launch_bounds__(512, 4) void accel_sym2_kernel(const f4* __restrict
     mine[2 * 64] = ry.x; mine[3 * 64] = ry.y;
     mine[4 * 64] = rz.x; mine[5 * 64] = rz.y;
   }
+  // An adding launch needs what an earlier launch stored in its rows (written from other XCDs: they come from the
+  // Infinity Cache or HBM, not the local L2). The walk's registers are dead here, so all twelve values of a thread are
+  // requested at once, in front of the barrier: one exposed round trip. (Fetched trip by trip inside the two passes
+  // below -- load, wait, add, store, six times each -- they cost 3.7 us of a 156-us launch, now 1.3 us.)
+  float* const o_b = out + ((size_t)slot * n + (size_t)tb * kSymTile) * 3;
+  float* const o_a = out + ((size_t)slot * n + (size_t)ta * kSymTile) * 3;
+  float oldb[6], olda[6];
+  if (!init) {
+#pragma unroll
+    for (int i = 0; i < 6; ++i) oldb[i] = o_b[threadIdx.x + i * 512];
+#pragma unroll
+    for (int i = 0; i < 6; ++i) olda[i] = o_a[threadIdx.x + i * 512];
+  }
   __syncthreads();
 
   // reactions: rows of tile b, target group 0 + target group 1; one coalesced pass over the tile's 1024 x 3 floats
-  float* const o_b = out + ((size_t)slot * n + (size_t)tb * kSymTile) * 3;
-  for (int o = threadIdx.x; o < kSymTile * 3; o += 512) {
+#pragma unroll
+  for (int i = 0; i < 6; ++i) {
+    const int o = threadIdx.x + i * 512;
     const int row = o / 3, comp = o - row * 3;
     const int c = row >> 6, l = row & 63, p = c & (kSym2Pairs - 1), hf = c / kSym2Pairs;
     const float* rs = react + ((p & 1) * 8 + (p >> 1) * 2) * 6 * 64 + (comp * 2 + hf) * 64 + l;
     const float v = rs[0] + rs[6 * 64];
-    o_b[o] = init ? v : o_b[o] + v;
+    o_b[o] = init ? v : oldb[i] + v;
   }
   __syncthreads();  // every reaction read is done: the LDS image takes the own sums
 #pragma unroll
@@ -375,14 +389,15 @@ __global__ __launch_bounds__(512, 4) void accel_sym2_kernel(const f4* __restrict
   }
   __syncthreads();
   // own sums: rows of tile a, the 4 source groups in order
-  float* const o_a = out + ((size_t)slot * n + (size_t)ta * kSymTile) * 3;
-  for (int o = threadIdx.x; o < kSymTile * 3; o += 512) {
+#pragma unroll
+  for (int i = 0; i < 6; ++i) {
+    const int o = threadIdx.x + i * 512;
     const int row = o / 3, comp = o - row * 3;
     const int g = row >> 9, t = (row >> 6) & (kSym2T - 1), l = row & 63;
     const float* os = ldsf + ((g * 3 + comp) * kSym2T + t) * 64 + l;
     constexpr int kSg = 2 * 3 * kSym2T * 64;
     const float v = ((os[0] + os[kSg]) + os[2 * kSg]) + os[3 * kSg];
-    o_a[o] = init ? v : o_a[o] + v;
+    o_a[o] = init ? v : olda[i] + v;
   }
 }
 
