@@ -69,7 +69,93 @@ def _resolve_device(device) -> torch.device:
     raise ValueError("device debe ser 'cuda', 'cpu' o None")
 
 
-class BaseSimulator:
+class _ChunkedRun:
+    """run() in captured chunks, for BaseSimulator and BatchedSimulator. Below ~16 k bodies a step is a handful of
+    microseconds of GPU work and run() is bound by its per-step host work (events, seven ctypes launches, three staged
+    copies, a state object): 110-280 us per step wall for 15-25 us of GPU time at the reference's dataset sizes (100-2000
+    bodies x 1000 steps, s01-dataset-generation.py:192-214). Those systems run in CHUNKS captured into a hipGraph: per
+    step the integrator's launches, the energy launches and ONE snapshot launch into a device ring; per chunk one replay,
+    one sync, one device->host copy. Same kernels in the same order as step(): bit-identical states (tested).
+
+    The simulator supplies: `_carried`, the public arrays a step rebinds paired with the static buffers a captured step
+    updates in place; `_chunk_scalars()`, every scalar the body bakes into its launches; `_chunk_body(m)` -> (body(count),
+    device buffers to copy per chunk); `_emit_states(host buffers, m, first, GPU seconds of each step, out)`; and
+    `_run_eager(steps, first, out)` for the tail."""
+
+    GRAPH_RUN_CHUNK = 32
+    _carried = (("accelerations", "_acc_g"),)
+
+    def _statics(self) -> list:
+        """The static buffers of the carried arrays, allocated on first use."""
+        for public, static in self._carried:
+            if getattr(self, static, None) is None:
+                setattr(self, static, torch.empty_like(getattr(self, public)))
+        return [getattr(self, static) for _, static in self._carried]
+
+    def _chunk_graph(self, m: int):
+        """(graph, device buffers) for a chunk of m steps; captured once per key and kept."""
+        cache = self.__dict__.setdefault("_run_graphs", {})
+        statics = self._statics()
+        # a graph bakes in buffer addresses and scalar arguments: every array that can be rebound after construction
+        # and every scalar the caller may have changed is in the key (the scratch is allocated once and never rebound)
+        key = (m, *(t.data_ptr() for t in (self.positions, self.velocities, self.masses, *statics)),
+               *self._chunk_scalars())
+        if key in cache:
+            return cache[key]
+        if len(cache) > 8:
+            cache.clear()
+        body, bufs = self._chunk_body(m)
+        dev = self.device
+        # capture on a side stream; the state is saved and restored around the (executed) warm-up pass
+        saved = [self.positions, self.velocities, *statics]
+        keep = [t.clone() for t in saved]
+
+        def restore():
+            for t, k in zip(saved, keep):
+                t.copy_(k)
+        side = torch.cuda.Stream(device=dev)
+        side.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(side):
+            body(1)                                          # every kernel of a step once (lazy initialisations)
+        torch.cuda.current_stream(dev).wait_stream(side)
+        restore()
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph):
+            body(m)
+        restore()
+        cache[key] = (graph, bufs)
+        return cache[key]
+
+    def _run_chunked(self, steps: int, big: int, out):
+        """Chunks of `big` steps, then of 8; the last < 8 steps run eagerly."""
+        done = 0
+        while steps - done >= 8:
+            m = big if steps - done >= big else 8
+            graph, bufs = self._chunk_graph(m)              # (capture leaves the state untouched)
+            if done == 0:                                    # a caller's handle on the old accelerations stays valid
+                for (public, _), static in zip(self._carried, self._statics()):
+                    static.copy_(getattr(self, public))
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            graph.replay()
+            e1.record()
+            host = [b.cpu() for b in bufs]                   # one device->host copy per buffer (synchronises)
+            self._emit_states(host, m, done, [e0.elapsed_time(e1) * 1e-3 / m] * m, out)   # the chunk's GPU time, spread
+            done += m
+        if done:
+            for (public, _), static in zip(self._carried, self._statics()):
+                setattr(self, public, static.clone())        # rebound, as step() does (simulation.py:168)
+        if done < steps:
+            self._run_eager(steps - done, done, out)
+
+
+class BaseSimulator(_ChunkedRun):
+    # What an integrator class states next to its step(): `_step_in_place()`, the same step on the static buffers of
+    # `_carried` without rebinding anything (capturable); `_carried` itself when the step carries more than the
+    # accelerations; and
+    _posm_after_step = False        # step() leaves _posm at the post-step positions (else the energies repack first)
+    _equal_mass_step = False        # the un-sharded step() has an equal-mass form (`_uniform`)
+
     def __init__(self, *, positions, velocities, masses, g_const: float = 1.0, softening: float = 0.1,
                  dt: float = 0.01, calc_energy: bool = True, device: str = None, process_group=None):
         self.device = _resolve_device(device)
@@ -110,7 +196,7 @@ class BaseSimulator:
         # NBD_UNIFORM_MASS=0 keeps the general kernel. The un-sharded Euler step and compute_accelerations() use the
         # general kernel.
         self._uniform = (direct.uniform_mass(self.masses)
-                         if ((self._sharded or isinstance(self, LeapFrogSimulator))
+                         if ((self._sharded or self._equal_mass_step)
                              and os.environ.get("NBD_UNIFORM_MASS", "1") != "0") else None)
         if not self._sharded:
             self._ws = direct.step_workspace(max(self.n, 1), self.device)
@@ -141,19 +227,27 @@ class BaseSimulator:
         if n_loc:
             direct.pack_posm(self.positions, self._mass_local, out=self._posm_local[:direct.padded_len(n_loc)])
 
-    def _force_sharded(self, vel=None, c_kick: float = 0.0) -> torch.Tensor:
+    def _force_sharded(self, vel=None, c_kick: float = 0.0, ev=None) -> torch.Tensor:
         """Force on the rank's bodies from `_posm_local` (already packed): start the all-gather, run the
-        local x local block while it is in flight, then the remote block + slab sum (+ fused kick)."""
+        local x local block while it is in flight, then the remote block + slab sum (+ fused kick).
+        `ev`: events recorded after the gather's start (ev[1]), the local block, the gather's end and the remote block."""
+        def mark(i):
+            if ev is not None:
+                ev[i].record()
         p = self.part
         handle = self._gather.start(self._posm_local, self._posm)
         acc = torch.empty((p.n_local, 3), dtype=torch.float32, device=self.device)
+        mark(1)
         if p.n_local:
             local = self._posm_local[:direct.padded_len(p.n_local)]
             direct.shard_force_local(local, p.n_local, self.n, p.lo, self._eps2, self._ws, uniform=self._uniform)
+        mark(2)
         self._gather.finish(handle, self._posm)
+        mark(3)
         if p.n_local:
             direct.shard_force_remote(self._posm, self.n, local, p.n_local, p.lo, self._eps2, self._g, acc,
                                       vel, c_kick, self._ws, uniform=self._uniform)
+        mark(4)
         return acc
 
     def compute_accelerations(self) -> torch.Tensor:
@@ -197,11 +291,19 @@ class BaseSimulator:
         if steps <= 0:
             return states
         if self._graph_run_ok(steps):
-            return self._run_graphed(steps)
-        return self._run_eager(steps, 0)
+            self._run_chunked(steps, self.GRAPH_RUN_CHUNK, states)
+        else:
+            self._run_eager(steps, 0, states)
+        return states
 
-    def _run_eager(self, steps: int, first_index: int) -> list[SimulationState]:
-        states = []
+    def _energies_into(self, out_uk, workspace=None):
+        """Energies of the state AFTER an un-sharded step (simulation.py:131-133), asynchronous."""
+        if not self._posm_after_step:
+            direct.pack_posm(self.positions, self.masses, out=self._posm)
+        direct.energy(self._posm, self.velocities, self.n, direct.f32(self.softening), self._g, out_uk=out_uk,
+                      workspace=workspace)
+
+    def _run_eager(self, steps: int, first_index: int, states):
         n_loc = self.part.n_local
         per_step = 3 * n_loc * 3 * 4
         chunk = max(1, min(max(steps, 32), (64 << 20) // max(per_step, 1)))
@@ -226,12 +328,7 @@ class BaseSimulator:
                 events.append((e0, e1))
                 if self.calc_energy:
                     if not self._sharded:
-                        # energies of the state AFTER the step (simulation.py:131-133). The leapfrog and Hermite
-                        # steps leave posm = current positions; the Euler step packs before its drift, so repack.
-                        if not isinstance(self, (LeapFrogSimulator, HermiteSimulator)):
-                            direct.pack_posm(self.positions, self.masses, out=self._posm)
-                        direct.energy(self._posm, self.velocities, self.n, direct.f32(self.softening),
-                                      self._g, out_uk=uk_dev[s])
+                        self._energies_into(uk_dev[s])
                     else:
                         u, k = self.compute_energies()
                         uk_dev[s, 0], uk_dev[s, 1] = u, k
@@ -242,126 +339,50 @@ class BaseSimulator:
             torch.cuda.current_stream(self.device).synchronize()
             # one pageable copy of the whole chunk (the pinned staging is reused); the states' tensors are
             # views into it -- 3 m small clones cost several times more in allocation and page faults
-            host = stage[:m].clone()
-            uk = uk_host[:m].tolist()
-            for s in range(m):
-                u, k = (uk[s][0], uk[s][1]) if self.calc_energy else (None, None)
-                states.append(SimulationState(
-                    positions=host[s, 0], velocities=host[s, 1],
-                    accelerations=host[s, 2], step=first_index + done + s,
-                    step_time=events[s][0].elapsed_time(events[s][1]) * 1e-3, u_energy=u, k_energy=k))
+            self._emit_states((stage[:m].clone(), uk_host[:m]), m, first_index + done,
+                              [e0.elapsed_time(e1) * 1e-3 for e0, e1 in events], states)
             done += m
-        return states
 
-    # ------------------------------------------------------------------ run(): captured chunks for small systems
-    # Below ~16 k bodies a step is a handful of microseconds of GPU work and run() is bound by its per-step host
-    # work (events, seven ctypes launches, three staged copies, a state object): 110-280 us per step wall for 15-25 us
-    # of GPU time at the reference's dataset sizes (100-2000 bodies x 1000 steps, s01-dataset-generation.py:192-214).
-    # Those systems run in CHUNKS captured into a hipGraph: per step the integrator's launches, the energy launches
-    # and ONE snapshot launch into a device ring; per chunk one replay, one sync, one device->host copy. Same
-    # kernels in the same order as step(): bit-identical states (tested).
+    def _emit_states(self, host, m, first, t_steps, states):
+        """m states from host copies of a chunk's ring (m, 3, n, 3) and energies (m, 2): views, no copies."""
+        ring = host[0]
+        uk = host[1].tolist() if self.calc_energy else None
+        for s in range(m):
+            u, k = (uk[s][0], uk[s][1]) if self.calc_energy else (None, None)
+            states.append(SimulationState(step=first + s, step_time=t_steps[s], positions=ring[s, 0],
+                                          velocities=ring[s, 1], accelerations=ring[s, 2], u_energy=u, k_energy=k))
+
+    # ------------------------------------------------------------------ run(): captured chunks (_ChunkedRun)
     GRAPH_RUN_MAX_BODIES = 16384
-    GRAPH_RUN_CHUNK = 32
+
+    @classmethod
+    def _capturable(cls) -> bool:
+        """The class that defines step() also defines _step_in_place(): an overriding step() is never replaced by an
+        inherited in-place step, it runs eagerly."""
+        owner = next(k for k in cls.__mro__ if "step" in vars(k))
+        return "_step_in_place" in vars(owner)
 
     def _graph_run_ok(self, steps: int) -> bool:
         return (not self._sharded and 0 < self.n <= self.GRAPH_RUN_MAX_BODIES and steps >= 8 and
-                type(self).step in (LeapFrogSimulator.step, EulerSimulator.step, HermiteSimulator.step) and
-                os.environ.get("NBD_RUN_GRAPH", "1") != "0")
+                self._capturable() and os.environ.get("NBD_RUN_GRAPH", "1") != "0")
 
-    def _step_in_place(self, acc):
-        """One integrator step on (positions, velocities, acc) without rebinding anything (capturable)."""
-        dt = direct.f32(self.dt)
-        if isinstance(self, LeapFrogSimulator):
-            direct.leapfrog_step(self.positions, self.velocities, acc, acc, self.masses, direct.f32(0.5 * self.dt), dt,
-                                 self._eps2, self._g, self._posm, self._ws, uniform=self._uniform)
-        elif isinstance(self, HermiteSimulator):        # the jerks are carried in the simulator's own static buffer
-            direct.hermite_step(self.positions, self.velocities, acc, self._jerk_g, acc, self._jerk_g, self.masses,
-                                self.dt, self._eps2, self._g, self._posm, self._hws)
-        else:
-            direct.euler_step(self.positions, self.velocities, acc, self.masses, dt, self._eps2, self._g, self._posm,
-                              self._ws)
+    def _chunk_scalars(self):
+        return (float(self.dt), float(self.softening), bool(self.calc_energy), self._eps2, self._g, self._uniform)
 
-    def _chunk_graph(self, m: int):
-        """(graph, ring, uk) for a chunk of m steps; captured once per m and kept."""
-        cache = self.__dict__.setdefault("_run_graphs", {})
-        # a graph bakes in buffer addresses and scalar arguments: anything the caller may have changed is in the key
-        key = (m, self.positions.data_ptr(), self.velocities.data_ptr(), self.masses.data_ptr(), float(self.dt),
-               bool(self.calc_energy))
-        if key in cache:
-            return cache[key]
-        if len(cache) > 8:
-            cache.clear()
+    def _chunk_body(self, m: int):
         n, dev = self.n, self.device
-        if getattr(self, "_acc_g", None) is None:
-            self._acc_g = torch.empty((n, 3), dtype=torch.float32, device=dev)
+        if getattr(self, "_energy_ws", None) is None:
             self._energy_ws = direct.alloc_bytes(_lib.lib().nbd_energy_workspace_bytes(n), dev)
-        hermite = isinstance(self, HermiteSimulator)
-        if hermite and getattr(self, "_jerk_g", None) is None:
-            self._jerk_g = torch.empty((n, 3), dtype=torch.float32, device=dev)
         ring = torch.empty((m, 3, n, 3), dtype=torch.float32, device=dev)
         uk = torch.zeros((m, 2), dtype=torch.float64, device=dev)
-        soft = direct.f32(self.softening)
-        leap = isinstance(self, (LeapFrogSimulator, HermiteSimulator))      # steps that leave posm = {x, m}
 
-        def body(count=m):
+        def body(count):
             for s_ in range(count):
-                self._step_in_place(self._acc_g)
+                self._step_in_place()
                 if self.calc_energy:
-                    if not leap:     # the Euler step packs before its drift: energies need the moved positions
-                        direct.pack_posm(self.positions, self.masses, out=self._posm)
-                    direct.energy(self._posm, self.velocities, n, soft, self._g, out_uk=uk[s_], workspace=self._energy_ws)
+                    self._energies_into(uk[s_], self._energy_ws)
                 direct.snapshot(self.positions, self.velocities, self._acc_g, ring[s_])
-        # capture on a side stream; the state is saved and restored around the (executed) warm-up pass
-        keep = (self.positions.clone(), self.velocities.clone(), self._acc_g.clone(),
-                self._jerk_g.clone() if hermite else None)
-
-        def restore():
-            self.positions.copy_(keep[0]); self.velocities.copy_(keep[1]); self._acc_g.copy_(keep[2])
-            if hermite:
-                self._jerk_g.copy_(keep[3])
-        side = torch.cuda.Stream(device=dev)
-        side.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(side):
-            body(1)                                          # every kernel of a step once (lazy initialisations)
-        torch.cuda.current_stream(dev).wait_stream(side)
-        restore()
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph):
-            body()
-        restore()
-        cache[key] = (graph, ring, uk)
-        return cache[key]
-
-    def _run_graphed(self, steps: int) -> list[SimulationState]:
-        n, dev = self.n, self.device
-        states, done = [], 0
-        first = True
-        while steps - done >= 8:                             # chunks of 32, then of 8; the last < 8 steps run eagerly
-            m = self.GRAPH_RUN_CHUNK if steps - done >= self.GRAPH_RUN_CHUNK else 8
-            graph, ring, uk = self._chunk_graph(m)          # (capture leaves the state untouched)
-            if first:                                        # a caller's handle on the old accelerations stays valid
-                self._acc_g.copy_(self.accelerations)
-                if isinstance(self, HermiteSimulator):
-                    self._jerk_g.copy_(self.jerks)
-                first = False
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            graph.replay()
-            e1.record()
-            host = ring.cpu()                                # one device->host copy per chunk (synchronises)
-            uk_h = uk.cpu().tolist() if self.calc_energy else None
-            t_step = e0.elapsed_time(e1) * 1e-3 / m          # GPU time of the chunk, spread over its steps
-            for s_ in range(m):
-                u, k = (uk_h[s_][0], uk_h[s_][1]) if self.calc_energy else (None, None)
-                states.append(SimulationState(step=done + s_, step_time=t_step, positions=host[s_, 0],
-                                              velocities=host[s_, 1], accelerations=host[s_, 2], u_energy=u, k_energy=k))
-            done += m
-        self.accelerations = self._acc_g.clone()             # rebound, as step() does (simulation.py:168)
-        if isinstance(self, HermiteSimulator):
-            self.jerks = self._jerk_g.clone()
-        if done < steps:
-            states += self._run_eager(steps - done, done)
-        return states
+        return body, ((ring, uk) if self.calc_energy else (ring,))
 
     def step(self):
         raise NotImplementedError("El método step debe ser implementado en la subclase")
@@ -386,10 +407,24 @@ class LeapFrogSimulator(BaseSimulator):
         if self._step_graph is not None:                 # capture_step(): the same launches and the collective, replayed
             self._step_graph.replay()
             return
+        self.accelerations = self._sharded_launches(self.accelerations, half, dt)
+
+    _posm_after_step = True
+    _equal_mass_step = True
+
+    def _step_in_place(self):
+        direct.leapfrog_step(self.positions, self.velocities, self._acc_g, self._acc_g, self.masses,
+                             direct.f32(0.5 * self.dt), direct.f32(self.dt), self._eps2, self._g, self._posm, self._ws,
+                             uniform=self._uniform)
+
+    def _sharded_launches(self, acc, half, dt, ev=None) -> torch.Tensor:
+        """The range-sharded step's launches from the accelerations `acc`; returns the new ones. `ev`: five events, ev[0]
+        recorded before the kick-drift and the others between the phases of _force_sharded()."""
+        if ev is not None:
+            ev[0].record()
         if self.part.n_local:
-            direct.kick_drift(self.positions, self.velocities, self.accelerations, self._mass_local, half, dt,
-                              posm=self._posm_local)
-        self.accelerations = self._force_sharded(self.velocities, half)
+            direct.kick_drift(self.positions, self.velocities, acc, self._mass_local, half, dt, posm=self._posm_local)
+        return self._force_sharded(self.velocities, half, ev)
 
     _step_graph = None
 
@@ -414,10 +449,7 @@ class LeapFrogSimulator(BaseSimulator):
             graph = torch.cuda.CUDAGraph()
             with torch.cuda.stream(side):
                 with torch.cuda.graph(graph, stream=side):
-                    if self.part.n_local:
-                        direct.kick_drift(self.positions, self.velocities, acc_static, self._mass_local, half, dt,
-                                          posm=self._posm_local)
-                    new_acc = self._force_sharded(self.velocities, half)
+                    new_acc = self._sharded_launches(acc_static, half, dt)
                     acc_static.copy_(new_acc)
             torch.cuda.current_stream(self.device).wait_stream(side)
             torch.cuda.synchronize(self.device)
@@ -441,25 +473,8 @@ class LeapFrogSimulator(BaseSimulator):
             raise _lib.NbdError("step_phases(): only the range-sharded step has phases")
         half, dt = direct.f32(0.5 * self.dt), direct.f32(self.dt)
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(5)]
-        p = self.part
         t0 = time.perf_counter()
-        ev[0].record()
-        if p.n_local:
-            direct.kick_drift(self.positions, self.velocities, self.accelerations, self._mass_local, half, dt,
-                              posm=self._posm_local)
-        handle = self._gather.start(self._posm_local, self._posm)
-        acc = torch.empty((p.n_local, 3), dtype=torch.float32, device=self.device)
-        ev[1].record()
-        local = self._posm_local[:direct.padded_len(p.n_local)]
-        if p.n_local:
-            direct.shard_force_local(local, p.n_local, self.n, p.lo, self._eps2, self._ws, uniform=self._uniform)
-        ev[2].record()
-        self._gather.finish(handle, self._posm)
-        ev[3].record()
-        if p.n_local:
-            direct.shard_force_remote(self._posm, self.n, local, p.n_local, p.lo, self._eps2, self._g, acc,
-                                      self.velocities, half, self._ws, uniform=self._uniform)
-        ev[4].record()
+        acc = self._sharded_launches(self.accelerations, half, dt, ev)
         host = (time.perf_counter() - t0) * 1e3
         if self._step_graph is not None:
             self.accelerations.copy_(acc)                # the captured step's static buffer
@@ -488,6 +503,9 @@ class EulerSimulator(BaseSimulator):
         if self.part.n_local:
             direct.drift(self.positions, self.velocities, dt)
 
+    def _step_in_place(self):           # (packs _posm before its drift: _posm_after_step stays False)
+        direct.euler_step(self.positions, self.velocities, self._acc_g, self.masses, direct.f32(self.dt), self._eps2,
+                          self._g, self._posm, self._ws)
 
 
 class HermiteSimulator(BaseSimulator):
@@ -529,6 +547,13 @@ class HermiteSimulator(BaseSimulator):
         direct.hermite_step(self.positions, self.velocities, self.accelerations, self.jerks, new_acc, new_jerk,
                             self.masses, self.dt, self._eps2, self._g, self._posm, self._hws)
         self.accelerations, self.jerks = new_acc, new_jerk
+
+    _carried = BaseSimulator._carried + (("jerks", "_jerk_g"),)
+    _posm_after_step = True
+
+    def _step_in_place(self):
+        direct.hermite_step(self.positions, self.velocities, self._acc_g, self._jerk_g, self._acc_g, self._jerk_g,
+                            self.masses, self.dt, self._eps2, self._g, self._posm, self._hws)
 
 
 class BlockHermiteSimulator(HermiteSimulator):
@@ -631,7 +656,36 @@ def _per_scene(x, n_scenes: int, name: str) -> list:
     return vals
 
 
-class BatchedSimulator:
+def _batch_chunk_layout(m: int, n: int, n_scenes: int):
+    """A batch's chunk buffer, in bytes: ring (m, 3, n, 3) fp32 | energies (m, S, 2) fp64 from the next multiple of 16
+    -> (ring bytes, energies' offset, size)."""
+    ring_b = m * 9 * n * 4
+    uk_at = (ring_b + 15) // 16 * 16
+    return ring_b, uk_at, uk_at + m * n_scenes * 16
+
+
+def _batch_chunk_views(buf, m: int, n: int, n_scenes: int):
+    """(ring, energies) views of a chunk buffer, on the device or in its host copy."""
+    ring_b, uk_at, size = _batch_chunk_layout(m, n, n_scenes)
+    return (buf[:ring_b].view(torch.float32).view(m, 3, n, 3),
+            buf[uk_at:size].view(torch.float64).view(m, n_scenes, 2))
+
+
+def _batch_states(host, m: int, offsets: list, calc_energy: bool, first: int, t_steps, out):
+    """Append m states per scene to `out` from a host copy of a chunk buffer (views into it, no copies)."""
+    n_scenes = len(offsets) - 1
+    ring, uk = _batch_chunk_views(host, m, offsets[-1], n_scenes)
+    uk = uk.tolist() if calc_energy else None
+    for s_ in range(m):
+        for i in range(n_scenes):
+            lo, hi = offsets[i], offsets[i + 1]
+            u, k = (uk[s_][i][0], uk[s_][i][1]) if calc_energy else (None, None)
+            out[i].append(SimulationState(step=first + s_, step_time=t_steps[s_], positions=ring[s_, 0, lo:hi],
+                                          velocities=ring[s_, 1, lo:hi], accelerations=ring[s_, 2, lo:hi],
+                                          u_energy=u, k_energy=k))
+
+
+class BatchedSimulator(_ChunkedRun):
     """S independent systems ("scenes") advanced together: one set of launches per step for all of them
     (csrc/direct_batch.hip). Each body feels only the bodies of its own scene, with that scene's g_const, softening
     and dt (scalars, or one value per scene). The scenes are stored back to back: `positions`, `velocities`,
@@ -645,7 +699,6 @@ class BatchedSimulator:
     alone. `jerks` is None for leapfrog and Euler. The integrator may switch between leapfrog and Euler after
     construction, but not into or out of Hermite."""
 
-    GRAPH_RUN_CHUNK = 32
     RING_BYTES = 64 << 20                                # the eager run()'s staging cap, per chunk of states
 
     def __init__(self, *, systems, integrator: str = "leapfrog", g_const=1.0, softening=0.1, dt=0.01,
@@ -683,6 +736,7 @@ class BatchedSimulator:
         self._hws = None
         self.jerks = None
         if self._hermite:
+            self._carried = self._carried + (("jerks", "_jerk_g"),)
             self.accelerations, self.jerks = self.compute_accelerations_and_jerks()
         else:
             self.accelerations = self.compute_accelerations()
@@ -757,16 +811,17 @@ class BatchedSimulator:
         uk = uk.cpu()
         return uk[:, 0].tolist(), uk[:, 1].tolist()
 
-    def _step_into(self, acc_in, acc_out, jerk_in=None, jerk_out=None):
+    def _step_into(self, cur, new):
+        """One step from the carried arrays `cur` into `new` (lists in the order of `_carried`; may be the same)."""
         P = self._params
         if self._hermite:
-            direct.batch_hermite_step(self._plan, self.positions, self.velocities, acc_in, jerk_in, acc_out, jerk_out,
+            direct.batch_hermite_step(self._plan, self.positions, self.velocities, cur[0], cur[1], new[0], new[1],
                                       self.masses, P[5:10], P[1], P[0], self._posm, self._hws)
         elif self.integrator == "leapfrog":
-            direct.batch_leapfrog_step(self._plan, self.positions, self.velocities, acc_in, acc_out, self.masses,
+            direct.batch_leapfrog_step(self._plan, self.positions, self.velocities, cur[0], new[0], self.masses,
                                        P[3], P[4], P[1], P[0], self._posm, self._ws)
         else:
-            direct.batch_euler_step(self._plan, self.positions, self.velocities, acc_out, self.masses, P[4], P[1],
+            direct.batch_euler_step(self._plan, self.positions, self.velocities, new[0], self.masses, P[4], P[1],
                                     P[0], self._posm, self._ws)
 
     def step(self):
@@ -776,37 +831,13 @@ class BatchedSimulator:
         if self.n == 0:
             return
         self._sync_params()
-        new_acc = torch.empty_like(self.accelerations)
-        if self._hermite:
-            new_jerk = torch.empty_like(self.jerks)
-            self._step_into(self.accelerations, new_acc, self.jerks, new_jerk)
-            self.accelerations, self.jerks = new_acc, new_jerk
-            return
-        self._step_into(self.accelerations, new_acc)
-        self.accelerations = new_acc
+        cur = [getattr(self, public) for public, _ in self._carried]
+        new = [torch.empty_like(t) for t in cur]
+        self._step_into(cur, new)
+        for (public, _), t in zip(self._carried, new):
+            setattr(self, public, t)
 
     # ------------------------------------------------------------------ run()
-    def _chunk_buffers(self, m: int):
-        """One device buffer = ring (m, 3, N, 3) fp32 | energies (m, S, 2) fp64: ONE device->host copy per chunk."""
-        ring_b = (m * 9 * self.n * 4 + 15) // 16 * 16
-        buf = torch.empty(ring_b + m * self.n_scenes * 16, dtype=torch.uint8, device=self.device)
-        ring = buf[:m * 9 * self.n * 4].view(torch.float32).view(m, 3, self.n, 3)
-        uk = buf[ring_b:].view(torch.float64).view(m, self.n_scenes, 2)
-        return buf, ring, uk, ring_b
-
-    def _states(self, host, m, ring_b, first, t_steps, out):
-        """Append m states per scene to `out` from a host copy of a chunk buffer (views into it, no copies)."""
-        ring = host[:m * 9 * self.n * 4].view(torch.float32).view(m, 3, self.n, 3)
-        uk = host[ring_b:].view(torch.float64).view(m, self.n_scenes, 2).tolist() if self.calc_energy else None
-        off = self.offsets.tolist()
-        for s_ in range(m):
-            for i in range(self.n_scenes):
-                lo, hi = off[i], off[i + 1]
-                u, k = (uk[s_][i][0], uk[s_][i][1]) if self.calc_energy else (None, None)
-                out[i].append(SimulationState(step=first + s_, step_time=t_steps[s_], positions=ring[s_, 0, lo:hi],
-                                              velocities=ring[s_, 1, lo:hi], accelerations=ring[s_, 2, lo:hi],
-                                              u_energy=u, k_energy=k))
-
     def _chunk_len(self) -> int:
         return max(1, min(self.GRAPH_RUN_CHUNK, self.RING_BYTES // max(36 * self.n, 1)))
 
@@ -827,37 +858,28 @@ class BatchedSimulator:
                                           u_energy=uk[0], k_energy=uk[1]) for s in range(steps)]
             return out
         self._sync_params()
-        done = 0
         big = self._chunk_len()
         if big >= 8 and os.environ.get("NBD_RUN_GRAPH", "1") != "0":
-            self._acc_g = getattr(self, "_acc_g", None)
-            if self._acc_g is None:
-                self._acc_g = torch.empty((self.n, 3), dtype=torch.float32, device=self.device)
-            if self._hermite and getattr(self, "_jerk_g", None) is None:     # the jerks' stable buffer, beside _acc_g
-                self._jerk_g = torch.empty((self.n, 3), dtype=torch.float32, device=self.device)
-            first = True
-            while steps - done >= 8:
-                m = big if steps - done >= big else 8
-                graph, buf, ring_b = self._chunk_graph(m)
-                if first:                                    # a caller's handle on the old accelerations stays valid
-                    self._acc_g.copy_(self.accelerations)
-                    if self._hermite:
-                        self._jerk_g.copy_(self.jerks)
-                    first = False
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-                graph.replay()
-                e1.record()
-                host = buf.cpu()                             # one device->host copy per chunk (synchronises)
-                self._states(host, m, ring_b, done, [e0.elapsed_time(e1) * 1e-3 / m / self.n_scenes] * m, out)
-                done += m
-            if not first:
-                self.accelerations = self._acc_g.clone()
-                if self._hermite:
-                    self.jerks = self._jerk_g.clone()
-        while done < steps:                                  # eager: the tail, or everything
+            self._run_chunked(steps, big, out)
+        else:
+            self._run_eager(steps, 0, out)
+        return out
+
+    def _chunk_buffers(self, m: int):
+        """One device buffer = ring | energies (_batch_chunk_layout): ONE device->host copy per chunk."""
+        size = _batch_chunk_layout(m, self.n, self.n_scenes)[2]
+        buf = torch.empty(size, dtype=torch.uint8, device=self.device)
+        return (buf,) + _batch_chunk_views(buf, m, self.n, self.n_scenes)
+
+    def _emit_states(self, host, m, first, t_steps, out):
+        _batch_states(host[0], m, self.offsets.tolist(), self.calc_energy, first,
+                      [t / self.n_scenes for t in t_steps], out)       # the batched step's GPU time, spread over S
+
+    def _run_eager(self, steps: int, first: int, out):
+        done = 0
+        while done < steps:
             m = min(self._chunk_len(), steps - done)
-            buf, ring, uk, ring_b = self._chunk_buffers(m)
+            buf, ring, uk = self._chunk_buffers(m)
             events = []
             for s_ in range(m):
                 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -869,48 +891,20 @@ class BatchedSimulator:
                     self._energies_into(uk[s_])
                 direct.snapshot(self.positions, self.velocities, self.accelerations, ring[s_])
             host = buf.cpu()
-            self._states(host, m, ring_b, done, [a.elapsed_time(b) * 1e-3 / self.n_scenes for a, b in events], out)
+            self._emit_states([host], m, first + done, [a.elapsed_time(b) * 1e-3 for a, b in events], out)
             done += m
-        return out
 
-    def _chunk_graph(self, m: int):
-        """(graph, buffer, ring offset) for a chunk of m steps; captured once per key and kept."""
-        cache = self.__dict__.setdefault("_run_graphs", {})
-        # a graph bakes in buffer addresses and scalar arguments: anything the caller may have changed is in the key
-        jerk_g = self._jerk_g if self._hermite else None
-        key = (m, self.positions.data_ptr(), self.velocities.data_ptr(), self.masses.data_ptr(), self._acc_g.data_ptr(),
-               jerk_g.data_ptr() if jerk_g is not None else None, self._params_key, bool(self.calc_energy),
-               self.integrator)
-        if key in cache:
-            return cache[key]
-        if len(cache) > 8:
-            cache.clear()
-        buf, ring, uk, ring_b = self._chunk_buffers(m)
+    def _chunk_scalars(self):
+        return (self._params_key, bool(self.calc_energy), self.integrator)
 
-        def body(count=m):
+    def _chunk_body(self, m: int):
+        buf, ring, uk = self._chunk_buffers(m)
+        statics = self._statics()
+
+        def body(count):
             for s_ in range(count):
-                self._step_into(self._acc_g, self._acc_g, jerk_g, jerk_g)
+                self._step_into(statics, statics)
                 if self.calc_energy:
                     self._energies_into(uk[s_])
-                direct.snapshot(self.positions, self.velocities, self._acc_g, ring[s_])
-        dev = self.device
-        # capture on a side stream; the state is saved and restored around the (executed) warm-up pass
-        keep = (self.positions.clone(), self.velocities.clone(), self._acc_g.clone(),
-                jerk_g.clone() if jerk_g is not None else None)
-
-        def restore():
-            self.positions.copy_(keep[0]); self.velocities.copy_(keep[1]); self._acc_g.copy_(keep[2])
-            if jerk_g is not None:
-                jerk_g.copy_(keep[3])
-        side = torch.cuda.Stream(device=dev)
-        side.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(side):
-            body(1)
-        torch.cuda.current_stream(dev).wait_stream(side)
-        restore()
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph):
-            body()
-        restore()
-        cache[key] = (graph, buf, ring_b)
-        return cache[key]
+                direct.snapshot(self.positions, self.velocities, statics[0], ring[s_])
+        return body, (buf,)

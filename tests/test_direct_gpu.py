@@ -780,3 +780,34 @@ def test_run_in_captured_chunks_equals_eager_run(cls, n, steps, energy, gpu_devi
     assert torch.equal(sa2[-1].positions, sb2[-1].positions) and torch.equal(sa2[-1].accelerations, sb2[-1].accelerations)
     a.step(); b.step()
     assert torch.equal(a.positions, b.positions) and torch.equal(a.velocities, b.velocities)
+
+
+@pytest.mark.gpu
+def test_captured_run_follows_a_changed_softening(gpu_device, monkeypatch):
+    """`softening` is baked into the captured energy launch (the force keeps the eps^2 of construction, eagerly too): a
+    second run() after changing it must capture afresh, not replay the old value. Energies and states equal the eager
+    run()'s bit for bit."""
+    from galaxify import galaxies
+    p, v, m = galaxies.generate_spiral(n_bodies=300, total_mass=1.0, radial_scale=3.0, height_scale=0.3, g_const=4.5e-6,
+                                       black_hole_mass=0.01, seed=5)
+    g = dict(pos=p, vel=v, mass=m, g_const=4.5e-6, softening=0.05, dt=1e-4)
+    a = _mk("LeapFrogSimulator", g)
+    b = _mk("LeapFrogSimulator", g)
+    assert a._graph_run_ok(16)
+    runs_a = [a.run(16)]
+    n_graphs = len(a._run_graphs)
+    a.softening = 0.5
+    runs_a.append(a.run(16))
+    assert len(a._run_graphs) > n_graphs
+    monkeypatch.setenv("NBD_RUN_GRAPH", "0")
+    assert not b._graph_run_ok(16)
+    runs_b = [b.run(16)]
+    b.softening = 0.5
+    runs_b.append(b.run(16))
+    for sa, sb in zip(runs_a, runs_b):
+        assert len(sa) == len(sb) == 16
+        for x, y in zip(sa, sb):
+            assert (x.u_energy, x.k_energy) == (y.u_energy, y.k_energy), x.step
+            assert torch.equal(x.positions, y.positions) and torch.equal(x.velocities, y.velocities)
+            assert torch.equal(x.accelerations, y.accelerations)
+    assert runs_b[1][0].u_energy > runs_b[0][-1].u_energy       # ten times the softening: a shallower potential

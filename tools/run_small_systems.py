@@ -1,5 +1,6 @@
-import sys, time, json
-sys.path.insert(0, "/root/repo/nbody-deep-sim_amd"); sys.path.insert(0, "/root/repo")
+import os, sys, time, json
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [os.path.join(ROOT, "nbody-deep-sim_amd"), ROOT]
 import torch
 from galaxify import galaxies, simulation
 out = {}
