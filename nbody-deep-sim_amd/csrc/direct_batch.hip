@@ -165,20 +165,20 @@ __global__ __launch_bounds__(256) void batch_energy_final_kernel(const SceneRec*
 
 int launch_update(const DevPlan& d, const BatchTotals& t, float* pos, float* vel, const float* acc, const float* mass,
                   const float* ck, const float* cd, float* posm, hipStream_t st) {
-  batch_update_kernel<<<bceil_div(t.n_rows, 256), 256, 0, st>>>(d.row_scene, d.scenes, t.n_rows, pos, vel, acc, mass,
+  batch_update_kernel<<<ceil_div(t.n_rows, 256), 256, 0, st>>>(d.row_scene, d.scenes, t.n_rows, pos, vel, acc, mass,
                                                                ck, cd, reinterpret_cast<f4*>(posm));
-  return bcheck();
+  return launch_status();
 }
 
 int launch_force(const DevPlan& d, const BatchTotals& t, const float* posm, const float* eps2, const float* g,
                  float* acc_out, float* vel, const float* ck, void* workspace, hipStream_t st) {
   float* ws = static_cast<float*>(workspace);
   batch_accel_kernel<<<t.n_items, 64 * kWaves, 0, st>>>(reinterpret_cast<const f4*>(posm), d.items, d.scenes, eps2, ws);
-  int rc = bcheck();
+  int rc = launch_status();
   if (rc) return rc;
-  batch_finish_kernel<<<bceil_div(3 * t.n_rows, 256), 256, 0, st>>>(d.row_scene, d.scenes, t.n_rows, ws, g, acc_out,
+  batch_finish_kernel<<<ceil_div(3 * t.n_rows, 256), 256, 0, st>>>(d.row_scene, d.scenes, t.n_rows, ws, g, acc_out,
                                                                    vel, ck);
-  return bcheck();
+  return launch_status();
 }
 
 }  // namespace
@@ -211,9 +211,9 @@ int nbd_batch_plan_fill(const int* offsets, int n_scenes, void* plan, size_t pla
     SceneRec& r = scenes[s];
     r.off = offsets[s]; r.n = offsets[s + 1] - offsets[s]; r.poff = poff; r.ws_off = ws_off; r.u_off = u_off;
     r.slabs = r.n > 0 ? scene_slabs(r.n) : 0;
-    r.n_chunks = bceil_div(r.n, kChunk);
-    r.groups = bceil_div(r.n, kTgtPerWG);
-    const int cpw = r.n > 0 ? bceil_div(r.n_chunks, r.slabs * kWaves) : 0;
+    r.n_chunks = ceil_div(r.n, kChunk);
+    r.groups = ceil_div(r.n, kTgtPerWG);
+    const int cpw = r.n > 0 ? ceil_div(r.n_chunks, r.slabs * kWaves) : 0;
     for (int g = 0; g < r.groups; ++g)
       for (int k = 0; k < r.slabs; ++k) items.insert(items.end(), {s, g, k, cpw});
     for (int i = 0; i < r.n_chunks * kChunk; ++i) rows[(size_t)poff + i] = s;
@@ -240,7 +240,7 @@ int nbd_batch_pack_posm_f32(const int* offsets, int n_scenes, const void* plan, 
   int rc = batch_prologue(offsets, n_scenes, plan, plan_bytes, &t);
   if (rc) return rc;
   if (t.n_total == 0) return 0;
-  if (!pos || !mass || !posm || bmisaligned16(posm)) return NBD_E_BADARG;
+  if (!pos || !mass || !posm || misaligned16(posm)) return NBD_E_BADARG;
   return launch_update(dev_plan(plan, t), t, const_cast<float*>(pos), nullptr, nullptr, mass, nullptr, nullptr, posm,
                        (hipStream_t)stream);
 }
@@ -252,7 +252,7 @@ int nbd_batch_accel_f32(const int* offsets, int n_scenes, const void* plan, size
   int rc = batch_prologue(offsets, n_scenes, plan, plan_bytes, &t);
   if (rc) return rc;
   if (t.n_total == 0) return 0;
-  if (!pos || !mass || !softening_sq || !g_const || !acc_out || !posm || bmisaligned16(posm)) return NBD_E_BADARG;
+  if (!pos || !mass || !softening_sq || !g_const || !acc_out || !posm || misaligned16(posm)) return NBD_E_BADARG;
   if (!workspace || workspace_bytes < ws_bytes_of(t)) return NBD_E_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
   const DevPlan d = dev_plan(plan, t);
@@ -269,7 +269,7 @@ int nbd_batch_leapfrog_step_f32(const int* offsets, int n_scenes, const void* pl
   if (rc) return rc;
   if (t.n_total == 0) return 0;
   if (!pos || !vel || !acc_in || !acc_out || !mass || !dt_half || !dt || !softening_sq || !g_const || !posm ||
-      bmisaligned16(posm))
+      misaligned16(posm))
     return NBD_E_BADARG;
   if (!workspace || workspace_bytes < ws_bytes_of(t)) return NBD_E_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
@@ -286,7 +286,7 @@ int nbd_batch_euler_step_f32(const int* offsets, int n_scenes, const void* plan,
   int rc = batch_prologue(offsets, n_scenes, plan, plan_bytes, &t);
   if (rc) return rc;
   if (t.n_total == 0) return 0;
-  if (!pos || !vel || !acc_out || !mass || !dt || !softening_sq || !g_const || !posm || bmisaligned16(posm))
+  if (!pos || !vel || !acc_out || !mass || !dt || !softening_sq || !g_const || !posm || misaligned16(posm))
     return NBD_E_BADARG;
   if (!workspace || workspace_bytes < ws_bytes_of(t)) return NBD_E_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
@@ -304,7 +304,7 @@ int nbd_batch_energies(const int* offsets, int n_scenes, const void* plan, size_
   int rc = batch_prologue(offsets, n_scenes, plan, plan_bytes, &t);
   if (rc) return rc;
   if (!out_uk || !g_const || !softening) return NBD_E_BADARG;
-  if (t.n_total > 0 && (!posm || !vel || bmisaligned16(posm))) return NBD_E_BADARG;
+  if (t.n_total > 0 && (!posm || !vel || misaligned16(posm))) return NBD_E_BADARG;
   if (!workspace || workspace_bytes < ws_bytes_of(t)) return NBD_E_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
   const DevPlan d = dev_plan(plan, t);
@@ -312,11 +312,11 @@ int nbd_batch_energies(const int* offsets, int n_scenes, const void* plan, size_
   if (t.n_items > 0) {
     batch_energy_kernel<<<t.n_items, 64 * kWaves, 0, st>>>(reinterpret_cast<const f4*>(posm), d.items, d.scenes,
                                                           softening, pu);
-    if ((rc = bcheck())) return rc;
+    if ((rc = launch_status())) return rc;
   }
   batch_energy_final_kernel<<<n_scenes, 256, 0, st>>>(d.scenes, reinterpret_cast<const f4*>(posm), vel, pu, g_const,
                                                       out_uk);
-  return bcheck();
+  return launch_status();
 }
 
 }  // extern "C"

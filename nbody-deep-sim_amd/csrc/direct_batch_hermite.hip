@@ -5,14 +5,14 @@
 // The scenes, the packed rows and the work list are those of direct_batch.hip (direct_batch_plan.h, unchanged): one item
 // per (scene, target group of 128, slab), the slab count of a scene being the single-system plan for its size. One step
 // is three launches for all scenes:
-//   predict  : one thread per packed row: posm = {x_p, m}, velp = {v_p, 0} (zeros in each scene's padding), the
-//              arithmetic of hermite_predict_kernel with the scene's own fp32 step constants
+//   predict  : one thread per packed row: posm = {x_p, m}, velp = {v_p, 0} (zeros in each scene's padding):
+//              hermite_predict (hermite_kernels.h) with the scene's own fp32 step constants
 //   evaluate : one workgroup per item: accel_jerk_body (hermite_kernels.h, KU = 2) on the item's scene, masked or not per scene
 //              from its softening^2; unscaled partial sums into float[slabs][6][n_s] at float 2 * ws_off of the slabs
-//   correct  : one workgroup per 64 packed rows (never across scenes): hermite_correct_kernel's fixed-order slab sum
-//              and corrector with the scene's G and constants; posm = {x1, m} for the energies after the step
-// A scene's work, its split of the sources, its slab sum and its arithmetic depend on n_s and its own parameters alone,
-// and each equals the single-system kernel's: its results are bit-identical to nbd_hermite_step_f32 on that scene alone.
+//   correct  : one workgroup per 64 packed rows (never across scenes): hermite_slab_sum and hermite_correct with the
+//              scene's G and constants; posm = {x1, m} for the energies after the step
+// A scene's work, its split of the sources and its slab sum depend on n_s and its own parameters alone, and its arithmetic
+// is the single-system kernels' own functions: its results are bit-identical to nbd_hermite_step_f32 on that scene alone.
 // No atomics, no memsets, no host syncs: deterministic and capturable.
 #include <hip/hip_runtime.h>
 #include <limits.h>
@@ -25,7 +25,8 @@
 
 namespace {
 
-// rows of the per-scene step-constant table hdt[5][S] (each formed in double and rounded once, as hermite_dt())
+// rows of the per-scene step-constant table hdt[5][S], HermiteDt's fields in order (the caller forms each in double and
+// rounds it once, as hermite_dt() does)
 enum { kDt = 0, kDtHalf = 1, kDt2Half = 2, kDt3Sixth = 3, kDt2Twelfth = 4 };
 
 // posm[r] = {x_p, m}, velp[r] = {v_p, 0} for every packed row r (zeros behind each scene's last body). acc == nullptr:
@@ -56,9 +57,9 @@ __global__ __launch_bounds__(256) void batch_hermite_predict_kernel(const int* _
       x[k] = pos[3 * b + k];
       v[k] = vel[3 * b + k];
       if (acc) {
-        const float a = acc[3 * b + k], j = jerk[3 * b + k];
-        x[k] = ((x[k] + v[k] * dt) + a * dt2_half) + j * dt3_sixth;
-        v[k] = (v[k] + a * dt) + j * dt2_half;
+        const PosVel p = hermite_predict(x[k], v[k], acc[3 * b + k], jerk[3 * b + k], dt, dt2_half, dt3_sixth);
+        x[k] = p.x;
+        v[k] = p.v;
       }
     }
     pm = f4{x[0], x[1], x[2], mass[b]};
@@ -92,7 +93,8 @@ __global__ __launch_bounds__(64 * kWaves, 5) void batch_accel_jerk_kernel(const 
   const int i0 = t_base + (threadIdx.x & 63), i1 = i0 + 64;
   const int cpw_q = n_chunks / (slabs * kWaves), cpw_r = n_chunks % (slabs * kWaves);
   const int jw = slab * kWaves + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int c_begin = jw * cpw_q + min(jw, cpw_r), c_end = c_begin + cpw_q + (jw < cpw_r ? 1 : 0);
+  int c_begin, c_end;
+  wave_chunk_range(jw, cpw_q, cpw_r, c_begin, c_end);
   float* dst = ws + 2 * (size_t)sc.ws_off + (size_t)slab * 6 * n + t_base;
   const int n_valid = min(kTgtPerWG, n - t_base);
   if (eps2 < kEps2Masked)
@@ -103,11 +105,10 @@ __global__ __launch_bounds__(64 * kWaves, 5) void batch_accel_jerk_kernel(const 
                               lds, dst, n, n_valid);
 }
 
-// One workgroup per 64 packed rows (a scene's rows are whole chunks of 64, so a block never spans two scenes):
-// hermite_correct_kernel's fixed order -- wave w sums slabs w, w+4, ..., the partials combined as (p0 + p1) + (p2 + p3)
-// -- then a1 = G_s sum, j1 = G_s sum. pos == nullptr: write a1, j1 only. Else the corrector: reads a0, j0 (acc_in /
-// jerk_in may alias acc_out / jerk_out: each element is read before it is written, by the same thread), x, v; writes
-// x1, v1, a1, j1 and posm = {x1, m}.
+// One workgroup per 64 packed rows (a scene's rows are whole chunks of 64, so a block never spans two scenes): a1, j1 =
+// hermite_slab_sum of the body's row in its scene's slabs, scaled by G_s. pos == nullptr: write a1, j1 only. Else
+// hermite_correct: reads a0, j0 (acc_in / jerk_in may alias acc_out / jerk_out: each element is read before it is
+// written, by the same thread), x, v; writes x1, v1, a1, j1 and posm = {x1, m}.
 __global__ __launch_bounds__(256) void batch_hermite_correct_kernel(const int* __restrict__ row_scene,
                                                                     const SceneRec* __restrict__ scenes,
                                                                     const float* __restrict__ ws,
@@ -118,29 +119,13 @@ __global__ __launch_bounds__(256) void batch_hermite_correct_kernel(const int* _
                                                                     float* jerk_out, const float* __restrict__ mass,
                                                                     f4* __restrict__ posm) {
   __shared__ float part[4][6][64];
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int lane = threadIdx.x & 63;
   const int r0 = blockIdx.x * 64;
   const int s = row_scene[r0];
   const SceneRec sc = load_scene(scenes, s);
-  const int n = sc.n;
   const int i = r0 - sc.poff + lane;
-  const float* slabs = ws + 2 * (size_t)sc.ws_off;
-  float sum[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  if (i < n)
-    for (int k = w; k < sc.slabs; k += 4)
-#pragma unroll
-      for (int c = 0; c < 6; ++c) sum[c] += slabs[((size_t)k * 6 + c) * n + i];
-#pragma unroll
-  for (int c = 0; c < 6; ++c) part[w][c][lane] = sum[c];
-  __syncthreads();
-  if (w != 0 || i >= n) return;
-  const float g = g_s[s];
   float a1[3], j1[3];
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    a1[k] = g * ((part[0][k][lane] + part[1][k][lane]) + (part[2][k][lane] + part[3][k][lane]));
-    j1[k] = g * ((part[0][k + 3][lane] + part[1][k + 3][lane]) + (part[2][k + 3][lane] + part[3][k + 3][lane]));
-  }
+  if (!hermite_slab_sum(ws + 2 * (size_t)sc.ws_off, sc.slabs, sc.n, i, i < sc.n, g_s[s], part, a1, j1)) return;
   const size_t b = (size_t)sc.off + i;
   if (pos) {
     const float dt_half = hdt[kDtHalf * n_scenes + s], dt2_twelfth = hdt[kDt2Twelfth * n_scenes + s];
@@ -172,10 +157,10 @@ bool hws_fits(const BatchTotals& t) { return 2 * t.ws_floats <= (int64_t)INT_MAX
 int launch_predict(const DevPlan& d, const BatchTotals& t, const float* pos, const float* vel, const float* acc,
                    const float* jerk, const float* mass, const float* hdt, int n_scenes, float* posm, void* workspace,
                    hipStream_t st) {
-  batch_hermite_predict_kernel<<<bceil_div(t.n_rows, 256), 256, 0, st>>>(
+  batch_hermite_predict_kernel<<<ceil_div(t.n_rows, 256), 256, 0, st>>>(
       d.row_scene, d.scenes, t.n_rows, pos, vel, acc, jerk, mass, hdt, n_scenes, reinterpret_cast<f4*>(posm),
       static_cast<f4*>(workspace));
-  return bcheck();
+  return launch_status();
 }
 
 // the force of every scene at posm / velp, then the slab sum (+ the corrector when pos is given)
@@ -187,12 +172,12 @@ int launch_force_correct(const DevPlan& d, const BatchTotals& t, float* posm, co
   float* slabs = reinterpret_cast<float*>(static_cast<char*>(workspace) + hws_slab_offset(t));
   batch_accel_jerk_kernel<<<t.n_items, 64 * kWaves, 0, st>>>(reinterpret_cast<const f4*>(posm), velp, d.items,
                                                              d.scenes, eps2, slabs);
-  int rc = bcheck();
+  int rc = launch_status();
   if (rc) return rc;
   batch_hermite_correct_kernel<<<t.n_rows / kChunk, 256, 0, st>>>(d.row_scene, d.scenes, slabs, g, hdt, n_scenes,
                                                                    pos, vel, acc_in, jerk_in, acc_out, jerk_out, mass,
                                                                    reinterpret_cast<f4*>(posm));
-  return bcheck();
+  return launch_status();
 }
 
 }  // namespace
@@ -218,9 +203,9 @@ int nbd_batch_accel_jerk_f32(const int* offsets, int n_scenes, const void* plan,
   if (rc) return rc;
   if (!hws_fits(t)) return NBD_E_UNSUPPORTED;
   if (t.n_total == 0) return 0;
-  if (!pos || !vel || !mass || !softening_sq || !g_const || !acc_out || !jerk_out || !posm || bmisaligned16(posm))
+  if (!pos || !vel || !mass || !softening_sq || !g_const || !acc_out || !jerk_out || !posm || misaligned16(posm))
     return NBD_E_BADARG;
-  if (!workspace || bmisaligned16(workspace) || workspace_bytes < hws_bytes_of(t)) return NBD_E_WORKSPACE;
+  if (!workspace || misaligned16(workspace) || workspace_bytes < hws_bytes_of(t)) return NBD_E_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
   const DevPlan d = dev_plan(plan, t);
   if ((rc = launch_predict(d, t, pos, vel, nullptr, nullptr, mass, nullptr, n_scenes, posm, workspace, st))) return rc;
@@ -238,9 +223,9 @@ int nbd_batch_hermite_step_f32(const int* offsets, int n_scenes, const void* pla
   if (!hws_fits(t)) return NBD_E_UNSUPPORTED;
   if (t.n_total == 0) return 0;
   if (!pos || !vel || !acc_in || !jerk_in || !acc_out || !jerk_out || !mass || !hdt || !softening_sq || !g_const ||
-      !posm || bmisaligned16(posm))
+      !posm || misaligned16(posm))
     return NBD_E_BADARG;
-  if (!workspace || bmisaligned16(workspace) || workspace_bytes < hws_bytes_of(t)) return NBD_E_WORKSPACE;
+  if (!workspace || misaligned16(workspace) || workspace_bytes < hws_bytes_of(t)) return NBD_E_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
   const DevPlan d = dev_plan(plan, t);
   if ((rc = launch_predict(d, t, pos, vel, acc_in, jerk_in, mass, hdt, n_scenes, posm, workspace, st))) return rc;

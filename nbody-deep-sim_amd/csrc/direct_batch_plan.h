@@ -24,8 +24,6 @@ struct SceneRec {
   int groups;   // ceil(n / 128)
 };
 
-inline int bceil_div(int a, int b) { return (a + b - 1) / b; }
-
 // The slab count of a scene: the single-system launch plan for its size (depends on n alone).
 int scene_slabs(int n) {
   struct Memo { int n, slabs; };
@@ -53,9 +51,9 @@ int batch_totals(const int* offsets, int n_scenes, BatchTotals* t) {
     const int n = offsets[s + 1] - offsets[s];
     if (offsets[s + 1] < offsets[s] || offsets[s + 1] < 0) return NBD_E_BADARG;
     if (n == 0) continue;
-    const int slabs = scene_slabs(n), groups = bceil_div(n, kTgtPerWG);
+    const int slabs = scene_slabs(n), groups = ceil_div(n, kTgtPerWG);
     items += (int64_t)groups * slabs;
-    rows += (int64_t)bceil_div(n, kChunk) * kChunk;
+    rows += (int64_t)ceil_div(n, kChunk) * kChunk;
     ws += (int64_t)slabs * n * 3;
     ud += (int64_t)groups * slabs;
   }
@@ -90,14 +88,11 @@ __device__ __forceinline__ SceneRec load_scene(const SceneRec* scenes, int s) {
   return SceneRec{a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
 }
 
-inline int bcheck() { const hipError_t e = hipGetLastError(); return e == hipSuccess ? 0 : (int)e; }
-bool bmisaligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; }
-
 // common argument checks of the launching entry points; fills t
 int batch_prologue(const int* offsets, int n_scenes, const void* plan, size_t plan_bytes, BatchTotals* t) {
   int rc = batch_totals(offsets, n_scenes, t);
   if (rc) return rc;
-  if (!plan || bmisaligned16(plan) || plan_bytes != plan_bytes_of(*t)) return NBD_E_BADARG;
+  if (!plan || misaligned16(plan) || plan_bytes != plan_bytes_of(*t)) return NBD_E_BADARG;
   return 0;
 }
 

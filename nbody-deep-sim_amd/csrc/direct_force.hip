@@ -586,7 +586,6 @@ AccelPlan plan_chunks(int n_chunks, int n_tgt) {
 AccelPlan plan_accel(int n_src, int n_tgt) { return plan_chunks(ceil_div(n_src, kChunk), n_tgt); }
 
 inline int check(hipError_t e) { return e == hipSuccess ? 0 : (int)e; }
-inline int launch_status() { return check(hipGetLastError()); }
 
 // all sources of an n_src array, split as the plan says
 SrcView full_view(int n_src, const AccelPlan& p) { return full_view(n_src, p.n_chunks, p.slabs); }
@@ -629,8 +628,6 @@ int launch_accel(const float* posm_src, SrcView sv, const float* posm_tgt, int n
 #undef NBD_LAUNCH
   return launch_status();
 }
-
-bool misaligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; }
 
 // ---- the symmetric force's launch plan (accel_sym_kernel): M even tiles of kSymTile, K slots, the remainder rows
 // [core, n) in one more slot

@@ -10,6 +10,8 @@
 //   correct  : fixed-order slab sum, a1 = G sum, j1 = G sum, then
 //              v1 = v + (a0 + a1) dt/2 + (j0 - j1) dt^2/12,  x1 = x + (v + v1) dt/2 + (a0 - a1) dt^2/12,
 //              posm = {x1, m} (energies after the step need no extra pack)
+// The arithmetic of all three (hermite_predict, accel_jerk_body, hermite_slab_sum, hermite_correct) and the step constants
+// (hermite_dt) live in hermite_kernels.h, shared with the block-timestep and the batched unit.
 // No atomics, no memsets, no host syncs: deterministic and capturable.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -34,17 +36,10 @@ __global__ __launch_bounds__(64 * kWaves, KU == 2 ? 6 : 5) void accel_jerk_kerne
   const int t_base = blockIdx.x * kTgtPerWG;
   const int i0 = t_base + (threadIdx.x & 63), i1 = i0 + 64;
   const int jw = blockIdx.y * kWaves + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int c_begin = jw * cpw_q + min(jw, cpw_r), c_end = c_begin + cpw_q + (jw < cpw_r ? 1 : 0);
+  int c_begin, c_end;
+  wave_chunk_range(jw, cpw_q, cpw_r, c_begin, c_end);
   accel_jerk_body<MASKED, KU>(posm, velp, n, min(i0, n - 1), min(i1, n - 1), i0, i1, c_begin, c_end, eps2, lds,
                               out + (size_t)blockIdx.y * 6 * n + t_base, n, min(kTgtPerWG, n - t_base));
-}
-
-// fp32 step constants, each formed in double and rounded once
-struct HermiteDt { float dt, dt_half, dt2_half, dt3_sixth, dt2_twelfth; };
-
-HermiteDt hermite_dt(double dt) {
-  return HermiteDt{(float)dt, (float)(0.5 * dt), (float)(0.5 * dt * dt), (float)(dt * dt * dt / 6.0),
-                   (float)(dt * dt / 12.0)};
 }
 
 // posm = {x_p, m}, velp = {v_p, 0} for rows [0, n_pad) (zero padding behind n). acc == nullptr: plain pack (x, v).
@@ -62,9 +57,9 @@ __global__ __launch_bounds__(256) void hermite_predict_kernel(const float* __res
       x[k] = pos[3 * i + k];
       v[k] = vel[3 * i + k];
       if (acc) {
-        const float a = acc[3 * i + k], j = jerk[3 * i + k];
-        x[k] = ((x[k] + v[k] * h.dt) + a * h.dt2_half) + j * h.dt3_sixth;
-        v[k] = (v[k] + a * h.dt) + j * h.dt2_half;
+        const PosVel p = hermite_predict(x[k], v[k], acc[3 * i + k], jerk[3 * i + k], h.dt, h.dt2_half, h.dt3_sixth);
+        x[k] = p.x;
+        v[k] = p.v;
       }
     }
     pm = f4{x[0], x[1], x[2], mass[i]};
@@ -74,32 +69,17 @@ __global__ __launch_bounds__(256) void hermite_predict_kernel(const float* __res
   velp[i] = vp;
 }
 
-// a1 = g * sum of the slabs, j1 likewise, in a fixed order (finish_kernel's scheme: wave w of the block sums slabs
-// w, w+4, ... of 64 consecutive bodies, the four partials combined as (p0 + p1) + (p2 + p3)). pos == nullptr: write a1, j1
-// only (the force on its own). Else the corrector: reads a0, j0 (acc_in / jerk_in, which may alias acc_out / jerk_out:
+// One workgroup per 64 consecutive bodies: a1, j1 = hermite_slab_sum of the body's row. pos == nullptr: write a1, j1
+// only (the force on its own). Else hermite_correct: reads a0, j0 (acc_in / jerk_in, which may alias acc_out / jerk_out:
 // each element is read before it is written, by the same thread), x, v; writes x1, v1, a1, j1 and posm = {x1, m}.
 __global__ __launch_bounds__(256) void hermite_correct_kernel(const float* __restrict__ slabs, int n_slabs, int n, float g,
                                                               HermiteDt h, float* pos, float* vel, const float* acc_in,
                                                               const float* jerk_in, float* acc_out, float* jerk_out,
                                                               const float* __restrict__ mass, f4* __restrict__ posm) {
   __shared__ float part[4][6][64];
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int i = blockIdx.x * 64 + lane;
-  float sum[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  if (i < n)
-    for (int s = w; s < n_slabs; s += 4)
-#pragma unroll
-      for (int k = 0; k < 6; ++k) sum[k] += slabs[((size_t)s * 6 + k) * n + i];
-#pragma unroll
-  for (int k = 0; k < 6; ++k) part[w][k][lane] = sum[k];
-  __syncthreads();
-  if (w != 0 || i >= n) return;
+  const int i = blockIdx.x * 64 + (threadIdx.x & 63);
   float a1[3], j1[3];
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    a1[k] = g * ((part[0][k][lane] + part[1][k][lane]) + (part[2][k][lane] + part[3][k][lane]));
-    j1[k] = g * ((part[0][k + 3][lane] + part[1][k + 3][lane]) + (part[2][k + 3][lane] + part[3][k + 3][lane]));
-  }
+  if (!hermite_slab_sum(slabs, n_slabs, n, i, i < n, g, part, a1, j1)) return;
   if (pos) {
     float x1[3];
 #pragma unroll
@@ -119,35 +99,21 @@ __global__ __launch_bounds__(256) void hermite_correct_kernel(const float* __res
   }
 }
 
-bool misaligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; }
-
-// the all-pairs force's launch geometry (nbd_accel_plan): same targets, same chunks, the same balance problem
-struct JerkPlan { int groups, slabs, n_chunks; };
-
-JerkPlan plan_jerk(int n) {
-  JerkPlan p;
-  int cpw = 0;
-  nbd_accel_plan(n, n, &p.groups, &p.slabs, &cpw);
-  p.n_chunks = ceil_div(n, kChunk);
-  return p;
-}
-
 size_t velp_bytes(int n) { return (size_t)ceil_div(n, kChunk) * kChunk * sizeof(f4); }
 
 // the unscaled partial sums of every body into float[slabs][6][n]
 int launch_jerk(const float* posm, const float* velp, int n, float eps2, float* slabs, const JerkPlan& p, int variant,
                 hipStream_t st) {
   dim3 grid(p.groups, p.slabs), block(64 * kWaves);
-  const int q = p.n_chunks / (p.slabs * kWaves), r = p.n_chunks % (p.slabs * kWaves);
+  const ChunkSplit c = chunk_split(p.n_chunks, p.slabs);
   const f4* pm = reinterpret_cast<const f4*>(posm);
   const f4* vp = reinterpret_cast<const f4*>(velp);
   const bool masked = eps2 < kEps2Masked;
-#define NBD_LAUNCH(M, K) accel_jerk_kernel<M, K><<<grid, block, 0, st>>>(pm, vp, n, q, r, eps2, slabs)
+#define NBD_LAUNCH(M, K) accel_jerk_kernel<M, K><<<grid, block, 0, st>>>(pm, vp, n, c.q, c.r, eps2, slabs)
   if (variant == 1) { if (masked) NBD_LAUNCH(true, 4); else NBD_LAUNCH(false, 4); }
   else              { if (masked) NBD_LAUNCH(true, 2); else NBD_LAUNCH(false, 2); }
 #undef NBD_LAUNCH
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : (int)e;
+  return launch_status();
 }
 
 }  // namespace
@@ -156,7 +122,7 @@ extern "C" {
 
 size_t nbd_hermite_workspace_bytes(int n) {
   if (n <= 0) return 0;
-  return velp_bytes(n) + (size_t)plan_jerk(n).slabs * 6 * n * sizeof(float);
+  return velp_bytes(n) + (size_t)plan_jerk(n, n).slabs * 6 * n * sizeof(float);
 }
 
 int nbd_hermite_pack_f32(const float* pos, const float* vel, const float* acc, const float* jerk, const float* mass,
@@ -167,8 +133,7 @@ int nbd_hermite_pack_f32(const float* pos, const float* vel, const float* acc, c
   const int n_pad = nbd_posm_padded_len(n);
   hermite_predict_kernel<<<ceil_div(n_pad, 256), 256, 0, (hipStream_t)stream>>>(
       pos, vel, acc, jerk, mass, n, n_pad, hermite_dt(dt), reinterpret_cast<f4*>(posm), reinterpret_cast<f4*>(velp));
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : (int)e;
+  return launch_status();
 }
 
 int nbd_accel_jerk_f32(const float* posm, const float* velp, int n, float softening_sq, float g_const, float* acc_out,
@@ -178,14 +143,13 @@ int nbd_accel_jerk_f32(const float* posm, const float* velp, int n, float soften
   if (!posm || !velp || !acc_out || !jerk_out || misaligned16(posm) || misaligned16(velp)) return NBD_E_BADARG;
   if (!workspace || workspace_bytes < nbd_hermite_workspace_bytes(n)) return NBD_E_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
-  const JerkPlan p = plan_jerk(n);
+  const JerkPlan p = plan_jerk(n, n);
   float* slabs = static_cast<float*>(workspace);
   int rc = launch_jerk(posm, velp, n, softening_sq, slabs, p, variant, st);
   if (rc) return rc;
   hermite_correct_kernel<<<ceil_div(n, 64), 256, 0, st>>>(slabs, p.slabs, n, g_const, hermite_dt(0.0), nullptr, nullptr,
                                                           nullptr, nullptr, acc_out, jerk_out, nullptr, nullptr);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : (int)e;
+  return launch_status();
 }
 
 int nbd_hermite_step_f32(float* pos, float* vel, const float* acc_in, const float* jerk_in, float* acc_out,
@@ -198,20 +162,18 @@ int nbd_hermite_step_f32(float* pos, float* vel, const float* acc_in, const floa
   if (!workspace || misaligned16(workspace) || workspace_bytes < nbd_hermite_workspace_bytes(n)) return NBD_E_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
   const HermiteDt h = hermite_dt(dt);
-  const JerkPlan p = plan_jerk(n);
+  const JerkPlan p = plan_jerk(n, n);
   float* velp = static_cast<float*>(workspace);
   float* slabs = reinterpret_cast<float*>(static_cast<char*>(workspace) + velp_bytes(n));
   const int n_pad = nbd_posm_padded_len(n);
   hermite_predict_kernel<<<ceil_div(n_pad, 256), 256, 0, st>>>(pos, vel, acc_in, jerk_in, mass, n, n_pad, h,
                                                                reinterpret_cast<f4*>(posm), reinterpret_cast<f4*>(velp));
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return (int)e;
-  int rc = launch_jerk(posm, velp, n, softening_sq, slabs, p, 0, st);
+  int rc = launch_status();
   if (rc) return rc;
+  if ((rc = launch_jerk(posm, velp, n, softening_sq, slabs, p, 0, st))) return rc;
   hermite_correct_kernel<<<ceil_div(n, 64), 256, 0, st>>>(slabs, p.slabs, n, g_const, h, pos, vel, acc_in, jerk_in,
                                                           acc_out, jerk_out, mass, reinterpret_cast<f4*>(posm));
-  e = hipGetLastError();
-  return e == hipSuccess ? 0 : (int)e;
+  return launch_status();
 }
 
 }  // extern "C"

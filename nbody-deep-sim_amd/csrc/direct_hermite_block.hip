@@ -13,8 +13,9 @@
 //              float[slabs][6][n_act] partial sums (accel_jerk_kernel's arithmetic and source order)
 //   correct  : fixed-order slab sum, the corrector with the body's own step h = d_i, the Aarseth criterion in fp64 for the
 //              new level, t_i = t_next (0 at the end of the interval), posm = {x1, m}
-// The fp32 step constants are formed in fp64 from dt and the tick count and rounded once, exactly as hermite_dt() does:
-// a body whose Delta is the whole interval gets the shared step's bits. No float atomics (the clamp counter is an integer
+// Predictor, force body, slab sum and corrector are the shared step's own functions (hermite_kernels.h), and the fp32
+// step constants come from hermite_dt() on the body's fp64 step (dt times its tick count): a body whose Delta is the
+// whole interval gets the shared step's bits. No float atomics (the clamp counter is an integer
 // atomic); the host reads {t_next, n_act} once per block step, so the path is eager-only.
 #include <hip/hip_runtime.h>
 #include <limits.h>
@@ -51,7 +52,8 @@ __global__ __launch_bounds__(64 * kWaves, 6) void accel_jerk_active_kernel(
   const int l0 = t_base + (threadIdx.x & 63);
   const int i0 = act[min(l0, n_act - 1)], i1 = act[min(l0 + 64, n_act - 1)];
   const int jw = blockIdx.y * kWaves + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int c_begin = jw * cpw_q + min(jw, cpw_r), c_end = c_begin + cpw_q + (jw < cpw_r ? 1 : 0);
+  int c_begin, c_end;
+  wave_chunk_range(jw, cpw_q, cpw_r, c_begin, c_end);
   accel_jerk_body<MASKED, 2>(posm, velp, n, i0, i1, i0, i1, c_begin, c_end, eps2, lds,
                              out + (size_t)blockIdx.y * 6 * n_act + t_base, n_act, min(kTgtPerWG, n_act - t_base));
 }
@@ -141,7 +143,8 @@ __global__ __launch_bounds__(256) void hblock_schedule_kernel(const int* __restr
 }
 
 // posm = {x_p, m}, velp = {v_p, 0} for rows [0, n_pad) (zero padding behind n): every body predicted from its last
-// correction to t_next = sched[0], over Delta_i = (t_next - t_i) dt / 2^K, the constants formed as hermite_dt() forms them.
+// correction to t_next = sched[0] by hermite_predict over Delta_i = (t_next - t_i) dt / 2^K, its constants from
+// hermite_dt().
 __global__ __launch_bounds__(256) void hblock_predict_kernel(const float* __restrict__ pos, const float* __restrict__ vel,
                                                              const float* __restrict__ acc, const float* __restrict__ jerk,
                                                              const float* __restrict__ mass, const int* __restrict__ ticks,
@@ -152,16 +155,14 @@ __global__ __launch_bounds__(256) void hblock_predict_kernel(const float* __rest
   if (i >= n_pad) return;
   f4 pm = {0.f, 0.f, 0.f, 0.f}, vp = {0.f, 0.f, 0.f, 0.f};
   if (i < n) {
-    const double h = dt * (double)(sched[kTNext] - ticks[i]) * tick;
-    const float c1 = (float)h, c2 = (float)(0.5 * h * h), c3 = (float)(h * h * h / 6.0);
+    const HermiteDt h = hermite_dt(dt * (double)(sched[kTNext] - ticks[i]) * tick);  // dt, dt2_half, dt3_sixth used
     float x[3], v[3];
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
-      x[k] = pos[3 * i + k];
-      v[k] = vel[3 * i + k];
-      const float a = acc[3 * i + k], j = jerk[3 * i + k];
-      x[k] = ((x[k] + v[k] * c1) + a * c2) + j * c3;
-      v[k] = (v[k] + a * c1) + j * c2;
+      const PosVel p = hermite_predict(pos[3 * i + k], vel[3 * i + k], acc[3 * i + k], jerk[3 * i + k], h.dt, h.dt2_half,
+                                       h.dt3_sixth);
+      x[k] = p.x;
+      v[k] = p.v;
     }
     pm = f4{x[0], x[1], x[2], mass[i]};
     vp = f4{v[0], v[1], v[2], 0.f};
@@ -170,11 +171,11 @@ __global__ __launch_bounds__(256) void hblock_predict_kernel(const float* __rest
   velp[i] = vp;
 }
 
-// The active bodies' corrector: a1 = g * sum of the slabs, j1 likewise, in hermite_correct_kernel's fixed order (wave w of
-// the block sums slabs w, w+4, ... of 64 consecutive list entries; the four partials combined as (p0 + p1) + (p2 + p3)).
-// pos == nullptr: write a1, j1 in list order only (the force on its own). Else, for body i = act[p] with its own step
-// h = dt 2^-k_i: the corrector, then the new level from the Aarseth criterion in fp64 (shrink freely; grow by one level
-// where t_next is a multiple of 2 d_i; deeper than K clamped and counted), t_i = t_next (0 at 2^K), posm = {x1, m}.
+// The active bodies' corrector, one workgroup per 64 consecutive list entries: a1, j1 = hermite_slab_sum of the entry's
+// row. pos == nullptr: write a1, j1 in list order only (the force on its own). Else, for body i = act[p] with its own step
+// h = dt 2^-k_i: hermite_correct with hermite_dt(h), then the new level from the Aarseth criterion in fp64 (shrink freely;
+// grow by one level where t_next is a multiple of 2 d_i; deeper than K clamped and counted), t_i = t_next (0 at 2^K),
+// posm = {x1, m}.
 __global__ __launch_bounds__(256) void hblock_correct_kernel(const float* __restrict__ slabs, int n_slabs,
                                                              const int* __restrict__ act, int n_act, float g, int K,
                                                              double dt, double tick, double eta, float* pos, float* vel,
@@ -182,23 +183,9 @@ __global__ __launch_bounds__(256) void hblock_correct_kernel(const float* __rest
                                                              int* __restrict__ ticks, int* __restrict__ levels,
                                                              int* __restrict__ sched, f4* __restrict__ posm) {
   __shared__ float part[4][6][64];
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int p = blockIdx.x * 64 + lane;
-  float sum[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  if (p < n_act)
-    for (int s = w; s < n_slabs; s += 4)
-#pragma unroll
-      for (int k = 0; k < 6; ++k) sum[k] += slabs[((size_t)s * 6 + k) * n_act + p];
-#pragma unroll
-  for (int k = 0; k < 6; ++k) part[w][k][lane] = sum[k];
-  __syncthreads();
-  if (w != 0 || p >= n_act) return;
+  const int p = blockIdx.x * 64 + (threadIdx.x & 63);
   float a1[3], j1[3];
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    a1[k] = g * ((part[0][k][lane] + part[1][k][lane]) + (part[2][k][lane] + part[3][k][lane]));
-    j1[k] = g * ((part[0][k + 3][lane] + part[1][k + 3][lane]) + (part[2][k + 3][lane] + part[3][k + 3][lane]));
-  }
+  if (!hermite_slab_sum(slabs, n_slabs, n_act, p, p < n_act, g, part, a1, j1)) return;
   if (!pos) {
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
@@ -211,17 +198,16 @@ __global__ __launch_bounds__(256) void hblock_correct_kernel(const float* __rest
   const int lev = levels[i];
   const int d = 1 << (K - lev);
   const double h = dt * (double)d * tick;
-  const float dt_half = (float)(0.5 * h), dt2_twelfth = (float)(h * h / 12.0);
+  const HermiteDt hc = hermite_dt(h);  // only dt_half and dt2_twelfth are used; the other three are never formed
   float x1[3];
   double a0d[3], j0d[3];
 #pragma unroll
   for (int k = 0; k < 3; ++k) {
     const float a0 = acc[3 * i + k], j0 = jerk[3 * i + k];
-    const float x = pos[3 * i + k], v = vel[3 * i + k];
-    const float v1 = (v + (a0 + a1[k]) * dt_half) + (j0 - j1[k]) * dt2_twelfth;
-    x1[k] = (x + (v + v1) * dt_half) + (a0 - a1[k]) * dt2_twelfth;
-    vel[3 * i + k] = v1;
-    pos[3 * i + k] = x1[k];
+    float x = pos[3 * i + k], v = vel[3 * i + k];
+    hermite_correct(x, v, a0, j0, a1[k], j1[k], hc.dt_half, hc.dt2_twelfth);
+    vel[3 * i + k] = v;
+    pos[3 * i + k] = x1[k] = x;
     acc[3 * i + k] = a1[k];
     jerk[3 * i + k] = j1[k];
     a0d[k] = a0;
@@ -262,18 +248,11 @@ __global__ __launch_bounds__(256) void hblock_correct_kernel(const float* __rest
   if (p == 0) sched[kTCur] = t_now;
 }
 
-bool misaligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; }
-
-struct ActPlan { int groups, slabs, n_chunks; };
-
 // All targets active: the shared step's plan, nbd_accel_plan(n, n), so that the sums are bit-identical to it. Fewer: the
 // plan of n_act targets, with the slab count raised until groups x slabs reaches kActSlabTarget (at least one chunk per
 // wave, at most kActMaxSlabs).
-ActPlan plan_active(int n, int n_act) {
-  ActPlan p;
-  int cpw = 0;
-  nbd_accel_plan(n, n_act, &p.groups, &p.slabs, &cpw);
-  p.n_chunks = ceil_div(n, kChunk);
+JerkPlan plan_active(int n, int n_act) {
+  JerkPlan p = plan_jerk(n, n_act);
   if (n_act < n && p.groups * p.slabs < kActSlabTarget) {
     int s = ceil_div(kActSlabTarget, p.groups);
     const int cap = p.n_chunks / kWaves < kActMaxSlabs ? p.n_chunks / kWaves : kActMaxSlabs;
@@ -306,20 +285,17 @@ size_t slab_floats(int n) {
   return most * 6;
 }
 
-inline int status() {
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : (int)e;
-}
-
 int launch_active(const float* posm, const float* velp, int n, const int* act, int n_act, float eps2, float* slabs,
-                  const ActPlan& p, hipStream_t st) {
+                  const JerkPlan& p, hipStream_t st) {
   dim3 grid(p.groups, p.slabs), block(64 * kWaves);
-  const int q = p.n_chunks / (p.slabs * kWaves), r = p.n_chunks % (p.slabs * kWaves);
+  const ChunkSplit c = chunk_split(p.n_chunks, p.slabs);
   const f4* pm = reinterpret_cast<const f4*>(posm);
   const f4* vp = reinterpret_cast<const f4*>(velp);
-  if (eps2 < kEps2Masked) accel_jerk_active_kernel<true><<<grid, block, 0, st>>>(pm, vp, n, act, n_act, q, r, eps2, slabs);
-  else accel_jerk_active_kernel<false><<<grid, block, 0, st>>>(pm, vp, n, act, n_act, q, r, eps2, slabs);
-  return status();
+  if (eps2 < kEps2Masked)
+    accel_jerk_active_kernel<true><<<grid, block, 0, st>>>(pm, vp, n, act, n_act, c.q, c.r, eps2, slabs);
+  else
+    accel_jerk_active_kernel<false><<<grid, block, 0, st>>>(pm, vp, n, act, n_act, c.q, c.r, eps2, slabs);
+  return launch_status();
 }
 
 bool bad_level(int K) { return K < 0 || K > kMaxLevel; }
@@ -347,7 +323,7 @@ int nbd_hblock_init_levels(const float* acc, const float* jerk, int n, double dt
   hipError_t e = hipMemsetAsync(sched + kTCur, 0, (NBD_HBLOCK_SCHED_INTS - kTCur) * sizeof(int), st);
   if (e != hipSuccess) return (int)e;
   hblock_init_kernel<<<ceil_div(n, 256), 256, 0, st>>>(acc, jerk, n, max_level, dt, eta, ticks, levels, sched);
-  return status();
+  return launch_status();
 }
 
 int nbd_hblock_schedule(const int* levels, int n, int max_level, int* sched, void* workspace, size_t workspace_bytes,
@@ -356,7 +332,7 @@ int nbd_hblock_schedule(const int* levels, int n, int max_level, int* sched, voi
   if (!workspace || misaligned16(workspace) || workspace_bytes < act_bytes(n)) return NBD_E_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
   hblock_schedule_kernel<<<ceil_div(n, 256), 256, 0, st>>>(levels, n, max_level, sched, ws_act(workspace));
-  int rc = status();
+  int rc = launch_status();
   if (rc || !host_sched) return rc;
   hipError_t e = hipMemcpyAsync(host_sched, sched, 4 * sizeof(int), hipMemcpyDeviceToHost, st);
   if (e == hipSuccess) e = hipStreamSynchronize(st);
@@ -373,7 +349,7 @@ int nbd_hblock_predict_f32(const float* pos, const float* vel, const float* acc,
   hblock_predict_kernel<<<ceil_div(n_pad, 256), 256, 0, (hipStream_t)stream>>>(
       pos, vel, acc, jerk, mass, ticks, n, n_pad, dt, ldexp(1.0, -max_level), sched, reinterpret_cast<f4*>(posm),
       reinterpret_cast<f4*>(velp));
-  return status();
+  return launch_status();
 }
 
 int nbd_hblock_force_f32(const float* posm, const float* velp, int n, int n_act, float softening_sq, void* workspace,
@@ -394,11 +370,11 @@ int nbd_hblock_correct_f32(float* pos, float* vel, float* acc, float* jerk, cons
     return NBD_E_BADARG;
   if (!workspace || misaligned16(workspace) || workspace_bytes < step_bytes(n, n_act)) return NBD_E_WORKSPACE;
   if (n_act == 0) return 0;
-  const ActPlan p = plan_active(n, n_act);
+  const JerkPlan p = plan_active(n, n_act);
   hblock_correct_kernel<<<ceil_div(n_act, 64), 256, 0, (hipStream_t)stream>>>(
       ws_slabs(workspace, n), p.slabs, ws_act(workspace), n_act, g_const, max_level, dt, ldexp(1.0, -max_level), eta,
       pos, vel, acc, jerk, mass, ticks, levels, sched, reinterpret_cast<f4*>(posm));
-  return status();
+  return launch_status();
 }
 
 int nbd_hblock_step_f32(float* pos, float* vel, float* acc, float* jerk, const float* mass, int* ticks, int* levels,
@@ -423,14 +399,14 @@ int nbd_accel_jerk_active_f32(const float* posm, const float* velp, int n, const
   if (!posm || !velp || !act || !acc_out || !jerk_out || misaligned16(posm) || misaligned16(velp)) return NBD_E_BADARG;
   if (!workspace || misaligned16(workspace) || workspace_bytes < step_bytes(n, n_act)) return NBD_E_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
-  const ActPlan p = plan_active(n, n_act);
+  const JerkPlan p = plan_active(n, n_act);
   float* slabs = ws_slabs(workspace, n);
   int rc = launch_active(posm, velp, n, act, n_act, softening_sq, slabs, p, st);
   if (rc) return rc;
   hblock_correct_kernel<<<ceil_div(n_act, 64), 256, 0, st>>>(slabs, p.slabs, act, n_act, g_const, 0, 1.0, 1.0, 1.0,
                                                              nullptr, nullptr, acc_out, jerk_out, nullptr, nullptr,
                                                              nullptr, nullptr, nullptr);
-  return status();
+  return launch_status();
 }
 
 }  // extern "C"

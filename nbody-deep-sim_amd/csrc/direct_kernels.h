@@ -1,5 +1,6 @@
-// direct_kernels.h -- device building blocks shared by the direct-force translation units (direct_force.hip: one
-// system; direct_batch.hip: many independent systems back to back): the pair arithmetic (interact, interact_block,
+// direct_kernels.h -- what the direct-path translation units share (direct_force.hip: one system; direct_batch.hip: many
+// independent systems back to back; through hermite_kernels.h the three Hermite units): the host helpers of their entry
+// points (ceil_div, misaligned16, launch_status) and the device building blocks: the pair arithmetic (interact, interact_block,
 // energy_pair) and, one level up, the wave bodies that walk the source chunks with it (accel_body, energy_body: target
 // loads, LDS-DMA chunk walk, pair loop, four-wave reduction, store). A force or energy kernel of either unit is a
 // prologue that reads its geometry (from blockIdx and arguments, or from a scene record) and one call of the body: that
@@ -7,6 +8,7 @@
 // The definitions sit in an anonymous namespace: every translation unit that includes this file gets its own inlined copies.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <stdint.h>
 
 #include "../../include/nbd.h"
 
@@ -28,6 +30,12 @@ constexpr int kMaxSlabs = 64;
 constexpr float kEps2Masked = 1e-24f;
 
 inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
+inline bool misaligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; }
+// 0 or the HIP error of the last launch, as the C-ABI returns it
+inline int launch_status() {
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? 0 : (int)e;
+}
 
 // Which sources a launch walks: the 64-source chunks of `src` minus a run of skipped physical chunks,
 // with an element-wise exclusion in the (at most two) chunks that hold a partial piece of the excluded

@@ -1,9 +1,14 @@
-// hermite_kernels.h -- the acceleration-plus-jerk wave body (accel_jerk_body: target loads, LDS-DMA chunk walk, pair
-// loop, four-wave reduction, store) and the corrector arithmetic shared by the Hermite translation units
-// (direct_hermite.hip: all targets, shared timestep; direct_hermite_block.hip: an active list of targets, block
-// timesteps; direct_batch_hermite.hip: many independent systems, shared timestep per system). Their force kernels are a
-// prologue that says which targets, which chunks and which output rows, and one call of the body: that is what keeps a
-// scene of a batch, or a block step at level 0, bit-identical to the shared-timestep kernel.
+// hermite_kernels.h -- everything the Hermite translation units share (direct_hermite.hip: all targets, shared timestep;
+// direct_hermite_block.hip: an active list of targets, block timesteps; direct_batch_hermite.hip: many independent
+// systems, shared timestep per system):
+//   - the acceleration-plus-jerk wave body (accel_jerk_body: target loads, LDS-DMA chunk walk, pair loop, four-wave
+//     reduction, store) and the split of the chunks over the waves (chunk_split on the host, wave_chunk_range in a kernel);
+//   - the O(N) arithmetic: the fp32 step constants (hermite_dt), the predictor (hermite_predict), the fixed-order slab sum
+//     (hermite_slab_sum) and the corrector (hermite_correct);
+//   - the launch plan of a force launch (JerkPlan, plan_jerk).
+// A kernel of one of the units is a prologue that says which targets, which chunks, which rows and which constants, and
+// calls of these: a scene of a batch, or a block step at level 0, is bit-identical to the shared-timestep step because
+// there is one copy of every rounded operation, not because three copies are kept alike.
 // The definitions sit in an anonymous namespace: every translation unit that includes this file gets its own inlined copies.
 #pragma once
 #include "direct_kernels.h"
@@ -161,8 +166,79 @@ __device__ __forceinline__ void accel_jerk_body(const f4* __restrict__ posm, con
   }
 }
 
-// One component of the shared-timestep corrector, each product and sum rounded on its own (the build has
-// -ffp-contract=off): v1 = v + (a0 + a1) dt/2 + (j0 - j1) dt^2/12, x1 = x + (v + v1) dt/2 + (a0 - a1) dt^2/12.
+// The balanced split of n_chunks source chunks over slabs x 4 waves: every wave walks q chunks, the first r waves one more.
+struct ChunkSplit { int q, r; };
+
+inline ChunkSplit chunk_split(int n_chunks, int slabs) {
+  return ChunkSplit{n_chunks / (slabs * kWaves), n_chunks % (slabs * kWaves)};
+}
+
+// the chunks [c_begin, c_end) of wave jw = slab * 4 + wave under that split
+__device__ __forceinline__ void wave_chunk_range(int jw, int q, int r, int& c_begin, int& c_end) {
+  c_begin = jw * q + min(jw, r);
+  c_end = c_begin + q + (jw < r ? 1 : 0);
+}
+
+// The geometry of a force launch: the all-pairs force's plan (nbd_accel_plan) for n_tgt targets under n sources -- same
+// targets, same chunks, the same balance problem.
+struct JerkPlan { int groups, slabs, n_chunks; };
+
+inline JerkPlan plan_jerk(int n, int n_tgt) {
+  JerkPlan p;
+  int cpw = 0;
+  nbd_accel_plan(n, n_tgt, &p.groups, &p.slabs, &cpw);
+  p.n_chunks = ceil_div(n, kChunk);
+  return p;
+}
+
+// fp32 step constants, each formed in double and rounded once. On the device too: a block-timestep body forms them from
+// its own fp64 step, so one whose step is the whole interval gets the shared step's bits.
+struct HermiteDt { float dt, dt_half, dt2_half, dt3_sixth, dt2_twelfth; };
+
+__host__ __device__ inline HermiteDt hermite_dt(double dt) {
+  return HermiteDt{(float)dt, (float)(0.5 * dt), (float)(0.5 * dt * dt), (float)(dt * dt * dt / 6.0),
+                   (float)(dt * dt / 12.0)};
+}
+
+// One component of the predictor, each product and sum rounded on its own (the build has -ffp-contract=off):
+// x_p = x + v dt + a dt^2/2 + j dt^3/6, v_p = v + a dt + j dt^2/2.
+struct PosVel { float x, v; };
+
+__device__ __forceinline__ PosVel hermite_predict(const float x, const float v, const float a, const float j,
+                                                  const float dt, const float dt2_half, const float dt3_sixth) {
+  return PosVel{((x + v * dt) + a * dt2_half) + j * dt3_sixth, (v + a * dt) + j * dt2_half};
+}
+
+// a1 = g * sum of the slabs, j1 likewise, in a fixed order, for a workgroup of 4 waves on 64 consecutive rows of
+// slabs = float[n_slabs][6][stride] (finish_kernel's scheme: wave w sums slabs w, w+4, ... of its lane's row, the four
+// partials combined as (p0 + p1) + (p2 + p3)). Every thread of the workgroup calls it (it holds the barrier) with its
+// row = first row + lane; a row that is not valid reads nothing. part: the workgroup's exchange buffer. True for the
+// one thread per valid row (wave 0) that holds a1, j1.
+__device__ __forceinline__ bool hermite_slab_sum(const float* __restrict__ slabs, int n_slabs, int stride, int row,
+                                                 bool valid, float g, float (*part)[6][64], float* a1, float* j1) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  float sum[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  if (valid)
+    for (int s = w; s < n_slabs; s += 4)
+#pragma unroll
+      for (int k = 0; k < 6; ++k) sum[k] += slabs[((size_t)s * 6 + k) * stride + row];
+#pragma unroll
+  for (int k = 0; k < 6; ++k) part[w][k][lane] = sum[k];
+  __syncthreads();
+  if (w != 0 || !valid) return false;
+  auto total = [&](int k) {
+    return g * ((part[0][k][lane] + part[1][k][lane]) + (part[2][k][lane] + part[3][k][lane]));
+  };
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    a1[k] = total(k);
+    j1[k] = total(k + 3);
+  }
+  return true;
+}
+
+// One component of the corrector, each product and sum rounded on its own:
+// v1 = v + (a0 + a1) dt/2 + (j0 - j1) dt^2/12, x1 = x + (v + v1) dt/2 + (a0 - a1) dt^2/12.
 __device__ __forceinline__ void hermite_correct(float& x, float& v, const float a0, const float j0, const float a1,
                                                 const float j1, const float dt_half, const float dt2_twelfth) {
   const float v1 = (v + (a0 + a1) * dt_half) + (j0 - j1) * dt2_twelfth;
