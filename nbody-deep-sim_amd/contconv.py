@@ -16,16 +16,17 @@ becomes one dense GEMM and the (E, I, O) tensor (34 GB at N = 16 384) is never f
 """
 from __future__ import annotations
 
-import time
-
 import numpy as np
 import torch
 import torch.nn as nn
 
-from gnn import MLP, _WeightCache, ensure_eval, head_chain, run_chain, transform_to_graph  # noqa: F401  (same import as contconv.py:6)
+from gnn import transform_to_graph  # noqa: F401  (same import as contconv.py:6)
+from gnn import (MLP, _WeightCache, decoder_autograd, decoder_linears, ensure_eval, eval_graph_batch, head_chain, model_input,
+                 model_input_of, run_chain)
 from nbd import autograd as ag
 from nbd import graphops, nnops
 from nbd._lib import NbdError
+from nbd.data import Data
 
 
 # Node-chunked bin+contract was measured and rejected: chunks small enough for the Infinity Cache leave
@@ -325,8 +326,7 @@ class ContinuousConvModel(nn.Module):
         if pre is not None:
             x, pos = pre
         else:
-            x = torch.cat((x7[:, :3], x7[:, 6:]), dim=-1) if self.in_channels == 4 else x7
-            x = x.to(torch.float32).contiguous()
+            x = model_input_of(x7, self.in_channels)
             pos = x[:, :3].contiguous()
         c = self.continuous_conv_dim
         enc_dim = self.in_channels if w["enc"] is None else c
@@ -412,7 +412,6 @@ class ContinuousConvModel(nn.Module):
         [pos | mass] is concatenated and the prediction lands in the caller's buffer (three launches fewer per step).
         kick = (vel, c): vel += c * prediction in the decoder kernel's epilogue when the fused head runs; `_kick_done`
         tells the caller whether it did (otherwise the caller kicks)."""
-        from nbd.data import Data
         ensure_eval(self)
         self._kick_done = False
         with torch.no_grad():
@@ -429,7 +428,6 @@ class ContinuousConvModel(nn.Module):
     def predict(self, pos, feat):
         """contconv.py:261-271. (The reference also builds a k=50 kNN graph here that forward() then
         ignores; that dead work is not reproduced.)"""
-        from nbd.data import Data
         ensure_eval(self)
         with torch.no_grad():
             # predict() is the rollout entry point (Trainer.step): consecutive calls see almost the same configuration,
@@ -437,43 +435,29 @@ class ContinuousConvModel(nn.Module):
             # far enough to matter (graphops.RadiusCache; the result is exact either way)
             if getattr(self, "_radius_cache", None) is None:
                 self._radius_cache = graphops.RadiusCache()
-            if (self.in_channels == 4 and pos.dtype == torch.float32 and feat.dtype == torch.float32 and pos.is_cuda
-                    and pos.dim() == 2 and pos.shape[1] == 3 and feat.dim() == 2 and feat.shape[1] >= 4
-                    and not self.training):
-                # the model input is [pos | mass] (contconv.py:219-220): built directly -- the reference's route
-                # (cat to 7 columns, slice, cat again, two contiguous copies) is four more launches per step
-                data = Data(x=pos, batch=None)                      # .x is only consulted for its device and row count
-                data._x_pos = (torch.cat((pos, feat[:, 3:]), dim=-1), pos.contiguous())
-            else:
-                data = Data(x=torch.cat((pos, feat), dim=-1), batch=None)
+            data = self._rollout_data(pos, feat, None)
             data._radius_cache = self._radius_cache if self.use_radius_cache else None
             return self.forward(data)
+
+    def _rollout_data(self, pos, feat, batch):
+        """The Data object predict() / predict_batched() hand to forward()."""
+        if (self.in_channels == 4 and pos.dtype == torch.float32 and feat.dtype == torch.float32 and pos.is_cuda
+                and pos.dim() == 2 and pos.shape[1] == 3 and feat.dim() == 2 and feat.shape[1] >= 4):
+            # the model input is [pos | mass] (contconv.py:219-220): built directly -- the reference's route
+            # (cat to 7 columns, slice, cat again, two contiguous copies) is four more launches per step
+            data = Data(x=pos, batch=batch)                         # .x is only consulted for its device and row count
+            data._x_pos = (model_input(pos, feat, 4, dtype=None), pos.contiguous())
+            return data
+        return Data(x=torch.cat((pos, feat), dim=-1), batch=batch)
 
     def predict_batched(self, pos, feat, batch):
         """predict() for several independent systems at once (Trainer.test_from_dir): `batch` (sorted int64) names every
         body's system; the radius graph stays inside a system (radius_graph(batch=...)). One set of launches for all."""
-        from nbd.data import Data
         ensure_eval(self)
         with torch.no_grad():
-            if (self.in_channels == 4 and pos.dtype == torch.float32 and feat.dtype == torch.float32 and pos.is_cuda
-                    and pos.dim() == 2 and pos.shape[1] == 3 and feat.dim() == 2 and feat.shape[1] >= 4):
-                data = Data(x=pos, batch=batch)
-                data._x_pos = (torch.cat((pos, feat[:, 3:]), dim=-1), pos.contiguous())
-            else:
-                data = Data(x=torch.cat((pos, feat), dim=-1), batch=batch)
-            return self.forward(data)
+            return self.forward(self._rollout_data(pos, feat, batch))
 
-    def eval_graph_batch(self, data):
-        self.eval()
-        with torch.no_grad():
-            torch.cuda.synchronize()
-            start = time.time()
-            acc_pred = self.forward(data)
-            torch.cuda.synchronize()
-            end = time.time()
-            mse_loss = torch.nn.functional.mse_loss(acc_pred, data.y, reduction="mean")
-            loss = torch.sqrt(mse_loss)
-        return loss.item(), mse_loss.item(), end - start
+    eval_graph_batch = eval_graph_batch
 
     # ------------------------------------------------------------------ training (contconv.py:236-247)
     def _encoder_autograd(self, x):
@@ -513,7 +497,7 @@ class ContinuousConvModel(nn.Module):
                 or len({("mean" if l.agg == "mean" else "sum") for l in self.contconv}) != 1
                 or (enc is not None and (len(enc.lins) > _lib.TRAIN_MAX_MLP or (enc.has_norm and not self.training)))):
             return None
-        head = [self.output] if isinstance(self.output, nn.Linear) else [m for m in self.output if isinstance(m, nn.Linear)]
+        head = decoder_linears(self.output)
         if len(head) > _lib.TRAIN_MAX_MLP:
             return None
         params, bns = [], []
@@ -552,8 +536,7 @@ class ContinuousConvModel(nn.Module):
         x7 = data.x
         if not x7.is_cuda:
             raise NbdError("ContinuousConvModel.forward: data must live on the GPU (no CPU path)")
-        x = torch.cat((x7[:, :3], x7[:, 6:]), dim=-1) if self.in_channels == 4 else x7
-        x = x.to(torch.float32).contiguous()
+        x = model_input_of(x7, self.in_channels)
         pos = x[:, :3].contiguous()
         lists = graphops.radius_lists(pos, self.radius, getattr(data, "batch", None), loop=self.self_loops,
                                       max_num_neighbors=self.max_num_neighbors)
@@ -581,14 +564,8 @@ class ContinuousConvModel(nn.Module):
             h = layer(pos, h, lists=lists, act="tanh", graph=graph if layer.agg not in ("max", "min", "mul") else None)
             if self.training and self.continuous_conv_dropout > 0:
                 h = torch.nn.functional.dropout(h, p=self.continuous_conv_dropout, training=True)
-        z = ag.LayerNormFn.apply(torch.cat((enc, h), dim=-1), self.layer_norm.weight, self.layer_norm.bias,
-                                 self.layer_norm.eps)
-        if isinstance(self.output, nn.Linear):
-            return ag.linear(z, self.output.weight, self.output.bias)
-        lins = [m for m in self.output if isinstance(m, nn.Linear)]
-        for i, lin in enumerate(lins):
-            z = ag.linear(z, lin.weight, lin.bias, act="tanh" if i < len(lins) - 1 else None)
-        return z
+        return decoder_autograd(ag.LayerNormFn.apply(torch.cat((enc, h), dim=-1), self.layer_norm.weight, self.layer_norm.bias,
+                                                     self.layer_norm.eps), self.output)
 
     def compute_loss(self, data):
         """contconv.py:236-240."""

@@ -86,13 +86,52 @@ def run_chain(x, chain, out_last=None):
     return x
 
 
+def decoder_linears(output):
+    """The Linears of a decoder, in order: torch Sequential(Linear, Tanh, Linear, ...) or a single Linear."""
+    return [output] if isinstance(output, Linear) else [m for m in output if isinstance(m, Linear)]
+
+
 def head_chain(output):
-    """torch Sequential(Linear, Tanh, Linear, ...) or a single Linear -> [(W, b, act)]."""
-    if isinstance(output, Linear):
-        return [(output.weight.detach().contiguous(), output.bias.detach().contiguous(), None)]
-    lins = [m for m in output if isinstance(m, Linear)]
+    """A decoder (decoder_linears) -> [(W, b, act)], tanh between layers."""
+    lins = decoder_linears(output)
     return [(l.weight.detach().contiguous(), l.bias.detach().contiguous(), "tanh" if i < len(lins) - 1 else None)
             for i, l in enumerate(lins)]
+
+
+def decoder_autograd(z, output):
+    """The LayerNorm output z through a decoder's Linears (tanh between layers) as autograd Functions over the HIP kernels."""
+    lins = decoder_linears(output)
+    for i, lin in enumerate(lins):
+        z = ag.linear(z, lin.weight, lin.bias, act="tanh" if i < len(lins) - 1 else None)
+    return z
+
+
+def model_input(pos, feat, width, dtype=torch.float32):
+    """The model input of the (pos, feat = [vel | mass]) callers: [pos | mass] when the model is `width` = 4 wide
+    (gnn.py:131-132), else [pos | feat]; converted to `dtype` (None: left as concatenated)."""
+    x = torch.cat((pos, feat[:, 3:] if width == 4 else feat), dim=-1)
+    return x if dtype is None else x.to(dtype)
+
+
+def model_input_of(x7, width, contiguous=True):
+    """The fp32 model input of the data.x callers, x7 = [pos | vel | mass]: [pos | mass] at `width` = 4, else x7 itself."""
+    x = (torch.cat((x7[:, :3], x7[:, 6:]), dim=-1) if width == 4 else x7).to(torch.float32)
+    return x.contiguous() if contiguous else x
+
+
+def eval_graph_batch(self, data):
+    """GraphModel's and ContinuousConvModel's method: (rmse, mse, seconds) as gnn.py:193-203; the time brackets forward()
+    with a device sync."""
+    self.eval()
+    with torch.no_grad():
+        torch.cuda.synchronize()
+        start = time.time()
+        acc_pred = self.forward(data)
+        torch.cuda.synchronize()
+        end = time.time()
+        mse_loss = torch.nn.functional.mse_loss(acc_pred, data.y, reduction="mean")
+        loss = torch.sqrt(mse_loss)
+    return loss.item(), mse_loss.item(), end - start
 
 
 class _WeightCache:
@@ -225,8 +264,8 @@ class GraphModel(torch.nn.Module):
         x7 = data.x
         if not x7.is_cuda:
             raise NbdError("GraphModel.forward: data must live on the GPU (no CPU path)")
-        x_in = torch.cat((x7[:, :3], x7[:, 6:]), dim=-1) if self.input_dim == 4 else x7
-        return self._forward_inference(x_in.to(torch.float32), data.edge_index, getattr(data, "_regular_k", None))
+        return self._forward_inference(model_input_of(x7, self.input_dim, contiguous=False), data.edge_index,
+                                       getattr(data, "_regular_k", None))
 
     def _forward_inference(self, x_in, ei, reg, out=None):
         """Inference forward on the model input x_in (n, input_dim) = [pos | mass] or [pos | vel | mass]."""
@@ -478,6 +517,15 @@ class GraphModel(torch.nn.Module):
         graphops.mark(buf, "_nbd_grouped")
         return out
 
+    def _hinted_knn(self, pos, k):
+        """The kNN graph of a rollout's search: the previous call's graph (same n, k) is both the hint and the output
+        buffer -- consecutive configurations are close, and the search result does not depend on the hint."""
+        buf = self._knn_buf
+        if buf is not None and (buf.shape != (2, pos.shape[0] * max(min(k, pos.shape[0] - 1), 0)) or buf.device != pos.device):
+            buf = None
+        self._knn_buf = graphops.knn_graph(pos, k=k, batch=None, loop=False, hint=buf, out=buf)
+        return self._knn_buf
+
     def predict(self, pos, feat, neighbors=None):
         """gnn.py:205-215. The reference never forwards `self.neighbors` here, so the graph uses
         transform_to_graph's default k = 50; `neighbors=` is this build's optional override."""
@@ -486,21 +534,12 @@ class GraphModel(torch.nn.Module):
             k = 50 if neighbors is None else neighbors
             if not pos.is_cuda:
                 raise NbdError("GraphModel.predict: tensors must live on the GPU (no CPU path)")
-            # transform_to_graph + forward without materialising x = [pos | feat] first: the model input is
-            # [pos | mass] (input_dim == 4, gnn.py:131-132) or [pos | feat]
-            # the previous call's graph (same n, k) is both the hint and the output buffer of this search: in a
-            # rollout consecutive configurations are close, and the search result does not depend on the hint
-            kk = max(min(k, pos.shape[0] - 1), 0)
-            x_in = torch.cat((pos, feat[:, 3:]), dim=-1) if self.input_dim == 4 else torch.cat((pos, feat), dim=-1)
-            x_in = x_in.to(torch.float32)
+            # transform_to_graph + forward without materialising x = [pos | feat] first
+            x_in = model_input(pos, feat, self.input_dim)
             pred = self._predict_one_call(x_in, pos.contiguous(), k)       # search + layers in one C-ABI call
             if pred is not None:
                 return pred
-            buf = self._knn_buf
-            if buf is not None and (buf.shape != (2, pos.shape[0] * kk) or buf.device != pos.device):
-                buf = None
-            ei = graphops.knn_graph(pos, k=k, batch=None, loop=False, hint=buf, out=buf)
-            self._knn_buf = ei
+            ei = self._hinted_knn(pos, k)
             # First call of a sequence: the graph just built is the buffer and hint the one-call pass was missing -- take
             # that pass now (one more, hinted, search), so that this call and every later one run the SAME arithmetic
             # (exponential tables or not): predict() on the same input returns the same bits, call after call.
@@ -519,8 +558,7 @@ class GraphModel(torch.nn.Module):
             k = 50 if neighbors is None else neighbors
             if not pos.is_cuda:
                 raise NbdError("GraphModel.predict_batched: tensors must live on the GPU (no CPU path)")
-            x_in = torch.cat((pos, feat[:, 3:]), dim=-1) if self.input_dim == 4 else torch.cat((pos, feat), dim=-1)
-            x_in = x_in.to(torch.float32)
+            x_in = model_input(pos, feat, self.input_dim)
             # the search always writes into a buffer of the layout's size (remembered on `batch`): no per-call read-back of
             # the edge count, safe inside a hipGraph capture; self is masked in the kernel (the rollout's form of the rule)
             _, e = graphops.knn_layout(batch, pos.shape[0], k, False, pos.device)
@@ -554,37 +592,20 @@ class GraphModel(torch.nn.Module):
         general path below, and the caller must then not have relied on it (Trainer checks before capturing)."""
         with torch.no_grad():
             n = pos.shape[0]
-            kk = max(min(k, n - 1), 0)
             adv = None if advance is None else (advance[0], advance[1], posm, advance[2])
             pred = self._predict_one_call(posm[:n], pos, k, out=out, kick=self._kick_hint, advance=adv)
             if pred is not None:
                 return pred
             if advance is not None:
                 raise NbdUnsupported("GraphModel._predict_posm: the pre-advancing step needs the one-call fused path")
-            buf = self._knn_buf
-            if buf is not None and (buf.shape != (2, n * kk) or buf.device != pos.device):
-                buf = None
-            ei = graphops.knn_graph(pos, k=k, batch=None, loop=False, hint=buf, out=buf)
-            self._knn_buf = ei
-            return self._forward_inference(posm[:n], ei, kk, out=out)
+            return self._forward_inference(posm[:n], self._hinted_knn(pos, k), max(min(k, n - 1), 0), out=out)
 
     def predict_graph(self, data):
         self.eval()
         with torch.no_grad():
             return self.forward(data)
 
-    def eval_graph_batch(self, data):
-        """(rmse, mse, seconds) as gnn.py:193-203; the time brackets forward() with a device sync."""
-        self.eval()
-        with torch.no_grad():
-            torch.cuda.synchronize()
-            start = time.time()
-            acc_pred = self.forward(data)
-            torch.cuda.synchronize()
-            end = time.time()
-            mse_loss = torch.nn.functional.mse_loss(acc_pred, data.y, reduction="mean")
-            loss = torch.sqrt(mse_loss)
-        return loss.item(), mse_loss.item(), end - start
+    eval_graph_batch = eval_graph_batch
 
     # ------------------------------------------------------------------ training (gnn.py:150-191)
     def _graph_lists(self, data, n):
@@ -615,7 +636,7 @@ class GraphModel(torch.nn.Module):
                 or (enc is not None and (enc.has_norm or (self.training and enc.dropout > 0) or len(enc.lins) > _lib.TRAIN_MAX_MLP))
                 or len(self.gnns) > _lib.GNN_MAX_LAYERS):
             return None
-        head = [self.output] if isinstance(self.output, Linear) else [m for m in self.output if isinstance(m, Linear)]
+        head = decoder_linears(self.output)
         if len(head) > _lib.TRAIN_MAX_MLP:
             return None
         params = []
@@ -640,8 +661,7 @@ class GraphModel(torch.nn.Module):
         if not x7.is_cuda:
             raise NbdError("GraphModel.forward: data must live on the GPU (no CPU path)")
         n, h = x7.shape[0], self.gnn_dim
-        x_in = torch.cat((x7[:, :3], x7[:, 6:]), dim=-1) if self.input_dim == 4 else x7
-        x_in = x_in.to(torch.float32).contiguous()
+        x_in = model_input_of(x7, self.input_dim)
         lists = self._graph_lists(data, n)
         one = self._one_call_train(x_in, lists)
         if one is not None:
@@ -673,13 +693,8 @@ class GraphModel(torch.nn.Module):
                 s = ag.EdgeAggregateFn.apply(pq, lists, h, "mean" if self.aggr == "mean" else "sum")
                 x = ag.linear(s, g.nn[2].weight, g.nn[2].bias, bias_rowscale=brs)
         z = torch.cat((enc, x), dim=-1)
-        z = ag.LayerNormFn.apply(z, self.layer_norm.weight, self.layer_norm.bias, self.layer_norm.eps)
-        if isinstance(self.output, Linear):
-            return ag.linear(z, self.output.weight, self.output.bias)
-        lins = [m for m in self.output if isinstance(m, Linear)]
-        for i, lin in enumerate(lins):
-            z = ag.linear(z, lin.weight, lin.bias, act="tanh" if i < len(lins) - 1 else None)
-        return z
+        return decoder_autograd(ag.LayerNormFn.apply(z, self.layer_norm.weight, self.layer_norm.bias, self.layer_norm.eps),
+                                self.output)
 
     def compute_loss(self, data):
         """gnn.py:150-161: (RMSE of the scaled accelerations, plain MSE)."""

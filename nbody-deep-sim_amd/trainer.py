@@ -8,6 +8,10 @@ Differences that do not change outputs: the leapfrog updates run in the HIP kick
 the 18 N `.item()` host syncs per rollout step (trainer.py:286-312) are replaced by one bulk
 device->host copy per rollout; step_time is measured with HIP events (the reference's
 un-synchronised time.time() would time kernel launches only).
+
+One leapfrog step (`_leapfrog`, in place: `step` runs it on clones, `_capture_step` captures it on static buffers) and
+one rollout engine (`_rollout`): `evaluate_rollout` hands it one scene and the model's own predict,
+`evaluate_rollout_scenes` all scenes of a file and the model's predict_batched bound to their batch.
 """
 from __future__ import annotations
 
@@ -20,7 +24,7 @@ import pandas as pd
 import torch
 
 from datautils import get_dataloader
-from nbd import direct
+from nbd import direct, graphops
 from nbd._lib import NbdUnsupported
 
 ROLLOUT_COLUMNS = ["filename", "scene", "step", "x", "y", "z", "vx", "vy", "vz", "ax", "ay", "az",
@@ -93,18 +97,68 @@ class Trainer:
         return epoch_losses, epoch_mse_losses
 
     # ------------------------------------------------------------------ trainer.py:217-226
-    def step(self, pos, vel, m, acc, dt, predict=None):
-        """Leapfrog with model-predicted accelerations; functional (returns new tensors). predict: the function standing
-        in for self.model.predict (the scenes-together rollout passes the model's predict_batched bound to its batch)."""
+    def _leapfrog(self, pos, vel, m, acc, dt, predict=None, packed=None, pre=None, out=None):
+        """THE leapfrog step with model-predicted accelerations, IN PLACE on pos / vel: kick-drift, prediction, the second
+        half-kick unless the model's epilogue did it, and -- with `out`, the caller's acceleration buffer -- the copy-back when
+        the model returned a buffer of its own. Returns the new accelerations. predict: the function standing in for
+        self.model.predict (the scenes-together rollout passes the model's predict_batched bound to its batch).
+        packed = (posm, m_flat): the model reads the packed {x,y,z,m} rows the kick-drift kernel writes anyway, no
+        concatenations. pre = (vel_half, pos_pre), with packed: the model's last layer does the leapfrog bookkeeping in its
+        epilogue -- this step's velocity and position out, the next step's half-kick and drift in -- so the step is the
+        search and the layers only (GraphModel, H = 64: include/nbd.h nbd_gnn_layer_args.adv_*)."""
         half, full = direct.f32(0.5 * dt), direct.f32(dt)
+        if pre is not None:
+            o_acc = self.model._predict_posm(packed[0], pre[1], out=out, kick=(vel, half), advance=(pre[0], pos, full))
+            if not self.model._advance_done:
+                raise RuntimeError("pre-advancing step fell off the one-call path during capture")
+            kicked = True                                                          # an epilogue that advances has kicked
+        elif packed is not None:
+            direct.kick_drift(pos, vel, acc, packed[1], half, full, posm=packed[0])
+            # the second half-kick rides in the last layer's epilogue when the model's fused path allows it
+            o_acc = self.model._predict_posm(packed[0], pos, out=out, kick=(vel, half))    # acc is consumed by kick_drift above
+            kicked = getattr(self.model, "_kick_done", False)
+        else:
+            direct.kick_drift(pos, vel, acc, None, half, full)                     # vel += .5dt acc ; pos += dt vel
+            o_acc = (predict or self.model.predict)(pos, torch.cat([vel, m], dim=-1))
+            kicked = False
+        if not kicked:
+            direct.kick(vel, o_acc, half)                                          # vel += .5dt o_acc
+        if out is None:
+            return o_acc
+        if o_acc.data_ptr() != out.data_ptr():
+            out.copy_(o_acc)
+        return out
+
+    def step(self, pos, vel, m, acc, dt, predict=None):
+        """Leapfrog with model-predicted accelerations; functional (returns new tensors): _leapfrog on clones."""
         pos_, vel_ = pos.contiguous().clone(), vel.contiguous().clone()
-        direct.kick_drift(pos_, vel_, acc.contiguous(), None, half, full)          # vel_ = vel + .5dt acc ; pos_ = pos + dt vel_
-        acc_ = (predict or self.model.predict)(pos_, torch.cat([vel_, m], dim=-1))
-        direct.kick(vel_, acc_, half)                                              # vel_ += .5dt acc_
-        return pos_, vel_, acc_
+        return pos_, vel_, self._leapfrog(pos_, vel_, m, acc.contiguous(), dt, predict)
+
+    def _probe_pre_advance(self, s_pos, s_vel, s_acc, m, packed, dt):
+        """Can the captured step take the pre-advancing form of _leapfrog? Takes the first half-step here, once, by the usual
+        kernel, and runs one un-captured step: (vel_half, pos_pre) when this model / shape takes the one-call path with the
+        epilogue, else None. Only the dedicated refusal (NbdUnsupported) means "no": any other failure is a real one and
+        goes to the caller's handler."""
+        half, full = direct.f32(0.5 * dt), direct.f32(dt)
+        posm, m_flat = packed
+        vel_half, pos_pre = s_vel.clone(), s_pos.clone()
+        direct.kick_drift(pos_pre, vel_half, s_acc, m_flat, half, full, posm=posm)
+        try:
+            t_pos, t_vel, t_acc, t_vh, t_pp, t_pm = (t.clone() for t in (s_pos, s_vel, s_acc, vel_half, pos_pre, posm))
+            self.model._predict_posm(t_pm, t_pp, out=t_acc, kick=(t_vel, half), advance=(t_vh, t_pos, full))
+            if self.model._advance_done:
+                # ... and the probe's step must BE step(): same position, velocity and acceleration (bit for bit: the
+                # epilogue rounds as the separate kernels do)
+                e_pos, e_vel, e_acc = self.step(s_pos, s_vel, m, s_acc, dt)
+                if not (torch.equal(e_pos, t_pos) and torch.equal(e_vel, t_vel) and torch.equal(e_acc, t_acc)):
+                    raise RuntimeError("the pre-advancing step does not reproduce Trainer.step()")
+                return vel_half, pos_pre
+        except NbdUnsupported:
+            pass
+        return None
 
     def _capture_step(self, pos, vel, m, acc, dt, predict=None):
-        """Capture self.step() on static buffers into a hipGraph; returns a callable that advances the
+        """Capture _leapfrog() on static buffers into a hipGraph; returns a callable that advances the
         static state by one step per call and hands back (pos, vel, acc) copies, or None if capture is
         not possible (then the eager path is used). Same kernels, same arithmetic, fewer launch gaps."""
         try:
@@ -116,57 +170,21 @@ class Trainer:
                     self.step(s_pos, s_vel, m, s_acc, dt, predict)
             torch.cuda.current_stream().wait_stream(side)
             graph = torch.cuda.CUDAGraph()
-            half, full = direct.f32(0.5 * dt), direct.f32(dt)
-            # a model whose input is [pos | mass] (GraphModel, input_dim 4) can read the packed {x,y,z,m} rows the
-            # kick-drift kernel writes anyway: no concatenations in the captured step
-            packed = (predict is None and hasattr(self.model, "_predict_posm") and getattr(self.model, "input_dim", 0) == 4
-                      and m.dim() == 2 and m.shape[1] == 1 and m.dtype == torch.float32)
             keep = [m]                 # every buffer the captured kernels touch must outlive the graph
-            if packed:
-                posm = torch.zeros((direct.padded_len(s_pos.shape[0]), 4), dtype=torch.float32, device=s_pos.device)
-                m_flat = m.reshape(-1).contiguous()
-                keep += [posm, m_flat]
-            # Pre-advancing form (GraphModel, H = 64: include/nbd.h nbd_gnn_layer_args.adv_*): the last layer's epilogue does
-            # the leapfrog bookkeeping -- this step's velocity and position out, the next step's half-kick and drift in --
-            # so a replay is the search and the layers only. The first half-step is taken here, once, by the usual kernel.
-            pre = None
-            if packed and self.pre_advance and getattr(self.model, "supports_pre_advance", False):
-                vel_half, pos_pre = s_vel.clone(), s_pos.clone()
-                direct.kick_drift(pos_pre, vel_half, s_acc, m_flat, half, full, posm=posm)
-                # one un-captured step: does this model / shape take the one-call path with the epilogue? Only the dedicated
-                # refusal (NbdUnsupported) means "no": any other failure is a real one and goes to the handler below.
-                try:
-                    t_pos, t_vel, t_acc, t_vh, t_pp, t_pm = (t.clone() for t in (s_pos, s_vel, s_acc, vel_half, pos_pre, posm))
-                    self.model._predict_posm(t_pm, t_pp, out=t_acc, kick=(t_vel, half), advance=(t_vh, t_pos, full))
-                    if self.model._advance_done:
-                        # ... and the probe's step must BE step(): same position, velocity and acceleration (bit for bit:
-                        # the epilogue rounds as the separate kernels do)
-                        e_pos, e_vel, e_acc = self.step(s_pos, s_vel, m, s_acc, dt)
-                        if not (torch.equal(e_pos, t_pos) and torch.equal(e_vel, t_vel) and torch.equal(e_acc, t_acc)):
-                            raise RuntimeError("the pre-advancing step does not reproduce Trainer.step()")
-                        pre = (vel_half, pos_pre)
-                        keep += [vel_half, pos_pre]
-                except NbdUnsupported:
-                    pre = None
+            # a model whose input is [pos | mass] (GraphModel, input_dim 4) takes _leapfrog's packed form
+            packed = pre = None
+            if (predict is None and hasattr(self.model, "_predict_posm") and getattr(self.model, "input_dim", 0) == 4
+                    and m.dim() == 2 and m.shape[1] == 1 and m.dtype == torch.float32):
+                packed = (torch.zeros((direct.padded_len(s_pos.shape[0]), 4), dtype=torch.float32, device=s_pos.device),
+                          m.reshape(-1).contiguous())
+                keep += packed
+                if self.pre_advance and getattr(self.model, "supports_pre_advance", False):
+                    pre = self._probe_pre_advance(s_pos, s_vel, s_acc, m, packed, dt)
+                    keep += pre or ()
             with torch.cuda.graph(graph):
-                # step() on the static state IN PLACE (same kernels and arithmetic; the functional clones and
-                # copy-backs of step() would be five more launches per replay)
-                if pre is not None:
-                    o_acc = self.model._predict_posm(posm, pre[1], out=s_acc, kick=(s_vel, half), advance=(pre[0], s_pos, full))
-                    if not self.model._advance_done:
-                        raise RuntimeError("pre-advancing step fell off the one-call path during capture")
-                elif packed:
-                    direct.kick_drift(s_pos, s_vel, s_acc, m_flat, half, full, posm=posm)
-                    # the second half-kick rides in the last layer's epilogue when the model's fused path allows it
-                    o_acc = self.model._predict_posm(posm, s_pos, out=s_acc, kick=(s_vel, half))   # s_acc is consumed by kick_drift above
-                    if not getattr(self.model, "_kick_done", False):
-                        direct.kick(s_vel, o_acc, half)
-                else:
-                    direct.kick_drift(s_pos, s_vel, s_acc, None, half, full)
-                    o_acc = (predict or self.model.predict)(s_pos, torch.cat([s_vel, m], dim=-1))
-                    direct.kick(s_vel, o_acc, half)
-                if o_acc.data_ptr() != s_acc.data_ptr():
-                    s_acc.copy_(o_acc)
+                # IN PLACE on the static state (the functional clones and copy-backs of step() would be five more
+                # launches per replay)
+                self._leapfrog(s_pos, s_vel, m, s_acc, dt, predict, packed, pre, out=s_acc)
         except Exception as exc:                          # pragma: no cover - depends on runtime support
             import warnings
             warnings.warn(f"hipGraph capture of the rollout step failed ({exc}); using eager launches")
@@ -174,11 +192,11 @@ class Trainer:
             self.last_capture = None
             return None
 
-        self.last_capture = "pre_advance" if pre is not None else ("packed" if packed else "generic")
+        self.last_capture = "pre_advance" if pre is not None else ("packed" if packed is not None else "generic")
 
         def advance(clone=True):
             """One captured step. clone=False hands back the graph's own state buffers: valid only until
-            the next call (evaluate_rollout copies them into its table right away). The buffers are outputs: in the
+            the next call (_rollout copies them into its table right away). The buffers are outputs: in the
             pre-advancing form the next step starts from the graph's own pre-advanced copy, not from what they hold."""
             graph.replay()
             return (s_pos.clone(), s_vel.clone(), s_acc.clone()) if clone else (s_pos, s_vel, s_acc)
@@ -219,21 +237,23 @@ class Trainer:
         df_new["step_time"] = np.repeat(times, n)
         return df_new[ROLLOUT_COLUMNS]
 
-    def evaluate_rollout_scenes(self, filename, datas, sim_steps, dt, df):
-        """evaluate_rollout for ALL scenes of a file advanced TOGETHER as one batched system (trainer.py:171-175 runs them
-        one after another: at the reference's sizes -- 3 .. 500 bodies -- a step is pure launch latency, the same few
-        launches whether they carry one scene or six). Needs model.predict_batched(pos, feat, batch) (GraphModel,
-        ContinuousConvModel): neighbours are searched inside a scene only. Rows come out exactly as the per-scene calls
-        would append them (scene-major); `step_time` = the batched step's time / number of scenes."""
-        ins = [self._rollout_inputs(d, sim_steps) for d in datas]
-        sizes = [g.shape[1] for g, *_ in ins]
-        pos, vel, m = (torch.cat([x[k] for x in ins]).contiguous() for k in (1, 2, 3))
-        feats = torch.cat([x[4] for x in ins])
-        batch = torch.repeat_interleave(torch.arange(len(ins), device=pos.device), torch.tensor(sizes, device=pos.device))
-        from nbd import graphops
-        graphops.mark(batch, "_nbd_sorted")
-        predict = lambda p_, f_: self.model.predict_batched(p_, f_, batch)     # noqa: E731
-        n_all = pos.shape[0]
+    @staticmethod
+    def _scene_frames(filename, scenes, sizes, table, times):
+        """One frame per scene, scene-major, from the host table (steps, sum(sizes), 18) of scenes laid side by side
+        along the body axis."""
+        frames, lo = [], 0
+        for scene, n in zip(scenes, sizes):
+            frames.append(Trainer._rollout_frame(filename, scene, table[:, lo:lo + n], times, table.shape[0], n))
+            lo += n
+        return frames
+
+    def _rollout(self, filename, scenes, ins, sim_steps, dt, df, predict=None):
+        """THE rollout engine: the scenes `scenes` (ids) with inputs `ins` (_rollout_inputs of each) advance as one system
+        through `predict` (None: the model's own predict, and _capture_step's packed / pre-advancing forms); `step_time` =
+        the step's event time / number of scenes advanced together. Rows are appended to `df` scene-major."""
+        def join(k, dim=0):                    # the scenes' k-th input side by side; one scene: the tensor itself, no copy
+            return ins[0][k] if len(ins) == 1 else torch.cat([x[k] for x in ins], dim=dim).contiguous()
+        gt, pos, vel, m, feats = join(0, dim=1), join(1), join(2), join(3), join(4)
 
         def timed(fn):
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -241,9 +261,11 @@ class Trainer:
             out = fn()
             e1.record()
             return out, (e0, e1)
-        acc, ev = timed(lambda: predict(pos, feats[:, 3:].contiguous()))
+
+        acc, ev = timed(lambda: (predict or self.model.predict)(pos, feats[:, 3:].contiguous()))
         events = [ev]
-        pred = torch.empty((sim_steps, n_all, 9), dtype=torch.float32, device=pos.device)
+        # per step [pred_pos pred_vel pred_acc] (n, 9), written into one preallocated device table
+        pred = torch.empty((sim_steps, pos.shape[0], 9), dtype=gt.dtype, device=gt.device)
         torch.cat([pos, vel, acc], dim=1, out=pred[0])
         graphed = (self._capture_step(pos, vel, m, acc, dt, predict=predict)
                    if (self.use_hip_graph and sim_steps >= self.hip_graph_min_steps) else None)
@@ -257,54 +279,32 @@ class Trainer:
             events.append(ev)
             torch.cat([pos, vel, acc], dim=1, out=pred[step])
         torch.cuda.synchronize()
-        self.last_rollout_timing = {"steps": sim_steps - 1, "loop_wall_s": time.perf_counter() - t_loop,
-                                    "captured": graphed is not None, "scenes_together": len(ins), "bodies": n_all}
-        times = np.array([a.elapsed_time(b) * 1e-3 for a, b in events]) / len(ins)
-        pred_h = pred.cpu().numpy().astype(np.float64)
-        frames, lo = [], 0
-        for scene, ((gt, *_), n) in enumerate(zip(ins, sizes)):
-            table = np.concatenate([gt.cpu().numpy().astype(np.float64), pred_h[:, lo:lo + n]], axis=2)
-            frames.append(self._rollout_frame(filename, scene, table, times, sim_steps, n))
-            lo += n
-        if df is not None and len(df):
-            frames.insert(0, df)
-        return pd.concat(frames, ignore_index=True)
-
-    def evaluate_rollout(self, filename, data, scene, sim_steps, dt, df):
-        gt, pos, vel, m, feats = self._rollout_inputs(data, sim_steps)
-        n = gt.shape[1]
-
-        def timed(fn):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            out = fn()
-            e1.record()
-            return out, (e0, e1)
-
-        pred_accs, ev = timed(lambda: self.model.predict(pos, feats[:, 3:].contiguous()))
-        events = [ev]
-        # per step [pred_pos pred_vel pred_acc] (n, 9), written into one preallocated device table
-        pred = torch.empty((sim_steps, n, 9), dtype=gt.dtype, device=gt.device)
-        torch.cat([pos, vel, pred_accs], dim=1, out=pred[0])
-        graphed = self._capture_step(pos, vel, m, pred_accs, dt) if (self.use_hip_graph and sim_steps >= self.hip_graph_min_steps) else None
-        torch.cuda.synchronize()
-        t_loop = time.perf_counter()
-        for step in range(1, sim_steps):
-            if graphed is not None:
-                (pos, vel, pred_accs), ev = timed(lambda: graphed(clone=False))
-            else:
-                (pos, vel, pred_accs), ev = timed(lambda: self.step(pos, vel, m, pred_accs, dt))
-            events.append(ev)
-            torch.cat([pos, vel, pred_accs], dim=1, out=pred[step])
-        torch.cuda.synchronize()
         # wall time of the stepping loop alone (launches + GPU, no table building): how far the harness is from the
         # captured step's own GPU time
         self.last_rollout_timing = {"steps": sim_steps - 1, "loop_wall_s": time.perf_counter() - t_loop,
-                                    "captured": graphed is not None}
+                                    "captured": graphed is not None, "scenes_together": len(ins), "bodies": pos.shape[0]}
+        times = np.array([a.elapsed_time(b) * 1e-3 for a, b in events]) / len(ins)
         table = torch.cat([gt, pred], dim=2).cpu().numpy().astype(np.float64)      # ONE device->host copy
-        times = np.array([a.elapsed_time(b) * 1e-3 for a, b in events])
-        df_new = self._rollout_frame(filename, scene, table, times, sim_steps, n)
-        return df_new if df is None or len(df) == 0 else pd.concat([df, df_new], ignore_index=True)
+        frames = self._scene_frames(filename, scenes, [x[0].shape[1] for x in ins], table, times)
+        if df is not None and len(df):
+            frames.insert(0, df)
+        return frames[0] if len(frames) == 1 else pd.concat(frames, ignore_index=True)
+
+    def evaluate_rollout_scenes(self, filename, datas, sim_steps, dt, df):
+        """evaluate_rollout for ALL scenes of a file advanced TOGETHER as one batched system (trainer.py:171-175 runs them
+        one after another: at the reference's sizes -- 3 .. 500 bodies -- a step is pure launch latency, the same few
+        launches whether they carry one scene or six). Needs model.predict_batched(pos, feat, batch) (GraphModel,
+        ContinuousConvModel): neighbours are searched inside a scene only. Rows come out exactly as the per-scene calls
+        would append them (scene-major); `step_time` = the batched step's time / number of scenes."""
+        ins = [self._rollout_inputs(d, sim_steps) for d in datas]
+        dev = ins[0][1].device
+        batch = torch.repeat_interleave(torch.arange(len(ins), device=dev), torch.tensor([x[0].shape[1] for x in ins], device=dev))
+        graphops.mark(batch, "_nbd_sorted")
+        return self._rollout(filename, range(len(ins)), ins, sim_steps, dt, df,
+                             predict=lambda p_, f_: self.model.predict_batched(p_, f_, batch))
+
+    def evaluate_rollout(self, filename, data, scene, sim_steps, dt, df):
+        return self._rollout(filename, [scene], [self._rollout_inputs(data, sim_steps)], sim_steps, dt, df)
 
     # ------------------------------------------------------------------ trainer.py:202-215
     def evaluate_stepwise(self, filename, loader, df):
