@@ -190,6 +190,27 @@ size_t nbd_energy_workspace_bytes(int n);
 int nbd_energy_f32(const float* posm, const float* vel, int n, float softening, float g_const,
                    double* out_uk, void* workspace, size_t workspace_bytes, nbd_stream_t stream);
 
+/* ---------------------------------------------- consistent-potential diagnostics (csrc/direct_diag.hip)
+ * An extension (the reference has nbd_energy_f32's convention only). The force above is the gradient of the Plummer
+ * potential, not of -G m_i m_j / (|r| + softening): the energy an exact integrator conserves is K + 1/2 sum m_i phi_i with
+ *   phi[i] = -g_const * sum_{j != i} m_j (|r_j - r_i|^2 + softening_sq)^(-1/2),
+ * the pair with global index j == tgt_global_offset + i excluded by index. Arguments as nbd_accel_f32 (rectangular:
+ * sources, targets, the targets' offset in the source numbering); phi_out: double[n_tgt]. The pair term is fp32 (exact
+ * differences, fma, v_rsq_f32); no fp32 sum runs past one 64-source chunk, everything above it and the factor -g_const
+ * are fp64, in a fixed order: bit-identical run to run. Coincident distinct bodies with softening_sq = 0 give -inf.
+ * Workspace: nbd_potential_workspace_bytes(n_src, n_tgt), 8-byte aligned. n_src = 0 gives zeros. */
+size_t nbd_potential_workspace_bytes(int n_src, int n_tgt);
+int nbd_potential_f32(const float* posm_src, int n_src, const float* posm_tgt, int n_tgt, int tgt_global_offset,
+                      float softening_sq, float g_const, double* phi_out, void* workspace, size_t workspace_bytes,
+                      nbd_stream_t stream);
+/* The conserved quantities of the n bodies of posm (packed {x,y,z,m}), vel (n,3) and phi (double[n], as above):
+ * out_row = device double[16] = {M, Cx, Cy, Cz, Px, Py, Pz, Lx, Ly, Lz, K, U, E, Q, 0, 0} with M = sum m,
+ * C = sum m x / M, P = sum m v, L = sum m x cross v, K = sum 1/2 m |v|^2, U = 1/2 sum m phi, E = K + U, Q = -2 K / U
+ * (C = 0 when M = 0, Q = 0 when U = 0). Every product is formed in fp64 from the fp32 state and summed in a fixed order;
+ * K therefore differs from nbd_energy_f32's (fp32 products) in the last digits. n = 0 gives a row of zeros. */
+int nbd_invariants_f64(const float* posm, const float* vel, const double* phi, int n, double* out_row,
+                       nbd_stream_t stream);
+
 /* ---------------------------------------------------------------- batched direct integrator
  * An ensemble of S >= 1 independent systems ("scenes") in one set of arrays: scene s owns bodies
  * [offsets[s], offsets[s + 1]) of pos / vel / acc (n,3) and mass (n,); offsets is a HOST int array of S + 1 entries,
@@ -233,6 +254,16 @@ int nbd_batch_euler_step_f32(const int* offsets, int n_scenes, const void* plan,
 int nbd_batch_energies(const int* offsets, int n_scenes, const void* plan, size_t plan_bytes, const float* posm,
                        const float* vel, const float* softening, const float* g_const, double* out_uk, void* workspace,
                        size_t workspace_bytes, nbd_stream_t stream);
+/* nbd_potential_f32 per scene (csrc/direct_diag.hip) from posm as packed by the entries above: phi_out is a device
+ * double[N_total] in body order, scene s with its softening_sq[s] and g_const[s]. A scene's values are bit-identical to
+ * nbd_potential_f32 on that scene alone. Workspace: the one nbd_batch_plan reports is large enough (8-byte aligned). */
+int nbd_batch_potential_f32(const int* offsets, int n_scenes, const void* plan, size_t plan_bytes, const float* posm,
+                            const float* softening_sq, const float* g_const, double* phi_out, void* workspace,
+                            size_t workspace_bytes, nbd_stream_t stream);
+/* nbd_invariants_f64 per scene: out_rows is a device double[S][16]; a zero-body scene gives a row of zeros. A scene's
+ * row is bit-identical to nbd_invariants_f64 on that scene alone. */
+int nbd_batch_invariants_f64(const int* offsets, int n_scenes, const void* plan, size_t plan_bytes, const float* posm,
+                             const float* vel, const double* phi, double* out_rows, nbd_stream_t stream);
 
 /* Hermite per scene (csrc/direct_batch_hermite.hip): the scheme of nbd_hermite_step_f32 below applied to every scene,
  * three launches for all scenes, on the plan above. A scene's pos / vel / acc / jerk are bit-identical to

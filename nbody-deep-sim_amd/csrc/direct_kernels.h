@@ -1,7 +1,8 @@
 // direct_kernels.h -- what the direct-path translation units share (direct_force.hip: one system; direct_batch.hip: many
-// independent systems back to back; through hermite_kernels.h the three Hermite units): the host helpers of their entry
+// independent systems back to back; direct_diag.hip: the diagnostics of both; through hermite_kernels.h the three Hermite
+// units): the host helpers of their entry
 // points (ceil_div, misaligned16, launch_status) and the device building blocks: the pair arithmetic (interact, interact_block,
-// energy_pair) and, one level up, the wave bodies that walk the source chunks with it (accel_body, energy_body: target
+// energy_pair, potential_pair) and, one level up, the wave bodies that walk the source chunks with it (accel_body, energy_body, potential_body: target
 // loads, LDS-DMA chunk walk, pair loop, four-wave reduction, store). A force or energy kernel of either unit is a
 // prologue that reads its geometry (from blockIdx and arguments, or from a scene record) and one call of the body: that
 // is what keeps a scene of a batch bit-identical to the same system run alone.
@@ -287,6 +288,90 @@ __device__ __forceinline__ void energy_body(const f4* __restrict__ posm, int n, 
   if (lane == 0) red[wave] = acc;
   __syncthreads();
   if (threadIdx.x == 0) *dst = (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+// ---- per-body potential of the softening the FORCE uses (csrc/direct_diag.hip): u_i = sum_{j != i} m_j (|r_ij|^2 + eps^2)^(-1/2),
+// the sum whose gradient interact() evaluates (energy_pair above is the reference's |r| + eps instead). One source
+// against the lane's two targets: exact fp32 differences, fma for r^2 + eps^2, v_rsq_f32, fma with m_j -- 5 packed ops
+// + 2 v_rsq_f32. MASKED drops j == i and the padding by index (the i == j term is m_i / eps, not 0, so it can never be
+// left to the arithmetic); un-masked, a padding entry (m = 0) adds 0 exactly as long as eps^2 >= kEps2Masked keeps s
+// finite. Coincident distinct bodies at eps = 0 give +inf here (phi = -inf).
+template <bool MASKED>
+__device__ __forceinline__ void potential_pair(const f4 p, const f2 xi, const f2 yi, const f2 zi, const f2 e2, f2& u,
+                                               int j, int i0, int i1, int n_src) {
+  const f2 dx = f2{p.x, p.x} - xi, dy = f2{p.y, p.y} - yi, dz = f2{p.z, p.z} - zi;
+  f2 r2 = __builtin_elementwise_fma(dx, dx, e2);
+  r2 = __builtin_elementwise_fma(dy, dy, r2);
+  r2 = __builtin_elementwise_fma(dz, dz, r2);
+  f2 s = {__builtin_amdgcn_rsqf(r2.x), __builtin_amdgcn_rsqf(r2.y)};
+  if (MASKED) {
+    s.x = (j < n_src && j != i0) ? s.x : 0.0f;
+    s.y = (j < n_src && j != i1) ? s.y : 0.0f;
+  }
+  u = __builtin_elementwise_fma(f2{p.w, p.w}, s, u);      // plain C consumer of v_rsq_f32 (see interact())
+}
+
+// The wave body of the potential kernels. Geometry as accel_body: 4 waves on the 128 targets tgt[t_base ..] (global index
+// tgt_off + row), wave jw = slab * 4 + w walks the chunks [jw*q + min(jw, r), ... + q (+1 if jw < r)) of the n_chunks
+// source chunks, q = n_chunks / (slabs * 4), r the remainder, each chunk through the double-buffered LDS-DMA stage. The
+// chunks that hold one of the group's own indices take the masked pair (every chunk when all_masked: eps^2 < kEps2Masked).
+// Precision: an fp32 sum never runs past one chunk (64 terms of one sign); the chunk sums are added in fp64, in chunk
+// order, then the four waves as (w0 + w1) + (w2 + w3) through LDS. dst[row] = this slab's fp64 partial for the valid
+// rows of the group (no G, no sign: the finishing pass adds the slabs in slab order). lds: the workgroup's f4[kPotLdsF4].
+constexpr int kPotLdsF4 = kWaves * 2 * kChunk + kWaves * 2 * 64 / 2;
+
+__device__ __forceinline__ void potential_body(const f4* __restrict__ src, int n_src, int n_chunks, int slabs,
+                                               const bool all_masked, const f4* __restrict__ tgt, int n_tgt, int tgt_off,
+                                               int t_base, int slab, float eps2, f4* lds, double* __restrict__ dst) {
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int i0 = t_base + lane, i1 = t_base + 64 + lane;
+  const f4 t0 = tgt[min(i0, n_tgt - 1)], t1 = tgt[min(i1, n_tgt - 1)];
+  const f2 xi = {t0.x, t1.x}, yi = {t0.y, t1.y}, zi = {t0.z, t1.z};
+  f2 e2 = {eps2, eps2};
+  asm volatile("" : "+v"(e2));  // keep eps^2 in VGPRs: an SGPR operand halves v_pk_fma issue
+  double phi0 = 0.0, phi1 = 0.0;
+
+  const int parts = slabs * kWaves, cpw_q = n_chunks / parts, cpw_r = n_chunks % parts;
+  const int jw = slab * kWaves + wave;
+  const int c_begin = jw * cpw_q + min(jw, cpw_r), c_end = c_begin + cpw_q + (jw < cpw_r ? 1 : 0);
+  const int g_lo = tgt_off + t_base, g_hi = g_lo + kTgtPerWG;      // the group's own source indices
+  f4* stage = &lds[wave * 2 * kChunk];
+  const f4* s_lane = src + lane;
+  if (c_begin < c_end)
+    __builtin_amdgcn_global_load_lds(GPTR(s_lane + (size_t)c_begin * kChunk), LPTR(stage), 16, 0, 0);
+  for (int c = c_begin; c < c_end; ++c) {
+    const int b = (c - c_begin) & 1;
+    if (c + 1 < c_end) {
+      __builtin_amdgcn_global_load_lds(GPTR(s_lane + (size_t)(c + 1) * kChunk), LPTR(stage + (b ^ 1) * kChunk), 16, 0, 0);
+      asm volatile("s_waitcnt vmcnt(1)" ::: "memory");  // chunk c has landed, c+1 in flight
+    } else {
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
+    const f4* buf = stage + b * kChunk;
+    const int j0 = c * kChunk;
+    f2 u = {0.f, 0.f};
+    if (all_masked || (j0 < g_hi && j0 + kChunk > g_lo)) {
+#pragma unroll 4
+      for (int j = 0; j < kChunk; ++j)
+        potential_pair<true>(buf[j], xi, yi, zi, e2, u, j0 + j, tgt_off + i0, tgt_off + i1, n_src);
+    } else {
+#pragma unroll 8
+      for (int j = 0; j < kChunk; ++j) potential_pair<false>(buf[j], xi, yi, zi, e2, u, j0 + j, 0, 0, n_src);
+    }
+    phi0 += (double)u.x;
+    phi1 += (double)u.y;
+  }
+
+  double* red = reinterpret_cast<double*>(&lds[kWaves * 2 * kChunk]);  // [wave][half][64]
+  red[(wave * 2 + 0) * 64 + lane] = phi0;
+  red[(wave * 2 + 1) * 64 + lane] = phi1;
+  __syncthreads();
+  const int n_valid = min(kTgtPerWG, n_tgt - t_base);
+  if ((int)threadIdx.x < n_valid) {
+    const double* r = red + threadIdx.x;          // row lt = half * 64 + lane sits at [wave][lt]
+    dst[threadIdx.x] = (r[0] + r[2 * 64]) + (r[4 * 64] + r[6 * 64]);
+  }
 }
 
 }  // namespace

@@ -20,6 +20,10 @@ evaluation per step; csrc/direct_hermite.hip).
 
 Fourth addition: `BlockHermiteSimulator`, the same scheme with individual block timesteps inside each output interval
 (csrc/direct_hermite_block.hip).
+
+Fifth addition: `compute_potentials()` / `compute_invariants()` and `calc_invariants=`: the per-body potential of the
+softening the force uses and the conserved quantities formed from it (`Invariants`; csrc/direct_diag.hip).
+`compute_energies()`, `u_energy` and `k_energy` keep the reference's convention.
 """
 from __future__ import annotations
 
@@ -35,8 +39,42 @@ from nbd import dist as nbd_dist
 
 
 @dataclass
+class Invariants:
+    """The conserved quantities of one system (a row of nbd_invariants_f64): total mass, centre of mass, linear and
+    angular momentum, kinetic energy K = sum 1/2 m |v|^2, potential energy U = 1/2 sum m_i phi_i of the Plummer potential
+    the force derives from (phi_i = -G sum_{j != i} m_j (r_ij^2 + eps^2)^(-1/2)), E = K + U and the virial ratio
+    Q = -2 K / U (0 when U = 0). Every product is formed in fp64 from the fp32 state, so k_energy differs from
+    compute_energies()'s K (fp32 products) in the last digits; u_energy differs from compute_energies()'s U by
+    construction wherever the softening is not 0 (that one is the reference's -G m_i m_j / (|r| + eps))."""
+
+    mass: float
+    com: tuple
+    momentum: tuple
+    angular_momentum: tuple
+    k_energy: float
+    u_energy: float
+    energy: float
+    virial_ratio: float
+
+    @classmethod
+    def from_row(cls, row) -> "Invariants":
+        """From the 16 doubles {M, C (3), P (3), L (3), K, U, E, Q, 0, 0} (a list, array or CPU tensor)."""
+        r = [float(x) for x in (row.tolist() if hasattr(row, "tolist") else row)]
+        if len(r) != direct.INVARIANT_ROW:
+            raise ValueError(f"Invariants.from_row: expected {direct.INVARIANT_ROW} values, got {len(r)}")
+        return cls(mass=r[0], com=tuple(r[1:4]), momentum=tuple(r[4:7]), angular_momentum=tuple(r[7:10]),
+                   k_energy=r[10], u_energy=r[11], energy=r[12], virial_ratio=r[13])
+
+    def row(self) -> list:
+        """The 16 doubles from_row() takes."""
+        return [self.mass, *self.com, *self.momentum, *self.angular_momentum, self.k_energy, self.u_energy, self.energy,
+                self.virial_ratio, 0.0, 0.0]
+
+
+@dataclass
 class SimulationState:
-    """Snapshot of one step; field names and order as simulation.py:8-18."""
+    """Snapshot of one step; field names and order as simulation.py:8-18, then `invariants` (an addition: the
+    Invariants of the state after the step when the simulator was built with calc_invariants=True, else None)."""
 
     step: int
     step_time: float
@@ -45,6 +83,7 @@ class SimulationState:
     accelerations: torch.Tensor
     u_energy: float = None
     k_energy: float = None
+    invariants: Invariants = None
 
 
 def _to_f32(x, device) -> torch.Tensor:
@@ -157,7 +196,8 @@ class BaseSimulator(_ChunkedRun):
     _equal_mass_step = False        # the un-sharded step() has an equal-mass form (`_uniform`)
 
     def __init__(self, *, positions, velocities, masses, g_const: float = 1.0, softening: float = 0.1,
-                 dt: float = 0.01, calc_energy: bool = True, device: str = None, process_group=None):
+                 dt: float = 0.01, calc_energy: bool = True, device: str = None, process_group=None,
+                 calc_invariants: bool = False):
         self.device = _resolve_device(device)
         _lib.lib()  # fail now, loudly, if the extension is not built
 
@@ -165,6 +205,7 @@ class BaseSimulator(_ChunkedRun):
         self.g_const = g_const
         self.softening = softening
         self.calc_energy = calc_energy
+        self.calc_invariants = calc_invariants
         # fp32 scalars exactly as torch forms them from the Python doubles (simulation.py:82,88,164)
         self._eps2 = direct.f32(softening ** 2)
         self._g = direct.f32(g_const)
@@ -273,6 +314,47 @@ class BaseSimulator(_ChunkedRun):
         u, k = uk.cpu().tolist()
         return u, k
 
+    # ------------------------------------------------------------------ consistent-potential diagnostics
+    def _refuse_sharded(self, what: str):
+        if self._sharded:
+            raise ValueError(f"{type(self).__name__}.{what}: there are no range-sharded diagnostics; process_group is not "
+                             "supported here")
+
+    def _potentials_into(self, phi):
+        """phi (n,) float64 from _posm (already packed), asynchronous."""
+        if getattr(self, "_diag_ws", None) is None:
+            self._diag_ws = direct.potential_workspace(self.n, self.n, self.device)
+        return direct.potential(self._posm, self.n, self._posm, self.n, 0, self._eps2, self._g, out=phi,
+                                workspace=self._diag_ws)
+
+    def compute_potentials(self) -> torch.Tensor:
+        """phi_i = -G sum_{j != i} m_j (|r_ij|^2 + eps^2)^(-1/2) -> new (n,) float64 device tensor: the potential the force
+        of compute_accelerations() is the gradient of (pair terms in fp32, sums in fp64; csrc/direct_diag.hip). Coincident
+        distinct bodies at softening 0 give -inf."""
+        self._refuse_sharded("compute_potentials()")
+        if self.n == 0:
+            return torch.zeros((0,), dtype=torch.float64, device=self.device)
+        direct.pack_posm(self.positions, self.masses, out=self._posm)
+        return self._potentials_into(None)
+
+    def compute_invariants(self) -> Invariants:
+        """Mass, centre of mass, momentum, angular momentum, K, U = 1/2 sum m phi, E = K + U and the virial ratio of the
+        current state (see Invariants). compute_energies() is untouched: it keeps the reference's potential."""
+        self._refuse_sharded("compute_invariants()")
+        if self.n == 0:
+            return Invariants.from_row([0.0] * direct.INVARIANT_ROW)
+        phi = self.compute_potentials()
+        return Invariants.from_row(direct.invariants(self._posm, self.velocities, phi, self.n).cpu())
+
+    def _invariants_into(self, out_row):
+        """Invariants row of the state AFTER an un-sharded step, asynchronous (phi into a buffer kept by the simulator)."""
+        if getattr(self, "_phi", None) is None:
+            self._phi = torch.empty((self.n,), dtype=torch.float64, device=self.device)
+        if not self._posm_after_step:
+            direct.pack_posm(self.positions, self.masses, out=self._posm)
+        self._potentials_into(self._phi)
+        direct.invariants(self._posm, self.velocities, self._phi, self.n, out=out_row)
+
     def gather(self, name: str) -> torch.Tensor:
         """Global (n,3) copy of a sharded state array on every rank ('positions', ...)."""
         local = getattr(self, name)
@@ -290,6 +372,8 @@ class BaseSimulator(_ChunkedRun):
         states = []
         if steps <= 0:
             return states
+        if self.calc_invariants:
+            self._refuse_sharded("run() with calc_invariants")
         if self._graph_run_ok(steps):
             self._run_chunked(steps, self.GRAPH_RUN_CHUNK, states)
         else:
@@ -316,6 +400,8 @@ class BaseSimulator(_ChunkedRun):
         stage, uk_host = cached
         chunk = stage.shape[0]
         uk_dev = torch.zeros((chunk, 2), dtype=torch.float64, device=self.device)
+        inv_dev = (torch.zeros((chunk, direct.INVARIANT_ROW), dtype=torch.float64, device=self.device)
+                   if self.calc_invariants else None)
         done = 0
         while done < steps:
             m = min(chunk, steps - done)
@@ -332,6 +418,8 @@ class BaseSimulator(_ChunkedRun):
                     else:
                         u, k = self.compute_energies()
                         uk_dev[s, 0], uk_dev[s, 1] = u, k
+                if self.calc_invariants and self.n:
+                    self._invariants_into(inv_dev[s])
                 stage[s, 0].copy_(self.positions, non_blocking=True)
                 stage[s, 1].copy_(self.velocities, non_blocking=True)
                 stage[s, 2].copy_(self.accelerations, non_blocking=True)
@@ -339,18 +427,23 @@ class BaseSimulator(_ChunkedRun):
             torch.cuda.current_stream(self.device).synchronize()
             # one pageable copy of the whole chunk (the pinned staging is reused); the states' tensors are
             # views into it -- 3 m small clones cost several times more in allocation and page faults
-            self._emit_states((stage[:m].clone(), uk_host[:m]), m, first_index + done,
-                              [e0.elapsed_time(e1) * 1e-3 for e0, e1 in events], states)
+            host = [stage[:m].clone()] + ([uk_host[:m]] if self.calc_energy else []) + \
+                ([inv_dev[:m].cpu()] if self.calc_invariants else [])
+            self._emit_states(host, m, first_index + done, [e0.elapsed_time(e1) * 1e-3 for e0, e1 in events], states)
             done += m
 
     def _emit_states(self, host, m, first, t_steps, states):
-        """m states from host copies of a chunk's ring (m, 3, n, 3) and energies (m, 2): views, no copies."""
+        """m states from host copies of a chunk's ring (m, 3, n, 3), then (with calc_energy) its energies (m, 2), then
+        (with calc_invariants) its invariant rows (m, 16): views, no copies."""
+        rest = iter(host[1:])
         ring = host[0]
-        uk = host[1].tolist() if self.calc_energy else None
+        uk = next(rest).tolist() if self.calc_energy else None
+        inv = next(rest).tolist() if self.calc_invariants else None
         for s in range(m):
             u, k = (uk[s][0], uk[s][1]) if self.calc_energy else (None, None)
             states.append(SimulationState(step=first + s, step_time=t_steps[s], positions=ring[s, 0],
-                                          velocities=ring[s, 1], accelerations=ring[s, 2], u_energy=u, k_energy=k))
+                                          velocities=ring[s, 1], accelerations=ring[s, 2], u_energy=u, k_energy=k,
+                                          invariants=Invariants.from_row(inv[s]) if inv is not None else None))
 
     # ------------------------------------------------------------------ run(): captured chunks (_ChunkedRun)
     GRAPH_RUN_MAX_BODIES = 16384
@@ -367,7 +460,8 @@ class BaseSimulator(_ChunkedRun):
                 self._capturable() and os.environ.get("NBD_RUN_GRAPH", "1") != "0")
 
     def _chunk_scalars(self):
-        return (float(self.dt), float(self.softening), bool(self.calc_energy), self._eps2, self._g, self._uniform)
+        return (float(self.dt), float(self.softening), bool(self.calc_energy), self._eps2, self._g, self._uniform,
+                bool(self.calc_invariants))
 
     def _chunk_body(self, m: int):
         n, dev = self.n, self.device
@@ -375,14 +469,17 @@ class BaseSimulator(_ChunkedRun):
             self._energy_ws = direct.alloc_bytes(_lib.lib().nbd_energy_workspace_bytes(n), dev)
         ring = torch.empty((m, 3, n, 3), dtype=torch.float32, device=dev)
         uk = torch.zeros((m, 2), dtype=torch.float64, device=dev)
+        inv = torch.zeros((m, direct.INVARIANT_ROW), dtype=torch.float64, device=dev) if self.calc_invariants else None
 
         def body(count):
             for s_ in range(count):
                 self._step_in_place()
                 if self.calc_energy:
                     self._energies_into(uk[s_], self._energy_ws)
+                if self.calc_invariants:
+                    self._invariants_into(inv[s_])
                 direct.snapshot(self.positions, self.velocities, self._acc_g, ring[s_])
-        return body, ((ring, uk) if self.calc_energy else (ring,))
+        return body, (ring,) + ((uk,) if self.calc_energy else ()) + ((inv,) if self.calc_invariants else ())
 
     def step(self):
         raise NotImplementedError("El método step debe ser implementado en la subclase")
@@ -519,12 +616,14 @@ class HermiteSimulator(BaseSimulator):
     range-sharded form (process_group is refused) and no equal-mass specialisation."""
 
     def __init__(self, *, positions, velocities, masses, g_const: float = 1.0, softening: float = 0.1,
-                 dt: float = 0.01, calc_energy: bool = True, device: str = None, process_group=None):
+                 dt: float = 0.01, calc_energy: bool = True, device: str = None, process_group=None,
+                 calc_invariants: bool = False):
         if process_group is not None:
             raise ValueError("HermiteSimulator: there is no range-sharded Hermite step; process_group is not supported")
         self.jerks = None
         super().__init__(positions=positions, velocities=velocities, masses=masses, g_const=g_const,
-                         softening=softening, dt=dt, calc_energy=calc_energy, device=device)
+                         softening=softening, dt=dt, calc_energy=calc_energy, device=device,
+                         calc_invariants=calc_invariants)
         self._velp = direct.alloc_posm(self.n, self.device)
         self._hws = direct.hermite_workspace(max(self.n, 1), self.device)
         self.accelerations, self.jerks = self.compute_accelerations_and_jerks()
@@ -575,12 +674,13 @@ class BlockHermiteSimulator(HermiteSimulator):
 
     def __init__(self, *, positions, velocities, masses, g_const: float = 1.0, softening: float = 0.1,
                  dt: float = 0.01, calc_energy: bool = True, device: str = None, process_group=None,
-                 eta: float = 0.02, max_level: int = 10):
+                 eta: float = 0.02, max_level: int = 10, calc_invariants: bool = False):
         if process_group is not None:
             raise ValueError("BlockHermiteSimulator: there is no range-sharded Hermite step; process_group is not "
                              "supported")
         super().__init__(positions=positions, velocities=velocities, masses=masses, g_const=g_const,
-                         softening=softening, dt=dt, calc_energy=calc_energy, device=device)
+                         softening=softening, dt=dt, calc_energy=calc_energy, device=device,
+                         calc_invariants=calc_invariants)
         self.eta = eta
         self.max_level = max_level
         self.levels = torch.zeros(self.n, dtype=torch.int32, device=self.device)
@@ -671,18 +771,21 @@ def _batch_chunk_views(buf, m: int, n: int, n_scenes: int):
             buf[uk_at:size].view(torch.float64).view(m, n_scenes, 2))
 
 
-def _batch_states(host, m: int, offsets: list, calc_energy: bool, first: int, t_steps, out):
-    """Append m states per scene to `out` from a host copy of a chunk buffer (views into it, no copies)."""
+def _batch_states(host, m: int, offsets: list, calc_energy: bool, first: int, t_steps, out, inv=None):
+    """Append m states per scene to `out` from a host copy of a chunk buffer (views into it, no copies). inv: a host copy
+    of the chunk's invariant rows (m, S, 16), or None."""
     n_scenes = len(offsets) - 1
     ring, uk = _batch_chunk_views(host, m, offsets[-1], n_scenes)
     uk = uk.tolist() if calc_energy else None
+    inv = inv.tolist() if inv is not None else None
     for s_ in range(m):
         for i in range(n_scenes):
             lo, hi = offsets[i], offsets[i + 1]
             u, k = (uk[s_][i][0], uk[s_][i][1]) if calc_energy else (None, None)
             out[i].append(SimulationState(step=first + s_, step_time=t_steps[s_], positions=ring[s_, 0, lo:hi],
                                           velocities=ring[s_, 1, lo:hi], accelerations=ring[s_, 2, lo:hi],
-                                          u_energy=u, k_energy=k))
+                                          u_energy=u, k_energy=k,
+                                          invariants=Invariants.from_row(inv[s_][i]) if inv is not None else None))
 
 
 class BatchedSimulator(_ChunkedRun):
@@ -702,7 +805,7 @@ class BatchedSimulator(_ChunkedRun):
     RING_BYTES = 64 << 20                                # the eager run()'s staging cap, per chunk of states
 
     def __init__(self, *, systems, integrator: str = "leapfrog", g_const=1.0, softening=0.1, dt=0.01,
-                 calc_energy: bool = True, device: str = None):
+                 calc_energy: bool = True, device: str = None, calc_invariants: bool = False):
         if integrator not in ("leapfrog", "euler", "hermite"):
             raise ValueError("integrator must be 'leapfrog', 'euler' or 'hermite'")
         self.device = _resolve_device(device)
@@ -712,6 +815,7 @@ class BatchedSimulator(_ChunkedRun):
             raise ValueError("systems: need at least one (positions, velocities, masses) scene")
         self.integrator = integrator
         self.calc_energy = calc_energy
+        self.calc_invariants = calc_invariants
         self.n_scenes = len(systems)
         pos, vel, mass = [], [], []
         for i, sysm in enumerate(systems):
@@ -734,6 +838,7 @@ class BatchedSimulator(_ChunkedRun):
         self._params_key = None
         self._hermite = integrator == "hermite"          # fixed at construction: the state carries jerks or not
         self._hws = None
+        self._phi = None
         self.jerks = None
         if self._hermite:
             self._carried = self._carried + (("jerks", "_jerk_g"),)
@@ -811,6 +916,33 @@ class BatchedSimulator(_ChunkedRun):
         uk = uk.cpu()
         return uk[:, 0].tolist(), uk[:, 1].tolist()
 
+    # ------------------------------------------------------------------ consistent-potential diagnostics
+    def _potentials_into(self, phi):
+        """phi (N_total,) float64 from _posm (already packed, parameters in sync), asynchronous."""
+        P = self._params
+        return direct.batch_potential(self._plan, self._posm, P[1], P[0], phi, self._ws)
+
+    def _invariants_into(self, out_rows):
+        """(S, 16) invariant rows of the state a step left (posm = its positions), asynchronous."""
+        if self._phi is None:
+            self._phi = torch.zeros((self.n,), dtype=torch.float64, device=self.device)
+        self._potentials_into(self._phi)
+        direct.batch_invariants(self._plan, self._posm, self.velocities, self._phi, out_rows)
+
+    def compute_potentials(self) -> torch.Tensor:
+        """Every body's potential under the bodies of its own scene, with the scene's softening and g_const -> new
+        (N_total,) float64 device tensor in scene order (BaseSimulator.compute_potentials per scene, bit for bit)."""
+        self._sync_params()
+        direct.batch_pack_posm(self._plan, self.positions, self.masses, self._posm)
+        return self._potentials_into(torch.zeros((self.n,), dtype=torch.float64, device=self.device))
+
+    def compute_invariants(self) -> list:
+        """One Invariants per scene (BaseSimulator.compute_invariants per scene, bit for bit; zeros for an empty scene)."""
+        phi = self.compute_potentials()
+        rows = torch.zeros((self.n_scenes, direct.INVARIANT_ROW), dtype=torch.float64, device=self.device)
+        direct.batch_invariants(self._plan, self._posm, self.velocities, phi, rows)
+        return [Invariants.from_row(r) for r in rows.cpu().tolist()]
+
     def _step_into(self, cur, new):
         """One step from the carried arrays `cur` into `new` (lists in the order of `_carried`; may be the same)."""
         P = self._params
@@ -855,7 +987,9 @@ class BatchedSimulator(_ChunkedRun):
             empty = torch.zeros((0, 3), dtype=torch.float32)
             for i in range(self.n_scenes):
                 out[i] = [SimulationState(step=s, step_time=0.0, positions=empty, velocities=empty, accelerations=empty,
-                                          u_energy=uk[0], k_energy=uk[1]) for s in range(steps)]
+                                          u_energy=uk[0], k_energy=uk[1],
+                                          invariants=(Invariants.from_row([0.0] * direct.INVARIANT_ROW)
+                                                      if self.calc_invariants else None)) for s in range(steps)]
             return out
         self._sync_params()
         big = self._chunk_len()
@@ -871,15 +1005,23 @@ class BatchedSimulator(_ChunkedRun):
         buf = torch.empty(size, dtype=torch.uint8, device=self.device)
         return (buf,) + _batch_chunk_views(buf, m, self.n, self.n_scenes)
 
+    def _inv_buffer(self, m: int):
+        """The chunk's invariant rows (m, S, 16), a second device buffer next to ring | energies; None without the flag."""
+        if not self.calc_invariants:
+            return None
+        return torch.zeros((m, self.n_scenes, direct.INVARIANT_ROW), dtype=torch.float64, device=self.device)
+
     def _emit_states(self, host, m, first, t_steps, out):
         _batch_states(host[0], m, self.offsets.tolist(), self.calc_energy, first,
-                      [t / self.n_scenes for t in t_steps], out)       # the batched step's GPU time, spread over S
+                      [t / self.n_scenes for t in t_steps], out,       # the batched step's GPU time, spread over S
+                      inv=host[1] if self.calc_invariants else None)
 
     def _run_eager(self, steps: int, first: int, out):
         done = 0
         while done < steps:
             m = min(self._chunk_len(), steps - done)
             buf, ring, uk = self._chunk_buffers(m)
+            inv = self._inv_buffer(m)
             events = []
             for s_ in range(m):
                 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -889,16 +1031,19 @@ class BatchedSimulator(_ChunkedRun):
                 events.append((e0, e1))
                 if self.calc_energy:
                     self._energies_into(uk[s_])
+                if inv is not None:
+                    self._invariants_into(inv[s_])
                 direct.snapshot(self.positions, self.velocities, self.accelerations, ring[s_])
-            host = buf.cpu()
-            self._emit_states([host], m, first + done, [a.elapsed_time(b) * 1e-3 for a, b in events], out)
+            host = [buf.cpu()] + ([inv.cpu()] if inv is not None else [])
+            self._emit_states(host, m, first + done, [a.elapsed_time(b) * 1e-3 for a, b in events], out)
             done += m
 
     def _chunk_scalars(self):
-        return (self._params_key, bool(self.calc_energy), self.integrator)
+        return (self._params_key, bool(self.calc_energy), self.integrator, bool(self.calc_invariants))
 
     def _chunk_body(self, m: int):
         buf, ring, uk = self._chunk_buffers(m)
+        inv = self._inv_buffer(m)
         statics = self._statics()
 
         def body(count):
@@ -906,5 +1051,7 @@ class BatchedSimulator(_ChunkedRun):
                 self._step_into(statics, statics)
                 if self.calc_energy:
                     self._energies_into(uk[s_])
+                if inv is not None:
+                    self._invariants_into(inv[s_])
                 direct.snapshot(self.positions, self.velocities, statics[0], ring[s_])
-        return body, (buf,)
+        return body, (buf,) + ((inv,) if inv is not None else ())

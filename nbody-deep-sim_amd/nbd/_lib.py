@@ -174,6 +174,15 @@ SIGNATURES = {
     "nbd_energy_workspace_bytes": (c_size_t, [c_int]),
     "nbd_energy_f32": (c_int, [c_void_p, c_void_p, c_int, c_float, c_float, c_void_p, c_void_p,
                                c_size_t, c_void_p]),
+    # --- consistent-potential diagnostics (csrc/direct_diag.hip)
+    "nbd_potential_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "nbd_potential_f32": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_float, c_float, c_void_p, c_void_p,
+                                  c_size_t, c_void_p]),
+    "nbd_invariants_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
+    "nbd_batch_potential_f32": (c_int, [c_void_p, c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p,
+                                        c_void_p, c_size_t, c_void_p]),
+    "nbd_batch_invariants_f64": (c_int, [c_void_p, c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p,
+                                         c_void_p]),
     # --- batched direct integrator (csrc/direct_batch.hip)
     "nbd_batch_plan": (c_int, [c_void_p, c_int, POINTER(c_int), POINTER(c_int), POINTER(c_size_t), POINTER(c_size_t)]),
     "nbd_batch_plan_fill": (c_int, [c_void_p, c_int, c_void_p, c_size_t]),

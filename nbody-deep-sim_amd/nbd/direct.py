@@ -267,6 +267,52 @@ def energy(posm, vel, n: int, softening: float, g_const: float, out_uk=None, wor
     return out_uk
 
 
+# ---------------------------------------------------------------- consistent-potential diagnostics (csrc/direct_diag.hip)
+INVARIANT_ROW = 16              # doubles per row: {M, C (3), P (3), L (3), K, U, E, Q, 0, 0}
+
+
+def potential_workspace(n_src: int, n_tgt: int, device) -> torch.Tensor:
+    return alloc_bytes(_lib.lib().nbd_potential_workspace_bytes(int(n_src), int(n_tgt)), device)
+
+
+def potential(posm_src: torch.Tensor, n_src: int, posm_tgt: torch.Tensor, n_tgt: int, tgt_offset: int,
+              softening_sq: float, g_const: float, out: torch.Tensor | None = None,
+              workspace: torch.Tensor | None = None) -> torch.Tensor:
+    """phi (n_tgt,) float64 of targets posm_tgt[:n_tgt] under sources posm_src[:n_src]:
+    phi_i = -G sum_{j != i} m_j (|r_ij|^2 + eps^2)^(-1/2), the potential the force of `accel` derives from (j == tgt_offset
+    + i excluded by index). Asynchronous, deterministic."""
+    _chk(posm_src, (padded_len(n_src), 4), "posm_src") if n_src > 0 else None
+    _chk(posm_tgt, None, "posm_tgt")
+    if posm_tgt.dim() != 2 or posm_tgt.shape[1] != 4 or posm_tgt.shape[0] < n_tgt:
+        raise _lib.NbdError(f"posm_tgt: need >= {n_tgt} rows of 4, got {tuple(posm_tgt.shape)}")
+    dev = posm_tgt.device
+    if out is None:
+        out = torch.empty((n_tgt,), dtype=torch.float64, device=dev)
+    _chk(out, (n_tgt,), "phi_out", torch.float64)
+    need = _lib.lib().nbd_potential_workspace_bytes(n_src, n_tgt)
+    if workspace is None or _nbytes(workspace) < need:
+        workspace = alloc_bytes(need, dev)
+    with _lib.on_device(dev):
+        _lib.check(_lib.lib().nbd_potential_f32(
+            posm_src.data_ptr() if n_src > 0 else None, n_src, posm_tgt.data_ptr(), n_tgt, int(tgt_offset),
+            float(softening_sq), float(g_const), out.data_ptr(), workspace.data_ptr(), _nbytes(workspace),
+            _lib.current_stream(dev)), "nbd_potential_f32")
+    return out
+
+
+def invariants(posm, vel, phi, n: int, out: torch.Tensor | None = None) -> torch.Tensor:
+    """Device double[16] = {M, C, P, L, K, U, E, Q, 0, 0} of the n bodies of posm / vel with their potentials phi (as
+    `potential` returns them); every product in fp64 from the fp32 state, fixed summation order. Asynchronous."""
+    _chk(posm, (padded_len(n), 4), "posm"); _chk(vel, (n, 3), "vel"); _chk(phi, (n,), "phi", torch.float64)
+    dev = vel.device
+    if out is None:
+        out = torch.empty(INVARIANT_ROW, dtype=torch.float64, device=dev)
+    _chk(out, (INVARIANT_ROW,), "out_row", torch.float64)
+    with _lib.on_device(dev):
+        _lib.check(_lib.lib().nbd_invariants_f64(posm.data_ptr(), vel.data_ptr(), phi.data_ptr(), n, out.data_ptr(),
+                                                 _lib.current_stream(dev)), "nbd_invariants_f64")
+    return out
+
 
 # ---------------------------------------------------------------- 4th-order Hermite integrator (csrc/direct_hermite.hip)
 def hermite_workspace(n: int, device) -> torch.Tensor:
@@ -509,6 +555,30 @@ def batch_energies(plan: BatchPlan, posm, vel, soft, g, out_uk, ws) -> torch.Ten
             *plan.head(), posm.data_ptr(), vel.data_ptr(), _param(soft, plan, "softening"), _param(g, plan, "g_const"),
             out_uk.data_ptr(), ws.data_ptr(), _nbytes(ws), _lib.current_stream(vel.device)), "nbd_batch_energies")
     return out_uk
+
+
+def batch_potential(plan: BatchPlan, posm, eps2, g, phi_out, ws) -> torch.Tensor:
+    """phi_out (N_total,) float64 = every body's potential under the bodies of its own scene (`potential` per scene, bit
+    for bit) from posm as the batch entries leave it. eps2, g: device fp32 (S,); ws: plan.workspace(). Asynchronous."""
+    plan.check_state(posm, ws)
+    _chk(phi_out, (plan.n_total,), "phi_out", torch.float64)
+    with _lib.on_device(posm.device):
+        _lib.check(_lib.lib().nbd_batch_potential_f32(
+            *plan.head(), posm.data_ptr(), _param(eps2, plan, "softening_sq"), _param(g, plan, "g_const"),
+            phi_out.data_ptr(), ws.data_ptr(), _nbytes(ws), _lib.current_stream(posm.device)), "nbd_batch_potential_f32")
+    return phi_out
+
+
+def batch_invariants(plan: BatchPlan, posm, vel, phi, out_rows) -> torch.Tensor:
+    """out_rows (S, 16) float64 = `invariants` of every scene (bit for bit) from posm, vel and phi (batch_potential)."""
+    plan.check_state(posm, None, (vel, "vel"))
+    _chk(phi, (plan.n_total,), "phi", torch.float64)
+    _chk(out_rows, (plan.n_scenes, INVARIANT_ROW), "out_rows", torch.float64)
+    with _lib.on_device(vel.device):
+        _lib.check(_lib.lib().nbd_batch_invariants_f64(
+            *plan.head(), posm.data_ptr(), vel.data_ptr(), phi.data_ptr(), out_rows.data_ptr(),
+            _lib.current_stream(vel.device)), "nbd_batch_invariants_f64")
+    return out_rows
 
 
 # ---------------------------------------------------------------- Hermite per scene (csrc/direct_batch_hermite.hip)
