@@ -124,8 +124,9 @@ class ContinuousConv(nn.Module):
                 centres = torch.zeros(1, dtype=torch.int32, device=positions.device)
         r2 = float(np.float32(self.radius ** 2))                       # contconv.py:86: python double -> fp32
         if self.agg in ("max", "min", "mul"):
-            self.last_path = "extreme"
-            return self._forward_extreme(positions, features, rowptr, centres, act, out)
+            red = self._forward_extreme(positions, features, rowptr, centres, act, out)
+            self.last_path = "extreme"           # (set last: the per-edge messages come from a nested forward with agg = "sum")
+            return red
         if self.agg != "mean":
             scale = None
         training_path = torch.is_grad_enabled() and (self.filters.requires_grad or features.requires_grad)

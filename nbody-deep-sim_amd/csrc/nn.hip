@@ -3,7 +3,8 @@
 //   nbd_linear_f32          Y = act(rowscale * (X W^T) + b): torch.nn.Linear (+tanh, + PyG-MLP/BatchNorm
 //                           folded on the host) -- gnn.py:57-63,75-93,105-114; contconv.py:136-141,206-216;
 //                           also the ContinuousConv contraction (contconv.py:92) after cell binning.
-//                           fp32-input MFMA (v_mfma_f32_32x32x2_f32): exact fp32 products, k-ordered fmaf chain.
+//                           fp32-input MFMA (v_mfma_f32_32x32x2_f32): exact fp32 products, k-ordered fmaf chains of
+//                           at most 256 terms, summed in order (blocked summation).
 //   nbd_edgeconv_aggregate_f32   S_i = aggr_j tanh(P_i + Q_j) over the edges grouped by target i:
 //                           EdgeConv (gnn.py:75-93) after factoring its first Linear per node:
 //                           W1 [x_i || x_j - x_i] + b1 = (W1a - W1b) x_i + b1  +  W1b x_j  =  P_i + Q_j.
@@ -56,11 +57,17 @@ __global__ __launch_bounds__(256) void linear_kernel(
   const int wm = wave % WM, wn = wave / WM;
   const int row0 = blockIdx.x * BM, col0 = blockIdx.y * BN;
 
-  f16v acc[NT];
+  // Blocked summation: the k-ordered chain of a product is cut every FLUSH_K terms -- the chain's sum goes into `tot` and
+  // the chain starts again from zero --, so its rounding error grows with sqrt(FLUSH_K) + sqrt(K / FLUSH_K), not with
+  // sqrt(K) (the binned ContinuousConv contraction at K = 27 x 70 = 1890 sat at 4.1 x the reference's own fp32 error
+  // with one chain). K <= FLUSH_K never flushes and gives the bits of the single chain.
+  constexpr int FLUSH_K = 8 * BK;
+  const bool blocked = K > FLUSH_K;                // uniform
+  f16v acc[NT], tot[NT];
 #pragma unroll
   for (int t = 0; t < NT; ++t)
 #pragma unroll
-    for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
+    for (int r = 0; r < 16; ++r) { acc[t][r] = 0.f; tot[t][r] = 0.f; }
 
   // VEC path: the K-slab of step k + 1 is fetched into registers before the MFMAs of step k (a product with K = 256
   // otherwise exposes eight global-load latencies back to back: 20 us for 16 384 x 256 x 64 against 4 us of traffic)
@@ -84,6 +91,12 @@ __global__ __launch_bounds__(256) void linear_kernel(
   };
   if (VEC && K > 0) prefetch(0);
   for (int k0 = 0; k0 < K; k0 += BK) {
+    if (k0 > 0 && k0 % FLUSH_K == 0) {
+#pragma unroll
+      for (int t = 0; t < NT; ++t)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) { tot[t][r] = __fadd_rn(tot[t][r], acc[t][r]); acc[t][r] = 0.f; }
+    }
     __syncthreads();   // previous step's fragment reads are done
     if (VEC) {
       const int q = tid & 7, r8 = tid >> 3;
@@ -131,7 +144,7 @@ __global__ __launch_bounds__(256) void linear_kernel(
     for (int r = 0; r < 16; ++r) {
       const int row = row0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
       if (row < n_rows && col < n_cols) {
-        float v = acc[t][r];
+        float v = blocked ? __fadd_rn(tot[t][r], acc[t][r]) : acc[t][r];
         if (rowscale) v = __fmul_rn(v, rowscale[row]);
         const float bb = bias_rowscale ? __fmul_rn(b, bias_rowscale[row]) : b;
         Y[(size_t)row * ldy + col] = act_apply(__fadd_rn(v, bb), act);

@@ -841,7 +841,9 @@ def test_contconv_public_helpers_reproduce_the_reference_class(case, gpu_device)
 def test_contconv_kernels_reproduce_reference_interpolation(case, gpu_device):
     """48 isolated edges (target t_k, source s_k = t_k + r_k): the HIP binning + GEMM must give
     window_k * sum_i filt_k[i][:] feat[s_k][i] with filt_k = the REFERENCE's trilinear_interpolate(
-    (ball_to_cube(r_k) + 1)(D-1)/2) as stored by tests/golden/make_golden_surrogate.py (contconv.py:84-93)."""
+    (ball_to_cube(r_k) + 1)(D-1)/2) as stored by tests/golden/make_golden_surrogate.py (contconv.py:84-93).
+    (The stronger pin -- the reference's whole forward on dense graphs, every path, at the reference's own fp32 error:
+    test_contconv_forward_reproduces_the_reference_run below.)"""
     import contconv
     g = _ref_vectors("contconv")
     filters = torch.tensor(g[f"c{case}_filters"])
@@ -869,6 +871,121 @@ def test_contconv_kernels_reproduce_reference_interpolation(case, gpu_device):
     err = (got[:k][ok] - ref[ok]).norm() / ref[ok].norm()
     assert err < 2e-4, err                                                  # interpolation argument perturbed by <= 1e-4 rel
     assert float(got[k:].abs().max()) == 0.0                               # sources receive nothing
+
+
+# ContinuousConv.forward pinned by the reference's own fp64 run up to its scatter call (tests/contconv_pin_cases.py,
+# tests/golden/surrogate_ref_contconv_forward_*.npz; the host side of the pin: tests/test_surrogate_oracle.py)
+def _pin_case(case, agg=None):
+    """(layer, pos, feat, edge_index on the GPU, rows that must be exactly 0.0, inputs) of a pinned case."""
+    import contconv
+    import contconv_pin_cases as pc
+    n, d, i, o, case_agg, radius, _, _ = pc.CASES[case]
+    inp = pc.checked_inputs(case)
+    layer = contconv.ContinuousConv(i, o, d, radius=radius, agg=agg or case_agg).cuda()
+    with torch.no_grad():
+        layer.filters.copy_(torch.from_numpy(inp["filters"]).cuda())
+    ei = inp["edge_index"]
+    rel = inp["pos"].astype(np.float64)[ei[1]] - inp["pos"].astype(np.float64)[ei[0]]
+    inside = ((rel ** 2).sum(1) < radius ** 2).astype(np.float64)               # exact: the lattice (contconv_pin_cases)
+    zero_rows = torch.from_numpy(np.bincount(ei[0], weights=inside, minlength=n) == 0)   # no edge, or none inside the radius
+    return layer, torch.from_numpy(inp["pos"]).cuda(), torch.from_numpy(inp["feat"]).cuda(), torch.from_numpy(ei).cuda(), zero_rows, inp
+
+
+def _exactly_zero(got, zero_rows):
+    return not zero_rows.any() or float(got.cpu()[zero_rows].abs().max()) == 0.0
+
+
+@pytest.mark.parametrize("case", ["f0", "f1", "f2", "f3", "f4", "f5"])
+def test_contconv_forward_reproduces_the_reference_run(case, gpu_device):
+    """Inference through edge_index= on the fused and the binned path against out64, the reference's own fp64 run of
+    forward (contconv.py:80-98) on a dense, permuted edge list with duplicates, edges beyond the radius, a coincident pair
+    and a pair at exactly the radius. Bars: the project's, and four times the reference's own fp32 error."""
+    import contconv_pin_cases as pc
+    layer, pos, feat, ei, zero_rows, _ = _pin_case(case)
+    assert layer.fused_ok()
+    with torch.no_grad():
+        got = layer(pos, feat, edge_index=ei)
+        assert layer.last_path == "fused"
+        again = layer(pos, feat, edge_index=ei)
+        by_target = layer(pos, feat, edge_index=ei[:, torch.sort(ei[0], stable=True).indices])
+        layer.use_fused = False
+        old = layer(pos, feat, edge_index=ei)
+        assert layer.last_path == "binned"
+        old_again = layer(pos, feat, edge_index=ei)
+    pc.check(got.cpu().numpy(), case, "out", "fused")
+    pc.check(old.cpu().numpy(), case, "out", "binned")
+    assert torch.equal(got, again) and torch.equal(old, old_again)             # a second call gives the same bits
+    assert torch.equal(got, by_target)                                         # the layer sorts stably by target
+    assert _exactly_zero(got, zero_rows) and _exactly_zero(old, zero_rows)
+
+
+def test_contconv_extreme_aggregation_reproduces_the_reference_run(gpu_device):
+    """f6 (max, no self loops): rows without edges and rows whose every listed edge is beyond the radius are exactly 0.0 --
+    also under sum and mean on the fused and the binned path, where an edge beyond the radius still counts in the mean."""
+    import contconv_pin_cases as pc
+    layer, pos, feat, ei, zero_rows, inp = _pin_case("f6")
+    deg = np.bincount(inp["edge_index"][0], minlength=pos.shape[0])
+    assert (deg == 0).any() and (zero_rows.numpy() & (deg > 0)).any()
+    with torch.no_grad():
+        got = layer(pos, feat, edge_index=ei)
+        assert layer.last_path == "extreme"
+        again = layer(pos, feat, edge_index=ei)
+    pc.check(got.cpu().numpy(), "f6", "out", "extreme")
+    assert torch.equal(got, again) and _exactly_zero(got, zero_rows)
+    for agg in ("sum", "mean"):
+        lin, _, _, _, _, _ = _pin_case("f6", agg=agg)
+        for fused in (True, False):
+            lin.use_fused = fused
+            with torch.no_grad():
+                out = lin(pos, feat, edge_index=ei)
+            assert lin.last_path == ("fused" if fused else "binned") and _exactly_zero(out, zero_rows)
+            assert bool(torch.isfinite(out).all()) and float(out.abs().max()) > 0.0
+
+
+@pytest.mark.parametrize("case", ["f1", "f2", "f5"])
+def test_contconv_forward_through_the_search_lists_reproduces_the_reference_run(case, gpu_device):
+    """Inference through lists= (graphops.radius_lists on the same positions): the search's edges agree index for index with
+    the radius-graph part of the stored edge list, and the output with out64_lists, the reference's messages of those edges."""
+    import contconv_pin_cases as pc
+    from nbd import graphops
+    layer, pos, feat, ei, _, _ = _pin_case(case)
+    _, _, _, _, _, radius, cap, loop = pc.CASES[case]
+    stored = ei[:, torch.from_numpy(pc.fixture()[f"{case}_radius_at"].astype(np.int64)).cuda()]
+    assert torch.equal(graphops.radius_graph(pos, radius, None, loop=loop, max_num_neighbors=cap), stored)
+    lists = graphops.radius_lists(pos, radius, None, loop=loop, max_num_neighbors=cap)
+    e = stored.shape[1]
+    order = torch.sort(stored[0], stable=True).indices                          # CSR by aggregation target, centres ascending
+    assert int(lists.rowptr[-1]) == e and torch.equal(lists.centres[:e].long(), stored[1][order])
+    assert torch.equal(lists.rowptr.long(), torch.cat([torch.zeros(1, dtype=torch.int64, device="cuda"),
+                                                        torch.cumsum(torch.bincount(stored[0], minlength=pos.shape[0]), 0)]))
+    with torch.no_grad():
+        got = layer(pos, feat, lists=lists)
+        assert layer.last_path == "fused"
+        layer.use_fused = False
+        old = layer(pos, feat, lists=lists)
+        assert layer.last_path == "binned"
+    pc.check(got.cpu().numpy(), case, "out_lists", "fused, lists=")
+    pc.check(old.cpu().numpy(), case, "out_lists", "binned, lists=")
+
+
+def test_contconv_tanh_epilogue_and_strided_output_reproduce_the_reference_run(gpu_device):
+    """f2 with act="tanh" (the model's next operation, contconv.py:228-230) and with out= a column view of a wider buffer."""
+    import contconv_pin_cases as pc
+    layer, pos, feat, ei, _, _ = _pin_case("f2")
+    n, i, o = pos.shape[0], layer.in_channels, layer.out_channels
+    for fused in (True, False):
+        layer.use_fused = fused
+        path = "fused" if fused else "binned"
+        buf = torch.zeros((n, i + o + 2), device="cuda")          # how the model passes its concatenation buffer
+        with torch.no_grad():
+            got = layer(pos, feat, edge_index=ei)
+            got_t = layer(pos, feat, edge_index=ei, act="tanh")
+            assert layer.last_path == path
+            layer(pos, feat, edge_index=ei, out=buf[:, i:i + o])
+            assert layer.last_path == path
+        pc.check(got_t.cpu().numpy(), "f2", "tanh", path)
+        assert torch.equal(buf[:, i:i + o], got)
+        assert float(buf[:, i + o:].abs().max()) == 0.0 and float(buf[:, :i].abs().max()) == 0.0
 
 
 def test_trainer_rollout_reproduces_reference_frame(gpu_device):

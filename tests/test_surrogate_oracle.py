@@ -246,3 +246,83 @@ def test_contconv_oracle_product_aggregation_known_answer():
         m10 = add(pos, feat, ei[:, 2:3])[1]
     assert torch.allclose(out[0], m01 * m02, rtol=1e-6, atol=0) and torch.allclose(out[1], m10, rtol=1e-6, atol=0)
     assert torch.equal(out[2], torch.ones(2)) and torch.equal(out[3], torch.ones(2))
+
+
+# ------------------------------------------------------------------ ContinuousConv.forward pinned by the reference's own run
+# tests/golden/surrogate_ref_contconv_forward_*.npz: the reference's forward executed in fp64 (and fp32, for the yardstick)
+# up to its scatter call, with its own autograd (make_golden_surrogate.py: contconv_forward_vectors). The same fixtures and
+# bars hold the HIP paths in tests/test_surrogate_gpu.py and tests/test_train_gpu.py.
+def _pin_oracle(case, inp, dtype=torch.float32):
+    import contconv_pin_cases as pc
+    _, d, i, o, agg, radius, _, _ = pc.CASES[case]
+    ora = so.ContinuousConvOracle(i, o, d, radius=radius, agg=agg)
+    with torch.no_grad():
+        ora.filters.copy_(torch.from_numpy(inp["filters"]))
+    return ora.to(dtype)
+
+
+@pytest.mark.parametrize("case", ["f0", "f1", "f2", "f3", "f4", "f5", "f6", "g0", "g1", "g2"])
+def test_contconv_pin_inputs_and_edges_regenerate_to_the_stored_digests(case):
+    import contconv_pin_cases as pc
+    inp = pc.checked_inputs(case)                         # asserts the sha256 of pos, feat, filters, dout
+    fx = pc.fixture()
+    ei, radius_at = pc.edges(case, inp["pos"])
+    assert np.array_equal(ei, fx[f"{case}_edge_index"]) and np.array_equal(radius_at, fx[f"{case}_radius_at"])
+    n, radius = pc.CASES[case][0], pc.CASES[case][5]
+    assert fx[f"{case}_out64"].dtype == np.float64 and fx[f"{case}_out64"].shape == (n, pc.CASES[case][3])
+    # the lattice: every relative position and dist2 is exact in fp32, the special pairs are there, rows are not sorted
+    rel32 = inp["pos"][ei[1]] - inp["pos"][ei[0]]
+    rel64 = inp["pos"].astype(np.float64)[ei[1]] - inp["pos"].astype(np.float64)[ei[0]]
+    d32 = (rel32 ** 2).sum(1, dtype=np.float32)
+    assert np.array_equal(rel32.astype(np.float64), rel64) and np.array_equal(d32.astype(np.float64), (rel64 ** 2).sum(1))
+    assert ((d32 == 0) & (ei[0] != ei[1])).any() and (np.diff(ei[0]) < 0).any()
+    if radius in pc.EXACT_RADIUS:
+        assert (d32.astype(np.float64) == radius ** 2).sum() >= 2
+    pairs = ei[0].astype(np.int64) * n + ei[1]
+    assert len(pairs) - len(np.unique(pairs)) >= 2                                  # exact duplicate edges
+
+
+@pytest.mark.parametrize("case", ["f0", "f1", "f2", "f3", "f4", "f5", "f6"])
+def test_contconv_oracle_forward_meets_the_kernels_bars_against_the_reference_run(case):
+    import contconv_pin_cases as pc
+    inp = pc.checked_inputs(case)
+    ora = _pin_oracle(case, inp)
+    pos, feat, ei = torch.from_numpy(inp["pos"]), torch.from_numpy(inp["feat"]), torch.from_numpy(inp["edge_index"])
+    with torch.no_grad():
+        pc.check(ora(pos, feat, ei, edge_block=1024).numpy(), case, "out", "oracle fp32")
+        if case in pc.LISTS_CASES:
+            at = torch.from_numpy(pc.fixture()[f"{case}_radius_at"].astype(np.int64))
+            pc.check(ora(pos, feat, ei[:, at], edge_block=1024).numpy(), case, "out_lists", "oracle fp32, radius graph alone")
+
+
+@pytest.mark.parametrize("case", ["g0", "g1", "g2", "f2"])
+def test_contconv_oracle_autograd_meets_the_gradient_bars_against_the_reference_run(case):
+    import contconv_pin_cases as pc
+    inp = pc.checked_inputs(case)
+    ora = _pin_oracle(case, inp)
+    pos, ei = torch.from_numpy(inp["pos"]), torch.from_numpy(inp["edge_index"])
+    feat = torch.from_numpy(inp["feat"]).clone().requires_grad_()
+    out = ora(pos, feat, ei, edge_block=1024)
+    out.backward(torch.from_numpy(inp["dout"]))
+    pc.check(out.detach().numpy(), case, "out", "oracle fp32")
+    pc.check(feat.grad.numpy(), case, "dfeat", "oracle autograd fp32")
+    if case in pc.G_CASES:
+        pc.check(ora.filters.grad.numpy(), case, "dfilters", "oracle autograd fp32")
+
+
+@pytest.mark.parametrize("case", ["f3", "f5"])
+def test_contconv_pin_sees_a_swapped_edge_index_and_a_negated_relative_position(case):
+    """The two misreadings of forward the fixtures exist to catch -- aggregating at edge_index[1] and pos[row] - pos[col] -- must
+    each FAIL the bars (computed in fp64, so nothing but the misreading separates them from the reference's run)."""
+    import contconv_pin_cases as pc
+    inp = pc.checked_inputs(case)
+    ora = _pin_oracle(case, inp, torch.float64)
+    pos, feat, ei = (torch.from_numpy(inp[k]) for k in ("pos", "feat", "edge_index"))
+    with torch.no_grad():
+        right = ora(pos.double(), feat.double(), ei, edge_block=1024).numpy()
+        swapped = ora(pos.double(), feat.double(), ei[[1, 0]], edge_block=1024).numpy()
+        negated = ora(-pos.double(), feat.double(), ei, edge_block=1024).numpy()
+    assert max(pc.ratios(right, case)[:2]) <= pc.FACTOR
+    for wrong in (swapped, negated):
+        qg, qr, g, r = pc.ratios(wrong, case)
+        assert qg > pc.FACTOR and qr > pc.FACTOR and g > pc.TOL and r > 10 * pc.TOL, (qg, qr, g, r)

@@ -370,6 +370,47 @@ def test_contconv_layer_gradients_match_oracle(agg, D, I, O, gpu_device):
     assert torch.equal(g1, layer.filters.grad) or global_rel(g1.cpu(), layer.filters.grad.cpu()) < 1e-6
 
 
+@pytest.mark.parametrize("case", ["g0", "g1", "g2", "f2"])
+def test_contconv_training_paths_reproduce_the_reference_run_and_its_autograd(case, gpu_device):
+    """The training forward and backward of one layer against the reference's own fp64 run of forward and its own autograd
+    on loss = (aggregate(conv_edge) * dout).sum() (tests/golden/surrogate_ref_contconv_forward_*.npz, tests/
+    contconv_pin_cases.py): on the path the layer picks (pair lists where trains_fused()) and on the binned-matrix path, on a
+    permuted edge list with duplicates and edges beyond the radius (which count in the mean). Bars: the project's, and four
+    times the reference's own fp32 error against its fp64 run."""
+    import contconv
+    import contconv_pin_cases as pc
+    n, d, i, o, agg, radius, _, _ = pc.CASES[case]
+    inp = pc.checked_inputs(case)
+    layer = contconv.ContinuousConv(i, o, d, radius=radius, agg=agg).cuda()
+    with torch.no_grad():
+        layer.filters.copy_(torch.from_numpy(inp["filters"]).cuda())
+    pos, ei = torch.from_numpy(inp["pos"]).cuda(), torch.from_numpy(inp["edge_index"]).cuda()
+    dout = torch.from_numpy(inp["dout"]).cuda()
+    picks = "fused_train" if layer.trains_fused() else "binned_train"
+    for fused in (True, False):
+        layer.use_fused = fused
+        layer.filters.grad = None
+        feat = torch.from_numpy(inp["feat"]).cuda().requires_grad_()
+        out = layer(pos, feat, edge_index=ei)
+        path = layer.last_path
+        assert path == (picks if fused else "binned_train")
+        out.backward(dout)
+        pc.check(out.detach().cpu().numpy(), case, "out", path)
+        pc.check(feat.grad.cpu().numpy(), case, "dfeat", path)
+        if case in pc.G_CASES:
+            pc.check(layer.filters.grad.cpu().numpy(), case, "dfilters", path)
+
+
+def test_contconv_pinned_cases_reach_both_training_paths(gpu_device):
+    import contconv
+    import contconv_pin_cases as pc
+    fused = {}
+    for case in pc.GRAD_CASES:
+        _, d, i, o, agg, radius, _, _ = pc.CASES[case]
+        fused[case] = contconv.ContinuousConv(i, o, d, radius=radius, agg=agg).cuda().trains_fused()
+    assert any(fused.values())       # "fused_train" occurs; "binned_train" is forced on every case by use_fused = False
+
+
 @pytest.mark.parametrize("D,I,O,n", [(6, 64, 64, 3000), (4, 128, 32, 1500), (3, 8, 128, 700)])
 def test_contconv_pair_list_backward_equals_binned_backward(D, I, O, n, gpu_device):
     """The training step on the pair lists (ag.ContConvFusedFn: fused forward, nbd_contconv_filter_grad_f32, feature
