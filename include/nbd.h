@@ -310,6 +310,43 @@ int nbd_hermite_step_f32(float* pos, float* vel, const float* acc_in, const floa
                          float* jerk_out, const float* mass, int n, double dt, float softening_sq, float g_const,
                          float* posm, void* workspace, size_t workspace_bytes, nbd_stream_t stream);
 
+/* ---- range-sharded Hermite step (csrc/direct_hermite_shard.hip): one rank of a range partition owns bodies
+ * [lo, lo + n_local) of n_total and advances them by the scheme above. The exchanged row is 8 floats,
+ * {x_p, y_p, z_p, m, vx_p, vy_p, vz_p, 0}: the predicted state and the mass, ONE all-gather per step.
+ *   send : float[send_rows][8], the rank's own rows, zero behind n_local; send_rows >= nbd_posm_padded_len(n_local)
+ *          (a ragged partition sends more rows than it owns: they are the zeros)
+ *   all  : float[nbd_posm_padded_len(n_total)][8], every rank's rows in global order, zero behind n_total
+ * A step is, in the caller's stream:
+ *   nbd_hermite_shard_predict_f32       hermite predictor of the own bodies -> send
+ *   (start the all-gather of send into all)
+ *   nbd_hermite_shard_force_local_f32   own bodies as sources (reads send only); runs while the gather is in flight
+ *   (wait for the gather)
+ *   nbd_hermite_shard_force_remote_f32  all other bodies as sources (rows [lo, lo + n_local) of `all` are never used:
+ *                                       whole 64-row chunks inside the range are not read, the rest of it is dropped by
+ *                                       select), then a launch of its own: a1, j1 = G * (fixed-order sum of every slab,
+ *                                       local ones first) and the corrector of the own rows
+ * Four launches. Any lo and n_local; n_local == 0 is a no-op returning 0; a rank that owns everything (a one-rank group)
+ * has no remote launch. Below softening_sq = 1e-24 the i == j term is dropped by index. The workspace holds the partial
+ * sums (6 floats per target and slab) between the two force calls of a step: nbd_hermite_shard_workspace_bytes, the same
+ * buffer for both. A wave's sequential fp32 chain stays <= 4096 sources. Deterministic and capturable. */
+int nbd_hermite_shard_plan(int n_total, int lo, int n_local, int* slabs_local, int* chunks_per_wave_local,
+                           int* slabs_remote, int* chunks_per_wave_remote);
+size_t nbd_hermite_shard_workspace_bytes(int n_total, int lo, int n_local);
+/* send rows [0, n_local) = the state predicted over dt from (acc, jerk) with the masses (mass: the rank's n_local), rows
+ * [n_local, send_rows) = 0. With acc and jerk both null a plain pack of (pos, vel), as nbd_hermite_pack_f32. */
+int nbd_hermite_shard_predict_f32(const float* pos, const float* vel, const float* acc, const float* jerk,
+                                  const float* mass, int n_local, double dt, float* send, int send_rows,
+                                  nbd_stream_t stream);
+int nbd_hermite_shard_force_local_f32(const float* send, int n_local, float softening_sq, void* workspace,
+                                      size_t workspace_bytes, int n_total, int lo, nbd_stream_t stream);
+/* pos non-null: the corrector -- pos, vel (n_local,3) in place from acc_in, jerk_in, dt; acc_out, jerk_out = a1, j1 at
+ * the predicted state (acc_in may alias acc_out, jerk_in may alias jerk_out). pos null: the force on its own, acc_out
+ * and jerk_out only (vel, acc_in, jerk_in and dt are not used). */
+int nbd_hermite_shard_force_remote_f32(const float* all, int n_total, const float* send, int n_local, int lo,
+                                       float softening_sq, float g_const, float* pos, float* vel, const float* acc_in,
+                                       const float* jerk_in, float* acc_out, float* jerk_out, double dt, void* workspace,
+                                       size_t workspace_bytes, nbd_stream_t stream);
+
 /* ------------------------------------------------ block-timestep Hermite integrator (csrc/direct_hermite_block.hip)
  * The scheme above with individual power-of-two steps (Makino & Aarseth 1992). One output interval dt is 2^K integer
  * ticks, K = max_level in [0, 20]. Body i keeps x, v, a, j at its last correction tick ticks[i] (int32) and a level

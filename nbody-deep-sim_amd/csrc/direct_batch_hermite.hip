@@ -98,11 +98,11 @@ __global__ __launch_bounds__(64 * kWaves, 5) void batch_accel_jerk_kernel(const 
   float* dst = ws + 2 * (size_t)sc.ws_off + (size_t)slab * 6 * n + t_base;
   const int n_valid = min(kTgtPerWG, n - t_base);
   if (eps2 < kEps2Masked)
-    accel_jerk_body<true, 2>(posm + poff, velp + poff, n, min(i0, n - 1), min(i1, n - 1), i0, i1, c_begin, c_end, eps2,
-                             lds, dst, n, n_valid);
+    accel_jerk_body<true, 2>(posm + poff, velp + poff, n, posm + poff, velp + poff, min(i0, n - 1), min(i1, n - 1), i0, i1,
+                             c_begin, c_end, eps2, lds, dst, n, n_valid);
   else
-    accel_jerk_body<false, 2>(posm + poff, velp + poff, n, min(i0, n - 1), min(i1, n - 1), i0, i1, c_begin, c_end, eps2,
-                              lds, dst, n, n_valid);
+    accel_jerk_body<false, 2>(posm + poff, velp + poff, n, posm + poff, velp + poff, min(i0, n - 1), min(i1, n - 1), i0, i1,
+                              c_begin, c_end, eps2, lds, dst, n, n_valid);
 }
 
 // One workgroup per 64 packed rows (a scene's rows are whole chunks of 64, so a block never spans two scenes): a1, j1 =

@@ -590,23 +590,6 @@ inline int check(hipError_t e) { return e == hipSuccess ? 0 : (int)e; }
 // all sources of an n_src array, split as the plan says
 SrcView full_view(int n_src, const AccelPlan& p) { return full_view(n_src, p.n_chunks, p.slabs); }
 
-// logical chunk count of "n_src sources without the indices [ex_lo, ex_hi)": whole chunks inside the
-// excluded range are hopped over, chunks that straddle one of its ends are walked with the element mask
-int excluded_view(int n_src, int ex_lo, int ex_hi, SrcView* v) {
-  const int phys = ceil_div(n_src, kChunk);
-  int c0 = ceil_div(ex_lo, kChunk), c1 = ex_hi / kChunk;      // whole chunks [c0, c1) lie inside
-  if (ex_hi >= n_src) c1 = phys;                               // the tail chunk holds padding only beyond ex_hi
-  if (c1 < c0) c1 = c0;
-  if (v) {
-    v->n_src = n_src; v->skip_c0 = c0; v->skip_cn = c1 - c0; v->ex_lo = ex_lo; v->ex_hi = ex_hi;
-    v->edge0 = (ex_lo % kChunk) ? ex_lo / kChunk : -1;
-    v->edge1 = (ex_hi % kChunk && ex_hi < n_src) ? ex_hi / kChunk : -1;
-    if (ex_hi <= ex_lo) { v->skip_c0 = phys; v->skip_cn = 0; v->edge0 = v->edge1 = -1; }
-    v->tail = (n_src % kChunk) ? n_src / kChunk : -1;
-  }
-  return ex_hi <= ex_lo ? phys : phys - (c1 - c0);
-}
-
 // force into slabs (or straight into acc_out when one slab), no finishing pass
 int launch_accel(const float* posm_src, SrcView sv, const float* posm_tgt, int n_tgt, int off,
                  float eps2, float direct_scale, float* slabs_or_acc, const AccelPlan& p,

@@ -38,7 +38,7 @@ __global__ __launch_bounds__(64 * kWaves, KU == 2 ? 6 : 5) void accel_jerk_kerne
   const int jw = blockIdx.y * kWaves + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   int c_begin, c_end;
   wave_chunk_range(jw, cpw_q, cpw_r, c_begin, c_end);
-  accel_jerk_body<MASKED, KU>(posm, velp, n, min(i0, n - 1), min(i1, n - 1), i0, i1, c_begin, c_end, eps2, lds,
+  accel_jerk_body<MASKED, KU>(posm, velp, n, posm, velp, min(i0, n - 1), min(i1, n - 1), i0, i1, c_begin, c_end, eps2, lds,
                               out + (size_t)blockIdx.y * 6 * n + t_base, n, min(kTgtPerWG, n - t_base));
 }
 

@@ -54,7 +54,7 @@ __global__ __launch_bounds__(64 * kWaves, 6) void accel_jerk_active_kernel(
   const int jw = blockIdx.y * kWaves + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   int c_begin, c_end;
   wave_chunk_range(jw, cpw_q, cpw_r, c_begin, c_end);
-  accel_jerk_body<MASKED, 2>(posm, velp, n, i0, i1, i0, i1, c_begin, c_end, eps2, lds,
+  accel_jerk_body<MASKED, 2>(posm, velp, n, posm, velp, i0, i1, i0, i1, c_begin, c_end, eps2, lds,
                              out + (size_t)blockIdx.y * 6 * n_act + t_base, n_act, min(kTgtPerWG, n_act - t_base));
 }
 

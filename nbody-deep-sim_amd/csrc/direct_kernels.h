@@ -69,6 +69,23 @@ __host__ __device__ inline SrcView full_view(int n_src, int n_chunks, int slabs)
   return v;
 }
 
+// logical chunk count of "n_src sources without the indices [ex_lo, ex_hi)": whole chunks inside the
+// excluded range are hopped over, chunks that straddle one of its ends are walked with the element mask
+inline int excluded_view(int n_src, int ex_lo, int ex_hi, SrcView* v) {
+  const int phys = ceil_div(n_src, kChunk);
+  int c0 = ceil_div(ex_lo, kChunk), c1 = ex_hi / kChunk;      // whole chunks [c0, c1) lie inside
+  if (ex_hi >= n_src) c1 = phys;                               // the tail chunk holds padding only beyond ex_hi
+  if (c1 < c0) c1 = c0;
+  if (v) {
+    v->n_src = n_src; v->skip_c0 = c0; v->skip_cn = c1 - c0; v->ex_lo = ex_lo; v->ex_hi = ex_hi;
+    v->edge0 = (ex_lo % kChunk) ? ex_lo / kChunk : -1;
+    v->edge1 = (ex_hi % kChunk && ex_hi < n_src) ? ex_hi / kChunk : -1;
+    if (ex_hi <= ex_lo) { v->skip_c0 = phys; v->skip_cn = 0; v->edge0 = v->edge1 = -1; }
+    v->tail = (n_src % kChunk) ? n_src / kChunk : -1;
+  }
+  return ex_hi <= ex_lo ? phys : phys - (c1 - c0);
+}
+
 // One source against the lane's two targets. 12 packed ops + 2 v_rsq_f32 (UNI: 11, see accel_kernel).
 template <bool MASKED, bool UNI = false>
 __device__ __forceinline__ void interact(const f4 p, const f2 xi, const f2 yi, const f2 zi,

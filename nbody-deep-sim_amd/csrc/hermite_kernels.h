@@ -1,8 +1,10 @@
 // hermite_kernels.h -- everything the Hermite translation units share (direct_hermite.hip: all targets, shared timestep;
 // direct_hermite_block.hip: an active list of targets, block timesteps; direct_batch_hermite.hip: many independent
-// systems, shared timestep per system):
+// systems, shared timestep per system; direct_hermite_shard.hip: one rank's bodies of a range partition):
 //   - the acceleration-plus-jerk wave body (accel_jerk_body: target loads, LDS-DMA chunk walk, pair loop, four-wave
-//     reduction, store) and the split of the chunks over the waves (chunk_split on the host, wave_chunk_range in a kernel);
+//     reduction, store; its compile-time parameters also give direct_hermite_shard.hip's range-sharded blocks: targets
+//     apart from the sources, 8-float rows, a skipped source range) and the split of the chunks over the waves
+//     (chunk_split on the host, wave_chunk_range in a kernel);
 //   - the O(N) arithmetic: the fp32 step constants (hermite_dt), the predictor (hermite_predict), the fixed-order slab sum
 //     (hermite_slab_sum) and the corrector (hermite_correct);
 //   - the launch plan of a force launch (JerkPlan, plan_jerk).
@@ -17,9 +19,20 @@ namespace {
 
 // One source against the lane's two targets, index-masked (softening^2 below kEps2Masked): accel_kernel's rule, only
 // j == i and the padding behind n are dropped. ja accumulates w dv, jb accumulates (r.v s^2) w dr; j = ja - 3 jb.
-__device__ __forceinline__ void jerk_pair_masked(const f4 p, const f4 q, const f2 xi, const f2 yi, const f2 zi,
+// RANGE (an edge chunk of a range-sharded walk, direct_hermite_shard.hip): the sources [ex_lo, ex_hi) are dropped too,
+// by the same select on s, and their rows are replaced by zeros before any arithmetic (a select, not a product:
+// whatever such a row holds, NaN included, never reaches a sum).
+template <bool RANGE = false>
+__device__ __forceinline__ void jerk_pair_masked(f4 p, f4 q, const f2 xi, const f2 yi, const f2 zi,
                                                  const f2 ui, const f2 vi, const f2 wi, const f2 e2, f2* acc, int j,
-                                                 int i0, int i1, int n) {
+                                                 int i0, int i1, int n, int ex_lo = 0, int ex_hi = 0) {
+  bool live = j < n;
+  if (RANGE) {
+    const bool ex = (unsigned)(j - ex_lo) < (unsigned)(ex_hi - ex_lo);
+    p = ex ? f4{0.f, 0.f, 0.f, 0.f} : p;
+    q = ex ? f4{0.f, 0.f, 0.f, 0.f} : q;
+    live = live && !ex;
+  }
   const f2 dx = f2{p.x, p.x} - xi, dy = f2{p.y, p.y} - yi, dz = f2{p.z, p.z} - zi;
   const f2 du = f2{q.x, q.x} - ui, dv = f2{q.y, q.y} - vi, dw = f2{q.z, q.z} - wi;
   f2 r2 = __builtin_elementwise_fma(dx, dx, e2);
@@ -29,7 +42,6 @@ __device__ __forceinline__ void jerk_pair_masked(const f4 p, const f4 q, const f
   rv = __builtin_elementwise_fma(dy, dv, rv);
   rv = __builtin_elementwise_fma(dz, dw, rv);
   f2 s = {__builtin_amdgcn_rsqf(r2.x), __builtin_amdgcn_rsqf(r2.y)};
-  const bool live = j < n;
   s.x = (live && j != i0) ? s.x : 0.0f;
   s.y = (live && j != i1) ? s.y : 0.0f;
   const f2 s2 = s * s;
@@ -92,20 +104,30 @@ __device__ __forceinline__ void jerk_block(const f4* __restrict__ bp, const f4* 
 }
 
 // The wave body of every acceleration-plus-jerk kernel. accel_kernel's structure: a workgroup is 4 waves on 128 targets,
-// two per lane in packed fp32 (rows r0, r1 of posm / velp; i0, i1 are the source indices the masked loop takes for the
+// two per lane in packed fp32 (rows r0, r1 of tpos / tvel; i0, i1 are the source indices the masked loop takes for the
 // lane's own); every wave streams its chunks [c_begin, c_end) of the n sources, each chunk = 64 positions + 64 velocities
 // (2 KiB) by LDS-DMA, double-buffered behind a counted vmcnt; the 4 waves' partials are reduced through LDS in wave order
 // into one coalesced store of 6 x n_valid floats: dst[comp * stride + t], t < n_valid. lds: the workgroup's
 // f4[kWaves * 4 * kChunk] (16 KiB), [wave][buffer][pos | vel][64] staging; after its last chunk a wave puts its [12][64]
 // partials into its own part.
-template <bool MASKED, int KU>
-__device__ __forceinline__ void accel_jerk_body(const f4* __restrict__ posm, const f4* __restrict__ velp, int n, int r0,
+// Compile-time shape, all defaults = the un-sharded kernels (targets and sources in the same two arrays):
+//   SS    : quads between consecutive rows of spos / svel and of tpos / tvel. 1: two arrays of float4 (posm, velp);
+//           2: one array of 8-float rows {x, y, z, m, vx, vy, vz, 0} (svel = spos + 1), the layout a range-sharded rank
+//           sends and gathers. A lane's LDS-DMA fetches its own row's quad, so the chunk lands de-interleaved in the same
+//           [pos | vel][64] staging either way and the pair loops do not know the difference.
+//   RANGE : the walk is over the view *sv (direct_kernels.h): [c_begin, c_end) are LOGICAL chunks that hop over the run of
+//           physical chunks lying wholly inside [ex_lo, ex_hi), and the (at most two) chunks that straddle an end of that
+//           range take the masked loop with the range mask; every other chunk takes the loop MASKED says.
+template <bool MASKED, int KU, int SS = 1, bool RANGE = false>
+__device__ __forceinline__ void accel_jerk_body(const f4* __restrict__ spos, const f4* __restrict__ svel, int n,
+                                                const f4* __restrict__ tpos, const f4* __restrict__ tvel, int r0,
                                                 int r1, int i0, int i1, int c_begin, int c_end, float eps2, f4* lds,
-                                                float* __restrict__ dst, int stride, int n_valid) {
+                                                float* __restrict__ dst, int stride, int n_valid,
+                                                const SrcView* sv = nullptr) {
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const f4 t0 = posm[r0], t1 = posm[r1];
-  const f4 u0 = velp[r0], u1 = velp[r1];
+  const f4 t0 = tpos[r0 * SS], t1 = tpos[r1 * SS];
+  const f4 u0 = tvel[r0 * SS], u1 = tvel[r1 * SS];
   const f2 xi = {t0.x, t1.x}, yi = {t0.y, t1.y}, zi = {t0.z, t1.z};
   const f2 ui = {u0.x, u1.x}, vi = {u0.y, u1.y}, wi = {u0.z, u1.z};
   f2 acc[9];
@@ -115,11 +137,14 @@ __device__ __forceinline__ void accel_jerk_body(const f4* __restrict__ posm, con
   asm volatile("" : "+v"(e2));  // keep eps^2 in VGPRs: an SGPR operand halves v_pk_fma issue
 
   f4* stage = &lds[wave * 4 * kChunk];
-  const f4* p_lane = posm + lane;
-  const f4* v_lane = velp + lane;
+  const f4* p_lane = spos + lane * SS;
+  const f4* v_lane = svel + lane * SS;
+  // logical -> physical chunk: hop over the skipped run
+  auto phys = [&](int c) { return RANGE ? c + (c >= sv->skip_c0 ? sv->skip_cn : 0) : c; };
   auto fetch = [&](int c, int b) {
-    __builtin_amdgcn_global_load_lds(GPTR(p_lane + (size_t)c * kChunk), LPTR(stage + b * 2 * kChunk), 16, 0, 0);
-    __builtin_amdgcn_global_load_lds(GPTR(v_lane + (size_t)c * kChunk), LPTR(stage + b * 2 * kChunk + kChunk), 16, 0, 0);
+    const size_t at = (size_t)phys(c) * (kChunk * SS);
+    __builtin_amdgcn_global_load_lds(GPTR(p_lane + at), LPTR(stage + b * 2 * kChunk), 16, 0, 0);
+    __builtin_amdgcn_global_load_lds(GPTR(v_lane + at), LPTR(stage + b * 2 * kChunk + kChunk), 16, 0, 0);
   };
   if (c_begin < c_end) fetch(c_begin, 0);
   for (int c = c_begin; c < c_end; ++c) {
@@ -132,8 +157,14 @@ __device__ __forceinline__ void accel_jerk_body(const f4* __restrict__ posm, con
     }
     const f4* bp = stage + b * 2 * kChunk;
     const f4* bv = bp + kChunk;
-    if (MASKED) {
-      const int j0 = c * kChunk;
+    const int pc = phys(c);
+    if (RANGE && (pc == sv->edge0 || pc == sv->edge1)) {
+      const int j0 = pc * kChunk;
+#pragma unroll 2
+      for (int j = 0; j < kChunk; ++j)
+        jerk_pair_masked<true>(bp[j], bv[j], xi, yi, zi, ui, vi, wi, e2, acc, j0 + j, i0, i1, n, sv->ex_lo, sv->ex_hi);
+    } else if (MASKED) {
+      const int j0 = pc * kChunk;
 #pragma unroll 2
       for (int j = 0; j < kChunk; ++j)
         jerk_pair_masked(bp[j], bv[j], xi, yi, zi, ui, vi, wi, e2, acc, j0 + j, i0, i1, n);

@@ -613,33 +613,77 @@ class HermiteSimulator(BaseSimulator):
         correct  v1 = v + (a0 + a1) dt/2 + (j0 - j1) dt^2/12,  x1 = x + (v + v1) dt/2 + (a0 - a1) dt^2/12
     One acceleration + jerk evaluation per step (csrc/direct_hermite.hip), fp32 state. `jerks` (n,3) is public next to
     `accelerations`; both hold the values evaluated at the last predicted state (PEC) and are rebound by step(). No
-    range-sharded form (process_group is refused) and no equal-mass specialisation."""
+    equal-mass specialisation.
+
+    With `process_group=` the bodies are range-sharded as for LeapFrogSimulator (csrc/direct_hermite_shard.hip; DESIGN.md
+    §8): positions, velocities, accelerations and jerks hold the rank's rows [lo, hi), `gather()` assembles any of them,
+    and a step is predict + pack of the own bodies -> ONE all-gather of 8-float rows {x_p, m, v_p, 0} in flight || own x
+    own block -> own x others block + slab sum + corrector. Eager only: there is no captured form of the sharded step."""
 
     def __init__(self, *, positions, velocities, masses, g_const: float = 1.0, softening: float = 0.1,
                  dt: float = 0.01, calc_energy: bool = True, device: str = None, process_group=None,
                  calc_invariants: bool = False):
-        if process_group is not None:
-            raise ValueError("HermiteSimulator: there is no range-sharded Hermite step; process_group is not supported")
+        if process_group is not None and not (torch.distributed.is_available() and
+                                              isinstance(process_group, torch.distributed.ProcessGroup)):
+            raise ValueError("HermiteSimulator: process_group must be a torch.distributed process group, got "
+                             f"{type(process_group).__name__}")
         self.jerks = None
         super().__init__(positions=positions, velocities=velocities, masses=masses, g_const=g_const,
                          softening=softening, dt=dt, calc_energy=calc_energy, device=device,
-                         calc_invariants=calc_invariants)
-        self._velp = direct.alloc_posm(self.n, self.device)
-        self._hws = direct.hermite_workspace(max(self.n, 1), self.device)
+                         process_group=process_group, calc_invariants=calc_invariants)
+        if not self._sharded:
+            self._velp = direct.alloc_posm(self.n, self.device)
+            self._hws = direct.hermite_workspace(max(self.n, 1), self.device)
+        else:
+            # the rank's own predicted rows: source of its local block and send buffer of the gather (max_count rows so
+            # that ragged shards send equal, zero-padded pieces); the gathered rows of all bodies; the partial sums
+            part = self.part
+            self._rows_local = direct.alloc_hermite_rows(part.max_count, self.device)
+            self._rows_all = direct.alloc_hermite_rows(self.n, self.device)
+            self._hws = direct.hermite_shard_workspace(self.n, part.lo, part.n_local, self.device) \
+                if part.n_local else None
+            self._hgather = nbd_dist.RowGather(part, direct.HERMITE_ROW, torch.float32, self.device, process_group,
+                                               collective=True)
         self.accelerations, self.jerks = self.compute_accelerations_and_jerks()
 
     def compute_accelerations_and_jerks(self):
-        """(a, j) of the current state as new (n,3) tensors: a_i = G sum_{j!=i} m_j r_ij s^3,
-        j_i = G sum_{j!=i} m_j (v_ij s^3 - 3 (r_ij.v_ij) s^5 r_ij), s = (|r_ij|^2 + eps^2)^(-1/2)."""
+        """(a, j) of the current state as new (n,3) tensors -- (n_local,3), the rank's rows, when sharded:
+        a_i = G sum_{j!=i} m_j r_ij s^3, j_i = G sum_{j!=i} m_j (v_ij s^3 - 3 (r_ij.v_ij) s^5 r_ij),
+        s = (|r_ij|^2 + eps^2)^(-1/2)."""
         if self.n == 0:
             z = torch.zeros((0, 3), dtype=torch.float32, device=self.device)
             return z, z.clone()
+        if self._sharded:
+            return self._sharded_launches(None, None)
         direct.hermite_pack(self.positions, self.velocities, self.masses, self._posm, self._velp)
         return direct.accel_jerk(self._posm, self._velp, self.n, self._eps2, self._g, workspace=self._hws)
+
+    def _sharded_launches(self, acc, jerk):
+        """The range-sharded launches from the carried (acc, jerk): predict + pack of the own bodies, the all-gather in
+        flight during the own x own block, then the own x others block, the slab sum and the corrector; returns the new
+        (acc, jerk). With acc and jerk None the force of the current state on its own (a plain pack, no corrector)."""
+        p = self.part
+        n_loc, rows = p.n_local, self._rows_local
+        new_acc = torch.empty((n_loc, 3), dtype=torch.float32, device=self.device)
+        new_jerk = torch.empty((n_loc, 3), dtype=torch.float32, device=self.device)
+        direct.hermite_shard_predict(self.positions, self.velocities, self._mass_local, rows, acc, jerk, self.dt)
+        handle = self._hgather.start(rows, self._rows_all)
+        if n_loc:
+            direct.hermite_shard_force_local(rows, n_loc, self.n, p.lo, self._eps2, self._hws)
+        self._hgather.finish(handle, self._rows_all)
+        if n_loc:
+            step = {} if acc is None else dict(pos=self.positions, vel=self.velocities, acc_in=acc, jerk_in=jerk,
+                                               dt=self.dt)
+            direct.hermite_shard_force_remote(self._rows_all, self.n, rows, n_loc, p.lo, self._eps2, self._g, new_acc,
+                                              new_jerk, self._hws, **step)
+        return new_acc, new_jerk
 
     def step(self):
         """One predictor-corrector step: positions and velocities in place, `accelerations` and `jerks` rebound."""
         if self.n == 0:
+            return
+        if self._sharded:
+            self.accelerations, self.jerks = self._sharded_launches(self.accelerations, self.jerks)
             return
         new_acc = torch.empty_like(self.accelerations)
         new_jerk = torch.empty_like(self.jerks)
@@ -676,7 +720,7 @@ class BlockHermiteSimulator(HermiteSimulator):
                  dt: float = 0.01, calc_energy: bool = True, device: str = None, process_group=None,
                  eta: float = 0.02, max_level: int = 10, calc_invariants: bool = False):
         if process_group is not None:
-            raise ValueError("BlockHermiteSimulator: there is no range-sharded Hermite step; process_group is not "
+            raise ValueError("BlockHermiteSimulator: there is no range-sharded block-timestep step; process_group is not "
                              "supported")
         super().__init__(positions=positions, velocities=velocities, masses=masses, g_const=g_const,
                          softening=softening, dt=dt, calc_energy=calc_energy, device=device,

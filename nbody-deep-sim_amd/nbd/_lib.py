@@ -211,6 +211,16 @@ SIGNATURES = {
                                    c_int, c_void_p]),
     "nbd_hermite_step_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
                                      c_double, c_float, c_float, c_void_p, c_void_p, c_size_t, c_void_p]),
+    # --- range-sharded Hermite step (csrc/direct_hermite_shard.hip)
+    "nbd_hermite_shard_plan": (c_int, [c_int, c_int, c_int, POINTER(c_int), POINTER(c_int), POINTER(c_int),
+                                       POINTER(c_int)]),
+    "nbd_hermite_shard_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "nbd_hermite_shard_predict_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_double,
+                                              c_void_p, c_int, c_void_p]),
+    "nbd_hermite_shard_force_local_f32": (c_int, [c_void_p, c_int, c_float, c_void_p, c_size_t, c_int, c_int, c_void_p]),
+    "nbd_hermite_shard_force_remote_f32": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_float, c_float, c_void_p,
+                                                   c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_void_p,
+                                                   c_size_t, c_void_p]),
     # --- block-timestep Hermite integrator (csrc/direct_hermite_block.hip)
     "nbd_hblock_workspace_bytes": (c_size_t, [c_int]),
     "nbd_hblock_init_levels": (c_int, [c_void_p, c_void_p, c_int, c_double, c_double, c_int, c_void_p, c_void_p,

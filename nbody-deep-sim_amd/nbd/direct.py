@@ -373,6 +373,84 @@ def hermite_step(pos, vel, acc_in, jerk_in, acc_out, jerk_out, mass, dt: float, 
             workspace.data_ptr(), _nbytes(workspace), _lib.current_stream(pos.device)), "nbd_hermite_step_f32")
 
 
+# ------------------------------------------------------ range-sharded Hermite step (csrc/direct_hermite_shard.hip)
+HERMITE_ROW = 8                 # floats per exchanged row: {x_p, y_p, z_p, m, vx_p, vy_p, vz_p, 0}
+
+
+def alloc_hermite_rows(n: int, device) -> torch.Tensor:
+    """Zeroed (padded_len(n), 8) rows: a rank's send buffer, or the gathered array of all n bodies."""
+    return torch.zeros((padded_len(n), HERMITE_ROW), dtype=torch.float32, device=device)
+
+
+def hermite_shard_plan(n_total: int, lo: int, n_local: int) -> dict:
+    a, b, c, d = ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    _lib.check(_lib.lib().nbd_hermite_shard_plan(n_total, lo, n_local, a, b, c, d), "nbd_hermite_shard_plan")
+    return {"slabs_local": a.value, "chunks_per_wave_local": b.value, "slabs_remote": c.value,
+            "chunks_per_wave_remote": d.value}
+
+
+def hermite_shard_workspace(n_total: int, lo: int, n_local: int, device) -> torch.Tensor:
+    return alloc_bytes(_lib.lib().nbd_hermite_shard_workspace_bytes(n_total, lo, n_local), device)
+
+
+def _chk_rows(t: torch.Tensor, n: int, name: str):
+    """An array of 8-float rows that holds at least padded_len(n) of them."""
+    _chk(t, None, name)
+    if t.dim() != 2 or t.shape[1] != HERMITE_ROW or t.shape[0] < padded_len(n):
+        raise _lib.NbdError(f"{name}: need >= {padded_len(n)} rows of {HERMITE_ROW}, got {tuple(t.shape)}")
+
+
+def hermite_shard_predict(pos, vel, mass, send, acc=None, jerk=None, dt: float = 0.0) -> None:
+    """First launch of the sharded Hermite step: send[:n_local] = {x_p, m, v_p, 0} of the rank's bodies predicted over dt
+    from (acc, jerk) -- a plain pack of (pos, vel) when both are None -- and zeros in every row behind n_local."""
+    n = pos.shape[0]
+    _chk(pos, (n, 3), "pos"); _chk(vel, (n, 3), "vel"); _chk(mass, (n,), "mass")
+    _chk_rows(send, n, "send")
+    if (acc is None) != (jerk is None):
+        raise _lib.NbdError("hermite_shard_predict: give both acc and jerk, or neither")
+    if acc is not None:
+        _chk(acc, (n, 3), "acc"); _chk(jerk, (n, 3), "jerk")
+    with _lib.on_device(send.device):
+        _lib.check(_lib.lib().nbd_hermite_shard_predict_f32(
+            pos.data_ptr(), vel.data_ptr(), _lib.ptr(acc), _lib.ptr(jerk), mass.data_ptr(), n, float(dt),
+            send.data_ptr(), send.shape[0], _lib.current_stream(send.device)), "nbd_hermite_shard_predict_f32")
+
+
+def hermite_shard_force_local(send: torch.Tensor, n_local: int, n_total: int, lo: int, softening_sq: float,
+                              workspace: torch.Tensor) -> None:
+    """Second launch: acceleration + jerk partial sums of the own bodies under the own bodies (reads `send` only, so it
+    runs while the all-gather is in flight)."""
+    _chk_rows(send, n_local, "send")
+    with _lib.on_device(send.device):
+        _lib.check(_lib.lib().nbd_hermite_shard_force_local_f32(
+            send.data_ptr(), n_local, float(softening_sq), workspace.data_ptr(), _nbytes(workspace), n_total, lo,
+            _lib.current_stream(send.device)), "nbd_hermite_shard_force_local_f32")
+
+
+def hermite_shard_force_remote(rows_all: torch.Tensor, n_total: int, send: torch.Tensor, n_local: int, lo: int,
+                               softening_sq: float, g_const: float, acc_out: torch.Tensor, jerk_out: torch.Tensor,
+                               workspace: torch.Tensor, pos=None, vel=None, acc_in=None, jerk_in=None,
+                               dt: float = 0.0) -> None:
+    """Third and fourth launch: every other body of the gathered rows as a source, then a1, j1 = G * sum(slabs) into
+    acc_out, jerk_out. With pos, vel, acc_in, jerk_in and dt also the corrector of the own rows (pos, vel in place;
+    acc_out may be acc_in and jerk_out jerk_in); with none of them the force on its own."""
+    _chk_rows(rows_all, n_total, "rows_all")
+    _chk_rows(send, n_local, "send")
+    _chk(acc_out, (n_local, 3), "acc_out"); _chk(jerk_out, (n_local, 3), "jerk_out")
+    step = (pos, vel, acc_in, jerk_in)
+    if any(t is None for t in step) != all(t is None for t in step):
+        raise _lib.NbdError("hermite_shard_force_remote: give pos, vel, acc_in and jerk_in, or none of them")
+    if pos is not None:
+        for t, nm in zip(step, ("pos", "vel", "acc_in", "jerk_in")):
+            _chk(t, (n_local, 3), nm)
+    with _lib.on_device(rows_all.device):
+        _lib.check(_lib.lib().nbd_hermite_shard_force_remote_f32(
+            rows_all.data_ptr(), n_total, send.data_ptr(), n_local, lo, float(softening_sq), float(g_const),
+            _lib.ptr(pos), _lib.ptr(vel), _lib.ptr(acc_in), _lib.ptr(jerk_in), acc_out.data_ptr(), jerk_out.data_ptr(),
+            float(dt), workspace.data_ptr(), _nbytes(workspace), _lib.current_stream(rows_all.device)),
+            "nbd_hermite_shard_force_remote_f32")
+
+
 # ---------------------------------------------------- block-timestep Hermite integrator (csrc/direct_hermite_block.hip)
 HBLOCK_SCHED_INTS = 32          # NBD_HBLOCK_SCHED_INTS: {t_next, n_act, clamped, ...} of the block schedule
 
