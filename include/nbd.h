@@ -347,6 +347,45 @@ int nbd_hermite_shard_force_remote_f32(const float* all, int n_total, const floa
                                        const float* jerk_in, float* acc_out, float* jerk_out, double dt, void* workspace,
                                        size_t workspace_bytes, nbd_stream_t stream);
 
+/* ---- double-precision Hermite (csrc/direct_hermite_f64.hip): the step of nbd_hermite_step_f32 and the diagnostics of a
+ * system with fp64 state, fp64 scalars and fp64 pair arithmetic throughout (the reciprocal square root is v_rsq_f64
+ * refined in fp64 to about 1 ulp; the step constants are the doubles formed from dt). An extension, used only when asked
+ * for; the fp32 entries are untouched by it. The packed sources are rows of 4 doubles, 32-byte aligned:
+ *   posd : double[nbd_posm_padded_len(n)][4] = {x, y, z, m}, veld : the same shape = {vx, vy, vz, 0}, zero rows behind n.
+ * i == j is dropped by index below softening_sq = 1e-24 and in the chunk that holds the targets' own rows, elsewhere by
+ * the term being an exact zero; a massless body is a valid source and target. Deterministic (fixed-order sums, no
+ * atomics; the workspace may hold anything on entry) and capturable (no memsets, no host syncs).
+ * Workspace of every entry: nbd_hermite_f64_workspace_bytes(n), 8-byte aligned (6 doubles per body and slab). */
+size_t nbd_hermite_f64_workspace_bytes(int n);
+/* The launch geometry at n bodies: groups of 64 targets, source slabs, the largest chunk count of a wave. */
+int nbd_hermite_f64_plan(int n, int* groups, int* slabs, int* chunks_per_wave);
+/* posd = {x_p, m}, veld = {v_p, 0}: the state predicted over dt from (acc, jerk), or a plain pack of (pos, vel) when both
+ * are null. pos, vel, acc, jerk: double (n,3); mass: double (n). */
+int nbd_hermite_f64_pack(const double* pos, const double* vel, const double* acc, const double* jerk, const double* mass,
+                         int n, double dt, double* posd, double* veld, nbd_stream_t stream);
+/* The force alone: acc_out and jerk_out, double (n,3), of all n bodies of posd / veld. slabs: 0 for the plan's split of
+ * the sources, or an explicit slab count in [1, 64] (tests: it sets how many chunks a wave walks; the workspace then
+ * needs slabs * 6 * n doubles). */
+int nbd_accel_jerk_f64(const double* posd, const double* veld, int n, double softening_sq, double g_const,
+                       double* acc_out, double* jerk_out, void* workspace, size_t workspace_bytes, int slabs,
+                       nbd_stream_t stream);
+/* One step, three launches, as nbd_hermite_step_f32: pos, vel in place; acc_out, jerk_out = a1, j1 at the predicted state
+ * (acc_in may alias acc_out, jerk_in may alias jerk_out); posd = {x1, m}; veld is scratch. */
+int nbd_hermite_step_f64(double* pos, double* vel, const double* acc_in, const double* jerk_in, double* acc_out,
+                         double* jerk_out, const double* mass, int n, double dt, double softening_sq, double g_const,
+                         double* posd, double* veld, void* workspace, size_t workspace_bytes, nbd_stream_t stream);
+/* out_uk = {U, K} in nbd_energy_f32's (the reference's) convention, U = sum_{i<j} -G m_i m_j / (|r_ij| + softening),
+ * K = sum 1/2 m |v|^2, from posd and vel double (n,3). n = 0 gives {0, 0}. */
+int nbd_energy_f64(const double* posd, const double* vel, int n, double softening, double g_const, double* out_uk,
+                   void* workspace, size_t workspace_bytes, nbd_stream_t stream);
+/* phi_out[i] = -G sum_{j != i} m_j (|r_ij|^2 + softening_sq)^(-1/2), double (n): nbd_potential_f32's potential. */
+int nbd_potential_f64(const double* posd, int n, double softening_sq, double g_const, double* phi_out, void* workspace,
+                      size_t workspace_bytes, nbd_stream_t stream);
+/* nbd_invariants_f64's row {M, C (3), P (3), L (3), K, U, E, Q, 0, 0} from an fp64 state (pos, vel double (n,3), mass
+ * double (n)) and its potentials phi (nbd_potential_f64): the same sums in the same order. */
+int nbd_invariants_state_f64(const double* pos, const double* vel, const double* mass, const double* phi, int n,
+                             double* out_row, nbd_stream_t stream);
+
 /* ------------------------------------------------ block-timestep Hermite integrator (csrc/direct_hermite_block.hip)
  * The scheme above with individual power-of-two steps (Makino & Aarseth 1992). One output interval dt is 2^K integer
  * ticks, K = max_level in [0, 20]. Body i keeps x, v, a, j at its last correction tick ticks[i] (int32) and a level

@@ -10,8 +10,8 @@
 // potential_kernel: potential_body of direct_kernels.h (accel_body's geometry and LDS-DMA chunk walk; per pair 5 packed
 // fp32 ops + 2 v_rsq_f32; fp32 sums of at most one 64-source chunk, everything above that in fp64) into one fp64 slab per
 // source split; potential_finish_kernel adds the slabs in slab order and applies -G in fp64. invariants_kernel: one
-// workgroup per system, every product formed in fp64 from the fp32 state, thread-strided sums and a fixed shuffle / LDS
-// tree. The batched kernels are a prologue that reads the scene record (direct_batch_plan.h) and the same bodies: a scene
+// workgroup per system (invariants_body of direct_kernels.h), every product formed in fp64 from the fp32 state,
+// thread-strided sums and a fixed shuffle / LDS tree. The batched kernels are a prologue that reads the scene record (direct_batch_plan.h) and the same bodies: a scene
 // of a batch is bit-identical to the same system alone. No atomics, no memsets, no host syncs: deterministic, capturable.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -21,10 +21,6 @@
 #include "direct_kernels.h"
 
 namespace {
-
-constexpr int kInvThreads = 1024;            // one workgroup per system: 16 waves
-constexpr int kInvWaves = kInvThreads / 64;
-constexpr int kInvSums = 12;                 // M, m x (3), m v (3), m x cross v (3), K, sum m phi
 
 __global__ __launch_bounds__(64 * kWaves) void potential_kernel(const f4* __restrict__ src, int n_src, int n_chunks,
                                                                 int all_masked, const f4* __restrict__ tgt, int n_tgt,
@@ -48,56 +44,23 @@ __global__ __launch_bounds__(256) void potential_finish_kernel(const double* __r
   if (i < n_tgt) phi[i] = finish_phi(slabs + i, n_slabs, (size_t)n_tgt, g);
 }
 
-// The body of the invariants kernels: the workgroup's 1024 threads over the n bodies of one system (posm rows, vel (n,3),
-// phi (n)); row = {M, C (3), P (3), L (3), K, U, E, Q, 0, 0}. Thread t sums bodies t, t + 1024, ... in index order, then
-// a shuffle tree per wave and the 16 wave sums in wave order. C = 0 when M = 0, Q = 0 when U = 0.
-__device__ __forceinline__ void invariants_body(const f4* __restrict__ posm, const float* __restrict__ vel,
-                                                const double* __restrict__ phi, int n, double* __restrict__ row,
-                                                double (*red)[kInvWaves]) {
-  double a[kInvSums];
-#pragma unroll
-  for (int q = 0; q < kInvSums; ++q) a[q] = 0.0;
-  for (int i = threadIdx.x; i < n; i += kInvThreads) {
+// A body of the fp32 state for invariants_body (direct_kernels.h): posm rows and vel (n,3), promoted to fp64.
+struct PackedF32State {
+  const f4* __restrict__ posm;
+  const float* __restrict__ vel;
+  __device__ __forceinline__ void operator()(int i, double& m, double* x, double* v) const {
     const f4 p = posm[i];
-    const double m = p.w, x = p.x, y = p.y, z = p.z;
-    const double vx = vel[3 * (size_t)i], vy = vel[3 * (size_t)i + 1], vz = vel[3 * (size_t)i + 2];
-    a[0] += m;
-    a[1] += m * x; a[2] += m * y; a[3] += m * z;
-    a[4] += m * vx; a[5] += m * vy; a[6] += m * vz;
-    a[7] += m * (y * vz - z * vy); a[8] += m * (z * vx - x * vz); a[9] += m * (x * vy - y * vx);
-    a[10] += 0.5 * m * ((vx * vx + vy * vy) + vz * vz);
-    a[11] += m * phi[i];
+    m = p.w; x[0] = p.x; x[1] = p.y; x[2] = p.z;
+    v[0] = vel[3 * (size_t)i]; v[1] = vel[3 * (size_t)i + 1]; v[2] = vel[3 * (size_t)i + 2];
   }
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int q = 0; q < kInvSums; ++q) {
-    for (int off = 32; off > 0; off >>= 1) a[q] += __shfl_down(a[q], off);
-    if (lane == 0) red[q][wave] = a[q];
-  }
-  __syncthreads();
-  if (threadIdx.x < kInvSums) {
-    double s = red[threadIdx.x][0];
-    for (int w = 1; w < kInvWaves; ++w) s += red[threadIdx.x][w];
-    red[threadIdx.x][0] = s;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const double M = red[0][0], K = red[10][0], U = 0.5 * red[11][0];
-    row[0] = M;
-    for (int q = 1; q <= 3; ++q) row[q] = M != 0.0 ? red[q][0] / M : 0.0;
-    for (int q = 4; q <= 9; ++q) row[q] = red[q][0];
-    row[10] = K; row[11] = U; row[12] = K + U;
-    row[13] = U != 0.0 ? -2.0 * K / U : 0.0;
-    row[14] = 0.0; row[15] = 0.0;
-  }
-}
+};
 
 __global__ __launch_bounds__(kInvThreads) void invariants_kernel(const f4* __restrict__ posm,
                                                                  const float* __restrict__ vel,
                                                                  const double* __restrict__ phi, int n,
                                                                  double* __restrict__ row) {
   __shared__ double red[kInvSums][kInvWaves];
-  invariants_body(posm, vel, phi, n, row, red);
+  invariants_body(PackedF32State{posm, vel}, phi, n, row, red);
 }
 
 // ---- the batched forms: the scene's geometry from its record, then the same bodies
@@ -143,7 +106,8 @@ __global__ __launch_bounds__(kInvThreads) void batch_invariants_kernel(const Sce
                                                                        double* __restrict__ rows) {
   __shared__ double red[kInvSums][kInvWaves];
   const SceneRec sc = load_scene(scenes, blockIdx.x);
-  invariants_body(posm + sc.poff, vel + (size_t)sc.off * 3, phi + sc.off, sc.n, rows + (size_t)blockIdx.x * 16, red);
+  invariants_body(PackedF32State{posm + sc.poff, vel + (size_t)sc.off * 3}, phi + sc.off, sc.n,
+                  rows + (size_t)blockIdx.x * 16, red);
 }
 
 inline int potential_slabs(int n_src, int n_tgt) {

@@ -1,0 +1,565 @@
+// direct_hermite_f64.hip -- the double-precision form of direct_hermite.hip's shared-timestep 4th-order Hermite step and of
+// the diagnostics that go with it, for gfx950 (MI355X). An extension: the reference is fp32 only, and so is every other
+// unit of this library; nothing here is reached unless the caller asks for float64. C-ABI: the nbd_*_f64 entries of
+// include/nbd.h under "double-precision Hermite"; Python: galaxify.simulation.HermiteSimulator(dtype=torch.float64).
+//
+// State, scalars, pair arithmetic and every sum are fp64; there is no fp32 intermediate anywhere. The sources are two
+// arrays of 32-byte rows, posd = {x, y, z, m} and veld = {vx, vy, vz, 0}, zero rows behind n up to a multiple of 64.
+//
+// One wave body (walk_f64) for all three O(N^2) sums, parametrised by the pair functor -- acceleration + jerk
+// (AccelJerkPair), the Plummer potential of the force's softening (PotentialPair), the reference's pair energy
+// -m_i m_j / (|r| + eps) (EnergyPair). The structure is the fp32 units' (accel_jerk_body, hermite_kernels.h): a workgroup
+// is 4 waves on the same 64 targets, ONE per lane (there is no packed fp64 arithmetic to fill with a second one); every
+// wave streams its own chunks of 64 sources through LDS by LDS-DMA, double-buffered behind a counted vmcnt; the chunks are
+// split over slabs x 4 waves by the balanced split (chunk_split / wave_chunk_range); the four waves' partials are added
+// through LDS in wave order, the slabs by a finishing launch in slab order. No atomics, no memsets, no host syncs:
+// deterministic run to run with a workspace that may hold anything, and capturable.
+//
+// The reciprocal square root: v_rsq_f64 as the seed -- its input range is all of fp64, so no separation or softening has
+// to fit the fp32 exponent range as it would for a v_rsq_f32 seed -- refined by one third-order and one second-order
+// Newton step on the fma residual 1 - x y^2 (rsqrt_f64). The second step squares whatever the first leaves, so the result
+// is good to the rounding of its last two operations (about 1 ulp) for any seed better than 2^-10.
+//
+// One step is three launches, as in fp32 (PEC form; a0, j0 carried):
+//   predict : hermite_predict<double> -> posd = {x_p, m}, veld = {v_p, 0}
+//   evaluate: accel_jerk_f64_kernel -> double[slabs][6][n] partial sums (unscaled)
+//   correct : the slabs in slab order, a1 = G sum, j1 = G sum, hermite_correct<double>, posd = {x1, m}
+// The predictor, the corrector and the step constants are hermite_kernels.h's templates at T = double: the step constants
+// are the five doubles formed from dt, never rounded to fp32.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "../../include/nbd.h"
+#include "direct_kernels.h"
+#include "hermite_kernels.h"
+
+namespace {
+
+typedef double d4 __attribute__((ext_vector_type(4)));
+
+constexpr int kTgtF64 = 64;                      // targets per workgroup: one per lane, = one source chunk
+constexpr int kRowQuads = 2;                     // 16-byte LDS-DMA pieces per 32-byte row
+constexpr int kChunkQuads = kChunk * kRowQuads;  // 128 quads = 2 KiB per chunk and array
+constexpr double kEps2MaskedF64 = 1e-24;         // the fp32 kernels' rule (kEps2Masked): below it i == j goes by index
+constexpr int kTargetWGs = 1024;                 // ~4 workgroups per CU (32 KiB of LDS each: at most 5 fit)
+constexpr int kSumThreads = 1024;                // the one-workgroup sums (energy_finish): 16 waves
+constexpr int kSumWaves = kSumThreads / 64;
+
+inline bool misaligned32(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 31) != 0; }
+inline bool misaligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7) != 0; }
+
+// x^(-1/2) to about 1 ulp. y0 = v_rsq_f64 (a compiler builtin: hipcc pads the transcendental -> VALU wait state for its
+// consumers). With h = 1 - x y^2 formed by one fma from the rounded x y (its absolute error is 2^-53, and h is what the
+// correction is proportional to): y1 = y0 (1 + h/2 + 3 h^2/8) leaves O(h^3), y2 = y1 (1 + h/2) squares that.
+__device__ __forceinline__ double rsqrt_f64(const double x) {
+  const double y0 = __builtin_amdgcn_rsq(x);
+  double t = x * y0;
+  double h = __builtin_fma(-t, y0, 1.0);
+  const double y1 = __builtin_fma(y0 * h, __builtin_fma(0.375, h, 0.5), y0);
+  t = x * y1;
+  h = __builtin_fma(-t, y1, 1.0);
+  return __builtin_fma(0.5 * y1, h, y1);
+}
+
+// ---- the pair functors. A functor holds its lane's target and partial sums; pair<MASKED>(p, q, j) adds source j (row p
+// of posd, row q of veld where kVel) -- MASKED: exclusions by index, else by the arithmetic; out(k) is partial sum k of kOut.
+
+// a_i = sum_j m_j r_ij s^3, j_i = sum_j m_j (v_ij s^3 - 3 (r_ij.v_ij) s^5 r_ij), s = (|r_ij|^2 + eps^2)^(-1/2): the
+// operations of jerk_pair_masked / jerk_block (hermite_kernels.h) one for one. acc[3..5] accumulates w dv, acc[6..8]
+// (r.v s^2) w dr; j = acc[3..5] - 3 acc[6..8]. MASKED drops j == i and the padding behind n by a select on s (after the
+// refinement: whatever the dropped r^2 gave, NaN included, never reaches a sum). Un-masked, i == j and a padding row add
+// exact zeros: dr = dv = 0 resp. m = 0, with s finite because eps^2 >= kEps2MaskedF64.
+struct AccelJerkPair {
+  static constexpr bool kVel = true;
+  static constexpr int kOut = 6;
+  double xi, yi, zi, ui, vi, wi, e2;
+  double acc[9];
+  int i, n;
+
+  __device__ __forceinline__ AccelJerkPair(const d4 tp, const d4 tv, double eps2, int i_, int n_)
+      : xi(tp.x), yi(tp.y), zi(tp.z), ui(tv.x), vi(tv.y), wi(tv.z), e2(eps2), i(i_), n(n_) {
+#pragma unroll
+    for (int k = 0; k < 9; ++k) acc[k] = 0.0;
+  }
+
+  template <bool MASKED>
+  __device__ __forceinline__ void pair(const d4 p, const d4 q, int j) {
+    const double dx = p.x - xi, dy = p.y - yi, dz = p.z - zi;      // r_j - r_i
+    const double du = q.x - ui, dv = q.y - vi, dw = q.z - wi;
+    double r2 = __builtin_fma(dx, dx, e2);
+    r2 = __builtin_fma(dy, dy, r2);
+    r2 = __builtin_fma(dz, dz, r2);
+    double rv = dx * du;
+    rv = __builtin_fma(dy, dv, rv);
+    rv = __builtin_fma(dz, dw, rv);
+    double s = rsqrt_f64(r2);
+    if (MASKED) s = (j < n && j != i) ? s : 0.0;
+    const double s2 = s * s;
+    const double w = (s2 * s) * p.w;
+    const double c = (rv * s2) * w;
+    acc[0] = __builtin_fma(w, dx, acc[0]);
+    acc[1] = __builtin_fma(w, dy, acc[1]);
+    acc[2] = __builtin_fma(w, dz, acc[2]);
+    acc[3] = __builtin_fma(w, du, acc[3]);
+    acc[4] = __builtin_fma(w, dv, acc[4]);
+    acc[5] = __builtin_fma(w, dw, acc[5]);
+    acc[6] = __builtin_fma(c, dx, acc[6]);
+    acc[7] = __builtin_fma(c, dy, acc[7]);
+    acc[8] = __builtin_fma(c, dz, acc[8]);
+  }
+
+  __device__ __forceinline__ double out(int k) const { return k < 3 ? acc[k] : acc[k] - 3.0 * acc[k + 3]; }
+};
+
+// u_i = sum_{j != i} m_j (|r_ij|^2 + eps^2)^(-1/2): potential_pair (direct_kernels.h) in fp64. The i == j term is
+// m_i / eps, never a zero: the chunk that holds the group's own indices is always walked MASKED.
+struct PotentialPair {
+  static constexpr bool kVel = false;
+  static constexpr int kOut = 1;
+  double xi, yi, zi, e2, u;
+  int i, n;
+
+  __device__ __forceinline__ PotentialPair(const d4 tp, double eps2, int i_, int n_)
+      : xi(tp.x), yi(tp.y), zi(tp.z), e2(eps2), u(0.0), i(i_), n(n_) {}
+
+  template <bool MASKED>
+  __device__ __forceinline__ void pair(const d4 p, const d4, int j) {
+    const double dx = p.x - xi, dy = p.y - yi, dz = p.z - zi;
+    double r2 = __builtin_fma(dx, dx, e2);
+    r2 = __builtin_fma(dy, dy, r2);
+    r2 = __builtin_fma(dz, dz, r2);
+    double s = rsqrt_f64(r2);
+    if (MASKED) s = (j < n && j != i) ? s : 0.0;
+    u = __builtin_fma(p.w, s, u);
+  }
+
+  __device__ __forceinline__ double out(int) const { return u; }
+};
+
+// u_i = sum_{j > i} m_j / (|r_ij| + eps), the reference's convention (energy_pair, direct_kernels.h): the square root and
+// the quotient are the compiler's fp64 expansions (correctly rounded; |r| = 0 is an ordinary input to them). Always by
+// index (j > i and j < n): the kernel walks it MASKED in every chunk.
+struct EnergyPair {
+  static constexpr bool kVel = false;
+  static constexpr int kOut = 1;
+  double xi, yi, zi, soft, u;
+  int i, n;
+
+  __device__ __forceinline__ EnergyPair(const d4 tp, double soft_, int i_, int n_)
+      : xi(tp.x), yi(tp.y), zi(tp.z), soft(soft_), u(0.0), i(i_), n(n_) {}
+
+  template <bool MASKED>
+  __device__ __forceinline__ void pair(const d4 p, const d4, int j) {
+    const double dx = p.x - xi, dy = p.y - yi, dz = p.z - zi;
+    double d2 = dx * dx;
+    d2 = __builtin_fma(dy, dy, d2);
+    d2 = __builtin_fma(dz, dz, d2);
+    const double t = p.w / (__builtin_sqrt(d2) + soft);
+    u += (j > i && j < n) ? t : 0.0;
+  }
+
+  __device__ __forceinline__ double out(int) const { return u; }
+};
+
+// LDS of a workgroup, in 16-byte quads: [wave][buffer][pos (| vel)][128]
+template <bool VEL>
+constexpr int stage_quads() { return 2 * (VEL ? 2 : 1) * kChunkQuads; }
+
+// The wave body. The wave walks the chunks [c_begin, c_end) of posd (and veld): chunk c = rows [64 c, 64 c + 64), 2 KiB per
+// array, fetched as two 1-KiB LDS-DMA pieces (lane l brings quads l and 64 + l of the chunk, so the rows land as they lie
+// in memory), the next chunk in flight while this one is used. all_masked, or the chunk own_chunk (the one that holds the
+// group's own indices), takes pair<true>, every other chunk pair<false>. Then the 4 waves' kOut partials per lane go
+// through LDS -- a wave's staging is free after its last chunk: its loads have landed and its reads precede these writes --
+// and are added in wave order into dst[k * stride + t], t < n_valid.
+template <class Pair>
+__device__ __forceinline__ void walk_f64(Pair& pr, const d4* __restrict__ posd, const d4* __restrict__ veld, int c_begin,
+                                         int c_end, bool all_masked, int own_chunk, f4* lds, double* __restrict__ dst,
+                                         size_t stride, int n_valid) {
+  constexpr bool VEL = Pair::kVel;
+  constexpr int kArr = VEL ? 2 : 1;
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  f4* stage = &lds[wave * stage_quads<VEL>()];
+  const f4* p_lane = reinterpret_cast<const f4*>(posd) + lane;
+  const f4* v_lane = reinterpret_cast<const f4*>(veld) + lane;
+  auto fetch = [&](int c, int b) {
+    const size_t at = (size_t)c * kChunkQuads;
+    f4* to = stage + b * kArr * kChunkQuads;
+    __builtin_amdgcn_global_load_lds(GPTR(p_lane + at), LPTR(to), 16, 0, 0);
+    __builtin_amdgcn_global_load_lds(GPTR(p_lane + at + 64), LPTR(to + 64), 16, 0, 0);
+    if (VEL) {
+      __builtin_amdgcn_global_load_lds(GPTR(v_lane + at), LPTR(to + kChunkQuads), 16, 0, 0);
+      __builtin_amdgcn_global_load_lds(GPTR(v_lane + at + 64), LPTR(to + kChunkQuads + 64), 16, 0, 0);
+    }
+  };
+  if (c_begin < c_end) fetch(c_begin, 0);
+  for (int c = c_begin; c < c_end; ++c) {
+    const int b = (c - c_begin) & 1;
+    if (c + 1 < c_end) {
+      fetch(c + 1, b ^ 1);
+      // chunk c has landed, c + 1 (2 loads per array) in flight
+      if (VEL) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+      else asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
+    } else {
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
+    const d4* bp = reinterpret_cast<const d4*>(stage + b * kArr * kChunkQuads);
+    const d4* bv = VEL ? bp + kChunk : bp;
+    const int j0 = c * kChunk;
+    if (all_masked || c == own_chunk) {
+#pragma unroll 2
+      for (int j = 0; j < kChunk; ++j) pr.template pair<true>(bp[j], bv[j], j0 + j);
+    } else {
+#pragma unroll 4
+      for (int j = 0; j < kChunk; ++j) pr.template pair<false>(bp[j], bv[j], j0 + j);
+    }
+  }
+
+  constexpr int kPart = stage_quads<VEL>() * 2;                      // doubles per wave; [k][64] in the first kOut * 64
+  static_assert(Pair::kOut * 64 <= kPart, "the partials must fit a wave's staging");
+  double* red = reinterpret_cast<double*>(lds);
+#pragma unroll
+  for (int k = 0; k < Pair::kOut; ++k) red[wave * kPart + k * 64 + lane] = pr.out(k);
+  __syncthreads();
+  for (int o = threadIdx.x; o < Pair::kOut * 64; o += 64 * kWaves) {
+    const int k = o >> 6, t = o & 63;
+    if (t >= n_valid) continue;
+    double sum = red[o];
+#pragma unroll
+    for (int w = 1; w < kWaves; ++w) sum += red[w * kPart + o];
+    dst[(size_t)k * stride + t] = sum;
+  }
+}
+
+// Acceleration + jerk of all n bodies under all n bodies: grid = (groups of 64 targets, slabs), the n_chunks source chunks
+// spread over all slabs x 4 waves to within one (cpw_q each, the first cpw_r waves one more). out: double[slab][6][n].
+__global__ __launch_bounds__(64 * kWaves) void accel_jerk_f64_kernel(const d4* __restrict__ posd,
+                                                                     const d4* __restrict__ veld, int n, int cpw_q,
+                                                                     int cpw_r, double eps2, int all_masked,
+                                                                     double* __restrict__ out) {
+  __shared__ __attribute__((aligned(32))) f4 lds[kWaves * stage_quads<true>()];
+  const int t_base = blockIdx.x * kTgtF64;
+  const int i = t_base + (threadIdx.x & 63), row = min(i, n - 1);
+  const int jw = blockIdx.y * kWaves + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  int c_begin, c_end;
+  wave_chunk_range(jw, cpw_q, cpw_r, c_begin, c_end);
+  AccelJerkPair pr(posd[row], veld[row], eps2, i, n);
+  walk_f64(pr, posd, veld, c_begin, c_end, all_masked != 0, blockIdx.x, lds,
+           out + (size_t)blockIdx.y * AccelJerkPair::kOut * n + t_base, (size_t)n, min(kTgtF64, n - t_base));
+}
+
+// The same geometry for the potential. out: double[slab][n].
+__global__ __launch_bounds__(64 * kWaves) void potential_f64_kernel(const d4* __restrict__ posd, int n, int cpw_q,
+                                                                    int cpw_r, double eps2, int all_masked,
+                                                                    double* __restrict__ out) {
+  __shared__ __attribute__((aligned(32))) f4 lds[kWaves * stage_quads<false>()];
+  const int t_base = blockIdx.x * kTgtF64;
+  const int i = t_base + (threadIdx.x & 63);
+  const int jw = blockIdx.y * kWaves + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  int c_begin, c_end;
+  wave_chunk_range(jw, cpw_q, cpw_r, c_begin, c_end);
+  PotentialPair pr(posd[min(i, n - 1)], eps2, i, n);
+  walk_f64(pr, posd, posd, c_begin, c_end, all_masked != 0, blockIdx.x, lds, out + (size_t)blockIdx.y * n + t_base,
+           (size_t)n, min(kTgtF64, n - t_base));
+}
+
+// The pair energies of the upper triangle: group g needs the chunks [g, n_chunks) only (chunk g is the group's own rows),
+// split over the slabs x 4 waves of the group by the same balanced split. out: double[slab][n].
+__global__ __launch_bounds__(64 * kWaves) void energy_f64_kernel(const d4* __restrict__ posd, int n, int n_chunks,
+                                                                 double soft, double* __restrict__ out) {
+  __shared__ __attribute__((aligned(32))) f4 lds[kWaves * stage_quads<false>()];
+  const int t_base = blockIdx.x * kTgtF64;
+  const int i = t_base + (threadIdx.x & 63);
+  const int jw = blockIdx.y * kWaves + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int span = n_chunks - (int)blockIdx.x, parts = gridDim.y * kWaves;
+  int c_begin, c_end;
+  wave_chunk_range(jw, span / parts, span % parts, c_begin, c_end);
+  EnergyPair pr(posd[min(i, n - 1)], soft, i, n);
+  walk_f64(pr, posd, posd, c_begin + blockIdx.x, c_end + blockIdx.x, true, blockIdx.x, lds,
+           out + (size_t)blockIdx.y * n + t_base, (size_t)n, min(kTgtF64, n - t_base));
+}
+
+// posd = {x_p, m}, veld = {v_p, 0} for rows [0, n_pad) (zero rows behind n). acc == nullptr: plain pack (x, v).
+__global__ __launch_bounds__(256) void predict_f64_kernel(const double* __restrict__ pos, const double* __restrict__ vel,
+                                                          const double* __restrict__ acc, const double* __restrict__ jerk,
+                                                          const double* __restrict__ mass, int n, int n_pad,
+                                                          HermiteStep<double> h, d4* __restrict__ posd,
+                                                          d4* __restrict__ veld) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n_pad) return;
+  d4 pm = {0.0, 0.0, 0.0, 0.0}, vp = {0.0, 0.0, 0.0, 0.0};
+  if (i < n) {
+    double x[3], v[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      x[k] = pos[3 * (size_t)i + k];
+      v[k] = vel[3 * (size_t)i + k];
+      if (acc) {
+        const PosVelT<double> p = hermite_predict(x[k], v[k], acc[3 * (size_t)i + k], jerk[3 * (size_t)i + k], h.dt,
+                                                  h.dt2_half, h.dt3_sixth);
+        x[k] = p.x;
+        v[k] = p.v;
+      }
+    }
+    pm = d4{x[0], x[1], x[2], mass[i]};
+    vp = d4{v[0], v[1], v[2], 0.0};
+  }
+  posd[i] = pm;
+  veld[i] = vp;
+}
+
+// One thread per body: a1 = g * (slab 0 + slab 1 + ...) in slab order, j1 likewise, from double[n_slabs][6][n].
+// pos == nullptr: write a1, j1 only (the force on its own). Else hermite_correct: reads a0, j0 (acc_in / jerk_in, which may
+// alias acc_out / jerk_out: each element is read before it is written, by the same thread), x, v; writes x1, v1, a1, j1
+// and posd = {x1, m}.
+__global__ __launch_bounds__(256) void correct_f64_kernel(const double* __restrict__ slabs, int n_slabs, int n, double g,
+                                                          HermiteStep<double> h, double* pos, double* vel,
+                                                          const double* acc_in, const double* jerk_in, double* acc_out,
+                                                          double* jerk_out, const double* __restrict__ mass,
+                                                          d4* __restrict__ posd) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  double sum[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  for (int s = 0; s < n_slabs; ++s)
+#pragma unroll
+    for (int k = 0; k < 6; ++k) sum[k] += slabs[((size_t)s * 6 + k) * n + i];
+  double a1[3], j1[3];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    a1[k] = g * sum[k];
+    j1[k] = g * sum[k + 3];
+  }
+  if (pos) {
+    double x1[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      const double a0 = acc_in[3 * (size_t)i + k], j0 = jerk_in[3 * (size_t)i + k];
+      double x = pos[3 * (size_t)i + k], v = vel[3 * (size_t)i + k];
+      hermite_correct(x, v, a0, j0, a1[k], j1[k], h.dt_half, h.dt2_twelfth);
+      vel[3 * (size_t)i + k] = v;
+      pos[3 * (size_t)i + k] = x1[k] = x;
+    }
+    posd[i] = d4{x1[0], x1[1], x1[2], mass[i]};
+  }
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    acc_out[3 * (size_t)i + k] = a1[k];
+    jerk_out[3 * (size_t)i + k] = j1[k];
+  }
+}
+
+// phi[i] = -G (slab 0 + slab 1 + ...) in slab order (0 - G sum: a body without partners gets +0)
+__global__ __launch_bounds__(256) void potential_finish_f64_kernel(const double* __restrict__ slabs, int n_slabs, int n,
+                                                                   double g, double* __restrict__ phi) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  double sum = 0.0;
+  for (int s = 0; s < n_slabs; ++s) sum += slabs[(size_t)s * n + i];
+  phi[i] = 0.0 - g * sum;
+}
+
+// {U, K} = {-G sum_i m_i u_i, sum_i 1/2 m_i |v_i|^2}, u_i = the slabs in slab order: one workgroup, thread t over the
+// bodies t, t + 1024, ... in index order, then a shuffle tree per wave and the 16 wave sums in wave order.
+__global__ __launch_bounds__(kSumThreads) void energy_finish_f64_kernel(const double* __restrict__ slabs, int n_slabs,
+                                                                        int n, const d4* __restrict__ posd,
+                                                                        const double* __restrict__ vel, double g,
+                                                                        double* __restrict__ out_uk) {
+  __shared__ double red[2][kSumWaves];
+  double a[2] = {0.0, 0.0};
+  for (int i = threadIdx.x; i < n; i += kSumThreads) {
+    double u = 0.0;
+    for (int s = 0; s < n_slabs; ++s) u += slabs[(size_t)s * n + i];
+    const double m = posd[i].w;
+    const double vx = vel[3 * (size_t)i], vy = vel[3 * (size_t)i + 1], vz = vel[3 * (size_t)i + 2];
+    a[0] += m * u;
+    a[1] += 0.5 * m * ((vx * vx + vy * vy) + vz * vz);
+  }
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int q = 0; q < 2; ++q) {
+    for (int off = 32; off > 0; off >>= 1) a[q] += __shfl_down(a[q], off);
+    if (lane == 0) red[q][wave] = a[q];
+  }
+  __syncthreads();
+  if (threadIdx.x < 2) {
+    double s = red[threadIdx.x][0];
+    for (int w = 1; w < kSumWaves; ++w) s += red[threadIdx.x][w];
+    out_uk[threadIdx.x] = threadIdx.x == 0 ? 0.0 - g * s : s;
+  }
+}
+
+// A body of the fp64 state for invariants_body (direct_kernels.h)
+struct F64State {
+  const double* __restrict__ pos;
+  const double* __restrict__ vel;
+  const double* __restrict__ mass;
+  __device__ __forceinline__ void operator()(int i, double& m, double* x, double* v) const {
+    m = mass[i];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      x[k] = pos[3 * (size_t)i + k];
+      v[k] = vel[3 * (size_t)i + k];
+    }
+  }
+};
+
+__global__ __launch_bounds__(kInvThreads) void invariants_state_f64_kernel(const double* __restrict__ pos,
+                                                                           const double* __restrict__ vel,
+                                                                           const double* __restrict__ mass,
+                                                                           const double* __restrict__ phi, int n,
+                                                                           double* __restrict__ row) {
+  __shared__ double red[kInvSums][kInvWaves];
+  invariants_body(F64State{pos, vel, mass}, phi, n, row, red);
+}
+
+// The geometry of the three pair launches: groups of 64 targets, and enough slabs for ~kTargetWGs workgroups as long as
+// every wave of a slab still has a chunk to walk.
+struct F64Plan { int groups, slabs, n_chunks; };
+
+F64Plan plan_f64(int n) {
+  F64Plan p;
+  p.groups = p.n_chunks = ceil_div(n, kChunk);
+  int slabs = ceil_div(kTargetWGs, p.groups);
+  const int cap = p.n_chunks / kWaves;
+  slabs = slabs > cap ? cap : slabs;
+  slabs = slabs > kMaxSlabs ? kMaxSlabs : slabs;
+  p.slabs = slabs < 1 ? 1 : slabs;
+  return p;
+}
+
+size_t rows_bytes(int n) { return (size_t)ceil_div(n, kChunk) * kChunk * sizeof(d4); }
+
+// the unscaled acceleration + jerk partial sums of every body into double[slabs][6][n]
+int launch_jerk_f64(const double* posd, const double* veld, int n, double eps2, double* out, const F64Plan& p, int slabs,
+                    hipStream_t st) {
+  const ChunkSplit c = chunk_split(p.n_chunks, slabs);
+  accel_jerk_f64_kernel<<<dim3(p.groups, slabs), 64 * kWaves, 0, st>>>(
+      reinterpret_cast<const d4*>(posd), reinterpret_cast<const d4*>(veld), n, c.q, c.r, eps2,
+      eps2 < kEps2MaskedF64 ? 1 : 0, out);
+  return launch_status();
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t nbd_hermite_f64_workspace_bytes(int n) {
+  if (n <= 0) return 0;
+  return (size_t)plan_f64(n).slabs * 6 * n * sizeof(double);
+}
+
+int nbd_hermite_f64_plan(int n, int* groups, int* slabs, int* chunks_per_wave) {
+  if (n <= 0) return NBD_E_BADARG;
+  const F64Plan p = plan_f64(n);
+  if (groups) *groups = p.groups;
+  if (slabs) *slabs = p.slabs;
+  if (chunks_per_wave) *chunks_per_wave = ceil_div(p.n_chunks, p.slabs * kWaves);
+  return 0;
+}
+
+int nbd_hermite_f64_pack(const double* pos, const double* vel, const double* acc, const double* jerk, const double* mass,
+                         int n, double dt, double* posd, double* veld, nbd_stream_t stream) {
+  if (n < 0 || (n > 0 && (!pos || !vel || !mass || !posd || !veld)) || (!acc != !jerk)) return NBD_E_BADARG;
+  if (misaligned32(posd) || misaligned32(veld)) return NBD_E_BADARG;
+  if (n == 0) return 0;
+  const int n_pad = nbd_posm_padded_len(n);
+  predict_f64_kernel<<<ceil_div(n_pad, 256), 256, 0, (hipStream_t)stream>>>(
+      pos, vel, acc, jerk, mass, n, n_pad, hermite_step_constants<double>(dt), reinterpret_cast<d4*>(posd),
+      reinterpret_cast<d4*>(veld));
+  return launch_status();
+}
+
+int nbd_accel_jerk_f64(const double* posd, const double* veld, int n, double softening_sq, double g_const,
+                       double* acc_out, double* jerk_out, void* workspace, size_t workspace_bytes, int slabs,
+                       nbd_stream_t stream) {
+  if (n < 0 || slabs < 0 || slabs > kMaxSlabs) return NBD_E_BADARG;
+  if (n == 0) return 0;
+  if (!posd || !veld || !acc_out || !jerk_out || misaligned32(posd) || misaligned32(veld)) return NBD_E_BADARG;
+  const F64Plan p = plan_f64(n);
+  if (slabs == 0) slabs = p.slabs;
+  if (!workspace || misaligned8(workspace) || workspace_bytes < (size_t)slabs * 6 * n * sizeof(double))
+    return NBD_E_WORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  double* part = static_cast<double*>(workspace);
+  const int rc = launch_jerk_f64(posd, veld, n, softening_sq, part, p, slabs, st);
+  if (rc) return rc;
+  correct_f64_kernel<<<ceil_div(n, 256), 256, 0, st>>>(part, slabs, n, g_const, hermite_step_constants<double>(0.0),
+                                                       nullptr, nullptr, nullptr, nullptr, acc_out, jerk_out, nullptr,
+                                                       nullptr);
+  return launch_status();
+}
+
+int nbd_hermite_step_f64(double* pos, double* vel, const double* acc_in, const double* jerk_in, double* acc_out,
+                         double* jerk_out, const double* mass, int n, double dt, double softening_sq, double g_const,
+                         double* posd, double* veld, void* workspace, size_t workspace_bytes, nbd_stream_t stream) {
+  if (n < 0) return NBD_E_BADARG;
+  if (n == 0) return 0;
+  if (!pos || !vel || !acc_in || !jerk_in || !acc_out || !jerk_out || !mass || !posd || !veld || misaligned32(posd) ||
+      misaligned32(veld))
+    return NBD_E_BADARG;
+  if (!workspace || misaligned8(workspace) || workspace_bytes < nbd_hermite_f64_workspace_bytes(n))
+    return NBD_E_WORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  const HermiteStep<double> h = hermite_step_constants<double>(dt);
+  const F64Plan p = plan_f64(n);
+  double* part = static_cast<double*>(workspace);
+  const int n_pad = nbd_posm_padded_len(n);
+  predict_f64_kernel<<<ceil_div(n_pad, 256), 256, 0, st>>>(pos, vel, acc_in, jerk_in, mass, n, n_pad, h,
+                                                           reinterpret_cast<d4*>(posd), reinterpret_cast<d4*>(veld));
+  int rc = launch_status();
+  if (rc) return rc;
+  if ((rc = launch_jerk_f64(posd, veld, n, softening_sq, part, p, p.slabs, st))) return rc;
+  correct_f64_kernel<<<ceil_div(n, 256), 256, 0, st>>>(part, p.slabs, n, g_const, h, pos, vel, acc_in, jerk_in, acc_out,
+                                                       jerk_out, mass, reinterpret_cast<d4*>(posd));
+  return launch_status();
+}
+
+int nbd_energy_f64(const double* posd, const double* vel, int n, double softening, double g_const, double* out_uk,
+                   void* workspace, size_t workspace_bytes, nbd_stream_t stream) {
+  if (n < 0 || !out_uk || misaligned8(out_uk)) return NBD_E_BADARG;
+  if (n > 0 && (!posd || !vel || misaligned32(posd))) return NBD_E_BADARG;
+  hipStream_t st = (hipStream_t)stream;
+  const d4* pd = reinterpret_cast<const d4*>(posd);
+  double* part = static_cast<double*>(workspace);
+  int slabs = 0;
+  if (n > 0) {
+    const F64Plan p = plan_f64(n);
+    slabs = p.slabs;
+    if (!workspace || misaligned8(workspace) || workspace_bytes < (size_t)slabs * n * sizeof(double))
+      return NBD_E_WORKSPACE;
+    energy_f64_kernel<<<dim3(p.groups, slabs), 64 * kWaves, 0, st>>>(pd, n, p.n_chunks, softening, part);
+    const int rc = launch_status();
+    if (rc) return rc;
+  }
+  energy_finish_f64_kernel<<<1, kSumThreads, 0, st>>>(part, slabs, n, pd, vel, g_const, out_uk);
+  return launch_status();
+}
+
+int nbd_potential_f64(const double* posd, int n, double softening_sq, double g_const, double* phi_out, void* workspace,
+                      size_t workspace_bytes, nbd_stream_t stream) {
+  if (n < 0) return NBD_E_BADARG;
+  if (n == 0) return 0;
+  if (!posd || misaligned32(posd) || !phi_out || misaligned8(phi_out)) return NBD_E_BADARG;
+  const F64Plan p = plan_f64(n);
+  if (!workspace || misaligned8(workspace) || workspace_bytes < (size_t)p.slabs * n * sizeof(double))
+    return NBD_E_WORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  double* part = static_cast<double*>(workspace);
+  const ChunkSplit c = chunk_split(p.n_chunks, p.slabs);
+  potential_f64_kernel<<<dim3(p.groups, p.slabs), 64 * kWaves, 0, st>>>(
+      reinterpret_cast<const d4*>(posd), n, c.q, c.r, softening_sq, softening_sq < kEps2MaskedF64 ? 1 : 0, part);
+  const int rc = launch_status();
+  if (rc) return rc;
+  potential_finish_f64_kernel<<<ceil_div(n, 256), 256, 0, st>>>(part, p.slabs, n, g_const, phi_out);
+  return launch_status();
+}
+
+int nbd_invariants_state_f64(const double* pos, const double* vel, const double* mass, const double* phi, int n,
+                             double* out_row, nbd_stream_t stream) {
+  if (n < 0 || !out_row || misaligned8(out_row)) return NBD_E_BADARG;
+  if (n > 0 && (!pos || !vel || !mass || !phi || misaligned8(phi))) return NBD_E_BADARG;
+  invariants_state_f64_kernel<<<1, kInvThreads, 0, (hipStream_t)stream>>>(pos, vel, mass, phi, n, out_row);
+  return launch_status();
+}
+
+}  // extern "C"

@@ -3,7 +3,7 @@
 // units): the host helpers of their entry
 // points (ceil_div, misaligned16, launch_status) and the device building blocks: the pair arithmetic (interact, interact_block,
 // energy_pair, potential_pair) and, one level up, the wave bodies that walk the source chunks with it (accel_body, energy_body, potential_body: target
-// loads, LDS-DMA chunk walk, pair loop, four-wave reduction, store). A force or energy kernel of either unit is a
+// loads, LDS-DMA chunk walk, pair loop, four-wave reduction, store), and the sums of the conserved quantities (invariants_body). A force or energy kernel of either unit is a
 // prologue that reads its geometry (from blockIdx and arguments, or from a scene record) and one call of the body: that
 // is what keeps a scene of a batch bit-identical to the same system run alone.
 // The definitions sit in an anonymous namespace: every translation unit that includes this file gets its own inlined copies.
@@ -388,6 +388,56 @@ __device__ __forceinline__ void potential_body(const f4* __restrict__ src, int n
   if ((int)threadIdx.x < n_valid) {
     const double* r = red + threadIdx.x;          // row lt = half * 64 + lane sits at [wave][lt]
     dst[threadIdx.x] = (r[0] + r[2 * 64]) + (r[4 * 64] + r[6 * 64]);
+  }
+}
+
+// ---- conserved quantities (csrc/direct_diag.hip from the fp32 state, csrc/direct_hermite_f64.hip from an fp64 one).
+// The body of the invariants kernels: the workgroup's 1024 threads over the n bodies of one system -- state(i, m, x, v)
+// gives body i's mass, position and velocity as doubles -- and phi (n); row = {M, C (3), P (3), L (3), K, U, E, Q, 0, 0}.
+// Thread t sums bodies t, t + 1024, ... in index order, then a shuffle tree per wave and the 16 wave sums in wave order.
+// C = 0 when M = 0, Q = 0 when U = 0.
+constexpr int kInvThreads = 1024;            // one workgroup per system: 16 waves
+constexpr int kInvWaves = kInvThreads / 64;
+constexpr int kInvSums = 12;                 // M, m x (3), m v (3), m x cross v (3), K, sum m phi
+
+template <class State>
+__device__ __forceinline__ void invariants_body(const State state, const double* __restrict__ phi, int n,
+                                                double* __restrict__ row, double (*red)[kInvWaves]) {
+  double a[kInvSums];
+#pragma unroll
+  for (int q = 0; q < kInvSums; ++q) a[q] = 0.0;
+  for (int i = threadIdx.x; i < n; i += kInvThreads) {
+    double m, xs[3], vs[3];
+    state(i, m, xs, vs);
+    const double x = xs[0], y = xs[1], z = xs[2], vx = vs[0], vy = vs[1], vz = vs[2];
+    a[0] += m;
+    a[1] += m * x; a[2] += m * y; a[3] += m * z;
+    a[4] += m * vx; a[5] += m * vy; a[6] += m * vz;
+    a[7] += m * (y * vz - z * vy); a[8] += m * (z * vx - x * vz); a[9] += m * (x * vy - y * vx);
+    a[10] += 0.5 * m * ((vx * vx + vy * vy) + vz * vz);
+    a[11] += m * phi[i];
+  }
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int q = 0; q < kInvSums; ++q) {
+    for (int off = 32; off > 0; off >>= 1) a[q] += __shfl_down(a[q], off);
+    if (lane == 0) red[q][wave] = a[q];
+  }
+  __syncthreads();
+  if (threadIdx.x < kInvSums) {
+    double s = red[threadIdx.x][0];
+    for (int w = 1; w < kInvWaves; ++w) s += red[threadIdx.x][w];
+    red[threadIdx.x][0] = s;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const double M = red[0][0], K = red[10][0], U = 0.5 * red[11][0];
+    row[0] = M;
+    for (int q = 1; q <= 3; ++q) row[q] = M != 0.0 ? red[q][0] / M : 0.0;
+    for (int q = 4; q <= 9; ++q) row[q] = red[q][0];
+    row[10] = K; row[11] = U; row[12] = K + U;
+    row[13] = U != 0.0 ? -2.0 * K / U : 0.0;
+    row[14] = 0.0; row[15] = 0.0;
   }
 }
 

@@ -6,7 +6,8 @@
 //     apart from the sources, 8-float rows, a skipped source range) and the split of the chunks over the waves
 //     (chunk_split on the host, wave_chunk_range in a kernel);
 //   - the O(N) arithmetic: the fp32 step constants (hermite_dt), the predictor (hermite_predict), the fixed-order slab sum
-//     (hermite_slab_sum) and the corrector (hermite_correct);
+//     (hermite_slab_sum) and the corrector (hermite_correct); the constants, the predictor and the corrector are templates
+//     of the scalar type, instantiated with double by direct_hermite_f64.hip (the float instantiation is the code it was);
 //   - the launch plan of a force launch (JerkPlan, plan_jerk).
 // A kernel of one of the units is a prologue that says which targets, which chunks, which rows and which constants, and
 // calls of these: a scene of a batch, or a block step at level 0, is bit-identical to the shared-timestep step because
@@ -224,20 +225,29 @@ inline JerkPlan plan_jerk(int n, int n_tgt) {
 
 // fp32 step constants, each formed in double and rounded once. On the device too: a block-timestep body forms them from
 // its own fp64 step, so one whose step is the whole interval gets the shared step's bits.
-struct HermiteDt { float dt, dt_half, dt2_half, dt3_sixth, dt2_twelfth; };
+// (T = double, direct_hermite_f64.hip: the same five doubles, not rounded again.)
+template <class T>
+struct HermiteStep { T dt, dt_half, dt2_half, dt3_sixth, dt2_twelfth; };
+using HermiteDt = HermiteStep<float>;
 
-__host__ __device__ inline HermiteDt hermite_dt(double dt) {
-  return HermiteDt{(float)dt, (float)(0.5 * dt), (float)(0.5 * dt * dt), (float)(dt * dt * dt / 6.0),
-                   (float)(dt * dt / 12.0)};
+template <class T>
+__host__ __device__ inline HermiteStep<T> hermite_step_constants(double dt) {
+  return HermiteStep<T>{(T)dt, (T)(0.5 * dt), (T)(0.5 * dt * dt), (T)(dt * dt * dt / 6.0), (T)(dt * dt / 12.0)};
 }
+
+__host__ __device__ inline HermiteDt hermite_dt(double dt) { return hermite_step_constants<float>(dt); }
 
 // One component of the predictor, each product and sum rounded on its own (the build has -ffp-contract=off):
 // x_p = x + v dt + a dt^2/2 + j dt^3/6, v_p = v + a dt + j dt^2/2.
-struct PosVel { float x, v; };
+// T = float for the fp32 units, double for direct_hermite_f64.hip.
+template <class T>
+struct PosVelT { T x, v; };
+using PosVel = PosVelT<float>;
 
-__device__ __forceinline__ PosVel hermite_predict(const float x, const float v, const float a, const float j,
-                                                  const float dt, const float dt2_half, const float dt3_sixth) {
-  return PosVel{((x + v * dt) + a * dt2_half) + j * dt3_sixth, (v + a * dt) + j * dt2_half};
+template <class T>
+__device__ __forceinline__ PosVelT<T> hermite_predict(const T x, const T v, const T a, const T j, const T dt,
+                                                      const T dt2_half, const T dt3_sixth) {
+  return PosVelT<T>{((x + v * dt) + a * dt2_half) + j * dt3_sixth, (v + a * dt) + j * dt2_half};
 }
 
 // a1 = g * sum of the slabs, j1 likewise, in a fixed order, for a workgroup of 4 waves on 64 consecutive rows of
@@ -270,9 +280,10 @@ __device__ __forceinline__ bool hermite_slab_sum(const float* __restrict__ slabs
 
 // One component of the corrector, each product and sum rounded on its own:
 // v1 = v + (a0 + a1) dt/2 + (j0 - j1) dt^2/12, x1 = x + (v + v1) dt/2 + (a0 - a1) dt^2/12.
-__device__ __forceinline__ void hermite_correct(float& x, float& v, const float a0, const float j0, const float a1,
-                                                const float j1, const float dt_half, const float dt2_twelfth) {
-  const float v1 = (v + (a0 + a1) * dt_half) + (j0 - j1) * dt2_twelfth;
+template <class T>
+__device__ __forceinline__ void hermite_correct(T& x, T& v, const T a0, const T j0, const T a1, const T j1,
+                                                const T dt_half, const T dt2_twelfth) {
+  const T v1 = (v + (a0 + a1) * dt_half) + (j0 - j1) * dt2_twelfth;
   x = (x + (v + v1) * dt_half) + (a0 - a1) * dt2_twelfth;
   v = v1;
 }

@@ -21,6 +21,9 @@ evaluation per step; csrc/direct_hermite.hip).
 Fourth addition: `BlockHermiteSimulator`, the same scheme with individual block timesteps inside each output interval
 (csrc/direct_hermite_block.hip).
 
+Sixth addition: `HermiteSimulator(dtype=torch.float64)`, the same scheme with float64 state, scalars and pair arithmetic
+(csrc/direct_hermite_f64.hip). The default stays float32 and takes the paths it took.
+
 Fifth addition: `compute_potentials()` / `compute_invariants()` and `calc_invariants=`: the per-body potential of the
 softening the force uses and the conserved quantities formed from it (`Invariants`; csrc/direct_diag.hip).
 `compute_energies()`, `u_energy` and `k_energy` keep the reference's convention.
@@ -91,6 +94,13 @@ def _to_f32(x, device) -> torch.Tensor:
     if isinstance(x, torch.Tensor):
         return x.detach().to(device=device, dtype=torch.float32, copy=True).contiguous()
     return torch.tensor(np.asarray(x), dtype=torch.float32, device=device).contiguous()
+
+
+def _to_f64(x, device) -> torch.Tensor:
+    """A float64 device copy, converted directly (never through float32)."""
+    if isinstance(x, torch.Tensor):
+        return x.detach().to(device=device, dtype=torch.float64, copy=True).contiguous()
+    return torch.tensor(np.asarray(x), dtype=torch.float64, device=device).contiguous()
 
 
 def _resolve_device(device) -> torch.device:
@@ -389,12 +399,13 @@ class BaseSimulator(_ChunkedRun):
 
     def _run_eager(self, steps: int, first_index: int, states):
         n_loc = self.part.n_local
-        per_step = 3 * n_loc * 3 * 4
+        dtype = self.positions.dtype                     # float32, or float64 for HermiteSimulator(dtype=torch.float64)
+        per_step = 3 * n_loc * 3 * self.positions.element_size()
         chunk = max(1, min(max(steps, 32), (64 << 20) // max(per_step, 1)))
         # pinned staging is expensive to create (page-locking): keep it across run() calls
         cached = getattr(self, "_run_stage", None)
         if cached is None or cached[0].shape[0] < chunk:
-            cached = (torch.empty((chunk, 3, n_loc, 3), dtype=torch.float32).pin_memory(),
+            cached = (torch.empty((chunk, 3, n_loc, 3), dtype=dtype).pin_memory(),
                       torch.empty((chunk, 2), dtype=torch.float64).pin_memory())
             self._run_stage = cached
         stage, uk_host = cached
@@ -618,16 +629,36 @@ class HermiteSimulator(BaseSimulator):
     With `process_group=` the bodies are range-sharded as for LeapFrogSimulator (csrc/direct_hermite_shard.hip; DESIGN.md
     §8): positions, velocities, accelerations and jerks hold the rank's rows [lo, hi), `gather()` assembles any of them,
     and a step is predict + pack of the own bodies -> ONE all-gather of 8-float rows {x_p, m, v_p, 0} in flight || own x
-    own block -> own x others block + slab sum + corrector. Eager only: there is no captured form of the sharded step."""
+    own block -> own x others block + slab sum + corrector. Eager only: there is no captured form of the sharded step.
+
+    With `dtype=torch.float64` (csrc/direct_hermite_f64.hip) positions, velocities, masses,
+    accelerations and jerks are float64 device tensors (the inputs are converted directly, not through float32), g_const,
+    softening ** 2, dt and the step constants go to the kernels as the Python doubles, and step(), the compute_*() methods
+    and run() -- its states, energies and invariants -- are float64 end to end: there is no fp32 pair term anywhere.
+    run() is eager in this mode, and there is no range-sharded form: float64 with `process_group=` raises ValueError."""
+
+    _f64 = False
+
+    @staticmethod
+    def _check_dtype(dtype, process_group):
+        if dtype not in (torch.float32, torch.float64):
+            raise ValueError(f"HermiteSimulator: dtype must be torch.float32 or torch.float64, got {dtype!r}")
+        if dtype == torch.float64 and process_group is not None:
+            raise ValueError("HermiteSimulator: dtype=torch.float64 has no range-sharded form; process_group is not "
+                             "supported with it")
 
     def __init__(self, *, positions, velocities, masses, g_const: float = 1.0, softening: float = 0.1,
                  dt: float = 0.01, calc_energy: bool = True, device: str = None, process_group=None,
-                 calc_invariants: bool = False):
+                 calc_invariants: bool = False, dtype=torch.float32):
+        self._check_dtype(dtype, process_group)                  # before anything is resolved, allocated or launched
         if process_group is not None and not (torch.distributed.is_available() and
                                               isinstance(process_group, torch.distributed.ProcessGroup)):
             raise ValueError("HermiteSimulator: process_group must be a torch.distributed process group, got "
                              f"{type(process_group).__name__}")
         self.jerks = None
+        if dtype == torch.float64:
+            self._init_f64(positions, velocities, masses, g_const, softening, dt, calc_energy, device, calc_invariants)
+            return
         super().__init__(positions=positions, velocities=velocities, masses=masses, g_const=g_const,
                          softening=softening, dt=dt, calc_energy=calc_energy, device=device,
                          process_group=process_group, calc_invariants=calc_invariants)
@@ -646,13 +677,96 @@ class HermiteSimulator(BaseSimulator):
                                                collective=True)
         self.accelerations, self.jerks = self.compute_accelerations_and_jerks()
 
+    # ------------------------------------------------------------------ float64 mode (csrc/direct_hermite_f64.hip)
+    def _init_f64(self, positions, velocities, masses, g_const, softening, dt, calc_energy, device, calc_invariants):
+        """BaseSimulator's constructor for a float64, un-sharded state: nothing of the fp32 paths is allocated."""
+        self._f64 = True
+        self.device = _resolve_device(device)
+        _lib.lib()
+        self.dt, self.g_const, self.softening = dt, g_const, softening
+        self.calc_energy, self.calc_invariants = calc_energy, calc_invariants
+        self.positions = _to_f64(positions, self.device)
+        self.velocities = _to_f64(velocities, self.device)
+        self.masses = _to_f64(masses, self.device)
+        self.n = self.positions.shape[0]
+        if self.positions.shape != (self.n, 3) or self.velocities.shape != (self.n, 3) or self.masses.shape != (self.n,):
+            raise ValueError("positions/velocities must be (n,3) and masses (n,)")
+        self.process_group, self._sharded, self._uniform = None, False, None
+        self.part = nbd_dist.RangePartition(self.n, 1, 0)
+        self._posd = direct.alloc_rows_f64(self.n, self.device)
+        self._veld = direct.alloc_rows_f64(self.n, self.device)
+        self._hws = direct.hermite_f64_workspace(max(self.n, 1), self.device)
+        self.accelerations, self.jerks = self.compute_accelerations_and_jerks()
+
+    def _f64_scalars(self):
+        """(softening^2, G) as the Python doubles, read when a launch is made."""
+        return float(self.softening) ** 2, float(self.g_const)
+
+    def _pack_f64(self):
+        direct.hermite_f64_pack(self.positions, self.velocities, self.masses, self._posd, self._veld)
+
+    def _graph_run_ok(self, steps: int) -> bool:
+        return not self._f64 and super()._graph_run_ok(steps)        # float64: run() is eager, there is no captured form
+
+    def compute_accelerations(self) -> torch.Tensor:
+        if self._f64:
+            return self.compute_accelerations_and_jerks()[0]
+        return super().compute_accelerations()
+
+    def compute_energies(self):
+        if not self._f64:
+            return super().compute_energies()
+        if self.n == 0:
+            return 0.0, 0.0
+        self._pack_f64()
+        u, k = direct.energy_f64(self._posd, self.velocities, self.n, self.softening, self.g_const, self._hws).cpu().tolist()
+        return u, k
+
+    def _energies_into(self, out_uk, workspace=None):
+        if not self._f64:
+            return super()._energies_into(out_uk, workspace)
+        direct.energy_f64(self._posd, self.velocities, self.n, self.softening, self.g_const, self._hws, out_uk=out_uk)
+
+    def _potentials_into(self, phi):
+        if not self._f64:
+            return super()._potentials_into(phi)
+        eps2, g = self._f64_scalars()
+        return direct.potential_f64(self._posd, self.n, eps2, g, self._hws, out=phi)
+
+    def compute_potentials(self) -> torch.Tensor:
+        if not self._f64:
+            return super().compute_potentials()
+        if self.n == 0:
+            return torch.zeros((0,), dtype=torch.float64, device=self.device)
+        self._pack_f64()
+        return self._potentials_into(None)
+
+    def compute_invariants(self) -> Invariants:
+        if not self._f64:
+            return super().compute_invariants()
+        if self.n == 0:
+            return Invariants.from_row([0.0] * direct.INVARIANT_ROW)
+        phi = self.compute_potentials()
+        return Invariants.from_row(direct.invariants_state_f64(self.positions, self.velocities, self.masses, phi).cpu())
+
+    def _invariants_into(self, out_row):
+        if not self._f64:
+            return super()._invariants_into(out_row)
+        if getattr(self, "_phi", None) is None:
+            self._phi = torch.empty((self.n,), dtype=torch.float64, device=self.device)
+        self._potentials_into(self._phi)                             # _posd is the post-step state (_posm_after_step)
+        direct.invariants_state_f64(self.positions, self.velocities, self.masses, self._phi, out=out_row)
+
     def compute_accelerations_and_jerks(self):
         """(a, j) of the current state as new (n,3) tensors -- (n_local,3), the rank's rows, when sharded:
         a_i = G sum_{j!=i} m_j r_ij s^3, j_i = G sum_{j!=i} m_j (v_ij s^3 - 3 (r_ij.v_ij) s^5 r_ij),
         s = (|r_ij|^2 + eps^2)^(-1/2)."""
         if self.n == 0:
-            z = torch.zeros((0, 3), dtype=torch.float32, device=self.device)
+            z = torch.zeros((0, 3), dtype=self.positions.dtype, device=self.device)
             return z, z.clone()
+        if self._f64:
+            self._pack_f64()
+            return direct.accel_jerk_f64(self._posd, self._veld, self.n, *self._f64_scalars(), workspace=self._hws)
         if self._sharded:
             return self._sharded_launches(None, None)
         direct.hermite_pack(self.positions, self.velocities, self.masses, self._posm, self._velp)
@@ -687,6 +801,11 @@ class HermiteSimulator(BaseSimulator):
             return
         new_acc = torch.empty_like(self.accelerations)
         new_jerk = torch.empty_like(self.jerks)
+        if self._f64:
+            direct.hermite_step_f64(self.positions, self.velocities, self.accelerations, self.jerks, new_acc, new_jerk,
+                                    self.masses, self.dt, *self._f64_scalars(), self._posd, self._veld, self._hws)
+            self.accelerations, self.jerks = new_acc, new_jerk
+            return
         direct.hermite_step(self.positions, self.velocities, self.accelerations, self.jerks, new_acc, new_jerk,
                             self.masses, self.dt, self._eps2, self._g, self._posm, self._hws)
         self.accelerations, self.jerks = new_acc, new_jerk

@@ -221,6 +221,18 @@ SIGNATURES = {
     "nbd_hermite_shard_force_remote_f32": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_float, c_float, c_void_p,
                                                    c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_void_p,
                                                    c_size_t, c_void_p]),
+    # --- double-precision Hermite (csrc/direct_hermite_f64.hip)
+    "nbd_hermite_f64_workspace_bytes": (c_size_t, [c_int]),
+    "nbd_hermite_f64_plan": (c_int, [c_int, POINTER(c_int), POINTER(c_int), POINTER(c_int)]),
+    "nbd_hermite_f64_pack": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_double, c_void_p,
+                                     c_void_p, c_void_p]),
+    "nbd_accel_jerk_f64": (c_int, [c_void_p, c_void_p, c_int, c_double, c_double, c_void_p, c_void_p, c_void_p, c_size_t,
+                                   c_int, c_void_p]),
+    "nbd_hermite_step_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                                     c_double, c_double, c_double, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "nbd_energy_f64": (c_int, [c_void_p, c_void_p, c_int, c_double, c_double, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "nbd_potential_f64": (c_int, [c_void_p, c_int, c_double, c_double, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "nbd_invariants_state_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
     # --- block-timestep Hermite integrator (csrc/direct_hermite_block.hip)
     "nbd_hblock_workspace_bytes": (c_size_t, [c_int]),
     "nbd_hblock_init_levels": (c_int, [c_void_p, c_void_p, c_int, c_double, c_double, c_int, c_void_p, c_void_p,

@@ -451,6 +451,123 @@ def hermite_shard_force_remote(rows_all: torch.Tensor, n_total: int, send: torch
             "nbd_hermite_shard_force_remote_f32")
 
 
+# ---------------------------------------------------------- double-precision Hermite (csrc/direct_hermite_f64.hip)
+F64 = torch.float64
+
+
+def alloc_rows_f64(n: int, device) -> torch.Tensor:
+    """Zeroed (padded_len(n), 4) float64 rows: posd = {x, y, z, m} or veld = {vx, vy, vz, 0}."""
+    return torch.zeros((padded_len(n), 4), dtype=F64, device=device)
+
+
+def hermite_f64_plan(n: int) -> dict:
+    g, s, c = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    _lib.check(_lib.lib().nbd_hermite_f64_plan(int(n), g, s, c), "nbd_hermite_f64_plan")
+    return {"groups": g.value, "slabs": s.value, "chunks_per_wave": c.value}
+
+
+def hermite_f64_workspace(n: int, device, slabs: int = 0) -> torch.Tensor:
+    """The partial sums of every f64 entry at n bodies (or of accel_jerk_f64 with an explicit slab count)."""
+    need = _lib.lib().nbd_hermite_f64_workspace_bytes(int(n))
+    return alloc_bytes(max(need, int(slabs) * 6 * int(n) * 8), device)
+
+
+def _chk_rows_f64(posd, veld, n: int):
+    _chk(posd, (padded_len(n), 4), "posd", F64)
+    if veld is not None:
+        _chk(veld, (padded_len(n), 4), "veld", F64)
+
+
+def hermite_f64_pack(pos, vel, mass, posd, veld, acc=None, jerk=None, dt: float = 0.0) -> None:
+    """hermite_pack in float64: posd = {x_p, m}, veld = {v_p, 0}, predicted over dt from (acc, jerk) or a plain pack."""
+    n = pos.shape[0]
+    _chk(pos, (n, 3), "pos", F64); _chk(vel, (n, 3), "vel", F64); _chk(mass, (n,), "mass", F64)
+    _chk_rows_f64(posd, veld, n)
+    if (acc is None) != (jerk is None):
+        raise _lib.NbdError("hermite_f64_pack: give both acc and jerk, or neither")
+    if acc is not None:
+        _chk(acc, (n, 3), "acc", F64); _chk(jerk, (n, 3), "jerk", F64)
+    with _lib.on_device(pos.device):
+        _lib.check(_lib.lib().nbd_hermite_f64_pack(
+            pos.data_ptr(), vel.data_ptr(), _lib.ptr(acc), _lib.ptr(jerk), mass.data_ptr(), n, float(dt),
+            posd.data_ptr(), veld.data_ptr(), _lib.current_stream(pos.device)), "nbd_hermite_f64_pack")
+
+
+def accel_jerk_f64(posd, veld, n: int, softening_sq: float, g_const: float, workspace=None, slabs: int = 0):
+    """accel_jerk in float64: new (acc, jerk), each (n,3) float64. slabs: 0 = the plan's source split, else that many."""
+    _chk_rows_f64(posd, veld, n)
+    dev = posd.device
+    acc_out = torch.empty((n, 3), dtype=F64, device=dev)
+    jerk_out = torch.empty((n, 3), dtype=F64, device=dev)
+    if workspace is None:                       # a given workspace is checked by the entry, against what this call uses
+        workspace = hermite_f64_workspace(n, dev, slabs)
+    with _lib.on_device(dev):
+        _lib.check(_lib.lib().nbd_accel_jerk_f64(
+            posd.data_ptr(), veld.data_ptr(), n, float(softening_sq), float(g_const), acc_out.data_ptr(),
+            jerk_out.data_ptr(), workspace.data_ptr(), _nbytes(workspace), int(slabs), _lib.current_stream(dev)),
+            "nbd_accel_jerk_f64")
+    return acc_out, jerk_out
+
+
+def hermite_step_f64(pos, vel, acc_in, jerk_in, acc_out, jerk_out, mass, dt: float, softening_sq: float,
+                     g_const: float, posd, veld, workspace) -> None:
+    """hermite_step in float64 (three launches): pos, vel in place; acc_out, jerk_out may be acc_in, jerk_in;
+    posd = {x1, m}; veld is scratch. dt, softening_sq and g_const go in as the Python doubles."""
+    n = pos.shape[0]
+    for t, nm in ((pos, "pos"), (vel, "vel"), (acc_in, "acc_in"), (jerk_in, "jerk_in"), (acc_out, "acc_out"),
+                  (jerk_out, "jerk_out")):
+        _chk(t, (n, 3), nm, F64)
+    _chk(mass, (n,), "mass", F64)
+    _chk_rows_f64(posd, veld, n)
+    with _lib.on_device(pos.device):
+        _lib.check(_lib.lib().nbd_hermite_step_f64(
+            pos.data_ptr(), vel.data_ptr(), acc_in.data_ptr(), jerk_in.data_ptr(), acc_out.data_ptr(),
+            jerk_out.data_ptr(), mass.data_ptr(), n, float(dt), float(softening_sq), float(g_const), posd.data_ptr(),
+            veld.data_ptr(), workspace.data_ptr(), _nbytes(workspace), _lib.current_stream(pos.device)),
+            "nbd_hermite_step_f64")
+
+
+def energy_f64(posd, vel, n: int, softening: float, g_const: float, workspace, out_uk=None):
+    """Device double[2] = {U, K} in the reference's convention from a float64 state; asynchronous."""
+    _chk_rows_f64(posd, None, n); _chk(vel, (n, 3), "vel", F64)
+    if out_uk is None:
+        out_uk = torch.empty(2, dtype=F64, device=vel.device)
+    _chk(out_uk, (2,), "out_uk", F64)
+    with _lib.on_device(vel.device):
+        _lib.check(_lib.lib().nbd_energy_f64(posd.data_ptr(), vel.data_ptr(), n, float(softening), float(g_const),
+                                             out_uk.data_ptr(), workspace.data_ptr(), _nbytes(workspace),
+                                             _lib.current_stream(vel.device)), "nbd_energy_f64")
+    return out_uk
+
+
+def potential_f64(posd, n: int, softening_sq: float, g_const: float, workspace, out=None) -> torch.Tensor:
+    """phi (n,) float64 of the n bodies of posd under each other, pair terms in float64; asynchronous."""
+    _chk_rows_f64(posd, None, n)
+    if out is None:
+        out = torch.empty((n,), dtype=F64, device=posd.device)
+    _chk(out, (n,), "phi_out", F64)
+    with _lib.on_device(posd.device):
+        _lib.check(_lib.lib().nbd_potential_f64(posd.data_ptr(), n, float(softening_sq), float(g_const), out.data_ptr(),
+                                                workspace.data_ptr(), _nbytes(workspace),
+                                                _lib.current_stream(posd.device)), "nbd_potential_f64")
+    return out
+
+
+def invariants_state_f64(pos, vel, mass, phi, out=None) -> torch.Tensor:
+    """`invariants` from a float64 state (pos, vel (n,3), mass (n)) and its potentials phi; asynchronous."""
+    n = pos.shape[0]
+    _chk(pos, (n, 3), "pos", F64); _chk(vel, (n, 3), "vel", F64); _chk(mass, (n,), "mass", F64)
+    _chk(phi, (n,), "phi", F64)
+    if out is None:
+        out = torch.empty(INVARIANT_ROW, dtype=F64, device=vel.device)
+    _chk(out, (INVARIANT_ROW,), "out_row", F64)
+    with _lib.on_device(vel.device):
+        _lib.check(_lib.lib().nbd_invariants_state_f64(pos.data_ptr(), vel.data_ptr(), mass.data_ptr(), phi.data_ptr(), n,
+                                                       out.data_ptr(), _lib.current_stream(vel.device)),
+                   "nbd_invariants_state_f64")
+    return out
+
+
 # ---------------------------------------------------- block-timestep Hermite integrator (csrc/direct_hermite_block.hip)
 HBLOCK_SCHED_INTS = 32          # NBD_HBLOCK_SCHED_INTS: {t_next, n_act, clamped, ...} of the block schedule
 

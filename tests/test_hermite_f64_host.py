@@ -1,0 +1,153 @@
+"""HermiteSimulator(dtype=torch.float64) without a GPU: the new C-ABI entries are declared and bound, the fp64 oracle stays
+inside the accuracy bar of the GPU tests under its own reorderings (so the bar is not tighter than fp64 allows), the
+restated diagnostics agree with diag_oracle where that one applies, the two-body oracle is in its convergent regime, and
+the constructor's ValueErrors come before anything touches a device."""
+import ctypes
+import inspect
+import os
+import re
+
+import numpy as np
+import pytest
+import torch
+
+import diag_oracle as do
+import hermite_f64_oracle as fo
+import hermite_oracle as ho
+from conftest import ROOT, load_golden
+from nbd import _lib
+
+ENTRIES = ("nbd_hermite_f64_workspace_bytes", "nbd_hermite_f64_plan", "nbd_hermite_f64_pack", "nbd_accel_jerk_f64",
+           "nbd_hermite_step_f64", "nbd_energy_f64", "nbd_potential_f64", "nbd_invariants_state_f64")
+
+
+def test_new_symbols_are_declared_and_bound():
+    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "nbd.h")).read(), flags=re.S)
+    L = _lib.lib()
+    for name in ENTRIES:
+        assert re.search(r"\b%s\s*\(" % name, text), f"{name} not declared in include/nbd.h"
+        assert name in _lib.SIGNATURES and getattr(L, name).argtypes == _lib.SIGNATURES[name][1]
+    assert L.nbd_abi_version() == _lib.ABI_VERSION == 2          # entries were added, nothing else changed
+
+
+def test_plan_and_argument_checks_without_a_gpu():
+    L = _lib.lib()
+    g, s, c = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    assert L.nbd_hermite_f64_plan(0, g, s, c) == -1 and L.nbd_hermite_f64_workspace_bytes(0) == 0
+    seen = set()
+    for n in (1, 2, 63, 64, 65, 130, 448, 449, 1000, 5000, 8192, 65536):
+        assert L.nbd_hermite_f64_plan(n, g, s, c) == 0
+        chunks = (n + 63) // 64
+        assert g.value == chunks and 1 <= s.value <= 64
+        assert s.value * 4 * c.value >= chunks and (c.value - 1) * s.value * 4 < chunks     # covered, and balanced
+        assert s.value == 1 or s.value * 4 <= chunks                                        # no slab without work
+        assert L.nbd_hermite_f64_workspace_bytes(n) == s.value * 6 * n * 8
+        seen.add(s.value > 1)
+    assert L.nbd_hermite_f64_plan(448, g, s, c) == 0 and s.value == 1       # the smallest n on each side of the only
+    assert L.nbd_hermite_f64_plan(449, g, s, c) == 0 and s.value == 2       # threshold below 8192: one slab -> several
+    assert seen == {False, True}
+    big = 1 << 30
+    assert L.nbd_accel_jerk_f64(None, None, -1, 0.01, 1.0, None, None, None, 0, 0, None) == -1
+    assert L.nbd_accel_jerk_f64(None, None, 4, 0.01, 1.0, None, None, None, 0, 0, None) == -1
+    assert L.nbd_accel_jerk_f64(0x1000, 0x2010, 4, 0.01, 1.0, 0x3000, 0x4000, 0x5000, big, 0, None) == -1   # 32 bytes
+    assert L.nbd_accel_jerk_f64(0x1000, 0x2000, 4, 0.01, 1.0, 0x3000, 0x4000, 0x5000, big, 65, None) == -1
+    assert L.nbd_accel_jerk_f64(0x1000, 0x2000, 4, 0.01, 1.0, 0x3000, 0x4000, 0x5000, 4 * 6 * 8 - 1, 0, None) == -2
+    assert L.nbd_accel_jerk_f64(0x1000, 0x2000, 4, 0.01, 1.0, 0x3000, 0x4000, 0x5000, 4 * 6 * 8, 2, None) == -2
+    assert L.nbd_accel_jerk_f64(None, None, 0, 0.01, 1.0, None, None, None, 0, 0, None) == 0
+    assert L.nbd_hermite_f64_pack(None, None, None, None, None, 4, 0.1, None, None, None) == -1
+    assert L.nbd_hermite_f64_pack(0x1000, 0x1000, 0x1000, None, 0x1000, 4, 0.1, 0x1000, 0x1000, None) == -1
+    assert L.nbd_hermite_step_f64(*([None] * 7), 4, 0.1, 0.01, 1.0, None, None, None, 0, None) == -1
+    assert L.nbd_hermite_step_f64(*([0x1000] * 7), 4, 0.1, 0.01, 1.0, 0x1000, 0x1000, None, 0, None) == -2
+    assert L.nbd_energy_f64(None, None, 4, 0.1, 1.0, 0x1000, None, 0, None) == -1
+    assert L.nbd_energy_f64(0x1000, 0x1000, 4, 0.1, 1.0, None, None, 0, None) == -1           # {U, K} is always written
+    assert L.nbd_energy_f64(0x1000, 0x1000, 4, 0.1, 1.0, 0x1000, 0x1000, 8, None) == -2
+    assert L.nbd_potential_f64(None, 4, 0.01, 1.0, None, None, 0, None) == -1
+    assert L.nbd_potential_f64(0x1000, 4, 0.01, 1.0, 0x1000, 0x1000, 8, None) == -2
+    assert L.nbd_potential_f64(None, 0, 0.01, 1.0, None, None, 0, None) == 0
+    assert L.nbd_invariants_state_f64(None, None, None, None, 4, 0x1000, None) == -1
+    assert L.nbd_invariants_state_f64(None, None, None, None, 0, None, None) == -1
+
+
+@pytest.mark.parametrize("n", [2, 65, 1000])
+def test_oracle_stays_inside_the_bar_under_reordering(n):
+    """The sources summed in reversed and in permuted order: the fp64 oracle against itself, at the bar the GPU is held
+    to. Were the bar tighter than fp64 summation allows, this would fail."""
+    x, v, m = fo.plummer_case(n, seed=40 + n)
+    g, eps2 = 1.0, 0.05 ** 2
+    a, j = fo.accel_jerk(x, v, m, g, eps2)
+    sa, sj = fo.accel_jerk_abs(x, v, m, g, eps2)
+    phi, sp = fo.potentials(x, m, g, eps2)
+    rng = np.random.default_rng(n)
+    for order in (np.arange(n)[::-1].copy(), rng.permutation(n)):
+        a2, j2 = fo.accel_jerk(x, v, m, g, eps2, order)
+        for got, ref, t, s_abs in ((a2, a, n, sa), (j2, j, 4 * n, sj), (fo.potentials(x, m, g, eps2, order)[0], phi, n, sp)):
+            ok, frac = fo.within(got, ref, t, s_abs)
+            assert ok, (n, frac)
+        s1, s_abs = fo.sums(x, v, m, phi)
+        s2, _ = fo.sums(x[order], v[order], m[order], phi[order])
+        ok, frac = fo.within(s2, s1, n, s_abs)
+        assert ok, (n, frac)
+        u1, k1, ua, ka = fo.reference_energies(x, v, m, g, 0.05)
+        u2, k2, _, _ = fo.reference_energies(x[order], v[order], m[order], g, 0.05)
+        assert fo.within(u2, u1, n * (n - 1) // 2, ua)[0] and fo.within(k2, k1, n, ka)[0]
+    # a sum with an fp32 intermediate misses the bar by orders of magnitude
+    a32 = fo.accel_jerk(x.astype(np.float32).astype(np.float64), v, m, g, eps2)[0]
+    assert not fo.within(a32, a, n, sa)[0] and fo.within(a32, a, n, sa)[1] > 1e3
+
+
+def test_restated_diagnostics_are_diag_oracle_on_fp32_inputs():
+    g = load_golden("direct_plummer_n300_ragged_mass")
+    x, v, m = (np.asarray(g[k], np.float64) for k in ("pos", "vel", "mass"))
+    gc, eps = float(g["g_const"]), float(g["softening"])
+    phi, _ = fo.potentials(x, m, gc, eps * eps)
+    assert np.array_equal(phi, do.potentials(x, m, gc, eps * eps))
+    assert np.array_equal(fo.sums(x, v, m, phi)[0], do.sums(x, v, m, phi)[0])
+    assert np.array_equal(fo.invariants_row(x, v, m, phi), do.invariants_row(x, v, m, phi))
+    assert fo.reference_energies(x, v, m, gc, eps)[:2] == do.reference_energies(x, v, m, gc, eps)
+
+
+def test_perturbed_inputs_are_not_fp32_representable_and_keep_a_massless_body():
+    g = load_golden("direct_plummer_n300_ragged_mass")
+    x, v, m = fo.perturbed(g["pos"], g["vel"], g["mass"], 7)
+    assert x.dtype == v.dtype == m.dtype == np.float64
+    assert (np.asarray(g["mass"]) == 0).sum() == (m == 0).sum() > 0
+    assert np.abs(x - g["pos"]).max() <= 1e-9 and np.abs(m - g["mass"]).max() <= 1e-9
+
+
+def test_two_body_oracle_is_in_the_convergent_regime():
+    """e = 0.5, eps = 0.1, one period: halving dt divides the oracle's position error (the difference to the run with
+    half the step) by 12 to 20 -- 4th order -- at every step count the GPU test compares. (The ENERGY error after this
+    whole period falls by 32 per halving, which is asserted too: it is what the GPU's energy error is compared with.)"""
+    x, v, m, period = ho.two_body(0.5)
+    runs = {s: ho.hermite_run(x, v, m, period / s, 1.0, 0.01, s) for s in (256, 512, 1024, 2048, 4096)}
+    d = [np.abs(runs[s][0] - runs[2 * s][0]).max() for s in (256, 512, 1024, 2048)]
+    for k in range(3):
+        assert 12.0 < d[k] / d[k + 1] < 20.0, d
+    e0 = fo.energy(x, v, m, 1.0, 0.01)
+    err = [abs(fo.energy(runs[s][0], runs[s][1], m, 1.0, 0.01) - e0) / abs(e0) for s in (256, 512, 1024, 2048)]
+    for k in range(3):
+        assert 24.0 < err[k] / err[k + 1] < 40.0, err
+    assert err[-1] > 1e-12                               # still far above fp64 rounding: the comparison means something
+
+
+def test_dtype_errors_come_before_any_device_work():
+    from galaxify import simulation
+    z = np.zeros((4, 3))
+    kw = dict(positions=z, velocities=z, masses=np.ones(4))
+    for bad in (torch.float16, torch.bfloat16, torch.int32, "float64", None):
+        with pytest.raises(ValueError, match="dtype"):
+            simulation.HermiteSimulator(dtype=bad, **kw)
+    with pytest.raises(ValueError, match="float64.*process_group|process_group.*float64"):
+        simulation.HermiteSimulator(dtype=torch.float64, process_group=object(), **kw)
+    # on a stub, as the diagnostics' refusals are tested: the check itself, and what the mode switches off
+    simulation.HermiteSimulator._check_dtype(torch.float32, object())
+    simulation.HermiteSimulator._check_dtype(torch.float64, None)
+    sim = object.__new__(simulation.HermiteSimulator)
+    assert sim._f64 is False
+    sim._f64, sim._sharded, sim.n = True, False, 100
+    assert not sim._graph_run_ok(64)
+    # the keyword is HermiteSimulator's alone
+    assert inspect.signature(simulation.HermiteSimulator.__init__).parameters["dtype"].default is torch.float32
+    for cls in (simulation.BlockHermiteSimulator, simulation.BatchedSimulator, simulation.LeapFrogSimulator,
+                simulation.EulerSimulator):
+        assert "dtype" not in inspect.signature(cls.__init__).parameters
