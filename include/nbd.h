@@ -429,6 +429,47 @@ int nbd_accel_jerk_active_f32(const float* posm, const float* velp, int n, const
                               float softening_sq, float g_const, float* acc_out, float* jerk_out, void* workspace,
                               size_t workspace_bytes, nbd_stream_t stream);
 
+/* ---- double-precision block-timestep Hermite (csrc/direct_hermite_block_f64.hip): the block scheme above with the
+ * number format of "double-precision Hermite". State, masses, a, j, G, softening_sq, dt, every body's own step constants,
+ * the pair arithmetic and all sums are fp64; ticks, levels and sched are the int32 arrays described above, and
+ * nbd_hblock_schedule is the scheduler of this mode too. posd / veld: the 32-byte-aligned rows of 4 doubles of
+ * nbd_hermite_f64_pack. A block step is nbd_hblock_schedule, then predict, force and correct (or nbd_hblock_step_f64,
+ * all three). With every body active the sums are nbd_hermite_step_f64's bits, so max_level = 0 is that step. i == j is
+ * dropped by index below softening_sq = 1e-24, otherwise by the term being an exact zero. Workspace:
+ * nbd_hblock_f64_workspace_bytes(n), 32-byte aligned; it holds the active list and, 32-byte aligned behind it, the partial
+ * sums (6 doubles per listed body and slab). Deterministic (no float atomics, no memsets in a step; the workspace may
+ * hold anything on entry). Eager-only, as the fp32 mode. An extension, used only when asked for. */
+size_t nbd_hblock_f64_workspace_bytes(int n);
+/* nbd_hblock_init_levels from acc, jerk double (n,3). */
+int nbd_hblock_init_levels_f64(const double* acc, const double* jerk, int n, double dt, double eta, int max_level,
+                               int* ticks, int* levels, int* sched, nbd_stream_t stream);
+/* posd = {x_p, m}, veld = {v_p, 0} of every body predicted to t_next = sched[0] over (t_next - ticks[i]) dt / 2^K, the
+ * step constants formed in fp64 from that step; zero rows behind n. pos, vel, acc, jerk: double (n,3); mass: double (n). */
+int nbd_hblock_predict_f64(const double* pos, const double* vel, const double* acc, const double* jerk,
+                           const double* mass, const int* ticks, int n, int max_level, double dt, int* sched,
+                           double* posd, double* veld, nbd_stream_t stream);
+/* Acceleration + jerk partial sums of the n_act listed bodies (n_act as schedule reported) under all n of posd / veld. */
+int nbd_hblock_force_f64(const double* posd, const double* veld, int n, int n_act, double softening_sq, void* workspace,
+                         size_t workspace_bytes, nbd_stream_t stream);
+/* The slabs in slab order, the corrector with each listed body's own step, new level, ticks[i] = t_next (0 at 2^K),
+ * posd[i] = {x1, m}. */
+int nbd_hblock_correct_f64(double* pos, double* vel, double* acc, double* jerk, const double* mass, int* ticks,
+                           int* levels, int n, int n_act, int max_level, double dt, double eta, double g_const,
+                           int* sched, double* posd, void* workspace, size_t workspace_bytes, nbd_stream_t stream);
+/* predict + force + correct of one block step (n_act >= 1). */
+int nbd_hblock_step_f64(double* pos, double* vel, double* acc, double* jerk, const double* mass, int* ticks, int* levels,
+                        int n, int n_act, int max_level, double dt, double eta, double softening_sq, double g_const,
+                        int* sched, double* posd, double* veld, void* workspace, size_t workspace_bytes,
+                        nbd_stream_t stream);
+/* The force alone (tests, profiling): acc_out, jerk_out double (n_act,3) of the bodies act[0..n_act) (a device int32
+ * list, any order) under all n bodies of posd / veld, in list order. slabs as in nbd_accel_jerk_f64: 0 for the plan's
+ * split of the sources, or an explicit count in [1, 64]; the workspace then needs the list part of
+ * nbd_hblock_f64_workspace_bytes(n) (4 bytes per body, n rounded up to a multiple of 8) plus slabs * 6 * n_act doubles.
+ * With every body listed the sums are nbd_accel_jerk_f64's bits at the same slab count. */
+int nbd_accel_jerk_active_f64(const double* posd, const double* veld, int n, const int* act, int n_act,
+                              double softening_sq, double g_const, double* acc_out, double* jerk_out, void* workspace,
+                              size_t workspace_bytes, int slabs, nbd_stream_t stream);
+
 /* ------------------------------------------------------------ surrogate models: graph build
  * Replace the torch_cluster kernels the reference reaches through PyG. Index-exact rule (the
  * reference delegates ties/truncation to torch_cluster; fixed here, see oracle/surrogate_oracle.py):

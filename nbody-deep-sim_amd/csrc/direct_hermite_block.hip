@@ -17,26 +17,21 @@
 // step constants come from hermite_dt() on the body's fp64 step (dt times its tick count): a body whose Delta is the
 // whole interval gets the shared step's bits. No float atomics (the clamp counter is an integer
 // atomic); the host reads {t_next, n_act} once per block step, so the path is eager-only.
+// The schedule record's layout and the level arithmetic (criterion, wanted_level, norm3) live in hermite_block_kernels.h,
+// shared with the float64 form of this unit, direct_hermite_block_f64.hip; hblock_schedule_kernel serves both.
 #include <hip/hip_runtime.h>
 #include <limits.h>
-#include <math.h>
 #include <stdint.h>
 
 #include "../../include/nbd.h"
 #include "direct_kernels.h"
+#include "hermite_block_kernels.h"
 #include "hermite_kernels.h"
 
 namespace {
 
-constexpr int kMaxLevel = 20;        // 2^20 ticks per interval: the tick count fits an int32 with room for t_i + d_i
 constexpr int kActSlabTarget = 512;  // small active sets: raise the slab count until groups x slabs reaches ~2 per CU
 constexpr int kActMaxSlabs = 256;
-
-// sched[NBD_HBLOCK_SCHED_INTS]: t_next and n_act of the block step being taken, the cumulative clamp count, the tick T
-// every body has reached (the last t_next, 0 at the start of an interval), the compaction's write cursor and its count
-// of finished workgroups (both 0 between launches), and the level histogram (bin k: bodies at level k)
-enum { kTNext = 0, kNAct = 1, kClamped = 2, kTCur = 3, kCursor = 4, kDone = 5, kHist = 8 };
-static_assert(kHist + kMaxLevel + 1 <= NBD_HBLOCK_SCHED_INTS, "sched holds the level histogram");
 
 // Acceleration + jerk of the n_act targets act[0..n_act) under all n sources: accel_jerk_kernel<MASKED, 2> with its
 // targets gathered through the index list (the same accel_jerk_body, so the same chunk stream and wave reduction).
@@ -57,26 +52,6 @@ __global__ __launch_bounds__(64 * kWaves, 6) void accel_jerk_active_kernel(
   accel_jerk_body<MASKED, 2>(posm, velp, n, posm, velp, i0, i1, i0, i1, c_begin, c_end, eps2, lds,
                              out + (size_t)blockIdx.y * 6 * n_act + t_base, n_act, min(kTgtPerWG, n_act - t_base));
 }
-
-// The Aarseth criterion sqrt(eta num / den). den = 0 (no jerk and no higher derivative: a lone body, or one in a
-// uniform field) allows any step: +inf, not the NaN of 0/0. A NaN that comes from NaN forces stays NaN (clamped).
-__device__ __forceinline__ double criterion(double eta, double num, double den) {
-  return den == 0.0 ? INFINITY : sqrt(eta * num / den);
-}
-
-// The level a criterion value asks for: the smallest k >= 0 with dt 2^-k <= crit, compared against the exact powers of
-// two. K + 1 means "deeper than K" (also for NaN, which no comparison accepts); +inf gives 0.
-__device__ __forceinline__ int wanted_level(double crit, double dt, int K) {
-  int k = 0;
-  double step = dt;
-  while (k <= K && !(step <= crit)) {
-    ++k;
-    step *= 0.5;
-  }
-  return k;
-}
-
-__device__ __forceinline__ double norm3(double x, double y, double z) { return sqrt(x * x + y * y + z * z); }
 
 // Initial levels from dt_i = (eta / 2) |a| / |j| in fp64 (+inf where j = 0); every tick to 0. Levels deeper than K are clamped and counted.
 __global__ __launch_bounds__(256) void hblock_init_kernel(const float* __restrict__ acc, const float* __restrict__ jerk,
@@ -297,8 +272,6 @@ int launch_active(const float* posm, const float* velp, int n, const int* act, i
     accel_jerk_active_kernel<false><<<grid, block, 0, st>>>(pm, vp, n, act, n_act, c.q, c.r, eps2, slabs);
   return launch_status();
 }
-
-bool bad_level(int K) { return K < 0 || K > kMaxLevel; }
 
 int* ws_act(void* ws) { return static_cast<int*>(ws); }
 float* ws_slabs(void* ws, int n) { return reinterpret_cast<float*>(static_cast<char*>(ws) + act_bytes(n)); }

@@ -1,0 +1,176 @@
+// hermite_f64_kernels.h -- what the double-precision Hermite translation units share (direct_hermite_f64.hip: all targets,
+// shared timestep, and the diagnostics; direct_hermite_block_f64.hip: an active list of targets, block timesteps): the
+// packed-row type and its alignment checks, the reciprocal square root (rsqrt_f64), the acceleration-plus-jerk pair functor
+// (AccelJerkPair), the wave body that walks the source chunks with a functor (walk_f64) and the geometry of a pair launch
+// (F64Plan, plan_f64). As in hermite_kernels.h there is one copy of every rounded operation: a block step whose active
+// list is every body has the shared step's bits because both kernels are a prologue and a call of the same walk_f64.
+// The definitions sit in an anonymous namespace: every translation unit that includes this file gets its own inlined copies.
+#pragma once
+#include "direct_kernels.h"
+#include "hermite_kernels.h"
+
+namespace {
+
+typedef double d4 __attribute__((ext_vector_type(4)));
+
+constexpr int kTgtF64 = 64;                      // targets per workgroup: one per lane, = one source chunk
+constexpr int kRowQuads = 2;                     // 16-byte LDS-DMA pieces per 32-byte row
+constexpr int kChunkQuads = kChunk * kRowQuads;  // 128 quads = 2 KiB per chunk and array
+constexpr double kEps2MaskedF64 = 1e-24;         // the fp32 kernels' rule (kEps2Masked): below it i == j goes by index
+constexpr int kTargetWGs = 1024;                 // ~4 workgroups per CU (32 KiB of LDS each: at most 5 fit)
+
+inline bool misaligned32(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 31) != 0; }
+inline bool misaligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7) != 0; }
+
+// x^(-1/2) to about 1 ulp. y0 = v_rsq_f64 (a compiler builtin: hipcc pads the transcendental -> VALU wait state for its
+// consumers). With h = 1 - x y^2 formed by one fma from the rounded x y (its absolute error is 2^-53, and h is what the
+// correction is proportional to): y1 = y0 (1 + h/2 + 3 h^2/8) leaves O(h^3), y2 = y1 (1 + h/2) squares that.
+__device__ __forceinline__ double rsqrt_f64(const double x) {
+  const double y0 = __builtin_amdgcn_rsq(x);
+  double t = x * y0;
+  double h = __builtin_fma(-t, y0, 1.0);
+  const double y1 = __builtin_fma(y0 * h, __builtin_fma(0.375, h, 0.5), y0);
+  t = x * y1;
+  h = __builtin_fma(-t, y1, 1.0);
+  return __builtin_fma(0.5 * y1, h, y1);
+}
+
+// ---- the pair functors. A functor holds its lane's target and partial sums; pair<MASKED>(p, q, j) adds source j (row p
+// of posd, row q of veld where kVel) -- MASKED: exclusions by index, else by the arithmetic; out(k) is partial sum k of kOut.
+
+// a_i = sum_j m_j r_ij s^3, j_i = sum_j m_j (v_ij s^3 - 3 (r_ij.v_ij) s^5 r_ij), s = (|r_ij|^2 + eps^2)^(-1/2): the
+// operations of jerk_pair_masked / jerk_block (hermite_kernels.h) one for one. acc[3..5] accumulates w dv, acc[6..8]
+// (r.v s^2) w dr; j = acc[3..5] - 3 acc[6..8]. MASKED drops j == i and the padding behind n by a select on s (after the
+// refinement: whatever the dropped r^2 gave, NaN included, never reaches a sum). Un-masked, i == j and a padding row add
+// exact zeros: dr = dv = 0 resp. m = 0, with s finite because eps^2 >= kEps2MaskedF64.
+struct AccelJerkPair {
+  static constexpr bool kVel = true;
+  static constexpr int kOut = 6;
+  double xi, yi, zi, ui, vi, wi, e2;
+  double acc[9];
+  int i, n;
+
+  __device__ __forceinline__ AccelJerkPair(const d4 tp, const d4 tv, double eps2, int i_, int n_)
+      : xi(tp.x), yi(tp.y), zi(tp.z), ui(tv.x), vi(tv.y), wi(tv.z), e2(eps2), i(i_), n(n_) {
+#pragma unroll
+    for (int k = 0; k < 9; ++k) acc[k] = 0.0;
+  }
+
+  template <bool MASKED>
+  __device__ __forceinline__ void pair(const d4 p, const d4 q, int j) {
+    const double dx = p.x - xi, dy = p.y - yi, dz = p.z - zi;      // r_j - r_i
+    const double du = q.x - ui, dv = q.y - vi, dw = q.z - wi;
+    double r2 = __builtin_fma(dx, dx, e2);
+    r2 = __builtin_fma(dy, dy, r2);
+    r2 = __builtin_fma(dz, dz, r2);
+    double rv = dx * du;
+    rv = __builtin_fma(dy, dv, rv);
+    rv = __builtin_fma(dz, dw, rv);
+    double s = rsqrt_f64(r2);
+    if (MASKED) s = (j < n && j != i) ? s : 0.0;
+    const double s2 = s * s;
+    const double w = (s2 * s) * p.w;
+    const double c = (rv * s2) * w;
+    acc[0] = __builtin_fma(w, dx, acc[0]);
+    acc[1] = __builtin_fma(w, dy, acc[1]);
+    acc[2] = __builtin_fma(w, dz, acc[2]);
+    acc[3] = __builtin_fma(w, du, acc[3]);
+    acc[4] = __builtin_fma(w, dv, acc[4]);
+    acc[5] = __builtin_fma(w, dw, acc[5]);
+    acc[6] = __builtin_fma(c, dx, acc[6]);
+    acc[7] = __builtin_fma(c, dy, acc[7]);
+    acc[8] = __builtin_fma(c, dz, acc[8]);
+  }
+
+  __device__ __forceinline__ double out(int k) const { return k < 3 ? acc[k] : acc[k] - 3.0 * acc[k + 3]; }
+};
+
+// LDS of a workgroup, in 16-byte quads: [wave][buffer][pos (| vel)][128]
+template <bool VEL>
+constexpr int stage_quads() { return 2 * (VEL ? 2 : 1) * kChunkQuads; }
+
+// The wave body. The wave walks the chunks [c_begin, c_end) of posd (and veld): chunk c = rows [64 c, 64 c + 64), 2 KiB per
+// array, fetched as two 1-KiB LDS-DMA pieces (lane l brings quads l and 64 + l of the chunk, so the rows land as they lie
+// in memory), the next chunk in flight while this one is used. all_masked, or the chunk own_chunk (the one that holds the
+// group's own indices; -1 for gathered targets, which have none), takes pair<true>, every other chunk pair<false>. Then
+// the 4 waves' kOut partials per lane go through LDS -- a wave's staging is free after its last chunk: its loads have
+// landed and its reads precede these writes -- and are added in wave order into dst[k * stride + t], t < n_valid.
+template <class Pair>
+__device__ __forceinline__ void walk_f64(Pair& pr, const d4* __restrict__ posd, const d4* __restrict__ veld, int c_begin,
+                                         int c_end, bool all_masked, int own_chunk, f4* lds, double* __restrict__ dst,
+                                         size_t stride, int n_valid) {
+  constexpr bool VEL = Pair::kVel;
+  constexpr int kArr = VEL ? 2 : 1;
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  f4* stage = &lds[wave * stage_quads<VEL>()];
+  const f4* p_lane = reinterpret_cast<const f4*>(posd) + lane;
+  const f4* v_lane = reinterpret_cast<const f4*>(veld) + lane;
+  auto fetch = [&](int c, int b) {
+    const size_t at = (size_t)c * kChunkQuads;
+    f4* to = stage + b * kArr * kChunkQuads;
+    __builtin_amdgcn_global_load_lds(GPTR(p_lane + at), LPTR(to), 16, 0, 0);
+    __builtin_amdgcn_global_load_lds(GPTR(p_lane + at + 64), LPTR(to + 64), 16, 0, 0);
+    if (VEL) {
+      __builtin_amdgcn_global_load_lds(GPTR(v_lane + at), LPTR(to + kChunkQuads), 16, 0, 0);
+      __builtin_amdgcn_global_load_lds(GPTR(v_lane + at + 64), LPTR(to + kChunkQuads + 64), 16, 0, 0);
+    }
+  };
+  if (c_begin < c_end) fetch(c_begin, 0);
+  for (int c = c_begin; c < c_end; ++c) {
+    const int b = (c - c_begin) & 1;
+    if (c + 1 < c_end) {
+      fetch(c + 1, b ^ 1);
+      // chunk c has landed, c + 1 (2 loads per array) in flight
+      if (VEL) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+      else asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
+    } else {
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
+    const d4* bp = reinterpret_cast<const d4*>(stage + b * kArr * kChunkQuads);
+    const d4* bv = VEL ? bp + kChunk : bp;
+    const int j0 = c * kChunk;
+    if (all_masked || c == own_chunk) {
+#pragma unroll 2
+      for (int j = 0; j < kChunk; ++j) pr.template pair<true>(bp[j], bv[j], j0 + j);
+    } else {
+#pragma unroll 4
+      for (int j = 0; j < kChunk; ++j) pr.template pair<false>(bp[j], bv[j], j0 + j);
+    }
+  }
+
+  constexpr int kPart = stage_quads<VEL>() * 2;                      // doubles per wave; [k][64] in the first kOut * 64
+  static_assert(Pair::kOut * 64 <= kPart, "the partials must fit a wave's staging");
+  double* red = reinterpret_cast<double*>(lds);
+#pragma unroll
+  for (int k = 0; k < Pair::kOut; ++k) red[wave * kPart + k * 64 + lane] = pr.out(k);
+  __syncthreads();
+  for (int o = threadIdx.x; o < Pair::kOut * 64; o += 64 * kWaves) {
+    const int k = o >> 6, t = o & 63;
+    if (t >= n_valid) continue;
+    double sum = red[o];
+#pragma unroll
+    for (int w = 1; w < kWaves; ++w) sum += red[w * kPart + o];
+    dst[(size_t)k * stride + t] = sum;
+  }
+}
+
+// The geometry of a pair launch: groups of 64 targets, and enough slabs for ~kTargetWGs workgroups as long as every wave
+// of a slab still has a chunk to walk. n_tgt targets under n sources; n_tgt = n is the shared step's plan.
+struct F64Plan { int groups, slabs, n_chunks; };
+
+inline F64Plan plan_f64(int n, int n_tgt) {
+  F64Plan p;
+  p.n_chunks = ceil_div(n, kChunk);
+  p.groups = ceil_div(n_tgt, kTgtF64);
+  int slabs = ceil_div(kTargetWGs, p.groups);
+  const int cap = p.n_chunks / kWaves;
+  slabs = slabs > cap ? cap : slabs;
+  slabs = slabs > kMaxSlabs ? kMaxSlabs : slabs;
+  p.slabs = slabs < 1 ? 1 : slabs;
+  return p;
+}
+
+inline F64Plan plan_f64(int n) { return plan_f64(n, n); }
+
+}  // namespace

@@ -7,7 +7,8 @@
 //     (chunk_split on the host, wave_chunk_range in a kernel);
 //   - the O(N) arithmetic: the fp32 step constants (hermite_dt), the predictor (hermite_predict), the fixed-order slab sum
 //     (hermite_slab_sum) and the corrector (hermite_correct); the constants, the predictor and the corrector are templates
-//     of the scalar type, instantiated with double by direct_hermite_f64.hip (the float instantiation is the code it was);
+//     of the scalar type, instantiated with double by direct_hermite_f64.hip and direct_hermite_block_f64.hip (the float
+//     instantiation is the code it was);
 //   - the launch plan of a force launch (JerkPlan, plan_jerk).
 // A kernel of one of the units is a prologue that says which targets, which chunks, which rows and which constants, and
 // calls of these: a scene of a batch, or a block step at level 0, is bit-identical to the shared-timestep step because
@@ -225,7 +226,7 @@ inline JerkPlan plan_jerk(int n, int n_tgt) {
 
 // fp32 step constants, each formed in double and rounded once. On the device too: a block-timestep body forms them from
 // its own fp64 step, so one whose step is the whole interval gets the shared step's bits.
-// (T = double, direct_hermite_f64.hip: the same five doubles, not rounded again.)
+// (T = double, direct_hermite_f64.hip and direct_hermite_block_f64.hip: the same five doubles, not rounded again.)
 template <class T>
 struct HermiteStep { T dt, dt_half, dt2_half, dt3_sixth, dt2_twelfth; };
 using HermiteDt = HermiteStep<float>;
@@ -239,7 +240,7 @@ __host__ __device__ inline HermiteDt hermite_dt(double dt) { return hermite_step
 
 // One component of the predictor, each product and sum rounded on its own (the build has -ffp-contract=off):
 // x_p = x + v dt + a dt^2/2 + j dt^3/6, v_p = v + a dt + j dt^2/2.
-// T = float for the fp32 units, double for direct_hermite_f64.hip.
+// T = float for the fp32 units, double for direct_hermite_f64.hip and direct_hermite_block_f64.hip.
 template <class T>
 struct PosVelT { T x, v; };
 using PosVel = PosVelT<float>;

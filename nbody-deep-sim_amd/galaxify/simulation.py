@@ -24,6 +24,9 @@ Fourth addition: `BlockHermiteSimulator`, the same scheme with individual block 
 Sixth addition: `HermiteSimulator(dtype=torch.float64)`, the same scheme with float64 state, scalars and pair arithmetic
 (csrc/direct_hermite_f64.hip). The default stays float32 and takes the paths it took.
 
+Seventh addition: `BlockHermiteSimulator(dtype=torch.float64)`, block timesteps in that float64 format
+(csrc/direct_hermite_block_f64.hip). Again the default is float32 and takes the paths it took.
+
 Fifth addition: `compute_potentials()` / `compute_invariants()` and `calc_invariants=`: the per-body potential of the
 softening the force uses and the conserved quantities formed from it (`Invariants`; csrc/direct_diag.hip).
 `compute_energies()`, `u_energy` and `k_energy` keep the reference's convention.
@@ -831,26 +834,39 @@ class BlockHermiteSimulator(HermiteSimulator):
     Counters (cumulative Python ints): `block_steps`, `pair_interactions` (sum of n_act * n over block steps) and `clamped`
     (levels the criterion wanted deeper than max_level, NaN criteria included). `accelerations` and `jerks` are updated in
     place. Eager-only: every block step reads {t_next, n_act} back to the host (csrc/direct_hermite_block.hip). Setting
-    `level_history` to a list records a CPU copy of `levels` after every block step (tests, diagnostics)."""
+    `level_history` to a list records a CPU copy of `levels` after every block step (tests, diagnostics).
+
+    `dtype` is HermiteSimulator's keyword and is handed on to it (default torch.float32; anything but float32 or float64
+    raises ValueError before anything is allocated).
+    With `dtype=torch.float64` (csrc/direct_hermite_block_f64.hip) the same scheme runs in the number
+    format of HermiteSimulator(dtype=torch.float64): positions, velocities, masses, accelerations and jerks are float64
+    device tensors, g_const, softening ** 2, dt and every body's own step constants go to the kernels as doubles, and the
+    pair arithmetic and all sums are float64; levels, ticks and the schedule stay int32. An fp32 block run stops gaining
+    from a smaller eta at the fp32 floor of the orbit; this mode follows the criterion down to float64 rounding. With
+    max_level=0 it is HermiteSimulator(dtype=torch.float64) bit for bit. compute_*() and run() are that class's."""
 
     MAX_LEVEL_LIMIT = 20
 
     def __init__(self, *, positions, velocities, masses, g_const: float = 1.0, softening: float = 0.1,
                  dt: float = 0.01, calc_energy: bool = True, device: str = None, process_group=None,
-                 eta: float = 0.02, max_level: int = 10, calc_invariants: bool = False):
+                 eta: float = 0.02, max_level: int = 10, calc_invariants: bool = False, **hermite_kw):
+        # hermite_kw: the keywords that are HermiteSimulator's own and mean here what they mean there -- `dtype`
+        # (default torch.float32). They go to HermiteSimulator.__init__ as given, which refuses a name it does not know.
         if process_group is not None:
             raise ValueError("BlockHermiteSimulator: there is no range-sharded block-timestep step; process_group is not "
                              "supported")
+        self._check_dtype(hermite_kw.get("dtype", torch.float32), None)     # before anything is resolved or allocated
         super().__init__(positions=positions, velocities=velocities, masses=masses, g_const=g_const,
                          softening=softening, dt=dt, calc_energy=calc_energy, device=device,
-                         calc_invariants=calc_invariants)
+                         calc_invariants=calc_invariants, **hermite_kw)
         self.eta = eta
         self.max_level = max_level
         self.levels = torch.zeros(self.n, dtype=torch.int32, device=self.device)
         self._ticks = torch.zeros(self.n, dtype=torch.int32, device=self.device)
         self._sched = torch.zeros(direct.HBLOCK_SCHED_INTS, dtype=torch.int32, device=self.device)
         self._sched_host = torch.zeros(4, dtype=torch.int32).pin_memory()
-        self._bws = direct.hblock_workspace(max(self.n, 1), self.device)
+        workspace = direct.hblock_f64_workspace if self._f64 else direct.hblock_workspace
+        self._bws = workspace(max(self.n, 1), self.device)
         self.block_steps = 0
         self.pair_interactions = 0
         self.clamped = 0
@@ -869,13 +885,22 @@ class BlockHermiteSimulator(HermiteSimulator):
         self._leveled_for = (self.dt, self.eta, self.max_level)
         if self.n == 0:
             return
-        direct.hblock_init_levels(self.accelerations, self.jerks, self.dt, self.eta, self.max_level, self._ticks,
-                                  self.levels, self._sched)
+        init = direct.hblock_init_levels_f64 if self._f64 else direct.hblock_init_levels
+        init(self.accelerations, self.jerks, self.dt, self.eta, self.max_level, self._ticks, self.levels, self._sched)
         self._read_clamped()
 
     def _read_clamped(self):
         self._sched_host.copy_(self._sched[:4])
         self.clamped = int(self._sched_host[2])
+
+    def _block_step(self, n_act: int):
+        """Predict, force and correct of the block step the schedule has just listed."""
+        state = (self.positions, self.velocities, self.accelerations, self.jerks, self.masses, self._ticks, self.levels,
+                 n_act, self.max_level, self.dt, self.eta)
+        if self._f64:
+            direct.hblock_step_f64(*state, *self._f64_scalars(), self._sched, self._posd, self._veld, self._bws)
+        else:
+            direct.hblock_step(*state, self._eps2, self._g, self._sched, self._posm, self._velp, self._bws)
 
     def step(self):
         """One output interval: block steps until every body is back at tick 2^max_level (at most 2^max_level of them)."""
@@ -893,9 +918,7 @@ class BlockHermiteSimulator(HermiteSimulator):
             if not (t_prev < t_next <= end and 1 <= n_act <= self.n):
                 raise RuntimeError(f"BlockHermiteSimulator: corrupt schedule (t_next={t_next}, n_act={n_act}, "
                                    f"previous tick {t_prev})")
-            direct.hblock_step(self.positions, self.velocities, self.accelerations, self.jerks, self.masses,
-                               self._ticks, self.levels, n_act, K, self.dt, self.eta, self._eps2, self._g, self._sched,
-                               self._posm, self._velp, self._bws)
+            self._block_step(n_act)
             self.block_steps += 1
             self.pair_interactions += n_act * self.n
             if self.level_history is not None:

@@ -249,6 +249,21 @@ SIGNATURES = {
                                     c_size_t, c_void_p]),
     "nbd_accel_jerk_active_f32": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_float, c_float, c_void_p,
                                           c_void_p, c_void_p, c_size_t, c_void_p]),
+    # --- double-precision block-timestep Hermite (csrc/direct_hermite_block_f64.hip)
+    "nbd_hblock_f64_workspace_bytes": (c_size_t, [c_int]),
+    "nbd_hblock_init_levels_f64": (c_int, [c_void_p, c_void_p, c_int, c_double, c_double, c_int, c_void_p, c_void_p,
+                                           c_void_p, c_void_p]),
+    "nbd_hblock_predict_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
+                                       c_double, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "nbd_hblock_force_f64": (c_int, [c_void_p, c_void_p, c_int, c_int, c_double, c_void_p, c_size_t, c_void_p]),
+    "nbd_hblock_correct_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                                       c_int, c_int, c_double, c_double, c_double, c_void_p, c_void_p, c_void_p,
+                                       c_size_t, c_void_p]),
+    "nbd_hblock_step_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
+                                    c_int, c_double, c_double, c_double, c_double, c_void_p, c_void_p, c_void_p,
+                                    c_void_p, c_size_t, c_void_p]),
+    "nbd_accel_jerk_active_f64": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_double, c_double, c_void_p,
+                                          c_void_p, c_void_p, c_size_t, c_int, c_void_p]),
     # --- generators on the device (csrc/generators.hip)
     "nbd_disk_workspace_bytes": (c_size_t, [c_int]),
     "nbd_disk_from_draws_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_double, c_double, c_double, c_double,

@@ -640,6 +640,99 @@ def accel_jerk_active(posm, velp, n: int, act, softening_sq: float, g_const: flo
             _lib.current_stream(dev)), "nbd_accel_jerk_active_f32")
     return acc_out, jerk_out
 
+
+# ------------------------------- double-precision block-timestep Hermite (csrc/direct_hermite_block_f64.hip)
+def hblock_f64_workspace(n: int, device, slabs: int = 0, n_act: int = 0) -> torch.Tensor:
+    """Active list + float64 partial sums of one block step (nbd_hblock_f64_workspace_bytes), or of accel_jerk_active_f64
+    with an explicit slab count on n_act targets."""
+    need = _lib.lib().nbd_hblock_f64_workspace_bytes(int(n))
+    return alloc_bytes(max(need, (int(n) + 7) // 8 * 32 + int(slabs) * 6 * int(n_act) * 8), device)
+
+
+def _chk_hblock_f64(pos, vel, acc, jerk, mass, ticks, levels, sched, posd, veld) -> int:
+    n = pos.shape[0]
+    for t, nm in ((pos, "pos"), (vel, "vel"), (acc, "acc"), (jerk, "jerk")):
+        _chk(t, (n, 3), nm, F64)
+    _chk(mass, (n,), "mass", F64)
+    _chk_rows_f64(posd, veld, n)
+    _chk(ticks, (n,), "ticks", torch.int32); _chk(levels, (n,), "levels", torch.int32)
+    _chk(sched, (HBLOCK_SCHED_INTS,), "sched", torch.int32)
+    return n
+
+
+def hblock_init_levels_f64(acc, jerk, dt: float, eta: float, max_level: int, ticks, levels, sched) -> None:
+    """hblock_init_levels from float64 acc, jerk."""
+    n = acc.shape[0]
+    _chk(acc, (n, 3), "acc", F64); _chk(jerk, (n, 3), "jerk", F64)
+    _chk(ticks, (n,), "ticks", torch.int32); _chk(levels, (n,), "levels", torch.int32)
+    _chk(sched, (HBLOCK_SCHED_INTS,), "sched", torch.int32)
+    with _lib.on_device(acc.device):
+        _lib.check(_lib.lib().nbd_hblock_init_levels_f64(
+            acc.data_ptr(), jerk.data_ptr(), n, float(dt), float(eta), int(max_level), ticks.data_ptr(),
+            levels.data_ptr(), sched.data_ptr(), _lib.current_stream(acc.device)), "nbd_hblock_init_levels_f64")
+
+
+def hblock_predict_f64(pos, vel, acc, jerk, mass, ticks, levels, max_level: int, dt: float, sched, posd, veld) -> None:
+    """First launch of a float64 block step: every body predicted to t_next = sched[0] into posd / veld."""
+    n = _chk_hblock_f64(pos, vel, acc, jerk, mass, ticks, levels, sched, posd, veld)
+    with _lib.on_device(pos.device):
+        _lib.check(_lib.lib().nbd_hblock_predict_f64(
+            pos.data_ptr(), vel.data_ptr(), acc.data_ptr(), jerk.data_ptr(), mass.data_ptr(), ticks.data_ptr(), n,
+            int(max_level), float(dt), sched.data_ptr(), posd.data_ptr(), veld.data_ptr(),
+            _lib.current_stream(pos.device)), "nbd_hblock_predict_f64")
+
+
+def hblock_force_f64(posd, veld, n: int, n_act: int, softening_sq: float, workspace) -> None:
+    """Second launch: the partial sums of the n_act bodies the schedule listed in the workspace."""
+    _chk_rows_f64(posd, veld, n)
+    with _lib.on_device(posd.device):
+        _lib.check(_lib.lib().nbd_hblock_force_f64(
+            posd.data_ptr(), veld.data_ptr(), n, int(n_act), float(softening_sq), workspace.data_ptr(),
+            _nbytes(workspace), _lib.current_stream(posd.device)), "nbd_hblock_force_f64")
+
+
+def hblock_correct_f64(pos, vel, acc, jerk, mass, ticks, levels, n_act: int, max_level: int, dt: float, eta: float,
+                       g_const: float, sched, posd, workspace) -> None:
+    """Third launch: slab sum, corrector and new level of the listed bodies; posd = {x1, m} for them."""
+    n = _chk_hblock_f64(pos, vel, acc, jerk, mass, ticks, levels, sched, posd, None)
+    with _lib.on_device(pos.device):
+        _lib.check(_lib.lib().nbd_hblock_correct_f64(
+            pos.data_ptr(), vel.data_ptr(), acc.data_ptr(), jerk.data_ptr(), mass.data_ptr(), ticks.data_ptr(),
+            levels.data_ptr(), n, int(n_act), int(max_level), float(dt), float(eta), float(g_const), sched.data_ptr(),
+            posd.data_ptr(), workspace.data_ptr(), _nbytes(workspace), _lib.current_stream(pos.device)),
+            "nbd_hblock_correct_f64")
+
+
+def hblock_step_f64(pos, vel, acc, jerk, mass, ticks, levels, n_act: int, max_level: int, dt: float, eta: float,
+                    softening_sq: float, g_const: float, sched, posd, veld, workspace) -> None:
+    """hblock_step in float64 (three launches): dt, eta, softening_sq and g_const go in as the Python doubles."""
+    n = _chk_hblock_f64(pos, vel, acc, jerk, mass, ticks, levels, sched, posd, veld)
+    with _lib.on_device(pos.device):
+        _lib.check(_lib.lib().nbd_hblock_step_f64(
+            pos.data_ptr(), vel.data_ptr(), acc.data_ptr(), jerk.data_ptr(), mass.data_ptr(), ticks.data_ptr(),
+            levels.data_ptr(), n, int(n_act), int(max_level), float(dt), float(eta), float(softening_sq),
+            float(g_const), sched.data_ptr(), posd.data_ptr(), veld.data_ptr(), workspace.data_ptr(),
+            _nbytes(workspace), _lib.current_stream(pos.device)), "nbd_hblock_step_f64")
+
+
+def accel_jerk_active_f64(posd, veld, n: int, act, softening_sq: float, g_const: float, workspace=None, slabs: int = 0):
+    """accel_jerk_active in float64: (acc, jerk), each (len(act), 3) float64, in list order. slabs: 0 = the plan's source
+    split, else that many. The all-bodies list gives accel_jerk_f64's bits at the same slab count."""
+    _chk_rows_f64(posd, veld, n)
+    _chk(act, None, "act", torch.int32)
+    n_act = act.numel()
+    dev = posd.device
+    acc_out = torch.empty((n_act, 3), dtype=F64, device=dev)
+    jerk_out = torch.empty((n_act, 3), dtype=F64, device=dev)
+    if workspace is None:                       # a given workspace is checked by the entry, against what this call uses
+        workspace = hblock_f64_workspace(n, dev, slabs, n_act)
+    with _lib.on_device(dev):
+        _lib.check(_lib.lib().nbd_accel_jerk_active_f64(
+            posd.data_ptr(), veld.data_ptr(), n, act.data_ptr(), n_act, float(softening_sq), float(g_const),
+            acc_out.data_ptr(), jerk_out.data_ptr(), workspace.data_ptr(), _nbytes(workspace), int(slabs),
+            _lib.current_stream(dev)), "nbd_accel_jerk_active_f64")
+    return acc_out, jerk_out
+
 # ---------------------------------------------------------------- batched direct integrator (csrc/direct_batch.hip)
 class BatchPlan:
     """The host offsets of an ensemble of scenes and the device work list built from them (nbd_batch_plan /

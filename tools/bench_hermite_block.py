@@ -1,6 +1,6 @@
 """Block-timestep Hermite (BlockHermiteSimulator) on the MI355X, in one run.
 
-  python tools/bench_hermite_block.py [--out FILE]
+  python tools/bench_hermite_block.py [--out FILE] [--dtype float64]
 
 1. The active-subset force at n = 65 536 sources: nbd_accel_jerk_active_f32 (kernel + slab sum) for n_act = 65 536,
    8 192, 1 024, 128, interleaved with nbd_accel_jerk_f32 on the same state; time and pair rate of each.
@@ -11,6 +11,14 @@
    sweep; error against the exact closed orbit and the wall time of the steps (all launch-bound at n = 2). (b) A Plummer
    sphere of n = 16 384, eps = 0.01, one time unit: shared dt = 1/64 ... 1/1024 and block eta sweeps (dt = 1/16,
    max_level 10), max-body and 99.9th-percentile position error against a block run at eta = 0.0025, with wall time.
+
+With --dtype float64 (BlockHermiteSimulator(dtype=torch.float64), csrc/direct_hermite_block_f64.hip), all in one process:
+1. nbd_accel_jerk_active_f64 with every body listed against nbd_accel_jerk_f64 (the same wave body and plan), and shorter
+   lists, interleaved as above.
+2. The block-step cost fit of both precisions, from the same run.
+3. The e = 0.9 orbit (eps = 0, one period as 4 output steps, max_level 16): eta = 0.01 ... 0.000625 in float64 beside
+   float32; error, pair interactions, clamped levels and wall time per eta.
+The default output is profiles/r13_hermite_block_f64.json.
 """
 import argparse
 import json
@@ -72,9 +80,37 @@ def active_force(n=65536, reps=20):
     return rows
 
 
-def block_step_cost(n=65536, K=10, reps=15):
+def active_force_f64(n=65536, reps=10):
     p, v, m = generate_plummer(n, seed=1)
-    kw = dict(positions=p, velocities=v, masses=m, softening=0.01, dt=1e-3, calc_energy=False, device="cuda")
+    dev = torch.device("cuda")
+    f64 = lambda a: torch.tensor(np.asarray(a, np.float64), dtype=torch.float64, device=dev)      # noqa: E731
+    posd, veld = direct.alloc_rows_f64(n, dev), direct.alloc_rows_f64(n, dev)
+    direct.hermite_f64_pack(f64(p), f64(v), f64(m), posd, veld)
+    eps2 = 0.01 ** 2
+    hws, bws = direct.hermite_f64_workspace(n, dev), direct.hblock_f64_workspace(n, dev)
+    rng = np.random.default_rng(0)
+    rows = []
+    for n_act in (65536, 8192, 1024, 128):
+        act = torch.tensor(np.sort(rng.permutation(n)[:n_act]), dtype=torch.int32, device=dev)
+        f_all = (lambda: direct.accel_jerk_f64(posd, veld, n, eps2, 1.0, workspace=hws))
+        f_act = (lambda: direct.accel_jerk_active_f64(posd, veld, n, act, eps2, 1.0, workspace=bws))
+        for _ in range(2):
+            f_all(); f_act()
+        full, part = [], []
+        for _ in range(3):                                   # interleaved rounds
+            full.append(_event_ms(f_all, reps)); part.append(_event_ms(f_act, reps))
+        full_ms, act_ms = float(np.median(full)), float(np.median(part))
+        rows.append({"n": n, "n_act": n_act, "accel_jerk_f64_ms": full_ms, "active_f64_ms": act_ms,
+                     "ratio_to_full": act_ms / full_ms,
+                     "pair_rate_fraction": (n_act / act_ms) / (n / full_ms)})
+        print(json.dumps(rows[-1]), flush=True)
+    return rows
+
+
+def block_step_cost(n=65536, K=10, reps=15, dtype=torch.float32):
+    p, v, m = generate_plummer(n, seed=1)
+    kw = dict(positions=p, velocities=v, masses=m, softening=0.01, dt=1e-3, calc_energy=False, device="cuda",
+              dtype=dtype)
     he = simulation.HermiteSimulator(**kw)
     for _ in range(3):
         he.step()
@@ -94,9 +130,7 @@ def block_step_cost(n=65536, K=10, reps=15):
             t0 = time.perf_counter()
             direct.hblock_schedule(sim.levels, K, sim._sched, sim._bws, host_sched=host)
             got = int(host[1])
-            direct.hblock_step(sim.positions, sim.velocities, sim.accelerations, sim.jerks, sim.masses, sim._ticks,
-                               sim.levels, got, K, sim.dt, sim.eta, sim._eps2, sim._g, sim._sched, sim._posm, sim._velp,
-                               sim._bws)
+            sim._block_step(got)
             torch.cuda.synchronize()
             if r >= 2:
                 wall.append((time.perf_counter() - t0) * 1e3)
@@ -106,8 +140,8 @@ def block_step_cost(n=65536, K=10, reps=15):
     f = np.array([q["n_act"] / n for q in pts])
     t = np.array([q["block_step_ms"] for q in pts])
     slope, icpt = np.polyfit(f, t, 1)
-    return {"n": n, "max_level": K, "hermite_step_ms": t_full, "points": pts, "fit_T_full_ms": float(slope),
-            "fit_F_us": float(icpt * 1e3)}
+    return {"n": n, "max_level": K, "dtype": str(dtype), "hermite_step_ms": t_full, "points": pts,
+            "fit_T_full_ms": float(slope), "fit_F_us": float(icpt * 1e3)}
 
 
 def _wall(fn):
@@ -138,6 +172,25 @@ def orbit(e=0.9):
         out["block"].append({"eta": eta, "block_steps": sim.block_steps, "pairs": sim.pair_interactions, "wall_s": s,
                              "err": ho.orbit_error(sim.positions.cpu().numpy(), x0.astype(np.float32))})
         print(json.dumps(out["block"][-1]), flush=True)
+    return out
+
+
+def orbit_f64(e=0.9, K=16):
+    """The eta sweep of the eccentric orbit in both precisions: the fp32 run stops gaining at its floor, fp64 does not."""
+    x0, v0, m, period = ho.two_body(e)
+    out = []
+    for eta in (0.01, 0.0025, 0.000625):
+        row = {"eta": eta, "max_level": K}
+        for name, dtype, ref in (("float64", torch.float64, x0), ("float32", torch.float32, x0.astype(np.float32))):
+            kw = dict(positions=x0, velocities=v0, masses=m, softening=0.0, dt=period / 4, calc_energy=False,
+                      device="cuda", eta=eta, max_level=K, dtype=dtype)
+            simulation.BlockHermiteSimulator(**kw).step()       # warm
+            sim = simulation.BlockHermiteSimulator(**kw)
+            s = _wall(lambda: [sim.step() for _ in range(4)])
+            row[name] = {"err": ho.orbit_error(sim.positions.cpu().numpy(), ref), "pairs": sim.pair_interactions,
+                         "block_steps": sim.block_steps, "clamped": sim.clamped, "wall_s": s}
+        out.append(row)
+        print(json.dumps(row), flush=True)
     return out
 
 
@@ -179,16 +232,26 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
     ap.add_argument("--only", default="force,cost,orbit,plummer")
+    ap.add_argument("--dtype", default="float32", choices=["float32", "float64"])
     args = ap.parse_args()
     parts = args.only.split(",")
     res = {"device": torch.cuda.get_device_name(0)}
-    if "force" in parts:
+    if args.dtype == "float64":
+        args.out = args.out or os.path.join(ROOT, "profiles", "r13_hermite_block_f64.json")
+        if "force" in parts:
+            res["active_force_f64"] = active_force_f64()
+        if "cost" in parts:
+            res["block_step_cost_f64"] = block_step_cost(dtype=torch.float64)
+            res["block_step_cost_f32"] = block_step_cost(dtype=torch.float32)
+        if "orbit" in parts:
+            res["orbit_e09"] = orbit_f64()
+    elif "force" in parts:
         res["active_force"] = active_force()
-    if "cost" in parts:
+    if args.dtype == "float32" and "cost" in parts:
         res["block_step_cost"] = block_step_cost()
-    if "orbit" in parts:
+    if args.dtype == "float32" and "orbit" in parts:
         res["orbit_e09"] = orbit()
-    if "plummer" in parts:
+    if args.dtype == "float32" and "plummer" in parts:
         res["plummer16k"] = plummer()
     txt = json.dumps(res, indent=1)
     if args.out:
