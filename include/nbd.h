@@ -470,6 +470,33 @@ int nbd_accel_jerk_active_f64(const double* posd, const double* veld, int n, con
                               double softening_sq, double g_const, double* acc_out, double* jerk_out, void* workspace,
                               size_t workspace_bytes, int slabs, nbd_stream_t stream);
 
+/* ---- backward of the all-pairs acceleration (csrc/direct_grad.hip): the vector-Jacobian product of
+ *   a_i = G sum_{j != i} m_j d s^3,  d = x_j - x_i,  s = (|d|^2 + softening_sq)^(-1/2)
+ * with a cotangent g = dL/da (n,3). With h_ij = m_i g_j - m_j g_i:
+ *   grad_pos[i]  =  G sum_{j != i} [ s^3 h_ij - 3 s^5 d (d . h_ij) ]      (n,3)
+ *   grad_mass[i] = -G sum_{j != i}   s^3 (d . g_j)                         (n)
+ * An extension (the reference gets these from torch's autograd). The sources are the packed rows of the force entries
+ * and, in the same layout, the cotangent rows {gx, gy, gz, 0} with zero rows behind n up to a multiple of 64:
+ * nbd_hermite_pack_f32 / nbd_hermite_f64_pack with the cotangent passed as the velocities write exactly this pair.
+ * i == j is dropped by index below softening_sq = 1e-24 (the result is the closed form over j != i; torch's autograd gives
+ * NaN there), otherwise it is dropped by index in the chunks that hold the targets' own rows and nowhere else (the term
+ * is not an exact zero of the arithmetic here). A massless body is a valid source and target. Either of grad_pos /
+ * grad_mass may be null (not both).
+ * Two launches (partial sums per slab, then the slabs in a fixed order and G applied once); no atomics, no memsets, no
+ * host syncs: deterministic with a workspace that may hold anything on entry, and capturable. Refused with
+ * NBD_E_BADARG before any launch: n < 0, a null or misaligned pointer (packed rows 16 bytes in fp32 and 32 in fp64; the
+ * workspace 16 resp. 8; the outputs their element size), a non-finite softening_sq or g_const. n = 0 succeeds and touches
+ * nothing. */
+/* Workspace of nbd_accel_vjp_f32: 4 floats per body and slab of the force plan (nbd_accel_plan at n sources, n targets). */
+size_t nbd_accel_vjp_workspace_bytes(int n);
+int nbd_accel_vjp_f32(const float* posm, const float* cot, int n, float softening_sq, float g_const, float* grad_pos,
+                      float* grad_mass, void* workspace, nbd_stream_t stream);
+/* float64: slabs = 0 for the split of nbd_hermite_f64_plan, or an explicit slab count in [1, 64] (tests: it sets how many
+ * chunks a wave walks). Workspace: 4 doubles per body and slab; 0 for a slab count outside [0, 64]. */
+size_t nbd_accel_vjp_f64_workspace_bytes(int n, int slabs);
+int nbd_accel_vjp_f64(const double* posd, const double* cotd, int n, double softening_sq, double g_const,
+                      double* grad_pos, double* grad_mass, void* workspace, int slabs, nbd_stream_t stream);
+
 /* ------------------------------------------------------------ surrogate models: graph build
  * Replace the torch_cluster kernels the reference reaches through PyG. Index-exact rule (the
  * reference delegates ties/truncation to torch_cluster; fixed here, see oracle/surrogate_oracle.py):

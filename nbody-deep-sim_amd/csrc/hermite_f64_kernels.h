@@ -39,7 +39,7 @@ __device__ __forceinline__ double rsqrt_f64(const double x) {
 // of posd, row q of veld where kVel) -- MASKED: exclusions by index, else by the arithmetic; out(k) is partial sum k of kOut.
 
 // a_i = sum_j m_j r_ij s^3, j_i = sum_j m_j (v_ij s^3 - 3 (r_ij.v_ij) s^5 r_ij), s = (|r_ij|^2 + eps^2)^(-1/2): the
-// operations of jerk_pair_masked / jerk_block (hermite_kernels.h) one for one. acc[3..5] accumulates w dv, acc[6..8]
+// operations of AccelJerkPolicy::masked / ::block (hermite_kernels.h) one for one. acc[3..5] accumulates w dv, acc[6..8]
 // (r.v s^2) w dr; j = acc[3..5] - 3 acc[6..8]. MASKED drops j == i and the padding behind n by a select on s (after the
 // refinement: whatever the dropped r^2 gave, NaN included, never reaches a sum). Un-masked, i == j and a padding row add
 // exact zeros: dr = dv = 0 resp. m = 0, with s finite because eps^2 >= kEps2MaskedF64.

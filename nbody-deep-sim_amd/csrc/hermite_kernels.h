@@ -19,91 +19,107 @@
 
 namespace {
 
-// One source against the lane's two targets, index-masked (softening^2 below kEps2Masked): accel_kernel's rule, only
-// j == i and the padding behind n are dropped. ja accumulates w dv, jb accumulates (r.v s^2) w dr; j = ja - 3 jb.
-// RANGE (an edge chunk of a range-sharded walk, direct_hermite_shard.hip): the sources [ex_lo, ex_hi) are dropped too,
-// by the same select on s, and their rows are replaced by zeros before any arithmetic (a select, not a product:
-// whatever such a row holds, NaN included, never reaches a sum).
-template <bool RANGE = false>
-__device__ __forceinline__ void jerk_pair_masked(f4 p, f4 q, const f2 xi, const f2 yi, const f2 zi,
-                                                 const f2 ui, const f2 vi, const f2 wi, const f2 e2, f2* acc, int j,
-                                                 int i0, int i1, int n, int ex_lo = 0, int ex_hi = 0) {
-  bool live = j < n;
-  if (RANGE) {
-    const bool ex = (unsigned)(j - ex_lo) < (unsigned)(ex_hi - ex_lo);
-    p = ex ? f4{0.f, 0.f, 0.f, 0.f} : p;
-    q = ex ? f4{0.f, 0.f, 0.f, 0.f} : q;
-    live = live && !ex;
-  }
-  const f2 dx = f2{p.x, p.x} - xi, dy = f2{p.y, p.y} - yi, dz = f2{p.z, p.z} - zi;
-  const f2 du = f2{q.x, q.x} - ui, dv = f2{q.y, q.y} - vi, dw = f2{q.z, q.z} - wi;
-  f2 r2 = __builtin_elementwise_fma(dx, dx, e2);
-  r2 = __builtin_elementwise_fma(dy, dy, r2);
-  r2 = __builtin_elementwise_fma(dz, dz, r2);
-  f2 rv = dx * du;
-  rv = __builtin_elementwise_fma(dy, dv, rv);
-  rv = __builtin_elementwise_fma(dz, dw, rv);
-  f2 s = {__builtin_amdgcn_rsqf(r2.x), __builtin_amdgcn_rsqf(r2.y)};
-  s.x = (live && j != i0) ? s.x : 0.0f;
-  s.y = (live && j != i1) ? s.y : 0.0f;
-  const f2 s2 = s * s;
-  const f2 w = (s2 * s) * f2{p.w, p.w};
-  const f2 c = (rv * s2) * w;
-  acc[0] = __builtin_elementwise_fma(w, dx, acc[0]);
-  acc[1] = __builtin_elementwise_fma(w, dy, acc[1]);
-  acc[2] = __builtin_elementwise_fma(w, dz, acc[2]);
-  acc[3] = __builtin_elementwise_fma(w, du, acc[3]);
-  acc[4] = __builtin_elementwise_fma(w, dv, acc[4]);
-  acc[5] = __builtin_elementwise_fma(w, dw, acc[5]);
-  acc[6] = __builtin_elementwise_fma(c, dx, acc[6]);
-  acc[7] = __builtin_elementwise_fma(c, dy, acc[7]);
-  acc[8] = __builtin_elementwise_fma(c, dz, acc[8]);
-}
+// The pair policy of accel_jerk_body: what a target loads from its two rows, the masked pair, the un-masked block of KU
+// sources, the number of per-lane accumulators and of outputs, and how an output is formed from the accumulators. This one
+// is acceleration plus jerk; direct_grad.hip states the vector-Jacobian product of the acceleration as a second one and
+// walks the chunks with the same body. own(pc, i0): the physical chunk pc holds indices of the workgroup's own targets
+// and takes the masked pair for that reason alone (never, here: i == j is an exact zero).
+struct AccelJerkPolicy {
+  static constexpr int kAcc = 9, kOut = 6;
+  f2 xi, yi, zi, ui, vi, wi;
 
-// KU sources at once, un-masked: interact_block's shape (the 2 KU v_rsq_f32 issued back to back, the mass splat folded
-// into op_sel by one asm multiply that consumes s^3, never the rsq result itself -- see interact()). Per source and pair
-// of targets: 6 v_pk_add (differences), 5 v_pk_fma + 1 v_pk_mul (r^2, r.v), 2 v_rsq_f32, 5 v_pk_mul (s^2, s^3, w, r.v s^2,
-// c = (r.v s^2) w), 9 v_pk_fma (a, w dv, c dr): 26 packed ops (the factor -3 of the jerk's second sum is applied once, to
-// the finished per-lane sum).
-template <int KU>
-__device__ __forceinline__ void jerk_block(const f4* __restrict__ bp, const f4* __restrict__ bv, const f2 xi,
-                                           const f2 yi, const f2 zi, const f2 ui, const f2 vi, const f2 wi,
-                                           const f2 e2, f2* acc) {
-  f2 zm[KU], dx[KU], dy[KU], dz[KU], du[KU], dv[KU], dw[KU], s[KU], rv[KU];
-#pragma unroll
-  for (int u = 0; u < KU; ++u) {
-    const f4 p = bp[u], q = bv[u];
-    zm[u] = f2{p.z, p.w};
-    dx[u] = f2{p.x, p.x} - xi; dy[u] = f2{p.y, p.y} - yi; dz[u] = f2{p.z, p.z} - zi;
-    du[u] = f2{q.x, q.x} - ui; dv[u] = f2{q.y, q.y} - vi; dw[u] = f2{q.z, q.z} - wi;
-    f2 r2 = __builtin_elementwise_fma(dx[u], dx[u], e2);
-    r2 = __builtin_elementwise_fma(dy[u], dy[u], r2);
-    s[u] = __builtin_elementwise_fma(dz[u], dz[u], r2);
-    f2 t = dx[u] * du[u];
-    t = __builtin_elementwise_fma(dy[u], dv[u], t);
-    rv[u] = __builtin_elementwise_fma(dz[u], dw[u], t);
+  // t0, t1: the position rows of the lane's two targets, u0, u1: their velocity rows
+  __device__ __forceinline__ AccelJerkPolicy(const f4 t0, const f4 t1, const f4 u0, const f4 u1)
+      : xi{t0.x, t1.x}, yi{t0.y, t1.y}, zi{t0.z, t1.z}, ui{u0.x, u1.x}, vi{u0.y, u1.y}, wi{u0.z, u1.z} {}
+
+  __device__ __forceinline__ bool own(int, int) const { return false; }
+
+  // One source against the lane's two targets, index-masked (softening^2 below kEps2Masked): accel_kernel's rule, only
+  // j == i and the padding behind n are dropped. ja accumulates w dv, jb accumulates (r.v s^2) w dr; j = ja - 3 jb.
+  // RANGE (an edge chunk of a range-sharded walk, direct_hermite_shard.hip): the sources [ex_lo, ex_hi) are dropped too,
+  // by the same select on s, and their rows are replaced by zeros before any arithmetic (a select, not a product:
+  // whatever such a row holds, NaN included, never reaches a sum).
+  template <bool RANGE>
+  __device__ __forceinline__ void masked(f4 p, f4 q, const f2 e2, f2* acc, int j, int i0, int i1, int n, int ex_lo = 0,
+                                         int ex_hi = 0) const {
+    bool live = j < n;
+    if (RANGE) {
+      const bool ex = (unsigned)(j - ex_lo) < (unsigned)(ex_hi - ex_lo);
+      p = ex ? f4{0.f, 0.f, 0.f, 0.f} : p;
+      q = ex ? f4{0.f, 0.f, 0.f, 0.f} : q;
+      live = live && !ex;
+    }
+    const f2 dx = f2{p.x, p.x} - xi, dy = f2{p.y, p.y} - yi, dz = f2{p.z, p.z} - zi;
+    const f2 du = f2{q.x, q.x} - ui, dv = f2{q.y, q.y} - vi, dw = f2{q.z, q.z} - wi;
+    f2 r2 = __builtin_elementwise_fma(dx, dx, e2);
+    r2 = __builtin_elementwise_fma(dy, dy, r2);
+    r2 = __builtin_elementwise_fma(dz, dz, r2);
+    f2 rv = dx * du;
+    rv = __builtin_elementwise_fma(dy, dv, rv);
+    rv = __builtin_elementwise_fma(dz, dw, rv);
+    f2 s = {__builtin_amdgcn_rsqf(r2.x), __builtin_amdgcn_rsqf(r2.y)};
+    s.x = (live && j != i0) ? s.x : 0.0f;
+    s.y = (live && j != i1) ? s.y : 0.0f;
+    const f2 s2 = s * s;
+    const f2 w = (s2 * s) * f2{p.w, p.w};
+    const f2 c = (rv * s2) * w;
+    acc[0] = __builtin_elementwise_fma(w, dx, acc[0]);
+    acc[1] = __builtin_elementwise_fma(w, dy, acc[1]);
+    acc[2] = __builtin_elementwise_fma(w, dz, acc[2]);
+    acc[3] = __builtin_elementwise_fma(w, du, acc[3]);
+    acc[4] = __builtin_elementwise_fma(w, dv, acc[4]);
+    acc[5] = __builtin_elementwise_fma(w, dw, acc[5]);
+    acc[6] = __builtin_elementwise_fma(c, dx, acc[6]);
+    acc[7] = __builtin_elementwise_fma(c, dy, acc[7]);
+    acc[8] = __builtin_elementwise_fma(c, dz, acc[8]);
   }
+
+  // KU sources at once, un-masked: interact_block's shape (the 2 KU v_rsq_f32 issued back to back, the mass splat folded
+  // into op_sel by one asm multiply that consumes s^3, never the rsq result itself -- see interact()). Per source and pair
+  // of targets: 6 v_pk_add (differences), 5 v_pk_fma + 1 v_pk_mul (r^2, r.v), 2 v_rsq_f32, 5 v_pk_mul (s^2, s^3, w, r.v s^2,
+  // c = (r.v s^2) w), 9 v_pk_fma (a, w dv, c dr): 26 packed ops (the factor -3 of the jerk's second sum is applied once, to
+  // the finished per-lane sum).
+  template <int KU>
+  __device__ __forceinline__ void block(const f4* __restrict__ bp, const f4* __restrict__ bv, const f2 e2, f2* acc) const {
+    f2 zm[KU], dx[KU], dy[KU], dz[KU], du[KU], dv[KU], dw[KU], s[KU], rv[KU];
 #pragma unroll
-  for (int u = 0; u < KU; ++u) s[u] = f2{__builtin_amdgcn_rsqf(s[u].x), __builtin_amdgcn_rsqf(s[u].y)};
-  __builtin_amdgcn_sched_group_barrier(0x400, 2 * KU, 0);      // 0x400 = TRANS: keep the rsq's together
+    for (int u = 0; u < KU; ++u) {
+      const f4 p = bp[u], q = bv[u];
+      zm[u] = f2{p.z, p.w};
+      dx[u] = f2{p.x, p.x} - xi; dy[u] = f2{p.y, p.y} - yi; dz[u] = f2{p.z, p.z} - zi;
+      du[u] = f2{q.x, q.x} - ui; dv[u] = f2{q.y, q.y} - vi; dw[u] = f2{q.z, q.z} - wi;
+      f2 r2 = __builtin_elementwise_fma(dx[u], dx[u], e2);
+      r2 = __builtin_elementwise_fma(dy[u], dy[u], r2);
+      s[u] = __builtin_elementwise_fma(dz[u], dz[u], r2);
+      f2 t = dx[u] * du[u];
+      t = __builtin_elementwise_fma(dy[u], dv[u], t);
+      rv[u] = __builtin_elementwise_fma(dz[u], dw[u], t);
+    }
 #pragma unroll
-  for (int u = 0; u < KU; ++u) {
-    const f2 s2 = s[u] * s[u];
-    const f2 s3 = s2 * s[u];
-    f2 w;
-    asm("v_pk_mul_f32 %0, %1, %2 op_sel:[1,0] op_sel_hi:[1,1]" : "=v"(w) : "v"(zm[u]), "v"(s3));
-    const f2 c = (rv[u] * s2) * w;
-    acc[0] = __builtin_elementwise_fma(w, dx[u], acc[0]);
-    acc[1] = __builtin_elementwise_fma(w, dy[u], acc[1]);
-    acc[2] = __builtin_elementwise_fma(w, dz[u], acc[2]);
-    acc[3] = __builtin_elementwise_fma(w, du[u], acc[3]);
-    acc[4] = __builtin_elementwise_fma(w, dv[u], acc[4]);
-    acc[5] = __builtin_elementwise_fma(w, dw[u], acc[5]);
-    acc[6] = __builtin_elementwise_fma(c, dx[u], acc[6]);
-    acc[7] = __builtin_elementwise_fma(c, dy[u], acc[7]);
-    acc[8] = __builtin_elementwise_fma(c, dz[u], acc[8]);
+    for (int u = 0; u < KU; ++u) s[u] = f2{__builtin_amdgcn_rsqf(s[u].x), __builtin_amdgcn_rsqf(s[u].y)};
+    __builtin_amdgcn_sched_group_barrier(0x400, 2 * KU, 0);      // 0x400 = TRANS: keep the rsq's together
+#pragma unroll
+    for (int u = 0; u < KU; ++u) {
+      const f2 s2 = s[u] * s[u];
+      const f2 s3 = s2 * s[u];
+      f2 w;
+      asm("v_pk_mul_f32 %0, %1, %2 op_sel:[1,0] op_sel_hi:[1,1]" : "=v"(w) : "v"(zm[u]), "v"(s3));
+      const f2 c = (rv[u] * s2) * w;
+      acc[0] = __builtin_elementwise_fma(w, dx[u], acc[0]);
+      acc[1] = __builtin_elementwise_fma(w, dy[u], acc[1]);
+      acc[2] = __builtin_elementwise_fma(w, dz[u], acc[2]);
+      acc[3] = __builtin_elementwise_fma(w, du[u], acc[3]);
+      acc[4] = __builtin_elementwise_fma(w, dv[u], acc[4]);
+      acc[5] = __builtin_elementwise_fma(w, dw[u], acc[5]);
+      acc[6] = __builtin_elementwise_fma(c, dx[u], acc[6]);
+      acc[7] = __builtin_elementwise_fma(c, dy[u], acc[7]);
+      acc[8] = __builtin_elementwise_fma(c, dz[u], acc[8]);
+    }
   }
-}
+
+  // j = (w dv) - 3 (r.v s^2 w dr)
+  __device__ __forceinline__ f2 out(const f2* acc, int k) const { return k < 3 ? acc[k] : acc[k] - 3.0f * acc[k + 3]; }
+};
 
 // The wave body of every acceleration-plus-jerk kernel. accel_kernel's structure: a workgroup is 4 waves on 128 targets,
 // two per lane in packed fp32 (rows r0, r1 of tpos / tvel; i0, i1 are the source indices the masked loop takes for the
@@ -111,7 +127,7 @@ __device__ __forceinline__ void jerk_block(const f4* __restrict__ bp, const f4* 
 // (2 KiB) by LDS-DMA, double-buffered behind a counted vmcnt; the 4 waves' partials are reduced through LDS in wave order
 // into one coalesced store of 6 x n_valid floats: dst[comp * stride + t], t < n_valid. lds: the workgroup's
 // f4[kWaves * 4 * kChunk] (16 KiB), [wave][buffer][pos | vel][64] staging; after its last chunk a wave puts its [12][64]
-// partials into its own part.
+// partials into its own part. (6 and 12: P::kOut and twice that, for the policy P.)
 // Compile-time shape, all defaults = the un-sharded kernels (targets and sources in the same two arrays):
 //   SS    : quads between consecutive rows of spos / svel and of tpos / tvel. 1: two arrays of float4 (posm, velp);
 //           2: one array of 8-float rows {x, y, z, m, vx, vy, vz, 0} (svel = spos + 1), the layout a range-sharded rank
@@ -120,7 +136,8 @@ __device__ __forceinline__ void jerk_block(const f4* __restrict__ bp, const f4* 
 //   RANGE : the walk is over the view *sv (direct_kernels.h): [c_begin, c_end) are LOGICAL chunks that hop over the run of
 //           physical chunks lying wholly inside [ex_lo, ex_hi), and the (at most two) chunks that straddle an end of that
 //           range take the masked loop with the range mask; every other chunk takes the loop MASKED says.
-template <bool MASKED, int KU, int SS = 1, bool RANGE = false>
+//   P     : the pair policy (above).
+template <bool MASKED, int KU, int SS = 1, bool RANGE = false, class P = AccelJerkPolicy>
 __device__ __forceinline__ void accel_jerk_body(const f4* __restrict__ spos, const f4* __restrict__ svel, int n,
                                                 const f4* __restrict__ tpos, const f4* __restrict__ tvel, int r0,
                                                 int r1, int i0, int i1, int c_begin, int c_end, float eps2, f4* lds,
@@ -130,11 +147,10 @@ __device__ __forceinline__ void accel_jerk_body(const f4* __restrict__ spos, con
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const f4 t0 = tpos[r0 * SS], t1 = tpos[r1 * SS];
   const f4 u0 = tvel[r0 * SS], u1 = tvel[r1 * SS];
-  const f2 xi = {t0.x, t1.x}, yi = {t0.y, t1.y}, zi = {t0.z, t1.z};
-  const f2 ui = {u0.x, u1.x}, vi = {u0.y, u1.y}, wi = {u0.z, u1.z};
-  f2 acc[9];
+  const P pol(t0, t1, u0, u1);
+  f2 acc[P::kAcc];
 #pragma unroll
-  for (int k = 0; k < 9; ++k) acc[k] = f2{0.f, 0.f};
+  for (int k = 0; k < P::kAcc; ++k) acc[k] = f2{0.f, 0.f};
   f2 e2 = {eps2, eps2};
   asm volatile("" : "+v"(e2));  // keep eps^2 in VGPRs: an SGPR operand halves v_pk_fma issue
 
@@ -164,31 +180,32 @@ __device__ __forceinline__ void accel_jerk_body(const f4* __restrict__ spos, con
       const int j0 = pc * kChunk;
 #pragma unroll 2
       for (int j = 0; j < kChunk; ++j)
-        jerk_pair_masked<true>(bp[j], bv[j], xi, yi, zi, ui, vi, wi, e2, acc, j0 + j, i0, i1, n, sv->ex_lo, sv->ex_hi);
-    } else if (MASKED) {
+        pol.template masked<true>(bp[j], bv[j], e2, acc, j0 + j, i0, i1, n, sv->ex_lo, sv->ex_hi);
+    } else if (MASKED || pol.own(pc, i0)) {
       const int j0 = pc * kChunk;
 #pragma unroll 2
       for (int j = 0; j < kChunk; ++j)
-        jerk_pair_masked(bp[j], bv[j], xi, yi, zi, ui, vi, wi, e2, acc, j0 + j, i0, i1, n);
+        pol.template masked<false>(bp[j], bv[j], e2, acc, j0 + j, i0, i1, n);
     } else {
 #pragma unroll 1
-      for (int j = 0; j < kChunk; j += KU) jerk_block<KU>(bp + j, bv + j, xi, yi, zi, ui, vi, wi, e2, acc);
+      for (int j = 0; j < kChunk; j += KU) pol.template block<KU>(bp + j, bv + j, e2, acc);
     }
   }
 
-  // j = (w dv) - 3 (r.v s^2 w dr); wavefront partials -> LDS -> one coalesced (6 x 128) store per workgroup. A wave's
-  // staging is free here: its loads have landed (vmcnt(0) on the last chunk) and its reads precede these writes.
-  constexpr int kPart = 4 * kChunk * 4;                              // floats per wave: [comp*2+half][64] in the first 768
+  // wavefront partials (P::out) -> LDS -> one coalesced (kOut x 128) store per workgroup. A wave's staging is free
+  // here: its loads have landed (vmcnt(0) on the last chunk) and its reads precede these writes.
+  constexpr int kPart = 4 * kChunk * 4;                   // floats per wave: [comp*2+half][64] in the first kOut * 128
+  static_assert(P::kOut * 128 <= kPart, "the partials must fit a wave's staging");
   float* red = reinterpret_cast<float*>(lds);
   float* mine = red + wave * kPart;
 #pragma unroll
-  for (int k = 0; k < 6; ++k) {
-    const f2 v = k < 3 ? acc[k] : acc[k] - 3.0f * acc[k + 3];
+  for (int k = 0; k < P::kOut; ++k) {
+    const f2 v = pol.out(acc, k);
     mine[(2 * k) * 64 + lane] = v.x;
     mine[(2 * k + 1) * 64 + lane] = v.y;
   }
   __syncthreads();
-  for (int o = threadIdx.x; o < 6 * kTgtPerWG; o += 64 * kWaves) {
+  for (int o = threadIdx.x; o < P::kOut * kTgtPerWG; o += 64 * kWaves) {
     const int comp = o >> 7, lt = o & 127;
     if (lt >= n_valid) continue;
     const int idx = (comp * 2 + (lt >> 6)) * 64 + (lt & 63);

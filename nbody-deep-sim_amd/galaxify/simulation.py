@@ -30,6 +30,10 @@ Seventh addition: `BlockHermiteSimulator(dtype=torch.float64)`, block timesteps 
 Fifth addition: `compute_potentials()` / `compute_invariants()` and `calc_invariants=`: the per-body potential of the
 softening the force uses and the conserved quantities formed from it (`Invariants`; csrc/direct_diag.hip).
 `compute_energies()`, `u_energy` and `k_energy` keep the reference's convention.
+
+Eighth addition: `compute_accelerations()` is differentiable. When torch records a graph and `positions` or `masses`
+requires grad, its result carries a grad_fn whose backward is a HIP kernel (csrc/direct_grad.hip; `nbd.autograd.direct_accel`
+is the function form; DESIGN.md K-VJP), as the reference's nine lines of torch do by themselves. Otherwise nothing changes.
 """
 from __future__ import annotations
 
@@ -309,12 +313,25 @@ class BaseSimulator(_ChunkedRun):
         (simulation.py:71-89)."""
         if self.n == 0:
             return torch.zeros((0, 3), dtype=torch.float32, device=self.device)
+        if self._wants_grad():
+            return self._accelerations_with_grad()
         if not self._sharded:
             direct.pack_posm(self.positions, self.masses, out=self._posm)
             return direct.accel(self._posm, self.n, self._posm, self.n, 0, self._eps2, self._g,
                                 workspace=self._ws)
         self._pack_local()
         return self._force_sharded()
+
+    def _wants_grad(self) -> bool:
+        return torch.is_grad_enabled() and (self.positions.requires_grad or self.masses.requires_grad)
+
+    def _accelerations_with_grad(self) -> torch.Tensor:
+        """compute_accelerations() as a node of torch's graph (nbd.autograd.direct_accel: the same forward bits, and a
+        HIP backward with respect to positions and masses). The node packs its own copy of the state, so a later step()
+        does not change what backward() differentiates."""
+        self._refuse_sharded("compute_accelerations() with requires_grad")
+        from nbd.autograd import direct_accel
+        return direct_accel(self.positions, self.masses, self.g_const, self.softening)
 
     def compute_energies(self):
         """(U, K) as Python floats (simulation.py:91-115). Sharded: every rank evaluates the
@@ -713,6 +730,8 @@ class HermiteSimulator(BaseSimulator):
 
     def compute_accelerations(self) -> torch.Tensor:
         if self._f64:
+            if self.n and self._wants_grad():
+                return self._accelerations_with_grad()
             return self.compute_accelerations_and_jerks()[0]
         return super().compute_accelerations()
 

@@ -12,7 +12,7 @@ import torch
 from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
-from . import graphops, nnops
+from . import _lib, direct, graphops, nnops
 
 
 class EdgeLists:
@@ -582,3 +582,56 @@ class ContConvModelFn(Function):
             _lib.check(_lib.lib().nbd_cc_train_backward_f32(ctypes.byref(a), dout.data_ptr(), dout.stride(0), ctypes.byref(g),
                                                             _lib.current_stream(dev)), "nbd_cc_train_backward_f32")
         return (None, None, None, *grads)
+
+
+class DirectAccelFn(Function):
+    """a = the all-pairs acceleration of `positions` (n,3) and `masses` (n,), float32 or float64, differentiable with
+    respect to both (csrc/direct_grad.hip; not to g_const or softening, and once). Forward: the force kernel of that
+    dtype, so the bits of compute_accelerations() -- nbd_accel_f32 with the scalars rounded as BaseSimulator rounds them,
+    nbd_accel_jerk_f64 with zero velocity rows (the jerk is dropped). The node saves its own packed copy of the inputs
+    (16 or 32 bytes per body), never a view of the caller's tensors: the simulators' kernels write state through raw
+    pointers, which torch's version counters do not see. Backward: one nbd_accel_vjp_* launch pair for both gradients."""
+
+    @staticmethod
+    def forward(ctx, positions, masses, g_const, softening):
+        dtype = positions.dtype if isinstance(positions, torch.Tensor) else None
+        if dtype not in (torch.float32, torch.float64):
+            raise _lib.NbdError(f"direct_accel: positions must be float32 or float64, got {dtype}")
+        n = positions.shape[0] if positions.dim() == 2 else -1
+        pos, mass = positions.detach().contiguous(), masses.detach().contiguous()
+        direct._chk(pos, (n, 3), "positions", dtype); direct._chk(mass, (n,), "masses", dtype)
+        ctx.n, ctx.f64 = n, dtype == torch.float64
+        if n == 0:
+            return torch.zeros((0, 3), dtype=dtype, device=pos.device)
+        if ctx.f64:
+            ctx.eps2, ctx.g = float(softening) ** 2, float(g_const)
+            rows, zero_rows = direct.alloc_rows_f64(n, pos.device), direct.alloc_rows_f64(n, pos.device)
+            direct.hermite_f64_pack(pos, torch.zeros_like(pos), mass, rows, zero_rows)
+            acc = direct.accel_jerk_f64(rows, zero_rows, n, ctx.eps2, ctx.g)[0]
+        else:
+            ctx.eps2, ctx.g = direct.f32(float(softening) ** 2), direct.f32(g_const)
+            rows = direct.pack_posm(pos, mass)
+            acc = direct.accel(rows, n, rows, n, 0, ctx.eps2, ctx.g)
+        ctx.save_for_backward(rows)
+        return acc
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dacc):
+        want_pos, want_mass = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        n = ctx.n
+        if n == 0 or not (want_pos or want_mass):
+            z = dacc.new_zeros
+            return (z((n, 3)) if want_pos else None), (z((n,)) if want_mass else None), None, None
+        (rows,) = ctx.saved_tensors
+        cot = torch.zeros_like(rows)                      # {gx, gy, gz, 0}, zero rows behind n
+        cot[:n, :3] = dacc
+        vjp = direct.accel_vjp_f64 if ctx.f64 else direct.accel_vjp
+        gp, gm = vjp(rows, cot, n, ctx.eps2, ctx.g, want_pos=want_pos, want_mass=want_mass)
+        return gp, gm, None, None
+
+
+def direct_accel(positions, masses, g_const: float = 1.0, softening: float = 0.1):
+    """The reference's compute_accelerations() as a differentiable function of CUDA tensors `positions` (n,3) and `masses`
+    (n,) of one dtype, float32 or float64: a_i = G sum_{j != i} m_j (x_j - x_i) (|x_j - x_i|^2 + softening^2)^(-3/2)."""
+    return DirectAccelFn.apply(positions, masses, g_const, softening)

@@ -568,6 +568,71 @@ def invariants_state_f64(pos, vel, mass, phi, out=None) -> torch.Tensor:
     return out
 
 
+
+# ------------------------------------------------ backward of the all-pairs acceleration (csrc/direct_grad.hip)
+def accel_vjp_workspace(n: int, device) -> torch.Tensor:
+    return alloc_bytes(_lib.lib().nbd_accel_vjp_workspace_bytes(int(n)), device)
+
+
+def _chk_grads(n: int, dtype, dev, grad_pos, grad_mass, want_pos: bool, want_mass: bool):
+    if not (want_pos or want_mass):
+        raise _lib.NbdError("accel_vjp: neither gradient is asked for")
+    if want_pos and grad_pos is None:
+        grad_pos = torch.empty((n, 3), dtype=dtype, device=dev)
+    if want_mass and grad_mass is None:
+        grad_mass = torch.empty((n,), dtype=dtype, device=dev)
+    if want_pos:
+        _chk(grad_pos, (n, 3), "grad_pos", dtype)
+    if want_mass:
+        _chk(grad_mass, (n,), "grad_mass", dtype)
+    return (grad_pos if want_pos else None), (grad_mass if want_mass else None)
+
+
+def accel_vjp(posm, cot, n: int, softening_sq: float, g_const: float, grad_pos=None, grad_mass=None, workspace=None,
+              want_pos: bool = True, want_mass: bool = True):
+    """(grad_pos (n,3), grad_mass (n,)) of L with respect to the positions and masses packed in posm, for the cotangent
+    dL/da packed in cot = {gx, gy, gz, 0} (hermite_pack with the cotangent as the velocities), a the acceleration of
+    `accel`: dL/dx_i = G sum_j [s^3 h - 3 s^5 d (d.h)], h = m_i g_j - m_j g_i; dL/dm_i = -G sum_j s^3 (d.g_j).
+    A gradient that is not wanted is None and is not written."""
+    _chk(posm, (padded_len(n), 4), "posm"); _chk(cot, (padded_len(n), 4), "cot")
+    dev = posm.device
+    grad_pos, grad_mass = _chk_grads(n, torch.float32, dev, grad_pos, grad_mass, want_pos, want_mass)
+    need = _lib.lib().nbd_accel_vjp_workspace_bytes(n)
+    if workspace is None:
+        workspace = alloc_bytes(need, dev)
+    if _nbytes(workspace) < need:
+        raise _lib.NbdError(f"accel_vjp: workspace of {_nbytes(workspace)} bytes, {need} needed")
+    with _lib.on_device(dev):
+        _lib.check(_lib.lib().nbd_accel_vjp_f32(
+            posm.data_ptr(), cot.data_ptr(), n, float(softening_sq), float(g_const), _lib.ptr(grad_pos),
+            _lib.ptr(grad_mass), workspace.data_ptr(), _lib.current_stream(dev)), "nbd_accel_vjp_f32")
+    return grad_pos, grad_mass
+
+
+def accel_vjp_f64_workspace(n: int, device, slabs: int = 0) -> torch.Tensor:
+    return alloc_bytes(_lib.lib().nbd_accel_vjp_f64_workspace_bytes(int(n), int(slabs)), device)
+
+
+def accel_vjp_f64(posd, cotd, n: int, softening_sq: float, g_const: float, grad_pos=None, grad_mass=None,
+                  workspace=None, slabs: int = 0, want_pos: bool = True, want_mass: bool = True):
+    """accel_vjp in float64 (posd, cotd as hermite_f64_pack leaves them). slabs: 0 = the plan's source split."""
+    _chk_rows_f64(posd, cotd, n)
+    if not 0 <= int(slabs) <= 64:
+        raise _lib.NbdError(f"accel_vjp_f64: slabs must be in [0, 64], got {slabs}")
+    dev = posd.device
+    grad_pos, grad_mass = _chk_grads(n, F64, dev, grad_pos, grad_mass, want_pos, want_mass)
+    need = _lib.lib().nbd_accel_vjp_f64_workspace_bytes(n, int(slabs))
+    if workspace is None:
+        workspace = alloc_bytes(need, dev)
+    if _nbytes(workspace) < need:
+        raise _lib.NbdError(f"accel_vjp_f64: workspace of {_nbytes(workspace)} bytes, {need} needed")
+    with _lib.on_device(dev):
+        _lib.check(_lib.lib().nbd_accel_vjp_f64(
+            posd.data_ptr(), cotd.data_ptr(), n, float(softening_sq), float(g_const), _lib.ptr(grad_pos),
+            _lib.ptr(grad_mass), workspace.data_ptr(), int(slabs), _lib.current_stream(dev)), "nbd_accel_vjp_f64")
+    return grad_pos, grad_mass
+
+
 # ---------------------------------------------------- block-timestep Hermite integrator (csrc/direct_hermite_block.hip)
 HBLOCK_SCHED_INTS = 32          # NBD_HBLOCK_SCHED_INTS: {t_next, n_act, clamped, ...} of the block schedule
 
