@@ -137,6 +137,15 @@ int nbd_snapshot_f32(const float* pos, const float* vel, const float* acc, int n
 /* Bytes of scratch the fused step entry points need (always >= one slab). */
 size_t nbd_step_workspace_bytes(int n);
 
+/* Bytes of scratch at which the fused step runs its preferred plan; >= nbd_step_workspace_bytes(n), and equal to it
+ * wherever the step does not take the symmetric force. The symmetric force keeps one partial-sum slot of n rows per
+ * round of its tile tournament when the workspace holds them (K = min(M, 64) slots for M = 2 floor(n / 2048) tiles, one
+ * more for the rows behind the last whole tile): every round then stores and all M (M - 1) / 2 tile pairs go in ONE
+ * launch. A step entry reads the plan off workspace_bytes: the widest K that fits, never fewer than the min(M, 16) slots
+ * of nbd_step_workspace_bytes(n), below which it returns NBD_E_WORKSPACE. Every K gives the same terms in a fixed
+ * order of its own: deterministic, equal to any other K to summation-order rounding. */
+size_t nbd_step_workspace_pref_bytes(int n);
+
 /* One whole LeapFrogSimulator.step (simulation.py:153-170) on one GPU:
  *   kick-drift-pack -> all-pairs force -> kick, three launches on `stream`.
  * acc_in is a(t) (read), acc_out receives a(t+dt) (may alias acc_in).
@@ -160,7 +169,7 @@ int nbd_leapfrog_step_ev_f32(float* pos, float* vel, const float* acc_in, float*
  * simulation.py:80; one multiplication per sum rounds differently from one per term. The caller vouches that every
  * entry of `mass` equals mass_value. From n = 65 536 on (softening_sq >= 1e-24) the force evaluates each off-diagonal pair
  * once and feeds both rows (Newton's third law; nbd_accel_sym_uniform_f32), same terms summed in another fixed order.
- * Workspace: nbd_step_workspace_bytes(n). */
+ * Workspace: nbd_step_workspace_bytes(n) at least, nbd_step_workspace_pref_bytes(n) for the one-launch plan. */
 int nbd_leapfrog_step_uniform_f32(float* pos, float* vel, const float* acc_in, float* acc_out, const float* mass,
                                   float mass_value, int n, float dt_half, float dt, float softening_sq, float g_const,
                                   float* posm, void* workspace, size_t workspace_bytes, nbd_stream_t stream,
@@ -170,8 +179,8 @@ int nbd_leapfrog_step_uniform_f32(float* pos, float* vel, const float* acc_in, f
  * sum_j d_ij s_ij^3 over all n bodies of posm, each off-diagonal pair evaluated once (Newton's third law). Needs
  * n >= 2048 and softening_sq >= 1e-24 (else NBD_E_UNSUPPORTED). Deterministic. variant: the register shape (0: 4 source
  * groups per tile pair; 1: 2 source groups; 2: the step's, two sources per step packed by source), same sums in another
- * order. Workspace:
- * nbd_accel_sym_workspace_bytes(n). */
+ * order. Workspace: nbd_accel_sym_workspace_bytes(n) at least (min(M, 16) slots of n rows, one more when n is no multiple
+ * of 2048); a larger one widens the plan slot by slot as nbd_step_workspace_pref_bytes describes. */
 size_t nbd_accel_sym_workspace_bytes(int n);
 int nbd_accel_sym_uniform_f32(const float* posm, int n, float softening_sq, float g_const, float mass_value,
                               float* acc_out, void* workspace, size_t workspace_bytes, int variant, nbd_stream_t stream);

@@ -63,10 +63,13 @@ __global__ __launch_bounds__(64 * kWaves, KU == 4 ? 8 : 5) void accel_kernel(
 // The first core = M * S bodies (M even) are cut into M super-tiles of S = 1024. The M (M - 1) / 2 off-diagonal tile
 // pairs are the M - 1 rounds of a round-robin tournament (circle method): round r pairs every tile with exactly one
 // other, so one round writes each core row exactly once. Round r writes slot (r + 1) % K of the float[K][n][3] partial
-// array (K = min(M, 16)); the diagonal blocks (accel_kernel, one launch) write slot 0. The rounds go in launches of at
-// most K: the first launch (rounds 0 .. K-2) stores, every later one adds to what an earlier launch stored, so no two
-// workgroups of one launch touch the same (slot, row) and the per-row sums have a fixed order: deterministic, no atomics,
-// every slot written every step (no zero fill: capturable), and the workspace is the 16 slots the all-pairs step needs.
+// array; the diagonal blocks (accel_kernel, one launch) write slot 0. The rounds go in launches of at most K: the first
+// launch (rounds 0 .. K-2) stores, every later one adds to what an earlier launch stored, so no two workgroups of one
+// launch touch the same (slot, row) and the per-row sums have a fixed order: deterministic, no atomics, every slot written
+// every step (no zero fill: capturable). K is read off the workspace (plan_sym): min(M, 16) in the 16 slots the all-pairs
+// step needs at N = 65 536, up to min(M, 64) in a larger one. With K = M no round shares a slot: every round stores, the
+// fetch of an adding launch never runs and all M (M - 1) / 2 tile pairs go in ONE launch (N = 65 536: 2016 workgroups,
+// 3.94 residency rounds instead of four launches of one; 627.7 against 648.8 us, profiles/r15_sym_wide.txt).
 //
 // One workgroup = one tile pair (a, b): 4 target groups x SG source groups of waves. Wave (tg, sg) holds targets
 // a*S + tg*256 + 64 t + lane (t = 0..3, as the packed pairs {t0, t1}, {t2, t3}) and walks the 16 / SG 64-body chunks
@@ -79,7 +82,9 @@ __global__ __launch_bounds__(64 * kWaves, KU == 4 ? 8 : 5) void accel_kernel(
 // 6 DPP moves for 4 targets.
 constexpr int kSymTile = 1024;                   // S
 constexpr int kSymChunks = kSymTile / kChunk;    // 16
-constexpr int kSymSlots = 16;                    // K at most: the workspace of the all-pairs step at N = 65 536
+constexpr int kSymSlots = 16;                    // K of the narrow plan: the workspace of the all-pairs step at N = 65 536
+constexpr int kSymSlotsCap = 64;                 // K at most, whatever the workspace holds (memory at K = M grows as N^2)
+constexpr int kSymSlotsPref = 64;                // K of the preferred workspace (nbd_step_workspace_pref_bytes)
 
 __device__ __forceinline__ float rol1(float x) {  // lane l <- lane (l + 1) & 63
   return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(x), 0x134 /* wave_rol:1 */, 0xf, 0xf, false));
@@ -616,20 +621,41 @@ int launch_accel(const float* posm_src, SrcView sv, const float* posm_tgt, int n
 // [core, n) in one more slot
 struct SymPlan { int m, core, rem, slots, total_slots; };
 
-SymPlan plan_sym(int n) {
+// K = the widest plan that slots_avail slots of n rows hold: min(M, kSymSlotsCap, slots_avail less the remainder's slot),
+// and never below the narrow plan's min(M, kSymSlots), which is what the callers check the workspace against. With
+// K = M every round has a slot of its own: all rounds store, in ONE launch; with K < M the first K - 1 rounds store and
+// launches of K rounds add.
+SymPlan plan_sym(int n, int slots_avail = 0) {
   SymPlan p;
   p.m = n / kSymTile;
   p.m &= ~1;                                  // the circle method pairs an even number of tiles
   p.core = p.m * kSymTile;
   p.rem = n - p.core;
-  p.slots = p.m < kSymSlots ? p.m : kSymSlots;
+  const int narrow = p.m < kSymSlots ? p.m : kSymSlots, wide = p.m < kSymSlotsCap ? p.m : kSymSlotsCap;
+  const int avail = slots_avail - (p.rem > 0 ? 1 : 0);
+  p.slots = avail < narrow ? narrow : (avail < wide ? avail : wide);
   p.total_slots = p.slots + (p.rem > 0 ? 1 : 0);
   return p;
 }
 
+// the narrow plan's workspace: the least a symmetric call takes
 size_t sym_workspace_bytes(int n) {
   const SymPlan p = plan_sym(n);
   return p.m < 2 ? 0 : (size_t)p.total_slots * n * 3 * sizeof(float);
+}
+
+// how many slots of n rows a workspace holds (capped: the plan never uses more than kSymSlotsCap + 1)
+int sym_slots_avail(int n, size_t workspace_bytes) {
+  const size_t s = workspace_bytes / ((size_t)n * 3 * sizeof(float));
+  return s > (size_t)kSymSlotsCap + 1 ? kSymSlotsCap + 1 : (int)s;
+}
+
+// the workspace of the preferred plan: K = min(M, kSymSlotsPref)
+size_t sym_workspace_pref_bytes(int n) {
+  const SymPlan p = plan_sym(n);
+  if (p.m < 2) return 0;
+  const int k = p.m < kSymSlotsPref ? p.m : kSymSlotsPref;
+  return (size_t)(k + (p.rem > 0 ? 1 : 0)) * n * 3 * sizeof(float);
 }
 
 // the uniform-mass leapfrog step takes the symmetric force from this size on
@@ -640,8 +666,7 @@ bool sym_step(int n, float eps2) { return n >= kSymStepMinN && eps2 >= kEps2Mask
 // eps2 >= kEps2Masked (the i == j term of a diagonal block is then an exact zero)
 // variant 0: 4 source groups (16-wave workgroups, 64 VGPRs, 2 per CU: 8 waves per SIMD); 1: 2 source groups (8 waves,
 // 86 VGPRs: 4 waves per SIMD); 2: accel_sym2_kernel (two sources per step, 8 waves, <= 128 VGPRs: 4 waves per SIMD)
-int launch_sym(const float* posm, int n, float eps2, float* slots, hipStream_t st, int variant = 0) {
-  const SymPlan sp = plan_sym(n);
+int launch_sym(const float* posm, int n, float eps2, float* slots, const SymPlan& sp, hipStream_t st, int variant = 0) {
   const f4* pm = reinterpret_cast<const f4*>(posm);
   // the diagonal blocks (a, a): the all-pairs kernel on each tile, slot 0
   const AccelPlan dp = make_plan(kSymTile / kTgtPerWG, 1, kSymChunks);
@@ -728,6 +753,13 @@ size_t nbd_step_workspace_bytes(int n) {
   return sym > all_pairs ? sym : all_pairs;
 }
 
+size_t nbd_step_workspace_pref_bytes(int n) {
+  if (n <= 0) return 0;
+  const size_t least = nbd_step_workspace_bytes(n);
+  const size_t pref = sym_step(n, kEps2Masked) ? sym_workspace_pref_bytes(n) : 0;
+  return pref > least ? pref : least;
+}
+
 size_t nbd_accel_sym_workspace_bytes(int n) { return n <= 0 ? 0 : sym_workspace_bytes(n); }
 
 int nbd_accel_sym_uniform_f32(const float* posm, int n, float softening_sq, float g_const, float mass_value,
@@ -738,10 +770,11 @@ int nbd_accel_sym_uniform_f32(const float* posm, int n, float softening_sq, floa
   if (!workspace || workspace_bytes < sym_workspace_bytes(n)) return NBD_E_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
   float* slots = static_cast<float*>(workspace);
-  int rc = launch_sym(posm, n, softening_sq, slots, st, variant);
+  const SymPlan sp = plan_sym(n, sym_slots_avail(n, workspace_bytes));
+  int rc = launch_sym(posm, n, softening_sq, slots, sp, st, variant);
   if (rc) return rc;
   const int n3 = 3 * n;
-  finish_kernel<<<ceil_div(n3, 64), 256, 0, st>>>(slots, plan_sym(n).total_slots, (size_t)n3, g_const * mass_value,
+  finish_kernel<<<ceil_div(n3, 64), 256, 0, st>>>(slots, sp.total_slots, (size_t)n3, g_const * mass_value,
                                                    acc_out, nullptr, 0.f, n3);
   return launch_status();
 }
@@ -969,12 +1002,13 @@ static int step_force(float* pos, float* vel, const float* acc_in, float* acc_ou
   if (rc) return rc;
   float* slabs = static_cast<float*>(workspace);
   if (ev_force_begin && (rc = check(hipEventRecord((hipEvent_t)ev_force_begin, st)))) return rc;
-  if (sym) rc = launch_sym(posm, n, softening_sq, slabs, st, 2);
+  const SymPlan sp = plan_sym(n, sym ? sym_slots_avail(n, workspace_bytes) : 0);
+  if (sym) rc = launch_sym(posm, n, softening_sq, slabs, sp, st, 2);
   else rc = launch_accel(posm, full_view(n, p), posm, n, 0, softening_sq, 1.0f, slabs, p, st, uniform);
   if (rc) return rc;
   if (ev_force_end && (rc = check(hipEventRecord((hipEvent_t)ev_force_end, st)))) return rc;
   const int n3 = 3 * n;
-  const int n_slabs = sym ? plan_sym(n).total_slots : p.slabs;
+  const int n_slabs = sym ? sp.total_slots : p.slabs;
   finish_kernel<<<ceil_div(n3, 64), 256, 0, st>>>(slabs, n_slabs, (size_t)n3, g_scale, acc_out, vel, c_kick, n3);
   return launch_status();
 }

@@ -257,6 +257,9 @@ class BaseSimulator(_ChunkedRun):
                          if ((self._sharded or self._equal_mass_step)
                              and os.environ.get("NBD_UNIFORM_MASS", "1") != "0") else None)
         if not self._sharded:
+            # sized for the step's preferred plan (the equal-mass symmetric force: one partial-sum slot per round of its
+            # tile tournament, all rounds in one launch); NBD_SYM_SLOTS=16 keeps the 16-slot plan, as NBD_UNIFORM_MASS=0
+            # keeps the general kernel
             self._ws = direct.step_workspace(max(self.n, 1), self.device)
             self._posm_local, self._mass_local, self._gather = self._posm, self.masses, None
         else:

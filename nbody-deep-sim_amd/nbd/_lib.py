@@ -157,6 +157,7 @@ SIGNATURES = {
     "nbd_drift_f32": (c_int, [c_void_p, c_void_p, c_int, c_float, c_void_p]),
     "nbd_snapshot_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
     "nbd_step_workspace_bytes": (c_size_t, [c_int]),
+    "nbd_step_workspace_pref_bytes": (c_size_t, [c_int]),
     "nbd_leapfrog_step_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
                                       c_float, c_float, c_float, c_float, c_void_p, c_void_p,
                                       c_size_t, c_void_p]),

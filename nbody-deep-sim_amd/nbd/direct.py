@@ -6,6 +6,7 @@ wrong shape must never reach a hand-written kernel) and launches on torch's curr
 from __future__ import annotations
 
 import ctypes
+import os
 
 import numpy as np
 import torch
@@ -157,7 +158,16 @@ def _nbytes(t: torch.Tensor) -> int:
 
 
 def step_workspace(n: int, device) -> torch.Tensor:
-    return alloc_bytes(_lib.lib().nbd_step_workspace_bytes(n), device)
+    """Scratch of the fused step at its preferred plan (nbd_step_workspace_pref_bytes). The step reads its plan off the
+    size it is handed: NBD_SYM_SLOTS=K (read here, at allocation) caps the symmetric force's partial-sum slots at K -- the
+    A/B switch for measurements and the way back to the 16-slot plan (NBD_SYM_SLOTS=16); never below what the step needs."""
+    L = _lib.lib()
+    least, pref = L.nbd_step_workspace_bytes(n), L.nbd_step_workspace_pref_bytes(n)
+    cap = os.environ.get("NBD_SYM_SLOTS")
+    if cap is not None and pref > least:
+        # one slot = n rows of 3 floats; the slot of the rows behind the last whole tile comes on top of the K
+        pref = min(pref, (max(int(cap), 0) + (1 if n % 2048 else 0)) * n * 12)
+    return alloc_bytes(max(least, pref), device)
 
 
 def kick_drift(pos, vel, acc, mass, c_kick: float, c_drift: float, posm=None) -> None:
