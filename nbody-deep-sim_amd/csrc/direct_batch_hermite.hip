@@ -6,10 +6,10 @@
 // per (scene, target group of 128, slab), the slab count of a scene being the single-system plan for its size. One step
 // is three launches for all scenes:
 //   predict  : one thread per packed row: posm = {x_p, m}, velp = {v_p, 0} (zeros in each scene's padding):
-//              hermite_predict (hermite_kernels.h) with the scene's own fp32 step constants
+//              hermite_predict_row (hermite_kernels.h) with the scene's own fp32 step constants
 //   evaluate : one workgroup per item: accel_jerk_body (hermite_kernels.h, KU = 2) on the item's scene, masked or not per scene
 //              from its softening^2; unscaled partial sums into float[slabs][6][n_s] at float 2 * ws_off of the slabs
-//   correct  : one workgroup per 64 packed rows (never across scenes): hermite_slab_sum and hermite_correct with the
+//   correct  : one workgroup per 64 packed rows (never across scenes): hermite_slab_sum and hermite_correct_row with the
 //              scene's G and constants; posm = {x1, m} for the energies after the step
 // A scene's work, its split of the sources and its slab sum depend on n_s and its own parameters alone, and its arithmetic
 // is the single-system kernels' own functions: its results are bit-identical to nbd_hermite_step_f32 on that scene alone.
@@ -45,25 +45,15 @@ __global__ __launch_bounds__(256) void batch_hermite_predict_kernel(const int* _
   const int s = row_scene[r];
   const SceneRec sc = load_scene(scenes, s);
   const int i = r - sc.poff;
-  f4 pm = {0.f, 0.f, 0.f, 0.f}, vp = {0.f, 0.f, 0.f, 0.f};
+  f4 pm = HermiteFmt<float>::zero(), vp = HermiteFmt<float>::zero();
   if (i < sc.n) {
     const int b = sc.off + i;
     const float dt = acc ? hdt[kDt * n_scenes + s] : 0.f;
     const float dt2_half = acc ? hdt[kDt2Half * n_scenes + s] : 0.f;
     const float dt3_sixth = acc ? hdt[kDt3Sixth * n_scenes + s] : 0.f;
-    float x[3], v[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      x[k] = pos[3 * b + k];
-      v[k] = vel[3 * b + k];
-      if (acc) {
-        const PosVel p = hermite_predict(x[k], v[k], acc[3 * b + k], jerk[3 * b + k], dt, dt2_half, dt3_sixth);
-        x[k] = p.x;
-        v[k] = p.v;
-      }
-    }
-    pm = f4{x[0], x[1], x[2], mass[b]};
-    vp = f4{v[0], v[1], v[2], 0.f};
+    const PosVel3<float> p = hermite_predict_row(pos, vel, acc, jerk, (size_t)b, dt, dt2_half, dt3_sixth, acc != nullptr);
+    pm = hermite_row(p.x, mass[b]);
+    vp = hermite_row(p.v, 0.f);
   }
   posm[r] = pm;
   velp[r] = vp;
@@ -107,7 +97,7 @@ __global__ __launch_bounds__(64 * kWaves, 5) void batch_accel_jerk_kernel(const 
 
 // One workgroup per 64 packed rows (a scene's rows are whole chunks of 64, so a block never spans two scenes): a1, j1 =
 // hermite_slab_sum of the body's row in its scene's slabs, scaled by G_s. pos == nullptr: write a1, j1 only. Else
-// hermite_correct: reads a0, j0 (acc_in / jerk_in may alias acc_out / jerk_out: each element is read before it is
+// hermite_correct_row: reads a0, j0 (acc_in / jerk_in may alias acc_out / jerk_out: each element is read before it is
 // written, by the same thread), x, v; writes x1, v1, a1, j1 and posm = {x1, m}.
 __global__ __launch_bounds__(256) void batch_hermite_correct_kernel(const int* __restrict__ row_scene,
                                                                     const SceneRec* __restrict__ scenes,
@@ -118,33 +108,20 @@ __global__ __launch_bounds__(256) void batch_hermite_correct_kernel(const int* _
                                                                     const float* jerk_in, float* acc_out,
                                                                     float* jerk_out, const float* __restrict__ mass,
                                                                     f4* __restrict__ posm) {
-  __shared__ float part[4][6][64];
   const int lane = threadIdx.x & 63;
   const int r0 = blockIdx.x * 64;
   const int s = row_scene[r0];
   const SceneRec sc = load_scene(scenes, s);
   const int i = r0 - sc.poff + lane;
   float a1[3], j1[3];
-  if (!hermite_slab_sum(ws + 2 * (size_t)sc.ws_off, sc.slabs, sc.n, i, i < sc.n, g_s[s], part, a1, j1)) return;
+  if (!hermite_slab_sum(ws + 2 * (size_t)sc.ws_off, sc.slabs, sc.n, (size_t)i, i < sc.n, g_s[s], a1, j1)) return;
   const size_t b = (size_t)sc.off + i;
   if (pos) {
-    const float dt_half = hdt[kDtHalf * n_scenes + s], dt2_twelfth = hdt[kDt2Twelfth * n_scenes + s];
-    float x1[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      const float a0 = acc_in[3 * b + k], j0 = jerk_in[3 * b + k];
-      float x = pos[3 * b + k], v = vel[3 * b + k];
-      hermite_correct(x, v, a0, j0, a1[k], j1[k], dt_half, dt2_twelfth);
-      vel[3 * b + k] = v;
-      pos[3 * b + k] = x1[k] = x;
-    }
-    posm[r0 + lane] = f4{x1[0], x1[1], x1[2], mass[b]};
+    const Corrected<float> c = hermite_correct_row(pos, vel, acc_in, jerk_in, b, a1, j1, hdt[kDtHalf * n_scenes + s],
+                                                   hdt[kDt2Twelfth * n_scenes + s]);
+    posm[r0 + lane] = hermite_row(c.x1, mass[b]);
   }
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    acc_out[3 * b + k] = a1[k];
-    jerk_out[3 * b + k] = j1[k];
-  }
+  hermite_store_force(acc_out, jerk_out, b, a1, j1);
 }
 
 // workspace: velp float4[posm_rows] | slabs fp32[2 * ws_floats] (16-byte aligned: posm_rows * 16 bytes come first)

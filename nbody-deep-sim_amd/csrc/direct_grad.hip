@@ -255,16 +255,15 @@ __global__ __launch_bounds__(64 * kWaves) void accel_vjp_f64_kernel(const d4* __
            out + (size_t)blockIdx.y * AccelVjpPair::kOut * n + t_base, (size_t)n, min(kTgtF64, n - t_base));
 }
 
-// One thread per body: the slabs of double[n_slabs][4][n] in slab order, then G, once. Either output may be null.
+// One thread per body: the slabs of double[n_slabs][4][n] in slab order (slab_order_sum, hermite_kernels.h), then G,
+// once. Either output may be null.
 __global__ __launch_bounds__(256) void accel_vjp_finish_f64_kernel(const double* __restrict__ slabs, int n_slabs, int n,
                                                                    double g, double* __restrict__ grad_pos,
                                                                    double* __restrict__ grad_mass) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
-  double sum[4] = {0.0, 0.0, 0.0, 0.0};
-  for (int s = 0; s < n_slabs; ++s)
-#pragma unroll
-    for (int k = 0; k < 4; ++k) sum[k] += slabs[((size_t)s * 4 + k) * n + i];
+  double sum[4];
+  slab_order_sum<4>(slabs, n_slabs, (size_t)n, (size_t)i, sum);
   if (grad_pos) {
 #pragma unroll
     for (int k = 0; k < 3; ++k) grad_pos[3 * (size_t)i + k] = g * sum[k];

@@ -10,8 +10,10 @@
 //   correct  : fixed-order slab sum, a1 = G sum, j1 = G sum, then
 //              v1 = v + (a0 + a1) dt/2 + (j0 - j1) dt^2/12,  x1 = x + (v + v1) dt/2 + (a0 - a1) dt^2/12,
 //              posm = {x1, m} (energies after the step need no extra pack)
-// The arithmetic of all three (hermite_predict, accel_jerk_body, hermite_slab_sum, hermite_correct) and the step constants
-// (hermite_dt) live in hermite_kernels.h, shared with the block-timestep and the batched unit.
+// The arithmetic of all three (hermite_predict_row, accel_jerk_body, hermite_slab_sum, hermite_correct_row), the step
+// constants (hermite_dt) and the two O(N) kernels themselves (hermite_predict_kernel<T>, hermite_correct_kernel<T>, here
+// at T = float) live in hermite_kernels.h, shared with the block-timestep, the batched, the sharded and the float64
+// units.
 // No atomics, no memsets, no host syncs: deterministic and capturable.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -42,62 +44,7 @@ __global__ __launch_bounds__(64 * kWaves, KU == 2 ? 6 : 5) void accel_jerk_kerne
                               out + (size_t)blockIdx.y * 6 * n + t_base, n, min(kTgtPerWG, n - t_base));
 }
 
-// posm = {x_p, m}, velp = {v_p, 0} for rows [0, n_pad) (zero padding behind n). acc == nullptr: plain pack (x, v).
-__global__ __launch_bounds__(256) void hermite_predict_kernel(const float* __restrict__ pos, const float* __restrict__ vel,
-                                                              const float* __restrict__ acc, const float* __restrict__ jerk,
-                                                              const float* __restrict__ mass, int n, int n_pad, HermiteDt h,
-                                                              f4* __restrict__ posm, f4* __restrict__ velp) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= n_pad) return;
-  f4 pm = {0.f, 0.f, 0.f, 0.f}, vp = {0.f, 0.f, 0.f, 0.f};
-  if (i < n) {
-    float x[3], v[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      x[k] = pos[3 * i + k];
-      v[k] = vel[3 * i + k];
-      if (acc) {
-        const PosVel p = hermite_predict(x[k], v[k], acc[3 * i + k], jerk[3 * i + k], h.dt, h.dt2_half, h.dt3_sixth);
-        x[k] = p.x;
-        v[k] = p.v;
-      }
-    }
-    pm = f4{x[0], x[1], x[2], mass[i]};
-    vp = f4{v[0], v[1], v[2], 0.f};
-  }
-  posm[i] = pm;
-  velp[i] = vp;
-}
-
-// One workgroup per 64 consecutive bodies: a1, j1 = hermite_slab_sum of the body's row. pos == nullptr: write a1, j1
-// only (the force on its own). Else hermite_correct: reads a0, j0 (acc_in / jerk_in, which may alias acc_out / jerk_out:
-// each element is read before it is written, by the same thread), x, v; writes x1, v1, a1, j1 and posm = {x1, m}.
-__global__ __launch_bounds__(256) void hermite_correct_kernel(const float* __restrict__ slabs, int n_slabs, int n, float g,
-                                                              HermiteDt h, float* pos, float* vel, const float* acc_in,
-                                                              const float* jerk_in, float* acc_out, float* jerk_out,
-                                                              const float* __restrict__ mass, f4* __restrict__ posm) {
-  __shared__ float part[4][6][64];
-  const int i = blockIdx.x * 64 + (threadIdx.x & 63);
-  float a1[3], j1[3];
-  if (!hermite_slab_sum(slabs, n_slabs, n, i, i < n, g, part, a1, j1)) return;
-  if (pos) {
-    float x1[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      const float a0 = acc_in[3 * i + k], j0 = jerk_in[3 * i + k];
-      float x = pos[3 * i + k], v = vel[3 * i + k];
-      hermite_correct(x, v, a0, j0, a1[k], j1[k], h.dt_half, h.dt2_twelfth);
-      vel[3 * i + k] = v;
-      pos[3 * i + k] = x1[k] = x;
-    }
-    posm[i] = f4{x1[0], x1[1], x1[2], mass[i]};
-  }
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    acc_out[3 * i + k] = a1[k];
-    jerk_out[3 * i + k] = j1[k];
-  }
-}
+constexpr int kSumRows = HermiteFmt<float>::kSumRows;      // bodies per workgroup of the corrector launch
 
 size_t velp_bytes(int n) { return (size_t)ceil_div(n, kChunk) * kChunk * sizeof(f4); }
 
@@ -131,7 +78,7 @@ int nbd_hermite_pack_f32(const float* pos, const float* vel, const float* acc, c
   if (misaligned16(posm) || misaligned16(velp)) return NBD_E_BADARG;
   if (n == 0) return 0;
   const int n_pad = nbd_posm_padded_len(n);
-  hermite_predict_kernel<<<ceil_div(n_pad, 256), 256, 0, (hipStream_t)stream>>>(
+  hermite_predict_kernel<float><<<ceil_div(n_pad, 256), 256, 0, (hipStream_t)stream>>>(
       pos, vel, acc, jerk, mass, n, n_pad, hermite_dt(dt), reinterpret_cast<f4*>(posm), reinterpret_cast<f4*>(velp));
   return launch_status();
 }
@@ -147,8 +94,9 @@ int nbd_accel_jerk_f32(const float* posm, const float* velp, int n, float soften
   float* slabs = static_cast<float*>(workspace);
   int rc = launch_jerk(posm, velp, n, softening_sq, slabs, p, variant, st);
   if (rc) return rc;
-  hermite_correct_kernel<<<ceil_div(n, 64), 256, 0, st>>>(slabs, p.slabs, n, g_const, hermite_dt(0.0), nullptr, nullptr,
-                                                          nullptr, nullptr, acc_out, jerk_out, nullptr, nullptr);
+  hermite_correct_kernel<float><<<ceil_div(n, kSumRows), 256, 0, st>>>(slabs, p.slabs, n, g_const, hermite_dt(0.0),
+                                                                       nullptr, nullptr, nullptr, nullptr, acc_out,
+                                                                       jerk_out, nullptr, nullptr);
   return launch_status();
 }
 
@@ -166,13 +114,13 @@ int nbd_hermite_step_f32(float* pos, float* vel, const float* acc_in, const floa
   float* velp = static_cast<float*>(workspace);
   float* slabs = reinterpret_cast<float*>(static_cast<char*>(workspace) + velp_bytes(n));
   const int n_pad = nbd_posm_padded_len(n);
-  hermite_predict_kernel<<<ceil_div(n_pad, 256), 256, 0, st>>>(pos, vel, acc_in, jerk_in, mass, n, n_pad, h,
-                                                               reinterpret_cast<f4*>(posm), reinterpret_cast<f4*>(velp));
+  hermite_predict_kernel<float><<<ceil_div(n_pad, 256), 256, 0, st>>>(
+      pos, vel, acc_in, jerk_in, mass, n, n_pad, h, reinterpret_cast<f4*>(posm), reinterpret_cast<f4*>(velp));
   int rc = launch_status();
   if (rc) return rc;
   if ((rc = launch_jerk(posm, velp, n, softening_sq, slabs, p, 0, st))) return rc;
-  hermite_correct_kernel<<<ceil_div(n, 64), 256, 0, st>>>(slabs, p.slabs, n, g_const, h, pos, vel, acc_in, jerk_in,
-                                                          acc_out, jerk_out, mass, reinterpret_cast<f4*>(posm));
+  hermite_correct_kernel<float><<<ceil_div(n, kSumRows), 256, 0, st>>>(
+      slabs, p.slabs, n, g_const, h, pos, vel, acc_in, jerk_in, acc_out, jerk_out, mass, reinterpret_cast<f4*>(posm));
   return launch_status();
 }
 

@@ -17,8 +17,10 @@
 // step constants come from hermite_dt() on the body's fp64 step (dt times its tick count): a body whose Delta is the
 // whole interval gets the shared step's bits. No float atomics (the clamp counter is an integer
 // atomic); the host reads {t_next, n_act} once per block step, so the path is eager-only.
-// The schedule record's layout and the level arithmetic (criterion, wanted_level, norm3) live in hermite_block_kernels.h,
-// shared with the float64 form of this unit, direct_hermite_block_f64.hip; hblock_schedule_kernel serves both.
+// The schedule record's layout, the level arithmetic (criterion, wanted_level, norm3, hblock_relevel) and the O(N)
+// kernels (hblock_init_kernel<T>, hblock_predict_kernel<T>, hblock_correct_kernel<T>, here at T = float) live in
+// hermite_block_kernels.h, shared with the float64 form of this unit, direct_hermite_block_f64.hip; hblock_schedule_kernel
+// serves both.
 #include <hip/hip_runtime.h>
 #include <limits.h>
 #include <stdint.h>
@@ -32,6 +34,7 @@ namespace {
 
 constexpr int kActSlabTarget = 512;  // small active sets: raise the slab count until groups x slabs reaches ~2 per CU
 constexpr int kActMaxSlabs = 256;
+constexpr int kSumRows = HermiteFmt<float>::kSumRows;      // list entries per workgroup of the corrector launch
 
 // Acceleration + jerk of the n_act targets act[0..n_act) under all n sources: accel_jerk_kernel<MASKED, 2> with its
 // targets gathered through the index list (the same accel_jerk_body, so the same chunk stream and wave reduction).
@@ -51,30 +54,6 @@ __global__ __launch_bounds__(64 * kWaves, 6) void accel_jerk_active_kernel(
   wave_chunk_range(jw, cpw_q, cpw_r, c_begin, c_end);
   accel_jerk_body<MASKED, 2>(posm, velp, n, posm, velp, i0, i1, i0, i1, c_begin, c_end, eps2, lds,
                              out + (size_t)blockIdx.y * 6 * n_act + t_base, n_act, min(kTgtPerWG, n_act - t_base));
-}
-
-// Initial levels from dt_i = (eta / 2) |a| / |j| in fp64 (+inf where j = 0); every tick to 0. Levels deeper than K are clamped and counted.
-__global__ __launch_bounds__(256) void hblock_init_kernel(const float* __restrict__ acc, const float* __restrict__ jerk,
-                                                          int n, int K, double dt, double eta, int* __restrict__ ticks,
-                                                          int* __restrict__ levels, int* __restrict__ sched) {
-  __shared__ int hist[kMaxLevel + 1];
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (threadIdx.x <= K) hist[threadIdx.x] = 0;
-  __syncthreads();
-  if (i < n) {
-    const double a = norm3(acc[3 * i], acc[3 * i + 1], acc[3 * i + 2]);
-    const double j = norm3(jerk[3 * i], jerk[3 * i + 1], jerk[3 * i + 2]);
-    int k = wanted_level(j == 0.0 ? INFINITY : 0.5 * eta * a / j, dt, K);
-    if (k > K) {
-      k = K;
-      atomicAdd(&sched[kClamped], 1);
-    }
-    ticks[i] = 0;
-    levels[i] = k;
-    atomicAdd(&hist[k], 1);
-  }
-  __syncthreads();
-  if (threadIdx.x <= K && hist[threadIdx.x]) atomicAdd(&sched[kHist + threadIdx.x], hist[threadIdx.x]);
 }
 
 // t_next from the level histogram and the current tick T = sched[kTCur]; every block derives it alike. Each wave appends
@@ -115,112 +94,6 @@ __global__ __launch_bounds__(256) void hblock_schedule_kernel(const int* __restr
       sched[kDone] = 0;
     }
   }
-}
-
-// posm = {x_p, m}, velp = {v_p, 0} for rows [0, n_pad) (zero padding behind n): every body predicted from its last
-// correction to t_next = sched[0] by hermite_predict over Delta_i = (t_next - t_i) dt / 2^K, its constants from
-// hermite_dt().
-__global__ __launch_bounds__(256) void hblock_predict_kernel(const float* __restrict__ pos, const float* __restrict__ vel,
-                                                             const float* __restrict__ acc, const float* __restrict__ jerk,
-                                                             const float* __restrict__ mass, const int* __restrict__ ticks,
-                                                             int n, int n_pad, double dt, double tick,
-                                                             const int* __restrict__ sched, f4* __restrict__ posm,
-                                                             f4* __restrict__ velp) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= n_pad) return;
-  f4 pm = {0.f, 0.f, 0.f, 0.f}, vp = {0.f, 0.f, 0.f, 0.f};
-  if (i < n) {
-    const HermiteDt h = hermite_dt(dt * (double)(sched[kTNext] - ticks[i]) * tick);  // dt, dt2_half, dt3_sixth used
-    float x[3], v[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      const PosVel p = hermite_predict(pos[3 * i + k], vel[3 * i + k], acc[3 * i + k], jerk[3 * i + k], h.dt, h.dt2_half,
-                                       h.dt3_sixth);
-      x[k] = p.x;
-      v[k] = p.v;
-    }
-    pm = f4{x[0], x[1], x[2], mass[i]};
-    vp = f4{v[0], v[1], v[2], 0.f};
-  }
-  posm[i] = pm;
-  velp[i] = vp;
-}
-
-// The active bodies' corrector, one workgroup per 64 consecutive list entries: a1, j1 = hermite_slab_sum of the entry's
-// row. pos == nullptr: write a1, j1 in list order only (the force on its own). Else, for body i = act[p] with its own step
-// h = dt 2^-k_i: hermite_correct with hermite_dt(h), then the new level from the Aarseth criterion in fp64 (shrink freely;
-// grow by one level where t_next is a multiple of 2 d_i; deeper than K clamped and counted), t_i = t_next (0 at 2^K),
-// posm = {x1, m}.
-__global__ __launch_bounds__(256) void hblock_correct_kernel(const float* __restrict__ slabs, int n_slabs,
-                                                             const int* __restrict__ act, int n_act, float g, int K,
-                                                             double dt, double tick, double eta, float* pos, float* vel,
-                                                             float* acc, float* jerk, const float* __restrict__ mass,
-                                                             int* __restrict__ ticks, int* __restrict__ levels,
-                                                             int* __restrict__ sched, f4* __restrict__ posm) {
-  __shared__ float part[4][6][64];
-  const int p = blockIdx.x * 64 + (threadIdx.x & 63);
-  float a1[3], j1[3];
-  if (!hermite_slab_sum(slabs, n_slabs, n_act, p, p < n_act, g, part, a1, j1)) return;
-  if (!pos) {
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      acc[3 * p + k] = a1[k];
-      jerk[3 * p + k] = j1[k];
-    }
-    return;
-  }
-  const int i = act[p];
-  const int lev = levels[i];
-  const int d = 1 << (K - lev);
-  const double h = dt * (double)d * tick;
-  const HermiteDt hc = hermite_dt(h);  // only dt_half and dt2_twelfth are used; the other three are never formed
-  float x1[3];
-  double a0d[3], j0d[3];
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    const float a0 = acc[3 * i + k], j0 = jerk[3 * i + k];
-    float x = pos[3 * i + k], v = vel[3 * i + k];
-    hermite_correct(x, v, a0, j0, a1[k], j1[k], hc.dt_half, hc.dt2_twelfth);
-    vel[3 * i + k] = v;
-    pos[3 * i + k] = x1[k] = x;
-    acc[3 * i + k] = a1[k];
-    jerk[3 * i + k] = j1[k];
-    a0d[k] = a0;
-    j0d[k] = j0;
-  }
-  posm[i] = f4{x1[0], x1[1], x1[2], mass[i]};
-
-  // Aarseth: a3 = (12 (a0 - a1) + 6 h (j0 + j1)) / h^3, a2(t1) = (-6 (a0 - a1) - h (4 j0 + 2 j1)) / h^2 + h a3
-  double a3[3], a2[3];
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    const double da = a0d[k] - (double)a1[k];
-    a3[k] = (12.0 * da + 6.0 * h * (j0d[k] + (double)j1[k])) / (h * h * h);
-    a2[k] = (-6.0 * da - h * (4.0 * j0d[k] + 2.0 * (double)j1[k])) / (h * h) + h * a3[k];
-  }
-  const double na1 = norm3(a1[0], a1[1], a1[2]), nj1 = norm3(j1[0], j1[1], j1[2]);
-  const double na2 = norm3(a2[0], a2[1], a2[2]), na3 = norm3(a3[0], a3[1], a3[2]);
-  const double crit = criterion(eta, na1 * na2 + nj1 * nj1, nj1 * na3 + na2 * na2);
-  const int want = wanted_level(crit, dt, K);
-  const int t_next = sched[kTNext];
-  int nl = lev;
-  if (want > lev) {
-    nl = want;
-    if (nl > K) {
-      nl = K;
-      atomicAdd(&sched[kClamped], 1);
-    }
-  } else if (want < lev && (t_next & (2 * d - 1)) == 0) {
-    nl = lev - 1;
-  }
-  if (nl != lev) {
-    atomicSub(&sched[kHist + lev], 1);
-    atomicAdd(&sched[kHist + nl], 1);
-  }
-  levels[i] = nl;
-  const int t_now = t_next == (1 << K) ? 0 : t_next;
-  ticks[i] = t_now;
-  if (p == 0) sched[kTCur] = t_now;
 }
 
 // All targets active: the shared step's plan, nbd_accel_plan(n, n), so that the sums are bit-identical to it. Fewer: the
@@ -295,7 +168,7 @@ int nbd_hblock_init_levels(const float* acc, const float* jerk, int n, double dt
   // T, the cursor and the histogram start from zero; t_next, n_act and the clamp count are left as they are
   hipError_t e = hipMemsetAsync(sched + kTCur, 0, (NBD_HBLOCK_SCHED_INTS - kTCur) * sizeof(int), st);
   if (e != hipSuccess) return (int)e;
-  hblock_init_kernel<<<ceil_div(n, 256), 256, 0, st>>>(acc, jerk, n, max_level, dt, eta, ticks, levels, sched);
+  hblock_init_kernel<float><<<ceil_div(n, 256), 256, 0, st>>>(acc, jerk, n, max_level, dt, eta, ticks, levels, sched);
   return launch_status();
 }
 
@@ -319,7 +192,7 @@ int nbd_hblock_predict_f32(const float* pos, const float* vel, const float* acc,
   if (!pos || !vel || !acc || !jerk || !mass || !ticks || !sched || !posm || !velp) return NBD_E_BADARG;
   if (misaligned16(posm) || misaligned16(velp)) return NBD_E_BADARG;
   const int n_pad = nbd_posm_padded_len(n);
-  hblock_predict_kernel<<<ceil_div(n_pad, 256), 256, 0, (hipStream_t)stream>>>(
+  hblock_predict_kernel<float><<<ceil_div(n_pad, 256), 256, 0, (hipStream_t)stream>>>(
       pos, vel, acc, jerk, mass, ticks, n, n_pad, dt, ldexp(1.0, -max_level), sched, reinterpret_cast<f4*>(posm),
       reinterpret_cast<f4*>(velp));
   return launch_status();
@@ -344,7 +217,7 @@ int nbd_hblock_correct_f32(float* pos, float* vel, float* acc, float* jerk, cons
   if (!workspace || misaligned16(workspace) || workspace_bytes < step_bytes(n, n_act)) return NBD_E_WORKSPACE;
   if (n_act == 0) return 0;
   const JerkPlan p = plan_active(n, n_act);
-  hblock_correct_kernel<<<ceil_div(n_act, 64), 256, 0, (hipStream_t)stream>>>(
+  hblock_correct_kernel<float><<<ceil_div(n_act, kSumRows), 256, 0, (hipStream_t)stream>>>(
       ws_slabs(workspace, n), p.slabs, ws_act(workspace), n_act, g_const, max_level, dt, ldexp(1.0, -max_level), eta,
       pos, vel, acc, jerk, mass, ticks, levels, sched, reinterpret_cast<f4*>(posm));
   return launch_status();
@@ -376,9 +249,9 @@ int nbd_accel_jerk_active_f32(const float* posm, const float* velp, int n, const
   float* slabs = ws_slabs(workspace, n);
   int rc = launch_active(posm, velp, n, act, n_act, softening_sq, slabs, p, st);
   if (rc) return rc;
-  hblock_correct_kernel<<<ceil_div(n_act, 64), 256, 0, st>>>(slabs, p.slabs, act, n_act, g_const, 0, 1.0, 1.0, 1.0,
-                                                             nullptr, nullptr, acc_out, jerk_out, nullptr, nullptr,
-                                                             nullptr, nullptr, nullptr);
+  hblock_correct_kernel<float><<<ceil_div(n_act, kSumRows), 256, 0, st>>>(
+      slabs, p.slabs, act, n_act, g_const, 0, 1.0, 1.0, 1.0, nullptr, nullptr, acc_out, jerk_out, nullptr, nullptr,
+      nullptr, nullptr, nullptr);
   return launch_status();
 }
 

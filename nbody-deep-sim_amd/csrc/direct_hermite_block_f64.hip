@@ -15,6 +15,8 @@
 //              the same walk_f64 and AccelJerkPair (hermite_f64_kernels.h)
 //   correct  : the slabs in slab order, hermite_correct<double> with the body's own h, the Aarseth criterion on the fp64
 //              a0, j0, a1, j1 for the new level, t_i = t_next (0 at the end of the interval), posd = {x1, m}
+// The three O(N) kernels are hermite_block_kernels.h's templates at T = double (hblock_init_kernel, hblock_predict_kernel,
+// hblock_correct_kernel with its hblock_relevel): the same source as the fp32 unit's, not a copy of it.
 // Exclusions. Below eps^2 = 1e-24 every chunk is walked index-masked, as in the shared step. Otherwise NO chunk is: a
 // gathered group has no chunk of its own. The shared kernel walks its own chunk masked, which sets s = 0 for j == i and
 // for the padding, so w = c = 0 and each of the nine fma's adds a zero; un-masked, j == i has dr = dv = 0 with a finite
@@ -57,148 +59,7 @@ __global__ __launch_bounds__(64 * kWaves, 5) void accel_jerk_active_f64_kernel(c
            out + (size_t)blockIdx.y * AccelJerkPair::kOut * n_act + t_base, (size_t)n_act, min(kTgtF64, n_act - t_base));
 }
 
-// hblock_init_kernel on an fp64 a, j
-__global__ __launch_bounds__(256) void hblock_init_f64_kernel(const double* __restrict__ acc,
-                                                              const double* __restrict__ jerk, int n, int K, double dt,
-                                                              double eta, int* __restrict__ ticks,
-                                                              int* __restrict__ levels, int* __restrict__ sched) {
-  __shared__ int hist[kMaxLevel + 1];
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (threadIdx.x <= K) hist[threadIdx.x] = 0;
-  __syncthreads();
-  if (i < n) {
-    const size_t r = 3 * (size_t)i;
-    const double a = norm3(acc[r], acc[r + 1], acc[r + 2]);
-    const double j = norm3(jerk[r], jerk[r + 1], jerk[r + 2]);
-    int k = wanted_level(j == 0.0 ? INFINITY : 0.5 * eta * a / j, dt, K);
-    if (k > K) {
-      k = K;
-      atomicAdd(&sched[kClamped], 1);
-    }
-    ticks[i] = 0;
-    levels[i] = k;
-    atomicAdd(&hist[k], 1);
-  }
-  __syncthreads();
-  if (threadIdx.x <= K && hist[threadIdx.x]) atomicAdd(&sched[kHist + threadIdx.x], hist[threadIdx.x]);
-}
-
-// posd = {x_p, m}, veld = {v_p, 0} for rows [0, n_pad) (zero rows behind n): every body predicted from its last correction
-// to t_next = sched[kTNext] by hermite_predict<double> over Delta_i = (t_next - t_i) dt 2^-K. A body whose Delta is the
-// whole interval gets the shared fp64 step's constants.
-__global__ __launch_bounds__(256) void hblock_predict_f64_kernel(const double* __restrict__ pos,
-                                                                 const double* __restrict__ vel,
-                                                                 const double* __restrict__ acc,
-                                                                 const double* __restrict__ jerk,
-                                                                 const double* __restrict__ mass,
-                                                                 const int* __restrict__ ticks, int n, int n_pad,
-                                                                 double dt, double tick, const int* __restrict__ sched,
-                                                                 d4* __restrict__ posd, d4* __restrict__ veld) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= n_pad) return;
-  d4 pm = {0.0, 0.0, 0.0, 0.0}, vp = {0.0, 0.0, 0.0, 0.0};
-  if (i < n) {
-    const HermiteStep<double> h = hermite_step_constants<double>(dt * (double)(sched[kTNext] - ticks[i]) * tick);
-    const size_t r = 3 * (size_t)i;
-    double x[3], v[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      const PosVelT<double> p = hermite_predict(pos[r + k], vel[r + k], acc[r + k], jerk[r + k], h.dt, h.dt2_half,
-                                                h.dt3_sixth);
-      x[k] = p.x;
-      v[k] = p.v;
-    }
-    pm = d4{x[0], x[1], x[2], mass[i]};
-    vp = d4{v[0], v[1], v[2], 0.0};
-  }
-  posd[i] = pm;
-  veld[i] = vp;
-}
-
-// The active bodies' corrector, one thread per list entry p: a1 = g * (slab 0 + slab 1 + ...) of the entry's row in slab
-// order, j1 likewise (correct_f64_kernel's sum). pos == nullptr: write a1, j1 in list order only (the force on its own).
-// Else, for body i = act[p] with its own step h = dt 2^-k_i: hermite_correct<double> with hermite_step_constants<double>(h),
-// then hblock_correct_kernel's new level (shrink freely; grow by one where t_next is a multiple of 2 d_i; deeper than K
-// clamped and counted) from the criterion on the fp64 a0, j0, a1, j1, t_i = t_next (0 at 2^K), posd[i] = {x1, m}.
-__global__ __launch_bounds__(256) void hblock_correct_f64_kernel(const double* __restrict__ slabs, int n_slabs,
-                                                                 const int* __restrict__ act, int n_act, double g, int K,
-                                                                 double dt, double tick, double eta, double* pos,
-                                                                 double* vel, double* acc, double* jerk,
-                                                                 const double* __restrict__ mass, int* __restrict__ ticks,
-                                                                 int* __restrict__ levels, int* __restrict__ sched,
-                                                                 d4* __restrict__ posd) {
-  const int p = blockIdx.x * 256 + threadIdx.x;
-  if (p >= n_act) return;
-  double sum[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-  for (int s = 0; s < n_slabs; ++s)
-#pragma unroll
-    for (int k = 0; k < 6; ++k) sum[k] += slabs[((size_t)s * 6 + k) * n_act + p];
-  double a1[3], j1[3];
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    a1[k] = g * sum[k];
-    j1[k] = g * sum[k + 3];
-  }
-  if (!pos) {
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      acc[3 * (size_t)p + k] = a1[k];
-      jerk[3 * (size_t)p + k] = j1[k];
-    }
-    return;
-  }
-  const int i = act[p];
-  const size_t r = 3 * (size_t)i;
-  const int lev = levels[i];
-  const int d = 1 << (K - lev);
-  const double h = dt * (double)d * tick;
-  const HermiteStep<double> hc = hermite_step_constants<double>(h);
-  double x1[3], a0[3], j0[3];
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    a0[k] = acc[r + k];
-    j0[k] = jerk[r + k];
-    double x = pos[r + k], v = vel[r + k];
-    hermite_correct(x, v, a0[k], j0[k], a1[k], j1[k], hc.dt_half, hc.dt2_twelfth);
-    vel[r + k] = v;
-    pos[r + k] = x1[k] = x;
-    acc[r + k] = a1[k];
-    jerk[r + k] = j1[k];
-  }
-  posd[i] = d4{x1[0], x1[1], x1[2], mass[i]};
-
-  // Aarseth: a3 = (12 (a0 - a1) + 6 h (j0 + j1)) / h^3, a2(t1) = (-6 (a0 - a1) - h (4 j0 + 2 j1)) / h^2 + h a3
-  double a3[3], a2[3];
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    const double da = a0[k] - a1[k];
-    a3[k] = (12.0 * da + 6.0 * h * (j0[k] + j1[k])) / (h * h * h);
-    a2[k] = (-6.0 * da - h * (4.0 * j0[k] + 2.0 * j1[k])) / (h * h) + h * a3[k];
-  }
-  const double na1 = norm3(a1[0], a1[1], a1[2]), nj1 = norm3(j1[0], j1[1], j1[2]);
-  const double na2 = norm3(a2[0], a2[1], a2[2]), na3 = norm3(a3[0], a3[1], a3[2]);
-  const double crit = criterion(eta, na1 * na2 + nj1 * nj1, nj1 * na3 + na2 * na2);
-  const int want = wanted_level(crit, dt, K);
-  const int t_next = sched[kTNext];
-  int nl = lev;
-  if (want > lev) {
-    nl = want;
-    if (nl > K) {
-      nl = K;
-      atomicAdd(&sched[kClamped], 1);
-    }
-  } else if (want < lev && (t_next & (2 * d - 1)) == 0) {
-    nl = lev - 1;
-  }
-  if (nl != lev) {
-    atomicSub(&sched[kHist + lev], 1);
-    atomicAdd(&sched[kHist + nl], 1);
-  }
-  levels[i] = nl;
-  const int t_now = t_next == (1 << K) ? 0 : t_next;
-  ticks[i] = t_now;
-  if (p == 0) sched[kTCur] = t_now;
-}
+constexpr int kSumRows = HermiteFmt<double>::kSumRows;      // list entries per workgroup of the corrector launch
 
 // The workspace: the active list (nbd_hblock_schedule writes it at the start, as in fp32), then, 32-byte aligned, the
 // partial sums double[slabs][6][n_act]. The plan of n_act targets is plan_f64(n, n_act): with every body active that is
@@ -257,7 +118,7 @@ int nbd_hblock_init_levels_f64(const double* acc, const double* jerk, int n, dou
   // T, the cursor and the histogram start from zero; t_next, n_act and the clamp count are left as they are
   hipError_t e = hipMemsetAsync(sched + kTCur, 0, (NBD_HBLOCK_SCHED_INTS - kTCur) * sizeof(int), st);
   if (e != hipSuccess) return (int)e;
-  hblock_init_f64_kernel<<<ceil_div(n, 256), 256, 0, st>>>(acc, jerk, n, max_level, dt, eta, ticks, levels, sched);
+  hblock_init_kernel<double><<<ceil_div(n, 256), 256, 0, st>>>(acc, jerk, n, max_level, dt, eta, ticks, levels, sched);
   return launch_status();
 }
 
@@ -268,7 +129,7 @@ int nbd_hblock_predict_f64(const double* pos, const double* vel, const double* a
   if (!pos || !vel || !acc || !jerk || !mass || !ticks || !sched || !posd || !veld) return NBD_E_BADARG;
   if (misaligned32(posd) || misaligned32(veld)) return NBD_E_BADARG;
   const int n_pad = nbd_posm_padded_len(n);
-  hblock_predict_f64_kernel<<<ceil_div(n_pad, 256), 256, 0, (hipStream_t)stream>>>(
+  hblock_predict_kernel<double><<<ceil_div(n_pad, 256), 256, 0, (hipStream_t)stream>>>(
       pos, vel, acc, jerk, mass, ticks, n, n_pad, dt, ldexp(1.0, -max_level), sched, reinterpret_cast<d4*>(posd),
       reinterpret_cast<d4*>(veld));
   return launch_status();
@@ -293,7 +154,7 @@ int nbd_hblock_correct_f64(double* pos, double* vel, double* acc, double* jerk, 
     return NBD_E_BADARG;
   if (!workspace || misaligned32(workspace) || workspace_bytes < step_bytes_f64(n, n_act)) return NBD_E_WORKSPACE;
   if (n_act == 0) return 0;
-  hblock_correct_f64_kernel<<<ceil_div(n_act, 256), 256, 0, (hipStream_t)stream>>>(
+  hblock_correct_kernel<double><<<ceil_div(n_act, kSumRows), 256, 0, (hipStream_t)stream>>>(
       ws_slabs(workspace, n), plan_f64(n, n_act).slabs, ws_act(workspace), n_act, g_const, max_level, dt,
       ldexp(1.0, -max_level), eta, pos, vel, acc, jerk, mass, ticks, levels, sched, reinterpret_cast<d4*>(posd));
   return launch_status();
@@ -327,9 +188,9 @@ int nbd_accel_jerk_active_f64(const double* posd, const double* veld, int n, con
   double* part = ws_slabs(workspace, n);
   const int rc = launch_active_f64(posd, veld, n, act, n_act, softening_sq, part, p.groups, slabs, st);
   if (rc) return rc;
-  hblock_correct_f64_kernel<<<ceil_div(n_act, 256), 256, 0, st>>>(part, slabs, act, n_act, g_const, 0, 1.0, 1.0, 1.0,
-                                                                  nullptr, nullptr, acc_out, jerk_out, nullptr, nullptr,
-                                                                  nullptr, nullptr, nullptr);
+  hblock_correct_kernel<double><<<ceil_div(n_act, kSumRows), 256, 0, st>>>(
+      part, slabs, act, n_act, g_const, 0, 1.0, 1.0, 1.0, nullptr, nullptr, acc_out, jerk_out, nullptr, nullptr, nullptr,
+      nullptr, nullptr);
   return launch_status();
 }
 

@@ -21,11 +21,13 @@
 // is good to the rounding of its last two operations (about 1 ulp) for any seed better than 2^-10.
 //
 // One step is three launches, as in fp32 (PEC form; a0, j0 carried):
-//   predict : hermite_predict<double> -> posd = {x_p, m}, veld = {v_p, 0}
+//   predict : hermite_predict_kernel<double> -> posd = {x_p, m}, veld = {v_p, 0}
 //   evaluate: accel_jerk_f64_kernel -> double[slabs][6][n] partial sums (unscaled)
-//   correct : the slabs in slab order, a1 = G sum, j1 = G sum, hermite_correct<double>, posd = {x1, m}
-// The predictor, the corrector and the step constants are hermite_kernels.h's templates at T = double: the step constants
-// are the five doubles formed from dt, never rounded to fp32.
+//   correct : hermite_correct_kernel<double>: the slabs in slab order (slab_order_sum, one thread per body), a1 = G sum,
+//             j1 = G sum, the corrector, posd = {x1, m}
+// The two O(N) kernels, the predictor, the corrector and the step constants are hermite_kernels.h's templates at
+// T = double: the step constants are the five doubles formed from dt, never rounded to fp32. The finishing kernels of the
+// diagnostics add their slabs with the same slab_order_sum.
 // rsqrt_f64, AccelJerkPair, walk_f64 and plan_f64 live in hermite_f64_kernels.h, shared with direct_hermite_block_f64.hip.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -140,82 +142,13 @@ __global__ __launch_bounds__(64 * kWaves) void energy_f64_kernel(const d4* __res
            out + (size_t)blockIdx.y * n + t_base, (size_t)n, min(kTgtF64, n - t_base));
 }
 
-// posd = {x_p, m}, veld = {v_p, 0} for rows [0, n_pad) (zero rows behind n). acc == nullptr: plain pack (x, v).
-__global__ __launch_bounds__(256) void predict_f64_kernel(const double* __restrict__ pos, const double* __restrict__ vel,
-                                                          const double* __restrict__ acc, const double* __restrict__ jerk,
-                                                          const double* __restrict__ mass, int n, int n_pad,
-                                                          HermiteStep<double> h, d4* __restrict__ posd,
-                                                          d4* __restrict__ veld) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= n_pad) return;
-  d4 pm = {0.0, 0.0, 0.0, 0.0}, vp = {0.0, 0.0, 0.0, 0.0};
-  if (i < n) {
-    double x[3], v[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      x[k] = pos[3 * (size_t)i + k];
-      v[k] = vel[3 * (size_t)i + k];
-      if (acc) {
-        const PosVelT<double> p = hermite_predict(x[k], v[k], acc[3 * (size_t)i + k], jerk[3 * (size_t)i + k], h.dt,
-                                                  h.dt2_half, h.dt3_sixth);
-        x[k] = p.x;
-        v[k] = p.v;
-      }
-    }
-    pm = d4{x[0], x[1], x[2], mass[i]};
-    vp = d4{v[0], v[1], v[2], 0.0};
-  }
-  posd[i] = pm;
-  veld[i] = vp;
-}
-
-// One thread per body: a1 = g * (slab 0 + slab 1 + ...) in slab order, j1 likewise, from double[n_slabs][6][n].
-// pos == nullptr: write a1, j1 only (the force on its own). Else hermite_correct: reads a0, j0 (acc_in / jerk_in, which may
-// alias acc_out / jerk_out: each element is read before it is written, by the same thread), x, v; writes x1, v1, a1, j1
-// and posd = {x1, m}.
-__global__ __launch_bounds__(256) void correct_f64_kernel(const double* __restrict__ slabs, int n_slabs, int n, double g,
-                                                          HermiteStep<double> h, double* pos, double* vel,
-                                                          const double* acc_in, const double* jerk_in, double* acc_out,
-                                                          double* jerk_out, const double* __restrict__ mass,
-                                                          d4* __restrict__ posd) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  double sum[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-  for (int s = 0; s < n_slabs; ++s)
-#pragma unroll
-    for (int k = 0; k < 6; ++k) sum[k] += slabs[((size_t)s * 6 + k) * n + i];
-  double a1[3], j1[3];
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    a1[k] = g * sum[k];
-    j1[k] = g * sum[k + 3];
-  }
-  if (pos) {
-    double x1[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      const double a0 = acc_in[3 * (size_t)i + k], j0 = jerk_in[3 * (size_t)i + k];
-      double x = pos[3 * (size_t)i + k], v = vel[3 * (size_t)i + k];
-      hermite_correct(x, v, a0, j0, a1[k], j1[k], h.dt_half, h.dt2_twelfth);
-      vel[3 * (size_t)i + k] = v;
-      pos[3 * (size_t)i + k] = x1[k] = x;
-    }
-    posd[i] = d4{x1[0], x1[1], x1[2], mass[i]};
-  }
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    acc_out[3 * (size_t)i + k] = a1[k];
-    jerk_out[3 * (size_t)i + k] = j1[k];
-  }
-}
-
 // phi[i] = -G (slab 0 + slab 1 + ...) in slab order (0 - G sum: a body without partners gets +0)
 __global__ __launch_bounds__(256) void potential_finish_f64_kernel(const double* __restrict__ slabs, int n_slabs, int n,
                                                                    double g, double* __restrict__ phi) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
-  double sum = 0.0;
-  for (int s = 0; s < n_slabs; ++s) sum += slabs[(size_t)s * n + i];
+  double sum;
+  slab_order_sum<1>(slabs, n_slabs, (size_t)n, (size_t)i, &sum);
   phi[i] = 0.0 - g * sum;
 }
 
@@ -228,8 +161,8 @@ __global__ __launch_bounds__(kSumThreads) void energy_finish_f64_kernel(const do
   __shared__ double red[2][kSumWaves];
   double a[2] = {0.0, 0.0};
   for (int i = threadIdx.x; i < n; i += kSumThreads) {
-    double u = 0.0;
-    for (int s = 0; s < n_slabs; ++s) u += slabs[(size_t)s * n + i];
+    double u;
+    slab_order_sum<1>(slabs, n_slabs, (size_t)n, (size_t)i, &u);
     const double m = posd[i].w;
     const double vx = vel[3 * (size_t)i], vy = vel[3 * (size_t)i + 1], vz = vel[3 * (size_t)i + 2];
     a[0] += m * u;
@@ -273,6 +206,8 @@ __global__ __launch_bounds__(kInvThreads) void invariants_state_f64_kernel(const
   invariants_body(F64State{pos, vel, mass}, phi, n, row, red);
 }
 
+constexpr int kSumRows = HermiteFmt<double>::kSumRows;      // bodies per workgroup of the corrector launch
+
 size_t rows_bytes(int n) { return (size_t)ceil_div(n, kChunk) * kChunk * sizeof(d4); }
 
 // the unscaled acceleration + jerk partial sums of every body into double[slabs][6][n]
@@ -309,7 +244,7 @@ int nbd_hermite_f64_pack(const double* pos, const double* vel, const double* acc
   if (misaligned32(posd) || misaligned32(veld)) return NBD_E_BADARG;
   if (n == 0) return 0;
   const int n_pad = nbd_posm_padded_len(n);
-  predict_f64_kernel<<<ceil_div(n_pad, 256), 256, 0, (hipStream_t)stream>>>(
+  hermite_predict_kernel<double><<<ceil_div(n_pad, 256), 256, 0, (hipStream_t)stream>>>(
       pos, vel, acc, jerk, mass, n, n_pad, hermite_step_constants<double>(dt), reinterpret_cast<d4*>(posd),
       reinterpret_cast<d4*>(veld));
   return launch_status();
@@ -329,9 +264,9 @@ int nbd_accel_jerk_f64(const double* posd, const double* veld, int n, double sof
   double* part = static_cast<double*>(workspace);
   const int rc = launch_jerk_f64(posd, veld, n, softening_sq, part, p, slabs, st);
   if (rc) return rc;
-  correct_f64_kernel<<<ceil_div(n, 256), 256, 0, st>>>(part, slabs, n, g_const, hermite_step_constants<double>(0.0),
-                                                       nullptr, nullptr, nullptr, nullptr, acc_out, jerk_out, nullptr,
-                                                       nullptr);
+  hermite_correct_kernel<double><<<ceil_div(n, kSumRows), 256, 0, st>>>(
+      part, slabs, n, g_const, hermite_step_constants<double>(0.0), nullptr, nullptr, nullptr, nullptr, acc_out, jerk_out,
+      nullptr, nullptr);
   return launch_status();
 }
 
@@ -350,13 +285,13 @@ int nbd_hermite_step_f64(double* pos, double* vel, const double* acc_in, const d
   const F64Plan p = plan_f64(n);
   double* part = static_cast<double*>(workspace);
   const int n_pad = nbd_posm_padded_len(n);
-  predict_f64_kernel<<<ceil_div(n_pad, 256), 256, 0, st>>>(pos, vel, acc_in, jerk_in, mass, n, n_pad, h,
-                                                           reinterpret_cast<d4*>(posd), reinterpret_cast<d4*>(veld));
+  hermite_predict_kernel<double><<<ceil_div(n_pad, 256), 256, 0, st>>>(
+      pos, vel, acc_in, jerk_in, mass, n, n_pad, h, reinterpret_cast<d4*>(posd), reinterpret_cast<d4*>(veld));
   int rc = launch_status();
   if (rc) return rc;
   if ((rc = launch_jerk_f64(posd, veld, n, softening_sq, part, p, p.slabs, st))) return rc;
-  correct_f64_kernel<<<ceil_div(n, 256), 256, 0, st>>>(part, p.slabs, n, g_const, h, pos, vel, acc_in, jerk_in, acc_out,
-                                                       jerk_out, mass, reinterpret_cast<d4*>(posd));
+  hermite_correct_kernel<double><<<ceil_div(n, kSumRows), 256, 0, st>>>(
+      part, p.slabs, n, g_const, h, pos, vel, acc_in, jerk_in, acc_out, jerk_out, mass, reinterpret_cast<d4*>(posd));
   return launch_status();
 }
 

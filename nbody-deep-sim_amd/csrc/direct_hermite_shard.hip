@@ -6,14 +6,15 @@
 // The exchanged row is 8 floats, {x_p, y_p, z_p, m, vx_p, vy_p, vz_p, 0}: ONE all-gather per step carries both quads, and
 // accel_jerk_body (hermite_kernels.h, SS = 2) fetches a row's position quad and velocity quad by LDS-DMA at a two-quad
 // stride, so the gathered array is read as it lands (no de-interleave launch). A rank's step is four launches:
-//   predict : hermite_predict of the own bodies -> the send buffer, zero rows behind n_local
+//   predict : hermite_predict_row of the own bodies -> the send buffer, zero rows behind n_local
 //   local   : a, j partial sums of the own bodies under the own bodies (reads the send buffer only: runs while the
 //             gather is in flight); the un-sharded kernel's geometry on n_local sources
 //   remote  : the same under all bodies of the gathered array except [lo, lo + n_local): whole source chunks inside the
 //             range are hopped over, the <= 2 chunks that straddle an end take the masked loop with the range mask
 //             (excluded_view, direct_kernels.h -- the leapfrog shard's view)
-//   finish  : hermite_slab_sum over the local slabs, then the remote ones (a fixed order), times G, and hermite_correct of
-//             the own rows -- a launch of its own, as in the un-sharded step (or a1, j1 only: the force on its own)
+//   finish  : hermite_slab_sum over the local slabs, then the remote ones (a fixed order), times G, and
+//             hermite_correct_row of the own rows -- a launch of its own, as in the un-sharded step (or a1, j1 only: the
+//             force on its own)
 // Every rounded operation is one of hermite_kernels.h's. No atomics, no memsets, no host syncs: deterministic, capturable.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -53,53 +54,29 @@ __global__ __launch_bounds__(256) void shard_predict_kernel(const float* __restr
                                                             const float* __restrict__ acc, const float* __restrict__ jerk,
                                                             const float* __restrict__ mass, int n, int rows, HermiteDt h,
                                                             f4* __restrict__ send) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= rows) return;
-  f4 pm = {0.f, 0.f, 0.f, 0.f}, vp = {0.f, 0.f, 0.f, 0.f};
-  if (i < n) {
-    float x[3], v[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      x[k] = pos[3 * i + k];
-      v[k] = vel[3 * i + k];
-      if (acc) {
-        const PosVel p = hermite_predict(x[k], v[k], acc[3 * i + k], jerk[3 * i + k], h.dt, h.dt2_half, h.dt3_sixth);
-        x[k] = p.x;
-        v[k] = p.v;
-      }
-    }
-    pm = f4{x[0], x[1], x[2], mass[i]};
-    vp = f4{v[0], v[1], v[2], 0.f};
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (size_t)rows) return;
+  f4 pm = HermiteFmt<float>::zero(), vp = HermiteFmt<float>::zero();
+  if (i < (size_t)n) {
+    const PosVel3<float> p = hermite_predict_row(pos, vel, acc, jerk, i, h.dt, h.dt2_half, h.dt3_sixth, acc != nullptr);
+    pm = hermite_row(p.x, mass[i]);
+    vp = hermite_row(p.v, 0.f);
   }
   send[kRowQuads * i] = pm;
   send[kRowQuads * i + 1] = vp;
 }
 
 // One workgroup per 64 consecutive own bodies: a1, j1 = hermite_slab_sum of the body's row over all slabs, local ones
-// first. pos == nullptr: write a1, j1 only. Else hermite_correct (acc_in / jerk_in may alias acc_out / jerk_out: each
+// first. pos == nullptr: write a1, j1 only. Else hermite_correct_row (acc_in / jerk_in may alias acc_out / jerk_out: each
 // element is read before it is written, by the same thread).
 __global__ __launch_bounds__(256) void shard_finish_kernel(const float* __restrict__ slabs, int n_slabs, int n, float g,
                                                            HermiteDt h, float* pos, float* vel, const float* acc_in,
                                                            const float* jerk_in, float* acc_out, float* jerk_out) {
-  __shared__ float part[4][6][64];
-  const int i = blockIdx.x * 64 + (threadIdx.x & 63);
+  const size_t i = hermite_sum_row<float>();
   float a1[3], j1[3];
-  if (!hermite_slab_sum(slabs, n_slabs, n, i, i < n, g, part, a1, j1)) return;
-  if (pos) {
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      const float a0 = acc_in[3 * i + k], j0 = jerk_in[3 * i + k];
-      float x = pos[3 * i + k], v = vel[3 * i + k];
-      hermite_correct(x, v, a0, j0, a1[k], j1[k], h.dt_half, h.dt2_twelfth);
-      vel[3 * i + k] = v;
-      pos[3 * i + k] = x;
-    }
-  }
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    acc_out[3 * i + k] = a1[k];
-    jerk_out[3 * i + k] = j1[k];
-  }
+  if (!hermite_slab_sum(slabs, n_slabs, n, i, i < (size_t)n, g, a1, j1)) return;
+  if (pos) hermite_correct_row(pos, vel, acc_in, jerk_in, i, a1, j1, h.dt_half, h.dt2_twelfth);
+  hermite_store_force(acc_out, jerk_out, i, a1, j1);
 }
 
 // The geometry of a rank's two force launches: the leapfrog shard's slab counts (nbd_shard_plan: same targets, same
@@ -210,9 +187,9 @@ int nbd_hermite_shard_force_remote_f32(const float* all, int n_total, const floa
     const int rc = launch_status();
     if (rc) return rc;
   }
-  shard_finish_kernel<<<ceil_div(n_local, 64), 256, 0, st>>>(slabs, p.slabs_local + p.slabs_remote, n_local, g_const,
-                                                             hermite_dt(dt), pos, vel, acc_in, jerk_in, acc_out,
-                                                             jerk_out);
+  shard_finish_kernel<<<ceil_div(n_local, HermiteFmt<float>::kSumRows), 256, 0, st>>>(
+      slabs, p.slabs_local + p.slabs_remote, n_local, g_const, hermite_dt(dt), pos, vel, acc_in, jerk_in, acc_out,
+      jerk_out);
   return launch_status();
 }
 

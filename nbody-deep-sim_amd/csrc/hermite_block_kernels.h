@@ -1,13 +1,18 @@
 // hermite_block_kernels.h -- what the two block-timestep translation units share (direct_hermite_block.hip: fp32 state;
-// direct_hermite_block_f64.hip: fp64 state): the layout of the schedule record, and the level arithmetic (criterion,
-// wanted_level, norm3). Levels, ticks and the schedule are integers and the criterion is evaluated in fp64 in both modes,
-// so there is one copy of each; the scheduler itself (hblock_schedule_kernel, direct_hermite_block.hip) looks at nothing
-// else and serves both.
+// direct_hermite_block_f64.hip: fp64 state): the layout of the schedule record, the level arithmetic (criterion,
+// wanted_level, norm3), the re-levelling of a corrected body (hblock_relevel), and the three O(N) kernels as templates of
+// the state's scalar type T (hblock_init_kernel<T>, hblock_predict_kernel<T>, hblock_correct_kernel<T>), each unit
+// instantiating its own. Levels, ticks and the schedule are integers and the criterion is evaluated in fp64 in both
+// modes, so there is one copy of each; the scheduler itself (hblock_schedule_kernel, direct_hermite_block.hip) looks at
+// nothing else and serves both. The per-body arithmetic is hermite_kernels.h's (hermite_predict_row, hermite_slab_sum,
+// hermite_correct_row), the step constants hermite_step_constants<T> of the body's own fp64 step: a body whose step is
+// the whole interval gets the shared step's bits.
 // The definitions sit in an anonymous namespace: every translation unit that includes this file gets its own inlined copies.
 #pragma once
 #include <math.h>
 
 #include "direct_kernels.h"
+#include "hermite_kernels.h"
 
 namespace {
 
@@ -40,5 +45,127 @@ __device__ __forceinline__ int wanted_level(double crit, double dt, int K) {
 }
 
 __device__ __forceinline__ double norm3(double x, double y, double z) { return sqrt(x * x + y * y + z * z); }
+
+// Initial levels from dt_i = (eta / 2) |a| / |j| in fp64 (+inf where j = 0); every tick to 0. Levels deeper than K are
+// clamped and counted.
+template <class T>
+__global__ __launch_bounds__(256) void hblock_init_kernel(const T* __restrict__ acc, const T* __restrict__ jerk, int n,
+                                                          int K, double dt, double eta, int* __restrict__ ticks,
+                                                          int* __restrict__ levels, int* __restrict__ sched) {
+  __shared__ int hist[kMaxLevel + 1];
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (threadIdx.x <= K) hist[threadIdx.x] = 0;
+  __syncthreads();
+  if (i < (size_t)n) {
+    const double a = norm3(acc[3 * i], acc[3 * i + 1], acc[3 * i + 2]);
+    const double j = norm3(jerk[3 * i], jerk[3 * i + 1], jerk[3 * i + 2]);
+    int k = wanted_level(j == 0.0 ? INFINITY : 0.5 * eta * a / j, dt, K);
+    if (k > K) {
+      k = K;
+      atomicAdd(&sched[kClamped], 1);
+    }
+    ticks[i] = 0;
+    levels[i] = k;
+    atomicAdd(&hist[k], 1);
+  }
+  __syncthreads();
+  if (threadIdx.x <= K && hist[threadIdx.x]) atomicAdd(&sched[kHist + threadIdx.x], hist[threadIdx.x]);
+}
+
+// posm = {x_p, m}, velp = {v_p, 0} for rows [0, n_pad) (zero rows behind n): every body predicted from its last
+// correction to t_next = sched[kTNext] by hermite_predict_row over Delta_i = (t_next - t_i) dt / 2^K, its constants from
+// hermite_step_constants<T> (dt, dt2_half and dt3_sixth are used).
+template <class T>
+__global__ __launch_bounds__(256) void hblock_predict_kernel(const T* __restrict__ pos, const T* __restrict__ vel,
+                                                             const T* __restrict__ acc, const T* __restrict__ jerk,
+                                                             const T* __restrict__ mass, const int* __restrict__ ticks,
+                                                             int n, int n_pad, double dt, double tick,
+                                                             const int* __restrict__ sched,
+                                                             typename HermiteFmt<T>::Row* __restrict__ posm,
+                                                             typename HermiteFmt<T>::Row* __restrict__ velp) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (size_t)n_pad) return;
+  typename HermiteFmt<T>::Row pm = HermiteFmt<T>::zero(), vp = HermiteFmt<T>::zero();
+  if (i < (size_t)n) {
+    const HermiteStep<T> h = hermite_step_constants<T>(dt * (double)(sched[kTNext] - ticks[i]) * tick);
+    const PosVel3<T> p = hermite_predict_row(pos, vel, acc, jerk, i, h.dt, h.dt2_half, h.dt3_sixth, true);
+    pm = hermite_row(p.x, mass[i]);
+    vp = hermite_row(p.v, (T)0);
+  }
+  posm[i] = pm;
+  velp[i] = vp;
+}
+
+// The new level of body i, corrected from (a0, j0) to (a1, j1) over its step h = d ticks at level lev, from the Aarseth
+// criterion in fp64: shrink freely; grow by one level where t_next is a multiple of 2 d; deeper than K clamped and
+// counted. Moves the body in the level histogram, sets t_i = t_next (0 at 2^K); `first` (one thread of the launch)
+// publishes that tick as sched[kTCur].
+//   a3 = (12 (a0 - a1) + 6 h (j0 + j1)) / h^3, a2(t1) = (-6 (a0 - a1) - h (4 j0 + 2 j1)) / h^2 + h a3
+template <class T>
+__device__ __forceinline__ void hblock_relevel(const T* a0, const T* j0, const T* a1, const T* j1, double h, double dt,
+                                               double eta, int K, int lev, int d, int i, bool first,
+                                               int* __restrict__ ticks, int* __restrict__ levels,
+                                               int* __restrict__ sched) {
+  double a3[3], a2[3];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const double da = (double)a0[k] - (double)a1[k];
+    a3[k] = (12.0 * da + 6.0 * h * ((double)j0[k] + (double)j1[k])) / (h * h * h);
+    a2[k] = (-6.0 * da - h * (4.0 * (double)j0[k] + 2.0 * (double)j1[k])) / (h * h) + h * a3[k];
+  }
+  const double na1 = norm3(a1[0], a1[1], a1[2]), nj1 = norm3(j1[0], j1[1], j1[2]);
+  const double na2 = norm3(a2[0], a2[1], a2[2]), na3 = norm3(a3[0], a3[1], a3[2]);
+  const double crit = criterion(eta, na1 * na2 + nj1 * nj1, nj1 * na3 + na2 * na2);
+  const int want = wanted_level(crit, dt, K);
+  const int t_next = sched[kTNext];
+  int nl = lev;
+  if (want > lev) {
+    nl = want;
+    if (nl > K) {
+      nl = K;
+      atomicAdd(&sched[kClamped], 1);
+    }
+  } else if (want < lev && (t_next & (2 * d - 1)) == 0) {
+    nl = lev - 1;
+  }
+  if (nl != lev) {
+    atomicSub(&sched[kHist + lev], 1);
+    atomicAdd(&sched[kHist + nl], 1);
+  }
+  levels[i] = nl;
+  const int t_now = t_next == (1 << K) ? 0 : t_next;
+  ticks[i] = t_now;
+  if (first) sched[kTCur] = t_now;
+}
+
+// The active bodies' corrector, one workgroup per HermiteFmt<T>::kSumRows consecutive list entries: a1, j1 =
+// hermite_slab_sum of the entry's row p. pos == nullptr: write a1, j1 in list order only (the force on its own). Else, for
+// body i = act[p] with its own step h = dt 2^-k_i: hermite_correct_row with hermite_step_constants<T>(h) (only dt_half and
+// dt2_twelfth are used; the other three are never formed), a1, j1, posm = {x1, m}, then hblock_relevel.
+template <class T>
+__global__ __launch_bounds__(256) void hblock_correct_kernel(const T* __restrict__ slabs, int n_slabs,
+                                                             const int* __restrict__ act, int n_act, T g, int K,
+                                                             double dt, double tick, double eta, T* pos, T* vel, T* acc,
+                                                             T* jerk, const T* __restrict__ mass, int* __restrict__ ticks,
+                                                             int* __restrict__ levels, int* __restrict__ sched,
+                                                             typename HermiteFmt<T>::Row* __restrict__ posm) {
+  const size_t p = hermite_sum_row<T>();
+  T a1[3], j1[3];
+  if (!hermite_slab_sum(slabs, n_slabs, n_act, p, p < (size_t)n_act, g, a1, j1)) return;
+  if (!pos) {
+    hermite_store_force(acc, jerk, p, a1, j1);
+    return;
+  }
+  const int i = act[p];
+  const int lev = levels[i];
+  const int d = 1 << (K - lev);
+  const double h = dt * (double)d * tick;
+  const HermiteStep<T> hc = hermite_step_constants<T>(h);
+  const Corrected<T> c = hermite_correct_row(pos, vel, acc, jerk, (size_t)i, a1, j1, hc.dt_half, hc.dt2_twelfth);
+  hermite_store_force(acc, jerk, (size_t)i, a1, j1);
+  posm[i] = hermite_row(c.x1, mass[i]);
+  hblock_relevel(c.a0, c.j0, a1, j1, h, dt, eta, K, lev, d, i, p == 0, ticks, levels, sched);
+}
+
 
 }  // namespace

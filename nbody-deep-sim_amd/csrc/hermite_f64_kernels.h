@@ -11,8 +11,6 @@
 
 namespace {
 
-typedef double d4 __attribute__((ext_vector_type(4)));
-
 constexpr int kTgtF64 = 64;                      // targets per workgroup: one per lane, = one source chunk
 constexpr int kRowQuads = 2;                     // 16-byte LDS-DMA pieces per 32-byte row
 constexpr int kChunkQuads = kChunk * kRowQuads;  // 128 quads = 2 KiB per chunk and array

@@ -5,14 +5,18 @@
 //     reduction, store; its compile-time parameters also give direct_hermite_shard.hip's range-sharded blocks: targets
 //     apart from the sources, 8-float rows, a skipped source range) and the split of the chunks over the waves
 //     (chunk_split on the host, wave_chunk_range in a kernel);
-//   - the O(N) arithmetic: the fp32 step constants (hermite_dt), the predictor (hermite_predict), the fixed-order slab sum
-//     (hermite_slab_sum) and the corrector (hermite_correct); the constants, the predictor and the corrector are templates
-//     of the scalar type, instantiated with double by direct_hermite_f64.hip and direct_hermite_block_f64.hip (the float
-//     instantiation is the code it was);
+//   - the O(N) stages, templates of the scalar type T of the state (float; double for direct_hermite_f64.hip and
+//     direct_hermite_block_f64.hip): what the format fixes (HermiteFmt<T>: the packed row, the rows per workgroup of a
+//     finishing launch), the step constants (hermite_step_constants; hermite_dt for fp32), the predictor of one component
+//     and of one body (hermite_predict, hermite_predict_row), the fixed-order slab sum (hermite_slab_sum: the 4-wave
+//     scheme for float, slab_order_sum for double -- two orders, each format keeps its own), the corrector of one
+//     component and of one body (hermite_correct, hermite_correct_row), and the shared step's two O(N) kernels
+//     (hermite_predict_kernel<T>, hermite_correct_kernel<T>), which direct_hermite.hip and direct_hermite_f64.hip
+//     instantiate;
 //   - the launch plan of a force launch (JerkPlan, plan_jerk).
 // A kernel of one of the units is a prologue that says which targets, which chunks, which rows and which constants, and
 // calls of these: a scene of a batch, or a block step at level 0, is bit-identical to the shared-timestep step because
-// there is one copy of every rounded operation, not because three copies are kept alike.
+// there is one copy of every rounded operation, in either format, not because copies are kept alike.
 // The definitions sit in an anonymous namespace: every translation unit that includes this file gets its own inlined copies.
 #pragma once
 #include "direct_kernels.h"
@@ -255,12 +259,36 @@ __host__ __device__ inline HermiteStep<T> hermite_step_constants(double dt) {
 
 __host__ __device__ inline HermiteDt hermite_dt(double dt) { return hermite_step_constants<float>(dt); }
 
+// What a number format (the scalar type T of the state) fixes for the O(N) stages: the packed row {x, y, z, w} the force
+// kernels read, its zero (the padding behind n), and the geometry of the finishing launch that adds the slabs
+// (hermite_slab_sum below) -- the rows a 256-thread workgroup covers; a launch site takes its grid from it.
+template <class T> struct HermiteFmt;
+template <> struct HermiteFmt<float> {
+  using Row = f4;
+  static __device__ __forceinline__ Row zero() { return Row{0.f, 0.f, 0.f, 0.f}; }
+  static constexpr int kSumRows = 64;       // 4 waves on the same 64 rows
+};
+template <> struct HermiteFmt<double> {
+  using Row = d4;
+  static __device__ __forceinline__ Row zero() { return Row{0.0, 0.0, 0.0, 0.0}; }
+  static constexpr int kSumRows = 256;      // one thread per row
+};
+
+template <class T>
+__device__ __forceinline__ typename HermiteFmt<T>::Row hermite_row(const T* x, const T w) {
+  return typename HermiteFmt<T>::Row{x[0], x[1], x[2], w};
+}
+
+// the row of the finishing launch this thread works on
+template <class T>
+__device__ __forceinline__ size_t hermite_sum_row() {
+  return (size_t)blockIdx.x * HermiteFmt<T>::kSumRows + threadIdx.x % HermiteFmt<T>::kSumRows;
+}
+
 // One component of the predictor, each product and sum rounded on its own (the build has -ffp-contract=off):
 // x_p = x + v dt + a dt^2/2 + j dt^3/6, v_p = v + a dt + j dt^2/2.
-// T = float for the fp32 units, double for direct_hermite_f64.hip and direct_hermite_block_f64.hip.
 template <class T>
 struct PosVelT { T x, v; };
-using PosVel = PosVelT<float>;
 
 template <class T>
 __device__ __forceinline__ PosVelT<T> hermite_predict(const T x, const T v, const T a, const T j, const T dt,
@@ -268,13 +296,73 @@ __device__ __forceinline__ PosVelT<T> hermite_predict(const T x, const T v, cons
   return PosVelT<T>{((x + v * dt) + a * dt2_half) + j * dt3_sixth, (v + a * dt) + j * dt2_half};
 }
 
-// a1 = g * sum of the slabs, j1 likewise, in a fixed order, for a workgroup of 4 waves on 64 consecutive rows of
-// slabs = float[n_slabs][6][stride] (finish_kernel's scheme: wave w sums slabs w, w+4, ... of its lane's row, the four
-// partials combined as (p0 + p1) + (p2 + p3)). Every thread of the workgroup calls it (it holds the barrier) with its
-// row = first row + lane; a row that is not valid reads nothing. part: the workgroup's exchange buffer. True for the
-// one thread per valid row (wave 0) that holds a1, j1.
-__device__ __forceinline__ bool hermite_slab_sum(const float* __restrict__ slabs, int n_slabs, int stride, int row,
-                                                 bool valid, float g, float (*part)[6][64], float* a1, float* j1) {
+// The predictor of body i of pos, vel, acc, jerk (n, 3): its three components of x_p and of v_p. predict == false: x and
+// v as they are (a plain pack; acc and jerk are not read). (Two local arrays, copied out at the end: filled in place, the
+// returned struct makes hipcc pair the fp32 additions of x_p and v_p into v_pk_add_f32 -- the same bits, another kernel.)
+template <class T>
+struct PosVel3 { T x[3], v[3]; };
+
+template <class T>
+__device__ __forceinline__ PosVel3<T> hermite_predict_row(const T* __restrict__ pos, const T* __restrict__ vel,
+                                                          const T* __restrict__ acc, const T* __restrict__ jerk,
+                                                          const size_t i, const T dt, const T dt2_half,
+                                                          const T dt3_sixth, const bool predict) {
+  T x[3], v[3];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    x[k] = pos[3 * i + k];
+    v[k] = vel[3 * i + k];
+    if (predict) {
+      const PosVelT<T> p = hermite_predict(x[k], v[k], acc[3 * i + k], jerk[3 * i + k], dt, dt2_half, dt3_sixth);
+      x[k] = p.x;
+      v[k] = p.v;
+    }
+  }
+  return PosVel3<T>{{x[0], x[1], x[2]}, {v[0], v[1], v[2]}};
+}
+
+// posm = {x_p, m}, velp = {v_p, 0} for rows [0, n_pad) (zero rows behind n). acc == nullptr: plain pack (x, v).
+template <class T>
+__global__ __launch_bounds__(256) void hermite_predict_kernel(const T* __restrict__ pos, const T* __restrict__ vel,
+                                                              const T* __restrict__ acc, const T* __restrict__ jerk,
+                                                              const T* __restrict__ mass, int n, int n_pad,
+                                                              HermiteStep<T> h,
+                                                              typename HermiteFmt<T>::Row* __restrict__ posm,
+                                                              typename HermiteFmt<T>::Row* __restrict__ velp) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (size_t)n_pad) return;
+  typename HermiteFmt<T>::Row pm = HermiteFmt<T>::zero(), vp = HermiteFmt<T>::zero();
+  if (i < (size_t)n) {
+    const PosVel3<T> p = hermite_predict_row(pos, vel, acc, jerk, i, h.dt, h.dt2_half, h.dt3_sixth, acc != nullptr);
+    pm = hermite_row(p.x, mass[i]);
+    vp = hermite_row(p.v, (T)0);
+  }
+  posm[i] = pm;
+  velp[i] = vp;
+}
+
+// sum[k] = slab 0 + slab 1 + ... of row `row`, component k < K, of slabs = double[n_slabs][K][stride], in slab order:
+// the fp64 units' sum, one thread per row.
+template <int K>
+__device__ __forceinline__ void slab_order_sum(const double* __restrict__ slabs, int n_slabs, size_t stride, size_t row,
+                                               double* sum) {
+#pragma unroll
+  for (int k = 0; k < K; ++k) sum[k] = 0.0;
+  for (int s = 0; s < n_slabs; ++s)
+#pragma unroll
+    for (int k = 0; k < K; ++k) sum[k] += slabs[((size_t)s * K + k) * stride + row];
+}
+
+// a1 = g * sum of the slabs of slabs = T[n_slabs][6][stride], j1 likewise, in a fixed order, by a 256-thread workgroup on
+// HermiteFmt<T>::kSumRows consecutive rows; row = hermite_sum_row<T>(). Every thread of the workgroup calls it (the fp32
+// form holds a barrier); a row that is not valid reads nothing. True for the one thread per valid row that holds a1, j1.
+// The two formats add in different orders, and each keeps its own:
+//   float : finish_kernel's scheme, 4 waves on 64 rows: wave w sums slabs w, w+4, ... of its lane's row, the four
+//           partials combined through LDS as (p0 + p1) + (p2 + p3); wave 0 holds the result.
+//   double: slab_order_sum, one thread per row.
+__device__ __forceinline__ bool hermite_slab_sum(const float* __restrict__ slabs, int n_slabs, int stride, size_t row,
+                                                 bool valid, float g, float* a1, float* j1) {
+  __shared__ float part[4][6][64];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   float sum[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
   if (valid)
@@ -296,6 +384,19 @@ __device__ __forceinline__ bool hermite_slab_sum(const float* __restrict__ slabs
   return true;
 }
 
+__device__ __forceinline__ bool hermite_slab_sum(const double* __restrict__ slabs, int n_slabs, int stride, size_t row,
+                                                 bool valid, double g, double* a1, double* j1) {
+  if (!valid) return false;
+  double sum[6];
+  slab_order_sum<6>(slabs, n_slabs, (size_t)stride, row, sum);
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    a1[k] = g * sum[k];
+    j1[k] = g * sum[k + 3];
+  }
+  return true;
+}
+
 // One component of the corrector, each product and sum rounded on its own:
 // v1 = v + (a0 + a1) dt/2 + (j0 - j1) dt^2/12, x1 = x + (v + v1) dt/2 + (a0 - a1) dt^2/12.
 template <class T>
@@ -304,6 +405,57 @@ __device__ __forceinline__ void hermite_correct(T& x, T& v, const T a0, const T 
   const T v1 = (v + (a0 + a1) * dt_half) + (j0 - j1) * dt2_twelfth;
   x = (x + (v + v1) * dt_half) + (a0 - a1) * dt2_twelfth;
   v = v1;
+}
+
+// The corrector of body i: reads a0, j0 (acc_in / jerk_in, which may alias the arrays a1, j1 are stored to afterwards:
+// each element is read before it is written, by the same thread), x, v; writes x1, v1. Returns x1 and the a0, j0 it read.
+template <class T>
+struct Corrected { T x1[3], a0[3], j0[3]; };
+
+template <class T>
+__device__ __forceinline__ Corrected<T> hermite_correct_row(T* pos, T* vel, const T* acc_in, const T* jerk_in,
+                                                            const size_t i, const T* a1, const T* j1, const T dt_half,
+                                                            const T dt2_twelfth) {
+  Corrected<T> c;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    c.a0[k] = acc_in[3 * i + k];
+    c.j0[k] = jerk_in[3 * i + k];
+    T x = pos[3 * i + k], v = vel[3 * i + k];
+    hermite_correct(x, v, c.a0[k], c.j0[k], a1[k], j1[k], dt_half, dt2_twelfth);
+    vel[3 * i + k] = v;
+    pos[3 * i + k] = c.x1[k] = x;
+  }
+  return c;
+}
+
+// acc[i] = a1, jerk[i] = j1
+template <class T>
+__device__ __forceinline__ void hermite_store_force(T* acc, T* jerk, const size_t i, const T* a1, const T* j1) {
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    acc[3 * i + k] = a1[k];
+    jerk[3 * i + k] = j1[k];
+  }
+}
+
+// One workgroup per HermiteFmt<T>::kSumRows consecutive bodies: a1, j1 = hermite_slab_sum of the body's row. pos ==
+// nullptr: write a1, j1 only (the force on its own). Else hermite_correct_row, then a1, j1 and posm = {x1, m} (energies
+// after the step need no extra pack).
+template <class T>
+__global__ __launch_bounds__(256) void hermite_correct_kernel(const T* __restrict__ slabs, int n_slabs, int n, T g,
+                                                              HermiteStep<T> h, T* pos, T* vel, const T* acc_in,
+                                                              const T* jerk_in, T* acc_out, T* jerk_out,
+                                                              const T* __restrict__ mass,
+                                                              typename HermiteFmt<T>::Row* __restrict__ posm) {
+  const size_t i = hermite_sum_row<T>();
+  T a1[3], j1[3];
+  if (!hermite_slab_sum(slabs, n_slabs, n, i, i < (size_t)n, g, a1, j1)) return;
+  if (pos) {
+    const Corrected<T> c = hermite_correct_row(pos, vel, acc_in, jerk_in, i, a1, j1, h.dt_half, h.dt2_twelfth);
+    posm[i] = hermite_row(c.x1, mass[i]);
+  }
+  hermite_store_force(acc_out, jerk_out, i, a1, j1);
 }
 
 }  // namespace

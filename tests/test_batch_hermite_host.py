@@ -162,3 +162,6 @@ def test_step_kernels_have_no_scratch(asm, kernel):
     r = _resources(asm, _name(asm, kernel))
     assert r["private_segment_fixed_size"] == 0 and r["vgpr_spill_count"] == 0, r
     assert not any("scratch_" in ln or "buffer_" in ln for ln in _function(asm, _name(asm, kernel)).split("\n"))
+    desc = asm[asm.index(".amdhsa_kernel " + _name(asm, kernel)):]
+    lds = int(re.search(r"\.amdhsa_group_segment_fixed_size\s+(\d+)", desc).group(1))
+    assert lds == (6144 if kernel == "batch_hermite_correct_kernel" else 0)      # the slab sum's float[4][6][64]

@@ -21,8 +21,10 @@ ENTRIES = ("nbd_hblock_f64_workspace_bytes", "nbd_hblock_init_levels_f64", "nbd_
            "nbd_hblock_force_f64", "nbd_hblock_correct_f64", "nbd_hblock_step_f64", "nbd_accel_jerk_active_f64")
 SRC = os.path.join(ROOT, "nbody-deep-sim_amd", "csrc", "direct_hermite_block_f64.hip")
 FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-ffp-contract=off", "--cuda-device-only", "-S"]
-KERNELS = ("accel_jerk_active_f64_kernel", "hblock_init_f64_kernel", "hblock_predict_f64_kernel",
-           "hblock_correct_f64_kernel")
+# the force kernel, and the double instantiations of hermite_block_kernels.h's templates (the float ones:
+# test_block_hermite_host.py)
+KERNELS = ("accel_jerk_active_f64_kernel", "hblock_init_kernelId", "hblock_predict_kernelId", "hblock_correct_kernelId")
+LDS = {"hblock_init_kernelId": 84, "hblock_correct_kernelId": 0}      # int[21] of level counts; one thread per row: none
 
 
 @pytest.mark.parametrize("eps", [0.0, 0.01])
@@ -148,6 +150,9 @@ def test_new_kernels_have_no_scratch_and_no_spills(asm, kernel):
     num = lambda key: int(re.search(key + r":\s+(\d+)", meta).group(1))      # noqa: E731
     assert num(r"\.private_segment_fixed_size") == 0 and num(r"\.vgpr_spill_count") == 0
     assert num(r"\.sgpr_spill_count") == 0
+    if kernel in LDS:
+        desc = asm[asm.index(".amdhsa_kernel " + name):]
+        assert int(re.search(r"\.amdhsa_group_segment_fixed_size\s+(\d+)", desc).group(1)) == LDS[kernel]
     if kernel == "accel_jerk_active_f64_kernel":
         assert num(r"\.vgpr_count") <= 96               # 5 workgroups per CU (32 KiB of LDS each), as accel_jerk_f64_kernel
         body = asm[asm.index(name + ":"):]
@@ -163,8 +168,15 @@ def test_no_float_atomics_and_one_copy_of_the_wave_body(asm):
     units = {f: open(os.path.join(csrc, f)).read() for f in os.listdir(csrc) if f.endswith((".hip", ".h"))}
     for what in ("void walk_f64(", "struct AccelJerkPair", "double rsqrt_f64(", "F64Plan plan_f64(int n, int n_tgt)"):
         assert [f for f, text in units.items() if what in text] == ["hermite_f64_kernels.h"], what
-    for what in ("double criterion(", "int wanted_level(", "double norm3(", "enum { kTNext"):
+    for what in ("double criterion(", "int wanted_level(", "double norm3(", "enum { kTNext", "void hblock_relevel(",
+                 "void hblock_init_kernel(", "void hblock_predict_kernel(", "void hblock_correct_kernel("):
         assert [f for f, text in units.items() if what in text] == ["hermite_block_kernels.h"], what
+    # the O(N) stages of both formats: one row predictor, one row corrector, one slab-order sum, two templated kernels
+    for what in ("PosVel3<T> hermite_predict_row(", "Corrected<T> hermite_correct_row(", "void slab_order_sum(",
+                 "void hermite_predict_kernel(", "void hermite_correct_kernel(", "struct HermiteFmt<double>"):
+        assert [f for f, text in units.items() if what in text] == ["hermite_kernels.h"], what
+    for f in ("direct_hermite_f64.hip", "direct_hermite_block_f64.hip"):      # no slab loop written out in an fp64 unit
+        assert "+= slabs[" not in units[f], f
 
 
 def test_dtype_errors_come_before_any_device_work():

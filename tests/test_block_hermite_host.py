@@ -124,11 +124,19 @@ def test_active_kernel_resources(asm, masked):
 @pytest.mark.parametrize("kernel", ["hblock_init_kernel", "hblock_schedule_kernel", "hblock_predict_kernel",
                                     "hblock_correct_kernel"])
 def test_other_kernels_have_no_scratch(asm, kernel):
-    names = re.findall(r"\.name:\s+(\S*" + kernel + r"\S*)", asm)
+    """The scheduler, and the float instantiations (mangled ...kernelIfE...) of hermite_block_kernels.h's templates; the
+    double ones: test_block_hermite_f64_host.py. LDS: int[21] of level counts in init, the slab sum's float[4][6][64] in
+    the corrector."""
+    lds = {"hblock_init_kernel": 84, "hblock_correct_kernel": 6144}.get(kernel)
+    suffix = "" if kernel == "hblock_schedule_kernel" else "If"
+    names = re.findall(r"\.name:\s+(\S*" + kernel + suffix + r"\S*)", asm)
     assert len(names) == 1
     meta = _meta(asm, names[0])
     assert int(re.search(r"\.private_segment_fixed_size:\s+(\d+)", meta).group(1)) == 0
     assert int(re.search(r"\.vgpr_spill_count:\s+(\d+)", meta).group(1)) == 0
+    if lds is not None:
+        desc = asm[asm.index(".amdhsa_kernel " + names[0]):]
+        assert int(re.search(r"\.amdhsa_group_segment_fixed_size\s+(\d+)", desc).group(1)) == lds
 
 
 def test_no_float_atomics(asm):

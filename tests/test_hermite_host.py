@@ -117,11 +117,16 @@ def test_accel_jerk_kernel_resources(asm, masked, ku, max_vgpr):
 
 @pytest.mark.parametrize("kernel", ["hermite_predict_kernel", "hermite_correct_kernel"])
 def test_step_kernels_have_no_scratch(asm, kernel):
-    names = re.findall(r"\.name:\s+(\S*" + kernel + r"\S*)", asm)
+    """The float instantiations (mangled ...kernelIfE...) of hermite_kernels.h's two O(N) kernels; the double ones:
+    test_hermite_f64_host.py. The corrector's LDS is the slab sum's float[4][6][64]."""
+    lds = {"hermite_predict_kernel": 0, "hermite_correct_kernel": 6144}[kernel]
+    names = re.findall(r"\.name:\s+(\S*" + kernel + r"If\S*)", asm)
     assert len(names) == 1
     meta = _meta(asm, names[0])
     assert int(re.search(r"\.private_segment_fixed_size:\s+(\d+)", meta).group(1)) == 0
     assert int(re.search(r"\.vgpr_spill_count:\s+(\d+)", meta).group(1)) == 0
+    desc = asm[asm.index(".amdhsa_kernel " + names[0]):]
+    assert int(re.search(r"\.amdhsa_group_segment_fixed_size\s+(\d+)", desc).group(1)) == lds
 
 
 def _cli():
