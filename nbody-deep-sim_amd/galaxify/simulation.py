@@ -96,18 +96,12 @@ class SimulationState:
     invariants: Invariants = None
 
 
-def _to_f32(x, device) -> torch.Tensor:
-    # simulation.py:58-65 makes fp32 device copies with torch.tensor(...)
+def _to_device(x, device, dtype) -> torch.Tensor:
+    """A device copy in `dtype`, converted directly (float64 never through float32); simulation.py:58-65 makes its fp32
+    copies with torch.tensor(...)."""
     if isinstance(x, torch.Tensor):
-        return x.detach().to(device=device, dtype=torch.float32, copy=True).contiguous()
-    return torch.tensor(np.asarray(x), dtype=torch.float32, device=device).contiguous()
-
-
-def _to_f64(x, device) -> torch.Tensor:
-    """A float64 device copy, converted directly (never through float32)."""
-    if isinstance(x, torch.Tensor):
-        return x.detach().to(device=device, dtype=torch.float64, copy=True).contiguous()
-    return torch.tensor(np.asarray(x), dtype=torch.float64, device=device).contiguous()
+        return x.detach().to(device=device, dtype=dtype, copy=True).contiguous()
+    return torch.tensor(np.asarray(x), dtype=dtype, device=device).contiguous()
 
 
 def _resolve_device(device) -> torch.device:
@@ -205,16 +199,152 @@ class _ChunkedRun:
             self._run_eager(steps - done, done, out)
 
 
+class _Float32:
+    """The float32 number format: every nbd.direct call of a simulator `s` that depends on the format (the object keeps no
+    state of its own). BaseSimulator uses the diagnostics, the Hermite simulators all of it; `_Float64` has the same
+    methods. Packed sources: `s._posm` = {x, y, z, m} (BaseSimulator's) and `s._velp` = {vx, vy, vz, 0}.
+    Scalars: eps^2 and G are the fp32 values formed AT CONSTRUCTION (`s._eps2`, `s._g`: a later change of `softening` or
+    `g_const` does not reach the force); the energies read `s.softening`, and the step `s.dt`, at the launch. _Float64 reads
+    all three at every launch. A quirk, kept as it was found: unifying it would change results."""
+
+    dtype = torch.float32
+    capturable = True               # run() may capture chunks of steps
+    shardable = True                # there is a range-sharded step
+
+    def bind_scalars(self, s):
+        # fp32 scalars exactly as torch forms them from the Python doubles (simulation.py:82,88,164)
+        s._eps2 = direct.f32(s.softening ** 2)
+        s._g = direct.f32(s.g_const)
+
+    def hermite_scratch(self, s):
+        """BaseSimulator's scratch with its plain all-pairs force launch, then what the Hermite step adds."""
+        s._init_scratch()
+        if not s._sharded:
+            s._velp = direct.alloc_posm(s.n, s.device)
+            s._hws = direct.hermite_workspace(max(s.n, 1), s.device)
+        else:
+            # the rank's own predicted rows: source of its local block and send buffer of the gather (max_count rows so
+            # that ragged shards send equal, zero-padded pieces); the gathered rows of all bodies; the partial sums
+            part = s.part
+            s._rows_local = direct.alloc_hermite_rows(part.max_count, s.device)
+            s._rows_all = direct.alloc_hermite_rows(s.n, s.device)
+            s._hws = direct.hermite_shard_workspace(s.n, part.lo, part.n_local, s.device) if part.n_local else None
+            s._hgather = nbd_dist.RowGather(part, direct.HERMITE_ROW, torch.float32, s.device, s.process_group,
+                                            collective=True)
+
+    def pack(self, s):
+        """posm[:n] = {x,y,z,m} of ALL bodies in global order (one all-gather when sharded)."""
+        if not s._sharded:
+            direct.pack_posm(s.positions, s.masses, out=s._posm)
+        else:
+            s._pack_local()
+            s._gather.finish(s._gather.start(s._posm_local, s._posm), s._posm)
+
+    def accel(self, s):
+        if not s._sharded:
+            direct.pack_posm(s.positions, s.masses, out=s._posm)
+            return direct.accel(s._posm, s.n, s._posm, s.n, 0, s._eps2, s._g, workspace=s._ws)
+        s._pack_local()
+        return s._force_sharded()
+
+    def accel_jerk(self, s):
+        direct.hermite_pack(s.positions, s.velocities, s.masses, s._posm, s._velp)
+        return direct.accel_jerk(s._posm, s._velp, s.n, s._eps2, s._g, workspace=s._hws)
+
+    def hermite_step(self, s, acc, jerk, new_acc, new_jerk):
+        direct.hermite_step(s.positions, s.velocities, acc, jerk, new_acc, new_jerk, s.masses, s.dt, s._eps2, s._g,
+                            s._posm, s._hws)
+
+    def energies(self, s, vel, out_uk=None, workspace=None):
+        return direct.energy(s._posm, vel, s.n, direct.f32(s.softening), s._g, out_uk=out_uk, workspace=workspace)
+
+    def potentials(self, s, phi):
+        if getattr(s, "_diag_ws", None) is None:
+            s._diag_ws = direct.potential_workspace(s.n, s.n, s.device)
+        return direct.potential(s._posm, s.n, s._posm, s.n, 0, s._eps2, s._g, out=phi, workspace=s._diag_ws)
+
+    def invariants(self, s, phi, out=None):
+        return direct.invariants(s._posm, s.velocities, phi, s.n, out=out)
+
+    block_workspace = staticmethod(direct.hblock_workspace)
+    block_init_levels = staticmethod(direct.hblock_init_levels)
+
+    def block_step(self, s, *state):
+        direct.hblock_step(*state, s._eps2, s._g, s._sched, s._posm, s._velp, s._bws)
+
+
+class _Float64:
+    """The float64 number format of the Hermite simulators (csrc/direct_hermite_f64.hip, direct_hermite_block_f64.hip):
+    `_Float32`'s methods over the float64 entries; nothing of the fp32 paths is allocated or launched. Packed sources:
+    `s._posd` = {x, y, z, m}, `s._veld` = {vx, vy, vz, 0}; a step leaves `_posd` at the post-step state, and the invariants
+    come from the state arrays. Scalars: softening, g_const and dt are read as the Python doubles AT EVERY LAUNCH
+    (_Float32 forms eps^2 and G once, at construction). A quirk, kept as it was found."""
+
+    dtype = torch.float64
+    capturable = False              # run() is eager: there is no captured form
+    shardable = False               # and no range-sharded one
+
+    def bind_scalars(self, s):           # nothing is formed at construction
+        pass
+
+    def _scalars(self, s):               # (softening^2, G) as the Python doubles, read when a launch is made
+        return float(s.softening) ** 2, float(s.g_const)
+
+    def hermite_scratch(self, s):
+        s._posd, s._veld = direct.alloc_rows_f64(s.n, s.device), direct.alloc_rows_f64(s.n, s.device)
+        s._hws = direct.hermite_f64_workspace(max(s.n, 1), s.device)
+
+    def pack(self, s):
+        direct.hermite_f64_pack(s.positions, s.velocities, s.masses, s._posd, s._veld)
+
+    def accel(self, s):
+        return self.accel_jerk(s)[0]
+
+    def accel_jerk(self, s):
+        self.pack(s)
+        return direct.accel_jerk_f64(s._posd, s._veld, s.n, *self._scalars(s), workspace=s._hws)
+
+    def hermite_step(self, s, acc, jerk, new_acc, new_jerk):
+        direct.hermite_step_f64(s.positions, s.velocities, acc, jerk, new_acc, new_jerk, s.masses, s.dt,
+                                *self._scalars(s), s._posd, s._veld, s._hws)
+
+    def energies(self, s, vel, out_uk=None, workspace=None):
+        return direct.energy_f64(s._posd, vel, s.n, s.softening, s.g_const, s._hws, out_uk=out_uk)
+
+    def potentials(self, s, phi):
+        return direct.potential_f64(s._posd, s.n, *self._scalars(s), s._hws, out=phi)
+
+    def invariants(self, s, phi, out=None):
+        return direct.invariants_state_f64(s.positions, s.velocities, s.masses, phi, out=out)
+
+    block_workspace = staticmethod(direct.hblock_f64_workspace)
+    block_init_levels = staticmethod(direct.hblock_init_levels_f64)
+
+    def block_step(self, s, *state):
+        direct.hblock_step_f64(*state, *self._scalars(s), s._sched, s._posd, s._veld, s._bws)
+
+
+_FORMATS = {fmt.dtype: fmt for fmt in (_Float32(), _Float64())}
+
+
 class BaseSimulator(_ChunkedRun):
     # What an integrator class states next to its step(): `_step_in_place()`, the same step on the static buffers of
     # `_carried` without rebinding anything (capturable); `_carried` itself when the step carries more than the
     # accelerations; and
     _posm_after_step = False        # step() leaves _posm at the post-step positions (else the energies repack first)
     _equal_mass_step = False        # the un-sharded step() has an equal-mass form (`_uniform`)
+    _fmt = _FORMATS[torch.float32]  # the number format; HermiteSimulator chooses its own from `dtype`
 
     def __init__(self, *, positions, velocities, masses, g_const: float = 1.0, softening: float = 0.1,
                  dt: float = 0.01, calc_energy: bool = True, device: str = None, process_group=None,
                  calc_invariants: bool = False):
+        self._init_state(positions, velocities, masses, g_const, softening, dt, calc_energy, device, process_group,
+                         calc_invariants)
+        self._init_scratch()
+
+    def _init_state(self, positions, velocities, masses, g_const, softening, dt, calc_energy, device, process_group,
+                    calc_invariants):
+        """Device, scalars, the state in the format's dtype and the partition: no scratch, no launch."""
         self.device = _resolve_device(device)
         _lib.lib()  # fail now, loudly, if the extension is not built
 
@@ -223,13 +353,10 @@ class BaseSimulator(_ChunkedRun):
         self.softening = softening
         self.calc_energy = calc_energy
         self.calc_invariants = calc_invariants
-        # fp32 scalars exactly as torch forms them from the Python doubles (simulation.py:82,88,164)
-        self._eps2 = direct.f32(softening ** 2)
-        self._g = direct.f32(g_const)
+        self._fmt.bind_scalars(self)
 
-        full_pos = _to_f32(positions, self.device)
-        full_vel = _to_f32(velocities, self.device)
-        self.masses = _to_f32(masses, self.device)
+        full_pos, full_vel, self.masses = (_to_device(x, self.device, self._fmt.dtype)
+                                           for x in (positions, velocities, masses))
         self.n = full_pos.shape[0]
         if full_pos.shape != (self.n, 3) or full_vel.shape != (self.n, 3) or self.masses.shape != (self.n,):
             raise ValueError("positions/velocities must be (n,3) and masses (n,)")
@@ -244,8 +371,10 @@ class BaseSimulator(_ChunkedRun):
         self.positions = full_pos[lo:hi].clone() if self._sharded else full_pos
         self.velocities = full_vel[lo:hi].clone() if self._sharded else full_vel
         self.accelerations = None
+        self._uniform = None
 
-        # scratch owned by the simulator: packed sources (all ranks' bodies), slabs, energy partials
+    def _init_scratch(self):
+        """The fp32 scratch: packed sources (all ranks' bodies), slabs, energy partials; then the first force."""
         self._posm = direct.alloc_posm(self.n, self.device)
         self._posm.zero_()
         # equal masses (the published configurations): the force kernel without its per-pair mass multiply, the common
@@ -267,22 +396,15 @@ class BaseSimulator(_ChunkedRun):
             # (max_count rows so that ragged shards send equal, zero-padded pieces)
             self._posm_local = direct.alloc_posm(self.part.max_count, self.device)
             self._posm_local.zero_()
-            self._mass_local = self.masses[lo:hi].contiguous()
-            self._ws = direct.shard_workspace(self.n, lo, self.part.n_local, self.device) \
+            self._mass_local = self.masses[self.part.lo:self.part.hi].contiguous()
+            self._ws = direct.shard_workspace(self.n, self.part.lo, self.part.n_local, self.device) \
                 if self.part.n_local else None
-            self._gather = nbd_dist.RowGather(self.part, 4, torch.float32, self.device, process_group, collective=True)
+            self._gather = nbd_dist.RowGather(self.part, 4, torch.float32, self.device, self.process_group,
+                                              collective=True)
 
         self.accelerations = self.compute_accelerations()
 
     # ------------------------------------------------------------------ force
-    def _refresh_sources(self):
-        """posm[:n] = {x,y,z,m} of ALL bodies in global order (one all-gather when sharded)."""
-        if not self._sharded:
-            direct.pack_posm(self.positions, self.masses, out=self._posm)
-        else:
-            self._pack_local()
-            self._gather.finish(self._gather.start(self._posm_local, self._posm), self._posm)
-
     def _pack_local(self):
         n_loc = self.part.n_local
         if n_loc:
@@ -315,15 +437,10 @@ class BaseSimulator(_ChunkedRun):
         """a_i = G sum_{j!=i} m_j (r_j - r_i)/(|r_j - r_i|^2 + eps^2)^(3/2) -> new (n_local,3) tensor
         (simulation.py:71-89)."""
         if self.n == 0:
-            return torch.zeros((0, 3), dtype=torch.float32, device=self.device)
+            return torch.zeros((0, 3), dtype=self._fmt.dtype, device=self.device)
         if self._wants_grad():
             return self._accelerations_with_grad()
-        if not self._sharded:
-            direct.pack_posm(self.positions, self.masses, out=self._posm)
-            return direct.accel(self._posm, self.n, self._posm, self.n, 0, self._eps2, self._g,
-                                workspace=self._ws)
-        self._pack_local()
-        return self._force_sharded()
+        return self._fmt.accel(self)
 
     def _wants_grad(self) -> bool:
         return torch.is_grad_enabled() and (self.positions.requires_grad or self.masses.requires_grad)
@@ -341,11 +458,9 @@ class BaseSimulator(_ChunkedRun):
         global sums from the gathered state (velocities are gathered for this call)."""
         if self.n == 0:
             return 0.0, 0.0
-        self._refresh_sources()
+        self._fmt.pack(self)
         vel = self.gather("velocities") if self._sharded else self.velocities
-        uk = direct.energy(self._posm, vel, self.n, direct.f32(self.softening), self._g)
-        u, k = uk.cpu().tolist()
-        return u, k
+        return tuple(self._fmt.energies(self, vel).cpu().tolist())
 
     # ------------------------------------------------------------------ consistent-potential diagnostics
     def _refuse_sharded(self, what: str):
@@ -354,11 +469,8 @@ class BaseSimulator(_ChunkedRun):
                              "supported here")
 
     def _potentials_into(self, phi):
-        """phi (n,) float64 from _posm (already packed), asynchronous."""
-        if getattr(self, "_diag_ws", None) is None:
-            self._diag_ws = direct.potential_workspace(self.n, self.n, self.device)
-        return direct.potential(self._posm, self.n, self._posm, self.n, 0, self._eps2, self._g, out=phi,
-                                workspace=self._diag_ws)
+        """phi (n,) float64 from the packed sources (already packed), asynchronous."""
+        return self._fmt.potentials(self, phi)
 
     def compute_potentials(self) -> torch.Tensor:
         """phi_i = -G sum_{j != i} m_j (|r_ij|^2 + eps^2)^(-1/2) -> new (n,) float64 device tensor: the potential the force
@@ -367,7 +479,7 @@ class BaseSimulator(_ChunkedRun):
         self._refuse_sharded("compute_potentials()")
         if self.n == 0:
             return torch.zeros((0,), dtype=torch.float64, device=self.device)
-        direct.pack_posm(self.positions, self.masses, out=self._posm)
+        self._fmt.pack(self)
         return self._potentials_into(None)
 
     def compute_invariants(self) -> Invariants:
@@ -377,16 +489,16 @@ class BaseSimulator(_ChunkedRun):
         if self.n == 0:
             return Invariants.from_row([0.0] * direct.INVARIANT_ROW)
         phi = self.compute_potentials()
-        return Invariants.from_row(direct.invariants(self._posm, self.velocities, phi, self.n).cpu())
+        return Invariants.from_row(self._fmt.invariants(self, phi).cpu())
 
     def _invariants_into(self, out_row):
         """Invariants row of the state AFTER an un-sharded step, asynchronous (phi into a buffer kept by the simulator)."""
         if getattr(self, "_phi", None) is None:
             self._phi = torch.empty((self.n,), dtype=torch.float64, device=self.device)
         if not self._posm_after_step:
-            direct.pack_posm(self.positions, self.masses, out=self._posm)
+            self._fmt.pack(self)
         self._potentials_into(self._phi)
-        direct.invariants(self._posm, self.velocities, self._phi, self.n, out=out_row)
+        self._fmt.invariants(self, self._phi, out_row)
 
     def gather(self, name: str) -> torch.Tensor:
         """Global (n,3) copy of a sharded state array on every rank ('positions', ...)."""
@@ -416,9 +528,8 @@ class BaseSimulator(_ChunkedRun):
     def _energies_into(self, out_uk, workspace=None):
         """Energies of the state AFTER an un-sharded step (simulation.py:131-133), asynchronous."""
         if not self._posm_after_step:
-            direct.pack_posm(self.positions, self.masses, out=self._posm)
-        direct.energy(self._posm, self.velocities, self.n, direct.f32(self.softening), self._g, out_uk=out_uk,
-                      workspace=workspace)
+            self._fmt.pack(self)
+        self._fmt.energies(self, self.velocities, out_uk, workspace)
 
     def _run_eager(self, steps: int, first_index: int, states):
         n_loc = self.part.n_local
@@ -490,7 +601,7 @@ class BaseSimulator(_ChunkedRun):
         return "_step_in_place" in vars(owner)
 
     def _graph_run_ok(self, steps: int) -> bool:
-        return (not self._sharded and 0 < self.n <= self.GRAPH_RUN_MAX_BODIES and steps >= 8 and
+        return (self._fmt.capturable and not self._sharded and 0 < self.n <= self.GRAPH_RUN_MAX_BODIES and steps >= 8 and
                 self._capturable() and os.environ.get("NBD_RUN_GRAPH", "1") != "0")
 
     def _chunk_scalars(self):
@@ -660,14 +771,14 @@ class HermiteSimulator(BaseSimulator):
     and run() -- its states, energies and invariants -- are float64 end to end: there is no fp32 pair term anywhere.
     run() is eager in this mode, and there is no range-sharded form: float64 with `process_group=` raises ValueError."""
 
-    _f64 = False
+    _f64 = property(lambda self: self._fmt.dtype == torch.float64)       # read-only: tests and tools read it
 
     @staticmethod
     def _check_dtype(dtype, process_group):
-        if dtype not in (torch.float32, torch.float64):
+        if dtype not in _FORMATS:
             raise ValueError(f"HermiteSimulator: dtype must be torch.float32 or torch.float64, got {dtype!r}")
-        if dtype == torch.float64 and process_group is not None:
-            raise ValueError("HermiteSimulator: dtype=torch.float64 has no range-sharded form; process_group is not "
+        if process_group is not None and not _FORMATS[dtype].shardable:
+            raise ValueError(f"HermiteSimulator: dtype={dtype} has no range-sharded form; process_group is not "
                              "supported with it")
 
     def __init__(self, *, positions, velocities, masses, g_const: float = 1.0, softening: float = 0.1,
@@ -679,108 +790,11 @@ class HermiteSimulator(BaseSimulator):
             raise ValueError("HermiteSimulator: process_group must be a torch.distributed process group, got "
                              f"{type(process_group).__name__}")
         self.jerks = None
-        if dtype == torch.float64:
-            self._init_f64(positions, velocities, masses, g_const, softening, dt, calc_energy, device, calc_invariants)
-            return
-        super().__init__(positions=positions, velocities=velocities, masses=masses, g_const=g_const,
-                         softening=softening, dt=dt, calc_energy=calc_energy, device=device,
-                         process_group=process_group, calc_invariants=calc_invariants)
-        if not self._sharded:
-            self._velp = direct.alloc_posm(self.n, self.device)
-            self._hws = direct.hermite_workspace(max(self.n, 1), self.device)
-        else:
-            # the rank's own predicted rows: source of its local block and send buffer of the gather (max_count rows so
-            # that ragged shards send equal, zero-padded pieces); the gathered rows of all bodies; the partial sums
-            part = self.part
-            self._rows_local = direct.alloc_hermite_rows(part.max_count, self.device)
-            self._rows_all = direct.alloc_hermite_rows(self.n, self.device)
-            self._hws = direct.hermite_shard_workspace(self.n, part.lo, part.n_local, self.device) \
-                if part.n_local else None
-            self._hgather = nbd_dist.RowGather(part, direct.HERMITE_ROW, torch.float32, self.device, process_group,
-                                               collective=True)
+        self._fmt = _FORMATS[dtype]          # the only place the format is chosen; no method below asks which it is
+        self._init_state(positions, velocities, masses, g_const, softening, dt, calc_energy, device, process_group,
+                         calc_invariants)
+        self._fmt.hermite_scratch(self)
         self.accelerations, self.jerks = self.compute_accelerations_and_jerks()
-
-    # ------------------------------------------------------------------ float64 mode (csrc/direct_hermite_f64.hip)
-    def _init_f64(self, positions, velocities, masses, g_const, softening, dt, calc_energy, device, calc_invariants):
-        """BaseSimulator's constructor for a float64, un-sharded state: nothing of the fp32 paths is allocated."""
-        self._f64 = True
-        self.device = _resolve_device(device)
-        _lib.lib()
-        self.dt, self.g_const, self.softening = dt, g_const, softening
-        self.calc_energy, self.calc_invariants = calc_energy, calc_invariants
-        self.positions = _to_f64(positions, self.device)
-        self.velocities = _to_f64(velocities, self.device)
-        self.masses = _to_f64(masses, self.device)
-        self.n = self.positions.shape[0]
-        if self.positions.shape != (self.n, 3) or self.velocities.shape != (self.n, 3) or self.masses.shape != (self.n,):
-            raise ValueError("positions/velocities must be (n,3) and masses (n,)")
-        self.process_group, self._sharded, self._uniform = None, False, None
-        self.part = nbd_dist.RangePartition(self.n, 1, 0)
-        self._posd = direct.alloc_rows_f64(self.n, self.device)
-        self._veld = direct.alloc_rows_f64(self.n, self.device)
-        self._hws = direct.hermite_f64_workspace(max(self.n, 1), self.device)
-        self.accelerations, self.jerks = self.compute_accelerations_and_jerks()
-
-    def _f64_scalars(self):
-        """(softening^2, G) as the Python doubles, read when a launch is made."""
-        return float(self.softening) ** 2, float(self.g_const)
-
-    def _pack_f64(self):
-        direct.hermite_f64_pack(self.positions, self.velocities, self.masses, self._posd, self._veld)
-
-    def _graph_run_ok(self, steps: int) -> bool:
-        return not self._f64 and super()._graph_run_ok(steps)        # float64: run() is eager, there is no captured form
-
-    def compute_accelerations(self) -> torch.Tensor:
-        if self._f64:
-            if self.n and self._wants_grad():
-                return self._accelerations_with_grad()
-            return self.compute_accelerations_and_jerks()[0]
-        return super().compute_accelerations()
-
-    def compute_energies(self):
-        if not self._f64:
-            return super().compute_energies()
-        if self.n == 0:
-            return 0.0, 0.0
-        self._pack_f64()
-        u, k = direct.energy_f64(self._posd, self.velocities, self.n, self.softening, self.g_const, self._hws).cpu().tolist()
-        return u, k
-
-    def _energies_into(self, out_uk, workspace=None):
-        if not self._f64:
-            return super()._energies_into(out_uk, workspace)
-        direct.energy_f64(self._posd, self.velocities, self.n, self.softening, self.g_const, self._hws, out_uk=out_uk)
-
-    def _potentials_into(self, phi):
-        if not self._f64:
-            return super()._potentials_into(phi)
-        eps2, g = self._f64_scalars()
-        return direct.potential_f64(self._posd, self.n, eps2, g, self._hws, out=phi)
-
-    def compute_potentials(self) -> torch.Tensor:
-        if not self._f64:
-            return super().compute_potentials()
-        if self.n == 0:
-            return torch.zeros((0,), dtype=torch.float64, device=self.device)
-        self._pack_f64()
-        return self._potentials_into(None)
-
-    def compute_invariants(self) -> Invariants:
-        if not self._f64:
-            return super().compute_invariants()
-        if self.n == 0:
-            return Invariants.from_row([0.0] * direct.INVARIANT_ROW)
-        phi = self.compute_potentials()
-        return Invariants.from_row(direct.invariants_state_f64(self.positions, self.velocities, self.masses, phi).cpu())
-
-    def _invariants_into(self, out_row):
-        if not self._f64:
-            return super()._invariants_into(out_row)
-        if getattr(self, "_phi", None) is None:
-            self._phi = torch.empty((self.n,), dtype=torch.float64, device=self.device)
-        self._potentials_into(self._phi)                             # _posd is the post-step state (_posm_after_step)
-        direct.invariants_state_f64(self.positions, self.velocities, self.masses, self._phi, out=out_row)
 
     def compute_accelerations_and_jerks(self):
         """(a, j) of the current state as new (n,3) tensors -- (n_local,3), the rank's rows, when sharded:
@@ -789,13 +803,9 @@ class HermiteSimulator(BaseSimulator):
         if self.n == 0:
             z = torch.zeros((0, 3), dtype=self.positions.dtype, device=self.device)
             return z, z.clone()
-        if self._f64:
-            self._pack_f64()
-            return direct.accel_jerk_f64(self._posd, self._veld, self.n, *self._f64_scalars(), workspace=self._hws)
         if self._sharded:
             return self._sharded_launches(None, None)
-        direct.hermite_pack(self.positions, self.velocities, self.masses, self._posm, self._velp)
-        return direct.accel_jerk(self._posm, self._velp, self.n, self._eps2, self._g, workspace=self._hws)
+        return self._fmt.accel_jerk(self)
 
     def _sharded_launches(self, acc, jerk):
         """The range-sharded launches from the carried (acc, jerk): predict + pack of the own bodies, the all-gather in
@@ -826,21 +836,14 @@ class HermiteSimulator(BaseSimulator):
             return
         new_acc = torch.empty_like(self.accelerations)
         new_jerk = torch.empty_like(self.jerks)
-        if self._f64:
-            direct.hermite_step_f64(self.positions, self.velocities, self.accelerations, self.jerks, new_acc, new_jerk,
-                                    self.masses, self.dt, *self._f64_scalars(), self._posd, self._veld, self._hws)
-            self.accelerations, self.jerks = new_acc, new_jerk
-            return
-        direct.hermite_step(self.positions, self.velocities, self.accelerations, self.jerks, new_acc, new_jerk,
-                            self.masses, self.dt, self._eps2, self._g, self._posm, self._hws)
+        self._fmt.hermite_step(self, self.accelerations, self.jerks, new_acc, new_jerk)
         self.accelerations, self.jerks = new_acc, new_jerk
 
     _carried = BaseSimulator._carried + (("jerks", "_jerk_g"),)
     _posm_after_step = True
 
     def _step_in_place(self):
-        direct.hermite_step(self.positions, self.velocities, self._acc_g, self._jerk_g, self._acc_g, self._jerk_g,
-                            self.masses, self.dt, self._eps2, self._g, self._posm, self._hws)
+        self._fmt.hermite_step(self, self._acc_g, self._jerk_g, self._acc_g, self._jerk_g)
 
 
 class BlockHermiteSimulator(HermiteSimulator):
@@ -887,8 +890,7 @@ class BlockHermiteSimulator(HermiteSimulator):
         self._ticks = torch.zeros(self.n, dtype=torch.int32, device=self.device)
         self._sched = torch.zeros(direct.HBLOCK_SCHED_INTS, dtype=torch.int32, device=self.device)
         self._sched_host = torch.zeros(4, dtype=torch.int32).pin_memory()
-        workspace = direct.hblock_f64_workspace if self._f64 else direct.hblock_workspace
-        self._bws = workspace(max(self.n, 1), self.device)
+        self._bws = self._fmt.block_workspace(max(self.n, 1), self.device)
         self.block_steps = 0
         self.pair_interactions = 0
         self.clamped = 0
@@ -907,8 +909,8 @@ class BlockHermiteSimulator(HermiteSimulator):
         self._leveled_for = (self.dt, self.eta, self.max_level)
         if self.n == 0:
             return
-        init = direct.hblock_init_levels_f64 if self._f64 else direct.hblock_init_levels
-        init(self.accelerations, self.jerks, self.dt, self.eta, self.max_level, self._ticks, self.levels, self._sched)
+        self._fmt.block_init_levels(self.accelerations, self.jerks, self.dt, self.eta, self.max_level, self._ticks,
+                                    self.levels, self._sched)
         self._read_clamped()
 
     def _read_clamped(self):
@@ -917,12 +919,8 @@ class BlockHermiteSimulator(HermiteSimulator):
 
     def _block_step(self, n_act: int):
         """Predict, force and correct of the block step the schedule has just listed."""
-        state = (self.positions, self.velocities, self.accelerations, self.jerks, self.masses, self._ticks, self.levels,
-                 n_act, self.max_level, self.dt, self.eta)
-        if self._f64:
-            direct.hblock_step_f64(*state, *self._f64_scalars(), self._sched, self._posd, self._veld, self._bws)
-        else:
-            direct.hblock_step(*state, self._eps2, self._g, self._sched, self._posm, self._velp, self._bws)
+        self._fmt.block_step(self, self.positions, self.velocities, self.accelerations, self.jerks, self.masses,
+                             self._ticks, self.levels, n_act, self.max_level, self.dt, self.eta)
 
     def step(self):
         """One output interval: block steps until every body is back at tick 2^max_level (at most 2^max_level of them)."""
@@ -1027,7 +1025,7 @@ class BatchedSimulator(_ChunkedRun):
         self.n_scenes = len(systems)
         pos, vel, mass = [], [], []
         for i, sysm in enumerate(systems):
-            p, v, m = (_to_f32(x, self.device) for x in sysm)
+            p, v, m = (_to_device(x, self.device, torch.float32) for x in sysm)
             n = p.shape[0]
             if p.shape != (n, 3) or v.shape != (n, 3) or m.shape != (n,):
                 raise ValueError(f"scene {i}: positions/velocities must be (n,3) and masses (n,)")

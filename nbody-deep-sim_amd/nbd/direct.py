@@ -27,6 +27,13 @@ def padded_len(n: int) -> int:
     return _lib.lib().nbd_posm_padded_len(int(n))
 
 
+def _chk_packed(dtype, pos_rows, vel_rows, n: int):
+    """The packed (padded_len(n), 4) rows of n bodies in `dtype`; vel_rows None where the entry takes none."""
+    for t, name in zip((pos_rows, vel_rows), ("posm", "velp") if dtype == torch.float32 else ("posd", "veld")):
+        if t is not None:
+            _chk(t, (padded_len(n), 4), name, dtype)
+
+
 def accel_plan(n_src: int, n_tgt: int) -> dict:
     g, s, c = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
     _lib.check(_lib.lib().nbd_accel_plan(n_src, n_tgt, g, s, c), "nbd_accel_plan")
@@ -334,7 +341,7 @@ def hermite_pack(pos, vel, mass, posm, velp, acc=None, jerk=None, dt: float = 0.
     plain pack of (pos, vel) when both are None."""
     n = pos.shape[0]
     _chk(pos, (n, 3), "pos"); _chk(vel, (n, 3), "vel"); _chk(mass, (n,), "mass")
-    _chk(posm, (padded_len(n), 4), "posm"); _chk(velp, (padded_len(n), 4), "velp")
+    _chk_packed(torch.float32, posm, velp, n)
     if (acc is None) != (jerk is None):
         raise _lib.NbdError("hermite_pack: give both acc and jerk, or neither")
     if acc is not None:
@@ -349,7 +356,7 @@ def accel_jerk(posm, velp, n: int, softening_sq: float, g_const: float, acc_out=
                variant: int = 0):
     """(acc, jerk), each (n,3), of all n bodies of posm / velp (as hermite_pack leaves them):
     a_i = G sum_j m_j r_ij s^3, j_i = G sum_j m_j (v_ij s^3 - 3 (r_ij.v_ij) s^5 r_ij), s = (|r_ij|^2 + eps^2)^(-1/2)."""
-    _chk(posm, (padded_len(n), 4), "posm"); _chk(velp, (padded_len(n), 4), "velp")
+    _chk_packed(torch.float32, posm, velp, n)
     dev = posm.device
     if acc_out is None:
         acc_out = torch.empty((n, 3), dtype=torch.float32, device=dev)
@@ -375,7 +382,7 @@ def hermite_step(pos, vel, acc_in, jerk_in, acc_out, jerk_out, mass, dt: float, 
     for t, nm in ((pos, "pos"), (vel, "vel"), (acc_in, "acc_in"), (jerk_in, "jerk_in"), (acc_out, "acc_out"),
                   (jerk_out, "jerk_out")):
         _chk(t, (n, 3), nm)
-    _chk(mass, (n,), "mass"); _chk(posm, (padded_len(n), 4), "posm")
+    _chk(mass, (n,), "mass"); _chk_packed(torch.float32, posm, None, n)
     with _lib.on_device(pos.device):
         _lib.check(_lib.lib().nbd_hermite_step_f32(
             pos.data_ptr(), vel.data_ptr(), acc_in.data_ptr(), jerk_in.data_ptr(), acc_out.data_ptr(),
@@ -482,17 +489,13 @@ def hermite_f64_workspace(n: int, device, slabs: int = 0) -> torch.Tensor:
     return alloc_bytes(max(need, int(slabs) * 6 * int(n) * 8), device)
 
 
-def _chk_rows_f64(posd, veld, n: int):
-    _chk(posd, (padded_len(n), 4), "posd", F64)
-    if veld is not None:
-        _chk(veld, (padded_len(n), 4), "veld", F64)
 
 
 def hermite_f64_pack(pos, vel, mass, posd, veld, acc=None, jerk=None, dt: float = 0.0) -> None:
     """hermite_pack in float64: posd = {x_p, m}, veld = {v_p, 0}, predicted over dt from (acc, jerk) or a plain pack."""
     n = pos.shape[0]
     _chk(pos, (n, 3), "pos", F64); _chk(vel, (n, 3), "vel", F64); _chk(mass, (n,), "mass", F64)
-    _chk_rows_f64(posd, veld, n)
+    _chk_packed(F64, posd, veld, n)
     if (acc is None) != (jerk is None):
         raise _lib.NbdError("hermite_f64_pack: give both acc and jerk, or neither")
     if acc is not None:
@@ -505,7 +508,7 @@ def hermite_f64_pack(pos, vel, mass, posd, veld, acc=None, jerk=None, dt: float 
 
 def accel_jerk_f64(posd, veld, n: int, softening_sq: float, g_const: float, workspace=None, slabs: int = 0):
     """accel_jerk in float64: new (acc, jerk), each (n,3) float64. slabs: 0 = the plan's source split, else that many."""
-    _chk_rows_f64(posd, veld, n)
+    _chk_packed(F64, posd, veld, n)
     dev = posd.device
     acc_out = torch.empty((n, 3), dtype=F64, device=dev)
     jerk_out = torch.empty((n, 3), dtype=F64, device=dev)
@@ -528,7 +531,7 @@ def hermite_step_f64(pos, vel, acc_in, jerk_in, acc_out, jerk_out, mass, dt: flo
                   (jerk_out, "jerk_out")):
         _chk(t, (n, 3), nm, F64)
     _chk(mass, (n,), "mass", F64)
-    _chk_rows_f64(posd, veld, n)
+    _chk_packed(F64, posd, veld, n)
     with _lib.on_device(pos.device):
         _lib.check(_lib.lib().nbd_hermite_step_f64(
             pos.data_ptr(), vel.data_ptr(), acc_in.data_ptr(), jerk_in.data_ptr(), acc_out.data_ptr(),
@@ -539,7 +542,7 @@ def hermite_step_f64(pos, vel, acc_in, jerk_in, acc_out, jerk_out, mass, dt: flo
 
 def energy_f64(posd, vel, n: int, softening: float, g_const: float, workspace, out_uk=None):
     """Device double[2] = {U, K} in the reference's convention from a float64 state; asynchronous."""
-    _chk_rows_f64(posd, None, n); _chk(vel, (n, 3), "vel", F64)
+    _chk_packed(F64, posd, None, n); _chk(vel, (n, 3), "vel", F64)
     if out_uk is None:
         out_uk = torch.empty(2, dtype=F64, device=vel.device)
     _chk(out_uk, (2,), "out_uk", F64)
@@ -552,7 +555,7 @@ def energy_f64(posd, vel, n: int, softening: float, g_const: float, workspace, o
 
 def potential_f64(posd, n: int, softening_sq: float, g_const: float, workspace, out=None) -> torch.Tensor:
     """phi (n,) float64 of the n bodies of posd under each other, pair terms in float64; asynchronous."""
-    _chk_rows_f64(posd, None, n)
+    _chk_packed(F64, posd, None, n)
     if out is None:
         out = torch.empty((n,), dtype=F64, device=posd.device)
     _chk(out, (n,), "phi_out", F64)
@@ -626,7 +629,7 @@ def accel_vjp_f64_workspace(n: int, device, slabs: int = 0) -> torch.Tensor:
 def accel_vjp_f64(posd, cotd, n: int, softening_sq: float, g_const: float, grad_pos=None, grad_mass=None,
                   workspace=None, slabs: int = 0, want_pos: bool = True, want_mass: bool = True):
     """accel_vjp in float64 (posd, cotd as hermite_f64_pack leaves them). slabs: 0 = the plan's source split."""
-    _chk_rows_f64(posd, cotd, n)
+    _chk_packed(F64, posd, cotd, n)
     if not 0 <= int(slabs) <= 64:
         raise _lib.NbdError(f"accel_vjp_f64: slabs must be in [0, 64], got {slabs}")
     dev = posd.device
@@ -645,6 +648,18 @@ def accel_vjp_f64(posd, cotd, n: int, softening_sq: float, g_const: float, grad_
 
 # ---------------------------------------------------- block-timestep Hermite integrator (csrc/direct_hermite_block.hip)
 HBLOCK_SCHED_INTS = 32          # NBD_HBLOCK_SCHED_INTS: {t_next, n_act, clamped, ...} of the block schedule
+
+
+def _chk_hblock(dtype, pos, vel, acc, jerk, mass, ticks, levels, sched, pos_rows, vel_rows) -> int:
+    """The arguments of a block step in `dtype` (state, packed rows, int32 schedule arrays); returns n."""
+    n = pos.shape[0]
+    for t, nm in ((pos, "pos"), (vel, "vel"), (acc, "acc"), (jerk, "jerk")):
+        _chk(t, (n, 3), nm, dtype)
+    _chk(mass, (n,), "mass", dtype)
+    _chk_packed(dtype, pos_rows, vel_rows, n)
+    _chk(ticks, (n,), "ticks", torch.int32); _chk(levels, (n,), "levels", torch.int32)
+    _chk(sched, (HBLOCK_SCHED_INTS,), "sched", torch.int32)
+    return n
 
 
 def hblock_workspace(n: int, device) -> torch.Tensor:
@@ -683,12 +698,7 @@ def hblock_step(pos, vel, acc, jerk, mass, ticks, levels, n_act: int, max_level:
                 softening_sq: float, g_const: float, sched, posm, velp, workspace) -> None:
     """Predict all bodies to t_next, evaluate the n_act listed ones, correct and re-level them (three launches). pos, vel,
     acc, jerk, ticks, levels in place for the active bodies; posm = {x1, m} for them, predicted rows for the rest."""
-    n = pos.shape[0]
-    for t, nm in ((pos, "pos"), (vel, "vel"), (acc, "acc"), (jerk, "jerk")):
-        _chk(t, (n, 3), nm)
-    _chk(mass, (n,), "mass"); _chk(posm, (padded_len(n), 4), "posm"); _chk(velp, (padded_len(n), 4), "velp")
-    _chk(ticks, (n,), "ticks", torch.int32); _chk(levels, (n,), "levels", torch.int32)
-    _chk(sched, (HBLOCK_SCHED_INTS,), "sched", torch.int32)
+    n = _chk_hblock(torch.float32, pos, vel, acc, jerk, mass, ticks, levels, sched, posm, velp)
     with _lib.on_device(pos.device):
         _lib.check(_lib.lib().nbd_hblock_step_f32(
             pos.data_ptr(), vel.data_ptr(), acc.data_ptr(), jerk.data_ptr(), mass.data_ptr(), ticks.data_ptr(),
@@ -700,7 +710,7 @@ def hblock_step(pos, vel, acc, jerk, mass, ticks, levels, n_act: int, max_level:
 def accel_jerk_active(posm, velp, n: int, act, softening_sq: float, g_const: float, workspace=None):
     """(acc, jerk), each (len(act), 3), of the bodies act (a device int32 list, any order) under all n bodies of posm /
     velp, in list order. The all-bodies list gives accel_jerk's bits."""
-    _chk(posm, (padded_len(n), 4), "posm"); _chk(velp, (padded_len(n), 4), "velp")
+    _chk_packed(torch.float32, posm, velp, n)
     _chk(act, None, "act", torch.int32)
     n_act = act.numel()
     dev = posm.device
@@ -724,17 +734,6 @@ def hblock_f64_workspace(n: int, device, slabs: int = 0, n_act: int = 0) -> torc
     return alloc_bytes(max(need, (int(n) + 7) // 8 * 32 + int(slabs) * 6 * int(n_act) * 8), device)
 
 
-def _chk_hblock_f64(pos, vel, acc, jerk, mass, ticks, levels, sched, posd, veld) -> int:
-    n = pos.shape[0]
-    for t, nm in ((pos, "pos"), (vel, "vel"), (acc, "acc"), (jerk, "jerk")):
-        _chk(t, (n, 3), nm, F64)
-    _chk(mass, (n,), "mass", F64)
-    _chk_rows_f64(posd, veld, n)
-    _chk(ticks, (n,), "ticks", torch.int32); _chk(levels, (n,), "levels", torch.int32)
-    _chk(sched, (HBLOCK_SCHED_INTS,), "sched", torch.int32)
-    return n
-
-
 def hblock_init_levels_f64(acc, jerk, dt: float, eta: float, max_level: int, ticks, levels, sched) -> None:
     """hblock_init_levels from float64 acc, jerk."""
     n = acc.shape[0]
@@ -749,7 +748,7 @@ def hblock_init_levels_f64(acc, jerk, dt: float, eta: float, max_level: int, tic
 
 def hblock_predict_f64(pos, vel, acc, jerk, mass, ticks, levels, max_level: int, dt: float, sched, posd, veld) -> None:
     """First launch of a float64 block step: every body predicted to t_next = sched[0] into posd / veld."""
-    n = _chk_hblock_f64(pos, vel, acc, jerk, mass, ticks, levels, sched, posd, veld)
+    n = _chk_hblock(F64, pos, vel, acc, jerk, mass, ticks, levels, sched, posd, veld)
     with _lib.on_device(pos.device):
         _lib.check(_lib.lib().nbd_hblock_predict_f64(
             pos.data_ptr(), vel.data_ptr(), acc.data_ptr(), jerk.data_ptr(), mass.data_ptr(), ticks.data_ptr(), n,
@@ -759,7 +758,7 @@ def hblock_predict_f64(pos, vel, acc, jerk, mass, ticks, levels, max_level: int,
 
 def hblock_force_f64(posd, veld, n: int, n_act: int, softening_sq: float, workspace) -> None:
     """Second launch: the partial sums of the n_act bodies the schedule listed in the workspace."""
-    _chk_rows_f64(posd, veld, n)
+    _chk_packed(F64, posd, veld, n)
     with _lib.on_device(posd.device):
         _lib.check(_lib.lib().nbd_hblock_force_f64(
             posd.data_ptr(), veld.data_ptr(), n, int(n_act), float(softening_sq), workspace.data_ptr(),
@@ -769,7 +768,7 @@ def hblock_force_f64(posd, veld, n: int, n_act: int, softening_sq: float, worksp
 def hblock_correct_f64(pos, vel, acc, jerk, mass, ticks, levels, n_act: int, max_level: int, dt: float, eta: float,
                        g_const: float, sched, posd, workspace) -> None:
     """Third launch: slab sum, corrector and new level of the listed bodies; posd = {x1, m} for them."""
-    n = _chk_hblock_f64(pos, vel, acc, jerk, mass, ticks, levels, sched, posd, None)
+    n = _chk_hblock(F64, pos, vel, acc, jerk, mass, ticks, levels, sched, posd, None)
     with _lib.on_device(pos.device):
         _lib.check(_lib.lib().nbd_hblock_correct_f64(
             pos.data_ptr(), vel.data_ptr(), acc.data_ptr(), jerk.data_ptr(), mass.data_ptr(), ticks.data_ptr(),
@@ -781,7 +780,7 @@ def hblock_correct_f64(pos, vel, acc, jerk, mass, ticks, levels, n_act: int, max
 def hblock_step_f64(pos, vel, acc, jerk, mass, ticks, levels, n_act: int, max_level: int, dt: float, eta: float,
                     softening_sq: float, g_const: float, sched, posd, veld, workspace) -> None:
     """hblock_step in float64 (three launches): dt, eta, softening_sq and g_const go in as the Python doubles."""
-    n = _chk_hblock_f64(pos, vel, acc, jerk, mass, ticks, levels, sched, posd, veld)
+    n = _chk_hblock(F64, pos, vel, acc, jerk, mass, ticks, levels, sched, posd, veld)
     with _lib.on_device(pos.device):
         _lib.check(_lib.lib().nbd_hblock_step_f64(
             pos.data_ptr(), vel.data_ptr(), acc.data_ptr(), jerk.data_ptr(), mass.data_ptr(), ticks.data_ptr(),
@@ -793,7 +792,7 @@ def hblock_step_f64(pos, vel, acc, jerk, mass, ticks, levels, n_act: int, max_le
 def accel_jerk_active_f64(posd, veld, n: int, act, softening_sq: float, g_const: float, workspace=None, slabs: int = 0):
     """accel_jerk_active in float64: (acc, jerk), each (len(act), 3) float64, in list order. slabs: 0 = the plan's source
     split, else that many. The all-bodies list gives accel_jerk_f64's bits at the same slab count."""
-    _chk_rows_f64(posd, veld, n)
+    _chk_packed(F64, posd, veld, n)
     _chk(act, None, "act", torch.int32)
     n_act = act.numel()
     dev = posd.device

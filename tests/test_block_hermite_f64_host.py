@@ -197,5 +197,5 @@ def test_dtype_errors_come_before_any_device_work():
     with pytest.raises(TypeError, match="no_such_keyword"):
         simulation.BlockHermiteSimulator(no_such_keyword=1, **kw)
     sim = object.__new__(simulation.BlockHermiteSimulator)
-    sim._f64, sim._sharded, sim.n = True, False, 100
+    sim._fmt, sim._sharded, sim.n = simulation._FORMATS[torch.float64], False, 100
     assert not sim._graph_run_ok(64)                     # run() stays eager in this mode too

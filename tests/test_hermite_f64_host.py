@@ -171,10 +171,50 @@ def test_dtype_errors_come_before_any_device_work():
     simulation.HermiteSimulator._check_dtype(torch.float64, None)
     sim = object.__new__(simulation.HermiteSimulator)
     assert sim._f64 is False
-    sim._f64, sim._sharded, sim.n = True, False, 100
+    sim._fmt, sim._sharded, sim.n = simulation._FORMATS[torch.float64], False, 100
     assert not sim._graph_run_ok(64)
     # the keyword is HermiteSimulator's alone
     assert inspect.signature(simulation.HermiteSimulator.__init__).parameters["dtype"].default is torch.float32
     for cls in (simulation.BlockHermiteSimulator, simulation.BatchedSimulator, simulation.LeapFrogSimulator,
                 simulation.EulerSimulator):
         assert "dtype" not in inspect.signature(cls.__init__).parameters
+
+
+def test_the_number_format_is_an_object_not_a_branch():
+    """HermiteSimulator and BlockHermiteSimulator choose a format object once, in __init__, and no method body asks which
+    one it is; the two format classes answer the same calls; the constructors take what they took."""
+    from galaxify import simulation
+    herm, block = simulation.HermiteSimulator, simulation.BlockHermiteSimulator
+    assert not hasattr(herm, "_init_f64")
+    assert isinstance(vars(herm)["_f64"], property) and vars(herm)["_f64"].fset is None      # derived, read-only
+    conditionals = (r"\b(if|elif|while|and|or|not)\b[^\n]*\b_f64\b", r"\b_f64\b[^\n]*\belse\b",     # on the flag
+                    r"dtype\s*(==|!=|is\b)", r"(==|!=|\bis|\bis not)\s*torch\.float(32|64)\b",          # on the dtype
+                    r"isinstance\([^)]*_Float", r"_fmt\s*(==|!=|is\b)", r"(==|!=|\bis|\bis not)\s*_Float")  # on the object
+    for cls in (herm, block):
+        text = "\n".join(ln for ln in inspect.getsource(cls).splitlines() if not re.match(r"\s*_f64 = property\(", ln))
+        for pattern in conditionals:
+            assert not re.search(pattern, text), (cls.__name__, pattern, re.search(pattern, text).group(0))
+    assert "_f64 = property(" in inspect.getsource(herm)                 # (the one line left out above)
+    f32, f64 = simulation._FORMATS[torch.float32], simulation._FORMATS[torch.float64]
+    assert (f32.dtype, f64.dtype) == (torch.float32, torch.float64) and f32.capturable and not f64.capturable
+
+    def public(obj):
+        return {name for name in dir(type(obj)) if not name.startswith("_") and callable(getattr(obj, name))}
+    assert public(f64) == public(f32) and len(public(f32)) == 12
+    sim = object.__new__(block)
+    assert sim._fmt is f32 and sim._f64 is False
+    sim._fmt = f64
+    assert sim._f64 is True
+    with pytest.raises(AttributeError):
+        sim._f64 = False
+    base = ["self", "positions", "velocities", "masses", "g_const", "softening", "dt", "calc_energy", "device",
+            "process_group"]
+    defaults = {"g_const": 1.0, "softening": 0.1, "dt": 0.01, "calc_energy": True, "device": None, "process_group": None,
+                "calc_invariants": False, "dtype": torch.float32, "eta": 0.02, "max_level": 10}
+    for cls, names in ((herm, base + ["calc_invariants", "dtype"]),
+                       (block, base + ["eta", "max_level", "calc_invariants", "hermite_kw"])):
+        params = inspect.signature(cls.__init__).parameters
+        assert list(params) == names
+        for name, q in params.items():
+            kind = {"self": q.POSITIONAL_OR_KEYWORD, "hermite_kw": q.VAR_KEYWORD}.get(name, q.KEYWORD_ONLY)
+            assert q.kind is kind and q.default == defaults.get(name, q.empty), name
