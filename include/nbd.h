@@ -395,6 +395,44 @@ int nbd_potential_f64(const double* posd, int n, double softening_sq, double g_c
 int nbd_invariants_state_f64(const double* pos, const double* vel, const double* mass, const double* phi, int n,
                              double* out_row, nbd_stream_t stream);
 
+/* ---- double-precision range-sharded Hermite step (csrc/direct_hermite_shard_f64.hip): "range-sharded Hermite step" in
+ * the number format of "double-precision Hermite". State, masses, a, j, G, softening_sq, dt and the pair arithmetic are
+ * fp64; a rank that owns every body gets nbd_accel_jerk_f64's bits. The exchanged row is 8 doubles (64 bytes),
+ * {x_p, y_p, z_p, m, vx_p, vy_p, vz_p, 0}: ONE all-gather per step, read by the force kernels as it lands.
+ *   send : double[send_rows][8], 32-byte aligned, the rank's own rows, zero behind n_local;
+ *          send_rows >= nbd_posm_padded_len(n_local)
+ *   all  : double[nbd_posm_padded_len(n_total)][8], 32-byte aligned, every rank's rows in global order, zero behind n_total
+ * A step is the four launches of the fp32 entries, argument for argument: predict, (start the gather), force_local,
+ * (wait for it), force_remote = the remote block (rows [lo, lo + n_local) of `all` are never used: whole 64-row chunks
+ * inside the range are not read, the rest of it is dropped by select) + one launch that adds every slab in slab order,
+ * local ones first, times G, and corrects the own rows. Any lo and n_local; n_local == 0 is a no-op returning 0; a rank
+ * that owns everything has no remote launch. Below softening_sq = 1e-24 the i == j term is dropped by index.
+ * slabs, slabs_local, slabs_remote: 0 for the plan's split of the source chunks (the local block: nbd_hermite_f64_plan
+ * at n_local; the remote block: the same target groups, slabs for ~1024 workgroups while every wave keeps a chunk), or
+ * an explicit slab count in [1, 64] as nbd_accel_jerk_f64 takes one (tests: it sets how many chunks a wave walks). Both
+ * force calls of a step must be given the same slabs_local. The workspace holds the partial sums between them:
+ * (slabs_local + slabs_remote) * 6 * n_local doubles, 8-byte aligned, nbd_hermite_shard_f64_workspace_bytes with the same
+ * slab arguments (0 where an argument is out of range); force_local needs its slabs_local * 6 * n_local doubles of it.
+ * It may hold anything on entry. Deterministic; no atomics, no memsets, no host syncs. */
+int nbd_hermite_shard_f64_plan(int n_total, int lo, int n_local, int* slabs_local, int* chunks_per_wave_local,
+                               int* slabs_remote, int* chunks_per_wave_remote);
+size_t nbd_hermite_shard_f64_workspace_bytes(int n_total, int lo, int n_local, int slabs_local, int slabs_remote);
+/* send rows [0, n_local) = the state predicted over dt from (acc, jerk) with the masses (mass: the rank's n_local), rows
+ * [n_local, send_rows) = 0. With acc and jerk both null a plain pack of (pos, vel), as nbd_hermite_f64_pack. */
+int nbd_hermite_shard_predict_f64(const double* pos, const double* vel, const double* acc, const double* jerk,
+                                  const double* mass, int n_local, double dt, double* send, int send_rows,
+                                  nbd_stream_t stream);
+int nbd_hermite_shard_force_local_f64(const double* send, int n_local, double softening_sq, void* workspace,
+                                      size_t workspace_bytes, int n_total, int lo, int slabs, nbd_stream_t stream);
+/* pos non-null: the corrector -- pos, vel (n_local,3) in place from acc_in, jerk_in, dt; acc_out, jerk_out = a1, j1 at
+ * the predicted state (acc_in may alias acc_out, jerk_in may alias jerk_out). pos null: the force on its own, acc_out
+ * and jerk_out only (vel, acc_in, jerk_in and dt are not used). */
+int nbd_hermite_shard_force_remote_f64(const double* all, int n_total, const double* send, int n_local, int lo,
+                                       double softening_sq, double g_const, double* pos, double* vel,
+                                       const double* acc_in, const double* jerk_in, double* acc_out, double* jerk_out,
+                                       double dt, void* workspace, size_t workspace_bytes, int slabs_local,
+                                       int slabs_remote, nbd_stream_t stream);
+
 /* ------------------------------------------------ block-timestep Hermite integrator (csrc/direct_hermite_block.hip)
  * The scheme above with individual power-of-two steps (Makino & Aarseth 1992). One output interval dt is 2^K integer
  * ticks, K = max_level in [0, 20]. Body i keeps x, v, a, j at its last correction tick ticks[i] (int32) and a level

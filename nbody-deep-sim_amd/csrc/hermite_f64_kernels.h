@@ -16,6 +16,7 @@ constexpr int kRowQuads = 2;                     // 16-byte LDS-DMA pieces per 3
 constexpr int kChunkQuads = kChunk * kRowQuads;  // 128 quads = 2 KiB per chunk and array
 constexpr double kEps2MaskedF64 = 1e-24;         // the fp32 kernels' rule (kEps2Masked): below it i == j goes by index
 constexpr int kTargetWGs = 1024;                 // ~4 workgroups per CU (32 KiB of LDS each: at most 5 fit)
+constexpr int kNoBody = 0x7fffffff;              // a source index that is behind every n and is no target's own
 
 inline bool misaligned32(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 31) != 0; }
 inline bool misaligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7) != 0; }
@@ -93,25 +94,42 @@ constexpr int stage_quads() { return 2 * (VEL ? 2 : 1) * kChunkQuads; }
 // group's own indices; -1 for gathered targets, which have none), takes pair<true>, every other chunk pair<false>. Then
 // the 4 waves' kOut partials per lane go through LDS -- a wave's staging is free after its last chunk: its loads have
 // landed and its reads precede these writes -- and are added in wave order into dst[k * stride + t], t < n_valid.
-template <class Pair>
+// Compile-time shape, the defaults = two arrays of 32-byte rows, every chunk where it lies:
+//   RQ    : 16-byte quads from one source row to the next. 2: posd and veld as above. 4: ONE array of 64-byte rows
+//           {x, y, z, m, vx, vy, vz, 0} (veld = posd + 2 quads), what a range-sharded rank sends and gathers
+//           (direct_hermite_shard_f64.hip). Lane l then brings quad l & 1 of the rows l >> 1 and 32 + (l >> 1) of the
+//           chunk, the velocity quads two further on: the chunk lands in the same [pos | vel][128] image either way, and
+//           the pair loops do not know the difference.
+//   RANGE : the walk is over the view *sv (direct_kernels.h): [c_begin, c_end) are LOGICAL chunks that hop over the run of
+//           physical chunks lying wholly inside [ex_lo, ex_hi), and the (at most two) chunks that straddle an end of that
+//           range take pair<true> with the range mask: a source inside the range goes in as a zero row with an index no
+//           body has (a select on the row and on j: whatever such a row holds, NaN included, never reaches a sum). own_chunk
+//           and the index a pair is given are physical.
+template <class Pair, int RQ = kRowQuads, bool RANGE = false>
 __device__ __forceinline__ void walk_f64(Pair& pr, const d4* __restrict__ posd, const d4* __restrict__ veld, int c_begin,
                                          int c_end, bool all_masked, int own_chunk, f4* lds, double* __restrict__ dst,
-                                         size_t stride, int n_valid) {
+                                         size_t stride, int n_valid, const SrcView* sv = nullptr) {
   constexpr bool VEL = Pair::kVel;
   constexpr int kArr = VEL ? 2 : 1;
+  constexpr int kSrcQuads = kChunk * RQ;           // quads from one chunk to the next in memory
+  constexpr int kPiece = kSrcQuads / 2;            // and from the first LDS-DMA piece of a chunk to the second
+  static_assert(RQ == kRowQuads || RQ == 2 * kRowQuads, "rows of posd / veld, or {pos, vel} rows");
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   f4* stage = &lds[wave * stage_quads<VEL>()];
-  const f4* p_lane = reinterpret_cast<const f4*>(posd) + lane;
-  const f4* v_lane = reinterpret_cast<const f4*>(veld) + lane;
+  const int lane_quad = RQ == kRowQuads ? lane : (lane >> 1) * RQ + (lane & 1);
+  const f4* p_lane = reinterpret_cast<const f4*>(posd) + lane_quad;
+  const f4* v_lane = reinterpret_cast<const f4*>(veld) + lane_quad;
+  // logical -> physical chunk: hop over the skipped run
+  auto phys = [&](int c) { return RANGE ? c + (c >= sv->skip_c0 ? sv->skip_cn : 0) : c; };
   auto fetch = [&](int c, int b) {
-    const size_t at = (size_t)c * kChunkQuads;
+    const size_t at = (size_t)phys(c) * kSrcQuads;
     f4* to = stage + b * kArr * kChunkQuads;
     __builtin_amdgcn_global_load_lds(GPTR(p_lane + at), LPTR(to), 16, 0, 0);
-    __builtin_amdgcn_global_load_lds(GPTR(p_lane + at + 64), LPTR(to + 64), 16, 0, 0);
+    __builtin_amdgcn_global_load_lds(GPTR(p_lane + at + kPiece), LPTR(to + 64), 16, 0, 0);
     if (VEL) {
       __builtin_amdgcn_global_load_lds(GPTR(v_lane + at), LPTR(to + kChunkQuads), 16, 0, 0);
-      __builtin_amdgcn_global_load_lds(GPTR(v_lane + at + 64), LPTR(to + kChunkQuads + 64), 16, 0, 0);
+      __builtin_amdgcn_global_load_lds(GPTR(v_lane + at + kPiece), LPTR(to + kChunkQuads + 64), 16, 0, 0);
     }
   };
   if (c_begin < c_end) fetch(c_begin, 0);
@@ -127,8 +145,16 @@ __device__ __forceinline__ void walk_f64(Pair& pr, const d4* __restrict__ posd, 
     }
     const d4* bp = reinterpret_cast<const d4*>(stage + b * kArr * kChunkQuads);
     const d4* bv = VEL ? bp + kChunk : bp;
-    const int j0 = c * kChunk;
-    if (all_masked || c == own_chunk) {
+    const int pc = phys(c);
+    const int j0 = pc * kChunk;
+    if (RANGE && (pc == sv->edge0 || pc == sv->edge1)) {
+      const d4 none = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll 2
+      for (int j = 0; j < kChunk; ++j) {
+        const bool ex = (unsigned)(j0 + j - sv->ex_lo) < (unsigned)(sv->ex_hi - sv->ex_lo);
+        pr.template pair<true>(ex ? none : bp[j], ex ? none : bv[j], ex ? kNoBody : j0 + j);
+      }
+    } else if (all_masked || pc == own_chunk) {
 #pragma unroll 2
       for (int j = 0; j < kChunk; ++j) pr.template pair<true>(bp[j], bv[j], j0 + j);
     } else {
@@ -157,15 +183,20 @@ __device__ __forceinline__ void walk_f64(Pair& pr, const d4* __restrict__ posd, 
 // of a slab still has a chunk to walk. n_tgt targets under n sources; n_tgt = n is the shared step's plan.
 struct F64Plan { int groups, slabs, n_chunks; };
 
+// the slab count of `groups` target groups under n_chunks source chunks (at least 1: a wave may then be left without one)
+inline int slabs_f64(int groups, int n_chunks) {
+  int slabs = ceil_div(kTargetWGs, groups);
+  const int cap = n_chunks / kWaves;
+  slabs = slabs > cap ? cap : slabs;
+  slabs = slabs > kMaxSlabs ? kMaxSlabs : slabs;
+  return slabs < 1 ? 1 : slabs;
+}
+
 inline F64Plan plan_f64(int n, int n_tgt) {
   F64Plan p;
   p.n_chunks = ceil_div(n, kChunk);
   p.groups = ceil_div(n_tgt, kTgtF64);
-  int slabs = ceil_div(kTargetWGs, p.groups);
-  const int cap = p.n_chunks / kWaves;
-  slabs = slabs > cap ? cap : slabs;
-  slabs = slabs > kMaxSlabs ? kMaxSlabs : slabs;
-  p.slabs = slabs < 1 ? 1 : slabs;
+  p.slabs = slabs_f64(p.groups, p.n_chunks);
   return p;
 }
 

@@ -266,6 +266,20 @@ class _Float32:
     def invariants(self, s, phi, out=None):
         return direct.invariants(s._posm, s.velocities, phi, s.n, out=out)
 
+    # the range-sharded step's three calls on the scratch of hermite_scratch (HermiteSimulator._sharded_launches); the
+    # wrappers are looked up on nbd.direct when a call is made
+    def _shard_predict(self, s, acc, jerk):
+        direct.hermite_shard_predict(s.positions, s.velocities, s._mass_local, s._rows_local, acc, jerk, s.dt)
+
+    def _shard_local(self, s):
+        p = s.part
+        direct.hermite_shard_force_local(s._rows_local, p.n_local, s.n, p.lo, s._eps2, s._hws)
+
+    def _shard_remote(self, s, new_acc, new_jerk, **step):
+        p = s.part
+        direct.hermite_shard_force_remote(s._rows_all, s.n, s._rows_local, p.n_local, p.lo, s._eps2, s._g, new_acc,
+                                          new_jerk, s._hws, **step)
+
     block_workspace = staticmethod(direct.hblock_workspace)
     block_init_levels = staticmethod(direct.hblock_init_levels)
 
@@ -274,15 +288,17 @@ class _Float32:
 
 
 class _Float64:
-    """The float64 number format of the Hermite simulators (csrc/direct_hermite_f64.hip, direct_hermite_block_f64.hip):
-    `_Float32`'s methods over the float64 entries; nothing of the fp32 paths is allocated or launched. Packed sources:
-    `s._posd` = {x, y, z, m}, `s._veld` = {vx, vy, vz, 0}; a step leaves `_posd` at the post-step state, and the invariants
-    come from the state arrays. Scalars: softening, g_const and dt are read as the Python doubles AT EVERY LAUNCH
-    (_Float32 forms eps^2 and G once, at construction). A quirk, kept as it was found."""
+    """The float64 number format of the Hermite simulators (csrc/direct_hermite_f64.hip, direct_hermite_block_f64.hip,
+    direct_hermite_shard_f64.hip): `_Float32`'s methods over the float64 entries; nothing of the fp32 paths is allocated
+    or launched. Packed sources: `s._posd` = {x, y, z, m}, `s._veld` = {vx, vy, vz, 0}; a step leaves `_posd` at the
+    post-step state, and the invariants come from the state arrays. Sharded, the step works on 8-double rows
+    (`_rows_local`, `_rows_all`) and only the energies pack `posd` rows, of the gathered state, per call. Scalars:
+    softening, g_const and dt are read as the Python doubles AT EVERY LAUNCH, sharded or not (_Float32 forms eps^2 and G
+    once, at construction). A quirk, kept as it was found."""
 
     dtype = torch.float64
     capturable = False              # run() is eager: there is no captured form
-    shardable = False               # and no range-sharded one
+    shardable = True                # there is a range-sharded step
 
     def bind_scalars(self, s):           # nothing is formed at construction
         pass
@@ -291,14 +307,26 @@ class _Float64:
         return float(s.softening) ** 2, float(s.g_const)
 
     def hermite_scratch(self, s):
-        s._posd, s._veld = direct.alloc_rows_f64(s.n, s.device), direct.alloc_rows_f64(s.n, s.device)
-        s._hws = direct.hermite_f64_workspace(max(s.n, 1), s.device)
+        if not s._sharded:
+            s._posd, s._veld = direct.alloc_rows_f64(s.n, s.device), direct.alloc_rows_f64(s.n, s.device)
+            s._hws = direct.hermite_f64_workspace(max(s.n, 1), s.device)
+        else:
+            # as _Float32's: the rank's own predicted rows (max_count of them: equal, zero-padded pieces), the gathered
+            # rows of all bodies, the partial sums of the two force launches, the gather, the rank's masses
+            part = s.part
+            s._rows_local = direct.alloc_hermite_rows_f64(part.max_count, s.device)
+            s._rows_all = direct.alloc_hermite_rows_f64(s.n, s.device)
+            s._hws = direct.hermite_shard_f64_workspace(s.n, part.lo, part.n_local, s.device) if part.n_local else None
+            s._hgather = nbd_dist.RowGather(part, direct.HERMITE_ROW, torch.float64, s.device, s.process_group,
+                                            collective=True)
+            s._mass_local = s.masses[part.lo:part.hi].contiguous()
 
     def pack(self, s):
-        direct.hermite_f64_pack(s.positions, s.velocities, s.masses, s._posd, s._veld)
+        if not s._sharded:          # (sharded, only the energies read packed rows of all bodies: they pack them)
+            direct.hermite_f64_pack(s.positions, s.velocities, s.masses, s._posd, s._veld)
 
     def accel(self, s):
-        return self.accel_jerk(s)[0]
+        return s.compute_accelerations_and_jerks()[0]
 
     def accel_jerk(self, s):
         self.pack(s)
@@ -309,13 +337,32 @@ class _Float64:
                                 *self._scalars(s), s._posd, s._veld, s._hws)
 
     def energies(self, s, vel, out_uk=None, workspace=None):
-        return direct.energy_f64(s._posd, vel, s.n, s.softening, s.g_const, s._hws, out_uk=out_uk)
+        if not s._sharded:
+            return direct.energy_f64(s._posd, vel, s.n, s.softening, s.g_const, s._hws, out_uk=out_uk)
+        # occasional use: `vel` is the gathered velocities; a blocking gather of the positions, one pack of the gathered
+        # state with the replicated masses, the un-sharded entry. Scratch per call. Every rank gets the global sums.
+        posd, veld = direct.alloc_rows_f64(s.n, s.device), direct.alloc_rows_f64(s.n, s.device)
+        direct.hermite_f64_pack(s.gather("positions"), vel, s.masses, posd, veld)
+        return direct.energy_f64(posd, vel, s.n, s.softening, s.g_const, direct.hermite_f64_workspace(s.n, s.device),
+                                 out_uk=out_uk)
 
     def potentials(self, s, phi):
         return direct.potential_f64(s._posd, s.n, *self._scalars(s), s._hws, out=phi)
 
     def invariants(self, s, phi, out=None):
         return direct.invariants_state_f64(s.positions, s.velocities, s.masses, phi, out=out)
+
+    def _shard_predict(self, s, acc, jerk):
+        direct.hermite_shard_predict_f64(s.positions, s.velocities, s._mass_local, s._rows_local, acc, jerk, s.dt)
+
+    def _shard_local(self, s):
+        p = s.part
+        direct.hermite_shard_force_local_f64(s._rows_local, p.n_local, s.n, p.lo, self._scalars(s)[0], s._hws)
+
+    def _shard_remote(self, s, new_acc, new_jerk, **step):
+        p = s.part
+        direct.hermite_shard_force_remote_f64(s._rows_all, s.n, s._rows_local, p.n_local, p.lo, *self._scalars(s),
+                                              new_acc, new_jerk, s._hws, **step)
 
     block_workspace = staticmethod(direct.hblock_f64_workspace)
     block_init_levels = staticmethod(direct.hblock_init_levels_f64)
@@ -505,7 +552,7 @@ class BaseSimulator(_ChunkedRun):
         local = getattr(self, name)
         if not self._sharded:
             return local
-        out = torch.empty((self.n, 3), dtype=torch.float32, device=self.device)
+        out = torch.empty((self.n, 3), dtype=local.dtype, device=self.device)
         return nbd_dist.allgather_rows(local, self.part, out, group=self.process_group)
 
     # ------------------------------------------------------------------ run loop
@@ -769,7 +816,9 @@ class HermiteSimulator(BaseSimulator):
     accelerations and jerks are float64 device tensors (the inputs are converted directly, not through float32), g_const,
     softening ** 2, dt and the step constants go to the kernels as the Python doubles, and step(), the compute_*() methods
     and run() -- its states, energies and invariants -- are float64 end to end: there is no fp32 pair term anywhere.
-    run() is eager in this mode, and there is no range-sharded form: float64 with `process_group=` raises ValueError."""
+    run() is eager in this mode. With `process_group=` as well (csrc/direct_hermite_shard_f64.hip) the
+    sharded step above runs in float64: the exchanged rows are 8 doubles, still ONE all-gather per step, and
+    compute_energies() gathers the float64 state on every rank."""
 
     _f64 = property(lambda self: self._fmt.dtype == torch.float64)       # read-only: tests and tools read it
 
@@ -788,7 +837,7 @@ class HermiteSimulator(BaseSimulator):
         if process_group is not None and not (torch.distributed.is_available() and
                                               isinstance(process_group, torch.distributed.ProcessGroup)):
             raise ValueError("HermiteSimulator: process_group must be a torch.distributed process group, got "
-                             f"{type(process_group).__name__}")
+                             f"{type(process_group).__name__} (dtype={dtype})")
         self.jerks = None
         self._fmt = _FORMATS[dtype]          # the only place the format is chosen; no method below asks which it is
         self._init_state(positions, velocities, masses, g_const, softening, dt, calc_energy, device, process_group,
@@ -811,20 +860,18 @@ class HermiteSimulator(BaseSimulator):
         """The range-sharded launches from the carried (acc, jerk): predict + pack of the own bodies, the all-gather in
         flight during the own x own block, then the own x others block, the slab sum and the corrector; returns the new
         (acc, jerk). With acc and jerk None the force of the current state on its own (a plain pack, no corrector)."""
-        p = self.part
-        n_loc, rows = p.n_local, self._rows_local
-        new_acc = torch.empty((n_loc, 3), dtype=torch.float32, device=self.device)
-        new_jerk = torch.empty((n_loc, 3), dtype=torch.float32, device=self.device)
-        direct.hermite_shard_predict(self.positions, self.velocities, self._mass_local, rows, acc, jerk, self.dt)
-        handle = self._hgather.start(rows, self._rows_all)
+        fmt, n_loc = self._fmt, self.part.n_local
+        new_acc = torch.empty((n_loc, 3), dtype=fmt.dtype, device=self.device)
+        new_jerk = torch.empty((n_loc, 3), dtype=fmt.dtype, device=self.device)
+        fmt._shard_predict(self, acc, jerk)
+        handle = self._hgather.start(self._rows_local, self._rows_all)
         if n_loc:
-            direct.hermite_shard_force_local(rows, n_loc, self.n, p.lo, self._eps2, self._hws)
+            fmt._shard_local(self)
         self._hgather.finish(handle, self._rows_all)
         if n_loc:
             step = {} if acc is None else dict(pos=self.positions, vel=self.velocities, acc_in=acc, jerk_in=jerk,
                                                dt=self.dt)
-            direct.hermite_shard_force_remote(self._rows_all, self.n, rows, n_loc, p.lo, self._eps2, self._g, new_acc,
-                                              new_jerk, self._hws, **step)
+            fmt._shard_remote(self, new_acc, new_jerk, **step)
         return new_acc, new_jerk
 
     def step(self):

@@ -234,6 +234,17 @@ SIGNATURES = {
     "nbd_energy_f64": (c_int, [c_void_p, c_void_p, c_int, c_double, c_double, c_void_p, c_void_p, c_size_t, c_void_p]),
     "nbd_potential_f64": (c_int, [c_void_p, c_int, c_double, c_double, c_void_p, c_void_p, c_size_t, c_void_p]),
     "nbd_invariants_state_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
+    # --- double-precision range-sharded Hermite step (csrc/direct_hermite_shard_f64.hip)
+    "nbd_hermite_shard_f64_plan": (c_int, [c_int, c_int, c_int, POINTER(c_int), POINTER(c_int), POINTER(c_int),
+                                           POINTER(c_int)]),
+    "nbd_hermite_shard_f64_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
+    "nbd_hermite_shard_predict_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_double,
+                                              c_void_p, c_int, c_void_p]),
+    "nbd_hermite_shard_force_local_f64": (c_int, [c_void_p, c_int, c_double, c_void_p, c_size_t, c_int, c_int, c_int,
+                                                  c_void_p]),
+    "nbd_hermite_shard_force_remote_f64": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_double, c_double, c_void_p,
+                                                   c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_void_p,
+                                                   c_size_t, c_int, c_int, c_void_p]),
     # --- block-timestep Hermite integrator (csrc/direct_hermite_block.hip)
     "nbd_hblock_workspace_bytes": (c_size_t, [c_int]),
     "nbd_hblock_init_levels": (c_int, [c_void_p, c_void_p, c_int, c_double, c_double, c_int, c_void_p, c_void_p,

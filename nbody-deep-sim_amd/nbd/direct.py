@@ -410,9 +410,9 @@ def hermite_shard_workspace(n_total: int, lo: int, n_local: int, device) -> torc
     return alloc_bytes(_lib.lib().nbd_hermite_shard_workspace_bytes(n_total, lo, n_local), device)
 
 
-def _chk_rows(t: torch.Tensor, n: int, name: str):
-    """An array of 8-float rows that holds at least padded_len(n) of them."""
-    _chk(t, None, name)
+def _chk_rows(t: torch.Tensor, n: int, name: str, dtype=torch.float32):
+    """An array of 8-element rows of `dtype` that holds at least padded_len(n) of them."""
+    _chk(t, None, name, dtype)
     if t.dim() != 2 or t.shape[1] != HERMITE_ROW or t.shape[0] < padded_len(n):
         raise _lib.NbdError(f"{name}: need >= {padded_len(n)} rows of {HERMITE_ROW}, got {tuple(t.shape)}")
 
@@ -580,6 +580,76 @@ def invariants_state_f64(pos, vel, mass, phi, out=None) -> torch.Tensor:
                    "nbd_invariants_state_f64")
     return out
 
+
+
+# ----------------------- double-precision range-sharded Hermite step (csrc/direct_hermite_shard_f64.hip)
+def alloc_hermite_rows_f64(n: int, device) -> torch.Tensor:
+    """alloc_hermite_rows in float64: zeroed (padded_len(n), 8) rows of 64 bytes, {x_p, y_p, z_p, m, vx_p, vy_p, vz_p, 0}."""
+    return torch.zeros((padded_len(n), HERMITE_ROW), dtype=F64, device=device)
+
+
+def hermite_shard_f64_plan(n_total: int, lo: int, n_local: int) -> dict:
+    a, b, c, d = ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    _lib.check(_lib.lib().nbd_hermite_shard_f64_plan(n_total, lo, n_local, a, b, c, d), "nbd_hermite_shard_f64_plan")
+    return {"slabs_local": a.value, "chunks_per_wave_local": b.value, "slabs_remote": c.value,
+            "chunks_per_wave_remote": d.value}
+
+
+def hermite_shard_f64_workspace(n_total: int, lo: int, n_local: int, device, slabs_local: int = 0,
+                                slabs_remote: int = 0) -> torch.Tensor:
+    """The partial sums of a rank's two force launches; slab counts: 0 = the plan's, else that many."""
+    return alloc_bytes(_lib.lib().nbd_hermite_shard_f64_workspace_bytes(n_total, lo, n_local, int(slabs_local),
+                                                                        int(slabs_remote)), device)
+
+
+def hermite_shard_predict_f64(pos, vel, mass, send, acc=None, jerk=None, dt: float = 0.0) -> None:
+    """hermite_shard_predict in float64: send[:n_local] = {x_p, m, v_p, 0} of the rank's bodies predicted over dt from
+    (acc, jerk) -- a plain pack of (pos, vel) when both are None -- and zeros in every row behind n_local."""
+    n = pos.shape[0]
+    _chk(pos, (n, 3), "pos", F64); _chk(vel, (n, 3), "vel", F64); _chk(mass, (n,), "mass", F64)
+    _chk_rows(send, n, "send", F64)
+    if (acc is None) != (jerk is None):
+        raise _lib.NbdError("hermite_shard_predict_f64: give both acc and jerk, or neither")
+    if acc is not None:
+        _chk(acc, (n, 3), "acc", F64); _chk(jerk, (n, 3), "jerk", F64)
+    with _lib.on_device(send.device):
+        _lib.check(_lib.lib().nbd_hermite_shard_predict_f64(
+            pos.data_ptr(), vel.data_ptr(), _lib.ptr(acc), _lib.ptr(jerk), mass.data_ptr(), n, float(dt),
+            send.data_ptr(), send.shape[0], _lib.current_stream(send.device)), "nbd_hermite_shard_predict_f64")
+
+
+def hermite_shard_force_local_f64(send: torch.Tensor, n_local: int, n_total: int, lo: int, softening_sq: float,
+                                  workspace: torch.Tensor, slabs: int = 0) -> None:
+    """hermite_shard_force_local in float64. slabs: 0 = the plan's split of the own chunks, else that many slabs."""
+    _chk_rows(send, n_local, "send", F64)
+    with _lib.on_device(send.device):
+        _lib.check(_lib.lib().nbd_hermite_shard_force_local_f64(
+            send.data_ptr(), n_local, float(softening_sq), workspace.data_ptr(), _nbytes(workspace), n_total, lo,
+            int(slabs), _lib.current_stream(send.device)), "nbd_hermite_shard_force_local_f64")
+
+
+def hermite_shard_force_remote_f64(rows_all: torch.Tensor, n_total: int, send: torch.Tensor, n_local: int, lo: int,
+                                   softening_sq: float, g_const: float, acc_out: torch.Tensor, jerk_out: torch.Tensor,
+                                   workspace: torch.Tensor, pos=None, vel=None, acc_in=None, jerk_in=None,
+                                   dt: float = 0.0, slabs_local: int = 0, slabs_remote: int = 0) -> None:
+    """hermite_shard_force_remote in float64: every other body of the gathered rows as a source, then a1, j1 =
+    G * sum(slabs) into acc_out, jerk_out, and with pos, vel, acc_in, jerk_in and dt the corrector of the own rows.
+    slabs_local: what the local call was given; slabs_remote: 0 = the plan's split of the remote chunks."""
+    _chk_rows(rows_all, n_total, "rows_all", F64)
+    _chk_rows(send, n_local, "send", F64)
+    _chk(acc_out, (n_local, 3), "acc_out", F64); _chk(jerk_out, (n_local, 3), "jerk_out", F64)
+    step = (pos, vel, acc_in, jerk_in)
+    if any(t is None for t in step) != all(t is None for t in step):
+        raise _lib.NbdError("hermite_shard_force_remote_f64: give pos, vel, acc_in and jerk_in, or none of them")
+    if pos is not None:
+        for t, nm in zip(step, ("pos", "vel", "acc_in", "jerk_in")):
+            _chk(t, (n_local, 3), nm, F64)
+    with _lib.on_device(rows_all.device):
+        _lib.check(_lib.lib().nbd_hermite_shard_force_remote_f64(
+            rows_all.data_ptr(), n_total, send.data_ptr(), n_local, lo, float(softening_sq), float(g_const),
+            _lib.ptr(pos), _lib.ptr(vel), _lib.ptr(acc_in), _lib.ptr(jerk_in), acc_out.data_ptr(), jerk_out.data_ptr(),
+            float(dt), workspace.data_ptr(), _nbytes(workspace), int(slabs_local), int(slabs_remote),
+            _lib.current_stream(rows_all.device)), "nbd_hermite_shard_force_remote_f64")
 
 
 # ------------------------------------------------ backward of the all-pairs acceleration (csrc/direct_grad.hip)

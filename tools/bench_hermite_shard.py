@@ -6,7 +6,9 @@ Plummer sphere and runs, per step, exactly the launches the sharded HermiteSimul
     a, j (own x own)          | a, j (own x others) + slab sum + corrector
 
 -- with HIP-event times per phase: medians over windows, after a time-based warm-up. Writes
-profiles/r11_hermite_shard.json:   python tools/bench_hermite_shard.py [--n 65536 --world 8 --rank 3] [--big]"""
+profiles/r11_hermite_shard.json:   python tools/bench_hermite_shard.py [--n 65536 --world 8 --rank 3] [--big]
+--dtype float64 runs the same launches of the float64 step (csrc/direct_hermite_shard_f64.hip) against the un-sharded
+float64 kernels and writes profiles/r16_hermite_shard_f64.json:   python tools/bench_hermite_shard.py --dtype float64 --big"""
 import argparse
 import json
 import os
@@ -21,7 +23,44 @@ import torch
 from nbd import direct
 from nbd.plummer import generate_plummer
 
-EPS2, G, DT = direct.f32(0.01), 1.0, 1e-3
+G, DT = 1.0, 1e-3
+
+
+class Fmt32:
+    """The float32 entries the two measurements call; Fmt64 names the float64 ones."""
+    dtype, eps2, out = torch.float32, direct.f32(0.01), "r11_hermite_shard.json"
+    alloc_packed, workspace, pack = direct.alloc_posm, direct.hermite_workspace, direct.hermite_pack
+    rows, plan, shard_workspace = direct.alloc_hermite_rows, direct.hermite_shard_plan, direct.hermite_shard_workspace
+    predict, local, remote = (direct.hermite_shard_predict, direct.hermite_shard_force_local,
+                              direct.hermite_shard_force_remote)
+
+    @staticmethod
+    def force(posm, velp, n, acc, jerk, hws):
+        direct.accel_jerk(posm, velp, n, Fmt32.eps2, G, acc_out=acc, jerk_out=jerk, workspace=hws)
+
+    @staticmethod
+    def step(pos, vel, acc, jerk, mass, posm, velp, hws):
+        direct.hermite_step(pos, vel, acc, jerk, acc, jerk, mass, DT, Fmt32.eps2, G, posm, hws)
+
+
+class Fmt64:
+    dtype, eps2, out = torch.float64, 0.01, "r16_hermite_shard_f64.json"
+    alloc_packed, workspace, pack = direct.alloc_rows_f64, direct.hermite_f64_workspace, direct.hermite_f64_pack
+    rows, plan, shard_workspace = (direct.alloc_hermite_rows_f64, direct.hermite_shard_f64_plan,
+                                   direct.hermite_shard_f64_workspace)
+    predict, local, remote = (direct.hermite_shard_predict_f64, direct.hermite_shard_force_local_f64,
+                              direct.hermite_shard_force_remote_f64)
+
+    @staticmethod
+    def force(posd, veld, n, acc, jerk, hws):               # (allocates its outputs: two cached (n,3) blocks per call)
+        direct.accel_jerk_f64(posd, veld, n, Fmt64.eps2, G, workspace=hws)
+
+    @staticmethod
+    def step(pos, vel, acc, jerk, mass, posd, veld, hws):
+        direct.hermite_step_f64(pos, vel, acc, jerk, acc, jerk, mass, DT, Fmt64.eps2, G, posd, veld, hws)
+
+
+FORMATS = {"float32": Fmt32, "float64": Fmt64}
 
 
 def warm(fn, seconds=0.5):
@@ -46,16 +85,19 @@ def window_ms(fn, reps, windows):
     return statistics.median(out)
 
 
-def unsharded(n, dev, windows):
-    """nbd_accel_jerk_f32 and nbd_hermite_step_f32 at n bodies: (force ms, step ms)."""
+def unsharded(fmt, n, dev, windows):
+    """The un-sharded force (nbd_accel_jerk_f32 / _f64) and step (nbd_hermite_step_f32 / _f64) at n bodies:
+    (force ms, step ms)."""
     p, v, m = generate_plummer(n, seed=1234)
-    pos, vel, mass = (torch.tensor(a, dtype=torch.float32, device=dev) for a in (p, v, m))
-    posm, velp = direct.alloc_posm(n, dev), direct.alloc_posm(n, dev)
-    hws = direct.hermite_workspace(n, dev)
-    direct.hermite_pack(pos, vel, mass, posm, velp)
-    acc, jerk = direct.accel_jerk(posm, velp, n, EPS2, G, workspace=hws)
-    force = lambda: direct.accel_jerk(posm, velp, n, EPS2, G, acc_out=acc, jerk_out=jerk, workspace=hws)
-    step = lambda: direct.hermite_step(pos, vel, acc, jerk, acc, jerk, mass, DT, EPS2, G, posm, hws)
+    pos, vel, mass = (torch.tensor(a, dtype=fmt.dtype, device=dev) for a in (p, v, m))
+    posm, velp = fmt.alloc_packed(n, dev), fmt.alloc_packed(n, dev)
+    hws = fmt.workspace(n, dev)
+    fmt.pack(pos, vel, mass, posm, velp)
+    acc = torch.zeros((n, 3), dtype=fmt.dtype, device=dev)
+    jerk = torch.zeros((n, 3), dtype=fmt.dtype, device=dev)
+    force = lambda: fmt.force(posm, velp, n, acc, jerk, hws)
+    step = lambda: fmt.step(pos, vel, acc, jerk, mass, posm, velp, hws)
+    force()
     warm(force)
     reps = max(2, min(20, int(40e-3 / (2.0e-3 * (n / 65536) ** 2))))
     f_ms = window_ms(force, reps, windows)
@@ -63,34 +105,35 @@ def unsharded(n, dev, windows):
     return f_ms, window_ms(step, reps, windows)
 
 
-def rank_of(n, world, rank, dev, windows):
+def rank_of(fmt, n, world, rank, dev, windows):
     """The emulated rank's phases at n bodies over `world` ranks, in ms."""
     n_loc = n // world
     lo = rank * n_loc
+    eps2 = fmt.eps2
     p, v, m = generate_plummer(n, seed=1234)
-    pos_all, vel_all, mass_all = (torch.tensor(a, dtype=torch.float32, device=dev) for a in (p, v, m))
-    rows_all = direct.alloc_hermite_rows(n, dev)
-    direct.hermite_shard_predict(pos_all, vel_all, mass_all, rows_all)        # every body's rows, as gathered
+    pos_all, vel_all, mass_all = (torch.tensor(a, dtype=fmt.dtype, device=dev) for a in (p, v, m))
+    rows_all = fmt.rows(n, dev)
+    fmt.predict(pos_all, vel_all, mass_all, rows_all)               # every body's rows, as gathered
     pos, vel = pos_all[lo:lo + n_loc].clone(), vel_all[lo:lo + n_loc].clone()
     mass = mass_all[lo:lo + n_loc].contiguous()
-    send = direct.alloc_hermite_rows(n_loc, dev)
-    ws = direct.hermite_shard_workspace(n, lo, n_loc, dev)
-    acc = torch.zeros((n_loc, 3), device=dev)
-    jerk = torch.zeros((n_loc, 3), device=dev)
-    direct.hermite_shard_predict(pos, vel, mass, send)
-    direct.hermite_shard_force_local(send, n_loc, n, lo, EPS2, ws)
-    direct.hermite_shard_force_remote(rows_all, n, send, n_loc, lo, EPS2, G, acc, jerk, ws)
+    send = fmt.rows(n_loc, dev)
+    ws = fmt.shard_workspace(n, lo, n_loc, dev)
+    acc = torch.zeros((n_loc, 3), dtype=fmt.dtype, device=dev)
+    jerk = torch.zeros((n_loc, 3), dtype=fmt.dtype, device=dev)
+    fmt.predict(pos, vel, mass, send)
+    fmt.local(send, n_loc, n, lo, eps2, ws)
+    fmt.remote(rows_all, n, send, n_loc, lo, eps2, G, acc, jerk, ws)
 
     def step(ev=None):
         if ev: ev[0].record()
-        direct.hermite_shard_predict(pos, vel, mass, send, acc, jerk, DT)
+        fmt.predict(pos, vel, mass, send, acc, jerk, DT)
         if ev: ev[1].record()
         rows_all[lo:lo + n_loc].copy_(send[:n_loc])                # stands in for the all-gather's arrival
         if ev: ev[2].record()
-        direct.hermite_shard_force_local(send, n_loc, n, lo, EPS2, ws)
+        fmt.local(send, n_loc, n, lo, eps2, ws)
         if ev: ev[3].record()
-        direct.hermite_shard_force_remote(rows_all, n, send, n_loc, lo, EPS2, G, acc, jerk, ws, pos=pos, vel=vel,
-                                          acc_in=acc, jerk_in=jerk, dt=DT)
+        fmt.remote(rows_all, n, send, n_loc, lo, eps2, G, acc, jerk, ws, pos=pos, vel=vel, acc_in=acc, jerk_in=jerk,
+                   dt=DT)
         if ev: ev[4].record()
 
     warm(step)
@@ -105,7 +148,7 @@ def rank_of(n, world, rank, dev, windows):
         for i, k in enumerate(names):
             samples[k].append(ev[i].elapsed_time(ev[i + 1]))
     phase = {k: statistics.median(s) for k, s in samples.items()}
-    return {"n": n, "world": world, "rank": rank, "n_local": n_loc, "plan": direct.hermite_shard_plan(n, lo, n_loc),
+    return {"n": n, "world": world, "rank": rank, "n_local": n_loc, "plan": fmt.plan(n, lo, n_loc),
             "rank_step_ms": step_ms, "phase_ms": phase}
 
 
@@ -116,14 +159,19 @@ def main():
     ap.add_argument("--rank", type=int, default=3)
     ap.add_argument("--windows", type=int, default=9)
     ap.add_argument("--big", action="store_true", help="also BASELINE configs[4]'s rank shape: 65 536 of 524 288")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r11_hermite_shard.json"))
+    ap.add_argument("--dtype", choices=sorted(FORMATS), default="float32")
+    ap.add_argument("--out", default=None, help="default: profiles/r11_hermite_shard.json, or "
+                                                "profiles/r16_hermite_shard_f64.json with --dtype float64")
     args = ap.parse_args()
+    fmt = FORMATS[args.dtype]
+    out_path = args.out or os.path.join(ROOT, "profiles", fmt.out)
     dev = "cuda"
     results = []
     for n in [args.n] + ([args.n * args.world] if args.big else []):
         windows = args.windows if n == args.n else 3
-        f_ms, s_ms = unsharded(n, dev, windows)
-        r = rank_of(n, args.world, args.rank, dev, windows)
+        f_ms, s_ms = unsharded(fmt, n, dev, windows)
+        r = rank_of(fmt, n, args.world, args.rank, dev, windows)
+        r["dtype"] = args.dtype
         ph = r["phase_ms"]
         r["unsharded_force_ms"], r["unsharded_step_ms"] = f_ms, s_ms
         r["force_ratio"] = (ph["force_local"] + ph["force_remote_finish_correct"]) / (f_ms / args.world)
@@ -133,7 +181,7 @@ def main():
     out = {"tool": "tools/bench_hermite_shard.py", "device": torch.cuda.get_device_name(0),
            "what": "one emulated rank of the range-sharded Hermite step; force_ratio = (local + remote) / (unsharded "
                    "force / world), step_ratio = rank step / (unsharded step / world), same process", "results": results}
-    with open(args.out, "w") as f:
+    with open(out_path, "w") as f:
         json.dump(out, f, indent=1)
         f.write("\n")
 
