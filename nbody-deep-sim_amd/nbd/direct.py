@@ -127,10 +127,10 @@ def shard_force_local(posm_local: torch.Tensor, n_local: int, n_total: int, lo: 
     uniform: the bodies' common mass (uniform_mass) -> the kernel without its per-pair mass multiply."""
     _chk(posm_local, (padded_len(n_local), 4), "posm_local")
     with _lib.on_device(posm_local.device):
-        fn = _lib.lib().nbd_shard_force_local_f32 if uniform is None else _lib.lib().nbd_shard_force_local_uniform_f32
-        _lib.check(fn(
+        name = "nbd_shard_force_local_f32" if uniform is None else "nbd_shard_force_local_uniform_f32"
+        _lib.check(getattr(_lib.lib(), name)(
             posm_local.data_ptr(), n_local, float(softening_sq), workspace.data_ptr(), _nbytes(workspace),
-            n_total, lo, _lib.current_stream(posm_local.device)), "nbd_shard_force_local_f32")
+            n_total, lo, _lib.current_stream(posm_local.device)), name)
 
 
 def shard_force_remote(posm_all: torch.Tensor, n_total: int, posm_local: torch.Tensor, n_local: int, lo: int,

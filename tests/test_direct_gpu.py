@@ -272,7 +272,15 @@ def test_tensor_inputs_are_copied(gpu_device):
     assert torch.equal(pos.cpu(), torch.tensor(g["pos"]))       # caller's tensor untouched
 
 
-def _sharded_worker(rank, world, port, n, steps, out_dir):
+def _sharded_masses(n, masses):
+    from nbd.plummer import generate_plummer
+    p, v, m = generate_plummer(n, seed=77)
+    if masses == "ragged":
+        m = m * np.random.default_rng(1).uniform(0.5, 2.0, n)
+    return p, v, m
+
+
+def _sharded_worker(rank, world, port, n, steps, out_dir, masses="ragged"):
     import os
     import sys
     import torch.distributed as dist
@@ -284,43 +292,53 @@ def _sharded_worker(rank, world, port, n, steps, out_dir):
     dist.init_process_group("gloo", init_method=f"tcp://127.0.0.1:{port}", rank=rank, world_size=world)
     try:
         from galaxify import simulation
-        from nbd.plummer import generate_plummer
-        p, v, m = generate_plummer(n, seed=77)
-        m = m * np.random.default_rng(1).uniform(0.5, 2.0, n)
-        sim = simulation.LeapFrogSimulator(positions=p, velocities=v, masses=m, dt=0.01, calc_energy=True,
-                                           device="cuda", process_group=dist.group.WORLD)
-        for _ in range(steps):
-            sim.step()
-        u, k = sim.compute_energies()
-        full = {key: sim.gather(key).cpu().numpy() for key in ("positions", "velocities", "accelerations")}
+        p, v, m = _sharded_masses(n, masses)
+        kw = dict(positions=p, velocities=v, masses=m, dt=0.01, calc_energy=True, device="cuda",
+                  process_group=dist.group.WORLD)
+        out = {}
+        # equal masses: the Euler step too goes through the equal-mass shard entries
+        for cls, tag in (("LeapFrogSimulator", ""),) + ((("EulerSimulator", "euler_"),) if masses == "equal" else ()):
+            sim = getattr(simulation, cls)(**kw)
+            assert sim._sharded and (sim._uniform is not None) == (masses == "equal"), (cls, sim._uniform)
+            for _ in range(steps):
+                sim.step()
+            out[tag + "u"], out[tag + "k"] = sim.compute_energies()
+            for key in ("positions", "velocities", "accelerations"):
+                out[tag + key] = sim.gather(key).cpu().numpy()
         if rank == 0:
-            np.savez(os.path.join(out_dir, "sharded.npz"), u=u, k=k, **full)
+            np.savez(os.path.join(out_dir, "sharded.npz"), **out)
     finally:
         dist.destroy_process_group()
 
 
-@pytest.mark.parametrize("n", [1024, 1001])
-def test_two_rank_range_partition_on_gpu_matches_single_rank(n, tmp_path, gpu_device):
+@pytest.mark.parametrize("n,masses", [pytest.param(1024, "ragged", id="1024"), pytest.param(1001, "ragged", id="1001"),
+                                      pytest.param(1001, "equal", id="1001-equal")])
+def test_two_rank_range_partition_on_gpu_matches_single_rank(n, masses, tmp_path, gpu_device, monkeypatch):
     """The real sharded path (HIP kernels, tgt_global_offset, one all-gather per step) with two
-    processes sharing this GPU over gloo (RCCL needs distinct devices) vs the un-sharded simulator."""
+    processes sharing this GPU over gloo (RCCL needs distinct devices) vs the un-sharded simulator.
+    equal: unmodified Plummer masses, so the ranks run nbd_shard_force_*_uniform_f32 with real remote blocks (leapfrog
+    and Euler), against un-sharded simulators kept on the general kernel (NBD_UNIFORM_MASS=0)."""
     import socket
     import torch.multiprocessing as mp
     with socket.socket() as s:
         s.bind(("127.0.0.1", 0))
         port = s.getsockname()[1]
     steps = 3
-    mp.spawn(_sharded_worker, args=(2, port, n, steps, str(tmp_path)), nprocs=2, join=True)
+    mp.spawn(_sharded_worker, args=(2, port, n, steps, str(tmp_path), masses), nprocs=2, join=True)
     got = np.load(tmp_path / "sharded.npz")
-    from nbd.plummer import generate_plummer
-    p, v, m = generate_plummer(n, seed=77)
-    m = m * np.random.default_rng(1).uniform(0.5, 2.0, n)
-    sim = _mk("LeapFrogSimulator", dict(pos=p, vel=v, mass=m, g_const=1.0, softening=0.1, dt=0.01))
-    for _ in range(steps):
-        sim.step()
-    for key, ref in (("positions", sim.positions), ("velocities", sim.velocities), ("accelerations", sim.accelerations)):
-        assert row_rel(got[key], _np(ref)) < 2e-6, key
-    u, k = sim.compute_energies()
-    assert abs(got["u"] - u) < 1e-6 * abs(u) and abs(got["k"] - k) < 1e-6 * abs(k)
+    p, v, m = _sharded_masses(n, masses)
+    if masses == "equal":
+        monkeypatch.setenv("NBD_UNIFORM_MASS", "0")
+    for cls, tag in (("LeapFrogSimulator", ""),) + ((("EulerSimulator", "euler_"),) if masses == "equal" else ()):
+        sim = _mk(cls, dict(pos=p, vel=v, mass=m, g_const=1.0, softening=0.1, dt=0.01))
+        assert sim._uniform is None and not sim._sharded
+        for _ in range(steps):
+            sim.step()
+        for key, ref in (("positions", sim.positions), ("velocities", sim.velocities),
+                         ("accelerations", sim.accelerations)):
+            assert row_rel(got[tag + key], _np(ref)) < 2e-6, (cls, key)
+        u, k = sim.compute_energies()
+        assert abs(got[tag + "u"] - u) < 1e-6 * abs(u) and abs(got[tag + "k"] - k) < 1e-6 * abs(k), cls
 
 
 def test_bench_py_multi_rank_json_end_to_end(gpu_device, tmp_path):
