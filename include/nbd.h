@@ -133,6 +133,8 @@ int nbd_drift_f32(float* pos, const float* vel, int n, float c, nbd_stream_t str
  * (simulation.py:135-139) as one launch, so that a chunk of steps can be captured into a hipGraph with its
  * snapshots going to a device ring (one device->host copy per chunk instead of three per step). */
 int nbd_snapshot_f32(const float* pos, const float* vel, const float* acc, int n, float* out, nbd_stream_t stream);
+/* The same launch for a float64 state (the double-precision Hermite simulators): out is double[9n], 8-byte aligned. */
+int nbd_snapshot_f64(const double* pos, const double* vel, const double* acc, int n, double* out, nbd_stream_t stream);
 
 /* Bytes of scratch the fused step entry points need (always >= one slab). */
 size_t nbd_step_workspace_bytes(int n);
@@ -294,6 +296,59 @@ int nbd_batch_hermite_step_f32(const int* offsets, int n_scenes, const void* pla
                                float* vel, const float* acc_in, const float* jerk_in, float* acc_out, float* jerk_out,
                                const float* mass, const float* hdt, const float* softening_sq, const float* g_const,
                                float* posm, void* workspace, size_t workspace_bytes, nbd_stream_t stream);
+
+/* ---- double-precision Hermite per scene (csrc/direct_batch_hermite_f64.hip): "double-precision Hermite" below applied
+ * to every scene of a batch, one set of launches for all scenes. State, masses, a, j: double; offsets as above. A scene's
+ * pos / vel / acc / jerk, energies, potentials and invariants are bit-identical to the nbd_*_f64 entries of
+ * "double-precision Hermite" on that scene alone with the same parameters, wherever it stands in the batch.
+ *   plan   : a work list of its own (NOT the one of nbd_batch_plan): one item per scene x group of 64 targets x slab, the
+ *            slab count of a scene being nbd_hermite_f64_plan's for its size; same layout, same rules (16-byte aligned
+ *            device buffer, plan_bytes as reported). NBD_E_UNSUPPORTED when the items, the rows or the doubles of the
+ *            partial sums outgrow the kernels' int offsets.
+ *   posd, veld : double[rows][4], 32-byte aligned: {x, y, z, m} and {vx, vy, vz, 0}, every scene padded to whole chunks of
+ *            NBD_SRC_PAD rows with zero rows (rows as nbd_batch_f64_plan reports).
+ *   params : DEVICE double[NBD_BATCH_F64_PARAM_ROWS][S], 8-byte aligned, row r of scene s at params[r * S + s]; rows:
+ *            G, softening^2, softening, dt, dt/2, dt^2/2, dt^3/6, dt^2/12 -- the doubles nbd_hermite_step_f64 forms from
+ *            its dt (0.5*dt, 0.5*dt*dt, dt*dt*dt/6.0, dt*dt/12.0). Every per-scene scalar is read from this table by the
+ *            kernels: a step can be captured into a graph, and a changed parameter is a rewrite of the table.
+ *   workspace : nbd_batch_f64_workspace_bytes, 8-byte aligned (6 doubles per body and slab); it may hold anything.
+ * Argument errors return NBD_E_BADARG (NBD_E_WORKSPACE for the workspace) before any launch. No atomics, no memsets, no
+ * host syncs. */
+#define NBD_BATCH_F64_PARAM_ROWS 8
+/* Host-only: work items, packed rows and the bytes of the device plan. */
+int nbd_batch_f64_plan(const int* offsets, int n_scenes, int* n_items, int* rows, size_t* plan_bytes);
+/* Host-only: the bytes of the workspace of every entry below. */
+int nbd_batch_f64_workspace_bytes(const int* offsets, int n_scenes, size_t* bytes);
+/* Host-only: writes the plan into HOST memory (as nbd_batch_plan_fill). */
+int nbd_batch_f64_plan_fill(const int* offsets, int n_scenes, void* plan, size_t plan_bytes);
+/* posd = {x, m}, veld = {v, 0} of every scene (zero rows in each scene's padding): one launch. */
+int nbd_batch_pack_f64(const int* offsets, int n_scenes, const void* plan, size_t plan_bytes, const double* pos,
+                       const double* vel, const double* mass, double* posd, double* veld, nbd_stream_t stream);
+/* acc_out, jerk_out (N, 3) of the current state of every scene: the pack above, the acceleration + jerk, the slab sum in
+ * slab order with G_s. Leaves posd = {x, m}, veld = {v, 0}. */
+int nbd_batch_accel_jerk_f64(const int* offsets, int n_scenes, const void* plan, size_t plan_bytes, const double* pos,
+                             const double* vel, const double* mass, const double* params, double* acc_out,
+                             double* jerk_out, double* posd, double* veld, void* workspace, size_t workspace_bytes,
+                             nbd_stream_t stream);
+/* One Hermite step of every scene, three launches: pos, vel in place; acc_out, jerk_out = a1, j1 at the predicted state
+ * (acc_in may alias acc_out, jerk_in may alias jerk_out); posd = {x1, m}; veld is scratch. */
+int nbd_batch_hermite_step_f64(const int* offsets, int n_scenes, const void* plan, size_t plan_bytes, double* pos,
+                               double* vel, const double* acc_in, const double* jerk_in, double* acc_out,
+                               double* jerk_out, const double* mass, const double* params, double* posd, double* veld,
+                               void* workspace, size_t workspace_bytes, nbd_stream_t stream);
+/* nbd_energy_f64 per scene from posd (as the entries above leave it) and vel: out_uk is a device double[S][2] =
+ * {U_s, K_s}; a zero-body scene gives {0, 0}. */
+int nbd_batch_energies_f64(const int* offsets, int n_scenes, const void* plan, size_t plan_bytes, const double* posd,
+                           const double* vel, const double* params, double* out_uk, void* workspace,
+                           size_t workspace_bytes, nbd_stream_t stream);
+/* nbd_potential_f64 per scene: phi_out is a device double[N_total] in body order. */
+int nbd_batch_potential_f64(const int* offsets, int n_scenes, const void* plan, size_t plan_bytes, const double* posd,
+                            const double* params, double* phi_out, void* workspace, size_t workspace_bytes,
+                            nbd_stream_t stream);
+/* nbd_invariants_state_f64 per scene: out_rows is a device double[S][16]; a zero-body scene gives a row of zeros. */
+int nbd_batch_invariants_state_f64(const int* offsets, int n_scenes, const void* plan, size_t plan_bytes,
+                                   const double* pos, const double* vel, const double* mass, const double* phi,
+                                   double* out_rows, nbd_stream_t stream);
 
 /* ------------------------------------------------------------ 4th-order Hermite integrator (csrc/direct_hermite.hip)
  * An extension (the reference has Euler and leapfrog only): the shared-timestep predictor-corrector of Makino & Aarseth

@@ -17,10 +17,6 @@
 #include <hip/hip_runtime.h>
 #include <limits.h>
 #include <stdint.h>
-#include <string.h>
-
-#include <algorithm>
-#include <vector>
 
 #include "../../include/nbd.h"
 #include "direct_batch_plan.h"
@@ -202,35 +198,7 @@ int nbd_batch_plan_fill(const int* offsets, int n_scenes, void* plan, size_t pla
   const int rc = batch_totals(offsets, n_scenes, &t);
   if (rc) return rc;
   if (!plan || plan_bytes != plan_bytes_of(t)) return NBD_E_BADARG;
-  std::vector<int> items;             // (scene, group, slab, chunks per wave) before ordering
-  items.reserve((size_t)t.n_items * 4);
-  std::vector<SceneRec> scenes(n_scenes);
-  std::vector<int> rows((size_t)t.n_rows);
-  int poff = 0, ws_off = 0, u_off = 0;
-  for (int s = 0; s < n_scenes; ++s) {
-    SceneRec& r = scenes[s];
-    r.off = offsets[s]; r.n = offsets[s + 1] - offsets[s]; r.poff = poff; r.ws_off = ws_off; r.u_off = u_off;
-    r.slabs = r.n > 0 ? scene_slabs(r.n) : 0;
-    r.n_chunks = ceil_div(r.n, kChunk);
-    r.groups = ceil_div(r.n, kTgtPerWG);
-    const int cpw = r.n > 0 ? ceil_div(r.n_chunks, r.slabs * kWaves) : 0;
-    for (int g = 0; g < r.groups; ++g)
-      for (int k = 0; k < r.slabs; ++k) items.insert(items.end(), {s, g, k, cpw});
-    for (int i = 0; i < r.n_chunks * kChunk; ++i) rows[(size_t)poff + i] = s;
-    poff += r.n_chunks * kChunk; ws_off += r.slabs * r.n * 3; u_off += r.groups * r.slabs;
-  }
-  // dispatch order: longest items first (a stable order of the WORK; no sum depends on it)
-  std::vector<int> order(t.n_items);
-  for (int i = 0; i < t.n_items; ++i) order[i] = i;
-  std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return items[4 * a + 3] > items[4 * b + 3]; });
-  int* out = static_cast<int*>(plan);
-  for (int i = 0; i < t.n_items; ++i) {
-    const int* src = &items[4 * order[i]];
-    out[4 * i] = src[0]; out[4 * i + 1] = src[1]; out[4 * i + 2] = src[2]; out[4 * i + 3] = 0;
-  }
-  memcpy(out + 4 * (size_t)t.n_items, scenes.data(), scenes.size() * sizeof(SceneRec));
-  memcpy(reinterpret_cast<char*>(out + 4 * (size_t)t.n_items) + scenes.size() * sizeof(SceneRec), rows.data(),
-         rows.size() * sizeof(int));
+  batch_plan_fill(offsets, n_scenes, t, plan, scene_geom_f32);
   return 0;
 }
 

@@ -1,0 +1,414 @@
+// direct_batch_hermite_f64.hip -- direct_hermite_f64.hip's double-precision Hermite step and diagnostics, applied to every
+// scene of an ensemble of independent systems by one set of launches (gfx950): direct_batch_hermite.hip in the number
+// format of direct_hermite_f64.hip. C-ABI: the nbd_batch_*_f64 entries of include/nbd.h; Python:
+// galaxify.simulation.BatchedSimulator(integrator="hermite", dtype=torch.float64).
+//
+// The scenes lie back to back as in direct_batch.hip; the packed rows are posd = {x, y, z, m} and veld = {vx, vy, vz, 0},
+// d4 each, every scene padded to whole chunks of 64 rows with zero rows. The work list has the layout of the fp32 plan
+// (direct_batch_plan.h: items, scene records, row_scene) but its own contents: one item per (scene, group of 64 targets,
+// slab), the geometry of a scene being plan_f64(n_s) -- the one-system launch of direct_hermite_f64.hip for its size, a
+// function of n_s alone -- and ws_off the first DOUBLE of the scene's double[slabs][6][n_s] partial sums.
+//
+// Every per-scene scalar comes from ONE device table of doubles, par[kParams][S] (rows: ParamRow below), which the caller
+// forms on the host by the expressions of the one-system path; no kernel takes a per-scene scalar by value, so a step
+// can be captured into a graph and a changed dt, softening or G is a rewrite of the table. One step is three launches:
+//   predict  : one thread per packed row: hermite_predict_row<double> with the scene's constants
+//   evaluate : one workgroup per item: AccelJerkPair + walk_f64 on the scene's rows, the chunks of wave 4 k + w under the
+//              scene's own balanced split; unscaled partial sums into the scene's double[slabs][6][n_s]
+//   correct  : one thread per packed row: hermite_slab_sum (slab order) x G_s, hermite_correct_row, posd = {x1, m}
+// and the diagnostics walk the same items with EnergyPair / PotentialPair and finish per scene. Every kernel here is a
+// prologue that reads its geometry and calls the single copies of the arithmetic (hermite_kernels.h,
+// hermite_f64_kernels.h): a scene's results are bit-identical to the nbd_*_f64 entries on that scene alone. No atomics, no
+// memsets, no host syncs: deterministic with a workspace that may hold anything.
+#include <hip/hip_runtime.h>
+#include <limits.h>
+#include <stdint.h>
+
+#include "../../include/nbd.h"
+#include "direct_batch_plan.h"
+#include "direct_kernels.h"
+#include "hermite_f64_kernels.h"
+#include "hermite_kernels.h"
+
+namespace {
+
+// rows of the per-scene parameter table par[kParams][S]
+enum ParamRow { kG = 0, kEps2, kEps, kDt, kDtHalf, kDt2Half, kDt3Sixth, kDt2Twelfth, kParams };
+static_assert(kParams == NBD_BATCH_F64_PARAM_ROWS, "the table include/nbd.h describes");
+
+// ---- the fp64 plan: the layout and the checks of direct_batch_plan.h with plan_f64's geometry. The scene's slabs are
+// double[slabs][6][n], counted in DOUBLES (BatchTotals::ws_floats, SceneRec::ws_off); no energy partials.
+SceneGeom scene_geom_f64(int n) {
+  const F64Plan p = plan_f64(n);
+  return SceneGeom{p.slabs, p.groups, (int64_t)p.slabs * 6 * n, 0};
+}
+
+int batch_totals_f64(const int* offsets, int n_scenes, BatchTotals* t) {
+  return batch_totals(offsets, n_scenes, t, scene_geom_f64);
+}
+
+size_t ws_bytes_f64(const BatchTotals& t) { return (size_t)t.ws_floats * sizeof(double); }
+
+int prologue_f64(const int* offsets, int n_scenes, const void* plan, size_t plan_bytes, BatchTotals* t) {
+  return batch_prologue(offsets, n_scenes, plan, plan_bytes, t, scene_geom_f64);
+}
+
+bool bad_workspace(const void* workspace, size_t workspace_bytes, const BatchTotals& t) {
+  return !workspace || misaligned8(workspace) || workspace_bytes < ws_bytes_f64(t);
+}
+
+// What a workgroup of an item reads from the work list, uniform across the workgroup (SGPRs)
+struct Item {
+  int s, grp, slab, n, n_chunks, slabs, poff, ws_off;
+};
+
+__device__ __forceinline__ Item load_item(const int4* __restrict__ items, const SceneRec* __restrict__ scenes) {
+  const int4 it = items[blockIdx.x];
+  Item w;
+  w.s = __builtin_amdgcn_readfirstlane(it.x);
+  w.grp = __builtin_amdgcn_readfirstlane(it.y);
+  w.slab = __builtin_amdgcn_readfirstlane(it.z);
+  const SceneRec sc = load_scene(scenes, w.s);
+  w.n = __builtin_amdgcn_readfirstlane(sc.n);
+  w.n_chunks = __builtin_amdgcn_readfirstlane(sc.n_chunks);
+  w.slabs = __builtin_amdgcn_readfirstlane(sc.slabs);
+  w.poff = __builtin_amdgcn_readfirstlane(sc.poff);
+  w.ws_off = __builtin_amdgcn_readfirstlane(sc.ws_off);
+  return w;
+}
+
+// posd[r] = {x_p, m}, veld[r] = {v_p, 0} for every packed row r (zero rows behind each scene's last body).
+// acc == nullptr: a plain pack of (x, v).
+__global__ __launch_bounds__(256) void batch_predict_f64_kernel(const int* __restrict__ row_scene,
+                                                                const SceneRec* __restrict__ scenes, int n_rows,
+                                                                const double* __restrict__ pos,
+                                                                const double* __restrict__ vel,
+                                                                const double* __restrict__ acc,
+                                                                const double* __restrict__ jerk,
+                                                                const double* __restrict__ mass,
+                                                                const double* __restrict__ par, int n_scenes,
+                                                                d4* __restrict__ posd, d4* __restrict__ veld) {
+  const int r = blockIdx.x * 256 + threadIdx.x;
+  if (r >= n_rows) return;
+  const int s = row_scene[r];
+  const SceneRec sc = load_scene(scenes, s);
+  const int i = r - sc.poff;
+  d4 pm = HermiteFmt<double>::zero(), vp = HermiteFmt<double>::zero();
+  if (i < sc.n) {
+    const size_t b = (size_t)sc.off + i;
+    const double dt = acc ? par[kDt * n_scenes + s] : 0.0;
+    const double dt2_half = acc ? par[kDt2Half * n_scenes + s] : 0.0;
+    const double dt3_sixth = acc ? par[kDt3Sixth * n_scenes + s] : 0.0;
+    const PosVel3<double> p = hermite_predict_row(pos, vel, acc, jerk, b, dt, dt2_half, dt3_sixth, acc != nullptr);
+    pm = hermite_row(p.x, mass[b]);
+    vp = hermite_row(p.v, 0.0);
+  }
+  posd[r] = pm;
+  veld[r] = vp;
+}
+
+// One workgroup per item (s, g, k): accel_jerk_f64_kernel's prologue read from the scene record -- targets
+// [64 g, 64 g + 64) of scene s, the chunks of wave 4 k + w under chunk_split(n_chunks, slabs) of the scene -- then the
+// same walk_f64. out: the scene's double[slabs][6][n] at ws + ws_off.
+__global__ __launch_bounds__(64 * kWaves) void batch_accel_jerk_f64_kernel(const d4* __restrict__ posd,
+                                                                           const d4* __restrict__ veld,
+                                                                           const int4* __restrict__ items,
+                                                                           const SceneRec* __restrict__ scenes,
+                                                                           const double* __restrict__ par, int n_scenes,
+                                                                           double* __restrict__ ws) {
+  __shared__ __attribute__((aligned(32))) f4 lds[kWaves * stage_quads<true>()];
+  const Item w = load_item(items, scenes);
+  const double eps2 = par[kEps2 * n_scenes + w.s];
+  const d4* pd = posd + w.poff;
+  const d4* vd = veld + w.poff;
+  const int t_base = w.grp * kTgtF64;
+  const int i = t_base + (threadIdx.x & 63), row = min(i, w.n - 1);
+  const int jw = w.slab * kWaves + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int parts = w.slabs * kWaves;
+  int c_begin, c_end;
+  wave_chunk_range(jw, w.n_chunks / parts, w.n_chunks % parts, c_begin, c_end);
+  AccelJerkPair pr(pd[row], vd[row], eps2, i, w.n);
+  walk_f64(pr, pd, vd, c_begin, c_end, eps2 < kEps2MaskedF64, w.grp, lds,
+           ws + (size_t)w.ws_off + (size_t)w.slab * AccelJerkPair::kOut * w.n + t_base, (size_t)w.n,
+           min(kTgtF64, w.n - t_base));
+}
+
+// One thread per packed row (a row belongs to one scene; the padding rows leave at once): a1, j1 = hermite_slab_sum of the
+// body's row in its scene's slabs, scaled by G_s. pos == nullptr: write a1, j1 only. Else hermite_correct_row: reads a0,
+// j0 (acc_in / jerk_in may alias acc_out / jerk_out: each element is read before it is written, by the same thread), x,
+// v; writes x1, v1, a1, j1 and posd = {x1, m}.
+__global__ __launch_bounds__(256) void batch_correct_f64_kernel(const int* __restrict__ row_scene,
+                                                                const SceneRec* __restrict__ scenes, int n_rows,
+                                                                const double* __restrict__ ws,
+                                                                const double* __restrict__ par, int n_scenes,
+                                                                double* pos, double* vel, const double* acc_in,
+                                                                const double* jerk_in, double* acc_out, double* jerk_out,
+                                                                const double* __restrict__ mass, d4* __restrict__ posd) {
+  const int r = blockIdx.x * 256 + threadIdx.x;
+  if (r >= n_rows) return;
+  const int s = row_scene[r];
+  const SceneRec sc = load_scene(scenes, s);
+  const int i = r - sc.poff;
+  double a1[3], j1[3];
+  if (!hermite_slab_sum(ws + (size_t)sc.ws_off, sc.slabs, sc.n, (size_t)i, i < sc.n, par[kG * n_scenes + s], a1, j1))
+    return;
+  const size_t b = (size_t)sc.off + i;
+  if (pos) {
+    const Corrected<double> c = hermite_correct_row(pos, vel, acc_in, jerk_in, b, a1, j1,
+                                                    par[kDtHalf * n_scenes + s], par[kDt2Twelfth * n_scenes + s]);
+    posd[r] = hermite_row(c.x1, mass[b]);
+  }
+  hermite_store_force(acc_out, jerk_out, b, a1, j1);
+}
+
+// ---- diagnostics. Their partial sums are double[slabs][n] per scene, at the scene's ws_off (the front of its
+// double[slabs][6][n]).
+
+// energy_f64_kernel's prologue per item: group g walks the chunks [g, n_chunks) of its scene, split over slabs x 4 waves.
+__global__ __launch_bounds__(64 * kWaves) void batch_energy_f64_kernel(const d4* __restrict__ posd,
+                                                                       const int4* __restrict__ items,
+                                                                       const SceneRec* __restrict__ scenes,
+                                                                       const double* __restrict__ par, int n_scenes,
+                                                                       double* __restrict__ ws) {
+  __shared__ __attribute__((aligned(32))) f4 lds[kWaves * stage_quads<false>()];
+  const Item w = load_item(items, scenes);
+  const double soft = par[kEps * n_scenes + w.s];
+  const d4* pd = posd + w.poff;
+  const int t_base = w.grp * kTgtF64;
+  const int i = t_base + (threadIdx.x & 63);
+  const int jw = w.slab * kWaves + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int span = w.n_chunks - w.grp, parts = w.slabs * kWaves;
+  int c_begin, c_end;
+  wave_chunk_range(jw, span / parts, span % parts, c_begin, c_end);
+  EnergyPair pr(pd[min(i, w.n - 1)], soft, i, w.n);
+  walk_f64(pr, pd, pd, c_begin + w.grp, c_end + w.grp, true, w.grp, lds,
+           ws + (size_t)w.ws_off + (size_t)w.slab * w.n + t_base, (size_t)w.n, min(kTgtF64, w.n - t_base));
+}
+
+// one workgroup per scene: out_uk[s] = {U_s, K_s} (energy_finish_f64; an empty scene gives {0, 0})
+__global__ __launch_bounds__(kSumThreads) void batch_energy_finish_f64_kernel(const SceneRec* __restrict__ scenes,
+                                                                              const double* __restrict__ ws,
+                                                                              const d4* __restrict__ posd,
+                                                                              const double* __restrict__ vel,
+                                                                              const double* __restrict__ par,
+                                                                              int n_scenes, double* __restrict__ out_uk) {
+  __shared__ double red[2][kSumWaves];
+  const int s = blockIdx.x;
+  const SceneRec sc = load_scene(scenes, s);
+  energy_finish_f64(ws + (size_t)sc.ws_off, sc.slabs, sc.n, posd + sc.poff, vel + (size_t)sc.off * 3,
+                    par[kG * n_scenes + s], out_uk + 2 * (size_t)s, red);
+}
+
+// potential_f64_kernel's prologue per item
+__global__ __launch_bounds__(64 * kWaves) void batch_potential_f64_kernel(const d4* __restrict__ posd,
+                                                                          const int4* __restrict__ items,
+                                                                          const SceneRec* __restrict__ scenes,
+                                                                          const double* __restrict__ par, int n_scenes,
+                                                                          double* __restrict__ ws) {
+  __shared__ __attribute__((aligned(32))) f4 lds[kWaves * stage_quads<false>()];
+  const Item w = load_item(items, scenes);
+  const double eps2 = par[kEps2 * n_scenes + w.s];
+  const d4* pd = posd + w.poff;
+  const int t_base = w.grp * kTgtF64;
+  const int i = t_base + (threadIdx.x & 63);
+  const int jw = w.slab * kWaves + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int parts = w.slabs * kWaves;
+  int c_begin, c_end;
+  wave_chunk_range(jw, w.n_chunks / parts, w.n_chunks % parts, c_begin, c_end);
+  PotentialPair pr(pd[min(i, w.n - 1)], eps2, i, w.n);
+  walk_f64(pr, pd, pd, c_begin, c_end, eps2 < kEps2MaskedF64, w.grp, lds,
+           ws + (size_t)w.ws_off + (size_t)w.slab * w.n + t_base, (size_t)w.n, min(kTgtF64, w.n - t_base));
+}
+
+// phi[off_s + i] = potential_finish_f64 of body i of its scene: one thread per packed row
+__global__ __launch_bounds__(256) void batch_potential_finish_f64_kernel(const int* __restrict__ row_scene,
+                                                                         const SceneRec* __restrict__ scenes,
+                                                                         int n_rows, const double* __restrict__ ws,
+                                                                         const double* __restrict__ par, int n_scenes,
+                                                                         double* __restrict__ phi) {
+  const int r = blockIdx.x * 256 + threadIdx.x;
+  if (r >= n_rows) return;
+  const int s = row_scene[r];
+  const SceneRec sc = load_scene(scenes, s);
+  const int i = r - sc.poff;
+  if (i >= sc.n) return;
+  phi[(size_t)sc.off + i] = potential_finish_f64(ws + (size_t)sc.ws_off, sc.slabs, sc.n, i, par[kG * n_scenes + s]);
+}
+
+// one workgroup per scene: invariants_state_f64_kernel's body on the scene's part of the state
+__global__ __launch_bounds__(kInvThreads) void batch_invariants_state_f64_kernel(const SceneRec* __restrict__ scenes,
+                                                                                 const double* __restrict__ pos,
+                                                                                 const double* __restrict__ vel,
+                                                                                 const double* __restrict__ mass,
+                                                                                 const double* __restrict__ phi,
+                                                                                 double* __restrict__ rows) {
+  __shared__ double red[kInvSums][kInvWaves];
+  const SceneRec sc = load_scene(scenes, blockIdx.x);
+  const size_t off = (size_t)sc.off;
+  invariants_body(F64State{pos + 3 * off, vel + 3 * off, mass + off}, phi + off, sc.n,
+                  rows + (size_t)blockIdx.x * 16, red);
+}
+
+int launch_predict(const DevPlan& d, const BatchTotals& t, const double* pos, const double* vel, const double* acc,
+                   const double* jerk, const double* mass, const double* par, double* posd, double* veld,
+                   hipStream_t st) {
+  batch_predict_f64_kernel<<<ceil_div(t.n_rows, 256), 256, 0, st>>>(d.row_scene, d.scenes, t.n_rows, pos, vel, acc, jerk,
+                                                                    mass, par, t.n_scenes, reinterpret_cast<d4*>(posd),
+                                                                    reinterpret_cast<d4*>(veld));
+  return launch_status();
+}
+
+// the force of every scene at posd / veld, then the slab sum (+ the corrector when pos is given)
+int launch_force_correct(const DevPlan& d, const BatchTotals& t, double* posd, const double* veld, const double* par,
+                         double* pos, double* vel, const double* acc_in, const double* jerk_in, double* acc_out,
+                         double* jerk_out, const double* mass, void* workspace, hipStream_t st) {
+  double* ws = static_cast<double*>(workspace);
+  batch_accel_jerk_f64_kernel<<<t.n_items, 64 * kWaves, 0, st>>>(reinterpret_cast<const d4*>(posd),
+                                                                 reinterpret_cast<const d4*>(veld), d.items, d.scenes,
+                                                                 par, t.n_scenes, ws);
+  const int rc = launch_status();
+  if (rc) return rc;
+  batch_correct_f64_kernel<<<ceil_div(t.n_rows, 256), 256, 0, st>>>(d.row_scene, d.scenes, t.n_rows, ws, par, t.n_scenes,
+                                                                    pos, vel, acc_in, jerk_in, acc_out, jerk_out, mass,
+                                                                    reinterpret_cast<d4*>(posd));
+  return launch_status();
+}
+
+}  // namespace
+
+extern "C" {
+
+int nbd_batch_f64_plan(const int* offsets, int n_scenes, int* n_items, int* rows, size_t* plan_bytes) {
+  BatchTotals t;
+  const int rc = batch_totals_f64(offsets, n_scenes, &t);
+  if (rc) return rc;
+  if (n_items) *n_items = t.n_items;
+  if (rows) *rows = t.n_rows;
+  if (plan_bytes) *plan_bytes = plan_bytes_of(t);
+  return 0;
+}
+
+int nbd_batch_f64_workspace_bytes(const int* offsets, int n_scenes, size_t* bytes) {
+  BatchTotals t;
+  const int rc = batch_totals_f64(offsets, n_scenes, &t);
+  if (rc) return rc;
+  if (!bytes) return NBD_E_BADARG;
+  *bytes = ws_bytes_f64(t);
+  return 0;
+}
+
+int nbd_batch_f64_plan_fill(const int* offsets, int n_scenes, void* plan, size_t plan_bytes) {
+  BatchTotals t;
+  const int rc = batch_totals_f64(offsets, n_scenes, &t);
+  if (rc) return rc;
+  if (!plan || plan_bytes != plan_bytes_of(t)) return NBD_E_BADARG;
+  batch_plan_fill(offsets, n_scenes, t, plan, scene_geom_f64);
+  return 0;
+}
+
+int nbd_batch_pack_f64(const int* offsets, int n_scenes, const void* plan, size_t plan_bytes, const double* pos,
+                       const double* vel, const double* mass, double* posd, double* veld, nbd_stream_t stream) {
+  BatchTotals t;
+  const int rc = prologue_f64(offsets, n_scenes, plan, plan_bytes, &t);
+  if (rc) return rc;
+  if (t.n_total == 0) return 0;
+  if (!pos || !vel || !mass || !posd || !veld || misaligned32(posd) || misaligned32(veld)) return NBD_E_BADARG;
+  return launch_predict(dev_plan(plan, t), t, pos, vel, nullptr, nullptr, mass, nullptr, posd, veld,
+                        (hipStream_t)stream);
+}
+
+int nbd_batch_accel_jerk_f64(const int* offsets, int n_scenes, const void* plan, size_t plan_bytes, const double* pos,
+                             const double* vel, const double* mass, const double* params, double* acc_out,
+                             double* jerk_out, double* posd, double* veld, void* workspace, size_t workspace_bytes,
+                             nbd_stream_t stream) {
+  BatchTotals t;
+  int rc = prologue_f64(offsets, n_scenes, plan, plan_bytes, &t);
+  if (rc) return rc;
+  if (t.n_total == 0) return 0;
+  if (!pos || !vel || !mass || !params || misaligned8(params) || !acc_out || misaligned8(acc_out) || !jerk_out ||
+      misaligned8(jerk_out) || !posd || !veld || misaligned32(posd) || misaligned32(veld))
+    return NBD_E_BADARG;
+  if (bad_workspace(workspace, workspace_bytes, t)) return NBD_E_WORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  const DevPlan d = dev_plan(plan, t);
+  if ((rc = launch_predict(d, t, pos, vel, nullptr, nullptr, mass, nullptr, posd, veld, st))) return rc;
+  return launch_force_correct(d, t, posd, veld, params, nullptr, nullptr, nullptr, nullptr, acc_out, jerk_out, nullptr,
+                              workspace, st);
+}
+
+int nbd_batch_hermite_step_f64(const int* offsets, int n_scenes, const void* plan, size_t plan_bytes, double* pos,
+                               double* vel, const double* acc_in, const double* jerk_in, double* acc_out,
+                               double* jerk_out, const double* mass, const double* params, double* posd, double* veld,
+                               void* workspace, size_t workspace_bytes, nbd_stream_t stream) {
+  BatchTotals t;
+  int rc = prologue_f64(offsets, n_scenes, plan, plan_bytes, &t);
+  if (rc) return rc;
+  if (t.n_total == 0) return 0;
+  if (!pos || !vel || !acc_in || !jerk_in || !mass || !params || misaligned8(params) || !acc_out ||
+      misaligned8(acc_out) || !jerk_out || misaligned8(jerk_out) || !posd || !veld || misaligned32(posd) ||
+      misaligned32(veld))
+    return NBD_E_BADARG;
+  if (bad_workspace(workspace, workspace_bytes, t)) return NBD_E_WORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  const DevPlan d = dev_plan(plan, t);
+  if ((rc = launch_predict(d, t, pos, vel, acc_in, jerk_in, mass, params, posd, veld, st))) return rc;
+  return launch_force_correct(d, t, posd, veld, params, pos, vel, acc_in, jerk_in, acc_out, jerk_out, mass, workspace,
+                              st);
+}
+
+int nbd_batch_energies_f64(const int* offsets, int n_scenes, const void* plan, size_t plan_bytes, const double* posd,
+                           const double* vel, const double* params, double* out_uk, void* workspace,
+                           size_t workspace_bytes, nbd_stream_t stream) {
+  BatchTotals t;
+  int rc = prologue_f64(offsets, n_scenes, plan, plan_bytes, &t);
+  if (rc) return rc;
+  if (!out_uk || misaligned8(out_uk) || !params || misaligned8(params)) return NBD_E_BADARG;
+  if (t.n_total > 0 && (!posd || !vel || misaligned32(posd))) return NBD_E_BADARG;
+  if (t.n_total > 0 && bad_workspace(workspace, workspace_bytes, t)) return NBD_E_WORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  const DevPlan d = dev_plan(plan, t);
+  const d4* pd = reinterpret_cast<const d4*>(posd);
+  double* ws = static_cast<double*>(workspace);
+  if (t.n_items > 0) {
+    batch_energy_f64_kernel<<<t.n_items, 64 * kWaves, 0, st>>>(pd, d.items, d.scenes, params, n_scenes, ws);
+    if ((rc = launch_status())) return rc;
+  }
+  batch_energy_finish_f64_kernel<<<n_scenes, kSumThreads, 0, st>>>(d.scenes, ws, pd, vel, params, n_scenes, out_uk);
+  return launch_status();
+}
+
+int nbd_batch_potential_f64(const int* offsets, int n_scenes, const void* plan, size_t plan_bytes, const double* posd,
+                            const double* params, double* phi_out, void* workspace, size_t workspace_bytes,
+                            nbd_stream_t stream) {
+  BatchTotals t;
+  int rc = prologue_f64(offsets, n_scenes, plan, plan_bytes, &t);
+  if (rc) return rc;
+  if (t.n_total == 0) return 0;
+  if (!posd || misaligned32(posd) || !params || misaligned8(params) || !phi_out || misaligned8(phi_out))
+    return NBD_E_BADARG;
+  if (bad_workspace(workspace, workspace_bytes, t)) return NBD_E_WORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  const DevPlan d = dev_plan(plan, t);
+  double* ws = static_cast<double*>(workspace);
+  batch_potential_f64_kernel<<<t.n_items, 64 * kWaves, 0, st>>>(reinterpret_cast<const d4*>(posd), d.items, d.scenes,
+                                                                params, n_scenes, ws);
+  if ((rc = launch_status())) return rc;
+  batch_potential_finish_f64_kernel<<<ceil_div(t.n_rows, 256), 256, 0, st>>>(d.row_scene, d.scenes, t.n_rows, ws, params,
+                                                                             n_scenes, phi_out);
+  return launch_status();
+}
+
+int nbd_batch_invariants_state_f64(const int* offsets, int n_scenes, const void* plan, size_t plan_bytes,
+                                   const double* pos, const double* vel, const double* mass, const double* phi,
+                                   double* out_rows, nbd_stream_t stream) {
+  BatchTotals t;
+  const int rc = prologue_f64(offsets, n_scenes, plan, plan_bytes, &t);
+  if (rc) return rc;
+  if (!out_rows || misaligned8(out_rows)) return NBD_E_BADARG;
+  if (t.n_total > 0 && (!pos || !vel || !mass || !phi || misaligned8(phi))) return NBD_E_BADARG;
+  batch_invariants_state_f64_kernel<<<n_scenes, kInvThreads, 0, (hipStream_t)stream>>>(
+      dev_plan(plan, t).scenes, pos, vel, mass, phi, out_rows);
+  return launch_status();
+}
+
+}  // extern "C"

@@ -1,11 +1,16 @@
 // direct_batch_plan.h -- the device work list of the batched direct integrator (nbd_batch_plan / nbd_batch_plan_fill)
 // and the host checks every batched entry point makes before it launches, shared by direct_batch.hip (leapfrog, Euler,
-// energies) and direct_batch_hermite.hip (Hermite). The definitions sit in an anonymous namespace: every translation
-// unit that includes this file gets its own copies.
+// energies), direct_batch_hermite.hip (Hermite) and direct_batch_hermite_f64.hip (Hermite in double precision: the same
+// layout filled with another geometry per scene, SceneGeom below). The definitions sit in an anonymous namespace: every
+// translation unit that includes this file gets its own copies.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <limits.h>
 #include <stdint.h>
+#include <string.h>
+
+#include <algorithm>
+#include <vector>
 
 #include "../../include/nbd.h"
 #include "direct_kernels.h"
@@ -17,11 +22,12 @@ struct SceneRec {
   int off;      // first body of the scene in pos / vel / acc / mass
   int n;        // bodies
   int poff;     // first packed row (multiple of 64)
-  int ws_off;   // first float of the scene's slabs in the workspace: float[slabs][n][3]
+  int ws_off;   // first float of the scene's slabs in the workspace: float[slabs][n][3] (fp64 plan: first double of
+                // its double[slabs][6][n])
   int u_off;    // first fp64 energy partial of the scene: double[groups * slabs]
   int slabs;
   int n_chunks; // pad64(n) / 64
-  int groups;   // ceil(n / 128)
+  int groups;   // ceil(n / 128) (fp64 plan: ceil(n / 64))
 };
 
 // The slab count of a scene: the single-system launch plan for its size (depends on n alone).
@@ -38,29 +44,48 @@ int scene_slabs(int n) {
   return s;
 }
 
+// What a plan gives a scene of n > 0 bodies, and all that the fp32 plan and the fp64 plan
+// (direct_batch_hermite_f64.hip: groups of 64 targets, plan_f64's slabs) differ in: a function int -> SceneGeom.
+struct SceneGeom {
+  int slabs, groups;
+  int64_t ws;   // elements of the scene's slabs in the workspace, in the plan's own unit (ws_off counts them)
+  int64_t u;    // fp64 energy partials of the scene (u_off counts them)
+};
+
+// The fp32 plan: groups of 128 targets, float[slabs][n][3], one energy partial per item.
+inline SceneGeom scene_geom_f32(int n) {
+  const int slabs = scene_slabs(n), groups = ceil_div(n, kTgtPerWG);
+  return SceneGeom{slabs, groups, (int64_t)slabs * n * 3, (int64_t)groups * slabs};
+}
+
 struct BatchTotals {
   int n_scenes, n_items, n_total, n_rows;   // rows = packed rows (sum of pad64(n_s))
-  int64_t ws_floats, u_doubles;
+  int64_t ws_floats, u_doubles;             // sums of SceneGeom::ws (floats in the fp32 plan) and ::u
 };
 
 // Validates host offsets (offsets[0] == 0, non-decreasing) and sums the plan's sizes. Returns 0 or NBD_E_*.
-int batch_totals(const int* offsets, int n_scenes, BatchTotals* t) {
+template <class Geom>
+int batch_totals(const int* offsets, int n_scenes, BatchTotals* t, Geom geom) {
   if (!offsets || n_scenes <= 0 || offsets[0] != 0) return NBD_E_BADARG;
   int64_t items = 0, rows = 0, ws = 0, ud = 0;
   for (int s = 0; s < n_scenes; ++s) {
     const int n = offsets[s + 1] - offsets[s];
     if (offsets[s + 1] < offsets[s] || offsets[s + 1] < 0) return NBD_E_BADARG;
     if (n == 0) continue;
-    const int slabs = scene_slabs(n), groups = ceil_div(n, kTgtPerWG);
-    items += (int64_t)groups * slabs;
+    const SceneGeom g = geom(n);
+    items += (int64_t)g.groups * g.slabs;
     rows += (int64_t)ceil_div(n, kChunk) * kChunk;
-    ws += (int64_t)slabs * n * 3;
-    ud += (int64_t)groups * slabs;
+    ws += g.ws;
+    ud += g.u;
   }
   if (items > INT_MAX || rows > INT_MAX / 4 || ws > INT_MAX || ud > INT_MAX) return NBD_E_UNSUPPORTED;
   t->n_scenes = n_scenes; t->n_items = (int)items; t->n_total = offsets[n_scenes]; t->n_rows = (int)rows;
   t->ws_floats = ws; t->u_doubles = ud;
   return 0;
+}
+
+inline int batch_totals(const int* offsets, int n_scenes, BatchTotals* t) {
+  return batch_totals(offsets, n_scenes, t, scene_geom_f32);
 }
 
 // plan layout (int32): items int4[n_items] | scenes SceneRec[n_scenes] | row_scene int[n_rows]
@@ -88,12 +113,52 @@ __device__ __forceinline__ SceneRec load_scene(const SceneRec* scenes, int s) {
   return SceneRec{a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
 }
 
+// Writes the plan of the totals t (batch_totals with the same geom) into the host buffer `plan`, plan_bytes_of(t) bytes.
+template <class Geom>
+void batch_plan_fill(const int* offsets, int n_scenes, const BatchTotals& t, void* plan, Geom geom) {
+  std::vector<int> items;             // (scene, group, slab, chunks per wave) before ordering
+  items.reserve((size_t)t.n_items * 4);
+  std::vector<SceneRec> scenes(n_scenes);
+  std::vector<int> rows((size_t)t.n_rows);
+  int poff = 0, ws_off = 0, u_off = 0;
+  for (int s = 0; s < n_scenes; ++s) {
+    SceneRec& r = scenes[s];
+    r.off = offsets[s]; r.n = offsets[s + 1] - offsets[s]; r.poff = poff; r.ws_off = ws_off; r.u_off = u_off;
+    const SceneGeom g = r.n > 0 ? geom(r.n) : SceneGeom{0, 0, 0, 0};
+    r.slabs = g.slabs;
+    r.n_chunks = ceil_div(r.n, kChunk);
+    r.groups = g.groups;
+    const int cpw = r.n > 0 ? ceil_div(r.n_chunks, r.slabs * kWaves) : 0;
+    for (int grp = 0; grp < r.groups; ++grp)
+      for (int k = 0; k < r.slabs; ++k) items.insert(items.end(), {s, grp, k, cpw});
+    for (int i = 0; i < r.n_chunks * kChunk; ++i) rows[(size_t)poff + i] = s;
+    poff += r.n_chunks * kChunk; ws_off += (int)g.ws; u_off += (int)g.u;
+  }
+  // dispatch order: longest items first (a stable order of the WORK; no sum depends on it)
+  std::vector<int> order(t.n_items);
+  for (int i = 0; i < t.n_items; ++i) order[i] = i;
+  std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return items[4 * a + 3] > items[4 * b + 3]; });
+  int* out = static_cast<int*>(plan);
+  for (int i = 0; i < t.n_items; ++i) {
+    const int* src = &items[4 * order[i]];
+    out[4 * i] = src[0]; out[4 * i + 1] = src[1]; out[4 * i + 2] = src[2]; out[4 * i + 3] = 0;
+  }
+  memcpy(out + 4 * (size_t)t.n_items, scenes.data(), scenes.size() * sizeof(SceneRec));
+  memcpy(reinterpret_cast<char*>(out + 4 * (size_t)t.n_items) + scenes.size() * sizeof(SceneRec), rows.data(),
+         rows.size() * sizeof(int));
+}
+
 // common argument checks of the launching entry points; fills t
-int batch_prologue(const int* offsets, int n_scenes, const void* plan, size_t plan_bytes, BatchTotals* t) {
-  int rc = batch_totals(offsets, n_scenes, t);
+template <class Geom>
+int batch_prologue(const int* offsets, int n_scenes, const void* plan, size_t plan_bytes, BatchTotals* t, Geom geom) {
+  int rc = batch_totals(offsets, n_scenes, t, geom);
   if (rc) return rc;
   if (!plan || misaligned16(plan) || plan_bytes != plan_bytes_of(*t)) return NBD_E_BADARG;
   return 0;
+}
+
+inline int batch_prologue(const int* offsets, int n_scenes, const void* plan, size_t plan_bytes, BatchTotals* t) {
+  return batch_prologue(offsets, n_scenes, plan, plan_bytes, t, scene_geom_f32);
 }
 
 }  // namespace

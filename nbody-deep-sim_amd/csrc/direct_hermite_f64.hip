@@ -28,7 +28,8 @@
 // The two O(N) kernels, the predictor, the corrector and the step constants are hermite_kernels.h's templates at
 // T = double: the step constants are the five doubles formed from dt, never rounded to fp32. The finishing kernels of the
 // diagnostics add their slabs with the same slab_order_sum.
-// rsqrt_f64, AccelJerkPair, walk_f64 and plan_f64 live in hermite_f64_kernels.h, shared with direct_hermite_block_f64.hip.
+// rsqrt_f64, the pair functors, the bodies of the finishing kernels, walk_f64 and plan_f64 live in hermite_f64_kernels.h,
+// shared with direct_hermite_block_f64.hip and direct_batch_hermite_f64.hip.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -38,61 +39,6 @@
 #include "hermite_kernels.h"
 
 namespace {
-
-constexpr int kSumThreads = 1024;                // the one-workgroup sums (energy_finish): 16 waves
-constexpr int kSumWaves = kSumThreads / 64;
-
-// ---- the pair functors of the diagnostics (AccelJerkPair and what a functor is: hermite_f64_kernels.h)
-
-// u_i = sum_{j != i} m_j (|r_ij|^2 + eps^2)^(-1/2): potential_pair (direct_kernels.h) in fp64. The i == j term is
-// m_i / eps, never a zero: the chunk that holds the group's own indices is always walked MASKED.
-struct PotentialPair {
-  static constexpr bool kVel = false;
-  static constexpr int kOut = 1;
-  double xi, yi, zi, e2, u;
-  int i, n;
-
-  __device__ __forceinline__ PotentialPair(const d4 tp, double eps2, int i_, int n_)
-      : xi(tp.x), yi(tp.y), zi(tp.z), e2(eps2), u(0.0), i(i_), n(n_) {}
-
-  template <bool MASKED>
-  __device__ __forceinline__ void pair(const d4 p, const d4, int j) {
-    const double dx = p.x - xi, dy = p.y - yi, dz = p.z - zi;
-    double r2 = __builtin_fma(dx, dx, e2);
-    r2 = __builtin_fma(dy, dy, r2);
-    r2 = __builtin_fma(dz, dz, r2);
-    double s = rsqrt_f64(r2);
-    if (MASKED) s = (j < n && j != i) ? s : 0.0;
-    u = __builtin_fma(p.w, s, u);
-  }
-
-  __device__ __forceinline__ double out(int) const { return u; }
-};
-
-// u_i = sum_{j > i} m_j / (|r_ij| + eps), the reference's convention (energy_pair, direct_kernels.h): the square root and
-// the quotient are the compiler's fp64 expansions (correctly rounded; |r| = 0 is an ordinary input to them). Always by
-// index (j > i and j < n): the kernel walks it MASKED in every chunk.
-struct EnergyPair {
-  static constexpr bool kVel = false;
-  static constexpr int kOut = 1;
-  double xi, yi, zi, soft, u;
-  int i, n;
-
-  __device__ __forceinline__ EnergyPair(const d4 tp, double soft_, int i_, int n_)
-      : xi(tp.x), yi(tp.y), zi(tp.z), soft(soft_), u(0.0), i(i_), n(n_) {}
-
-  template <bool MASKED>
-  __device__ __forceinline__ void pair(const d4 p, const d4, int j) {
-    const double dx = p.x - xi, dy = p.y - yi, dz = p.z - zi;
-    double d2 = dx * dx;
-    d2 = __builtin_fma(dy, dy, d2);
-    d2 = __builtin_fma(dz, dz, d2);
-    const double t = p.w / (__builtin_sqrt(d2) + soft);
-    u += (j > i && j < n) ? t : 0.0;
-  }
-
-  __device__ __forceinline__ double out(int) const { return u; }
-};
 
 // Acceleration + jerk of all n bodies under all n bodies: grid = (groups of 64 targets, slabs), the n_chunks source chunks
 // spread over all slabs x 4 waves to within one (cpw_q each, the first cpw_r waves one more). out: double[slab][6][n].
@@ -142,60 +88,22 @@ __global__ __launch_bounds__(64 * kWaves) void energy_f64_kernel(const d4* __res
            out + (size_t)blockIdx.y * n + t_base, (size_t)n, min(kTgtF64, n - t_base));
 }
 
-// phi[i] = -G (slab 0 + slab 1 + ...) in slab order (0 - G sum: a body without partners gets +0)
+// phi[i] = potential_finish_f64 of body i
 __global__ __launch_bounds__(256) void potential_finish_f64_kernel(const double* __restrict__ slabs, int n_slabs, int n,
                                                                    double g, double* __restrict__ phi) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
-  double sum;
-  slab_order_sum<1>(slabs, n_slabs, (size_t)n, (size_t)i, &sum);
-  phi[i] = 0.0 - g * sum;
+  phi[i] = potential_finish_f64(slabs, n_slabs, n, i, g);
 }
 
-// {U, K} = {-G sum_i m_i u_i, sum_i 1/2 m_i |v_i|^2}, u_i = the slabs in slab order: one workgroup, thread t over the
-// bodies t, t + 1024, ... in index order, then a shuffle tree per wave and the 16 wave sums in wave order.
+// {U, K} of the one system: one workgroup
 __global__ __launch_bounds__(kSumThreads) void energy_finish_f64_kernel(const double* __restrict__ slabs, int n_slabs,
                                                                         int n, const d4* __restrict__ posd,
                                                                         const double* __restrict__ vel, double g,
                                                                         double* __restrict__ out_uk) {
   __shared__ double red[2][kSumWaves];
-  double a[2] = {0.0, 0.0};
-  for (int i = threadIdx.x; i < n; i += kSumThreads) {
-    double u;
-    slab_order_sum<1>(slabs, n_slabs, (size_t)n, (size_t)i, &u);
-    const double m = posd[i].w;
-    const double vx = vel[3 * (size_t)i], vy = vel[3 * (size_t)i + 1], vz = vel[3 * (size_t)i + 2];
-    a[0] += m * u;
-    a[1] += 0.5 * m * ((vx * vx + vy * vy) + vz * vz);
-  }
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int q = 0; q < 2; ++q) {
-    for (int off = 32; off > 0; off >>= 1) a[q] += __shfl_down(a[q], off);
-    if (lane == 0) red[q][wave] = a[q];
-  }
-  __syncthreads();
-  if (threadIdx.x < 2) {
-    double s = red[threadIdx.x][0];
-    for (int w = 1; w < kSumWaves; ++w) s += red[threadIdx.x][w];
-    out_uk[threadIdx.x] = threadIdx.x == 0 ? 0.0 - g * s : s;
-  }
+  energy_finish_f64(slabs, n_slabs, n, posd, vel, g, out_uk, red);
 }
-
-// A body of the fp64 state for invariants_body (direct_kernels.h)
-struct F64State {
-  const double* __restrict__ pos;
-  const double* __restrict__ vel;
-  const double* __restrict__ mass;
-  __device__ __forceinline__ void operator()(int i, double& m, double* x, double* v) const {
-    m = mass[i];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      x[k] = pos[3 * (size_t)i + k];
-      v[k] = vel[3 * (size_t)i + k];
-    }
-  }
-};
 
 __global__ __launch_bounds__(kInvThreads) void invariants_state_f64_kernel(const double* __restrict__ pos,
                                                                            const double* __restrict__ vel,

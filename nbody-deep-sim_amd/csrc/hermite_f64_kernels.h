@@ -1,9 +1,12 @@
 // hermite_f64_kernels.h -- what the double-precision Hermite translation units share (direct_hermite_f64.hip: all targets,
-// shared timestep, and the diagnostics; direct_hermite_block_f64.hip: an active list of targets, block timesteps): the
-// packed-row type and its alignment checks, the reciprocal square root (rsqrt_f64), the acceleration-plus-jerk pair functor
-// (AccelJerkPair), the wave body that walks the source chunks with a functor (walk_f64) and the geometry of a pair launch
-// (F64Plan, plan_f64). As in hermite_kernels.h there is one copy of every rounded operation: a block step whose active
-// list is every body has the shared step's bits because both kernels are a prologue and a call of the same walk_f64.
+// shared timestep, and the diagnostics; direct_hermite_block_f64.hip: an active list of targets, block timesteps;
+// direct_batch_hermite_f64.hip: many independent systems, shared timestep per system, and their diagnostics): the
+// packed-row type and its alignment checks, the reciprocal square root (rsqrt_f64), the pair functors (AccelJerkPair:
+// acceleration plus jerk; PotentialPair, EnergyPair: the diagnostics), the finishing sums of the diagnostics
+// (potential_finish_f64, energy_finish_f64, F64State), the wave body that walks the source chunks with a functor
+// (walk_f64) and the geometry of a pair launch (F64Plan, plan_f64). As in hermite_kernels.h there is one copy of every
+// rounded operation: a block step whose active list is every body, or a scene of a batch, has the shared step's bits
+// because the kernels are a prologue and a call of the same walk_f64.
 // The definitions sit in an anonymous namespace: every translation unit that includes this file gets its own inlined copies.
 #pragma once
 #include "direct_kernels.h"
@@ -82,6 +85,115 @@ struct AccelJerkPair {
   }
 
   __device__ __forceinline__ double out(int k) const { return k < 3 ? acc[k] : acc[k] - 3.0 * acc[k + 3]; }
+};
+
+// ---- the pair functors of the diagnostics
+
+// u_i = sum_{j != i} m_j (|r_ij|^2 + eps^2)^(-1/2): potential_pair (direct_kernels.h) in fp64. The i == j term is
+// m_i / eps, never a zero: the chunk that holds the group's own indices is always walked MASKED.
+struct PotentialPair {
+  static constexpr bool kVel = false;
+  static constexpr int kOut = 1;
+  double xi, yi, zi, e2, u;
+  int i, n;
+
+  __device__ __forceinline__ PotentialPair(const d4 tp, double eps2, int i_, int n_)
+      : xi(tp.x), yi(tp.y), zi(tp.z), e2(eps2), u(0.0), i(i_), n(n_) {}
+
+  template <bool MASKED>
+  __device__ __forceinline__ void pair(const d4 p, const d4, int j) {
+    const double dx = p.x - xi, dy = p.y - yi, dz = p.z - zi;
+    double r2 = __builtin_fma(dx, dx, e2);
+    r2 = __builtin_fma(dy, dy, r2);
+    r2 = __builtin_fma(dz, dz, r2);
+    double s = rsqrt_f64(r2);
+    if (MASKED) s = (j < n && j != i) ? s : 0.0;
+    u = __builtin_fma(p.w, s, u);
+  }
+
+  __device__ __forceinline__ double out(int) const { return u; }
+};
+
+// u_i = sum_{j > i} m_j / (|r_ij| + eps), the reference's convention (energy_pair, direct_kernels.h): the square root and
+// the quotient are the compiler's fp64 expansions (correctly rounded; |r| = 0 is an ordinary input to them). Always by
+// index (j > i and j < n): the kernel walks it MASKED in every chunk.
+struct EnergyPair {
+  static constexpr bool kVel = false;
+  static constexpr int kOut = 1;
+  double xi, yi, zi, soft, u;
+  int i, n;
+
+  __device__ __forceinline__ EnergyPair(const d4 tp, double soft_, int i_, int n_)
+      : xi(tp.x), yi(tp.y), zi(tp.z), soft(soft_), u(0.0), i(i_), n(n_) {}
+
+  template <bool MASKED>
+  __device__ __forceinline__ void pair(const d4 p, const d4, int j) {
+    const double dx = p.x - xi, dy = p.y - yi, dz = p.z - zi;
+    double d2 = dx * dx;
+    d2 = __builtin_fma(dy, dy, d2);
+    d2 = __builtin_fma(dz, dz, d2);
+    const double t = p.w / (__builtin_sqrt(d2) + soft);
+    u += (j > i && j < n) ? t : 0.0;
+  }
+
+  __device__ __forceinline__ double out(int) const { return u; }
+};
+
+// ---- the finishing sums of the diagnostics: the bodies of direct_hermite_f64.hip's finishing kernels (one system) and of
+// direct_batch_hermite_f64.hip's (one scene of a batch)
+
+constexpr int kSumThreads = 1024;                // the one-workgroup sums (energy_finish_f64): 16 waves
+constexpr int kSumWaves = kSumThreads / 64;
+
+// phi_i = -G (slab 0 + slab 1 + ...) in slab order (0 - G sum: a body without partners gets +0)
+__device__ __forceinline__ double potential_finish_f64(const double* __restrict__ slabs, int n_slabs, int n, int i,
+                                                       double g) {
+  double sum;
+  slab_order_sum<1>(slabs, n_slabs, (size_t)n, (size_t)i, &sum);
+  return 0.0 - g * sum;
+}
+
+// {U, K} = {-G sum_i m_i u_i, sum_i 1/2 m_i |v_i|^2}, u_i = the slabs in slab order: one workgroup of kSumThreads, thread
+// t over the bodies t, t + 1024, ... in index order, then a shuffle tree per wave and the 16 wave sums in wave order.
+__device__ __forceinline__ void energy_finish_f64(const double* __restrict__ slabs, int n_slabs, int n,
+                                                  const d4* __restrict__ posd, const double* __restrict__ vel, double g,
+                                                  double* __restrict__ out_uk, double (*red)[kSumWaves]) {
+  double a[2] = {0.0, 0.0};
+  for (int i = threadIdx.x; i < n; i += kSumThreads) {
+    double u;
+    slab_order_sum<1>(slabs, n_slabs, (size_t)n, (size_t)i, &u);
+    const double m = posd[i].w;
+    const double vx = vel[3 * (size_t)i], vy = vel[3 * (size_t)i + 1], vz = vel[3 * (size_t)i + 2];
+    a[0] += m * u;
+    a[1] += 0.5 * m * ((vx * vx + vy * vy) + vz * vz);
+  }
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int q = 0; q < 2; ++q) {
+    for (int off = 32; off > 0; off >>= 1) a[q] += __shfl_down(a[q], off);
+    if (lane == 0) red[q][wave] = a[q];
+  }
+  __syncthreads();
+  if (threadIdx.x < 2) {
+    double s = red[threadIdx.x][0];
+    for (int w = 1; w < kSumWaves; ++w) s += red[threadIdx.x][w];
+    out_uk[threadIdx.x] = threadIdx.x == 0 ? 0.0 - g * s : s;
+  }
+}
+
+// A body of the fp64 state for invariants_body (direct_kernels.h)
+struct F64State {
+  const double* __restrict__ pos;
+  const double* __restrict__ vel;
+  const double* __restrict__ mass;
+  __device__ __forceinline__ void operator()(int i, double& m, double* x, double* v) const {
+    m = mass[i];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      x[k] = pos[3 * (size_t)i + k];
+      v[k] = vel[3 * (size_t)i + k];
+    }
+  }
 };
 
 // LDS of a workgroup, in 16-byte quads: [wave][buffer][pos (| vel)][128]

@@ -34,6 +34,10 @@ softening the force uses and the conserved quantities formed from it (`Invariant
 Eighth addition: `compute_accelerations()` is differentiable. When torch records a graph and `positions` or `masses`
 requires grad, its result carries a grad_fn whose backward is a HIP kernel (csrc/direct_grad.hip; `nbd.autograd.direct_accel`
 is the function form; DESIGN.md K-VJP), as the reference's nine lines of torch do by themselves. Otherwise nothing changes.
+
+Ninth addition: `BatchedSimulator(integrator="hermite", dtype=torch.float64)`, the float64 Hermite step on every scene of
+a batch with one set of launches, each scene bit-identical to `HermiteSimulator(dtype=torch.float64)` of that scene alone,
+and run() in captured chunks (csrc/direct_batch_hermite_f64.hip). The default stays float32.
 """
 from __future__ import annotations
 
@@ -1009,26 +1013,27 @@ def _per_scene(x, n_scenes: int, name: str) -> list:
     return vals
 
 
-def _batch_chunk_layout(m: int, n: int, n_scenes: int):
-    """A batch's chunk buffer, in bytes: ring (m, 3, n, 3) fp32 | energies (m, S, 2) fp64 from the next multiple of 16
-    -> (ring bytes, energies' offset, size)."""
-    ring_b = m * 9 * n * 4
+def _batch_chunk_layout(m: int, n: int, n_scenes: int, dtype=torch.float32):
+    """A batch's chunk buffer, in bytes: ring (m, 3, n, 3) of the state's dtype | energies (m, S, 2) fp64 from the next
+    multiple of 16 -> (ring bytes, energies' offset, size)."""
+    ring_b = m * 9 * n * dtype.itemsize
     uk_at = (ring_b + 15) // 16 * 16
     return ring_b, uk_at, uk_at + m * n_scenes * 16
 
 
-def _batch_chunk_views(buf, m: int, n: int, n_scenes: int):
+def _batch_chunk_views(buf, m: int, n: int, n_scenes: int, dtype=torch.float32):
     """(ring, energies) views of a chunk buffer, on the device or in its host copy."""
-    ring_b, uk_at, size = _batch_chunk_layout(m, n, n_scenes)
-    return (buf[:ring_b].view(torch.float32).view(m, 3, n, 3),
+    ring_b, uk_at, size = _batch_chunk_layout(m, n, n_scenes, dtype)
+    return (buf[:ring_b].view(dtype).view(m, 3, n, 3),
             buf[uk_at:size].view(torch.float64).view(m, n_scenes, 2))
 
 
-def _batch_states(host, m: int, offsets: list, calc_energy: bool, first: int, t_steps, out, inv=None):
+def _batch_states(host, m: int, offsets: list, calc_energy: bool, first: int, t_steps, out, inv=None,
+                  dtype=torch.float32):
     """Append m states per scene to `out` from a host copy of a chunk buffer (views into it, no copies). inv: a host copy
     of the chunk's invariant rows (m, S, 16), or None."""
     n_scenes = len(offsets) - 1
-    ring, uk = _batch_chunk_views(host, m, offsets[-1], n_scenes)
+    ring, uk = _batch_chunk_views(host, m, offsets[-1], n_scenes, dtype)
     uk = uk.tolist() if calc_energy else None
     inv = inv.tolist() if inv is not None else None
     for s_ in range(m):
@@ -1039,6 +1044,119 @@ def _batch_states(host, m: int, offsets: list, calc_energy: bool, first: int, t_
                                           velocities=ring[s_, 1, lo:hi], accelerations=ring[s_, 2, lo:hi],
                                           u_energy=u, k_energy=k,
                                           invariants=Invariants.from_row(inv[s_][i]) if inv is not None else None))
+
+
+class _BatchFloat32:
+    """The float32 number format of BatchedSimulator: every allocation and nbd.direct call of a batch `s` that depends on
+    the format (the object keeps no state of its own); `_BatchFloat64` has the same methods. Packed sources: `s._posm` =
+    {x, y, z, m}; the Hermite calls keep their packed velocities inside `s._hws`, allocated on first use. Parameter table
+    `s._params`: rows g, eps^2, eps, dt / 2, dt, as torch forms the fp32 scalars from the Python doubles
+    (simulation.py:82,88,164), then the Hermite step constants dt, dt/2, dt^2/2, dt^3/6, dt^2/12, each formed in double
+    and rounded once (as HermiteSimulator's)."""
+
+    dtype = torch.float32
+    integrators = ("leapfrog", "euler", "hermite")
+
+    def scratch(self, s):
+        s._plan = direct.BatchPlan(s.sizes, s.device)
+        s._posm = s._plan.alloc_posm()
+        s._ws = s._plan.workspace()
+        s._params = torch.zeros((10, s.n_scenes), dtype=torch.float32, device=s.device)
+        s._hws = None
+
+    def param_rows(self, g, eps, dt) -> list:
+        f32 = direct.f32
+        return [[f32(x) for x in g], [f32(e ** 2) for e in eps], [f32(e) for e in eps],
+                [f32(0.5 * d) for d in dt], [f32(d) for d in dt],
+                [f32(d) for d in dt], [f32(0.5 * d) for d in dt], [f32(0.5 * d * d) for d in dt],
+                [f32(d * d * d / 6.0) for d in dt], [f32(d * d / 12.0) for d in dt]]
+
+    def _hermite_ws(self, s) -> torch.Tensor:
+        if s._hws is None:
+            s._hws = s._plan.hermite_workspace()
+        return s._hws
+
+    def accel(self, s):
+        acc = torch.zeros((s.n, 3), dtype=torch.float32, device=s.device)
+        P = s._params
+        direct.batch_accel(s._plan, s.positions, s.masses, P[1], P[0], acc, s._posm, s._ws)
+        return acc
+
+    def accel_jerk(self, s, acc, jerk):
+        P = s._params
+        direct.batch_accel_jerk(s._plan, s.positions, s.velocities, s.masses, P[1], P[0], acc, jerk, s._posm,
+                                self._hermite_ws(s))
+
+    def hermite_step(self, s, cur, new):
+        P = s._params
+        direct.batch_hermite_step(s._plan, s.positions, s.velocities, cur[0], cur[1], new[0], new[1], s.masses, P[5:10],
+                                  P[1], P[0], s._posm, s._hws)
+
+    def pack(self, s):
+        direct.batch_pack_posm(s._plan, s.positions, s.masses, s._posm)
+
+    def energies(self, s, out_uk):
+        P = s._params
+        direct.batch_energies(s._plan, s._posm, s.velocities, P[2], P[0], out_uk, s._ws)
+
+    def potentials(self, s, phi):
+        P = s._params
+        return direct.batch_potential(s._plan, s._posm, P[1], P[0], phi, s._ws)
+
+    def invariants(self, s, phi, out_rows):
+        return direct.batch_invariants(s._plan, s._posm, s.velocities, phi, out_rows)
+
+    snapshot = staticmethod(direct.snapshot)
+
+
+class _BatchFloat64:
+    """The float64 number format of BatchedSimulator (csrc/direct_batch_hermite_f64.hip): `_BatchFloat32`'s methods over the
+    float64 entries, Hermite only; nothing of the fp32 paths is allocated or launched. Packed sources: `s._posd` =
+    {x, y, z, m}, `s._veld` = {vx, vy, vz, 0}; ONE workspace `s._ws` for the step and the diagnostics. Parameter table
+    `s._params`: the doubles G, eps^2, eps and the five step constants, formed by the expressions of
+    HermiteSimulator(dtype=torch.float64)'s path (direct.batch_f64_params): the kernels read every per-scene scalar from
+    it, which is what lets run() capture the float64 step."""
+
+    dtype = torch.float64
+    integrators = ("hermite",)
+
+    def scratch(self, s):
+        s._plan = direct.BatchPlan(s.sizes, s.device, dtype=torch.float64)
+        s._posd = direct.alloc_batch_rows_f64(s._plan)
+        s._veld = direct.alloc_batch_rows_f64(s._plan)
+        s._ws = s._plan.workspace()
+        s._params = torch.zeros((direct.BATCH_F64_PARAM_ROWS, s.n_scenes), dtype=torch.float64, device=s.device)
+
+    def param_rows(self, g, eps, dt) -> list:
+        return direct.batch_f64_params(g, eps, dt)
+
+    def accel(self, s):
+        return s.compute_accelerations_and_jerks()[0]
+
+    def accel_jerk(self, s, acc, jerk):
+        direct.batch_accel_jerk_f64(s._plan, s.positions, s.velocities, s.masses, s._params, acc, jerk, s._posd, s._veld,
+                                    s._ws)
+
+    def hermite_step(self, s, cur, new):
+        direct.batch_hermite_step_f64(s._plan, s.positions, s.velocities, cur[0], cur[1], new[0], new[1], s.masses,
+                                      s._params, s._posd, s._veld, s._ws)
+
+    def pack(self, s):
+        direct.batch_pack_f64(s._plan, s.positions, s.velocities, s.masses, s._posd, s._veld)
+
+    def energies(self, s, out_uk):
+        direct.batch_energies_f64(s._plan, s._posd, s.velocities, s._params, out_uk, s._ws)
+
+    def potentials(self, s, phi):
+        return direct.batch_potential_f64(s._plan, s._posd, s._params, phi, s._ws)
+
+    def invariants(self, s, phi, out_rows):
+        return direct.batch_invariants_state_f64(s._plan, s.positions, s.velocities, s.masses, phi, out_rows)
+
+    snapshot = staticmethod(direct.snapshot_f64)
+
+
+_BATCH_FORMATS = {fmt.dtype: fmt for fmt in (_BatchFloat32(), _BatchFloat64())}
 
 
 class BatchedSimulator(_ChunkedRun):
@@ -1053,14 +1171,38 @@ class BatchedSimulator(_ChunkedRun):
     (csrc/direct_batch_hermite.hip): `jerks` (N_total, 3) is public next to `accelerations`, both rebound by step(), and
     each scene's positions, velocities, accelerations and jerks are bit-identical to a HermiteSimulator of that scene
     alone. `jerks` is None for leapfrog and Euler. The integrator may switch between leapfrog and Euler after
-    construction, but not into or out of Hermite."""
+    construction, but not into or out of Hermite.
+
+    With `dtype=torch.float64` (integrator="hermite" only; csrc/direct_batch_hermite_f64.hip) every
+    scene runs HermiteSimulator(dtype=torch.float64)'s step: positions, velocities, masses, accelerations and jerks are
+    float64 device tensors (the inputs are converted directly, not through float32), each scene's g_const, softening ** 2,
+    dt and step constants reach the kernels as doubles through a device table, and step(), the compute_*() methods and
+    run() -- its states, energies and invariants -- are float64 end to end, each scene bit-identical to a
+    HermiteSimulator(dtype=torch.float64) of that scene alone. Because the table, not a kernel argument, carries the
+    scalars, run() captures its chunks in this mode too. The default stays float32 and takes the paths it took."""
 
     RING_BYTES = 64 << 20                                # the eager run()'s staging cap, per chunk of states
 
+    @staticmethod
+    def _check_dtype(dtype, integrator):
+        if dtype not in _BATCH_FORMATS:
+            raise ValueError(f"BatchedSimulator: dtype must be torch.float32 or torch.float64, got {dtype!r}")
+        if integrator not in _BATCH_FORMATS[dtype].integrators:
+            raise ValueError(f"BatchedSimulator: dtype={dtype} has integrator='hermite' only (there is no float64 "
+                             f"leapfrog or Euler), got {integrator!r}")
+
     def __init__(self, *, systems, integrator: str = "leapfrog", g_const=1.0, softening=0.1, dt=0.01,
-                 calc_energy: bool = True, device: str = None, calc_invariants: bool = False):
+                 calc_energy: bool = True, device: str = None, calc_invariants: bool = False, **format_kw):
+        # format_kw: `dtype` (default torch.float32), the one keyword of the number format. As in BlockHermiteSimulator it
+        # is not a named parameter: HermiteSimulator's signature stays the only one that spells it (tested); any other
+        # name is refused as an unknown keyword is.
+        dtype = format_kw.pop("dtype", torch.float32)
+        if format_kw:
+            raise TypeError(f"BatchedSimulator.__init__() got an unexpected keyword argument {next(iter(format_kw))!r}")
         if integrator not in ("leapfrog", "euler", "hermite"):
             raise ValueError("integrator must be 'leapfrog', 'euler' or 'hermite'")
+        self._check_dtype(dtype, integrator)             # before anything is resolved, allocated or launched
+        self._fmt = _BATCH_FORMATS[dtype]                # the only place the format is chosen
         self.device = _resolve_device(device)
         _lib.lib()
         systems = list(systems)
@@ -1072,7 +1214,7 @@ class BatchedSimulator(_ChunkedRun):
         self.n_scenes = len(systems)
         pos, vel, mass = [], [], []
         for i, sysm in enumerate(systems):
-            p, v, m = (_to_device(x, self.device, torch.float32) for x in sysm)
+            p, v, m = (_to_device(x, self.device, dtype) for x in sysm)
             n = p.shape[0]
             if p.shape != (n, 3) or v.shape != (n, 3) or m.shape != (n,):
                 raise ValueError(f"scene {i}: positions/velocities must be (n,3) and masses (n,)")
@@ -1082,15 +1224,11 @@ class BatchedSimulator(_ChunkedRun):
         self.velocities = torch.cat(vel).contiguous()
         self.masses = torch.cat(mass).contiguous()
         self.n = self.positions.shape[0]
-        self._plan = direct.BatchPlan(self.sizes, self.device)
+        self._fmt.scratch(self)                          # the plan, the packed rows, the workspace, the parameter table
         self.offsets = torch.tensor(self._plan.offsets, dtype=torch.int64)
         self.g_const, self.softening, self.dt = g_const, softening, dt
-        self._posm = self._plan.alloc_posm()
-        self._ws = self._plan.workspace()
-        self._params = torch.zeros((10, self.n_scenes), dtype=torch.float32, device=self.device)
         self._params_key = None
         self._hermite = integrator == "hermite"          # fixed at construction: the state carries jerks or not
-        self._hws = None
         self._phi = None
         self.jerks = None
         if self._hermite:
@@ -1101,21 +1239,16 @@ class BatchedSimulator(_ChunkedRun):
 
     # ------------------------------------------------------------------ per-scene parameters
     def _sync_params(self):
-        """Rows g, eps^2, eps, dt / 2, dt of the device parameter table, as torch forms the fp32 scalars from the
-        Python doubles (simulation.py:82,88,164), then the Hermite step constants dt, dt/2, dt^2/2, dt^3/6, dt^2/12, each
-        formed in double and rounded once (as HermiteSimulator's); rewritten IN PLACE when an attribute changed
-        (captured graphs keep reading the same buffer). Returns the per-scene values (the graph cache key)."""
+        """The device parameter table in the format's own rows (`_BatchFloat32`, `_BatchFloat64`), rewritten IN PLACE when
+        an attribute changed (captured graphs keep reading the same buffer). Returns the per-scene values (the graph
+        cache key)."""
         S = self.n_scenes
         g = _per_scene(self.g_const, S, "g_const")
         eps = _per_scene(self.softening, S, "softening")
         dt = _per_scene(self.dt, S, "dt")
         key = (tuple(g), tuple(eps), tuple(dt))
         if key != self._params_key:
-            rows = [[direct.f32(x) for x in g], [direct.f32(e ** 2) for e in eps], [direct.f32(e) for e in eps],
-                    [direct.f32(0.5 * d) for d in dt], [direct.f32(d) for d in dt],
-                    [direct.f32(d) for d in dt], [direct.f32(0.5 * d) for d in dt], [direct.f32(0.5 * d * d) for d in dt],
-                    [direct.f32(d * d * d / 6.0) for d in dt], [direct.f32(d * d / 12.0) for d in dt]]
-            self._params.copy_(torch.tensor(rows, dtype=torch.float32))
+            self._params.copy_(torch.tensor(self._fmt.param_rows(g, eps, dt), dtype=self._fmt.dtype))
             self._params_key = key
         return key
 
@@ -1131,24 +1264,14 @@ class BatchedSimulator(_ChunkedRun):
     def compute_accelerations(self) -> torch.Tensor:
         """Force of every scene on its own bodies -> new (N_total, 3) tensor (simulation.py:71-89 per scene)."""
         self._sync_params()
-        acc = torch.zeros((self.n, 3), dtype=torch.float32, device=self.device)
-        P = self._params
-        direct.batch_accel(self._plan, self.positions, self.masses, P[1], P[0], acc, self._posm, self._ws)
-        return acc
-
-    def _hermite_ws(self) -> torch.Tensor:
-        if self._hws is None:
-            self._hws = self._plan.hermite_workspace()
-        return self._hws
+        return self._fmt.accel(self)
 
     def compute_accelerations_and_jerks(self):
         """(a, j) of every scene's current state as new (N_total, 3) tensors (HermiteSimulator's per scene)."""
         self._sync_params()
-        acc = torch.zeros((self.n, 3), dtype=torch.float32, device=self.device)
-        jerk = torch.zeros((self.n, 3), dtype=torch.float32, device=self.device)
-        P = self._params
-        direct.batch_accel_jerk(self._plan, self.positions, self.velocities, self.masses, P[1], P[0], acc, jerk,
-                                self._posm, self._hermite_ws())
+        acc = torch.zeros((self.n, 3), dtype=self._fmt.dtype, device=self.device)
+        jerk = torch.zeros((self.n, 3), dtype=self._fmt.dtype, device=self.device)
+        self._fmt.accel_jerk(self, acc, jerk)
         return acc, jerk
 
     def _check_integrator(self):
@@ -1157,13 +1280,12 @@ class BatchedSimulator(_ChunkedRun):
                              "construction (the state carries jerks only for Hermite); build a new simulator")
 
     def _energies_into(self, out_uk):
-        P = self._params
-        direct.batch_energies(self._plan, self._posm, self.velocities, P[2], P[0], out_uk, self._ws)
+        self._fmt.energies(self, out_uk)
 
     def compute_energies(self):
         """(u, k): two lists of S Python floats (simulation.py:91-115 per scene)."""
         self._sync_params()
-        direct.batch_pack_posm(self._plan, self.positions, self.masses, self._posm)
+        self._fmt.pack(self)
         uk = torch.empty((self.n_scenes, 2), dtype=torch.float64, device=self.device)
         self._energies_into(uk)
         uk = uk.cpu()
@@ -1171,37 +1293,35 @@ class BatchedSimulator(_ChunkedRun):
 
     # ------------------------------------------------------------------ consistent-potential diagnostics
     def _potentials_into(self, phi):
-        """phi (N_total,) float64 from _posm (already packed, parameters in sync), asynchronous."""
-        P = self._params
-        return direct.batch_potential(self._plan, self._posm, P[1], P[0], phi, self._ws)
+        """phi (N_total,) float64 from the packed sources (already packed, parameters in sync), asynchronous."""
+        return self._fmt.potentials(self, phi)
 
     def _invariants_into(self, out_rows):
-        """(S, 16) invariant rows of the state a step left (posm = its positions), asynchronous."""
+        """(S, 16) invariant rows of the state a step left (packed sources = its positions), asynchronous."""
         if self._phi is None:
             self._phi = torch.zeros((self.n,), dtype=torch.float64, device=self.device)
         self._potentials_into(self._phi)
-        direct.batch_invariants(self._plan, self._posm, self.velocities, self._phi, out_rows)
+        self._fmt.invariants(self, self._phi, out_rows)
 
     def compute_potentials(self) -> torch.Tensor:
         """Every body's potential under the bodies of its own scene, with the scene's softening and g_const -> new
         (N_total,) float64 device tensor in scene order (BaseSimulator.compute_potentials per scene, bit for bit)."""
         self._sync_params()
-        direct.batch_pack_posm(self._plan, self.positions, self.masses, self._posm)
+        self._fmt.pack(self)
         return self._potentials_into(torch.zeros((self.n,), dtype=torch.float64, device=self.device))
 
     def compute_invariants(self) -> list:
         """One Invariants per scene (BaseSimulator.compute_invariants per scene, bit for bit; zeros for an empty scene)."""
         phi = self.compute_potentials()
         rows = torch.zeros((self.n_scenes, direct.INVARIANT_ROW), dtype=torch.float64, device=self.device)
-        direct.batch_invariants(self._plan, self._posm, self.velocities, phi, rows)
+        self._fmt.invariants(self, phi, rows)
         return [Invariants.from_row(r) for r in rows.cpu().tolist()]
 
     def _step_into(self, cur, new):
         """One step from the carried arrays `cur` into `new` (lists in the order of `_carried`; may be the same)."""
         P = self._params
         if self._hermite:
-            direct.batch_hermite_step(self._plan, self.positions, self.velocities, cur[0], cur[1], new[0], new[1],
-                                      self.masses, P[5:10], P[1], P[0], self._posm, self._hws)
+            self._fmt.hermite_step(self, cur, new)
         elif self.integrator == "leapfrog":
             direct.batch_leapfrog_step(self._plan, self.positions, self.velocities, cur[0], new[0], self.masses,
                                        P[3], P[4], P[1], P[0], self._posm, self._ws)
@@ -1224,7 +1344,7 @@ class BatchedSimulator(_ChunkedRun):
 
     # ------------------------------------------------------------------ run()
     def _chunk_len(self) -> int:
-        return max(1, min(self.GRAPH_RUN_CHUNK, self.RING_BYTES // max(36 * self.n, 1)))
+        return max(1, min(self.GRAPH_RUN_CHUNK, self.RING_BYTES // max(9 * self._fmt.dtype.itemsize * self.n, 1)))
 
     def run(self, steps: int) -> list[list[SimulationState]]:
         """Run `steps` steps of every scene: S lists of reference-shaped SimulationState (simulation.py:117-146).
@@ -1237,7 +1357,7 @@ class BatchedSimulator(_ChunkedRun):
         self._check_integrator()
         if self.n == 0:
             uk = (0.0, 0.0) if self.calc_energy else (None, None)
-            empty = torch.zeros((0, 3), dtype=torch.float32)
+            empty = torch.zeros((0, 3), dtype=self._fmt.dtype)
             for i in range(self.n_scenes):
                 out[i] = [SimulationState(step=s, step_time=0.0, positions=empty, velocities=empty, accelerations=empty,
                                           u_energy=uk[0], k_energy=uk[1],
@@ -1254,9 +1374,9 @@ class BatchedSimulator(_ChunkedRun):
 
     def _chunk_buffers(self, m: int):
         """One device buffer = ring | energies (_batch_chunk_layout): ONE device->host copy per chunk."""
-        size = _batch_chunk_layout(m, self.n, self.n_scenes)[2]
+        size = _batch_chunk_layout(m, self.n, self.n_scenes, self._fmt.dtype)[2]
         buf = torch.empty(size, dtype=torch.uint8, device=self.device)
-        return (buf,) + _batch_chunk_views(buf, m, self.n, self.n_scenes)
+        return (buf,) + _batch_chunk_views(buf, m, self.n, self.n_scenes, self._fmt.dtype)
 
     def _inv_buffer(self, m: int):
         """The chunk's invariant rows (m, S, 16), a second device buffer next to ring | energies; None without the flag."""
@@ -1267,7 +1387,7 @@ class BatchedSimulator(_ChunkedRun):
     def _emit_states(self, host, m, first, t_steps, out):
         _batch_states(host[0], m, self.offsets.tolist(), self.calc_energy, first,
                       [t / self.n_scenes for t in t_steps], out,       # the batched step's GPU time, spread over S
-                      inv=host[1] if self.calc_invariants else None)
+                      inv=host[1] if self.calc_invariants else None, dtype=self._fmt.dtype)
 
     def _run_eager(self, steps: int, first: int, out):
         done = 0
@@ -1286,7 +1406,7 @@ class BatchedSimulator(_ChunkedRun):
                     self._energies_into(uk[s_])
                 if inv is not None:
                     self._invariants_into(inv[s_])
-                direct.snapshot(self.positions, self.velocities, self.accelerations, ring[s_])
+                self._fmt.snapshot(self.positions, self.velocities, self.accelerations, ring[s_])
             host = [buf.cpu()] + ([inv.cpu()] if inv is not None else [])
             self._emit_states(host, m, first + done, [a.elapsed_time(b) * 1e-3 for a, b in events], out)
             done += m
@@ -1306,5 +1426,5 @@ class BatchedSimulator(_ChunkedRun):
                     self._energies_into(uk[s_])
                 if inv is not None:
                     self._invariants_into(inv[s_])
-                direct.snapshot(self.positions, self.velocities, statics[0], ring[s_])
+                self._fmt.snapshot(self.positions, self.velocities, statics[0], ring[s_])
         return body, (buf,) + ((inv,) if inv is not None else ())

@@ -156,6 +156,7 @@ SIGNATURES = {
     "nbd_kick_f32": (c_int, [c_void_p, c_void_p, c_int, c_float, c_void_p]),
     "nbd_drift_f32": (c_int, [c_void_p, c_void_p, c_int, c_float, c_void_p]),
     "nbd_snapshot_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
+    "nbd_snapshot_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
     "nbd_step_workspace_bytes": (c_size_t, [c_int]),
     "nbd_step_workspace_pref_bytes": (c_size_t, [c_int]),
     "nbd_leapfrog_step_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
@@ -204,6 +205,23 @@ SIGNATURES = {
     "nbd_batch_hermite_step_f32": (c_int, [c_void_p, c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p,
                                            c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                            c_size_t, c_void_p]),
+    # --- double-precision Hermite per scene (csrc/direct_batch_hermite_f64.hip)
+    "nbd_batch_f64_plan": (c_int, [c_void_p, c_int, POINTER(c_int), POINTER(c_int), POINTER(c_size_t)]),
+    "nbd_batch_f64_workspace_bytes": (c_int, [c_void_p, c_int, POINTER(c_size_t)]),
+    "nbd_batch_f64_plan_fill": (c_int, [c_void_p, c_int, c_void_p, c_size_t]),
+    "nbd_batch_pack_f64": (c_int, [c_void_p, c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                   c_void_p]),
+    "nbd_batch_accel_jerk_f64": (c_int, [c_void_p, c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p,
+                                         c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "nbd_batch_hermite_step_f64": (c_int, [c_void_p, c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p,
+                                           c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
+                                           c_void_p]),
+    "nbd_batch_energies_f64": (c_int, [c_void_p, c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p,
+                                       c_void_p, c_size_t, c_void_p]),
+    "nbd_batch_potential_f64": (c_int, [c_void_p, c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p,
+                                        c_size_t, c_void_p]),
+    "nbd_batch_invariants_state_f64": (c_int, [c_void_p, c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p,
+                                               c_void_p, c_void_p, c_void_p]),
     # --- 4th-order Hermite integrator (csrc/direct_hermite.hip)
     "nbd_hermite_workspace_bytes": (c_size_t, [c_int]),
     "nbd_hermite_pack_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_double, c_void_p,

@@ -218,6 +218,17 @@ def snapshot(pos, vel, acc, out) -> None:
                                                _lib.current_stream(pos.device)), "nbd_snapshot_f32")
 
 
+def snapshot_f64(pos, vel, acc, out) -> None:
+    """snapshot of a float64 state: out (3, n, 3) float64 = [pos, vel, acc], one launch."""
+    n = pos.shape[0]
+    for t, nm in ((pos, "pos"), (vel, "vel"), (acc, "acc")):
+        _chk(t, (n, 3), nm, torch.float64)
+    _chk(out, (3, n, 3), "out", torch.float64)
+    with _lib.on_device(pos.device):
+        _lib.check(_lib.lib().nbd_snapshot_f64(pos.data_ptr(), vel.data_ptr(), acc.data_ptr(), n, out.data_ptr(),
+                                               _lib.current_stream(pos.device)), "nbd_snapshot_f64")
+
+
 def uniform_mass(mass: torch.Tensor):
     """The common mass as a Python float when every body has the same, finite, positive mass -- what
     nbd_leapfrog_step_uniform_f32 asks its caller to vouch for -- else None. One device read-back: call it once."""
@@ -880,23 +891,34 @@ def accel_jerk_active_f64(posd, veld, n: int, act, softening_sq: float, g_const:
 # ---------------------------------------------------------------- batched direct integrator (csrc/direct_batch.hip)
 class BatchPlan:
     """The host offsets of an ensemble of scenes and the device work list built from them (nbd_batch_plan /
-    nbd_batch_plan_fill): built once per set of scene sizes, passed to every batch_* call."""
+    nbd_batch_plan_fill): built once per set of scene sizes, passed to every batch_* call. dtype=torch.float64: the work
+    list of the batch_*_f64 calls instead (nbd_batch_f64_plan / nbd_batch_f64_plan_fill: groups of 64 targets, the
+    float64 step's slabs); `posm_rows` then counts the rows of posd / veld and `workspace_bytes` is the one workspace of
+    every float64 call. A plan serves the calls of its own dtype only."""
 
-    def __init__(self, sizes, device):
+    def __init__(self, sizes, device, dtype=torch.float32):
         sizes = [int(n) for n in sizes]
         if not sizes or min(sizes) < 0:
             raise _lib.NbdError("batch: need at least one scene and no negative size")
+        if dtype not in (torch.float32, F64):
+            raise _lib.NbdError(f"batch: dtype must be torch.float32 or torch.float64, got {dtype!r}")
+        self.dtype = dtype
         self.offsets = np.zeros(len(sizes) + 1, dtype=np.int32)
         np.cumsum(sizes, out=self.offsets[1:])
         self.n_scenes, self.n_total = len(sizes), int(self.offsets[-1])
         items, rows = ctypes.c_int(), ctypes.c_int()
         pb, wb = ctypes.c_size_t(), ctypes.c_size_t()
         L = _lib.lib()
-        _lib.check(L.nbd_batch_plan(self._off(), self.n_scenes, items, rows, pb, wb), "nbd_batch_plan")
+        if dtype == torch.float32:
+            _lib.check(L.nbd_batch_plan(self._off(), self.n_scenes, items, rows, pb, wb), "nbd_batch_plan")
+            fill, fill_name = L.nbd_batch_plan_fill, "nbd_batch_plan_fill"
+        else:
+            _lib.check(L.nbd_batch_f64_plan(self._off(), self.n_scenes, items, rows, pb), "nbd_batch_f64_plan")
+            _lib.check(L.nbd_batch_f64_workspace_bytes(self._off(), self.n_scenes, wb), "nbd_batch_f64_workspace_bytes")
+            fill, fill_name = L.nbd_batch_f64_plan_fill, "nbd_batch_f64_plan_fill"
         self.n_items, self.posm_rows, self.plan_bytes, self.workspace_bytes = items.value, rows.value, pb.value, wb.value
         host = np.zeros((self.plan_bytes + 15) // 16 * 4, dtype=np.int32)
-        _lib.check(L.nbd_batch_plan_fill(self._off(), self.n_scenes, host.ctypes.data, self.plan_bytes),
-                   "nbd_batch_plan_fill")
+        _lib.check(fill(self._off(), self.n_scenes, host.ctypes.data, self.plan_bytes), fill_name)
         self.plan = torch.from_numpy(host).to(device)
         self.device = self.plan.device
 
@@ -927,6 +949,8 @@ class BatchPlan:
         return alloc_bytes(self.hermite_workspace_bytes(), self.device)
 
     def check_state(self, posm, ws, *arrays):
+        if self.dtype != torch.float32:
+            raise _lib.NbdError("batch float32 call: the plan was built for float64")
         n = self.n_total
         for t, nm in arrays:
             _chk(t, (n, 3) if nm != "mass" else (n,), nm)
@@ -1046,3 +1070,105 @@ def batch_hermite_step(plan: BatchPlan, pos, vel, acc_in, jerk_in, acc_out, jerk
             jerk_out.data_ptr(), mass.data_ptr(), hdt.data_ptr(), _param(eps2, plan, "softening_sq"),
             _param(g, plan, "g_const"), posm.data_ptr(), hws.data_ptr(), _nbytes(hws), _lib.current_stream(pos.device)),
             "nbd_batch_hermite_step_f32")
+
+
+# ------------------------------------------- double-precision Hermite per scene (csrc/direct_batch_hermite_f64.hip)
+BATCH_F64_PARAM_ROWS = 8        # NBD_BATCH_F64_PARAM_ROWS: G, eps^2, eps, dt, dt/2, dt^2/2, dt^3/6, dt^2/12
+
+
+def batch_f64_params(g, eps, dt) -> list:
+    """The rows of the float64 calls' parameter table from each scene's Python doubles (g, eps, dt: S floats each), formed
+    by the expressions of the one-system float64 path: eps ** 2, and hermite_step_constants<double>'s 0.5 * dt,
+    0.5 * dt * dt, dt * dt * dt / 6.0, dt * dt / 12.0. -> BATCH_F64_PARAM_ROWS lists of S floats."""
+    return [[float(x) for x in g], [float(e) ** 2 for e in eps], [float(e) for e in eps], [float(d) for d in dt],
+            [0.5 * d for d in dt], [0.5 * d * d for d in dt], [d * d * d / 6.0 for d in dt], [d * d / 12.0 for d in dt]]
+
+
+def _chk_f64_batch(plan: BatchPlan, posd, veld, ws, params, *arrays):
+    """The checks every batch_*_f64 call makes: a float64 plan, the state arrays, the packed rows, the workspace and the
+    parameter table (each None where the call takes none)."""
+    if plan.dtype != F64:
+        raise _lib.NbdError("batch float64 call: the plan was built for float32 (BatchPlan(..., dtype=torch.float64))")
+    n = plan.n_total
+    for t, nm in arrays:
+        _chk(t, (n,) if nm in ("mass", "phi") else (n, 3), nm, F64)
+    for t, nm in ((posd, "posd"), (veld, "veld")):
+        if t is not None:
+            _chk(t, None, nm, F64)
+            if t.dim() != 2 or t.shape[1] != 4 or t.shape[0] < plan.posm_rows:
+                raise _lib.NbdError(f"{nm}: need >= {plan.posm_rows} rows of 4, got {tuple(t.shape)}")
+    if ws is not None and _nbytes(ws) < plan.workspace_bytes:
+        raise _lib.NbdError("batch float64 workspace too small")
+    if params is not None:
+        _chk(params, (BATCH_F64_PARAM_ROWS, plan.n_scenes), "params", F64)
+
+
+def alloc_batch_rows_f64(plan: BatchPlan) -> torch.Tensor:
+    """Zeroed (rows, 4) float64 rows of a float64 plan: posd or veld."""
+    return torch.zeros((max(plan.posm_rows, 1), 4), dtype=F64, device=plan.device)
+
+
+def batch_pack_f64(plan: BatchPlan, pos, vel, mass, posd, veld) -> None:
+    """posd = {x, m}, veld = {v, 0} of every scene."""
+    _chk_f64_batch(plan, posd, veld, None, None, (pos, "pos"), (vel, "vel"), (mass, "mass"))
+    with _lib.on_device(pos.device):
+        _lib.check(_lib.lib().nbd_batch_pack_f64(*plan.head(), pos.data_ptr(), vel.data_ptr(), mass.data_ptr(),
+                                                 posd.data_ptr(), veld.data_ptr(), _lib.current_stream(pos.device)),
+                   "nbd_batch_pack_f64")
+
+
+def batch_accel_jerk_f64(plan: BatchPlan, pos, vel, mass, params, acc_out, jerk_out, posd, veld, ws) -> None:
+    """batch_accel_jerk in float64 (accel_jerk_f64 per scene, bit for bit). params: device float64
+    (BATCH_F64_PARAM_ROWS, S) as batch_f64_params forms it; ws: plan.workspace()."""
+    _chk_f64_batch(plan, posd, veld, ws, params, (pos, "pos"), (vel, "vel"), (mass, "mass"), (acc_out, "acc_out"),
+                   (jerk_out, "jerk_out"))
+    with _lib.on_device(pos.device):
+        _lib.check(_lib.lib().nbd_batch_accel_jerk_f64(
+            *plan.head(), pos.data_ptr(), vel.data_ptr(), mass.data_ptr(), params.data_ptr(), acc_out.data_ptr(),
+            jerk_out.data_ptr(), posd.data_ptr(), veld.data_ptr(), ws.data_ptr(), _nbytes(ws),
+            _lib.current_stream(pos.device)), "nbd_batch_accel_jerk_f64")
+
+
+def batch_hermite_step_f64(plan: BatchPlan, pos, vel, acc_in, jerk_in, acc_out, jerk_out, mass, params, posd, veld,
+                           ws) -> None:
+    """batch_hermite_step in float64 (hermite_step_f64 per scene, bit for bit): pos, vel in place; acc_out, jerk_out (may
+    be acc_in, jerk_in); posd = {x1, m}; veld is scratch."""
+    _chk_f64_batch(plan, posd, veld, ws, params, (pos, "pos"), (vel, "vel"), (acc_in, "acc_in"), (jerk_in, "jerk_in"),
+                   (acc_out, "acc_out"), (jerk_out, "jerk_out"), (mass, "mass"))
+    with _lib.on_device(pos.device):
+        _lib.check(_lib.lib().nbd_batch_hermite_step_f64(
+            *plan.head(), pos.data_ptr(), vel.data_ptr(), acc_in.data_ptr(), jerk_in.data_ptr(), acc_out.data_ptr(),
+            jerk_out.data_ptr(), mass.data_ptr(), params.data_ptr(), posd.data_ptr(), veld.data_ptr(), ws.data_ptr(),
+            _nbytes(ws), _lib.current_stream(pos.device)), "nbd_batch_hermite_step_f64")
+
+
+def batch_energies_f64(plan: BatchPlan, posd, vel, params, out_uk, ws) -> torch.Tensor:
+    """out_uk (S, 2) float64 = {U_s, K_s} (energy_f64 per scene, bit for bit) from posd and vel; asynchronous."""
+    _chk_f64_batch(plan, posd, None, ws, params, (vel, "vel"))
+    _chk(out_uk, (plan.n_scenes, 2), "out_uk", F64)
+    with _lib.on_device(vel.device):
+        _lib.check(_lib.lib().nbd_batch_energies_f64(
+            *plan.head(), posd.data_ptr(), vel.data_ptr(), params.data_ptr(), out_uk.data_ptr(), ws.data_ptr(),
+            _nbytes(ws), _lib.current_stream(vel.device)), "nbd_batch_energies_f64")
+    return out_uk
+
+
+def batch_potential_f64(plan: BatchPlan, posd, params, phi_out, ws) -> torch.Tensor:
+    """phi_out (N_total,) float64 (potential_f64 per scene, bit for bit) from posd; asynchronous."""
+    _chk_f64_batch(plan, posd, None, ws, params, (phi_out, "phi"))
+    with _lib.on_device(posd.device):
+        _lib.check(_lib.lib().nbd_batch_potential_f64(
+            *plan.head(), posd.data_ptr(), params.data_ptr(), phi_out.data_ptr(), ws.data_ptr(), _nbytes(ws),
+            _lib.current_stream(posd.device)), "nbd_batch_potential_f64")
+    return phi_out
+
+
+def batch_invariants_state_f64(plan: BatchPlan, pos, vel, mass, phi, out_rows) -> torch.Tensor:
+    """out_rows (S, 16) float64 = invariants_state_f64 of every scene (bit for bit) from the state and phi."""
+    _chk_f64_batch(plan, None, None, None, None, (pos, "pos"), (vel, "vel"), (mass, "mass"), (phi, "phi"))
+    _chk(out_rows, (plan.n_scenes, INVARIANT_ROW), "out_rows", F64)
+    with _lib.on_device(vel.device):
+        _lib.check(_lib.lib().nbd_batch_invariants_state_f64(
+            *plan.head(), pos.data_ptr(), vel.data_ptr(), mass.data_ptr(), phi.data_ptr(), out_rows.data_ptr(),
+            _lib.current_stream(vel.device)), "nbd_batch_invariants_state_f64")
+    return out_rows

@@ -1,0 +1,253 @@
+"""BatchedSimulator(dtype=torch.float64) without a GPU: the new entries are in the header and the ctypes table, the float64
+work list has the geometry of the one-system float64 step for every scene, every launching entry rejects bad arguments
+before anything reaches the device, the constructor refuses what there is no float64 form of, and the evaluate kernel
+(gfx950 assembly, hipcc cross-compiles) has the registers, the LDS and the counted wait of the one-system kernel."""
+import ctypes
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+import torch
+
+from conftest import ROOT
+from nbd import _lib
+
+SRC = os.path.join(ROOT, "nbody-deep-sim_amd", "csrc", "direct_batch_hermite_f64.hip")
+FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-ffp-contract=off", "--cuda-device-only", "-S"]
+E_BADARG, E_WORKSPACE = -1, -2
+NEW = ["nbd_batch_f64_plan", "nbd_batch_f64_plan_fill", "nbd_batch_f64_workspace_bytes", "nbd_batch_pack_f64",
+       "nbd_batch_accel_jerk_f64", "nbd_batch_hermite_step_f64", "nbd_batch_energies_f64", "nbd_batch_potential_f64",
+       "nbd_batch_invariants_state_f64", "nbd_snapshot_f64"]
+SIZES = [3, 0, 64, 65, 449, 1, 1000]
+
+
+def _off(sizes):
+    off = np.zeros(len(sizes) + 1, dtype=np.int32)
+    np.cumsum(sizes, out=off[1:])
+    return off
+
+
+def _plan(sizes):
+    """(offsets, rows, plan bytes, workspace bytes, items (k, 4), scene records (S, 8), row_scene, the filled buffer)"""
+    L = _lib.lib()
+    off = _off(sizes)
+    items, rows, pb, wb = ctypes.c_int(), ctypes.c_int(), ctypes.c_size_t(), ctypes.c_size_t()
+    assert L.nbd_batch_f64_plan(off.ctypes.data, len(sizes), items, rows, pb) == 0
+    assert L.nbd_batch_f64_workspace_bytes(off.ctypes.data, len(sizes), wb) == 0
+    buf = np.zeros((pb.value + 15) // 16 * 4, dtype=np.int32)
+    assert L.nbd_batch_f64_plan_fill(off.ctypes.data, len(sizes), buf.ctypes.data, pb.value) == 0
+    k, S = items.value, len(sizes)
+    assert pb.value == 16 * k + 32 * S + 4 * rows.value
+    return (off, rows.value, pb.value, wb.value, buf[:4 * k].reshape(k, 4), buf[4 * k:4 * k + 8 * S].reshape(S, 8),
+            buf[4 * k + 8 * S:4 * k + 8 * S + rows.value], buf)
+
+
+def _lone_plan(n):
+    g, s, c = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    assert _lib.lib().nbd_hermite_f64_plan(n, g, s, c) == 0
+    return g.value, s.value
+
+
+def test_new_symbols_are_declared_and_bound():
+    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "nbd.h")).read(), flags=re.S)
+    declared = set(re.findall(r"\b(nbd_[a-z0-9_]+)\s*\(", text))
+    L = _lib.lib()
+    for sym in NEW:
+        assert sym in declared and sym in _lib.SIGNATURES and hasattr(L, sym), sym
+    assert "#define NBD_ABI_VERSION 2" in open(os.path.join(ROOT, "include", "nbd.h")).read()
+    assert L.nbd_abi_version() == 2
+
+
+def test_plan_has_the_one_system_geometry_of_every_scene():
+    off, rows, _, ws_bytes, items, scenes, row_scene, _ = _plan(SIZES)
+    want_items, want_rows, area_end = 0, 0, 0
+    seen = set()
+    for s, n in enumerate(SIZES):
+        o, nn, poff, ws_off, _, slabs, n_chunks, groups = (int(x) for x in scenes[s])
+        assert (o, nn, poff) == (off[s], n, want_rows)
+        if n == 0:
+            assert (slabs, n_chunks, groups) == (0, 0, 0)
+            continue
+        lone_groups, lone_slabs = _lone_plan(n)
+        assert (groups, slabs, n_chunks) == (lone_groups, lone_slabs, (n + 63) // 64) and groups == (n + 63) // 64
+        want_items += groups * slabs
+        assert (row_scene[poff:poff + 64 * n_chunks] == s).all()
+        want_rows += 64 * n_chunks
+        # double[slabs][6][n] of the scene, disjoint from every other scene's and inside the reported workspace
+        assert ws_off == area_end
+        area_end = ws_off + slabs * 6 * n
+        assert 8 * area_end <= ws_bytes
+    assert len(items) == want_items and rows == want_rows == len(row_scene) and ws_bytes == 8 * area_end
+    for s, g, k, pad in items.tolist():
+        assert SIZES[s] > 0 and 0 <= g < scenes[s][7] and 0 <= k < scenes[s][5] and pad == 0
+        assert (s, g, k) not in seen
+        seen.add((s, g, k))
+    assert len(seen) == want_items
+    assert _lone_plan(448)[1] == 1 and _lone_plan(449)[1] == 2          # the slab boundary the GPU tests cross
+
+
+def test_plan_of_empty_scenes_and_bad_offsets():
+    L = _lib.lib()
+    _, rows, pb, wb, items, _, _, _ = _plan([0, 0])
+    assert (rows, wb, len(items), pb) == (0, 0, 0, 64)
+    n = ctypes.c_size_t()
+    for bad, S in ((np.array([0, 5, 2], dtype=np.int32), 2), (np.array([1, 5], dtype=np.int32), 1),
+                   (np.array([0, 5], dtype=np.int32), 0)):
+        assert L.nbd_batch_f64_plan(bad.ctypes.data, S, None, None, None) == E_BADARG
+        assert L.nbd_batch_f64_workspace_bytes(bad.ctypes.data, S, n) == E_BADARG
+        assert L.nbd_batch_f64_plan_fill(bad.ctypes.data, S, bad.ctypes.data, 64) == E_BADARG
+    off = _off([5, 7])
+    assert L.nbd_batch_f64_plan(None, 1, None, None, None) == E_BADARG
+    assert L.nbd_batch_f64_workspace_bytes(off.ctypes.data, 2, None) == E_BADARG
+    # the partial sums counted in doubles must stay within the int offsets: 1 slab x 6 x 4e8 bodies does not
+    big = _off([400_000_000])
+    assert L.nbd_batch_f64_plan(big.ctypes.data, 1, None, None, None) == -3
+    assert L.nbd_batch_f64_workspace_bytes(big.ctypes.data, 1, n) == -3
+
+
+# entry -> (device pointers between the plan head and the tail, index of posd among them, takes a workspace)
+SHAPE = {"nbd_batch_pack_f64": (5, 3, False), "nbd_batch_accel_jerk_f64": (8, 6, True),
+         "nbd_batch_hermite_step_f64": (10, 8, True), "nbd_batch_energies_f64": (4, 0, True),
+         "nbd_batch_potential_f64": (3, 0, True), "nbd_batch_invariants_state_f64": (5, None, False)}
+
+
+def _call(name, head, ptrs, ws=None, wsb=0):
+    tail = (ws, wsb, None) if SHAPE[name][2] else (None,)
+    return getattr(_lib.lib(), name)(*head, *ptrs, *tail)
+
+
+@pytest.mark.parametrize("name", sorted(SHAPE))
+def test_bad_arguments_are_rejected_without_touching_the_gpu(name):
+    sizes = [5, 0, 70]
+    off, _, pb, need, _, _, _, host = _plan(sizes)
+    S, p = len(sizes), host.ctypes.data
+    assert p % 16 == 0 and need > 0
+    keep = np.zeros(64, dtype=np.float64)
+    A = (keep.ctypes.data + 31) // 32 * 32                  # a 32-byte aligned host address; no entry dereferences it
+    k, posd_at, has_ws = SHAPE[name]
+    head = (off.ctypes.data, S, p, pb)
+    # every device pointer NULL, then one NULL among the rest
+    assert _call(name, head, [None] * k, A, need) == E_BADARG
+    for i in range(k):
+        q = [A] * k
+        q[i] = None
+        assert _call(name, head, q, A, need) == E_BADARG, i
+    # the packed rows need 32-byte alignment
+    if posd_at is not None:
+        q = [A] * k
+        q[posd_at] = A + 16
+        assert _call(name, head, q, A, need) == E_BADARG
+    # the plan: 16-byte aligned, its byte count the reported one, offsets and scene count valid
+    for bad_head in ((off.ctypes.data, S, p, pb + 16), (off.ctypes.data, S, None, pb), (off.ctypes.data, S, p + 4, pb),
+                     (off.ctypes.data, 0, p, pb), (None, S, p, pb)):
+        assert _call(name, bad_head, [A] * k, A, need) == E_BADARG, bad_head
+    if has_ws:
+        # arrays given but no workspace, a misaligned one, or one a byte short: NBD_E_WORKSPACE, still before any launch
+        for ws, wsb in ((None, need), (A + 4, need), (A, need - 1), (A, 0)):
+            assert _call(name, head, [A] * k, ws, wsb) == E_WORKSPACE, (ws, wsb)
+
+
+def test_snapshot_f64_argument_checks():
+    L = _lib.lib()
+    assert L.nbd_snapshot_f64(None, None, None, 4, None, None) == E_BADARG
+    assert L.nbd_snapshot_f64(None, None, None, -1, None, None) == E_BADARG
+    assert L.nbd_snapshot_f64(None, None, None, 0, None, None) == 0
+    keep = np.zeros(8, dtype=np.float64)
+    A = keep.ctypes.data
+    assert L.nbd_snapshot_f64(A, A, A, 4, A + 4, None) == E_BADARG       # the output is an array of doubles
+
+
+def test_an_all_empty_batch_is_a_no_op_without_a_gpu():
+    off, _, pb, _, _, _, _, host = _plan([0, 0])
+    L = _lib.lib()
+    head = (off.ctypes.data, 2, host.ctypes.data, pb)
+    assert L.nbd_batch_pack_f64(*head, *[None] * 5, None) == 0
+    assert L.nbd_batch_accel_jerk_f64(*head, *[None] * 8, None, 0, None) == 0
+    assert L.nbd_batch_hermite_step_f64(*head, *[None] * 10, None, 0, None) == 0
+    assert L.nbd_batch_potential_f64(*head, *[None] * 3, None, 0, None) == 0
+
+
+def test_parameter_rows_are_the_one_system_expressions():
+    from nbd import direct
+    g, eps, dt = [1.0, 0.7], [0.1, 0.0], [0.01, 1.0 / 3.0]
+    rows = direct.batch_f64_params(g, eps, dt)
+    assert len(rows) == direct.BATCH_F64_PARAM_ROWS == 8
+    for s in range(2):
+        d = dt[s]
+        # _Float64._scalars and hermite_step_constants<double>, written out
+        assert [r[s] for r in rows] == [g[s], float(eps[s]) ** 2, eps[s], d, 0.5 * d, 0.5 * d * d, d * d * d / 6.0,
+                                        d * d / 12.0]
+
+
+def test_constructor_refuses_before_any_device_is_resolved():
+    from galaxify import simulation
+    z = np.zeros((4, 3))
+    scene = (z, z, np.ones(4))
+    # device="tpu" would raise ValueError("device debe ser ...") and device="cpu" RuntimeError: the dtype check comes first
+    with pytest.raises(ValueError, match="dtype must be"):
+        simulation.BatchedSimulator(systems=[scene], integrator="hermite", dtype=torch.float16, device="cpu")
+    with pytest.raises(ValueError, match="dtype must be"):
+        simulation.BatchedSimulator(systems=[scene], dtype=torch.float16, device="cpu")
+    for integrator in ("leapfrog", "euler"):
+        with pytest.raises(ValueError, match="hermite"):
+            simulation.BatchedSimulator(systems=[scene], integrator=integrator, dtype=torch.float64, device="cpu")
+    with pytest.raises(RuntimeError):                      # a valid combination reaches the device rule
+        simulation.BatchedSimulator(systems=[scene], integrator="hermite", dtype=torch.float64, device="cpu")
+
+
+def test_chunk_layout_takes_the_element_size():
+    from galaxify import simulation
+    m, n, S = 3, 5, 2
+    assert simulation._batch_chunk_layout(m, n, S) == simulation._batch_chunk_layout(m, n, S, torch.float32)
+    ring_b, uk_at, size = simulation._batch_chunk_layout(m, n, S, torch.float64)
+    assert ring_b == m * 72 * n and uk_at == (ring_b + 15) // 16 * 16 and size == uk_at + m * S * 16
+    buf = torch.zeros(size, dtype=torch.uint8)
+    ring, uk = simulation._batch_chunk_views(buf, m, n, S, torch.float64)
+    assert ring.dtype == torch.float64 and tuple(ring.shape) == (m, 3, n, 3) and tuple(uk.shape) == (m, S, 2)
+
+
+# ---- the evaluate kernel in gfx950 assembly
+@pytest.fixture(scope="module")
+def asm(tmp_path_factory):
+    out = str(tmp_path_factory.mktemp("isa") / "direct_batch_hermite_f64.s")
+    subprocess.run(["/opt/rocm/bin/hipcc", *FLAGS, "-o", out, SRC], check=True, capture_output=True)
+    return open(out).read()
+
+
+def _name(asm, kernel):
+    names = [m for m in re.findall(r"^(_Z\S+):", asm, flags=re.M) if kernel in m]
+    assert len(names) == 1, names
+    return names[0]
+
+
+def _resources(asm, name):
+    meta = asm[asm.index(".name:           " + name):]
+    meta = meta[:meta.index(".name:           ", 20) if ".name:           " in meta[20:] else len(meta)]
+    out = {k: int(re.search(r"\." + k + r":\s+(\d+)", meta).group(1))
+           for k in ("vgpr_count", "vgpr_spill_count", "private_segment_fixed_size")}
+    desc = asm[asm.index(".amdhsa_kernel " + name):]
+    out["lds"] = int(re.search(r"\.amdhsa_group_segment_fixed_size\s+(\d+)", desc).group(1))
+    return out
+
+
+def test_evaluate_kernel_has_no_spills_no_scratch_and_the_32_kib_stage(asm):
+    name = _name(asm, "batch_accel_jerk_f64_kernel")
+    r = _resources(asm, name)
+    assert r["vgpr_spill_count"] == 0 and r["private_segment_fixed_size"] == 0, r
+    assert r["lds"] == 32768 and r["vgpr_count"] <= 96, r       # 5 workgroups of 4 waves per CU
+    i = asm.index(name + ":")
+    body = asm[i:asm.index(".Lfunc_end", i)]
+    assert "global_load_lds_dwordx4" in body and "v_rsq_f64" in body
+    assert not any("scratch_" in ln for ln in body.split("\n"))
+    assert "s_waitcnt vmcnt(4)" in body                                             # walk_f64's counted wait, as written
+    assert not re.search(r"\batomic", body)
+
+
+@pytest.mark.parametrize("kernel", ["batch_predict_f64_kernel", "batch_correct_f64_kernel", "batch_energy_f64_kernel",
+                                    "batch_potential_f64_kernel", "batch_energy_finish_f64_kernel",
+                                    "batch_potential_finish_f64_kernel", "batch_invariants_state_f64_kernel"])
+def test_other_kernels_have_no_scratch(asm, kernel):
+    r = _resources(asm, _name(asm, kernel))
+    assert r["vgpr_spill_count"] == 0 and r["private_segment_fixed_size"] == 0, r

@@ -8,8 +8,13 @@ Times are wall clock around run() after a warm-up run() of the same length (grap
 GPU time = the sum of SimulationState.step_time (the batched step's GPU time is spread over its S scenes).
 --integrator hermite compares scene-by-scene HermiteSimulator.run() with one batched Hermite run(), and adds the batched
 leapfrog time of the same scenes from the same process (batched_leapfrog_*, hermite_over_leapfrog_gpu).
+--integrator hermite --dtype float64 compares scene-by-scene HermiteSimulator(dtype=torch.float64).run() (eager: the
+one-system float64 step has no captured form) with one batched float64 run(), and adds the batched float32 Hermite time
+of the same scenes from the same process (batched_f32_hermite_*, f64_over_f32_gpu). --out FILE also writes the line there
+(profiles/r17_batch_hermite_f64.json is this tool's output for float64).
 
   python tools/bench_direct_scenes.py [--sample 128] [--cases six,many,large] [--integrator leapfrog|hermite]
+                                      [--dtype float32|float64] [--out FILE]
 """
 import argparse
 import json
@@ -39,29 +44,32 @@ def timed(fn):
     return time.perf_counter() - t0, out
 
 
-def batched(systems, steps, energy, integrator):
-    """(wall s, GPU s) of one batched run() after a warm-up run() of the same length."""
+def batched(systems, steps, energy, integrator, **kw):
+    """(wall s, GPU s) of one batched run() after a warm-up run() of the same length. kw: dtype=torch.float64."""
     bat = simulation.BatchedSimulator(systems=systems, integrator=integrator, g_const=G, softening=EPS, dt=DT,
-                                      calc_energy=energy, device="cuda")
+                                      calc_energy=energy, device="cuda", **kw)
     bat.run(steps)
     wall, runs = timed(lambda: bat.run(steps))
     return wall, sum(st.step_time for r in runs for st in r)
 
 
-def case(sizes, steps, energy, sample=None, integrator="leapfrog"):
+def case(sizes, steps, energy, sample=None, integrator="leapfrog", dtype=torch.float32):
     systems = [spiral(n, 1 + i) for i, n in enumerate(sizes)]
     seq = systems if sample is None else systems[:sample]
     cls = simulation.HermiteSimulator if integrator == "hermite" else simulation.LeapFrogSimulator
-    sims = [cls(positions=p, velocities=v, masses=m, g_const=G, softening=EPS, dt=DT, calc_energy=energy, device="cuda")
-            for p, v, m in seq]
+    kw = {} if dtype == torch.float32 else {"dtype": dtype}           # (only the Hermite classes take the keyword)
+    sims = [cls(positions=p, velocities=v, masses=m, g_const=G, softening=EPS, dt=DT, calc_energy=energy, device="cuda",
+                **kw) for p, v, m in seq]
     for s in sims:
         s.run(steps)                                      # warm-up: captures
     wall_seq, runs = timed(lambda: [s.run(steps) for s in sims])
     gpu_seq = sum(st.step_time for r in runs for st in r)
     scale = len(systems) / len(seq)
-    wall_bat, gpu_bat = batched(systems, steps, energy, integrator)
+    wall_bat, gpu_bat = batched(systems, steps, energy, integrator, **kw)
     pairs = sum(n * n for n in sizes) * steps
     out = {} if integrator == "leapfrog" else {"integrator": integrator}
+    if kw:
+        out["dtype"] = str(dtype).replace("torch.", "")
     out.update({"scenes": len(sizes), "bodies": sum(sizes), "steps": steps, "energy": energy,
                 "scene_by_scene_sampled": len(seq),
                 "scene_by_scene_wall_us_per_step": 1e6 * wall_seq * scale / steps,
@@ -71,7 +79,11 @@ def case(sizes, steps, energy, sample=None, integrator="leapfrog"):
                 "speedup_wall": wall_seq * scale / wall_bat, "speedup_gpu": gpu_seq * scale / gpu_bat,
                 "batched_gpairs_per_s_gpu": pairs / gpu_bat * 1e-9,
                 "scene_by_scene_gpairs_per_s_gpu": pairs / (gpu_seq * scale) * 1e-9})
-    if integrator != "leapfrog":
+    if kw:
+        wall_32, gpu_32 = batched(systems, steps, energy, integrator)
+        out.update({"batched_f32_hermite_wall_us_per_step": 1e6 * wall_32 / steps,
+                    "batched_f32_hermite_gpu_us_per_step": 1e6 * gpu_32 / steps, "f64_over_f32_gpu": gpu_bat / gpu_32})
+    elif integrator != "leapfrog":
         wall_lf, gpu_lf = batched(systems, steps, energy, "leapfrog")
         out.update({"batched_leapfrog_wall_us_per_step": 1e6 * wall_lf / steps,
                     "batched_leapfrog_gpu_us_per_step": 1e6 * gpu_lf / steps,
@@ -84,18 +96,26 @@ def main():
     ap.add_argument("--sample", type=int, default=128)
     ap.add_argument("--cases", default="six,many,large")
     ap.add_argument("--integrator", choices=("leapfrog", "hermite"), default="leapfrog")
+    ap.add_argument("--dtype", choices=("float32", "float64"), default="float32")
+    ap.add_argument("--out", default=None, help="also write the JSON line to this file")
     a = ap.parse_args()
-    it = a.integrator
+    if a.dtype == "float64" and a.integrator != "hermite":
+        ap.error("--dtype float64 needs --integrator hermite (there is no float64 leapfrog)")
+    it, dt = a.integrator, getattr(torch, a.dtype)
     torch.cuda.set_device(0)
     out = {"device": torch.cuda.get_device_name(0)}
     todo = a.cases.split(",")
     if "six" in todo:
-        out["six"] = case([3, 25, 50, 100, 250, 500], 1000, True, integrator=it)
+        out["six"] = case([3, 25, 50, 100, 250, 500], 1000, True, integrator=it, dtype=dt)
     if "many" in todo:
-        out["many"] = case([100] * 1024, 100, True, sample=a.sample, integrator=it)
+        out["many"] = case([100] * 1024, 100, True, sample=a.sample, integrator=it, dtype=dt)
     if "large" in todo:
-        out["large"] = case([16384] * 4, 100, False, integrator=it)
-    print(json.dumps(out))
+        out["large"] = case([16384] * 4, 100, False, integrator=it, dtype=dt)
+    line = json.dumps(out)
+    print(line)
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
 
 
 if __name__ == "__main__":
