@@ -599,6 +599,37 @@ size_t nbd_accel_vjp_f64_workspace_bytes(int n, int slabs);
 int nbd_accel_vjp_f64(const double* posd, const double* cotd, int n, double softening_sq, double g_const,
                       double* grad_pos, double* grad_mass, void* workspace, int slabs, nbd_stream_t stream);
 
+/* ------------------------------------------------------------ backward of the Hermite force (direct_hermite_grad.hip)
+ * The vector-Jacobian product of (a, j) of nbd_accel_jerk_f32 / nbd_accel_jerk_f64,
+ *   j_i = G sum_{j != i} m_j [ s^3 w - 3 s^5 (d . w) d ],  w = v_j - v_i,
+ * with the cotangents cota = dL/da and cotj = dL/dj, packed as nbd_accel_vjp_* takes its cotangent ({gx, gy, gz, 0}, zero
+ * rows behind n up to a multiple of 64; posm / velp resp. posd / veld are the packed rows of the force entries). With
+ * h = m_i cotj_j - m_j cotj_i:
+ *   grad_vel[i]  =  G sum_j [ s^3 h - 3 s^5 d (d . h) ]                                                  (n,3)
+ *   grad_pos[i]  =  nbd_accel_vjp_*'s grad_pos of cota
+ *                 + G sum_j { -3 s^5 [ (h . w) d + (d . h) w + (d . w) h ] + 15 s^7 (d . w)(d . h) d }   (n,3)
+ *   grad_mass[i] =  nbd_accel_vjp_*'s grad_mass of cota
+ *                 - G sum_j [ s^3 (cotj_j . w) - 3 s^5 (d . w)(d . cotj_j) ]                             (n)
+ * Either cotangent may be null (not both): with cotj null grad_pos and grad_mass are nbd_accel_vjp_*'s bits and grad_vel
+ * is zeros; with cota null only the new kernels run. With both, the cota part is computed by nbd_accel_vjp_* into the
+ * workspace and added last, after G. Any of the three outputs may be null (not all) and is then not written. i == j as
+ * for nbd_accel_vjp_*. No atomics, no memsets, no host syncs: deterministic with a workspace that may hold anything on
+ * entry, and capturable. Refused with NBD_E_BADARG before any launch: n < 0, a null posm / velp / workspace, a misaligned
+ * pointer (rows 16 bytes in fp32 and 32 in fp64; the workspace 16 resp. 8; the outputs their element size), no cotangent,
+ * no output, a workspace smaller than nbd_accel_jerk_vjp_*workspace_bytes, slabs outside [0, 64], a non-finite
+ * softening_sq or g_const. n = 0 succeeds and touches nothing. */
+/* Workspace in floats, S = the slabs of the force plan (nbd_accel_plan at n sources, n targets): 7 S n rounded up to a
+ * multiple of 4, then 4 S n (nbd_accel_vjp_f32's own) and 4 n (its results). */
+size_t nbd_accel_jerk_vjp_workspace_bytes(int n);
+int nbd_accel_jerk_vjp_f32(const float* posm, const float* velp, const float* cota, const float* cotj, int n,
+                           float softening_sq, float g_const, float* grad_pos, float* grad_vel, float* grad_mass,
+                           void* workspace, size_t workspace_bytes, nbd_stream_t stream);
+/* float64: slabs as in nbd_accel_vjp_f64. Workspace: the same sum in doubles; 0 for a slab count outside [0, 64]. */
+size_t nbd_accel_jerk_vjp_f64_workspace_bytes(int n, int slabs);
+int nbd_accel_jerk_vjp_f64(const double* posd, const double* veld, const double* cota, const double* cotj, int n,
+                           double softening_sq, double g_const, double* grad_pos, double* grad_vel, double* grad_mass,
+                           void* workspace, size_t workspace_bytes, int slabs, nbd_stream_t stream);
+
 /* ------------------------------------------------------------ surrogate models: graph build
  * Replace the torch_cluster kernels the reference reaches through PyG. Index-exact rule (the
  * reference delegates ties/truncation to torch_cluster; fixed here, see oracle/surrogate_oracle.py):

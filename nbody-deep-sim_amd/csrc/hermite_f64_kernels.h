@@ -38,7 +38,8 @@ __device__ __forceinline__ double rsqrt_f64(const double x) {
 }
 
 // ---- the pair functors. A functor holds its lane's target and partial sums; pair<MASKED>(p, q, j) adds source j (row p
-// of posd, row q of veld where kVel) -- MASKED: exclusions by index, else by the arithmetic; out(k) is partial sum k of kOut.
+// of posd, row q of veld where kVel; with kStreams = 3, pair<MASKED>(p, q, r, j) with row r of a third array) -- MASKED:
+// exclusions by index, else by the arithmetic; out(k) is partial sum k of kOut.
 
 // a_i = sum_j m_j r_ij s^3, j_i = sum_j m_j (v_ij s^3 - 3 (r_ij.v_ij) s^5 r_ij), s = (|r_ij|^2 + eps^2)^(-1/2): the
 // operations of AccelJerkPolicy::masked / ::block (hermite_kernels.h) one for one. acc[3..5] accumulates w dv, acc[6..8]
@@ -200,12 +201,25 @@ struct F64State {
 template <bool VEL>
 constexpr int stage_quads() { return 2 * (VEL ? 2 : 1) * kChunkQuads; }
 
+// ... and with NS arrays streamed: [wave][buffer][array][128]
+template <int NS>
+constexpr int stage_quads_n() { return 2 * NS * kChunkQuads; }
+
+// The arrays a functor streams per source: kVel ? 2 : 1, or the functor's own kStreams (3: direct_hermite_grad.hip's
+// {x, m}, {v, 0} and a cotangent row; pair<MASKED>(p, q, r, j) then takes the third row after the second).
+template <class Pair, class = void>
+struct PairStreams { static constexpr int value = Pair::kVel ? 2 : 1; };
+template <class Pair>
+struct PairStreams<Pair, decltype((void)Pair::kStreams)> { static constexpr int value = Pair::kStreams; };
+
 // The wave body. The wave walks the chunks [c_begin, c_end) of posd (and veld): chunk c = rows [64 c, 64 c + 64), 2 KiB per
 // array, fetched as two 1-KiB LDS-DMA pieces (lane l brings quads l and 64 + l of the chunk, so the rows land as they lie
 // in memory), the next chunk in flight while this one is used. all_masked, or the chunk own_chunk (the one that holds the
 // group's own indices; -1 for gathered targets, which have none), takes pair<true>, every other chunk pair<false>. Then
 // the 4 waves' kOut partials per lane go through LDS -- a wave's staging is free after its last chunk: its loads have
 // landed and its reads precede these writes -- and are added in wave order into dst[k * stride + t], t < n_valid.
+// A functor with kStreams = 3 (PairStreams above) streams `third` as well: two more loads per chunk, [pos | vel | third][128]
+// staging, the counted wait at six loads, masked or un-masked chunks only.
 // Compile-time shape, the defaults = two arrays of 32-byte rows, every chunk where it lies:
 //   RQ    : 16-byte quads from one source row to the next. 2: posd and veld as above. 4: ONE array of 64-byte rows
 //           {x, y, z, m, vx, vy, vz, 0} (veld = posd + 2 quads), what a range-sharded rank sends and gathers
@@ -220,18 +234,21 @@ constexpr int stage_quads() { return 2 * (VEL ? 2 : 1) * kChunkQuads; }
 template <class Pair, int RQ = kRowQuads, bool RANGE = false>
 __device__ __forceinline__ void walk_f64(Pair& pr, const d4* __restrict__ posd, const d4* __restrict__ veld, int c_begin,
                                          int c_end, bool all_masked, int own_chunk, f4* lds, double* __restrict__ dst,
-                                         size_t stride, int n_valid, const SrcView* sv = nullptr) {
-  constexpr bool VEL = Pair::kVel;
-  constexpr int kArr = VEL ? 2 : 1;
+                                         size_t stride, int n_valid, const SrcView* sv = nullptr,
+                                         const d4* __restrict__ third = nullptr) {
+  constexpr int kArr = PairStreams<Pair>::value;
+  constexpr bool VEL = kArr >= 2;
+  static_assert(kArr >= 1 && kArr <= 3 && (kArr < 3 || (RQ == kRowQuads && !RANGE)), "three arrays: un-sharded rows only");
   constexpr int kSrcQuads = kChunk * RQ;           // quads from one chunk to the next in memory
   constexpr int kPiece = kSrcQuads / 2;            // and from the first LDS-DMA piece of a chunk to the second
   static_assert(RQ == kRowQuads || RQ == 2 * kRowQuads, "rows of posd / veld, or {pos, vel} rows");
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  f4* stage = &lds[wave * stage_quads<VEL>()];
+  f4* stage = &lds[wave * stage_quads_n<kArr>()];
   const int lane_quad = RQ == kRowQuads ? lane : (lane >> 1) * RQ + (lane & 1);
   const f4* p_lane = reinterpret_cast<const f4*>(posd) + lane_quad;
   const f4* v_lane = reinterpret_cast<const f4*>(veld) + lane_quad;
+  const f4* b_lane = reinterpret_cast<const f4*>(third) + lane_quad;
   // logical -> physical chunk: hop over the skipped run
   auto phys = [&](int c) { return RANGE ? c + (c >= sv->skip_c0 ? sv->skip_cn : 0) : c; };
   auto fetch = [&](int c, int b) {
@@ -243,6 +260,10 @@ __device__ __forceinline__ void walk_f64(Pair& pr, const d4* __restrict__ posd, 
       __builtin_amdgcn_global_load_lds(GPTR(v_lane + at), LPTR(to + kChunkQuads), 16, 0, 0);
       __builtin_amdgcn_global_load_lds(GPTR(v_lane + at + kPiece), LPTR(to + kChunkQuads + 64), 16, 0, 0);
     }
+    if constexpr (kArr == 3) {
+      __builtin_amdgcn_global_load_lds(GPTR(b_lane + at), LPTR(to + 2 * kChunkQuads), 16, 0, 0);
+      __builtin_amdgcn_global_load_lds(GPTR(b_lane + at + kPiece), LPTR(to + 2 * kChunkQuads + 64), 16, 0, 0);
+    }
   };
   if (c_begin < c_end) fetch(c_begin, 0);
   for (int c = c_begin; c < c_end; ++c) {
@@ -250,7 +271,8 @@ __device__ __forceinline__ void walk_f64(Pair& pr, const d4* __restrict__ posd, 
     if (c + 1 < c_end) {
       fetch(c + 1, b ^ 1);
       // chunk c has landed, c + 1 (2 loads per array) in flight
-      if (VEL) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+      if constexpr (kArr == 3) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
+      else if (VEL) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
       else asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
     } else {
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -259,7 +281,16 @@ __device__ __forceinline__ void walk_f64(Pair& pr, const d4* __restrict__ posd, 
     const d4* bv = VEL ? bp + kChunk : bp;
     const int pc = phys(c);
     const int j0 = pc * kChunk;
-    if (RANGE && (pc == sv->edge0 || pc == sv->edge1)) {
+    if constexpr (kArr == 3) {
+      const d4* bb = bv + kChunk;
+      if (all_masked || pc == own_chunk) {
+#pragma unroll 2
+        for (int j = 0; j < kChunk; ++j) pr.template pair<true>(bp[j], bv[j], bb[j], j0 + j);
+      } else {
+#pragma unroll 2
+        for (int j = 0; j < kChunk; ++j) pr.template pair<false>(bp[j], bv[j], bb[j], j0 + j);
+      }
+    } else if (RANGE && (pc == sv->edge0 || pc == sv->edge1)) {
       const d4 none = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll 2
       for (int j = 0; j < kChunk; ++j) {
@@ -275,7 +306,7 @@ __device__ __forceinline__ void walk_f64(Pair& pr, const d4* __restrict__ posd, 
     }
   }
 
-  constexpr int kPart = stage_quads<VEL>() * 2;                      // doubles per wave; [k][64] in the first kOut * 64
+  constexpr int kPart = stage_quads_n<kArr>() * 2;                     // doubles per wave; [k][64] in the first kOut * 64
   static_assert(Pair::kOut * 64 <= kPart, "the partials must fit a wave's staging");
   double* red = reinterpret_cast<double*>(lds);
 #pragma unroll

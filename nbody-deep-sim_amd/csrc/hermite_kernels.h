@@ -128,7 +128,7 @@ struct AccelJerkPolicy {
 // The wave body of every acceleration-plus-jerk kernel. accel_kernel's structure: a workgroup is 4 waves on 128 targets,
 // two per lane in packed fp32 (rows r0, r1 of tpos / tvel; i0, i1 are the source indices the masked loop takes for the
 // lane's own); every wave streams its chunks [c_begin, c_end) of the n sources, each chunk = 64 positions + 64 velocities
-// (2 KiB) by LDS-DMA, double-buffered behind a counted vmcnt; the 4 waves' partials are reduced through LDS in wave order
+// (2 KiB; a third row with NS = 3) by LDS-DMA, double-buffered behind a counted vmcnt; the 4 waves' partials are reduced through LDS in wave order
 // into one coalesced store of 6 x n_valid floats: dst[comp * stride + t], t < n_valid. lds: the workgroup's
 // f4[kWaves * 4 * kChunk] (16 KiB), [wave][buffer][pos | vel][64] staging; after its last chunk a wave puts its [12][64]
 // partials into its own part. (6 and 12: P::kOut and twice that, for the policy P.)
@@ -141,46 +141,71 @@ struct AccelJerkPolicy {
 //           physical chunks lying wholly inside [ex_lo, ex_hi), and the (at most two) chunks that straddle an end of that
 //           range take the masked loop with the range mask; every other chunk takes the loop MASKED says.
 //   P     : the pair policy (above).
-template <bool MASKED, int KU, int SS = 1, bool RANGE = false, class P = AccelJerkPolicy>
+//   NS    : the rows streamed per source and loaded per target, 2 or 3. 3 (direct_hermite_grad.hip: {x, m}, {v, 0} and a
+//           cotangent row): sthird / tthird are the third arrays, every chunk is one more LDS-DMA, a wave's staging is
+//           [buffer][pos | vel | third][64] -- 6 kChunk quads instead of 4 --, the counted wait is vmcnt(3), and the
+//           policy's constructor and pair functions take the third row after the second.
+template <bool MASKED, int KU, int SS = 1, bool RANGE = false, class P = AccelJerkPolicy, int NS = 2>
 __device__ __forceinline__ void accel_jerk_body(const f4* __restrict__ spos, const f4* __restrict__ svel, int n,
                                                 const f4* __restrict__ tpos, const f4* __restrict__ tvel, int r0,
                                                 int r1, int i0, int i1, int c_begin, int c_end, float eps2, f4* lds,
                                                 float* __restrict__ dst, int stride, int n_valid,
-                                                const SrcView* sv = nullptr) {
+                                                const SrcView* sv = nullptr,
+                                                const f4* __restrict__ sthird = nullptr,
+                                                const f4* __restrict__ tthird = nullptr) {
+  static_assert(NS == 2 || NS == 3, "two or three rows per source");
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const f4 t0 = tpos[r0 * SS], t1 = tpos[r1 * SS];
   const f4 u0 = tvel[r0 * SS], u1 = tvel[r1 * SS];
-  const P pol(t0, t1, u0, u1);
+  const P pol = [&] {
+    if constexpr (NS == 3) return P(t0, t1, u0, u1, tthird[r0 * SS], tthird[r1 * SS]);
+    else return P(t0, t1, u0, u1);
+  }();
   f2 acc[P::kAcc];
 #pragma unroll
   for (int k = 0; k < P::kAcc; ++k) acc[k] = f2{0.f, 0.f};
   f2 e2 = {eps2, eps2};
   asm volatile("" : "+v"(e2));  // keep eps^2 in VGPRs: an SGPR operand halves v_pk_fma issue
 
-  f4* stage = &lds[wave * 4 * kChunk];
+  f4* stage = &lds[wave * 2 * NS * kChunk];
   const f4* p_lane = spos + lane * SS;
   const f4* v_lane = svel + lane * SS;
+  const f4* b_lane = NS == 3 ? sthird + lane * SS : nullptr;
   // logical -> physical chunk: hop over the skipped run
   auto phys = [&](int c) { return RANGE ? c + (c >= sv->skip_c0 ? sv->skip_cn : 0) : c; };
   auto fetch = [&](int c, int b) {
     const size_t at = (size_t)phys(c) * (kChunk * SS);
-    __builtin_amdgcn_global_load_lds(GPTR(p_lane + at), LPTR(stage + b * 2 * kChunk), 16, 0, 0);
-    __builtin_amdgcn_global_load_lds(GPTR(v_lane + at), LPTR(stage + b * 2 * kChunk + kChunk), 16, 0, 0);
+    __builtin_amdgcn_global_load_lds(GPTR(p_lane + at), LPTR(stage + b * NS * kChunk), 16, 0, 0);
+    __builtin_amdgcn_global_load_lds(GPTR(v_lane + at), LPTR(stage + b * NS * kChunk + kChunk), 16, 0, 0);
+    if constexpr (NS == 3)
+      __builtin_amdgcn_global_load_lds(GPTR(b_lane + at), LPTR(stage + b * NS * kChunk + 2 * kChunk), 16, 0, 0);
   };
   if (c_begin < c_end) fetch(c_begin, 0);
   for (int c = c_begin; c < c_end; ++c) {
     const int b = (c - c_begin) & 1;
     if (c + 1 < c_end) {
       fetch(c + 1, b ^ 1);
-      asm volatile("s_waitcnt vmcnt(2)" ::: "memory");  // chunk c has landed, c+1 (two loads) in flight
+      // chunk c has landed, c+1 (NS loads) in flight
+      if constexpr (NS == 3) asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
+      else asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
     } else {
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
-    const f4* bp = stage + b * 2 * kChunk;
+    const f4* bp = stage + b * NS * kChunk;
     const f4* bv = bp + kChunk;
     const int pc = phys(c);
-    if (RANGE && (pc == sv->edge0 || pc == sv->edge1)) {
+    if constexpr (NS == 3) {      // no range-sharded form: the masked pair or the un-masked block, with the third row
+      const f4* bb = bv + kChunk;
+      if (MASKED || pol.own(pc, i0)) {
+        const int j0 = pc * kChunk;
+#pragma unroll 2
+        for (int j = 0; j < kChunk; ++j) pol.masked(bp[j], bv[j], bb[j], e2, acc, j0 + j, i0, i1, n);
+      } else {
+#pragma unroll 1
+        for (int j = 0; j < kChunk; j += KU) pol.template block<KU>(bp + j, bv + j, bb + j, e2, acc);
+      }
+    } else if (RANGE && (pc == sv->edge0 || pc == sv->edge1)) {
       const int j0 = pc * kChunk;
 #pragma unroll 2
       for (int j = 0; j < kChunk; ++j)
@@ -198,7 +223,7 @@ __device__ __forceinline__ void accel_jerk_body(const f4* __restrict__ spos, con
 
   // wavefront partials (P::out) -> LDS -> one coalesced (kOut x 128) store per workgroup. A wave's staging is free
   // here: its loads have landed (vmcnt(0) on the last chunk) and its reads precede these writes.
-  constexpr int kPart = 4 * kChunk * 4;                   // floats per wave: [comp*2+half][64] in the first kOut * 128
+  constexpr int kPart = 2 * NS * kChunk * 4;              // floats per wave: [comp*2+half][64] in the first kOut * 128
   static_assert(P::kOut * 128 <= kPart, "the partials must fit a wave's staging");
   float* red = reinterpret_cast<float*>(lds);
   float* mine = red + wave * kPart;

@@ -38,6 +38,10 @@ is the function form; DESIGN.md K-VJP), as the reference's nine lines of torch d
 Ninth addition: `BatchedSimulator(integrator="hermite", dtype=torch.float64)`, the float64 Hermite step on every scene of
 a batch with one set of launches, each scene bit-identical to `HermiteSimulator(dtype=torch.float64)` of that scene alone,
 and run() in captured chunks (csrc/direct_batch_hermite_f64.hip). The default stays float32.
+
+Tenth addition: `HermiteSimulator.compute_accelerations_and_jerks()` is differentiable in the same way, with respect to
+`positions`, `velocities` and `masses` (csrc/direct_hermite_grad.hip; `nbd.autograd.direct_accel_jerk` is the function form;
+DESIGN.md K-HVJP). `BlockHermiteSimulator` inherits it; `BatchedSimulator` does not have it.
 """
 from __future__ import annotations
 
@@ -852,10 +856,18 @@ class HermiteSimulator(BaseSimulator):
     def compute_accelerations_and_jerks(self):
         """(a, j) of the current state as new (n,3) tensors -- (n_local,3), the rank's rows, when sharded:
         a_i = G sum_{j!=i} m_j r_ij s^3, j_i = G sum_{j!=i} m_j (v_ij s^3 - 3 (r_ij.v_ij) s^5 r_ij),
-        s = (|r_ij|^2 + eps^2)^(-1/2)."""
+        s = (|r_ij|^2 + eps^2)^(-1/2).
+        With grad enabled and positions, velocities or masses requiring grad, the pair are nodes of torch's graph
+        (nbd.autograd.direct_accel_jerk: the same forward bits, and a HIP backward, csrc/direct_hermite_grad.hip); the node
+        packs its own copy of the state. step() and run() stay non-differentiable in-place kernels."""
         if self.n == 0:
             z = torch.zeros((0, 3), dtype=self.positions.dtype, device=self.device)
             return z, z.clone()
+        if torch.is_grad_enabled() and (self.positions.requires_grad or self.velocities.requires_grad or
+                                        self.masses.requires_grad):
+            self._refuse_sharded("compute_accelerations_and_jerks() with requires_grad")
+            from nbd.autograd import direct_accel_jerk
+            return direct_accel_jerk(self.positions, self.velocities, self.masses, self.g_const, self.softening)
         if self._sharded:
             return self._sharded_launches(None, None)
         return self._fmt.accel_jerk(self)

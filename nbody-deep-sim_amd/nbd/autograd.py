@@ -635,3 +635,71 @@ def direct_accel(positions, masses, g_const: float = 1.0, softening: float = 0.1
     """The reference's compute_accelerations() as a differentiable function of CUDA tensors `positions` (n,3) and `masses`
     (n,) of one dtype, float32 or float64: a_i = G sum_{j != i} m_j (x_j - x_i) (|x_j - x_i|^2 + softening^2)^(-3/2)."""
     return DirectAccelFn.apply(positions, masses, g_const, softening)
+
+
+class DirectAccelJerkFn(Function):
+    """(a, j) = the all-pairs acceleration and jerk of `positions`, `velocities` (n,3) and `masses` (n,), float32 or
+    float64, differentiable with respect to all three (csrc/direct_hermite_grad.hip; not to g_const or softening, and
+    once). Forward: the pack and the force entry of HermiteSimulator.compute_accelerations_and_jerks() in that dtype, so
+    its bits -- nbd_accel_jerk_f32 with the scalars rounded as the simulator rounds them, nbd_accel_jerk_f64 with the
+    Python doubles. The node saves its own packed rows (32 or 64 bytes per body), never views of the caller's tensors,
+    for the reason DirectAccelFn states. A cotangent that is missing arrives as None (set_materialize_grads(False)) and
+    its launches are skipped. Backward: one nbd_accel_jerk_vjp_* call for the gradients that are asked for."""
+
+    @staticmethod
+    def forward(ctx, positions, velocities, masses, g_const, softening):
+        dtype = positions.dtype if isinstance(positions, torch.Tensor) else None
+        if dtype not in (torch.float32, torch.float64):
+            raise _lib.NbdError(f"direct_accel_jerk: positions must be float32 or float64, got {dtype}")
+        n = positions.shape[0] if positions.dim() == 2 else -1
+        pos, vel, mass = (t.detach().contiguous() for t in (positions, velocities, masses))
+        direct._chk(pos, (n, 3), "positions", dtype); direct._chk(vel, (n, 3), "velocities", dtype)
+        direct._chk(mass, (n,), "masses", dtype)
+        ctx.set_materialize_grads(False)
+        ctx.n, ctx.f64, ctx.dev = n, dtype == torch.float64, pos.device
+        if n == 0:
+            z = torch.zeros((0, 3), dtype=dtype, device=pos.device)
+            return z, z.clone()
+        if ctx.f64:
+            ctx.eps2, ctx.g = float(softening) ** 2, float(g_const)
+            rows, vrows = direct.alloc_rows_f64(n, pos.device), direct.alloc_rows_f64(n, pos.device)
+            direct.hermite_f64_pack(pos, vel, mass, rows, vrows)
+            acc, jerk = direct.accel_jerk_f64(rows, vrows, n, ctx.eps2, ctx.g)
+        else:
+            ctx.eps2, ctx.g = direct.f32(float(softening) ** 2), direct.f32(g_const)
+            rows, vrows = direct.alloc_posm(n, pos.device), direct.alloc_posm(n, pos.device)
+            direct.hermite_pack(pos, vel, mass, rows, vrows)
+            acc, jerk = direct.accel_jerk(rows, vrows, n, ctx.eps2, ctx.g)
+        ctx.save_for_backward(rows, vrows)
+        return acc, jerk
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dacc, djerk):
+        wants = ctx.needs_input_grad[:3]
+        n = ctx.n
+        if not any(wants):
+            return None, None, None, None, None
+        if n == 0 or (dacc is None and djerk is None):
+            kw = dict(dtype=torch.float64 if ctx.f64 else torch.float32, device=ctx.dev)
+            return tuple(torch.zeros(s, **kw) if w else None for w, s in zip(wants, ((n, 3), (n, 3), (n,)))) + (None, None)
+        rows, vrows = ctx.saved_tensors
+
+        def packed(cot):                                  # {gx, gy, gz, 0}, zero rows behind n
+            if cot is None:
+                return None
+            out = torch.zeros_like(rows)
+            out[:n, :3] = cot
+            return out
+
+        vjp = direct.accel_jerk_vjp_f64 if ctx.f64 else direct.accel_jerk_vjp
+        gp, gv, gm = vjp(rows, vrows, packed(dacc), packed(djerk), n, ctx.eps2, ctx.g, want_pos=wants[0],
+                         want_vel=wants[1], want_mass=wants[2])
+        return gp, gv, gm, None, None
+
+
+def direct_accel_jerk(positions, velocities, masses, g_const: float = 1.0, softening: float = 0.1):
+    """HermiteSimulator.compute_accelerations_and_jerks() as a differentiable function of CUDA tensors `positions`,
+    `velocities` (n,3) and `masses` (n,) of one dtype, float32 or float64: with d = x_j - x_i, w = v_j - v_i and
+    s = (|d|^2 + softening^2)^(-1/2), a_i = G sum_{j != i} m_j s^3 d and j_i = G sum_{j != i} m_j [s^3 w - 3 s^5 (d.w) d]."""
+    return DirectAccelJerkFn.apply(positions, velocities, masses, g_const, softening)

@@ -727,6 +727,82 @@ def accel_vjp_f64(posd, cotd, n: int, softening_sq: float, g_const: float, grad_
     return grad_pos, grad_mass
 
 
+# ------------------------------------------------ backward of the Hermite force (csrc/direct_hermite_grad.hip)
+def accel_jerk_vjp_workspace(n: int, device) -> torch.Tensor:
+    return alloc_bytes(_lib.lib().nbd_accel_jerk_vjp_workspace_bytes(int(n)), device)
+
+
+def accel_jerk_vjp_f64_workspace(n: int, device, slabs: int = 0) -> torch.Tensor:
+    return alloc_bytes(_lib.lib().nbd_accel_jerk_vjp_f64_workspace_bytes(int(n), int(slabs)), device)
+
+
+def _accel_jerk_vjp(dtype, name, rows, vrows, cota, cotj, n, grads, wants, workspace, need, launch):
+    """What accel_jerk_vjp and accel_jerk_vjp_f64 share: the checks, the outputs that are asked for, the workspace."""
+    _chk_packed(dtype, rows, vrows, n)
+    if cota is None and cotj is None:
+        raise _lib.NbdError(f"{name}: neither cotangent is given")
+    for t, nm in ((cota, "cota"), (cotj, "cotj")):
+        if t is not None:
+            _chk(t, (padded_len(n), 4), nm, dtype)
+    if not any(wants):
+        raise _lib.NbdError(f"{name}: no gradient is asked for")
+    dev = rows.device
+    out = []
+    for g, want, nm, shape in zip(grads, wants, ("grad_pos", "grad_vel", "grad_mass"), ((n, 3), (n, 3), (n,))):
+        if want and g is None:
+            g = torch.empty(shape, dtype=dtype, device=dev)
+        if want:
+            _chk(g, shape, nm, dtype)
+        out.append(g if want else None)
+    if workspace is None:
+        workspace = alloc_bytes(need, dev)
+    if _nbytes(workspace) < need:
+        raise _lib.NbdError(f"{name}: workspace of {_nbytes(workspace)} bytes, {need} needed")
+    if n:
+        with _lib.on_device(dev):
+            launch(out, workspace, _lib.current_stream(dev))
+    return tuple(out)
+
+
+def accel_jerk_vjp(posm, velp, cota, cotj, n: int, softening_sq: float, g_const: float, grad_pos=None, grad_vel=None,
+                   grad_mass=None, workspace=None, want_pos: bool = True, want_vel: bool = True, want_mass: bool = True):
+    """(grad_pos (n,3), grad_vel (n,3), grad_mass (n,)) of L with respect to the positions, velocities and masses packed in
+    posm / velp (as hermite_pack leaves them), for the cotangents dL/da and dL/dj of `accel_jerk`, packed in cota and
+    cotj = {gx, gy, gz, 0} (hermite_pack with a cotangent as the velocities). Either cotangent may be None: with cotj None
+    the results are accel_vjp's bits and grad_vel is zeros. A gradient that is not wanted is None and is not written.
+    The formulas: csrc/direct_hermite_grad.hip."""
+    L = _lib.lib()
+
+    def launch(out, ws, stream):
+        _lib.check(L.nbd_accel_jerk_vjp_f32(
+            posm.data_ptr(), velp.data_ptr(), _lib.ptr(cota), _lib.ptr(cotj), n, float(softening_sq), float(g_const),
+            _lib.ptr(out[0]), _lib.ptr(out[1]), _lib.ptr(out[2]), ws.data_ptr(), _nbytes(ws), stream),
+            "nbd_accel_jerk_vjp_f32")
+
+    return _accel_jerk_vjp(torch.float32, "accel_jerk_vjp", posm, velp, cota, cotj, n, (grad_pos, grad_vel, grad_mass),
+                           (want_pos, want_vel, want_mass), workspace, L.nbd_accel_jerk_vjp_workspace_bytes(int(n)),
+                           launch)
+
+
+def accel_jerk_vjp_f64(posd, veld, cota, cotj, n: int, softening_sq: float, g_const: float, grad_pos=None,
+                       grad_vel=None, grad_mass=None, workspace=None, slabs: int = 0, want_pos: bool = True,
+                       want_vel: bool = True, want_mass: bool = True):
+    """accel_jerk_vjp in float64 (rows as hermite_f64_pack leaves them). slabs: 0 = the plan's source split."""
+    if not 0 <= int(slabs) <= 64:
+        raise _lib.NbdError(f"accel_jerk_vjp_f64: slabs must be in [0, 64], got {slabs}")
+    L = _lib.lib()
+
+    def launch(out, ws, stream):
+        _lib.check(L.nbd_accel_jerk_vjp_f64(
+            posd.data_ptr(), veld.data_ptr(), _lib.ptr(cota), _lib.ptr(cotj), n, float(softening_sq), float(g_const),
+            _lib.ptr(out[0]), _lib.ptr(out[1]), _lib.ptr(out[2]), ws.data_ptr(), _nbytes(ws), int(slabs), stream),
+            "nbd_accel_jerk_vjp_f64")
+
+    return _accel_jerk_vjp(F64, "accel_jerk_vjp_f64", posd, veld, cota, cotj, n, (grad_pos, grad_vel, grad_mass),
+                           (want_pos, want_vel, want_mass), workspace,
+                           L.nbd_accel_jerk_vjp_f64_workspace_bytes(int(n), int(slabs)), launch)
+
+
 # ---------------------------------------------------- block-timestep Hermite integrator (csrc/direct_hermite_block.hip)
 HBLOCK_SCHED_INTS = 32          # NBD_HBLOCK_SCHED_INTS: {t_next, n_act, clamped, ...} of the block schedule
 
