@@ -450,6 +450,28 @@ int nbd_potential_f64(const double* posd, int n, double softening_sq, double g_c
 int nbd_invariants_state_f64(const double* pos, const double* vel, const double* mass, const double* phi, int n,
                              double* out_row, nbd_stream_t stream);
 
+/* ---- double-precision leapfrog (csrc/direct_leapfrog_f64.hip): the steps of nbd_leapfrog_step_f32 and
+ * nbd_euler_step_f32 and the acceleration on its own, in the number format of "double-precision Hermite" above: fp64
+ * state, scalars, pair arithmetic and sums, posd as described there (no veld: no velocity row is read by the force).
+ * Every product and sum of the O(N) updates rounds on its own. Deterministic (the workspace may hold anything on entry)
+ * and capturable. A workspace of nbd_hermite_f64_workspace_bytes(n) bytes is large enough for every entry at slabs = 0. */
+/* slabs * 3 * n doubles; slabs = 0: the slab count of nbd_hermite_f64_plan(n). 0 for n <= 0 or slabs outside [0, 64]. */
+size_t nbd_accel_f64_workspace_bytes(int n, int slabs);
+/* acc_out, double (n,3), of all n bodies of posd: for every n and every slab count (0: the plan's; [1, 64]: explicit, as
+ * nbd_accel_jerk_f64 takes one) the bits of nbd_accel_jerk_f64's acc_out at that slab count. */
+int nbd_accel_f64(const double* posd, int n, double softening_sq, double g_const, double* acc_out, void* workspace,
+                  size_t workspace_bytes, int slabs, nbd_stream_t stream);
+/* One kick-drift-kick step, three launches: v += dt_half acc_in, x += dt v, posd = {x, m}; acc_out = a(x); v += dt_half
+ * acc_out. pos, vel in place; acc_in may alias acc_out; posd is left at the post-step positions. */
+int nbd_leapfrog_step_f64(double* pos, double* vel, const double* acc_in, double* acc_out, const double* mass, int n,
+                          double dt_half, double dt, double softening_sq, double g_const, double* posd, void* workspace,
+                          size_t workspace_bytes, nbd_stream_t stream);
+/* One Euler step, three launches, in the reference's order: posd = {x, m}; acc_out = a(x); v += dt acc_out, x += dt v.
+ * posd is left at the positions from BEFORE the drift, as nbd_euler_step_f32 leaves posm. */
+int nbd_euler_step_f64(double* pos, double* vel, double* acc_out, const double* mass, int n, double dt,
+                       double softening_sq, double g_const, double* posd, void* workspace, size_t workspace_bytes,
+                       nbd_stream_t stream);
+
 /* ---- double-precision range-sharded Hermite step (csrc/direct_hermite_shard_f64.hip): "range-sharded Hermite step" in
  * the number format of "double-precision Hermite". State, masses, a, j, G, softening_sq, dt and the pair arithmetic are
  * fp64; a rank that owns every body gets nbd_accel_jerk_f64's bits. The exchanged row is 8 doubles (64 bytes),

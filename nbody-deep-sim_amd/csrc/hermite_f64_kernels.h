@@ -1,8 +1,9 @@
 // hermite_f64_kernels.h -- what the double-precision Hermite translation units share (direct_hermite_f64.hip: all targets,
 // shared timestep, and the diagnostics; direct_hermite_block_f64.hip: an active list of targets, block timesteps;
-// direct_batch_hermite_f64.hip: many independent systems, shared timestep per system, and their diagnostics): the
+// direct_batch_hermite_f64.hip: many independent systems, shared timestep per system, and their diagnostics;
+// direct_leapfrog_f64.hip: the acceleration alone, for the leapfrog and Euler steps): the
 // packed-row type and its alignment checks, the reciprocal square root (rsqrt_f64), the pair functors (AccelJerkPair:
-// acceleration plus jerk; PotentialPair, EnergyPair: the diagnostics), the finishing sums of the diagnostics
+// acceleration plus jerk; AccelPair: its acceleration alone; PotentialPair, EnergyPair: the diagnostics), the finishing sums of the diagnostics
 // (potential_finish_f64, energy_finish_f64, F64State), the wave body that walks the source chunks with a functor
 // (walk_f64) and the geometry of a pair launch (F64Plan, plan_f64). As in hermite_kernels.h there is one copy of every
 // rounded operation: a block step whose active list is every body, or a scene of a batch, has the shared step's bits
@@ -86,6 +87,36 @@ struct AccelJerkPair {
   }
 
   __device__ __forceinline__ double out(int k) const { return k < 3 ? acc[k] : acc[k] - 3.0 * acc[k + 3]; }
+};
+
+// a_i = sum_j m_j r_ij s^3 alone (direct_leapfrog_f64.hip): AccelJerkPair::pair's operations for acc[0..2], one for one
+// and in the same order, so the sums are that functor's bits; no velocity row is loaded and no second array streamed.
+struct AccelPair {
+  static constexpr bool kVel = false;
+  static constexpr int kOut = 3;
+  double xi, yi, zi, e2;
+  double acc[3];
+  int i, n;
+
+  __device__ __forceinline__ AccelPair(const d4 tp, double eps2, int i_, int n_)
+      : xi(tp.x), yi(tp.y), zi(tp.z), e2(eps2), acc{0.0, 0.0, 0.0}, i(i_), n(n_) {}
+
+  template <bool MASKED>
+  __device__ __forceinline__ void pair(const d4 p, const d4, int j) {
+    const double dx = p.x - xi, dy = p.y - yi, dz = p.z - zi;      // r_j - r_i
+    double r2 = __builtin_fma(dx, dx, e2);
+    r2 = __builtin_fma(dy, dy, r2);
+    r2 = __builtin_fma(dz, dz, r2);
+    double s = rsqrt_f64(r2);
+    if (MASKED) s = (j < n && j != i) ? s : 0.0;
+    const double s2 = s * s;
+    const double w = (s2 * s) * p.w;
+    acc[0] = __builtin_fma(w, dx, acc[0]);
+    acc[1] = __builtin_fma(w, dy, acc[1]);
+    acc[2] = __builtin_fma(w, dz, acc[2]);
+  }
+
+  __device__ __forceinline__ double out(int k) const { return acc[k]; }
 };
 
 // ---- the pair functors of the diagnostics

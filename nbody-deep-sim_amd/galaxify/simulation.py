@@ -42,6 +42,11 @@ and run() in captured chunks (csrc/direct_batch_hermite_f64.hip; DESIGN.md K-BH6
 Tenth addition: `HermiteSimulator.compute_accelerations_and_jerks()` is differentiable in the same way, with respect to
 `positions`, `velocities` and `masses` (csrc/direct_hermite_grad.hip; `nbd.autograd.direct_accel_jerk` is the function form;
 DESIGN.md K-HVJP). `BlockHermiteSimulator` inherits it; `BatchedSimulator` does not have it.
+
+Eleventh addition: `LeapFrogSimulator(dtype=torch.float64)` and `EulerSimulator(dtype=torch.float64)`, the reference's two
+schemes with float64 state, scalars and pair arithmetic (csrc/direct_leapfrog_f64.hip): un-sharded, run()
+eager. The default stays float32 and takes the paths it took. The float64 `compute_accelerations()` of every simulator is
+that unit's acceleration-only kernel, bit-identical to the acceleration of the Hermite force.
 """
 from __future__ import annotations
 
@@ -209,8 +214,9 @@ class _ChunkedRun:
 
 class _Float32:
     """The float32 number format: every nbd.direct call of a simulator `s` that depends on the format (the object keeps no
-    state of its own). BaseSimulator uses the diagnostics, the Hermite simulators all of it; `_Float64` has the same
-    methods. Packed sources: `s._posm` = {x, y, z, m} (BaseSimulator's) and `s._velp` = {vx, vy, vz, 0}.
+    state of its own). BaseSimulator uses the diagnostics, LeapFrogSimulator and EulerSimulator the scratch and the step
+    of theirs as well (`_base_scratch`, `_leapfrog_step`, `_euler_step`), the Hermite simulators the rest; `_Float64` has
+    the same methods. Packed sources: `s._posm` = {x, y, z, m} (BaseSimulator's) and `s._velp` = {vx, vy, vz, 0}.
     Scalars: eps^2 and G are the fp32 values formed AT CONSTRUCTION (`s._eps2`, `s._g`: a later change of `softening` or
     `g_const` does not reach the force); the energies read `s.softening`, and the step `s.dt`, at the launch. _Float64 reads
     all three at every launch. A quirk, kept as it was found: unifying it would change results."""
@@ -218,6 +224,7 @@ class _Float32:
     dtype = torch.float32
     capturable = True               # run() may capture chunks of steps
     shardable = True                # there is a range-sharded step
+    leapfrog_shardable = True       # ... and a range-sharded leapfrog / Euler step
 
     def bind_scalars(self, s):
         # fp32 scalars exactly as torch forms them from the Python doubles (simulation.py:82,88,164)
@@ -239,6 +246,18 @@ class _Float32:
             s._hws = direct.hermite_shard_workspace(s.n, part.lo, part.n_local, s.device) if part.n_local else None
             s._hgather = nbd_dist.RowGather(part, direct.HERMITE_ROW, torch.float32, s.device, s.process_group,
                                             collective=True)
+
+    def _base_scratch(self, s):
+        """BaseSimulator's scratch (LeapFrogSimulator, EulerSimulator) and the first force."""
+        s._init_scratch()
+
+    # the un-sharded leapfrog and Euler steps (LeapFrogSimulator, EulerSimulator): acc_out may be acc_in
+    def _leapfrog_step(self, s, acc_in, acc_out):
+        direct.leapfrog_step(s.positions, s.velocities, acc_in, acc_out, s.masses, direct.f32(0.5 * s.dt),
+                             direct.f32(s.dt), s._eps2, s._g, s._posm, s._ws, uniform=s._uniform)
+
+    def _euler_step(self, s, acc_out):
+        direct.euler_step(s.positions, s.velocities, acc_out, s.masses, direct.f32(s.dt), s._eps2, s._g, s._posm, s._ws)
 
     def pack(self, s):
         """posm[:n] = {x,y,z,m} of ALL bodies in global order (one all-gather when sharded)."""
@@ -297,7 +316,7 @@ class _Float32:
 
 class _Float64:
     """The float64 number format of the Hermite simulators (csrc/direct_hermite_f64.hip, direct_hermite_block_f64.hip,
-    direct_hermite_shard_f64.hip): `_Float32`'s methods over the float64 entries; nothing of the fp32 paths is allocated
+    direct_hermite_shard_f64.hip) and of LeapFrogSimulator and EulerSimulator (csrc/direct_leapfrog_f64.hip): `_Float32`'s methods over the float64 entries; nothing of the fp32 paths is allocated
     or launched. Packed sources: `s._posd` = {x, y, z, m}, `s._veld` = {vx, vy, vz, 0}; a step leaves `_posd` at the
     post-step state, and the invariants come from the state arrays. Sharded, the step works on 8-double rows
     (`_rows_local`, `_rows_all`) and only the energies pack `posd` rows, of the gathered state, per call. Scalars:
@@ -307,6 +326,7 @@ class _Float64:
     dtype = torch.float64
     capturable = False              # run() is eager: there is no captured form
     shardable = True                # there is a range-sharded step
+    leapfrog_shardable = False      # ... but no range-sharded leapfrog or Euler step
 
     def bind_scalars(self, s):           # nothing is formed at construction
         pass
@@ -333,8 +353,25 @@ class _Float64:
         if not s._sharded:          # (sharded, only the energies read packed rows of all bodies: they pack them)
             direct.hermite_f64_pack(s.positions, s.velocities, s.masses, s._posd, s._veld)
 
+    def _base_scratch(self, s):
+        """The un-sharded scratch of hermite_scratch (`_posd`, `_veld`, `_hws`: the pack, the energies, the potentials and
+        the invariants work on it as they are) and the first force."""
+        self.hermite_scratch(s)
+        s.accelerations = s.compute_accelerations()
+
+    # csrc/direct_leapfrog_f64.hip; dt/2 is formed here, in Python
+    def _leapfrog_step(self, s, acc_in, acc_out):
+        direct.leapfrog_step_f64(s.positions, s.velocities, acc_in, acc_out, s.masses, 0.5 * s.dt, s.dt,
+                                 *self._scalars(s), s._posd, s._hws)
+
+    def _euler_step(self, s, acc_out):
+        direct.euler_step_f64(s.positions, s.velocities, acc_out, s.masses, s.dt, *self._scalars(s), s._posd, s._hws)
+
     def accel(self, s):
-        return s.compute_accelerations_and_jerks()[0]
+        if s._sharded:              # (the sharded Hermite step's force; there is no sharded leapfrog in this format)
+            return s.compute_accelerations_and_jerks()[0]
+        self.pack(s)
+        return direct.accel_f64(s._posd, s.n, *self._scalars(s), workspace=s._hws)
 
     def accel_jerk(self, s):
         self.pack(s)
@@ -388,14 +425,30 @@ class BaseSimulator(_ChunkedRun):
     # accelerations; and
     _posm_after_step = False        # step() leaves _posm at the post-step positions (else the energies repack first)
     _equal_mass_step = False        # the un-sharded step() has an equal-mass form (`_uniform`)
-    _fmt = _FORMATS[torch.float32]  # the number format; HermiteSimulator chooses its own from `dtype`
+    _fmt = _FORMATS[torch.float32]  # the number format; the constructors choose it from `dtype`
 
     def __init__(self, *, positions, velocities, masses, g_const: float = 1.0, softening: float = 0.1,
                  dt: float = 0.01, calc_energy: bool = True, device: str = None, process_group=None,
-                 calc_invariants: bool = False):
+                 calc_invariants: bool = False, **format_kw):
+        # format_kw: `dtype` (default torch.float32), the one keyword of the number format, taken as BatchedSimulator
+        # takes it; any other name is refused as an unknown keyword is.
+        dtype = format_kw.pop("dtype", torch.float32)
+        if format_kw:
+            raise TypeError(f"{type(self).__name__}.__init__() got an unexpected keyword argument "
+                            f"{next(iter(format_kw))!r}")
+        self._check_format(dtype, process_group)         # before anything is resolved, allocated or launched
+        self._fmt = _FORMATS[dtype]                      # the only place the format is chosen
         self._init_state(positions, velocities, masses, g_const, softening, dt, calc_energy, device, process_group,
                          calc_invariants)
-        self._init_scratch()
+        self._fmt._base_scratch(self)
+
+    @classmethod
+    def _check_format(cls, dtype, process_group):
+        if dtype not in _FORMATS:
+            raise ValueError(f"{cls.__name__}: dtype must be torch.float32 or torch.float64, got {dtype!r}")
+        if process_group is not None and not _FORMATS[dtype].leapfrog_shardable:
+            raise ValueError(f"{cls.__name__}: dtype={dtype} has no range-sharded form; process_group is not supported "
+                             "with it")
 
     def _init_state(self, positions, velocities, masses, g_const, softening, dt, calc_energy, device, process_group,
                     calc_invariants):
@@ -686,19 +739,23 @@ class BaseSimulator(_ChunkedRun):
 
 
 class LeapFrogSimulator(BaseSimulator):
+    """The reference's kick-drift-kick integrator. With `dtype=torch.float64` (csrc/direct_leapfrog_f64.hip; DESIGN.md
+    K-L64) positions, velocities, masses and accelerations are float64 device tensors (the inputs are converted directly,
+    not through float32), g_const, softening ** 2, dt and dt / 2 go to the kernels as the Python doubles, and step(), the
+    compute_*() methods and run() are float64 end to end; run() is eager and there is no range-sharded form in this mode."""
+
     def step(self):
         """Kick-drift-kick (simulation.py:153-170); one force evaluation per step; positions and
         velocities are updated in place, `accelerations` is rebound to a new tensor (:168)."""
         if self.n == 0:
             return
-        half = direct.f32(0.5 * self.dt)
-        dt = direct.f32(self.dt)
         if not self._sharded:
             new_acc = torch.empty_like(self.accelerations)
-            direct.leapfrog_step(self.positions, self.velocities, self.accelerations, new_acc, self.masses,
-                                 half, dt, self._eps2, self._g, self._posm, self._ws, uniform=self._uniform)
+            self._fmt._leapfrog_step(self, self.accelerations, new_acc)
             self.accelerations = new_acc
             return
+        half = direct.f32(0.5 * self.dt)
+        dt = direct.f32(self.dt)
         # sharded: kick+drift+pack of the own bodies -> all-gather in flight || own x own force block ->
         # own x remote block + slab sum + second kick. Four launches and one collective.
         if self._step_graph is not None:                 # capture_step(): the same launches and the collective, replayed
@@ -710,9 +767,7 @@ class LeapFrogSimulator(BaseSimulator):
     _equal_mass_step = True
 
     def _step_in_place(self):
-        direct.leapfrog_step(self.positions, self.velocities, self._acc_g, self._acc_g, self.masses,
-                             direct.f32(0.5 * self.dt), direct.f32(self.dt), self._eps2, self._g, self._posm, self._ws,
-                             uniform=self._uniform)
+        self._fmt._leapfrog_step(self, self._acc_g, self._acc_g)
 
     def _sharded_launches(self, acc, half, dt, ev=None) -> torch.Tensor:
         """The range-sharded step's launches from the accelerations `acc`; returns the new ones. `ev`: five events, ev[0]
@@ -784,25 +839,25 @@ class LeapFrogSimulator(BaseSimulator):
 
 
 class EulerSimulator(BaseSimulator):
+    """The reference's Euler integrator; `dtype=torch.float64` as in LeapFrogSimulator."""
+
     def step(self):
         """a(t) -> v += dt a -> x += dt v (simulation.py:173-187)."""
         if self.n == 0:
             return
-        dt = direct.f32(self.dt)
         if not self._sharded:
             new_acc = torch.empty_like(self.accelerations)
-            direct.euler_step(self.positions, self.velocities, new_acc, self.masses, dt, self._eps2,
-                              self._g, self._posm, self._ws)
+            self._fmt._euler_step(self, new_acc)
             self.accelerations = new_acc
             return
+        dt = direct.f32(self.dt)
         self._pack_local()
         self.accelerations = self._force_sharded(self.velocities, dt)        # a(t), v += dt a fused
         if self.part.n_local:
             direct.drift(self.positions, self.velocities, dt)
 
     def _step_in_place(self):           # (packs _posm before its drift: _posm_after_step stays False)
-        direct.euler_step(self.positions, self.velocities, self._acc_g, self.masses, direct.f32(self.dt), self._eps2,
-                          self._g, self._posm, self._ws)
+        self._fmt._euler_step(self, self._acc_g)
 
 
 class HermiteSimulator(BaseSimulator):

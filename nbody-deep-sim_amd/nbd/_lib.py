@@ -252,6 +252,13 @@ SIGNATURES = {
     "nbd_energy_f64": (c_int, [c_void_p, c_void_p, c_int, c_double, c_double, c_void_p, c_void_p, c_size_t, c_void_p]),
     "nbd_potential_f64": (c_int, [c_void_p, c_int, c_double, c_double, c_void_p, c_void_p, c_size_t, c_void_p]),
     "nbd_invariants_state_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
+    # --- double-precision leapfrog (csrc/direct_leapfrog_f64.hip)
+    "nbd_accel_f64_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "nbd_accel_f64": (c_int, [c_void_p, c_int, c_double, c_double, c_void_p, c_void_p, c_size_t, c_int, c_void_p]),
+    "nbd_leapfrog_step_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_double, c_double,
+                                      c_double, c_double, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "nbd_euler_step_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_double, c_double, c_double, c_void_p,
+                                   c_void_p, c_size_t, c_void_p]),
     # --- double-precision range-sharded Hermite step (csrc/direct_hermite_shard_f64.hip)
     "nbd_hermite_shard_f64_plan": (c_int, [c_int, c_int, c_int, POINTER(c_int), POINTER(c_int), POINTER(c_int),
                                            POINTER(c_int)]),

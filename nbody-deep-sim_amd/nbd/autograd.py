@@ -588,7 +588,7 @@ class DirectAccelFn(Function):
     """a = the all-pairs acceleration of `positions` (n,3) and `masses` (n,), float32 or float64, differentiable with
     respect to both (csrc/direct_grad.hip; not to g_const or softening, and once). Forward: the force kernel of that
     dtype, so the bits of compute_accelerations() -- nbd_accel_f32 with the scalars rounded as BaseSimulator rounds them,
-    nbd_accel_jerk_f64 with zero velocity rows (the jerk is dropped). The node saves its own packed copy of the inputs
+    nbd_accel_f64 from the packed positions alone (the bits of nbd_accel_jerk_f64's acceleration). The node saves its own packed copy of the inputs
     (16 or 32 bytes per body), never a view of the caller's tensors: the simulators' kernels write state through raw
     pointers, which torch's version counters do not see. Backward: one nbd_accel_vjp_* launch pair for both gradients."""
 
@@ -605,9 +605,9 @@ class DirectAccelFn(Function):
             return torch.zeros((0, 3), dtype=dtype, device=pos.device)
         if ctx.f64:
             ctx.eps2, ctx.g = float(softening) ** 2, float(g_const)
-            rows, zero_rows = direct.alloc_rows_f64(n, pos.device), direct.alloc_rows_f64(n, pos.device)
-            direct.hermite_f64_pack(pos, torch.zeros_like(pos), mass, rows, zero_rows)
-            acc = direct.accel_jerk_f64(rows, zero_rows, n, ctx.eps2, ctx.g)[0]
+            rows = direct.alloc_rows_f64(n, pos.device)
+            direct.hermite_f64_pack(pos, pos, mass, rows, direct.alloc_rows_f64(n, pos.device))   # (veld is not read)
+            acc = direct.accel_f64(rows, n, ctx.eps2, ctx.g)
         else:
             ctx.eps2, ctx.g = direct.f32(float(softening) ** 2), direct.f32(g_const)
             rows = direct.pack_posm(pos, mass)

@@ -592,6 +592,59 @@ def invariants_state_f64(pos, vel, mass, phi, out=None) -> torch.Tensor:
     return out
 
 
+# ---------------------------------------------------------- double-precision leapfrog (csrc/direct_leapfrog_f64.hip)
+def accel_f64_workspace(n: int, device, slabs: int = 0) -> torch.Tensor:
+    """The partial sums of accel_f64 at n bodies: 3 doubles per body and slab (slabs: 0 = the plan's)."""
+    return alloc_bytes(_lib.lib().nbd_accel_f64_workspace_bytes(int(n), int(slabs)), device)
+
+
+def accel_f64(posd, n: int, softening_sq: float, g_const: float, workspace=None, slabs: int = 0, out=None):
+    """The all-pairs acceleration in float64: new (n,3) float64, the bits of accel_jerk_f64's acceleration at the same
+    slab count, from posd alone. slabs: 0 = the plan's source split, else that many."""
+    _chk_packed(F64, posd, None, n)
+    dev = posd.device
+    if out is None:
+        out = torch.empty((n, 3), dtype=F64, device=dev)
+    _chk(out, (n, 3), "acc_out", F64)
+    if workspace is None:                       # a given workspace is checked by the entry, against what this call uses
+        workspace = accel_f64_workspace(n, dev, slabs)
+    with _lib.on_device(dev):
+        _lib.check(_lib.lib().nbd_accel_f64(
+            posd.data_ptr(), n, float(softening_sq), float(g_const), out.data_ptr(), workspace.data_ptr(),
+            _nbytes(workspace), int(slabs), _lib.current_stream(dev)), "nbd_accel_f64")
+    return out
+
+
+def leapfrog_step_f64(pos, vel, acc_in, acc_out, mass, dt_half: float, dt: float, softening_sq: float, g_const: float,
+                      posd, workspace) -> None:
+    """leapfrog_step in float64 (three launches): pos, vel in place; acc_out may be acc_in; posd = {x1, m}. dt_half, dt,
+    softening_sq and g_const go in as the Python doubles."""
+    n = pos.shape[0]
+    for t, nm in ((pos, "pos"), (vel, "vel"), (acc_in, "acc_in"), (acc_out, "acc_out")):
+        _chk(t, (n, 3), nm, F64)
+    _chk(mass, (n,), "mass", F64)
+    _chk_packed(F64, posd, None, n)
+    with _lib.on_device(pos.device):
+        _lib.check(_lib.lib().nbd_leapfrog_step_f64(
+            pos.data_ptr(), vel.data_ptr(), acc_in.data_ptr(), acc_out.data_ptr(), mass.data_ptr(), n, float(dt_half),
+            float(dt), float(softening_sq), float(g_const), posd.data_ptr(), workspace.data_ptr(), _nbytes(workspace),
+            _lib.current_stream(pos.device)), "nbd_leapfrog_step_f64")
+
+
+def euler_step_f64(pos, vel, acc_out, mass, dt: float, softening_sq: float, g_const: float, posd, workspace) -> None:
+    """euler_step in float64 (three launches): acc_out = a(x), v += dt a, x += dt v; posd keeps the positions from before
+    the drift."""
+    n = pos.shape[0]
+    for t, nm in ((pos, "pos"), (vel, "vel"), (acc_out, "acc_out")):
+        _chk(t, (n, 3), nm, F64)
+    _chk(mass, (n,), "mass", F64)
+    _chk_packed(F64, posd, None, n)
+    with _lib.on_device(pos.device):
+        _lib.check(_lib.lib().nbd_euler_step_f64(
+            pos.data_ptr(), vel.data_ptr(), acc_out.data_ptr(), mass.data_ptr(), n, float(dt), float(softening_sq),
+            float(g_const), posd.data_ptr(), workspace.data_ptr(), _nbytes(workspace),
+            _lib.current_stream(pos.device)), "nbd_euler_step_f64")
+
 
 # ----------------------- double-precision range-sharded Hermite step (csrc/direct_hermite_shard_f64.hip)
 def alloc_hermite_rows_f64(n: int, device) -> torch.Tensor:
