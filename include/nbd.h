@@ -450,6 +450,37 @@ int nbd_potential_f64(const double* posd, int n, double softening_sq, double g_c
 int nbd_invariants_state_f64(const double* pos, const double* vel, const double* mass, const double* phi, int n,
                              double* out_row, nbd_stream_t stream);
 
+/* ---- 6th-order Hermite (csrc/direct_hermite6_f64.hip): the shared-timestep 6th-order Hermite step (Nitadori & Makino
+ * 2008) in the number format of "double-precision Hermite" above -- fp64 state, scalars, pair arithmetic and sums; there
+ * is no fp32 form. The force evaluation carries the snap s = d^2 a / dt^2 and streams a third array of packed rows,
+ *   accd : double[nbd_posm_padded_len(n)][4] = {ax, ay, az, 0}, 32-byte aligned, zero rows behind n, as veld.
+ * With r = x_j - x_i, v = v_j - v_i, a = a_j - a_i, s = (|r|^2 + softening_sq)^(-1/2), w = m_j s^3, alpha = (r.v) s^2 and
+ * gamma = (v.v + r.a) s^2 the pair terms are A = w r, J = w v - 3 alpha w r, S = w a - 6 alpha w v + (15 alpha^2 -
+ * 3 gamma) w r. i == j, massless bodies, determinism and capturability as above. The acceleration and the jerk are the
+ * bits of nbd_accel_jerk_f64 at the same slab count. */
+/* plan_f64(n).slabs * 9 * n * 8: 9 doubles per body and slab (the slab count is nbd_hermite_f64_plan's). */
+size_t nbd_hermite6_f64_workspace_bytes(int n);
+/* posd = {x_p, m}, veld = {v_p, 0}, accd = {a_p, 0}: the state predicted over dt by the Taylor series to the crackle
+ * c = d^3 a / dt^3. With jerk, snap and crackle all null a plain pack of (pos, vel, acc), and a null acc gives zero rows;
+ * jerk, snap and crackle are given together, with acc. All arrays double (n,3); mass: double (n). */
+int nbd_hermite6_f64_pack(const double* pos, const double* vel, const double* acc, const double* jerk,
+                          const double* snap, const double* crackle, const double* mass, int n, double dt, double* posd,
+                          double* veld, double* accd, nbd_stream_t stream);
+/* The force alone: acc_out, jerk_out and snap_out, double (n,3), of all n bodies of posd / veld / accd. slabs: 0 for the
+ * plan's split of the sources, or an explicit slab count in [1, 64] (the workspace then needs slabs * 9 * n doubles). */
+int nbd_accel_jerk_snap_f64(const double* posd, const double* veld, const double* accd, int n, double softening_sq,
+                            double g_const, double* acc_out, double* jerk_out, double* snap_out, void* workspace,
+                            size_t workspace_bytes, int slabs, nbd_stream_t stream);
+/* One step, three launches (predict, evaluate, correct): pos, vel in place; acc_out, jerk_out, snap_out = a1, j1, s1 at
+ * the predicted state; crackle_out = the third derivative at t1 of the quintic through (a, j, s) at both ends. Every
+ * output may alias its input. posd = {x1, m}; veld and accd are scratch. Workspace: nbd_hermite6_f64_workspace_bytes(n),
+ * 8-byte aligned. */
+int nbd_hermite6_step_f64(double* pos, double* vel, const double* acc_in, const double* jerk_in, const double* snap_in,
+                          const double* crackle_in, double* acc_out, double* jerk_out, double* snap_out,
+                          double* crackle_out, const double* mass, int n, double dt, double softening_sq, double g_const,
+                          double* posd, double* veld, double* accd, void* workspace, size_t workspace_bytes,
+                          nbd_stream_t stream);
+
 /* ---- double-precision leapfrog (csrc/direct_leapfrog_f64.hip): the steps of nbd_leapfrog_step_f32 and
  * nbd_euler_step_f32 and the acceleration on its own, in the number format of "double-precision Hermite" above: fp64
  * state, scalars, pair arithmetic and sums, posd as described there (no veld: no velocity row is read by the force).

@@ -964,6 +964,84 @@ class HermiteSimulator(BaseSimulator):
         self._fmt.hermite_step(self, self._acc_g, self._jerk_g, self._acc_g, self._jerk_g)
 
 
+class Hermite6Simulator(HermiteSimulator):
+    """Shared-timestep 6th-order Hermite predictor-corrector (Nitadori & Makino 2008) in float64
+    (csrc/direct_hermite6_f64.hip), an extension the reference does not have. The force evaluation carries
+    one more derivative than HermiteSimulator's, the snap s = d^2 a / dt^2, and still runs once per step. With a0, j0, s0
+    and the crackle c0 = d^3 a / dt^3 carried from the previous step:
+        predict  x_p = x + v dt + a0 dt^2/2 + j0 dt^3/6 + s0 dt^4/24 + c0 dt^5/120
+                 v_p = v + a0 dt + j0 dt^2/2 + s0 dt^3/6 + c0 dt^4/24
+                 a_p = a0 + j0 dt + s0 dt^2/2 + c0 dt^3/6
+        evaluate a1, j1, s1 at (x_p, v_p, a_p)
+        correct  v1 = v + (a0 + a1) dt/2 - (j1 - j0) dt^2/10 + (s0 + s1) dt^3/120
+                 x1 = x + (v + v1) dt/2 - (a1 - a0) dt^2/10 + (j0 + j1) dt^3/120
+                 c1 = [60 (a1 - a0) - dt (36 j1 + 24 j0) + dt^2 (9 s1 - 3 s0)] / dt^3
+    At construction the acceleration comes first (the inherited evaluation), then the evaluation with that acceleration
+    as the third source array gives the snap, and c = 0.
+
+    `accelerations`, `jerks`, `snaps` and `crackles` are (n,3) float64 device tensors that hold the values at the last
+    predicted state; step() rebinds them. positions, velocities and masses are float64 as for
+    HermiteSimulator(dtype=torch.float64), whose compute_energies(), compute_potentials(), compute_invariants(), gather()
+    and eager run() work here unchanged. The only number format is float64 (`dtype` defaults to it): the fp32 Hermite run
+    already sits on the fp32 floor at a few dozen steps, so a higher order buys nothing there. There is no range-sharded,
+    batched, block-timestep, captured or differentiable form."""
+
+    def __init__(self, *, positions, velocities, masses, g_const: float = 1.0, softening: float = 0.1,
+                 dt: float = 0.01, calc_energy: bool = True, device: str = None, process_group=None,
+                 calc_invariants: bool = False, **format_kw):
+        # all refusals before anything is resolved, allocated or launched
+        dtype = format_kw.pop("dtype", torch.float64)
+        if format_kw:
+            raise TypeError(f"{type(self).__name__}.__init__() got an unexpected keyword argument "
+                            f"{next(iter(format_kw))!r}")
+        if dtype is not torch.float64:
+            raise ValueError(f"Hermite6Simulator: dtype must be torch.float64, got {dtype!r}: the 4th-order fp32 run "
+                             "already sits on the fp32 floor, so there is no fp32 form of the 6th-order scheme")
+        if process_group is not None:
+            raise ValueError("Hermite6Simulator: there is no range-sharded 6th-order step; process_group is not "
+                             "supported")
+        self.jerks = self.snaps = self.crackles = None
+        self._fmt = _FORMATS[torch.float64]
+        self._init_state(positions, velocities, masses, g_const, softening, dt, calc_energy, device, None,
+                         calc_invariants)
+        self._fmt.hermite_scratch(self)
+        # the third source array, and one workspace for every entry: 9 doubles per body and slab, where the inherited
+        # force and the diagnostics need at most 6
+        self._accd = direct.alloc_rows_f64(self.n, self.device)
+        self._hws = direct.hermite6_workspace(max(self.n, 1), self.device)
+        self.accelerations, self.jerks, self.snaps = self.compute_accelerations_jerks_and_snaps()
+        self.crackles = torch.zeros_like(self.snaps)
+
+    def compute_accelerations_jerks_and_snaps(self):
+        """(a, j, s) of the current state as new (n,3) float64 tensors, in two passes: the acceleration first, then the
+        evaluation that takes it as the third source array,
+            s_i = G sum_{j!=i} m_j s^3 (a_ij - 6 alpha v_ij + (15 alpha^2 - 3 gamma) r_ij),
+            alpha = (r_ij.v_ij) s^2, gamma = (v_ij.v_ij + r_ij.a_ij) s^2, s = (|r_ij|^2 + eps^2)^(-1/2).
+        a and j are compute_accelerations_and_jerks()'s bits. Not differentiable."""
+        if torch.is_grad_enabled() and (self.positions.requires_grad or self.velocities.requires_grad or
+                                        self.masses.requires_grad):
+            raise RuntimeError("Hermite6Simulator.compute_accelerations_jerks_and_snaps(): there is no differentiable "
+                               "form of the snap evaluation; call it under torch.no_grad() or on a detached state")
+        if self.n == 0:
+            z = torch.zeros((0, 3), dtype=torch.float64, device=self.device)
+            return z, z.clone(), z.clone()
+        acc = self._fmt.accel(self)
+        direct.hermite6_pack(self.positions, self.velocities, self.masses, self._posd, self._veld, self._accd, acc=acc)
+        return direct.accel_jerk_snap_f64(self._posd, self._veld, self._accd, self.n, *self._fmt._scalars(self),
+                                          workspace=self._hws)
+
+    def step(self):
+        """One predictor-corrector step: positions and velocities in place, `accelerations`, `jerks`, `snaps` and
+        `crackles` rebound."""
+        if self.n == 0:
+            return
+        cur = (self.accelerations, self.jerks, self.snaps, self.crackles)
+        new = tuple(torch.empty_like(t) for t in cur)
+        direct.hermite6_step_f64(self.positions, self.velocities, *cur, *new, self.masses, self.dt,
+                                 *self._fmt._scalars(self), self._posd, self._veld, self._accd, self._hws)
+        self.accelerations, self.jerks, self.snaps, self.crackles = new
+
+
 class BlockHermiteSimulator(HermiteSimulator):
     """HermiteSimulator with individual block timesteps (Makino & Aarseth 1992), an extension the reference does not have.
     `dt` is the output interval and the longest step: one step() advances every body by dt, in 2^max_level ticks. Body i

@@ -252,6 +252,14 @@ SIGNATURES = {
     "nbd_energy_f64": (c_int, [c_void_p, c_void_p, c_int, c_double, c_double, c_void_p, c_void_p, c_size_t, c_void_p]),
     "nbd_potential_f64": (c_int, [c_void_p, c_int, c_double, c_double, c_void_p, c_void_p, c_size_t, c_void_p]),
     "nbd_invariants_state_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
+    # --- 6th-order Hermite, float64 (csrc/direct_hermite6_f64.hip)
+    "nbd_hermite6_f64_workspace_bytes": (c_size_t, [c_int]),
+    "nbd_hermite6_f64_pack": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                                      c_double, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "nbd_accel_jerk_snap_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_double, c_double, c_void_p, c_void_p,
+                                        c_void_p, c_void_p, c_size_t, c_int, c_void_p]),
+    "nbd_hermite6_step_f64": (c_int, [c_void_p] * 11 + [c_int, c_double, c_double, c_double, c_void_p, c_void_p,
+                                                        c_void_p, c_void_p, c_size_t, c_void_p]),
     # --- double-precision leapfrog (csrc/direct_leapfrog_f64.hip)
     "nbd_accel_f64_workspace_bytes": (c_size_t, [c_int, c_int]),
     "nbd_accel_f64": (c_int, [c_void_p, c_int, c_double, c_double, c_void_p, c_void_p, c_size_t, c_int, c_void_p]),

@@ -592,6 +592,75 @@ def invariants_state_f64(pos, vel, mass, phi, out=None) -> torch.Tensor:
     return out
 
 
+# ---------------------------------------------------------- 6th-order Hermite, float64 (csrc/direct_hermite6_f64.hip)
+def _chk_accd(accd, n: int):
+    """The third packed array {ax, ay, az, 0}: laid out like veld."""
+    _chk(accd, (padded_len(n), 4), "accd", F64)
+
+
+def hermite6_workspace(n: int, device, slabs: int = 0) -> torch.Tensor:
+    """The partial sums of the 6th-order entries at n bodies: 9 doubles per body and slab (or of accel_jerk_snap_f64
+    with an explicit slab count)."""
+    need = _lib.lib().nbd_hermite6_f64_workspace_bytes(int(n))
+    return alloc_bytes(max(need, int(slabs) * 9 * int(n) * 8), device)
+
+
+def hermite6_pack(pos, vel, mass, posd, veld, accd, acc=None, jerk=None, snap=None, crackle=None,
+                  dt: float = 0.0) -> None:
+    """posd = {x_p, m}, veld = {v_p, 0}, accd = {a_p, 0}, predicted over dt from (acc, jerk, snap, crackle); with jerk,
+    snap and crackle all None a plain pack of (pos, vel, acc), and acc None gives zero rows."""
+    n = pos.shape[0]
+    _chk(pos, (n, 3), "pos", F64); _chk(vel, (n, 3), "vel", F64); _chk(mass, (n,), "mass", F64)
+    _chk_packed(F64, posd, veld, n); _chk_accd(accd, n)
+    higher = (jerk, snap, crackle)
+    if len({t is None for t in higher}) != 1 or (jerk is not None and acc is None):
+        raise _lib.NbdError("hermite6_pack: give acc, jerk, snap and crackle, or acc alone, or none of them")
+    for t, nm in ((acc, "acc"), (jerk, "jerk"), (snap, "snap"), (crackle, "crackle")):
+        if t is not None:
+            _chk(t, (n, 3), nm, F64)
+    with _lib.on_device(pos.device):
+        _lib.check(_lib.lib().nbd_hermite6_f64_pack(
+            pos.data_ptr(), vel.data_ptr(), _lib.ptr(acc), _lib.ptr(jerk), _lib.ptr(snap), _lib.ptr(crackle),
+            mass.data_ptr(), n, float(dt), posd.data_ptr(), veld.data_ptr(), accd.data_ptr(),
+            _lib.current_stream(pos.device)), "nbd_hermite6_f64_pack")
+
+
+def accel_jerk_snap_f64(posd, veld, accd, n: int, softening_sq: float, g_const: float, workspace=None, slabs: int = 0):
+    """New (acc, jerk, snap), each (n,3) float64, of the n bodies of the packed rows; acc and jerk are accel_jerk_f64's
+    bits at the same slab count. slabs: 0 = the plan's source split, else that many."""
+    _chk_packed(F64, posd, veld, n); _chk_accd(accd, n)
+    dev = posd.device
+    acc_out, jerk_out, snap_out = (torch.empty((n, 3), dtype=F64, device=dev) for _ in range(3))
+    if workspace is None:                       # a given workspace is checked by the entry, against what this call uses
+        workspace = hermite6_workspace(n, dev, slabs)
+    with _lib.on_device(dev):
+        _lib.check(_lib.lib().nbd_accel_jerk_snap_f64(
+            posd.data_ptr(), veld.data_ptr(), accd.data_ptr(), n, float(softening_sq), float(g_const),
+            acc_out.data_ptr(), jerk_out.data_ptr(), snap_out.data_ptr(), workspace.data_ptr(), _nbytes(workspace),
+            int(slabs), _lib.current_stream(dev)), "nbd_accel_jerk_snap_f64")
+    return acc_out, jerk_out, snap_out
+
+
+def hermite6_step_f64(pos, vel, acc_in, jerk_in, snap_in, crackle_in, acc_out, jerk_out, snap_out, crackle_out, mass,
+                      dt: float, softening_sq: float, g_const: float, posd, veld, accd, workspace) -> None:
+    """One 6th-order Hermite step (three launches): pos, vel in place; every output may be its input; posd = {x1, m};
+    veld and accd are scratch. dt, softening_sq and g_const go in as the Python doubles."""
+    n = pos.shape[0]
+    for t, nm in ((pos, "pos"), (vel, "vel"), (acc_in, "acc_in"), (jerk_in, "jerk_in"), (snap_in, "snap_in"),
+                  (crackle_in, "crackle_in"), (acc_out, "acc_out"), (jerk_out, "jerk_out"), (snap_out, "snap_out"),
+                  (crackle_out, "crackle_out")):
+        _chk(t, (n, 3), nm, F64)
+    _chk(mass, (n,), "mass", F64)
+    _chk_packed(F64, posd, veld, n); _chk_accd(accd, n)
+    with _lib.on_device(pos.device):
+        _lib.check(_lib.lib().nbd_hermite6_step_f64(
+            pos.data_ptr(), vel.data_ptr(), acc_in.data_ptr(), jerk_in.data_ptr(), snap_in.data_ptr(),
+            crackle_in.data_ptr(), acc_out.data_ptr(), jerk_out.data_ptr(), snap_out.data_ptr(), crackle_out.data_ptr(),
+            mass.data_ptr(), n, float(dt), float(softening_sq), float(g_const), posd.data_ptr(), veld.data_ptr(),
+            accd.data_ptr(), workspace.data_ptr(), _nbytes(workspace), _lib.current_stream(pos.device)),
+            "nbd_hermite6_step_f64")
+
+
 # ---------------------------------------------------------- double-precision leapfrog (csrc/direct_leapfrog_f64.hip)
 def accel_f64_workspace(n: int, device, slabs: int = 0) -> torch.Tensor:
     """The partial sums of accel_f64 at n bodies: 3 doubles per body and slab (slabs: 0 = the plan's)."""
