@@ -350,6 +350,49 @@ int nbd_batch_invariants_state_f64(const int* offsets, int n_scenes, const void*
                                    const double* pos, const double* vel, const double* mass, const double* phi,
                                    double* out_rows, nbd_stream_t stream);
 
+/* ---- 6th-order Hermite per scene (csrc/direct_batch_hermite6_f64.hip): "6th-order Hermite" below applied to every scene
+ * of a batch, one set of launches for all scenes. A scene's pos / vel / acc / jerk / snap / crackle are bit-identical to
+ * the nbd_*hermite6* / nbd_accel_jerk_snap_f64 entries on that scene alone with the same parameters, wherever it stands
+ * in the batch.
+ *   plan   : the layout, the items, the rows and the plan_bytes of nbd_batch_f64_plan (ask it for them), filled by
+ *            nbd_batch_hermite6_f64_plan_fill: only each scene's first workspace double differs, counting
+ *            double[slabs][9][n_s] per scene. The float64 diagnostic entries above (nbd_batch_energies_f64,
+ *            nbd_batch_potential_f64, nbd_batch_invariants_state_f64, nbd_batch_pack_f64, nbd_batch_accel_jerk_f64) run
+ *            unchanged on this plan with this workspace and this table: they read a scene's workspace offset from the
+ *            plan, use the front of its region, and read rows 0..2 of the table.
+ *   posd, veld, accd : double[rows][4], 32-byte aligned: {x, y, z, m}, {vx, vy, vz, 0} and {ax, ay, az, 0}, padded as above.
+ *   params : DEVICE double[NBD_BATCH_H6_PARAM_ROWS][S], 8-byte aligned, row r of scene s at params[r * S + s]; rows:
+ *            G, softening^2, softening (as NBD_BATCH_F64_PARAM_ROWS' first three), then the doubles nbd_hermite6_step_f64
+ *            forms from its dt, with dt2 = dt*dt and dt3 = dt2*dt: dt, 0.5*dt, 0.5*dt2, dt3/6.0, dt2*dt2/24.0,
+ *            dt2*dt3/120.0, dt2/10.0, dt3/120.0, dt2, dt3. No kernel takes a per-scene scalar by value.
+ *   workspace : nbd_batch_hermite6_f64_workspace_bytes, 8-byte aligned (9 doubles per body and slab); it may hold anything.
+ * Argument errors return NBD_E_BADARG (NBD_E_WORKSPACE for the workspace) before any launch. No atomics, no memsets, no
+ * host syncs. */
+#define NBD_BATCH_H6_PARAM_ROWS 13
+/* Host-only: writes the 9-row plan into HOST memory; plan_bytes as nbd_batch_f64_plan reports. */
+int nbd_batch_hermite6_f64_plan_fill(const int* offsets, int n_scenes, void* plan, size_t plan_bytes);
+/* Host-only: the bytes of the workspace of the entries below (1.5 x nbd_batch_f64_workspace_bytes). */
+int nbd_batch_hermite6_f64_workspace_bytes(const int* offsets, int n_scenes, size_t* bytes);
+/* posd = {x, m}, veld = {v, 0}, accd = {a, 0} of every scene (acc == NULL: accd = 0; zero rows in each scene's padding):
+ * one launch. */
+int nbd_batch_hermite6_pack_f64(const int* offsets, int n_scenes, const void* plan, size_t plan_bytes, const double* pos,
+                                const double* vel, const double* acc, const double* mass, double* posd, double* veld,
+                                double* accd, nbd_stream_t stream);
+/* acc_out, jerk_out, snap_out (N, 3) of every scene from the packed rows (nbd_accel_jerk_snap_f64 per scene at the plan's
+ * slab count): the evaluation and the slab sum in slab order with G_s, two launches. */
+int nbd_batch_accel_jerk_snap_f64(const int* offsets, int n_scenes, const void* plan, size_t plan_bytes,
+                                  const double* posd, const double* veld, const double* accd, const double* params,
+                                  double* acc_out, double* jerk_out, double* snap_out, void* workspace,
+                                  size_t workspace_bytes, nbd_stream_t stream);
+/* One 6th-order Hermite step of every scene, three launches (nbd_hermite6_step_f64 per scene): pos, vel in place; every
+ * output may alias its input; posd = {x1, m}; veld and accd are scratch. */
+int nbd_batch_hermite6_step_f64(const int* offsets, int n_scenes, const void* plan, size_t plan_bytes, double* pos,
+                                double* vel, const double* acc_in, const double* jerk_in, const double* snap_in,
+                                const double* crackle_in, double* acc_out, double* jerk_out, double* snap_out,
+                                double* crackle_out, const double* mass, const double* params, double* posd,
+                                double* veld, double* accd, void* workspace, size_t workspace_bytes,
+                                nbd_stream_t stream);
+
 /* ------------------------------------------------------------ 4th-order Hermite integrator (csrc/direct_hermite.hip)
  * An extension (the reference has Euler and leapfrog only): the shared-timestep predictor-corrector of Makino & Aarseth
  * (1992), one acceleration + jerk evaluation per step, fp32 state. With r_ij = x_j - x_i, v_ij = v_j - v_i and

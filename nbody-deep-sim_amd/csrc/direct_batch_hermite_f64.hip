@@ -57,26 +57,6 @@ bool bad_workspace(const void* workspace, size_t workspace_bytes, const BatchTot
   return !workspace || misaligned8(workspace) || workspace_bytes < ws_bytes_f64(t);
 }
 
-// What a workgroup of an item reads from the work list, uniform across the workgroup (SGPRs)
-struct Item {
-  int s, grp, slab, n, n_chunks, slabs, poff, ws_off;
-};
-
-__device__ __forceinline__ Item load_item(const int4* __restrict__ items, const SceneRec* __restrict__ scenes) {
-  const int4 it = items[blockIdx.x];
-  Item w;
-  w.s = __builtin_amdgcn_readfirstlane(it.x);
-  w.grp = __builtin_amdgcn_readfirstlane(it.y);
-  w.slab = __builtin_amdgcn_readfirstlane(it.z);
-  const SceneRec sc = load_scene(scenes, w.s);
-  w.n = __builtin_amdgcn_readfirstlane(sc.n);
-  w.n_chunks = __builtin_amdgcn_readfirstlane(sc.n_chunks);
-  w.slabs = __builtin_amdgcn_readfirstlane(sc.slabs);
-  w.poff = __builtin_amdgcn_readfirstlane(sc.poff);
-  w.ws_off = __builtin_amdgcn_readfirstlane(sc.ws_off);
-  return w;
-}
-
 // posd[r] = {x_p, m}, veld[r] = {v_p, 0} for every packed row r (zero rows behind each scene's last body).
 // acc == nullptr: a plain pack of (x, v).
 __global__ __launch_bounds__(256) void batch_predict_f64_kernel(const int* __restrict__ row_scene,

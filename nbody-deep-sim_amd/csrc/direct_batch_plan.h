@@ -1,8 +1,9 @@
 // direct_batch_plan.h -- the device work list of the batched direct integrator (nbd_batch_plan / nbd_batch_plan_fill)
 // and the host checks every batched entry point makes before it launches, shared by direct_batch.hip (leapfrog, Euler,
-// energies), direct_batch_hermite.hip (Hermite) and direct_batch_hermite_f64.hip (Hermite in double precision: the same
-// layout filled with another geometry per scene, SceneGeom below). The definitions sit in an anonymous namespace: every
-// translation unit that includes this file gets its own copies.
+// energies), direct_batch_hermite.hip (Hermite), direct_batch_hermite_f64.hip (Hermite in double precision: the same
+// layout filled with another geometry per scene, SceneGeom below) and direct_batch_hermite6_f64.hip (6th-order Hermite:
+// that geometry with nine doubles per body and slab). The definitions sit in an anonymous namespace: every translation
+// unit that includes this file gets its own copies.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <limits.h>
@@ -23,7 +24,7 @@ struct SceneRec {
   int n;        // bodies
   int poff;     // first packed row (multiple of 64)
   int ws_off;   // first float of the scene's slabs in the workspace: float[slabs][n][3] (fp64 plan: first double of
-                // its double[slabs][6][n])
+                // its double[slabs][6][n], or [9] in the 6th-order plan)
   int u_off;    // first fp64 energy partial of the scene: double[groups * slabs]
   int slabs;
   int n_chunks; // pad64(n) / 64
@@ -111,6 +112,27 @@ __device__ __forceinline__ SceneRec load_scene(const SceneRec* scenes, int s) {
   const int4* q = reinterpret_cast<const int4*>(scenes + s);
   const int4 a = q[0], b = q[1];
   return SceneRec{a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+}
+
+// What a workgroup of an item of the fp64 plans reads from the work list (direct_batch_hermite_f64.hip,
+// direct_batch_hermite6_f64.hip: one workgroup per item), uniform across the workgroup (SGPRs)
+struct Item {
+  int s, grp, slab, n, n_chunks, slabs, poff, ws_off;
+};
+
+__device__ __forceinline__ Item load_item(const int4* __restrict__ items, const SceneRec* __restrict__ scenes) {
+  const int4 it = items[blockIdx.x];
+  Item w;
+  w.s = __builtin_amdgcn_readfirstlane(it.x);
+  w.grp = __builtin_amdgcn_readfirstlane(it.y);
+  w.slab = __builtin_amdgcn_readfirstlane(it.z);
+  const SceneRec sc = load_scene(scenes, w.s);
+  w.n = __builtin_amdgcn_readfirstlane(sc.n);
+  w.n_chunks = __builtin_amdgcn_readfirstlane(sc.n_chunks);
+  w.slabs = __builtin_amdgcn_readfirstlane(sc.slabs);
+  w.poff = __builtin_amdgcn_readfirstlane(sc.poff);
+  w.ws_off = __builtin_amdgcn_readfirstlane(sc.ws_off);
+  return w;
 }
 
 // Writes the plan of the totals t (batch_totals with the same geom) into the host buffer `plan`, plan_bytes_of(t) bytes.

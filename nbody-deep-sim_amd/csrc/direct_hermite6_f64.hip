@@ -8,8 +8,9 @@
 //   A_ij = w r,  J_ij = w v - 3 alpha w r,  S_ij = w a - 6 alpha w v + (15 alpha^2 - 3 gamma) w r
 // The sources are three arrays of 32-byte rows: posd = {x, y, z, m}, veld = {vx, vy, vz, 0} and accd = {ax, ay, az, 0},
 // zero rows behind n up to a multiple of 64. The evaluation is walk_f64 (hermite_f64_kernels.h) with three streamed
-// arrays and the pair functor AccelJerkSnapPair below, in accel_jerk_f64_kernel's geometry (plan_f64, chunk_split, four
-// waves on 64 targets, LDS-DMA double buffering, the counted vmcnt(6)); 48 KiB of LDS per workgroup: three per CU.
+// arrays and the pair functor AccelJerkSnapPair (hermite6_f64_kernels.h), in accel_jerk_f64_kernel's geometry (plan_f64,
+// chunk_split, four waves on 64 targets, LDS-DMA double buffering, the counted vmcnt(6)); 48 KiB of LDS per workgroup:
+// three per CU.
 //
 // One step is three launches (PEC form; a0, j0, s0 and the crackle c0 = d^3 a / dt^3 carried):
 //   predict : hermite6_predict_kernel -> posd = {x_p, m}, veld = {v_p, 0}, accd = {a_p, 0}, Taylor series to c0
@@ -18,88 +19,18 @@
 //             the corrector, c1 = the third derivative at t1 of the quintic through (a, j, s) at both ends, posd = {x1, m}
 // The step constants are doubles formed from the double dt and are never rounded to fp32; every product and sum of the
 // two O(N) kernels rounds on its own (the build has -ffp-contract=off). No atomics, no memsets, no host syncs:
-// deterministic run to run with a workspace that may hold anything.
+// deterministic run to run with a workspace that may hold anything. The functor, the step constants and the per-row
+// bodies of the two O(N) kernels are in hermite6_f64_kernels.h, shared with direct_batch_hermite6_f64.hip (many systems).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../../include/nbd.h"
 #include "direct_kernels.h"
+#include "hermite6_f64_kernels.h"
 #include "hermite_f64_kernels.h"
 #include "hermite_kernels.h"
 
 namespace {
-
-// The pair functor (what a functor is: hermite_f64_kernels.h). p = {x, y, z, m}, q = {vx, vy, vz, 0}, r = {ax, ay, az, 0}
-// of source j. acc[0..8] are AccelJerkPair's sums, formed by AccelJerkPair::pair's operations one for one and in the same
-// order, so out(0..5) are that functor's bits. The snap has sums of its own: sn[0..2] = sum w a, sn[3..5] = sum alpha w v,
-// sn[6..8] = sum (15 alpha^2 - 3 gamma) w r; out(6..8) = (sn[0..2] - 6 sn[3..5]) + sn[6..8]. MASKED drops j == i and the
-// padding behind n by the select on s (after the refinement: w, alpha and gamma of a dropped pair are exact zeros whatever
-// its r^2 gave, NaN included). Un-masked, i == j (r = v = a = 0, s finite) and a padding row (m = 0) add exact zeros.
-struct AccelJerkSnapPair {
-  static constexpr int kStreams = 3;
-  static constexpr int kOut = 9;
-  double xi, yi, zi, ui, vi, wi, axi, ayi, azi, e2;
-  double acc[9], sn[9];
-  int i, n;
-
-  __device__ __forceinline__ AccelJerkSnapPair(const d4 tp, const d4 tv, const d4 ta, double eps2, int i_, int n_)
-      : xi(tp.x), yi(tp.y), zi(tp.z), ui(tv.x), vi(tv.y), wi(tv.z), axi(ta.x), ayi(ta.y), azi(ta.z), e2(eps2), i(i_),
-        n(n_) {
-#pragma unroll
-    for (int k = 0; k < 9; ++k) acc[k] = sn[k] = 0.0;
-  }
-
-  template <bool MASKED>
-  __device__ __forceinline__ void pair(const d4 p, const d4 q, const d4 r, int j) {
-    const double dx = p.x - xi, dy = p.y - yi, dz = p.z - zi;      // r_j - r_i
-    const double du = q.x - ui, dv = q.y - vi, dw = q.z - wi;
-    const double dax = r.x - axi, day = r.y - ayi, daz = r.z - azi;
-    double r2 = __builtin_fma(dx, dx, e2);
-    r2 = __builtin_fma(dy, dy, r2);
-    r2 = __builtin_fma(dz, dz, r2);
-    double rv = dx * du;
-    rv = __builtin_fma(dy, dv, rv);
-    rv = __builtin_fma(dz, dw, rv);
-    double va = du * du;                                           // v.v + r.a
-    va = __builtin_fma(dv, dv, va);
-    va = __builtin_fma(dw, dw, va);
-    va = __builtin_fma(dx, dax, va);
-    va = __builtin_fma(dy, day, va);
-    va = __builtin_fma(dz, daz, va);
-    double s = rsqrt_f64(r2);
-    if (MASKED) s = (j < n && j != i) ? s : 0.0;
-    const double s2 = s * s;
-    const double w = (s2 * s) * p.w;
-    const double al = rv * s2;
-    const double c = al * w;
-    const double gm = va * s2;
-    const double b = __builtin_fma(15.0 * al, al, -3.0 * gm) * w;
-    acc[0] = __builtin_fma(w, dx, acc[0]);
-    acc[1] = __builtin_fma(w, dy, acc[1]);
-    acc[2] = __builtin_fma(w, dz, acc[2]);
-    acc[3] = __builtin_fma(w, du, acc[3]);
-    acc[4] = __builtin_fma(w, dv, acc[4]);
-    acc[5] = __builtin_fma(w, dw, acc[5]);
-    acc[6] = __builtin_fma(c, dx, acc[6]);
-    acc[7] = __builtin_fma(c, dy, acc[7]);
-    acc[8] = __builtin_fma(c, dz, acc[8]);
-    sn[0] = __builtin_fma(w, dax, sn[0]);
-    sn[1] = __builtin_fma(w, day, sn[1]);
-    sn[2] = __builtin_fma(w, daz, sn[2]);
-    sn[3] = __builtin_fma(c, du, sn[3]);
-    sn[4] = __builtin_fma(c, dv, sn[4]);
-    sn[5] = __builtin_fma(c, dw, sn[5]);
-    sn[6] = __builtin_fma(b, dx, sn[6]);
-    sn[7] = __builtin_fma(b, dy, sn[7]);
-    sn[8] = __builtin_fma(b, dz, sn[8]);
-  }
-
-  __device__ __forceinline__ double out(int k) const {
-    if (k < 3) return acc[k];
-    if (k < 6) return acc[k] - 3.0 * acc[k + 3];
-    return (sn[k - 6] - 6.0 * sn[k - 3]) + sn[k];
-  }
-};
 
 // Acceleration + jerk + snap of all n bodies under all n bodies, accel_jerk_f64_kernel's geometry: grid = (groups of 64
 // targets, slabs), the source chunks spread over all slabs x 4 waves to within one. out: double[slab][9][n].
@@ -120,15 +51,6 @@ __global__ __launch_bounds__(64 * kWaves) void accel_jerk_snap_f64_kernel(const 
            accd);
 }
 
-// The step constants: doubles formed from the double dt.
-struct Hermite6Step { double dt, dt_half, dt2_half, dt3_6, dt4_24, dt5_120, dt2_10, dt3_120, dt2, dt3; };
-
-inline Hermite6Step hermite6_step_constants(double dt) {
-  const double dt2 = dt * dt, dt3 = dt2 * dt;
-  return Hermite6Step{dt, 0.5 * dt, 0.5 * dt2, dt3 / 6.0, dt2 * dt2 / 24.0, dt2 * dt3 / 120.0, dt2 / 10.0, dt3 / 120.0,
-                      dt2, dt3};
-}
-
 // posd = {x_p, m}, veld = {v_p, 0}, accd = {a_p, 0} for rows [0, n_pad), zero rows behind n:
 //   x_p = x + v dt + a dt^2/2 + j dt^3/6 + s dt^4/24 + c dt^5/120,  v_p = v + a dt + j dt^2/2 + s dt^3/6 + c dt^4/24,
 //   a_p = a + j dt + s dt^2/2 + c dt^3/6.
@@ -145,24 +67,7 @@ __global__ __launch_bounds__(256) void hermite6_predict_kernel(const double* __r
   const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= (size_t)n_pad) return;
   d4 pm = {0.0, 0.0, 0.0, 0.0}, vp = pm, ap = pm;
-  if (i < (size_t)n) {
-    double x[3], v[3], a[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      x[k] = pos[3 * i + k];
-      v[k] = vel[3 * i + k];
-      a[k] = acc ? acc[3 * i + k] : 0.0;
-      if (jerk) {
-        const double j = jerk[3 * i + k], s = snap[3 * i + k], c = crackle[3 * i + k];
-        x[k] = ((((x[k] + v[k] * h.dt) + a[k] * h.dt2_half) + j * h.dt3_6) + s * h.dt4_24) + c * h.dt5_120;
-        v[k] = (((v[k] + a[k] * h.dt) + j * h.dt2_half) + s * h.dt3_6) + c * h.dt4_24;
-        a[k] = ((a[k] + j * h.dt) + s * h.dt2_half) + c * h.dt3_6;
-      }
-    }
-    pm = d4{x[0], x[1], x[2], mass[i]};
-    vp = d4{v[0], v[1], v[2], 0.0};
-    ap = d4{a[0], a[1], a[2], 0.0};
-  }
+  if (i < (size_t)n) hermite6_predict_row(pos, vel, acc, jerk, snap, crackle, mass, i, h, pm, vp, ap);
   posd[i] = pm;
   veld[i] = vp;
   accd[i] = ap;
@@ -183,27 +88,8 @@ __global__ __launch_bounds__(256) void hermite6_finish_kernel(const double* __re
                                                               const double* __restrict__ mass, d4* __restrict__ posd) {
   const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= (size_t)n) return;
-  double sum[9];
-  slab_order_sum<9>(slabs, n_slabs, (size_t)n, i, sum);
-  double x1[3];
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    const double a1 = g * sum[k], j1 = g * sum[k + 3], s1 = g * sum[k + 6];
-    if (pos) {
-      const double a0 = acc_in[3 * i + k], j0 = jerk_in[3 * i + k], s0 = snap_in[3 * i + k];
-      const double x = pos[3 * i + k], v = vel[3 * i + k];
-      const double v1 = ((v + (a0 + a1) * h.dt_half) - (j1 - j0) * h.dt2_10) + (s0 + s1) * h.dt3_120;
-      x1[k] = ((x + (v + v1) * h.dt_half) - (a1 - a0) * h.dt2_10) + (j0 + j1) * h.dt3_120;
-      vel[3 * i + k] = v1;
-      pos[3 * i + k] = x1[k];
-      crackle_out[3 * i + k] =
-          ((60.0 * (a1 - a0) - h.dt * (36.0 * j1 + 24.0 * j0)) + h.dt2 * (9.0 * s1 - 3.0 * s0)) / h.dt3;
-    }
-    acc_out[3 * i + k] = a1;
-    jerk_out[3 * i + k] = j1;
-    snap_out[3 * i + k] = s1;
-  }
-  if (pos) posd[i] = d4{x1[0], x1[1], x1[2], mass[i]};
+  hermite6_finish_row(slabs, n_slabs, (size_t)n, i, i, g, h, pos, vel, acc_in, jerk_in, snap_in, acc_out, jerk_out,
+                      snap_out, crackle_out, mass, posd, i);
 }
 
 // the unscaled acceleration + jerk + snap partial sums of every body into double[slabs][9][n]

@@ -984,7 +984,8 @@ class Hermite6Simulator(HermiteSimulator):
     HermiteSimulator(dtype=torch.float64), whose compute_energies(), compute_potentials(), compute_invariants(), gather()
     and eager run() work here unchanged. The only number format is float64 (`dtype` defaults to it): the fp32 Hermite run
     already sits on the fp32 floor at a few dozen steps, so a higher order buys nothing there. There is no range-sharded,
-    batched, block-timestep, captured or differentiable form."""
+    block-timestep or differentiable form; many systems stepped together, with a captured run(), are
+    BatchedSimulator(integrator="hermite6"), each scene bit-identical to this simulator on it alone."""
 
     def __init__(self, *, positions, velocities, masses, g_const: float = 1.0, softening: float = 0.1,
                  dt: float = 0.01, calc_energy: bool = True, device: str = None, process_group=None,
@@ -1301,7 +1302,45 @@ class _BatchFloat64:
     snapshot = staticmethod(direct.snapshot_f64)
 
 
+class _BatchHermite6(_BatchFloat64):
+    """The float64 format of BatchedSimulator(integrator="hermite6") (csrc/direct_batch_hermite6_f64.hip): `_BatchFloat64`
+    with the 9-row plan and its workspace, the third packed array `s._accd` = {ax, ay, az, 0} and the taller parameter
+    table (direct.batch_h6_params: G, eps^2, eps, then Hermite6Step's constants). The carried arrays are
+    (accelerations, jerks, snaps, crackles). The inherited pack, acceleration + jerk, energies, potentials and invariants
+    run on the same plan, workspace and table: they read a scene's workspace offset from the plan and rows 0..2 of the
+    table."""
+
+    integrators = ("hermite6",)
+
+    def scratch(self, s):
+        s._plan = direct.BatchPlan(s.sizes, s.device, dtype=torch.float64, order=6)
+        s._posd, s._veld, s._accd = (direct.alloc_batch_rows_f64(s._plan) for _ in range(3))
+        s._ws = s._plan.workspace()
+        s._params = torch.zeros((direct.BATCH_H6_PARAM_ROWS, s.n_scenes), dtype=torch.float64, device=s.device)
+
+    def param_rows(self, g, eps, dt) -> list:
+        return direct.batch_h6_params(g, eps, dt)
+
+    def accel_jerk_snap(self, s, acc, jerk, snap):
+        """Hermite6Simulator's two passes: the acceleration first (acc, jerk serve as its outputs), then the evaluation
+        that takes it as the third source array."""
+        self.accel_jerk(s, acc, jerk)
+        direct.batch_hermite6_pack_f64(s._plan, s.positions, s.velocities, s.masses, s._posd, s._veld, s._accd, acc=acc)
+        direct.batch_accel_jerk_snap_f64(s._plan, s._posd, s._veld, s._accd, s._params, acc, jerk, snap, s._ws)
+
+    def hermite_step(self, s, cur, new):
+        direct.batch_hermite6_step_f64(s._plan, s.positions, s.velocities, *cur, *new, s.masses, s._params, s._posd,
+                                       s._veld, s._accd, s._ws)
+
+
 _BATCH_FORMATS = {fmt.dtype: fmt for fmt in (_BatchFloat32(), _BatchFloat64())}
+_BATCH_HERMITE6 = _BatchHermite6()
+_BATCH_INTEGRATORS = ("leapfrog", "euler", "hermite", "hermite6")
+
+
+def _batch_format(dtype, integrator):
+    """The format object of a batch: by dtype, and the 6th-order scheme has one of its own."""
+    return _BATCH_HERMITE6 if integrator == "hermite6" else _BATCH_FORMATS[dtype]
 
 
 class BatchedSimulator(_ChunkedRun):
@@ -1324,7 +1363,15 @@ class BatchedSimulator(_ChunkedRun):
     dt and step constants reach the kernels as doubles through a device table, and step(), the compute_*() methods and
     run() -- its states, energies and invariants -- are float64 end to end, each scene bit-identical to a
     HermiteSimulator(dtype=torch.float64) of that scene alone. Because the table, not a kernel argument, carries the
-    scalars, run() captures its chunks in this mode too. The default stays float32 and takes the paths it took."""
+    scalars, run() captures its chunks in this mode too. The default stays float32 and takes the paths it took.
+
+    integrator="hermite6" (csrc/direct_batch_hermite6_f64.hip) is Hermite6Simulator's 6th-order step on
+    every scene, float64 only (`dtype` then defaults to torch.float64; torch.float32 is refused): `accelerations`,
+    `jerks`, `snaps` and `crackles` are (N_total, 3) float64 tensors rebound by step(), built as Hermite6Simulator builds
+    them (the acceleration first, then the evaluation with it as the third source array, crackle 0), and each scene's
+    state is bit-identical to a Hermite6Simulator of that scene alone. run() captures its chunks as for the float64
+    4th-order mode, the four arrays stepped in place; energies, potentials and invariants are that mode's. The
+    integrator cannot switch into or out of "hermite6", nor between "hermite" and "hermite6"."""
 
     RING_BYTES = 64 << 20                                # the eager run()'s staging cap, per chunk of states
 
@@ -1332,22 +1379,26 @@ class BatchedSimulator(_ChunkedRun):
     def _check_dtype(dtype, integrator):
         if dtype not in _BATCH_FORMATS:
             raise ValueError(f"BatchedSimulator: dtype must be torch.float32 or torch.float64, got {dtype!r}")
-        if integrator not in _BATCH_FORMATS[dtype].integrators:
+        if integrator == "hermite6":
+            if dtype is not torch.float64:
+                raise ValueError(f"BatchedSimulator: integrator='hermite6' is float64 only (dtype must be "
+                                 f"torch.float64, got {dtype!r}): there is no fp32 form of the 6th-order scheme")
+        elif integrator not in _BATCH_FORMATS[dtype].integrators:
             raise ValueError(f"BatchedSimulator: dtype={dtype} has integrator='hermite' only (there is no float64 "
                              f"leapfrog or Euler), got {integrator!r}")
 
     def __init__(self, *, systems, integrator: str = "leapfrog", g_const=1.0, softening=0.1, dt=0.01,
                  calc_energy: bool = True, device: str = None, calc_invariants: bool = False, **format_kw):
-        # format_kw: `dtype` (default torch.float32), the one keyword of the number format. As in BlockHermiteSimulator it
+        # format_kw: `dtype` (default torch.float32; torch.float64 for "hermite6"), the one keyword of the number format. As in BlockHermiteSimulator it
         # is not a named parameter: HermiteSimulator's signature stays the only one that spells it (tested); any other
         # name is refused as an unknown keyword is.
-        dtype = format_kw.pop("dtype", torch.float32)
+        dtype = format_kw.pop("dtype", torch.float64 if integrator == "hermite6" else torch.float32)
         if format_kw:
             raise TypeError(f"BatchedSimulator.__init__() got an unexpected keyword argument {next(iter(format_kw))!r}")
-        if integrator not in ("leapfrog", "euler", "hermite"):
-            raise ValueError("integrator must be 'leapfrog', 'euler' or 'hermite'")
+        if integrator not in _BATCH_INTEGRATORS:
+            raise ValueError("integrator must be 'leapfrog', 'euler', 'hermite' or 'hermite6'")
         self._check_dtype(dtype, integrator)             # before anything is resolved, allocated or launched
-        self._fmt = _BATCH_FORMATS[dtype]                # the only place the format is chosen
+        self._fmt = _batch_format(dtype, integrator)     # the only place the format is chosen
         self.device = _resolve_device(device)
         _lib.lib()
         systems = list(systems)
@@ -1373,10 +1424,15 @@ class BatchedSimulator(_ChunkedRun):
         self.offsets = torch.tensor(self._plan.offsets, dtype=torch.int64)
         self.g_const, self.softening, self.dt = g_const, softening, dt
         self._params_key = None
-        self._hermite = integrator == "hermite"          # fixed at construction: the state carries jerks or not
+        self._hermite = integrator in ("hermite", "hermite6")   # fixed at construction: the state carries jerks or not
+        self._order6 = integrator == "hermite6"          # ... and snaps and crackles
         self._phi = None
-        self.jerks = None
-        if self._hermite:
+        self.jerks = self.snaps = self.crackles = None
+        if self._order6:
+            self._carried = self._carried + (("jerks", "_jerk_g"), ("snaps", "_snap_g"), ("crackles", "_crackle_g"))
+            self.accelerations, self.jerks, self.snaps = self.compute_accelerations_jerks_and_snaps()
+            self.crackles = torch.zeros_like(self.snaps)
+        elif self._hermite:
             self._carried = self._carried + (("jerks", "_jerk_g"),)
             self.accelerations, self.jerks = self.compute_accelerations_and_jerks()
         else:
@@ -1419,8 +1475,22 @@ class BatchedSimulator(_ChunkedRun):
         self._fmt.accel_jerk(self, acc, jerk)
         return acc, jerk
 
+    def compute_accelerations_jerks_and_snaps(self):
+        """(a, j, s) of every scene's current state as new (N_total, 3) float64 tensors, in Hermite6Simulator's two
+        passes per scene (integrator="hermite6" only)."""
+        if not self._order6:
+            raise ValueError("BatchedSimulator.compute_accelerations_jerks_and_snaps(): integrator='hermite6' only")
+        self._sync_params()
+        acc, jerk, snap = (torch.zeros((self.n, 3), dtype=torch.float64, device=self.device) for _ in range(3))
+        self._fmt.accel_jerk_snap(self, acc, jerk, snap)
+        return acc, jerk, snap
+
     def _check_integrator(self):
-        if (self.integrator == "hermite") != self._hermite:
+        if (self.integrator == "hermite6") != self._order6:
+            raise ValueError("BatchedSimulator: the integrator cannot change into or out of 'hermite6' after "
+                             "construction (the state carries snaps and crackles only for the 6th-order scheme, and "
+                             "its plan and parameter table are its own); build a new simulator")
+        if (self.integrator == "hermite") != (self._hermite and not self._order6):
             raise ValueError("BatchedSimulator: the integrator cannot change into or out of 'hermite' after "
                              "construction (the state carries jerks only for Hermite); build a new simulator")
 
@@ -1475,8 +1545,8 @@ class BatchedSimulator(_ChunkedRun):
                                     P[0], self._posm, self._ws)
 
     def step(self):
-        """One step of every scene; positions and velocities in place, `accelerations` (and for Hermite `jerks`)
-        rebound to new tensors."""
+        """One step of every scene; positions and velocities in place, `accelerations` (for Hermite `jerks`, for the
+        6th-order scheme `snaps` and `crackles` as well) rebound to new tensors."""
         self._check_integrator()
         if self.n == 0:
             return

@@ -222,6 +222,14 @@ SIGNATURES = {
                                         c_size_t, c_void_p]),
     "nbd_batch_invariants_state_f64": (c_int, [c_void_p, c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p,
                                                c_void_p, c_void_p, c_void_p]),
+    # --- 6th-order Hermite per scene (csrc/direct_batch_hermite6_f64.hip)
+    "nbd_batch_hermite6_f64_plan_fill": (c_int, [c_void_p, c_int, c_void_p, c_size_t]),
+    "nbd_batch_hermite6_f64_workspace_bytes": (c_int, [c_void_p, c_int, POINTER(c_size_t)]),
+    "nbd_batch_hermite6_pack_f64": (c_int, [c_void_p, c_int, c_void_p, c_size_t] + [c_void_p] * 7 + [c_void_p]),
+    "nbd_batch_accel_jerk_snap_f64": (c_int, [c_void_p, c_int, c_void_p, c_size_t] + [c_void_p] * 7 +
+                                      [c_void_p, c_size_t, c_void_p]),
+    "nbd_batch_hermite6_step_f64": (c_int, [c_void_p, c_int, c_void_p, c_size_t] + [c_void_p] * 15 +
+                                    [c_void_p, c_size_t, c_void_p]),
     # --- 4th-order Hermite integrator (csrc/direct_hermite.hip)
     "nbd_hermite_workspace_bytes": (c_size_t, [c_int]),
     "nbd_hermite_pack_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_double, c_void_p,

@@ -1092,15 +1092,21 @@ class BatchPlan:
     nbd_batch_plan_fill): built once per set of scene sizes, passed to every batch_* call. dtype=torch.float64: the work
     list of the batch_*_f64 calls instead (nbd_batch_f64_plan / nbd_batch_f64_plan_fill: groups of 64 targets, the
     float64 step's slabs); `posm_rows` then counts the rows of posd / veld and `workspace_bytes` is the one workspace of
-    every float64 call. A plan serves the calls of its own dtype only."""
+    every float64 call. A plan serves the calls of its own dtype only. order=6 (float64 only): the same work list with
+    room for the 6th-order step's partial sums (nbd_batch_hermite6_f64_plan_fill: 9 doubles per body and slab where the
+    4th-order step has 6) for the batch_hermite6_* calls; the float64 diagnostics, batch_pack_f64 and batch_accel_jerk_f64
+    run on it too, with its workspace and a BATCH_H6_PARAM_ROWS table."""
 
-    def __init__(self, sizes, device, dtype=torch.float32):
+    def __init__(self, sizes, device, dtype=torch.float32, order: int = 4):
         sizes = [int(n) for n in sizes]
         if not sizes or min(sizes) < 0:
             raise _lib.NbdError("batch: need at least one scene and no negative size")
         if dtype not in (torch.float32, F64):
             raise _lib.NbdError(f"batch: dtype must be torch.float32 or torch.float64, got {dtype!r}")
-        self.dtype = dtype
+        if order not in (4, 6) or (order == 6 and dtype != F64):
+            raise _lib.NbdError(f"batch: order must be 4, or 6 with dtype=torch.float64, got order={order!r}")
+        self.dtype, self.order = dtype, order
+        self.param_rows = None if dtype == torch.float32 else (BATCH_F64_PARAM_ROWS, BATCH_H6_PARAM_ROWS)[order == 6]
         self.offsets = np.zeros(len(sizes) + 1, dtype=np.int32)
         np.cumsum(sizes, out=self.offsets[1:])
         self.n_scenes, self.n_total = len(sizes), int(self.offsets[-1])
@@ -1114,6 +1120,10 @@ class BatchPlan:
             _lib.check(L.nbd_batch_f64_plan(self._off(), self.n_scenes, items, rows, pb), "nbd_batch_f64_plan")
             _lib.check(L.nbd_batch_f64_workspace_bytes(self._off(), self.n_scenes, wb), "nbd_batch_f64_workspace_bytes")
             fill, fill_name = L.nbd_batch_f64_plan_fill, "nbd_batch_f64_plan_fill"
+            if order == 6:                    # items, rows and bytes are the float64 plan's
+                _lib.check(L.nbd_batch_hermite6_f64_workspace_bytes(self._off(), self.n_scenes, wb),
+                           "nbd_batch_hermite6_f64_workspace_bytes")
+                fill, fill_name = L.nbd_batch_hermite6_f64_plan_fill, "nbd_batch_hermite6_f64_plan_fill"
         self.n_items, self.posm_rows, self.plan_bytes, self.workspace_bytes = items.value, rows.value, pb.value, wb.value
         host = np.zeros((self.plan_bytes + 15) // 16 * 4, dtype=np.int32)
         _lib.check(fill(self._off(), self.n_scenes, host.ctypes.data, self.plan_bytes), fill_name)
@@ -1272,6 +1282,7 @@ def batch_hermite_step(plan: BatchPlan, pos, vel, acc_in, jerk_in, acc_out, jerk
 
 # ------------------------------------------- double-precision Hermite per scene (csrc/direct_batch_hermite_f64.hip)
 BATCH_F64_PARAM_ROWS = 8        # NBD_BATCH_F64_PARAM_ROWS: G, eps^2, eps, dt, dt/2, dt^2/2, dt^3/6, dt^2/12
+BATCH_H6_PARAM_ROWS = 13        # NBD_BATCH_H6_PARAM_ROWS: G, eps^2, eps, then Hermite6Step's ten members
 
 
 def batch_f64_params(g, eps, dt) -> list:
@@ -1297,8 +1308,8 @@ def _chk_f64_batch(plan: BatchPlan, posd, veld, ws, params, *arrays):
                 raise _lib.NbdError(f"{nm}: need >= {plan.posm_rows} rows of 4, got {tuple(t.shape)}")
     if ws is not None and _nbytes(ws) < plan.workspace_bytes:
         raise _lib.NbdError("batch float64 workspace too small")
-    if params is not None:
-        _chk(params, (BATCH_F64_PARAM_ROWS, plan.n_scenes), "params", F64)
+    if params is not None:                 # the plan's own table: the 6th-order plan's is taller, rows 0-2 the same
+        _chk(params, (plan.param_rows, plan.n_scenes), "params", F64)
 
 
 def alloc_batch_rows_f64(plan: BatchPlan) -> torch.Tensor:
@@ -1370,3 +1381,65 @@ def batch_invariants_state_f64(plan: BatchPlan, pos, vel, mass, phi, out_rows) -
             *plan.head(), pos.data_ptr(), vel.data_ptr(), mass.data_ptr(), phi.data_ptr(), out_rows.data_ptr(),
             _lib.current_stream(vel.device)), "nbd_batch_invariants_state_f64")
     return out_rows
+
+
+# ------------------------------------------------- 6th-order Hermite per scene (csrc/direct_batch_hermite6_f64.hip)
+def batch_h6_params(g, eps, dt) -> list:
+    """The rows of the 6th-order calls' parameter table from each scene's Python doubles (g, eps, dt: S floats each):
+    batch_f64_params' first three rows, then hermite6_step_constants' expressions (dt2 = dt * dt, dt3 = dt2 * dt).
+    -> BATCH_H6_PARAM_ROWS lists of S floats."""
+    dt = [float(d) for d in dt]
+    dt2 = [d * d for d in dt]
+    dt3 = [d2 * d for d2, d in zip(dt2, dt)]
+    return [[float(x) for x in g], [float(e) ** 2 for e in eps], [float(e) for e in eps], dt,
+            [0.5 * d for d in dt], [0.5 * d2 for d2 in dt2], [d3 / 6.0 for d3 in dt3], [d2 * d2 / 24.0 for d2 in dt2],
+            [d2 * d3 / 120.0 for d2, d3 in zip(dt2, dt3)], [d2 / 10.0 for d2 in dt2], [d3 / 120.0 for d3 in dt3],
+            dt2, dt3]
+
+
+def _chk_h6_batch(plan: BatchPlan, posd, veld, accd, ws, params, *arrays):
+    """_chk_f64_batch for a 6th-order plan, and the third packed array."""
+    if plan.dtype != F64 or plan.order != 6:
+        raise _lib.NbdError("batch 6th-order call: the plan was not built for it "
+                            "(BatchPlan(..., dtype=torch.float64, order=6))")
+    _chk_f64_batch(plan, posd, veld, ws, params, *arrays)
+    _chk(accd, None, "accd", F64)
+    if accd.dim() != 2 or accd.shape[1] != 4 or accd.shape[0] < plan.posm_rows:
+        raise _lib.NbdError(f"accd: need >= {plan.posm_rows} rows of 4, got {tuple(accd.shape)}")
+
+
+def batch_hermite6_pack_f64(plan: BatchPlan, pos, vel, mass, posd, veld, accd, acc=None) -> None:
+    """posd = {x, m}, veld = {v, 0}, accd = {a, 0} of every scene (acc None: zero rows)."""
+    _chk_h6_batch(plan, posd, veld, accd, None, None, (pos, "pos"), (vel, "vel"), (mass, "mass"),
+                  *(((acc, "acc"),) if acc is not None else ()))
+    with _lib.on_device(pos.device):
+        _lib.check(_lib.lib().nbd_batch_hermite6_pack_f64(
+            *plan.head(), pos.data_ptr(), vel.data_ptr(), _lib.ptr(acc), mass.data_ptr(), posd.data_ptr(),
+            veld.data_ptr(), accd.data_ptr(), _lib.current_stream(pos.device)), "nbd_batch_hermite6_pack_f64")
+
+
+def batch_accel_jerk_snap_f64(plan: BatchPlan, posd, veld, accd, params, acc_out, jerk_out, snap_out, ws) -> None:
+    """acc_out, jerk_out, snap_out of every scene from the packed rows (accel_jerk_snap_f64 per scene, bit for bit).
+    params: device float64 (BATCH_H6_PARAM_ROWS, S) as batch_h6_params forms it; ws: plan.workspace()."""
+    _chk_h6_batch(plan, posd, veld, accd, ws, params, (acc_out, "acc_out"), (jerk_out, "jerk_out"),
+                  (snap_out, "snap_out"))
+    with _lib.on_device(posd.device):
+        _lib.check(_lib.lib().nbd_batch_accel_jerk_snap_f64(
+            *plan.head(), posd.data_ptr(), veld.data_ptr(), accd.data_ptr(), params.data_ptr(), acc_out.data_ptr(),
+            jerk_out.data_ptr(), snap_out.data_ptr(), ws.data_ptr(), _nbytes(ws), _lib.current_stream(posd.device)),
+            "nbd_batch_accel_jerk_snap_f64")
+
+
+def batch_hermite6_step_f64(plan: BatchPlan, pos, vel, acc_in, jerk_in, snap_in, crackle_in, acc_out, jerk_out, snap_out,
+                            crackle_out, mass, params, posd, veld, accd, ws) -> None:
+    """One 6th-order Hermite step of every scene (hermite6_step_f64 per scene, bit for bit): pos, vel in place; every
+    output may be its input; posd = {x1, m}; veld and accd are scratch."""
+    _chk_h6_batch(plan, posd, veld, accd, ws, params, (pos, "pos"), (vel, "vel"), (acc_in, "acc_in"),
+                  (jerk_in, "jerk_in"), (snap_in, "snap_in"), (crackle_in, "crackle_in"), (acc_out, "acc_out"),
+                  (jerk_out, "jerk_out"), (snap_out, "snap_out"), (crackle_out, "crackle_out"), (mass, "mass"))
+    with _lib.on_device(pos.device):
+        _lib.check(_lib.lib().nbd_batch_hermite6_step_f64(
+            *plan.head(), pos.data_ptr(), vel.data_ptr(), acc_in.data_ptr(), jerk_in.data_ptr(), snap_in.data_ptr(),
+            crackle_in.data_ptr(), acc_out.data_ptr(), jerk_out.data_ptr(), snap_out.data_ptr(), crackle_out.data_ptr(),
+            mass.data_ptr(), params.data_ptr(), posd.data_ptr(), veld.data_ptr(), accd.data_ptr(), ws.data_ptr(),
+            _nbytes(ws), _lib.current_stream(pos.device)), "nbd_batch_hermite6_step_f64")

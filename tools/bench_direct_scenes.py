@@ -12,8 +12,11 @@ leapfrog time of the same scenes from the same process (batched_leapfrog_*, herm
 one-system float64 step has no captured form) with one batched float64 run(), and adds the batched float32 Hermite time
 of the same scenes from the same process (batched_f32_hermite_*, f64_over_f32_gpu). --out FILE also writes the line there
 (profiles/r17_batch_hermite_f64.json is this tool's output for float64).
+--integrator hermite6 (float64 implied) compares scene-by-scene Hermite6Simulator.run() (eager) with one batched 6th-order
+run(), and adds the batched float64 4th-order time of the same scenes from the same process (batched_f64_hermite_*,
+hermite6_over_hermite_gpu); profiles/r21_batch_hermite6.json holds two runs' lines.
 
-  python tools/bench_direct_scenes.py [--sample 128] [--cases six,many,large] [--integrator leapfrog|hermite]
+  python tools/bench_direct_scenes.py [--sample 128] [--cases six,many,large] [--integrator leapfrog|hermite|hermite6]
                                       [--dtype float32|float64] [--out FILE]
 """
 import argparse
@@ -56,7 +59,8 @@ def batched(systems, steps, energy, integrator, **kw):
 def case(sizes, steps, energy, sample=None, integrator="leapfrog", dtype=torch.float32):
     systems = [spiral(n, 1 + i) for i, n in enumerate(sizes)]
     seq = systems if sample is None else systems[:sample]
-    cls = simulation.HermiteSimulator if integrator == "hermite" else simulation.LeapFrogSimulator
+    cls = {"hermite": simulation.HermiteSimulator, "hermite6": simulation.Hermite6Simulator}.get(
+        integrator, simulation.LeapFrogSimulator)
     kw = {} if dtype == torch.float32 else {"dtype": dtype}           # (only the Hermite classes take the keyword)
     sims = [cls(positions=p, velocities=v, masses=m, g_const=G, softening=EPS, dt=DT, calc_energy=energy, device="cuda",
                 **kw) for p, v, m in seq]
@@ -79,7 +83,12 @@ def case(sizes, steps, energy, sample=None, integrator="leapfrog", dtype=torch.f
                 "speedup_wall": wall_seq * scale / wall_bat, "speedup_gpu": gpu_seq * scale / gpu_bat,
                 "batched_gpairs_per_s_gpu": pairs / gpu_bat * 1e-9,
                 "scene_by_scene_gpairs_per_s_gpu": pairs / (gpu_seq * scale) * 1e-9})
-    if kw:
+    if integrator == "hermite6":
+        wall_4, gpu_4 = batched(systems, steps, energy, "hermite", **kw)
+        out.update({"batched_f64_hermite_wall_us_per_step": 1e6 * wall_4 / steps,
+                    "batched_f64_hermite_gpu_us_per_step": 1e6 * gpu_4 / steps,
+                    "hermite6_over_hermite_gpu": gpu_bat / gpu_4})
+    elif kw:
         wall_32, gpu_32 = batched(systems, steps, energy, integrator)
         out.update({"batched_f32_hermite_wall_us_per_step": 1e6 * wall_32 / steps,
                     "batched_f32_hermite_gpu_us_per_step": 1e6 * gpu_32 / steps, "f64_over_f32_gpu": gpu_bat / gpu_32})
@@ -95,12 +104,14 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sample", type=int, default=128)
     ap.add_argument("--cases", default="six,many,large")
-    ap.add_argument("--integrator", choices=("leapfrog", "hermite"), default="leapfrog")
+    ap.add_argument("--integrator", choices=("leapfrog", "hermite", "hermite6"), default="leapfrog")
     ap.add_argument("--dtype", choices=("float32", "float64"), default="float32")
     ap.add_argument("--out", default=None, help="also write the JSON line to this file")
     a = ap.parse_args()
-    if a.dtype == "float64" and a.integrator != "hermite":
+    if a.dtype == "float64" and a.integrator == "leapfrog":
         ap.error("--dtype float64 needs --integrator hermite (there is no float64 leapfrog)")
+    if a.integrator == "hermite6":
+        a.dtype = "float64"                               # the only number format of the 6th-order scheme
     it, dt = a.integrator, getattr(torch, a.dtype)
     torch.cuda.set_device(0)
     out = {"device": torch.cuda.get_device_name(0)}
