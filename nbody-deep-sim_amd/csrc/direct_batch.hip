@@ -40,17 +40,12 @@ __global__ __launch_bounds__(64 * kWaves, 5) void batch_accel_kernel(const f4* _
                                                                      const float* __restrict__ eps2_s,
                                                                      float* __restrict__ ws) {
   __shared__ f4 lds[kAccelLdsF4];
-  const int4 it = items[blockIdx.x];
-  const int s = __builtin_amdgcn_readfirstlane(it.x), grp = __builtin_amdgcn_readfirstlane(it.y);
-  const int slab = __builtin_amdgcn_readfirstlane(it.z);
-  const SceneRec sc = load_scene(scenes, s);
-  const int n = __builtin_amdgcn_readfirstlane(sc.n);
-  const int n_chunks = __builtin_amdgcn_readfirstlane(sc.n_chunks), slabs = __builtin_amdgcn_readfirstlane(sc.slabs);
-  const f4* src = posm + __builtin_amdgcn_readfirstlane(sc.poff);
-  const float eps2 = eps2_s[s];
-  const int t_base = grp * kTgtPerWG;
-  accel_body<8, false>(src, full_view(n, n_chunks, slabs), eps2 < kEps2Masked, src, n, 0, t_base, slab, eps2, 1.0f, lds,
-                       ws + sc.ws_off + ((size_t)slab * n + t_base) * 3);
+  const Item w = load_item(items, scenes);
+  const f4* src = posm + w.poff;
+  const float eps2 = eps2_s[w.s];
+  const int t_base = w.grp * kTgtPerWG;
+  accel_body<8, false>(src, full_view(w.n, w.n_chunks, w.slabs), eps2 < kEps2Masked, src, w.n, 0, t_base, w.slab, eps2,
+                       1.0f, lds, ws + w.sc.ws_off + ((size_t)w.slab * w.n + t_base) * 3);
 }
 
 // ---- per packed row r: scene s = row_scene[r], body i = r - poff_s. Optional kick v += ck_s a, optional drift
@@ -62,15 +57,12 @@ __global__ __launch_bounds__(256) void batch_update_kernel(const int* __restrict
                                                            const float* __restrict__ acc, const float* __restrict__ mass,
                                                            const float* __restrict__ ck_s, const float* __restrict__ cd_s,
                                                            f4* __restrict__ posm) {
-  const int r = blockIdx.x * 256 + threadIdx.x;
-  if (r >= n_rows) return;
-  const int s = row_scene[r];
-  const SceneRec sc = load_scene(scenes, s);
-  const int i = r - sc.poff;
+  PlanRow w;
+  if (!load_row(row_scene, scenes, n_rows, w)) return;
   f4 pm = {0.f, 0.f, 0.f, 0.f};
-  if (i < sc.n) {
-    const int b = sc.off + i;
-    const float ck = acc ? ck_s[s] : 0.f, cd = cd_s ? cd_s[s] : 0.f;
+  if (w.i() < w.sc.n) {
+    const int b = w.sc.off + w.i();
+    const float ck = acc ? ck_s[w.s] : 0.f, cd = cd_s ? cd_s[w.s] : 0.f;
     float x[3];
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
@@ -83,7 +75,7 @@ __global__ __launch_bounds__(256) void batch_update_kernel(const int* __restrict
     }
     pm = f4{x[0], x[1], x[2], mass[b]};
   }
-  posm[r] = pm;
+  posm[w.r] = pm;
 }
 
 // ---- fixed-order slab sum: acc = G_s * (slab_0 + slab_1 + ...) in slab order, optional fused kick v += ck_s acc.
@@ -96,18 +88,16 @@ __global__ __launch_bounds__(256) void batch_finish_kernel(const int* __restrict
   const int e = blockIdx.x * 256 + threadIdx.x;
   if (e >= 3 * n_rows) return;
   const int r = e / 3, comp = e - 3 * r;
-  const int s = row_scene[r];
-  const SceneRec sc = load_scene(scenes, s);
-  const int i = r - sc.poff;
-  if (i >= sc.n) return;
-  const float* p = ws + sc.ws_off + (size_t)i * 3 + comp;
-  const size_t stride = (size_t)sc.n * 3;
+  const PlanRow w = row_of(row_scene, scenes, r);
+  if (w.i() >= w.sc.n) return;
+  const float* p = ws + w.sc.ws_off + (size_t)w.i() * 3 + comp;
+  const size_t stride = (size_t)w.sc.n * 3;
   float sum = p[0];
-  for (int k = 1; k < sc.slabs; ++k) sum += p[k * stride];
-  const float a = __fmul_rn(g_s[s], sum);
-  const size_t o = (size_t)(sc.off + i) * 3 + comp;
+  for (int k = 1; k < w.sc.slabs; ++k) sum += p[k * stride];
+  const float a = __fmul_rn(g_s[w.s], sum);
+  const size_t o = (size_t)(w.sc.off + w.i()) * 3 + comp;
   acc[o] = a;
-  if (vel) vel[o] = __fadd_rn(vel[o], __fmul_rn(ck_s[s], a));
+  if (vel) vel[o] = __fadd_rn(vel[o], __fmul_rn(ck_s[w.s], a));
 }
 
 // ---- segmented potential energy: one workgroup per item, energy_kernel's body (energy_body) on the item's scene (upper triangle,
@@ -118,15 +108,10 @@ __global__ __launch_bounds__(64 * kWaves) void batch_energy_kernel(const f4* __r
                                                                    const float* __restrict__ soft_s,
                                                                    double* __restrict__ pu) {
   __shared__ f4 lds[kEnergyLdsF4];
-  const int4 it = items[blockIdx.x];
-  const int s = __builtin_amdgcn_readfirstlane(it.x), grp = __builtin_amdgcn_readfirstlane(it.y);
-  const int slab = __builtin_amdgcn_readfirstlane(it.z);
-  const SceneRec sc = load_scene(scenes, s);
-  const int n = __builtin_amdgcn_readfirstlane(sc.n), n_chunks = __builtin_amdgcn_readfirstlane(sc.n_chunks);
-  const int slabs = __builtin_amdgcn_readfirstlane(sc.slabs);
-  const float soft = soft_s[s];
-  energy_body(posm + __builtin_amdgcn_readfirstlane(sc.poff), n, n_chunks, grp * kTgtPerWG, slab, slabs, soft,
-              !(soft > 0.f), lds, pu + (size_t)sc.u_off + (size_t)grp * slabs + slab);
+  const Item w = load_item(items, scenes);
+  const float soft = soft_s[w.s];
+  energy_body(posm + w.poff, w.n, w.n_chunks, w.grp * kTgtPerWG, w.slab, w.slabs, soft, !(soft > 0.f), lds,
+              pu + (size_t)w.sc.u_off + (size_t)w.grp * w.slabs + w.slab);
 }
 
 // one workgroup per scene: U_s = -G_s * (sum of its partials), K_s = sum 0.5 m v^2 (fp32 terms as kinetic_kernel,

@@ -40,23 +40,20 @@ __global__ __launch_bounds__(256) void batch_hermite_predict_kernel(const int* _
                                                                     const float* __restrict__ mass,
                                                                     const float* __restrict__ hdt, int n_scenes,
                                                                     f4* __restrict__ posm, f4* __restrict__ velp) {
-  const int r = blockIdx.x * 256 + threadIdx.x;
-  if (r >= n_rows) return;
-  const int s = row_scene[r];
-  const SceneRec sc = load_scene(scenes, s);
-  const int i = r - sc.poff;
+  PlanRow w;
+  if (!load_row(row_scene, scenes, n_rows, w)) return;
   f4 pm = HermiteFmt<float>::zero(), vp = HermiteFmt<float>::zero();
-  if (i < sc.n) {
-    const int b = sc.off + i;
-    const float dt = acc ? hdt[kDt * n_scenes + s] : 0.f;
-    const float dt2_half = acc ? hdt[kDt2Half * n_scenes + s] : 0.f;
-    const float dt3_sixth = acc ? hdt[kDt3Sixth * n_scenes + s] : 0.f;
+  if (w.i() < w.sc.n) {
+    const int b = w.sc.off + w.i();
+    const float dt = acc ? hdt[kDt * n_scenes + w.s] : 0.f;
+    const float dt2_half = acc ? hdt[kDt2Half * n_scenes + w.s] : 0.f;
+    const float dt3_sixth = acc ? hdt[kDt3Sixth * n_scenes + w.s] : 0.f;
     const PosVel3<float> p = hermite_predict_row(pos, vel, acc, jerk, (size_t)b, dt, dt2_half, dt3_sixth, acc != nullptr);
     pm = hermite_row(p.x, mass[b]);
     vp = hermite_row(p.v, 0.f);
   }
-  posm[r] = pm;
-  velp[r] = vp;
+  posm[w.r] = pm;
+  velp[w.r] = vp;
 }
 
 // One workgroup per item (s, g, k): targets [128 g, 128 g + 128) of scene s (its packed rows of posm / velp) against the
@@ -71,28 +68,19 @@ __global__ __launch_bounds__(64 * kWaves, 5) void batch_accel_jerk_kernel(const 
                                                                           const float* __restrict__ eps2_s,
                                                                           float* __restrict__ ws) {
   __shared__ f4 lds[kWaves * 4 * kChunk];
-  const int4 it = items[blockIdx.x];
-  const int s = __builtin_amdgcn_readfirstlane(it.x), grp = __builtin_amdgcn_readfirstlane(it.y);
-  const int slab = __builtin_amdgcn_readfirstlane(it.z);
-  const SceneRec sc = load_scene(scenes, s);
-  const int n = __builtin_amdgcn_readfirstlane(sc.n);
-  const int n_chunks = __builtin_amdgcn_readfirstlane(sc.n_chunks), slabs = __builtin_amdgcn_readfirstlane(sc.slabs);
-  const int poff = __builtin_amdgcn_readfirstlane(sc.poff);
-  const float eps2 = eps2_s[s];
-  const int t_base = grp * kTgtPerWG;
-  const int i0 = t_base + (threadIdx.x & 63), i1 = i0 + 64;
-  const int cpw_q = n_chunks / (slabs * kWaves), cpw_r = n_chunks % (slabs * kWaves);
-  const int jw = slab * kWaves + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  int c_begin, c_end;
-  wave_chunk_range(jw, cpw_q, cpw_r, c_begin, c_end);
-  float* dst = ws + 2 * (size_t)sc.ws_off + (size_t)slab * 6 * n + t_base;
-  const int n_valid = min(kTgtPerWG, n - t_base);
+  const Item w = load_item(items, scenes);
+  const float eps2 = eps2_s[w.s];
+  const Group128<int> g(w.grp, w.slab, w.n);
+  const ChunkSplit sp = chunk_split(w.n_chunks, w.slabs);
+  const ChunkRange c = wave_chunks(g.jw(), sp.q, sp.r);
+  float* dst = g.dst(ws + 2 * (size_t)w.sc.ws_off);
+  const int n_valid = g.n_valid();
   if (eps2 < kEps2Masked)
-    accel_jerk_body<true, 2>(posm + poff, velp + poff, n, posm + poff, velp + poff, min(i0, n - 1), min(i1, n - 1), i0, i1,
-                             c_begin, c_end, eps2, lds, dst, n, n_valid);
+    accel_jerk_body<true, 2>(posm + w.poff, velp + w.poff, w.n, posm + w.poff, velp + w.poff, g.r0(), g.r1(), g.i0, g.i1,
+                             c.begin, c.end, eps2, lds, dst, w.n, n_valid);
   else
-    accel_jerk_body<false, 2>(posm + poff, velp + poff, n, posm + poff, velp + poff, min(i0, n - 1), min(i1, n - 1), i0, i1,
-                              c_begin, c_end, eps2, lds, dst, n, n_valid);
+    accel_jerk_body<false, 2>(posm + w.poff, velp + w.poff, w.n, posm + w.poff, velp + w.poff, g.r0(), g.r1(), g.i0, g.i1,
+                              c.begin, c.end, eps2, lds, dst, w.n, n_valid);
 }
 
 // One workgroup per 64 packed rows (a scene's rows are whole chunks of 64, so a block never spans two scenes): a1, j1 =

@@ -44,25 +44,8 @@ __device__ __forceinline__ Hermite6Step load_step(const double* __restrict__ par
   return Hermite6Step{p[0], p[S], p[2 * S], p[3 * S], p[4 * S], p[5 * S], p[6 * S], p[7 * S], p[8 * S], p[9 * S]};
 }
 
-// ---- the 9-row plan: the float64 plan's geometry (plan_f64), the scene's slabs double[slabs][9][n] counted in DOUBLES
-SceneGeom scene_geom_h6(int n) {
-  const F64Plan p = plan_f64(n);
-  return SceneGeom{p.slabs, p.groups, (int64_t)p.slabs * 9 * n, 0};
-}
-
-int batch_totals_h6(const int* offsets, int n_scenes, BatchTotals* t) {
-  return batch_totals(offsets, n_scenes, t, scene_geom_h6);
-}
-
-size_t ws_bytes_h6(const BatchTotals& t) { return (size_t)t.ws_floats * sizeof(double); }
-
-int prologue_h6(const int* offsets, int n_scenes, const void* plan, size_t plan_bytes, BatchTotals* t) {
-  return batch_prologue(offsets, n_scenes, plan, plan_bytes, t, scene_geom_h6);
-}
-
-bool bad_workspace(const void* workspace, size_t workspace_bytes, const BatchTotals& t) {
-  return !workspace || misaligned8(workspace) || workspace_bytes < ws_bytes_h6(t);
-}
+// the plan counted in doubles (direct_batch_plan.h) with the scene's slabs double[slabs][9][n]
+constexpr int kOut = AccelJerkSnapPair::kOut;
 
 // posd[r] = {x_p, m}, veld[r] = {v_p, 0}, accd[r] = {a_p, 0} for every packed row r (zero rows behind each scene's last
 // body). jerk == nullptr (then snap, crackle and par are too): a plain pack of (x, v, a); acc == nullptr as well: accd = 0.
@@ -71,20 +54,17 @@ __global__ __launch_bounds__(256) void batch_hermite6_predict_kernel(
     const double* __restrict__ vel, const double* __restrict__ acc, const double* __restrict__ jerk,
     const double* __restrict__ snap, const double* __restrict__ crackle, const double* __restrict__ mass,
     const double* __restrict__ par, int n_scenes, d4* __restrict__ posd, d4* __restrict__ veld, d4* __restrict__ accd) {
-  const int r = blockIdx.x * 256 + threadIdx.x;
-  if (r >= n_rows) return;
-  const int s = row_scene[r];
-  const SceneRec sc = load_scene(scenes, s);
-  const int i = r - sc.poff;
+  PlanRow w;
+  if (!load_row(row_scene, scenes, n_rows, w)) return;
   d4 pm = {0.0, 0.0, 0.0, 0.0}, vp = pm, ap = pm;
-  if (i < sc.n) {
+  if (w.i() < w.sc.n) {
     Hermite6Step h = {};
-    if (jerk) h = load_step(par, n_scenes, s);
-    hermite6_predict_row(pos, vel, acc, jerk, snap, crackle, mass, (size_t)sc.off + i, h, pm, vp, ap);
+    if (jerk) h = load_step(par, n_scenes, w.s);
+    hermite6_predict_row(pos, vel, acc, jerk, snap, crackle, mass, (size_t)w.sc.off + w.i(), h, pm, vp, ap);
   }
-  posd[r] = pm;
-  veld[r] = vp;
-  accd[r] = ap;
+  posd[w.r] = pm;
+  veld[w.r] = vp;
+  accd[w.r] = ap;
 }
 
 // One workgroup per item (s, g, k): accel_jerk_snap_f64_kernel's prologue read from the scene record -- targets
@@ -100,16 +80,11 @@ __global__ __launch_bounds__(64 * kWaves) void batch_accel_jerk_snap_f64_kernel(
   const d4* pd = posd + w.poff;
   const d4* vd = veld + w.poff;
   const d4* ad = accd + w.poff;
-  const int t_base = w.grp * kTgtF64;
-  const int i = t_base + (threadIdx.x & 63), row = min(i, w.n - 1);
-  const int jw = w.slab * kWaves + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int parts = w.slabs * kWaves;
-  int c_begin, c_end;
-  wave_chunk_range(jw, w.n_chunks / parts, w.n_chunks % parts, c_begin, c_end);
-  AccelJerkSnapPair pr(pd[row], vd[row], ad[row], eps2, i, w.n);
-  walk_f64(pr, pd, vd, c_begin, c_end, eps2 < kEps2MaskedF64, w.grp, lds,
-           ws + (size_t)w.ws_off + (size_t)w.slab * AccelJerkSnapPair::kOut * w.n + t_base, (size_t)w.n,
-           min(kTgtF64, w.n - t_base), nullptr, ad);
+  const Group64<int> g(w.grp, w.slab, w.n);
+  const ChunkRange c = wave_chunks_of(g.jw(), w.n_chunks, w.slabs);
+  AccelJerkSnapPair pr(pd[g.row()], vd[g.row()], ad[g.row()], eps2, g.i, w.n);
+  walk_f64(pr, pd, vd, c.begin, c.end, eps2 < kEps2MaskedF64, w.grp, lds,
+           g.dst<AccelJerkSnapPair>(ws + (size_t)w.ws_off), (size_t)w.n, g.n_valid(), nullptr, ad);
 }
 
 // One thread per packed row (a row belongs to one scene; the padding rows leave at once): hermite6_finish_row of the body's
@@ -119,16 +94,12 @@ __global__ __launch_bounds__(256) void batch_hermite6_finish_kernel(
     const double* __restrict__ par, int n_scenes, double* pos, double* vel, const double* acc_in, const double* jerk_in,
     const double* snap_in, double* acc_out, double* jerk_out, double* snap_out, double* crackle_out,
     const double* __restrict__ mass, d4* __restrict__ posd) {
-  const int r = blockIdx.x * 256 + threadIdx.x;
-  if (r >= n_rows) return;
-  const int s = row_scene[r];
-  const SceneRec sc = load_scene(scenes, s);
-  const int i = r - sc.poff;
-  if (i >= sc.n) return;
-  const Hermite6Step h = load_step(par, n_scenes, s);
-  hermite6_finish_row(ws + (size_t)sc.ws_off, sc.slabs, (size_t)sc.n, (size_t)i, (size_t)sc.off + i,
-                      par[kG * n_scenes + s], h, pos, vel, acc_in, jerk_in, snap_in, acc_out, jerk_out, snap_out,
-                      crackle_out, mass, posd, (size_t)r);
+  PlanRow w;
+  if (!load_row(row_scene, scenes, n_rows, w) || w.i() >= w.sc.n) return;
+  const Hermite6Step h = load_step(par, n_scenes, w.s);
+  hermite6_finish_row(ws + (size_t)w.sc.ws_off, w.sc.slabs, (size_t)w.sc.n, (size_t)w.i(), (size_t)w.sc.off + w.i(),
+                      par[kG * n_scenes + w.s], h, pos, vel, acc_in, jerk_in, snap_in, acc_out, jerk_out, snap_out,
+                      crackle_out, mass, posd, (size_t)w.r);
 }
 
 int launch_predict(const DevPlan& d, const BatchTotals& t, const double* pos, const double* vel, const double* acc,
@@ -166,28 +137,18 @@ bool bad_rows(const double* posd, const double* veld, const double* accd) {
 extern "C" {
 
 int nbd_batch_hermite6_f64_plan_fill(const int* offsets, int n_scenes, void* plan, size_t plan_bytes) {
-  BatchTotals t;
-  const int rc = batch_totals_h6(offsets, n_scenes, &t);
-  if (rc) return rc;
-  if (!plan || plan_bytes != plan_bytes_of(t)) return NBD_E_BADARG;
-  batch_plan_fill(offsets, n_scenes, t, plan, scene_geom_h6);
-  return 0;
+  return plan_fill_f64<kOut>(offsets, n_scenes, plan, plan_bytes);
 }
 
 int nbd_batch_hermite6_f64_workspace_bytes(const int* offsets, int n_scenes, size_t* bytes) {
-  BatchTotals t;
-  const int rc = batch_totals_h6(offsets, n_scenes, &t);
-  if (rc) return rc;
-  if (!bytes) return NBD_E_BADARG;
-  *bytes = ws_bytes_h6(t);
-  return 0;
+  return workspace_bytes_f64<kOut>(offsets, n_scenes, bytes);
 }
 
 int nbd_batch_hermite6_pack_f64(const int* offsets, int n_scenes, const void* plan, size_t plan_bytes, const double* pos,
                                 const double* vel, const double* acc, const double* mass, double* posd, double* veld,
                                 double* accd, nbd_stream_t stream) {
   BatchTotals t;
-  const int rc = prologue_h6(offsets, n_scenes, plan, plan_bytes, &t);
+  const int rc = prologue_f64<kOut>(offsets, n_scenes, plan, plan_bytes, &t);
   if (rc) return rc;
   if (t.n_total == 0) return 0;
   if (!pos || !vel || !mass || bad_rows(posd, veld, accd)) return NBD_E_BADARG;
@@ -200,7 +161,7 @@ int nbd_batch_accel_jerk_snap_f64(const int* offsets, int n_scenes, const void* 
                                   double* acc_out, double* jerk_out, double* snap_out, void* workspace,
                                   size_t workspace_bytes, nbd_stream_t stream) {
   BatchTotals t;
-  const int rc = prologue_h6(offsets, n_scenes, plan, plan_bytes, &t);
+  const int rc = prologue_f64<kOut>(offsets, n_scenes, plan, plan_bytes, &t);
   if (rc) return rc;
   if (t.n_total == 0) return 0;
   if (bad_rows(posd, veld, accd) || !params || misaligned8(params) || !acc_out || misaligned8(acc_out) || !jerk_out ||
@@ -219,7 +180,7 @@ int nbd_batch_hermite6_step_f64(const int* offsets, int n_scenes, const void* pl
                                 double* veld, double* accd, void* workspace, size_t workspace_bytes,
                                 nbd_stream_t stream) {
   BatchTotals t;
-  int rc = prologue_h6(offsets, n_scenes, plan, plan_bytes, &t);
+  int rc = prologue_f64<kOut>(offsets, n_scenes, plan, plan_bytes, &t);
   if (rc) return rc;
   if (t.n_total == 0) return 0;
   if (!pos || !vel || !acc_in || !jerk_in || !snap_in || !crackle_in || !mass || !params || misaligned8(params) ||

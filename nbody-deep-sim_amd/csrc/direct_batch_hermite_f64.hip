@@ -36,26 +36,8 @@ namespace {
 enum ParamRow { kG = 0, kEps2, kEps, kDt, kDtHalf, kDt2Half, kDt3Sixth, kDt2Twelfth, kParams };
 static_assert(kParams == NBD_BATCH_F64_PARAM_ROWS, "the table include/nbd.h describes");
 
-// ---- the fp64 plan: the layout and the checks of direct_batch_plan.h with plan_f64's geometry. The scene's slabs are
-// double[slabs][6][n], counted in DOUBLES (BatchTotals::ws_floats, SceneRec::ws_off); no energy partials.
-SceneGeom scene_geom_f64(int n) {
-  const F64Plan p = plan_f64(n);
-  return SceneGeom{p.slabs, p.groups, (int64_t)p.slabs * 6 * n, 0};
-}
-
-int batch_totals_f64(const int* offsets, int n_scenes, BatchTotals* t) {
-  return batch_totals(offsets, n_scenes, t, scene_geom_f64);
-}
-
-size_t ws_bytes_f64(const BatchTotals& t) { return (size_t)t.ws_floats * sizeof(double); }
-
-int prologue_f64(const int* offsets, int n_scenes, const void* plan, size_t plan_bytes, BatchTotals* t) {
-  return batch_prologue(offsets, n_scenes, plan, plan_bytes, t, scene_geom_f64);
-}
-
-bool bad_workspace(const void* workspace, size_t workspace_bytes, const BatchTotals& t) {
-  return !workspace || misaligned8(workspace) || workspace_bytes < ws_bytes_f64(t);
-}
+// the plan counted in doubles (direct_batch_plan.h) with the scene's slabs double[slabs][6][n]
+constexpr int kOut = AccelJerkPair::kOut;
 
 // posd[r] = {x_p, m}, veld[r] = {v_p, 0} for every packed row r (zero rows behind each scene's last body).
 // acc == nullptr: a plain pack of (x, v).
@@ -68,23 +50,20 @@ __global__ __launch_bounds__(256) void batch_predict_f64_kernel(const int* __res
                                                                 const double* __restrict__ mass,
                                                                 const double* __restrict__ par, int n_scenes,
                                                                 d4* __restrict__ posd, d4* __restrict__ veld) {
-  const int r = blockIdx.x * 256 + threadIdx.x;
-  if (r >= n_rows) return;
-  const int s = row_scene[r];
-  const SceneRec sc = load_scene(scenes, s);
-  const int i = r - sc.poff;
+  PlanRow w;
+  if (!load_row(row_scene, scenes, n_rows, w)) return;
   d4 pm = HermiteFmt<double>::zero(), vp = HermiteFmt<double>::zero();
-  if (i < sc.n) {
-    const size_t b = (size_t)sc.off + i;
-    const double dt = acc ? par[kDt * n_scenes + s] : 0.0;
-    const double dt2_half = acc ? par[kDt2Half * n_scenes + s] : 0.0;
-    const double dt3_sixth = acc ? par[kDt3Sixth * n_scenes + s] : 0.0;
+  if (w.i() < w.sc.n) {
+    const size_t b = (size_t)w.sc.off + w.i();
+    const double dt = acc ? par[kDt * n_scenes + w.s] : 0.0;
+    const double dt2_half = acc ? par[kDt2Half * n_scenes + w.s] : 0.0;
+    const double dt3_sixth = acc ? par[kDt3Sixth * n_scenes + w.s] : 0.0;
     const PosVel3<double> p = hermite_predict_row(pos, vel, acc, jerk, b, dt, dt2_half, dt3_sixth, acc != nullptr);
     pm = hermite_row(p.x, mass[b]);
     vp = hermite_row(p.v, 0.0);
   }
-  posd[r] = pm;
-  veld[r] = vp;
+  posd[w.r] = pm;
+  veld[w.r] = vp;
 }
 
 // One workgroup per item (s, g, k): accel_jerk_f64_kernel's prologue read from the scene record -- targets
@@ -101,16 +80,11 @@ __global__ __launch_bounds__(64 * kWaves) void batch_accel_jerk_f64_kernel(const
   const double eps2 = par[kEps2 * n_scenes + w.s];
   const d4* pd = posd + w.poff;
   const d4* vd = veld + w.poff;
-  const int t_base = w.grp * kTgtF64;
-  const int i = t_base + (threadIdx.x & 63), row = min(i, w.n - 1);
-  const int jw = w.slab * kWaves + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int parts = w.slabs * kWaves;
-  int c_begin, c_end;
-  wave_chunk_range(jw, w.n_chunks / parts, w.n_chunks % parts, c_begin, c_end);
-  AccelJerkPair pr(pd[row], vd[row], eps2, i, w.n);
-  walk_f64(pr, pd, vd, c_begin, c_end, eps2 < kEps2MaskedF64, w.grp, lds,
-           ws + (size_t)w.ws_off + (size_t)w.slab * AccelJerkPair::kOut * w.n + t_base, (size_t)w.n,
-           min(kTgtF64, w.n - t_base));
+  const Group64<int> g(w.grp, w.slab, w.n);
+  const ChunkRange c = wave_chunks_of(g.jw(), w.n_chunks, w.slabs);
+  AccelJerkPair pr(pd[g.row()], vd[g.row()], eps2, g.i, w.n);
+  walk_f64(pr, pd, vd, c.begin, c.end, eps2 < kEps2MaskedF64, w.grp, lds,
+           g.dst<AccelJerkPair>(ws + (size_t)w.ws_off), (size_t)w.n, g.n_valid());
 }
 
 // One thread per packed row (a row belongs to one scene; the padding rows leave at once): a1, j1 = hermite_slab_sum of the
@@ -124,19 +98,17 @@ __global__ __launch_bounds__(256) void batch_correct_f64_kernel(const int* __res
                                                                 double* pos, double* vel, const double* acc_in,
                                                                 const double* jerk_in, double* acc_out, double* jerk_out,
                                                                 const double* __restrict__ mass, d4* __restrict__ posd) {
-  const int r = blockIdx.x * 256 + threadIdx.x;
-  if (r >= n_rows) return;
-  const int s = row_scene[r];
-  const SceneRec sc = load_scene(scenes, s);
-  const int i = r - sc.poff;
+  PlanRow w;
+  if (!load_row(row_scene, scenes, n_rows, w)) return;
   double a1[3], j1[3];
-  if (!hermite_slab_sum(ws + (size_t)sc.ws_off, sc.slabs, sc.n, (size_t)i, i < sc.n, par[kG * n_scenes + s], a1, j1))
+  if (!hermite_slab_sum(ws + (size_t)w.sc.ws_off, w.sc.slabs, w.sc.n, (size_t)w.i(), w.i() < w.sc.n,
+                        par[kG * n_scenes + w.s], a1, j1))
     return;
-  const size_t b = (size_t)sc.off + i;
+  const size_t b = (size_t)w.sc.off + w.i();
   if (pos) {
     const Corrected<double> c = hermite_correct_row(pos, vel, acc_in, jerk_in, b, a1, j1,
-                                                    par[kDtHalf * n_scenes + s], par[kDt2Twelfth * n_scenes + s]);
-    posd[r] = hermite_row(c.x1, mass[b]);
+                                                    par[kDtHalf * n_scenes + w.s], par[kDt2Twelfth * n_scenes + w.s]);
+    posd[w.r] = hermite_row(c.x1, mass[b]);
   }
   hermite_store_force(acc_out, jerk_out, b, a1, j1);
 }
@@ -154,15 +126,11 @@ __global__ __launch_bounds__(64 * kWaves) void batch_energy_f64_kernel(const d4*
   const Item w = load_item(items, scenes);
   const double soft = par[kEps * n_scenes + w.s];
   const d4* pd = posd + w.poff;
-  const int t_base = w.grp * kTgtF64;
-  const int i = t_base + (threadIdx.x & 63);
-  const int jw = w.slab * kWaves + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int span = w.n_chunks - w.grp, parts = w.slabs * kWaves;
-  int c_begin, c_end;
-  wave_chunk_range(jw, span / parts, span % parts, c_begin, c_end);
-  EnergyPair pr(pd[min(i, w.n - 1)], soft, i, w.n);
-  walk_f64(pr, pd, pd, c_begin + w.grp, c_end + w.grp, true, w.grp, lds,
-           ws + (size_t)w.ws_off + (size_t)w.slab * w.n + t_base, (size_t)w.n, min(kTgtF64, w.n - t_base));
+  const Group64<int> g(w.grp, w.slab, w.n);
+  const ChunkRange c = wave_chunks_upper(g.jw(), w.n_chunks, w.grp, w.slabs);
+  EnergyPair pr(pd[g.row()], soft, g.i, w.n);
+  walk_f64(pr, pd, pd, c.begin + w.grp, c.end + w.grp, true, w.grp, lds, g.dst<EnergyPair>(ws + (size_t)w.ws_off),
+           (size_t)w.n, g.n_valid());
 }
 
 // one workgroup per scene: out_uk[s] = {U_s, K_s} (energy_finish_f64; an empty scene gives {0, 0})
@@ -189,15 +157,11 @@ __global__ __launch_bounds__(64 * kWaves) void batch_potential_f64_kernel(const 
   const Item w = load_item(items, scenes);
   const double eps2 = par[kEps2 * n_scenes + w.s];
   const d4* pd = posd + w.poff;
-  const int t_base = w.grp * kTgtF64;
-  const int i = t_base + (threadIdx.x & 63);
-  const int jw = w.slab * kWaves + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int parts = w.slabs * kWaves;
-  int c_begin, c_end;
-  wave_chunk_range(jw, w.n_chunks / parts, w.n_chunks % parts, c_begin, c_end);
-  PotentialPair pr(pd[min(i, w.n - 1)], eps2, i, w.n);
-  walk_f64(pr, pd, pd, c_begin, c_end, eps2 < kEps2MaskedF64, w.grp, lds,
-           ws + (size_t)w.ws_off + (size_t)w.slab * w.n + t_base, (size_t)w.n, min(kTgtF64, w.n - t_base));
+  const Group64<int> g(w.grp, w.slab, w.n);
+  const ChunkRange c = wave_chunks_of(g.jw(), w.n_chunks, w.slabs);
+  PotentialPair pr(pd[g.row()], eps2, g.i, w.n);
+  walk_f64(pr, pd, pd, c.begin, c.end, eps2 < kEps2MaskedF64, w.grp, lds, g.dst<PotentialPair>(ws + (size_t)w.ws_off),
+           (size_t)w.n, g.n_valid());
 }
 
 // phi[off_s + i] = potential_finish_f64 of body i of its scene: one thread per packed row
@@ -206,13 +170,10 @@ __global__ __launch_bounds__(256) void batch_potential_finish_f64_kernel(const i
                                                                          int n_rows, const double* __restrict__ ws,
                                                                          const double* __restrict__ par, int n_scenes,
                                                                          double* __restrict__ phi) {
-  const int r = blockIdx.x * 256 + threadIdx.x;
-  if (r >= n_rows) return;
-  const int s = row_scene[r];
-  const SceneRec sc = load_scene(scenes, s);
-  const int i = r - sc.poff;
-  if (i >= sc.n) return;
-  phi[(size_t)sc.off + i] = potential_finish_f64(ws + (size_t)sc.ws_off, sc.slabs, sc.n, i, par[kG * n_scenes + s]);
+  PlanRow w;
+  if (!load_row(row_scene, scenes, n_rows, w) || w.i() >= w.sc.n) return;
+  phi[(size_t)w.sc.off + w.i()] =
+      potential_finish_f64(ws + (size_t)w.sc.ws_off, w.sc.slabs, w.sc.n, w.i(), par[kG * n_scenes + w.s]);
 }
 
 // one workgroup per scene: invariants_state_f64_kernel's body on the scene's part of the state
@@ -260,7 +221,7 @@ extern "C" {
 
 int nbd_batch_f64_plan(const int* offsets, int n_scenes, int* n_items, int* rows, size_t* plan_bytes) {
   BatchTotals t;
-  const int rc = batch_totals_f64(offsets, n_scenes, &t);
+  const int rc = batch_totals_f64<kOut>(offsets, n_scenes, &t);
   if (rc) return rc;
   if (n_items) *n_items = t.n_items;
   if (rows) *rows = t.n_rows;
@@ -269,27 +230,17 @@ int nbd_batch_f64_plan(const int* offsets, int n_scenes, int* n_items, int* rows
 }
 
 int nbd_batch_f64_workspace_bytes(const int* offsets, int n_scenes, size_t* bytes) {
-  BatchTotals t;
-  const int rc = batch_totals_f64(offsets, n_scenes, &t);
-  if (rc) return rc;
-  if (!bytes) return NBD_E_BADARG;
-  *bytes = ws_bytes_f64(t);
-  return 0;
+  return workspace_bytes_f64<kOut>(offsets, n_scenes, bytes);
 }
 
 int nbd_batch_f64_plan_fill(const int* offsets, int n_scenes, void* plan, size_t plan_bytes) {
-  BatchTotals t;
-  const int rc = batch_totals_f64(offsets, n_scenes, &t);
-  if (rc) return rc;
-  if (!plan || plan_bytes != plan_bytes_of(t)) return NBD_E_BADARG;
-  batch_plan_fill(offsets, n_scenes, t, plan, scene_geom_f64);
-  return 0;
+  return plan_fill_f64<kOut>(offsets, n_scenes, plan, plan_bytes);
 }
 
 int nbd_batch_pack_f64(const int* offsets, int n_scenes, const void* plan, size_t plan_bytes, const double* pos,
                        const double* vel, const double* mass, double* posd, double* veld, nbd_stream_t stream) {
   BatchTotals t;
-  const int rc = prologue_f64(offsets, n_scenes, plan, plan_bytes, &t);
+  const int rc = prologue_f64<kOut>(offsets, n_scenes, plan, plan_bytes, &t);
   if (rc) return rc;
   if (t.n_total == 0) return 0;
   if (!pos || !vel || !mass || !posd || !veld || misaligned32(posd) || misaligned32(veld)) return NBD_E_BADARG;
@@ -302,7 +253,7 @@ int nbd_batch_accel_jerk_f64(const int* offsets, int n_scenes, const void* plan,
                              double* jerk_out, double* posd, double* veld, void* workspace, size_t workspace_bytes,
                              nbd_stream_t stream) {
   BatchTotals t;
-  int rc = prologue_f64(offsets, n_scenes, plan, plan_bytes, &t);
+  int rc = prologue_f64<kOut>(offsets, n_scenes, plan, plan_bytes, &t);
   if (rc) return rc;
   if (t.n_total == 0) return 0;
   if (!pos || !vel || !mass || !params || misaligned8(params) || !acc_out || misaligned8(acc_out) || !jerk_out ||
@@ -321,7 +272,7 @@ int nbd_batch_hermite_step_f64(const int* offsets, int n_scenes, const void* pla
                                double* jerk_out, const double* mass, const double* params, double* posd, double* veld,
                                void* workspace, size_t workspace_bytes, nbd_stream_t stream) {
   BatchTotals t;
-  int rc = prologue_f64(offsets, n_scenes, plan, plan_bytes, &t);
+  int rc = prologue_f64<kOut>(offsets, n_scenes, plan, plan_bytes, &t);
   if (rc) return rc;
   if (t.n_total == 0) return 0;
   if (!pos || !vel || !acc_in || !jerk_in || !mass || !params || misaligned8(params) || !acc_out ||
@@ -340,7 +291,7 @@ int nbd_batch_energies_f64(const int* offsets, int n_scenes, const void* plan, s
                            const double* vel, const double* params, double* out_uk, void* workspace,
                            size_t workspace_bytes, nbd_stream_t stream) {
   BatchTotals t;
-  int rc = prologue_f64(offsets, n_scenes, plan, plan_bytes, &t);
+  int rc = prologue_f64<kOut>(offsets, n_scenes, plan, plan_bytes, &t);
   if (rc) return rc;
   if (!out_uk || misaligned8(out_uk) || !params || misaligned8(params)) return NBD_E_BADARG;
   if (t.n_total > 0 && (!posd || !vel || misaligned32(posd))) return NBD_E_BADARG;
@@ -361,7 +312,7 @@ int nbd_batch_potential_f64(const int* offsets, int n_scenes, const void* plan, 
                             const double* params, double* phi_out, void* workspace, size_t workspace_bytes,
                             nbd_stream_t stream) {
   BatchTotals t;
-  int rc = prologue_f64(offsets, n_scenes, plan, plan_bytes, &t);
+  int rc = prologue_f64<kOut>(offsets, n_scenes, plan, plan_bytes, &t);
   if (rc) return rc;
   if (t.n_total == 0) return 0;
   if (!posd || misaligned32(posd) || !params || misaligned8(params) || !phi_out || misaligned8(phi_out))
@@ -382,7 +333,7 @@ int nbd_batch_invariants_state_f64(const int* offsets, int n_scenes, const void*
                                    const double* pos, const double* vel, const double* mass, const double* phi,
                                    double* out_rows, nbd_stream_t stream) {
   BatchTotals t;
-  const int rc = prologue_f64(offsets, n_scenes, plan, plan_bytes, &t);
+  const int rc = prologue_f64<kOut>(offsets, n_scenes, plan, plan_bytes, &t);
   if (rc) return rc;
   if (!out_rows || misaligned8(out_rows)) return NBD_E_BADARG;
   if (t.n_total > 0 && (!pos || !vel || !mass || !phi || misaligned8(phi))) return NBD_E_BADARG;

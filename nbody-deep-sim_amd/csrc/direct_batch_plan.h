@@ -1,9 +1,11 @@
-// direct_batch_plan.h -- the device work list of the batched direct integrator (nbd_batch_plan / nbd_batch_plan_fill)
-// and the host checks every batched entry point makes before it launches, shared by direct_batch.hip (leapfrog, Euler,
-// energies), direct_batch_hermite.hip (Hermite), direct_batch_hermite_f64.hip (Hermite in double precision: the same
-// layout filled with another geometry per scene, SceneGeom below) and direct_batch_hermite6_f64.hip (6th-order Hermite:
-// that geometry with nine doubles per body and slab). The definitions sit in an anonymous namespace: every translation
-// unit that includes this file gets its own copies.
+// direct_batch_plan.h -- the device work list of the batched direct integrator (nbd_batch_plan / nbd_batch_plan_fill),
+// what a kernel reads from it (load_item: one workgroup per item; load_row: one thread per packed row) and the host
+// checks every batched entry point makes before it launches. Shared by direct_batch.hip (leapfrog, Euler, energies),
+// direct_diag.hip (the batched diagnostics), direct_batch_hermite.hip (Hermite), direct_batch_hermite_f64.hip (Hermite in
+// double precision) and direct_batch_hermite6_f64.hip (6th-order Hermite). The two float64 units fill the same layout
+// with another geometry per scene (SceneGeom below); the host shell of such a plan counted in doubles -- totals, plan
+// fill, workspace size and checks, for kOut doubles per body and slab -- is here once, at the end. The definitions sit in
+// an anonymous namespace: every translation unit that includes this file gets its own copies.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <limits.h>
@@ -15,6 +17,7 @@
 
 #include "../../include/nbd.h"
 #include "direct_kernels.h"
+#include "hermite_f64_kernels.h"
 
 namespace {
 
@@ -45,8 +48,8 @@ int scene_slabs(int n) {
   return s;
 }
 
-// What a plan gives a scene of n > 0 bodies, and all that the fp32 plan and the fp64 plan
-// (direct_batch_hermite_f64.hip: groups of 64 targets, plan_f64's slabs) differ in: a function int -> SceneGeom.
+// What a plan gives a scene of n > 0 bodies, and all that the fp32 plan and the fp64 plans (scene_geom_f64 below: groups
+// of 64 targets, plan_f64's slabs) differ in: a function int -> SceneGeom.
 struct SceneGeom {
   int slabs, groups;
   int64_t ws;   // elements of the scene's slabs in the workspace, in the plan's own unit (ws_off counts them)
@@ -114,10 +117,39 @@ __device__ __forceinline__ SceneRec load_scene(const SceneRec* scenes, int s) {
   return SceneRec{a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
 }
 
-// What a workgroup of an item of the fp64 plans reads from the work list (direct_batch_hermite_f64.hip,
-// direct_batch_hermite6_f64.hip: one workgroup per item), uniform across the workgroup (SGPRs)
+// What a thread that works on packed row r reads from the plan: the row's scene s and record sc, and the body
+// i = r - poff of that scene (i >= sc.n: a padding row).
+struct PlanRow {
+  int r, s;
+  SceneRec sc;
+  __device__ __forceinline__ int i() const { return r - sc.poff; }
+};
+
+__device__ __forceinline__ PlanRow row_of(const int* __restrict__ row_scene, const SceneRec* __restrict__ scenes,
+                                          int r) {
+  PlanRow w;
+  w.r = r;
+  w.s = row_scene[r];
+  w.sc = load_scene(scenes, w.s);
+  return w;
+}
+
+// ... of a per-row kernel (256 threads per workgroup, one per packed row) into w. False behind the last row: w is not
+// set and the thread leaves.
+__device__ __forceinline__ bool load_row(const int* __restrict__ row_scene, const SceneRec* __restrict__ scenes,
+                                         int n_rows, PlanRow& w) {
+  const int r = blockIdx.x * 256 + threadIdx.x;
+  if (r >= n_rows) return false;
+  w = row_of(row_scene, scenes, r);
+  return true;
+}
+
+// What a workgroup of an item reads from the work list (one workgroup per item, in every plan), uniform across the
+// workgroup (SGPRs); sc is the scene's record as it was loaded, for what a kernel only adds to a pointer (u_off, and the
+// fp32 units' ws_off)
 struct Item {
   int s, grp, slab, n, n_chunks, slabs, poff, ws_off;
+  SceneRec sc;
 };
 
 __device__ __forceinline__ Item load_item(const int4* __restrict__ items, const SceneRec* __restrict__ scenes) {
@@ -126,12 +158,12 @@ __device__ __forceinline__ Item load_item(const int4* __restrict__ items, const 
   w.s = __builtin_amdgcn_readfirstlane(it.x);
   w.grp = __builtin_amdgcn_readfirstlane(it.y);
   w.slab = __builtin_amdgcn_readfirstlane(it.z);
-  const SceneRec sc = load_scene(scenes, w.s);
-  w.n = __builtin_amdgcn_readfirstlane(sc.n);
-  w.n_chunks = __builtin_amdgcn_readfirstlane(sc.n_chunks);
-  w.slabs = __builtin_amdgcn_readfirstlane(sc.slabs);
-  w.poff = __builtin_amdgcn_readfirstlane(sc.poff);
-  w.ws_off = __builtin_amdgcn_readfirstlane(sc.ws_off);
+  w.sc = load_scene(scenes, w.s);
+  w.n = __builtin_amdgcn_readfirstlane(w.sc.n);
+  w.n_chunks = __builtin_amdgcn_readfirstlane(w.sc.n_chunks);
+  w.slabs = __builtin_amdgcn_readfirstlane(w.sc.slabs);
+  w.poff = __builtin_amdgcn_readfirstlane(w.sc.poff);
+  w.ws_off = __builtin_amdgcn_readfirstlane(w.sc.ws_off);
   return w;
 }
 
@@ -181,6 +213,50 @@ int batch_prologue(const int* offsets, int n_scenes, const void* plan, size_t pl
 
 inline int batch_prologue(const int* offsets, int n_scenes, const void* plan, size_t plan_bytes, BatchTotals* t) {
   return batch_prologue(offsets, n_scenes, plan, plan_bytes, t, scene_geom_f32);
+}
+
+// ---- the plans counted in doubles (direct_batch_hermite_f64.hip: kOut = 6; direct_batch_hermite6_f64.hip: kOut = 9): the
+// layout and the checks above with plan_f64's geometry -- one item per (scene, group of 64 targets, slab), the one-system
+// float64 launch for the scene's size. The scene's slabs are double[slabs][kOut][n], counted in DOUBLES
+// (BatchTotals::ws_floats, SceneRec::ws_off); no energy partials. The items, rows and bytes of the plan do not depend on
+// kOut, only ws_off does.
+template <int kOut>
+SceneGeom scene_geom_f64(int n) {
+  const F64Plan p = plan_f64(n);
+  return SceneGeom{p.slabs, p.groups, (int64_t)p.slabs * kOut * n, 0};
+}
+
+template <int kOut>
+int batch_totals_f64(const int* offsets, int n_scenes, BatchTotals* t) {
+  return batch_totals(offsets, n_scenes, t, scene_geom_f64<kOut>);
+}
+inline size_t ws_bytes_f64(const BatchTotals& t) { return (size_t)t.ws_floats * sizeof(double); }
+template <int kOut>
+int prologue_f64(const int* offsets, int n_scenes, const void* plan, size_t plan_bytes, BatchTotals* t) {
+  return batch_prologue(offsets, n_scenes, plan, plan_bytes, t, scene_geom_f64<kOut>);
+}
+inline bool bad_workspace(const void* workspace, size_t workspace_bytes, const BatchTotals& t) {
+  return !workspace || misaligned8(workspace) || workspace_bytes < ws_bytes_f64(t);
+}
+
+// the bodies of the nbd_batch_*f64_plan_fill and nbd_batch_*f64_workspace_bytes entries
+template <int kOut>
+int plan_fill_f64(const int* offsets, int n_scenes, void* plan, size_t plan_bytes) {
+  BatchTotals t;
+  const int rc = batch_totals_f64<kOut>(offsets, n_scenes, &t);
+  if (rc) return rc;
+  if (!plan || plan_bytes != plan_bytes_of(t)) return NBD_E_BADARG;
+  batch_plan_fill(offsets, n_scenes, t, plan, scene_geom_f64<kOut>);
+  return 0;
+}
+template <int kOut>
+int workspace_bytes_f64(const int* offsets, int n_scenes, size_t* bytes) {
+  BatchTotals t;
+  const int rc = batch_totals_f64<kOut>(offsets, n_scenes, &t);
+  if (rc) return rc;
+  if (!bytes) return NBD_E_BADARG;
+  *bytes = ws_bytes_f64(t);
+  return 0;
 }
 
 }  // namespace

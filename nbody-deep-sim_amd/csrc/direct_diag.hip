@@ -72,17 +72,12 @@ __global__ __launch_bounds__(64 * kWaves) void batch_potential_kernel(const f4* 
                                                                       const float* __restrict__ eps2_s,
                                                                       double* __restrict__ ws) {
   __shared__ f4 lds[kPotLdsF4];
-  const int4 it = items[blockIdx.x];
-  const int s = __builtin_amdgcn_readfirstlane(it.x), grp = __builtin_amdgcn_readfirstlane(it.y);
-  const int slab = __builtin_amdgcn_readfirstlane(it.z);
-  const SceneRec sc = load_scene(scenes, s);
-  const int n = __builtin_amdgcn_readfirstlane(sc.n);
-  const int n_chunks = __builtin_amdgcn_readfirstlane(sc.n_chunks), slabs = __builtin_amdgcn_readfirstlane(sc.slabs);
-  const f4* src = posm + __builtin_amdgcn_readfirstlane(sc.poff);
-  const float eps2 = eps2_s[s];
-  const int t_base = grp * kTgtPerWG;
-  potential_body(src, n, n_chunks, slabs, eps2 < kEps2Masked, src, n, 0, t_base, slab, eps2, lds,
-                 ws + sc.ws_off / 3 + (size_t)slab * n + t_base);
+  const Item w = load_item(items, scenes);
+  const f4* src = posm + w.poff;
+  const float eps2 = eps2_s[w.s];
+  const int t_base = w.grp * kTgtPerWG;
+  potential_body(src, w.n, w.n_chunks, w.slabs, eps2 < kEps2Masked, src, w.n, 0, t_base, w.slab, eps2, lds,
+                 ws + w.sc.ws_off / 3 + (size_t)w.slab * w.n + t_base);
 }
 
 __global__ __launch_bounds__(256) void batch_potential_finish_kernel(const int* __restrict__ row_scene,
@@ -90,13 +85,9 @@ __global__ __launch_bounds__(256) void batch_potential_finish_kernel(const int* 
                                                                      const double* __restrict__ ws,
                                                                      const float* __restrict__ g_s,
                                                                      double* __restrict__ phi) {
-  const int r = blockIdx.x * 256 + threadIdx.x;
-  if (r >= n_rows) return;
-  const int s = row_scene[r];
-  const SceneRec sc = load_scene(scenes, s);
-  const int i = r - sc.poff;
-  if (i >= sc.n) return;
-  phi[sc.off + i] = finish_phi(ws + sc.ws_off / 3 + i, sc.slabs, (size_t)sc.n, g_s[s]);
+  PlanRow w;
+  if (!load_row(row_scene, scenes, n_rows, w) || w.i() >= w.sc.n) return;
+  phi[w.sc.off + w.i()] = finish_phi(ws + w.sc.ws_off / 3 + w.i(), w.sc.slabs, (size_t)w.sc.n, g_s[w.s]);
 }
 
 __global__ __launch_bounds__(kInvThreads) void batch_invariants_kernel(const SceneRec* __restrict__ scenes,
@@ -115,8 +106,6 @@ inline int potential_slabs(int n_src, int n_tgt) {
   if (nbd_accel_plan(n_src, n_tgt, nullptr, &s, nullptr) != 0 || s < 1) s = 1;
   return s;
 }
-
-inline bool misaligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7) != 0; }
 
 }  // namespace
 

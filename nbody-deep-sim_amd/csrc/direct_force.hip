@@ -873,7 +873,7 @@ ShardPlan plan_shard(int n_total, int lo, int n_local) {
 
 int nbd_shard_plan(int n_total, int lo, int n_local, int* slabs_local, int* cpw_local, int* slabs_remote,
                    int* cpw_remote) {
-  if (n_total <= 0 || lo < 0 || n_local <= 0 || lo + n_local > n_total) return NBD_E_BADARG;
+  if (!shard_args_ok(n_total, lo, n_local) || n_local == 0) return NBD_E_BADARG;
   const ShardPlan sp = plan_shard(n_total, lo, n_local);
   if (slabs_local) *slabs_local = sp.local.slabs;
   if (cpw_local) *cpw_local = sp.local.cpw;
@@ -883,7 +883,7 @@ int nbd_shard_plan(int n_total, int lo, int n_local, int* slabs_local, int* cpw_
 }
 
 size_t nbd_shard_workspace_bytes(int n_total, int lo, int n_local) {
-  if (n_total <= 0 || lo < 0 || n_local <= 0 || lo + n_local > n_total) return 0;
+  if (!shard_args_ok(n_total, lo, n_local) || n_local == 0) return 0;
   const ShardPlan sp = plan_shard(n_total, lo, n_local);
   return (size_t)(sp.local.slabs + sp.remote.slabs) * n_local * 3 * sizeof(float);
 }
@@ -891,7 +891,7 @@ size_t nbd_shard_workspace_bytes(int n_total, int lo, int n_local) {
 // the rank's own block: targets and sources are the same array, the diagonal is at j == i (offset 0)
 static int shard_force_local(const float* posm_local, int n_local, float softening_sq, void* workspace,
                              size_t workspace_bytes, int n_total, int lo, nbd_stream_t stream, bool uniform) {
-  if (n_local < 0 || n_total < 0 || lo < 0 || lo + n_local > n_total) return NBD_E_BADARG;
+  if (!shard_args_ok(n_total, lo, n_local)) return NBD_E_BADARG;
   if (n_local == 0) return 0;
   if (!posm_local || misaligned16(posm_local)) return NBD_E_BADARG;
   if (!workspace || workspace_bytes < nbd_shard_workspace_bytes(n_total, lo, n_local)) return NBD_E_WORKSPACE;
@@ -904,7 +904,7 @@ static int shard_force_local(const float* posm_local, int n_local, float softeni
 static int shard_force_remote(const float* posm_all, int n_total, const float* posm_local, int n_local, int lo,
                               float softening_sq, float g_scale, float* acc_out, float* vel, float c_kick,
                               void* workspace, size_t workspace_bytes, nbd_stream_t stream, bool uniform) {
-  if (n_local < 0 || n_total < 0 || lo < 0 || lo + n_local > n_total) return NBD_E_BADARG;
+  if (!shard_args_ok(n_total, lo, n_local)) return NBD_E_BADARG;
   if (n_local == 0) return 0;
   if (!posm_all || !posm_local || !acc_out || misaligned16(posm_all) || misaligned16(posm_local)) return NBD_E_BADARG;
   if (!workspace || workspace_bytes < nbd_shard_workspace_bytes(n_total, lo, n_local)) return NBD_E_WORKSPACE;

@@ -35,13 +35,10 @@ __global__ __launch_bounds__(64 * kWaves, KU == 2 ? 6 : 5) void accel_jerk_kerne
     const f4* __restrict__ posm, const f4* __restrict__ velp, int n, int cpw_q, int cpw_r, float eps2,
     float* __restrict__ out) {
   __shared__ f4 lds[kWaves * 4 * kChunk];
-  const int t_base = blockIdx.x * kTgtPerWG;
-  const int i0 = t_base + (threadIdx.x & 63), i1 = i0 + 64;
-  const int jw = blockIdx.y * kWaves + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  int c_begin, c_end;
-  wave_chunk_range(jw, cpw_q, cpw_r, c_begin, c_end);
-  accel_jerk_body<MASKED, KU>(posm, velp, n, posm, velp, min(i0, n - 1), min(i1, n - 1), i0, i1, c_begin, c_end, eps2, lds,
-                              out + (size_t)blockIdx.y * 6 * n + t_base, n, min(kTgtPerWG, n - t_base));
+  const Group128<unsigned> g(blockIdx.x, blockIdx.y, n);
+  const ChunkRange c = wave_chunks(g.jw(), cpw_q, cpw_r);
+  accel_jerk_body<MASKED, KU>(posm, velp, n, posm, velp, g.r0(), g.r1(), g.i0, g.i1, c.begin, c.end, eps2, lds,
+                              g.dst(out), n, g.n_valid());
 }
 
 constexpr int kSumRows = HermiteFmt<float>::kSumRows;      // bodies per workgroup of the corrector launch

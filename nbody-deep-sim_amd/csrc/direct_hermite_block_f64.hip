@@ -49,14 +49,12 @@ __global__ __launch_bounds__(64 * kWaves, 5) void accel_jerk_active_f64_kernel(c
                                                                             int cpw_q, int cpw_r, double eps2,
                                                                             int all_masked, double* __restrict__ out) {
   __shared__ __attribute__((aligned(32))) f4 lds[kWaves * stage_quads<true>()];
-  const int t_base = blockIdx.x * kTgtF64;
-  const int i = act[min(t_base + (int)(threadIdx.x & 63), n_act - 1)];
-  const int jw = blockIdx.y * kWaves + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  int c_begin, c_end;
-  wave_chunk_range(jw, cpw_q, cpw_r, c_begin, c_end);
+  const Group64<unsigned> g(blockIdx.x, blockIdx.y, n_act);      // a group of list entries: the lane's body is act[its entry]
+  const ChunkRange c = wave_chunks(g.jw(), cpw_q, cpw_r);
+  const int i = act[g.row()];
   AccelJerkPair pr(posd[i], veld[i], eps2, i, n);
-  walk_f64(pr, posd, veld, c_begin, c_end, all_masked != 0, -1, lds,
-           out + (size_t)blockIdx.y * AccelJerkPair::kOut * n_act + t_base, (size_t)n_act, min(kTgtF64, n_act - t_base));
+  walk_f64(pr, posd, veld, c.begin, c.end, all_masked != 0, -1, lds, g.dst<AccelJerkPair>(out), (size_t)n_act,
+           g.n_valid());
 }
 
 constexpr int kSumRows = HermiteFmt<double>::kSumRows;      // list entries per workgroup of the corrector launch

@@ -28,8 +28,9 @@
 // The two O(N) kernels, the predictor, the corrector and the step constants are hermite_kernels.h's templates at
 // T = double: the step constants are the five doubles formed from dt, never rounded to fp32. The finishing kernels of the
 // diagnostics add their slabs with the same slab_order_sum.
-// rsqrt_f64, the pair functors, the bodies of the finishing kernels, walk_f64 and plan_f64 live in hermite_f64_kernels.h,
-// shared with direct_hermite_block_f64.hip and direct_batch_hermite_f64.hip.
+// rsqrt_f64, the pair functors, the bodies of the finishing kernels, walk_f64, the kernels' prologue (Group64,
+// wave_chunks_upper) and plan_f64 live in hermite_f64_kernels.h, shared with every other float64 unit (the block-timestep,
+// the sharded, the batched, the leapfrog, the 6th-order and the backward ones).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -47,14 +48,11 @@ __global__ __launch_bounds__(64 * kWaves) void accel_jerk_f64_kernel(const d4* _
                                                                      int cpw_r, double eps2, int all_masked,
                                                                      double* __restrict__ out) {
   __shared__ __attribute__((aligned(32))) f4 lds[kWaves * stage_quads<true>()];
-  const int t_base = blockIdx.x * kTgtF64;
-  const int i = t_base + (threadIdx.x & 63), row = min(i, n - 1);
-  const int jw = blockIdx.y * kWaves + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  int c_begin, c_end;
-  wave_chunk_range(jw, cpw_q, cpw_r, c_begin, c_end);
-  AccelJerkPair pr(posd[row], veld[row], eps2, i, n);
-  walk_f64(pr, posd, veld, c_begin, c_end, all_masked != 0, blockIdx.x, lds,
-           out + (size_t)blockIdx.y * AccelJerkPair::kOut * n + t_base, (size_t)n, min(kTgtF64, n - t_base));
+  const Group64<unsigned> g(blockIdx.x, blockIdx.y, n);
+  const ChunkRange c = wave_chunks(g.jw(), cpw_q, cpw_r);
+  AccelJerkPair pr(posd[g.row()], veld[g.row()], eps2, g.i, n);
+  walk_f64(pr, posd, veld, c.begin, c.end, all_masked != 0, blockIdx.x, lds, g.dst<AccelJerkPair>(out), (size_t)n,
+           g.n_valid());
 }
 
 // The same geometry for the potential. out: double[slab][n].
@@ -62,14 +60,11 @@ __global__ __launch_bounds__(64 * kWaves) void potential_f64_kernel(const d4* __
                                                                     int cpw_r, double eps2, int all_masked,
                                                                     double* __restrict__ out) {
   __shared__ __attribute__((aligned(32))) f4 lds[kWaves * stage_quads<false>()];
-  const int t_base = blockIdx.x * kTgtF64;
-  const int i = t_base + (threadIdx.x & 63);
-  const int jw = blockIdx.y * kWaves + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  int c_begin, c_end;
-  wave_chunk_range(jw, cpw_q, cpw_r, c_begin, c_end);
-  PotentialPair pr(posd[min(i, n - 1)], eps2, i, n);
-  walk_f64(pr, posd, posd, c_begin, c_end, all_masked != 0, blockIdx.x, lds, out + (size_t)blockIdx.y * n + t_base,
-           (size_t)n, min(kTgtF64, n - t_base));
+  const Group64<unsigned> g(blockIdx.x, blockIdx.y, n);
+  const ChunkRange c = wave_chunks(g.jw(), cpw_q, cpw_r);
+  PotentialPair pr(posd[g.row()], eps2, g.i, n);
+  walk_f64(pr, posd, posd, c.begin, c.end, all_masked != 0, blockIdx.x, lds, g.dst<PotentialPair>(out), (size_t)n,
+           g.n_valid());
 }
 
 // The pair energies of the upper triangle: group g needs the chunks [g, n_chunks) only (chunk g is the group's own rows),
@@ -77,15 +72,11 @@ __global__ __launch_bounds__(64 * kWaves) void potential_f64_kernel(const d4* __
 __global__ __launch_bounds__(64 * kWaves) void energy_f64_kernel(const d4* __restrict__ posd, int n, int n_chunks,
                                                                  double soft, double* __restrict__ out) {
   __shared__ __attribute__((aligned(32))) f4 lds[kWaves * stage_quads<false>()];
-  const int t_base = blockIdx.x * kTgtF64;
-  const int i = t_base + (threadIdx.x & 63);
-  const int jw = blockIdx.y * kWaves + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int span = n_chunks - (int)blockIdx.x, parts = gridDim.y * kWaves;
-  int c_begin, c_end;
-  wave_chunk_range(jw, span / parts, span % parts, c_begin, c_end);
-  EnergyPair pr(posd[min(i, n - 1)], soft, i, n);
-  walk_f64(pr, posd, posd, c_begin + blockIdx.x, c_end + blockIdx.x, true, blockIdx.x, lds,
-           out + (size_t)blockIdx.y * n + t_base, (size_t)n, min(kTgtF64, n - t_base));
+  const Group64<unsigned> g(blockIdx.x, blockIdx.y, n);
+  const ChunkRange c = wave_chunks_upper<unsigned>(g.jw(), n_chunks, blockIdx.x, gridDim.y);
+  EnergyPair pr(posd[g.row()], soft, g.i, n);
+  walk_f64(pr, posd, posd, c.begin + blockIdx.x, c.end + blockIdx.x, true, blockIdx.x, lds, g.dst<EnergyPair>(out),
+           (size_t)n, g.n_valid());
 }
 
 // phi[i] = potential_finish_f64 of body i

@@ -311,14 +311,11 @@ __global__ __launch_bounds__(64 * kWaves) void accel_jerk_vjp_f64_kernel(const d
                                                                          int cpw_r, double eps2, int all_masked,
                                                                          double* __restrict__ out) {
   __shared__ __attribute__((aligned(32))) f4 lds[kWaves * stage_quads_n<3>()];
-  const int t_base = blockIdx.x * kTgtF64;
-  const int i = t_base + (threadIdx.x & 63), row = min(i, n - 1);
-  const int jw = blockIdx.y * kWaves + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  int c_begin, c_end;
-  wave_chunk_range(jw, cpw_q, cpw_r, c_begin, c_end);
-  AccelJerkVjpPair pr(posd[row], veld[row], cotj[row], eps2, i, n);
-  walk_f64(pr, posd, veld, c_begin, c_end, all_masked != 0, blockIdx.x, lds,
-           out + (size_t)blockIdx.y * kHvjpOut * n + t_base, (size_t)n, min(kTgtF64, n - t_base), nullptr, cotj);
+  const Group64<unsigned> g(blockIdx.x, blockIdx.y, n);
+  const ChunkRange c = wave_chunks(g.jw(), cpw_q, cpw_r);
+  AccelJerkVjpPair pr(posd[g.row()], veld[g.row()], cotj[g.row()], eps2, g.i, n);
+  walk_f64(pr, posd, veld, c.begin, c.end, all_masked != 0, blockIdx.x, lds, g.dst<AccelJerkVjpPair>(out), (size_t)n,
+           g.n_valid(), nullptr, cotj);
 }
 
 // One thread per body: the slabs of double[n_slabs][7][n] in slab order (slab_order_sum, hermite_kernels.h), then G, once,

@@ -38,15 +38,11 @@ __global__ __launch_bounds__(64 * kWaves, RANGE ? 5 : 6) void shard_accel_jerk_k
     const f4* __restrict__ src, const SrcView sv, const f4* __restrict__ tgt, int n_tgt, int tgt_off, float eps2,
     float* __restrict__ out) {
   __shared__ f4 lds[kWaves * 4 * kChunk];
-  const int t_base = blockIdx.x * kTgtPerWG;
-  const int l0 = t_base + (threadIdx.x & 63), l1 = l0 + 64;
-  const int jw = blockIdx.y * kWaves + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  int c_begin, c_end;
-  wave_chunk_range(jw, sv.cpw_q, sv.cpw_r, c_begin, c_end);
-  accel_jerk_body<MASKED, 2, kRowQuads, RANGE>(src, src + 1, sv.n_src, tgt, tgt + 1, min(l0, n_tgt - 1),
-                                               min(l1, n_tgt - 1), tgt_off + l0, tgt_off + l1, c_begin, c_end, eps2, lds,
-                                               out + (size_t)blockIdx.y * 6 * n_tgt + t_base, n_tgt,
-                                               min(kTgtPerWG, n_tgt - t_base), &sv);
+  const Group128<unsigned> g(blockIdx.x, blockIdx.y, n_tgt);
+  const ChunkRange c = wave_chunks(g.jw(), sv.cpw_q, sv.cpw_r);
+  accel_jerk_body<MASKED, 2, kRowQuads, RANGE>(src, src + 1, sv.n_src, tgt, tgt + 1, g.r0(), g.r1(), tgt_off + g.i0,
+                                               tgt_off + g.i1, c.begin, c.end, eps2, lds, g.dst(out), n_tgt, g.n_valid(),
+                                               &sv);
 }
 
 // rows [0, rows) of the send buffer: {x_p, m}, {v_p, 0} of the rank's bodies, zeros behind n. acc == nullptr: plain pack.
@@ -82,10 +78,6 @@ __global__ __launch_bounds__(256) void shard_finish_kernel(const float* __restri
 // The geometry of a rank's two force launches: the leapfrog shard's slab counts (nbd_shard_plan: same targets, same
 // chunks, the same balance problem), raised where a wave's sequential fp32 chain would pass 64 chunks (4096 sources).
 struct HShardPlan { int groups, slabs_local, chunks_local, slabs_remote, chunks_remote; SrcView remote; };
-
-bool shard_args_ok(int n_total, int lo, int n_local) {
-  return n_total >= 0 && lo >= 0 && n_local >= 0 && lo <= n_total && n_local <= n_total - lo;
-}
 
 int chain_slabs(int slabs, int n_chunks) {
   const int min_slabs = ceil_div(n_chunks, kWaves * 64);

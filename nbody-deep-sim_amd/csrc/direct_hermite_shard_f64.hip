@@ -41,16 +41,13 @@ __global__ __launch_bounds__(64 * kWaves) void shard_accel_jerk_f64_kernel(const
                                                                            int tgt_off, double eps2, int all_masked,
                                                                            double* __restrict__ out) {
   __shared__ __attribute__((aligned(32))) f4 lds[kWaves * stage_quads<true>()];
-  const int t_base = blockIdx.x * kTgtF64;
-  const int t = t_base + (threadIdx.x & 63);
-  const size_t row = (size_t)min(t, n_tgt - 1) * 2;
-  const int jw = blockIdx.y * kWaves + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  int c_begin, c_end;
-  wave_chunk_range(jw, sv.cpw_q, sv.cpw_r, c_begin, c_end);
-  AccelJerkPair pr(tgt[row], tgt[row + 1], eps2, tgt_off + t, sv.n_src);
-  walk_f64<AccelJerkPair, kShardRowQuads, RANGE>(
-      pr, src, src + 1, c_begin, c_end, all_masked != 0, RANGE ? -1 : (int)blockIdx.x, lds,
-      out + (size_t)blockIdx.y * AccelJerkPair::kOut * n_tgt + t_base, (size_t)n_tgt, min(kTgtF64, n_tgt - t_base), &sv);
+  const Group64<unsigned> g(blockIdx.x, blockIdx.y, n_tgt);
+  const ChunkRange c = wave_chunks(g.jw(), sv.cpw_q, sv.cpw_r);
+  const size_t row = (size_t)g.row() * 2;
+  AccelJerkPair pr(tgt[row], tgt[row + 1], eps2, tgt_off + g.i, sv.n_src);
+  walk_f64<AccelJerkPair, kShardRowQuads, RANGE>(pr, src, src + 1, c.begin, c.end, all_masked != 0,
+                                                 RANGE ? -1 : (int)blockIdx.x, lds, g.dst<AccelJerkPair>(out),
+                                                 (size_t)n_tgt, g.n_valid(), &sv);
 }
 
 // rows [0, rows) of the send buffer: {x_p, m}, {v_p, 0} of the rank's bodies, zeros behind n. acc == nullptr: plain pack.
@@ -90,10 +87,6 @@ __global__ __launch_bounds__(256) void shard_finish_f64_kernel(const double* __r
 // groups and slabs_f64's count for its logical chunks (none, and no launch, where the rank owns every body). An explicit
 // slab count in [1, kMaxSlabs] replaces either.
 struct HShardPlanF64 { int groups, slabs_local, chunks_local, slabs_remote, chunks_remote; SrcView remote; };
-
-bool shard_args_ok(int n_total, int lo, int n_local) {
-  return n_total >= 0 && lo >= 0 && n_local >= 0 && lo <= n_total && n_local <= n_total - lo;
-}
 
 bool slab_arg_ok(int slabs) { return slabs >= 0 && slabs <= kMaxSlabs; }
 

@@ -1,7 +1,7 @@
 // direct_kernels.h -- what the direct-path translation units share (direct_force.hip: one system; direct_batch.hip: many
 // independent systems back to back; direct_diag.hip: the diagnostics of both; through hermite_kernels.h the three Hermite
 // units): the host helpers of their entry
-// points (ceil_div, misaligned16, launch_status) and the device building blocks: the pair arithmetic (interact, interact_block,
+// points (ceil_div, misaligned8 / 16 / 32, shard_args_ok, launch_status) and the device building blocks: the pair arithmetic (interact, interact_block,
 // energy_pair, potential_pair) and, one level up, the wave bodies that walk the source chunks with it (accel_body, energy_body, potential_body: target
 // loads, LDS-DMA chunk walk, pair loop, four-wave reduction, store), and the sums of the conserved quantities (invariants_body). A force or energy kernel of either unit is a
 // prologue that reads its geometry (from blockIdx and arguments, or from a scene record) and one call of the body: that
@@ -33,6 +33,13 @@ constexpr float kEps2Masked = 1e-24f;
 
 inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 inline bool misaligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; }
+inline bool misaligned32(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 31) != 0; }
+inline bool misaligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7) != 0; }
+// a rank's bodies [lo, lo + n_local) lie within the n_total of a range partition (every range-sharded entry point; no
+// sum that could overflow)
+inline bool shard_args_ok(int n_total, int lo, int n_local) {
+  return n_total >= 0 && lo >= 0 && n_local >= 0 && lo <= n_total && n_local <= n_total - lo;
+}
 // 0 or the HIP error of the last launch, as the C-ABI returns it
 inline int launch_status() {
   const hipError_t e = hipGetLastError();

@@ -36,14 +36,11 @@ namespace {
 __global__ __launch_bounds__(64 * kWaves) void accel_f64_kernel(const d4* __restrict__ posd, int n, int cpw_q, int cpw_r,
                                                                 double eps2, int all_masked, double* __restrict__ out) {
   __shared__ __attribute__((aligned(32))) f4 lds[kWaves * stage_quads<false>()];
-  const int t_base = blockIdx.x * kTgtF64;
-  const int i = t_base + (threadIdx.x & 63), row = min(i, n - 1);
-  const int jw = blockIdx.y * kWaves + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  int c_begin, c_end;
-  wave_chunk_range(jw, cpw_q, cpw_r, c_begin, c_end);
-  AccelPair pr(posd[row], eps2, i, n);
-  walk_f64(pr, posd, posd, c_begin, c_end, all_masked != 0, blockIdx.x, lds,
-           out + (size_t)blockIdx.y * AccelPair::kOut * n + t_base, (size_t)n, min(kTgtF64, n - t_base));
+  const Group64<unsigned> g(blockIdx.x, blockIdx.y, n);
+  const ChunkRange c = wave_chunks(g.jw(), cpw_q, cpw_r);
+  AccelPair pr(posd[g.row()], eps2, g.i, n);
+  walk_f64(pr, posd, posd, c.begin, c.end, all_masked != 0, blockIdx.x, lds, g.dst<AccelPair>(out), (size_t)n,
+           g.n_valid());
 }
 
 // v += c_half a ; x += dt v ; posd = {x, m} for rows [0, n_pad), zero rows behind n. acc == nullptr: a plain pack of the

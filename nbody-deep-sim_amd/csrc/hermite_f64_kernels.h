@@ -1,13 +1,17 @@
-// hermite_f64_kernels.h -- what the double-precision Hermite translation units share (direct_hermite_f64.hip: all targets,
+// hermite_f64_kernels.h -- what the double-precision translation units share (direct_hermite_f64.hip: all targets,
 // shared timestep, and the diagnostics; direct_hermite_block_f64.hip: an active list of targets, block timesteps;
-// direct_batch_hermite_f64.hip: many independent systems, shared timestep per system, and their diagnostics;
-// direct_leapfrog_f64.hip: the acceleration alone, for the leapfrog and Euler steps): the
-// packed-row type and its alignment checks, the reciprocal square root (rsqrt_f64), the pair functors (AccelJerkPair:
-// acceleration plus jerk; AccelPair: its acceleration alone; PotentialPair, EnergyPair: the diagnostics), the finishing sums of the diagnostics
-// (potential_finish_f64, energy_finish_f64, F64State), the wave body that walks the source chunks with a functor
-// (walk_f64) and the geometry of a pair launch (F64Plan, plan_f64). As in hermite_kernels.h there is one copy of every
-// rounded operation: a block step whose active list is every body, or a scene of a batch, has the shared step's bits
-// because the kernels are a prologue and a call of the same walk_f64.
+// direct_hermite_shard_f64.hip: one rank's bodies of a range partition; direct_batch_hermite_f64.hip: many independent
+// systems, shared timestep per system, and their diagnostics; direct_leapfrog_f64.hip: the acceleration alone, for the
+// leapfrog and Euler steps; direct_hermite6_f64.hip and direct_batch_hermite6_f64.hip: the 6th order, with
+// hermite6_f64_kernels.h; direct_grad.hip and direct_hermite_grad.hip: the float64 backward kernels): the reciprocal
+// square root (rsqrt_f64), the pair functors (AccelJerkPair: acceleration plus jerk; AccelPair: its acceleration alone;
+// PotentialPair, EnergyPair: the diagnostics), the finishing sums of the diagnostics (potential_finish_f64,
+// energy_finish_f64, F64State), the wave body that walks the source chunks with a functor (walk_f64), the prologue of a
+// kernel that calls it (Group64: the workgroup's targets, the wave's place in the chunk split, the slab destination;
+// wave_chunks_upper: the upper-triangle chunk range of the energies) and the geometry of a pair launch (F64Plan,
+// plan_f64). As in hermite_kernels.h there is one copy of every rounded operation and of every prologue line: a block
+// step whose active list is every body, a rank that owns every body, or a scene of a batch, has the shared step's bits
+// because the kernels are the same Group64 and a call of the same walk_f64.
 // The definitions sit in an anonymous namespace: every translation unit that includes this file gets its own inlined copies.
 #pragma once
 #include "direct_kernels.h"
@@ -21,9 +25,6 @@ constexpr int kChunkQuads = kChunk * kRowQuads;  // 128 quads = 2 KiB per chunk 
 constexpr double kEps2MaskedF64 = 1e-24;         // the fp32 kernels' rule (kEps2Masked): below it i == j goes by index
 constexpr int kTargetWGs = 1024;                 // ~4 workgroups per CU (32 KiB of LDS each: at most 5 fit)
 constexpr int kNoBody = 0x7fffffff;              // a source index that is behind every n and is no target's own
-
-inline bool misaligned32(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 31) != 0; }
-inline bool misaligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7) != 0; }
 
 // x^(-1/2) to about 1 ulp. y0 = v_rsq_f64 (a compiler builtin: hipcc pads the transcendental -> VALU wait state for its
 // consumers). With h = 1 - x y^2 formed by one fma from the rounded x y (its absolute error is 2^-53, and h is what the
@@ -351,6 +352,37 @@ __device__ __forceinline__ void walk_f64(Pair& pr, const d4* __restrict__ posd, 
     for (int w = 1; w < kWaves; ++w) sum += red[w * kPart + o];
     dst[(size_t)k * stride + t] = sum;
   }
+}
+
+// The prologue of every walk_f64 kernel: Group128 (hermite_kernels.h) with one target per lane, i (behind n it repeats
+// row n - 1 and stores nothing). One copy of these lines is what keeps a scene of a batch, or a rank that owns every
+// body, on the one-system kernel's geometry. A kernel is then: the group, the wave's chunks (wave_chunks /
+// wave_chunks_of, hermite_kernels.h, or wave_chunks_upper), the pair functor, one walk_f64.
+template <class I>
+struct Group64 {
+  I slab;
+  int n, t_base, i;
+
+  __device__ __forceinline__ Group64(I grp, I slab_, int n_)
+      : slab(slab_), n(n_), t_base(grp * kTgtF64), i(t_base + (threadIdx.x & 63)) {}
+  __device__ __forceinline__ int row() const { return min(i, n - 1); }
+  __device__ __forceinline__ int jw() const { return slab * kWaves + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6); }
+  __device__ __forceinline__ int n_valid() const { return min(kTgtF64, n - t_base); }
+  // the group's place in the slab of base = double[slabs][Pair::kOut][n]: walk_f64's dst (with stride n)
+  template <class Pair>
+  __device__ __forceinline__ double* dst(double* __restrict__ base) const {
+    return base + (size_t)slab * Pair::kOut * n + t_base;
+  }
+};
+
+// The chunks of wave jw in the upper triangle (the pair energies): group grp needs the chunks [grp, n_chunks) only, chunk
+// grp being its own rows. The balanced split of that span over slabs x 4 waves, COUNTED FROM grp: the kernel walks
+// [grp + begin, grp + end). (The sum is left to the kernel: formed here, the compiler orders the additions of grp + end
+// another way than the kernels had.) I: as in Group64.
+template <class I>
+__device__ __forceinline__ ChunkRange wave_chunks_upper(int jw, int n_chunks, I grp, I slabs) {
+  const int span = n_chunks - (int)grp, parts = slabs * kWaves;
+  return wave_chunks(jw, span / parts, span % parts);
 }
 
 // The geometry of a pair launch: groups of 64 targets, and enough slabs for ~kTargetWGs workgroups as long as every wave

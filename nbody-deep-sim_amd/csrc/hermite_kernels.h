@@ -3,8 +3,9 @@
 // systems, shared timestep per system; direct_hermite_shard.hip: one rank's bodies of a range partition):
 //   - the acceleration-plus-jerk wave body (accel_jerk_body: target loads, LDS-DMA chunk walk, pair loop, four-wave
 //     reduction, store; its compile-time parameters also give direct_hermite_shard.hip's range-sharded blocks: targets
-//     apart from the sources, 8-float rows, a skipped source range) and the split of the chunks over the waves
-//     (chunk_split on the host, wave_chunk_range in a kernel);
+//     apart from the sources, 8-float rows, a skipped source range), the split of the chunks over the waves (chunk_split
+//     on the host or from a scene record, wave_chunk_range / wave_chunks in a kernel) and the prologue of a kernel that
+//     calls the body (Group128: the workgroup's two targets per lane, the wave's place in the split, the slab destination);
 //   - the O(N) stages, templates of the scalar type T of the state (float; double for direct_hermite_f64.hip and
 //     direct_hermite_block_f64.hip): what the format fixes (HermiteFmt<T>: the packed row, the rows per workgroup of a
 //     finishing launch), the step constants (hermite_step_constants; hermite_dt for fp32), the predictor of one component
@@ -248,7 +249,7 @@ __device__ __forceinline__ void accel_jerk_body(const f4* __restrict__ spos, con
 // The balanced split of n_chunks source chunks over slabs x 4 waves: every wave walks q chunks, the first r waves one more.
 struct ChunkSplit { int q, r; };
 
-inline ChunkSplit chunk_split(int n_chunks, int slabs) {
+__host__ __device__ inline ChunkSplit chunk_split(int n_chunks, int slabs) {
   return ChunkSplit{n_chunks / (slabs * kWaves), n_chunks % (slabs * kWaves)};
 }
 
@@ -257,6 +258,45 @@ __device__ __forceinline__ void wave_chunk_range(int jw, int q, int r, int& c_be
   c_begin = jw * q + min(jw, r);
   c_end = c_begin + q + (jw < r ? 1 : 0);
 }
+
+// ... as a value: from the launch's (q, r), or with (q, r) formed from a scene's n_chunks and slabs (a batch item)
+struct ChunkRange { int begin, end; };
+
+__device__ __forceinline__ ChunkRange wave_chunks(int jw, int q, int r) {
+  ChunkRange c;
+  wave_chunk_range(jw, q, r, c.begin, c.end);
+  return c;
+}
+
+__device__ __forceinline__ ChunkRange wave_chunks_of(int jw, int n_chunks, int slabs) {
+  const int parts = slabs * kWaves;
+  return wave_chunks(jw, n_chunks / parts, n_chunks % parts);
+}
+
+// The prologue of every accel_jerk_body kernel: what workgroup (grp, slab) of n targets and its lanes work on. t_base is
+// the group's first target; i0 and i1 = i0 + 64 are the lane's two (either may lie behind n: it then repeats row n - 1
+// and stores nothing), r0() and r1() their rows; jw() is the wave's place in the split of the chunks, slab * 4 + wave;
+// n_valid() the targets of the group that exist. grp and slab come from blockIdx (one system, a rank's block:
+// I = unsigned) or from a work item (a scene of a batch, load_item of direct_batch_plan.h: I = int) and keep their type;
+// what is not a member is formed where the kernel asks for it. Both so that every kernel compiles to the instructions
+// it had with these lines written out in it.
+template <class I>
+struct Group128 {
+  I slab;
+  int n, t_base, i0, i1;
+
+  __device__ __forceinline__ Group128(I grp, I slab_, int n_)
+      : slab(slab_), n(n_), t_base(grp * kTgtPerWG), i0(t_base + (threadIdx.x & 63)), i1(i0 + 64) {}
+  __device__ __forceinline__ int jw() const { return slab * kWaves + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6); }
+  __device__ __forceinline__ int r0() const { return min(i0, n - 1); }
+  __device__ __forceinline__ int r1() const { return min(i1, n - 1); }
+  __device__ __forceinline__ int n_valid() const { return min(kTgtPerWG, n - t_base); }
+  // the group's place in the slab of base = float[slabs][P::kOut][n]: accel_jerk_body's dst (with stride n)
+  template <class P = AccelJerkPolicy>
+  __device__ __forceinline__ float* dst(float* __restrict__ base) const {
+    return base + (size_t)slab * P::kOut * n + t_base;
+  }
+};
 
 // The geometry of a force launch: the all-pairs force's plan (nbd_accel_plan) for n_tgt targets under n sources -- same
 // targets, same chunks, the same balance problem.
