@@ -164,16 +164,13 @@ def _disk_on_device(n, total_mass, radial_scale, height_scale, g_const, black_ho
     mass = torch.empty(n, dtype=torch.float64, device=dev)
     if n == 0:
         return pos, vel, mass
-    L = _lib.lib()
-    ws = torch.empty(L.nbd_disk_workspace_bytes(n), dtype=torch.uint8, device=dev)
+    ws = torch.empty(_lib.lib().nbd_disk_workspace_bytes(n), dtype=torch.uint8, device=dev)
     off = (ctypes.c_double * 3)(*[float(t) for t in offset])
     v0 = (ctypes.c_double * 3)(*[float(t) for t in initial_vel])
-    with _lib.on_device(dev):
-        _lib.check(L.nbd_disk_from_draws_f64(u_r_d.data_ptr(), u_z_d.data_ptr(), u_phi_d.data_ptr(), n, float(total_mass),
-                                             float(radial_scale), float(height_scale), float(g_const),
-                                             float(black_hole_mass), int(bool(clockwise)), rot_d.data_ptr(), off, v0,
-                                             pos.data_ptr(), vel.data_ptr(), mass.data_ptr(), ws.data_ptr(), ws.numel(),
-                                             _lib.current_stream(dev)), "nbd_disk_from_draws_f64")
+    _lib.launch("nbd_disk_from_draws_f64", dev, u_r_d.data_ptr(), u_z_d.data_ptr(), u_phi_d.data_ptr(), n,
+                float(total_mass), float(radial_scale), float(height_scale), float(g_const), float(black_hole_mass),
+                int(bool(clockwise)), rot_d.data_ptr(), off, v0, pos.data_ptr(), vel.data_ptr(), mass.data_ptr(),
+                ws.data_ptr(), ws.numel())
     return pos, vel, mass
 
 
@@ -186,11 +183,7 @@ def _spiral_on_device(n, total_mass, radial_scale, height_scale, g_const, black_
     mass = torch.empty(n, dtype=torch.float64, device=dev)
     if n == 0:
         return pos, vel, mass
-    with _lib.on_device(dev):
-        _lib.check(_lib.lib().nbd_spiral_from_draws_f64(raw.data_ptr() if n > 1 else None, n, float(total_mass),
-                                                        float(radial_scale), float(height_scale), float(g_const),
-                                                        float(black_hole_mass), int(n_arms), float(pitch_angle),
-                                                        float(arm_strength), pos.data_ptr(), vel.data_ptr(),
-                                                        mass.data_ptr(), _lib.current_stream(dev)),
-                   "nbd_spiral_from_draws_f64")
+    _lib.launch("nbd_spiral_from_draws_f64", dev, raw.data_ptr() if n > 1 else None, n, float(total_mass),
+                float(radial_scale), float(height_scale), float(g_const), float(black_hole_mass), int(n_arms),
+                float(pitch_angle), float(arm_strength), pos.data_ptr(), vel.data_ptr(), mass.data_ptr())
     return pos, vel, mass

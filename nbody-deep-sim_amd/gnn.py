@@ -509,8 +509,7 @@ class GraphModel(torch.nn.Module):
             last.adv_pos_out, last.adv_dt = pos_out.data_ptr(), float(dt)
         else:
             last.adv_vel_half = last.adv_pos = last.adv_posm = last.adv_pos_out = None
-        with _lib.on_device(dev):
-            _lib.check(_lib.lib().nbd_gnn_forward_f32(ctypes.byref(fa), _lib.current_stream(dev)), "nbd_gnn_forward_f32")
+        _lib.launch("nbd_gnn_forward_f32", dev, ctypes.byref(fa))
         self._kick_done = kick is not None
         self._advance_done = advance is not None
         self.last_path = ("one_call+tables" if fa.workspace_bytes else "one_call") + ("+pre_advance" if advance is not None else "")

@@ -529,3 +529,23 @@ def on_device(device):
     if idx is None or idx == torch.cuda.current_device():
         return _NO_GUARD
     return torch.cuda.device(device)
+
+
+def launch(name: str, device, *args, after=(), what: str | None = None) -> None:
+    """Entry `name` of the library on torch's current stream of `device`, made current for the call: name(*args, stream,
+    *after), a failure raised as check() raises it. The arguments go through as they are given. after: what an entry
+    takes behind its stream (the event handles of the leapfrog step); what: the name in the message where it is not
+    the entry's own."""
+    guard = on_device(device)
+    if guard is _NO_GUARD:                  # the usual case, without the two calls a `with` makes
+        code = getattr(lib(), name)(*args, current_stream(device), *after)
+    else:
+        with guard:
+            code = getattr(lib(), name)(*args, current_stream(device), *after)
+    if code != 0:
+        check(code, what or name)
+
+
+def call(name: str, *args) -> None:
+    """Entry `name` that takes no stream and returns a status (a plan, a size written through a pointer)."""
+    check(getattr(lib(), name)(*args), name)

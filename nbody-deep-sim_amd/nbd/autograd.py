@@ -437,8 +437,7 @@ class GnnModelFn(Function):
             raise _lib.NbdError("nbd_gnn_train_workspace_bytes: configuration rejected")
         ws = torch.empty(need, dtype=torch.uint8, device=dev)
         a.workspace, a.workspace_bytes = ws.data_ptr(), need
-        with _lib.on_device(dev):
-            _lib.check(L.nbd_gnn_train_forward_f32(ctypes.byref(a), _lib.current_stream(dev)), "nbd_gnn_train_forward_f32")
+        _lib.launch("nbd_gnn_train_forward_f32", dev, ctypes.byref(a))
         ctx.args, ctx.keep, ctx.lists = a, (x_in, ws, p, out.data_ptr()), lists      # (the output itself is not read back)
         ctx._nbd_versions = _versions([x_in, *params])
         ctx._nbd_params = [x_in, *params]
@@ -469,9 +468,7 @@ class GnnModelFn(Function):
         for i in range(a.n_head):
             g.head_w[i], g.head_b[i] = grads[k].data_ptr(), grads[k + 1].data_ptr()
             k += 2
-        with _lib.on_device(dev):
-            _lib.check(_lib.lib().nbd_gnn_train_backward_f32(ctypes.byref(a), dout.data_ptr(), dout.stride(0), ctypes.byref(g),
-                                                             _lib.current_stream(dev)), "nbd_gnn_train_backward_f32")
+        _lib.launch("nbd_gnn_train_backward_f32", dev, ctypes.byref(a), dout.data_ptr(), dout.stride(0), ctypes.byref(g))
         return (None, None, None, *grads)
 
 
@@ -545,8 +542,7 @@ class ContConvModelFn(Function):
             raise _lib.NbdError("nbd_cc_train_workspace_bytes: configuration rejected")
         ws = torch.empty(need, dtype=torch.uint8, device=dev)
         a.workspace, a.workspace_bytes = ws.data_ptr(), need
-        with _lib.on_device(dev):
-            _lib.check(L.nbd_cc_train_forward_f32(ctypes.byref(a), _lib.current_stream(dev)), "nbd_cc_train_forward_f32")
+        _lib.launch("nbd_cc_train_forward_f32", dev, ctypes.byref(a))
         ctx.args, ctx.keep, ctx.spec = a, (x, ws, p, graph, keep, scale), spec
         ctx._nbd_versions = _versions([x, *params])
         ctx._nbd_params = [x, *params]
@@ -578,9 +574,7 @@ class ContConvModelFn(Function):
         for i in range(a.n_head):
             g.head_w[i], g.head_b[i] = grads[k].data_ptr(), grads[k + 1].data_ptr()
             k += 2
-        with _lib.on_device(dev):
-            _lib.check(_lib.lib().nbd_cc_train_backward_f32(ctypes.byref(a), dout.data_ptr(), dout.stride(0), ctypes.byref(g),
-                                                            _lib.current_stream(dev)), "nbd_cc_train_backward_f32")
+        _lib.launch("nbd_cc_train_backward_f32", dev, ctypes.byref(a), dout.data_ptr(), dout.stride(0), ctypes.byref(g))
         return (None, None, None, *grads)
 
 

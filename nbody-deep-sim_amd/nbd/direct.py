@@ -2,6 +2,8 @@
 
 Every function takes torch CUDA(=HIP) tensors, checks dtype/shape/contiguity on the host (a
 wrong shape must never reach a hand-written kernel) and launches on torch's current stream.
+A float64 wrapper that repeats a float32 one is a second binding of the same private body: the
+body takes the dtype, the C entry's name and, where an error names the caller, the public name.
 """
 from __future__ import annotations
 
@@ -23,6 +25,30 @@ def _chk(t: torch.Tensor, shape, name: str, dtype=torch.float32):
         raise _lib.NbdError(f"{name}: expected shape {tuple(shape)}, got {tuple(t.shape)}")
 
 
+def _chk_n3(dtype, n: int, names, *tensors):
+    """The tensors, under the names the messages use, are all (n, 3) of `dtype`. (Positional: this runs in every eager
+    step, and a call with keywords costs a measurable part of one.)"""
+    shape = (n, 3)
+    for name, t in zip(names, tensors):
+        _chk(t, shape, name, dtype)
+
+
+def _chk_together(who: str, text: str, dtype, n: int, names, *tensors):
+    """Optional (n, 3) inputs that come together: all of them, and then checked, or none; else '`who`: give `text`'."""
+    given = [t is not None for t in tensors]
+    if any(given) != all(given):
+        raise _lib.NbdError(f"{who}: give {text}")
+    if given[0]:
+        _chk_n3(dtype, n, names, *tensors)
+
+
+def _chk_min_rows(t: torch.Tensor, rows: int, width: int, name: str, dtype=torch.float32):
+    """An array of `width`-element rows of `dtype` that holds at least `rows` of them."""
+    _chk(t, None, name, dtype)
+    if t.dim() != 2 or t.shape[1] != width or t.shape[0] < rows:
+        raise _lib.NbdError(f"{name}: need >= {rows} rows of {width}, got {tuple(t.shape)}")
+
+
 def padded_len(n: int) -> int:
     return _lib.lib().nbd_posm_padded_len(int(n))
 
@@ -34,10 +60,19 @@ def _chk_packed(dtype, pos_rows, vel_rows, n: int):
             _chk(t, (padded_len(n), 4), name, dtype)
 
 
+_PLAN3 = ("groups", "slabs", "chunks_per_wave")
+_PLAN4 = ("slabs_local", "chunks_per_wave_local", "slabs_remote", "chunks_per_wave_remote")
+
+
+def _plan(entry: str, keys, *args) -> dict:
+    """The ints a *_plan entry writes behind `args`, under `keys`."""
+    out = [ctypes.c_int() for _ in keys]
+    _lib.call(entry, *args, *out)
+    return {k: v.value for k, v in zip(keys, out)}
+
+
 def accel_plan(n_src: int, n_tgt: int) -> dict:
-    g, s, c = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
-    _lib.check(_lib.lib().nbd_accel_plan(n_src, n_tgt, g, s, c), "nbd_accel_plan")
-    return {"groups": g.value, "slabs": s.value, "chunks_per_wave": c.value}
+    return _plan("nbd_accel_plan", _PLAN3, n_src, n_tgt)
 
 
 def alloc_posm(n: int, device) -> torch.Tensor:
@@ -54,9 +89,7 @@ def pack_posm(pos: torch.Tensor, mass: torch.Tensor, out: torch.Tensor | None = 
     if out is None:
         out = alloc_posm(n, pos.device)
     _chk(out, (padded_len(n), 4), "posm")
-    with _lib.on_device(pos.device):
-        _lib.check(_lib.lib().nbd_pack_posm_f32(pos.data_ptr(), mass.data_ptr(), n, out.data_ptr(),
-                                                _lib.current_stream(pos.device)), "nbd_pack_posm_f32")
+    _lib.launch("nbd_pack_posm_f32", pos.device, pos.data_ptr(), mass.data_ptr(), n, out.data_ptr())
     return out
 
 
@@ -69,9 +102,7 @@ def accel(posm_src: torch.Tensor, n_src: int, posm_tgt: torch.Tensor, n_tgt: int
           workspace: torch.Tensor | None = None) -> torch.Tensor:
     """acc (n_tgt,3) of targets posm_tgt[:n_tgt] under sources posm_src[:n_src] (simulation.py:71-89)."""
     _chk(posm_src, (padded_len(n_src), 4), "posm_src") if n_src > 0 else None
-    _chk(posm_tgt, None, "posm_tgt")
-    if posm_tgt.dim() != 2 or posm_tgt.shape[1] != 4 or posm_tgt.shape[0] < n_tgt:
-        raise _lib.NbdError(f"posm_tgt: need >= {n_tgt} rows of 4, got {tuple(posm_tgt.shape)}")
+    _chk_min_rows(posm_tgt, n_tgt, 4, "posm_tgt")
     dev = posm_tgt.device
     if out is None:
         out = torch.empty((n_tgt, 3), dtype=torch.float32, device=dev)
@@ -79,11 +110,9 @@ def accel(posm_src: torch.Tensor, n_src: int, posm_tgt: torch.Tensor, n_tgt: int
     need = _lib.lib().nbd_accel_workspace_bytes(n_src, n_tgt)
     if workspace is None or workspace.numel() * workspace.element_size() < need:
         workspace = alloc_bytes(need, dev)
-    with _lib.on_device(dev):
-        _lib.check(_lib.lib().nbd_accel_f32(
-            posm_src.data_ptr() if n_src > 0 else None, n_src, posm_tgt.data_ptr(), n_tgt, tgt_offset,
-            float(softening_sq), float(g_const), out.data_ptr(), workspace.data_ptr(),
-            workspace.numel() * workspace.element_size(), _lib.current_stream(dev)), "nbd_accel_f32")
+    _lib.launch("nbd_accel_f32", dev, posm_src.data_ptr() if n_src > 0 else None, n_src, posm_tgt.data_ptr(), n_tgt,
+                tgt_offset, float(softening_sq), float(g_const), out.data_ptr(), workspace.data_ptr(),
+                workspace.numel() * workspace.element_size())
     return out
 
 
@@ -92,9 +121,7 @@ def accel_tuned(posm_src: torch.Tensor, n_src: int, posm_tgt: torch.Tensor, n_tg
                 out: torch.Tensor | None = None, workspace: torch.Tensor | None = None) -> torch.Tensor:
     """`accel` with an explicit launch geometry and an optional excluded source range (tuning hook)."""
     _chk(posm_src, (padded_len(n_src), 4), "posm_src")
-    _chk(posm_tgt, None, "posm_tgt")
-    if posm_tgt.dim() != 2 or posm_tgt.shape[1] != 4 or posm_tgt.shape[0] < n_tgt:
-        raise _lib.NbdError(f"posm_tgt: need >= {n_tgt} rows of 4, got {tuple(posm_tgt.shape)}")
+    _chk_min_rows(posm_tgt, n_tgt, 4, "posm_tgt")
     dev = posm_tgt.device
     if out is None:
         out = torch.empty((n_tgt, 3), dtype=torch.float32, device=dev)
@@ -102,19 +129,14 @@ def accel_tuned(posm_src: torch.Tensor, n_src: int, posm_tgt: torch.Tensor, n_tg
     need = _lib.lib().nbd_accel_tuned_workspace_bytes(n_tgt, slabs)
     if workspace is None or _nbytes(workspace) < need:
         workspace = alloc_bytes(need, dev)
-    with _lib.on_device(dev):
-        _lib.check(_lib.lib().nbd_accel_tuned_f32(
-            posm_src.data_ptr(), n_src, int(exclude[0]), int(exclude[1]), posm_tgt.data_ptr(), n_tgt, tgt_offset,
-            float(softening_sq), float(g_const), out.data_ptr(), workspace.data_ptr(), _nbytes(workspace),
-            int(slabs), int(variant), _lib.current_stream(dev)), "nbd_accel_tuned_f32")
+    _lib.launch("nbd_accel_tuned_f32", dev, posm_src.data_ptr(), n_src, int(exclude[0]), int(exclude[1]),
+                posm_tgt.data_ptr(), n_tgt, tgt_offset, float(softening_sq), float(g_const), out.data_ptr(),
+                workspace.data_ptr(), _nbytes(workspace), int(slabs), int(variant))
     return out
 
 
 def shard_plan(n_total: int, lo: int, n_local: int) -> dict:
-    a, b, c, d = ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
-    _lib.check(_lib.lib().nbd_shard_plan(n_total, lo, n_local, a, b, c, d), "nbd_shard_plan")
-    return {"slabs_local": a.value, "chunks_per_wave_local": b.value, "slabs_remote": c.value,
-            "chunks_per_wave_remote": d.value}
+    return _plan("nbd_shard_plan", _PLAN4, n_total, lo, n_local)
 
 
 def shard_workspace(n_total: int, lo: int, n_local: int, device) -> torch.Tensor:
@@ -126,11 +148,9 @@ def shard_force_local(posm_local: torch.Tensor, n_local: int, n_total: int, lo: 
     """First launch of the sharded force: own bodies as sources (runs while the all-gather is in flight).
     uniform: the bodies' common mass (uniform_mass) -> the kernel without its per-pair mass multiply."""
     _chk(posm_local, (padded_len(n_local), 4), "posm_local")
-    with _lib.on_device(posm_local.device):
-        name = "nbd_shard_force_local_f32" if uniform is None else "nbd_shard_force_local_uniform_f32"
-        _lib.check(getattr(_lib.lib(), name)(
-            posm_local.data_ptr(), n_local, float(softening_sq), workspace.data_ptr(), _nbytes(workspace),
-            n_total, lo, _lib.current_stream(posm_local.device)), name)
+    _lib.launch("nbd_shard_force_local_f32" if uniform is None else "nbd_shard_force_local_uniform_f32",
+                posm_local.device, posm_local.data_ptr(), n_local, float(softening_sq), workspace.data_ptr(),
+                _nbytes(workspace), n_total, lo)
 
 
 def shard_force_remote(posm_all: torch.Tensor, n_total: int, posm_local: torch.Tensor, n_local: int, lo: int,
@@ -142,17 +162,12 @@ def shard_force_remote(posm_all: torch.Tensor, n_total: int, posm_local: torch.T
     _chk(acc_out, (n_local, 3), "acc_out")
     if vel is not None:
         _chk(vel, (n_local, 3), "vel")
-    with _lib.on_device(posm_all.device):
-        if uniform is not None:
-            _lib.check(_lib.lib().nbd_shard_force_remote_uniform_f32(
-                posm_all.data_ptr(), n_total, posm_local.data_ptr(), n_local, lo, float(softening_sq),
-                float(g_const), float(uniform), acc_out.data_ptr(), _lib.ptr(vel), float(c_kick), workspace.data_ptr(),
-                _nbytes(workspace), _lib.current_stream(posm_all.device)), "nbd_shard_force_remote_uniform_f32")
-            return
-        _lib.check(_lib.lib().nbd_shard_force_remote_f32(
-            posm_all.data_ptr(), n_total, posm_local.data_ptr(), n_local, lo, float(softening_sq),
-            float(g_const), acc_out.data_ptr(), _lib.ptr(vel), float(c_kick), workspace.data_ptr(),
-            _nbytes(workspace), _lib.current_stream(posm_all.device)), "nbd_shard_force_remote_f32")
+    head = (posm_all.data_ptr(), n_total, posm_local.data_ptr(), n_local, lo, float(softening_sq), float(g_const))
+    tail = (acc_out.data_ptr(), _lib.ptr(vel), float(c_kick), workspace.data_ptr(), _nbytes(workspace))
+    if uniform is not None:
+        _lib.launch("nbd_shard_force_remote_uniform_f32", posm_all.device, *head, float(uniform), *tail)
+        return
+    _lib.launch("nbd_shard_force_remote_f32", posm_all.device, *head, *tail)
 
 
 def f32(x: float) -> float:
@@ -187,46 +202,37 @@ def kick_drift(pos, vel, acc, mass, c_kick: float, c_drift: float, posm=None) ->
         _chk(mass, (n,), "mass")
         if posm.dtype != torch.float32 or not posm.is_contiguous() or posm.shape[0] < padded_len(n):
             raise _lib.NbdError("posm: need contiguous fp32 (>= padded_len(n), 4)")
-    with _lib.on_device(pos.device):
-        _lib.check(_lib.lib().nbd_kick_drift_f32(pos.data_ptr(), vel.data_ptr(), _lib.ptr(acc),
-                                                 _lib.ptr(mass), n, c_kick, c_drift, _lib.ptr(posm),
-                                                 _lib.current_stream(pos.device)), "nbd_kick_drift_f32")
+    _lib.launch("nbd_kick_drift_f32", pos.device, pos.data_ptr(), vel.data_ptr(), _lib.ptr(acc), _lib.ptr(mass), n,
+                c_kick, c_drift, _lib.ptr(posm))
 
 
 def kick(vel, acc, c: float) -> None:
     n = vel.shape[0]
     _chk(vel, (n, 3), "vel"); _chk(acc, (n, 3), "acc")
-    with _lib.on_device(vel.device):
-        _lib.check(_lib.lib().nbd_kick_f32(vel.data_ptr(), acc.data_ptr(), n, c,
-                                           _lib.current_stream(vel.device)), "nbd_kick_f32")
+    _lib.launch("nbd_kick_f32", vel.device, vel.data_ptr(), acc.data_ptr(), n, c)
 
 
 def drift(pos, vel, c: float) -> None:
     n = pos.shape[0]
     _chk(pos, (n, 3), "pos"); _chk(vel, (n, 3), "vel")
-    with _lib.on_device(pos.device):
-        _lib.check(_lib.lib().nbd_drift_f32(pos.data_ptr(), vel.data_ptr(), n, c,
-                                            _lib.current_stream(pos.device)), "nbd_drift_f32")
+    _lib.launch("nbd_drift_f32", pos.device, pos.data_ptr(), vel.data_ptr(), n, c)
+
+
+def _snapshot(dtype, entry: str, pos, vel, acc, out) -> None:
+    n = pos.shape[0]
+    _chk_n3(dtype, n, ("pos", "vel", "acc"), pos, vel, acc)
+    _chk(out, (3, n, 3), "out", dtype)
+    _lib.launch(entry, pos.device, pos.data_ptr(), vel.data_ptr(), acc.data_ptr(), n, out.data_ptr())
 
 
 def snapshot(pos, vel, acc, out) -> None:
     """out (3, n, 3) = [pos, vel, acc]: one launch (a slot of run()'s device ring)."""
-    n = pos.shape[0]
-    _chk(pos, (n, 3), "pos"); _chk(vel, (n, 3), "vel"); _chk(acc, (n, 3), "acc"); _chk(out, (3, n, 3), "out")
-    with _lib.on_device(pos.device):
-        _lib.check(_lib.lib().nbd_snapshot_f32(pos.data_ptr(), vel.data_ptr(), acc.data_ptr(), n, out.data_ptr(),
-                                               _lib.current_stream(pos.device)), "nbd_snapshot_f32")
+    _snapshot(torch.float32, "nbd_snapshot_f32", pos, vel, acc, out)
 
 
 def snapshot_f64(pos, vel, acc, out) -> None:
     """snapshot of a float64 state: out (3, n, 3) float64 = [pos, vel, acc], one launch."""
-    n = pos.shape[0]
-    for t, nm in ((pos, "pos"), (vel, "vel"), (acc, "acc")):
-        _chk(t, (n, 3), nm, torch.float64)
-    _chk(out, (3, n, 3), "out", torch.float64)
-    with _lib.on_device(pos.device):
-        _lib.check(_lib.lib().nbd_snapshot_f64(pos.data_ptr(), vel.data_ptr(), acc.data_ptr(), n, out.data_ptr(),
-                                               _lib.current_stream(pos.device)), "nbd_snapshot_f64")
+    _snapshot(F64, "nbd_snapshot_f64", pos, vel, acc, out)
 
 
 def uniform_mass(mass: torch.Tensor):
@@ -245,53 +251,46 @@ def leapfrog_step(pos, vel, acc_in, acc_out, mass, dt_half: float, dt: float, so
     handle exists) recorded around the force kernel -- bench.py's roofline hook. uniform: the bodies' common mass
     (uniform_mass(mass)) -> the force kernel without its per-pair mass multiply (nbd_leapfrog_step_uniform_f32)."""
     n = pos.shape[0]
-    for t, nm in ((pos, "pos"), (vel, "vel"), (acc_in, "acc_in"), (acc_out, "acc_out")):
-        _chk(t, (n, 3), nm)
+    _chk_n3(torch.float32, n, ("pos", "vel", "acc_in", "acc_out"), pos, vel, acc_in, acc_out)
     _chk(mass, (n,), "mass"); _chk(posm, (padded_len(n), 4), "posm")
-    with _lib.on_device(pos.device):
-        if uniform is not None:
-            _lib.check(_lib.lib().nbd_leapfrog_step_uniform_f32(
-                pos.data_ptr(), vel.data_ptr(), acc_in.data_ptr(), acc_out.data_ptr(), mass.data_ptr(), float(uniform), n,
-                dt_half, dt, softening_sq, g_const, posm.data_ptr(), workspace.data_ptr(), _nbytes(workspace),
-                _lib.current_stream(pos.device),
-                None if ev_begin is None else ev_begin.cuda_event,
-                None if ev_end is None else ev_end.cuda_event), "nbd_leapfrog_step_uniform_f32")
-            return
-        _lib.check(_lib.lib().nbd_leapfrog_step_ev_f32(
-            pos.data_ptr(), vel.data_ptr(), acc_in.data_ptr(), acc_out.data_ptr(), mass.data_ptr(), n,
-            dt_half, dt, softening_sq, g_const, posm.data_ptr(), workspace.data_ptr(), _nbytes(workspace),
-            _lib.current_stream(pos.device),
-            None if ev_begin is None else ev_begin.cuda_event,
-            None if ev_end is None else ev_end.cuda_event), "nbd_leapfrog_step_f32")
+    events = (None if ev_begin is None else ev_begin.cuda_event, None if ev_end is None else ev_end.cuda_event)
+    if uniform is not None:
+        _lib.launch("nbd_leapfrog_step_uniform_f32", pos.device, pos.data_ptr(), vel.data_ptr(), acc_in.data_ptr(),
+                    acc_out.data_ptr(), mass.data_ptr(), float(uniform), n, dt_half, dt, softening_sq, g_const,
+                    posm.data_ptr(), workspace.data_ptr(), _nbytes(workspace), after=events)
+        return
+    # the failure has always been reported under the name of the entry without events; callers may match on that text
+    _lib.launch("nbd_leapfrog_step_ev_f32", pos.device, pos.data_ptr(), vel.data_ptr(), acc_in.data_ptr(),
+                acc_out.data_ptr(), mass.data_ptr(), n, dt_half, dt, softening_sq, g_const, posm.data_ptr(),
+                workspace.data_ptr(), _nbytes(workspace), after=events, what="nbd_leapfrog_step_f32")
 
 
 def euler_step(pos, vel, acc_out, mass, dt: float, softening_sq: float, g_const: float, posm,
                workspace) -> None:
     n = pos.shape[0]
-    for t, nm in ((pos, "pos"), (vel, "vel"), (acc_out, "acc_out")):
-        _chk(t, (n, 3), nm)
+    _chk_n3(torch.float32, n, ("pos", "vel", "acc_out"), pos, vel, acc_out)
     _chk(mass, (n,), "mass"); _chk(posm, (padded_len(n), 4), "posm")
-    with _lib.on_device(pos.device):
-        _lib.check(_lib.lib().nbd_euler_step_f32(
-            pos.data_ptr(), vel.data_ptr(), acc_out.data_ptr(), mass.data_ptr(), n, dt, softening_sq,
-            g_const, posm.data_ptr(), workspace.data_ptr(), _nbytes(workspace),
-            _lib.current_stream(pos.device)), "nbd_euler_step_f32")
+    _lib.launch("nbd_euler_step_f32", pos.device, pos.data_ptr(), vel.data_ptr(), acc_out.data_ptr(), mass.data_ptr(),
+                n, dt, softening_sq, g_const, posm.data_ptr(), workspace.data_ptr(), _nbytes(workspace))
+
+
+def _energy_out(dtype, rows, vel, n: int, out_uk):
+    """The checks energy and energy_f64 share; out_uk, new when None."""
+    _chk_packed(dtype, rows, None, n); _chk(vel, (n, 3), "vel", dtype)
+    if out_uk is None:
+        out_uk = torch.empty(2, dtype=torch.float64, device=vel.device)
+    _chk(out_uk, (2,), "out_uk", torch.float64)
+    return out_uk
 
 
 def energy(posm, vel, n: int, softening: float, g_const: float, out_uk=None, workspace=None):
     """Device double[2] = {U, K} (simulation.py:91-115); asynchronous."""
-    _chk(posm, (padded_len(n), 4), "posm"); _chk(vel, (n, 3), "vel")
-    dev = vel.device
-    if out_uk is None:
-        out_uk = torch.empty(2, dtype=torch.float64, device=dev)
-    _chk(out_uk, (2,), "out_uk", torch.float64)
+    out_uk = _energy_out(torch.float32, posm, vel, n, out_uk)
     need = _lib.lib().nbd_energy_workspace_bytes(n)
     if workspace is None or _nbytes(workspace) < need:
-        workspace = alloc_bytes(need, dev)
-    with _lib.on_device(dev):
-        _lib.check(_lib.lib().nbd_energy_f32(posm.data_ptr(), vel.data_ptr(), n, softening, g_const,
-                                             out_uk.data_ptr(), workspace.data_ptr(), _nbytes(workspace),
-                                             _lib.current_stream(dev)), "nbd_energy_f32")
+        workspace = alloc_bytes(need, vel.device)
+    _lib.launch("nbd_energy_f32", vel.device, posm.data_ptr(), vel.data_ptr(), n, softening, g_const,
+                out_uk.data_ptr(), workspace.data_ptr(), _nbytes(workspace))
     return out_uk
 
 
@@ -310,9 +309,7 @@ def potential(posm_src: torch.Tensor, n_src: int, posm_tgt: torch.Tensor, n_tgt:
     phi_i = -G sum_{j != i} m_j (|r_ij|^2 + eps^2)^(-1/2), the potential the force of `accel` derives from (j == tgt_offset
     + i excluded by index). Asynchronous, deterministic."""
     _chk(posm_src, (padded_len(n_src), 4), "posm_src") if n_src > 0 else None
-    _chk(posm_tgt, None, "posm_tgt")
-    if posm_tgt.dim() != 2 or posm_tgt.shape[1] != 4 or posm_tgt.shape[0] < n_tgt:
-        raise _lib.NbdError(f"posm_tgt: need >= {n_tgt} rows of 4, got {tuple(posm_tgt.shape)}")
+    _chk_min_rows(posm_tgt, n_tgt, 4, "posm_tgt")
     dev = posm_tgt.device
     if out is None:
         out = torch.empty((n_tgt,), dtype=torch.float64, device=dev)
@@ -320,11 +317,9 @@ def potential(posm_src: torch.Tensor, n_src: int, posm_tgt: torch.Tensor, n_tgt:
     need = _lib.lib().nbd_potential_workspace_bytes(n_src, n_tgt)
     if workspace is None or _nbytes(workspace) < need:
         workspace = alloc_bytes(need, dev)
-    with _lib.on_device(dev):
-        _lib.check(_lib.lib().nbd_potential_f32(
-            posm_src.data_ptr() if n_src > 0 else None, n_src, posm_tgt.data_ptr(), n_tgt, int(tgt_offset),
-            float(softening_sq), float(g_const), out.data_ptr(), workspace.data_ptr(), _nbytes(workspace),
-            _lib.current_stream(dev)), "nbd_potential_f32")
+    _lib.launch("nbd_potential_f32", dev, posm_src.data_ptr() if n_src > 0 else None, n_src, posm_tgt.data_ptr(), n_tgt,
+                int(tgt_offset), float(softening_sq), float(g_const), out.data_ptr(), workspace.data_ptr(),
+                _nbytes(workspace))
     return out
 
 
@@ -336,9 +331,7 @@ def invariants(posm, vel, phi, n: int, out: torch.Tensor | None = None) -> torch
     if out is None:
         out = torch.empty(INVARIANT_ROW, dtype=torch.float64, device=dev)
     _chk(out, (INVARIANT_ROW,), "out_row", torch.float64)
-    with _lib.on_device(dev):
-        _lib.check(_lib.lib().nbd_invariants_f64(posm.data_ptr(), vel.data_ptr(), phi.data_ptr(), n, out.data_ptr(),
-                                                 _lib.current_stream(dev)), "nbd_invariants_f64")
+    _lib.launch("nbd_invariants_f64", dev, posm.data_ptr(), vel.data_ptr(), phi.data_ptr(), n, out.data_ptr())
     return out
 
 
@@ -347,20 +340,19 @@ def hermite_workspace(n: int, device) -> torch.Tensor:
     return alloc_bytes(_lib.lib().nbd_hermite_workspace_bytes(int(n)), device)
 
 
+def _hermite_pack(dtype, entry: str, who: str, pos, vel, mass, rows, vrows, acc, jerk, dt) -> None:
+    n = pos.shape[0]
+    _chk_n3(dtype, n, ("pos", "vel"), pos, vel); _chk(mass, (n,), "mass", dtype)
+    _chk_packed(dtype, rows, vrows, n)
+    _chk_together(who, "both acc and jerk, or neither", dtype, n, ("acc", "jerk"), acc, jerk)
+    _lib.launch(entry, pos.device, pos.data_ptr(), vel.data_ptr(), _lib.ptr(acc), _lib.ptr(jerk), mass.data_ptr(), n,
+                float(dt), rows.data_ptr(), vrows.data_ptr())
+
+
 def hermite_pack(pos, vel, mass, posm, velp, acc=None, jerk=None, dt: float = 0.0) -> None:
     """posm = {x_p, m}, velp = {v_p, 0} (padded_len(n) rows each): the predicted state after dt from (acc, jerk), or a
     plain pack of (pos, vel) when both are None."""
-    n = pos.shape[0]
-    _chk(pos, (n, 3), "pos"); _chk(vel, (n, 3), "vel"); _chk(mass, (n,), "mass")
-    _chk_packed(torch.float32, posm, velp, n)
-    if (acc is None) != (jerk is None):
-        raise _lib.NbdError("hermite_pack: give both acc and jerk, or neither")
-    if acc is not None:
-        _chk(acc, (n, 3), "acc"); _chk(jerk, (n, 3), "jerk")
-    with _lib.on_device(pos.device):
-        _lib.check(_lib.lib().nbd_hermite_pack_f32(
-            pos.data_ptr(), vel.data_ptr(), _lib.ptr(acc), _lib.ptr(jerk), mass.data_ptr(), n, float(dt),
-            posm.data_ptr(), velp.data_ptr(), _lib.current_stream(pos.device)), "nbd_hermite_pack_f32")
+    _hermite_pack(torch.float32, "nbd_hermite_pack_f32", "hermite_pack", pos, vel, mass, posm, velp, acc, jerk, dt)
 
 
 def accel_jerk(posm, velp, n: int, softening_sq: float, g_const: float, acc_out=None, jerk_out=None, workspace=None,
@@ -373,32 +365,34 @@ def accel_jerk(posm, velp, n: int, softening_sq: float, g_const: float, acc_out=
         acc_out = torch.empty((n, 3), dtype=torch.float32, device=dev)
     if jerk_out is None:
         jerk_out = torch.empty((n, 3), dtype=torch.float32, device=dev)
-    _chk(acc_out, (n, 3), "acc_out"); _chk(jerk_out, (n, 3), "jerk_out")
+    _chk_n3(torch.float32, n, ("acc_out", "jerk_out"), acc_out, jerk_out)
     need = _lib.lib().nbd_hermite_workspace_bytes(n)
     if workspace is None or _nbytes(workspace) < need:
         workspace = alloc_bytes(need, dev)
-    with _lib.on_device(dev):
-        _lib.check(_lib.lib().nbd_accel_jerk_f32(
-            posm.data_ptr(), velp.data_ptr(), n, float(softening_sq), float(g_const), acc_out.data_ptr(),
-            jerk_out.data_ptr(), workspace.data_ptr(), _nbytes(workspace), int(variant), _lib.current_stream(dev)),
-            "nbd_accel_jerk_f32")
+    _lib.launch("nbd_accel_jerk_f32", dev, posm.data_ptr(), velp.data_ptr(), n, float(softening_sq), float(g_const),
+                acc_out.data_ptr(), jerk_out.data_ptr(), workspace.data_ptr(), _nbytes(workspace), int(variant))
     return acc_out, jerk_out
+
+
+def _hermite_step(dtype, entry: str, pos, vel, acc_in, jerk_in, acc_out, jerk_out, mass, dt, softening_sq, g_const,
+                  rows, vrows, workspace) -> None:
+    """vrows: the packed velocities where the entry takes them as scratch (float64), else None."""
+    n = pos.shape[0]
+    _chk_n3(dtype, n, ("pos", "vel", "acc_in", "jerk_in", "acc_out", "jerk_out"), pos, vel, acc_in, jerk_in, acc_out,
+            jerk_out)
+    _chk(mass, (n,), "mass", dtype); _chk_packed(dtype, rows, vrows, n)
+    _lib.launch(entry, pos.device, pos.data_ptr(), vel.data_ptr(), acc_in.data_ptr(), jerk_in.data_ptr(),
+                acc_out.data_ptr(), jerk_out.data_ptr(), mass.data_ptr(), n, float(dt), float(softening_sq),
+                float(g_const), *(t.data_ptr() for t in (rows, vrows) if t is not None), workspace.data_ptr(),
+                _nbytes(workspace))
 
 
 def hermite_step(pos, vel, acc_in, jerk_in, acc_out, jerk_out, mass, dt: float, softening_sq: float, g_const: float,
                  posm, workspace) -> None:
     """One predictor-corrector step (three launches): pos, vel in place; acc_out, jerk_out = a, j at the predicted state
     (may be acc_in, jerk_in); posm = {x1, m}. dt is the Python double: the fp32 step constants are formed from it."""
-    n = pos.shape[0]
-    for t, nm in ((pos, "pos"), (vel, "vel"), (acc_in, "acc_in"), (jerk_in, "jerk_in"), (acc_out, "acc_out"),
-                  (jerk_out, "jerk_out")):
-        _chk(t, (n, 3), nm)
-    _chk(mass, (n,), "mass"); _chk_packed(torch.float32, posm, None, n)
-    with _lib.on_device(pos.device):
-        _lib.check(_lib.lib().nbd_hermite_step_f32(
-            pos.data_ptr(), vel.data_ptr(), acc_in.data_ptr(), jerk_in.data_ptr(), acc_out.data_ptr(),
-            jerk_out.data_ptr(), mass.data_ptr(), n, float(dt), float(softening_sq), float(g_const), posm.data_ptr(),
-            workspace.data_ptr(), _nbytes(workspace), _lib.current_stream(pos.device)), "nbd_hermite_step_f32")
+    _hermite_step(torch.float32, "nbd_hermite_step_f32", pos, vel, acc_in, jerk_in, acc_out, jerk_out, mass, dt,
+                  softening_sq, g_const, posm, None, workspace)
 
 
 # ------------------------------------------------------ range-sharded Hermite step (csrc/direct_hermite_shard.hip)
@@ -411,10 +405,7 @@ def alloc_hermite_rows(n: int, device) -> torch.Tensor:
 
 
 def hermite_shard_plan(n_total: int, lo: int, n_local: int) -> dict:
-    a, b, c, d = ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
-    _lib.check(_lib.lib().nbd_hermite_shard_plan(n_total, lo, n_local, a, b, c, d), "nbd_hermite_shard_plan")
-    return {"slabs_local": a.value, "chunks_per_wave_local": b.value, "slabs_remote": c.value,
-            "chunks_per_wave_remote": d.value}
+    return _plan("nbd_hermite_shard_plan", _PLAN4, n_total, lo, n_local)
 
 
 def hermite_shard_workspace(n_total: int, lo: int, n_local: int, device) -> torch.Tensor:
@@ -428,31 +419,46 @@ def _chk_rows(t: torch.Tensor, n: int, name: str, dtype=torch.float32):
         raise _lib.NbdError(f"{name}: need >= {padded_len(n)} rows of {HERMITE_ROW}, got {tuple(t.shape)}")
 
 
+def _hermite_shard_predict(dtype, entry: str, who: str, pos, vel, mass, send, acc, jerk, dt) -> None:
+    n = pos.shape[0]
+    _chk_n3(dtype, n, ("pos", "vel"), pos, vel); _chk(mass, (n,), "mass", dtype)
+    _chk_rows(send, n, "send", dtype)
+    _chk_together(who, "both acc and jerk, or neither", dtype, n, ("acc", "jerk"), acc, jerk)
+    _lib.launch(entry, send.device, pos.data_ptr(), vel.data_ptr(), _lib.ptr(acc), _lib.ptr(jerk), mass.data_ptr(), n,
+                float(dt), send.data_ptr(), send.shape[0])
+
+
+def _hermite_shard_force_local(dtype, entry: str, send, n_local, n_total, lo, softening_sq, workspace, *slabs) -> None:
+    _chk_rows(send, n_local, "send", dtype)
+    _lib.launch(entry, send.device, send.data_ptr(), n_local, float(softening_sq), workspace.data_ptr(),
+                _nbytes(workspace), n_total, lo, *map(int, slabs))
+
+
+def _hermite_shard_force_remote(dtype, entry: str, who: str, rows_all, n_total, send, n_local, lo, softening_sq, g_const,
+                                acc_out, jerk_out, workspace, pos, vel, acc_in, jerk_in, dt, *slabs) -> None:
+    _chk_rows(rows_all, n_total, "rows_all", dtype)
+    _chk_rows(send, n_local, "send", dtype)
+    _chk_n3(dtype, n_local, ("acc_out", "jerk_out"), acc_out, jerk_out)
+    _chk_together(who, "pos, vel, acc_in and jerk_in, or none of them", dtype, n_local,
+                  ("pos", "vel", "acc_in", "jerk_in"), pos, vel, acc_in, jerk_in)
+    _lib.launch(entry, rows_all.device, rows_all.data_ptr(), n_total, send.data_ptr(), n_local, lo, float(softening_sq),
+                float(g_const), _lib.ptr(pos), _lib.ptr(vel), _lib.ptr(acc_in), _lib.ptr(jerk_in), acc_out.data_ptr(),
+                jerk_out.data_ptr(), float(dt), workspace.data_ptr(), _nbytes(workspace), *map(int, slabs))
+
+
 def hermite_shard_predict(pos, vel, mass, send, acc=None, jerk=None, dt: float = 0.0) -> None:
     """First launch of the sharded Hermite step: send[:n_local] = {x_p, m, v_p, 0} of the rank's bodies predicted over dt
     from (acc, jerk) -- a plain pack of (pos, vel) when both are None -- and zeros in every row behind n_local."""
-    n = pos.shape[0]
-    _chk(pos, (n, 3), "pos"); _chk(vel, (n, 3), "vel"); _chk(mass, (n,), "mass")
-    _chk_rows(send, n, "send")
-    if (acc is None) != (jerk is None):
-        raise _lib.NbdError("hermite_shard_predict: give both acc and jerk, or neither")
-    if acc is not None:
-        _chk(acc, (n, 3), "acc"); _chk(jerk, (n, 3), "jerk")
-    with _lib.on_device(send.device):
-        _lib.check(_lib.lib().nbd_hermite_shard_predict_f32(
-            pos.data_ptr(), vel.data_ptr(), _lib.ptr(acc), _lib.ptr(jerk), mass.data_ptr(), n, float(dt),
-            send.data_ptr(), send.shape[0], _lib.current_stream(send.device)), "nbd_hermite_shard_predict_f32")
+    _hermite_shard_predict(torch.float32, "nbd_hermite_shard_predict_f32", "hermite_shard_predict", pos, vel, mass, send,
+                           acc, jerk, dt)
 
 
 def hermite_shard_force_local(send: torch.Tensor, n_local: int, n_total: int, lo: int, softening_sq: float,
                               workspace: torch.Tensor) -> None:
     """Second launch: acceleration + jerk partial sums of the own bodies under the own bodies (reads `send` only, so it
     runs while the all-gather is in flight)."""
-    _chk_rows(send, n_local, "send")
-    with _lib.on_device(send.device):
-        _lib.check(_lib.lib().nbd_hermite_shard_force_local_f32(
-            send.data_ptr(), n_local, float(softening_sq), workspace.data_ptr(), _nbytes(workspace), n_total, lo,
-            _lib.current_stream(send.device)), "nbd_hermite_shard_force_local_f32")
+    _hermite_shard_force_local(torch.float32, "nbd_hermite_shard_force_local_f32", send, n_local, n_total, lo,
+                               softening_sq, workspace)
 
 
 def hermite_shard_force_remote(rows_all: torch.Tensor, n_total: int, send: torch.Tensor, n_local: int, lo: int,
@@ -462,21 +468,9 @@ def hermite_shard_force_remote(rows_all: torch.Tensor, n_total: int, send: torch
     """Third and fourth launch: every other body of the gathered rows as a source, then a1, j1 = G * sum(slabs) into
     acc_out, jerk_out. With pos, vel, acc_in, jerk_in and dt also the corrector of the own rows (pos, vel in place;
     acc_out may be acc_in and jerk_out jerk_in); with none of them the force on its own."""
-    _chk_rows(rows_all, n_total, "rows_all")
-    _chk_rows(send, n_local, "send")
-    _chk(acc_out, (n_local, 3), "acc_out"); _chk(jerk_out, (n_local, 3), "jerk_out")
-    step = (pos, vel, acc_in, jerk_in)
-    if any(t is None for t in step) != all(t is None for t in step):
-        raise _lib.NbdError("hermite_shard_force_remote: give pos, vel, acc_in and jerk_in, or none of them")
-    if pos is not None:
-        for t, nm in zip(step, ("pos", "vel", "acc_in", "jerk_in")):
-            _chk(t, (n_local, 3), nm)
-    with _lib.on_device(rows_all.device):
-        _lib.check(_lib.lib().nbd_hermite_shard_force_remote_f32(
-            rows_all.data_ptr(), n_total, send.data_ptr(), n_local, lo, float(softening_sq), float(g_const),
-            _lib.ptr(pos), _lib.ptr(vel), _lib.ptr(acc_in), _lib.ptr(jerk_in), acc_out.data_ptr(), jerk_out.data_ptr(),
-            float(dt), workspace.data_ptr(), _nbytes(workspace), _lib.current_stream(rows_all.device)),
-            "nbd_hermite_shard_force_remote_f32")
+    _hermite_shard_force_remote(torch.float32, "nbd_hermite_shard_force_remote_f32", "hermite_shard_force_remote",
+                                rows_all, n_total, send, n_local, lo, softening_sq, g_const, acc_out, jerk_out, workspace,
+                                pos, vel, acc_in, jerk_in, dt)
 
 
 # ---------------------------------------------------------- double-precision Hermite (csrc/direct_hermite_f64.hip)
@@ -489,9 +483,7 @@ def alloc_rows_f64(n: int, device) -> torch.Tensor:
 
 
 def hermite_f64_plan(n: int) -> dict:
-    g, s, c = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
-    _lib.check(_lib.lib().nbd_hermite_f64_plan(int(n), g, s, c), "nbd_hermite_f64_plan")
-    return {"groups": g.value, "slabs": s.value, "chunks_per_wave": c.value}
+    return _plan("nbd_hermite_f64_plan", _PLAN3, int(n))
 
 
 def hermite_f64_workspace(n: int, device, slabs: int = 0) -> torch.Tensor:
@@ -500,21 +492,9 @@ def hermite_f64_workspace(n: int, device, slabs: int = 0) -> torch.Tensor:
     return alloc_bytes(max(need, int(slabs) * 6 * int(n) * 8), device)
 
 
-
-
 def hermite_f64_pack(pos, vel, mass, posd, veld, acc=None, jerk=None, dt: float = 0.0) -> None:
     """hermite_pack in float64: posd = {x_p, m}, veld = {v_p, 0}, predicted over dt from (acc, jerk) or a plain pack."""
-    n = pos.shape[0]
-    _chk(pos, (n, 3), "pos", F64); _chk(vel, (n, 3), "vel", F64); _chk(mass, (n,), "mass", F64)
-    _chk_packed(F64, posd, veld, n)
-    if (acc is None) != (jerk is None):
-        raise _lib.NbdError("hermite_f64_pack: give both acc and jerk, or neither")
-    if acc is not None:
-        _chk(acc, (n, 3), "acc", F64); _chk(jerk, (n, 3), "jerk", F64)
-    with _lib.on_device(pos.device):
-        _lib.check(_lib.lib().nbd_hermite_f64_pack(
-            pos.data_ptr(), vel.data_ptr(), _lib.ptr(acc), _lib.ptr(jerk), mass.data_ptr(), n, float(dt),
-            posd.data_ptr(), veld.data_ptr(), _lib.current_stream(pos.device)), "nbd_hermite_f64_pack")
+    _hermite_pack(F64, "nbd_hermite_f64_pack", "hermite_f64_pack", pos, vel, mass, posd, veld, acc, jerk, dt)
 
 
 def accel_jerk_f64(posd, veld, n: int, softening_sq: float, g_const: float, workspace=None, slabs: int = 0):
@@ -525,11 +505,8 @@ def accel_jerk_f64(posd, veld, n: int, softening_sq: float, g_const: float, work
     jerk_out = torch.empty((n, 3), dtype=F64, device=dev)
     if workspace is None:                       # a given workspace is checked by the entry, against what this call uses
         workspace = hermite_f64_workspace(n, dev, slabs)
-    with _lib.on_device(dev):
-        _lib.check(_lib.lib().nbd_accel_jerk_f64(
-            posd.data_ptr(), veld.data_ptr(), n, float(softening_sq), float(g_const), acc_out.data_ptr(),
-            jerk_out.data_ptr(), workspace.data_ptr(), _nbytes(workspace), int(slabs), _lib.current_stream(dev)),
-            "nbd_accel_jerk_f64")
+    _lib.launch("nbd_accel_jerk_f64", dev, posd.data_ptr(), veld.data_ptr(), n, float(softening_sq), float(g_const),
+                acc_out.data_ptr(), jerk_out.data_ptr(), workspace.data_ptr(), _nbytes(workspace), int(slabs))
     return acc_out, jerk_out
 
 
@@ -537,30 +514,15 @@ def hermite_step_f64(pos, vel, acc_in, jerk_in, acc_out, jerk_out, mass, dt: flo
                      g_const: float, posd, veld, workspace) -> None:
     """hermite_step in float64 (three launches): pos, vel in place; acc_out, jerk_out may be acc_in, jerk_in;
     posd = {x1, m}; veld is scratch. dt, softening_sq and g_const go in as the Python doubles."""
-    n = pos.shape[0]
-    for t, nm in ((pos, "pos"), (vel, "vel"), (acc_in, "acc_in"), (jerk_in, "jerk_in"), (acc_out, "acc_out"),
-                  (jerk_out, "jerk_out")):
-        _chk(t, (n, 3), nm, F64)
-    _chk(mass, (n,), "mass", F64)
-    _chk_packed(F64, posd, veld, n)
-    with _lib.on_device(pos.device):
-        _lib.check(_lib.lib().nbd_hermite_step_f64(
-            pos.data_ptr(), vel.data_ptr(), acc_in.data_ptr(), jerk_in.data_ptr(), acc_out.data_ptr(),
-            jerk_out.data_ptr(), mass.data_ptr(), n, float(dt), float(softening_sq), float(g_const), posd.data_ptr(),
-            veld.data_ptr(), workspace.data_ptr(), _nbytes(workspace), _lib.current_stream(pos.device)),
-            "nbd_hermite_step_f64")
+    _hermite_step(F64, "nbd_hermite_step_f64", pos, vel, acc_in, jerk_in, acc_out, jerk_out, mass, dt, softening_sq,
+                  g_const, posd, veld, workspace)
 
 
 def energy_f64(posd, vel, n: int, softening: float, g_const: float, workspace, out_uk=None):
     """Device double[2] = {U, K} in the reference's convention from a float64 state; asynchronous."""
-    _chk_packed(F64, posd, None, n); _chk(vel, (n, 3), "vel", F64)
-    if out_uk is None:
-        out_uk = torch.empty(2, dtype=F64, device=vel.device)
-    _chk(out_uk, (2,), "out_uk", F64)
-    with _lib.on_device(vel.device):
-        _lib.check(_lib.lib().nbd_energy_f64(posd.data_ptr(), vel.data_ptr(), n, float(softening), float(g_const),
-                                             out_uk.data_ptr(), workspace.data_ptr(), _nbytes(workspace),
-                                             _lib.current_stream(vel.device)), "nbd_energy_f64")
+    out_uk = _energy_out(F64, posd, vel, n, out_uk)
+    _lib.launch("nbd_energy_f64", vel.device, posd.data_ptr(), vel.data_ptr(), n, float(softening), float(g_const),
+                out_uk.data_ptr(), workspace.data_ptr(), _nbytes(workspace))
     return out_uk
 
 
@@ -570,25 +532,21 @@ def potential_f64(posd, n: int, softening_sq: float, g_const: float, workspace, 
     if out is None:
         out = torch.empty((n,), dtype=F64, device=posd.device)
     _chk(out, (n,), "phi_out", F64)
-    with _lib.on_device(posd.device):
-        _lib.check(_lib.lib().nbd_potential_f64(posd.data_ptr(), n, float(softening_sq), float(g_const), out.data_ptr(),
-                                                workspace.data_ptr(), _nbytes(workspace),
-                                                _lib.current_stream(posd.device)), "nbd_potential_f64")
+    _lib.launch("nbd_potential_f64", posd.device, posd.data_ptr(), n, float(softening_sq), float(g_const),
+                out.data_ptr(), workspace.data_ptr(), _nbytes(workspace))
     return out
 
 
 def invariants_state_f64(pos, vel, mass, phi, out=None) -> torch.Tensor:
     """`invariants` from a float64 state (pos, vel (n,3), mass (n)) and its potentials phi; asynchronous."""
     n = pos.shape[0]
-    _chk(pos, (n, 3), "pos", F64); _chk(vel, (n, 3), "vel", F64); _chk(mass, (n,), "mass", F64)
+    _chk_n3(F64, n, ("pos", "vel"), pos, vel); _chk(mass, (n,), "mass", F64)
     _chk(phi, (n,), "phi", F64)
     if out is None:
         out = torch.empty(INVARIANT_ROW, dtype=F64, device=vel.device)
     _chk(out, (INVARIANT_ROW,), "out_row", F64)
-    with _lib.on_device(vel.device):
-        _lib.check(_lib.lib().nbd_invariants_state_f64(pos.data_ptr(), vel.data_ptr(), mass.data_ptr(), phi.data_ptr(), n,
-                                                       out.data_ptr(), _lib.current_stream(vel.device)),
-                   "nbd_invariants_state_f64")
+    _lib.launch("nbd_invariants_state_f64", vel.device, pos.data_ptr(), vel.data_ptr(), mass.data_ptr(), phi.data_ptr(),
+                n, out.data_ptr())
     return out
 
 
@@ -610,7 +568,7 @@ def hermite6_pack(pos, vel, mass, posd, veld, accd, acc=None, jerk=None, snap=No
     """posd = {x_p, m}, veld = {v_p, 0}, accd = {a_p, 0}, predicted over dt from (acc, jerk, snap, crackle); with jerk,
     snap and crackle all None a plain pack of (pos, vel, acc), and acc None gives zero rows."""
     n = pos.shape[0]
-    _chk(pos, (n, 3), "pos", F64); _chk(vel, (n, 3), "vel", F64); _chk(mass, (n,), "mass", F64)
+    _chk_n3(F64, n, ("pos", "vel"), pos, vel); _chk(mass, (n,), "mass", F64)
     _chk_packed(F64, posd, veld, n); _chk_accd(accd, n)
     higher = (jerk, snap, crackle)
     if len({t is None for t in higher}) != 1 or (jerk is not None and acc is None):
@@ -618,11 +576,9 @@ def hermite6_pack(pos, vel, mass, posd, veld, accd, acc=None, jerk=None, snap=No
     for t, nm in ((acc, "acc"), (jerk, "jerk"), (snap, "snap"), (crackle, "crackle")):
         if t is not None:
             _chk(t, (n, 3), nm, F64)
-    with _lib.on_device(pos.device):
-        _lib.check(_lib.lib().nbd_hermite6_f64_pack(
-            pos.data_ptr(), vel.data_ptr(), _lib.ptr(acc), _lib.ptr(jerk), _lib.ptr(snap), _lib.ptr(crackle),
-            mass.data_ptr(), n, float(dt), posd.data_ptr(), veld.data_ptr(), accd.data_ptr(),
-            _lib.current_stream(pos.device)), "nbd_hermite6_f64_pack")
+    _lib.launch("nbd_hermite6_f64_pack", pos.device, pos.data_ptr(), vel.data_ptr(), _lib.ptr(acc), _lib.ptr(jerk),
+                _lib.ptr(snap), _lib.ptr(crackle), mass.data_ptr(), n, float(dt), posd.data_ptr(), veld.data_ptr(),
+                accd.data_ptr())
 
 
 def accel_jerk_snap_f64(posd, veld, accd, n: int, softening_sq: float, g_const: float, workspace=None, slabs: int = 0):
@@ -633,11 +589,9 @@ def accel_jerk_snap_f64(posd, veld, accd, n: int, softening_sq: float, g_const: 
     acc_out, jerk_out, snap_out = (torch.empty((n, 3), dtype=F64, device=dev) for _ in range(3))
     if workspace is None:                       # a given workspace is checked by the entry, against what this call uses
         workspace = hermite6_workspace(n, dev, slabs)
-    with _lib.on_device(dev):
-        _lib.check(_lib.lib().nbd_accel_jerk_snap_f64(
-            posd.data_ptr(), veld.data_ptr(), accd.data_ptr(), n, float(softening_sq), float(g_const),
-            acc_out.data_ptr(), jerk_out.data_ptr(), snap_out.data_ptr(), workspace.data_ptr(), _nbytes(workspace),
-            int(slabs), _lib.current_stream(dev)), "nbd_accel_jerk_snap_f64")
+    _lib.launch("nbd_accel_jerk_snap_f64", dev, posd.data_ptr(), veld.data_ptr(), accd.data_ptr(), n,
+                float(softening_sq), float(g_const), acc_out.data_ptr(), jerk_out.data_ptr(), snap_out.data_ptr(),
+                workspace.data_ptr(), _nbytes(workspace), int(slabs))
     return acc_out, jerk_out, snap_out
 
 
@@ -646,19 +600,14 @@ def hermite6_step_f64(pos, vel, acc_in, jerk_in, snap_in, crackle_in, acc_out, j
     """One 6th-order Hermite step (three launches): pos, vel in place; every output may be its input; posd = {x1, m};
     veld and accd are scratch. dt, softening_sq and g_const go in as the Python doubles."""
     n = pos.shape[0]
-    for t, nm in ((pos, "pos"), (vel, "vel"), (acc_in, "acc_in"), (jerk_in, "jerk_in"), (snap_in, "snap_in"),
-                  (crackle_in, "crackle_in"), (acc_out, "acc_out"), (jerk_out, "jerk_out"), (snap_out, "snap_out"),
-                  (crackle_out, "crackle_out")):
-        _chk(t, (n, 3), nm, F64)
+    state = (pos, vel, acc_in, jerk_in, snap_in, crackle_in, acc_out, jerk_out, snap_out, crackle_out)
+    _chk_n3(F64, n, ("pos", "vel", "acc_in", "jerk_in", "snap_in", "crackle_in", "acc_out", "jerk_out", "snap_out",
+                     "crackle_out"), *state)
     _chk(mass, (n,), "mass", F64)
     _chk_packed(F64, posd, veld, n); _chk_accd(accd, n)
-    with _lib.on_device(pos.device):
-        _lib.check(_lib.lib().nbd_hermite6_step_f64(
-            pos.data_ptr(), vel.data_ptr(), acc_in.data_ptr(), jerk_in.data_ptr(), snap_in.data_ptr(),
-            crackle_in.data_ptr(), acc_out.data_ptr(), jerk_out.data_ptr(), snap_out.data_ptr(), crackle_out.data_ptr(),
-            mass.data_ptr(), n, float(dt), float(softening_sq), float(g_const), posd.data_ptr(), veld.data_ptr(),
-            accd.data_ptr(), workspace.data_ptr(), _nbytes(workspace), _lib.current_stream(pos.device)),
-            "nbd_hermite6_step_f64")
+    _lib.launch("nbd_hermite6_step_f64", pos.device, *(t.data_ptr() for t in state), mass.data_ptr(), n, float(dt),
+                float(softening_sq), float(g_const), posd.data_ptr(), veld.data_ptr(), accd.data_ptr(),
+                workspace.data_ptr(), _nbytes(workspace))
 
 
 # ---------------------------------------------------------- double-precision leapfrog (csrc/direct_leapfrog_f64.hip)
@@ -677,10 +626,8 @@ def accel_f64(posd, n: int, softening_sq: float, g_const: float, workspace=None,
     _chk(out, (n, 3), "acc_out", F64)
     if workspace is None:                       # a given workspace is checked by the entry, against what this call uses
         workspace = accel_f64_workspace(n, dev, slabs)
-    with _lib.on_device(dev):
-        _lib.check(_lib.lib().nbd_accel_f64(
-            posd.data_ptr(), n, float(softening_sq), float(g_const), out.data_ptr(), workspace.data_ptr(),
-            _nbytes(workspace), int(slabs), _lib.current_stream(dev)), "nbd_accel_f64")
+    _lib.launch("nbd_accel_f64", dev, posd.data_ptr(), n, float(softening_sq), float(g_const), out.data_ptr(),
+                workspace.data_ptr(), _nbytes(workspace), int(slabs))
     return out
 
 
@@ -689,30 +636,24 @@ def leapfrog_step_f64(pos, vel, acc_in, acc_out, mass, dt_half: float, dt: float
     """leapfrog_step in float64 (three launches): pos, vel in place; acc_out may be acc_in; posd = {x1, m}. dt_half, dt,
     softening_sq and g_const go in as the Python doubles."""
     n = pos.shape[0]
-    for t, nm in ((pos, "pos"), (vel, "vel"), (acc_in, "acc_in"), (acc_out, "acc_out")):
-        _chk(t, (n, 3), nm, F64)
+    _chk_n3(F64, n, ("pos", "vel", "acc_in", "acc_out"), pos, vel, acc_in, acc_out)
     _chk(mass, (n,), "mass", F64)
     _chk_packed(F64, posd, None, n)
-    with _lib.on_device(pos.device):
-        _lib.check(_lib.lib().nbd_leapfrog_step_f64(
-            pos.data_ptr(), vel.data_ptr(), acc_in.data_ptr(), acc_out.data_ptr(), mass.data_ptr(), n, float(dt_half),
-            float(dt), float(softening_sq), float(g_const), posd.data_ptr(), workspace.data_ptr(), _nbytes(workspace),
-            _lib.current_stream(pos.device)), "nbd_leapfrog_step_f64")
+    _lib.launch("nbd_leapfrog_step_f64", pos.device, pos.data_ptr(), vel.data_ptr(), acc_in.data_ptr(),
+                acc_out.data_ptr(), mass.data_ptr(), n, float(dt_half), float(dt), float(softening_sq), float(g_const),
+                posd.data_ptr(), workspace.data_ptr(), _nbytes(workspace))
 
 
 def euler_step_f64(pos, vel, acc_out, mass, dt: float, softening_sq: float, g_const: float, posd, workspace) -> None:
     """euler_step in float64 (three launches): acc_out = a(x), v += dt a, x += dt v; posd keeps the positions from before
     the drift."""
     n = pos.shape[0]
-    for t, nm in ((pos, "pos"), (vel, "vel"), (acc_out, "acc_out")):
-        _chk(t, (n, 3), nm, F64)
+    _chk_n3(F64, n, ("pos", "vel", "acc_out"), pos, vel, acc_out)
     _chk(mass, (n,), "mass", F64)
     _chk_packed(F64, posd, None, n)
-    with _lib.on_device(pos.device):
-        _lib.check(_lib.lib().nbd_euler_step_f64(
-            pos.data_ptr(), vel.data_ptr(), acc_out.data_ptr(), mass.data_ptr(), n, float(dt), float(softening_sq),
-            float(g_const), posd.data_ptr(), workspace.data_ptr(), _nbytes(workspace),
-            _lib.current_stream(pos.device)), "nbd_euler_step_f64")
+    _lib.launch("nbd_euler_step_f64", pos.device, pos.data_ptr(), vel.data_ptr(), acc_out.data_ptr(), mass.data_ptr(),
+                n, float(dt), float(softening_sq), float(g_const), posd.data_ptr(), workspace.data_ptr(),
+                _nbytes(workspace))
 
 
 # ----------------------- double-precision range-sharded Hermite step (csrc/direct_hermite_shard_f64.hip)
@@ -722,10 +663,7 @@ def alloc_hermite_rows_f64(n: int, device) -> torch.Tensor:
 
 
 def hermite_shard_f64_plan(n_total: int, lo: int, n_local: int) -> dict:
-    a, b, c, d = ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
-    _lib.check(_lib.lib().nbd_hermite_shard_f64_plan(n_total, lo, n_local, a, b, c, d), "nbd_hermite_shard_f64_plan")
-    return {"slabs_local": a.value, "chunks_per_wave_local": b.value, "slabs_remote": c.value,
-            "chunks_per_wave_remote": d.value}
+    return _plan("nbd_hermite_shard_f64_plan", _PLAN4, n_total, lo, n_local)
 
 
 def hermite_shard_f64_workspace(n_total: int, lo: int, n_local: int, device, slabs_local: int = 0,
@@ -738,27 +676,15 @@ def hermite_shard_f64_workspace(n_total: int, lo: int, n_local: int, device, sla
 def hermite_shard_predict_f64(pos, vel, mass, send, acc=None, jerk=None, dt: float = 0.0) -> None:
     """hermite_shard_predict in float64: send[:n_local] = {x_p, m, v_p, 0} of the rank's bodies predicted over dt from
     (acc, jerk) -- a plain pack of (pos, vel) when both are None -- and zeros in every row behind n_local."""
-    n = pos.shape[0]
-    _chk(pos, (n, 3), "pos", F64); _chk(vel, (n, 3), "vel", F64); _chk(mass, (n,), "mass", F64)
-    _chk_rows(send, n, "send", F64)
-    if (acc is None) != (jerk is None):
-        raise _lib.NbdError("hermite_shard_predict_f64: give both acc and jerk, or neither")
-    if acc is not None:
-        _chk(acc, (n, 3), "acc", F64); _chk(jerk, (n, 3), "jerk", F64)
-    with _lib.on_device(send.device):
-        _lib.check(_lib.lib().nbd_hermite_shard_predict_f64(
-            pos.data_ptr(), vel.data_ptr(), _lib.ptr(acc), _lib.ptr(jerk), mass.data_ptr(), n, float(dt),
-            send.data_ptr(), send.shape[0], _lib.current_stream(send.device)), "nbd_hermite_shard_predict_f64")
+    _hermite_shard_predict(F64, "nbd_hermite_shard_predict_f64", "hermite_shard_predict_f64", pos, vel, mass, send, acc,
+                           jerk, dt)
 
 
 def hermite_shard_force_local_f64(send: torch.Tensor, n_local: int, n_total: int, lo: int, softening_sq: float,
                                   workspace: torch.Tensor, slabs: int = 0) -> None:
     """hermite_shard_force_local in float64. slabs: 0 = the plan's split of the own chunks, else that many slabs."""
-    _chk_rows(send, n_local, "send", F64)
-    with _lib.on_device(send.device):
-        _lib.check(_lib.lib().nbd_hermite_shard_force_local_f64(
-            send.data_ptr(), n_local, float(softening_sq), workspace.data_ptr(), _nbytes(workspace), n_total, lo,
-            int(slabs), _lib.current_stream(send.device)), "nbd_hermite_shard_force_local_f64")
+    _hermite_shard_force_local(F64, "nbd_hermite_shard_force_local_f64", send, n_local, n_total, lo, softening_sq,
+                               workspace, slabs)
 
 
 def hermite_shard_force_remote_f64(rows_all: torch.Tensor, n_total: int, send: torch.Tensor, n_local: int, lo: int,
@@ -768,21 +694,9 @@ def hermite_shard_force_remote_f64(rows_all: torch.Tensor, n_total: int, send: t
     """hermite_shard_force_remote in float64: every other body of the gathered rows as a source, then a1, j1 =
     G * sum(slabs) into acc_out, jerk_out, and with pos, vel, acc_in, jerk_in and dt the corrector of the own rows.
     slabs_local: what the local call was given; slabs_remote: 0 = the plan's split of the remote chunks."""
-    _chk_rows(rows_all, n_total, "rows_all", F64)
-    _chk_rows(send, n_local, "send", F64)
-    _chk(acc_out, (n_local, 3), "acc_out", F64); _chk(jerk_out, (n_local, 3), "jerk_out", F64)
-    step = (pos, vel, acc_in, jerk_in)
-    if any(t is None for t in step) != all(t is None for t in step):
-        raise _lib.NbdError("hermite_shard_force_remote_f64: give pos, vel, acc_in and jerk_in, or none of them")
-    if pos is not None:
-        for t, nm in zip(step, ("pos", "vel", "acc_in", "jerk_in")):
-            _chk(t, (n_local, 3), nm, F64)
-    with _lib.on_device(rows_all.device):
-        _lib.check(_lib.lib().nbd_hermite_shard_force_remote_f64(
-            rows_all.data_ptr(), n_total, send.data_ptr(), n_local, lo, float(softening_sq), float(g_const),
-            _lib.ptr(pos), _lib.ptr(vel), _lib.ptr(acc_in), _lib.ptr(jerk_in), acc_out.data_ptr(), jerk_out.data_ptr(),
-            float(dt), workspace.data_ptr(), _nbytes(workspace), int(slabs_local), int(slabs_remote),
-            _lib.current_stream(rows_all.device)), "nbd_hermite_shard_force_remote_f64")
+    _hermite_shard_force_remote(F64, "nbd_hermite_shard_force_remote_f64", "hermite_shard_force_remote_f64", rows_all,
+                                n_total, send, n_local, lo, softening_sq, g_const, acc_out, jerk_out, workspace, pos, vel,
+                                acc_in, jerk_in, dt, slabs_local, slabs_remote)
 
 
 # ------------------------------------------------ backward of the all-pairs acceleration (csrc/direct_grad.hip)
@@ -804,6 +718,22 @@ def _chk_grads(n: int, dtype, dev, grad_pos, grad_mass, want_pos: bool, want_mas
     return (grad_pos if want_pos else None), (grad_mass if want_mass else None)
 
 
+def _accel_vjp(dtype, entry: str, who: str, rows, cot, n, softening_sq, g_const, grad_pos, grad_mass, workspace,
+               want_pos, want_mass, need_entry: str, *slabs):
+    """What accel_vjp and accel_vjp_f64 share behind their own checks of the packed rows: the outputs that are asked
+    for, the workspace (need_entry(n, *slabs) bytes) and the launch."""
+    dev = rows.device
+    grad_pos, grad_mass = _chk_grads(n, dtype, dev, grad_pos, grad_mass, want_pos, want_mass)
+    need = getattr(_lib.lib(), need_entry)(n, *slabs)
+    if workspace is None:
+        workspace = alloc_bytes(need, dev)
+    if _nbytes(workspace) < need:
+        raise _lib.NbdError(f"{who}: workspace of {_nbytes(workspace)} bytes, {need} needed")
+    _lib.launch(entry, dev, rows.data_ptr(), cot.data_ptr(), n, float(softening_sq), float(g_const), _lib.ptr(grad_pos),
+                _lib.ptr(grad_mass), workspace.data_ptr(), *slabs)
+    return grad_pos, grad_mass
+
+
 def accel_vjp(posm, cot, n: int, softening_sq: float, g_const: float, grad_pos=None, grad_mass=None, workspace=None,
               want_pos: bool = True, want_mass: bool = True):
     """(grad_pos (n,3), grad_mass (n,)) of L with respect to the positions and masses packed in posm, for the cotangent
@@ -811,18 +741,8 @@ def accel_vjp(posm, cot, n: int, softening_sq: float, g_const: float, grad_pos=N
     `accel`: dL/dx_i = G sum_j [s^3 h - 3 s^5 d (d.h)], h = m_i g_j - m_j g_i; dL/dm_i = -G sum_j s^3 (d.g_j).
     A gradient that is not wanted is None and is not written."""
     _chk(posm, (padded_len(n), 4), "posm"); _chk(cot, (padded_len(n), 4), "cot")
-    dev = posm.device
-    grad_pos, grad_mass = _chk_grads(n, torch.float32, dev, grad_pos, grad_mass, want_pos, want_mass)
-    need = _lib.lib().nbd_accel_vjp_workspace_bytes(n)
-    if workspace is None:
-        workspace = alloc_bytes(need, dev)
-    if _nbytes(workspace) < need:
-        raise _lib.NbdError(f"accel_vjp: workspace of {_nbytes(workspace)} bytes, {need} needed")
-    with _lib.on_device(dev):
-        _lib.check(_lib.lib().nbd_accel_vjp_f32(
-            posm.data_ptr(), cot.data_ptr(), n, float(softening_sq), float(g_const), _lib.ptr(grad_pos),
-            _lib.ptr(grad_mass), workspace.data_ptr(), _lib.current_stream(dev)), "nbd_accel_vjp_f32")
-    return grad_pos, grad_mass
+    return _accel_vjp(torch.float32, "nbd_accel_vjp_f32", "accel_vjp", posm, cot, n, softening_sq, g_const, grad_pos,
+                      grad_mass, workspace, want_pos, want_mass, "nbd_accel_vjp_workspace_bytes")
 
 
 def accel_vjp_f64_workspace(n: int, device, slabs: int = 0) -> torch.Tensor:
@@ -835,18 +755,8 @@ def accel_vjp_f64(posd, cotd, n: int, softening_sq: float, g_const: float, grad_
     _chk_packed(F64, posd, cotd, n)
     if not 0 <= int(slabs) <= 64:
         raise _lib.NbdError(f"accel_vjp_f64: slabs must be in [0, 64], got {slabs}")
-    dev = posd.device
-    grad_pos, grad_mass = _chk_grads(n, F64, dev, grad_pos, grad_mass, want_pos, want_mass)
-    need = _lib.lib().nbd_accel_vjp_f64_workspace_bytes(n, int(slabs))
-    if workspace is None:
-        workspace = alloc_bytes(need, dev)
-    if _nbytes(workspace) < need:
-        raise _lib.NbdError(f"accel_vjp_f64: workspace of {_nbytes(workspace)} bytes, {need} needed")
-    with _lib.on_device(dev):
-        _lib.check(_lib.lib().nbd_accel_vjp_f64(
-            posd.data_ptr(), cotd.data_ptr(), n, float(softening_sq), float(g_const), _lib.ptr(grad_pos),
-            _lib.ptr(grad_mass), workspace.data_ptr(), int(slabs), _lib.current_stream(dev)), "nbd_accel_vjp_f64")
-    return grad_pos, grad_mass
+    return _accel_vjp(F64, "nbd_accel_vjp_f64", "accel_vjp_f64", posd, cotd, n, softening_sq, g_const, grad_pos,
+                      grad_mass, workspace, want_pos, want_mass, "nbd_accel_vjp_f64_workspace_bytes", int(slabs))
 
 
 # ------------------------------------------------ backward of the Hermite force (csrc/direct_hermite_grad.hip)
@@ -858,8 +768,10 @@ def accel_jerk_vjp_f64_workspace(n: int, device, slabs: int = 0) -> torch.Tensor
     return alloc_bytes(_lib.lib().nbd_accel_jerk_vjp_f64_workspace_bytes(int(n), int(slabs)), device)
 
 
-def _accel_jerk_vjp(dtype, name, rows, vrows, cota, cotj, n, grads, wants, workspace, need, launch):
-    """What accel_jerk_vjp and accel_jerk_vjp_f64 share: the checks, the outputs that are asked for, the workspace."""
+def _accel_jerk_vjp(dtype, entry: str, name: str, rows, vrows, cota, cotj, n, softening_sq, g_const, grads, wants,
+                    workspace, need, *slabs):
+    """What accel_jerk_vjp and accel_jerk_vjp_f64 share: the checks, the outputs that are asked for, the workspace of
+    `need` bytes and the launch."""
     _chk_packed(dtype, rows, vrows, n)
     if cota is None and cotj is None:
         raise _lib.NbdError(f"{name}: neither cotangent is given")
@@ -881,8 +793,9 @@ def _accel_jerk_vjp(dtype, name, rows, vrows, cota, cotj, n, grads, wants, works
     if _nbytes(workspace) < need:
         raise _lib.NbdError(f"{name}: workspace of {_nbytes(workspace)} bytes, {need} needed")
     if n:
-        with _lib.on_device(dev):
-            launch(out, workspace, _lib.current_stream(dev))
+        _lib.launch(entry, dev, rows.data_ptr(), vrows.data_ptr(), _lib.ptr(cota), _lib.ptr(cotj), n,
+                    float(softening_sq), float(g_const), *map(_lib.ptr, out), workspace.data_ptr(), _nbytes(workspace),
+                    *slabs)
     return tuple(out)
 
 
@@ -893,17 +806,9 @@ def accel_jerk_vjp(posm, velp, cota, cotj, n: int, softening_sq: float, g_const:
     cotj = {gx, gy, gz, 0} (hermite_pack with a cotangent as the velocities). Either cotangent may be None: with cotj None
     the results are accel_vjp's bits and grad_vel is zeros. A gradient that is not wanted is None and is not written.
     The formulas: csrc/direct_hermite_grad.hip."""
-    L = _lib.lib()
-
-    def launch(out, ws, stream):
-        _lib.check(L.nbd_accel_jerk_vjp_f32(
-            posm.data_ptr(), velp.data_ptr(), _lib.ptr(cota), _lib.ptr(cotj), n, float(softening_sq), float(g_const),
-            _lib.ptr(out[0]), _lib.ptr(out[1]), _lib.ptr(out[2]), ws.data_ptr(), _nbytes(ws), stream),
-            "nbd_accel_jerk_vjp_f32")
-
-    return _accel_jerk_vjp(torch.float32, "accel_jerk_vjp", posm, velp, cota, cotj, n, (grad_pos, grad_vel, grad_mass),
-                           (want_pos, want_vel, want_mass), workspace, L.nbd_accel_jerk_vjp_workspace_bytes(int(n)),
-                           launch)
+    return _accel_jerk_vjp(torch.float32, "nbd_accel_jerk_vjp_f32", "accel_jerk_vjp", posm, velp, cota, cotj, n,
+                           softening_sq, g_const, (grad_pos, grad_vel, grad_mass), (want_pos, want_vel, want_mass),
+                           workspace, _lib.lib().nbd_accel_jerk_vjp_workspace_bytes(int(n)))
 
 
 def accel_jerk_vjp_f64(posd, veld, cota, cotj, n: int, softening_sq: float, g_const: float, grad_pos=None,
@@ -912,32 +817,30 @@ def accel_jerk_vjp_f64(posd, veld, cota, cotj, n: int, softening_sq: float, g_co
     """accel_jerk_vjp in float64 (rows as hermite_f64_pack leaves them). slabs: 0 = the plan's source split."""
     if not 0 <= int(slabs) <= 64:
         raise _lib.NbdError(f"accel_jerk_vjp_f64: slabs must be in [0, 64], got {slabs}")
-    L = _lib.lib()
-
-    def launch(out, ws, stream):
-        _lib.check(L.nbd_accel_jerk_vjp_f64(
-            posd.data_ptr(), veld.data_ptr(), _lib.ptr(cota), _lib.ptr(cotj), n, float(softening_sq), float(g_const),
-            _lib.ptr(out[0]), _lib.ptr(out[1]), _lib.ptr(out[2]), ws.data_ptr(), _nbytes(ws), int(slabs), stream),
-            "nbd_accel_jerk_vjp_f64")
-
-    return _accel_jerk_vjp(F64, "accel_jerk_vjp_f64", posd, veld, cota, cotj, n, (grad_pos, grad_vel, grad_mass),
-                           (want_pos, want_vel, want_mass), workspace,
-                           L.nbd_accel_jerk_vjp_f64_workspace_bytes(int(n), int(slabs)), launch)
+    return _accel_jerk_vjp(F64, "nbd_accel_jerk_vjp_f64", "accel_jerk_vjp_f64", posd, veld, cota, cotj, n, softening_sq,
+                           g_const, (grad_pos, grad_vel, grad_mass), (want_pos, want_vel, want_mass), workspace,
+                           _lib.lib().nbd_accel_jerk_vjp_f64_workspace_bytes(int(n), int(slabs)), int(slabs))
 
 
 # ---------------------------------------------------- block-timestep Hermite integrator (csrc/direct_hermite_block.hip)
 HBLOCK_SCHED_INTS = 32          # NBD_HBLOCK_SCHED_INTS: {t_next, n_act, clamped, ...} of the block schedule
 
 
+def _chk_sched(n: int, ticks, levels, sched):
+    """The int32 schedule arrays of a block step; ticks None where the entry takes none."""
+    if ticks is not None:
+        _chk(ticks, (n,), "ticks", torch.int32)
+    _chk(levels, (n,), "levels", torch.int32)
+    _chk(sched, (HBLOCK_SCHED_INTS,), "sched", torch.int32)
+
+
 def _chk_hblock(dtype, pos, vel, acc, jerk, mass, ticks, levels, sched, pos_rows, vel_rows) -> int:
     """The arguments of a block step in `dtype` (state, packed rows, int32 schedule arrays); returns n."""
     n = pos.shape[0]
-    for t, nm in ((pos, "pos"), (vel, "vel"), (acc, "acc"), (jerk, "jerk")):
-        _chk(t, (n, 3), nm, dtype)
+    _chk_n3(dtype, n, ("pos", "vel", "acc", "jerk"), pos, vel, acc, jerk)
     _chk(mass, (n,), "mass", dtype)
     _chk_packed(dtype, pos_rows, vel_rows, n)
-    _chk(ticks, (n,), "ticks", torch.int32); _chk(levels, (n,), "levels", torch.int32)
-    _chk(sched, (HBLOCK_SCHED_INTS,), "sched", torch.int32)
+    _chk_sched(n, ticks, levels, sched)
     return n
 
 
@@ -946,63 +849,69 @@ def hblock_workspace(n: int, device) -> torch.Tensor:
     return alloc_bytes(_lib.lib().nbd_hblock_workspace_bytes(int(n)), device)
 
 
+def _hblock_init_levels(dtype, entry: str, acc, jerk, dt, eta, max_level, ticks, levels, sched) -> None:
+    n = acc.shape[0]
+    _chk_n3(dtype, n, ("acc", "jerk"), acc, jerk)
+    _chk_sched(n, ticks, levels, sched)
+    _lib.launch(entry, acc.device, acc.data_ptr(), jerk.data_ptr(), n, float(dt), float(eta), int(max_level),
+                ticks.data_ptr(), levels.data_ptr(), sched.data_ptr())
+
+
 def hblock_init_levels(acc, jerk, dt: float, eta: float, max_level: int, ticks, levels, sched) -> None:
     """ticks = 0, levels from dt_i = (eta / 2) |a| / |j| quantised to dt 2^-k (k in [0, max_level]; deeper ones are
     clamped and counted in sched[2]); starts a new interval."""
-    n = acc.shape[0]
-    _chk(acc, (n, 3), "acc"); _chk(jerk, (n, 3), "jerk")
-    _chk(ticks, (n,), "ticks", torch.int32); _chk(levels, (n,), "levels", torch.int32)
-    _chk(sched, (HBLOCK_SCHED_INTS,), "sched", torch.int32)
-    with _lib.on_device(acc.device):
-        _lib.check(_lib.lib().nbd_hblock_init_levels(
-            acc.data_ptr(), jerk.data_ptr(), n, float(dt), float(eta), int(max_level), ticks.data_ptr(),
-            levels.data_ptr(), sched.data_ptr(), _lib.current_stream(acc.device)), "nbd_hblock_init_levels")
+    _hblock_init_levels(torch.float32, "nbd_hblock_init_levels", acc, jerk, dt, eta, max_level, ticks, levels, sched)
 
 
 def hblock_schedule(levels, max_level: int, sched, workspace, host_sched=None) -> None:
     """t_next and the active list of the next block step (sched[0], sched[1]; the list into the workspace). host_sched: an
     int32 CPU tensor of at least 4 elements (pinned is fastest) that receives sched[0..4) after a stream sync."""
     n = levels.shape[0]
-    _chk(levels, (n,), "levels", torch.int32)
-    _chk(sched, (HBLOCK_SCHED_INTS,), "sched", torch.int32)
+    _chk_sched(n, None, levels, sched)
     if host_sched is not None and (host_sched.is_cuda or host_sched.dtype != torch.int32 or host_sched.numel() < 4):
         raise _lib.NbdError("hblock_schedule: host_sched must be an int32 CPU tensor of 4 elements")
-    with _lib.on_device(levels.device):
-        _lib.check(_lib.lib().nbd_hblock_schedule(
-            levels.data_ptr(), n, int(max_level), sched.data_ptr(), workspace.data_ptr(), _nbytes(workspace),
-            _lib.ptr(host_sched), _lib.current_stream(levels.device)), "nbd_hblock_schedule")
+    _lib.launch("nbd_hblock_schedule", levels.device, levels.data_ptr(), n, int(max_level), sched.data_ptr(),
+                workspace.data_ptr(), _nbytes(workspace), _lib.ptr(host_sched))
+
+
+def _hblock_step(dtype, entry: str, pos, vel, acc, jerk, mass, ticks, levels, n_act, max_level, dt, eta, softening_sq,
+                 g_const, sched, rows, vrows, workspace) -> None:
+    n = _chk_hblock(dtype, pos, vel, acc, jerk, mass, ticks, levels, sched, rows, vrows)
+    _lib.launch(entry, pos.device, pos.data_ptr(), vel.data_ptr(), acc.data_ptr(), jerk.data_ptr(), mass.data_ptr(),
+                ticks.data_ptr(), levels.data_ptr(), n, int(n_act), int(max_level), float(dt), float(eta),
+                float(softening_sq), float(g_const), sched.data_ptr(), rows.data_ptr(), vrows.data_ptr(),
+                workspace.data_ptr(), _nbytes(workspace))
 
 
 def hblock_step(pos, vel, acc, jerk, mass, ticks, levels, n_act: int, max_level: int, dt: float, eta: float,
                 softening_sq: float, g_const: float, sched, posm, velp, workspace) -> None:
     """Predict all bodies to t_next, evaluate the n_act listed ones, correct and re-level them (three launches). pos, vel,
     acc, jerk, ticks, levels in place for the active bodies; posm = {x1, m} for them, predicted rows for the rest."""
-    n = _chk_hblock(torch.float32, pos, vel, acc, jerk, mass, ticks, levels, sched, posm, velp)
-    with _lib.on_device(pos.device):
-        _lib.check(_lib.lib().nbd_hblock_step_f32(
-            pos.data_ptr(), vel.data_ptr(), acc.data_ptr(), jerk.data_ptr(), mass.data_ptr(), ticks.data_ptr(),
-            levels.data_ptr(), n, int(n_act), int(max_level), float(dt), float(eta), float(softening_sq),
-            float(g_const), sched.data_ptr(), posm.data_ptr(), velp.data_ptr(), workspace.data_ptr(),
-            _nbytes(workspace), _lib.current_stream(pos.device)), "nbd_hblock_step_f32")
+    _hblock_step(torch.float32, "nbd_hblock_step_f32", pos, vel, acc, jerk, mass, ticks, levels, n_act, max_level, dt,
+                 eta, softening_sq, g_const, sched, posm, velp, workspace)
+
+
+def _accel_jerk_active(dtype, entry: str, rows, vrows, n, act, softening_sq, g_const, workspace, new_workspace, *slabs):
+    """new_workspace(device, n_act): the workspace where none is given."""
+    _chk_packed(dtype, rows, vrows, n)
+    _chk(act, None, "act", torch.int32)
+    n_act = act.numel()
+    dev = rows.device
+    acc_out = torch.empty((n_act, 3), dtype=dtype, device=dev)
+    jerk_out = torch.empty((n_act, 3), dtype=dtype, device=dev)
+    if workspace is None:                       # a given workspace is checked by the entry, against what this call uses
+        workspace = new_workspace(dev, n_act)
+    _lib.launch(entry, dev, rows.data_ptr(), vrows.data_ptr(), n, act.data_ptr(), n_act, float(softening_sq),
+                float(g_const), acc_out.data_ptr(), jerk_out.data_ptr(), workspace.data_ptr(), _nbytes(workspace),
+                *map(int, slabs))
+    return acc_out, jerk_out
 
 
 def accel_jerk_active(posm, velp, n: int, act, softening_sq: float, g_const: float, workspace=None):
     """(acc, jerk), each (len(act), 3), of the bodies act (a device int32 list, any order) under all n bodies of posm /
     velp, in list order. The all-bodies list gives accel_jerk's bits."""
-    _chk_packed(torch.float32, posm, velp, n)
-    _chk(act, None, "act", torch.int32)
-    n_act = act.numel()
-    dev = posm.device
-    acc_out = torch.empty((n_act, 3), dtype=torch.float32, device=dev)
-    jerk_out = torch.empty((n_act, 3), dtype=torch.float32, device=dev)
-    if workspace is None:                       # a given workspace is checked by the entry, against what this call uses
-        workspace = hblock_workspace(n, dev)
-    with _lib.on_device(dev):
-        _lib.check(_lib.lib().nbd_accel_jerk_active_f32(
-            posm.data_ptr(), velp.data_ptr(), n, act.data_ptr(), n_act, float(softening_sq), float(g_const),
-            acc_out.data_ptr(), jerk_out.data_ptr(), workspace.data_ptr(), _nbytes(workspace),
-            _lib.current_stream(dev)), "nbd_accel_jerk_active_f32")
-    return acc_out, jerk_out
+    return _accel_jerk_active(torch.float32, "nbd_accel_jerk_active_f32", posm, velp, n, act, softening_sq, g_const,
+                              workspace, lambda dev, n_act: hblock_workspace(n, dev))
 
 
 # ------------------------------- double-precision block-timestep Hermite (csrc/direct_hermite_block_f64.hip)
@@ -1015,76 +924,46 @@ def hblock_f64_workspace(n: int, device, slabs: int = 0, n_act: int = 0) -> torc
 
 def hblock_init_levels_f64(acc, jerk, dt: float, eta: float, max_level: int, ticks, levels, sched) -> None:
     """hblock_init_levels from float64 acc, jerk."""
-    n = acc.shape[0]
-    _chk(acc, (n, 3), "acc", F64); _chk(jerk, (n, 3), "jerk", F64)
-    _chk(ticks, (n,), "ticks", torch.int32); _chk(levels, (n,), "levels", torch.int32)
-    _chk(sched, (HBLOCK_SCHED_INTS,), "sched", torch.int32)
-    with _lib.on_device(acc.device):
-        _lib.check(_lib.lib().nbd_hblock_init_levels_f64(
-            acc.data_ptr(), jerk.data_ptr(), n, float(dt), float(eta), int(max_level), ticks.data_ptr(),
-            levels.data_ptr(), sched.data_ptr(), _lib.current_stream(acc.device)), "nbd_hblock_init_levels_f64")
+    _hblock_init_levels(F64, "nbd_hblock_init_levels_f64", acc, jerk, dt, eta, max_level, ticks, levels, sched)
 
 
 def hblock_predict_f64(pos, vel, acc, jerk, mass, ticks, levels, max_level: int, dt: float, sched, posd, veld) -> None:
     """First launch of a float64 block step: every body predicted to t_next = sched[0] into posd / veld."""
     n = _chk_hblock(F64, pos, vel, acc, jerk, mass, ticks, levels, sched, posd, veld)
-    with _lib.on_device(pos.device):
-        _lib.check(_lib.lib().nbd_hblock_predict_f64(
-            pos.data_ptr(), vel.data_ptr(), acc.data_ptr(), jerk.data_ptr(), mass.data_ptr(), ticks.data_ptr(), n,
-            int(max_level), float(dt), sched.data_ptr(), posd.data_ptr(), veld.data_ptr(),
-            _lib.current_stream(pos.device)), "nbd_hblock_predict_f64")
+    _lib.launch("nbd_hblock_predict_f64", pos.device, pos.data_ptr(), vel.data_ptr(), acc.data_ptr(), jerk.data_ptr(),
+                mass.data_ptr(), ticks.data_ptr(), n, int(max_level), float(dt), sched.data_ptr(), posd.data_ptr(),
+                veld.data_ptr())
 
 
 def hblock_force_f64(posd, veld, n: int, n_act: int, softening_sq: float, workspace) -> None:
     """Second launch: the partial sums of the n_act bodies the schedule listed in the workspace."""
     _chk_packed(F64, posd, veld, n)
-    with _lib.on_device(posd.device):
-        _lib.check(_lib.lib().nbd_hblock_force_f64(
-            posd.data_ptr(), veld.data_ptr(), n, int(n_act), float(softening_sq), workspace.data_ptr(),
-            _nbytes(workspace), _lib.current_stream(posd.device)), "nbd_hblock_force_f64")
+    _lib.launch("nbd_hblock_force_f64", posd.device, posd.data_ptr(), veld.data_ptr(), n, int(n_act),
+                float(softening_sq), workspace.data_ptr(), _nbytes(workspace))
 
 
 def hblock_correct_f64(pos, vel, acc, jerk, mass, ticks, levels, n_act: int, max_level: int, dt: float, eta: float,
                        g_const: float, sched, posd, workspace) -> None:
     """Third launch: slab sum, corrector and new level of the listed bodies; posd = {x1, m} for them."""
     n = _chk_hblock(F64, pos, vel, acc, jerk, mass, ticks, levels, sched, posd, None)
-    with _lib.on_device(pos.device):
-        _lib.check(_lib.lib().nbd_hblock_correct_f64(
-            pos.data_ptr(), vel.data_ptr(), acc.data_ptr(), jerk.data_ptr(), mass.data_ptr(), ticks.data_ptr(),
-            levels.data_ptr(), n, int(n_act), int(max_level), float(dt), float(eta), float(g_const), sched.data_ptr(),
-            posd.data_ptr(), workspace.data_ptr(), _nbytes(workspace), _lib.current_stream(pos.device)),
-            "nbd_hblock_correct_f64")
+    _lib.launch("nbd_hblock_correct_f64", pos.device, pos.data_ptr(), vel.data_ptr(), acc.data_ptr(), jerk.data_ptr(),
+                mass.data_ptr(), ticks.data_ptr(), levels.data_ptr(), n, int(n_act), int(max_level), float(dt),
+                float(eta), float(g_const), sched.data_ptr(), posd.data_ptr(), workspace.data_ptr(), _nbytes(workspace))
 
 
 def hblock_step_f64(pos, vel, acc, jerk, mass, ticks, levels, n_act: int, max_level: int, dt: float, eta: float,
                     softening_sq: float, g_const: float, sched, posd, veld, workspace) -> None:
     """hblock_step in float64 (three launches): dt, eta, softening_sq and g_const go in as the Python doubles."""
-    n = _chk_hblock(F64, pos, vel, acc, jerk, mass, ticks, levels, sched, posd, veld)
-    with _lib.on_device(pos.device):
-        _lib.check(_lib.lib().nbd_hblock_step_f64(
-            pos.data_ptr(), vel.data_ptr(), acc.data_ptr(), jerk.data_ptr(), mass.data_ptr(), ticks.data_ptr(),
-            levels.data_ptr(), n, int(n_act), int(max_level), float(dt), float(eta), float(softening_sq),
-            float(g_const), sched.data_ptr(), posd.data_ptr(), veld.data_ptr(), workspace.data_ptr(),
-            _nbytes(workspace), _lib.current_stream(pos.device)), "nbd_hblock_step_f64")
+    _hblock_step(F64, "nbd_hblock_step_f64", pos, vel, acc, jerk, mass, ticks, levels, n_act, max_level, dt, eta,
+                 softening_sq, g_const, sched, posd, veld, workspace)
 
 
 def accel_jerk_active_f64(posd, veld, n: int, act, softening_sq: float, g_const: float, workspace=None, slabs: int = 0):
     """accel_jerk_active in float64: (acc, jerk), each (len(act), 3) float64, in list order. slabs: 0 = the plan's source
     split, else that many. The all-bodies list gives accel_jerk_f64's bits at the same slab count."""
-    _chk_packed(F64, posd, veld, n)
-    _chk(act, None, "act", torch.int32)
-    n_act = act.numel()
-    dev = posd.device
-    acc_out = torch.empty((n_act, 3), dtype=F64, device=dev)
-    jerk_out = torch.empty((n_act, 3), dtype=F64, device=dev)
-    if workspace is None:                       # a given workspace is checked by the entry, against what this call uses
-        workspace = hblock_f64_workspace(n, dev, slabs, n_act)
-    with _lib.on_device(dev):
-        _lib.check(_lib.lib().nbd_accel_jerk_active_f64(
-            posd.data_ptr(), veld.data_ptr(), n, act.data_ptr(), n_act, float(softening_sq), float(g_const),
-            acc_out.data_ptr(), jerk_out.data_ptr(), workspace.data_ptr(), _nbytes(workspace), int(slabs),
-            _lib.current_stream(dev)), "nbd_accel_jerk_active_f64")
-    return acc_out, jerk_out
+    return _accel_jerk_active(F64, "nbd_accel_jerk_active_f64", posd, veld, n, act, softening_sq, g_const, workspace,
+                              lambda dev, n_act: hblock_f64_workspace(n, dev, slabs, n_act), slabs)
+
 
 # ---------------------------------------------------------------- batched direct integrator (csrc/direct_batch.hip)
 class BatchPlan:
@@ -1112,21 +991,20 @@ class BatchPlan:
         self.n_scenes, self.n_total = len(sizes), int(self.offsets[-1])
         items, rows = ctypes.c_int(), ctypes.c_int()
         pb, wb = ctypes.c_size_t(), ctypes.c_size_t()
-        L = _lib.lib()
+        scenes = (self._off(), self.n_scenes)
         if dtype == torch.float32:
-            _lib.check(L.nbd_batch_plan(self._off(), self.n_scenes, items, rows, pb, wb), "nbd_batch_plan")
-            fill, fill_name = L.nbd_batch_plan_fill, "nbd_batch_plan_fill"
+            _lib.call("nbd_batch_plan", *scenes, items, rows, pb, wb)
+            fill = "nbd_batch_plan_fill"
         else:
-            _lib.check(L.nbd_batch_f64_plan(self._off(), self.n_scenes, items, rows, pb), "nbd_batch_f64_plan")
-            _lib.check(L.nbd_batch_f64_workspace_bytes(self._off(), self.n_scenes, wb), "nbd_batch_f64_workspace_bytes")
-            fill, fill_name = L.nbd_batch_f64_plan_fill, "nbd_batch_f64_plan_fill"
+            _lib.call("nbd_batch_f64_plan", *scenes, items, rows, pb)
+            _lib.call("nbd_batch_f64_workspace_bytes", *scenes, wb)
+            fill = "nbd_batch_f64_plan_fill"
             if order == 6:                    # items, rows and bytes are the float64 plan's
-                _lib.check(L.nbd_batch_hermite6_f64_workspace_bytes(self._off(), self.n_scenes, wb),
-                           "nbd_batch_hermite6_f64_workspace_bytes")
-                fill, fill_name = L.nbd_batch_hermite6_f64_plan_fill, "nbd_batch_hermite6_f64_plan_fill"
+                _lib.call("nbd_batch_hermite6_f64_workspace_bytes", *scenes, wb)
+                fill = "nbd_batch_hermite6_f64_plan_fill"
         self.n_items, self.posm_rows, self.plan_bytes, self.workspace_bytes = items.value, rows.value, pb.value, wb.value
         host = np.zeros((self.plan_bytes + 15) // 16 * 4, dtype=np.int32)
-        _lib.check(fill(self._off(), self.n_scenes, host.ctypes.data, self.plan_bytes), fill_name)
+        _lib.call(fill, *scenes, host.ctypes.data, self.plan_bytes)
         self.plan = torch.from_numpy(host).to(device)
         self.device = self.plan.device
 
@@ -1146,8 +1024,7 @@ class BatchPlan:
     def hermite_workspace_bytes(self) -> int:
         if getattr(self, "_hws_bytes", None) is None:          # asked on every step: one host query per plan
             nb = ctypes.c_size_t()
-            _lib.check(_lib.lib().nbd_batch_hermite_workspace_bytes(self._off(), self.n_scenes, nb),
-                       "nbd_batch_hermite_workspace_bytes")
+            _lib.call("nbd_batch_hermite_workspace_bytes", self._off(), self.n_scenes, nb)
             self._hws_bytes = nb.value
         return self._hws_bytes
 
@@ -1162,9 +1039,7 @@ class BatchPlan:
         n = self.n_total
         for t, nm in arrays:
             _chk(t, (n, 3) if nm != "mass" else (n,), nm)
-        _chk(posm, None, "posm")
-        if posm.dim() != 2 or posm.shape[1] != 4 or posm.shape[0] < self.posm_rows:
-            raise _lib.NbdError(f"posm: need >= {self.posm_rows} rows of 4, got {tuple(posm.shape)}")
+        _chk_min_rows(posm, self.posm_rows, 4, "posm")
         if ws is not None and _nbytes(ws) < self.workspace_bytes:
             raise _lib.NbdError("batch workspace too small")
 
@@ -1176,48 +1051,39 @@ def _param(p: torch.Tensor, plan: BatchPlan, name: str) -> int:
 
 def batch_pack_posm(plan: BatchPlan, pos, mass, posm) -> None:
     plan.check_state(posm, None, (pos, "pos"), (mass, "mass"))
-    with _lib.on_device(pos.device):
-        _lib.check(_lib.lib().nbd_batch_pack_posm_f32(*plan.head(), pos.data_ptr(), mass.data_ptr(), posm.data_ptr(),
-                                                      _lib.current_stream(pos.device)), "nbd_batch_pack_posm_f32")
+    _lib.launch("nbd_batch_pack_posm_f32", pos.device, *plan.head(), pos.data_ptr(), mass.data_ptr(), posm.data_ptr())
 
 
 def batch_accel(plan: BatchPlan, pos, mass, eps2, g, acc_out, posm, ws) -> None:
     """acc_out = the force of every scene on its own bodies (packs posm first). eps2, g: device fp32 (S,)."""
     plan.check_state(posm, ws, (pos, "pos"), (mass, "mass"), (acc_out, "acc_out"))
-    with _lib.on_device(pos.device):
-        _lib.check(_lib.lib().nbd_batch_accel_f32(
-            *plan.head(), pos.data_ptr(), mass.data_ptr(), _param(eps2, plan, "softening_sq"), _param(g, plan, "g_const"),
-            acc_out.data_ptr(), posm.data_ptr(), ws.data_ptr(), _nbytes(ws), _lib.current_stream(pos.device)),
-            "nbd_batch_accel_f32")
+    _lib.launch("nbd_batch_accel_f32", pos.device, *plan.head(), pos.data_ptr(), mass.data_ptr(),
+                _param(eps2, plan, "softening_sq"), _param(g, plan, "g_const"), acc_out.data_ptr(), posm.data_ptr(),
+                ws.data_ptr(), _nbytes(ws))
 
 
 def batch_leapfrog_step(plan: BatchPlan, pos, vel, acc_in, acc_out, mass, dt_half, dt, eps2, g, posm, ws) -> None:
     plan.check_state(posm, ws, (pos, "pos"), (vel, "vel"), (acc_in, "acc_in"), (acc_out, "acc_out"), (mass, "mass"))
-    with _lib.on_device(pos.device):
-        _lib.check(_lib.lib().nbd_batch_leapfrog_step_f32(
-            *plan.head(), pos.data_ptr(), vel.data_ptr(), acc_in.data_ptr(), acc_out.data_ptr(), mass.data_ptr(),
-            _param(dt_half, plan, "dt_half"), _param(dt, plan, "dt"), _param(eps2, plan, "softening_sq"),
-            _param(g, plan, "g_const"), posm.data_ptr(), ws.data_ptr(), _nbytes(ws), _lib.current_stream(pos.device)),
-            "nbd_batch_leapfrog_step_f32")
+    _lib.launch("nbd_batch_leapfrog_step_f32", pos.device, *plan.head(), pos.data_ptr(), vel.data_ptr(),
+                acc_in.data_ptr(), acc_out.data_ptr(), mass.data_ptr(), _param(dt_half, plan, "dt_half"),
+                _param(dt, plan, "dt"), _param(eps2, plan, "softening_sq"), _param(g, plan, "g_const"), posm.data_ptr(),
+                ws.data_ptr(), _nbytes(ws))
 
 
 def batch_euler_step(plan: BatchPlan, pos, vel, acc_out, mass, dt, eps2, g, posm, ws) -> None:
     plan.check_state(posm, ws, (pos, "pos"), (vel, "vel"), (acc_out, "acc_out"), (mass, "mass"))
-    with _lib.on_device(pos.device):
-        _lib.check(_lib.lib().nbd_batch_euler_step_f32(
-            *plan.head(), pos.data_ptr(), vel.data_ptr(), acc_out.data_ptr(), mass.data_ptr(), _param(dt, plan, "dt"),
-            _param(eps2, plan, "softening_sq"), _param(g, plan, "g_const"), posm.data_ptr(), ws.data_ptr(), _nbytes(ws),
-            _lib.current_stream(pos.device)), "nbd_batch_euler_step_f32")
+    _lib.launch("nbd_batch_euler_step_f32", pos.device, *plan.head(), pos.data_ptr(), vel.data_ptr(),
+                acc_out.data_ptr(), mass.data_ptr(), _param(dt, plan, "dt"), _param(eps2, plan, "softening_sq"),
+                _param(g, plan, "g_const"), posm.data_ptr(), ws.data_ptr(), _nbytes(ws))
 
 
 def batch_energies(plan: BatchPlan, posm, vel, soft, g, out_uk, ws) -> torch.Tensor:
     """out_uk (S, 2) float64 = {U_s, K_s} from posm (as the batch entries leave it) and vel; asynchronous."""
     plan.check_state(posm, ws, (vel, "vel"))
     _chk(out_uk, (plan.n_scenes, 2), "out_uk", torch.float64)
-    with _lib.on_device(vel.device):
-        _lib.check(_lib.lib().nbd_batch_energies(
-            *plan.head(), posm.data_ptr(), vel.data_ptr(), _param(soft, plan, "softening"), _param(g, plan, "g_const"),
-            out_uk.data_ptr(), ws.data_ptr(), _nbytes(ws), _lib.current_stream(vel.device)), "nbd_batch_energies")
+    _lib.launch("nbd_batch_energies", vel.device, *plan.head(), posm.data_ptr(), vel.data_ptr(),
+                _param(soft, plan, "softening"), _param(g, plan, "g_const"), out_uk.data_ptr(), ws.data_ptr(),
+                _nbytes(ws))
     return out_uk
 
 
@@ -1226,10 +1092,9 @@ def batch_potential(plan: BatchPlan, posm, eps2, g, phi_out, ws) -> torch.Tensor
     for bit) from posm as the batch entries leave it. eps2, g: device fp32 (S,); ws: plan.workspace(). Asynchronous."""
     plan.check_state(posm, ws)
     _chk(phi_out, (plan.n_total,), "phi_out", torch.float64)
-    with _lib.on_device(posm.device):
-        _lib.check(_lib.lib().nbd_batch_potential_f32(
-            *plan.head(), posm.data_ptr(), _param(eps2, plan, "softening_sq"), _param(g, plan, "g_const"),
-            phi_out.data_ptr(), ws.data_ptr(), _nbytes(ws), _lib.current_stream(posm.device)), "nbd_batch_potential_f32")
+    _lib.launch("nbd_batch_potential_f32", posm.device, *plan.head(), posm.data_ptr(),
+                _param(eps2, plan, "softening_sq"), _param(g, plan, "g_const"), phi_out.data_ptr(), ws.data_ptr(),
+                _nbytes(ws))
     return phi_out
 
 
@@ -1238,10 +1103,8 @@ def batch_invariants(plan: BatchPlan, posm, vel, phi, out_rows) -> torch.Tensor:
     plan.check_state(posm, None, (vel, "vel"))
     _chk(phi, (plan.n_total,), "phi", torch.float64)
     _chk(out_rows, (plan.n_scenes, INVARIANT_ROW), "out_rows", torch.float64)
-    with _lib.on_device(vel.device):
-        _lib.check(_lib.lib().nbd_batch_invariants_f64(
-            *plan.head(), posm.data_ptr(), vel.data_ptr(), phi.data_ptr(), out_rows.data_ptr(),
-            _lib.current_stream(vel.device)), "nbd_batch_invariants_f64")
+    _lib.launch("nbd_batch_invariants_f64", vel.device, *plan.head(), posm.data_ptr(), vel.data_ptr(), phi.data_ptr(),
+                out_rows.data_ptr())
     return out_rows
 
 
@@ -1257,11 +1120,9 @@ def batch_accel_jerk(plan: BatchPlan, pos, vel, mass, eps2, g, acc_out, jerk_out
     plan.check_state(posm, None, (pos, "pos"), (vel, "vel"), (mass, "mass"), (acc_out, "acc_out"),
                      (jerk_out, "jerk_out"))
     _hws(plan, hws)
-    with _lib.on_device(pos.device):
-        _lib.check(_lib.lib().nbd_batch_accel_jerk_f32(
-            *plan.head(), pos.data_ptr(), vel.data_ptr(), mass.data_ptr(), _param(eps2, plan, "softening_sq"),
-            _param(g, plan, "g_const"), acc_out.data_ptr(), jerk_out.data_ptr(), posm.data_ptr(), hws.data_ptr(),
-            _nbytes(hws), _lib.current_stream(pos.device)), "nbd_batch_accel_jerk_f32")
+    _lib.launch("nbd_batch_accel_jerk_f32", pos.device, *plan.head(), pos.data_ptr(), vel.data_ptr(), mass.data_ptr(),
+                _param(eps2, plan, "softening_sq"), _param(g, plan, "g_const"), acc_out.data_ptr(), jerk_out.data_ptr(),
+                posm.data_ptr(), hws.data_ptr(), _nbytes(hws))
 
 
 def batch_hermite_step(plan: BatchPlan, pos, vel, acc_in, jerk_in, acc_out, jerk_out, mass, hdt, eps2, g, posm,
@@ -1272,12 +1133,10 @@ def batch_hermite_step(plan: BatchPlan, pos, vel, acc_in, jerk_in, acc_out, jerk
                      (acc_out, "acc_out"), (jerk_out, "jerk_out"), (mass, "mass"))
     _chk(hdt, (5, plan.n_scenes), "hdt")
     _hws(plan, hws)
-    with _lib.on_device(pos.device):
-        _lib.check(_lib.lib().nbd_batch_hermite_step_f32(
-            *plan.head(), pos.data_ptr(), vel.data_ptr(), acc_in.data_ptr(), jerk_in.data_ptr(), acc_out.data_ptr(),
-            jerk_out.data_ptr(), mass.data_ptr(), hdt.data_ptr(), _param(eps2, plan, "softening_sq"),
-            _param(g, plan, "g_const"), posm.data_ptr(), hws.data_ptr(), _nbytes(hws), _lib.current_stream(pos.device)),
-            "nbd_batch_hermite_step_f32")
+    _lib.launch("nbd_batch_hermite_step_f32", pos.device, *plan.head(), pos.data_ptr(), vel.data_ptr(),
+                acc_in.data_ptr(), jerk_in.data_ptr(), acc_out.data_ptr(), jerk_out.data_ptr(), mass.data_ptr(),
+                hdt.data_ptr(), _param(eps2, plan, "softening_sq"), _param(g, plan, "g_const"), posm.data_ptr(),
+                hws.data_ptr(), _nbytes(hws))
 
 
 # ------------------------------------------- double-precision Hermite per scene (csrc/direct_batch_hermite_f64.hip)
@@ -1303,9 +1162,7 @@ def _chk_f64_batch(plan: BatchPlan, posd, veld, ws, params, *arrays):
         _chk(t, (n,) if nm in ("mass", "phi") else (n, 3), nm, F64)
     for t, nm in ((posd, "posd"), (veld, "veld")):
         if t is not None:
-            _chk(t, None, nm, F64)
-            if t.dim() != 2 or t.shape[1] != 4 or t.shape[0] < plan.posm_rows:
-                raise _lib.NbdError(f"{nm}: need >= {plan.posm_rows} rows of 4, got {tuple(t.shape)}")
+            _chk_min_rows(t, plan.posm_rows, 4, nm, F64)
     if ws is not None and _nbytes(ws) < plan.workspace_bytes:
         raise _lib.NbdError("batch float64 workspace too small")
     if params is not None:                 # the plan's own table: the 6th-order plan's is taller, rows 0-2 the same
@@ -1320,10 +1177,8 @@ def alloc_batch_rows_f64(plan: BatchPlan) -> torch.Tensor:
 def batch_pack_f64(plan: BatchPlan, pos, vel, mass, posd, veld) -> None:
     """posd = {x, m}, veld = {v, 0} of every scene."""
     _chk_f64_batch(plan, posd, veld, None, None, (pos, "pos"), (vel, "vel"), (mass, "mass"))
-    with _lib.on_device(pos.device):
-        _lib.check(_lib.lib().nbd_batch_pack_f64(*plan.head(), pos.data_ptr(), vel.data_ptr(), mass.data_ptr(),
-                                                 posd.data_ptr(), veld.data_ptr(), _lib.current_stream(pos.device)),
-                   "nbd_batch_pack_f64")
+    _lib.launch("nbd_batch_pack_f64", pos.device, *plan.head(), pos.data_ptr(), vel.data_ptr(), mass.data_ptr(),
+                posd.data_ptr(), veld.data_ptr())
 
 
 def batch_accel_jerk_f64(plan: BatchPlan, pos, vel, mass, params, acc_out, jerk_out, posd, veld, ws) -> None:
@@ -1331,11 +1186,9 @@ def batch_accel_jerk_f64(plan: BatchPlan, pos, vel, mass, params, acc_out, jerk_
     (BATCH_F64_PARAM_ROWS, S) as batch_f64_params forms it; ws: plan.workspace()."""
     _chk_f64_batch(plan, posd, veld, ws, params, (pos, "pos"), (vel, "vel"), (mass, "mass"), (acc_out, "acc_out"),
                    (jerk_out, "jerk_out"))
-    with _lib.on_device(pos.device):
-        _lib.check(_lib.lib().nbd_batch_accel_jerk_f64(
-            *plan.head(), pos.data_ptr(), vel.data_ptr(), mass.data_ptr(), params.data_ptr(), acc_out.data_ptr(),
-            jerk_out.data_ptr(), posd.data_ptr(), veld.data_ptr(), ws.data_ptr(), _nbytes(ws),
-            _lib.current_stream(pos.device)), "nbd_batch_accel_jerk_f64")
+    _lib.launch("nbd_batch_accel_jerk_f64", pos.device, *plan.head(), pos.data_ptr(), vel.data_ptr(), mass.data_ptr(),
+                params.data_ptr(), acc_out.data_ptr(), jerk_out.data_ptr(), posd.data_ptr(), veld.data_ptr(),
+                ws.data_ptr(), _nbytes(ws))
 
 
 def batch_hermite_step_f64(plan: BatchPlan, pos, vel, acc_in, jerk_in, acc_out, jerk_out, mass, params, posd, veld,
@@ -1344,31 +1197,25 @@ def batch_hermite_step_f64(plan: BatchPlan, pos, vel, acc_in, jerk_in, acc_out, 
     be acc_in, jerk_in); posd = {x1, m}; veld is scratch."""
     _chk_f64_batch(plan, posd, veld, ws, params, (pos, "pos"), (vel, "vel"), (acc_in, "acc_in"), (jerk_in, "jerk_in"),
                    (acc_out, "acc_out"), (jerk_out, "jerk_out"), (mass, "mass"))
-    with _lib.on_device(pos.device):
-        _lib.check(_lib.lib().nbd_batch_hermite_step_f64(
-            *plan.head(), pos.data_ptr(), vel.data_ptr(), acc_in.data_ptr(), jerk_in.data_ptr(), acc_out.data_ptr(),
-            jerk_out.data_ptr(), mass.data_ptr(), params.data_ptr(), posd.data_ptr(), veld.data_ptr(), ws.data_ptr(),
-            _nbytes(ws), _lib.current_stream(pos.device)), "nbd_batch_hermite_step_f64")
+    _lib.launch("nbd_batch_hermite_step_f64", pos.device, *plan.head(), pos.data_ptr(), vel.data_ptr(),
+                acc_in.data_ptr(), jerk_in.data_ptr(), acc_out.data_ptr(), jerk_out.data_ptr(), mass.data_ptr(),
+                params.data_ptr(), posd.data_ptr(), veld.data_ptr(), ws.data_ptr(), _nbytes(ws))
 
 
 def batch_energies_f64(plan: BatchPlan, posd, vel, params, out_uk, ws) -> torch.Tensor:
     """out_uk (S, 2) float64 = {U_s, K_s} (energy_f64 per scene, bit for bit) from posd and vel; asynchronous."""
     _chk_f64_batch(plan, posd, None, ws, params, (vel, "vel"))
     _chk(out_uk, (plan.n_scenes, 2), "out_uk", F64)
-    with _lib.on_device(vel.device):
-        _lib.check(_lib.lib().nbd_batch_energies_f64(
-            *plan.head(), posd.data_ptr(), vel.data_ptr(), params.data_ptr(), out_uk.data_ptr(), ws.data_ptr(),
-            _nbytes(ws), _lib.current_stream(vel.device)), "nbd_batch_energies_f64")
+    _lib.launch("nbd_batch_energies_f64", vel.device, *plan.head(), posd.data_ptr(), vel.data_ptr(), params.data_ptr(),
+                out_uk.data_ptr(), ws.data_ptr(), _nbytes(ws))
     return out_uk
 
 
 def batch_potential_f64(plan: BatchPlan, posd, params, phi_out, ws) -> torch.Tensor:
     """phi_out (N_total,) float64 (potential_f64 per scene, bit for bit) from posd; asynchronous."""
     _chk_f64_batch(plan, posd, None, ws, params, (phi_out, "phi"))
-    with _lib.on_device(posd.device):
-        _lib.check(_lib.lib().nbd_batch_potential_f64(
-            *plan.head(), posd.data_ptr(), params.data_ptr(), phi_out.data_ptr(), ws.data_ptr(), _nbytes(ws),
-            _lib.current_stream(posd.device)), "nbd_batch_potential_f64")
+    _lib.launch("nbd_batch_potential_f64", posd.device, *plan.head(), posd.data_ptr(), params.data_ptr(),
+                phi_out.data_ptr(), ws.data_ptr(), _nbytes(ws))
     return phi_out
 
 
@@ -1376,10 +1223,8 @@ def batch_invariants_state_f64(plan: BatchPlan, pos, vel, mass, phi, out_rows) -
     """out_rows (S, 16) float64 = invariants_state_f64 of every scene (bit for bit) from the state and phi."""
     _chk_f64_batch(plan, None, None, None, None, (pos, "pos"), (vel, "vel"), (mass, "mass"), (phi, "phi"))
     _chk(out_rows, (plan.n_scenes, INVARIANT_ROW), "out_rows", F64)
-    with _lib.on_device(vel.device):
-        _lib.check(_lib.lib().nbd_batch_invariants_state_f64(
-            *plan.head(), pos.data_ptr(), vel.data_ptr(), mass.data_ptr(), phi.data_ptr(), out_rows.data_ptr(),
-            _lib.current_stream(vel.device)), "nbd_batch_invariants_state_f64")
+    _lib.launch("nbd_batch_invariants_state_f64", vel.device, *plan.head(), pos.data_ptr(), vel.data_ptr(),
+                mass.data_ptr(), phi.data_ptr(), out_rows.data_ptr())
     return out_rows
 
 
@@ -1403,19 +1248,15 @@ def _chk_h6_batch(plan: BatchPlan, posd, veld, accd, ws, params, *arrays):
         raise _lib.NbdError("batch 6th-order call: the plan was not built for it "
                             "(BatchPlan(..., dtype=torch.float64, order=6))")
     _chk_f64_batch(plan, posd, veld, ws, params, *arrays)
-    _chk(accd, None, "accd", F64)
-    if accd.dim() != 2 or accd.shape[1] != 4 or accd.shape[0] < plan.posm_rows:
-        raise _lib.NbdError(f"accd: need >= {plan.posm_rows} rows of 4, got {tuple(accd.shape)}")
+    _chk_min_rows(accd, plan.posm_rows, 4, "accd", F64)
 
 
 def batch_hermite6_pack_f64(plan: BatchPlan, pos, vel, mass, posd, veld, accd, acc=None) -> None:
     """posd = {x, m}, veld = {v, 0}, accd = {a, 0} of every scene (acc None: zero rows)."""
     _chk_h6_batch(plan, posd, veld, accd, None, None, (pos, "pos"), (vel, "vel"), (mass, "mass"),
                   *(((acc, "acc"),) if acc is not None else ()))
-    with _lib.on_device(pos.device):
-        _lib.check(_lib.lib().nbd_batch_hermite6_pack_f64(
-            *plan.head(), pos.data_ptr(), vel.data_ptr(), _lib.ptr(acc), mass.data_ptr(), posd.data_ptr(),
-            veld.data_ptr(), accd.data_ptr(), _lib.current_stream(pos.device)), "nbd_batch_hermite6_pack_f64")
+    _lib.launch("nbd_batch_hermite6_pack_f64", pos.device, *plan.head(), pos.data_ptr(), vel.data_ptr(), _lib.ptr(acc),
+                mass.data_ptr(), posd.data_ptr(), veld.data_ptr(), accd.data_ptr())
 
 
 def batch_accel_jerk_snap_f64(plan: BatchPlan, posd, veld, accd, params, acc_out, jerk_out, snap_out, ws) -> None:
@@ -1423,11 +1264,9 @@ def batch_accel_jerk_snap_f64(plan: BatchPlan, posd, veld, accd, params, acc_out
     params: device float64 (BATCH_H6_PARAM_ROWS, S) as batch_h6_params forms it; ws: plan.workspace()."""
     _chk_h6_batch(plan, posd, veld, accd, ws, params, (acc_out, "acc_out"), (jerk_out, "jerk_out"),
                   (snap_out, "snap_out"))
-    with _lib.on_device(posd.device):
-        _lib.check(_lib.lib().nbd_batch_accel_jerk_snap_f64(
-            *plan.head(), posd.data_ptr(), veld.data_ptr(), accd.data_ptr(), params.data_ptr(), acc_out.data_ptr(),
-            jerk_out.data_ptr(), snap_out.data_ptr(), ws.data_ptr(), _nbytes(ws), _lib.current_stream(posd.device)),
-            "nbd_batch_accel_jerk_snap_f64")
+    _lib.launch("nbd_batch_accel_jerk_snap_f64", posd.device, *plan.head(), posd.data_ptr(), veld.data_ptr(),
+                accd.data_ptr(), params.data_ptr(), acc_out.data_ptr(), jerk_out.data_ptr(), snap_out.data_ptr(),
+                ws.data_ptr(), _nbytes(ws))
 
 
 def batch_hermite6_step_f64(plan: BatchPlan, pos, vel, acc_in, jerk_in, snap_in, crackle_in, acc_out, jerk_out, snap_out,
@@ -1437,9 +1276,7 @@ def batch_hermite6_step_f64(plan: BatchPlan, pos, vel, acc_in, jerk_in, snap_in,
     _chk_h6_batch(plan, posd, veld, accd, ws, params, (pos, "pos"), (vel, "vel"), (acc_in, "acc_in"),
                   (jerk_in, "jerk_in"), (snap_in, "snap_in"), (crackle_in, "crackle_in"), (acc_out, "acc_out"),
                   (jerk_out, "jerk_out"), (snap_out, "snap_out"), (crackle_out, "crackle_out"), (mass, "mass"))
-    with _lib.on_device(pos.device):
-        _lib.check(_lib.lib().nbd_batch_hermite6_step_f64(
-            *plan.head(), pos.data_ptr(), vel.data_ptr(), acc_in.data_ptr(), jerk_in.data_ptr(), snap_in.data_ptr(),
-            crackle_in.data_ptr(), acc_out.data_ptr(), jerk_out.data_ptr(), snap_out.data_ptr(), crackle_out.data_ptr(),
-            mass.data_ptr(), params.data_ptr(), posd.data_ptr(), veld.data_ptr(), accd.data_ptr(), ws.data_ptr(),
-            _nbytes(ws), _lib.current_stream(pos.device)), "nbd_batch_hermite6_step_f64")
+    _lib.launch("nbd_batch_hermite6_step_f64", pos.device, *plan.head(), pos.data_ptr(), vel.data_ptr(),
+                acc_in.data_ptr(), jerk_in.data_ptr(), snap_in.data_ptr(), crackle_in.data_ptr(), acc_out.data_ptr(),
+                jerk_out.data_ptr(), snap_out.data_ptr(), crackle_out.data_ptr(), mass.data_ptr(), params.data_ptr(),
+                posd.data_ptr(), veld.data_ptr(), accd.data_ptr(), ws.data_ptr(), _nbytes(ws))

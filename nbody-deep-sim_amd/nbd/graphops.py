@@ -109,15 +109,12 @@ def knn_graph(x: torch.Tensor, k: int, batch: torch.Tensor | None = None, loop: 
     use_hint = (hint is not None and lo is None and e > 0 and hint.shape == (2, e) and hint.dtype == torch.int64
                 and hint.is_contiguous() and hint.device == dev)
     if e:
-        with _lib.on_device(dev):
-            if use_hint:
-                _lib.check(_lib.lib().nbd_knn_graph_hint_f32(pos.data_ptr(), n, k, int(loop), None, None, None, e,
-                                                             ei.data_ptr(), hint.data_ptr(), _stream(dev)),
-                           "nbd_knn_graph_hint_f32")
-            else:
-                _lib.check(_lib.lib().nbd_knn_graph_f32(pos.data_ptr(), n, k, int(loop), _lib.ptr(lo), _lib.ptr(hi),
-                                                        _lib.ptr(off), e, ei.data_ptr(), _stream(dev)),
-                           "nbd_knn_graph_f32")
+        if use_hint:
+            _lib.launch("nbd_knn_graph_hint_f32", dev, pos.data_ptr(), n, k, int(loop), None, None, None, e,
+                        ei.data_ptr(), hint.data_ptr())
+        else:
+            _lib.launch("nbd_knn_graph_f32", dev, pos.data_ptr(), n, k, int(loop), _lib.ptr(lo), _lib.ptr(hi),
+                        _lib.ptr(off), e, ei.data_ptr())
     mark(ei, "_nbd_grouped")      # edges come out grouped by centre (row 1 ascending): csr_by_target need not check
     return ei
 
@@ -269,9 +266,7 @@ def csr_by_target(edge_index: torch.Tensor, n: int, return_tgt: bool = False):
             and edge_index.stride(1) == 1):
         # known to be grouped by ascending target (knn_graph's output, collated batches of it): one launch
         rowptr = torch.empty(n + 1, dtype=torch.int32, device=edge_index.device)
-        with _lib.on_device(edge_index.device):
-            _lib.check(_lib.lib().nbd_rowptr_sorted_i64(tgt.data_ptr(), tgt.numel(), n, rowptr.data_ptr(),
-                                                        _stream(edge_index.device)), "nbd_rowptr_sorted_i64")
+        _lib.launch("nbd_rowptr_sorted_i64", edge_index.device, tgt.data_ptr(), tgt.numel(), n, rowptr.data_ptr())
         return (rowptr, src.contiguous(), tgt.contiguous()) if return_tgt else (rowptr, src.contiguous())
     if not marked(edge_index, "_nbd_grouped") and tgt.numel() > 1 and bool((tgt[1:] < tgt[:-1]).any()):
         order = torch.sort(tgt, stable=True).indices
@@ -298,10 +293,8 @@ def csr_by_key(key: torch.Tensor, val: torch.Tensor, n: int, validate: bool = Tr
     scratch = torch.empty(max(e, 1), dtype=torch.int32, device=dev)
     out = torch.empty(max(e, 1), dtype=torch.int32, device=dev)
     bad = torch.empty(1, dtype=torch.int32, device=dev)
-    with _lib.on_device(dev):
-        _lib.check(_lib.lib().nbd_csr_by_key_i64(key.data_ptr(), val.data_ptr(), e, n, rowptr.data_ptr(),
-                                                 cursor.data_ptr(), scratch.data_ptr(), out.data_ptr(), bad.data_ptr(),
-                                                 _lib.current_stream(dev)), "nbd_csr_by_key_i64")
+    _lib.launch("nbd_csr_by_key_i64", dev, key.data_ptr(), val.data_ptr(), e, n, rowptr.data_ptr(), cursor.data_ptr(),
+                scratch.data_ptr(), out.data_ptr(), bad.data_ptr())
     if validate and int(bad.item()):      # one host sync; out-of-range keys are skipped by the kernels either way
         raise _lib.NbdError(f"csr_by_key: an index lies outside [0, {n})")
     return rowptr, out[:e]

@@ -42,11 +42,9 @@ def linear(x, w, bias=None, act=None, out=None, rowscale=None, bias_rowscale=Non
     ldy = _mat(out, "out")
     need = _lib.lib().nbd_linear_workspace_bytes(n, m, k)
     ws = torch.empty(need, dtype=torch.uint8, device=x.device) if need else None
-    with _lib.on_device(x.device):
-        _lib.check(_lib.lib().nbd_linear_f32(x.data_ptr(), ldx, w.data_ptr(), ldw, _vec(bias, m, "bias"),
-                                             _vec(rowscale, n, "rowscale"), _vec(bias_rowscale, n, "bias_rowscale"),
-                                             ACT[act], out.data_ptr(), ldy, n, m, k, _lib.ptr(ws), need,
-                                             _lib.current_stream(x.device)), "nbd_linear_f32")
+    _lib.launch("nbd_linear_f32", x.device, x.data_ptr(), ldx, w.data_ptr(), ldw, _vec(bias, m, "bias"),
+                _vec(rowscale, n, "rowscale"), _vec(bias_rowscale, n, "bias_rowscale"), ACT[act], out.data_ptr(), ldy,
+                n, m, k, _lib.ptr(ws), need)
     return out
 
 
@@ -65,10 +63,8 @@ def edgeconv_aggregate(pq, h, rowptr, src, fixed_k, aggr, out=None):
     n_edges = 0 if src is None else src.numel()
     if rowptr is None and n * fixed_k != n_edges:
         raise _lib.NbdError(f"fixed_k={fixed_k} x n={n} != {n_edges} edges")
-    with _lib.on_device(pq.device):
-        _lib.check(_lib.lib().nbd_edgeconv_aggregate_f32(pq.data_ptr(), ld, h, _lib.ptr(rowptr), _lib.ptr(src),
-                                                         fixed_k, n, AGGR[aggr], out.data_ptr(), ldo,
-                                                         _lib.current_stream(pq.device)), "nbd_edgeconv_aggregate_f32")
+    _lib.launch("nbd_edgeconv_aggregate_f32", pq.device, pq.data_ptr(), ld, h, _lib.ptr(rowptr), _lib.ptr(src), fixed_k,
+                n, AGGR[aggr], out.data_ptr(), ldo)
     return out
 
 
@@ -80,10 +76,8 @@ def edge_messages(pq, h, src, tgt):
     for t in (src, tgt):
         if t.dtype != torch.int64 or not t.is_contiguous() or t.numel() != e:
             raise _lib.NbdError("src/tgt must be contiguous int64 of equal length")
-    with _lib.on_device(pq.device):
-        _lib.check(_lib.lib().nbd_edge_messages_f32(pq.data_ptr(), ld, h, src.data_ptr(), tgt.data_ptr(), e,
-                                                    m.data_ptr(), h, _lib.current_stream(pq.device)),
-                   "nbd_edge_messages_f32")
+    _lib.launch("nbd_edge_messages_f32", pq.device, pq.data_ptr(), ld, h, src.data_ptr(), tgt.data_ptr(), e,
+                m.data_ptr(), h)
     return m
 
 
@@ -91,10 +85,8 @@ def segment_reduce(m, rowptr, n, mode, out=None):
     h = m.shape[1]
     if out is None:
         out = torch.empty((n, h), dtype=torch.float32, device=m.device)
-    with _lib.on_device(m.device):
-        _lib.check(_lib.lib().nbd_segment_reduce_f32(m.data_ptr(), _mat(m, "m") if m.shape[0] else h, h,
-                                                     rowptr.data_ptr(), n, AGGR[mode], out.data_ptr(), _mat(out, "out"),
-                                                     _lib.current_stream(m.device)), "nbd_segment_reduce_f32")
+    _lib.launch("nbd_segment_reduce_f32", m.device, m.data_ptr(), _mat(m, "m") if m.shape[0] else h, h,
+                rowptr.data_ptr(), n, AGGR[mode], out.data_ptr(), _mat(out, "out"))
     return out
 
 
@@ -104,10 +96,8 @@ def layernorm(x, gamma, beta, eps, out=None):
     if out is None:
         out = torch.empty((n, c), dtype=torch.float32, device=x.device)
     ldy = _mat(out, "out")
-    with _lib.on_device(x.device):
-        _lib.check(_lib.lib().nbd_layernorm_f32(x.data_ptr(), ldx, c, _vec(gamma, c, "gamma"), _vec(beta, c, "beta"),
-                                                float(eps), out.data_ptr(), ldy, n,
-                                                _lib.current_stream(x.device)), "nbd_layernorm_f32")
+    _lib.launch("nbd_layernorm_f32", x.device, x.data_ptr(), ldx, c, _vec(gamma, c, "gamma"), _vec(beta, c, "beta"),
+                float(eps), out.data_ptr(), ldy, n)
     return out
 
 
@@ -174,11 +164,8 @@ def ln_mlp_head(x, gamma, beta, eps, plan, out=None, kick_vel=None, kick_c=0.0):
         raise _lib.NbdError("ln_mlp_head: kick_vel must be a contiguous fp32 (n, out_dim) tensor")
     g_ptr = None if plan["folded"] else _vec(gamma, c, "gamma")
     b_ptr = None if plan["folded"] else _vec(beta, c, "beta")
-    with _lib.on_device(x.device):
-        _lib.check(_lib.lib().nbd_ln_mlp_head_f32(x.data_ptr(), ldx, c, g_ptr, b_ptr,
-                                                  float(eps), plan["n"], plan["w"], plan["b"], plan["dims"], out.data_ptr(),
-                                                  out.stride(0), _lib.ptr(kick_vel), float(kick_c), n,
-                                                  _lib.current_stream(x.device)), "nbd_ln_mlp_head_f32")
+    _lib.launch("nbd_ln_mlp_head_f32", x.device, x.data_ptr(), ldx, c, g_ptr, b_ptr, float(eps), plan["n"], plan["w"],
+                plan["b"], plan["dims"], out.data_ptr(), out.stride(0), _lib.ptr(kick_vel), float(kick_c), n)
     return out
 
 
@@ -204,12 +191,8 @@ def contconv_bin(pos, feat, rowptr, centres, d, radius_sq, out=None, node_begin=
         out = torch.empty((count, kc), dtype=torch.float32, device=feat.device)
     if out.dim() != 2 or out.shape[0] < count or out.shape[1] != kc or not out.is_contiguous():
         raise _lib.NbdError(f"A must be contiguous (>= {count}, {kc})")
-    with _lib.on_device(feat.device):
-        _lib.check(_lib.lib().nbd_contconv_bin_f32(pos.data_ptr(), feat.data_ptr(), ldf, i_ch, rowptr.data_ptr(),
-                                                   centres.data_ptr(), node_begin, count, d, float(radius_sq),
-                                                   _lib.ptr(cell_map), cells_out, out.data_ptr(),
-                                                   _lib.current_stream(feat.device)),
-                   "nbd_contconv_bin_f32")
+    _lib.launch("nbd_contconv_bin_f32", feat.device, pos.data_ptr(), feat.data_ptr(), ldf, i_ch, rowptr.data_ptr(),
+                centres.data_ptr(), node_begin, count, d, float(radius_sq), _lib.ptr(cell_map), cells_out, out.data_ptr())
     return out
 
 
@@ -222,9 +205,7 @@ def ball_to_cube(r: torch.Tensor) -> torch.Tensor:
         raise _lib.NbdError("ball_to_cube: r must be (..., 3)")
     rc = r.detach().to(torch.float32).reshape(-1, 3).contiguous()
     out = torch.empty_like(rc)
-    with _lib.on_device(rc.device):
-        _lib.check(_lib.lib().nbd_ball_to_cube_f32(rc.data_ptr(), rc.shape[0], out.data_ptr(), _lib.current_stream(rc.device)),
-                   "nbd_ball_to_cube_f32")
+    _lib.launch("nbd_ball_to_cube_f32", rc.device, rc.data_ptr(), rc.shape[0], out.data_ptr())
     return out.reshape(shape)
 
 
@@ -239,9 +220,8 @@ def trilinear_interpolate(filters: torch.Tensor, coords: torch.Tensor) -> torch.
     f = filters.detach().to(torch.float32).contiguous()
     c = coords.detach().to(torch.float32).contiguous()
     out = torch.empty((c.shape[0], i_ch, o_ch), dtype=torch.float32, device=f.device)
-    with _lib.on_device(f.device):
-        _lib.check(_lib.lib().nbd_trilinear_interpolate_f32(f.data_ptr(), d, i_ch, o_ch, c.data_ptr(), c.shape[0], out.data_ptr(),
-                                                            _lib.current_stream(f.device)), "nbd_trilinear_interpolate_f32")
+    _lib.launch("nbd_trilinear_interpolate_f32", f.device, f.data_ptr(), d, i_ch, o_ch, c.data_ptr(), c.shape[0],
+                out.data_ptr())
     return out
 
 
@@ -266,10 +246,8 @@ def contconv_shuffle_filters_kernel(filters: torch.Tensor, cells: torch.Tensor, 
     L = _lib.lib()
     ii, oo = (o_ch, i_ch) if transposed else (i_ch, o_ch)
     out = torch.empty(L.nbd_contconv_filter_floats(ii, oo, k), dtype=torch.float32, device=f.device)
-    with _lib.on_device(f.device):
-        _lib.check(L.nbd_contconv_shuffle_filters_f32(f.data_ptr(), cells.data_ptr(), k, i_ch, o_ch, int(transposed),
-                                                      out.data_ptr(), _lib.current_stream(f.device)),
-                   "nbd_contconv_shuffle_filters_f32")
+    _lib.launch("nbd_contconv_shuffle_filters_f32", f.device, f.data_ptr(), cells.data_ptr(), k, i_ch, o_ch,
+                int(transposed), out.data_ptr())
     return out
 
 
@@ -281,11 +259,9 @@ def contconv_filter_grad_full(feat, g, rowptr, pair_buf, edge_capacity: int, n_c
     out = torch.empty((d, d, d, i_ch, o_ch), dtype=torch.float32, device=feat.device)
     need = n_cells * i_ch * o_ch * 4 + L.nbd_contconv_filter_grad_workspace_bytes(n, int(n_cells), i_ch, o_ch)
     ws = _ws(need, feat.device)
-    with _lib.on_device(feat.device):
-        _lib.check(L.nbd_contconv_filter_grad_full_f32(feat.data_ptr(), ldf, i_ch, g.data_ptr(), ldg, o_ch, rowptr.data_ptr(), n,
-                                                       int(edge_capacity), pair_buf.data_ptr(), int(n_cells),
-                                                       _lib.ptr(cell_map), d * d * d, out.data_ptr(), _lib.ptr(ws), need,
-                                                       _lib.current_stream(feat.device)), "nbd_contconv_filter_grad_full_f32")
+    _lib.launch("nbd_contconv_filter_grad_full_f32", feat.device, feat.data_ptr(), ldf, i_ch, g.data_ptr(), ldg, o_ch,
+                rowptr.data_ptr(), n, int(edge_capacity), pair_buf.data_ptr(), int(n_cells), _lib.ptr(cell_map), d * d * d,
+                out.data_ptr(), _lib.ptr(ws), need)
     return out
 
 
@@ -303,10 +279,8 @@ def contconv_pairs(pos, rowptr, centres, edge_capacity: int, d: int, radius_sq: 
     L = _lib.lib()
     nbytes = L.nbd_contconv_pairs_bytes(n, int(edge_capacity), int(n_cells))
     buf = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=pos.device)
-    with _lib.on_device(pos.device):
-        _lib.check(L.nbd_contconv_pairs_f32(pos.data_ptr(), rowptr.data_ptr(), centres.data_ptr(), n, int(edge_capacity),
-                                            int(d), float(radius_sq), _lib.ptr(cell_map), int(n_cells), buf.data_ptr(),
-                                            buf.numel(), _lib.current_stream(pos.device)), "nbd_contconv_pairs_f32")
+    _lib.launch("nbd_contconv_pairs_f32", pos.device, pos.data_ptr(), rowptr.data_ptr(), centres.data_ptr(), n,
+                int(edge_capacity), int(d), float(radius_sq), _lib.ptr(cell_map), int(n_cells), buf.data_ptr(), buf.numel())
     return buf, int(edge_capacity)
 
 
@@ -333,10 +307,8 @@ def contconv_pairs_batch(pos, rowptr, centres, edge_capacity: int, radius_sq: fl
     ncs = (ctypes.c_int * k)(*[int(j[2]) for j in jobs])
     ptrs = (ctypes.c_void_p * k)(*[b.data_ptr() for b in bufs])
     sizes = (ctypes.c_size_t * k)(*[b.numel() for b in bufs])
-    with _lib.on_device(pos.device):
-        _lib.check(L.nbd_contconv_pairs_batch_f32(pos.data_ptr(), rowptr.data_ptr(), centres.data_ptr(), n, edge_capacity,
-                                                  float(radius_sq), k, ds, maps, ncs, ptrs, sizes,
-                                                  _lib.current_stream(pos.device)), "nbd_contconv_pairs_batch_f32")
+    _lib.launch("nbd_contconv_pairs_batch_f32", pos.device, pos.data_ptr(), rowptr.data_ptr(), centres.data_ptr(), n,
+                edge_capacity, float(radius_sq), k, ds, maps, ncs, ptrs, sizes)
     return [(b, edge_capacity) for b in bufs]
 
 
@@ -367,9 +339,7 @@ def contconv_pairs_jobs(pos, jobs):
         a.pair_lists, a.pair_lists_bytes = buf.data_ptr(), buf.numel()
         r2 = float(j["radius_sq"]) if r2 is None else r2
         out.append((buf, cap_e))
-    with _lib.on_device(pos.device):
-        _lib.check(L.nbd_contconv_pairs_jobs_f32(pos.data_ptr(), n, r2, len(jobs), arr, _lib.current_stream(pos.device)),
-                   "nbd_contconv_pairs_jobs_f32")
+    _lib.launch("nbd_contconv_pairs_jobs_f32", pos.device, pos.data_ptr(), n, r2, len(jobs), arr)
     return out
 
 
@@ -382,11 +352,9 @@ def contconv_filter_grad(feat, g, rowptr, pair_buf, edge_capacity: int, n_cells:
     out = torch.empty((n_cells, i_ch, o_ch), dtype=torch.float32, device=feat.device)
     need = L.nbd_contconv_filter_grad_workspace_bytes(n, int(n_cells), i_ch, o_ch)
     ws = _ws(need, feat.device)
-    with _lib.on_device(feat.device):
-        _lib.check(L.nbd_contconv_filter_grad_f32(feat.data_ptr(), ldf, i_ch, g.data_ptr(), ldg, o_ch, rowptr.data_ptr(), n,
-                                                  int(edge_capacity), pair_buf.data_ptr(), int(n_cells), out.data_ptr(),
-                                                  _lib.ptr(ws), need, _lib.current_stream(feat.device)),
-                   "nbd_contconv_filter_grad_f32")
+    _lib.launch("nbd_contconv_filter_grad_f32", feat.device, feat.data_ptr(), ldf, i_ch, g.data_ptr(), ldg, o_ch,
+                rowptr.data_ptr(), n, int(edge_capacity), pair_buf.data_ptr(), int(n_cells), out.data_ptr(), _lib.ptr(ws),
+                need)
     return out
 
 
@@ -428,20 +396,15 @@ def contconv_fused(feat, rowptr, pair_buf, edge_capacity: int, filt_shuffled, n_
         raise _lib.NbdError(f"out must be ({n}, {o_ch})")
     need = L.nbd_contconv_fused_workspace_bytes(n, n_cells, o_ch)
     ws = torch.empty(max(need, 16), dtype=torch.uint8, device=feat.device)
-    with _lib.on_device(feat.device):
-        _lib.check(L.nbd_contconv_fused_f32(feat.data_ptr(), ldf, i_ch, rowptr.data_ptr(), n, int(edge_capacity),
-                                            pair_buf.data_ptr(), filt_shuffled.data_ptr(), int(n_cells), int(o_ch),
-                                            _lib.ptr(rowscale), 1 if act == "tanh" else 0, out.data_ptr(), ldo,
-                                            ws.data_ptr(), ws.numel(), _lib.current_stream(feat.device)),
-                   "nbd_contconv_fused_f32")
+    _lib.launch("nbd_contconv_fused_f32", feat.device, feat.data_ptr(), ldf, i_ch, rowptr.data_ptr(), n,
+                int(edge_capacity), pair_buf.data_ptr(), filt_shuffled.data_ptr(), int(n_cells), int(o_ch),
+                _lib.ptr(rowscale), 1 if act == "tanh" else 0, out.data_ptr(), ldo, ws.data_ptr(), ws.numel())
     return out
 
 
 def degree_scale(rowptr, n, mode, device):
     out = torch.empty(n, dtype=torch.float32, device=device)
-    with _lib.on_device(device):
-        _lib.check(_lib.lib().nbd_degree_scale_f32(rowptr.data_ptr(), n, mode, out.data_ptr(),
-                                                   _lib.current_stream(device)), "nbd_degree_scale_f32")
+    _lib.launch("nbd_degree_scale_f32", device, rowptr.data_ptr(), n, mode, out.data_ptr())
     return out
 
 
@@ -489,9 +452,7 @@ def gnn_layer(**kw):
     a = gnn_layer_args(**kw)
     if a is None:
         return False
-    dev = kw["out"].device
-    with _lib.on_device(dev):
-        _lib.check(_lib.lib().nbd_gnn_layer_f32(ctypes.byref(a), _lib.current_stream(dev)), "nbd_gnn_layer_f32")
+    _lib.launch("nbd_gnn_layer_f32", kw["out"].device, ctypes.byref(a))
     return True
 
 
@@ -504,11 +465,8 @@ def act_bwd(dy, y, act, rowscale=None):
     """rowscale * dy * act'(y) with y the forward output (tanh: 1 - y^2)."""
     n, c = dy.shape
     g = torch.empty((n, c), dtype=torch.float32, device=dy.device)
-    with _lib.on_device(dy.device):
-        _lib.check(_lib.lib().nbd_act_bwd_f32(dy.data_ptr(), _mat(dy, "dy"), y.data_ptr() if y is not None else None,
-                                              _mat(y, "y") if y is not None else 0, ACT[act],
-                                              _vec(rowscale, n, "rowscale"), g.data_ptr(), c, n, c,
-                                              _lib.current_stream(dy.device)), "nbd_act_bwd_f32")
+    _lib.launch("nbd_act_bwd_f32", dy.device, dy.data_ptr(), _mat(dy, "dy"), y.data_ptr() if y is not None else None,
+                _mat(y, "y") if y is not None else 0, ACT[act], _vec(rowscale, n, "rowscale"), g.data_ptr(), c, n, c)
     return g
 
 
@@ -517,10 +475,8 @@ def colsum(x, rowweight=None):
     out = torch.empty(c, dtype=torch.float32, device=x.device)
     need = _lib.lib().nbd_colsum_workspace_bytes(n, c)
     ws = _ws(need, x.device)
-    with _lib.on_device(x.device):
-        _lib.check(_lib.lib().nbd_colsum_f32(x.data_ptr(), _mat(x, "x") if n else c, _vec(rowweight, n, "rowweight"),
-                                             n, c, out.data_ptr(), _lib.ptr(ws), need,
-                                             _lib.current_stream(x.device)), "nbd_colsum_f32")
+    _lib.launch("nbd_colsum_f32", x.device, x.data_ptr(), _mat(x, "x") if n else c, _vec(rowweight, n, "rowweight"), n, c,
+                out.data_ptr(), _lib.ptr(ws), need)
     return out
 
 
@@ -533,10 +489,8 @@ def linear_wgrad(g, x):
     dw = torch.empty((m, k), dtype=torch.float32, device=g.device)
     need = _lib.lib().nbd_linear_wgrad_workspace_bytes(n, m, k)
     ws = _ws(need, g.device)
-    with _lib.on_device(g.device):
-        _lib.check(_lib.lib().nbd_linear_wgrad_f32(g.data_ptr(), _mat(g, "g") if n else m, x.data_ptr(),
-                                                   _mat(x, "x") if n else k, n, m, k, dw.data_ptr(), k, _lib.ptr(ws),
-                                                   need, _lib.current_stream(g.device)), "nbd_linear_wgrad_f32")
+    _lib.launch("nbd_linear_wgrad_f32", g.device, g.data_ptr(), _mat(g, "g") if n else m, x.data_ptr(),
+                _mat(x, "x") if n else k, n, m, k, dw.data_ptr(), k, _lib.ptr(ws), need)
     return dw
 
 
@@ -550,11 +504,9 @@ def linear_wgrad_bias(g, x, rowweight=None):
     db = torch.empty(m, dtype=torch.float32, device=g.device)
     need = _lib.lib().nbd_linear_wgrad_bias_workspace_bytes(n, m, k)
     ws = _ws(need, g.device)
-    with _lib.on_device(g.device):
-        _lib.check(_lib.lib().nbd_linear_wgrad_bias_f32(g.data_ptr(), _mat(g, "g") if n else m, x.data_ptr(),
-                                                        _mat(x, "x") if n else k, _vec(rowweight, n, "rowweight"), n, m, k,
-                                                        dw.data_ptr(), k, db.data_ptr(), _lib.ptr(ws), need,
-                                                        _lib.current_stream(g.device)), "nbd_linear_wgrad_bias_f32")
+    _lib.launch("nbd_linear_wgrad_bias_f32", g.device, g.data_ptr(), _mat(g, "g") if n else m, x.data_ptr(),
+                _mat(x, "x") if n else k, _vec(rowweight, n, "rowweight"), n, m, k, dw.data_ptr(), k, db.data_ptr(),
+                _lib.ptr(ws), need)
     return dw, db
 
 
@@ -563,11 +515,9 @@ def edgeconv_aggregate_bwd(pq, h, ds, rowptr, src, fixed_k, rowptr_t, tgt_t, agg
     dpq = torch.empty((n, 2 * h), dtype=torch.float32, device=pq.device)
     if rowptr_t.dtype != torch.int32 or rowptr_t.numel() != n + 1 or tgt_t.dtype != torch.int32:
         raise _lib.NbdError("rowptr_t int32 [n+1] / tgt_t int32 required")
-    with _lib.on_device(pq.device):
-        _lib.check(_lib.lib().nbd_edgeconv_aggregate_bwd_f32(
-            pq.data_ptr(), _mat(pq, "pq"), h, ds.data_ptr(), _mat(ds, "ds"), _lib.ptr(rowptr), _lib.ptr(src), fixed_k,
-            rowptr_t.data_ptr(), _lib.ptr(tgt_t), n, AGGR[aggr], dpq.data_ptr(), 2 * h,
-            _lib.current_stream(pq.device)), "nbd_edgeconv_aggregate_bwd_f32")
+    _lib.launch("nbd_edgeconv_aggregate_bwd_f32", pq.device, pq.data_ptr(), _mat(pq, "pq"), h, ds.data_ptr(),
+                _mat(ds, "ds"), _lib.ptr(rowptr), _lib.ptr(src), fixed_k, rowptr_t.data_ptr(), _lib.ptr(tgt_t), n,
+                AGGR[aggr], dpq.data_ptr(), 2 * h)
     return dpq
 
 
@@ -578,11 +528,9 @@ def layernorm_bwd(x, gamma, eps, dy):
     db = torch.empty(c, dtype=torch.float32, device=x.device)
     need = _lib.lib().nbd_layernorm_bwd_workspace_bytes(n, c)
     ws = _ws(need, x.device)
-    with _lib.on_device(x.device):
-        _lib.check(_lib.lib().nbd_layernorm_bwd_f32(x.data_ptr(), _mat(x, "x") if n else c, c, _vec(gamma, c, "gamma"),
-                                                    float(eps), dy.data_ptr(), _mat(dy, "dy") if n else c,
-                                                    dx.data_ptr(), c, dg.data_ptr(), db.data_ptr(), n, _lib.ptr(ws),
-                                                    need, _lib.current_stream(x.device)), "nbd_layernorm_bwd_f32")
+    _lib.launch("nbd_layernorm_bwd_f32", x.device, x.data_ptr(), _mat(x, "x") if n else c, c, _vec(gamma, c, "gamma"),
+                float(eps), dy.data_ptr(), _mat(dy, "dy") if n else c, dx.data_ptr(), c, dg.data_ptr(), db.data_ptr(), n,
+                _lib.ptr(ws), need)
     return dx, dg, db
 
 
@@ -590,11 +538,8 @@ def segment_max_bwd(m, x, rowptr, dx):
     e, h = m.shape
     n = x.shape[0]
     dm = torch.empty((e, h), dtype=torch.float32, device=m.device)
-    with _lib.on_device(m.device):
-        _lib.check(_lib.lib().nbd_segment_max_bwd_f32(m.data_ptr(), _mat(m, "m") if e else h, h, x.data_ptr(),
-                                                      _mat(x, "x"), rowptr.data_ptr(), n, dx.data_ptr(), _mat(dx, "dx"),
-                                                      dm.data_ptr(), h, _lib.current_stream(m.device)),
-                   "nbd_segment_max_bwd_f32")
+    _lib.launch("nbd_segment_max_bwd_f32", m.device, m.data_ptr(), _mat(m, "m") if e else h, h, x.data_ptr(),
+                _mat(x, "x"), rowptr.data_ptr(), n, dx.data_ptr(), _mat(dx, "dx"), dm.data_ptr(), h)
     return dm
 
 
@@ -602,10 +547,8 @@ def segment_mul_bwd(m, rowptr, n, dx):
     """Gradient of the per-target product (segment_reduce mode "mul") with respect to its rows."""
     e, h = m.shape
     dm = torch.empty((e, h), dtype=torch.float32, device=m.device)
-    with _lib.on_device(m.device):
-        _lib.check(_lib.lib().nbd_segment_mul_bwd_f32(m.data_ptr(), _mat(m, "m") if e else h, h, rowptr.data_ptr(), n,
-                                                      dx.data_ptr(), _mat(dx, "dx"), dm.data_ptr(), h,
-                                                      _lib.current_stream(m.device)), "nbd_segment_mul_bwd_f32")
+    _lib.launch("nbd_segment_mul_bwd_f32", m.device, m.data_ptr(), _mat(m, "m") if e else h, h, rowptr.data_ptr(), n,
+                dx.data_ptr(), _mat(dx, "dx"), dm.data_ptr(), h)
     return dm
 
 
@@ -619,12 +562,9 @@ def batchnorm_train_fwd(x, gamma, beta, eps, act):
     mean, var, rstd = (torch.empty(c, dtype=torch.float32, device=dev) for _ in range(3))
     need = _lib.lib().nbd_batchnorm_train_workspace_bytes(n, c)
     ws = _ws(need, dev)
-    with _lib.on_device(dev):
-        _lib.check(_lib.lib().nbd_batchnorm_train_fwd_f32(x.data_ptr(), _mat(x, "x"), n, c, _vec(gamma, c, "gamma"),
-                                                          _vec(beta, c, "beta"), float(eps), ACT[act], y.data_ptr(), c,
-                                                          mean.data_ptr(), var.data_ptr(), rstd.data_ptr(),
-                                                          _lib.ptr(ws), need, _lib.current_stream(dev)),
-                   "nbd_batchnorm_train_fwd_f32")
+    _lib.launch("nbd_batchnorm_train_fwd_f32", dev, x.data_ptr(), _mat(x, "x"), n, c, _vec(gamma, c, "gamma"),
+                _vec(beta, c, "beta"), float(eps), ACT[act], y.data_ptr(), c, mean.data_ptr(), var.data_ptr(),
+                rstd.data_ptr(), _lib.ptr(ws), need)
     return y, mean, var, rstd
 
 
@@ -635,12 +575,9 @@ def batchnorm_train_bwd(x, gamma, mean, rstd, act, y, dy):
     dg, db = torch.empty(c, dtype=torch.float32, device=dev), torch.empty(c, dtype=torch.float32, device=dev)
     need = _lib.lib().nbd_batchnorm_train_workspace_bytes(n, c)
     ws = _ws(need, dev)
-    with _lib.on_device(dev):
-        _lib.check(_lib.lib().nbd_batchnorm_train_bwd_f32(x.data_ptr(), _mat(x, "x"), n, c, _vec(gamma, c, "gamma"),
-                                                          mean.data_ptr(), rstd.data_ptr(), ACT[act], y.data_ptr(),
-                                                          _mat(y, "y"), dy.data_ptr(), _mat(dy, "dy"), dx.data_ptr(), c,
-                                                          dg.data_ptr(), db.data_ptr(), _lib.ptr(ws), need,
-                                                          _lib.current_stream(dev)), "nbd_batchnorm_train_bwd_f32")
+    _lib.launch("nbd_batchnorm_train_bwd_f32", dev, x.data_ptr(), _mat(x, "x"), n, c, _vec(gamma, c, "gamma"),
+                mean.data_ptr(), rstd.data_ptr(), ACT[act], y.data_ptr(), _mat(y, "y"), dy.data_ptr(), _mat(dy, "dy"),
+                dx.data_ptr(), c, dg.data_ptr(), db.data_ptr(), _lib.ptr(ws), need)
     return dx, dg, db
 
 
@@ -655,10 +592,7 @@ def contconv_bin_bwd(pos, da, i_ch, d, radius_sq, rowptr_s=None, tgt_s=None, deg
         if t is not None and (t.dtype != torch.int32 or not t.is_contiguous()):
             raise _lib.NbdError("contconv_bin_bwd: index lists must be contiguous int32")
     dfeat = torch.empty((n, i_ch), dtype=torch.float32, device=pos.device)
-    with _lib.on_device(pos.device):
-        _lib.check(_lib.lib().nbd_contconv_bin_bwd_f32(pos.data_ptr(), da.data_ptr(), i_ch, _lib.ptr(rowptr_s),
-                                                       tgt_s.data_ptr(), _lib.ptr(deg), cap, n, d, float(radius_sq),
-                                                       _lib.ptr(cell_map), cells_out, dfeat.data_ptr(), i_ch,
-                                                       _lib.current_stream(pos.device)),
-                   "nbd_contconv_bin_bwd_f32")
+    _lib.launch("nbd_contconv_bin_bwd_f32", pos.device, pos.data_ptr(), da.data_ptr(), i_ch, _lib.ptr(rowptr_s),
+                tgt_s.data_ptr(), _lib.ptr(deg), cap, n, d, float(radius_sq), _lib.ptr(cell_map), cells_out,
+                dfeat.data_ptr(), i_ch)
     return dfeat
