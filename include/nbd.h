@@ -584,6 +584,44 @@ int nbd_hermite_shard_force_remote_f64(const double* all, int n_total, const dou
                                        double dt, void* workspace, size_t workspace_bytes, int slabs_local,
                                        int slabs_remote, nbd_stream_t stream);
 
+/* ---- 6th-order Hermite, range-sharded (csrc/direct_hermite6_shard_f64.hip): "6th-order Hermite" above for one rank of a
+ * range partition, in the form of "double-precision range-sharded Hermite step": the five entries mirror the
+ * nbd_hermite_shard_*_f64 entries in argument order and error codes, with the snap and the crackle beside the jerk. The
+ * exchanged row is 12 doubles (96 bytes), {x_p, y_p, z_p, m, vx_p, vy_p, vz_p, 0, ax_p, ay_p, az_p, 0}: ONE all-gather
+ * per step carries the three source arrays of nbd_accel_jerk_snap_f64, read by the force kernels as it lands.
+ *   send : double[send_rows][12], 32-byte aligned, the rank's own rows, zero behind n_local;
+ *          send_rows >= nbd_posm_padded_len(n_local)
+ *   all  : double[nbd_posm_padded_len(n_total)][12], 32-byte aligned, every rank's rows in global order, zero behind
+ *          n_total
+ * The force kernels fetch whole 64-row chunks: both arrays must be allocated to those padded lengths. A step is predict,
+ * (start the gather), force_local, (wait for it), force_remote = the remote block (rows [lo, lo + n_local) of `all` are
+ * never used) + one launch that adds every slab in slab order, local ones first, times G, and corrects the own rows. Any
+ * lo and n_local; n_local == 0 is a no-op returning 0; a rank that owns everything has no remote launch and gets
+ * nbd_accel_jerk_snap_f64's bits; acc_out and jerk_out of any rank are nbd_hermite_shard_force_*_f64's bits at the same
+ * slab counts. Slab arguments and the plan are those of the 4th-order entries; the workspace is (slabs_local +
+ * slabs_remote) * 9 * n_local doubles, 8-byte aligned, and may hold anything on entry. Deterministic; no atomics, no
+ * memsets, no host syncs. */
+int nbd_hermite6_shard_f64_plan(int n_total, int lo, int n_local, int* slabs_local, int* chunks_per_wave_local,
+                                int* slabs_remote, int* chunks_per_wave_remote);
+size_t nbd_hermite6_shard_f64_workspace_bytes(int n_total, int lo, int n_local, int slabs_local, int slabs_remote);
+/* send rows [0, n_local) = the state predicted over dt by the Taylor series to the crackle, with the masses (mass: the
+ * rank's n_local), rows [n_local, send_rows) = 0. jerk, snap and crackle all null: a plain pack of (pos, vel, acc), and a
+ * null acc gives a zero third quad pair; jerk, snap and crackle are given together, with acc (nbd_hermite6_f64_pack). */
+int nbd_hermite6_shard_predict_f64(const double* pos, const double* vel, const double* acc, const double* jerk,
+                                   const double* snap, const double* crackle, const double* mass, int n_local, double dt,
+                                   double* send, int send_rows, nbd_stream_t stream);
+int nbd_hermite6_shard_force_local_f64(const double* send, int n_local, double softening_sq, void* workspace,
+                                       size_t workspace_bytes, int n_total, int lo, int slabs, nbd_stream_t stream);
+/* pos non-null: the corrector -- pos, vel (n_local,3) in place from acc_in, jerk_in, snap_in, dt; acc_out, jerk_out,
+ * snap_out = a1, j1, s1 at the predicted state, crackle_out = c1 (every output may alias its input). pos null: the force
+ * on its own, acc_out, jerk_out and snap_out only (vel, the inputs, crackle_out and dt are not used). */
+int nbd_hermite6_shard_force_remote_f64(const double* all, int n_total, const double* send, int n_local, int lo,
+                                        double softening_sq, double g_const, double* pos, double* vel,
+                                        const double* acc_in, const double* jerk_in, const double* snap_in,
+                                        double* acc_out, double* jerk_out, double* snap_out, double* crackle_out,
+                                        double dt, void* workspace, size_t workspace_bytes, int slabs_local,
+                                        int slabs_remote, nbd_stream_t stream);
+
 /* ------------------------------------------------ block-timestep Hermite integrator (csrc/direct_hermite_block.hip)
  * The scheme above with individual power-of-two steps (Makino & Aarseth 1992). One output interval dt is 2^K integer
  * ticks, K = max_level in [0, 20]. Body i keeps x, v, a, j at its last correction tick ticks[i] (int32) and a level

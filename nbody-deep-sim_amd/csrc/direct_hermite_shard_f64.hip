@@ -83,26 +83,8 @@ __global__ __launch_bounds__(256) void shard_finish_f64_kernel(const double* __r
   hermite_store_force(acc_out, jerk_out, i, a1, j1);
 }
 
-// The geometry of a rank's two force launches. The local block is plan_f64(n_local); the remote block has the same target
-// groups and slabs_f64's count for its logical chunks (none, and no launch, where the rank owns every body). An explicit
-// slab count in [1, kMaxSlabs] replaces either.
-struct HShardPlanF64 { int groups, slabs_local, chunks_local, slabs_remote, chunks_remote; SrcView remote; };
-
-bool slab_arg_ok(int slabs) { return slabs >= 0 && slabs <= kMaxSlabs; }
-
-// n_local > 0; slabs_local, slabs_remote: 0 = the plan's
-HShardPlanF64 plan_hshard_f64(int n_total, int lo, int n_local, int slabs_local, int slabs_remote) {
-  HShardPlanF64 p;
-  const F64Plan local = plan_f64(n_local);
-  p.groups = local.groups;
-  p.chunks_local = local.n_chunks;
-  p.slabs_local = slabs_local ? slabs_local : local.slabs;
-  p.chunks_remote = excluded_view(n_total, lo, lo + n_local, &p.remote);
-  p.slabs_remote = p.chunks_remote == 0 ? 0 : slabs_remote ? slabs_remote : slabs_f64(p.groups, p.chunks_remote);
-  split_chunks(p.remote, p.chunks_remote, p.slabs_remote > 0 ? p.slabs_remote : 1);
-  return p;
-}
-
+// The geometry of a rank's two force launches: HShardPlanF64, plan_hshard_f64 and slab_arg_ok of hermite_f64_kernels.h
+// (shared with direct_hermite6_shard_f64.hip).
 size_t slab_doubles(int n_local) { return (size_t)AccelJerkPair::kOut * n_local; }
 
 }  // namespace

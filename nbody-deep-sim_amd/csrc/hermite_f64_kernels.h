@@ -2,7 +2,7 @@
 // shared timestep, and the diagnostics; direct_hermite_block_f64.hip: an active list of targets, block timesteps;
 // direct_hermite_shard_f64.hip: one rank's bodies of a range partition; direct_batch_hermite_f64.hip: many independent
 // systems, shared timestep per system, and their diagnostics; direct_leapfrog_f64.hip: the acceleration alone, for the
-// leapfrog and Euler steps; direct_hermite6_f64.hip and direct_batch_hermite6_f64.hip: the 6th order, with
+// leapfrog and Euler steps; direct_hermite6_f64.hip, direct_batch_hermite6_f64.hip and direct_hermite6_shard_f64.hip: the 6th order, with
 // hermite6_f64_kernels.h; direct_grad.hip and direct_hermite_grad.hip: the float64 backward kernels): the reciprocal
 // square root (rsqrt_f64), the pair functors (AccelJerkPair: acceleration plus jerk; AccelPair: its acceleration alone;
 // PotentialPair, EnergyPair: the diagnostics), the finishing sums of the diagnostics (potential_finish_f64,
@@ -251,13 +251,16 @@ struct PairStreams<Pair, decltype((void)Pair::kStreams)> { static constexpr int 
 // the 4 waves' kOut partials per lane go through LDS -- a wave's staging is free after its last chunk: its loads have
 // landed and its reads precede these writes -- and are added in wave order into dst[k * stride + t], t < n_valid.
 // A functor with kStreams = 3 (PairStreams above) streams `third` as well: two more loads per chunk, [pos | vel | third][128]
-// staging, the counted wait at six loads, masked or un-masked chunks only.
+// staging, the counted wait at six loads; with RANGE the edge chunks put three zero rows in for an excluded source.
 // Compile-time shape, the defaults = two arrays of 32-byte rows, every chunk where it lies:
 //   RQ    : 16-byte quads from one source row to the next. 2: posd and veld as above. 4: ONE array of 64-byte rows
 //           {x, y, z, m, vx, vy, vz, 0} (veld = posd + 2 quads), what a range-sharded rank sends and gathers
 //           (direct_hermite_shard_f64.hip). Lane l then brings quad l & 1 of the rows l >> 1 and 32 + (l >> 1) of the
 //           chunk, the velocity quads two further on: the chunk lands in the same [pos | vel][128] image either way, and
-//           the pair loops do not know the difference.
+//           the pair loops do not know the difference. 6 (three arrays only): ONE array of 96-byte rows
+//           {x, y, z, m | vx, vy, vz, 0 | ax, ay, az, 0} (veld = posd + 2 quads, third = posd + 4 quads), the 6th-order
+//           rank's row (direct_hermite6_shard_f64.hip): the same lane mapping at a six-quad row stride, the second piece
+//           kChunk * RQ / 2 quads on, into the same [pos | vel | third][128] image; the counted wait stays vmcnt(6).
 //   RANGE : the walk is over the view *sv (direct_kernels.h): [c_begin, c_end) are LOGICAL chunks that hop over the run of
 //           physical chunks lying wholly inside [ex_lo, ex_hi), and the (at most two) chunks that straddle an end of that
 //           range take pair<true> with the range mask: a source inside the range goes in as a zero row with an index no
@@ -270,10 +273,13 @@ __device__ __forceinline__ void walk_f64(Pair& pr, const d4* __restrict__ posd, 
                                          const d4* __restrict__ third = nullptr) {
   constexpr int kArr = PairStreams<Pair>::value;
   constexpr bool VEL = kArr >= 2;
-  static_assert(kArr >= 1 && kArr <= 3 && (kArr < 3 || (RQ == kRowQuads && !RANGE)), "three arrays: un-sharded rows only");
+  static_assert(kArr >= 1 && kArr <= 3, "one to three streamed arrays");
+  static_assert(kArr < 3 || (RQ == kRowQuads && !RANGE) || RQ == 3 * kRowQuads,
+                "three arrays: un-sharded 32-byte rows, or {pos, vel, third} rows");
   constexpr int kSrcQuads = kChunk * RQ;           // quads from one chunk to the next in memory
   constexpr int kPiece = kSrcQuads / 2;            // and from the first LDS-DMA piece of a chunk to the second
-  static_assert(RQ == kRowQuads || RQ == 2 * kRowQuads, "rows of posd / veld, or {pos, vel} rows");
+  static_assert(RQ == kRowQuads || (RQ == 2 * kRowQuads && kArr < 3) || (RQ == 3 * kRowQuads && kArr == 3),
+                "rows of posd / veld / third, {pos, vel} rows, or {pos, vel, third} rows");
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   f4* stage = &lds[wave * stage_quads_n<kArr>()];
@@ -315,7 +321,14 @@ __device__ __forceinline__ void walk_f64(Pair& pr, const d4* __restrict__ posd, 
     const int j0 = pc * kChunk;
     if constexpr (kArr == 3) {
       const d4* bb = bv + kChunk;
-      if (all_masked || pc == own_chunk) {
+      if (RANGE && (pc == sv->edge0 || pc == sv->edge1)) {
+        const d4 none = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll 2
+        for (int j = 0; j < kChunk; ++j) {
+          const bool ex = (unsigned)(j0 + j - sv->ex_lo) < (unsigned)(sv->ex_hi - sv->ex_lo);
+          pr.template pair<true>(ex ? none : bp[j], ex ? none : bv[j], ex ? none : bb[j], ex ? kNoBody : j0 + j);
+        }
+      } else if (all_masked || pc == own_chunk) {
 #pragma unroll 2
         for (int j = 0; j < kChunk; ++j) pr.template pair<true>(bp[j], bv[j], bb[j], j0 + j);
       } else {
@@ -407,5 +420,27 @@ inline F64Plan plan_f64(int n, int n_tgt) {
 }
 
 inline F64Plan plan_f64(int n) { return plan_f64(n, n); }
+
+// The geometry of a range-sharded rank's two force launches (direct_hermite_shard_f64.hip: the 4th order;
+// direct_hermite6_shard_f64.hip: the 6th). The local block is plan_f64(n_local); the remote block has the same target
+// groups and slabs_f64's count for its logical chunks (none, and no launch, where the rank owns every body). An explicit
+// slab count in [1, kMaxSlabs] replaces either. The view's chunk counts come from n_total: no logical chunk maps behind
+// the padded length of the gathered array.
+struct HShardPlanF64 { int groups, slabs_local, chunks_local, slabs_remote, chunks_remote; SrcView remote; };
+
+inline bool slab_arg_ok(int slabs) { return slabs >= 0 && slabs <= kMaxSlabs; }
+
+// n_local > 0; slabs_local, slabs_remote: 0 = the plan's
+inline HShardPlanF64 plan_hshard_f64(int n_total, int lo, int n_local, int slabs_local, int slabs_remote) {
+  HShardPlanF64 p;
+  const F64Plan local = plan_f64(n_local);
+  p.groups = local.groups;
+  p.chunks_local = local.n_chunks;
+  p.slabs_local = slabs_local ? slabs_local : local.slabs;
+  p.chunks_remote = excluded_view(n_total, lo, lo + n_local, &p.remote);
+  p.slabs_remote = p.chunks_remote == 0 ? 0 : slabs_remote ? slabs_remote : slabs_f64(p.groups, p.chunks_remote);
+  split_chunks(p.remote, p.chunks_remote, p.slabs_remote > 0 ? p.slabs_remote : 1);
+  return p;
+}
 
 }  // namespace

@@ -983,9 +983,17 @@ class Hermite6Simulator(HermiteSimulator):
     predicted state; step() rebinds them. positions, velocities and masses are float64 as for
     HermiteSimulator(dtype=torch.float64), whose compute_energies(), compute_potentials(), compute_invariants(), gather()
     and eager run() work here unchanged. The only number format is float64 (`dtype` defaults to it): the fp32 Hermite run
-    already sits on the fp32 floor at a few dozen steps, so a higher order buys nothing there. There is no range-sharded,
-    block-timestep or differentiable form; many systems stepped together, with a captured run(), are
-    BatchedSimulator(integrator="hermite6"), each scene bit-identical to this simulator on it alone."""
+    already sits on the fp32 floor at a few dozen steps, so a higher order buys nothing there. There is no block-timestep
+    or differentiable form; many systems stepped together, with a captured run(), are
+    BatchedSimulator(integrator="hermite6"), each scene bit-identical to this simulator on it alone.
+
+    With `process_group=` the bodies are range-sharded as for HermiteSimulator(dtype=torch.float64)
+    (csrc/direct_hermite6_shard_f64.hip): positions, velocities, accelerations, jerks, snaps and crackles
+    hold the rank's rows [lo, hi), `gather()` assembles any of them, and a step is predict + pack of the own bodies ->
+    ONE all-gather of 12-double rows {x_p, m, v_p, 0, a_p, 0} in flight || own x own block -> own x others block + slab
+    sum + corrector. Construction takes two exchanges (the acceleration, then the snap from it). run() is eager,
+    compute_energies() gathers the float64 state on every rank, and compute_potentials(), compute_invariants() and
+    run() with calc_invariants are refused as they are for the sharded HermiteSimulator."""
 
     def __init__(self, *, positions, velocities, masses, g_const: float = 1.0, softening: float = 0.1,
                  dt: float = 0.01, calc_energy: bool = True, device: str = None, process_group=None,
@@ -998,18 +1006,33 @@ class Hermite6Simulator(HermiteSimulator):
         if dtype is not torch.float64:
             raise ValueError(f"Hermite6Simulator: dtype must be torch.float64, got {dtype!r}: the 4th-order fp32 run "
                              "already sits on the fp32 floor, so there is no fp32 form of the 6th-order scheme")
-        if process_group is not None:
-            raise ValueError("Hermite6Simulator: there is no range-sharded 6th-order step; process_group is not "
-                             "supported")
+        if process_group is not None and not (torch.distributed.is_available() and
+                                              isinstance(process_group, torch.distributed.ProcessGroup)):
+            raise ValueError("Hermite6Simulator: process_group must be a torch.distributed process group, got "
+                             f"{type(process_group).__name__}")
         self.jerks = self.snaps = self.crackles = None
         self._fmt = _FORMATS[torch.float64]
-        self._init_state(positions, velocities, masses, g_const, softening, dt, calc_energy, device, None,
+        self._init_state(positions, velocities, masses, g_const, softening, dt, calc_energy, device, process_group,
                          calc_invariants)
-        self._fmt.hermite_scratch(self)
-        # the third source array, and one workspace for every entry: 9 doubles per body and slab, where the inherited
-        # force and the diagnostics need at most 6
-        self._accd = direct.alloc_rows_f64(self.n, self.device)
-        self._hws = direct.hermite6_workspace(max(self.n, 1), self.device)
+        if self._sharded:
+            # as _Float64.hermite_scratch's sharded half, on 12-double rows: the rank's own predicted rows (max_count of
+            # them: equal, zero-padded pieces), the gathered rows of all bodies -- both to the padded length the force
+            # kernels fetch --, the partial sums of the two force launches (9 doubles per body and slab), the gather, the
+            # rank's masses
+            part = self.part
+            self._rows_local = direct.alloc_hermite6_rows_f64(part.max_count, self.device)
+            self._rows_all = direct.alloc_hermite6_rows_f64(self.n, self.device)
+            self._hws = direct.hermite6_shard_f64_workspace(self.n, part.lo, part.n_local, self.device) \
+                if part.n_local else None
+            self._hgather = nbd_dist.RowGather(part, direct.HERMITE6_ROW, torch.float64, self.device,
+                                               self.process_group, collective=True)
+            self._mass_local = self.masses[part.lo:part.hi].contiguous()
+        else:
+            self._fmt.hermite_scratch(self)
+            # the third source array, and one workspace for every entry: 9 doubles per body and slab, where the
+            # inherited force and the diagnostics need at most 6
+            self._accd = direct.alloc_rows_f64(self.n, self.device)
+            self._hws = direct.hermite6_workspace(max(self.n, 1), self.device)
         self.accelerations, self.jerks, self.snaps = self.compute_accelerations_jerks_and_snaps()
         self.crackles = torch.zeros_like(self.snaps)
 
@@ -1018,7 +1041,8 @@ class Hermite6Simulator(HermiteSimulator):
         evaluation that takes it as the third source array,
             s_i = G sum_{j!=i} m_j s^3 (a_ij - 6 alpha v_ij + (15 alpha^2 - 3 gamma) r_ij),
             alpha = (r_ij.v_ij) s^2, gamma = (v_ij.v_ij + r_ij.a_ij) s^2, s = (|r_ij|^2 + eps^2)^(-1/2).
-        a and j are compute_accelerations_and_jerks()'s bits. Not differentiable."""
+        a and j are compute_accelerations_and_jerks()'s bits. Not differentiable. Sharded: the rank's rows, from two
+        exchanges."""
         if torch.is_grad_enabled() and (self.positions.requires_grad or self.velocities.requires_grad or
                                         self.masses.requires_grad):
             raise RuntimeError("Hermite6Simulator.compute_accelerations_jerks_and_snaps(): there is no differentiable "
@@ -1026,6 +1050,8 @@ class Hermite6Simulator(HermiteSimulator):
         if self.n == 0:
             z = torch.zeros((0, 3), dtype=torch.float64, device=self.device)
             return z, z.clone(), z.clone()
+        if self._sharded:           # two exchanges: the rows with a zero third quad pair give a, the rows with that a give s
+            return self._sharded_launches6(acc_src=self._sharded_launches6()[0])
         acc = self._fmt.accel(self)
         direct.hermite6_pack(self.positions, self.velocities, self.masses, self._posd, self._veld, self._accd, acc=acc)
         return direct.accel_jerk_snap_f64(self._posd, self._veld, self._accd, self.n, *self._fmt._scalars(self),
@@ -1036,11 +1062,48 @@ class Hermite6Simulator(HermiteSimulator):
         `crackles` rebound."""
         if self.n == 0:
             return
+        if self._sharded:
+            self.accelerations, self.jerks = self._sharded_launches(self.accelerations, self.jerks)
+            return
         cur = (self.accelerations, self.jerks, self.snaps, self.crackles)
         new = tuple(torch.empty_like(t) for t in cur)
         direct.hermite6_step_f64(self.positions, self.velocities, *cur, *new, self.masses, self.dt,
                                  *self._fmt._scalars(self), self._posd, self._veld, self._accd, self._hws)
         self.accelerations, self.jerks, self.snaps, self.crackles = new
+
+    def _sharded_launches(self, acc, jerk):
+        """HermiteSimulator's hook on the 6th-order launches: from the carried (acc, jerk) -- with `snaps` and `crackles`
+        -- one step, `snaps` and `crackles` rebound, the new (acc, jerk) returned; with None the force of the current
+        state on its own (a zero third quad pair: a and j do not read it)."""
+        if acc is None:
+            return self._sharded_launches6()[:2]
+        acc, jerk, self.snaps, self.crackles = self._sharded_launches6((acc, jerk, self.snaps, self.crackles))
+        return acc, jerk
+
+    def _sharded_launches6(self, cur=None, acc_src=None):
+        """The range-sharded launches: predict + pack of the own bodies, ONE all-gather of 12-double rows in flight
+        during the own x own block, then the own x others block, the slab sum and the corrector. cur = the carried (acc,
+        jerk, snap, crackle): a step, returns the new four. cur None: the force of the current state on its own, the
+        rows a plain pack with acc_src (or zeros) as the third quad pair; returns (acc, jerk, snap)."""
+        p, n_loc = self.part, self.part.n_local
+        new = tuple(torch.empty((n_loc, 3), dtype=torch.float64, device=self.device) for _ in range(4 if cur else 3))
+        eps2, g = self._fmt._scalars(self)
+        if cur:
+            direct.hermite6_shard_predict_f64(self.positions, self.velocities, self._mass_local, self._rows_local, *cur,
+                                              dt=self.dt)
+        else:
+            direct.hermite6_shard_predict_f64(self.positions, self.velocities, self._mass_local, self._rows_local,
+                                              acc=acc_src)
+        handle = self._hgather.start(self._rows_local, self._rows_all)
+        if n_loc:
+            direct.hermite6_shard_force_local_f64(self._rows_local, n_loc, self.n, p.lo, eps2, self._hws)
+        self._hgather.finish(handle, self._rows_all)
+        if n_loc:
+            step = dict(pos=self.positions, vel=self.velocities, acc_in=cur[0], jerk_in=cur[1], snap_in=cur[2],
+                        crackle_out=new[3], dt=self.dt) if cur else {}
+            direct.hermite6_shard_force_remote_f64(self._rows_all, self.n, self._rows_local, n_loc, p.lo, eps2, g,
+                                                   *new[:3], self._hws, **step)
+        return new
 
 
 class BlockHermiteSimulator(HermiteSimulator):

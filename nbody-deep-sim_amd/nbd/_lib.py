@@ -286,6 +286,15 @@ SIGNATURES = {
     "nbd_hermite_shard_force_remote_f64": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_double, c_double, c_void_p,
                                                    c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_void_p,
                                                    c_size_t, c_int, c_int, c_void_p]),
+    # --- 6th-order Hermite, range-sharded (csrc/direct_hermite6_shard_f64.hip)
+    "nbd_hermite6_shard_f64_plan": (c_int, [c_int, c_int, c_int, POINTER(c_int), POINTER(c_int), POINTER(c_int),
+                                            POINTER(c_int)]),
+    "nbd_hermite6_shard_f64_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
+    "nbd_hermite6_shard_predict_f64": (c_int, [c_void_p] * 7 + [c_int, c_double, c_void_p, c_int, c_void_p]),
+    "nbd_hermite6_shard_force_local_f64": (c_int, [c_void_p, c_int, c_double, c_void_p, c_size_t, c_int, c_int, c_int,
+                                                   c_void_p]),
+    "nbd_hermite6_shard_force_remote_f64": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_double, c_double] +
+                                            [c_void_p] * 9 + [c_double, c_void_p, c_size_t, c_int, c_int, c_void_p]),
     # --- block-timestep Hermite integrator (csrc/direct_hermite_block.hip)
     "nbd_hblock_workspace_bytes": (c_size_t, [c_int]),
     "nbd_hblock_init_levels": (c_int, [c_void_p, c_void_p, c_int, c_double, c_double, c_int, c_void_p, c_void_p,

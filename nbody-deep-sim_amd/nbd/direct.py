@@ -699,6 +699,83 @@ def hermite_shard_force_remote_f64(rows_all: torch.Tensor, n_total: int, send: t
                                 acc_in, jerk_in, dt, slabs_local, slabs_remote)
 
 
+# ----------------------- range-sharded 6th-order Hermite step, float64 (csrc/direct_hermite6_shard_f64.hip)
+HERMITE6_ROW = 12               # doubles per exchanged row: {x_p, y_p, z_p, m, vx_p, vy_p, vz_p, 0, ax_p, ay_p, az_p, 0}
+
+
+def alloc_hermite6_rows_f64(n: int, device) -> torch.Tensor:
+    """Zeroed (padded_len(n), 12) float64 rows of 96 bytes: a rank's send buffer, or the gathered array of all n bodies.
+    The force kernels fetch whole 64-row chunks, so both are allocated to the padded length."""
+    return torch.zeros((padded_len(n), HERMITE6_ROW), dtype=F64, device=device)
+
+
+def hermite6_shard_f64_plan(n_total: int, lo: int, n_local: int) -> dict:
+    return _plan("nbd_hermite6_shard_f64_plan", _PLAN4, n_total, lo, n_local)
+
+
+def hermite6_shard_f64_workspace(n_total: int, lo: int, n_local: int, device, slabs_local: int = 0,
+                                 slabs_remote: int = 0) -> torch.Tensor:
+    """The partial sums of a rank's two force launches, 9 doubles per body and slab; slab counts: 0 = the plan's, else
+    that many."""
+    return alloc_bytes(_lib.lib().nbd_hermite6_shard_f64_workspace_bytes(n_total, lo, n_local, int(slabs_local),
+                                                                         int(slabs_remote)), device)
+
+
+def _chk_rows6(t: torch.Tensor, n: int, name: str):
+    """An array of 12-double rows that holds at least padded_len(n) of them."""
+    _chk_min_rows(t, padded_len(n), HERMITE6_ROW, name, F64)
+
+
+def hermite6_shard_predict_f64(pos, vel, mass, send, acc=None, jerk=None, snap=None, crackle=None,
+                               dt: float = 0.0) -> None:
+    """First launch of the sharded 6th-order step: send[:n_local] = {x_p, m, v_p, 0, a_p, 0} of the rank's bodies
+    predicted over dt from (acc, jerk, snap, crackle) -- with jerk, snap and crackle all None a plain pack of (pos, vel,
+    acc), and acc None gives a zero third quad pair -- and zeros in every row behind n_local."""
+    n = pos.shape[0]
+    _chk_n3(F64, n, ("pos", "vel"), pos, vel); _chk(mass, (n,), "mass", F64)
+    _chk_rows6(send, n, "send")
+    higher = (jerk, snap, crackle)
+    if len({t is None for t in higher}) != 1 or (jerk is not None and acc is None):
+        raise _lib.NbdError("hermite6_shard_predict_f64: give acc, jerk, snap and crackle, or acc alone, or none of them")
+    for t, nm in ((acc, "acc"), (jerk, "jerk"), (snap, "snap"), (crackle, "crackle")):
+        if t is not None:
+            _chk(t, (n, 3), nm, F64)
+    _lib.launch("nbd_hermite6_shard_predict_f64", send.device, pos.data_ptr(), vel.data_ptr(), _lib.ptr(acc),
+                _lib.ptr(jerk), _lib.ptr(snap), _lib.ptr(crackle), mass.data_ptr(), n, float(dt), send.data_ptr(),
+                send.shape[0])
+
+
+def hermite6_shard_force_local_f64(send: torch.Tensor, n_local: int, n_total: int, lo: int, softening_sq: float,
+                                   workspace: torch.Tensor, slabs: int = 0) -> None:
+    """Second launch: acceleration + jerk + snap partial sums of the own bodies under the own bodies (reads `send` only,
+    so it runs while the all-gather is in flight). slabs: 0 = the plan's split of the own chunks, else that many slabs."""
+    _chk_rows6(send, n_local, "send")
+    _lib.launch("nbd_hermite6_shard_force_local_f64", send.device, send.data_ptr(), n_local, float(softening_sq),
+                workspace.data_ptr(), _nbytes(workspace), n_total, lo, int(slabs))
+
+
+def hermite6_shard_force_remote_f64(rows_all: torch.Tensor, n_total: int, send: torch.Tensor, n_local: int, lo: int,
+                                    softening_sq: float, g_const: float, acc_out: torch.Tensor, jerk_out: torch.Tensor,
+                                    snap_out: torch.Tensor, workspace: torch.Tensor, pos=None, vel=None, acc_in=None,
+                                    jerk_in=None, snap_in=None, crackle_out=None, dt: float = 0.0, slabs_local: int = 0,
+                                    slabs_remote: int = 0) -> None:
+    """Third and fourth launch: every other body of the gathered rows as a source, then a1, j1, s1 = G * sum(slabs) into
+    acc_out, jerk_out, snap_out. With pos, vel, acc_in, jerk_in, snap_in, crackle_out and dt also the corrector of the own
+    rows (pos, vel in place; every output may be its input) and c1 into crackle_out; with none of them the force on its
+    own. slabs_local: what the local call was given; slabs_remote: 0 = the plan's split of the remote chunks."""
+    _chk_rows6(rows_all, n_total, "rows_all")
+    _chk_rows6(send, n_local, "send")
+    _chk_n3(F64, n_local, ("acc_out", "jerk_out", "snap_out"), acc_out, jerk_out, snap_out)
+    _chk_together("hermite6_shard_force_remote_f64", "pos, vel, acc_in, jerk_in, snap_in and crackle_out, or none of them",
+                  F64, n_local, ("pos", "vel", "acc_in", "jerk_in", "snap_in", "crackle_out"), pos, vel, acc_in, jerk_in,
+                  snap_in, crackle_out)
+    _lib.launch("nbd_hermite6_shard_force_remote_f64", rows_all.device, rows_all.data_ptr(), n_total, send.data_ptr(),
+                n_local, lo, float(softening_sq), float(g_const), _lib.ptr(pos), _lib.ptr(vel), _lib.ptr(acc_in),
+                _lib.ptr(jerk_in), _lib.ptr(snap_in), acc_out.data_ptr(), jerk_out.data_ptr(), snap_out.data_ptr(),
+                _lib.ptr(crackle_out), float(dt), workspace.data_ptr(), _nbytes(workspace), int(slabs_local),
+                int(slabs_remote))
+
+
 # ------------------------------------------------ backward of the all-pairs acceleration (csrc/direct_grad.hip)
 def accel_vjp_workspace(n: int, device) -> torch.Tensor:
     return alloc_bytes(_lib.lib().nbd_accel_vjp_workspace_bytes(int(n)), device)

@@ -8,7 +8,11 @@ Plummer sphere and runs, per step, exactly the launches the sharded HermiteSimul
 -- with HIP-event times per phase: medians over windows, after a time-based warm-up. Writes
 profiles/r11_hermite_shard.json:   python tools/bench_hermite_shard.py [--n 65536 --world 8 --rank 3] [--big]
 --dtype float64 runs the same launches of the float64 step (csrc/direct_hermite_shard_f64.hip) against the un-sharded
-float64 kernels and writes profiles/r16_hermite_shard_f64.json:   python tools/bench_hermite_shard.py --dtype float64 --big"""
+float64 kernels and writes profiles/r16_hermite_shard_f64.json:   python tools/bench_hermite_shard.py --dtype float64 --big
+--integrator hermite6 runs the launches of the sharded Hermite6Simulator (csrc/direct_hermite6_shard_f64.hip, 12-double
+rows) against the un-sharded 6th-order kernels and writes profiles/r22_hermite6_shard.json:
+    python tools/bench_hermite_shard.py --integrator hermite6 --big
+No multi-rank transport is in any of these numbers: the all-gather is a device copy of the rank's own rows."""
 import argparse
 import json
 import os
@@ -26,7 +30,44 @@ from nbd.plummer import generate_plummer
 G, DT = 1.0, 1e-3
 
 
-class Fmt32:
+class _Fourth:
+    """What the two measurements call, on the 4th-order entries a subclass names: the carried derivatives (acc, jerk), the
+    un-sharded (force, step) calls and the three calls of a rank's step."""
+    integrator = "hermite"
+
+    @classmethod
+    def new_state(cls, n, dev):
+        return [torch.zeros((n, 3), dtype=cls.dtype, device=dev) for _ in range(2)]
+
+    @classmethod
+    def unsharded_calls(cls, n, dev, pos, vel, mass):
+        posm, velp = cls.alloc_packed(n, dev), cls.alloc_packed(n, dev)
+        hws = cls.workspace(n, dev)
+        cls.pack(pos, vel, mass, posm, velp)
+        acc, jerk = cls.new_state(n, dev)
+        return (lambda: cls.force(posm, velp, n, acc, jerk, hws),
+                lambda: cls.step(pos, vel, acc, jerk, mass, posm, velp, hws))
+
+    @classmethod
+    def pack_rows(cls, pos, vel, mass, rows):
+        cls.predict(pos, vel, mass, rows)
+
+    @classmethod
+    def predict_step(cls, pos, vel, mass, send, state):
+        cls.predict(pos, vel, mass, send, *state, DT)
+
+    @classmethod
+    def remote_force(cls, rows_all, n, send, n_loc, lo, ws, state):
+        cls.remote(rows_all, n, send, n_loc, lo, cls.eps2, G, *state, ws)
+
+    @classmethod
+    def remote_step(cls, rows_all, n, send, n_loc, lo, ws, pos, vel, state):
+        acc, jerk = state
+        cls.remote(rows_all, n, send, n_loc, lo, cls.eps2, G, acc, jerk, ws, pos=pos, vel=vel, acc_in=acc, jerk_in=jerk,
+                   dt=DT)
+
+
+class Fmt32(_Fourth):
     """The float32 entries the two measurements call; Fmt64 names the float64 ones."""
     dtype, eps2, out = torch.float32, direct.f32(0.01), "r11_hermite_shard.json"
     alloc_packed, workspace, pack = direct.alloc_posm, direct.hermite_workspace, direct.hermite_pack
@@ -43,7 +84,7 @@ class Fmt32:
         direct.hermite_step(pos, vel, acc, jerk, acc, jerk, mass, DT, Fmt32.eps2, G, posm, hws)
 
 
-class Fmt64:
+class Fmt64(_Fourth):
     dtype, eps2, out = torch.float64, 0.01, "r16_hermite_shard_f64.json"
     alloc_packed, workspace, pack = direct.alloc_rows_f64, direct.hermite_f64_workspace, direct.hermite_f64_pack
     rows, plan, shard_workspace = (direct.alloc_hermite_rows_f64, direct.hermite_shard_f64_plan,
@@ -58,6 +99,39 @@ class Fmt64:
     @staticmethod
     def step(pos, vel, acc, jerk, mass, posd, veld, hws):
         direct.hermite_step_f64(pos, vel, acc, jerk, acc, jerk, mass, DT, Fmt64.eps2, G, posd, veld, hws)
+
+
+class Fmt6(_Fourth):
+    """The 6th-order entries: float64, rows of 12 doubles, (acc, jerk, snap, crackle) carried."""
+    integrator = "hermite6"
+    dtype, eps2, out = torch.float64, 0.01, "r22_hermite6_shard.json"
+    rows, plan, shard_workspace = (direct.alloc_hermite6_rows_f64, direct.hermite6_shard_f64_plan,
+                                   direct.hermite6_shard_f64_workspace)
+    predict, local = direct.hermite6_shard_predict_f64, direct.hermite6_shard_force_local_f64
+
+    @classmethod
+    def new_state(cls, n, dev):
+        return [torch.zeros((n, 3), dtype=cls.dtype, device=dev) for _ in range(4)]
+
+    @classmethod
+    def unsharded_calls(cls, n, dev, pos, vel, mass):
+        posd, veld, accd = (direct.alloc_rows_f64(n, dev) for _ in range(3))
+        hws = direct.hermite6_workspace(n, dev)
+        state = cls.new_state(n, dev)
+        direct.hermite6_pack(pos, vel, mass, posd, veld, accd, acc=state[0])
+        return (lambda: direct.accel_jerk_snap_f64(posd, veld, accd, n, cls.eps2, G, workspace=hws),
+                lambda: direct.hermite6_step_f64(pos, vel, *state, *state, mass, DT, cls.eps2, G, posd, veld, accd, hws))
+
+    @classmethod
+    def remote_force(cls, rows_all, n, send, n_loc, lo, ws, state):
+        direct.hermite6_shard_force_remote_f64(rows_all, n, send, n_loc, lo, cls.eps2, G, *state[:3], ws)
+
+    @classmethod
+    def remote_step(cls, rows_all, n, send, n_loc, lo, ws, pos, vel, state):
+        acc, jerk, snap, crackle = state
+        direct.hermite6_shard_force_remote_f64(rows_all, n, send, n_loc, lo, cls.eps2, G, acc, jerk, snap, ws, pos=pos,
+                                               vel=vel, acc_in=acc, jerk_in=jerk, snap_in=snap, crackle_out=crackle,
+                                               dt=DT)
 
 
 FORMATS = {"float32": Fmt32, "float64": Fmt64}
@@ -90,13 +164,7 @@ def unsharded(fmt, n, dev, windows):
     (force ms, step ms)."""
     p, v, m = generate_plummer(n, seed=1234)
     pos, vel, mass = (torch.tensor(a, dtype=fmt.dtype, device=dev) for a in (p, v, m))
-    posm, velp = fmt.alloc_packed(n, dev), fmt.alloc_packed(n, dev)
-    hws = fmt.workspace(n, dev)
-    fmt.pack(pos, vel, mass, posm, velp)
-    acc = torch.zeros((n, 3), dtype=fmt.dtype, device=dev)
-    jerk = torch.zeros((n, 3), dtype=fmt.dtype, device=dev)
-    force = lambda: fmt.force(posm, velp, n, acc, jerk, hws)
-    step = lambda: fmt.step(pos, vel, acc, jerk, mass, posm, velp, hws)
+    force, step = fmt.unsharded_calls(n, dev, pos, vel, mass)
     force()
     warm(force)
     reps = max(2, min(20, int(40e-3 / (2.0e-3 * (n / 65536) ** 2))))
@@ -113,27 +181,25 @@ def rank_of(fmt, n, world, rank, dev, windows):
     p, v, m = generate_plummer(n, seed=1234)
     pos_all, vel_all, mass_all = (torch.tensor(a, dtype=fmt.dtype, device=dev) for a in (p, v, m))
     rows_all = fmt.rows(n, dev)
-    fmt.predict(pos_all, vel_all, mass_all, rows_all)               # every body's rows, as gathered
+    fmt.pack_rows(pos_all, vel_all, mass_all, rows_all)             # every body's rows, as gathered
     pos, vel = pos_all[lo:lo + n_loc].clone(), vel_all[lo:lo + n_loc].clone()
     mass = mass_all[lo:lo + n_loc].contiguous()
     send = fmt.rows(n_loc, dev)
     ws = fmt.shard_workspace(n, lo, n_loc, dev)
-    acc = torch.zeros((n_loc, 3), dtype=fmt.dtype, device=dev)
-    jerk = torch.zeros((n_loc, 3), dtype=fmt.dtype, device=dev)
-    fmt.predict(pos, vel, mass, send)
+    state = fmt.new_state(n_loc, dev)
+    fmt.pack_rows(pos, vel, mass, send)
     fmt.local(send, n_loc, n, lo, eps2, ws)
-    fmt.remote(rows_all, n, send, n_loc, lo, eps2, G, acc, jerk, ws)
+    fmt.remote_force(rows_all, n, send, n_loc, lo, ws, state)
 
     def step(ev=None):
         if ev: ev[0].record()
-        fmt.predict(pos, vel, mass, send, acc, jerk, DT)
+        fmt.predict_step(pos, vel, mass, send, state)
         if ev: ev[1].record()
         rows_all[lo:lo + n_loc].copy_(send[:n_loc])                # stands in for the all-gather's arrival
         if ev: ev[2].record()
         fmt.local(send, n_loc, n, lo, eps2, ws)
         if ev: ev[3].record()
-        fmt.remote(rows_all, n, send, n_loc, lo, eps2, G, acc, jerk, ws, pos=pos, vel=vel, acc_in=acc, jerk_in=jerk,
-                   dt=DT)
+        fmt.remote_step(rows_all, n, send, n_loc, lo, ws, pos, vel, state)
         if ev: ev[4].record()
 
     warm(step)
@@ -160,10 +226,15 @@ def main():
     ap.add_argument("--windows", type=int, default=9)
     ap.add_argument("--big", action="store_true", help="also BASELINE configs[4]'s rank shape: 65 536 of 524 288")
     ap.add_argument("--dtype", choices=sorted(FORMATS), default="float32")
+    ap.add_argument("--integrator", choices=("hermite", "hermite6"), default="hermite",
+                    help="hermite6: the 6th-order step (float64 only; --dtype is then float64)")
     ap.add_argument("--out", default=None, help="default: profiles/r11_hermite_shard.json, or "
-                                                "profiles/r16_hermite_shard_f64.json with --dtype float64")
+                                                "profiles/r16_hermite_shard_f64.json with --dtype float64, or "
+                                                "profiles/r22_hermite6_shard.json with --integrator hermite6")
     args = ap.parse_args()
-    fmt = FORMATS[args.dtype]
+    if args.integrator == "hermite6":
+        args.dtype = "float64"
+    fmt = Fmt6 if args.integrator == "hermite6" else FORMATS[args.dtype]
     out_path = args.out or os.path.join(ROOT, "profiles", fmt.out)
     dev = "cuda"
     results = []
@@ -171,7 +242,7 @@ def main():
         windows = args.windows if n == args.n else 3
         f_ms, s_ms = unsharded(fmt, n, dev, windows)
         r = rank_of(fmt, n, args.world, args.rank, dev, windows)
-        r["dtype"] = args.dtype
+        r["dtype"], r["integrator"] = args.dtype, fmt.integrator
         ph = r["phase_ms"]
         r["unsharded_force_ms"], r["unsharded_step_ms"] = f_ms, s_ms
         r["force_ratio"] = (ph["force_local"] + ph["force_remote_finish_correct"]) / (f_ms / args.world)
@@ -179,7 +250,8 @@ def main():
         results.append(r)
         print(json.dumps(r), flush=True)
     out = {"tool": "tools/bench_hermite_shard.py", "device": torch.cuda.get_device_name(0),
-           "what": "one emulated rank of the range-sharded Hermite step; force_ratio = (local + remote) / (unsharded "
+           "what": "one emulated rank of the range-sharded Hermite step, no multi-rank transport (the all-gather is a "
+                   "device copy); force_ratio = (local + remote) / (unsharded "
                    "force / world), step_ratio = rank step / (unsharded step / world), same process", "results": results}
     with open(out_path, "w") as f:
         json.dump(out, f, indent=1)
