@@ -584,7 +584,7 @@ int nbd_hermite_shard_force_remote_f64(const double* all, int n_total, const dou
                                        double dt, void* workspace, size_t workspace_bytes, int slabs_local,
                                        int slabs_remote, nbd_stream_t stream);
 
-/* ---- 6th-order Hermite, range-sharded (csrc/direct_hermite6_shard_f64.hip): "6th-order Hermite" above for one rank of a
+/* ---- 6th-order Hermite, range-sharded (csrc/direct_hermite_shard_f64.hip, with the 4th order): "6th-order Hermite" above for one rank of a
  * range partition, in the form of "double-precision range-sharded Hermite step": the five entries mirror the
  * nbd_hermite_shard_*_f64 entries in argument order and error codes, with the snap and the crackle beside the jerk. The
  * exchanged row is 12 doubles (96 bytes), {x_p, y_p, z_p, m, vx_p, vy_p, vz_p, 0, ax_p, ay_p, az_p, 0}: ONE all-gather

@@ -1,53 +1,80 @@
-// direct_hermite_shard_f64.hip -- the double-precision form of direct_hermite_shard.hip's range-sharded 4th-order Hermite
-// step, in the number format of direct_hermite_f64.hip: one rank of a torch.distributed group owns the bodies
-// [lo, lo + n_local) of n_total and needs every other rank's PREDICTED position, mass and velocity per step. C-ABI: the
-// nbd_hermite_shard_*_f64 entries of include/nbd.h; Python: galaxify.simulation.HermiteSimulator(dtype=torch.float64,
-// process_group=...).
+// direct_hermite_shard_f64.hip -- the double-precision range-sharded Hermite steps, 4th order (the form of
+// direct_hermite_shard.hip's step in the number format of direct_hermite_f64.hip) and 6th order (the sharded form of
+// direct_hermite6_f64.hip's step): one rank of a torch.distributed group owns the bodies [lo, lo + n_local) of n_total and
+// needs every other rank's PREDICTED rows per step. C-ABI: the nbd_hermite_shard_*_f64 and nbd_hermite6_shard_* entries of
+// include/nbd.h; Python: galaxify.simulation.HermiteSimulator(dtype=torch.float64, process_group=...) and
+// Hermite6Simulator(process_group=...).
 //
-// The exchanged row is 8 doubles, {x_p, y_p, z_p, m, vx_p, vy_p, vz_p, 0}, 64 bytes: ONE all-gather per step carries both
-// halves, and walk_f64 (hermite_f64_kernels.h, RQ = 4) fetches a chunk's position quads and velocity quads by LDS-DMA at
-// a four-quad row stride into the LDS image the un-sharded kernels use, so the gathered array is read as it lands (no
-// de-interleave launch) and the pair loops are the un-sharded ones. A rank's step is four launches, as in fp32:
-//   predict : hermite_predict_row<double> of the own bodies -> the send buffer, zero rows behind n_local
-//   local   : a, j partial sums of the own bodies under the own bodies (reads the send buffer only: runs while the
-//             gather is in flight); accel_jerk_f64_kernel's geometry on n_local sources
+// The exchanged row is kArr 32-byte pieces (d4), the streamed arrays side by side: ONE all-gather per step carries them
+// all, and walk_f64 (hermite_f64_kernels.h, RQ = 2 kArr) fetches a chunk's pieces by LDS-DMA at the row's stride into the
+// [array][128] LDS image the un-sharded kernels use, so the gathered array is read as it lands (no de-interleave launch)
+// and the pair loops are the un-sharded ones. A rank's step is four launches, as in fp32:
+//   predict : the predictor of the own bodies -> the send buffer, zero rows behind n_local
+//   local   : partial sums of the own bodies under the own bodies (reads the send buffer only: runs while the gather is
+//             in flight); the un-sharded pair kernel's geometry on n_local sources
 //   remote  : the same targets under all bodies of the gathered array except [lo, lo + n_local): whole source chunks
 //             inside the range are hopped over, the <= 2 chunks that straddle an end take the masked loop with the range
 //             mask (excluded_view, direct_kernels.h)
-//   finish  : slab_order_sum over the local slabs, then the remote ones, times G, and hermite_correct_row<double> of the
-//             own rows (or a1, j1 only: the force on its own)
-// Every rounded operation is hermite_f64_kernels.h's or hermite_kernels.h's: a rank that owns every body computes
-// nbd_accel_jerk_f64's bits. No atomics, no memsets, no host syncs: deterministic with a workspace that may hold anything.
+//   finish  : slab_order_sum over the local slabs, then the remote ones, times G, and the corrector of the own rows (or
+//             the force on its own)
+// What the orders differ in (Order4, Order6 below; the row kernels and the pointer lists of the entries):
+//             row, 8-byte doubles                         sums per body   predictor              finish
+//   4th : {x_p, m | v_p, 0}, 8                            a, j: 6         hermite_predict_row    hermite_correct_row
+//   6th : {x_p, m | v_p, 0 | a_p, 0}, 12                  a, j, s: 9      hermite6_predict_row   hermite6_finish_row: the
+//                                                                                                corrector and c1
+// Every rounded operation is hermite_f64_kernels.h's, hermite6_f64_kernels.h's or hermite_kernels.h's: a rank that owns
+// every body computes nbd_accel_jerk_f64's resp. nbd_accel_jerk_snap_f64's bits, and a and j of any 6th-order rank are the
+// 4th order's at the same slab counts. No atomics, no memsets, no host syncs: deterministic with a workspace that may hold
+// anything. The LDS-DMA fetch reads whole 64-row chunks: the send buffer and the gathered array are allocated to
+// nbd_posm_padded_len(rows) rows with zero rows behind the data, and the view's chunk counts come from n_total.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../../include/nbd.h"
 #include "direct_kernels.h"
+#include "hermite6_f64_kernels.h"
 #include "hermite_f64_kernels.h"
 #include "hermite_kernels.h"
 
 namespace {
 
-constexpr int kShardRowQuads = 2 * kRowQuads;      // 16-byte quads per exchanged row: {x_p, m}, {v_p, 0}
+// An order: its pair functor, the d4 pieces of an exchanged row (= the arrays the functor streams) and the functor of the
+// target whose row starts at `row`.
+struct Order4 {
+  using Pair = AccelJerkPair;
+  static constexpr int kArr = 2;                   // {x_p, m}, {v_p, 0}
+  static __device__ __forceinline__ Pair make(const d4* __restrict__ row, double eps2, int i, int n) {
+    return Pair(row[0], row[1], eps2, i, n);
+  }
+};
 
-// Acceleration + jerk partial sums of the targets tgt[0 .. n_tgt) (64-byte rows; global index tgt_off + row) under the
-// sources of the view sv on src (64-byte rows): accel_jerk_f64_kernel's geometry -- grid = (target groups of 64, slabs),
-// the view's logical chunks spread over all slabs x 4 waves to within one. RANGE: sv leaves [ex_lo, ex_hi) out (the
-// remote block: no target has a source index of its own there); else sv is the full view of src (the local block,
-// src == tgt: group g's own indices are chunk g). out: double[slab][6][n_tgt].
-template <bool RANGE>
-__global__ __launch_bounds__(64 * kWaves) void shard_accel_jerk_f64_kernel(const d4* __restrict__ src, const SrcView sv,
-                                                                           const d4* __restrict__ tgt, int n_tgt,
-                                                                           int tgt_off, double eps2, int all_masked,
-                                                                           double* __restrict__ out) {
-  __shared__ __attribute__((aligned(32))) f4 lds[kWaves * stage_quads<true>()];
+struct Order6 {
+  using Pair = AccelJerkSnapPair;
+  static constexpr int kArr = 3;                   // {x_p, m}, {v_p, 0}, {a_p, 0}
+  static __device__ __forceinline__ Pair make(const d4* __restrict__ row, double eps2, int i, int n) {
+    return Pair(row[0], row[1], row[2], eps2, i, n);
+  }
+};
+
+// The partial sums (Pair::kOut per target) of the targets tgt[0 .. n_tgt) (exchanged rows; global index tgt_off + row)
+// under the sources of the view sv on src (exchanged rows): the un-sharded pair kernel's geometry -- grid = (target groups
+// of 64, slabs), the view's logical chunks spread over all slabs x 4 waves to within one. RANGE: sv leaves [ex_lo, ex_hi)
+// out (the remote block: no target has a source index of its own there); else sv is the full view of src (the local block,
+// src == tgt: group g's own indices are chunk g). out: double[slab][kOut][n_tgt].
+template <class Order, bool RANGE>
+__global__ __launch_bounds__(64 * kWaves) void shard_pair_f64_kernel(const d4* __restrict__ src, const SrcView sv,
+                                                                     const d4* __restrict__ tgt, int n_tgt, int tgt_off,
+                                                                     double eps2, int all_masked,
+                                                                     double* __restrict__ out) {
+  using Pair = typename Order::Pair;
+  constexpr int kArr = Order::kArr;
+  __shared__ __attribute__((aligned(32))) f4 lds[kWaves * stage_quads_n<kArr>()];
   const Group64<unsigned> g(blockIdx.x, blockIdx.y, n_tgt);
   const ChunkRange c = wave_chunks(g.jw(), sv.cpw_q, sv.cpw_r);
-  const size_t row = (size_t)g.row() * 2;
-  AccelJerkPair pr(tgt[row], tgt[row + 1], eps2, tgt_off + g.i, sv.n_src);
-  walk_f64<AccelJerkPair, kShardRowQuads, RANGE>(pr, src, src + 1, c.begin, c.end, all_masked != 0,
-                                                 RANGE ? -1 : (int)blockIdx.x, lds, g.dst<AccelJerkPair>(out),
-                                                 (size_t)n_tgt, g.n_valid(), &sv);
+  Pair pr = Order::make(tgt + (size_t)g.row() * kArr, eps2, tgt_off + g.i, sv.n_src);
+  walk_f64<Pair, kArr * kRowQuads, RANGE>(pr, src, src + 1, c.begin, c.end, all_masked != 0,
+                                          RANGE ? -1 : (int)blockIdx.x, lds, g.dst<Pair>(out), (size_t)n_tgt,
+                                          g.n_valid(), &sv, kArr == 3 ? src + 2 : nullptr);
 }
 
 // rows [0, rows) of the send buffer: {x_p, m}, {v_p, 0} of the rank's bodies, zeros behind n. acc == nullptr: plain pack.
@@ -69,6 +96,25 @@ __global__ __launch_bounds__(256) void shard_predict_f64_kernel(const double* __
   send[2 * i + 1] = vp;
 }
 
+// ... and of the 6th order: {x_p, m}, {v_p, 0}, {a_p, 0}. jerk == nullptr (then snap and crackle are too): plain pack of
+// (pos, vel, acc); acc == nullptr as well: a zero third piece.
+__global__ __launch_bounds__(256) void shard6_predict_f64_kernel(const double* __restrict__ pos,
+                                                                 const double* __restrict__ vel,
+                                                                 const double* __restrict__ acc,
+                                                                 const double* __restrict__ jerk,
+                                                                 const double* __restrict__ snap,
+                                                                 const double* __restrict__ crackle,
+                                                                 const double* __restrict__ mass, int n, int rows,
+                                                                 Hermite6Step h, d4* __restrict__ send) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (size_t)rows) return;
+  d4 pm = {0.0, 0.0, 0.0, 0.0}, vp = pm, ap = pm;
+  if (i < (size_t)n) hermite6_predict_row(pos, vel, acc, jerk, snap, crackle, mass, i, h, pm, vp, ap);
+  send[3 * i] = pm;
+  send[3 * i + 1] = vp;
+  send[3 * i + 2] = ap;
+}
+
 // One thread per own body: a1, j1 = G * (the body's row of every slab in slab order, local ones first). pos == nullptr:
 // write a1, j1 only. Else hermite_correct_row (acc_in / jerk_in may alias acc_out / jerk_out: each element is read before
 // it is written, by the same thread).
@@ -83,16 +129,27 @@ __global__ __launch_bounds__(256) void shard_finish_f64_kernel(const double* __r
   hermite_store_force(acc_out, jerk_out, i, a1, j1);
 }
 
-// The geometry of a rank's two force launches: HShardPlanF64, plan_hshard_f64 and slab_arg_ok of hermite_f64_kernels.h
-// (shared with direct_hermite6_shard_f64.hip).
-size_t slab_doubles(int n_local) { return (size_t)AccelJerkPair::kOut * n_local; }
+// ... and of the 6th order: a1, j1, s1, and with pos hermite6_finish_row's corrector and c1 (the same aliasing rule).
+__global__ __launch_bounds__(256) void shard6_finish_f64_kernel(const double* __restrict__ slabs, int n_slabs, int n,
+                                                                double g, Hermite6Step h, double* pos, double* vel,
+                                                                const double* acc_in, const double* jerk_in,
+                                                                const double* snap_in, double* acc_out,
+                                                                double* jerk_out, double* snap_out,
+                                                                double* crackle_out) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (size_t)n) return;
+  hermite6_finish_row<false>(slabs, n_slabs, (size_t)n, i, i, g, h, pos, vel, acc_in, jerk_in, snap_in, acc_out,
+                             jerk_out, snap_out, crackle_out, nullptr, nullptr, i);
+}
 
-}  // namespace
+// ---- the host bodies of the entries. The geometry of a rank's two force launches is the same for both orders:
+// HShardPlanF64, plan_hshard_f64 and slab_arg_ok of hermite_f64_kernels.h.
 
-extern "C" {
+template <class Order>
+size_t slab_doubles(int n_local) { return (size_t)Order::Pair::kOut * n_local; }
 
-int nbd_hermite_shard_f64_plan(int n_total, int lo, int n_local, int* slabs_local, int* chunks_per_wave_local,
-                               int* slabs_remote, int* chunks_per_wave_remote) {
+int shard_plan(int n_total, int lo, int n_local, int* slabs_local, int* chunks_per_wave_local, int* slabs_remote,
+               int* chunks_per_wave_remote) {
   if (!shard_args_ok(n_total, lo, n_local) || n_local == 0) return NBD_E_BADARG;
   const HShardPlanF64 p = plan_hshard_f64(n_total, lo, n_local, 0, 0);
   if (slabs_local) *slabs_local = p.slabs_local;
@@ -103,11 +160,83 @@ int nbd_hermite_shard_f64_plan(int n_total, int lo, int n_local, int* slabs_loca
   return 0;
 }
 
-size_t nbd_hermite_shard_f64_workspace_bytes(int n_total, int lo, int n_local, int slabs_local, int slabs_remote) {
+template <class Order>
+size_t shard_workspace_bytes(int n_total, int lo, int n_local, int slabs_local, int slabs_remote) {
   if (!shard_args_ok(n_total, lo, n_local) || n_local == 0 || !slab_arg_ok(slabs_local) || !slab_arg_ok(slabs_remote))
     return 0;
   const HShardPlanF64 p = plan_hshard_f64(n_total, lo, n_local, slabs_local, slabs_remote);
-  return (size_t)(p.slabs_local + p.slabs_remote) * slab_doubles(n_local) * sizeof(double);
+  return (size_t)(p.slabs_local + p.slabs_remote) * slab_doubles<Order>(n_local) * sizeof(double);
+}
+
+template <class Order>
+int shard_force_local(const double* send, int n_local, double softening_sq, void* workspace, size_t workspace_bytes,
+                      int n_total, int lo, int slabs, nbd_stream_t stream) {
+  if (!shard_args_ok(n_total, lo, n_local) || !slab_arg_ok(slabs)) return NBD_E_BADARG;
+  if (n_local == 0) return 0;
+  if (!send || misaligned32(send)) return NBD_E_BADARG;
+  const HShardPlanF64 p = plan_hshard_f64(n_total, lo, n_local, slabs, 0);
+  // what this launch writes: the local slabs (the remote call checks the whole buffer)
+  if (!workspace || misaligned8(workspace) ||
+      workspace_bytes < (size_t)p.slabs_local * slab_doubles<Order>(n_local) * sizeof(double))
+    return NBD_E_WORKSPACE;
+  // the full view of the send buffer: chunks_local = ceil(n_local / 64) chunks, all within its padded rows
+  const SrcView sv = full_view(n_local, p.chunks_local, p.slabs_local);
+  const d4* s = reinterpret_cast<const d4*>(send);
+  // the rank's own block: targets and sources are the same rows, the diagonal is at j == i (offset 0)
+  shard_pair_f64_kernel<Order, false><<<dim3(p.groups, p.slabs_local), 64 * kWaves, 0, (hipStream_t)stream>>>(
+      s, sv, s, n_local, 0, softening_sq, softening_sq < kEps2MaskedF64 ? 1 : 0, static_cast<double*>(workspace));
+  return launch_status();
+}
+
+// The force part of a remote entry: the checks (state_ok: what the entry found of its own pointer list), the remote
+// block where the rank does not own every body, then finish(slabs, n_slabs, stream), the entry's finish launch.
+template <class Order, class Finish>
+int shard_force_remote(const double* all, int n_total, const double* send, int n_local, int lo, double softening_sq,
+                       bool state_ok, void* workspace, size_t workspace_bytes, int slabs_local, int slabs_remote,
+                       nbd_stream_t stream, Finish finish) {
+  if (!shard_args_ok(n_total, lo, n_local) || !slab_arg_ok(slabs_local) || !slab_arg_ok(slabs_remote))
+    return NBD_E_BADARG;
+  if (n_local == 0) return 0;
+  if (!all || !send || misaligned32(all) || misaligned32(send) || !state_ok) return NBD_E_BADARG;
+  if (!workspace || misaligned8(workspace) ||
+      workspace_bytes < shard_workspace_bytes<Order>(n_total, lo, n_local, slabs_local, slabs_remote))
+    return NBD_E_WORKSPACE;
+  const HShardPlanF64 p = plan_hshard_f64(n_total, lo, n_local, slabs_local, slabs_remote);
+  double* slabs = static_cast<double*>(workspace);
+  hipStream_t st = (hipStream_t)stream;
+  if (p.slabs_remote > 0) {
+    // the diagonal never occurs here (every j in [lo, lo + n_local) is left out); lo keeps the index meaning. The view
+    // is excluded_view(n_total, ...): its logical chunks map to physical chunks below ceil(n_total / 64)
+    shard_pair_f64_kernel<Order, true><<<dim3(p.groups, p.slabs_remote), 64 * kWaves, 0, st>>>(
+        reinterpret_cast<const d4*>(all), p.remote, reinterpret_cast<const d4*>(send), n_local, lo, softening_sq,
+        softening_sq < kEps2MaskedF64 ? 1 : 0, slabs + (size_t)p.slabs_local * slab_doubles<Order>(n_local));
+    const int rc = launch_status();
+    if (rc) return rc;
+  }
+  finish(slabs, p.slabs_local + p.slabs_remote, st);
+  return launch_status();
+}
+
+}  // namespace
+
+extern "C" {
+
+int nbd_hermite_shard_f64_plan(int n_total, int lo, int n_local, int* slabs_local, int* chunks_per_wave_local,
+                               int* slabs_remote, int* chunks_per_wave_remote) {
+  return shard_plan(n_total, lo, n_local, slabs_local, chunks_per_wave_local, slabs_remote, chunks_per_wave_remote);
+}
+
+int nbd_hermite6_shard_f64_plan(int n_total, int lo, int n_local, int* slabs_local, int* chunks_per_wave_local,
+                                int* slabs_remote, int* chunks_per_wave_remote) {
+  return shard_plan(n_total, lo, n_local, slabs_local, chunks_per_wave_local, slabs_remote, chunks_per_wave_remote);
+}
+
+size_t nbd_hermite_shard_f64_workspace_bytes(int n_total, int lo, int n_local, int slabs_local, int slabs_remote) {
+  return shard_workspace_bytes<Order4>(n_total, lo, n_local, slabs_local, slabs_remote);
+}
+
+size_t nbd_hermite6_shard_f64_workspace_bytes(int n_total, int lo, int n_local, int slabs_local, int slabs_remote) {
+  return shard_workspace_bytes<Order6>(n_total, lo, n_local, slabs_local, slabs_remote);
 }
 
 int nbd_hermite_shard_predict_f64(const double* pos, const double* vel, const double* acc, const double* jerk,
@@ -121,22 +250,27 @@ int nbd_hermite_shard_predict_f64(const double* pos, const double* vel, const do
   return launch_status();
 }
 
+int nbd_hermite6_shard_predict_f64(const double* pos, const double* vel, const double* acc, const double* jerk,
+                                   const double* snap, const double* crackle, const double* mass, int n_local, double dt,
+                                   double* send, int send_rows, nbd_stream_t stream) {
+  if (n_local < 0 || send_rows < nbd_posm_padded_len(n_local)) return NBD_E_BADARG;
+  if ((!jerk != !snap) || (!jerk != !crackle) || (jerk && !acc)) return NBD_E_BADARG;
+  if (send_rows == 0) return 0;
+  if (!send || misaligned32(send) || (n_local > 0 && (!pos || !vel || !mass))) return NBD_E_BADARG;
+  shard6_predict_f64_kernel<<<ceil_div(send_rows, 256), 256, 0, (hipStream_t)stream>>>(
+      pos, vel, acc, jerk, snap, crackle, mass, n_local, send_rows, hermite6_step_constants(dt),
+      reinterpret_cast<d4*>(send));
+  return launch_status();
+}
+
 int nbd_hermite_shard_force_local_f64(const double* send, int n_local, double softening_sq, void* workspace,
                                       size_t workspace_bytes, int n_total, int lo, int slabs, nbd_stream_t stream) {
-  if (!shard_args_ok(n_total, lo, n_local) || !slab_arg_ok(slabs)) return NBD_E_BADARG;
-  if (n_local == 0) return 0;
-  if (!send || misaligned32(send)) return NBD_E_BADARG;
-  const HShardPlanF64 p = plan_hshard_f64(n_total, lo, n_local, slabs, 0);
-  // what this launch writes: the local slabs (the remote call checks the whole buffer)
-  if (!workspace || misaligned8(workspace) ||
-      workspace_bytes < (size_t)p.slabs_local * slab_doubles(n_local) * sizeof(double))
-    return NBD_E_WORKSPACE;
-  const SrcView sv = full_view(n_local, p.chunks_local, p.slabs_local);
-  const d4* s = reinterpret_cast<const d4*>(send);
-  // the rank's own block: targets and sources are the same rows, the diagonal is at j == i (offset 0)
-  shard_accel_jerk_f64_kernel<false><<<dim3(p.groups, p.slabs_local), 64 * kWaves, 0, (hipStream_t)stream>>>(
-      s, sv, s, n_local, 0, softening_sq, softening_sq < kEps2MaskedF64 ? 1 : 0, static_cast<double*>(workspace));
-  return launch_status();
+  return shard_force_local<Order4>(send, n_local, softening_sq, workspace, workspace_bytes, n_total, lo, slabs, stream);
+}
+
+int nbd_hermite6_shard_force_local_f64(const double* send, int n_local, double softening_sq, void* workspace,
+                                       size_t workspace_bytes, int n_total, int lo, int slabs, nbd_stream_t stream) {
+  return shard_force_local<Order6>(send, n_local, softening_sq, workspace, workspace_bytes, n_total, lo, slabs, stream);
 }
 
 int nbd_hermite_shard_force_remote_f64(const double* all, int n_total, const double* send, int n_local, int lo,
@@ -144,29 +278,31 @@ int nbd_hermite_shard_force_remote_f64(const double* all, int n_total, const dou
                                        const double* acc_in, const double* jerk_in, double* acc_out, double* jerk_out,
                                        double dt, void* workspace, size_t workspace_bytes, int slabs_local,
                                        int slabs_remote, nbd_stream_t stream) {
-  if (!shard_args_ok(n_total, lo, n_local) || !slab_arg_ok(slabs_local) || !slab_arg_ok(slabs_remote))
-    return NBD_E_BADARG;
-  if (n_local == 0) return 0;
-  if (!all || !send || !acc_out || !jerk_out || misaligned32(all) || misaligned32(send)) return NBD_E_BADARG;
-  if (pos && (!vel || !acc_in || !jerk_in)) return NBD_E_BADARG;
-  if (!workspace || misaligned8(workspace) ||
-      workspace_bytes < nbd_hermite_shard_f64_workspace_bytes(n_total, lo, n_local, slabs_local, slabs_remote))
-    return NBD_E_WORKSPACE;
-  const HShardPlanF64 p = plan_hshard_f64(n_total, lo, n_local, slabs_local, slabs_remote);
-  double* slabs = static_cast<double*>(workspace);
-  hipStream_t st = (hipStream_t)stream;
-  if (p.slabs_remote > 0) {
-    // the diagonal never occurs here (every j in [lo, lo + n_local) is left out); lo keeps the index meaning
-    shard_accel_jerk_f64_kernel<true><<<dim3(p.groups, p.slabs_remote), 64 * kWaves, 0, st>>>(
-        reinterpret_cast<const d4*>(all), p.remote, reinterpret_cast<const d4*>(send), n_local, lo, softening_sq,
-        softening_sq < kEps2MaskedF64 ? 1 : 0, slabs + (size_t)p.slabs_local * slab_doubles(n_local));
-    const int rc = launch_status();
-    if (rc) return rc;
-  }
-  shard_finish_f64_kernel<<<ceil_div(n_local, HermiteFmt<double>::kSumRows), 256, 0, st>>>(
-      slabs, p.slabs_local + p.slabs_remote, n_local, g_const, hermite_step_constants<double>(dt), pos, vel, acc_in,
-      jerk_in, acc_out, jerk_out);
-  return launch_status();
+  const bool state_ok = acc_out && jerk_out && !(pos && (!vel || !acc_in || !jerk_in));
+  return shard_force_remote<Order4>(
+      all, n_total, send, n_local, lo, softening_sq, state_ok, workspace, workspace_bytes, slabs_local, slabs_remote,
+      stream, [=](const double* slabs, int n_slabs, hipStream_t st) {
+        shard_finish_f64_kernel<<<ceil_div(n_local, HermiteFmt<double>::kSumRows), 256, 0, st>>>(
+            slabs, n_slabs, n_local, g_const, hermite_step_constants<double>(dt), pos, vel, acc_in, jerk_in, acc_out,
+            jerk_out);
+      });
+}
+
+int nbd_hermite6_shard_force_remote_f64(const double* all, int n_total, const double* send, int n_local, int lo,
+                                        double softening_sq, double g_const, double* pos, double* vel,
+                                        const double* acc_in, const double* jerk_in, const double* snap_in,
+                                        double* acc_out, double* jerk_out, double* snap_out, double* crackle_out,
+                                        double dt, void* workspace, size_t workspace_bytes, int slabs_local,
+                                        int slabs_remote, nbd_stream_t stream) {
+  const bool state_ok =
+      acc_out && jerk_out && snap_out && !(pos && (!vel || !acc_in || !jerk_in || !snap_in || !crackle_out));
+  return shard_force_remote<Order6>(
+      all, n_total, send, n_local, lo, softening_sq, state_ok, workspace, workspace_bytes, slabs_local, slabs_remote,
+      stream, [=](const double* slabs, int n_slabs, hipStream_t st) {
+        shard6_finish_f64_kernel<<<ceil_div(n_local, 256), 256, 0, st>>>(
+            slabs, n_slabs, n_local, g_const, hermite6_step_constants(dt), pos, vel, acc_in, jerk_in, snap_in, acc_out,
+            jerk_out, snap_out, crackle_out);
+      });
 }
 
 }  // extern "C"

@@ -1,6 +1,6 @@
 // hermite6_f64_kernels.h -- what the 6th-order Hermite translation units share (direct_hermite6_f64.hip: one system;
-// direct_batch_hermite6_f64.hip: many independent systems, shared timestep per system; direct_hermite6_shard_f64.hip: one
-// rank's bodies of a range partition): the pair functor of the
+// direct_batch_hermite6_f64.hip: many independent systems, shared timestep per system; direct_hermite_shard_f64.hip: one
+// rank's bodies of a range partition, beside the 4th order): the pair functor of the
 // acceleration + jerk + snap evaluation (AccelJerkSnapPair), the step constants (Hermite6Step, hermite6_step_constants)
 // and the per-row bodies of the predictor and of the finishing kernel (hermite6_predict_row, hermite6_finish_row). As in
 // hermite_f64_kernels.h there is one copy of every rounded operation: a scene of a batch has the one-system step's bits
@@ -130,7 +130,7 @@ __device__ __forceinline__ void hermite6_predict_row(const double* __restrict__ 
 //   x1 = x + (v + v1) dt/2 - (a1 - a0) dt^2/10 + (j0 + j1) dt^3/120
 //   c1 = [60 (a1 - a0) - dt (36 j1 + 24 j0) + dt^2 (9 s1 - 3 s0)] / dt^3
 // with pos and vel in place and posd[r] = {x1, m}. The outputs may alias acc_in, jerk_in, snap_in: each element is read
-// before it is written, by the same thread. POSD = false (a range-sharded rank, direct_hermite6_shard_f64.hip: its packed
+// before it is written, by the same thread. POSD = false (a range-sharded rank, direct_hermite_shard_f64.hip: its packed
 // rows are rebuilt by the next predictor): posd and mass are not used.
 template <bool POSD = true>
 __device__ __forceinline__ void hermite6_finish_row(const double* __restrict__ slabs, int n_slabs, size_t n, size_t i,

@@ -1,9 +1,9 @@
 // hermite_f64_kernels.h -- what the double-precision translation units share (direct_hermite_f64.hip: all targets,
 // shared timestep, and the diagnostics; direct_hermite_block_f64.hip: an active list of targets, block timesteps;
-// direct_hermite_shard_f64.hip: one rank's bodies of a range partition; direct_batch_hermite_f64.hip: many independent
-// systems, shared timestep per system, and their diagnostics; direct_leapfrog_f64.hip: the acceleration alone, for the
-// leapfrog and Euler steps; direct_hermite6_f64.hip, direct_batch_hermite6_f64.hip and direct_hermite6_shard_f64.hip: the 6th order, with
-// hermite6_f64_kernels.h; direct_grad.hip and direct_hermite_grad.hip: the float64 backward kernels): the reciprocal
+// direct_hermite_shard_f64.hip: one rank's bodies of a range partition, 4th and 6th order;
+// direct_batch_hermite_f64.hip: many independent systems, shared timestep per system, and their diagnostics;
+// direct_leapfrog_f64.hip: the acceleration alone, for the leapfrog and Euler steps; direct_hermite6_f64.hip and
+// direct_batch_hermite6_f64.hip: the 6th order, with hermite6_f64_kernels.h; direct_grad.hip and direct_hermite_grad.hip: the float64 backward kernels): the reciprocal
 // square root (rsqrt_f64), the pair functors (AccelJerkPair: acceleration plus jerk; AccelPair: its acceleration alone;
 // PotentialPair, EnergyPair: the diagnostics), the finishing sums of the diagnostics (potential_finish_f64,
 // energy_finish_f64, F64State), the wave body that walks the source chunks with a functor (walk_f64), the prologue of a
@@ -259,7 +259,7 @@ struct PairStreams<Pair, decltype((void)Pair::kStreams)> { static constexpr int 
 //           chunk, the velocity quads two further on: the chunk lands in the same [pos | vel][128] image either way, and
 //           the pair loops do not know the difference. 6 (three arrays only): ONE array of 96-byte rows
 //           {x, y, z, m | vx, vy, vz, 0 | ax, ay, az, 0} (veld = posd + 2 quads, third = posd + 4 quads), the 6th-order
-//           rank's row (direct_hermite6_shard_f64.hip): the same lane mapping at a six-quad row stride, the second piece
+//           rank's row (the same unit): the same lane mapping at a six-quad row stride, the second piece
 //           kChunk * RQ / 2 quads on, into the same [pos | vel | third][128] image; the counted wait stays vmcnt(6).
 //   RANGE : the walk is over the view *sv (direct_kernels.h): [c_begin, c_end) are LOGICAL chunks that hop over the run of
 //           physical chunks lying wholly inside [ex_lo, ex_hi), and the (at most two) chunks that straddle an end of that
@@ -421,8 +421,8 @@ inline F64Plan plan_f64(int n, int n_tgt) {
 
 inline F64Plan plan_f64(int n) { return plan_f64(n, n); }
 
-// The geometry of a range-sharded rank's two force launches (direct_hermite_shard_f64.hip: the 4th order;
-// direct_hermite6_shard_f64.hip: the 6th). The local block is plan_f64(n_local); the remote block has the same target
+// The geometry of a range-sharded rank's two force launches (direct_hermite_shard_f64.hip, the same for the 4th and the
+// 6th order). The local block is plan_f64(n_local); the remote block has the same target
 // groups and slabs_f64's count for its logical chunks (none, and no launch, where the rank owns every body). An explicit
 // slab count in [1, kMaxSlabs] replaces either. The view's chunk counts come from n_total: no logical chunk maps behind
 // the padded length of the gathered array.

@@ -212,6 +212,21 @@ class _ChunkedRun:
             self._run_eager(steps - done, done, out)
 
 
+def _hermite_shard_scratch(s, alloc_rows, workspace, width, dtype, own_mass):
+    """The range-sharded Hermite scratch of simulator `s`, from what a number format names (its row allocator, workspace
+    function, row width and dtype): the rank's own predicted rows -- source of its local block and send buffer of the
+    gather, max_count of them so that ragged shards send equal, zero-padded pieces --, the gathered rows of all bodies,
+    the partial sums of the two force launches, the gather, and with own_mass the rank's masses (BaseSimulator's scratch
+    has them for _Float32)."""
+    part = s.part
+    s._rows_local = alloc_rows(part.max_count, s.device)
+    s._rows_all = alloc_rows(s.n, s.device)
+    s._hws = workspace(s.n, part.lo, part.n_local, s.device) if part.n_local else None
+    s._hgather = nbd_dist.RowGather(part, width, dtype, s.device, s.process_group, collective=True)
+    if own_mass:
+        s._mass_local = s.masses[part.lo:part.hi].contiguous()
+
+
 class _Float32:
     """The float32 number format: every nbd.direct call of a simulator `s` that depends on the format (the object keeps no
     state of its own). BaseSimulator uses the diagnostics, LeapFrogSimulator and EulerSimulator the scratch and the step
@@ -238,14 +253,8 @@ class _Float32:
             s._velp = direct.alloc_posm(s.n, s.device)
             s._hws = direct.hermite_workspace(max(s.n, 1), s.device)
         else:
-            # the rank's own predicted rows: source of its local block and send buffer of the gather (max_count rows so
-            # that ragged shards send equal, zero-padded pieces); the gathered rows of all bodies; the partial sums
-            part = s.part
-            s._rows_local = direct.alloc_hermite_rows(part.max_count, s.device)
-            s._rows_all = direct.alloc_hermite_rows(s.n, s.device)
-            s._hws = direct.hermite_shard_workspace(s.n, part.lo, part.n_local, s.device) if part.n_local else None
-            s._hgather = nbd_dist.RowGather(part, direct.HERMITE_ROW, torch.float32, s.device, s.process_group,
-                                            collective=True)
+            _hermite_shard_scratch(s, direct.alloc_hermite_rows, direct.hermite_shard_workspace, direct.HERMITE_ROW,
+                                   self.dtype, own_mass=False)
 
     def _base_scratch(self, s):
         """BaseSimulator's scratch (LeapFrogSimulator, EulerSimulator) and the first force."""
@@ -293,19 +302,23 @@ class _Float32:
     def invariants(self, s, phi, out=None):
         return direct.invariants(s._posm, s.velocities, phi, s.n, out=out)
 
-    # the range-sharded step's three calls on the scratch of hermite_scratch (HermiteSimulator._sharded_launches); the
+    # the range-sharded step's three calls on the scratch of hermite_scratch (HermiteSimulator._sharded_launches; carried
+    # = the carried derivatives or None, new = the outputs, `_shard_force_outputs` of them for the force on its own); the
     # wrappers are looked up on nbd.direct when a call is made
-    def _shard_predict(self, s, acc, jerk):
+    _shard_force_outputs = 2        # a, j
+
+    def _shard_predict(self, s, carried):
+        acc, jerk = carried or (None, None)
         direct.hermite_shard_predict(s.positions, s.velocities, s._mass_local, s._rows_local, acc, jerk, s.dt)
 
     def _shard_local(self, s):
         p = s.part
         direct.hermite_shard_force_local(s._rows_local, p.n_local, s.n, p.lo, s._eps2, s._hws)
 
-    def _shard_remote(self, s, new_acc, new_jerk, **step):
+    def _shard_remote(self, s, carried, new, **step):
         p = s.part
-        direct.hermite_shard_force_remote(s._rows_all, s.n, s._rows_local, p.n_local, p.lo, s._eps2, s._g, new_acc,
-                                          new_jerk, s._hws, **step)
+        direct.hermite_shard_force_remote(s._rows_all, s.n, s._rows_local, p.n_local, p.lo, s._eps2, s._g, *new,
+                                          s._hws, **step)
 
     block_workspace = staticmethod(direct.hblock_workspace)
     block_init_levels = staticmethod(direct.hblock_init_levels)
@@ -339,15 +352,11 @@ class _Float64:
             s._posd, s._veld = direct.alloc_rows_f64(s.n, s.device), direct.alloc_rows_f64(s.n, s.device)
             s._hws = direct.hermite_f64_workspace(max(s.n, 1), s.device)
         else:
-            # as _Float32's: the rank's own predicted rows (max_count of them: equal, zero-padded pieces), the gathered
-            # rows of all bodies, the partial sums of the two force launches, the gather, the rank's masses
-            part = s.part
-            s._rows_local = direct.alloc_hermite_rows_f64(part.max_count, s.device)
-            s._rows_all = direct.alloc_hermite_rows_f64(s.n, s.device)
-            s._hws = direct.hermite_shard_f64_workspace(s.n, part.lo, part.n_local, s.device) if part.n_local else None
-            s._hgather = nbd_dist.RowGather(part, direct.HERMITE_ROW, torch.float64, s.device, s.process_group,
-                                            collective=True)
-            s._mass_local = s.masses[part.lo:part.hi].contiguous()
+            self._shard_scratch(s)
+
+    def _shard_scratch(self, s):
+        _hermite_shard_scratch(s, direct.alloc_hermite_rows_f64, direct.hermite_shard_f64_workspace, direct.HERMITE_ROW,
+                               self.dtype, own_mass=True)
 
     def pack(self, s):
         if not s._sharded:          # (sharded, only the energies read packed rows of all bodies: they pack them)
@@ -397,17 +406,20 @@ class _Float64:
     def invariants(self, s, phi, out=None):
         return direct.invariants_state_f64(s.positions, s.velocities, s.masses, phi, out=out)
 
-    def _shard_predict(self, s, acc, jerk):
+    _shard_force_outputs = 2        # a, j
+
+    def _shard_predict(self, s, carried):
+        acc, jerk = carried or (None, None)
         direct.hermite_shard_predict_f64(s.positions, s.velocities, s._mass_local, s._rows_local, acc, jerk, s.dt)
 
     def _shard_local(self, s):
         p = s.part
         direct.hermite_shard_force_local_f64(s._rows_local, p.n_local, s.n, p.lo, self._scalars(s)[0], s._hws)
 
-    def _shard_remote(self, s, new_acc, new_jerk, **step):
+    def _shard_remote(self, s, carried, new, **step):
         p = s.part
         direct.hermite_shard_force_remote_f64(s._rows_all, s.n, s._rows_local, p.n_local, p.lo, *self._scalars(s),
-                                              new_acc, new_jerk, s._hws, **step)
+                                              *new, s._hws, **step)
 
     block_workspace = staticmethod(direct.hblock_f64_workspace)
     block_init_levels = staticmethod(direct.hblock_init_levels_f64)
@@ -416,7 +428,46 @@ class _Float64:
         direct.hblock_step_f64(*state, *self._scalars(s), s._sched, s._posd, s._veld, s._bws)
 
 
+class _Hermite6Float64(_Float64):
+    """The number format of Hermite6Simulator: `_Float64` with the calls that differ for the 6th order
+    (csrc/direct_hermite6_f64.hip; sharded, the 6th-order entries of csrc/direct_hermite_shard_f64.hip). Un-sharded, a
+    third source array `s._accd` = {ax, ay, az, 0} and one workspace for every entry: 9 doubles per body and slab, where
+    the inherited force and the diagnostics need at most 6. Sharded, 12-double rows {x_p, m, v_p, 0, a_p, 0}, 9 doubles per
+    body and slab, the snap as a third output and the crackle as the fourth of a step."""
+
+    def hermite_scratch(self, s):
+        super().hermite_scratch(s)
+        if not s._sharded:
+            s._accd = direct.alloc_rows_f64(s.n, s.device)
+            s._hws = direct.hermite6_workspace(max(s.n, 1), s.device)
+
+    def _shard_scratch(self, s):
+        _hermite_shard_scratch(s, direct.alloc_hermite6_rows_f64, direct.hermite6_shard_f64_workspace,
+                               direct.HERMITE6_ROW, self.dtype, own_mass=True)
+
+    _shard_force_outputs = 3        # a, j, s
+
+    def _shard_predict(self, s, carried, acc=None):
+        """carried None: a plain pack, with `acc` (or zeros) as the third quad pair."""
+        if carried:
+            direct.hermite6_shard_predict_f64(s.positions, s.velocities, s._mass_local, s._rows_local, *carried, dt=s.dt)
+        else:
+            direct.hermite6_shard_predict_f64(s.positions, s.velocities, s._mass_local, s._rows_local, acc=acc)
+
+    def _shard_local(self, s):
+        p = s.part
+        direct.hermite6_shard_force_local_f64(s._rows_local, p.n_local, s.n, p.lo, self._scalars(s)[0], s._hws)
+
+    def _shard_remote(self, s, carried, new, **step):
+        p = s.part
+        if carried:
+            step.update(snap_in=carried[2], crackle_out=new[3])
+        direct.hermite6_shard_force_remote_f64(s._rows_all, s.n, s._rows_local, p.n_local, p.lo, *self._scalars(s),
+                                               *new[:3], s._hws, **step)
+
+
 _FORMATS = {fmt.dtype: fmt for fmt in (_Float32(), _Float64())}
+_HERMITE6 = _Hermite6Float64()
 
 
 class BaseSimulator(_ChunkedRun):
@@ -924,33 +975,35 @@ class HermiteSimulator(BaseSimulator):
             from nbd.autograd import direct_accel_jerk
             return direct_accel_jerk(self.positions, self.velocities, self.masses, self.g_const, self.softening)
         if self._sharded:
-            return self._sharded_launches(None, None)
+            return self._sharded_launches()[:2]       # (the 6th-order format's force has the snap behind them)
         return self._fmt.accel_jerk(self)
 
-    def _sharded_launches(self, acc, jerk):
-        """The range-sharded launches from the carried (acc, jerk): predict + pack of the own bodies, the all-gather in
-        flight during the own x own block, then the own x others block, the slab sum and the corrector; returns the new
-        (acc, jerk). With acc and jerk None the force of the current state on its own (a plain pack, no corrector)."""
+    def _sharded_launches(self, carried=None, **pack):
+        """The range-sharded launches from the carried derivatives, (acc, jerk) or the format's longer tuple: predict +
+        pack of the own bodies, ONE all-gather in flight during the own x own block, then the own x others block, the
+        slab sum and the corrector; returns as many new (n_local,3) tensors. With carried None the force of the current
+        state on its own (a plain pack -- `pack` goes to the format's predictor --, no corrector): the format's
+        `_shard_force_outputs` tensors."""
         fmt, n_loc = self._fmt, self.part.n_local
-        new_acc = torch.empty((n_loc, 3), dtype=fmt.dtype, device=self.device)
-        new_jerk = torch.empty((n_loc, 3), dtype=fmt.dtype, device=self.device)
-        fmt._shard_predict(self, acc, jerk)
+        new = tuple(torch.empty((n_loc, 3), dtype=fmt.dtype, device=self.device)
+                    for _ in range(len(carried) if carried else fmt._shard_force_outputs))
+        fmt._shard_predict(self, carried, **pack)
         handle = self._hgather.start(self._rows_local, self._rows_all)
         if n_loc:
             fmt._shard_local(self)
         self._hgather.finish(handle, self._rows_all)
         if n_loc:
-            step = {} if acc is None else dict(pos=self.positions, vel=self.velocities, acc_in=acc, jerk_in=jerk,
-                                               dt=self.dt)
-            fmt._shard_remote(self, new_acc, new_jerk, **step)
-        return new_acc, new_jerk
+            step = dict(pos=self.positions, vel=self.velocities, acc_in=carried[0], jerk_in=carried[1],
+                        dt=self.dt) if carried else {}
+            fmt._shard_remote(self, carried, new, **step)
+        return new
 
     def step(self):
         """One predictor-corrector step: positions and velocities in place, `accelerations` and `jerks` rebound."""
         if self.n == 0:
             return
         if self._sharded:
-            self.accelerations, self.jerks = self._sharded_launches(self.accelerations, self.jerks)
+            self.accelerations, self.jerks = self._sharded_launches((self.accelerations, self.jerks))
             return
         new_acc = torch.empty_like(self.accelerations)
         new_jerk = torch.empty_like(self.jerks)
@@ -988,10 +1041,11 @@ class Hermite6Simulator(HermiteSimulator):
     BatchedSimulator(integrator="hermite6"), each scene bit-identical to this simulator on it alone.
 
     With `process_group=` the bodies are range-sharded as for HermiteSimulator(dtype=torch.float64)
-    (csrc/direct_hermite6_shard_f64.hip): positions, velocities, accelerations, jerks, snaps and crackles
-    hold the rank's rows [lo, hi), `gather()` assembles any of them, and a step is predict + pack of the own bodies ->
-    ONE all-gather of 12-double rows {x_p, m, v_p, 0, a_p, 0} in flight || own x own block -> own x others block + slab
-    sum + corrector. Construction takes two exchanges (the acceleration, then the snap from it). run() is eager,
+    (the 6th-order entries of csrc/direct_hermite_shard_f64.hip): positions, velocities, accelerations,
+    jerks, snaps and crackles hold the rank's rows [lo, hi), `gather()` assembles any of them, and a step is
+    HermiteSimulator's sequence through the 6th-order format object: predict + pack of the own bodies -> ONE all-gather of
+    12-double rows {x_p, m, v_p, 0, a_p, 0} in flight || own x own block -> own x others block + slab sum + corrector.
+    Construction takes two exchanges (the acceleration, then the snap from it). run() is eager,
     compute_energies() gathers the float64 state on every rank, and compute_potentials(), compute_invariants() and
     run() with calc_invariants are refused as they are for the sharded HermiteSimulator."""
 
@@ -1011,28 +1065,10 @@ class Hermite6Simulator(HermiteSimulator):
             raise ValueError("Hermite6Simulator: process_group must be a torch.distributed process group, got "
                              f"{type(process_group).__name__}")
         self.jerks = self.snaps = self.crackles = None
-        self._fmt = _FORMATS[torch.float64]
+        self._fmt = _HERMITE6                # the only place the format is chosen
         self._init_state(positions, velocities, masses, g_const, softening, dt, calc_energy, device, process_group,
                          calc_invariants)
-        if self._sharded:
-            # as _Float64.hermite_scratch's sharded half, on 12-double rows: the rank's own predicted rows (max_count of
-            # them: equal, zero-padded pieces), the gathered rows of all bodies -- both to the padded length the force
-            # kernels fetch --, the partial sums of the two force launches (9 doubles per body and slab), the gather, the
-            # rank's masses
-            part = self.part
-            self._rows_local = direct.alloc_hermite6_rows_f64(part.max_count, self.device)
-            self._rows_all = direct.alloc_hermite6_rows_f64(self.n, self.device)
-            self._hws = direct.hermite6_shard_f64_workspace(self.n, part.lo, part.n_local, self.device) \
-                if part.n_local else None
-            self._hgather = nbd_dist.RowGather(part, direct.HERMITE6_ROW, torch.float64, self.device,
-                                               self.process_group, collective=True)
-            self._mass_local = self.masses[part.lo:part.hi].contiguous()
-        else:
-            self._fmt.hermite_scratch(self)
-            # the third source array, and one workspace for every entry: 9 doubles per body and slab, where the
-            # inherited force and the diagnostics need at most 6
-            self._accd = direct.alloc_rows_f64(self.n, self.device)
-            self._hws = direct.hermite6_workspace(max(self.n, 1), self.device)
+        self._fmt.hermite_scratch(self)
         self.accelerations, self.jerks, self.snaps = self.compute_accelerations_jerks_and_snaps()
         self.crackles = torch.zeros_like(self.snaps)
 
@@ -1051,7 +1087,7 @@ class Hermite6Simulator(HermiteSimulator):
             z = torch.zeros((0, 3), dtype=torch.float64, device=self.device)
             return z, z.clone(), z.clone()
         if self._sharded:           # two exchanges: the rows with a zero third quad pair give a, the rows with that a give s
-            return self._sharded_launches6(acc_src=self._sharded_launches6()[0])
+            return self._sharded_launches(acc=self._sharded_launches()[0])
         acc = self._fmt.accel(self)
         direct.hermite6_pack(self.positions, self.velocities, self.masses, self._posd, self._veld, self._accd, acc=acc)
         return direct.accel_jerk_snap_f64(self._posd, self._veld, self._accd, self.n, *self._fmt._scalars(self),
@@ -1062,48 +1098,14 @@ class Hermite6Simulator(HermiteSimulator):
         `crackles` rebound."""
         if self.n == 0:
             return
-        if self._sharded:
-            self.accelerations, self.jerks = self._sharded_launches(self.accelerations, self.jerks)
-            return
         cur = (self.accelerations, self.jerks, self.snaps, self.crackles)
+        if self._sharded:
+            self.accelerations, self.jerks, self.snaps, self.crackles = self._sharded_launches(cur)
+            return
         new = tuple(torch.empty_like(t) for t in cur)
         direct.hermite6_step_f64(self.positions, self.velocities, *cur, *new, self.masses, self.dt,
                                  *self._fmt._scalars(self), self._posd, self._veld, self._accd, self._hws)
         self.accelerations, self.jerks, self.snaps, self.crackles = new
-
-    def _sharded_launches(self, acc, jerk):
-        """HermiteSimulator's hook on the 6th-order launches: from the carried (acc, jerk) -- with `snaps` and `crackles`
-        -- one step, `snaps` and `crackles` rebound, the new (acc, jerk) returned; with None the force of the current
-        state on its own (a zero third quad pair: a and j do not read it)."""
-        if acc is None:
-            return self._sharded_launches6()[:2]
-        acc, jerk, self.snaps, self.crackles = self._sharded_launches6((acc, jerk, self.snaps, self.crackles))
-        return acc, jerk
-
-    def _sharded_launches6(self, cur=None, acc_src=None):
-        """The range-sharded launches: predict + pack of the own bodies, ONE all-gather of 12-double rows in flight
-        during the own x own block, then the own x others block, the slab sum and the corrector. cur = the carried (acc,
-        jerk, snap, crackle): a step, returns the new four. cur None: the force of the current state on its own, the
-        rows a plain pack with acc_src (or zeros) as the third quad pair; returns (acc, jerk, snap)."""
-        p, n_loc = self.part, self.part.n_local
-        new = tuple(torch.empty((n_loc, 3), dtype=torch.float64, device=self.device) for _ in range(4 if cur else 3))
-        eps2, g = self._fmt._scalars(self)
-        if cur:
-            direct.hermite6_shard_predict_f64(self.positions, self.velocities, self._mass_local, self._rows_local, *cur,
-                                              dt=self.dt)
-        else:
-            direct.hermite6_shard_predict_f64(self.positions, self.velocities, self._mass_local, self._rows_local,
-                                              acc=acc_src)
-        handle = self._hgather.start(self._rows_local, self._rows_all)
-        if n_loc:
-            direct.hermite6_shard_force_local_f64(self._rows_local, n_loc, self.n, p.lo, eps2, self._hws)
-        self._hgather.finish(handle, self._rows_all)
-        if n_loc:
-            step = dict(pos=self.positions, vel=self.velocities, acc_in=cur[0], jerk_in=cur[1], snap_in=cur[2],
-                        crackle_out=new[3], dt=self.dt) if cur else {}
-            direct.hermite6_shard_force_remote_f64(self._rows_all, self.n, self._rows_local, n_loc, p.lo, eps2, g,
-                                                   *new[:3], self._hws, **step)
-        return new
 
 
 class BlockHermiteSimulator(HermiteSimulator):

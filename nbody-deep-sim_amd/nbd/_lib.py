@@ -286,7 +286,7 @@ SIGNATURES = {
     "nbd_hermite_shard_force_remote_f64": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_double, c_double, c_void_p,
                                                    c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_void_p,
                                                    c_size_t, c_int, c_int, c_void_p]),
-    # --- 6th-order Hermite, range-sharded (csrc/direct_hermite6_shard_f64.hip)
+    # --- 6th-order Hermite, range-sharded (csrc/direct_hermite_shard_f64.hip, with the 4th order)
     "nbd_hermite6_shard_f64_plan": (c_int, [c_int, c_int, c_int, POINTER(c_int), POINTER(c_int), POINTER(c_int),
                                             POINTER(c_int)]),
     "nbd_hermite6_shard_f64_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),

@@ -412,11 +412,9 @@ def hermite_shard_workspace(n_total: int, lo: int, n_local: int, device) -> torc
     return alloc_bytes(_lib.lib().nbd_hermite_shard_workspace_bytes(n_total, lo, n_local), device)
 
 
-def _chk_rows(t: torch.Tensor, n: int, name: str, dtype=torch.float32):
-    """An array of 8-element rows of `dtype` that holds at least padded_len(n) of them."""
-    _chk(t, None, name, dtype)
-    if t.dim() != 2 or t.shape[1] != HERMITE_ROW or t.shape[0] < padded_len(n):
-        raise _lib.NbdError(f"{name}: need >= {padded_len(n)} rows of {HERMITE_ROW}, got {tuple(t.shape)}")
+def _chk_rows(t: torch.Tensor, n: int, name: str, dtype=torch.float32, width: int = HERMITE_ROW):
+    """An array of `width`-element exchanged rows of `dtype` that holds at least padded_len(n) of them."""
+    _chk_min_rows(t, padded_len(n), width, name, dtype)
 
 
 def _hermite_shard_predict(dtype, entry: str, who: str, pos, vel, mass, send, acc, jerk, dt) -> None:
@@ -428,8 +426,9 @@ def _hermite_shard_predict(dtype, entry: str, who: str, pos, vel, mass, send, ac
                 float(dt), send.data_ptr(), send.shape[0])
 
 
-def _hermite_shard_force_local(dtype, entry: str, send, n_local, n_total, lo, softening_sq, workspace, *slabs) -> None:
-    _chk_rows(send, n_local, "send", dtype)
+def _hermite_shard_force_local(dtype, entry: str, send, n_local, n_total, lo, softening_sq, workspace, *slabs,
+                               width: int = HERMITE_ROW) -> None:
+    _chk_rows(send, n_local, "send", dtype, width)
     _lib.launch(entry, send.device, send.data_ptr(), n_local, float(softening_sq), workspace.data_ptr(),
                 _nbytes(workspace), n_total, lo, *map(int, slabs))
 
@@ -656,7 +655,7 @@ def euler_step_f64(pos, vel, acc_out, mass, dt: float, softening_sq: float, g_co
                 _nbytes(workspace))
 
 
-# ----------------------- double-precision range-sharded Hermite step (csrc/direct_hermite_shard_f64.hip)
+# ----------------------- double-precision range-sharded Hermite step (csrc/direct_hermite_shard_f64.hip: the 4th order)
 def alloc_hermite_rows_f64(n: int, device) -> torch.Tensor:
     """alloc_hermite_rows in float64: zeroed (padded_len(n), 8) rows of 64 bytes, {x_p, y_p, z_p, m, vx_p, vy_p, vz_p, 0}."""
     return torch.zeros((padded_len(n), HERMITE_ROW), dtype=F64, device=device)
@@ -699,7 +698,7 @@ def hermite_shard_force_remote_f64(rows_all: torch.Tensor, n_total: int, send: t
                                 acc_in, jerk_in, dt, slabs_local, slabs_remote)
 
 
-# ----------------------- range-sharded 6th-order Hermite step, float64 (csrc/direct_hermite6_shard_f64.hip)
+# ----------------------- range-sharded 6th-order Hermite step, float64 (csrc/direct_hermite_shard_f64.hip: the 6th order)
 HERMITE6_ROW = 12               # doubles per exchanged row: {x_p, y_p, z_p, m, vx_p, vy_p, vz_p, 0, ax_p, ay_p, az_p, 0}
 
 
@@ -721,11 +720,6 @@ def hermite6_shard_f64_workspace(n_total: int, lo: int, n_local: int, device, sl
                                                                          int(slabs_remote)), device)
 
 
-def _chk_rows6(t: torch.Tensor, n: int, name: str):
-    """An array of 12-double rows that holds at least padded_len(n) of them."""
-    _chk_min_rows(t, padded_len(n), HERMITE6_ROW, name, F64)
-
-
 def hermite6_shard_predict_f64(pos, vel, mass, send, acc=None, jerk=None, snap=None, crackle=None,
                                dt: float = 0.0) -> None:
     """First launch of the sharded 6th-order step: send[:n_local] = {x_p, m, v_p, 0, a_p, 0} of the rank's bodies
@@ -733,7 +727,7 @@ def hermite6_shard_predict_f64(pos, vel, mass, send, acc=None, jerk=None, snap=N
     acc), and acc None gives a zero third quad pair -- and zeros in every row behind n_local."""
     n = pos.shape[0]
     _chk_n3(F64, n, ("pos", "vel"), pos, vel); _chk(mass, (n,), "mass", F64)
-    _chk_rows6(send, n, "send")
+    _chk_rows(send, n, "send", F64, HERMITE6_ROW)
     higher = (jerk, snap, crackle)
     if len({t is None for t in higher}) != 1 or (jerk is not None and acc is None):
         raise _lib.NbdError("hermite6_shard_predict_f64: give acc, jerk, snap and crackle, or acc alone, or none of them")
@@ -749,9 +743,8 @@ def hermite6_shard_force_local_f64(send: torch.Tensor, n_local: int, n_total: in
                                    workspace: torch.Tensor, slabs: int = 0) -> None:
     """Second launch: acceleration + jerk + snap partial sums of the own bodies under the own bodies (reads `send` only,
     so it runs while the all-gather is in flight). slabs: 0 = the plan's split of the own chunks, else that many slabs."""
-    _chk_rows6(send, n_local, "send")
-    _lib.launch("nbd_hermite6_shard_force_local_f64", send.device, send.data_ptr(), n_local, float(softening_sq),
-                workspace.data_ptr(), _nbytes(workspace), n_total, lo, int(slabs))
+    _hermite_shard_force_local(F64, "nbd_hermite6_shard_force_local_f64", send, n_local, n_total, lo, softening_sq,
+                               workspace, slabs, width=HERMITE6_ROW)
 
 
 def hermite6_shard_force_remote_f64(rows_all: torch.Tensor, n_total: int, send: torch.Tensor, n_local: int, lo: int,
@@ -763,8 +756,8 @@ def hermite6_shard_force_remote_f64(rows_all: torch.Tensor, n_total: int, send: 
     acc_out, jerk_out, snap_out. With pos, vel, acc_in, jerk_in, snap_in, crackle_out and dt also the corrector of the own
     rows (pos, vel in place; every output may be its input) and c1 into crackle_out; with none of them the force on its
     own. slabs_local: what the local call was given; slabs_remote: 0 = the plan's split of the remote chunks."""
-    _chk_rows6(rows_all, n_total, "rows_all")
-    _chk_rows6(send, n_local, "send")
+    _chk_rows(rows_all, n_total, "rows_all", F64, HERMITE6_ROW)
+    _chk_rows(send, n_local, "send", F64, HERMITE6_ROW)
     _chk_n3(F64, n_local, ("acc_out", "jerk_out", "snap_out"), acc_out, jerk_out, snap_out)
     _chk_together("hermite6_shard_force_remote_f64", "pos, vel, acc_in, jerk_in, snap_in and crackle_out, or none of them",
                   F64, n_local, ("pos", "vel", "acc_in", "jerk_in", "snap_in", "crackle_out"), pos, vel, acc_in, jerk_in,

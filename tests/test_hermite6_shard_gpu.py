@@ -1,4 +1,4 @@
-"""Range-sharded 6th-order Hermite step (csrc/direct_hermite6_shard_f64.hip, Hermite6Simulator(process_group=...)) on the
+"""Range-sharded 6th-order Hermite step (csrc/direct_hermite_shard_f64.hip, Hermite6Simulator(process_group=...)) on the
 GPU against the fp64 oracles. The force at the bars of tests/hermite_f64_oracle.py and tests/hermite6_oracle.py:
 |got - ref| <= (T + 32) 2^-53 sum|terms|, T = n_total for the acceleration, 4 n_total for the jerk and 19 n_total for the
 snap -- any-order bounds, so they hold for the sharded order (own block, then the others) as for the un-sharded one. The

@@ -1,4 +1,5 @@
-"""Hermite6Simulator(process_group=...) without a GPU (csrc/direct_hermite6_shard_f64.hip).
+"""Hermite6Simulator(process_group=...) without a GPU (the 6th-order entries and kernels of
+csrc/direct_hermite_shard_f64.hip).
 
 World_size-2, -3 and -8 gloo runs on CPU of the PRODUCT's distributed control flow: nbd/dist.py (partition, ONE all-gather
 of 12-double rows per step, two at construction) and the sharded branches of galaxify.simulation.Hermite6Simulator. The
@@ -10,7 +11,6 @@ scratch, no spills, 48 KiB of LDS within the register budget of three workgroups
 import ctypes
 import os
 import re
-import subprocess
 import sys
 
 import numpy as np
@@ -24,11 +24,10 @@ import hermite_f64_oracle as fo
 from conftest import PKG, ROOT
 from nbd import _lib
 from test_dist_gloo import _free_port, _install_cpu_standins
+from test_hermite_shard_f64_host import _kernel, _no_scratch_no_spills, asm  # noqa: F401  (asm: the unit's assembly)
 
 STEPS = 5
 DT, G, SOFT = 0.01, 1.0, 0.05
-SRC = os.path.join(ROOT, "nbody-deep-sim_amd", "csrc", "direct_hermite6_shard_f64.hip")
-FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-ffp-contract=off", "--cuda-device-only", "-S"]
 ENTRIES = ("nbd_hermite6_shard_f64_plan", "nbd_hermite6_shard_f64_workspace_bytes", "nbd_hermite6_shard_predict_f64",
            "nbd_hermite6_shard_force_local_f64", "nbd_hermite6_shard_force_remote_f64")
 KEYS = ("positions", "velocities", "accelerations", "jerks", "snaps")
@@ -355,31 +354,7 @@ def test_plan_workspace_and_argument_checks_without_a_gpu():
         assert rem(*{**ok, **change}.values()) == rc, change
 
 
-@pytest.fixture(scope="module")
-def asm(tmp_path_factory):
-    out = str(tmp_path_factory.mktemp("isa") / "direct_hermite6_shard_f64.s")
-    subprocess.run(["/opt/rocm/bin/hipcc", *FLAGS, "-o", out, SRC], check=True, capture_output=True)
-    return open(out).read()
-
-
-def _kernel(asm, kernel):
-    """(metadata, descriptor, body) of the one kernel whose name holds `kernel`."""
-    names = re.findall(r"\.name:\s+(\S*" + kernel + r"\S*)", asm)
-    assert len(names) == 1, names
-    meta = asm[asm.index(".name:           " + names[0]):]
-    meta = meta[:meta.index(".name:           ", 20) if ".name:           " in meta[20:] else len(meta)]
-    desc = asm[asm.index(".amdhsa_kernel " + names[0]):]
-    desc = desc[:desc.index(".end_amdhsa_kernel")]
-    body = asm[asm.index(names[0] + ":"):]
-    return meta, desc, body[:body.index(".Lfunc_end")]
-
-
-def _no_scratch_no_spills(meta):
-    for key in ("private_segment_fixed_size", "vgpr_spill_count", "sgpr_spill_count"):
-        assert int(re.search(r"\." + key + r":\s+(\d+)", meta).group(1)) == 0, key
-
-
-@pytest.mark.parametrize("kernel", ["shard_accel_jerk_snap_f64_kernelILb0E", "shard_accel_jerk_snap_f64_kernelILb1E"])
+@pytest.mark.parametrize("kernel", ["shard_pair_f64_kernelINS_6Order6ELb0E", "shard_pair_f64_kernelINS_6Order6ELb1E"])
 def test_pair_kernels_resources_and_instructions(asm, kernel):
     """The local (RANGE = false) and remote (RANGE = true) pair kernels: no scratch, no spills, exactly 48 KiB of LDS --
     three workgroups per CU, 3 waves per SIMD -- and at most 168 VGPRs, the register budget at that occupancy (the

@@ -1,4 +1,5 @@
-"""HermiteSimulator(dtype=torch.float64, process_group=...) without a GPU (csrc/direct_hermite_shard_f64.hip).
+"""HermiteSimulator(dtype=torch.float64, process_group=...) without a GPU (csrc/direct_hermite_shard_f64.hip: its 4th-order
+entries and kernels; the 6th-order ones are test_hermite6_shard_host.py's, which takes the assembly helpers from here).
 
 World_size-2, -3 and -8 gloo runs on CPU of the PRODUCT's distributed control flow in float64: nbd/dist.py (partition, ONE
 all-gather of 8-double rows per step) and the sharded branches of galaxify.simulation.HermiteSimulator routed through the
@@ -331,27 +332,43 @@ def test_plan_workspace_and_argument_checks_without_a_gpu():
         assert rem(*{**ok, **change}.values()) == rc, change
 
 
+_ASM = []           # the unit's gfx950 assembly, compiled once per process for this file and test_hermite6_shard_host.py
+
+
 @pytest.fixture(scope="module")
 def asm(tmp_path_factory):
-    out = str(tmp_path_factory.mktemp("isa") / "direct_hermite_shard_f64.s")
-    subprocess.run(["/opt/rocm/bin/hipcc", *FLAGS, "-o", out, SRC], check=True, capture_output=True)
-    return open(out).read()
+    if not _ASM:
+        out = str(tmp_path_factory.mktemp("isa") / "direct_hermite_shard_f64.s")
+        subprocess.run(["/opt/rocm/bin/hipcc", *FLAGS, "-o", out, SRC], check=True, capture_output=True)
+        _ASM.append(open(out).read())
+    return _ASM[0]
 
 
-@pytest.mark.parametrize("kernel,lds", [("shard_predict_f64_kernel", 0), ("shard_finish_f64_kernel", 0),
-                                        ("shard_accel_jerk_f64_kernelILb0E", 32768),
-                                        ("shard_accel_jerk_f64_kernelILb1E", 32768)])
-def test_new_kernels_have_no_scratch_no_spills_and_no_fp32(asm, kernel, lds):
-    """predict, finish, and the local (RANGE = false) and remote (RANGE = true) force kernels: the force kernels keep the
-    un-sharded kernels' 32 KiB of LDS, the O(N) kernels use none."""
+def _kernel(asm, kernel):
+    """(metadata, descriptor, body) of the one kernel whose name holds `kernel`."""
     names = re.findall(r"\.name:\s+(\S*" + kernel + r"\S*)", asm)
     assert len(names) == 1, names
     meta = asm[asm.index(".name:           " + names[0]):]
     meta = meta[:meta.index(".name:           ", 20) if ".name:           " in meta[20:] else len(meta)]
+    desc = asm[asm.index(".amdhsa_kernel " + names[0]):]
+    desc = desc[:desc.index(".end_amdhsa_kernel")]
+    body = asm[asm.index(names[0] + ":"):]
+    return meta, desc, body[:body.index(".Lfunc_end")]
+
+
+def _no_scratch_no_spills(meta):
     for key in ("private_segment_fixed_size", "vgpr_spill_count", "sgpr_spill_count"):
         assert int(re.search(r"\." + key + r":\s+(\d+)", meta).group(1)) == 0, key
-    desc = asm[asm.index(".amdhsa_kernel " + names[0]):]
+
+
+@pytest.mark.parametrize("kernel,lds", [("shard_predict_f64_kernel", 0), ("shard_finish_f64_kernel", 0),
+                                        ("shard_pair_f64_kernelINS_6Order4ELb0E", 32768),
+                                        ("shard_pair_f64_kernelINS_6Order4ELb1E", 32768)])
+def test_new_kernels_have_no_scratch_no_spills_and_no_fp32(asm, kernel, lds):
+    """predict, finish, and the local (RANGE = false) and remote (RANGE = true) 4th-order force kernels: the force kernels
+    keep the un-sharded kernels' 32 KiB of LDS, the O(N) kernels use none."""
+    meta, desc, body = _kernel(asm, kernel)
+    _no_scratch_no_spills(meta)
     got = int(re.search(r"\.amdhsa_group_segment_fixed_size\s+(\d+)", desc).group(1))
     assert got == lds and got <= 32768
-    body = asm[asm.index(names[0] + ":"):]
-    assert "v_cvt_f32_f64" not in body[:body.index(".Lfunc_end")]
+    assert "v_cvt_f32_f64" not in body

@@ -9,7 +9,7 @@ Plummer sphere and runs, per step, exactly the launches the sharded HermiteSimul
 profiles/r11_hermite_shard.json:   python tools/bench_hermite_shard.py [--n 65536 --world 8 --rank 3] [--big]
 --dtype float64 runs the same launches of the float64 step (csrc/direct_hermite_shard_f64.hip) against the un-sharded
 float64 kernels and writes profiles/r16_hermite_shard_f64.json:   python tools/bench_hermite_shard.py --dtype float64 --big
---integrator hermite6 runs the launches of the sharded Hermite6Simulator (csrc/direct_hermite6_shard_f64.hip, 12-double
+--integrator hermite6 runs the launches of the sharded Hermite6Simulator (the same unit's 6th-order entries, 12-double
 rows) against the un-sharded 6th-order kernels and writes profiles/r22_hermite6_shard.json:
     python tools/bench_hermite_shard.py --integrator hermite6 --big
 No multi-rank transport is in any of these numbers: the all-gather is a device copy of the rank's own rows."""
