@@ -19,6 +19,7 @@ accel_vjp_oracle.py -- where sums may cancel (h, and every dot product), the pro
   dL/dx, component k: 8 (alpha) + 6 ((h . w) d_k: h_l w_l d_k, h in its two parts) + 6 ((d . h) w_k) + 6 ((d . w) h_k)
       + 18 ((d . w)(d . h) d_k: d_l w_l d_p h_p d_k, h in its two parts) = 44 per source, T = 44 n;
   dL/dm: 3 (alpha) + 3 (beta_j,l w_l) + 9 (d_l w_l d_p beta_j,p) = 15 per source, T = 15 n.
+accel_jerk_vjp_of_rows is the same arithmetic for a subset of the target rows (tests/vjp_rows_oracle.py).
 """
 import numpy as np
 
@@ -28,19 +29,21 @@ _ROWS = 128
 T_VEL, T_POS, T_MASS = 8, 44, 15            # terms per source
 
 
-def _beta_lines(x, v, m, cot, g, eps2, order):
-    """The beta lines of dL/dx (n,3) and dL/dm (n,) and the sum of |terms| of each, sources in the order `order`."""
-    n = x.shape[0]
+def _beta_lines(x, v, m, cot, g, eps2, order, rows):
+    """The beta lines of dL/dx (len(rows),3) and dL/dm (len(rows),) of the target rows `rows` and the sum of |terms| of
+    each, sources in the order `order`."""
+    nr = rows.size
     xs, vs, ms, bs = x[order], v[order], m[order], cot[order]
     ams, abs_ = np.abs(ms), np.abs(bs)
-    gx = np.zeros((n, 3)); gm = np.zeros(n); sx = np.zeros((n, 3)); sm = np.zeros(n)
-    for lo in range(0, n, _ROWS):
-        hi = min(n, lo + _ROWS)
-        mi, bi = m[lo:hi, None], cot[lo:hi]
-        d = [xs[None, :, k] - x[lo:hi, None, k] for k in range(3)]
-        w = [vs[None, :, k] - v[lo:hi, None, k] for k in range(3)]
+    gx = np.zeros((nr, 3)); gm = np.zeros(nr); sx = np.zeros((nr, 3)); sm = np.zeros(nr)
+    for lo in range(0, nr, _ROWS):
+        hi = min(nr, lo + _ROWS)
+        rr = rows[lo:hi]
+        mi, bi = m[rr, None], cot[rr]
+        d = [xs[None, :, k] - x[rr, None, k] for k in range(3)]
+        w = [vs[None, :, k] - v[rr, None, k] for k in range(3)]
         r2 = d[0] * d[0] + d[1] * d[1] + d[2] * d[2] + eps2
-        own = order[None, :] == np.arange(lo, hi)[:, None]
+        own = order[None, :] == rr[:, None]
         r2[own] = 1.0                                                            # any finite value: zeroed below
         s = 1.0 / np.sqrt(r2)
         s[own] = 0.0
@@ -72,17 +75,25 @@ def _beta_lines(x, v, m, cot, g, eps2, order):
 def accel_jerk_vjp(x, v, m, cota, cotj, g, eps2, order=None):
     """(dL/dx (n,3), dL/dv (n,3), dL/dm (n,), sum|terms| of dL/dx, of dL/dv, of dL/dm) in fp64, the sources summed in the
     order `order` (a permutation of the bodies; None: as they are). cota or cotj None: that cotangent is zero."""
+    return accel_jerk_vjp_of_rows(x, v, m, cota, cotj, g, eps2, order, np.arange(np.asarray(x).shape[0]))
+
+
+def accel_jerk_vjp_of_rows(x, v, m, cota, cotj, g, eps2, order, rows):
+    """accel_jerk_vjp for the target rows `rows` (any indices, any order) under all n sources: the six results have
+    len(rows) rows. accel_jerk_vjp is this with rows = 0 .. n - 1."""
     x = np.asarray(x, np.float64); v = np.asarray(v, np.float64); m = np.asarray(m, np.float64)
     n = x.shape[0]
-    gx = np.zeros((n, 3)); gv = np.zeros((n, 3)); gm = np.zeros(n)
-    sx = np.zeros((n, 3)); sv = np.zeros((n, 3)); sm = np.zeros(n)
+    rows = np.asarray(rows, np.int64)
+    nr = rows.size
+    gx = np.zeros((nr, 3)); gv = np.zeros((nr, 3)); gm = np.zeros(nr)
+    sx = np.zeros((nr, 3)); sv = np.zeros((nr, 3)); sm = np.zeros(nr)
     if cota is not None:
-        ax, am, asx, asm = vo.accel_vjp(x, m, cota, g, eps2, order)
+        ax, am, asx, asm = vo.accel_vjp_of_rows(x, m, cota, g, eps2, order, rows)
         gx, gm, sx, sm = gx + ax, gm + am, sx + asx, sm + asm
     if cotj is not None:
         cotj = np.asarray(cotj, np.float64)
-        gv, _, sv, _ = vo.accel_vjp(x, m, cotj, g, eps2, order)
-        bx, bm, bsx, bsm = _beta_lines(x, v, m, cotj, g, eps2, np.arange(n) if order is None else np.asarray(order))
+        gv, _, sv, _ = vo.accel_vjp_of_rows(x, m, cotj, g, eps2, order, rows)
+        bx, bm, bsx, bsm = _beta_lines(x, v, m, cotj, g, eps2, np.arange(n) if order is None else np.asarray(order), rows)
         gx, gm, sx, sm = gx + bx, gm + bm, sx + bsx, sm + bsm
     return gx, gv, gm, sx, sv, sm
 

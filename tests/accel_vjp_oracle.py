@@ -13,6 +13,7 @@ The terms of the sums, for the bar of hermite_f64_oracle (|got - ref| <= (T + 32
       3 s^5 d_k d_l h_l (l = 0, 1, 2) split by the two parts of h -- so T = 8 n (h and d . h may cancel, so their
       products are the terms, not their sums);
   mass gradient: 3 per source, s^3 d_l g_j,l, so T = 3 n.
+accel_vjp_of_rows is the same arithmetic for a subset of the target rows (tests/vjp_rows_oracle.py).
 """
 import numpy as np
 
@@ -24,18 +25,27 @@ def accel_vjp(x, m, cot, g, eps2, order=None):
     the order `order` (a permutation of the bodies; None: as they are). Blocks of target rows against all sources, one
     (rows, n) array per scalar of a pair; with h = m_i g_j - m_j g_i split as stated, d . h = m_i (d . g_j) - m_j (d . g_i)
     and the sums over j of s^3 times a factor of j alone are matrix-vector products."""
+    return accel_vjp_of_rows(x, m, cot, g, eps2, order, np.arange(np.asarray(x).shape[0]))
+
+
+def accel_vjp_of_rows(x, m, cot, g, eps2, order, rows):
+    """accel_vjp for the target rows `rows` (any indices, any order) under all n sources: the four results have
+    len(rows) rows. accel_vjp is this with rows = 0 .. n - 1."""
     x = np.asarray(x, np.float64); m = np.asarray(m, np.float64); cot = np.asarray(cot, np.float64)
     n = x.shape[0]
     order = np.arange(n) if order is None else np.asarray(order)
+    rows = np.asarray(rows, np.int64)
     xs, ms, gs = x[order], m[order], cot[order]
     ams, ags = np.abs(ms), np.abs(gs)
-    gx = np.zeros((n, 3)); gm = np.zeros(n); sx = np.zeros((n, 3)); sm = np.zeros(n)
-    for lo in range(0, n, _ROWS):
-        hi = min(n, lo + _ROWS)
-        mi, gi = m[lo:hi, None], cot[lo:hi]
-        d = [xs[None, :, k] - x[lo:hi, None, k] for k in range(3)]               # x_j - x_i, by component
+    nr = rows.size
+    gx = np.zeros((nr, 3)); gm = np.zeros(nr); sx = np.zeros((nr, 3)); sm = np.zeros(nr)
+    for lo in range(0, nr, _ROWS):
+        hi = min(nr, lo + _ROWS)
+        rr = rows[lo:hi]
+        mi, gi = m[rr, None], cot[rr]
+        d = [xs[None, :, k] - x[rr, None, k] for k in range(3)]                  # x_j - x_i, by component
         r2 = d[0] * d[0] + d[1] * d[1] + d[2] * d[2] + eps2
-        own = order[None, :] == np.arange(lo, hi)[:, None]
+        own = order[None, :] == rr[:, None]
         r2[own] = 1.0                                                            # any finite value: zeroed below
         s = 1.0 / np.sqrt(r2)
         s[own] = 0.0
