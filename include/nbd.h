@@ -706,6 +706,51 @@ int nbd_accel_jerk_active_f64(const double* posd, const double* veld, int n, con
                               double softening_sq, double g_const, double* acc_out, double* jerk_out, void* workspace,
                               size_t workspace_bytes, int slabs, nbd_stream_t stream);
 
+/* ---- block-timestep 6th-order Hermite (csrc/direct_hermite6_block_f64.hip): "6th-order Hermite" above with the
+ * individual power-of-two steps of "double-precision block-timestep Hermite", float64 only. Body i keeps x, v, a, j, s
+ * and the crackle c at its last correction tick; ticks, levels and sched are the int32 arrays of the block scheme, the
+ * scheduler is nbd_hblock_schedule and the initial levels are nbd_hblock_init_levels_f64's. posd / veld / accd: the
+ * 32-byte-aligned rows of 4 doubles of nbd_hermite6_f64_pack. A block step is nbd_hblock_schedule, then predict, force and
+ * correct (or nbd_hblock6_step_f64, all three). The new level of a corrected body comes from the generalised Aarseth
+ * criterion for p = 6, with eta in the 4th-order convention,
+ *   dt_i = (eta^3 (|a1||s1| + |j1|^2) / (|c1||a5| + |a4|^2))^(1/6),
+ * a4 (at the end of the step) and a5 from the quintic through (a, j, s) at both ends, c1 the crackle just formed; den = 0
+ * allows any step. The level rules are the block scheme's. With every body active the sums are nbd_hermite6_step_f64's
+ * bits, so max_level = 0 is that step. i == j is dropped by index below softening_sq = 1e-24, otherwise by the term being
+ * an exact zero. Workspace: nbd_hblock6_f64_workspace_bytes(n), 32-byte aligned; it holds the active list and, 32-byte
+ * aligned behind it, the partial sums (9 doubles per listed body and slab). Deterministic (no float atomics, no memsets
+ * in a step; the workspace may hold anything on entry). Eager-only. Bad arguments are refused before any launch. */
+size_t nbd_hblock6_f64_workspace_bytes(int n);
+/* posd = {x_p, m}, veld = {v_p, 0}, accd = {a_p, 0} of every body predicted to t_next = sched[0] over
+ * (t_next - ticks[i]) dt / 2^K by the Taylor series to the crackle; zero rows behind n. */
+int nbd_hblock6_predict_f64(const double* pos, const double* vel, const double* acc, const double* jerk,
+                            const double* snap, const double* crackle, const double* mass, const int* ticks, int n,
+                            int max_level, double dt, int* sched, double* posd, double* veld, double* accd,
+                            nbd_stream_t stream);
+/* Acceleration + jerk + snap partial sums of the n_act listed bodies (n_act as schedule reported) under all n sources. */
+int nbd_hblock6_force_f64(const double* posd, const double* veld, const double* accd, int n, int n_act,
+                          double softening_sq, void* workspace, size_t workspace_bytes, nbd_stream_t stream);
+/* The slabs in slab order, the 6th-order corrector and crackle with each listed body's own step, new level,
+ * ticks[i] = t_next (0 at 2^K), posd[i] = {x1, m}. */
+int nbd_hblock6_correct_f64(double* pos, double* vel, double* acc, double* jerk, double* snap, double* crackle,
+                            const double* mass, int* ticks, int* levels, int n, int n_act, int max_level, double dt,
+                            double eta, double g_const, int* sched, double* posd, void* workspace,
+                            size_t workspace_bytes, nbd_stream_t stream);
+/* predict + force + correct of one block step (n_act >= 1). */
+int nbd_hblock6_step_f64(double* pos, double* vel, double* acc, double* jerk, double* snap, double* crackle,
+                         const double* mass, int* ticks, int* levels, int n, int n_act, int max_level, double dt,
+                         double eta, double softening_sq, double g_const, int* sched, double* posd, double* veld,
+                         double* accd, void* workspace, size_t workspace_bytes, nbd_stream_t stream);
+/* The force alone (tests, profiling): acc_out, jerk_out, snap_out double (n_act,3) of the bodies act[0..n_act) (a device
+ * int32 list, any order) under all n bodies of posd / veld / accd, in list order. slabs: 0 for the plan's split of the
+ * sources, or an explicit count in [1, 64]; the workspace then needs the list part of nbd_hblock6_f64_workspace_bytes(n)
+ * (4 bytes per body, n rounded up to a multiple of 8) plus slabs * 9 * n_act doubles. With every body listed the sums
+ * are nbd_accel_jerk_snap_f64's bits at the same slab count. */
+int nbd_accel_jerk_snap_active_f64(const double* posd, const double* veld, const double* accd, int n, const int* act,
+                                   int n_act, double softening_sq, double g_const, double* acc_out, double* jerk_out,
+                                   double* snap_out, void* workspace, size_t workspace_bytes, int slabs,
+                                   nbd_stream_t stream);
+
 /* ---- backward of the all-pairs acceleration (csrc/direct_grad.hip): the vector-Jacobian product of
  *   a_i = G sum_{j != i} m_j d s^3,  d = x_j - x_i,  s = (|d|^2 + softening_sq)^(-1/2)
  * with a cotangent g = dL/da (n,3). With h_ij = m_i g_j - m_j g_i:

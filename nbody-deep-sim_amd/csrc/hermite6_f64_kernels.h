@@ -1,6 +1,7 @@
 // hermite6_f64_kernels.h -- what the 6th-order Hermite translation units share (direct_hermite6_f64.hip: one system;
 // direct_batch_hermite6_f64.hip: many independent systems, shared timestep per system; direct_hermite_shard_f64.hip: one
-// rank's bodies of a range partition, beside the 4th order): the pair functor of the
+// rank's bodies of a range partition, beside the 4th order; direct_hermite6_block_f64.hip: an active list of targets,
+// block timesteps, each body with its own step constants): the pair functor of the
 // acceleration + jerk + snap evaluation (AccelJerkSnapPair), the step constants (Hermite6Step, hermite6_step_constants)
 // and the per-row bodies of the predictor and of the finishing kernel (hermite6_predict_row, hermite6_finish_row). As in
 // hermite_f64_kernels.h there is one copy of every rounded operation: a scene of a batch has the one-system step's bits
@@ -85,10 +86,12 @@ struct AccelJerkSnapPair {
   }
 };
 
-// The step constants: doubles formed from the double dt.
+// The step constants: doubles formed from the double dt. On the device too: a block-timestep body
+// (direct_hermite6_block_f64.hip) forms them from its own step, so one whose step is the whole interval gets the shared
+// step's bits.
 struct Hermite6Step { double dt, dt_half, dt2_half, dt3_6, dt4_24, dt5_120, dt2_10, dt3_120, dt2, dt3; };
 
-inline Hermite6Step hermite6_step_constants(double dt) {
+__host__ __device__ inline Hermite6Step hermite6_step_constants(double dt) {
   const double dt2 = dt * dt, dt3 = dt2 * dt;
   return Hermite6Step{dt, 0.5 * dt, 0.5 * dt2, dt3 / 6.0, dt2 * dt2 / 24.0, dt2 * dt3 / 120.0, dt2 / 10.0, dt3 / 120.0,
                       dt2, dt3};
@@ -132,8 +135,13 @@ __device__ __forceinline__ void hermite6_predict_row(const double* __restrict__ 
 // with pos and vel in place and posd[r] = {x1, m}. The outputs may alias acc_in, jerk_in, snap_in: each element is read
 // before it is written, by the same thread. POSD = false (a range-sharded rank, direct_hermite_shard_f64.hip: its packed
 // rows are rebuilt by the next predictor): posd and mass are not used.
+// Returns both ends of the step as the corrector used them (a0, j0, s0 as read; a1, j1, s1, c1 as stored; zeros for a0,
+// j0, s0, c1 where pos == nullptr): what a block-timestep body's new level is formed from (hblock6_relevel,
+// hermite_block_kernels.h). A caller that drops them pays nothing.
+struct Hermite6Ends { double a0[3], j0[3], s0[3], a1[3], j1[3], s1[3], c1[3]; };
+
 template <bool POSD = true>
-__device__ __forceinline__ void hermite6_finish_row(const double* __restrict__ slabs, int n_slabs, size_t n, size_t i,
+__device__ __forceinline__ Hermite6Ends hermite6_finish_row(const double* __restrict__ slabs, int n_slabs, size_t n, size_t i,
                                                     size_t b, double g, const Hermite6Step& h, double* pos, double* vel,
                                                     const double* acc_in, const double* jerk_in, const double* snap_in,
                                                     double* acc_out, double* jerk_out, double* snap_out,
@@ -142,9 +150,11 @@ __device__ __forceinline__ void hermite6_finish_row(const double* __restrict__ s
   double sum[9];
   slab_order_sum<9>(slabs, n_slabs, n, i, sum);
   double x1[3];
+  Hermite6Ends e;
 #pragma unroll
   for (int k = 0; k < 3; ++k) {
     const double a1 = g * sum[k], j1 = g * sum[k + 3], s1 = g * sum[k + 6];
+    e.a0[k] = e.j0[k] = e.s0[k] = e.c1[k] = 0.0;
     if (pos) {
       const double a0 = acc_in[3 * b + k], j0 = jerk_in[3 * b + k], s0 = snap_in[3 * b + k];
       const double x = pos[3 * b + k], v = vel[3 * b + k];
@@ -152,16 +162,20 @@ __device__ __forceinline__ void hermite6_finish_row(const double* __restrict__ s
       x1[k] = ((x + (v + v1) * h.dt_half) - (a1 - a0) * h.dt2_10) + (j0 + j1) * h.dt3_120;
       vel[3 * b + k] = v1;
       pos[3 * b + k] = x1[k];
-      crackle_out[3 * b + k] =
+      crackle_out[3 * b + k] = e.c1[k] =
           ((60.0 * (a1 - a0) - h.dt * (36.0 * j1 + 24.0 * j0)) + h.dt2 * (9.0 * s1 - 3.0 * s0)) / h.dt3;
+      e.a0[k] = a0;
+      e.j0[k] = j0;
+      e.s0[k] = s0;
     }
-    acc_out[3 * b + k] = a1;
-    jerk_out[3 * b + k] = j1;
-    snap_out[3 * b + k] = s1;
+    acc_out[3 * b + k] = e.a1[k] = a1;
+    jerk_out[3 * b + k] = e.j1[k] = j1;
+    snap_out[3 * b + k] = e.s1[k] = s1;
   }
   if constexpr (POSD) {
     if (pos) posd[r] = d4{x1[0], x1[1], x1[2], mass[b]};
   }
+  return e;
 }
 
 }  // namespace

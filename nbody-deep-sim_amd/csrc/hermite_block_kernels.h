@@ -7,6 +7,8 @@
 // nothing else and serves both. The per-body arithmetic is hermite_kernels.h's (hermite_predict_row, hermite_slab_sum,
 // hermite_correct_row), the step constants hermite_step_constants<T> of the body's own fp64 step: a body whose step is
 // the whole interval gets the shared step's bits.
+// The 6th-order block unit (direct_hermite6_block_f64.hip) takes the record, the level arithmetic, hblock_move_level and
+// hblock6_relevel from here and has O(N) kernels of its own over hermite6_f64_kernels.h's rows.
 // The definitions sit in an anonymous namespace: every translation unit that includes this file gets its own inlined copies.
 #pragma once
 #include <math.h>
@@ -96,27 +98,13 @@ __global__ __launch_bounds__(256) void hblock_predict_kernel(const T* __restrict
   velp[i] = vp;
 }
 
-// The new level of body i, corrected from (a0, j0) to (a1, j1) over its step h = d ticks at level lev, from the Aarseth
-// criterion in fp64: shrink freely; grow by one level where t_next is a multiple of 2 d; deeper than K clamped and
+// The level rules and the bookkeeping of a corrected body i at level lev (step d ticks) whose criterion wants level
+// `want`: shrink freely; grow by one level where t_next is a multiple of 2 d; deeper than K (NaN included) clamped and
 // counted. Moves the body in the level histogram, sets t_i = t_next (0 at 2^K); `first` (one thread of the launch)
 // publishes that tick as sched[kTCur].
-//   a3 = (12 (a0 - a1) + 6 h (j0 + j1)) / h^3, a2(t1) = (-6 (a0 - a1) - h (4 j0 + 2 j1)) / h^2 + h a3
-template <class T>
-__device__ __forceinline__ void hblock_relevel(const T* a0, const T* j0, const T* a1, const T* j1, double h, double dt,
-                                               double eta, int K, int lev, int d, int i, bool first,
-                                               int* __restrict__ ticks, int* __restrict__ levels,
-                                               int* __restrict__ sched) {
-  double a3[3], a2[3];
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    const double da = (double)a0[k] - (double)a1[k];
-    a3[k] = (12.0 * da + 6.0 * h * ((double)j0[k] + (double)j1[k])) / (h * h * h);
-    a2[k] = (-6.0 * da - h * (4.0 * (double)j0[k] + 2.0 * (double)j1[k])) / (h * h) + h * a3[k];
-  }
-  const double na1 = norm3(a1[0], a1[1], a1[2]), nj1 = norm3(j1[0], j1[1], j1[2]);
-  const double na2 = norm3(a2[0], a2[1], a2[2]), na3 = norm3(a3[0], a3[1], a3[2]);
-  const double crit = criterion(eta, na1 * na2 + nj1 * nj1, nj1 * na3 + na2 * na2);
-  const int want = wanted_level(crit, dt, K);
+__device__ __forceinline__ void hblock_move_level(int want, int K, int lev, int d, int i, bool first,
+                                                  int* __restrict__ ticks, int* __restrict__ levels,
+                                                  int* __restrict__ sched) {
   const int t_next = sched[kTNext];
   int nl = lev;
   if (want > lev) {
@@ -136,6 +124,54 @@ __device__ __forceinline__ void hblock_relevel(const T* a0, const T* j0, const T
   const int t_now = t_next == (1 << K) ? 0 : t_next;
   ticks[i] = t_now;
   if (first) sched[kTCur] = t_now;
+}
+
+// The new level of body i, corrected from (a0, j0) to (a1, j1) over its step h = d ticks at level lev, from the Aarseth
+// criterion in fp64, by hblock_move_level's rules.
+//   a3 =(12 (a0 - a1) + 6 h (j0 + j1)) / h^3, a2(t1) = (-6 (a0 - a1) - h (4 j0 + 2 j1)) / h^2 + h a3
+template <class T>
+__device__ __forceinline__ void hblock_relevel(const T* a0, const T* j0, const T* a1, const T* j1, double h, double dt,
+                                               double eta, int K, int lev, int d, int i, bool first,
+                                               int* __restrict__ ticks, int* __restrict__ levels,
+                                               int* __restrict__ sched) {
+  double a3[3], a2[3];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const double da = (double)a0[k] - (double)a1[k];
+    a3[k] = (12.0 * da + 6.0 * h * ((double)j0[k] + (double)j1[k])) / (h * h * h);
+    a2[k] = (-6.0 * da - h * (4.0 * (double)j0[k] + 2.0 * (double)j1[k])) / (h * h) + h * a3[k];
+  }
+  const double na1 = norm3(a1[0], a1[1], a1[2]), nj1 = norm3(j1[0], j1[1], j1[2]);
+  const double na2 = norm3(a2[0], a2[1], a2[2]), na3 = norm3(a3[0], a3[1], a3[2]);
+  const double crit = criterion(eta, na1 * na2 + nj1 * nj1, nj1 * na3 + na2 * na2);
+  hblock_move_level(wanted_level(crit, dt, K), K, lev, d, i, first, ticks, levels, sched);
+}
+
+// ... and of a 6th-order body (direct_hermite6_block_f64.hip), corrected from (a0, j0, s0) to (a1, j1, s1) with the
+// crackle c1 just formed: the generalised criterion of Nitadori & Makino (2008) for p = 6, with eta in the 4th-order
+// convention (dt_i = sqrt(eta ...) there),
+//   dt_i = (eta^3 (|a1||s1| + |j1|^2) / (|c1||a5| + |a4(t1)|^2))^(1/6)  = cbrt(criterion(eta^3, num, den)),
+// from the derivatives of the quintic through both ends,
+//   a5 = (720 (a1 - a0) - 360 h (j1 + j0) + 60 h^2 (s1 - s0)) / h^5
+//   a4(t1) = (-360 (a1 - a0) + h (168 j1 + 192 j0) + h^2 (-24 s1 + 36 s0)) / h^4 + h a5,   a3(t1) = c1.
+// Every operation rounds on its own (the build has -ffp-contract=off). The level rules are hblock_move_level's.
+__device__ __forceinline__ void hblock6_relevel(const double* a0, const double* j0, const double* s0, const double* a1,
+                                                const double* j1, const double* s1, const double* c1, double h,
+                                                double dt, double eta, int K, int lev, int d, int i, bool first,
+                                                int* __restrict__ ticks, int* __restrict__ levels,
+                                                int* __restrict__ sched) {
+  double a4[3], a5[3];
+  const double h2 = h * h, h4 = h2 * h2, h5 = h4 * h;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const double da = a1[k] - a0[k];
+    a5[k] = ((720.0 * da - 360.0 * h * (j1[k] + j0[k])) + 60.0 * h2 * (s1[k] - s0[k])) / h5;
+    a4[k] = ((-360.0 * da + h * (168.0 * j1[k] + 192.0 * j0[k])) + h2 * (-24.0 * s1[k] + 36.0 * s0[k])) / h4 + h * a5[k];
+  }
+  const double na1 = norm3(a1[0], a1[1], a1[2]), nj1 = norm3(j1[0], j1[1], j1[2]), ns1 = norm3(s1[0], s1[1], s1[2]);
+  const double nc1 = norm3(c1[0], c1[1], c1[2]), na4 = norm3(a4[0], a4[1], a4[2]), na5 = norm3(a5[0], a5[1], a5[2]);
+  const double crit = cbrt(criterion(eta * eta * eta, na1 * ns1 + nj1 * nj1, nc1 * na5 + na4 * na4));
+  hblock_move_level(wanted_level(crit, dt, K), K, lev, d, i, first, ticks, levels, sched);
 }
 
 // The active bodies' corrector, one workgroup per HermiteFmt<T>::kSumRows consecutive list entries: a1, j1 =

@@ -465,6 +465,10 @@ class _Hermite6Float64(_Float64):
         direct.hermite6_shard_force_remote_f64(s._rows_all, s.n, s._rows_local, p.n_local, p.lo, *self._scalars(s),
                                                *new[:3], s._hws, **step)
 
+    # BlockHermite6Simulator (csrc/direct_hermite6_block_f64.hip): 9 doubles per listed body and slab; the initial levels
+    # are the inherited block_init_levels, from a and j
+    block_workspace = staticmethod(direct.hblock6_workspace)
+
 
 _FORMATS = {fmt.dtype: fmt for fmt in (_Float32(), _Float64())}
 _HERMITE6 = _Hermite6Float64()
@@ -1036,9 +1040,10 @@ class Hermite6Simulator(HermiteSimulator):
     predicted state; step() rebinds them. positions, velocities and masses are float64 as for
     HermiteSimulator(dtype=torch.float64), whose compute_energies(), compute_potentials(), compute_invariants(), gather()
     and eager run() work here unchanged. The only number format is float64 (`dtype` defaults to it): the fp32 Hermite run
-    already sits on the fp32 floor at a few dozen steps, so a higher order buys nothing there. There is no block-timestep
-    or differentiable form; many systems stepped together, with a captured run(), are
-    BatchedSimulator(integrator="hermite6"), each scene bit-identical to this simulator on it alone.
+    already sits on the fp32 floor at a few dozen steps, so a higher order buys nothing there. There is no differentiable
+    form. Individual block timesteps are BlockHermite6Simulator (with max_level=0 this simulator bit for bit); many systems
+    stepped together, with a captured run(), are BatchedSimulator(integrator="hermite6"), each scene bit-identical to this
+    simulator on it alone.
 
     With `process_group=` the bodies are range-sharded as for HermiteSimulator(dtype=torch.float64)
     (the 6th-order entries of csrc/direct_hermite_shard_f64.hip): positions, velocities, accelerations,
@@ -1108,7 +1113,80 @@ class Hermite6Simulator(HermiteSimulator):
         self.accelerations, self.jerks, self.snaps, self.crackles = new
 
 
-class BlockHermiteSimulator(HermiteSimulator):
+class _BlockSteps:
+    """What the block-timestep simulators share (BlockHermiteSimulator, BlockHermite6Simulator), mixed in in front of the
+    shared-timestep class whose scheme they run: the parameters `eta` and `max_level`, the int32 schedule state, the
+    counters, the initial levels and the loop of block steps that makes one step(). The class states `_block_step(n_act)`,
+    the predict, force and correct of the block step the schedule has just listed; its format object gives the
+    workspace (`block_workspace`) and the initial levels (`block_init_levels`, from `accelerations` and `jerks`)."""
+
+    MAX_LEVEL_LIMIT = 20
+
+    def _init_block(self, eta, max_level):
+        self.eta = eta
+        self.max_level = max_level
+        self.levels = torch.zeros(self.n, dtype=torch.int32, device=self.device)
+        self._ticks = torch.zeros(self.n, dtype=torch.int32, device=self.device)
+        self._sched = torch.zeros(direct.HBLOCK_SCHED_INTS, dtype=torch.int32, device=self.device)
+        self._sched_host = torch.zeros(4, dtype=torch.int32).pin_memory()
+        self._bws = self._fmt.block_workspace(max(self.n, 1), self.device)
+        self.block_steps = 0
+        self.pair_interactions = 0
+        self.clamped = 0
+        self.level_history = None
+        self._leveled_for = None
+        self._set_levels()
+
+    def _check_params(self):
+        who = type(self).__name__
+        if not (isinstance(self.max_level, int) and 0 <= self.max_level <= self.MAX_LEVEL_LIMIT):
+            raise ValueError(f"{who}: max_level must be an int in [0, {self.MAX_LEVEL_LIMIT}]")
+        if not (self.dt > 0 and self.eta > 0):
+            raise ValueError(f"{who}: dt and eta must be positive")
+
+    def _set_levels(self):
+        self._check_params()
+        self._leveled_for = (self.dt, self.eta, self.max_level)
+        if self.n == 0:
+            return
+        self._fmt.block_init_levels(self.accelerations, self.jerks, self.dt, self.eta, self.max_level, self._ticks,
+                                    self.levels, self._sched)
+        self._read_clamped()
+
+    def _read_clamped(self):
+        self._sched_host.copy_(self._sched[:4])
+        self.clamped = int(self._sched_host[2])
+
+    def step(self):
+        """One output interval: block steps until every body is back at tick 2^max_level (at most 2^max_level of them)."""
+        if self.n == 0:
+            return
+        if self._leveled_for != (self.dt, self.eta, self.max_level):
+            self._set_levels()
+        who = type(self).__name__
+        K = self.max_level
+        end = 1 << K
+        host = self._sched_host
+        t_prev = 0
+        for _ in range(end):
+            direct.hblock_schedule(self.levels, K, self._sched, self._bws, host_sched=host)
+            t_next, n_act = int(host[0]), int(host[1])
+            if not (t_prev < t_next <= end and 1 <= n_act <= self.n):
+                raise RuntimeError(f"{who}: corrupt schedule (t_next={t_next}, n_act={n_act}, previous tick {t_prev})")
+            self._block_step(n_act)
+            self.block_steps += 1
+            self.pair_interactions += n_act * self.n
+            if self.level_history is not None:
+                self.level_history.append(self.levels.cpu())
+            if t_next == end:
+                break
+            t_prev = t_next
+        else:
+            raise RuntimeError(f"{who}: interval not finished within {end} block steps")
+        self._read_clamped()
+
+
+class BlockHermiteSimulator(_BlockSteps, HermiteSimulator):
     """HermiteSimulator with individual block timesteps (Makino & Aarseth 1992), an extension the reference does not have.
     `dt` is the output interval and the longest step: one step() advances every body by dt, in 2^max_level ticks. Body i
     moves with its own step dt 2^-k_i, k_i = levels[i] in [0, max_level], chosen by the Aarseth criterion
@@ -1132,8 +1210,6 @@ class BlockHermiteSimulator(HermiteSimulator):
     from a smaller eta at the fp32 floor of the orbit; this mode follows the criterion down to float64 rounding. With
     max_level=0 it is HermiteSimulator(dtype=torch.float64) bit for bit. compute_*() and run() are that class's."""
 
-    MAX_LEVEL_LIMIT = 20
-
     def __init__(self, *, positions, velocities, masses, g_const: float = 1.0, softening: float = 0.1,
                  dt: float = 0.01, calc_energy: bool = True, device: str = None, process_group=None,
                  eta: float = 0.02, max_level: int = 10, calc_invariants: bool = False, **hermite_kw):
@@ -1146,71 +1222,60 @@ class BlockHermiteSimulator(HermiteSimulator):
         super().__init__(positions=positions, velocities=velocities, masses=masses, g_const=g_const,
                          softening=softening, dt=dt, calc_energy=calc_energy, device=device,
                          calc_invariants=calc_invariants, **hermite_kw)
-        self.eta = eta
-        self.max_level = max_level
-        self.levels = torch.zeros(self.n, dtype=torch.int32, device=self.device)
-        self._ticks = torch.zeros(self.n, dtype=torch.int32, device=self.device)
-        self._sched = torch.zeros(direct.HBLOCK_SCHED_INTS, dtype=torch.int32, device=self.device)
-        self._sched_host = torch.zeros(4, dtype=torch.int32).pin_memory()
-        self._bws = self._fmt.block_workspace(max(self.n, 1), self.device)
-        self.block_steps = 0
-        self.pair_interactions = 0
-        self.clamped = 0
-        self.level_history = None
-        self._leveled_for = None
-        self._set_levels()
-
-    def _check_params(self):
-        if not (isinstance(self.max_level, int) and 0 <= self.max_level <= self.MAX_LEVEL_LIMIT):
-            raise ValueError(f"BlockHermiteSimulator: max_level must be an int in [0, {self.MAX_LEVEL_LIMIT}]")
-        if not (self.dt > 0 and self.eta > 0):
-            raise ValueError("BlockHermiteSimulator: dt and eta must be positive")
-
-    def _set_levels(self):
-        self._check_params()
-        self._leveled_for = (self.dt, self.eta, self.max_level)
-        if self.n == 0:
-            return
-        self._fmt.block_init_levels(self.accelerations, self.jerks, self.dt, self.eta, self.max_level, self._ticks,
-                                    self.levels, self._sched)
-        self._read_clamped()
-
-    def _read_clamped(self):
-        self._sched_host.copy_(self._sched[:4])
-        self.clamped = int(self._sched_host[2])
+        self._init_block(eta, max_level)
 
     def _block_step(self, n_act: int):
         """Predict, force and correct of the block step the schedule has just listed."""
         self._fmt.block_step(self, self.positions, self.velocities, self.accelerations, self.jerks, self.masses,
                              self._ticks, self.levels, n_act, self.max_level, self.dt, self.eta)
 
-    def step(self):
-        """One output interval: block steps until every body is back at tick 2^max_level (at most 2^max_level of them)."""
-        if self.n == 0:
-            return
-        if self._leveled_for != (self.dt, self.eta, self.max_level):
-            self._set_levels()
-        K = self.max_level
-        end = 1 << K
-        host = self._sched_host
-        t_prev = 0
-        for _ in range(end):
-            direct.hblock_schedule(self.levels, K, self._sched, self._bws, host_sched=host)
-            t_next, n_act = int(host[0]), int(host[1])
-            if not (t_prev < t_next <= end and 1 <= n_act <= self.n):
-                raise RuntimeError(f"BlockHermiteSimulator: corrupt schedule (t_next={t_next}, n_act={n_act}, "
-                                   f"previous tick {t_prev})")
-            self._block_step(n_act)
-            self.block_steps += 1
-            self.pair_interactions += n_act * self.n
-            if self.level_history is not None:
-                self.level_history.append(self.levels.cpu())
-            if t_next == end:
-                break
-            t_prev = t_next
-        else:
-            raise RuntimeError(f"BlockHermiteSimulator: interval not finished within {end} block steps")
-        self._read_clamped()
+
+class BlockHermite6Simulator(_BlockSteps, Hermite6Simulator):
+    """Hermite6Simulator with individual block timesteps, the form Nitadori & Makino (2008) wrote the scheme for
+    (csrc/direct_hermite6_block_f64.hip), an extension the reference does not have. `dt` is the output
+    interval and the longest step: one step() advances every body by dt, in 2^max_level ticks. Body i carries x, v, a, j,
+    s and the crackle c at its last correction and moves with its own step h_i = dt 2^-k_i, k_i = levels[i] in
+    [0, max_level]. A block step predicts every body to the next due time by Hermite6Simulator's Taylor series over its
+    own elapsed time, evaluates a1, j1, s1 of the due bodies against all predicted bodies, corrects them with their own
+    h_i and re-levels them from the generalised Aarseth criterion for p = 6,
+        dt_i = (eta^3 (|a1||s1| + |j1|^2) / (|c1||a5| + |a4|^2))^(1/6),
+    a4 (at the end of the step) and a5 from the quintic through (a, j, s) at both ends, c1 the crackle just formed; eta
+    keeps BlockHermiteSimulator's convention (dt_i = sqrt(eta ...) there). Levels may deepen at any block step and rise
+    by one where the block allows. Initial levels (at construction, and after dt, eta or max_level change) come from
+    dt_i = (eta / 2) |a| / |j|; the start is Hermite6Simulator's (a first, then the snap from it, c = 0).
+
+    The public surface is BlockHermiteSimulator's: `eta`, `max_level`, `levels`, the cumulative counters `block_steps`,
+    `pair_interactions` and `clamped`, `level_history`, MAX_LEVEL_LIMIT. `accelerations`, `jerks`, `snaps` and `crackles`
+    are updated in place. Float64 only and eager-only (every block step reads {t_next, n_act} back to the host); there is
+    no range-sharded, batched, captured or differentiable form. With max_level=0 it is Hermite6Simulator bit for bit.
+    compute_*() and run() are that class's."""
+
+    def __init__(self, *, positions, velocities, masses, g_const: float = 1.0, softening: float = 0.1,
+                 dt: float = 0.01, calc_energy: bool = True, device: str = None, process_group=None,
+                 eta: float = 0.02, max_level: int = 10, calc_invariants: bool = False, **format_kw):
+        # all refusals before anything is resolved, allocated or launched; format_kw is Hermite6Simulator's (`dtype`)
+        unknown = [k for k in format_kw if k != "dtype"]
+        if unknown:
+            raise TypeError(f"{type(self).__name__}.__init__() got an unexpected keyword argument {unknown[0]!r}")
+        dtype = format_kw.get("dtype", torch.float64)
+        if dtype is not torch.float64:
+            raise ValueError(f"BlockHermite6Simulator: dtype must be torch.float64, got {dtype!r}: there is no fp32 form "
+                             "of the 6th-order scheme")
+        if process_group is not None:
+            raise ValueError("BlockHermite6Simulator: there is no range-sharded block-timestep step; process_group is "
+                             "not supported")
+        super().__init__(positions=positions, velocities=velocities, masses=masses, g_const=g_const,
+                         softening=softening, dt=dt, calc_energy=calc_energy, device=device,
+                         calc_invariants=calc_invariants, **format_kw)
+        self._init_block(eta, max_level)
+
+    def _block_step(self, n_act: int):
+        """Predict, force and correct of the block step the schedule has just listed."""
+        direct.hblock6_step_f64(self.positions, self.velocities, self.accelerations, self.jerks, self.snaps,
+                                self.crackles, self.masses, self._ticks, self.levels, n_act, self.max_level, self.dt,
+                                self.eta, *self._fmt._scalars(self), self._sched, self._posd, self._veld, self._accd,
+                                self._bws)
+
 
 def _per_scene(x, n_scenes: int, name: str) -> list:
     """A scalar, or one value per scene -> list of S Python floats."""

@@ -326,6 +326,17 @@ SIGNATURES = {
                                     c_void_p, c_size_t, c_void_p]),
     "nbd_accel_jerk_active_f64": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_double, c_double, c_void_p,
                                           c_void_p, c_void_p, c_size_t, c_int, c_void_p]),
+    # --- block-timestep 6th-order Hermite (csrc/direct_hermite6_block_f64.hip)
+    "nbd_hblock6_f64_workspace_bytes": (c_size_t, [c_int]),
+    "nbd_hblock6_predict_f64": (c_int, [c_void_p] * 8 + [c_int, c_int, c_double] + [c_void_p] * 5),
+    "nbd_hblock6_force_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_double, c_void_p, c_size_t,
+                                      c_void_p]),
+    "nbd_hblock6_correct_f64": (c_int, [c_void_p] * 9 + [c_int, c_int, c_int, c_double, c_double, c_double, c_void_p,
+                                                         c_void_p, c_void_p, c_size_t, c_void_p]),
+    "nbd_hblock6_step_f64": (c_int, [c_void_p] * 9 + [c_int, c_int, c_int, c_double, c_double, c_double, c_double] +
+                             [c_void_p] * 5 + [c_size_t, c_void_p]),
+    "nbd_accel_jerk_snap_active_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_double, c_double,
+                                               c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_void_p]),
     # --- backward of the all-pairs acceleration (csrc/direct_grad.hip)
     "nbd_accel_vjp_workspace_bytes": (c_size_t, [c_int]),
     "nbd_accel_vjp_f32": (c_int, [c_void_p, c_void_p, c_int, c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p]),

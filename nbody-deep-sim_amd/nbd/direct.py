@@ -1035,6 +1035,88 @@ def accel_jerk_active_f64(posd, veld, n: int, act, softening_sq: float, g_const:
                               lambda dev, n_act: hblock_f64_workspace(n, dev, slabs, n_act), slabs)
 
 
+# ------------------------------------- block-timestep 6th-order Hermite, float64 (csrc/direct_hermite6_block_f64.hip)
+_HBLOCK6_STATE = ("pos", "vel", "acc", "jerk", "snap", "crackle")
+
+
+def _chk_hblock6(state, mass, ticks, levels, sched, posd, veld, accd) -> int:
+    """The arguments of a 6th-order block step (the six (n,3) state arrays, packed rows, int32 schedule arrays); veld and
+    accd None where the entry takes none. Returns n."""
+    n = state[0].shape[0]
+    _chk_n3(F64, n, _HBLOCK6_STATE, *state)
+    _chk(mass, (n,), "mass", F64)
+    _chk_packed(F64, posd, veld, n)
+    if accd is not None:
+        _chk_accd(accd, n)
+    _chk_sched(n, ticks, levels, sched)
+    return n
+
+
+def hblock6_workspace(n: int, device, slabs: int = 0, n_act: int = 0) -> torch.Tensor:
+    """Active list + float64 partial sums of one 6th-order block step (nbd_hblock6_f64_workspace_bytes), or of
+    accel_jerk_snap_active_f64 with an explicit slab count on n_act targets."""
+    need = _lib.lib().nbd_hblock6_f64_workspace_bytes(int(n))
+    return alloc_bytes(max(need, (int(n) + 7) // 8 * 32 + int(slabs) * 9 * int(n_act) * 8), device)
+
+
+def hblock6_predict_f64(pos, vel, acc, jerk, snap, crackle, mass, ticks, levels, max_level: int, dt: float, sched, posd,
+                        veld, accd) -> None:
+    """First launch of a 6th-order block step: every body predicted to t_next = sched[0] into posd / veld / accd."""
+    state = (pos, vel, acc, jerk, snap, crackle)
+    n = _chk_hblock6(state, mass, ticks, levels, sched, posd, veld, accd)
+    _lib.launch("nbd_hblock6_predict_f64", pos.device, *(t.data_ptr() for t in state), mass.data_ptr(),
+                ticks.data_ptr(), n, int(max_level), float(dt), sched.data_ptr(), posd.data_ptr(), veld.data_ptr(),
+                accd.data_ptr())
+
+
+def hblock6_force_f64(posd, veld, accd, n: int, n_act: int, softening_sq: float, workspace) -> None:
+    """Second launch: the partial sums of the n_act bodies the schedule listed in the workspace."""
+    _chk_packed(F64, posd, veld, n); _chk_accd(accd, n)
+    _lib.launch("nbd_hblock6_force_f64", posd.device, posd.data_ptr(), veld.data_ptr(), accd.data_ptr(), n, int(n_act),
+                float(softening_sq), workspace.data_ptr(), _nbytes(workspace))
+
+
+def hblock6_correct_f64(pos, vel, acc, jerk, snap, crackle, mass, ticks, levels, n_act: int, max_level: int, dt: float,
+                        eta: float, g_const: float, sched, posd, workspace) -> None:
+    """Third launch: slab sum, corrector, crackle and new level of the listed bodies; posd = {x1, m} for them."""
+    state = (pos, vel, acc, jerk, snap, crackle)
+    n = _chk_hblock6(state, mass, ticks, levels, sched, posd, None, None)
+    _lib.launch("nbd_hblock6_correct_f64", pos.device, *(t.data_ptr() for t in state), mass.data_ptr(),
+                ticks.data_ptr(), levels.data_ptr(), n, int(n_act), int(max_level), float(dt), float(eta),
+                float(g_const), sched.data_ptr(), posd.data_ptr(), workspace.data_ptr(), _nbytes(workspace))
+
+
+def hblock6_step_f64(pos, vel, acc, jerk, snap, crackle, mass, ticks, levels, n_act: int, max_level: int, dt: float,
+                     eta: float, softening_sq: float, g_const: float, sched, posd, veld, accd, workspace) -> None:
+    """Predict all bodies to t_next, evaluate the n_act listed ones, correct and re-level them (three launches). pos, vel,
+    acc, jerk, snap, crackle, ticks, levels in place for the active bodies; posd = {x1, m} for them, predicted rows for
+    the rest. dt, eta, softening_sq and g_const go in as the Python doubles."""
+    state = (pos, vel, acc, jerk, snap, crackle)
+    n = _chk_hblock6(state, mass, ticks, levels, sched, posd, veld, accd)
+    _lib.launch("nbd_hblock6_step_f64", pos.device, *(t.data_ptr() for t in state), mass.data_ptr(), ticks.data_ptr(),
+                levels.data_ptr(), n, int(n_act), int(max_level), float(dt), float(eta), float(softening_sq),
+                float(g_const), sched.data_ptr(), posd.data_ptr(), veld.data_ptr(), accd.data_ptr(),
+                workspace.data_ptr(), _nbytes(workspace))
+
+
+def accel_jerk_snap_active_f64(posd, veld, accd, n: int, act, softening_sq: float, g_const: float, workspace=None,
+                               slabs: int = 0):
+    """(acc, jerk, snap), each (len(act), 3) float64, of the bodies act (a device int32 list, any order) under all n
+    bodies of posd / veld / accd, in list order. slabs: 0 = the plan's source split, else that many. The all-bodies list
+    gives accel_jerk_snap_f64's bits at the same slab count."""
+    _chk_packed(F64, posd, veld, n); _chk_accd(accd, n)
+    _chk(act, None, "act", torch.int32)
+    n_act = act.numel()
+    dev = posd.device
+    acc_out, jerk_out, snap_out = (torch.empty((n_act, 3), dtype=F64, device=dev) for _ in range(3))
+    if workspace is None:                       # a given workspace is checked by the entry, against what this call uses
+        workspace = hblock6_workspace(n, dev, slabs, n_act)
+    _lib.launch("nbd_accel_jerk_snap_active_f64", dev, posd.data_ptr(), veld.data_ptr(), accd.data_ptr(), n,
+                act.data_ptr(), n_act, float(softening_sq), float(g_const), acc_out.data_ptr(), jerk_out.data_ptr(),
+                snap_out.data_ptr(), workspace.data_ptr(), _nbytes(workspace), int(slabs))
+    return acc_out, jerk_out, snap_out
+
+
 # ---------------------------------------------------------------- batched direct integrator (csrc/direct_batch.hip)
 class BatchPlan:
     """The host offsets of an ensemble of scenes and the device work list built from them (nbd_batch_plan /

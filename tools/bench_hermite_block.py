@@ -19,6 +19,15 @@ With --dtype float64 (BlockHermiteSimulator(dtype=torch.float64), csrc/direct_he
 3. The e = 0.9 orbit (eps = 0, one period as 4 output steps, max_level 16): eta = 0.01 ... 0.000625 in float64 beside
    float32; error, pair interactions, clamped levels and wall time per eta.
 The default output is profiles/r13_hermite_block_f64.json.
+
+With --order 6 (BlockHermite6Simulator, csrc/direct_hermite6_block_f64.hip; float64), all in one process:
+1. nbd_accel_jerk_snap_active_f64 with every body listed against nbd_accel_jerk_snap_f64 (the same wave body and plan),
+   and shorter lists, interleaved as above.
+2. The block-step cost fit of the 6th order (T_full the Hermite6Simulator step) beside the float64 4th order's.
+3. The e = 0.9 orbit (eps = 0, one period as 4 output steps, max_level 16): eta = 0.01 ... 0.000625 at the 6th order
+   beside BlockHermiteSimulator(dtype=torch.float64); error, pair interactions, clamped levels, wall time and the GPU
+   time of the four output steps (HIP events) per eta.
+The default output is profiles/r23_hermite6_block.json.
 """
 import argparse
 import json
@@ -107,16 +116,47 @@ def active_force_f64(n=65536, reps=10):
     return rows
 
 
-def block_step_cost(n=65536, K=10, reps=15, dtype=torch.float32):
+def active_force6(n=65536, reps=10):
+    p, v, m = generate_plummer(n, seed=1)
+    dev = torch.device("cuda")
+    f64 = lambda a: torch.tensor(np.asarray(a, np.float64), dtype=torch.float64, device=dev)      # noqa: E731
+    posd, veld, accd = (direct.alloc_rows_f64(n, dev) for _ in range(3))
+    eps2 = 0.01 ** 2
+    hws, bws = direct.hermite6_workspace(n, dev), direct.hblock6_workspace(n, dev)
+    direct.hermite6_pack(f64(p), f64(v), f64(m), posd, veld, accd)
+    acc = direct.accel_jerk_snap_f64(posd, veld, accd, n, eps2, 1.0, workspace=hws)[0]
+    direct.hermite6_pack(f64(p), f64(v), f64(m), posd, veld, accd, acc=acc)
+    rng = np.random.default_rng(0)
+    rows = []
+    for n_act in (65536, 8192, 1024, 128):
+        act = torch.tensor(np.sort(rng.permutation(n)[:n_act]), dtype=torch.int32, device=dev)
+        f_all = (lambda: direct.accel_jerk_snap_f64(posd, veld, accd, n, eps2, 1.0, workspace=hws))
+        f_act = (lambda: direct.accel_jerk_snap_active_f64(posd, veld, accd, n, act, eps2, 1.0, workspace=bws))
+        for _ in range(2):
+            f_all(); f_act()
+        full, part = [], []
+        for _ in range(3):                                   # interleaved rounds
+            full.append(_event_ms(f_all, reps)); part.append(_event_ms(f_act, reps))
+        full_ms, act_ms = float(np.median(full)), float(np.median(part))
+        rows.append({"n": n, "n_act": n_act, "accel_jerk_snap_f64_ms": full_ms, "active_snap_f64_ms": act_ms,
+                     "ratio_to_full": act_ms / full_ms,
+                     "pair_rate_fraction": (n_act / act_ms) / (n / full_ms)})
+        print(json.dumps(rows[-1]), flush=True)
+    return rows
+
+
+def block_step_cost(n=65536, K=10, reps=15, dtype=torch.float32, order=4):
     p, v, m = generate_plummer(n, seed=1)
     kw = dict(positions=p, velocities=v, masses=m, softening=0.01, dt=1e-3, calc_energy=False, device="cuda",
               dtype=dtype)
-    he = simulation.HermiteSimulator(**kw)
+    shared, block = ((simulation.HermiteSimulator, simulation.BlockHermiteSimulator) if order == 4 else
+                     (simulation.Hermite6Simulator, simulation.BlockHermite6Simulator))
+    he = shared(**kw)
     for _ in range(3):
         he.step()
     torch.cuda.synchronize()
     t_full = _event_ms(he.step, reps)
-    sim = simulation.BlockHermiteSimulator(max_level=K, **kw)
+    sim = block(max_level=K, **kw)
     host = sim._sched_host
     pts = []
     for n_act in (128, 1024, 8192, 32768, 65536):
@@ -140,7 +180,7 @@ def block_step_cost(n=65536, K=10, reps=15, dtype=torch.float32):
     f = np.array([q["n_act"] / n for q in pts])
     t = np.array([q["block_step_ms"] for q in pts])
     slope, icpt = np.polyfit(f, t, 1)
-    return {"n": n, "max_level": K, "dtype": str(dtype), "hermite_step_ms": t_full, "points": pts,
+    return {"n": n, "max_level": K, "dtype": str(dtype), "order": order, "hermite_step_ms": t_full, "points": pts,
             "fit_T_full_ms": float(slope), "fit_F_us": float(icpt * 1e3)}
 
 
@@ -194,6 +234,31 @@ def orbit_f64(e=0.9, K=16):
     return out
 
 
+def orbit6(e=0.9, K=16):
+    """The eta sweep of the eccentric orbit at the 6th order beside the float64 4th order."""
+    x0, v0, m, period = ho.two_body(e)
+    out = []
+    for eta in (0.01, 0.0025, 0.000625):
+        row = {"eta": eta, "max_level": K}
+        for name, cls, fmt in (("order6", simulation.BlockHermite6Simulator, {}),
+                               ("order4_float64", simulation.BlockHermiteSimulator, {"dtype": torch.float64})):
+            kw = dict(positions=x0, velocities=v0, masses=m, softening=0.0, dt=period / 4, calc_energy=False,
+                      device="cuda", eta=eta, max_level=K, **fmt)
+            cls(**kw).step()                                    # warm
+            sim = cls(**kw)
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            s = _wall(lambda: [sim.step() for _ in range(4)])
+            e1.record()
+            torch.cuda.synchronize()
+            row[name] = {"err": ho.orbit_error(sim.positions.cpu().numpy(), x0), "pairs": sim.pair_interactions,
+                         "block_steps": sim.block_steps, "clamped": sim.clamped, "wall_s": s,
+                         "gpu_ms": e0.elapsed_time(e1)}
+        out.append(row)
+        print(json.dumps(row), flush=True)
+    return out
+
+
 def plummer(n=16384, eps=0.01):
     p, v, m = generate_plummer(n, seed=3)
     kw = dict(positions=p, velocities=v, masses=m, softening=eps, calc_energy=False, device="cuda")
@@ -233,10 +298,21 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--only", default="force,cost,orbit,plummer")
     ap.add_argument("--dtype", default="float32", choices=["float32", "float64"])
+    ap.add_argument("--order", type=int, default=4, choices=[4, 6])
     args = ap.parse_args()
     parts = args.only.split(",")
     res = {"device": torch.cuda.get_device_name(0)}
-    if args.dtype == "float64":
+    if args.order == 6:                                         # float64 only, whatever --dtype says
+        args.dtype = "order6"
+        args.out = args.out or os.path.join(ROOT, "profiles", "r23_hermite6_block.json")
+        if "force" in parts:
+            res["active_force_snap_f64"] = active_force6()
+        if "cost" in parts:
+            res["block_step_cost_order6"] = block_step_cost(dtype=torch.float64, order=6)
+            res["block_step_cost_f64"] = block_step_cost(dtype=torch.float64)
+        if "orbit" in parts:
+            res["orbit_e09"] = orbit6()
+    elif args.dtype == "float64":
         args.out = args.out or os.path.join(ROOT, "profiles", "r13_hermite_block_f64.json")
         if "force" in parts:
             res["active_force_f64"] = active_force_f64()
