@@ -706,7 +706,7 @@ int nbd_accel_jerk_active_f64(const double* posd, const double* veld, int n, con
                               double softening_sq, double g_const, double* acc_out, double* jerk_out, void* workspace,
                               size_t workspace_bytes, int slabs, nbd_stream_t stream);
 
-/* ---- block-timestep 6th-order Hermite (csrc/direct_hermite6_block_f64.hip): "6th-order Hermite" above with the
+/* ---- block-timestep 6th-order Hermite (csrc/direct_hermite_block_f64.hip): "6th-order Hermite" above with the
  * individual power-of-two steps of "double-precision block-timestep Hermite", float64 only. Body i keeps x, v, a, j, s
  * and the crackle c at its last correction tick; ticks, levels and sched are the int32 arrays of the block scheme, the
  * scheduler is nbd_hblock_schedule and the initial levels are nbd_hblock_init_levels_f64's. posd / veld / accd: the

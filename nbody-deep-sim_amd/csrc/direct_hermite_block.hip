@@ -160,16 +160,7 @@ size_t nbd_hblock_workspace_bytes(int n) {
 
 int nbd_hblock_init_levels(const float* acc, const float* jerk, int n, double dt, double eta, int max_level, int* ticks,
                            int* levels, int* sched, nbd_stream_t stream) {
-  if (n < 0 || bad_level(max_level) || !(dt > 0.0) || !(eta > 0.0)) return NBD_E_BADARG;
-  if (!sched) return NBD_E_BADARG;
-  if (n == 0) return 0;
-  if (!acc || !jerk || !ticks || !levels) return NBD_E_BADARG;
-  hipStream_t st = (hipStream_t)stream;
-  // T, the cursor and the histogram start from zero; t_next, n_act and the clamp count are left as they are
-  hipError_t e = hipMemsetAsync(sched + kTCur, 0, (NBD_HBLOCK_SCHED_INTS - kTCur) * sizeof(int), st);
-  if (e != hipSuccess) return (int)e;
-  hblock_init_kernel<float><<<ceil_div(n, 256), 256, 0, st>>>(acc, jerk, n, max_level, dt, eta, ticks, levels, sched);
-  return launch_status();
+  return hblock_init_levels(acc, jerk, n, dt, eta, max_level, ticks, levels, sched, (hipStream_t)stream);
 }
 
 int nbd_hblock_schedule(const int* levels, int n, int max_level, int* sched, void* workspace, size_t workspace_bytes,

@@ -1,6 +1,6 @@
 // hermite6_f64_kernels.h -- what the 6th-order Hermite translation units share (direct_hermite6_f64.hip: one system;
 // direct_batch_hermite6_f64.hip: many independent systems, shared timestep per system; direct_hermite_shard_f64.hip: one
-// rank's bodies of a range partition, beside the 4th order; direct_hermite6_block_f64.hip: an active list of targets,
+// rank's bodies of a range partition, beside the 4th order; direct_hermite_block_f64.hip: an active list of targets,
 // block timesteps, each body with its own step constants): the pair functor of the
 // acceleration + jerk + snap evaluation (AccelJerkSnapPair), the step constants (Hermite6Step, hermite6_step_constants)
 // and the per-row bodies of the predictor and of the finishing kernel (hermite6_predict_row, hermite6_finish_row). As in
@@ -87,7 +87,7 @@ struct AccelJerkSnapPair {
 };
 
 // The step constants: doubles formed from the double dt. On the device too: a block-timestep body
-// (direct_hermite6_block_f64.hip) forms them from its own step, so one whose step is the whole interval gets the shared
+// (direct_hermite_block_f64.hip) forms them from its own step, so one whose step is the whole interval gets the shared
 // step's bits.
 struct Hermite6Step { double dt, dt_half, dt2_half, dt3_6, dt4_24, dt5_120, dt2_10, dt3_120, dt2, dt3; };
 

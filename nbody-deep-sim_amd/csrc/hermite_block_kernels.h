@@ -1,14 +1,15 @@
 // hermite_block_kernels.h -- what the two block-timestep translation units share (direct_hermite_block.hip: fp32 state;
-// direct_hermite_block_f64.hip: fp64 state): the layout of the schedule record, the level arithmetic (criterion,
-// wanted_level, norm3), the re-levelling of a corrected body (hblock_relevel), and the three O(N) kernels as templates of
-// the state's scalar type T (hblock_init_kernel<T>, hblock_predict_kernel<T>, hblock_correct_kernel<T>), each unit
-// instantiating its own. Levels, ticks and the schedule are integers and the criterion is evaluated in fp64 in both
-// modes, so there is one copy of each; the scheduler itself (hblock_schedule_kernel, direct_hermite_block.hip) looks at
-// nothing else and serves both. The per-body arithmetic is hermite_kernels.h's (hermite_predict_row, hermite_slab_sum,
-// hermite_correct_row), the step constants hermite_step_constants<T> of the body's own fp64 step: a body whose step is
-// the whole interval gets the shared step's bits.
-// The 6th-order block unit (direct_hermite6_block_f64.hip) takes the record, the level arithmetic, hblock_move_level and
-// hblock6_relevel from here and has O(N) kernels of its own over hermite6_f64_kernels.h's rows.
+// direct_hermite_block_f64.hip: fp64 state, 4th and 6th order): the layout of the schedule record, the level arithmetic
+// (criterion, wanted_level, norm3), the re-levelling of a corrected body (hblock_relevel), the three O(N) kernels as
+// templates of the state's scalar type T (hblock_init_kernel<T>, hblock_predict_kernel<T>, hblock_correct_kernel<T>), each
+// unit instantiating its own, and the host body of the initial-levels entries (hblock_init_levels<T>). Levels, ticks and
+// the schedule are integers and the criterion is evaluated in fp64 in both modes, so there is one copy of each; the
+// scheduler itself (hblock_schedule_kernel, direct_hermite_block.hip) looks at nothing else and serves both. The per-body
+// arithmetic is hermite_kernels.h's (hermite_predict_row, hermite_slab_sum, hermite_correct_row), the step constants
+// hermite_step_constants<T> of the body's own fp64 step: a body whose step is the whole interval gets the shared step's
+// bits.
+// The 6th order of the fp64 unit takes the record, the level arithmetic, the initial levels, hblock_move_level and
+// hblock6_relevel from here and has O(N) kernels of its own, in that unit, over hermite6_f64_kernels.h's rows.
 // The definitions sit in an anonymous namespace: every translation unit that includes this file gets its own inlined copies.
 #pragma once
 #include <math.h>
@@ -72,6 +73,21 @@ __global__ __launch_bounds__(256) void hblock_init_kernel(const T* __restrict__ 
   }
   __syncthreads();
   if (threadIdx.x <= K && hist[threadIdx.x]) atomicAdd(&sched[kHist + threadIdx.x], hist[threadIdx.x]);
+}
+
+// The host body of nbd_hblock_init_levels (T = float) and nbd_hblock_init_levels_f64 (T = double).
+template <class T>
+int hblock_init_levels(const T* acc, const T* jerk, int n, double dt, double eta, int max_level, int* ticks, int* levels,
+                       int* sched, hipStream_t st) {
+  if (n < 0 || bad_level(max_level) || !(dt > 0.0) || !(eta > 0.0)) return NBD_E_BADARG;
+  if (!sched) return NBD_E_BADARG;
+  if (n == 0) return 0;
+  if (!acc || !jerk || !ticks || !levels) return NBD_E_BADARG;
+  // T, the cursor and the histogram start from zero; t_next, n_act and the clamp count are left as they are
+  hipError_t e = hipMemsetAsync(sched + kTCur, 0, (NBD_HBLOCK_SCHED_INTS - kTCur) * sizeof(int), st);
+  if (e != hipSuccess) return (int)e;
+  hblock_init_kernel<T><<<ceil_div(n, 256), 256, 0, st>>>(acc, jerk, n, max_level, dt, eta, ticks, levels, sched);
+  return launch_status();
 }
 
 // posm = {x_p, m}, velp = {v_p, 0} for rows [0, n_pad) (zero rows behind n): every body predicted from its last
@@ -147,7 +163,7 @@ __device__ __forceinline__ void hblock_relevel(const T* a0, const T* j0, const T
   hblock_move_level(wanted_level(crit, dt, K), K, lev, d, i, first, ticks, levels, sched);
 }
 
-// ... and of a 6th-order body (direct_hermite6_block_f64.hip), corrected from (a0, j0, s0) to (a1, j1, s1) with the
+// ... and of a 6th-order body (direct_hermite_block_f64.hip), corrected from (a0, j0, s0) to (a1, j1, s1) with the
 // crackle c1 just formed: the generalised criterion of Nitadori & Makino (2008) for p = 6, with eta in the 4th-order
 // convention (dt_i = sqrt(eta ...) there),
 //   dt_i = (eta^3 (|a1||s1| + |j1|^2) / (|c1||a5| + |a4(t1)|^2))^(1/6)  = cbrt(criterion(eta^3, num, den)),
@@ -202,6 +218,5 @@ __global__ __launch_bounds__(256) void hblock_correct_kernel(const T* __restrict
   posm[i] = hermite_row(c.x1, mass[i]);
   hblock_relevel(c.a0, c.j0, a1, j1, h, dt, eta, K, lev, d, i, p == 0, ticks, levels, sched);
 }
-
 
 }  // namespace

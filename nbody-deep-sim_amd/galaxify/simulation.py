@@ -323,8 +323,9 @@ class _Float32:
     block_workspace = staticmethod(direct.hblock_workspace)
     block_init_levels = staticmethod(direct.hblock_init_levels)
 
-    def block_step(self, s, *state):
-        direct.hblock_step(*state, s._eps2, s._g, s._sched, s._posm, s._velp, s._bws)
+    def block_step(self, s, n_act: int):
+        direct.hblock_step(s.positions, s.velocities, s.accelerations, s.jerks, s.masses, s._ticks, s.levels, n_act,
+                           s.max_level, s.dt, s.eta, s._eps2, s._g, s._sched, s._posm, s._velp, s._bws)
 
 
 class _Float64:
@@ -424,8 +425,9 @@ class _Float64:
     block_workspace = staticmethod(direct.hblock_f64_workspace)
     block_init_levels = staticmethod(direct.hblock_init_levels_f64)
 
-    def block_step(self, s, *state):
-        direct.hblock_step_f64(*state, *self._scalars(s), s._sched, s._posd, s._veld, s._bws)
+    def block_step(self, s, n_act: int):
+        direct.hblock_step_f64(s.positions, s.velocities, s.accelerations, s.jerks, s.masses, s._ticks, s.levels, n_act,
+                               s.max_level, s.dt, s.eta, *self._scalars(s), s._sched, s._posd, s._veld, s._bws)
 
 
 class _Hermite6Float64(_Float64):
@@ -465,9 +467,14 @@ class _Hermite6Float64(_Float64):
         direct.hermite6_shard_force_remote_f64(s._rows_all, s.n, s._rows_local, p.n_local, p.lo, *self._scalars(s),
                                                *new[:3], s._hws, **step)
 
-    # BlockHermite6Simulator (csrc/direct_hermite6_block_f64.hip): 9 doubles per listed body and slab; the initial levels
-    # are the inherited block_init_levels, from a and j
+    # BlockHermite6Simulator (the 6th order of csrc/direct_hermite_block_f64.hip): 9 doubles per listed body and slab; the
+    # initial levels are the inherited block_init_levels, from a and j
     block_workspace = staticmethod(direct.hblock6_workspace)
+
+    def block_step(self, s, n_act: int):
+        direct.hblock6_step_f64(s.positions, s.velocities, s.accelerations, s.jerks, s.snaps, s.crackles, s.masses,
+                                s._ticks, s.levels, n_act, s.max_level, s.dt, s.eta, *self._scalars(s), s._sched,
+                                s._posd, s._veld, s._accd, s._bws)
 
 
 _FORMATS = {fmt.dtype: fmt for fmt in (_Float32(), _Float64())}
@@ -1116,11 +1123,18 @@ class Hermite6Simulator(HermiteSimulator):
 class _BlockSteps:
     """What the block-timestep simulators share (BlockHermiteSimulator, BlockHermite6Simulator), mixed in in front of the
     shared-timestep class whose scheme they run: the parameters `eta` and `max_level`, the int32 schedule state, the
-    counters, the initial levels and the loop of block steps that makes one step(). The class states `_block_step(n_act)`,
-    the predict, force and correct of the block step the schedule has just listed; its format object gives the
-    workspace (`block_workspace`) and the initial levels (`block_init_levels`, from `accelerations` and `jerks`)."""
+    counters, the initial levels, the loop of block steps that makes one step() and the refusal of `process_group`. The
+    class's format object gives the workspace (`block_workspace`), the initial levels (`block_init_levels`, from
+    `accelerations` and `jerks`) and `block_step(sim, n_act)`: the predict, force and correct of the block step the
+    schedule has just listed, over the simulator's own state arrays."""
 
     MAX_LEVEL_LIMIT = 20
+
+    @classmethod
+    def _refuse_process_group(cls, process_group):
+        if process_group is not None:
+            raise ValueError(f"{cls.__name__}: there is no range-sharded block-timestep step; process_group is not "
+                             "supported")
 
     def _init_block(self, eta, max_level):
         self.eta = eta
@@ -1173,7 +1187,7 @@ class _BlockSteps:
             t_next, n_act = int(host[0]), int(host[1])
             if not (t_prev < t_next <= end and 1 <= n_act <= self.n):
                 raise RuntimeError(f"{who}: corrupt schedule (t_next={t_next}, n_act={n_act}, previous tick {t_prev})")
-            self._block_step(n_act)
+            self._fmt.block_step(self, n_act)
             self.block_steps += 1
             self.pair_interactions += n_act * self.n
             if self.level_history is not None:
@@ -1215,25 +1229,18 @@ class BlockHermiteSimulator(_BlockSteps, HermiteSimulator):
                  eta: float = 0.02, max_level: int = 10, calc_invariants: bool = False, **hermite_kw):
         # hermite_kw: the keywords that are HermiteSimulator's own and mean here what they mean there -- `dtype`
         # (default torch.float32). They go to HermiteSimulator.__init__ as given, which refuses a name it does not know.
-        if process_group is not None:
-            raise ValueError("BlockHermiteSimulator: there is no range-sharded block-timestep step; process_group is not "
-                             "supported")
+        self._refuse_process_group(process_group)
         self._check_dtype(hermite_kw.get("dtype", torch.float32), None)     # before anything is resolved or allocated
         super().__init__(positions=positions, velocities=velocities, masses=masses, g_const=g_const,
                          softening=softening, dt=dt, calc_energy=calc_energy, device=device,
                          calc_invariants=calc_invariants, **hermite_kw)
         self._init_block(eta, max_level)
 
-    def _block_step(self, n_act: int):
-        """Predict, force and correct of the block step the schedule has just listed."""
-        self._fmt.block_step(self, self.positions, self.velocities, self.accelerations, self.jerks, self.masses,
-                             self._ticks, self.levels, n_act, self.max_level, self.dt, self.eta)
-
 
 class BlockHermite6Simulator(_BlockSteps, Hermite6Simulator):
     """Hermite6Simulator with individual block timesteps, the form Nitadori & Makino (2008) wrote the scheme for
-    (csrc/direct_hermite6_block_f64.hip), an extension the reference does not have. `dt` is the output
-    interval and the longest step: one step() advances every body by dt, in 2^max_level ticks. Body i carries x, v, a, j,
+    (csrc/direct_hermite_block_f64.hip at the 6th order), an extension the reference does not have.
+    `dt` is the output interval and the longest step: one step() advances every body by dt, in 2^max_level ticks. Body i carries x, v, a, j,
     s and the crackle c at its last correction and moves with its own step h_i = dt 2^-k_i, k_i = levels[i] in
     [0, max_level]. A block step predicts every body to the next due time by Hermite6Simulator's Taylor series over its
     own elapsed time, evaluates a1, j1, s1 of the due bodies against all predicted bodies, corrects them with their own
@@ -1261,20 +1268,11 @@ class BlockHermite6Simulator(_BlockSteps, Hermite6Simulator):
         if dtype is not torch.float64:
             raise ValueError(f"BlockHermite6Simulator: dtype must be torch.float64, got {dtype!r}: there is no fp32 form "
                              "of the 6th-order scheme")
-        if process_group is not None:
-            raise ValueError("BlockHermite6Simulator: there is no range-sharded block-timestep step; process_group is "
-                             "not supported")
+        self._refuse_process_group(process_group)
         super().__init__(positions=positions, velocities=velocities, masses=masses, g_const=g_const,
                          softening=softening, dt=dt, calc_energy=calc_energy, device=device,
                          calc_invariants=calc_invariants, **format_kw)
         self._init_block(eta, max_level)
-
-    def _block_step(self, n_act: int):
-        """Predict, force and correct of the block step the schedule has just listed."""
-        direct.hblock6_step_f64(self.positions, self.velocities, self.accelerations, self.jerks, self.snaps,
-                                self.crackles, self.masses, self._ticks, self.levels, n_act, self.max_level, self.dt,
-                                self.eta, *self._fmt._scalars(self), self._sched, self._posd, self._veld, self._accd,
-                                self._bws)
 
 
 def _per_scene(x, n_scenes: int, name: str) -> list:

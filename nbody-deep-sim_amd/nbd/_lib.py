@@ -326,7 +326,7 @@ SIGNATURES = {
                                     c_void_p, c_size_t, c_void_p]),
     "nbd_accel_jerk_active_f64": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_double, c_double, c_void_p,
                                           c_void_p, c_void_p, c_size_t, c_int, c_void_p]),
-    # --- block-timestep 6th-order Hermite (csrc/direct_hermite6_block_f64.hip)
+    # --- block-timestep 6th-order Hermite (csrc/direct_hermite_block_f64.hip)
     "nbd_hblock6_f64_workspace_bytes": (c_size_t, [c_int]),
     "nbd_hblock6_predict_f64": (c_int, [c_void_p] * 8 + [c_int, c_int, c_double] + [c_void_p] * 5),
     "nbd_hblock6_force_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_double, c_void_p, c_size_t,

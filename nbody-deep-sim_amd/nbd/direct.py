@@ -904,12 +904,30 @@ def _chk_sched(n: int, ticks, levels, sched):
     _chk(sched, (HBLOCK_SCHED_INTS,), "sched", torch.int32)
 
 
-def _chk_hblock(dtype, pos, vel, acc, jerk, mass, ticks, levels, sched, pos_rows, vel_rows) -> int:
-    """The arguments of a block step in `dtype` (state, packed rows, int32 schedule arrays); returns n."""
-    n = pos.shape[0]
-    _chk_n3(dtype, n, ("pos", "vel", "acc", "jerk"), pos, vel, acc, jerk)
+_HBLOCK_STATE = ("pos", "vel", "acc", "jerk", "snap", "crackle")      # the 4th order carries the first four
+
+
+def _chk_block_rows(dtype, n: int, rows):
+    """The packed source arrays a block entry takes, (pos_rows[, vel_rows[, accd]]), as _chk_packed and _chk_accd check
+    them."""
+    shape = (padded_len(n), 4)
+    for t, name in zip(rows, ("posm", "velp") if dtype == torch.float32 else ("posd", "veld", "accd")):
+        _chk(t, shape, name, dtype)
+
+
+def _ptrs(tensors):
+    """The device pointers of a state or row tuple, for a launch's argument list. (A map, not a generator expression: this
+    runs in every eager block step, and the generator's frames cost a measurable part of one.)"""
+    return map(torch.Tensor.data_ptr, tensors)
+
+
+def _chk_hblock(dtype, state, mass, ticks, levels, sched, rows) -> int:
+    """The arguments of a block step in `dtype`: state = the (n,3) arrays (pos, vel, acc, jerk[, snap, crackle]), rows =
+    the packed rows the entry takes (pos_rows[, vel_rows[, accd]]), the int32 schedule arrays; returns n."""
+    n = state[0].shape[0]
+    _chk_n3(dtype, n, _HBLOCK_STATE, *state)
     _chk(mass, (n,), "mass", dtype)
-    _chk_packed(dtype, pos_rows, vel_rows, n)
+    _chk_block_rows(dtype, n, rows)
     _chk_sched(n, ticks, levels, sched)
     return n
 
@@ -944,52 +962,77 @@ def hblock_schedule(levels, max_level: int, sched, workspace, host_sched=None) -
                 workspace.data_ptr(), _nbytes(workspace), _lib.ptr(host_sched))
 
 
-def _hblock_step(dtype, entry: str, pos, vel, acc, jerk, mass, ticks, levels, n_act, max_level, dt, eta, softening_sq,
-                 g_const, sched, rows, vrows, workspace) -> None:
-    n = _chk_hblock(dtype, pos, vel, acc, jerk, mass, ticks, levels, sched, rows, vrows)
-    _lib.launch(entry, pos.device, pos.data_ptr(), vel.data_ptr(), acc.data_ptr(), jerk.data_ptr(), mass.data_ptr(),
-                ticks.data_ptr(), levels.data_ptr(), n, int(n_act), int(max_level), float(dt), float(eta),
-                float(softening_sq), float(g_const), sched.data_ptr(), rows.data_ptr(), vrows.data_ptr(),
-                workspace.data_ptr(), _nbytes(workspace))
+def _hblock_step(dtype, entry: str, state, mass, ticks, levels, n_act, max_level, dt, eta, softening_sq, g_const, sched,
+                 rows, workspace) -> None:
+    """A whole block step of either order and format: the state tuple gives the leading pointers, the row tuple the
+    trailing ones."""
+    n = _chk_hblock(dtype, state, mass, ticks, levels, sched, rows)
+    _lib.launch(entry, state[0].device, *_ptrs(state), mass.data_ptr(), ticks.data_ptr(), levels.data_ptr(), n, int(n_act),
+                int(max_level), float(dt), float(eta), float(softening_sq), float(g_const), sched.data_ptr(),
+                *_ptrs(rows), workspace.data_ptr(), _nbytes(workspace))
 
 
 def hblock_step(pos, vel, acc, jerk, mass, ticks, levels, n_act: int, max_level: int, dt: float, eta: float,
                 softening_sq: float, g_const: float, sched, posm, velp, workspace) -> None:
     """Predict all bodies to t_next, evaluate the n_act listed ones, correct and re-level them (three launches). pos, vel,
     acc, jerk, ticks, levels in place for the active bodies; posm = {x1, m} for them, predicted rows for the rest."""
-    _hblock_step(torch.float32, "nbd_hblock_step_f32", pos, vel, acc, jerk, mass, ticks, levels, n_act, max_level, dt,
-                 eta, softening_sq, g_const, sched, posm, velp, workspace)
+    _hblock_step(torch.float32, "nbd_hblock_step_f32", (pos, vel, acc, jerk), mass, ticks, levels, n_act, max_level, dt,
+                 eta, softening_sq, g_const, sched, (posm, velp), workspace)
 
 
-def _accel_jerk_active(dtype, entry: str, rows, vrows, n, act, softening_sq, g_const, workspace, new_workspace, *slabs):
-    """new_workspace(device, n_act): the workspace where none is given."""
-    _chk_packed(dtype, rows, vrows, n)
+def _accel_jerk_active(dtype, entry: str, rows, n, act, softening_sq, g_const, workspace, new_workspace, *slabs):
+    """The force of a list on its own: one (len(act), 3) output per packed source array of `rows` (acc, jerk[, snap]).
+    new_workspace(device, n_act): the workspace where none is given."""
+    _chk_block_rows(dtype, n, rows)
     _chk(act, None, "act", torch.int32)
     n_act = act.numel()
-    dev = rows.device
-    acc_out = torch.empty((n_act, 3), dtype=dtype, device=dev)
-    jerk_out = torch.empty((n_act, 3), dtype=dtype, device=dev)
+    dev = rows[0].device
+    outs = tuple(torch.empty((n_act, 3), dtype=dtype, device=dev) for _ in rows)
     if workspace is None:                       # a given workspace is checked by the entry, against what this call uses
         workspace = new_workspace(dev, n_act)
-    _lib.launch(entry, dev, rows.data_ptr(), vrows.data_ptr(), n, act.data_ptr(), n_act, float(softening_sq),
-                float(g_const), acc_out.data_ptr(), jerk_out.data_ptr(), workspace.data_ptr(), _nbytes(workspace),
-                *map(int, slabs))
-    return acc_out, jerk_out
+    _lib.launch(entry, dev, *_ptrs(rows), n, act.data_ptr(), n_act, float(softening_sq), float(g_const), *_ptrs(outs),
+                workspace.data_ptr(), _nbytes(workspace), *map(int, slabs))
+    return outs
 
 
 def accel_jerk_active(posm, velp, n: int, act, softening_sq: float, g_const: float, workspace=None):
     """(acc, jerk), each (len(act), 3), of the bodies act (a device int32 list, any order) under all n bodies of posm /
     velp, in list order. The all-bodies list gives accel_jerk's bits."""
-    return _accel_jerk_active(torch.float32, "nbd_accel_jerk_active_f32", posm, velp, n, act, softening_sq, g_const,
+    return _accel_jerk_active(torch.float32, "nbd_accel_jerk_active_f32", (posm, velp), n, act, softening_sq, g_const,
                               workspace, lambda dev, n_act: hblock_workspace(n, dev))
 
 
-# ------------------------------- double-precision block-timestep Hermite (csrc/direct_hermite_block_f64.hip)
+# ---------------- double-precision block-timestep Hermite, 4th and 6th order (csrc/direct_hermite_block_f64.hip)
+def _hblock_f64_workspace(entry: str, sums: int, n, device, slabs, n_act) -> torch.Tensor:
+    """`entry`(n) bytes, or the list and `sums` doubles per slab and target of an explicit slab count on n_act targets."""
+    need = getattr(_lib.lib(), entry)(int(n))
+    return alloc_bytes(max(need, (int(n) + 7) // 8 * 32 + int(slabs) * sums * int(n_act) * 8), device)
+
+
+def _hblock_predict(entry: str, state, mass, ticks, levels, max_level, dt, sched, rows) -> None:
+    n = _chk_hblock(F64, state, mass, ticks, levels, sched, rows)
+    _lib.launch(entry, state[0].device, *_ptrs(state), mass.data_ptr(), ticks.data_ptr(), n, int(max_level), float(dt),
+                sched.data_ptr(), *_ptrs(rows))
+
+
+def _hblock_force(entry: str, rows, n, n_act, softening_sq, workspace) -> None:
+    _chk_block_rows(F64, n, rows)
+    _lib.launch(entry, rows[0].device, *_ptrs(rows), n, int(n_act), float(softening_sq), workspace.data_ptr(),
+                _nbytes(workspace))
+
+
+def _hblock_correct(entry: str, state, mass, ticks, levels, n_act, max_level, dt, eta, g_const, sched, posd,
+                    workspace) -> None:
+    n = _chk_hblock(F64, state, mass, ticks, levels, sched, (posd,))
+    _lib.launch(entry, state[0].device, *_ptrs(state), mass.data_ptr(), ticks.data_ptr(), levels.data_ptr(), n, int(n_act),
+                int(max_level), float(dt), float(eta), float(g_const), sched.data_ptr(), posd.data_ptr(),
+                workspace.data_ptr(), _nbytes(workspace))
+
+
 def hblock_f64_workspace(n: int, device, slabs: int = 0, n_act: int = 0) -> torch.Tensor:
     """Active list + float64 partial sums of one block step (nbd_hblock_f64_workspace_bytes), or of accel_jerk_active_f64
     with an explicit slab count on n_act targets."""
-    need = _lib.lib().nbd_hblock_f64_workspace_bytes(int(n))
-    return alloc_bytes(max(need, (int(n) + 7) // 8 * 32 + int(slabs) * 6 * int(n_act) * 8), device)
+    return _hblock_f64_workspace("nbd_hblock_f64_workspace_bytes", 6, n, device, slabs, n_act)
 
 
 def hblock_init_levels_f64(acc, jerk, dt: float, eta: float, max_level: int, ticks, levels, sched) -> None:
@@ -999,91 +1042,59 @@ def hblock_init_levels_f64(acc, jerk, dt: float, eta: float, max_level: int, tic
 
 def hblock_predict_f64(pos, vel, acc, jerk, mass, ticks, levels, max_level: int, dt: float, sched, posd, veld) -> None:
     """First launch of a float64 block step: every body predicted to t_next = sched[0] into posd / veld."""
-    n = _chk_hblock(F64, pos, vel, acc, jerk, mass, ticks, levels, sched, posd, veld)
-    _lib.launch("nbd_hblock_predict_f64", pos.device, pos.data_ptr(), vel.data_ptr(), acc.data_ptr(), jerk.data_ptr(),
-                mass.data_ptr(), ticks.data_ptr(), n, int(max_level), float(dt), sched.data_ptr(), posd.data_ptr(),
-                veld.data_ptr())
+    _hblock_predict("nbd_hblock_predict_f64", (pos, vel, acc, jerk), mass, ticks, levels, max_level, dt, sched,
+                    (posd, veld))
 
 
 def hblock_force_f64(posd, veld, n: int, n_act: int, softening_sq: float, workspace) -> None:
     """Second launch: the partial sums of the n_act bodies the schedule listed in the workspace."""
-    _chk_packed(F64, posd, veld, n)
-    _lib.launch("nbd_hblock_force_f64", posd.device, posd.data_ptr(), veld.data_ptr(), n, int(n_act),
-                float(softening_sq), workspace.data_ptr(), _nbytes(workspace))
+    _hblock_force("nbd_hblock_force_f64", (posd, veld), n, n_act, softening_sq, workspace)
 
 
 def hblock_correct_f64(pos, vel, acc, jerk, mass, ticks, levels, n_act: int, max_level: int, dt: float, eta: float,
                        g_const: float, sched, posd, workspace) -> None:
     """Third launch: slab sum, corrector and new level of the listed bodies; posd = {x1, m} for them."""
-    n = _chk_hblock(F64, pos, vel, acc, jerk, mass, ticks, levels, sched, posd, None)
-    _lib.launch("nbd_hblock_correct_f64", pos.device, pos.data_ptr(), vel.data_ptr(), acc.data_ptr(), jerk.data_ptr(),
-                mass.data_ptr(), ticks.data_ptr(), levels.data_ptr(), n, int(n_act), int(max_level), float(dt),
-                float(eta), float(g_const), sched.data_ptr(), posd.data_ptr(), workspace.data_ptr(), _nbytes(workspace))
+    _hblock_correct("nbd_hblock_correct_f64", (pos, vel, acc, jerk), mass, ticks, levels, n_act, max_level, dt, eta,
+                    g_const, sched, posd, workspace)
 
 
 def hblock_step_f64(pos, vel, acc, jerk, mass, ticks, levels, n_act: int, max_level: int, dt: float, eta: float,
                     softening_sq: float, g_const: float, sched, posd, veld, workspace) -> None:
     """hblock_step in float64 (three launches): dt, eta, softening_sq and g_const go in as the Python doubles."""
-    _hblock_step(F64, "nbd_hblock_step_f64", pos, vel, acc, jerk, mass, ticks, levels, n_act, max_level, dt, eta,
-                 softening_sq, g_const, sched, posd, veld, workspace)
+    _hblock_step(F64, "nbd_hblock_step_f64", (pos, vel, acc, jerk), mass, ticks, levels, n_act, max_level, dt, eta,
+                 softening_sq, g_const, sched, (posd, veld), workspace)
 
 
 def accel_jerk_active_f64(posd, veld, n: int, act, softening_sq: float, g_const: float, workspace=None, slabs: int = 0):
     """accel_jerk_active in float64: (acc, jerk), each (len(act), 3) float64, in list order. slabs: 0 = the plan's source
     split, else that many. The all-bodies list gives accel_jerk_f64's bits at the same slab count."""
-    return _accel_jerk_active(F64, "nbd_accel_jerk_active_f64", posd, veld, n, act, softening_sq, g_const, workspace,
+    return _accel_jerk_active(F64, "nbd_accel_jerk_active_f64", (posd, veld), n, act, softening_sq, g_const, workspace,
                               lambda dev, n_act: hblock_f64_workspace(n, dev, slabs, n_act), slabs)
-
-
-# ------------------------------------- block-timestep 6th-order Hermite, float64 (csrc/direct_hermite6_block_f64.hip)
-_HBLOCK6_STATE = ("pos", "vel", "acc", "jerk", "snap", "crackle")
-
-
-def _chk_hblock6(state, mass, ticks, levels, sched, posd, veld, accd) -> int:
-    """The arguments of a 6th-order block step (the six (n,3) state arrays, packed rows, int32 schedule arrays); veld and
-    accd None where the entry takes none. Returns n."""
-    n = state[0].shape[0]
-    _chk_n3(F64, n, _HBLOCK6_STATE, *state)
-    _chk(mass, (n,), "mass", F64)
-    _chk_packed(F64, posd, veld, n)
-    if accd is not None:
-        _chk_accd(accd, n)
-    _chk_sched(n, ticks, levels, sched)
-    return n
 
 
 def hblock6_workspace(n: int, device, slabs: int = 0, n_act: int = 0) -> torch.Tensor:
     """Active list + float64 partial sums of one 6th-order block step (nbd_hblock6_f64_workspace_bytes), or of
     accel_jerk_snap_active_f64 with an explicit slab count on n_act targets."""
-    need = _lib.lib().nbd_hblock6_f64_workspace_bytes(int(n))
-    return alloc_bytes(max(need, (int(n) + 7) // 8 * 32 + int(slabs) * 9 * int(n_act) * 8), device)
+    return _hblock_f64_workspace("nbd_hblock6_f64_workspace_bytes", 9, n, device, slabs, n_act)
 
 
 def hblock6_predict_f64(pos, vel, acc, jerk, snap, crackle, mass, ticks, levels, max_level: int, dt: float, sched, posd,
                         veld, accd) -> None:
     """First launch of a 6th-order block step: every body predicted to t_next = sched[0] into posd / veld / accd."""
-    state = (pos, vel, acc, jerk, snap, crackle)
-    n = _chk_hblock6(state, mass, ticks, levels, sched, posd, veld, accd)
-    _lib.launch("nbd_hblock6_predict_f64", pos.device, *(t.data_ptr() for t in state), mass.data_ptr(),
-                ticks.data_ptr(), n, int(max_level), float(dt), sched.data_ptr(), posd.data_ptr(), veld.data_ptr(),
-                accd.data_ptr())
+    _hblock_predict("nbd_hblock6_predict_f64", (pos, vel, acc, jerk, snap, crackle), mass, ticks, levels, max_level, dt,
+                    sched, (posd, veld, accd))
 
 
 def hblock6_force_f64(posd, veld, accd, n: int, n_act: int, softening_sq: float, workspace) -> None:
     """Second launch: the partial sums of the n_act bodies the schedule listed in the workspace."""
-    _chk_packed(F64, posd, veld, n); _chk_accd(accd, n)
-    _lib.launch("nbd_hblock6_force_f64", posd.device, posd.data_ptr(), veld.data_ptr(), accd.data_ptr(), n, int(n_act),
-                float(softening_sq), workspace.data_ptr(), _nbytes(workspace))
+    _hblock_force("nbd_hblock6_force_f64", (posd, veld, accd), n, n_act, softening_sq, workspace)
 
 
 def hblock6_correct_f64(pos, vel, acc, jerk, snap, crackle, mass, ticks, levels, n_act: int, max_level: int, dt: float,
                         eta: float, g_const: float, sched, posd, workspace) -> None:
     """Third launch: slab sum, corrector, crackle and new level of the listed bodies; posd = {x1, m} for them."""
-    state = (pos, vel, acc, jerk, snap, crackle)
-    n = _chk_hblock6(state, mass, ticks, levels, sched, posd, None, None)
-    _lib.launch("nbd_hblock6_correct_f64", pos.device, *(t.data_ptr() for t in state), mass.data_ptr(),
-                ticks.data_ptr(), levels.data_ptr(), n, int(n_act), int(max_level), float(dt), float(eta),
-                float(g_const), sched.data_ptr(), posd.data_ptr(), workspace.data_ptr(), _nbytes(workspace))
+    _hblock_correct("nbd_hblock6_correct_f64", (pos, vel, acc, jerk, snap, crackle), mass, ticks, levels, n_act,
+                    max_level, dt, eta, g_const, sched, posd, workspace)
 
 
 def hblock6_step_f64(pos, vel, acc, jerk, snap, crackle, mass, ticks, levels, n_act: int, max_level: int, dt: float,
@@ -1091,12 +1102,8 @@ def hblock6_step_f64(pos, vel, acc, jerk, snap, crackle, mass, ticks, levels, n_
     """Predict all bodies to t_next, evaluate the n_act listed ones, correct and re-level them (three launches). pos, vel,
     acc, jerk, snap, crackle, ticks, levels in place for the active bodies; posd = {x1, m} for them, predicted rows for
     the rest. dt, eta, softening_sq and g_const go in as the Python doubles."""
-    state = (pos, vel, acc, jerk, snap, crackle)
-    n = _chk_hblock6(state, mass, ticks, levels, sched, posd, veld, accd)
-    _lib.launch("nbd_hblock6_step_f64", pos.device, *(t.data_ptr() for t in state), mass.data_ptr(), ticks.data_ptr(),
-                levels.data_ptr(), n, int(n_act), int(max_level), float(dt), float(eta), float(softening_sq),
-                float(g_const), sched.data_ptr(), posd.data_ptr(), veld.data_ptr(), accd.data_ptr(),
-                workspace.data_ptr(), _nbytes(workspace))
+    _hblock_step(F64, "nbd_hblock6_step_f64", (pos, vel, acc, jerk, snap, crackle), mass, ticks, levels, n_act,
+                 max_level, dt, eta, softening_sq, g_const, sched, (posd, veld, accd), workspace)
 
 
 def accel_jerk_snap_active_f64(posd, veld, accd, n: int, act, softening_sq: float, g_const: float, workspace=None,
@@ -1104,17 +1111,8 @@ def accel_jerk_snap_active_f64(posd, veld, accd, n: int, act, softening_sq: floa
     """(acc, jerk, snap), each (len(act), 3) float64, of the bodies act (a device int32 list, any order) under all n
     bodies of posd / veld / accd, in list order. slabs: 0 = the plan's source split, else that many. The all-bodies list
     gives accel_jerk_snap_f64's bits at the same slab count."""
-    _chk_packed(F64, posd, veld, n); _chk_accd(accd, n)
-    _chk(act, None, "act", torch.int32)
-    n_act = act.numel()
-    dev = posd.device
-    acc_out, jerk_out, snap_out = (torch.empty((n_act, 3), dtype=F64, device=dev) for _ in range(3))
-    if workspace is None:                       # a given workspace is checked by the entry, against what this call uses
-        workspace = hblock6_workspace(n, dev, slabs, n_act)
-    _lib.launch("nbd_accel_jerk_snap_active_f64", dev, posd.data_ptr(), veld.data_ptr(), accd.data_ptr(), n,
-                act.data_ptr(), n_act, float(softening_sq), float(g_const), acc_out.data_ptr(), jerk_out.data_ptr(),
-                snap_out.data_ptr(), workspace.data_ptr(), _nbytes(workspace), int(slabs))
-    return acc_out, jerk_out, snap_out
+    return _accel_jerk_active(F64, "nbd_accel_jerk_snap_active_f64", (posd, veld, accd), n, act, softening_sq, g_const,
+                              workspace, lambda dev, n_act: hblock6_workspace(n, dev, slabs, n_act), slabs)
 
 
 # ---------------------------------------------------------------- batched direct integrator (csrc/direct_batch.hip)

@@ -1,5 +1,5 @@
 """fp64 numpy restatement of the block-timestep 6th-order Hermite integrator that BlockHermite6Simulator runs
-(csrc/direct_hermite6_block_f64.hip), built on hermite6_oracle (the pair sums, the start, the crackle) and
+(csrc/direct_hermite_block_f64.hip), built on hermite6_oracle (the pair sums, the start, the crackle) and
 block_hermite_oracle (wanted_level, _margin, the level rules, the planted-binary sphere).
 
 One output interval dt is 2^K ticks (K = max_level). Body i keeps x, v, a, j, s and the crackle c at its last correction

@@ -1,6 +1,6 @@
 """BlockHermite6Simulator and the nbd_hblock6_*_f64 / nbd_accel_jerk_snap_active_f64 kernels on the MI355X
-(csrc/direct_hermite6_block_f64.hip): max_level 0 is Hermite6Simulator bit for bit, the active-subset force at the accuracy
-bars of tests/hermite_f64_oracle.py and bit-equal to the all-bodies kernel, levels and state against the fp64 block oracle
+(the 6th order of csrc/direct_hermite_block_f64.hip): max_level 0 is Hermite6Simulator bit for bit, the active-subset
+force at the accuracy bars of tests/hermite_f64_oracle.py and bit-equal to the all-bodies kernel, levels and state against the fp64 block oracle
 (tests/block_hermite6_oracle.py), the eccentric orbit the order pays on, run() against eager steps and the edge cases of
 the 4th-order block mode. No input is fp32-representable (the orbit: see block_hermite_f64_cases.orbit), and every
 workspace is NaN-filled before a call."""
@@ -207,22 +207,23 @@ def test_cancellation_case(gpu_device):
 
 # ---------------------------------------------------------------- 3. levels and state against the fp64 oracle
 def _watch_crackles(sim, failed):
-    """Wrap sim._block_step: after every block step the crackle of each listed body is the c1 formula on the simulator's own
-    (a, j, s) before and after, with the body's own step, componentwise within 16 * 2^-53 of the sum of its |terms|
-    (test_hermite6_gpu.py's bar and factor)."""
-    inner = sim._block_step
+    """Wrap the block step of sim's format object (which is returned, to be put back): after every block step the crackle
+    of each listed body is the c1 formula on the simulator's own (a, j, s) before and after, with the body's own step,
+    componentwise within 16 * 2^-53 of the sum of its |terms| (test_hermite6_gpu.py's bar and factor)."""
+    inner = sim._fmt
 
-    def step(n_act):
+    def step(fmt, s, n_act):
         act = _np(sim._bws[: 4 * n_act].view(torch.int32)).astype(np.int64)
         h = (sim.dt * 2.0 ** -_np(sim.levels)[act].astype(np.float64))[:, None]
         before = [_np(t)[act] for t in (sim.accelerations, sim.jerks, sim.snaps)]
-        inner(n_act)
+        inner.block_step(s, n_act)
         after = [_np(t)[act] for t in (sim.accelerations, sim.jerks, sim.snaps)]
         err = np.abs(_np(sim.crackles)[act] - h6.crackle(*before, *after, h))
         tol = 16 * fo.U53 * h6.crackle_abs(*before, *after, h)
         if not np.all(err <= tol):
             failed.append((sim.block_steps, float((err / tol).max())))
-    sim._block_step = step
+    sim._fmt = type("Watched", (type(inner),), {"block_step": step})()
+    return inner
 
 
 @pytest.mark.parametrize("eps", [0.0, 0.01])
@@ -237,9 +238,9 @@ def test_levels_and_state_match_the_fp64_oracle(gpu_device, eps):
     sim = _sim("BlockHermite6Simulator", x, v, m, softening=eps, dt=c6.DT, eta=c6.ETA, max_level=c6.K)
     sim.level_history = []
     bad_crackles = []
-    _watch_crackles(sim, bad_crackles)
+    fmt = _watch_crackles(sim, bad_crackles)
     sim.step()
-    del sim._block_step
+    sim._fmt = fmt
     assert sim.block_steps == want["block_steps"] and sim.pair_interactions == want["pair_interactions"]
     assert len(sim.level_history) == len(want["history"])
     for k, (a, b) in enumerate(zip(sim.level_history, want["history"])):

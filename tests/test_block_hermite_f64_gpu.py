@@ -368,6 +368,32 @@ def test_default_dtype_is_untouched(gpu_device):
     assert wide.positions.dtype == F64 and wide.block_steps >= 1
 
 
+@pytest.mark.parametrize("order", [4, 6])
+def test_a_refused_step_launches_nothing(gpu_device, order):
+    """n = 65 with all 65 listed (two target groups, the second ragged) and a workspace 32 bytes short of
+    nbd_hblock(6)_f64_workspace_bytes(65), still 32-byte aligned: the step is refused for the size (-2) before its first
+    launch, so the packed rows the predictor would overwrite keep their sentinel, bit for bit."""
+    from nbd import _lib, direct
+    n, K, sentinel = 65, 4, -1234.5625
+    rng = np.random.default_rng(65)
+    state = [_dev(rng.standard_normal((n, 3)) + 0.1, gpu_device) for _ in range(order)]
+    mass = _dev(rng.uniform(0.5, 1.5, n), gpu_device)
+    ticks, levels = (torch.zeros(n, dtype=torch.int32, device=gpu_device) for _ in range(2))
+    sched = torch.zeros(direct.HBLOCK_SCHED_INTS, dtype=torch.int32, device=gpu_device)
+    sched[0], sched[1] = 1 << K, n
+    rows = [direct.alloc_rows_f64(n, gpu_device).fill_(sentinel) for _ in range(order // 2)]
+    size, step = ((_lib.lib().nbd_hblock_f64_workspace_bytes, direct.hblock_step_f64) if order == 4 else
+                  (_lib.lib().nbd_hblock6_f64_workspace_bytes, direct.hblock6_step_f64))
+    ws = _nan_fill(torch.empty(size(n) - 32, dtype=torch.uint8, device=gpu_device))
+    assert ws.data_ptr() % 32 == 0
+    with pytest.raises(_lib.NbdError, match="code -2"):
+        step(*state, mass, ticks, levels, n, K, 1.0 / 32, 0.02, EPS * EPS, G, sched, *rows, ws)
+    torch.cuda.synchronize()
+    want = torch.full_like(rows[0], sentinel).view(torch.int64)
+    for r in rows:
+        assert torch.equal(r.view(torch.int64), want)
+
+
 def test_unsupported_dtype_raises(gpu_device):
     from galaxify import simulation
     z = np.zeros((4, 3))

@@ -21,10 +21,13 @@ ENTRIES = ("nbd_hblock_f64_workspace_bytes", "nbd_hblock_init_levels_f64", "nbd_
            "nbd_hblock_force_f64", "nbd_hblock_correct_f64", "nbd_hblock_step_f64", "nbd_accel_jerk_active_f64")
 SRC = os.path.join(ROOT, "nbody-deep-sim_amd", "csrc", "direct_hermite_block_f64.hip")
 FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-ffp-contract=off", "--cuda-device-only", "-S"]
-# the force kernel, and the double instantiations of hermite_block_kernels.h's templates (the float ones:
-# test_block_hermite_host.py)
-KERNELS = ("accel_jerk_active_f64_kernel", "hblock_init_kernelId", "hblock_predict_kernelId", "hblock_correct_kernelId")
-LDS = {"hblock_init_kernelId": 84, "hblock_correct_kernelId": 0}      # int[21] of level counts; one thread per row: none
+# the two instantiations of the force kernel (the mangled name carries the order), the double instantiations of
+# hermite_block_kernels.h's templates (the float ones: test_block_hermite_host.py) and the 6th order's O(N) kernels
+FORCE4, FORCE6 = "active_force_f64_kernelINS_6Order4E", "active_force_f64_kernelINS_6Order6E"
+KERNELS = (FORCE4, FORCE6, "hblock_init_kernelId", "hblock_predict_kernelId", "hblock_correct_kernelId",
+           "hblock6_predict_kernel", "hblock6_correct_kernel")
+# int[21] of level counts; one thread per row: none; [wave][buffer][array][128] quads of two resp. three source arrays
+LDS = {"hblock_init_kernelId": 84, "hblock_correct_kernelId": 0, FORCE4: 32768, FORCE6: 49152}
 
 
 @pytest.mark.parametrize("eps", [0.0, 0.01])
@@ -153,7 +156,9 @@ def test_new_kernels_have_no_scratch_and_no_spills(asm, kernel):
     if kernel in LDS:
         desc = asm[asm.index(".amdhsa_kernel " + name):]
         assert int(re.search(r"\.amdhsa_group_segment_fixed_size\s+(\d+)", desc).group(1)) == LDS[kernel]
-    if kernel == "accel_jerk_active_f64_kernel":
+    if kernel == FORCE6:
+        assert num(r"\.vgpr_count") <= 168              # 3 workgroups per CU (48 KiB of LDS each), as accel_jerk_snap_f64_kernel
+    if kernel == FORCE4:
         assert num(r"\.vgpr_count") <= 96               # 5 workgroups per CU (32 KiB of LDS each), as accel_jerk_f64_kernel
         body = asm[asm.index(name + ":"):]
         body = body[:body.index(".Lfunc_end")]
@@ -177,6 +182,13 @@ def test_no_float_atomics_and_one_copy_of_the_wave_body(asm):
         assert [f for f, text in units.items() if what in text] == ["hermite_kernels.h"], what
     for f in ("direct_hermite_f64.hip", "direct_hermite_block_f64.hip"):      # no slab loop written out in an fp64 unit
         assert "+= slabs[" not in units[f], f
+    # one float64 block unit for both orders, and one copy of its workspace arithmetic and of the force launch: each is
+    # defined once, under no other spelling (the fp32 unit, direct_hermite_block.hip, has a step_bytes and a launch_active
+    # of its own, over its own plan and wave body, and no slab_rows)
+    for what in ("slab_rows", "step_bytes", "launch_active"):
+        defs = {f: re.findall(r"^(?:inline )?(?:size_t|int) (%s\w*)\(" % what, text, flags=re.M)
+                for f, text in units.items() if f != "direct_hermite_block.hip"}
+        assert {f: d for f, d in defs.items() if d} == {"direct_hermite_block_f64.hip": [what]}, (what, defs)
 
 
 def test_dtype_errors_come_before_any_device_work():

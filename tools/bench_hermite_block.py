@@ -20,7 +20,7 @@ With --dtype float64 (BlockHermiteSimulator(dtype=torch.float64), csrc/direct_he
    float32; error, pair interactions, clamped levels and wall time per eta.
 The default output is profiles/r13_hermite_block_f64.json.
 
-With --order 6 (BlockHermite6Simulator, csrc/direct_hermite6_block_f64.hip; float64), all in one process:
+With --order 6 (BlockHermite6Simulator, the 6th order of csrc/direct_hermite_block_f64.hip; float64), all in one process:
 1. nbd_accel_jerk_snap_active_f64 with every body listed against nbd_accel_jerk_snap_f64 (the same wave body and plan),
    and shorter lists, interleaved as above.
 2. The block-step cost fit of the 6th order (T_full the Hermite6Simulator step) beside the float64 4th order's.
@@ -170,7 +170,7 @@ def block_step_cost(n=65536, K=10, reps=15, dtype=torch.float32, order=4):
             t0 = time.perf_counter()
             direct.hblock_schedule(sim.levels, K, sim._sched, sim._bws, host_sched=host)
             got = int(host[1])
-            sim._block_step(got)
+            sim._fmt.block_step(sim, got)
             torch.cuda.synchronize()
             if r >= 2:
                 wall.append((time.perf_counter() - t0) * 1e3)
