@@ -751,6 +751,92 @@ int nbd_accel_jerk_snap_active_f64(const double* posd, const double* veld, const
                                    double* snap_out, void* workspace, size_t workspace_bytes, int slabs,
                                    nbd_stream_t stream);
 
+/* ---- block-timestep Hermite per scene, 4th and 6th order (csrc/direct_batch_hermite_block_f64.hip): the two block
+ * schemes above applied to every scene of an ensemble (offsets, n_scenes as in "batched direct integrator") by ONE
+ * schedule and one set of launches per block step, float64 only. All scenes share one tick grid of 2^K ticks per output
+ * interval (K = max_level, one value for the batch); scene s's tick is dt_s / 2^K long. The scheduler runs over the bodies
+ * of all scenes as one pool; under the block condition a scene gets exactly the active set, at exactly the ticks, it would
+ * have alone, so each scene's state, levels and counters are bit-identical to the nbd_hblock_*_f64 / nbd_hblock6_*_f64
+ * entries on that scene alone, whatever its companions.
+ *   plan    : its own work list in the layout of the float64 batch plan (nbd_batch_hblock_f64_plan for the sizes;
+ *             nbd_batch_hblock_f64_plan_fill / nbd_batch_hblock6_f64_plan_fill into a host buffer the caller copies to the
+ *             device). The list is STATIC: scene s has max over g in [1, ceil(n_s / 64)] of g * slabs(g) items, slabs(g)
+ *             the one-system plan's slab count for g groups of 64 targets under the scene's sources; a block step uses
+ *             the first groups * slabs of them for the scene's active count and the rest leave at once.
+ *   params  : DEVICE double[NBD_BATCH_HBLOCK_PARAM_ROWS][S], 8-byte aligned, row r of scene s at params[r * S + s]; rows:
+ *             G, softening^2, softening, dt, eta.
+ *   bsched  : DEVICE int[(S + 1) * NBD_HBLOCK_SCHED_INTS], zero before the first nbd_batch_hblock_init_levels_f64. Record
+ *             0 is the ensemble's: [0] t_next, [1] n_act_total, [3] the tick every body has reached, [5] and [8..] the
+ *             scheduler's own (finished workgroups, histogram of all levels). Record 1 + s is scene s's: [0] t_next,
+ *             [1] the scene's active count of this block step, [2] its cumulative clamp count, [4] and [8..] its list cursor
+ *             and level histogram.
+ *   counters: DEVICE int64[S][2], zero at the start: the scene's cumulative block steps (those with an active body of
+ *             the scene) and pair interactions (sum of n_act_s * n_s). The scheduler adds to them; nothing per scene is
+ *             read by the host in a block step.
+ *   workspace: nbd_batch_hblock_f64_workspace_bytes / nbd_batch_hblock6_f64_workspace_bytes, 32-byte aligned: the active
+ *             lists (int32, n_total rounded up to a multiple of 8; scene s's segment starts at its body offset and holds
+ *             scene-local indices) and behind them each scene's partial sums, sized for the largest slabs * n_act any of
+ *             its active sets can need (6 resp. 9 doubles per listed body and slab).
+ *   posd / veld / accd: the packed rows of the float64 batch entries (nbd_batch_pack_f64, nbd_batch_hermite6_pack_f64).
+ * A block step is nbd_batch_hblock_schedule, then predict, force and correct (or nbd_batch_hblock_step_f64 /
+ * nbd_batch_hblock6_step_f64, all three). Deterministic: no float atomics, no memsets in a step, the workspace may hold
+ * anything on entry. Eager-only: the host reads {t_next, n_act_total} once per block step. The plan and workspace-size
+ * entries are host-only. Bad arguments are refused before any launch. */
+#define NBD_BATCH_HBLOCK_PARAM_ROWS 5
+int nbd_batch_hblock_f64_plan(const int* offsets, int n_scenes, int* n_items, int* rows, size_t* plan_bytes);
+int nbd_batch_hblock_f64_plan_fill(const int* offsets, int n_scenes, void* plan, size_t plan_bytes);
+int nbd_batch_hblock6_f64_plan_fill(const int* offsets, int n_scenes, void* plan, size_t plan_bytes);
+int nbd_batch_hblock_f64_workspace_bytes(const int* offsets, int n_scenes, size_t* bytes);
+int nbd_batch_hblock6_f64_workspace_bytes(const int* offsets, int n_scenes, size_t* bytes);
+/* ticks = 0 and levels from dt_i = (eta_s / 2) |a| / |j| of the scenes with mask[s] != 0 (mask: DEVICE int[S], or NULL for
+ * all), their clamp counts and histograms; then the ensemble's histogram and tick 0. Either order (plan of either). */
+int nbd_batch_hblock_init_levels_f64(const int* offsets, int n_scenes, const void* plan, size_t plan_bytes,
+                                     const double* acc, const double* jerk, const double* params, int max_level,
+                                     const int* mask, int* ticks, int* levels, int* bsched, nbd_stream_t stream);
+/* t_next and every scene's active list of the next block step, the scenes' counts and counters. host_sched: NULL, or 4
+ * ints of HOST memory that receive record 0's first four after a stream sync. Either order. */
+int nbd_batch_hblock_schedule(const int* offsets, int n_scenes, const void* plan, size_t plan_bytes, const int* levels,
+                              int max_level, int* bsched, long long* counters, void* workspace, size_t workspace_bytes,
+                              int* host_sched, nbd_stream_t stream);
+/* Every body predicted to t_next over (t_next - ticks[i]) dt_s / 2^K into the packed rows; zero rows behind each scene. */
+int nbd_batch_hblock_predict_f64(const int* offsets, int n_scenes, const void* plan, size_t plan_bytes,
+                                 const double* pos, const double* vel, const double* acc, const double* jerk,
+                                 const double* mass, const int* ticks, const double* params, int max_level,
+                                 const int* bsched, double* posd, double* veld, nbd_stream_t stream);
+int nbd_batch_hblock6_predict_f64(const int* offsets, int n_scenes, const void* plan, size_t plan_bytes,
+                                  const double* pos, const double* vel, const double* acc, const double* jerk,
+                                  const double* snap, const double* crackle, const double* mass, const int* ticks,
+                                  const double* params, int max_level, const int* bsched, double* posd, double* veld,
+                                  double* accd, nbd_stream_t stream);
+/* The partial sums of every scene's listed bodies under the scene's sources, at the one-system plan of its active count. */
+int nbd_batch_hblock_force_f64(const int* offsets, int n_scenes, const void* plan, size_t plan_bytes,
+                               const double* posd, const double* veld, const double* params, const int* bsched,
+                               void* workspace, size_t workspace_bytes, nbd_stream_t stream);
+int nbd_batch_hblock6_force_f64(const int* offsets, int n_scenes, const void* plan, size_t plan_bytes,
+                                const double* posd, const double* veld, const double* accd, const double* params,
+                                const int* bsched, void* workspace, size_t workspace_bytes, nbd_stream_t stream);
+/* The slabs in slab order x G_s, the corrector with each listed body's own step, its new level with eta_s,
+ * ticks[i] = t_next (0 at 2^K), posd = {x1, m}; the histograms and the scene's clamp count. */
+int nbd_batch_hblock_correct_f64(const int* offsets, int n_scenes, const void* plan, size_t plan_bytes, double* pos,
+                                 double* vel, double* acc, double* jerk, const double* mass, int* ticks, int* levels,
+                                 const double* params, int max_level, int* bsched, double* posd, void* workspace,
+                                 size_t workspace_bytes, nbd_stream_t stream);
+int nbd_batch_hblock6_correct_f64(const int* offsets, int n_scenes, const void* plan, size_t plan_bytes, double* pos,
+                                  double* vel, double* acc, double* jerk, double* snap, double* crackle,
+                                  const double* mass, int* ticks, int* levels, const double* params, int max_level,
+                                  int* bsched, double* posd, void* workspace, size_t workspace_bytes,
+                                  nbd_stream_t stream);
+/* predict + force + correct of the block step the schedule has just listed. */
+int nbd_batch_hblock_step_f64(const int* offsets, int n_scenes, const void* plan, size_t plan_bytes, double* pos,
+                              double* vel, double* acc, double* jerk, const double* mass, int* ticks, int* levels,
+                              const double* params, int max_level, int* bsched, double* posd, double* veld,
+                              void* workspace, size_t workspace_bytes, nbd_stream_t stream);
+int nbd_batch_hblock6_step_f64(const int* offsets, int n_scenes, const void* plan, size_t plan_bytes, double* pos,
+                               double* vel, double* acc, double* jerk, double* snap, double* crackle,
+                               const double* mass, int* ticks, int* levels, const double* params, int max_level,
+                               int* bsched, double* posd, double* veld, double* accd, void* workspace,
+                               size_t workspace_bytes, nbd_stream_t stream);
+
 /* ---- backward of the all-pairs acceleration (csrc/direct_grad.hip): the vector-Jacobian product of
  *   a_i = G sum_{j != i} m_j d s^3,  d = x_j - x_i,  s = (|d|^2 + softening_sq)^(-1/2)
  * with a cotangent g = dL/da (n,3). With h_ij = m_i g_j - m_j g_i:

@@ -2,7 +2,8 @@
 // what a kernel reads from it (load_item: one workgroup per item; load_row: one thread per packed row) and the host
 // checks every batched entry point makes before it launches. Shared by direct_batch.hip (leapfrog, Euler, energies),
 // direct_diag.hip (the batched diagnostics), direct_batch_hermite.hip (Hermite), direct_batch_hermite_f64.hip (Hermite in
-// double precision) and direct_batch_hermite6_f64.hip (6th-order Hermite). The two float64 units fill the same layout
+// double precision), direct_batch_hermite6_f64.hip (6th-order Hermite) and direct_batch_hermite_block_f64.hip (block
+// timesteps per scene: the same layout with a static work list, a geometry of its own). The two shared-timestep float64 units fill the same layout
 // with another geometry per scene (SceneGeom below); the host shell of such a plan counted in doubles -- totals, plan
 // fill, workspace size and checks, for kOut doubles per body and slab -- is here once, at the end. The definitions sit in
 // an anonymous namespace: every translation unit that includes this file gets its own copies.

@@ -17,7 +17,7 @@
 //              gathered through the list, the same walk_f64 and pair functor
 //   correct  : the slabs in slab order, the corrector with the body's own h_i, the criterion for the new level,
 //              t_i = t_next (0 at the end of the interval), posd = {x1, m}
-// What the orders differ in (Order4, Order6 below; the O(N) kernels and the pointer lists of the entries):
+// What the orders differ in (Order4, Order6 of hermite_block_f64_kernels.h; the O(N) kernels and the pointer lists of the entries):
 //         state         packed rows (d4)        sums: kOut   predict, correct
 //   4th : x v a j       {x_p, m}, {v_p, 0}      a, j: 6      hblock_predict_kernel<double>, hblock_correct_kernel<double>:
 //                                                            hermite_block_kernels.h's templates, the fp32 unit's source
@@ -51,33 +51,12 @@
 #include "../../include/nbd.h"
 #include "direct_kernels.h"
 #include "hermite6_f64_kernels.h"
+#include "hermite_block_f64_kernels.h"
 #include "hermite_block_kernels.h"
 #include "hermite_f64_kernels.h"
 #include "hermite_kernels.h"
 
 namespace {
-
-// An order: its pair functor, the d4 arrays the functor streams, the workgroups per CU the force kernel is bound to, and
-// the functor of target i from those arrays (accd: the 6th order's third; the 4th is handed nullptr and never reads it).
-struct Order4 {
-  using Pair = AccelJerkPair;
-  static constexpr int kArr = 2;                   // {x_p, m}, {v_p, 0}
-  static constexpr int kMinWG = 5;
-  static __device__ __forceinline__ Pair make(const d4* __restrict__ posd, const d4* __restrict__ veld,
-                                              const d4* __restrict__, int i, double eps2, int n) {
-    return Pair(posd[i], veld[i], eps2, i, n);
-  }
-};
-
-struct Order6 {
-  using Pair = AccelJerkSnapPair;
-  static constexpr int kArr = 3;                   // {x_p, m}, {v_p, 0}, {a_p, 0}
-  static constexpr int kMinWG = 1;
-  static __device__ __forceinline__ Pair make(const d4* __restrict__ posd, const d4* __restrict__ veld,
-                                              const d4* __restrict__ accd, int i, double eps2, int n) {
-    return Pair(posd[i], veld[i], accd[i], eps2, i, n);
-  }
-};
 
 // The sums (Pair::kOut per target) of the n_act targets act[0..n_act) under all n sources. Grid = (ceil(n_act / 64),
 // slabs), block = 4 waves on the same 64 list entries, one per lane. The lanes behind n_act repeat the last target and
@@ -109,7 +88,7 @@ __global__ __launch_bounds__(256) void hblock6_predict_kernel(
   if (i >= (size_t)n_pad) return;
   d4 pm = {0.0, 0.0, 0.0, 0.0}, vp = pm, ap = pm;
   if (i < (size_t)n) {
-    const Hermite6Step h = hermite6_step_constants(dt * (double)(sched[kTNext] - ticks[i]) * tick);
+    const Hermite6Step h = hermite6_step_constants(hblock_ticks_len(dt, sched[kTNext] - ticks[i], tick));
     hermite6_predict_row(pos, vel, acc, jerk, snap, crackle, mass, i, h, pm, vp, ap);
   }
   posd[i] = pm;
@@ -138,7 +117,7 @@ __global__ __launch_bounds__(256) void hblock6_correct_kernel(const double* __re
   const int i = act[p];
   const int lev = levels[i];
   const int d = 1 << (K - lev);
-  const double h = dt * (double)d * tick;
+  const double h = hblock_ticks_len(dt, d, tick);
   const Hermite6Ends e = hermite6_finish_row(slabs, n_slabs, (size_t)n_act, p, (size_t)i, g, hermite6_step_constants(h),
                                              pos, vel, acc, jerk, snap, acc, jerk, snap, crackle, mass, posd, (size_t)i);
   hblock6_relevel(e.a0, e.j0, e.s0, e.a1, e.j1, e.s1, e.c1, h, dt, eta, K, lev, d, i, p == 0, ticks, levels, sched);

@@ -31,7 +31,7 @@ constexpr int kMaxSlabs = 64;
 // term), so the index-masked kernel is used (fill_diagonal_ semantics, simulation.py:85)
 constexpr float kEps2Masked = 1e-24f;
 
-inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
+__host__ __device__ inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 inline bool misaligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; }
 inline bool misaligned32(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 31) != 0; }
 inline bool misaligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7) != 0; }

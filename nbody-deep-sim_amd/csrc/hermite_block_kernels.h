@@ -8,6 +8,8 @@
 // arithmetic is hermite_kernels.h's (hermite_predict_row, hermite_slab_sum, hermite_correct_row), the step constants
 // hermite_step_constants<T> of the body's own fp64 step: a body whose step is the whole interval gets the shared step's
 // bits.
+// direct_batch_hermite_block_f64.hip (both orders for every scene of a batch) takes the record's layout, the level
+// arithmetic, hblock_ticks_len, hblock_initial_level and the two re-levelling functions from here and has kernels of its own.
 // The 6th order of the fp64 unit takes the record, the level arithmetic, the initial levels, hblock_move_level and
 // hblock6_relevel from here and has O(N) kernels of its own, in that unit, over hermite6_f64_kernels.h's rows.
 // The definitions sit in an anonymous namespace: every translation unit that includes this file gets its own inlined copies.
@@ -49,6 +51,20 @@ __device__ __forceinline__ int wanted_level(double crit, double dt, int K) {
 
 __device__ __forceinline__ double norm3(double x, double y, double z) { return sqrt(x * x + y * y + z * z); }
 
+// The length of `ticks` ticks of an interval dt of 2^K ticks (tick = 2^-K): a body's elapsed time since its last
+// correction (the predictors) and its own step (the correctors), in the one-system units and in the batched one
+// (direct_batch_hermite_block_f64.hip, where dt is the scene's).
+__device__ __forceinline__ double hblock_ticks_len(double dt, int ticks, double tick) { return dt * (double)ticks * tick; }
+
+// The initial level of body i from dt_i = (eta / 2) |a| / |j| in fp64 (+inf where j = 0): K + 1 where deeper than K.
+template <class T>
+__device__ __forceinline__ int hblock_initial_level(const T* __restrict__ acc, const T* __restrict__ jerk, size_t i,
+                                                    int K, double dt, double eta) {
+  const double a = norm3(acc[3 * i], acc[3 * i + 1], acc[3 * i + 2]);
+  const double j = norm3(jerk[3 * i], jerk[3 * i + 1], jerk[3 * i + 2]);
+  return wanted_level(j == 0.0 ? INFINITY : 0.5 * eta * a / j, dt, K);
+}
+
 // Initial levels from dt_i = (eta / 2) |a| / |j| in fp64 (+inf where j = 0); every tick to 0. Levels deeper than K are
 // clamped and counted.
 template <class T>
@@ -60,9 +76,7 @@ __global__ __launch_bounds__(256) void hblock_init_kernel(const T* __restrict__ 
   if (threadIdx.x <= K) hist[threadIdx.x] = 0;
   __syncthreads();
   if (i < (size_t)n) {
-    const double a = norm3(acc[3 * i], acc[3 * i + 1], acc[3 * i + 2]);
-    const double j = norm3(jerk[3 * i], jerk[3 * i + 1], jerk[3 * i + 2]);
-    int k = wanted_level(j == 0.0 ? INFINITY : 0.5 * eta * a / j, dt, K);
+    int k = hblock_initial_level(acc, jerk, i, K, dt, eta);
     if (k > K) {
       k = K;
       atomicAdd(&sched[kClamped], 1);
@@ -105,7 +119,7 @@ __global__ __launch_bounds__(256) void hblock_predict_kernel(const T* __restrict
   if (i >= (size_t)n_pad) return;
   typename HermiteFmt<T>::Row pm = HermiteFmt<T>::zero(), vp = HermiteFmt<T>::zero();
   if (i < (size_t)n) {
-    const HermiteStep<T> h = hermite_step_constants<T>(dt * (double)(sched[kTNext] - ticks[i]) * tick);
+    const HermiteStep<T> h = hermite_step_constants<T>(hblock_ticks_len(dt, sched[kTNext] - ticks[i], tick));
     const PosVel3<T> p = hermite_predict_row(pos, vel, acc, jerk, i, h.dt, h.dt2_half, h.dt3_sixth, true);
     pm = hermite_row(p.x, mass[i]);
     vp = hermite_row(p.v, (T)0);
@@ -211,7 +225,7 @@ __global__ __launch_bounds__(256) void hblock_correct_kernel(const T* __restrict
   const int i = act[p];
   const int lev = levels[i];
   const int d = 1 << (K - lev);
-  const double h = dt * (double)d * tick;
+  const double h = hblock_ticks_len(dt, d, tick);
   const HermiteStep<T> hc = hermite_step_constants<T>(h);
   const Corrected<T> c = hermite_correct_row(pos, vel, acc, jerk, (size_t)i, a1, j1, hc.dt_half, hc.dt2_twelfth);
   hermite_store_force(acc, jerk, (size_t)i, a1, j1);

@@ -1,5 +1,6 @@
 // hermite_f64_kernels.h -- what the double-precision translation units share (direct_hermite_f64.hip: all targets,
 // shared timestep, and the diagnostics; direct_hermite_block_f64.hip: an active list of targets, block timesteps;
+// direct_batch_hermite_block_f64.hip: the active lists of every scene of a batch;
 // direct_hermite_shard_f64.hip: one rank's bodies of a range partition, 4th and 6th order;
 // direct_batch_hermite_f64.hip: many independent systems, shared timestep per system, and their diagnostics;
 // direct_leapfrog_f64.hip: the acceleration alone, for the leapfrog and Euler steps; direct_hermite6_f64.hip and
@@ -402,8 +403,9 @@ __device__ __forceinline__ ChunkRange wave_chunks_upper(int jw, int n_chunks, I 
 // of a slab still has a chunk to walk. n_tgt targets under n sources; n_tgt = n is the shared step's plan.
 struct F64Plan { int groups, slabs, n_chunks; };
 
-// the slab count of `groups` target groups under n_chunks source chunks (at least 1: a wave may then be left without one)
-inline int slabs_f64(int groups, int n_chunks) {
+// the slab count of `groups` target groups under n_chunks source chunks (at least 1: a wave may then be left without one).
+// On the device too: a scene of a batched block step (direct_batch_hermite_block_f64.hip) forms it from its own active count.
+__host__ __device__ inline int slabs_f64(int groups, int n_chunks) {
   int slabs = ceil_div(kTargetWGs, groups);
   const int cap = n_chunks / kWaves;
   slabs = slabs > cap ? cap : slabs;

@@ -1254,7 +1254,8 @@ class BlockHermite6Simulator(_BlockSteps, Hermite6Simulator):
     The public surface is BlockHermiteSimulator's: `eta`, `max_level`, `levels`, the cumulative counters `block_steps`,
     `pair_interactions` and `clamped`, `level_history`, MAX_LEVEL_LIMIT. `accelerations`, `jerks`, `snaps` and `crackles`
     are updated in place. Float64 only and eager-only (every block step reads {t_next, n_act} back to the host); there is
-    no range-sharded, batched, captured or differentiable form. With max_level=0 it is Hermite6Simulator bit for bit.
+    no range-sharded, captured or differentiable form; BatchedSimulator(integrator="block_hermite6") is the batched one.
+    With max_level=0 it is Hermite6Simulator bit for bit.
     compute_*() and run() are that class's."""
 
     def __init__(self, *, positions, velocities, masses, g_const: float = 1.0, softening: float = 0.1,
@@ -1320,7 +1321,33 @@ def _batch_states(host, m: int, offsets: list, calc_energy: bool, first: int, t_
                                           invariants=Invariants.from_row(inv[s_][i]) if inv is not None else None))
 
 
-class _BatchFloat32:
+class _BatchFormat:
+    """What every format object of BatchedSimulator shares: the parameter table's upkeep (`extra_params`, `write_params`),
+    one step() of the shared-timestep integrators (`advance`: new carried arrays, rebound) and the flags `capturable`
+    (run() may capture its chunks) and `block` (a block-timestep format, `_BatchBlock`)."""
+
+    capturable = True
+    block = False
+
+    def extra_params(self, s) -> tuple:
+        """Per-scene parameter lists beyond (g_const, softening, dt); they join the key of the table."""
+        return ()
+
+    def write_params(self, s, g, eps, dt):
+        s._params.copy_(torch.tensor(self.param_rows(g, eps, dt), dtype=self.dtype))
+
+    def start(self, s):
+        """What the format sets up once the first forces are known (nothing for a shared timestep)."""
+
+    def advance(self, s):
+        cur = [getattr(s, public) for public, _ in s._carried]
+        new = [torch.empty_like(t) for t in cur]
+        s._step_into(cur, new)
+        for (public, _), t in zip(s._carried, new):
+            setattr(s, public, t)
+
+
+class _BatchFloat32(_BatchFormat):
     """The float32 number format of BatchedSimulator: every allocation and nbd.direct call of a batch `s` that depends on
     the format (the object keeps no state of its own); `_BatchFloat64` has the same methods. Packed sources: `s._posm` =
     {x, y, z, m}; the Hermite calls keep their packed velocities inside `s._hws`, allocated on first use. Parameter table
@@ -1383,7 +1410,7 @@ class _BatchFloat32:
     snapshot = staticmethod(direct.snapshot)
 
 
-class _BatchFloat64:
+class _BatchFloat64(_BatchFormat):
     """The float64 number format of BatchedSimulator (csrc/direct_batch_hermite_f64.hip): `_BatchFloat32`'s methods over the
     float64 entries, Hermite only; nothing of the fp32 paths is allocated or launched. Packed sources: `s._posd` =
     {x, y, z, m}, `s._veld` = {vx, vy, vz, 0}; ONE workspace `s._ws` for the step and the diagnostics. Parameter table
@@ -1461,14 +1488,129 @@ class _BatchHermite6(_BatchFloat64):
                                        s._veld, s._accd, s._ws)
 
 
+class _BatchBlock:
+    """The block-timestep part of a batch format (csrc/direct_batch_hermite_block_f64.hip; DESIGN.md K-BHB), mixed in in
+    front of the shared-timestep float64 format whose scheme it runs (`_BatchFloat64`: "block_hermite"; `_BatchHermite6`:
+    "block_hermite6"). That format keeps the plan, the packed rows, the first forces and the diagnostics. Added here: the
+    static work list and workspace of the block step (`s._bplan`, `s._bws`), the int32 schedule state (`s.levels`,
+    `s._ticks`, the device records `s._bsched`), the per-scene counters `s._counters`, a second parameter table
+    `s._bparams` (G, eps^2, eps, dt, eta), the initial levels and the loop of ensemble block steps that makes one
+    step() -- `_BlockSteps.step` with ONE schedule and one host read for all scenes."""
+
+    capturable = False
+    block = True
+    order = 4
+    integrators = ("block_hermite",)
+    state_names = ("positions", "velocities", "accelerations", "jerks")
+    row_names = ("_posd", "_veld")
+
+    def scratch(self, s):
+        super().scratch(s)
+        s._bplan = direct.BatchBlockPlan(s.sizes, s.device, order=self.order)
+        s._bws = s._bplan.workspace()
+        s._bsched = s._bplan.sched()
+        s._counters = s._bplan.counters()
+        s._bparams = torch.zeros((direct.BATCH_HBLOCK_PARAM_ROWS, s.n_scenes), dtype=torch.float64, device=s.device)
+        s.levels = torch.zeros(s.n, dtype=torch.int32, device=s.device)
+        s._ticks = torch.zeros(s.n, dtype=torch.int32, device=s.device)
+        s._sched_host = torch.zeros(4, dtype=torch.int32).pin_memory()
+        s._leveled_for = None
+
+    def extra_params(self, s) -> tuple:
+        return (_per_scene(s.eta, s.n_scenes, "eta"),)
+
+    def write_params(self, s, g, eps, dt, eta):
+        super().write_params(s, g, eps, dt)
+        s._bparams.copy_(torch.tensor(direct.batch_hblock_params(g, eps, dt, eta), dtype=torch.float64))
+
+    @staticmethod
+    def check_level(max_level):
+        limit = _BlockSteps.MAX_LEVEL_LIMIT
+        if not (isinstance(max_level, int) and 0 <= max_level <= limit):
+            raise ValueError(f"BatchedSimulator: max_level must be an int in [0, {limit}]")
+
+    @classmethod
+    def check_params(cls, s, dt, eta):
+        cls.check_level(s.max_level)
+        if not (all(d > 0 for d in dt) and all(e > 0 for e in eta)):
+            raise ValueError("BatchedSimulator: dt and eta must be positive")
+
+    def start(self, s):
+        s._sync_params()
+        self.set_levels(s)
+
+    def set_levels(self, s):
+        """`_BlockSteps._set_levels` per scene: the initial levels of the scenes whose dt or eta changed (all of them the
+        first time and after max_level changed), from the batch's accelerations and jerks. Parameters in sync."""
+        dt, eta = s._params_key[2], s._params_key[3]
+        new = (dt, eta, s.max_level)
+        old = s._leveled_for
+        if new == old:
+            return
+        self.check_params(s, dt, eta)
+        s._leveled_for = new
+        if s.n == 0:
+            return
+        mask = None
+        if old is not None and old[2] == s.max_level:
+            mask = torch.tensor([int(a != b or c != d) for a, b, c, d in zip(dt, old[0], eta, old[1])],
+                                dtype=torch.int32).to(s.device)
+        direct.batch_hblock_init_levels(s._bplan, s.accelerations, s.jerks, s._bparams, s.max_level, s._ticks, s.levels,
+                                        s._bsched, mask=mask)
+
+    def advance(self, s):
+        """One output interval of every scene: ensemble block steps until every body is back at tick 2^max_level."""
+        self.set_levels(s)
+        K = s.max_level
+        end = 1 << K
+        host = s._sched_host
+        state = tuple(getattr(s, name) for name in self.state_names)
+        rows = tuple(getattr(s, name) for name in self.row_names)
+        t_prev = 0
+        for _ in range(end):
+            direct.batch_hblock_schedule(s._bplan, s.levels, K, s._bsched, s._counters, s._bws, host_sched=host)
+            t_next, n_act = int(host[0]), int(host[1])
+            if not (t_prev < t_next <= end and 1 <= n_act <= s.n):
+                raise RuntimeError(f"BatchedSimulator: corrupt schedule (t_next={t_next}, n_act={n_act}, previous tick "
+                                   f"{t_prev})")
+            direct.batch_hblock_step(s._bplan, state, s.masses, s._ticks, s.levels, s._bparams, K, s._bsched, rows,
+                                     s._bws)
+            s.block_steps += 1
+            if s.tick_history is not None:
+                s.tick_history.append((t_next, n_act))
+            if s.level_history is not None:
+                s.level_history.append(s.levels.cpu())
+            if t_next == end:
+                break
+            t_prev = t_next
+        else:
+            raise RuntimeError(f"BatchedSimulator: interval not finished within {end} block steps")
+
+
+class _BatchBlockHermite(_BatchBlock, _BatchFloat64):
+    """BatchedSimulator(integrator="block_hermite"): BlockHermiteSimulator(dtype=torch.float64)'s scheme per scene."""
+
+
+class _BatchBlockHermite6(_BatchBlock, _BatchHermite6):
+    """BatchedSimulator(integrator="block_hermite6"): BlockHermite6Simulator's scheme per scene."""
+
+    order = 6
+    integrators = ("block_hermite6",)
+    state_names = _BatchBlock.state_names + ("snaps", "crackles")
+    row_names = _BatchBlock.row_names + ("_accd",)
+
+
 _BATCH_FORMATS = {fmt.dtype: fmt for fmt in (_BatchFloat32(), _BatchFloat64())}
-_BATCH_HERMITE6 = _BatchHermite6()
-_BATCH_INTEGRATORS = ("leapfrog", "euler", "hermite", "hermite6")
+# the integrators with a float64-only format of their own
+_BATCH_OWN_FORMATS = {"hermite6": _BatchHermite6(), "block_hermite": _BatchBlockHermite(),
+                      "block_hermite6": _BatchBlockHermite6()}
+_BATCH_INTEGRATORS = ("leapfrog", "euler", "hermite", "hermite6", "block_hermite", "block_hermite6")
+_BATCH_BLOCK_INTEGRATORS = ("block_hermite", "block_hermite6")
 
 
 def _batch_format(dtype, integrator):
-    """The format object of a batch: by dtype, and the 6th-order scheme has one of its own."""
-    return _BATCH_HERMITE6 if integrator == "hermite6" else _BATCH_FORMATS[dtype]
+    """The format object of a batch: by dtype, and the 6th-order and the block schemes have one of their own."""
+    return _BATCH_OWN_FORMATS.get(integrator) or _BATCH_FORMATS[dtype]
 
 
 class BatchedSimulator(_ChunkedRun):
@@ -1499,7 +1641,22 @@ class BatchedSimulator(_ChunkedRun):
     them (the acceleration first, then the evaluation with it as the third source array, crackle 0), and each scene's
     state is bit-identical to a Hermite6Simulator of that scene alone. run() captures its chunks as for the float64
     4th-order mode, the four arrays stepped in place; energies, potentials and invariants are that mode's. The
-    integrator cannot switch into or out of "hermite6", nor between "hermite" and "hermite6"."""
+    integrator cannot switch into or out of "hermite6", nor between "hermite" and "hermite6".
+
+    integrator="block_hermite" and "block_hermite6" (csrc/direct_batch_hermite_block_f64.hip; DESIGN.md K-BHB) run
+    BlockHermiteSimulator(dtype=torch.float64)'s resp. BlockHermite6Simulator's individual block timesteps on every scene,
+    float64 only. All scenes share one grid of 2^max_level ticks per output interval (`max_level`: one int for the batch, in
+    [0, MAX_LEVEL_LIMIT]); `eta` is a float or one value per scene. Under the block condition the union of the scenes'
+    schedules is itself a block schedule, so ONE scheduler launch, one host read of {t_next, n_act_total} and one predict /
+    force / correct launch set serve all scenes per ensemble block step, and every scene still takes exactly the block
+    steps it would take alone: its positions, velocities, accelerations, jerks (snaps, crackles), `levels` and counters
+    are bit-identical to the one-system block simulator of that scene, whatever its companions. `levels` is an
+    (N_total,) int32 device tensor; `block_steps` counts the ensemble's block steps; `scene_counters()` reads the per-scene
+    counters the kernels keep on the device; `tick_history` (set to a list) receives (t_next, n_act_total) per ensemble
+    block step and `level_history` a CPU copy of `levels`. The carried arrays are updated in place. Changing dt, eta or
+    max_level re-derives the initial levels of the scenes concerned before the next step(). Eager-only; with max_level=0
+    the modes are "hermite" (float64) and "hermite6" bit for bit. The integrator cannot change into, out of or between
+    the block modes; `eta` and `max_level` are refused with any other integrator."""
 
     RING_BYTES = 64 << 20                                # the eager run()'s staging cap, per chunk of states
 
@@ -1507,35 +1664,47 @@ class BatchedSimulator(_ChunkedRun):
     def _check_dtype(dtype, integrator):
         if dtype not in _BATCH_FORMATS:
             raise ValueError(f"BatchedSimulator: dtype must be torch.float32 or torch.float64, got {dtype!r}")
-        if integrator == "hermite6":
+        if integrator in _BATCH_OWN_FORMATS:
             if dtype is not torch.float64:
-                raise ValueError(f"BatchedSimulator: integrator='hermite6' is float64 only (dtype must be "
-                                 f"torch.float64, got {dtype!r}): there is no fp32 form of the 6th-order scheme")
+                raise ValueError(f"BatchedSimulator: integrator={integrator!r} is float64 only (dtype must be "
+                                 f"torch.float64, got {dtype!r}): there is no fp32 form of "
+                                 + ("the 6th-order scheme" if integrator == "hermite6" else "the batched block schemes"))
         elif integrator not in _BATCH_FORMATS[dtype].integrators:
             raise ValueError(f"BatchedSimulator: dtype={dtype} has integrator='hermite' only (there is no float64 "
                              f"leapfrog or Euler), got {integrator!r}")
 
     def __init__(self, *, systems, integrator: str = "leapfrog", g_const=1.0, softening=0.1, dt=0.01,
-                 calc_energy: bool = True, device: str = None, calc_invariants: bool = False, **format_kw):
-        # format_kw: `dtype` (default torch.float32; torch.float64 for "hermite6"), the one keyword of the number format. As in BlockHermiteSimulator it
-        # is not a named parameter: HermiteSimulator's signature stays the only one that spells it (tested); any other
+                 calc_energy: bool = True, device: str = None, calc_invariants: bool = False, eta=None,
+                 max_level: int = None, **format_kw):
+        # format_kw: `dtype` (default torch.float32; torch.float64 for "hermite6" and the block modes), the one keyword of
+        # the number format. As in BlockHermiteSimulator it is not a named parameter: HermiteSimulator's signature stays the only one that spells it (tested); any other
         # name is refused as an unknown keyword is.
-        dtype = format_kw.pop("dtype", torch.float64 if integrator == "hermite6" else torch.float32)
+        dtype = format_kw.pop("dtype", torch.float64 if integrator in _BATCH_OWN_FORMATS else torch.float32)
         if format_kw:
             raise TypeError(f"BatchedSimulator.__init__() got an unexpected keyword argument {next(iter(format_kw))!r}")
         if integrator not in _BATCH_INTEGRATORS:
-            raise ValueError("integrator must be 'leapfrog', 'euler', 'hermite' or 'hermite6'")
+            raise ValueError("integrator must be 'leapfrog', 'euler', 'hermite', 'hermite6', 'block_hermite' or "
+                             "'block_hermite6'")
         self._check_dtype(dtype, integrator)             # before anything is resolved, allocated or launched
+        if integrator in _BATCH_BLOCK_INTEGRATORS:
+            self.eta = 0.02 if eta is None else eta      # the defaults of the one-system block simulators
+            self.max_level = 10 if max_level is None else max_level
+            _BatchBlock.check_level(self.max_level)
+        elif eta is not None or max_level is not None:
+            raise ValueError(f"BatchedSimulator: eta and max_level belong to the block integrators "
+                             f"{_BATCH_BLOCK_INTEGRATORS}, not to integrator={integrator!r}")
         self._fmt = _batch_format(dtype, integrator)     # the only place the format is chosen
         self.device = _resolve_device(device)
         _lib.lib()
         systems = list(systems)
         if not systems:
             raise ValueError("systems: need at least one (positions, velocities, masses) scene")
-        self.integrator = integrator
+        self.integrator = self._built_as = integrator
         self.calc_energy = calc_energy
         self.calc_invariants = calc_invariants
         self.n_scenes = len(systems)
+        self.block_steps = 0                             # the block modes' public state; `levels` is theirs alone
+        self.levels = self.tick_history = self.level_history = None
         pos, vel, mass = [], [], []
         for i, sysm in enumerate(systems):
             p, v, m = (_to_device(x, self.device, dtype) for x in sysm)
@@ -1552,8 +1721,8 @@ class BatchedSimulator(_ChunkedRun):
         self.offsets = torch.tensor(self._plan.offsets, dtype=torch.int64)
         self.g_const, self.softening, self.dt = g_const, softening, dt
         self._params_key = None
-        self._hermite = integrator in ("hermite", "hermite6")   # fixed at construction: the state carries jerks or not
-        self._order6 = integrator == "hermite6"          # ... and snaps and crackles
+        self._hermite = integrator not in ("leapfrog", "euler")   # fixed at construction: the state carries jerks or not
+        self._order6 = integrator in ("hermite6", "block_hermite6")         # ... and snaps and crackles
         self._phi = None
         self.jerks = self.snaps = self.crackles = None
         if self._order6:
@@ -1565,6 +1734,19 @@ class BatchedSimulator(_ChunkedRun):
             self.accelerations, self.jerks = self.compute_accelerations_and_jerks()
         else:
             self.accelerations = self.compute_accelerations()
+        self._fmt.start(self)                            # a block format: the initial levels
+
+    MAX_LEVEL_LIMIT = _BlockSteps.MAX_LEVEL_LIMIT
+
+    def scene_counters(self) -> list:
+        """The block modes' counters per scene, cumulative, as the one-system block simulator of that scene reports them:
+        dicts of `block_steps` (the ensemble block steps in which the scene had an active body), `pair_interactions` (sum of
+        n_act_s * n_s) and `clamped`. Read from the device tables here, and only here."""
+        if not self._fmt.block:
+            raise ValueError("BatchedSimulator.scene_counters(): the block integrators only")
+        counts = self._counters.cpu().tolist()
+        clamped = self._bsched[1:, 2].cpu().tolist()
+        return [{"block_steps": c[0], "pair_interactions": c[1], "clamped": k} for c, k in zip(counts, clamped)]
 
     # ------------------------------------------------------------------ per-scene parameters
     def _sync_params(self):
@@ -1575,9 +1757,10 @@ class BatchedSimulator(_ChunkedRun):
         g = _per_scene(self.g_const, S, "g_const")
         eps = _per_scene(self.softening, S, "softening")
         dt = _per_scene(self.dt, S, "dt")
-        key = (tuple(g), tuple(eps), tuple(dt))
+        extra = self._fmt.extra_params(self)
+        key = (tuple(g), tuple(eps), tuple(dt)) + tuple(tuple(x) for x in extra)
         if key != self._params_key:
-            self._params.copy_(torch.tensor(self._fmt.param_rows(g, eps, dt), dtype=self._fmt.dtype))
+            self._fmt.write_params(self, g, eps, dt, *extra)
             self._params_key = key
         return key
 
@@ -1607,13 +1790,20 @@ class BatchedSimulator(_ChunkedRun):
         """(a, j, s) of every scene's current state as new (N_total, 3) float64 tensors, in Hermite6Simulator's two
         passes per scene (integrator="hermite6" only)."""
         if not self._order6:
-            raise ValueError("BatchedSimulator.compute_accelerations_jerks_and_snaps(): integrator='hermite6' only")
+            raise ValueError("BatchedSimulator.compute_accelerations_jerks_and_snaps(): integrator='hermite6' (or "
+                             "'block_hermite6') only")
         self._sync_params()
         acc, jerk, snap = (torch.zeros((self.n, 3), dtype=torch.float64, device=self.device) for _ in range(3))
         self._fmt.accel_jerk_snap(self, acc, jerk, snap)
         return acc, jerk, snap
 
     def _check_integrator(self):
+        if self._fmt.block or self.integrator in _BATCH_BLOCK_INTEGRATORS:
+            if self.integrator != self._built_as:
+                raise ValueError("BatchedSimulator: the integrator cannot change into, out of or between the block "
+                                 "modes after construction (their schedule state, plan and tables are their own); "
+                                 "build a new simulator")
+            return
         if (self.integrator == "hermite6") != self._order6:
             raise ValueError("BatchedSimulator: the integrator cannot change into or out of 'hermite6' after "
                              "construction (the state carries snaps and crackles only for the 6th-order scheme, and "
@@ -1674,16 +1864,13 @@ class BatchedSimulator(_ChunkedRun):
 
     def step(self):
         """One step of every scene; positions and velocities in place, `accelerations` (for Hermite `jerks`, for the
-        6th-order scheme `snaps` and `crackles` as well) rebound to new tensors."""
+        6th-order scheme `snaps` and `crackles` as well) rebound to new tensors. The block modes advance every scene by its
+        own dt in ensemble block steps and update the carried arrays in place."""
         self._check_integrator()
         if self.n == 0:
             return
         self._sync_params()
-        cur = [getattr(self, public) for public, _ in self._carried]
-        new = [torch.empty_like(t) for t in cur]
-        self._step_into(cur, new)
-        for (public, _), t in zip(self._carried, new):
-            setattr(self, public, t)
+        self._fmt.advance(self)
 
     # ------------------------------------------------------------------ run()
     def _chunk_len(self) -> int:
@@ -1709,7 +1896,7 @@ class BatchedSimulator(_ChunkedRun):
             return out
         self._sync_params()
         big = self._chunk_len()
-        if big >= 8 and os.environ.get("NBD_RUN_GRAPH", "1") != "0":
+        if big >= 8 and self._fmt.capturable and os.environ.get("NBD_RUN_GRAPH", "1") != "0":
             self._run_chunked(steps, big, out)
         else:
             self._run_eager(steps, 0, out)

@@ -337,6 +337,31 @@ SIGNATURES = {
                              [c_void_p] * 5 + [c_size_t, c_void_p]),
     "nbd_accel_jerk_snap_active_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_double, c_double,
                                                c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_void_p]),
+    # --- block-timestep Hermite per scene, 4th and 6th order (csrc/direct_batch_hermite_block_f64.hip)
+    "nbd_batch_hblock_f64_plan": (c_int, [c_void_p, c_int, POINTER(c_int), POINTER(c_int), POINTER(c_size_t)]),
+    "nbd_batch_hblock_f64_plan_fill": (c_int, [c_void_p, c_int, c_void_p, c_size_t]),
+    "nbd_batch_hblock6_f64_plan_fill": (c_int, [c_void_p, c_int, c_void_p, c_size_t]),
+    "nbd_batch_hblock_f64_workspace_bytes": (c_int, [c_void_p, c_int, POINTER(c_size_t)]),
+    "nbd_batch_hblock6_f64_workspace_bytes": (c_int, [c_void_p, c_int, POINTER(c_size_t)]),
+    "nbd_batch_hblock_init_levels_f64": (c_int, [c_void_p, c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p,
+                                                 c_int] + [c_void_p] * 5),
+    "nbd_batch_hblock_schedule": (c_int, [c_void_p, c_int, c_void_p, c_size_t, c_void_p, c_int, c_void_p, c_void_p,
+                                          c_void_p, c_size_t, c_void_p, c_void_p]),
+    "nbd_batch_hblock_predict_f64": (c_int, [c_void_p, c_int, c_void_p, c_size_t] + [c_void_p] * 7 + [c_int] +
+                                     [c_void_p] * 4),
+    "nbd_batch_hblock6_predict_f64": (c_int, [c_void_p, c_int, c_void_p, c_size_t] + [c_void_p] * 9 + [c_int] +
+                                      [c_void_p] * 5),
+    "nbd_batch_hblock_force_f64": (c_int, [c_void_p, c_int, c_void_p, c_size_t] + [c_void_p] * 5 + [c_size_t, c_void_p]),
+    "nbd_batch_hblock6_force_f64": (c_int, [c_void_p, c_int, c_void_p, c_size_t] + [c_void_p] * 6 +
+                                    [c_size_t, c_void_p]),
+    "nbd_batch_hblock_correct_f64": (c_int, [c_void_p, c_int, c_void_p, c_size_t] + [c_void_p] * 8 + [c_int] +
+                                     [c_void_p] * 3 + [c_size_t, c_void_p]),
+    "nbd_batch_hblock6_correct_f64": (c_int, [c_void_p, c_int, c_void_p, c_size_t] + [c_void_p] * 10 + [c_int] +
+                                      [c_void_p] * 3 + [c_size_t, c_void_p]),
+    "nbd_batch_hblock_step_f64": (c_int, [c_void_p, c_int, c_void_p, c_size_t] + [c_void_p] * 8 + [c_int] +
+                                  [c_void_p] * 4 + [c_size_t, c_void_p]),
+    "nbd_batch_hblock6_step_f64": (c_int, [c_void_p, c_int, c_void_p, c_size_t] + [c_void_p] * 10 + [c_int] +
+                                   [c_void_p] * 5 + [c_size_t, c_void_p]),
     # --- backward of the all-pairs acceleration (csrc/direct_grad.hip)
     "nbd_accel_vjp_workspace_bytes": (c_size_t, [c_int]),
     "nbd_accel_vjp_f32": (c_int, [c_void_p, c_void_p, c_int, c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p]),

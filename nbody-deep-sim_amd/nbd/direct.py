@@ -1430,3 +1430,136 @@ def batch_hermite6_step_f64(plan: BatchPlan, pos, vel, acc_in, jerk_in, snap_in,
                 acc_in.data_ptr(), jerk_in.data_ptr(), snap_in.data_ptr(), crackle_in.data_ptr(), acc_out.data_ptr(),
                 jerk_out.data_ptr(), snap_out.data_ptr(), crackle_out.data_ptr(), mass.data_ptr(), params.data_ptr(),
                 posd.data_ptr(), veld.data_ptr(), accd.data_ptr(), ws.data_ptr(), _nbytes(ws))
+
+
+# ------------------------- block-timestep Hermite per scene, 4th and 6th order (csrc/direct_batch_hermite_block_f64.hip)
+BATCH_HBLOCK_PARAM_ROWS = 5     # NBD_BATCH_HBLOCK_PARAM_ROWS: G, eps^2, eps, dt, eta
+
+
+def batch_hblock_params(g, eps, dt, eta) -> list:
+    """The rows of the batched block step's parameter table from each scene's Python doubles, formed as the one-system
+    block simulators hand them to their entries: float(g), float(eps) ** 2, float(dt), float(eta).
+    -> BATCH_HBLOCK_PARAM_ROWS lists of S floats."""
+    return [[float(x) for x in g], [float(e) ** 2 for e in eps], [float(e) for e in eps], [float(d) for d in dt],
+            [float(x) for x in eta]]
+
+
+class BatchBlockPlan:
+    """The static work list of the batched block-timestep step (nbd_batch_hblock_f64_plan and the order's plan_fill),
+    next to a float64 BatchPlan of the same scenes: `n_items` workgroups per force launch (every scene's worst case),
+    `workspace_bytes` for the active lists and the partial sums (order 4: 6 doubles per listed body and slab; 6: 9)."""
+
+    def __init__(self, sizes, device, order: int = 4):
+        sizes = [int(n) for n in sizes]
+        if not sizes or min(sizes) < 0:
+            raise _lib.NbdError("batch: need at least one scene and no negative size")
+        if order not in (4, 6):
+            raise _lib.NbdError(f"batch block plan: order must be 4 or 6, got {order!r}")
+        self.order = order
+        self.offsets = np.zeros(len(sizes) + 1, dtype=np.int32)
+        np.cumsum(sizes, out=self.offsets[1:])
+        self.n_scenes, self.n_total = len(sizes), int(self.offsets[-1])
+        items, rows = ctypes.c_int(), ctypes.c_int()
+        pb, wb = ctypes.c_size_t(), ctypes.c_size_t()
+        scenes = (self.offsets.ctypes.data, self.n_scenes)
+        tag = "hblock" if order == 4 else "hblock6"
+        _lib.call("nbd_batch_hblock_f64_plan", *scenes, items, rows, pb)
+        _lib.call(f"nbd_batch_{tag}_f64_workspace_bytes", *scenes, wb)
+        self.n_items, self.posm_rows, self.plan_bytes, self.workspace_bytes = items.value, rows.value, pb.value, wb.value
+        self.host = np.zeros((self.plan_bytes + 15) // 16 * 4, dtype=np.int32)
+        _lib.call(f"nbd_batch_{tag}_f64_plan_fill", *scenes, self.host.ctypes.data, self.plan_bytes)
+        self.plan = torch.from_numpy(self.host).to(device) if device is not None else None
+        self.device = self.plan.device if self.plan is not None else None
+
+    def head(self):
+        return (self.offsets.ctypes.data, self.n_scenes, self.plan.data_ptr(), self.plan_bytes)
+
+    def workspace(self) -> torch.Tensor:
+        return alloc_bytes(self.workspace_bytes, self.device)
+
+    def sched(self) -> torch.Tensor:
+        """The zeroed device records: the ensemble's, then one per scene."""
+        return torch.zeros((self.n_scenes + 1, HBLOCK_SCHED_INTS), dtype=torch.int32, device=self.device)
+
+    def counters(self) -> torch.Tensor:
+        """The zeroed per-scene {block steps, pair interactions}."""
+        return torch.zeros((self.n_scenes, 2), dtype=torch.int64, device=self.device)
+
+
+def _chk_bblock(plan: BatchBlockPlan, state, mass, ticks, levels, params, bsched, rows, ws):
+    """The arguments of a batched block call, each None where the call takes none: the (N_total, 3) state arrays, the int32
+    schedule arrays, the parameter table, the records, the packed rows and the workspace."""
+    n = plan.n_total
+    _chk_n3(F64, n, _HBLOCK_STATE, *state)
+    if mass is not None:
+        _chk(mass, (n,), "mass", F64)
+    for t, nm in ((ticks, "ticks"), (levels, "levels")):
+        if t is not None:
+            _chk(t, (n,), nm, torch.int32)
+    _chk(params, (BATCH_HBLOCK_PARAM_ROWS, plan.n_scenes), "params", F64)
+    _chk(bsched, (plan.n_scenes + 1, HBLOCK_SCHED_INTS), "bsched", torch.int32)
+    for t, nm in zip(rows, ("posd", "veld", "accd")):
+        _chk_min_rows(t, plan.posm_rows, 4, nm, F64)
+    if ws is not None and _nbytes(ws) < plan.workspace_bytes:
+        raise _lib.NbdError("batch block workspace too small")
+
+
+def batch_hblock_init_levels(plan: BatchBlockPlan, acc, jerk, params, max_level: int, ticks, levels, bsched,
+                             mask=None) -> None:
+    """ticks = 0 and levels from dt_i = (eta_s / 2) |a| / |j| quantised to dt_s 2^-k for every scene (mask: a device int32
+    (S,), only the scenes it marks); the scenes' clamp counts and histograms, the ensemble's histogram, tick 0."""
+    _chk_bblock(plan, (acc, jerk), None, ticks, levels, params, bsched, (), None)
+    if mask is not None:
+        _chk(mask, (plan.n_scenes,), "mask", torch.int32)
+    _lib.launch("nbd_batch_hblock_init_levels_f64", bsched.device, *plan.head(), acc.data_ptr(), jerk.data_ptr(),
+                params.data_ptr(), int(max_level), _lib.ptr(mask), ticks.data_ptr(), levels.data_ptr(), bsched.data_ptr())
+
+
+def batch_hblock_schedule(plan: BatchBlockPlan, levels, max_level: int, bsched, counters, workspace,
+                          host_sched=None) -> None:
+    """t_next and every scene's active list of the next block step (bsched, the workspace), the per-scene counters.
+    host_sched: an int32 CPU tensor of at least 4 elements that receives {t_next, n_act_total, ...} after a stream sync."""
+    _chk(levels, (plan.n_total,), "levels", torch.int32)
+    _chk(bsched, (plan.n_scenes + 1, HBLOCK_SCHED_INTS), "bsched", torch.int32)
+    _chk(counters, (plan.n_scenes, 2), "counters", torch.int64)
+    if host_sched is not None and (host_sched.is_cuda or host_sched.dtype != torch.int32 or host_sched.numel() < 4):
+        raise _lib.NbdError("batch_hblock_schedule: host_sched must be an int32 CPU tensor of 4 elements")
+    _lib.launch("nbd_batch_hblock_schedule", levels.device, *plan.head(), levels.data_ptr(), int(max_level),
+                bsched.data_ptr(), counters.data_ptr(), workspace.data_ptr(), _nbytes(workspace), _lib.ptr(host_sched))
+
+
+def _bblock_entry(plan: BatchBlockPlan, stage: str) -> str:
+    return f"nbd_batch_{'hblock' if plan.order == 4 else 'hblock6'}_{stage}_f64"
+
+
+def batch_hblock_predict(plan: BatchBlockPlan, state, mass, ticks, params, max_level: int, bsched, rows) -> None:
+    """First launch of a batched block step: every body predicted to t_next into the packed rows. state: (pos, vel, acc,
+    jerk[, snap, crackle]); rows: (posd, veld[, accd])."""
+    _chk_bblock(plan, state, mass, ticks, None, params, bsched, rows, None)
+    _lib.launch(_bblock_entry(plan, "predict"), bsched.device, *plan.head(), *_ptrs(state), mass.data_ptr(),
+                ticks.data_ptr(), params.data_ptr(), int(max_level), bsched.data_ptr(), *_ptrs(rows))
+
+
+def batch_hblock_force(plan: BatchBlockPlan, rows, params, bsched, workspace) -> None:
+    """Second launch: the partial sums of every scene's listed bodies."""
+    _chk_bblock(plan, (), None, None, None, params, bsched, rows, workspace)
+    _lib.launch(_bblock_entry(plan, "force"), bsched.device, *plan.head(), *_ptrs(rows), params.data_ptr(),
+                bsched.data_ptr(), workspace.data_ptr(), _nbytes(workspace))
+
+
+def batch_hblock_correct(plan: BatchBlockPlan, state, mass, ticks, levels, params, max_level: int, bsched, posd,
+                         workspace) -> None:
+    """Third launch: slab sum, corrector and new level of every listed body; posd = {x1, m} for them."""
+    _chk_bblock(plan, state, mass, ticks, levels, params, bsched, (posd,), workspace)
+    _lib.launch(_bblock_entry(plan, "correct"), bsched.device, *plan.head(), *_ptrs(state), mass.data_ptr(),
+                ticks.data_ptr(), levels.data_ptr(), params.data_ptr(), int(max_level), bsched.data_ptr(),
+                posd.data_ptr(), workspace.data_ptr(), _nbytes(workspace))
+
+
+def batch_hblock_step(plan: BatchBlockPlan, state, mass, ticks, levels, params, max_level: int, bsched, rows,
+                      workspace) -> None:
+    """Predict, force and correct of the block step batch_hblock_schedule has just listed (three launches), in place."""
+    _chk_bblock(plan, state, mass, ticks, levels, params, bsched, rows, workspace)
+    _lib.launch(_bblock_entry(plan, "step"), bsched.device, *plan.head(), *_ptrs(state), mass.data_ptr(),
+                ticks.data_ptr(), levels.data_ptr(), params.data_ptr(), int(max_level), bsched.data_ptr(), *_ptrs(rows),
+                workspace.data_ptr(), _nbytes(workspace))
