@@ -186,6 +186,11 @@ int nbd_leapfrog_step_uniform_f32(float* pos, float* vel, const float* acc_in, f
 size_t nbd_accel_sym_workspace_bytes(int n);
 int nbd_accel_sym_uniform_f32(const float* posm, int n, float softening_sq, float g_const, float mass_value,
                               float* acc_out, void* workspace, size_t workspace_bytes, int variant, nbd_stream_t stream);
+/* The same force as the step launches it: variant 2, and where the workspace gives every round a slot of its own (K = M)
+ * the diagonal blocks run as the trailing workgroups of the one pair launch instead of in a launch in front of it. Same
+ * arguments, checks and workspace; bit-identical to variant 2 on the same workspace size. */
+int nbd_accel_sym_tail_uniform_f32(const float* posm, int n, float softening_sq, float g_const, float mass_value,
+                                   float* acc_out, void* workspace, size_t workspace_bytes, nbd_stream_t stream);
 
 /* One whole EulerSimulator.step (simulation.py:173-187): force -> kick(dt) -> drift(dt). */
 int nbd_euler_step_f32(float* pos, float* vel, float* acc_out, const float* mass, int n, float dt,

@@ -69,7 +69,10 @@ __global__ __launch_bounds__(64 * kWaves, KU == 4 ? 8 : 5) void accel_kernel(
 // every step (no zero fill: capturable). K is read off the workspace (plan_sym): min(M, 16) in the 16 slots the all-pairs
 // step needs at N = 65 536, up to min(M, 64) in a larger one. With K = M no round shares a slot: every round stores, the
 // fetch of an adding launch never runs and all M (M - 1) / 2 tile pairs go in ONE launch (N = 65 536: 2016 workgroups,
-// 3.94 residency rounds instead of four launches of one; 627.7 against 648.8 us, profiles/r15_sym_wide.txt).
+// 3.94 residency rounds instead of four launches of one; 627.7 against 648.8 us, profiles/r15_sym_wide.txt). The step's
+// form of that launch (accel_sym2_tail_kernel) carries the diagonal blocks too, as its highest-numbered workgroups: same
+// slot 0, same arithmetic and order as the diagonal launch, one launch less (599.6 against 20.3 + 587.4 us,
+// profiles/r25_sym_tail.txt).
 //
 // One workgroup = one tile pair (a, b): 4 target groups x SG source groups of waves. Wave (tg, sg) holds targets
 // a*S + tg*256 + 64 t + lane (t = 0..3, as the packed pairs {t0, t1}, {t2, t3}) and walks the 16 / SG 64-body chunks
@@ -250,15 +253,18 @@ __global__ __launch_bounds__(256 * SG, 2 * SG) void accel_sym_kernel(const f4* _
 constexpr int kSym2Pairs = kSymChunks / 2;   // chunk pairs (p, p + 8) of a tile
 constexpr int kSym2T = 8;                    // targets per lane
 constexpr int kSym2G = 2;                    // targets per scheduling group of the step (4: 128 VGPRs, 3 s_nop)
+constexpr int kSym2XyF = kSym2Pairs * 128 * 4;   // [pair][128] {x, x', y, y'}
+constexpr int kSym2ZF = kSym2Pairs * 128 * 2;    // [pair][128] {z, z'}
+constexpr int kSym2ReactF = 2 * 8 * 6 * 64;      // [j][wave][comp * 2 + half][lane]
+constexpr int kSym2OwnF = 8 * 3 * kSym2T * 64;   // [sg][tg][comp][t][lane], over all of the above after the walk
+static_assert(kSym2XyF + kSym2ZF + kSym2ReactF == kSym2OwnF, "one 48-KiB LDS image");
+constexpr int kSym2LdsF4 = kSym2OwnF / 4;        // the workgroup's f4[kSym2LdsF4], ONE object (keeps hipcc's waits sane)
 
-__global__ __launch_bounds__(512, 4) void accel_sym2_kernel(const f4* __restrict__ posm, int n, int m, int r0,
-                                                            int n_slots, float eps2, float* __restrict__ out) {
-  constexpr int kXyF = kSym2Pairs * 128 * 4;      // [pair][128] {x, x', y, y'}
-  constexpr int kZF = kSym2Pairs * 128 * 2;       // [pair][128] {z, z'}
-  constexpr int kReactF = 2 * 8 * 6 * 64;         // [j][wave][comp * 2 + half][lane]
-  constexpr int kOwnF = 8 * 3 * kSym2T * 64;      // [sg][tg][comp][t][lane], over all of the above after the walk
-  static_assert(kXyF + kZF + kReactF == kOwnF, "one 48-KiB LDS image");
-  __shared__ f4 lds[kOwnF / 4];                   // ONE object (keeps hipcc's waits sane)
+// The tile pair of workgroup wg of the launch that starts at round r0, by the 512 threads of a workgroup: the body of
+// accel_sym2_kernel and of the leading workgroups of accel_sym2_tail_kernel.
+__device__ __forceinline__ void sym2_body(const f4* __restrict__ posm, int n, int m, int r0, int n_slots, int wg,
+                                          float eps2, float* __restrict__ out, f4* lds) {
+  constexpr int kXyF = kSym2XyF, kZF = kSym2ZF;
   float* const ldsf = reinterpret_cast<float*>(lds);
   f4* const xy = lds;
   f2* const zz = reinterpret_cast<f2*>(ldsf + kXyF);
@@ -266,7 +272,7 @@ __global__ __launch_bounds__(512, 4) void accel_sym2_kernel(const f4* __restrict
 
   int ta, tb, slot;
   bool init;
-  sym_round_match(blockIdx.x, m, r0, n_slots, ta, tb, slot, init);
+  sym_round_match(wg, m, r0, n_slots, ta, tb, slot, init);
 
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -404,6 +410,40 @@ __global__ __launch_bounds__(512, 4) void accel_sym2_kernel(const f4* __restrict
     const float v = ((os[0] + os[kSg]) + os[2 * kSg]) + os[3 * kSg];
     o_a[o] = init ? v : olda[i] + v;
   }
+}
+
+__global__ __launch_bounds__(512, 4) void accel_sym2_kernel(const f4* __restrict__ posm, int n, int m, int r0,
+                                                            int n_slots, float eps2, float* __restrict__ out) {
+  __shared__ f4 lds[kSym2LdsF4];
+  sym2_body(posm, n, m, r0, n_slots, blockIdx.x, eps2, out, lds);
+}
+
+// ---- the whole core in ONE launch, for the plan with a slot per round (K = M): workgroups [0, M (M - 1) / 2) are the
+// tile pairs of accel_sym2_kernel, all rounds storing into slots 1 .. M - 1; the 4 M workgroups behind them run the
+// diagonal blocks into slot 0, with the arithmetic and the summation order of the diagonal launch of launch_sym
+// (accel_kernel<false, 8, true> on 8 groups x 1 slab per tile: accel_body<8, true> and the plan of 16 chunks over 4
+// waves). A trailing workgroup is two such groups of 4 waves side by side, group 2 d + h of the M x 8 in half h of
+// workgroup d, each half on its own accel_body LDS region of the 48-KiB object (2 x 14 KiB); both halves walk 4 chunks
+// per wave and meet at accel_body's one barrier. Workgroups are handed out in index order, so the diagonal groups come
+// last: they take the slots the fourth residency round leaves empty (N = 65 536: 2016 pair jobs in 4 x 512 slots) and
+// the slots that finished pair jobs free, where a launch of their own ran at 2 waves per SIMD behind a launch boundary.
+// No two workgroups write the same (slot, row): no order between them is needed.
+__global__ __launch_bounds__(512, 4) void accel_sym2_tail_kernel(const f4* __restrict__ posm, int n, int m, float eps2,
+                                                                 float* __restrict__ out) {
+  __shared__ f4 lds[kSym2LdsF4];
+  static_assert(2 * kAccelLdsF4 <= kSym2LdsF4, "two accel_body regions in the tile-pair image");
+  const int pairs = (m >> 1) * (m - 1);
+  if ((int)blockIdx.x < pairs) {
+    sym2_body(posm, n, m, 0, m, blockIdx.x, eps2, out, lds);
+    return;
+  }
+  const int half = __builtin_amdgcn_readfirstlane(threadIdx.x >> 8);
+  const int g = ((int)blockIdx.x - pairs) * 2 + half;          // group g of the M x 8 diagonal groups
+  constexpr int kGroups = kSymTile / kTgtPerWG;
+  const int tz = (g / kGroups) * kSymTile, t_base = (g % kGroups) * kTgtPerWG;
+  const SrcView sv = full_view(kSymTile, kSymChunks, 1);
+  accel_body<8, true>(posm + tz, sv, std::false_type{}, posm + tz, kSymTile, 0, t_base, 0, eps2, 1.0f,
+                      lds + half * kAccelLdsF4, out + ((size_t)tz + t_base) * 3, (int)(threadIdx.x & 255));
 }
 
 // acc = g * (slab_0 + slab_1 + ...), optional fused kick v += c * acc (simulation.py:88,170).
@@ -668,16 +708,29 @@ bool sym_step(int n, float eps2) { return n >= kSymStepMinN && eps2 >= kEps2Mask
 // eps2 >= kEps2Masked (the i == j term of a diagonal block is then an exact zero)
 // variant 0: 4 source groups (16-wave workgroups, 64 VGPRs, 2 per CU: 8 waves per SIMD); 1: 2 source groups (8 waves,
 // 86 VGPRs: 4 waves per SIMD); 2: accel_sym2_kernel (two sources per step, 8 waves, <= 128 VGPRs: 4 waves per SIMD)
+// kSymTailVariant (no number of the C-ABI): variant 2 with the diagonal blocks as the trailing workgroups of the one
+// pair launch where every round has its own slot (accel_sym2_tail_kernel); with K < M an adding round reads slot 0, the
+// diagonal launch has to come first and this IS variant 2.
+constexpr int kSymTailVariant = 3;
 int launch_sym(const float* posm, int n, float eps2, float* slots, const SymPlan& sp, hipStream_t st, int variant = 0) {
   const f4* pm = reinterpret_cast<const f4*>(posm);
-  // the diagonal blocks (a, a): the all-pairs kernel on each tile, slot 0
-  const AccelPlan dp = make_plan(kSymTile / kTgtPerWG, 1, kSymChunks);
-  int rc = launch_accel(posm, full_view(kSymTile, dp), posm, kSymTile, 0, eps2, 1.0f, slots, dp, st, true, n, sp.m,
-                        kSymTile);
-  if (rc) return rc;
-  // the off-diagonal rounds: [0, K-1) stores, then launches of K rounds add
+  const bool tail = variant == kSymTailVariant && sp.slots == sp.m;
+  if (variant == kSymTailVariant) variant = 2;
+  int rc = 0;
+  if (tail) {
+    accel_sym2_tail_kernel<<<(sp.m / 2) * (sp.m - 1) + sp.m * (kSymTile / kTgtPerWG) / 2, 512, 0, st>>>(pm, n, sp.m,
+                                                                                                      eps2, slots);
+    if ((rc = launch_status())) return rc;
+  } else {
+    // the diagonal blocks (a, a): the all-pairs kernel on each tile, slot 0
+    const AccelPlan dp = make_plan(kSymTile / kTgtPerWG, 1, kSymChunks);
+    rc = launch_accel(posm, full_view(kSymTile, dp), posm, kSymTile, 0, eps2, 1.0f, slots, dp, st, true, n, sp.m,
+                      kSymTile);
+    if (rc) return rc;
+  }
+  // the off-diagonal rounds: [0, K-1) stores, then launches of K rounds add (the tail launch has run them all)
   const int rounds = sp.m - 1;
-  for (int r0 = 0; r0 < rounds;) {
+  for (int r0 = tail ? rounds : 0; r0 < rounds;) {
     const int r1 = r0 == 0 ? (sp.slots - 1 < rounds ? sp.slots - 1 : rounds) : (r0 + sp.slots < rounds ? r0 + sp.slots : rounds);
     const int wgs = (r1 - r0) * (sp.m / 2);
     if (variant == 2) accel_sym2_kernel<<<wgs, 512, 0, st>>>(pm, n, sp.m, r0, sp.slots, eps2, slots);
@@ -764,9 +817,10 @@ size_t nbd_step_workspace_pref_bytes(int n) {
 
 size_t nbd_accel_sym_workspace_bytes(int n) { return n <= 0 ? 0 : sym_workspace_bytes(n); }
 
-int nbd_accel_sym_uniform_f32(const float* posm, int n, float softening_sq, float g_const, float mass_value,
-                              float* acc_out, void* workspace, size_t workspace_bytes, int variant, nbd_stream_t stream) {
-  if (n < 0 || (n > 0 && (!posm || !acc_out)) || misaligned16(posm) || variant < 0 || variant > 2) return NBD_E_BADARG;
+// the symmetric force on its own: launch_sym(variant) and the finishing pass
+static int accel_sym_uniform(const float* posm, int n, float softening_sq, float g_const, float mass_value,
+                             float* acc_out, void* workspace, size_t workspace_bytes, int variant, nbd_stream_t stream) {
+  if (n < 0 || (n > 0 && (!posm || !acc_out)) || misaligned16(posm)) return NBD_E_BADARG;
   if (n == 0) return 0;
   if (plan_sym(n).m < 2 || softening_sq < kEps2Masked) return NBD_E_UNSUPPORTED;
   if (!workspace || workspace_bytes < sym_workspace_bytes(n)) return NBD_E_WORKSPACE;
@@ -779,6 +833,19 @@ int nbd_accel_sym_uniform_f32(const float* posm, int n, float softening_sq, floa
   finish_kernel<<<ceil_div(n3, 64), 256, 0, st>>>(slots, sp.total_slots, (size_t)n3, g_const * mass_value,
                                                    acc_out, nullptr, 0.f, n3);
   return launch_status();
+}
+
+int nbd_accel_sym_uniform_f32(const float* posm, int n, float softening_sq, float g_const, float mass_value,
+                              float* acc_out, void* workspace, size_t workspace_bytes, int variant, nbd_stream_t stream) {
+  if (variant < 0 || variant > 2) return NBD_E_BADARG;
+  return accel_sym_uniform(posm, n, softening_sq, g_const, mass_value, acc_out, workspace, workspace_bytes, variant,
+                           stream);
+}
+
+int nbd_accel_sym_tail_uniform_f32(const float* posm, int n, float softening_sq, float g_const, float mass_value,
+                                   float* acc_out, void* workspace, size_t workspace_bytes, nbd_stream_t stream) {
+  return accel_sym_uniform(posm, n, softening_sq, g_const, mass_value, acc_out, workspace, workspace_bytes,
+                           kSymTailVariant, stream);
 }
 
 int nbd_accel_f32(const float* posm_src, int n_src, const float* posm_tgt, int n_tgt,
@@ -993,7 +1060,8 @@ int nbd_snapshot_f64(const double* pos, const double* vel, const double* acc, in
 // What the whole-system steps share: check, update the bodies and pack them (the kick-drift of a leapfrog step with
 // acc_in; euler: a plain pack), the force of all n bodies into slabs, then acc = g_scale * (slab sum) and the fused kick
 // v += c_kick acc. uniform: the kernels without the per-pair mass multiply (g_scale carries the mass), and from
-// kSymStepMinN bodies on every pair once (accel_sym2_kernel).
+// kSymStepMinN bodies on every pair once (accel_sym2_tail_kernel where the workspace holds a slot per round: three
+// launches a step; else the diagonal launch and accel_sym2_kernel).
 static int step_force(float* pos, float* vel, const float* acc_in, float* acc_out, const float* mass, int n, bool euler,
                       float c_kick, float c_drift, float softening_sq, float g_scale, bool uniform, float* posm,
                       void* workspace, size_t workspace_bytes, nbd_stream_t stream, void* ev_force_begin,
@@ -1013,7 +1081,7 @@ static int step_force(float* pos, float* vel, const float* acc_in, float* acc_ou
   float* slabs = static_cast<float*>(workspace);
   if (ev_force_begin && (rc = check(hipEventRecord((hipEvent_t)ev_force_begin, st)))) return rc;
   const SymPlan sp = plan_sym(n, sym ? sym_slots_avail(n, workspace_bytes) : 0);
-  if (sym) rc = launch_sym(posm, n, softening_sq, slabs, sp, st, 2);
+  if (sym) rc = launch_sym(posm, n, softening_sq, slabs, sp, st, kSymTailVariant);
   else rc = launch_accel(posm, full_view(n, p), posm, n, 0, softening_sq, 1.0f, slabs, p, st, uniform);
   if (rc) return rc;
   if (ev_force_end && (rc = check(hipEventRecord((hipEvent_t)ev_force_end, st)))) return rc;

@@ -172,14 +172,16 @@ __device__ __forceinline__ void interact_block(const f4* __restrict__ buf, const
 // or a std::integral_constant where the kernel's template parameter decides (the dead loop is never emitted). The 4 waves' partials are reduced through LDS ([wave][comp*2+half][64]) in wave
 // order into one coalesced store dst[t * 3 + comp] = scale * sum for the valid targets. lds: the workgroup's
 // f4[kAccelLdsF4]: [wave][buffer][64] staging + [wave][6][64] partials, ONE object (keeps hipcc's waits sane).
+// tid: the thread's index among the 4 waves (threadIdx.x, or its low 8 bits where a 512-thread workgroup runs two groups
+// side by side, each on its own lds region: both halves then meet at the one __syncthreads()).
 constexpr int kAccelLdsF4 = kWaves * 2 * kChunk + kWaves * 6 * 64 / 4;
 
 template <int KU, bool UNI, class Masked>
 __device__ __forceinline__ void accel_body(const f4* __restrict__ src, const SrcView& sv, const Masked masked,
                                            const f4* __restrict__ tgt, int n_tgt, int tgt_off, int t_base, int slab,
-                                           float eps2, float scale, f4* lds, float* __restrict__ dst) {
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+                                           float eps2, float scale, f4* lds, float* __restrict__ dst, const int tid) {
+  const int lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int i0 = t_base + lane, i1 = t_base + 64 + lane;
   const f4 t0 = tgt[min(i0, n_tgt - 1)], t1 = tgt[min(i1, n_tgt - 1)];
   const f2 xi = {t0.x, t1.x}, yi = {t0.y, t1.y}, zi = {t0.z, t1.z};
@@ -225,7 +227,7 @@ __device__ __forceinline__ void accel_body(const f4* __restrict__ src, const Src
   mine[4 * 64 + lane] = az.x; mine[5 * 64 + lane] = az.y;
   __syncthreads();
   const int n_valid = min(kTgtPerWG, n_tgt - t_base) * 3;
-  for (int o = threadIdx.x; o < n_valid; o += 64 * kWaves) {
+  for (int o = tid; o < n_valid; o += 64 * kWaves) {
     const int lt = o / 3, comp = o - lt * 3;
     const int idx = (comp * 2 + (lt >> 6)) * 64 + (lt & 63);
     float sum = red[idx];
@@ -233,6 +235,14 @@ __device__ __forceinline__ void accel_body(const f4* __restrict__ src, const Src
     for (int w = 1; w < kWaves; ++w) sum += red[w * 6 * 64 + idx];
     dst[o] = __fmul_rn(scale, sum);
   }
+}
+
+// the workgroup IS the 4 waves
+template <int KU, bool UNI, class Masked>
+__device__ __forceinline__ void accel_body(const f4* __restrict__ src, const SrcView& sv, const Masked masked,
+                                           const f4* __restrict__ tgt, int n_tgt, int tgt_off, int t_base, int slab,
+                                           float eps2, float scale, f4* lds, float* __restrict__ dst) {
+  accel_body<KU, UNI>(src, sv, masked, tgt, n_tgt, tgt_off, t_base, slab, eps2, scale, lds, dst, threadIdx.x);
 }
 
 // ---- energies (simulation.py:91-115). U = sum_{i<j} -G m_i m_j / (|r_ij| + eps), K = sum 0.5 m v^2.

@@ -171,6 +171,8 @@ SIGNATURES = {
     "nbd_accel_sym_workspace_bytes": (c_size_t, [c_int]),
     "nbd_accel_sym_uniform_f32": (c_int, [c_void_p, c_int, c_float, c_float, c_float, c_void_p, c_void_p, c_size_t,
                                           c_int, c_void_p]),
+    "nbd_accel_sym_tail_uniform_f32": (c_int, [c_void_p, c_int, c_float, c_float, c_float, c_void_p, c_void_p,
+                                               c_size_t, c_void_p]),
     "nbd_euler_step_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_float, c_float,
                                    c_float, c_void_p, c_void_p, c_size_t, c_void_p]),
     "nbd_energy_workspace_bytes": (c_size_t, [c_int]),
