@@ -756,6 +756,56 @@ int nbd_accel_jerk_snap_active_f64(const double* posd, const double* veld, const
                                    double* snap_out, void* workspace, size_t workspace_bytes, int slabs,
                                    nbd_stream_t stream);
 
+/* ---- a block step divided over the ranks of a process group (csrc/direct_hermite_block_split_f64.hip), float64, both
+ * orders. Every rank holds the whole state, bit for bit the same, and runs nbd_hblock_schedule and the predict entry as
+ * they are. A block step with many active bodies is then: nbd_hblock_order_list (the list in ascending body index, alike
+ * on every rank); the rows entry for the rank's slice [first, first + count) of the list, which evaluates the slice at its
+ * own plan (the slab count of `count` targets), corrects it with each body's own step and writes a header row and one
+ * result row per entry into rows_out WITHOUT touching state, levels, ticks or sched; an exchange of the pieces (the
+ * caller's: equal pieces of 1 + q rows, rank after rank, into rows_all); and the apply entry on every rank over all n_act
+ * entries: the rows scattered into the state, posd[i] = {x1, m}, the new level, ticks[i] = t_next (0 at 2^K), the level
+ * histogram, the clamp count, the current tick. List entry p lies in row (p / q) (q + 1) + 1 + p % q of rows_all.
+ * A row is NBD_HBLOCK_SPLIT_ROW = 16 doubles (x1 v1 a1 j1, three spare) resp. NBD_HBLOCK6_SPLIT_ROW = 20 (x1 v1 a1 j1 s1
+ * c1, one spare); its last double-sized slot holds two int32, {the new level by the block scheme's rules, clamped}. The
+ * header row has the same width and starts with int32 {t_next, n_act, first, count}. Spare parts are written as zeros.
+ * Apply compares every piece's header with its own record and with the slice that piece should hold (first = min(r q,
+ * n_act)); on a mismatch it sets sched[6] (0 otherwise; nbd_hblock_init_levels* clear it) and writes the state all the
+ * same. The rows of a slice are the bits nbd_hblock*_correct_f64 would have stored wherever the slab counts of `count` and
+ * of n_act targets agree (always for n <= 448). Workspace: nbd_hblock_split_f64_workspace_bytes(n) resp. the hblock6 twin,
+ * 32-byte aligned: the ordered list, the ordering's scratch, then a block workspace of the order for the slice. Its head
+ * is laid out as nbd_hblock*_f64_workspace_bytes(n)'s, so nbd_hblock_schedule and an un-divided nbd_hblock*_step_f64 run on
+ * the same buffer. No float atomics, no memsets; buffers may hold anything on entry. Bad arguments (-1), then a short or
+ * misaligned workspace (-2), are refused before any launch. */
+#define NBD_HBLOCK_SPLIT_ROW 16
+#define NBD_HBLOCK6_SPLIT_ROW 20
+size_t nbd_hblock_split_f64_workspace_bytes(int n);
+size_t nbd_hblock6_split_f64_workspace_bytes(int n);
+/* The list nbd_hblock_schedule has just written, rewritten in ascending body index (two launches, integer work, no
+ * readback). sched is read only: t_next, n_act and the cursor fields stay as the scheduler left them. */
+int nbd_hblock_order_list(const int* levels, int n, int max_level, int* sched, void* workspace, size_t workspace_bytes,
+                          nbd_stream_t stream);
+/* The header and the `count` result rows of list entries [first, first + count) into rows_out (32-byte aligned,
+ * (1 + count) rows). count = 0: the header only, no force. posd / veld (/ accd): the predict entry's rows. */
+int nbd_hblock_split_rows_f64(const double* pos, const double* vel, const double* acc, const double* jerk,
+                              const int* levels, int n, int n_act, int first, int count, int max_level, double dt,
+                              double eta, double softening_sq, double g_const, const int* sched, const double* posd,
+                              const double* veld, double* rows_out, void* workspace, size_t workspace_bytes,
+                              nbd_stream_t stream);
+int nbd_hblock6_split_rows_f64(const double* pos, const double* vel, const double* acc, const double* jerk,
+                               const double* snap, const int* levels, int n, int n_act, int first, int count,
+                               int max_level, double dt, double eta, double softening_sq, double g_const,
+                               const int* sched, const double* posd, const double* veld, const double* accd,
+                               double* rows_out, void* workspace, size_t workspace_bytes, nbd_stream_t stream);
+/* All n_act rows of rows_all (world pieces of 1 + q rows; world * q >= n_act) into the state, with the bookkeeping. */
+int nbd_hblock_split_apply_f64(const double* rows_all, int world, int q, int n_act, double* pos, double* vel,
+                               double* acc, double* jerk, const double* mass, int* ticks, int* levels, int n,
+                               int max_level, int* sched, double* posd, void* workspace, size_t workspace_bytes,
+                               nbd_stream_t stream);
+int nbd_hblock6_split_apply_f64(const double* rows_all, int world, int q, int n_act, double* pos, double* vel,
+                                double* acc, double* jerk, double* snap, double* crackle, const double* mass,
+                                int* ticks, int* levels, int n, int max_level, int* sched, double* posd,
+                                void* workspace, size_t workspace_bytes, nbd_stream_t stream);
+
 /* ---- block-timestep Hermite per scene, 4th and 6th order (csrc/direct_batch_hermite_block_f64.hip): the two block
  * schemes above applied to every scene of an ensemble (offsets, n_scenes as in "batched direct integrator") by ONE
  * schedule and one set of launches per block step, float64 only. All scenes share one tick grid of 2^K ticks per output

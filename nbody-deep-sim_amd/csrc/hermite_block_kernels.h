@@ -12,6 +12,10 @@
 // arithmetic, hblock_ticks_len, hblock_initial_level and the two re-levelling functions from here and has kernels of its own.
 // The 6th order of the fp64 unit takes the record, the level arithmetic, the initial levels, hblock_move_level and
 // hblock6_relevel from here and has O(N) kernels of its own, in that unit, over hermite6_f64_kernels.h's rows.
+// direct_hermite_block_split_f64.hip (a block step divided over the ranks of a process group) corrects a slice without
+// touching the state and books all rows in a launch of its own, so the re-levelling is stated in its parts: the
+// criterion's wanted level (hblock_wanted, hblock6_wanted), the level rules (hblock_next_level, pure) and the bookkeeping
+// (hblock_book_level); hblock_move_level, hblock_relevel and hblock6_relevel are their compositions.
 // The definitions sit in an anonymous namespace: every translation unit that includes this file gets its own inlined copies.
 #pragma once
 #include <math.h>
@@ -25,8 +29,9 @@ constexpr int kMaxLevel = 20;        // 2^20 ticks per interval: the tick count 
 
 // sched[NBD_HBLOCK_SCHED_INTS]: t_next and n_act of the block step being taken, the cumulative clamp count, the tick T
 // every body has reached (the last t_next, 0 at the start of an interval), the compaction's write cursor and its count
-// of finished workgroups (both 0 between launches), and the level histogram (bin k: bodies at level k)
-enum { kTNext = 0, kNAct = 1, kClamped = 2, kTCur = 3, kCursor = 4, kDone = 5, kHist = 8 };
+// of finished workgroups (both 0 between launches), the flag a split block step raises when the ranks' headers disagree
+// (direct_hermite_block_split_f64.hip; 0 otherwise), and the level histogram (bin k: bodies at level k)
+enum { kTNext = 0, kNAct = 1, kClamped = 2, kTCur = 3, kCursor = 4, kDone = 5, kDiverged = 6, kHist = 8 };
 static_assert(kHist + kMaxLevel + 1 <= NBD_HBLOCK_SCHED_INTS, "sched holds the level histogram");
 
 inline bool bad_level(int K) { return K < 0 || K > kMaxLevel; }
@@ -128,24 +133,31 @@ __global__ __launch_bounds__(256) void hblock_predict_kernel(const T* __restrict
   velp[i] = vp;
 }
 
-// The level rules and the bookkeeping of a corrected body i at level lev (step d ticks) whose criterion wants level
-// `want`: shrink freely; grow by one level where t_next is a multiple of 2 d; deeper than K (NaN included) clamped and
-// counted. Moves the body in the level histogram, sets t_i = t_next (0 at 2^K); `first` (one thread of the launch)
-// publishes that tick as sched[kTCur].
-__device__ __forceinline__ void hblock_move_level(int want, int K, int lev, int d, int i, bool first,
-                                                  int* __restrict__ ticks, int* __restrict__ levels,
-                                                  int* __restrict__ sched) {
-  const int t_next = sched[kTNext];
+// The level rules of a corrected body at level lev (step d ticks) whose criterion wants level `want`, at the block step
+// to t_next: shrink freely; grow by one level where t_next is a multiple of 2 d; deeper than K (NaN included) clamped,
+// which `clamped` reports. Pure: direct_hermite_block_split_f64.hip forms a result row from it and books it elsewhere.
+__device__ __forceinline__ int hblock_next_level(int want, int K, int lev, int d, int t_next, bool& clamped) {
   int nl = lev;
+  clamped = false;
   if (want > lev) {
     nl = want;
     if (nl > K) {
       nl = K;
-      atomicAdd(&sched[kClamped], 1);
+      clamped = true;
     }
   } else if (want < lev && (t_next & (2 * d - 1)) == 0) {
     nl = lev - 1;
   }
+  return nl;
+}
+
+// The bookkeeping of a corrected body i that goes from level lev to nl at the block step to t_next: a clamp is counted,
+// the body moves in the level histogram, t_i = t_next (0 at 2^K); `first` (one thread of the launch) publishes that tick
+// as sched[kTCur].
+__device__ __forceinline__ void hblock_book_level(int nl, bool clamped, int K, int lev, int t_next, int i, bool first,
+                                                  int* __restrict__ ticks, int* __restrict__ levels,
+                                                  int* __restrict__ sched) {
+  if (clamped) atomicAdd(&sched[kClamped], 1);
   if (nl != lev) {
     atomicSub(&sched[kHist + lev], 1);
     atomicAdd(&sched[kHist + nl], 1);
@@ -156,14 +168,22 @@ __device__ __forceinline__ void hblock_move_level(int want, int K, int lev, int 
   if (first) sched[kTCur] = t_now;
 }
 
+// Both for a body corrected in place: hblock_next_level's rules, then hblock_book_level.
+__device__ __forceinline__ void hblock_move_level(int want, int K, int lev, int d, int i, bool first,
+                                                  int* __restrict__ ticks, int* __restrict__ levels,
+                                                  int* __restrict__ sched) {
+  const int t_next = sched[kTNext];
+  bool clamped;
+  const int nl = hblock_next_level(want, K, lev, d, t_next, clamped);
+  hblock_book_level(nl, clamped, K, lev, t_next, i, first, ticks, levels, sched);
+}
+
 // The new level of body i, corrected from (a0, j0) to (a1, j1) over its step h = d ticks at level lev, from the Aarseth
 // criterion in fp64, by hblock_move_level's rules.
 //   a3 =(12 (a0 - a1) + 6 h (j0 + j1)) / h^3, a2(t1) = (-6 (a0 - a1) - h (4 j0 + 2 j1)) / h^2 + h a3
 template <class T>
-__device__ __forceinline__ void hblock_relevel(const T* a0, const T* j0, const T* a1, const T* j1, double h, double dt,
-                                               double eta, int K, int lev, int d, int i, bool first,
-                                               int* __restrict__ ticks, int* __restrict__ levels,
-                                               int* __restrict__ sched) {
+__device__ __forceinline__ int hblock_wanted(const T* a0, const T* j0, const T* a1, const T* j1, double h, double dt,
+                                             double eta, int K) {
   double a3[3], a2[3];
 #pragma unroll
   for (int k = 0; k < 3; ++k) {
@@ -173,8 +193,15 @@ __device__ __forceinline__ void hblock_relevel(const T* a0, const T* j0, const T
   }
   const double na1 = norm3(a1[0], a1[1], a1[2]), nj1 = norm3(j1[0], j1[1], j1[2]);
   const double na2 = norm3(a2[0], a2[1], a2[2]), na3 = norm3(a3[0], a3[1], a3[2]);
-  const double crit = criterion(eta, na1 * na2 + nj1 * nj1, nj1 * na3 + na2 * na2);
-  hblock_move_level(wanted_level(crit, dt, K), K, lev, d, i, first, ticks, levels, sched);
+  return wanted_level(criterion(eta, na1 * na2 + nj1 * nj1, nj1 * na3 + na2 * na2), dt, K);
+}
+
+template <class T>
+__device__ __forceinline__ void hblock_relevel(const T* a0, const T* j0, const T* a1, const T* j1, double h, double dt,
+                                               double eta, int K, int lev, int d, int i, bool first,
+                                               int* __restrict__ ticks, int* __restrict__ levels,
+                                               int* __restrict__ sched) {
+  hblock_move_level(hblock_wanted(a0, j0, a1, j1, h, dt, eta, K), K, lev, d, i, first, ticks, levels, sched);
 }
 
 // ... and of a 6th-order body (direct_hermite_block_f64.hip), corrected from (a0, j0, s0) to (a1, j1, s1) with the
@@ -185,11 +212,9 @@ __device__ __forceinline__ void hblock_relevel(const T* a0, const T* j0, const T
 //   a5 = (720 (a1 - a0) - 360 h (j1 + j0) + 60 h^2 (s1 - s0)) / h^5
 //   a4(t1) = (-360 (a1 - a0) + h (168 j1 + 192 j0) + h^2 (-24 s1 + 36 s0)) / h^4 + h a5,   a3(t1) = c1.
 // Every operation rounds on its own (the build has -ffp-contract=off). The level rules are hblock_move_level's.
-__device__ __forceinline__ void hblock6_relevel(const double* a0, const double* j0, const double* s0, const double* a1,
-                                                const double* j1, const double* s1, const double* c1, double h,
-                                                double dt, double eta, int K, int lev, int d, int i, bool first,
-                                                int* __restrict__ ticks, int* __restrict__ levels,
-                                                int* __restrict__ sched) {
+__device__ __forceinline__ int hblock6_wanted(const double* a0, const double* j0, const double* s0, const double* a1,
+                                              const double* j1, const double* s1, const double* c1, double h, double dt,
+                                              double eta, int K) {
   double a4[3], a5[3];
   const double h2 = h * h, h4 = h2 * h2, h5 = h4 * h;
 #pragma unroll
@@ -200,8 +225,16 @@ __device__ __forceinline__ void hblock6_relevel(const double* a0, const double* 
   }
   const double na1 = norm3(a1[0], a1[1], a1[2]), nj1 = norm3(j1[0], j1[1], j1[2]), ns1 = norm3(s1[0], s1[1], s1[2]);
   const double nc1 = norm3(c1[0], c1[1], c1[2]), na4 = norm3(a4[0], a4[1], a4[2]), na5 = norm3(a5[0], a5[1], a5[2]);
-  const double crit = cbrt(criterion(eta * eta * eta, na1 * ns1 + nj1 * nj1, nc1 * na5 + na4 * na4));
-  hblock_move_level(wanted_level(crit, dt, K), K, lev, d, i, first, ticks, levels, sched);
+  return wanted_level(cbrt(criterion(eta * eta * eta, na1 * ns1 + nj1 * nj1, nc1 * na5 + na4 * na4)), dt, K);
+}
+
+__device__ __forceinline__ void hblock6_relevel(const double* a0, const double* j0, const double* s0, const double* a1,
+                                                const double* j1, const double* s1, const double* c1, double h,
+                                                double dt, double eta, int K, int lev, int d, int i, bool first,
+                                                int* __restrict__ ticks, int* __restrict__ levels,
+                                                int* __restrict__ sched) {
+  hblock_move_level(hblock6_wanted(a0, j0, s0, a1, j1, s1, c1, h, dt, eta, K), K, lev, d, i, first, ticks, levels,
+                    sched);
 }
 
 // The active bodies' corrector, one workgroup per HermiteFmt<T>::kSumRows consecutive list entries: a1, j1 =

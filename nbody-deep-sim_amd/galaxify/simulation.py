@@ -429,6 +429,21 @@ class _Float64:
         direct.hblock_step_f64(s.positions, s.velocities, s.accelerations, s.jerks, s.masses, s._ticks, s.levels, n_act,
                                s.max_level, s.dt, s.eta, *self._scalars(s), s._sched, s._posd, s._veld, s._bws)
 
+    # a block step divided over the ranks of a group (csrc/direct_hermite_block_split_f64.hip; _BlockSteps._split_step):
+    # the order, the predictor of all bodies, the state arrays a result row carries and the ones the rows are formed from
+    block_order = 4
+    split_row = direct.HBLOCK_SPLIT_ROW
+
+    def _block_predict(self, s):
+        direct.hblock_predict_f64(s.positions, s.velocities, s.accelerations, s.jerks, s.masses, s._ticks, s.levels,
+                                  s.max_level, s.dt, s._sched, s._posd, s._veld)
+
+    def _block_state(self, s):
+        return s.positions, s.velocities, s.accelerations, s.jerks
+
+    def _block_rows_in(self, s):
+        return self._block_state(s), (s._posd, s._veld)
+
 
 class _Hermite6Float64(_Float64):
     """The number format of Hermite6Simulator: `_Float64` with the calls that differ for the 6th order
@@ -475,6 +490,19 @@ class _Hermite6Float64(_Float64):
         direct.hblock6_step_f64(s.positions, s.velocities, s.accelerations, s.jerks, s.snaps, s.crackles, s.masses,
                                 s._ticks, s.levels, n_act, s.max_level, s.dt, s.eta, *self._scalars(s), s._sched,
                                 s._posd, s._veld, s._accd, s._bws)
+
+    block_order = 6
+    split_row = direct.HBLOCK6_SPLIT_ROW
+
+    def _block_predict(self, s):
+        direct.hblock6_predict_f64(s.positions, s.velocities, s.accelerations, s.jerks, s.snaps, s.crackles, s.masses,
+                                   s._ticks, s.levels, s.max_level, s.dt, s._sched, s._posd, s._veld, s._accd)
+
+    def _block_state(self, s):
+        return s.positions, s.velocities, s.accelerations, s.jerks, s.snaps, s.crackles
+
+    def _block_rows_in(self, s):             # the crackle is formed, never read
+        return self._block_state(s)[:5], (s._posd, s._veld, s._accd)
 
 
 _FORMATS = {fmt.dtype: fmt for fmt in (_Float32(), _Float64())}
@@ -1123,7 +1151,8 @@ class Hermite6Simulator(HermiteSimulator):
 class _BlockSteps:
     """What the block-timestep simulators share (BlockHermiteSimulator, BlockHermite6Simulator), mixed in in front of the
     shared-timestep class whose scheme they run: the parameters `eta` and `max_level`, the int32 schedule state, the
-    counters, the initial levels, the loop of block steps that makes one step() and the refusal of `process_group`. The
+    counters, the initial levels, the loop of block steps that makes one step(), and `process_group`: its refusals and
+    the block step divided over its ranks (`_split_step`; float64, state replicated on every rank). The
     class's format object gives the workspace (`block_workspace`), the initial levels (`block_init_levels`, from
     `accelerations` and `jerks`) and `block_step(sim, n_act)`: the predict, force and correct of the block step the
     schedule has just listed, over the simulator's own state arrays."""
@@ -1131,19 +1160,61 @@ class _BlockSteps:
     MAX_LEVEL_LIMIT = 20
 
     @classmethod
-    def _refuse_process_group(cls, process_group):
-        if process_group is not None:
-            raise ValueError(f"{cls.__name__}: there is no range-sharded block-timestep step; process_group is not "
-                             "supported")
+    def _check_group(cls, process_group, split_min_active, dtype):
+        """The refusals of `process_group` and `split_min_active`, before anything is resolved or allocated."""
+        who = cls.__name__
+        if process_group is None:
+            if split_min_active is not None:
+                raise ValueError(f"{who}: split_min_active is the threshold of the block steps divided over a "
+                                 "process_group; there is none")
+            return
+        import torch.distributed as dist
+        if not (dist.is_available() and isinstance(process_group, dist.ProcessGroup)):
+            raise ValueError(f"{who}: process_group must be a torch.distributed.ProcessGroup, got "
+                             f"{type(process_group).__name__}")
+        if dtype is not torch.float64:
+            raise ValueError(f"{who}: block steps are divided over a process_group in float64 only (dtype={dtype})")
+        if split_min_active is None:
+            raise ValueError(f"{who}: a process_group divides the block steps with at least split_min_active active "
+                             f"bodies, and no exchange has been measured to set that threshold by default: pass "
+                             f"split_min_active (an int >= 1; {who}.default_split_min_active(n, world) is the "
+                             "provisional model)")
+        if not (type(split_min_active) is int and split_min_active >= 1):
+            raise ValueError(f"{who}: split_min_active must be an int >= 1, got {split_min_active!r}")
 
-    def _init_block(self, eta, max_level):
+    @staticmethod
+    def default_split_min_active(n: int, world: int) -> int:
+        """A provisional threshold to pass as `split_min_active` (the constructors take none by themselves: a group
+        without a threshold is refused): max(64 world, ceil(2^25 / n)) active bodies. On one GPU, one of 8 emulated ranks and
+        no transport, the rank's share of a divided step first beats the un-divided step at n_act = 512 (n = 65 536) and
+        512 to 1 024 (n = 16 384); at this threshold it is 10 to 30 us ahead, which is what is left for an exchange that
+        nobody has measured (DESIGN.md K-HBS, NOTES.md; tools/bench_hermite_block_split.py)."""
+        return max(64 * world, -(-(1 << 25) // max(n, 1)))
+
+    def _init_block(self, eta, max_level, process_group=None, split_min_active=None):
         self.eta = eta
         self.max_level = max_level
         self.levels = torch.zeros(self.n, dtype=torch.int32, device=self.device)
         self._ticks = torch.zeros(self.n, dtype=torch.int32, device=self.device)
         self._sched = torch.zeros(direct.HBLOCK_SCHED_INTS, dtype=torch.int32, device=self.device)
-        self._sched_host = torch.zeros(4, dtype=torch.int32).pin_memory()
-        self._bws = self._fmt.block_workspace(max(self.n, 1), self.device)
+        self._sched_host = torch.zeros(8, dtype=torch.int32).pin_memory()
+        # the group of the divided block steps, in an attribute of its own: the state is replicated, so nothing of
+        # BaseSimulator's range-sharded path (`_sharded`, `part`) is used
+        self.process_group = self._split_group = process_group
+        world, self._split_rank = nbd_dist.group_info(process_group) if process_group is not None else (1, 0)
+        self._split_world = world
+        forced = os.environ.get("NBD_FORCE_SHARDED") == "1"
+        self._split = process_group is not None and self.n > 0 and (world > 1 or forced)
+        self.split_min_active = split_min_active      # (_check_group: an int with a group, None without)
+        self.split_block_steps = 0
+        self.exchanged_rows = 0
+        if self._split:
+            self._bws = direct.hblock_split_workspace(self.n, self.device, self._fmt.block_order)
+            q_max = direct.hblock_split_q(direct.hblock_split_slices(self.n, world))
+            self._pieces = nbd_dist.PieceExchange(world, q_max, self._fmt.split_row, self.device, process_group,
+                                                  collective=forced)
+        else:
+            self._bws = self._fmt.block_workspace(max(self.n, 1), self.device)
         self.block_steps = 0
         self.pair_interactions = 0
         self.clamped = 0
@@ -1168,8 +1239,28 @@ class _BlockSteps:
         self._read_clamped()
 
     def _read_clamped(self):
-        self._sched_host.copy_(self._sched[:4])
+        self._sched_host.copy_(self._sched[:8])
         self.clamped = int(self._sched_host[2])
+        if int(self._sched_host[direct.HBLOCK_SCHED_DIVERGED]):
+            raise RuntimeError(f"{type(self).__name__}: the replicas diverged: a rank's piece of a divided block step "
+                               "did not carry this rank's t_next, n_act or slice")
+
+    def _split_step(self, n_act: int):
+        """The block step the schedule has just listed, divided over the ranks: the list in index order, every body
+        predicted, this rank's slice into its piece, one exchange, all rows applied."""
+        fmt, K = self._fmt, self.max_level
+        slices = direct.hblock_split_slices(n_act, self._split_world)
+        q = direct.hblock_split_q(slices)
+        first, count = slices[self._split_rank]
+        direct.hblock_order_list(self.levels, K, self._sched, self._bws)
+        fmt._block_predict(self)
+        state, rows = fmt._block_rows_in(self)
+        direct.hblock_split_rows(state, self.levels, n_act, first, count, K, self.dt, self.eta, *fmt._scalars(self),
+                                 self._sched, rows, self._pieces.send, self._bws)
+        direct.hblock_split_apply(self._pieces.exchange(q), self._split_world, q, n_act, fmt._block_state(self),
+                                  self.masses, self._ticks, self.levels, K, self._sched, self._posd, self._bws)
+        self.split_block_steps += 1
+        self.exchanged_rows += n_act
 
     def step(self):
         """One output interval: block steps until every body is back at tick 2^max_level (at most 2^max_level of them)."""
@@ -1187,7 +1278,10 @@ class _BlockSteps:
             t_next, n_act = int(host[0]), int(host[1])
             if not (t_prev < t_next <= end and 1 <= n_act <= self.n):
                 raise RuntimeError(f"{who}: corrupt schedule (t_next={t_next}, n_act={n_act}, previous tick {t_prev})")
-            self._fmt.block_step(self, n_act)
+            if self._split and n_act >= self.split_min_active:
+                self._split_step(n_act)
+            else:
+                self._fmt.block_step(self, n_act)
             self.block_steps += 1
             self.pair_interactions += n_act * self.n
             if self.level_history is not None:
@@ -1222,19 +1316,40 @@ class BlockHermiteSimulator(_BlockSteps, HermiteSimulator):
     device tensors, g_const, softening ** 2, dt and every body's own step constants go to the kernels as doubles, and the
     pair arithmetic and all sums are float64; levels, ticks and the schedule stay int32. An fp32 block run stops gaining
     from a smaller eta at the fp32 floor of the orbit; this mode follows the criterion down to float64 rounding. With
-    max_level=0 it is HermiteSimulator(dtype=torch.float64) bit for bit. compute_*() and run() are that class's."""
+    max_level=0 it is HermiteSimulator(dtype=torch.float64) bit for bit. compute_*() and run() are that class's.
+
+    `process_group` (float64 only; csrc/direct_hermite_block_split_f64.hip, DESIGN.md K-HBS) divides the large block steps
+    over the ranks of a torch.distributed.ProcessGroup. Unlike the other `process_group=` simulators, which hold their own
+    rows, the state here is REPLICATED: positions, velocities, accelerations, jerks, masses and levels are the full arrays
+    on every rank, bit for bit the same, construction (first force, initial levels) runs redundantly on every rank, and
+    gather(), compute_energies(), compute_potentials(), compute_invariants() and run() (calc_invariants too) work unchanged
+    on every rank with no communication. A block step with at least `split_min_active` active bodies is divided: each
+    rank evaluates and corrects its slice of the index-ordered active list, one all_gather_into_tensor carries the
+    corrected rows (n_act of them, never n) and every rank applies all of them; smaller block steps run redundantly with
+    no collective. `split_min_active` (a keyword beside `dtype`; an int >= 1) is REQUIRED with a group and refused
+    without one: no exchange has been measured here, so there is no default, and a group without a threshold raises
+    ValueError as it did before this mode existed. `default_split_min_active(n, world)` = max(64 world, ceil(2^25 / n))
+    is a PROVISIONAL value to pass: it rests on a one-GPU measurement without transport. Counters: `split_block_steps` and `exchanged_rows` (sum of n_act over divided steps). The results are
+    the un-divided simulator's bit for bit wherever a slice and the whole block get the same slab count (every n <= 448;
+    always with one rank), and to rounding elsewhere. A one-rank group divides only with NBD_FORCE_SHARDED=1. step() raises
+    RuntimeError if the ranks' pieces ever disagree about t_next, n_act or the slices ("replicas diverged"). Anything that
+    is not a ProcessGroup, float32 with a group, a group without `split_min_active`, and a `split_min_active` without a
+    group or not an int >= 1 raise ValueError before a device is resolved."""
 
     def __init__(self, *, positions, velocities, masses, g_const: float = 1.0, softening: float = 0.1,
                  dt: float = 0.01, calc_energy: bool = True, device: str = None, process_group=None,
                  eta: float = 0.02, max_level: int = 10, calc_invariants: bool = False, **hermite_kw):
-        # hermite_kw: the keywords that are HermiteSimulator's own and mean here what they mean there -- `dtype`
-        # (default torch.float32). They go to HermiteSimulator.__init__ as given, which refuses a name it does not know.
-        self._refuse_process_group(process_group)
+        # hermite_kw: `split_min_active` (_BlockSteps; required with a group, refused without), taken out here, and the keywords that are
+        # HermiteSimulator's own and mean here what they mean there -- `dtype` (default torch.float32). Those go to
+        # HermiteSimulator.__init__ as given, which refuses a name it does not know.
+        split_min_active = hermite_kw.pop("split_min_active", None)
         self._check_dtype(hermite_kw.get("dtype", torch.float32), None)     # before anything is resolved or allocated
+        self._check_group(process_group, split_min_active, hermite_kw.get("dtype", torch.float32))
+        # the state is replicated: HermiteSimulator is built without the group, on all n bodies, on every rank
         super().__init__(positions=positions, velocities=velocities, masses=masses, g_const=g_const,
                          softening=softening, dt=dt, calc_energy=calc_energy, device=device,
                          calc_invariants=calc_invariants, **hermite_kw)
-        self._init_block(eta, max_level)
+        self._init_block(eta, max_level, process_group, split_min_active)
 
 
 class BlockHermite6Simulator(_BlockSteps, Hermite6Simulator):
@@ -1254,13 +1369,22 @@ class BlockHermite6Simulator(_BlockSteps, Hermite6Simulator):
     The public surface is BlockHermiteSimulator's: `eta`, `max_level`, `levels`, the cumulative counters `block_steps`,
     `pair_interactions` and `clamped`, `level_history`, MAX_LEVEL_LIMIT. `accelerations`, `jerks`, `snaps` and `crackles`
     are updated in place. Float64 only and eager-only (every block step reads {t_next, n_act} back to the host); there is
-    no range-sharded, captured or differentiable form; BatchedSimulator(integrator="block_hermite6") is the batched one.
+    no captured or differentiable form; BatchedSimulator(integrator="block_hermite6") is the batched one.
     With max_level=0 it is Hermite6Simulator bit for bit.
-    compute_*() and run() are that class's."""
+    compute_*() and run() are that class's.
+
+    `process_group` and `split_min_active` are BlockHermiteSimulator's (DESIGN.md K-HBS): the state (with `snaps` and
+    `crackles`) is REPLICATED on every rank -- not the rank's own rows, as in the other `process_group=` simulators -- so
+    gather(), compute_*() and run() work unchanged on every rank without communication; block steps with at least
+    `split_min_active` active bodies (required with a group; `default_split_min_active(n, world)` is a provisional value
+    to pass) are divided over the ranks, one
+    all_gather_into_tensor of the corrected rows each; `split_block_steps` and `exchanged_rows` count them. The same
+    refusals, each a ValueError before a device is resolved."""
 
     def __init__(self, *, positions, velocities, masses, g_const: float = 1.0, softening: float = 0.1,
                  dt: float = 0.01, calc_energy: bool = True, device: str = None, process_group=None,
-                 eta: float = 0.02, max_level: int = 10, calc_invariants: bool = False, **format_kw):
+                 eta: float = 0.02, max_level: int = 10, calc_invariants: bool = False,
+                 split_min_active: int = None, **format_kw):
         # all refusals before anything is resolved, allocated or launched; format_kw is Hermite6Simulator's (`dtype`)
         unknown = [k for k in format_kw if k != "dtype"]
         if unknown:
@@ -1269,11 +1393,12 @@ class BlockHermite6Simulator(_BlockSteps, Hermite6Simulator):
         if dtype is not torch.float64:
             raise ValueError(f"BlockHermite6Simulator: dtype must be torch.float64, got {dtype!r}: there is no fp32 form "
                              "of the 6th-order scheme")
-        self._refuse_process_group(process_group)
+        self._check_group(process_group, split_min_active, dtype)
+        # the state is replicated: Hermite6Simulator is built without the group, on all n bodies, on every rank
         super().__init__(positions=positions, velocities=velocities, masses=masses, g_const=g_const,
                          softening=softening, dt=dt, calc_energy=calc_energy, device=device,
                          calc_invariants=calc_invariants, **format_kw)
-        self._init_block(eta, max_level)
+        self._init_block(eta, max_level, process_group, split_min_active)
 
 
 def _per_scene(x, n_scenes: int, name: str) -> list:

@@ -339,6 +339,18 @@ SIGNATURES = {
                              [c_void_p] * 5 + [c_size_t, c_void_p]),
     "nbd_accel_jerk_snap_active_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_double, c_double,
                                                c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_void_p]),
+    # --- a block step divided over the ranks of a process group (csrc/direct_hermite_block_split_f64.hip)
+    "nbd_hblock_split_f64_workspace_bytes": (c_size_t, [c_int]),
+    "nbd_hblock6_split_f64_workspace_bytes": (c_size_t, [c_int]),
+    "nbd_hblock_order_list": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "nbd_hblock_split_rows_f64": (c_int, [c_void_p] * 5 + [c_int] * 5 + [c_double] * 4 + [c_void_p] * 5 +
+                                  [c_size_t, c_void_p]),
+    "nbd_hblock6_split_rows_f64": (c_int, [c_void_p] * 6 + [c_int] * 5 + [c_double] * 4 + [c_void_p] * 6 +
+                                   [c_size_t, c_void_p]),
+    "nbd_hblock_split_apply_f64": (c_int, [c_void_p, c_int, c_int, c_int] + [c_void_p] * 7 + [c_int, c_int] +
+                                   [c_void_p] * 3 + [c_size_t, c_void_p]),
+    "nbd_hblock6_split_apply_f64": (c_int, [c_void_p, c_int, c_int, c_int] + [c_void_p] * 9 + [c_int, c_int] +
+                                    [c_void_p] * 3 + [c_size_t, c_void_p]),
     # --- block-timestep Hermite per scene, 4th and 6th order (csrc/direct_batch_hermite_block_f64.hip)
     "nbd_batch_hblock_f64_plan": (c_int, [c_void_p, c_int, POINTER(c_int), POINTER(c_int), POINTER(c_size_t)]),
     "nbd_batch_hblock_f64_plan_fill": (c_int, [c_void_p, c_int, c_void_p, c_size_t]),

@@ -1115,6 +1115,90 @@ def accel_jerk_snap_active_f64(posd, veld, accd, n: int, act, softening_sq: floa
                               workspace, lambda dev, n_act: hblock6_workspace(n, dev, slabs, n_act), slabs)
 
 
+# ---------------- a block step divided over the ranks of a process group (csrc/direct_hermite_block_split_f64.hip)
+HBLOCK_SPLIT_ROW = 16           # NBD_HBLOCK_SPLIT_ROW: x1 v1 a1 j1, three spare doubles, {new level, clamped}
+HBLOCK6_SPLIT_ROW = 20          # NBD_HBLOCK6_SPLIT_ROW: x1 v1 a1 j1 s1 c1, one spare double, {new level, clamped}
+HBLOCK_SCHED_DIVERGED = 6       # the int of the schedule record a split apply raises when the pieces' headers disagree
+
+
+def hblock_split_slices(n_act: int, world: int) -> list:
+    """[(first, count)] * world: the slices of an ordered active list of n_act entries the ranks of a group evaluate.
+    Rank r takes [r q, min((r + 1) q, n_act)) with q = 64 ceil(ceil(n_act / world) / 64), so that no group of 64 targets
+    is cut; slices behind the list are (n_act, 0). q is formed here and nowhere else: hblock_split_q reads it off the
+    first slice."""
+    n_act, world = int(n_act), int(world)
+    if n_act < 1 or world < 1:
+        raise ValueError(f"hblock_split_slices: n_act={n_act} and world={world} must be at least 1")
+    q = 64 * -(-(-(-n_act // world)) // 64)
+    firsts = [min(r * q, n_act) for r in range(world + 1)]
+    return [(firsts[r], firsts[r + 1] - firsts[r]) for r in range(world)]
+
+
+def hblock_split_q(slices) -> int:
+    """The piece length q of hblock_split_slices(n_act, world): the first slice's count rounded up to a group of 64 (the
+    first slice is [0, min(q, n_act)))."""
+    return -(-slices[0][1] // 64) * 64
+
+
+def hblock_split_workspace(n: int, device, order: int = 4) -> torch.Tensor:
+    """The ordered list, the ordering's scratch and a slice's block workspace (nbd_hblock_split_f64_workspace_bytes, or
+    the hblock6 twin for order 6). Its head is a block workspace's: hblock_schedule and hblock*_step_f64 run on it too."""
+    entry = "nbd_hblock_split_f64_workspace_bytes" if order == 4 else "nbd_hblock6_split_f64_workspace_bytes"
+    return alloc_bytes(getattr(_lib.lib(), entry)(int(n)), device)
+
+
+def hblock_order_list(levels, max_level: int, sched, workspace) -> None:
+    """The list hblock_schedule has just written, in ascending body index (two launches, no readback)."""
+    n = levels.shape[0]
+    _chk_sched(n, None, levels, sched)
+    _lib.launch("nbd_hblock_order_list", levels.device, levels.data_ptr(), n, int(max_level), sched.data_ptr(),
+                workspace.data_ptr(), _nbytes(workspace))
+
+
+def hblock_split_rows(state, levels, n_act: int, first: int, count: int, max_level: int, dt: float, eta: float,
+                      softening_sq: float, g_const: float, sched, rows, rows_out, workspace) -> None:
+    """The header and the result rows of entries [first, first + count) of the ordered list into rows_out ((>= 1 + count,
+    row) float64), nothing of the state written. state = (pos, vel, acc, jerk) with rows = (posd, veld) for the 4th order,
+    (pos, vel, acc, jerk, snap) with (posd, veld, accd) for the 6th."""
+    n = state[0].shape[0]
+    six = len(rows) == 3
+    _chk_n3(F64, n, _HBLOCK_STATE, *state)
+    _chk_block_rows(F64, n, rows)
+    _chk_sched(n, None, levels, sched)
+    if len(state) != (5 if six else 4):
+        raise _lib.NbdError("hblock_split_rows: state is (pos, vel, acc, jerk) with two row arrays, or those and snap "
+                            "with three")
+    width = HBLOCK6_SPLIT_ROW if six else HBLOCK_SPLIT_ROW
+    if (rows_out.dtype != F64 or rows_out.dim() != 2 or rows_out.shape[1] != width or not rows_out.is_contiguous()
+            or rows_out.shape[0] < 1 + int(count) or rows_out.device != state[0].device):
+        raise _lib.NbdError(f"hblock_split_rows: rows_out must be a contiguous float64 (>= {1 + int(count)}, {width}) "
+                            "tensor on the state's device")
+    _lib.launch("nbd_hblock6_split_rows_f64" if six else "nbd_hblock_split_rows_f64", state[0].device, *_ptrs(state),
+                levels.data_ptr(), n, int(n_act), int(first), int(count), int(max_level), float(dt), float(eta),
+                float(softening_sq), float(g_const), sched.data_ptr(), *_ptrs(rows), rows_out.data_ptr(),
+                workspace.data_ptr(), _nbytes(workspace))
+
+
+def hblock_split_apply(rows_all, world: int, q: int, n_act: int, state, mass, ticks, levels, max_level: int, sched, posd,
+                       workspace) -> None:
+    """All n_act rows of rows_all (world pieces of 1 + q rows, contiguous) into state = (pos, vel, acc, jerk[, snap,
+    crackle]) with the block step's bookkeeping; posd = {x1, m} for them. A piece whose header disagrees with this
+    rank's record raises sched[HBLOCK_SCHED_DIVERGED]."""
+    n = _chk_hblock(F64, state, mass, ticks, levels, sched, (posd,))
+    six = len(state) == 6
+    width = HBLOCK6_SPLIT_ROW if six else HBLOCK_SPLIT_ROW
+    if len(state) not in (4, 6):
+        raise _lib.NbdError("hblock_split_apply: state is (pos, vel, acc, jerk) or those with snap and crackle")
+    if (rows_all.dtype != F64 or rows_all.dim() != 2 or rows_all.shape[1] != width or not rows_all.is_contiguous()
+            or rows_all.shape[0] < int(world) * (1 + int(q)) or rows_all.device != state[0].device):
+        raise _lib.NbdError(f"hblock_split_apply: rows_all must be a contiguous float64 (>= world (1 + q), {width}) "
+                            "tensor on the state's device")
+    _lib.launch("nbd_hblock6_split_apply_f64" if six else "nbd_hblock_split_apply_f64", state[0].device,
+                rows_all.data_ptr(), int(world), int(q), int(n_act), *_ptrs(state), mass.data_ptr(), ticks.data_ptr(),
+                levels.data_ptr(), n, int(max_level), sched.data_ptr(), posd.data_ptr(), workspace.data_ptr(),
+                _nbytes(workspace))
+
+
 # ---------------------------------------------------------------- batched direct integrator (csrc/direct_batch.hip)
 class BatchPlan:
     """The host offsets of an ensemble of scenes and the device work list built from them (nbd_batch_plan /

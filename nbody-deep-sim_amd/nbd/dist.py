@@ -77,6 +77,36 @@ class RowGather:
         return out
 
 
+class PieceExchange:
+    """The exchange of a block step divided over the ranks (BlockHermiteSimulator / BlockHermite6Simulator with a
+    process_group): every rank's piece of 1 + q result rows (a header row, then q rows; `cols` float64 each) into one
+    buffer of world pieces, rank after rank. Both buffers are allocated here, once, for q up to q_max: `send` (1 + q_max
+    rows; the rank writes its piece into send[:1 + q]) and a receive buffer of world (1 + q_max) rows.
+
+    `exchange(q)` is ONE all_gather_into_tensor of send[:1 + q] into the first world (1 + q) rows of the receive buffer,
+    which it returns; equal pieces, blocking on the current stream (the apply launch that follows needs every row). A
+    one-rank group that is not forced through the collective (`collective=False`) copies on the device instead."""
+
+    def __init__(self, world_size: int, q_max: int, cols: int, device, group=None, collective: bool = False,
+                 dtype=torch.float64):
+        if world_size < 1 or q_max < 1:
+            raise ValueError(f"bad exchange world_size={world_size} q_max={q_max}")
+        self.world_size, self.q_max, self.group = int(world_size), int(q_max), group
+        self.collective = collective or self.world_size > 1
+        self.send = torch.zeros((1 + self.q_max, cols), dtype=dtype, device=device)
+        self.recv = torch.zeros((self.world_size * (1 + self.q_max), cols), dtype=dtype, device=device)
+
+    def exchange(self, q: int) -> torch.Tensor:
+        if not 1 <= q <= self.q_max:
+            raise ValueError(f"piece length {q} outside [1, {self.q_max}]")
+        out = self.recv[:self.world_size * (1 + q)]
+        if not self.collective:
+            out.copy_(self.send[:1 + q])
+        else:
+            dist.all_gather_into_tensor(out, self.send[:1 + q], group=self.group)
+        return out
+
+
 def allgather_rows(local: torch.Tensor, part: RangePartition, out: torch.Tensor, group=None) -> torch.Tensor:
     """Blocking form for occasional use (state gathers for output, energies): allocates per call."""
     if local.shape[0] != part.n_local:
