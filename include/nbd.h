@@ -355,7 +355,7 @@ int nbd_batch_invariants_state_f64(const int* offsets, int n_scenes, const void*
                                    const double* pos, const double* vel, const double* mass, const double* phi,
                                    double* out_rows, nbd_stream_t stream);
 
-/* ---- 6th-order Hermite per scene (csrc/direct_batch_hermite6_f64.hip): "6th-order Hermite" below applied to every scene
+/* ---- 6th-order Hermite per scene (csrc/direct_batch_hermite_f64.hip): "6th-order Hermite" below applied to every scene
  * of a batch, one set of launches for all scenes. A scene's pos / vel / acc / jerk / snap / crackle are bit-identical to
  * the nbd_*hermite6* / nbd_accel_jerk_snap_f64 entries on that scene alone with the same parameters, wherever it stands
  * in the batch.
@@ -498,7 +498,7 @@ int nbd_potential_f64(const double* posd, int n, double softening_sq, double g_c
 int nbd_invariants_state_f64(const double* pos, const double* vel, const double* mass, const double* phi, int n,
                              double* out_row, nbd_stream_t stream);
 
-/* ---- 6th-order Hermite (csrc/direct_hermite6_f64.hip): the shared-timestep 6th-order Hermite step (Nitadori & Makino
+/* ---- 6th-order Hermite (csrc/direct_hermite_f64.hip): the shared-timestep 6th-order Hermite step (Nitadori & Makino
  * 2008) in the number format of "double-precision Hermite" above -- fp64 state, scalars, pair arithmetic and sums; there
  * is no fp32 form. The force evaluation carries the snap s = d^2 a / dt^2 and streams a third array of packed rows,
  *   accd : double[nbd_posm_padded_len(n)][4] = {ax, ay, az, 0}, 32-byte aligned, zero rows behind n, as veld.

@@ -53,10 +53,10 @@
 #include "direct_batch_plan.h"
 #include "direct_kernels.h"
 #include "hermite6_f64_kernels.h"
-#include "hermite_block_f64_kernels.h"
 #include "hermite_block_kernels.h"
 #include "hermite_f64_kernels.h"
 #include "hermite_kernels.h"
+#include "hermite_orders_f64.h"
 
 namespace {
 
@@ -287,7 +287,7 @@ __global__ __launch_bounds__(64 * kWaves, Order::kMinWG) void batch_active_force
   const Group64<int> g(w.grp / slabs, w.grp % slabs, n_act);
   const ChunkRange c = wave_chunks_of(g.jw(), w.n_chunks, slabs);
   const int i = act[(size_t)w.sc.off + g.row()];
-  Pair pr = Order::make(pd, vd, ad, i, eps2, w.n);
+  Pair pr = Order::make(pd, vd, ad, i, i, eps2, w.n);
   walk_f64(pr, pd, vd, c.begin, c.end, eps2 < kEps2MaskedF64, -1, lds, g.dst<Pair>(ws + (size_t)w.ws_off), (size_t)n_act,
            g.n_valid(), nullptr, ad);
 }

@@ -2,8 +2,8 @@
 // what a kernel reads from it (load_item: one workgroup per item; load_row: one thread per packed row) and the host
 // checks every batched entry point makes before it launches. Shared by direct_batch.hip (leapfrog, Euler, energies),
 // direct_diag.hip (the batched diagnostics), direct_batch_hermite.hip (Hermite), direct_batch_hermite_f64.hip (Hermite in
-// double precision), direct_batch_hermite6_f64.hip (6th-order Hermite) and direct_batch_hermite_block_f64.hip (block
-// timesteps per scene: the same layout with a static work list, a geometry of its own). The two shared-timestep float64 units fill the same layout
+// double precision, 4th and 6th order) and direct_batch_hermite_block_f64.hip (block
+// timesteps per scene: the same layout with a static work list, a geometry of its own). The shared-timestep float64 unit fills the same layout
 // with another geometry per scene (SceneGeom below); the host shell of such a plan counted in doubles -- totals, plan
 // fill, workspace size and checks, for kOut doubles per body and slab -- is here once, at the end. The definitions sit in
 // an anonymous namespace: every translation unit that includes this file gets its own copies.
@@ -216,7 +216,7 @@ inline int batch_prologue(const int* offsets, int n_scenes, const void* plan, si
   return batch_prologue(offsets, n_scenes, plan, plan_bytes, t, scene_geom_f32);
 }
 
-// ---- the plans counted in doubles (direct_batch_hermite_f64.hip: kOut = 6; direct_batch_hermite6_f64.hip: kOut = 9): the
+// ---- the plans counted in doubles (direct_batch_hermite_f64.hip: kOut = 6 at the 4th order, 9 at the 6th): the
 // layout and the checks above with plan_f64's geometry -- one item per (scene, group of 64 targets, slab), the one-system
 // float64 launch for the scene's size. The scene's slabs are double[slabs][kOut][n], counted in DOUBLES
 // (BatchTotals::ws_floats, SceneRec::ws_off); no energy partials. The items, rows and bytes of the plan do not depend on

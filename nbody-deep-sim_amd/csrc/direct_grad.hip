@@ -239,7 +239,7 @@ struct AccelVjpPair {
   __device__ __forceinline__ double out(int k) const { return k < 3 ? acc[k] - 3.0 * acc[k + 3] : acc[6]; }
 };
 
-// accel_jerk_f64_kernel's geometry (direct_hermite_f64.hip): grid = (groups of 64 targets, slabs). out: double[slab][4][n].
+// force_f64_kernel's geometry (direct_hermite_f64.hip): grid = (groups of 64 targets, slabs). out: double[slab][4][n].
 __global__ __launch_bounds__(64 * kWaves) void accel_vjp_f64_kernel(const d4* __restrict__ posd,
                                                                     const d4* __restrict__ cotd, int n, int cpw_q,
                                                                     int cpw_r, double eps2, int all_masked,

@@ -1,6 +1,6 @@
 // direct_hermite_block_f64.hip -- block-timestep Hermite integration in float64 for gfx950 (MI355X): the 4th order (the
 // double-precision form of direct_hermite_block.hip, in the number format of direct_hermite_f64.hip) and the 6th order
-// (the scheme of direct_hermite6_f64.hip, Nitadori & Makino 2008, on the same individual power-of-two steps). An
+// (the scheme of direct_hermite_f64.hip's 6th order, Nitadori & Makino 2008, on the same individual power-of-two steps). An
 // extension. C-ABI: the nbd_hblock_*_f64 / nbd_accel_jerk_active_f64 and the nbd_hblock6_*_f64 /
 // nbd_accel_jerk_snap_active_f64 entries of include/nbd.h; Python: galaxify.simulation.BlockHermiteSimulator(
 // dtype=torch.float64) and BlockHermite6Simulator.
@@ -17,7 +17,7 @@
 //              gathered through the list, the same walk_f64 and pair functor
 //   correct  : the slabs in slab order, the corrector with the body's own h_i, the criterion for the new level,
 //              t_i = t_next (0 at the end of the interval), posd = {x1, m}
-// What the orders differ in (Order4, Order6 of hermite_block_f64_kernels.h; the O(N) kernels and the pointer lists of the entries):
+// What the orders differ in (Order4, Order6 of hermite_orders_f64.h; the O(N) kernels and the pointer lists of the entries):
 //         state         packed rows (d4)        sums: kOut   predict, correct
 //   4th : x v a j       {x_p, m}, {v_p, 0}      a, j: 6      hblock_predict_kernel<double>, hblock_correct_kernel<double>:
 //                                                            hermite_block_kernels.h's templates, the fp32 unit's source
@@ -36,9 +36,9 @@
 // either sign leaves its bits alone: with every body listed the sums are the shared step's, bit for bit, in whatever
 // order the list holds them.
 // Resources (hipcc --offload-arch=gfx950 -O3, -Rpass-analysis=kernel-resource-usage). active_force_f64_kernel<Order4>: 90
-// VGPRs, 32 KiB of LDS: 5 workgroups per CU, what the LDS allows and what accel_jerk_f64_kernel reaches at 89 VGPRs (left
+// VGPRs, 32 KiB of LDS: 5 workgroups per CU, what the LDS allows and what force_f64_kernel<Order4> reaches at 89 VGPRs (left
 // alone the compiler takes 116 here, one wave per SIMD fewer: kMinWG = 5). <Order6>: 164 VGPRs, 0 AGPRs, 48 KiB of LDS, 3
-// waves per SIMD: three workgroups per CU by the LDS and by the registers alike, accel_jerk_snap_f64_kernel's figures,
+// waves per SIMD: three workgroups per CU by the LDS and by the registers alike, force_f64_kernel<Order6>'s figures,
 // which the compiler reaches unasked (kMinWG = 1). hblock6_predict_kernel: 50 VGPRs; hblock6_correct_kernel: 98. No SGPR
 // or VGPR spills and no scratch anywhere.
 // No float atomics (the clamp counter and the histogram are integer atomics), no memsets in a step; the host reads
@@ -51,10 +51,10 @@
 #include "../../include/nbd.h"
 #include "direct_kernels.h"
 #include "hermite6_f64_kernels.h"
-#include "hermite_block_f64_kernels.h"
 #include "hermite_block_kernels.h"
 #include "hermite_f64_kernels.h"
 #include "hermite_kernels.h"
+#include "hermite_orders_f64.h"
 
 namespace {
 
@@ -72,7 +72,7 @@ __global__ __launch_bounds__(64 * kWaves, Order::kMinWG) void active_force_f64_k
   const Group64<unsigned> g(blockIdx.x, blockIdx.y, n_act);      // a group of list entries: the lane's body is act[its entry]
   const ChunkRange c = wave_chunks(g.jw(), cpw_q, cpw_r);
   const int i = act[g.row()];
-  Pair pr = Order::make(posd, veld, accd, i, eps2, n);
+  Pair pr = Order::make(posd, veld, accd, i, i, eps2, n);
   walk_f64(pr, posd, veld, c.begin, c.end, all_masked != 0, -1, lds, g.dst<Pair>(out), (size_t)n_act, g.n_valid(),
            nullptr, Order::kArr == 3 ? accd : nullptr);
 }
@@ -156,13 +156,6 @@ int* ws_act(void* ws) { return static_cast<int*>(ws); }
 double* ws_slabs(void* ws, int n) { return reinterpret_cast<double*>(static_cast<char*>(ws) + act_bytes(n)); }
 
 inline bool bad_workspace(const void* ws, size_t have, size_t need) { return !ws || misaligned32(ws) || have < need; }
-
-// the packed source arrays of an order (accd is looked at by the 6th only)
-template <class Order>
-bool bad_rows(const double* posd, const double* veld, const double* accd) {
-  return !posd || !veld || misaligned32(posd) || misaligned32(veld) ||
-         (Order::kArr == 3 && (!accd || misaligned32(accd)));
-}
 
 template <class Order>
 int launch_active(const double* posd, const double* veld, const double* accd, int n, const int* act, int n_act,

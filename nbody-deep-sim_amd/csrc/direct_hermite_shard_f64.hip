@@ -1,6 +1,6 @@
 // direct_hermite_shard_f64.hip -- the double-precision range-sharded Hermite steps, 4th order (the form of
 // direct_hermite_shard.hip's step in the number format of direct_hermite_f64.hip) and 6th order (the sharded form of
-// direct_hermite6_f64.hip's step): one rank of a torch.distributed group owns the bodies [lo, lo + n_local) of n_total and
+// direct_hermite_f64.hip's 6th-order step): one rank of a torch.distributed group owns the bodies [lo, lo + n_local) of n_total and
 // needs every other rank's PREDICTED rows per step. C-ABI: the nbd_hermite_shard_*_f64 and nbd_hermite6_shard_* entries of
 // include/nbd.h; Python: galaxify.simulation.HermiteSimulator(dtype=torch.float64, process_group=...) and
 // Hermite6Simulator(process_group=...).
@@ -17,7 +17,7 @@
 //             mask (excluded_view, direct_kernels.h)
 //   finish  : slab_order_sum over the local slabs, then the remote ones, times G, and the corrector of the own rows (or
 //             the force on its own)
-// What the orders differ in (Order4, Order6 below; the row kernels and the pointer lists of the entries):
+// What the orders differ in (Order4, Order6 of hermite_orders_f64.h; the row kernels and the pointer lists of the entries):
 //             row, 8-byte doubles                         sums per body   predictor              finish
 //   4th : {x_p, m | v_p, 0}, 8                            a, j: 6         hermite_predict_row    hermite_correct_row
 //   6th : {x_p, m | v_p, 0 | a_p, 0}, 12                  a, j, s: 9      hermite6_predict_row   hermite6_finish_row: the
@@ -35,26 +35,9 @@
 #include "hermite6_f64_kernels.h"
 #include "hermite_f64_kernels.h"
 #include "hermite_kernels.h"
+#include "hermite_orders_f64.h"
 
 namespace {
-
-// An order: its pair functor, the d4 pieces of an exchanged row (= the arrays the functor streams) and the functor of the
-// target whose row starts at `row`.
-struct Order4 {
-  using Pair = AccelJerkPair;
-  static constexpr int kArr = 2;                   // {x_p, m}, {v_p, 0}
-  static __device__ __forceinline__ Pair make(const d4* __restrict__ row, double eps2, int i, int n) {
-    return Pair(row[0], row[1], eps2, i, n);
-  }
-};
-
-struct Order6 {
-  using Pair = AccelJerkSnapPair;
-  static constexpr int kArr = 3;                   // {x_p, m}, {v_p, 0}, {a_p, 0}
-  static __device__ __forceinline__ Pair make(const d4* __restrict__ row, double eps2, int i, int n) {
-    return Pair(row[0], row[1], row[2], eps2, i, n);
-  }
-};
 
 // The partial sums (Pair::kOut per target) of the targets tgt[0 .. n_tgt) (exchanged rows; global index tgt_off + row)
 // under the sources of the view sv on src (exchanged rows): the un-sharded pair kernel's geometry -- grid = (target groups
@@ -71,7 +54,7 @@ __global__ __launch_bounds__(64 * kWaves) void shard_pair_f64_kernel(const d4* _
   __shared__ __attribute__((aligned(32))) f4 lds[kWaves * stage_quads_n<kArr>()];
   const Group64<unsigned> g(blockIdx.x, blockIdx.y, n_tgt);
   const ChunkRange c = wave_chunks(g.jw(), sv.cpw_q, sv.cpw_r);
-  Pair pr = Order::make(tgt + (size_t)g.row() * kArr, eps2, tgt_off + g.i, sv.n_src);
+  Pair pr = Order::make(tgt, tgt + 1, tgt + 2, (size_t)g.row() * kArr, tgt_off + g.i, eps2, sv.n_src);
   walk_f64<Pair, kArr * kRowQuads, RANGE>(pr, src, src + 1, c.begin, c.end, all_masked != 0,
                                           RANGE ? -1 : (int)blockIdx.x, lds, g.dst<Pair>(out), (size_t)n_tgt,
                                           g.n_valid(), &sv, kArr == 3 ? src + 2 : nullptr);

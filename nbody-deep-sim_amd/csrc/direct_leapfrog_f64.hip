@@ -31,8 +31,8 @@
 
 namespace {
 
-// The acceleration of all n bodies under all n bodies: accel_jerk_f64_kernel's geometry -- grid = (groups of 64 targets,
-// slabs), the n_chunks source chunks spread over all slabs x 4 waves to within one. out: double[slab][3][n].
+// The acceleration of all n bodies under all n bodies: force_f64_kernel's geometry (direct_hermite_f64.hip) -- grid =
+// (groups of 64 targets, slabs), the n_chunks source chunks spread over all slabs x 4 waves to within one. out: double[slab][3][n].
 __global__ __launch_bounds__(64 * kWaves) void accel_f64_kernel(const d4* __restrict__ posd, int n, int cpw_q, int cpw_r,
                                                                 double eps2, int all_masked, double* __restrict__ out) {
   __shared__ __attribute__((aligned(32))) f4 lds[kWaves * stage_quads<false>()];

@@ -1,5 +1,5 @@
-// hermite6_f64_kernels.h -- what the 6th-order Hermite translation units share (direct_hermite6_f64.hip: one system;
-// direct_batch_hermite6_f64.hip: many independent systems, shared timestep per system; direct_hermite_shard_f64.hip: one
+// hermite6_f64_kernels.h -- what the 6th-order Hermite translation units share (direct_hermite_f64.hip: one system;
+// direct_batch_hermite_f64.hip: many independent systems, shared timestep per system; direct_hermite_shard_f64.hip: one
 // rank's bodies of a range partition, beside the 4th order; direct_hermite_block_f64.hip: an active list of targets,
 // block timesteps, each body with its own step constants): the pair functor of the
 // acceleration + jerk + snap evaluation (AccelJerkSnapPair), the step constants (Hermite6Step, hermite6_step_constants)

@@ -3,8 +3,7 @@
 // direct_batch_hermite_block_f64.hip: the active lists of every scene of a batch;
 // direct_hermite_shard_f64.hip: one rank's bodies of a range partition, 4th and 6th order;
 // direct_batch_hermite_f64.hip: many independent systems, shared timestep per system, and their diagnostics;
-// direct_leapfrog_f64.hip: the acceleration alone, for the leapfrog and Euler steps; direct_hermite6_f64.hip and
-// direct_batch_hermite6_f64.hip: the 6th order, with hermite6_f64_kernels.h; direct_grad.hip and direct_hermite_grad.hip: the float64 backward kernels): the reciprocal
+// direct_leapfrog_f64.hip: the acceleration alone, for the leapfrog and Euler steps; direct_grad.hip and direct_hermite_grad.hip: the float64 backward kernels): the reciprocal
 // square root (rsqrt_f64), the pair functors (AccelJerkPair: acceleration plus jerk; AccelPair: its acceleration alone;
 // PotentialPair, EnergyPair: the diagnostics), the finishing sums of the diagnostics (potential_finish_f64,
 // energy_finish_f64, F64State), the wave body that walks the source chunks with a functor (walk_f64), the prologue of a

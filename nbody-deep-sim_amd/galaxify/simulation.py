@@ -447,7 +447,7 @@ class _Float64:
 
 class _Hermite6Float64(_Float64):
     """The number format of Hermite6Simulator: `_Float64` with the calls that differ for the 6th order
-    (csrc/direct_hermite6_f64.hip; sharded, the 6th-order entries of csrc/direct_hermite_shard_f64.hip). Un-sharded, a
+    (csrc/direct_hermite_f64.hip; sharded, the 6th-order entries of csrc/direct_hermite_shard_f64.hip). Un-sharded, a
     third source array `s._accd` = {ax, ay, az, 0} and one workspace for every entry: 9 doubles per body and slab, where
     the inherited force and the diagnostics need at most 6. Sharded, 12-double rows {x_p, m, v_p, 0, a_p, 0}, 9 doubles per
     body and slab, the snap as a third output and the crackle as the fourth of a step."""
@@ -1058,7 +1058,7 @@ class HermiteSimulator(BaseSimulator):
 
 class Hermite6Simulator(HermiteSimulator):
     """Shared-timestep 6th-order Hermite predictor-corrector (Nitadori & Makino 2008) in float64
-    (csrc/direct_hermite6_f64.hip), an extension the reference does not have. The force evaluation carries
+    (csrc/direct_hermite_f64.hip), an extension the reference does not have. The force evaluation carries
     one more derivative than HermiteSimulator's, the snap s = d^2 a / dt^2, and still runs once per step. With a0, j0, s0
     and the crackle c0 = d^3 a / dt^3 carried from the previous step:
         predict  x_p = x + v dt + a0 dt^2/2 + j0 dt^3/6 + s0 dt^4/24 + c0 dt^5/120
@@ -1583,7 +1583,7 @@ class _BatchFloat64(_BatchFormat):
 
 
 class _BatchHermite6(_BatchFloat64):
-    """The float64 format of BatchedSimulator(integrator="hermite6") (csrc/direct_batch_hermite6_f64.hip): `_BatchFloat64`
+    """The float64 format of BatchedSimulator(integrator="hermite6") (csrc/direct_batch_hermite_f64.hip): `_BatchFloat64`
     with the 9-row plan and its workspace, the third packed array `s._accd` = {ax, ay, az, 0} and the taller parameter
     table (direct.batch_h6_params: G, eps^2, eps, then Hermite6Step's constants). The carried arrays are
     (accelerations, jerks, snaps, crackles). The inherited pack, acceleration + jerk, energies, potentials and invariants
@@ -1760,7 +1760,7 @@ class BatchedSimulator(_ChunkedRun):
     HermiteSimulator(dtype=torch.float64) of that scene alone. Because the table, not a kernel argument, carries the
     scalars, run() captures its chunks in this mode too. The default stays float32 and takes the paths it took.
 
-    integrator="hermite6" (csrc/direct_batch_hermite6_f64.hip) is Hermite6Simulator's 6th-order step on
+    integrator="hermite6" (csrc/direct_batch_hermite_f64.hip) is Hermite6Simulator's 6th-order step on
     every scene, float64 only (`dtype` then defaults to torch.float64; torch.float32 is refused): `accelerations`,
     `jerks`, `snaps` and `crackles` are (N_total, 3) float64 tensors rebound by step(), built as Hermite6Simulator builds
     them (the acceleration first, then the evaluation with it as the third source array, crackle 0), and each scene's

@@ -224,7 +224,7 @@ SIGNATURES = {
                                         c_size_t, c_void_p]),
     "nbd_batch_invariants_state_f64": (c_int, [c_void_p, c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p,
                                                c_void_p, c_void_p, c_void_p]),
-    # --- 6th-order Hermite per scene (csrc/direct_batch_hermite6_f64.hip)
+    # --- 6th-order Hermite per scene (csrc/direct_batch_hermite_f64.hip)
     "nbd_batch_hermite6_f64_plan_fill": (c_int, [c_void_p, c_int, c_void_p, c_size_t]),
     "nbd_batch_hermite6_f64_workspace_bytes": (c_int, [c_void_p, c_int, POINTER(c_size_t)]),
     "nbd_batch_hermite6_pack_f64": (c_int, [c_void_p, c_int, c_void_p, c_size_t] + [c_void_p] * 7 + [c_void_p]),
@@ -262,7 +262,7 @@ SIGNATURES = {
     "nbd_energy_f64": (c_int, [c_void_p, c_void_p, c_int, c_double, c_double, c_void_p, c_void_p, c_size_t, c_void_p]),
     "nbd_potential_f64": (c_int, [c_void_p, c_int, c_double, c_double, c_void_p, c_void_p, c_size_t, c_void_p]),
     "nbd_invariants_state_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
-    # --- 6th-order Hermite, float64 (csrc/direct_hermite6_f64.hip)
+    # --- 6th-order Hermite, float64 (csrc/direct_hermite_f64.hip)
     "nbd_hermite6_f64_workspace_bytes": (c_size_t, [c_int]),
     "nbd_hermite6_f64_pack": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
                                       c_double, c_void_p, c_void_p, c_void_p, c_void_p]),

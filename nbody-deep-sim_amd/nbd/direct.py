@@ -549,7 +549,7 @@ def invariants_state_f64(pos, vel, mass, phi, out=None) -> torch.Tensor:
     return out
 
 
-# ---------------------------------------------------------- 6th-order Hermite, float64 (csrc/direct_hermite6_f64.hip)
+# ---------------------------------------------------------- 6th-order Hermite, float64 (csrc/direct_hermite_f64.hip)
 def _chk_accd(accd, n: int):
     """The third packed array {ax, ay, az, 0}: laid out like veld."""
     _chk(accd, (padded_len(n), 4), "accd", F64)
@@ -1462,7 +1462,7 @@ def batch_invariants_state_f64(plan: BatchPlan, pos, vel, mass, phi, out_rows) -
     return out_rows
 
 
-# ------------------------------------------------- 6th-order Hermite per scene (csrc/direct_batch_hermite6_f64.hip)
+# ------------------------------------------------- 6th-order Hermite per scene (csrc/direct_batch_hermite_f64.hip)
 def batch_h6_params(g, eps, dt) -> list:
     """The rows of the 6th-order calls' parameter table from each scene's Python doubles (g, eps, dt: S floats each):
     batch_f64_params' first three rows, then hermite6_step_constants' expressions (dt2 = dt * dt, dt3 = dt2 * dt).

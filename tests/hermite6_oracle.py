@@ -1,5 +1,5 @@
 """fp64 numpy restatement of the 6th-order Hermite integrator (Nitadori & Makino 2008) that Hermite6Simulator runs in
-float64 (csrc/direct_hermite6_f64.hip), row-blocked like hermite_oracle.
+float64 (csrc/direct_hermite_f64.hip), row-blocked like hermite_oracle.
 
 Pair terms for target i and source j, with r = x_j - x_i, v = v_j - v_i, a = a_j - a_i, s = (|r|^2 + eps^2)^(-1/2):
     w = m_j s^3,  alpha = (r.v) s^2,  gamma = (v.v + r.a) s^2

@@ -1,4 +1,4 @@
-"""BatchedSimulator(integrator="hermite6") on the MI355X (csrc/direct_batch_hermite6_f64.hip): every scene is bit-identical
+"""BatchedSimulator(integrator="hermite6") on the MI355X (csrc/direct_batch_hermite_f64.hip): every scene is bit-identical
 to a Hermite6Simulator of that scene alone -- construction, steps, captured run(), energies, invariants -- whatever its
 companions and its place in the batch; the batch against the fp64 oracle of tests/hermite6_oracle.py, independently of
 the one-system path; a two-body orbit through a captured run(); the existing modes untouched.

@@ -233,7 +233,7 @@ def _resources(asm, name):
 
 
 def test_evaluate_kernel_has_no_spills_no_scratch_and_the_32_kib_stage(asm):
-    name = _name(asm, "batch_accel_jerk_f64_kernel")
+    name = _name(asm, "batch_force_f64_kernelINS_6Order4E")     # the mangled name carries the order
     r = _resources(asm, name)
     assert r["vgpr_spill_count"] == 0 and r["private_segment_fixed_size"] == 0, r
     assert r["lds"] == 32768 and r["vgpr_count"] <= 96, r       # 5 workgroups of 4 waves per CU

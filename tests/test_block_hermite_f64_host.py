@@ -157,9 +157,9 @@ def test_new_kernels_have_no_scratch_and_no_spills(asm, kernel):
         desc = asm[asm.index(".amdhsa_kernel " + name):]
         assert int(re.search(r"\.amdhsa_group_segment_fixed_size\s+(\d+)", desc).group(1)) == LDS[kernel]
     if kernel == FORCE6:
-        assert num(r"\.vgpr_count") <= 168              # 3 workgroups per CU (48 KiB of LDS each), as accel_jerk_snap_f64_kernel
+        assert num(r"\.vgpr_count") <= 168              # 3 workgroups per CU (48 KiB of LDS each), as force_f64_kernel<Order6>
     if kernel == FORCE4:
-        assert num(r"\.vgpr_count") <= 96               # 5 workgroups per CU (32 KiB of LDS each), as accel_jerk_f64_kernel
+        assert num(r"\.vgpr_count") <= 96               # 5 workgroups per CU (32 KiB of LDS each), as force_f64_kernel<Order4>
         body = asm[asm.index(name + ":"):]
         body = body[:body.index(".Lfunc_end")]
         assert "global_load_lds_dwordx4" in body and "v_rsq_f64" in body
@@ -180,6 +180,14 @@ def test_no_float_atomics_and_one_copy_of_the_wave_body(asm):
     for what in ("PosVel3<T> hermite_predict_row(", "Corrected<T> hermite_correct_row(", "void slab_order_sum(",
                  "void hermite_predict_kernel(", "void hermite_correct_kernel(", "struct HermiteFmt<double>"):
         assert [f for f, text in units.items() if what in text] == ["hermite_kernels.h"], what
+    # the two orders as types and the check of an order's packed arrays: the order header's, for every float64 unit
+    for what in ("struct Order4", "struct Order6", "bool bad_rows("):
+        assert [f for f, text in units.items() if what in text] == ["hermite_orders_f64.h"], what
+    # the shared-step batched unit states its parameter rows once, for both orders (the block-timestep batched unit has
+    # a table of its own, NBD_BATCH_HBLOCK_PARAM_ROWS)
+    assert units["direct_batch_hermite_f64.hip"].count("enum ParamRow") == 1
+    assert sorted(f for f, text in units.items() if "enum ParamRow" in text) == [
+        "direct_batch_hermite_block_f64.hip", "direct_batch_hermite_f64.hip"]
     for f in ("direct_hermite_f64.hip", "direct_hermite_block_f64.hip"):      # no slab loop written out in an fp64 unit
         assert "+= slabs[" not in units[f], f
     # one float64 block unit for both orders, and one copy of its workspace arithmetic and of the force launch: each is

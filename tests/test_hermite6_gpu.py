@@ -1,4 +1,4 @@
-"""Hermite6Simulator on the GPU (csrc/direct_hermite6_f64.hip) against the fp64 oracle of tests/hermite6_oracle.py.
+"""Hermite6Simulator on the GPU (csrc/direct_hermite_f64.hip) against the fp64 oracle of tests/hermite6_oracle.py.
 
 The acceleration and the jerk of the three-array evaluation are held to the BITS of direct.accel_jerk_f64 on the same
 packed rows at the same slab count (that entry has its own accuracy tests); the snap to the accuracy bar of

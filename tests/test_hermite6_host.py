@@ -18,7 +18,8 @@ import hermite_oracle as ho
 from conftest import ROOT
 from nbd import _lib
 
-SRC = os.path.join(ROOT, "nbody-deep-sim_amd", "csrc", "direct_hermite6_f64.hip")
+SRC = os.path.join(ROOT, "nbody-deep-sim_amd", "csrc", "direct_hermite_f64.hip")       # both orders' unit
+FORCE6 = "force_f64_kernelINS_6Order6E"                  # the mangled name carries the order
 FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-ffp-contract=off", "--cuda-device-only", "-S"]
 ENTRIES = ("nbd_hermite6_f64_workspace_bytes", "nbd_hermite6_f64_pack", "nbd_accel_jerk_snap_f64",
            "nbd_hermite6_step_f64")
@@ -192,12 +193,12 @@ def test_argument_checks_without_a_gpu():
 
 @pytest.fixture(scope="module")
 def asm(tmp_path_factory):
-    out = str(tmp_path_factory.mktemp("isa") / "direct_hermite6_f64.s")
+    out = str(tmp_path_factory.mktemp("isa") / "direct_hermite_f64.s")
     subprocess.run(["/opt/rocm/bin/hipcc", *FLAGS, "-o", out, SRC], check=True, capture_output=True)
     return open(out).read()
 
 
-@pytest.mark.parametrize("kernel", ["accel_jerk_snap_f64_kernel", "hermite6_predict_kernel", "hermite6_finish_kernel"])
+@pytest.mark.parametrize("kernel", [FORCE6, "hermite6_predict_kernel", "hermite6_finish_kernel"])
 def test_kernels_have_no_scratch_and_keep_their_occupancy(asm, kernel):
     """No scratch and no spills anywhere. The pair kernel holds 4 x stage_quads_n<3>() = 48 KiB of LDS, three workgroups
     (12 waves) per CU, which 168 VGPRs still allow; it streams by LDS-DMA and has no fp32 intermediate."""
@@ -214,7 +215,7 @@ def test_kernels_have_no_scratch_and_keep_their_occupancy(asm, kernel):
     body = body[:body.index(".Lfunc_end")]
     assert "v_cvt_f32_f64" not in body and "v_rsq_f32" not in body
     assert not re.search(r"\b(global|flat|ds|buffer)_atomic", body)
-    if kernel == "accel_jerk_snap_f64_kernel":
+    if kernel == FORCE6:
         assert lds == 48 * 1024
         assert num("vgpr_count") <= 168
         assert "global_load_lds_dwordx4" in body and "v_rsq_f64" in body and "vmcnt(6)" in body
