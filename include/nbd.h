@@ -1508,6 +1508,35 @@ int64_t nbd_csv_format_state(char* out, size_t cap, const char* prefix, size_t p
                              const int32_t* mass_off, const float* pos, const float* vel, const float* acc, int n,
                              const char* suffix, size_t suffix_len);
 
+/* ------------------------------------------------------------ tree-code gravity (csrc/tree_force.hip)
+ * The force of nbd_accel_f32 (targets = sources, fp32) in O(N log N): bodies are ordered by the Morton key of their
+ * position (21 bits per axis on the bounding cube of all bodies, stable radix sort: equal keys stay in index order) and
+ * the hierarchy is implicit over that order: a level-L node holds the sorted bodies [i 8^(L+1), min(n, (i+1) 8^(L+1))),
+ * so level 0 has ceil(n/8) nodes of up to 8 bodies and every level above groups 8 consecutive nodes until one is left.
+ * A node carries its mass M, centre of mass c, traceless quadrupole Q = sum m (3 d d^T - |d|^2 I) about c and the size
+ * s = longest edge of the AABB of its bodies + max-norm of (c - AABB centre); sums in fp64, stored fp32; a node without
+ * mass takes c = the mean of its bodies. Targets are walked in groups of 64 consecutive sorted bodies with AABB T; with
+ * d the distance from c to T (0 inside), a node is accepted when theta > 0 and s < theta d, else opened into its
+ * children, a level-0 node summed body by body (j == i excluded by index, as nbd_accel_f32 does at softening 0). An
+ * accepted node adds, with r = c - x_i and u = (|r|^2 + softening_sq)^(-1/2),
+ *     M r u^3 - (Q r) u^5 + 2.5 (r^T Q r) r u^7        (the Q terms only when quadrupole != 0),
+ * and g_const multiplies the finished sum. theta = 0 is the direct sum in tree order.
+ *   nbd_tree_plan             host: levels and nodes over all levels for n bodies (0, 0 for n = 0); n > 2^24 is
+ *                             NBD_E_UNSUPPORTED (every entry below refuses it the same way)
+ *   nbd_tree_workspace_bytes  bytes of the workspace (the radix sort's scratch included; 0 for n <= 0 or n > 2^24)
+ *   nbd_tree_build_f32        keys, sort, sorted bodies and every node into `workspace` (256-byte aligned); order_out[k]
+ *                             = the caller's index of the k-th sorted body. pos (n,3), mass (n,).
+ *   nbd_tree_accel_f32        the walk over a workspace nbd_tree_build_f32 filled for the same n; acc_out (n,3) in the
+ *                             CALLER's order; counters_out NULL or 2 x uint64 on the device = {accepted cells, rejected
+ *                             level-0 nodes} summed over the target groups. theta < 0 (or NaN) is NBD_E_BADARG.
+ * n = 0 is a no-op. No allocation, memset or synchronisation inside; bit-identical from run to run. */
+int nbd_tree_plan(int n, int* levels, int* nodes_total);
+size_t nbd_tree_workspace_bytes(int n);
+int nbd_tree_build_f32(const float* pos, const float* mass, int n, int* order_out, void* workspace,
+                       size_t workspace_bytes, nbd_stream_t stream);
+int nbd_tree_accel_f32(const void* workspace, int n, float theta, float softening_sq, float g_const, int quadrupole,
+                       float* acc_out, unsigned long long* counters_out, nbd_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

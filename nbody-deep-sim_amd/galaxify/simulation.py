@@ -47,6 +47,9 @@ Eleventh addition: `LeapFrogSimulator(dtype=torch.float64)` and `EulerSimulator(
 schemes with float64 state, scalars and pair arithmetic (csrc/direct_leapfrog_f64.hip): un-sharded, run()
 eager. The default stays float32 and takes the paths it took. The float64 `compute_accelerations()` of every simulator is
 that unit's acceleration-only kernel, bit-identical to the acceleration of the Hermite force.
+
+Twelfth addition: `TreeLeapFrogSimulator`, the leapfrog step with a Barnes-Hut force in O(N log N) (csrc/tree_force.hip;
+DESIGN.md K-T): float32, one GPU. `LeapFrogSimulator` is untouched.
 """
 from __future__ import annotations
 
@@ -926,6 +929,78 @@ class LeapFrogSimulator(BaseSimulator):
         return {"kick_drift_ms": ev[0].elapsed_time(ev[1]), "local_force_ms": ev[1].elapsed_time(ev[2]),
                 "gather_wait_ms": ev[2].elapsed_time(ev[3]), "remote_force_ms": ev[3].elapsed_time(ev[4]),
                 "host_enqueue_ms": host}
+
+
+class TreeLeapFrogSimulator(LeapFrogSimulator):
+    """LeapFrogSimulator with a Barnes-Hut force in place of the all-pairs sum (csrc/tree_force.hip):
+    O(N log N) per step, for softened collisionless systems where a relative force error of ~1e-3 is below the
+    discreteness noise. `theta` is the opening angle (0.5; 0 opens every node and is the direct sum in tree order),
+    `quadrupole` keeps the cells' quadrupole term (True). float32 only, one GPU, no gradients: `dtype=torch.float64`,
+    `process_group` and inputs that require grad are refused.
+
+    positions, velocities and accelerations stay in the caller's order; the bodies are re-sorted along a Morton curve
+    and the tree rebuilt inside every force evaluation (`tree_order()` is that permutation, `tree_counters()` the walk's
+    work). step() is kick-drift, sort + build, tree force, kick; run() is eager. compute_energies() and
+    compute_potentials() keep the all-pairs O(N^2) kernels: construct large systems with calc_energy=False."""
+
+    def __init__(self, *, theta: float = 0.5, quadrupole: bool = True, **kw):
+        name = type(self).__name__
+        if kw.get("dtype", torch.float32) != torch.float32:
+            raise ValueError(f"{name}: the tree force is float32 only, got dtype={kw['dtype']!r}")
+        if kw.get("process_group") is not None:
+            raise ValueError(f"{name}: there is no range-sharded tree force; process_group is not supported")
+        for key in ("positions", "velocities", "masses"):
+            if isinstance(kw.get(key), torch.Tensor) and kw[key].requires_grad:
+                raise ValueError(f"{name}: the tree force has no backward; {key} requires grad")
+        if not float(theta) >= 0.0:
+            raise ValueError(f"{name}: theta must be >= 0, got {theta!r}")
+        self.theta = float(theta)
+        self.quadrupole = bool(quadrupole)
+        super().__init__(**kw)
+
+    def _init_scratch(self):
+        """The packed sources the energy kernels read, the tree's workspace and outputs; then the first force. (None of
+        the all-pairs step's slabs: they are 16 n rows and this class never launches that step.)"""
+        from nbd import tree
+        self._posm = direct.alloc_posm(self.n, self.device)
+        self._posm.zero_()
+        self._uniform, self._ws, self._gather = None, None, None
+        self._posm_local, self._mass_local = self._posm, self.masses
+        self._tree_ws = tree.workspace(self.n, self.device) if self.n else None
+        self._order = torch.empty((self.n,), dtype=torch.int32, device=self.device)
+        self._counters = torch.zeros((2,), dtype=torch.int64, device=self.device)
+        self.accelerations = self.compute_accelerations()
+
+    def compute_accelerations(self) -> torch.Tensor:
+        """The tree force on the current positions -> new (n,3) tensor in the caller's order."""
+        if self.n == 0:
+            return torch.zeros((0, 3), dtype=torch.float32, device=self.device)
+        if self._wants_grad():
+            raise ValueError(f"{type(self).__name__}.compute_accelerations(): the tree force has no backward")
+        from nbd import tree
+        tree.build(self.positions, self.masses, self._tree_ws, self._order)
+        return tree.accel(self._tree_ws, self.n, self.theta, self._eps2, self._g, self.quadrupole,
+                          counters=self._counters)
+
+    def tree_order(self) -> torch.Tensor:
+        """order (n,) int32 of the last force evaluation: order[k] is the index of the k-th body along the Morton curve."""
+        return self._order.clone()
+
+    def tree_counters(self) -> tuple:
+        """(accepted cells, rejected level-0 nodes) of the last force evaluation, summed over the target groups."""
+        if self.n == 0:
+            return 0, 0
+        c = self._counters.cpu().tolist()
+        return int(c[0]), int(c[1])
+
+    def step(self):
+        """Kick-drift (the direct integrator's kernel), sort + build, tree force, kick."""
+        if self.n == 0:
+            return
+        half, dt = direct.f32(0.5 * self.dt), direct.f32(self.dt)
+        direct.kick_drift(self.positions, self.velocities, self.accelerations, self.masses, half, dt, posm=self._posm)
+        self.accelerations = self.compute_accelerations()
+        direct.kick(self.velocities, self.accelerations, half)
 
 
 class EulerSimulator(BaseSimulator):

@@ -389,6 +389,11 @@ SIGNATURES = {
     "nbd_accel_jerk_vjp_f64_workspace_bytes": (c_size_t, [c_int, c_int]),
     "nbd_accel_jerk_vjp_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_double, c_double, c_void_p,
                                        c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_void_p]),
+    # --- tree-code gravity (csrc/tree_force.hip)
+    "nbd_tree_plan": (c_int, [c_int, POINTER(c_int), POINTER(c_int)]),
+    "nbd_tree_workspace_bytes": (c_size_t, [c_int]),
+    "nbd_tree_build_f32": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "nbd_tree_accel_f32": (c_int, [c_void_p, c_int, c_float, c_float, c_float, c_int, c_void_p, c_void_p, c_void_p]),
     # --- generators on the device (csrc/generators.hip)
     "nbd_disk_workspace_bytes": (c_size_t, [c_int]),
     "nbd_disk_from_draws_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_double, c_double, c_double, c_double,

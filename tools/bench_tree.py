@@ -1,0 +1,132 @@
+"""The tree force (csrc/tree_force.hip) next to the all-pairs kernel on the MI355X, in one process.
+
+  python tools/bench_tree.py [--out FILE] [--sizes N ...]          (default: profiles/r28_tree.json)
+
+Per N (Plummer sphere, eps = 0.1, G = 1, quadrupoles on) and theta in {0.5, 0.75}:
+  build_ms    nbd_tree_build_f32: bounding box, Morton keys, radix sort, gather, every node
+  walk_ms     nbd_tree_accel_f32 with the counters
+  direct_ms   nbd_accel_f32 on the same bodies (packed once, outside the window)
+  counters    accepted cells and rejected level-0 nodes over all target groups, and what they come to per body:
+              interactions_per_body = (cells + 8 x level-0 nodes) x 64 / n against the n of the direct sum
+  row errors  256 sampled rows of the tree force, and of nbd_accel_f32, against float64 all-pairs rows (torch on the
+              device: a reference, not a product path), measured like conftest.row_rel
+Times are HIP events around `reps` calls; the three are measured in alternating rounds and the median round is kept.
+"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "nbody-deep-sim_amd"))
+
+from nbd import direct, tree  # noqa: E402
+from nbd.plummer import generate_plummer  # noqa: E402
+
+EPS, ROUNDS, SAMPLED = 0.1, 5, 256
+
+
+def _timed(fn, reps):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(reps):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / reps
+
+
+def _f64_rows(pos, mass, rows, eps2):
+    """float64 all-pairs accelerations of the sampled rows (G = 1), 16 rows at a time."""
+    p, m = pos.double(), mass.double()
+    out = torch.empty((len(rows), 3), dtype=torch.float64, device=pos.device)
+    for k in range(0, len(rows), 16):
+        r = rows[k:k + 16]
+        d = p[None, :, :] - p[r][:, None, :]
+        w = ((d * d).sum(2) + eps2) ** -1.5
+        w[torch.arange(len(r), device=pos.device), r] = 0.0
+        out[k:k + 16] = ((m[None, :] * w)[:, :, None] * d).sum(1)
+    return out.cpu().numpy()
+
+
+def _row_errors(a, ref):
+    nrm = np.linalg.norm(ref, axis=1)
+    floor = 1e-3 * np.sqrt((nrm ** 2).mean())
+    e = np.linalg.norm(a - ref, axis=1) / np.maximum(nrm, floor)
+    return {"max": float(e.max()), "rms": float(np.sqrt((e ** 2).mean()))}
+
+
+def case(n, thetas):
+    p, _, m = generate_plummer(n, seed=1)
+    dev = torch.device("cuda", torch.cuda.current_device())
+    pos = torch.tensor(np.asarray(p, np.float32), device=dev)
+    mass = torch.tensor(np.asarray(m, np.float32), device=dev)
+    eps2 = direct.f32(EPS ** 2)
+    posm = direct.pack_posm(pos, mass)
+    dws = direct.accel_workspace(n, n, dev)
+    dacc = torch.empty((n, 3), dtype=torch.float32, device=dev)
+    tws = tree.workspace(n, dev)
+    order = torch.empty((n,), dtype=torch.int32, device=dev)
+    tacc = torch.empty((n, 3), dtype=torch.float32, device=dev)
+    counters = torch.zeros((2,), dtype=torch.int64, device=dev)
+    rows = torch.tensor(np.random.default_rng(0).choice(n, min(SAMPLED, n), replace=False), device=dev)
+    ref = _f64_rows(pos, mass, rows, float(eps2))
+
+    def run_direct():
+        direct.accel(posm, n, posm, n, 0, eps2, 1.0, out=dacc, workspace=dws)
+
+    def run_build():
+        tree.build(pos, mass, tws, order)
+
+    reps_direct = max(2, min(50, int(4e10 / n / n)))
+    reps_tree = max(5, min(50, int(4e6 / n) * 5))
+    res = {"n": n, "plan": tree.plan(n), "workspace_bytes": tree.workspace_bytes(n), "reps_direct": reps_direct,
+           "reps_tree": reps_tree, "thetas": []}
+    run_direct(); run_build()
+    torch.cuda.synchronize()
+    res["direct_row_error"] = _row_errors(dacc[rows].cpu().numpy().astype(np.float64), ref)
+    for theta in thetas:
+        def run_walk():
+            tree.accel(tws, n, theta, eps2, 1.0, True, out=tacc, counters=counters)
+        run_walk()
+        torch.cuda.synchronize()
+        t = {"direct_ms": [], "build_ms": [], "walk_ms": []}
+        for _ in range(ROUNDS):
+            t["direct_ms"].append(_timed(run_direct, reps_direct))
+            t["build_ms"].append(_timed(run_build, reps_tree))
+            t["walk_ms"].append(_timed(run_walk, reps_tree))
+        row = {"theta": theta}
+        for key, vals in t.items():
+            row[key] = float(np.median(vals))
+            row[key + "_min"] = float(np.min(vals))
+        row["tree_ms"] = row["build_ms"] + row["walk_ms"]
+        row["direct_over_tree"] = row["direct_ms"] / row["tree_ms"]
+        row["tree_faster_than_direct"] = bool(row["tree_ms"] < row["direct_ms"])
+        cells, leaves = counters.cpu().tolist()
+        row["accepted_cells"], row["rejected_level0_nodes"] = int(cells), int(leaves)
+        row["interactions_per_body"] = (cells + 8 * leaves) * 64 / n
+        row["tree_row_error"] = _row_errors(tacc[rows].cpu().numpy().astype(np.float64), ref)
+        res["thetas"].append(row)
+        print(json.dumps({"n": n, **row}), flush=True)
+    return res
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r28_tree.json"))
+    ap.add_argument("--sizes", type=int, nargs="+", default=[65536, 262144, 524288])
+    ap.add_argument("--thetas", type=float, nargs="+", default=[0.5, 0.75])
+    args = ap.parse_args()
+    assert torch.cuda.is_available(), "needs the MI355X"
+    res = {"device": torch.cuda.get_device_name(0), "softening": EPS, "quadrupole": True, "sampled_rows": SAMPLED,
+           "rounds": ROUNDS, "cases": [case(n, args.thetas) for n in args.sizes]}
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(res, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()
