@@ -16,11 +16,13 @@
 // the order's step constants), which the caller forms on the host by the expressions of the one-system path; no kernel
 // takes a per-scene scalar by value, so a step can be captured into a graph and a changed dt, softening or G is a rewrite
 // of the table. One step is three launches:
-//   predict  : one thread per packed row: hermite_predict_row<double> resp. hermite6_predict_row with the scene's constants
+//   predict  : one thread per packed row. 4th: batch_hermite_predict_kernel<double> (hermite_batch_kernels.h, shared with
+//              the fp32 unit) on rows kStep.. of par; 6th: hermite6_predict_row with the scene's constants
 //   evaluate : one workgroup per item: batch_force_f64_kernel<Order>: Order::make's functor + walk_f64 on the scene's rows,
 //              the chunks of wave 4 k + w under the scene's own balanced split; unscaled partial sums into the scene's
 //              double[slabs][kOut][n_s]
-//   finish   : one thread per packed row. 4th: hermite_slab_sum (slab order) x G_s, hermite_correct_row, posd = {x1, m};
+//   finish   : one thread per packed row. 4th: batch_hermite_correct_kernel<double> (the same header) on rows kG and
+//              kStep.. of par: hermite_slab_sum (slab order) x G_s, hermite_correct_row, posd = {x1, m};
 //              6th: hermite6_finish_row (slab order, x G_s, corrector, crackle), posd = {x1, m}
 // and the diagnostics walk the same items with EnergyPair / PotentialPair and finish per scene. Every kernel here is a
 // prologue that reads its geometry and calls the single copies of the arithmetic (hermite_kernels.h,
@@ -28,8 +30,8 @@
 // scene alone. No atomics, no memsets, no host syncs: deterministic with a workspace that may hold anything.
 // Resources (hipcc --offload-arch=gfx950 -O3, -Rpass-analysis=kernel-resource-usage): batch_force_f64_kernel<Order4>: 89
 // VGPRs, 32 KiB of LDS, 5 waves per SIMD; <Order6>: 164 VGPRs, 48 KiB, 3 waves per SIMD -- force_f64_kernel<Order>'s
-// figures. batch_predict_f64_kernel: 32 VGPRs; batch_correct_f64_kernel: 46; batch_hermite6_predict_kernel: 52;
-// batch_hermite6_finish_kernel: 68. No spills and no scratch anywhere.
+// figures. batch_hermite_predict_kernel<double>: 32 VGPRs; batch_hermite_correct_kernel<double>: 46;
+// batch_hermite6_predict_kernel: 52; batch_hermite6_finish_kernel: 68. No spills and no scratch anywhere.
 #include <hip/hip_runtime.h>
 #include <limits.h>
 #include <stdint.h>
@@ -38,6 +40,7 @@
 #include "direct_batch_plan.h"
 #include "direct_kernels.h"
 #include "hermite6_f64_kernels.h"
+#include "hermite_batch_kernels.h"
 #include "hermite_f64_kernels.h"
 #include "hermite_kernels.h"
 #include "hermite_orders_f64.h"
@@ -48,7 +51,7 @@ namespace {
 // the order's own step constants from row kStep on
 enum ParamRow {
   kG = 0, kEps2, kEps, kStep,
-  kDt = kStep, kDtHalf, kDt2Half, kDt3Sixth, kDt2Twelfth, kParams4,      // 4th: the five of HermiteStep<double>
+  kParams4 = kStep + HermiteStepRow::kRows,                              // 4th: HermiteStep<double>'s, HermiteStepRow
   kParams6 = kStep + (int)(sizeof(Hermite6Step) / sizeof(double))        // 6th: Hermite6Step's members in its order
 };
 static_assert(kParams4 == NBD_BATCH_F64_PARAM_ROWS, "the table include/nbd.h describes");
@@ -64,33 +67,6 @@ __device__ __forceinline__ Hermite6Step load_step(const double* __restrict__ par
 // the plan counted in doubles (direct_batch_plan.h) with the scene's slabs double[slabs][kOut][n]: the 4th order's, and what
 // the diagnostics check a plan of either order against (its items, rows and bytes do not depend on kOut)
 constexpr int kOut = Order4::Pair::kOut;
-
-// posd[r] = {x_p, m}, veld[r] = {v_p, 0} for every packed row r (zero rows behind each scene's last body).
-// acc == nullptr: a plain pack of (x, v).
-__global__ __launch_bounds__(256) void batch_predict_f64_kernel(const int* __restrict__ row_scene,
-                                                                const SceneRec* __restrict__ scenes, int n_rows,
-                                                                const double* __restrict__ pos,
-                                                                const double* __restrict__ vel,
-                                                                const double* __restrict__ acc,
-                                                                const double* __restrict__ jerk,
-                                                                const double* __restrict__ mass,
-                                                                const double* __restrict__ par, int n_scenes,
-                                                                d4* __restrict__ posd, d4* __restrict__ veld) {
-  PlanRow w;
-  if (!load_row(row_scene, scenes, n_rows, w)) return;
-  d4 pm = HermiteFmt<double>::zero(), vp = HermiteFmt<double>::zero();
-  if (w.i() < w.sc.n) {
-    const size_t b = (size_t)w.sc.off + w.i();
-    const double dt = acc ? par[kDt * n_scenes + w.s] : 0.0;
-    const double dt2_half = acc ? par[kDt2Half * n_scenes + w.s] : 0.0;
-    const double dt3_sixth = acc ? par[kDt3Sixth * n_scenes + w.s] : 0.0;
-    const PosVel3<double> p = hermite_predict_row(pos, vel, acc, jerk, b, dt, dt2_half, dt3_sixth, acc != nullptr);
-    pm = hermite_row(p.x, mass[b]);
-    vp = hermite_row(p.v, 0.0);
-  }
-  posd[w.r] = pm;
-  veld[w.r] = vp;
-}
 
 // One workgroup per item (s, g, k): force_f64_kernel<Order>'s prologue (direct_hermite_f64.hip) read from the scene record
 // -- targets [64 g, 64 g + 64) of scene s, the chunks of wave 4 k + w under chunk_split(n_chunks, slabs) of the scene --
@@ -113,32 +89,6 @@ __global__ __launch_bounds__(64 * kWaves) void batch_force_f64_kernel(
   Pair pr = Order::make(pd, vd, ad, g.row(), g.i, eps2, w.n);
   walk_f64(pr, pd, vd, c.begin, c.end, eps2 < kEps2MaskedF64, w.grp, lds, g.dst<Pair>(ws + (size_t)w.ws_off), (size_t)w.n,
            g.n_valid(), nullptr, ad);
-}
-
-// One thread per packed row (a row belongs to one scene; the padding rows leave at once): a1, j1 = hermite_slab_sum of the
-// body's row in its scene's slabs, scaled by G_s. pos == nullptr: write a1, j1 only. Else hermite_correct_row: reads a0,
-// j0 (acc_in / jerk_in may alias acc_out / jerk_out: each element is read before it is written, by the same thread), x,
-// v; writes x1, v1, a1, j1 and posd = {x1, m}.
-__global__ __launch_bounds__(256) void batch_correct_f64_kernel(const int* __restrict__ row_scene,
-                                                                const SceneRec* __restrict__ scenes, int n_rows,
-                                                                const double* __restrict__ ws,
-                                                                const double* __restrict__ par, int n_scenes,
-                                                                double* pos, double* vel, const double* acc_in,
-                                                                const double* jerk_in, double* acc_out, double* jerk_out,
-                                                                const double* __restrict__ mass, d4* __restrict__ posd) {
-  PlanRow w;
-  if (!load_row(row_scene, scenes, n_rows, w)) return;
-  double a1[3], j1[3];
-  if (!hermite_slab_sum(ws + (size_t)w.sc.ws_off, w.sc.slabs, w.sc.n, (size_t)w.i(), w.i() < w.sc.n,
-                        par[kG * n_scenes + w.s], a1, j1))
-    return;
-  const size_t b = (size_t)w.sc.off + w.i();
-  if (pos) {
-    const Corrected<double> c = hermite_correct_row(pos, vel, acc_in, jerk_in, b, a1, j1,
-                                                    par[kDtHalf * n_scenes + w.s], par[kDt2Twelfth * n_scenes + w.s]);
-    posd[w.r] = hermite_row(c.x1, mass[b]);
-  }
-  hermite_store_force(acc_out, jerk_out, b, a1, j1);
 }
 
 // ---- the 6th order's O(N) kernels
@@ -316,9 +266,9 @@ int batch_step(const int* offsets, int n_scenes, const void* plan, size_t plan_b
 // (pos == nullptr: the force on its own) of the two orders, as the entries' lambdas call them
 void predict4(const DevPlan& d, const BatchTotals& t, const double* pos, const double* vel, const double* acc,
               const double* jerk, const double* mass, const double* par, double* posd, double* veld, hipStream_t st) {
-  batch_predict_f64_kernel<<<ceil_div(t.n_rows, 256), 256, 0, st>>>(d.row_scene, d.scenes, t.n_rows, pos, vel, acc, jerk,
-                                                                    mass, par, t.n_scenes, reinterpret_cast<d4*>(posd),
-                                                                    reinterpret_cast<d4*>(veld));
+  batch_hermite_predict_kernel<double><<<ceil_div(t.n_rows, 256), 256, 0, st>>>(
+      d.row_scene, d.scenes, t.n_rows, pos, vel, acc, jerk, mass, par ? par + (size_t)kStep * t.n_scenes : nullptr,
+      t.n_scenes, reinterpret_cast<d4*>(posd), reinterpret_cast<d4*>(veld));
 }
 
 void predict6(const DevPlan& d, const BatchTotals& t, const double* pos, const double* vel, const double* acc,
@@ -332,9 +282,9 @@ void predict6(const DevPlan& d, const BatchTotals& t, const double* pos, const d
 void finish4(const DevPlan& d, const BatchTotals& t, const double* ws, const double* par, double* pos, double* vel,
              const double* acc_in, const double* jerk_in, double* acc_out, double* jerk_out, const double* mass,
              double* posd, hipStream_t st) {
-  batch_correct_f64_kernel<<<ceil_div(t.n_rows, 256), 256, 0, st>>>(d.row_scene, d.scenes, t.n_rows, ws, par, t.n_scenes,
-                                                                    pos, vel, acc_in, jerk_in, acc_out, jerk_out, mass,
-                                                                    reinterpret_cast<d4*>(posd));
+  batch_hermite_correct_kernel<double><<<ceil_div(t.n_rows, HermiteFmt<double>::kSumRows), 256, 0, st>>>(
+      d.row_scene, d.scenes, t.n_rows, ws, par + (size_t)kG * t.n_scenes, par + (size_t)kStep * t.n_scenes, t.n_scenes,
+      pos, vel, acc_in, jerk_in, acc_out, jerk_out, mass, reinterpret_cast<d4*>(posd));
 }
 
 void finish6(const DevPlan& d, const BatchTotals& t, const double* ws, const double* par, double* pos, double* vel,

@@ -34,21 +34,23 @@
 //     finish  : hermite_correct_kernel<double>: the slabs in slab order (slab_order_sum, one thread per body), a1 = G sum,
 //               j1 = G sum, the corrector, posd = {x1, m}
 //   6th : a0, j0, s0 and the crackle c0 = d^3 a / dt^3 carried; packed rows ... and {a_p, 0}
-//     predict : hermite6_predict_kernel: Taylor series to c0
+//     predict : hermite6_predict_kernel<1>: Taylor series to c0
 //     evaluate: force_f64_kernel<Order6> -> double[slabs][9][n]
-//     finish  : hermite6_finish_kernel: slab_order_sum<9>, a1, j1, s1 = G sum, the corrector, c1 = the third derivative at
+//     finish  : hermite6_finish_kernel<>: slab_order_sum<9>, a1, j1, s1 = G sum, the corrector, c1 = the third derivative at
 //               t1 of the quintic through (a, j, s) at both ends, posd = {x1, m}
 // The 4th order's two O(N) kernels, the predictor, the corrector and the step constants are hermite_kernels.h's templates
-// at T = double; the 6th order's row bodies and step constants are hermite6_f64_kernels.h's. The step constants are doubles
-// formed from the double dt, never rounded to fp32; every product and sum of the O(N) kernels rounds on its own (the build
-// has -ffp-contract=off). The finishing kernels of the diagnostics add their slabs with the same slab_order_sum.
+// at T = double; the 6th order's two O(N) kernels, row bodies and step constants are hermite6_f64_kernels.h's (this unit
+// launches all four at the row stride 1 and with the packed store; direct_hermite_shard_f64.hip launches the same four
+// on a rank's send buffer). The step constants are doubles formed from the double dt, never rounded to fp32; every
+// product and sum of the O(N) kernels rounds on its own (the build has -ffp-contract=off). The finishing kernels of the
+// diagnostics add their slabs with the same slab_order_sum.
 // rsqrt_f64, the pair functors, the bodies of the finishing kernels, walk_f64, the kernels' prologue (Group64,
 // wave_chunks_upper) and plan_f64 live in hermite_f64_kernels.h, shared with every other float64 unit (the block-timestep,
 // the sharded, the batched, the leapfrog and the backward ones).
 // Resources (hipcc --offload-arch=gfx950 -O3, -Rpass-analysis=kernel-resource-usage). force_f64_kernel<Order4>: 89 VGPRs,
 // 32 KiB of LDS, 5 waves per SIMD: five workgroups per CU, what the LDS allows. <Order6>: 164 VGPRs, 0 AGPRs, 48 KiB of
 // LDS, 3 waves per SIMD: three workgroups per CU by the LDS and by the registers alike. hermite_predict_kernel<double>: 24
-// VGPRs; hermite_correct_kernel<double>: 42; hermite6_predict_kernel: 40; hermite6_finish_kernel: 52; potential_f64_kernel:
+// VGPRs; hermite_correct_kernel<double>: 42; hermite6_predict_kernel<1>: 40; hermite6_finish_kernel<>: 52; potential_f64_kernel:
 // 56 and energy_f64_kernel: 30, 16 KiB of LDS each. No SGPR or VGPR spills and no scratch anywhere.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -127,47 +129,6 @@ __global__ __launch_bounds__(kInvThreads) void invariants_state_f64_kernel(const
                                                                            double* __restrict__ row) {
   __shared__ double red[kInvSums][kInvWaves];
   invariants_body(F64State{pos, vel, mass}, phi, n, row, red);
-}
-
-// posd = {x_p, m}, veld = {v_p, 0}, accd = {a_p, 0} for rows [0, n_pad), zero rows behind n:
-//   x_p = x + v dt + a dt^2/2 + j dt^3/6 + s dt^4/24 + c dt^5/120,  v_p = v + a dt + j dt^2/2 + s dt^3/6 + c dt^4/24,
-//   a_p = a + j dt + s dt^2/2 + c dt^3/6.
-// jerk == nullptr (then snap and crackle are too): a plain pack of (pos, vel, acc); acc == nullptr as well: accd = 0.
-__global__ __launch_bounds__(256) void hermite6_predict_kernel(const double* __restrict__ pos,
-                                                               const double* __restrict__ vel,
-                                                               const double* __restrict__ acc,
-                                                               const double* __restrict__ jerk,
-                                                               const double* __restrict__ snap,
-                                                               const double* __restrict__ crackle,
-                                                               const double* __restrict__ mass, int n, int n_pad,
-                                                               Hermite6Step h, d4* __restrict__ posd,
-                                                               d4* __restrict__ veld, d4* __restrict__ accd) {
-  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= (size_t)n_pad) return;
-  d4 pm = {0.0, 0.0, 0.0, 0.0}, vp = pm, ap = pm;
-  if (i < (size_t)n) hermite6_predict_row(pos, vel, acc, jerk, snap, crackle, mass, i, h, pm, vp, ap);
-  posd[i] = pm;
-  veld[i] = vp;
-  accd[i] = ap;
-}
-
-// One thread per body: a1, j1, s1 = G (slab 0 + slab 1 + ...) of double[n_slabs][9][n] in slab order. pos == nullptr:
-// write them only (the force on its own). Else the corrector
-//   v1 = v + (a0 + a1) dt/2 - (j1 - j0) dt^2/10 + (s0 + s1) dt^3/120
-//   x1 = x + (v + v1) dt/2 - (a1 - a0) dt^2/10 + (j0 + j1) dt^3/120
-//   c1 = [60 (a1 - a0) - dt (36 j1 + 24 j0) + dt^2 (9 s1 - 3 s0)] / dt^3
-// with pos and vel in place and posd = {x1, m}. The outputs may alias acc_in, jerk_in, snap_in: each element is read
-// before it is written, by the same thread.
-__global__ __launch_bounds__(256) void hermite6_finish_kernel(const double* __restrict__ slabs, int n_slabs, int n,
-                                                              double g, Hermite6Step h, double* pos, double* vel,
-                                                              const double* acc_in, const double* jerk_in,
-                                                              const double* snap_in, double* acc_out, double* jerk_out,
-                                                              double* snap_out, double* crackle_out,
-                                                              const double* __restrict__ mass, d4* __restrict__ posd) {
-  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= (size_t)n) return;
-  hermite6_finish_row(slabs, n_slabs, (size_t)n, i, i, g, h, pos, vel, acc_in, jerk_in, snap_in, acc_out, jerk_out,
-                      snap_out, crackle_out, mass, posd, i);
 }
 
 constexpr int kSumRows = HermiteFmt<double>::kSumRows;      // bodies per workgroup of the 4th-order corrector launch
@@ -265,7 +226,7 @@ int nbd_hermite6_f64_pack(const double* pos, const double* vel, const double* ac
   if (misaligned32(posd) || misaligned32(veld) || misaligned32(accd)) return NBD_E_BADARG;
   if (n == 0) return 0;
   const int n_pad = nbd_posm_padded_len(n);
-  hermite6_predict_kernel<<<ceil_div(n_pad, 256), 256, 0, (hipStream_t)stream>>>(
+  hermite6_predict_kernel<><<<ceil_div(n_pad, 256), 256, 0, (hipStream_t)stream>>>(
       pos, vel, acc, jerk, snap, crackle, mass, n, n_pad, hermite6_step_constants(dt), reinterpret_cast<d4*>(posd),
       reinterpret_cast<d4*>(veld), reinterpret_cast<d4*>(accd));
   return launch_status();
@@ -289,7 +250,7 @@ int nbd_accel_jerk_snap_f64(const double* posd, const double* veld, const double
   return shared_force<Order6>(
       posd, veld, accd, n, softening_sq, acc_out && jerk_out && snap_out, workspace, workspace_bytes, slabs, stream,
       [=](const double* part, int n_slabs, hipStream_t st) {
-        hermite6_finish_kernel<<<ceil_div(n, 256), 256, 0, st>>>(
+        hermite6_finish_kernel<><<<ceil_div(n, 256), 256, 0, st>>>(
             part, n_slabs, n, g_const, hermite6_step_constants(0.0), nullptr, nullptr, nullptr, nullptr, nullptr,
             acc_out, jerk_out, snap_out, nullptr, nullptr, nullptr);
       });
@@ -327,11 +288,11 @@ int nbd_hermite6_step_f64(double* pos, double* vel, const double* acc_in, const 
   return shared_step<Order6>(
       n, state_ok, posd, veld, accd, softening_sq, workspace, workspace_bytes, stream,
       [=](hipStream_t st) {
-        hermite6_predict_kernel<<<ceil_div(n_pad, 256), 256, 0, st>>>(pos, vel, acc_in, jerk_in, snap_in, crackle_in,
+        hermite6_predict_kernel<><<<ceil_div(n_pad, 256), 256, 0, st>>>(pos, vel, acc_in, jerk_in, snap_in, crackle_in,
                                                                       mass, n, n_pad, h, pd, vd, ad);
       },
       [=](const double* part, int n_slabs, hipStream_t st) {
-        hermite6_finish_kernel<<<ceil_div(n, 256), 256, 0, st>>>(part, n_slabs, n, g_const, h, pos, vel, acc_in, jerk_in,
+        hermite6_finish_kernel<><<<ceil_div(n, 256), 256, 0, st>>>(part, n_slabs, n, g_const, h, pos, vel, acc_in, jerk_in,
                                                                  snap_in, acc_out, jerk_out, snap_out, crackle_out, mass,
                                                                  pd);
       });

@@ -5,16 +5,18 @@
 //
 // The exchanged row is 8 floats, {x_p, y_p, z_p, m, vx_p, vy_p, vz_p, 0}: ONE all-gather per step carries both quads, and
 // accel_jerk_body (hermite_kernels.h, SS = 2) fetches a row's position quad and velocity quad by LDS-DMA at a two-quad
-// stride, so the gathered array is read as it lands (no de-interleave launch). A rank's step is four launches:
-//   predict : hermite_predict_row of the own bodies -> the send buffer, zero rows behind n_local
+// stride, so the gathered array is read as it lands (no de-interleave launch). A rank's step is four launches; the two
+// O(N) ones are the un-sharded step's kernels (hermite_kernels.h), so the only kernel defined here is the pair kernel:
+//   predict : hermite_predict_kernel<float, 2> on the own bodies -> the send buffer (posm = send, velp = send + 1 at the
+//             row's two-quad stride), zero rows behind n_local
 //   local   : a, j partial sums of the own bodies under the own bodies (reads the send buffer only: runs while the
 //             gather is in flight); the un-sharded kernel's geometry on n_local sources
 //   remote  : the same under all bodies of the gathered array except [lo, lo + n_local): whole source chunks inside the
 //             range are hopped over, the <= 2 chunks that straddle an end take the masked loop with the range mask
 //             (excluded_view, direct_kernels.h -- the leapfrog shard's view)
-//   finish  : hermite_slab_sum over the local slabs, then the remote ones (a fixed order), times G, and
-//             hermite_correct_row of the own rows -- a launch of its own, as in the un-sharded step (or a1, j1 only: the
-//             force on its own)
+//   finish  : hermite_correct_kernel<float, false>: hermite_slab_sum over the local slabs, then the remote ones (a fixed
+//             order), times G, and hermite_correct_row of the own rows -- a launch of its own, as in the un-sharded step
+//             (or a1, j1 only: the force on its own); no packed row is stored, the next predictor rebuilds the send buffer
 // Every rounded operation is one of hermite_kernels.h's. No atomics, no memsets, no host syncs: deterministic, capturable.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -45,40 +47,9 @@ __global__ __launch_bounds__(64 * kWaves, RANGE ? 5 : 6) void shard_accel_jerk_k
                                                &sv);
 }
 
-// rows [0, rows) of the send buffer: {x_p, m}, {v_p, 0} of the rank's bodies, zeros behind n. acc == nullptr: plain pack.
-__global__ __launch_bounds__(256) void shard_predict_kernel(const float* __restrict__ pos, const float* __restrict__ vel,
-                                                            const float* __restrict__ acc, const float* __restrict__ jerk,
-                                                            const float* __restrict__ mass, int n, int rows, HermiteDt h,
-                                                            f4* __restrict__ send) {
-  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= (size_t)rows) return;
-  f4 pm = HermiteFmt<float>::zero(), vp = HermiteFmt<float>::zero();
-  if (i < (size_t)n) {
-    const PosVel3<float> p = hermite_predict_row(pos, vel, acc, jerk, i, h.dt, h.dt2_half, h.dt3_sixth, acc != nullptr);
-    pm = hermite_row(p.x, mass[i]);
-    vp = hermite_row(p.v, 0.f);
-  }
-  send[kRowQuads * i] = pm;
-  send[kRowQuads * i + 1] = vp;
-}
-
-// One workgroup per 64 consecutive own bodies: a1, j1 = hermite_slab_sum of the body's row over all slabs, local ones
-// first. pos == nullptr: write a1, j1 only. Else hermite_correct_row (acc_in / jerk_in may alias acc_out / jerk_out: each
-// element is read before it is written, by the same thread).
-__global__ __launch_bounds__(256) void shard_finish_kernel(const float* __restrict__ slabs, int n_slabs, int n, float g,
-                                                           HermiteDt h, float* pos, float* vel, const float* acc_in,
-                                                           const float* jerk_in, float* acc_out, float* jerk_out) {
-  const size_t i = hermite_sum_row<float>();
-  float a1[3], j1[3];
-  if (!hermite_slab_sum(slabs, n_slabs, n, i, i < (size_t)n, g, a1, j1)) return;
-  if (pos) hermite_correct_row(pos, vel, acc_in, jerk_in, i, a1, j1, h.dt_half, h.dt2_twelfth);
-  hermite_store_force(acc_out, jerk_out, i, a1, j1);
-}
-
-// The geometry of a rank's two force launches: the leapfrog shard's slab counts (nbd_shard_plan: same targets, same
-// chunks, the same balance problem), raised where a wave's sequential fp32 chain would pass 64 chunks (4096 sources).
-struct HShardPlan { int groups, slabs_local, chunks_local, slabs_remote, chunks_remote; SrcView remote; };
-
+// The geometry of a rank's two force launches (HShardPlan, hermite_kernels.h): the leapfrog shard's slab counts
+// (nbd_shard_plan: same targets, same chunks, the same balance problem), raised where a wave's sequential fp32 chain would
+// pass 64 chunks (4096 sources).
 int chain_slabs(int slabs, int n_chunks) {
   const int min_slabs = ceil_div(n_chunks, kWaves * 64);
   slabs = slabs < min_slabs ? min_slabs : slabs;
@@ -108,12 +79,8 @@ extern "C" {
 int nbd_hermite_shard_plan(int n_total, int lo, int n_local, int* slabs_local, int* chunks_per_wave_local,
                            int* slabs_remote, int* chunks_per_wave_remote) {
   if (!shard_args_ok(n_total, lo, n_local) || n_local == 0) return NBD_E_BADARG;
-  const HShardPlan p = plan_hshard(n_total, lo, n_local);
-  if (slabs_local) *slabs_local = p.slabs_local;
-  if (chunks_per_wave_local) *chunks_per_wave_local = ceil_div(p.chunks_local, p.slabs_local * kWaves);
-  if (slabs_remote) *slabs_remote = p.slabs_remote;
-  if (chunks_per_wave_remote)
-    *chunks_per_wave_remote = p.slabs_remote ? ceil_div(p.chunks_remote, p.slabs_remote * kWaves) : 0;
+  hshard_plan_out(plan_hshard(n_total, lo, n_local), slabs_local, chunks_per_wave_local, slabs_remote,
+                  chunks_per_wave_remote);
   return 0;
 }
 
@@ -129,8 +96,9 @@ int nbd_hermite_shard_predict_f32(const float* pos, const float* vel, const floa
   if (n_local < 0 || send_rows < nbd_posm_padded_len(n_local) || (!acc != !jerk)) return NBD_E_BADARG;
   if (send_rows == 0) return 0;
   if (!send || misaligned16(send) || (n_local > 0 && (!pos || !vel || !mass))) return NBD_E_BADARG;
-  shard_predict_kernel<<<ceil_div(send_rows, 256), 256, 0, (hipStream_t)stream>>>(
-      pos, vel, acc, jerk, mass, n_local, send_rows, hermite_dt(dt), reinterpret_cast<f4*>(send));
+  f4* s = reinterpret_cast<f4*>(send);
+  hermite_predict_kernel<float, kRowQuads><<<ceil_div(send_rows, 256), 256, 0, (hipStream_t)stream>>>(
+      pos, vel, acc, jerk, mass, n_local, send_rows, hermite_dt(dt), s, s + 1);
   return launch_status();
 }
 
@@ -179,9 +147,10 @@ int nbd_hermite_shard_force_remote_f32(const float* all, int n_total, const floa
     const int rc = launch_status();
     if (rc) return rc;
   }
-  shard_finish_kernel<<<ceil_div(n_local, HermiteFmt<float>::kSumRows), 256, 0, st>>>(
+  // all slabs, local ones first; the send buffer is not written (the next predictor rebuilds it)
+  hermite_correct_kernel<float, false><<<ceil_div(n_local, HermiteFmt<float>::kSumRows), 256, 0, st>>>(
       slabs, p.slabs_local + p.slabs_remote, n_local, g_const, hermite_dt(dt), pos, vel, acc_in, jerk_in, acc_out,
-      jerk_out);
+      jerk_out, nullptr, nullptr);
   return launch_status();
 }
 

@@ -8,20 +8,23 @@
 // The exchanged row is kArr 32-byte pieces (d4), the streamed arrays side by side: ONE all-gather per step carries them
 // all, and walk_f64 (hermite_f64_kernels.h, RQ = 2 kArr) fetches a chunk's pieces by LDS-DMA at the row's stride into the
 // [array][128] LDS image the un-sharded kernels use, so the gathered array is read as it lands (no de-interleave launch)
-// and the pair loops are the un-sharded ones. A rank's step is four launches, as in fp32:
-//   predict : the predictor of the own bodies -> the send buffer, zero rows behind n_local
+// and the pair loops are the un-sharded ones. A rank's step is four launches, as in fp32; the two O(N) ones are the
+// un-sharded steps' kernels (hermite_kernels.h, hermite6_f64_kernels.h), so the only kernel defined here is the pair kernel:
+//   predict : the un-sharded predictor kernel at the row's stride (the packed arrays are send, send + 1 and, at the 6th
+//             order, send + 2) on the own bodies -> the send buffer, zero rows behind n_local
 //   local   : partial sums of the own bodies under the own bodies (reads the send buffer only: runs while the gather is
 //             in flight); the un-sharded pair kernel's geometry on n_local sources
 //   remote  : the same targets under all bodies of the gathered array except [lo, lo + n_local): whole source chunks
 //             inside the range are hopped over, the <= 2 chunks that straddle an end take the masked loop with the range
 //             mask (excluded_view, direct_kernels.h)
-//   finish  : slab_order_sum over the local slabs, then the remote ones, times G, and the corrector of the own rows (or
+//   finish  : the un-sharded finishing kernel without its packed store (the next predictor rebuilds the send buffer):
+//             slab_order_sum over the local slabs, then the remote ones, times G, and the corrector of the own rows (or
 //             the force on its own)
-// What the orders differ in (Order4, Order6 of hermite_orders_f64.h; the row kernels and the pointer lists of the entries):
-//             row, 8-byte doubles                         sums per body   predictor              finish
-//   4th : {x_p, m | v_p, 0}, 8                            a, j: 6         hermite_predict_row    hermite_correct_row
-//   6th : {x_p, m | v_p, 0 | a_p, 0}, 12                  a, j, s: 9      hermite6_predict_row   hermite6_finish_row: the
-//                                                                                                corrector and c1
+// What the orders differ in (Order4, Order6 of hermite_orders_f64.h; the O(N) kernels and the pointer lists of the entries):
+//             row, 8-byte doubles           sums per body  predictor                          finish
+//   4th : {x_p, m | v_p, 0}, 8              a, j: 6        hermite_predict_kernel<double, 2>  hermite_correct_kernel<double, false>
+//   6th : {x_p, m | v_p, 0 | a_p, 0}, 12    a, j, s: 9     hermite6_predict_kernel<3>         hermite6_finish_kernel<false>: the
+//                                                                                             corrector and c1
 // Every rounded operation is hermite_f64_kernels.h's, hermite6_f64_kernels.h's or hermite_kernels.h's: a rank that owns
 // every body computes nbd_accel_jerk_f64's resp. nbd_accel_jerk_snap_f64's bits, and a and j of any 6th-order rank are the
 // 4th order's at the same slab counts. No atomics, no memsets, no host syncs: deterministic with a workspace that may hold
@@ -60,73 +63,8 @@ __global__ __launch_bounds__(64 * kWaves) void shard_pair_f64_kernel(const d4* _
                                           g.n_valid(), &sv, kArr == 3 ? src + 2 : nullptr);
 }
 
-// rows [0, rows) of the send buffer: {x_p, m}, {v_p, 0} of the rank's bodies, zeros behind n. acc == nullptr: plain pack.
-__global__ __launch_bounds__(256) void shard_predict_f64_kernel(const double* __restrict__ pos,
-                                                                const double* __restrict__ vel,
-                                                                const double* __restrict__ acc,
-                                                                const double* __restrict__ jerk,
-                                                                const double* __restrict__ mass, int n, int rows,
-                                                                HermiteStep<double> h, d4* __restrict__ send) {
-  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= (size_t)rows) return;
-  d4 pm = HermiteFmt<double>::zero(), vp = HermiteFmt<double>::zero();
-  if (i < (size_t)n) {
-    const PosVel3<double> p = hermite_predict_row(pos, vel, acc, jerk, i, h.dt, h.dt2_half, h.dt3_sixth, acc != nullptr);
-    pm = hermite_row(p.x, mass[i]);
-    vp = hermite_row(p.v, 0.0);
-  }
-  send[2 * i] = pm;
-  send[2 * i + 1] = vp;
-}
-
-// ... and of the 6th order: {x_p, m}, {v_p, 0}, {a_p, 0}. jerk == nullptr (then snap and crackle are too): plain pack of
-// (pos, vel, acc); acc == nullptr as well: a zero third piece.
-__global__ __launch_bounds__(256) void shard6_predict_f64_kernel(const double* __restrict__ pos,
-                                                                 const double* __restrict__ vel,
-                                                                 const double* __restrict__ acc,
-                                                                 const double* __restrict__ jerk,
-                                                                 const double* __restrict__ snap,
-                                                                 const double* __restrict__ crackle,
-                                                                 const double* __restrict__ mass, int n, int rows,
-                                                                 Hermite6Step h, d4* __restrict__ send) {
-  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= (size_t)rows) return;
-  d4 pm = {0.0, 0.0, 0.0, 0.0}, vp = pm, ap = pm;
-  if (i < (size_t)n) hermite6_predict_row(pos, vel, acc, jerk, snap, crackle, mass, i, h, pm, vp, ap);
-  send[3 * i] = pm;
-  send[3 * i + 1] = vp;
-  send[3 * i + 2] = ap;
-}
-
-// One thread per own body: a1, j1 = G * (the body's row of every slab in slab order, local ones first). pos == nullptr:
-// write a1, j1 only. Else hermite_correct_row (acc_in / jerk_in may alias acc_out / jerk_out: each element is read before
-// it is written, by the same thread).
-__global__ __launch_bounds__(256) void shard_finish_f64_kernel(const double* __restrict__ slabs, int n_slabs, int n,
-                                                               double g, HermiteStep<double> h, double* pos, double* vel,
-                                                               const double* acc_in, const double* jerk_in,
-                                                               double* acc_out, double* jerk_out) {
-  const size_t i = hermite_sum_row<double>();
-  double a1[3], j1[3];
-  if (!hermite_slab_sum(slabs, n_slabs, n, i, i < (size_t)n, g, a1, j1)) return;
-  if (pos) hermite_correct_row(pos, vel, acc_in, jerk_in, i, a1, j1, h.dt_half, h.dt2_twelfth);
-  hermite_store_force(acc_out, jerk_out, i, a1, j1);
-}
-
-// ... and of the 6th order: a1, j1, s1, and with pos hermite6_finish_row's corrector and c1 (the same aliasing rule).
-__global__ __launch_bounds__(256) void shard6_finish_f64_kernel(const double* __restrict__ slabs, int n_slabs, int n,
-                                                                double g, Hermite6Step h, double* pos, double* vel,
-                                                                const double* acc_in, const double* jerk_in,
-                                                                const double* snap_in, double* acc_out,
-                                                                double* jerk_out, double* snap_out,
-                                                                double* crackle_out) {
-  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= (size_t)n) return;
-  hermite6_finish_row<false>(slabs, n_slabs, (size_t)n, i, i, g, h, pos, vel, acc_in, jerk_in, snap_in, acc_out,
-                             jerk_out, snap_out, crackle_out, nullptr, nullptr, i);
-}
-
 // ---- the host bodies of the entries. The geometry of a rank's two force launches is the same for both orders:
-// HShardPlanF64, plan_hshard_f64 and slab_arg_ok of hermite_f64_kernels.h.
+// HShardPlan (hermite_kernels.h), plan_hshard_f64 and slab_arg_ok of hermite_f64_kernels.h.
 
 template <class Order>
 size_t slab_doubles(int n_local) { return (size_t)Order::Pair::kOut * n_local; }
@@ -134,12 +72,8 @@ size_t slab_doubles(int n_local) { return (size_t)Order::Pair::kOut * n_local; }
 int shard_plan(int n_total, int lo, int n_local, int* slabs_local, int* chunks_per_wave_local, int* slabs_remote,
                int* chunks_per_wave_remote) {
   if (!shard_args_ok(n_total, lo, n_local) || n_local == 0) return NBD_E_BADARG;
-  const HShardPlanF64 p = plan_hshard_f64(n_total, lo, n_local, 0, 0);
-  if (slabs_local) *slabs_local = p.slabs_local;
-  if (chunks_per_wave_local) *chunks_per_wave_local = ceil_div(p.chunks_local, p.slabs_local * kWaves);
-  if (slabs_remote) *slabs_remote = p.slabs_remote;
-  if (chunks_per_wave_remote)
-    *chunks_per_wave_remote = p.slabs_remote ? ceil_div(p.chunks_remote, p.slabs_remote * kWaves) : 0;
+  hshard_plan_out(plan_hshard_f64(n_total, lo, n_local, 0, 0), slabs_local, chunks_per_wave_local, slabs_remote,
+                  chunks_per_wave_remote);
   return 0;
 }
 
@@ -147,7 +81,7 @@ template <class Order>
 size_t shard_workspace_bytes(int n_total, int lo, int n_local, int slabs_local, int slabs_remote) {
   if (!shard_args_ok(n_total, lo, n_local) || n_local == 0 || !slab_arg_ok(slabs_local) || !slab_arg_ok(slabs_remote))
     return 0;
-  const HShardPlanF64 p = plan_hshard_f64(n_total, lo, n_local, slabs_local, slabs_remote);
+  const HShardPlan p = plan_hshard_f64(n_total, lo, n_local, slabs_local, slabs_remote);
   return (size_t)(p.slabs_local + p.slabs_remote) * slab_doubles<Order>(n_local) * sizeof(double);
 }
 
@@ -157,7 +91,7 @@ int shard_force_local(const double* send, int n_local, double softening_sq, void
   if (!shard_args_ok(n_total, lo, n_local) || !slab_arg_ok(slabs)) return NBD_E_BADARG;
   if (n_local == 0) return 0;
   if (!send || misaligned32(send)) return NBD_E_BADARG;
-  const HShardPlanF64 p = plan_hshard_f64(n_total, lo, n_local, slabs, 0);
+  const HShardPlan p = plan_hshard_f64(n_total, lo, n_local, slabs, 0);
   // what this launch writes: the local slabs (the remote call checks the whole buffer)
   if (!workspace || misaligned8(workspace) ||
       workspace_bytes < (size_t)p.slabs_local * slab_doubles<Order>(n_local) * sizeof(double))
@@ -184,7 +118,7 @@ int shard_force_remote(const double* all, int n_total, const double* send, int n
   if (!workspace || misaligned8(workspace) ||
       workspace_bytes < shard_workspace_bytes<Order>(n_total, lo, n_local, slabs_local, slabs_remote))
     return NBD_E_WORKSPACE;
-  const HShardPlanF64 p = plan_hshard_f64(n_total, lo, n_local, slabs_local, slabs_remote);
+  const HShardPlan p = plan_hshard_f64(n_total, lo, n_local, slabs_local, slabs_remote);
   double* slabs = static_cast<double*>(workspace);
   hipStream_t st = (hipStream_t)stream;
   if (p.slabs_remote > 0) {
@@ -228,8 +162,9 @@ int nbd_hermite_shard_predict_f64(const double* pos, const double* vel, const do
   if (n_local < 0 || send_rows < nbd_posm_padded_len(n_local) || (!acc != !jerk)) return NBD_E_BADARG;
   if (send_rows == 0) return 0;
   if (!send || misaligned32(send) || (n_local > 0 && (!pos || !vel || !mass))) return NBD_E_BADARG;
-  shard_predict_f64_kernel<<<ceil_div(send_rows, 256), 256, 0, (hipStream_t)stream>>>(
-      pos, vel, acc, jerk, mass, n_local, send_rows, hermite_step_constants<double>(dt), reinterpret_cast<d4*>(send));
+  d4* s = reinterpret_cast<d4*>(send);
+  hermite_predict_kernel<double, Order4::kArr><<<ceil_div(send_rows, 256), 256, 0, (hipStream_t)stream>>>(
+      pos, vel, acc, jerk, mass, n_local, send_rows, hermite_step_constants<double>(dt), s, s + 1);
   return launch_status();
 }
 
@@ -240,9 +175,9 @@ int nbd_hermite6_shard_predict_f64(const double* pos, const double* vel, const d
   if ((!jerk != !snap) || (!jerk != !crackle) || (jerk && !acc)) return NBD_E_BADARG;
   if (send_rows == 0) return 0;
   if (!send || misaligned32(send) || (n_local > 0 && (!pos || !vel || !mass))) return NBD_E_BADARG;
-  shard6_predict_f64_kernel<<<ceil_div(send_rows, 256), 256, 0, (hipStream_t)stream>>>(
-      pos, vel, acc, jerk, snap, crackle, mass, n_local, send_rows, hermite6_step_constants(dt),
-      reinterpret_cast<d4*>(send));
+  d4* s = reinterpret_cast<d4*>(send);
+  hermite6_predict_kernel<Order6::kArr><<<ceil_div(send_rows, 256), 256, 0, (hipStream_t)stream>>>(
+      pos, vel, acc, jerk, snap, crackle, mass, n_local, send_rows, hermite6_step_constants(dt), s, s + 1, s + 2);
   return launch_status();
 }
 
@@ -265,9 +200,9 @@ int nbd_hermite_shard_force_remote_f64(const double* all, int n_total, const dou
   return shard_force_remote<Order4>(
       all, n_total, send, n_local, lo, softening_sq, state_ok, workspace, workspace_bytes, slabs_local, slabs_remote,
       stream, [=](const double* slabs, int n_slabs, hipStream_t st) {
-        shard_finish_f64_kernel<<<ceil_div(n_local, HermiteFmt<double>::kSumRows), 256, 0, st>>>(
+        hermite_correct_kernel<double, false><<<ceil_div(n_local, HermiteFmt<double>::kSumRows), 256, 0, st>>>(
             slabs, n_slabs, n_local, g_const, hermite_step_constants<double>(dt), pos, vel, acc_in, jerk_in, acc_out,
-            jerk_out);
+            jerk_out, nullptr, nullptr);
       });
 }
 
@@ -282,9 +217,9 @@ int nbd_hermite6_shard_force_remote_f64(const double* all, int n_total, const do
   return shard_force_remote<Order6>(
       all, n_total, send, n_local, lo, softening_sq, state_ok, workspace, workspace_bytes, slabs_local, slabs_remote,
       stream, [=](const double* slabs, int n_slabs, hipStream_t st) {
-        shard6_finish_f64_kernel<<<ceil_div(n_local, 256), 256, 0, st>>>(
+        hermite6_finish_kernel<false><<<ceil_div(n_local, 256), 256, 0, st>>>(
             slabs, n_slabs, n_local, g_const, hermite6_step_constants(dt), pos, vel, acc_in, jerk_in, snap_in, acc_out,
-            jerk_out, snap_out, crackle_out);
+            jerk_out, snap_out, crackle_out, nullptr, nullptr);
       });
 }
 

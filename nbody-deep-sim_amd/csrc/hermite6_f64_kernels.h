@@ -2,8 +2,11 @@
 // direct_batch_hermite_f64.hip: many independent systems, shared timestep per system; direct_hermite_shard_f64.hip: one
 // rank's bodies of a range partition, beside the 4th order; direct_hermite_block_f64.hip: an active list of targets,
 // block timesteps, each body with its own step constants): the pair functor of the
-// acceleration + jerk + snap evaluation (AccelJerkSnapPair), the step constants (Hermite6Step, hermite6_step_constants)
-// and the per-row bodies of the predictor and of the finishing kernel (hermite6_predict_row, hermite6_finish_row). As in
+// acceleration + jerk + snap evaluation (AccelJerkSnapPair), the step constants (Hermite6Step, hermite6_step_constants),
+// the per-row bodies of the predictor and of the finishing kernel (hermite6_predict_row, hermite6_finish_row) and the
+// shared step's two O(N) kernels over them: hermite6_predict_kernel<SS> (SS: the row stride of the packed rows) and
+// hermite6_finish_kernel<POSD> (POSD: whether it stores the packed row), launched as <1> and <true> by
+// direct_hermite_f64.hip and as <3> (send, send + 1, send + 2) and <false> by direct_hermite_shard_f64.hip. As in
 // hermite_f64_kernels.h there is one copy of every rounded operation: a scene of a batch has the one-system step's bits
 // because the kernels of both units are a prologue and a call of the same inlined code.
 // The definitions sit in an anonymous namespace: every translation unit that includes this file gets its own inlined copies.
@@ -176,6 +179,45 @@ __device__ __forceinline__ Hermite6Ends hermite6_finish_row(const double* __rest
     if (pos) posd[r] = d4{x1[0], x1[1], x1[2], mass[b]};
   }
   return e;
+}
+
+// The shared step's two O(N) kernels (direct_hermite_f64.hip; direct_hermite_shard_f64.hip launches the same two on a
+// rank's own bodies).
+// posd = {x_p, m}, veld = {v_p, 0}, accd = {a_p, 0} for rows [0, n_pad), zero rows behind n: hermite6_predict_row of every
+// body. SS: the d4 between consecutive bodies of each of the three, hermite_predict_kernel's SS. 1: three arrays; 3: the send
+// buffer of a range-sharded rank, one array of rows {x_p, m | v_p, 0 | a_p, 0} (send, send + 1, send + 2).
+template <int SS = 1>
+__global__ __launch_bounds__(256) void hermite6_predict_kernel(const double* __restrict__ pos,
+                                                               const double* __restrict__ vel,
+                                                               const double* __restrict__ acc,
+                                                               const double* __restrict__ jerk,
+                                                               const double* __restrict__ snap,
+                                                               const double* __restrict__ crackle,
+                                                               const double* __restrict__ mass, int n, int n_pad,
+                                                               Hermite6Step h, d4* __restrict__ posd,
+                                                               d4* __restrict__ veld, d4* __restrict__ accd) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (size_t)n_pad) return;
+  d4 pm = {0.0, 0.0, 0.0, 0.0}, vp = pm, ap = pm;
+  if (i < (size_t)n) hermite6_predict_row(pos, vel, acc, jerk, snap, crackle, mass, i, h, pm, vp, ap);
+  posd[SS * i] = pm;
+  veld[SS * i] = vp;
+  accd[SS * i] = ap;
+}
+
+// One thread per body: hermite6_finish_row<POSD> of the body's row of double[n_slabs][9][n] (pos == nullptr: a1, j1, s1
+// only, the force on its own).
+template <bool POSD = true>
+__global__ __launch_bounds__(256) void hermite6_finish_kernel(const double* __restrict__ slabs, int n_slabs, int n,
+                                                              double g, Hermite6Step h, double* pos, double* vel,
+                                                              const double* acc_in, const double* jerk_in,
+                                                              const double* snap_in, double* acc_out, double* jerk_out,
+                                                              double* snap_out, double* crackle_out,
+                                                              const double* __restrict__ mass, d4* __restrict__ posd) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (size_t)n) return;
+  hermite6_finish_row<POSD>(slabs, n_slabs, (size_t)n, i, i, g, h, pos, vel, acc_in, jerk_in, snap_in, acc_out, jerk_out,
+                            snap_out, crackle_out, mass, posd, i);
 }
 
 }  // namespace

@@ -423,17 +423,15 @@ inline F64Plan plan_f64(int n, int n_tgt) {
 inline F64Plan plan_f64(int n) { return plan_f64(n, n); }
 
 // The geometry of a range-sharded rank's two force launches (direct_hermite_shard_f64.hip, the same for the 4th and the
-// 6th order). The local block is plan_f64(n_local); the remote block has the same target
+// 6th order) as an HShardPlan (hermite_kernels.h). The local block is plan_f64(n_local); the remote block has the same target
 // groups and slabs_f64's count for its logical chunks (none, and no launch, where the rank owns every body). An explicit
 // slab count in [1, kMaxSlabs] replaces either. The view's chunk counts come from n_total: no logical chunk maps behind
 // the padded length of the gathered array.
-struct HShardPlanF64 { int groups, slabs_local, chunks_local, slabs_remote, chunks_remote; SrcView remote; };
-
 inline bool slab_arg_ok(int slabs) { return slabs >= 0 && slabs <= kMaxSlabs; }
 
 // n_local > 0; slabs_local, slabs_remote: 0 = the plan's
-inline HShardPlanF64 plan_hshard_f64(int n_total, int lo, int n_local, int slabs_local, int slabs_remote) {
-  HShardPlanF64 p;
+inline HShardPlan plan_hshard_f64(int n_total, int lo, int n_local, int slabs_local, int slabs_remote) {
+  HShardPlan p;
   const F64Plan local = plan_f64(n_local);
   p.groups = local.groups;
   p.chunks_local = local.n_chunks;

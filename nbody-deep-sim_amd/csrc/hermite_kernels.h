@@ -1,6 +1,7 @@
 // hermite_kernels.h -- everything the Hermite translation units share (direct_hermite.hip: all targets, shared timestep;
 // direct_hermite_block.hip: an active list of targets, block timesteps; direct_batch_hermite.hip: many independent
-// systems, shared timestep per system; direct_hermite_shard.hip: one rank's bodies of a range partition):
+// systems, shared timestep per system; direct_hermite_shard.hip: one rank's bodies of a range partition; and their
+// float64 forms):
 //   - the acceleration-plus-jerk wave body (accel_jerk_body: target loads, LDS-DMA chunk walk, pair loop, four-wave
 //     reduction, store; its compile-time parameters also give direct_hermite_shard.hip's range-sharded blocks: targets
 //     apart from the sources, 8-float rows, a skipped source range), the split of the chunks over the waves (chunk_split
@@ -8,13 +9,18 @@
 //     calls the body (Group128: the workgroup's two targets per lane, the wave's place in the split, the slab destination);
 //   - the O(N) stages, templates of the scalar type T of the state (float; double for direct_hermite_f64.hip and
 //     direct_hermite_block_f64.hip): what the format fixes (HermiteFmt<T>: the packed row, the rows per workgroup of a
-//     finishing launch), the step constants (hermite_step_constants; hermite_dt for fp32), the predictor of one component
-//     and of one body (hermite_predict, hermite_predict_row), the fixed-order slab sum (hermite_slab_sum: the 4-wave
-//     scheme for float, slab_order_sum for double -- two orders, each format keeps its own), the corrector of one
-//     component and of one body (hermite_correct, hermite_correct_row), and the shared step's two O(N) kernels
-//     (hermite_predict_kernel<T>, hermite_correct_kernel<T>), which direct_hermite.hip and direct_hermite_f64.hip
-//     instantiate;
-//   - the launch plan of a force launch (JerkPlan, plan_jerk).
+//     finishing launch), the step constants (hermite_step_constants; hermite_dt for fp32; HermiteStepRow: their rows in
+//     a per-scene table), the predictor of one component and of one body (hermite_predict, hermite_predict_row), the
+//     fixed-order slab sum (hermite_slab_sum: the 4-wave scheme for float, slab_order_sum for double -- two orders, each
+//     format keeps its own), the corrector of one component and of one body (hermite_correct, hermite_correct_row), and
+//     the shared step's two O(N) kernels: hermite_predict_kernel<T, SS> (SS: the row stride of the packed rows) and
+//     hermite_correct_kernel<T, POSM> (POSM: whether it stores the packed row). direct_hermite.hip and
+//     direct_hermite_f64.hip instantiate <T, 1> and <T, true>; the range-sharded units, direct_hermite_shard.hip and
+//     direct_hermite_shard_f64.hip, launch the same two on a rank's own bodies as <T, 2> (posm = send, velp = send + 1)
+//     and <T, false>, and have no O(N) kernel of their own. The batched units' two (hermite_batch_kernels.h) are these
+//     with a scene's prologue;
+//   - the launch plan of a force launch (JerkPlan, plan_jerk) and of a range-sharded rank's two (HShardPlan,
+//     hshard_plan_out).
 // A kernel of one of the units is a prologue that says which targets, which chunks, which rows and which constants, and
 // calls of these: a scene of a batch, or a block step at level 0, is bit-identical to the shared-timestep step because
 // there is one copy of every rounded operation, in either format, not because copies are kept alike.
@@ -310,12 +316,30 @@ inline JerkPlan plan_jerk(int n, int n_tgt) {
   return p;
 }
 
+// The geometry of a range-sharded rank's two force launches, in either format (direct_hermite_shard.hip: plan_hshard;
+// hermite_f64_kernels.h: plan_hshard_f64 -- two plan functions, which choose their slab counts differently), and what a
+// plan entry writes out of it.
+struct HShardPlan { int groups, slabs_local, chunks_local, slabs_remote, chunks_remote; SrcView remote; };
+
+inline void hshard_plan_out(const HShardPlan& p, int* slabs_local, int* chunks_per_wave_local, int* slabs_remote,
+                            int* chunks_per_wave_remote) {
+  if (slabs_local) *slabs_local = p.slabs_local;
+  if (chunks_per_wave_local) *chunks_per_wave_local = ceil_div(p.chunks_local, p.slabs_local * kWaves);
+  if (slabs_remote) *slabs_remote = p.slabs_remote;
+  if (chunks_per_wave_remote)
+    *chunks_per_wave_remote = p.slabs_remote ? ceil_div(p.chunks_remote, p.slabs_remote * kWaves) : 0;
+}
+
 // fp32 step constants, each formed in double and rounded once. On the device too: a block-timestep body forms them from
 // its own fp64 step, so one whose step is the whole interval gets the shared step's bits.
 // (T = double, direct_hermite_f64.hip and direct_hermite_block_f64.hip: the same five doubles, not rounded again.)
 template <class T>
 struct HermiteStep { T dt, dt_half, dt2_half, dt3_sixth, dt2_twelfth; };
 using HermiteDt = HermiteStep<float>;
+
+// ... as the rows of a per-scene table T[kRows][S] (the batched units: field k of scene s at step[k * S + s])
+struct HermiteStepRow { enum { kDt, kDtHalf, kDt2Half, kDt3Sixth, kDt2Twelfth, kRows }; };
+static_assert(sizeof(HermiteStep<double>) == HermiteStepRow::kRows * sizeof(double), "one row per field, in its order");
 
 template <class T>
 __host__ __device__ inline HermiteStep<T> hermite_step_constants(double dt) {
@@ -387,7 +411,9 @@ __device__ __forceinline__ PosVel3<T> hermite_predict_row(const T* __restrict__ 
 }
 
 // posm = {x_p, m}, velp = {v_p, 0} for rows [0, n_pad) (zero rows behind n). acc == nullptr: plain pack (x, v).
-template <class T>
+// SS: the rows between consecutive bodies of posm and of velp, accel_jerk_body's SS. 1: two arrays; 2: the send buffer of
+// a range-sharded rank, one array of rows {x_p, m | v_p, 0} (posm = send, velp = send + 1).
+template <class T, int SS = 1>
 __global__ __launch_bounds__(256) void hermite_predict_kernel(const T* __restrict__ pos, const T* __restrict__ vel,
                                                               const T* __restrict__ acc, const T* __restrict__ jerk,
                                                               const T* __restrict__ mass, int n, int n_pad,
@@ -402,8 +428,8 @@ __global__ __launch_bounds__(256) void hermite_predict_kernel(const T* __restric
     pm = hermite_row(p.x, mass[i]);
     vp = hermite_row(p.v, (T)0);
   }
-  posm[i] = pm;
-  velp[i] = vp;
+  posm[SS * i] = pm;
+  velp[SS * i] = vp;
 }
 
 // sum[k] = slab 0 + slab 1 + ... of row `row`, component k < K, of slabs = double[n_slabs][K][stride], in slab order:
@@ -506,8 +532,9 @@ __device__ __forceinline__ void hermite_store_force(T* acc, T* jerk, const size_
 
 // One workgroup per HermiteFmt<T>::kSumRows consecutive bodies: a1, j1 = hermite_slab_sum of the body's row. pos ==
 // nullptr: write a1, j1 only (the force on its own). Else hermite_correct_row, then a1, j1 and posm = {x1, m} (energies
-// after the step need no extra pack).
-template <class T>
+// after the step need no extra pack). POSM = false (a range-sharded rank: its packed rows are rebuilt by the next
+// predictor): posm and mass are not used.
+template <class T, bool POSM = true>
 __global__ __launch_bounds__(256) void hermite_correct_kernel(const T* __restrict__ slabs, int n_slabs, int n, T g,
                                                               HermiteStep<T> h, T* pos, T* vel, const T* acc_in,
                                                               const T* jerk_in, T* acc_out, T* jerk_out,
@@ -518,7 +545,7 @@ __global__ __launch_bounds__(256) void hermite_correct_kernel(const T* __restric
   if (!hermite_slab_sum(slabs, n_slabs, n, i, i < (size_t)n, g, a1, j1)) return;
   if (pos) {
     const Corrected<T> c = hermite_correct_row(pos, vel, acc_in, jerk_in, i, a1, j1, h.dt_half, h.dt2_twelfth);
-    posm[i] = hermite_row(c.x1, mass[i]);
+    if constexpr (POSM) posm[i] = hermite_row(c.x1, mass[i]);
   }
   hermite_store_force(acc_out, jerk_out, i, a1, j1);
 }

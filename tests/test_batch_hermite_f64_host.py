@@ -245,7 +245,8 @@ def test_evaluate_kernel_has_no_spills_no_scratch_and_the_32_kib_stage(asm):
     assert not re.search(r"\batomic", body)
 
 
-@pytest.mark.parametrize("kernel", ["batch_predict_f64_kernel", "batch_correct_f64_kernel", "batch_energy_f64_kernel",
+@pytest.mark.parametrize("kernel", ["batch_hermite_predict_kernelIdE", "batch_hermite_correct_kernelIdE",
+                                    "batch_energy_f64_kernel",
                                     "batch_potential_f64_kernel", "batch_energy_finish_f64_kernel",
                                     "batch_potential_finish_f64_kernel", "batch_invariants_state_f64_kernel"])
 def test_other_kernels_have_no_scratch(asm, kernel):

@@ -180,6 +180,22 @@ def test_no_float_atomics_and_one_copy_of_the_wave_body(asm):
     for what in ("PosVel3<T> hermite_predict_row(", "Corrected<T> hermite_correct_row(", "void slab_order_sum(",
                  "void hermite_predict_kernel(", "void hermite_correct_kernel(", "struct HermiteFmt<double>"):
         assert [f for f, text in units.items() if what in text] == ["hermite_kernels.h"], what
+    # ... which the range-sharded units launch too (with a row stride, without the packed store): their only kernel is
+    # the pair kernel, and one struct describes a rank's plan in both formats
+    for f in ("direct_hermite_shard.hip", "direct_hermite_shard_f64.hip"):
+        assert units[f].count("__global__") == 1, f
+    assert sum(text.count("struct HShardPlan") for text in units.values()) == 1
+    # the 6th order's two O(N) kernels sit beside their row functions, for the un-sharded and the sharded unit
+    for what in ("void hermite6_predict_kernel(", "void hermite6_finish_kernel("):
+        assert [f for f, text in units.items() if what in text] == ["hermite6_f64_kernels.h"], what
+    # the batched shared-step units: one templated predictor and one corrector for both formats, and no shard or batch
+    # unit calls the row predictor from a kernel of its own
+    for what in ("void batch_hermite_predict_kernel(", "void batch_hermite_correct_kernel("):
+        assert [f for f, text in units.items() if what in text] == ["hermite_batch_kernels.h"], what
+        assert units["hermite_batch_kernels.h"].count(what) == 1, what
+    for f in ("direct_hermite_shard.hip", "direct_hermite_shard_f64.hip", "direct_batch_hermite.hip",
+              "direct_batch_hermite_f64.hip"):
+        assert "hermite_predict_row(" not in units[f], f
     # the two orders as types and the check of an order's packed arrays: the order header's, for every float64 unit
     for what in ("struct Order4", "struct Order6", "bool bad_rows("):
         assert [f for f, text in units.items() if what in text] == ["hermite_orders_f64.h"], what

@@ -373,8 +373,9 @@ def test_pair_kernels_resources_and_instructions(asm, kernel):
     assert not re.search(r"\b(global|flat|ds|buffer)_atomic", body)
 
 
-@pytest.mark.parametrize("kernel", ["shard6_predict_f64_kernel", "shard6_finish_f64_kernel"])
+@pytest.mark.parametrize("kernel", ["hermite6_predict_kernelILi3E", "hermite6_finish_kernelILb0E"])
 def test_row_kernels_have_no_lds_and_no_spills(asm, kernel):
+    """hermite6_predict_kernel<3> (the send buffer's three-piece stride) and hermite6_finish_kernel<false> (no packed row)"""
     meta, desc, body = _kernel(asm, kernel)
     _no_scratch_no_spills(meta)
     assert int(re.search(r"\.amdhsa_group_segment_fixed_size\s+(\d+)", desc).group(1)) == 0

@@ -361,12 +361,13 @@ def _no_scratch_no_spills(meta):
         assert int(re.search(r"\." + key + r":\s+(\d+)", meta).group(1)) == 0, key
 
 
-@pytest.mark.parametrize("kernel,lds", [("shard_predict_f64_kernel", 0), ("shard_finish_f64_kernel", 0),
+@pytest.mark.parametrize("kernel,lds", [("hermite_predict_kernelIdLi2E", 0), ("hermite_correct_kernelIdLb0E", 0),
                                         ("shard_pair_f64_kernelINS_6Order4ELb0E", 32768),
                                         ("shard_pair_f64_kernelINS_6Order4ELb1E", 32768)])
 def test_new_kernels_have_no_scratch_no_spills_and_no_fp32(asm, kernel, lds):
-    """predict, finish, and the local (RANGE = false) and remote (RANGE = true) 4th-order force kernels: the force kernels
-    keep the un-sharded kernels' 32 KiB of LDS, the O(N) kernels use none."""
+    """predict (hermite_predict_kernel<double, 2>: the send buffer's two-piece stride), finish
+    (hermite_correct_kernel<double, false>: no packed row), and the local (RANGE = false) and remote (RANGE = true)
+    4th-order force kernels: the force kernels keep the un-sharded kernels' 32 KiB of LDS, the O(N) kernels use none."""
     meta, desc, body = _kernel(asm, kernel)
     _no_scratch_no_spills(meta)
     got = int(re.search(r"\.amdhsa_group_segment_fixed_size\s+(\d+)", desc).group(1))
