@@ -1529,6 +1529,18 @@ int64_t nbd_csv_format_state(char* out, size_t cap, const char* prefix, size_t p
  *   nbd_tree_accel_f32        the walk over a workspace nbd_tree_build_f32 filled for the same n; acc_out (n,3) in the
  *                             CALLER's order; counters_out NULL or 2 x uint64 on the device = {accepted cells, rejected
  *                             level-0 nodes} summed over the target groups. theta < 0 (or NaN) is NBD_E_BADARG.
+ * The potential over the same terms: an accepted node adds
+ *     phi_cell = -( M u + 1/2 (r^T Q r) u^5 )           (quadrupole == 0: -M u),
+ * whose gradient is the force term above (d u / d x = u^3 r: -grad phi_cell = M u^3 r - (Q r) u^5 + 2.5 (r^T Q r) u^7 r),
+ * and a body j of a rejected level-0 node adds -m_j (|d|^2 + softening_sq)^(-1/2). j == i is excluded by index (its term
+ * would be m_i / eps, not 0), so a coincident distinct body is kept and gives -inf at softening 0; the zero-mass
+ * padding rows behind the last body are excluded too. Pair and cell terms are fp32 and an fp32 sum holds at most 8 of
+ * them (the bodies of one level-0 node, 8 consecutive cells); every sum above that is fp64 in a fixed order, and
+ * -g_const multiplies the finished sum in fp64. The walk, its lists and its counters are nbd_tree_accel_f32's.
+ *   nbd_tree_potential_f32        phi_out (n,) float64 in the CALLER's order; the other arguments, checks and return
+ *                                 codes as nbd_tree_accel_f32 (phi_out NULL is NBD_E_BADARG)
+ *   nbd_tree_accel_potential_f32  both from one walk: acc_out bit for bit nbd_tree_accel_f32's, phi_out bit for bit
+ *                                 nbd_tree_potential_f32's, the same counters
  * n = 0 is a no-op. No allocation, memset or synchronisation inside; bit-identical from run to run. */
 int nbd_tree_plan(int n, int* levels, int* nodes_total);
 size_t nbd_tree_workspace_bytes(int n);
@@ -1536,6 +1548,11 @@ int nbd_tree_build_f32(const float* pos, const float* mass, int n, int* order_ou
                        size_t workspace_bytes, nbd_stream_t stream);
 int nbd_tree_accel_f32(const void* workspace, int n, float theta, float softening_sq, float g_const, int quadrupole,
                        float* acc_out, unsigned long long* counters_out, nbd_stream_t stream);
+int nbd_tree_potential_f32(const void* workspace, int n, float theta, float softening_sq, float g_const, int quadrupole,
+                           double* phi_out, unsigned long long* counters_out, nbd_stream_t stream);
+int nbd_tree_accel_potential_f32(const void* workspace, int n, float theta, float softening_sq, float g_const,
+                                 int quadrupole, float* acc_out, double* phi_out, unsigned long long* counters_out,
+                                 nbd_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -30,6 +30,13 @@
 //           outer sums compensated) -- bit-identical from run to run.
 //           The pair term is the direct kernel's: exact differences, explicit FMAs, v_rsq_f32; j == i is excluded by
 //           index, so softening 0 and coincident bodies behave as nbd_accel_f32 does.
+//   phi     the same walk sums the potential whose gradient the force above is, over the same cells and bodies: a body adds
+//           m s (one FMA, s the masked rsq of the force), a cell M u + 1/2 (r.Qr) u^5 (two, u and r.Qr in registers). fp32
+//           sums stop at 8 terms -- the bodies of a level-0 node, 8 consecutive cells of a list pass -- and everything
+//           above them is fp64 in a fixed order: the lane's running sum, the 8 partial sums of a split group (a slab of
+//           doubles [split][n] behind every other region of the workspace), the factor -G. The self term (m_i / eps, not 0
+//           as in the force) is excluded by the same index mask, the padding rows too. ACC / PHI choose what a walk
+//           accumulates at compile time; the acc-only instantiations are the force kernel unchanged.
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 #include <math.h>
@@ -86,7 +93,7 @@ size_t sort_temp_bytes(int n) {
 }
 
 struct Layout {
-  size_t box, keys_in, keys_out, vals_in, order, posm, nodes, mom, aabb, gcnt, slabs, cub, cub_bytes, total;
+  size_t box, keys_in, keys_out, vals_in, order, posm, nodes, mom, aabb, gcnt, slabs, cub, cub_bytes, phi_slabs, total;
 };
 
 inline Layout layout(int n, const Levels& L) {
@@ -104,6 +111,7 @@ inline Layout layout(int n, const Levels& L) {
   w.slabs = take(L.split > 1 ? (size_t)L.split * n * 3 * 4 : 0);
   w.cub_bytes = sort_temp_bytes(n);
   w.cub = take(w.cub_bytes);
+  w.phi_slabs = take(L.split > 1 ? (size_t)L.split * n * 8 : 0);      // last: every offset above is the force's own
   w.total = o;
   return w;
 }
@@ -295,6 +303,13 @@ struct WalkArgs {
   int count[kMaxLevels], off[kMaxLevels];
   float theta2, eps2, g;
 };
+// what a walk that sums the potential takes (the acc-only walk keeps WalkArgs: its kernel arguments do not move)
+struct PhiWalkArgs : WalkArgs {
+  double* phi_out;         // (n,) in the caller's order (written here when split == 1)
+  double* phi_slabs;       // [split][n] partial sums in tree order (split > 1)
+};
+template <bool PHI> struct WalkArgsOf { typedef WalkArgs type; };
+template <> struct WalkArgsOf<true> { typedef PhiWalkArgs type; };
 
 __device__ __forceinline__ int lanes_below(unsigned long long mask) {
   return __builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
@@ -318,8 +333,8 @@ __device__ __forceinline__ void add_comp(float& tot, float& comp, float s) {
 
 constexpr int kWalkFixedLds = (3 * kListCap + 64 * kLeaf) * 16 + kListCap * 4 + 2 * kMaxLevels * 4;
 
-template <bool QUAD>
-__global__ __launch_bounds__(64) void tree_walk_kernel(const WalkArgs a) {
+template <bool QUAD, bool ACC, bool PHI>
+__global__ __launch_bounds__(64) void tree_walk_kernel(const typename WalkArgsOf<PHI>::type a) {
   extern __shared__ f4 lds[];
   f4* cells = lds;                                   // [kListCap][3]
   f4* stage = cells + 3 * kListCap;                  // [64][kLeaf] bodies of one pass of the level-0 list
@@ -343,12 +358,13 @@ __global__ __launch_bounds__(64) void tree_walk_kernel(const WalkArgs a) {
   __syncthreads();
 
   float ax = 0.f, ay = 0.f, az = 0.f, cx = 0.f, cy = 0.f, cz = 0.f;      // sums and their compensation
+  double phi = 0.0;                                                      // sum of m s and of M u + 1/2 (r.Qr) u^5
   const float eps2 = a.eps2;
   int sp = 1, nc = 0, nl = 0;
   unsigned cells_total = 0, leaves_total = 0;
 
   auto flush_cells = [&](int count) {
-    float sx = 0.f, sy = 0.f, sz = 0.f;
+    float sx = 0.f, sy = 0.f, sz = 0.f, sphi = 0.f;
 #pragma unroll 4
     for (int e = 0; e < count; ++e) {
       const f4 v0 = cells[3 * e], v1 = cells[3 * e + 1];
@@ -367,11 +383,17 @@ __global__ __launch_bounds__(64) void tree_walk_kernel(const WalkArgs a) {
         const float rqr = __builtin_fmaf(rz, qz, __builtin_fmaf(ry, qy, rx * qx));
         const float u5 = u3 * u2, u7 = u5 * u2;
         w = __builtin_fmaf(2.5f * rqr, u7, w);
-        sx = __builtin_fmaf(-u5, qx, sx); sy = __builtin_fmaf(-u5, qy, sy); sz = __builtin_fmaf(-u5, qz, sz);
+        if (ACC) { sx = __builtin_fmaf(-u5, qx, sx); sy = __builtin_fmaf(-u5, qy, sy); sz = __builtin_fmaf(-u5, qz, sz); }
+        if (PHI) sphi = __builtin_fmaf(0.5f * rqr, u5, sphi);
       }
-      sx = __builtin_fmaf(w, rx, sx); sy = __builtin_fmaf(w, ry, sy); sz = __builtin_fmaf(w, rz, sz);
+      if (ACC) { sx = __builtin_fmaf(w, rx, sx); sy = __builtin_fmaf(w, ry, sy); sz = __builtin_fmaf(w, rz, sz); }
+      if (PHI) {
+        sphi = __builtin_fmaf(v1.x, u, sphi);
+        if ((e & 7) == 7) { phi += (double)sphi; sphi = 0.f; }   // the fp32 sum ends after 8 cells
+      }
     }
-    add_comp(ax, cx, sx); add_comp(ay, cy, sy); add_comp(az, cz, sz);
+    if (ACC) { add_comp(ax, cx, sx); add_comp(ay, cy, sy); add_comp(az, cz, sz); }
+    if (PHI) phi += (double)sphi;
   };
 
   auto flush_leaves = [&](int count) {
@@ -386,7 +408,7 @@ __global__ __launch_bounds__(64) void tree_walk_kernel(const WalkArgs a) {
       __syncthreads();
       for (int e = 0; e < cnt; ++e) {
         const int j0 = __builtin_amdgcn_readfirstlane(leaf[base + e]) * kLeaf;
-        float nx = 0.f, ny = 0.f, nz = 0.f;
+        float nx = 0.f, ny = 0.f, nz = 0.f, nphi = 0.f;
 #pragma unroll
         for (int k = 0; k < kLeaf; ++k) {
           const f4 p = stage[e * kLeaf + k];
@@ -396,10 +418,14 @@ __global__ __launch_bounds__(64) void tree_walk_kernel(const WalkArgs a) {
           r2 = __builtin_fmaf(dz, dz, r2);
           float s = __builtin_amdgcn_rsqf(r2);
           s = (j0 + k != i && j0 + k < a.n) ? s : 0.f;        // j == i by index; the padding behind the last body
-          const float w = p.w * ((s * s) * s);
-          nx = __builtin_fmaf(w, dx, nx); ny = __builtin_fmaf(w, dy, ny); nz = __builtin_fmaf(w, dz, nz);
+          if (ACC) {
+            const float w = p.w * ((s * s) * s);
+            nx = __builtin_fmaf(w, dx, nx); ny = __builtin_fmaf(w, dy, ny); nz = __builtin_fmaf(w, dz, nz);
+          }
+          if (PHI) nphi = __builtin_fmaf(p.w, s, nphi);
         }
-        add_comp(ax, cx, nx); add_comp(ay, cy, ny); add_comp(az, cz, nz);
+        if (ACC) { add_comp(ax, cx, nx); add_comp(ay, cy, ny); add_comp(az, cz, nz); }
+        if (PHI) phi += (double)nphi;
       }
       __syncthreads();
     }
@@ -464,7 +490,7 @@ __global__ __launch_bounds__(64) void tree_walk_kernel(const WalkArgs a) {
   flush_cells(nc);
   flush_leaves(nl);
 
-  if (valid) {
+  if (ACC && valid) {
     if (a.split == 1) {
       const size_t o = (size_t)a.order[i] * 3;
       a.acc_out[o] = a.g * ax; a.acc_out[o + 1] = a.g * ay; a.acc_out[o + 2] = a.g * az;
@@ -472,6 +498,10 @@ __global__ __launch_bounds__(64) void tree_walk_kernel(const WalkArgs a) {
       const size_t o = ((size_t)part * a.n + i) * 3;
       a.slabs[o] = ax; a.slabs[o + 1] = ay; a.slabs[o + 2] = az;
     }
+  }
+  if constexpr (PHI) if (valid) {
+    if (a.split == 1) a.phi_out[a.order[i]] = 0.0 - (double)a.g * phi;
+    else a.phi_slabs[(size_t)part * a.n + i] = phi;
   }
   if (lane == 0) {
     const size_t o = ((size_t)part * gridDim.x + blockIdx.x) * 2;
@@ -491,6 +521,17 @@ __global__ __launch_bounds__(256) void slab_sum_kernel(const float* __restrict__
   for (int c = 0; c < 3; ++c) acc_out[o + c] = g * s[c];
 }
 
+// phi_out[order[i]] = -g * (slab 0 + slab 1 + ...)[i], in fp64: the waves of a group in their fixed order
+__global__ __launch_bounds__(256) void phi_slab_sum_kernel(const double* __restrict__ slabs, int split, int n,
+                                                           const int* __restrict__ order, double g,
+                                                           double* __restrict__ phi_out) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  double s = 0.0;
+  for (int w = 0; w < split; ++w) s += slabs[(size_t)w * n + i];
+  phi_out[order[i]] = 0.0 - g * s;
+}
+
 // counters[0..1] = the per-group pairs summed in a fixed order
 __global__ __launch_bounds__(256) void counter_kernel(const unsigned* __restrict__ gcnt, int groups,
                                                       unsigned long long* __restrict__ counters) {
@@ -507,6 +548,45 @@ __global__ __launch_bounds__(256) void counter_kernel(const unsigned* __restrict
     __syncthreads();
   }
   if (threadIdx.x == 0) { counters[0] = red[0][0]; counters[1] = red[1][0]; }
+}
+
+// One walk over a built workspace: the acceleration (acc_out), the potential (phi_out) or both.
+template <bool ACC, bool PHI>
+int tree_walk(const void* workspace, int n, float theta, float softening_sq, float g_const, int quadrupole,
+              float* acc_out, double* phi_out, unsigned long long* counters_out, nbd_stream_t stream) {
+  if (n < 0 || !(theta >= 0.f) || (n > 0 && (!workspace || (ACC && !acc_out) || (PHI && !phi_out)))) return NBD_E_BADARG;
+  if (n == 0) return 0;
+  if (n > kMaxBodies) return NBD_E_UNSUPPORTED;
+  if (reinterpret_cast<uintptr_t>(workspace) & 255) return NBD_E_BADARG;
+  const Levels L = plan_levels(n);
+  const Layout w = layout(n, L);
+  hipStream_t st = (hipStream_t)stream;
+  char* base = static_cast<char*>(const_cast<void*>(workspace));
+  typename WalkArgsOf<PHI>::type a = {};
+  a.posm = reinterpret_cast<const f4*>(base + w.posm);
+  a.nodes = reinterpret_cast<const f4*>(base + w.nodes);
+  a.order = reinterpret_cast<const int*>(base + w.order);
+  a.acc_out = acc_out;
+  a.gcnt = reinterpret_cast<unsigned*>(base + w.gcnt);
+  a.slabs = reinterpret_cast<float*>(base + w.slabs);
+  if constexpr (PHI) { a.phi_out = phi_out; a.phi_slabs = reinterpret_cast<double*>(base + w.phi_slabs); }
+  a.n = n; a.levels = L.levels; a.stack_cap = kStackPerLevel * L.levels;
+  a.split = L.split; a.start_level = L.start_level;
+  for (int l = 0; l < kMaxLevels; ++l) { a.count[l] = L.count[l]; a.off[l] = L.off[l]; }
+  a.theta2 = theta * theta; a.eps2 = softening_sq; a.g = g_const;
+  const int groups = pad64(n) / kGroup;
+  const size_t lds_bytes = kWalkFixedLds + (size_t)a.stack_cap * 4;
+  const dim3 grid(groups, L.split);
+  if (quadrupole) tree_walk_kernel<true, ACC, PHI><<<grid, 64, lds_bytes, st>>>(a);
+  else tree_walk_kernel<false, ACC, PHI><<<grid, 64, lds_bytes, st>>>(a);
+  if (L.split > 1) {
+    const int blocks = (n + 255) / 256;
+    if (ACC) slab_sum_kernel<<<blocks, 256, 0, st>>>(a.slabs, L.split, n, a.order, g_const, acc_out);
+    if constexpr (PHI)
+      phi_slab_sum_kernel<<<blocks, 256, 0, st>>>(a.phi_slabs, L.split, n, a.order, (double)g_const, phi_out);
+  }
+  if (counters_out) counter_kernel<<<1, 256, 0, st>>>(a.gcnt, groups * L.split, counters_out);
+  return launch_status();
 }
 
 }  // namespace
@@ -572,33 +652,21 @@ int nbd_tree_build_f32(const float* pos, const float* mass, int n, int* order_ou
 
 int nbd_tree_accel_f32(const void* workspace, int n, float theta, float softening_sq, float g_const, int quadrupole,
                        float* acc_out, unsigned long long* counters_out, nbd_stream_t stream) {
-  if (n < 0 || !(theta >= 0.f) || (n > 0 && (!workspace || !acc_out))) return NBD_E_BADARG;
-  if (n == 0) return 0;
-  if (n > kMaxBodies) return NBD_E_UNSUPPORTED;
-  if (reinterpret_cast<uintptr_t>(workspace) & 255) return NBD_E_BADARG;
-  const Levels L = plan_levels(n);
-  const Layout w = layout(n, L);
-  hipStream_t st = (hipStream_t)stream;
-  char* base = static_cast<char*>(const_cast<void*>(workspace));
-  WalkArgs a = {};
-  a.posm = reinterpret_cast<const f4*>(base + w.posm);
-  a.nodes = reinterpret_cast<const f4*>(base + w.nodes);
-  a.order = reinterpret_cast<const int*>(base + w.order);
-  a.acc_out = acc_out;
-  a.gcnt = reinterpret_cast<unsigned*>(base + w.gcnt);
-  a.slabs = reinterpret_cast<float*>(base + w.slabs);
-  a.n = n; a.levels = L.levels; a.stack_cap = kStackPerLevel * L.levels;
-  a.split = L.split; a.start_level = L.start_level;
-  for (int l = 0; l < kMaxLevels; ++l) { a.count[l] = L.count[l]; a.off[l] = L.off[l]; }
-  a.theta2 = theta * theta; a.eps2 = softening_sq; a.g = g_const;
-  const int groups = pad64(n) / kGroup;
-  const size_t lds_bytes = kWalkFixedLds + (size_t)a.stack_cap * 4;
-  const dim3 grid(groups, L.split);
-  if (quadrupole) tree_walk_kernel<true><<<grid, 64, lds_bytes, st>>>(a);
-  else tree_walk_kernel<false><<<grid, 64, lds_bytes, st>>>(a);
-  if (L.split > 1) slab_sum_kernel<<<(n + 255) / 256, 256, 0, st>>>(a.slabs, L.split, n, a.order, g_const, acc_out);
-  if (counters_out) counter_kernel<<<1, 256, 0, st>>>(a.gcnt, groups * L.split, counters_out);
-  return launch_status();
+  return tree_walk<true, false>(workspace, n, theta, softening_sq, g_const, quadrupole, acc_out, nullptr, counters_out,
+                                stream);
+}
+
+int nbd_tree_potential_f32(const void* workspace, int n, float theta, float softening_sq, float g_const, int quadrupole,
+                           double* phi_out, unsigned long long* counters_out, nbd_stream_t stream) {
+  return tree_walk<false, true>(workspace, n, theta, softening_sq, g_const, quadrupole, nullptr, phi_out, counters_out,
+                                stream);
+}
+
+int nbd_tree_accel_potential_f32(const void* workspace, int n, float theta, float softening_sq, float g_const,
+                                 int quadrupole, float* acc_out, double* phi_out, unsigned long long* counters_out,
+                                 nbd_stream_t stream) {
+  return tree_walk<true, true>(workspace, n, theta, softening_sq, g_const, quadrupole, acc_out, phi_out, counters_out,
+                               stream);
 }
 
 }  // extern "C"

@@ -940,11 +940,25 @@ class TreeLeapFrogSimulator(LeapFrogSimulator):
 
     positions, velocities and accelerations stay in the caller's order; the bodies are re-sorted along a Morton curve
     and the tree rebuilt inside every force evaluation (`tree_order()` is that permutation, `tree_counters()` the walk's
-    work). step() is kick-drift, sort + build, tree force, kick; run() is eager. compute_energies() and
-    compute_potentials() keep the all-pairs O(N^2) kernels: construct large systems with calc_energy=False."""
+    work). step() is kick-drift, sort + build, tree force, kick; run() is eager.
 
-    def __init__(self, *, theta: float = 0.5, quadrupole: bool = True, **kw):
+    `potential` chooses what compute_potentials(), compute_invariants() and run() with calc_invariants=True sum:
+      "direct" (the default)  the all-pairs O(N^2) potential of LeapFrogSimulator, bit for bit;
+      "tree"                  the tree's own potential, O(N log N): over the accepted cells and rejected level-0 nodes
+                              of the force walk, phi_cell = -(M u + 1/2 (r.Qr) u^5) and -m_j (|d|^2 + eps^2)^(-1/2) per
+                              body (fp32 terms, fp64 sums) -- the function whose gradient the tree force is, so
+                              E = K + 1/2 sum m phi is the figure of merit of this integrator. compute_potentials()
+                              sorts and builds on the current positions and walks for phi alone; while calc_invariants
+                              is True, step() takes a and phi from ONE walk and the invariants row of run() uses that
+                              phi: no second build, no second walk. a and tree_counters() are the plain step's.
+    compute_energies() and calc_energy keep the reference's all-pairs -G m m / (|r| + eps) kernel under either value:
+    that number has to be the reference's, and its pair term is not the one the cell records expand. It is O(N^2):
+    construct large systems with calc_energy=False."""
+
+    def __init__(self, *, theta: float = 0.5, quadrupole: bool = True, potential: str = "direct", **kw):
         name = type(self).__name__
+        if potential not in ("direct", "tree"):
+            raise ValueError(f"{name}: potential must be 'direct' or 'tree', got {potential!r}")
         if kw.get("dtype", torch.float32) != torch.float32:
             raise ValueError(f"{name}: the tree force is float32 only, got dtype={kw['dtype']!r}")
         if kw.get("process_group") is not None:
@@ -956,6 +970,7 @@ class TreeLeapFrogSimulator(LeapFrogSimulator):
             raise ValueError(f"{name}: theta must be >= 0, got {theta!r}")
         self.theta = float(theta)
         self.quadrupole = bool(quadrupole)
+        self.potential = potential
         super().__init__(**kw)
 
     def _init_scratch(self):
@@ -969,18 +984,47 @@ class TreeLeapFrogSimulator(LeapFrogSimulator):
         self._tree_ws = tree.workspace(self.n, self.device) if self.n else None
         self._order = torch.empty((self.n,), dtype=torch.int32, device=self.device)
         self._counters = torch.zeros((2,), dtype=torch.int64, device=self.device)
+        self._phi, self._phi_of_step = None, False       # phi of the last step's walk (potential="tree")
         self.accelerations = self.compute_accelerations()
 
     def compute_accelerations(self) -> torch.Tensor:
         """The tree force on the current positions -> new (n,3) tensor in the caller's order."""
+        return self._tree_force(None)
+
+    def _tree_force(self, phi) -> torch.Tensor:
+        """Sort + build, then the walk: for a alone, or (phi: (n,) float64) the fused one that also leaves phi there."""
         if self.n == 0:
             return torch.zeros((0, 3), dtype=torch.float32, device=self.device)
         if self._wants_grad():
             raise ValueError(f"{type(self).__name__}.compute_accelerations(): the tree force has no backward")
         from nbd import tree
         tree.build(self.positions, self.masses, self._tree_ws, self._order)
-        return tree.accel(self._tree_ws, self.n, self.theta, self._eps2, self._g, self.quadrupole,
-                          counters=self._counters)
+        walk = (self._tree_ws, self.n, self.theta, self._eps2, self._g, self.quadrupole)
+        if phi is None:
+            return tree.accel(*walk, counters=self._counters)
+        return tree.accel_potential(*walk, out=(None, phi), counters=self._counters)[0]
+
+    def compute_potentials(self) -> torch.Tensor:
+        """potential="direct": LeapFrogSimulator.compute_potentials(). potential="tree": sort + build on the current
+        positions, then the phi-only walk -> new (n,) float64 device tensor (coincident distinct bodies at softening 0
+        give -inf here too). tree_counters() keeps the last FORCE evaluation's figures."""
+        if self.potential != "tree" or self.n == 0:
+            return super().compute_potentials()
+        from nbd import tree
+        self._fmt.pack(self)                             # compute_invariants() reads the packed bodies next to phi
+        tree.build(self.positions, self.masses, self._tree_ws, self._order)
+        return tree.potential(self._tree_ws, self.n, self.theta, self._eps2, self._g, self.quadrupole)
+
+    def _invariants_into(self, out_row):
+        """potential="tree": the row from the phi the step's own walk left (step() packed `_posm` in its kick-drift)."""
+        if self.potential != "tree" or not self._phi_of_step:
+            return super()._invariants_into(out_row)
+        self._fmt.invariants(self, self._phi, out_row)
+
+    def _potentials_into(self, phi):
+        if self.potential != "tree":
+            return super()._potentials_into(phi)
+        return phi.copy_(self.compute_potentials())      # (only a row asked for without a fused step before it)
 
     def tree_order(self) -> torch.Tensor:
         """order (n,) int32 of the last force evaluation: order[k] is the index of the k-th body along the Morton curve."""
@@ -994,12 +1038,16 @@ class TreeLeapFrogSimulator(LeapFrogSimulator):
         return int(c[0]), int(c[1])
 
     def step(self):
-        """Kick-drift (the direct integrator's kernel), sort + build, tree force, kick."""
+        """Kick-drift (the direct integrator's kernel), sort + build, tree force, kick. With potential="tree" and
+        calc_invariants the force walk is the fused one and leaves phi of the new positions for the invariants."""
         if self.n == 0:
             return
         half, dt = direct.f32(0.5 * self.dt), direct.f32(self.dt)
         direct.kick_drift(self.positions, self.velocities, self.accelerations, self.masses, half, dt, posm=self._posm)
-        self.accelerations = self.compute_accelerations()
+        self._phi_of_step = self.potential == "tree" and bool(self.calc_invariants)
+        if self._phi_of_step and self._phi is None:
+            self._phi = torch.empty((self.n,), dtype=torch.float64, device=self.device)
+        self.accelerations = self._tree_force(self._phi if self._phi_of_step else None)
         direct.kick(self.velocities, self.accelerations, half)
 
 

@@ -11,6 +11,20 @@ Per N (Plummer sphere, eps = 0.1, G = 1, quadrupoles on) and theta in {0.5, 0.75
   row errors  256 sampled rows of the tree force, and of nbd_accel_f32, against float64 all-pairs rows (torch on the
               device: a reference, not a product path), measured like conftest.row_rel
 Times are HIP events around `reps` calls; the three are measured in alternating rounds and the median round is kept.
+
+  python tools/bench_tree.py --potential [--out FILE] [--sizes N ...]     (default: profiles/r30_tree_potential.json)
+
+The tree potential next to the all-pairs potential of csrc/direct_diag.hip, same inputs, same alternating rounds:
+  build_ms, walk_ms, direct_ms   as above
+  phi_walk_ms, fused_walk_ms     nbd_tree_potential_f32 and nbd_tree_accel_potential_f32 with the counters
+  direct_phi_ms                  nbd_potential_f32 on the same bodies
+  fused_over_walk                (a) what phi costs a force walk
+  tree_phi_over_direct_phi       (b) (build + phi-only walk) / all-pairs potential
+  run_step_ms                    (c) TreeLeapFrogSimulator.run() per step with calc_invariants=True, calc_energy=False,
+                                 potential="tree" and "direct" (HIP events around run(4), host copies of the states included)
+  phi_row_error                  256 sampled rows of the tree phi, and of nbd_potential_f32, against float64 all-pairs rows:
+                                 |phi - ref| / |ref|
+  u_rel_diff                     |U_tree - U_direct| / |U_direct|, U = 1/2 sum m phi in float64 from the two device phi
 """
 import argparse
 import json
@@ -57,6 +71,103 @@ def _row_errors(a, ref):
     floor = 1e-3 * np.sqrt((nrm ** 2).mean())
     e = np.linalg.norm(a - ref, axis=1) / np.maximum(nrm, floor)
     return {"max": float(e.max()), "rms": float(np.sqrt((e ** 2).mean()))}
+
+
+def _f64_phi_rows(pos, mass, rows, eps2):
+    """float64 all-pairs potentials of the sampled rows (G = 1), 16 rows at a time."""
+    p, m = pos.double(), mass.double()
+    out = torch.empty((len(rows),), dtype=torch.float64, device=pos.device)
+    for k in range(0, len(rows), 16):
+        r = rows[k:k + 16]
+        d = p[None, :, :] - p[r][:, None, :]
+        w = ((d * d).sum(2) + eps2) ** -0.5
+        w[torch.arange(len(r), device=pos.device), r] = 0.0
+        out[k:k + 16] = -(m[None, :] * w).sum(1)
+    return out.cpu().numpy()
+
+
+def _phi_errors(phi, ref):
+    e = np.abs(phi - ref) / np.abs(ref)
+    return {"max": float(e.max()), "rms": float(np.sqrt((e ** 2).mean()))}
+
+
+def _run_step_ms(p, m, theta, potential, steps=4):
+    """Per step of run(steps) with the invariants on, after one warm-up run (staging buffers, first launches)."""
+    from galaxify import simulation
+    v = np.zeros_like(p)
+    sim = simulation.TreeLeapFrogSimulator(positions=p, velocities=v, masses=m, g_const=1.0, softening=EPS, dt=1e-3,
+                                           calc_energy=False, calc_invariants=True, device="cuda", theta=theta,
+                                           potential=potential)
+    sim.run(2)
+    return _timed(lambda: sim.run(steps), 1) / steps
+
+
+def potential_case(n, thetas):
+    p, _, m = generate_plummer(n, seed=1)
+    p, m = np.asarray(p, np.float32), np.asarray(m, np.float32)
+    dev = torch.device("cuda", torch.cuda.current_device())
+    pos, mass = torch.tensor(p, device=dev), torch.tensor(m, device=dev)
+    eps2 = direct.f32(EPS ** 2)
+    posm = direct.pack_posm(pos, mass)
+    dws = direct.accel_workspace(n, n, dev)
+    pws = direct.potential_workspace(n, n, dev)
+    dacc = torch.empty((n, 3), dtype=torch.float32, device=dev)
+    dphi = torch.empty((n,), dtype=torch.float64, device=dev)
+    tws = tree.workspace(n, dev)
+    order = torch.empty((n,), dtype=torch.int32, device=dev)
+    tacc = torch.empty((n, 3), dtype=torch.float32, device=dev)
+    tphi = torch.empty((n,), dtype=torch.float64, device=dev)
+    counters = torch.zeros((2,), dtype=torch.int64, device=dev)
+    rows = torch.tensor(np.random.default_rng(0).choice(n, min(SAMPLED, n), replace=False), device=dev)
+    ref = _f64_phi_rows(pos, mass, rows, float(eps2))
+
+    runs = {"direct_ms": lambda: direct.accel(posm, n, posm, n, 0, eps2, 1.0, out=dacc, workspace=dws),
+            "direct_phi_ms": lambda: direct.potential(posm, n, posm, n, 0, eps2, 1.0, out=dphi, workspace=pws),
+            "build_ms": lambda: tree.build(pos, mass, tws, order)}
+    reps_direct = max(2, min(50, int(4e10 / n / n)))
+    reps_tree = max(5, min(50, int(4e6 / n) * 5))
+    res = {"n": n, "plan": tree.plan(n), "workspace_bytes": tree.workspace_bytes(n), "reps_direct": reps_direct,
+           "reps_tree": reps_tree, "thetas": []}
+    for fn in runs.values():
+        fn()
+    torch.cuda.synchronize()
+    res["direct_phi_row_error"] = _phi_errors(dphi[rows].cpu().numpy(), ref)
+    u_direct = 0.5 * float((mass.double() * dphi).sum())
+    for theta in thetas:
+        walk = (tws, n, theta, eps2, 1.0, True)
+        runs["walk_ms"] = lambda: tree.accel(*walk, out=tacc, counters=counters)
+        runs["phi_walk_ms"] = lambda: tree.potential(*walk, out=tphi, counters=counters)
+        runs["fused_walk_ms"] = lambda: tree.accel_potential(*walk, out=(tacc, tphi), counters=counters)
+        for key in ("walk_ms", "fused_walk_ms", "phi_walk_ms"):
+            runs[key]()
+        torch.cuda.synchronize()
+        t = {key: [] for key in runs}
+        for _ in range(ROUNDS):
+            for key, fn in runs.items():
+                t[key].append(_timed(fn, reps_direct if key.startswith("direct") else reps_tree))
+        row = {"theta": theta}
+        for key, vals in t.items():
+            row[key] = float(np.median(vals))
+            row[key + "_min"] = float(np.min(vals))
+        row["fused_over_walk"] = row["fused_walk_ms"] / row["walk_ms"]
+        row["phi_walk_over_walk"] = row["phi_walk_ms"] / row["walk_ms"]
+        row["tree_phi_ms"] = row["build_ms"] + row["phi_walk_ms"]
+        row["tree_phi_over_direct_phi"] = row["tree_phi_ms"] / row["direct_phi_ms"]
+        cells, leaves = counters.cpu().tolist()
+        row["accepted_cells"], row["rejected_level0_nodes"] = int(cells), int(leaves)
+        row["phi_row_error"] = _phi_errors(tphi[rows].cpu().numpy(), ref)
+        u_tree = 0.5 * float((mass.double() * tphi).sum())
+        row["u_tree"], row["u_direct"] = u_tree, u_direct
+        row["u_rel_diff"] = abs(u_tree - u_direct) / abs(u_direct)
+        steps = {"tree": [], "direct": []}
+        for which in ("tree", "direct", "tree", "direct"):
+            steps[which].append(_run_step_ms(p, m, theta, which))
+        row["run_step_ms"] = {which: float(np.min(vals)) for which, vals in steps.items()}
+        row["run_step_ms_all"] = steps
+        row["run_step_tree_over_direct"] = row["run_step_ms"]["tree"] / row["run_step_ms"]["direct"]
+        res["thetas"].append(row)
+        print(json.dumps({"n": n, **row}), flush=True)
+    return res
 
 
 def case(n, thetas):
@@ -116,13 +227,17 @@ def case(n, thetas):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r28_tree.json"))
+    ap.add_argument("--potential", action="store_true", help="the tree potential next to the all-pairs potential")
+    ap.add_argument("--out", default=None, help="profiles/r28_tree.json, or profiles/r30_tree_potential.json")
     ap.add_argument("--sizes", type=int, nargs="+", default=[65536, 262144, 524288])
     ap.add_argument("--thetas", type=float, nargs="+", default=[0.5, 0.75])
     args = ap.parse_args()
     assert torch.cuda.is_available(), "needs the MI355X"
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "r30_tree_potential.json" if args.potential else "r28_tree.json")
+    one = potential_case if args.potential else case
     res = {"device": torch.cuda.get_device_name(0), "softening": EPS, "quadrupole": True, "sampled_rows": SAMPLED,
-           "rounds": ROUNDS, "cases": [case(n, args.thetas) for n in args.sizes]}
+           "rounds": ROUNDS, "cases": [one(n, args.thetas) for n in args.sizes]}
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as f:
         json.dump(res, f, indent=1)
