@@ -1541,6 +1541,26 @@ int64_t nbd_csv_format_state(char* out, size_t cap, const char* prefix, size_t p
  *                                 codes as nbd_tree_accel_f32 (phi_out NULL is NBD_E_BADARG)
  *   nbd_tree_accel_potential_f32  both from one walk: acc_out bit for bit nbd_tree_accel_f32's, phi_out bit for bit
  *                                 nbd_tree_potential_f32's, the same counters
+ * Several ranks ("Several ranks"): every rank builds the same tree from the gathered packed rows, walks a
+ * contiguous range of the target GROUPS (group g = the sorted bodies [64 g, min(n, 64 g + 64)); ceil(n/64) of them) and
+ * places the exchanged rows by `order`. A group's walk reads nothing of another group's, so a row of a ranged walk is
+ * bit for bit the row the full walk gives that body, whatever the range.
+ *   nbd_tree_build_posm_f32       nbd_tree_build_f32 from packed rows posm (n,4) {x, y, z, m}, 16-byte aligned: order_out
+ *                                 and everything the walks read are bit for bit what the two-array build leaves
+ *   nbd_tree_accel_groups_f32     the walk of the target groups [group_lo, group_hi) alone: acc_sorted_out
+ *                                 ((group_hi - group_lo) 64, 3) in TREE order, row t = sorted body 64 group_lo + t
+ *                                 (acc_full[order[k]] == acc_sorted[k - 64 group_lo] bit for bit), rows behind body n - 1
+ *                                 written as 0; counters_out = the sums over these groups. 0 <= group_lo <= group_hi <=
+ *                                 ceil(n/64), else NBD_E_BADARG; an empty range returns 0, launches nothing and leaves
+ *                                 counters_out alone. The workspace is the full walk's (slabs and per-group counters at
+ *                                 the global body and group): ranged walks of one workspace run one after another.
+ *   nbd_tree_potential_groups_f32, nbd_tree_accel_potential_groups_f32
+ *                                 the same for phi_sorted_out ((group_hi - group_lo) 64,) float64 and for both
+ *   nbd_tree_scatter_f32          tree order -> a range [lo, hi) of the caller's order: for every sorted position k with
+ *                                 lo <= order[k] < hi, acc_out[order[k] - lo] = acc_sorted[k] and phi_out[order[k] - lo] =
+ *                                 phi_sorted[k]; acc_sorted (pad64(n),3) or NULL, phi_sorted (pad64(n),) or NULL (both
+ *                                 NULL, or 0 <= lo <= hi <= n violated: NBD_E_BADARG), acc_out (hi - lo, 3), phi_out
+ *                                 (hi - lo,). One thread per sorted body, no atomics.
  * n = 0 is a no-op. No allocation, memset or synchronisation inside; bit-identical from run to run. */
 int nbd_tree_plan(int n, int* levels, int* nodes_total);
 size_t nbd_tree_workspace_bytes(int n);
@@ -1553,6 +1573,19 @@ int nbd_tree_potential_f32(const void* workspace, int n, float theta, float soft
 int nbd_tree_accel_potential_f32(const void* workspace, int n, float theta, float softening_sq, float g_const,
                                  int quadrupole, float* acc_out, double* phi_out, unsigned long long* counters_out,
                                  nbd_stream_t stream);
+int nbd_tree_build_posm_f32(const float* posm, int n, int* order_out, void* workspace, size_t workspace_bytes,
+                            nbd_stream_t stream);
+int nbd_tree_accel_groups_f32(const void* workspace, int n, int group_lo, int group_hi, float theta, float softening_sq,
+                              float g_const, int quadrupole, float* acc_sorted_out, unsigned long long* counters_out,
+                              nbd_stream_t stream);
+int nbd_tree_potential_groups_f32(const void* workspace, int n, int group_lo, int group_hi, float theta,
+                                  float softening_sq, float g_const, int quadrupole, double* phi_sorted_out,
+                                  unsigned long long* counters_out, nbd_stream_t stream);
+int nbd_tree_accel_potential_groups_f32(const void* workspace, int n, int group_lo, int group_hi, float theta,
+                                        float softening_sq, float g_const, int quadrupole, float* acc_sorted_out,
+                                        double* phi_sorted_out, unsigned long long* counters_out, nbd_stream_t stream);
+int nbd_tree_scatter_f32(const void* workspace, int n, int lo, int hi, const float* acc_sorted, const double* phi_sorted,
+                         float* acc_out, double* phi_out, nbd_stream_t stream);
 
 #ifdef __cplusplus
 }

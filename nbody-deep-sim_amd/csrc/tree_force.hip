@@ -37,6 +37,13 @@
 //           doubles [split][n] behind every other region of the workspace), the factor -G. The self term (m_i / eps, not 0
 //           as in the force) is excluded by the same index mask, the padding rows too. ACC / PHI choose what a walk
 //           accumulates at compile time; the acc-only instantiations are the force kernel unchanged.
+//   ranks   ("Several ranks") every rank builds the same tree from the gathered packed rows {x, y, z, m}
+//           (the row stride of the box / key / gather kernels is a compile-time switch: the same values, the same bits)
+//           and walks a contiguous range of the target groups: RANGED offsets the group index of the same walk and
+//           leaves the finished rows in TREE order, row 0 = the first body of the range's first group, the padding rows
+//           of the last group as 0. Slabs and per-group counters stay indexed by the global body and group. A group's
+//           walk reads nothing of another group's, so a row is bit for bit the full walk's, whatever the range; the
+//           exchanged rows are placed into a range of the caller's order by scatter_kernel through `order`.
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 #include <math.h>
@@ -123,13 +130,16 @@ inline int launch_status() {
 
 // ---------------------------------------------------------------- bounding box, keys, gather
 
+// Rows of the caller's bodies: pos (n,3) beside mass (n,) (STRIDE 3) or packed {x, y, z, m} (STRIDE 4, what the
+// all-gather of a range-sharded step delivers); the layout is a compile-time switch of the three kernels that read them.
 // part[b] = {lo (3), pad, hi (3), pad} of the bodies block b strides over (+-inf where it sees none)
+template <int STRIDE>
 __global__ __launch_bounds__(256) void box_partial_kernel(const float* __restrict__ pos, int n, float* __restrict__ part) {
   __shared__ float red[6][256];
   float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
   for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256)
     for (int a = 0; a < 3; ++a) {
-      const float v = pos[(size_t)3 * i + a];
+      const float v = pos[(size_t)STRIDE * i + a];
       lo[a] = fminf(lo[a], v); hi[a] = fmaxf(hi[a], v);
     }
   for (int a = 0; a < 3; ++a) { red[a][threadIdx.x] = lo[a]; red[3 + a][threadIdx.x] = hi[a]; }
@@ -182,6 +192,7 @@ __device__ inline uint64_t spread21(uint32_t v) {      // bit k of the low 21 ->
   return x;
 }
 
+template <int STRIDE>
 __global__ __launch_bounds__(256) void key_kernel(const float* __restrict__ pos, int n, const float* __restrict__ box,
                                                   uint64_t* __restrict__ keys, int* __restrict__ vals) {
   const int i = blockIdx.x * 256 + threadIdx.x;
@@ -189,7 +200,7 @@ __global__ __launch_bounds__(256) void key_kernel(const float* __restrict__ pos,
   const float scale = box[3];
   uint32_t q[3];
   for (int a = 0; a < 3; ++a) {
-    const float f = (pos[(size_t)3 * i + a] - box[a]) * scale;
+    const float f = (pos[(size_t)STRIDE * i + a] - box[a]) * scale;
     q[a] = (uint32_t)fminf(fmaxf(f, 0.f), 2097151.f);       // a NaN coordinate lands in cell 0
   }
   keys[i] = spread21(q[0]) << 2 | spread21(q[1]) << 1 | spread21(q[2]);
@@ -197,6 +208,8 @@ __global__ __launch_bounds__(256) void key_kernel(const float* __restrict__ pos,
 }
 
 // posm[k] = {x, y, z, m} of body order[k] for k < n, zeros in the padding up to a multiple of 64; order_out = order
+// (STRIDE 4: `pos` holds the packed rows, 16-byte aligned, and `mass` is not read)
+template <int STRIDE>
 __global__ __launch_bounds__(256) void gather_kernel(const float* __restrict__ pos, const float* __restrict__ mass, int n,
                                                      int n_pad, const int* __restrict__ order, f4* __restrict__ posm,
                                                      int* __restrict__ order_out) {
@@ -205,7 +218,8 @@ __global__ __launch_bounds__(256) void gather_kernel(const float* __restrict__ p
   f4 p = {0.f, 0.f, 0.f, 0.f};
   if (k < n) {
     const int j = order[k];
-    p = f4{pos[(size_t)3 * j], pos[(size_t)3 * j + 1], pos[(size_t)3 * j + 2], mass[j]};
+    if (STRIDE == 4) p = reinterpret_cast<const f4*>(pos)[j];
+    else p = f4{pos[(size_t)3 * j], pos[(size_t)3 * j + 1], pos[(size_t)3 * j + 2], mass[j]};
     order_out[k] = j;
   }
   posm[k] = p;
@@ -310,6 +324,13 @@ struct PhiWalkArgs : WalkArgs {
 };
 template <bool PHI> struct WalkArgsOf { typedef WalkArgs type; };
 template <> struct WalkArgsOf<true> { typedef PhiWalkArgs type; };
+// what a walk of the target groups [group_lo, group_lo + gridDim.x) alone takes on top: acc_out / phi_out are then in TREE
+// order, row 0 = sorted body 64 group_lo, the padding rows of the last group included (the full walks keep their structs)
+template <bool PHI> struct RangedWalkArgs : WalkArgsOf<PHI>::type {
+  int group_lo, groups;    // first group of the launch; groups of the whole tree (the stride of gcnt)
+};
+template <bool PHI, bool RANGED> struct KernelArgsOf { typedef typename WalkArgsOf<PHI>::type type; };
+template <bool PHI> struct KernelArgsOf<PHI, true> { typedef RangedWalkArgs<PHI> type; };
 
 __device__ __forceinline__ int lanes_below(unsigned long long mask) {
   return __builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
@@ -333,8 +354,8 @@ __device__ __forceinline__ void add_comp(float& tot, float& comp, float s) {
 
 constexpr int kWalkFixedLds = (3 * kListCap + 64 * kLeaf) * 16 + kListCap * 4 + 2 * kMaxLevels * 4;
 
-template <bool QUAD, bool ACC, bool PHI>
-__global__ __launch_bounds__(64) void tree_walk_kernel(const typename WalkArgsOf<PHI>::type a) {
+template <bool QUAD, bool ACC, bool PHI, bool RANGED>
+__global__ __launch_bounds__(64) void tree_walk_kernel(const typename KernelArgsOf<PHI, RANGED>::type a) {
   extern __shared__ f4 lds[];
   f4* cells = lds;                                   // [kListCap][3]
   f4* stage = cells + 3 * kListCap;                  // [64][kLeaf] bodies of one pass of the level-0 list
@@ -344,7 +365,10 @@ __global__ __launch_bounds__(64) void tree_walk_kernel(const typename WalkArgsOf
 
   const int lane = threadIdx.x;
   const int part = blockIdx.y;                       // which of the group's `split` waves this is
-  const int i = blockIdx.x * kGroup + lane;
+  int group_lo = 0;                                  // the launch's first target group (its row 0 of a ranged output)
+  if constexpr (RANGED) group_lo = a.group_lo;
+  const int row0 = group_lo * kGroup;
+  const int i = (group_lo + blockIdx.x) * kGroup + lane;
   const bool valid = i < a.n;
   const f4 me = a.posm[i];
   const float x = me.x, y = me.y, z = me.z;
@@ -492,7 +516,7 @@ __global__ __launch_bounds__(64) void tree_walk_kernel(const typename WalkArgsOf
 
   if (ACC && valid) {
     if (a.split == 1) {
-      const size_t o = (size_t)a.order[i] * 3;
+      const size_t o = (size_t)(RANGED ? i - row0 : a.order[i]) * 3;
       a.acc_out[o] = a.g * ax; a.acc_out[o + 1] = a.g * ay; a.acc_out[o + 2] = a.g * az;
     } else {
       const size_t o = ((size_t)part * a.n + i) * 3;
@@ -500,11 +524,17 @@ __global__ __launch_bounds__(64) void tree_walk_kernel(const typename WalkArgsOf
     }
   }
   if constexpr (PHI) if (valid) {
-    if (a.split == 1) a.phi_out[a.order[i]] = 0.0 - (double)a.g * phi;
+    if (a.split == 1) a.phi_out[RANGED ? i - row0 : a.order[i]] = 0.0 - (double)a.g * phi;
     else a.phi_slabs[(size_t)part * a.n + i] = phi;
   }
+  if (RANGED && !valid && a.split == 1) {           // the rows behind body n - 1 of the last group
+    const size_t t = (size_t)(i - row0);
+    if (ACC) { a.acc_out[3 * t] = 0.f; a.acc_out[3 * t + 1] = 0.f; a.acc_out[3 * t + 2] = 0.f; }
+    if constexpr (PHI) a.phi_out[t] = 0.0;
+  }
   if (lane == 0) {
-    const size_t o = ((size_t)part * gridDim.x + blockIdx.x) * 2;
+    size_t o = ((size_t)part * gridDim.x + blockIdx.x) * 2;
+    if constexpr (RANGED) o = ((size_t)part * a.groups + group_lo + blockIdx.x) * 2;   // by the global group
     a.gcnt[o] = cells_total; a.gcnt[o + 1] = leaves_total;
   }
 }
@@ -532,12 +562,58 @@ __global__ __launch_bounds__(256) void phi_slab_sum_kernel(const double* __restr
   phi_out[order[i]] = 0.0 - g * s;
 }
 
-// counters[0..1] = the per-group pairs summed in a fixed order
-__global__ __launch_bounds__(256) void counter_kernel(const unsigned* __restrict__ gcnt, int groups,
-                                                      unsigned long long* __restrict__ counters) {
+// The two kernels above for the sorted bodies [first, first + rows) alone and in TREE order: row t of the output is
+// sorted body first + t, the same 8 slabs added in the same order, rows at or behind body n written as 0.
+__global__ __launch_bounds__(256) void slab_sum_rows_kernel(const float* __restrict__ slabs, int split, int n, int first,
+                                                            int rows, float g, float* __restrict__ acc_sorted) {
+  const int t = blockIdx.x * 256 + threadIdx.x;
+  if (t >= rows) return;
+  const int i = first + t;
+  float s[3] = {0.f, 0.f, 0.f};
+  if (i < n)
+    for (int w = 0; w < split; ++w)
+      for (int c = 0; c < 3; ++c) s[c] += slabs[((size_t)w * n + i) * 3 + c];
+  for (int c = 0; c < 3; ++c) acc_sorted[(size_t)t * 3 + c] = i < n ? g * s[c] : 0.f;
+}
+
+__global__ __launch_bounds__(256) void phi_slab_sum_rows_kernel(const double* __restrict__ slabs, int split, int n,
+                                                                int first, int rows, double g,
+                                                                double* __restrict__ phi_sorted) {
+  const int t = blockIdx.x * 256 + threadIdx.x;
+  if (t >= rows) return;
+  const int i = first + t;
+  double s = 0.0;
+  if (i < n)
+    for (int w = 0; w < split; ++w) s += slabs[(size_t)w * n + i];
+  phi_sorted[t] = i < n ? 0.0 - g * s : 0.0;
+}
+
+// out[order[k] - lo] = sorted[k] for every sorted position k whose body the range [lo, hi) of the caller's order holds
+// (order is a permutation: every output row is written once)
+__global__ __launch_bounds__(256) void scatter_kernel(const int* __restrict__ order, int n, int lo, int hi,
+                                                      const float* __restrict__ acc_sorted,
+                                                      const double* __restrict__ phi_sorted, float* __restrict__ acc_out,
+                                                      double* __restrict__ phi_out) {
+  const int k = blockIdx.x * 256 + threadIdx.x;
+  if (k >= n) return;
+  const int j = order[k];
+  if (j < lo || j >= hi) return;
+  const size_t o = (size_t)(j - lo);
+  if (acc_sorted)
+    for (int c = 0; c < 3; ++c) acc_out[o * 3 + c] = acc_sorted[(size_t)k * 3 + c];
+  if (phi_sorted) phi_out[o] = phi_sorted[k];
+}
+
+// counters[0..1] = the per-group pairs of the groups [lo, hi) of all `split` waves (gcnt: [split][groups][2]); integers
+__global__ __launch_bounds__(256) void counter_kernel(const unsigned* __restrict__ gcnt, int groups, int split, int lo,
+                                                      int hi, unsigned long long* __restrict__ counters) {
   __shared__ unsigned long long red[2][256];
   unsigned long long c = 0, l = 0;
-  for (int g = threadIdx.x; g < groups; g += 256) { c += gcnt[2 * g]; l += gcnt[2 * g + 1]; }
+  for (int w = 0; w < split; ++w)
+    for (int g = lo + threadIdx.x; g < hi; g += 256) {
+      const size_t o = ((size_t)w * groups + g) * 2;
+      c += gcnt[o]; l += gcnt[o + 1];
+    }
   red[0][threadIdx.x] = c; red[1][threadIdx.x] = l;
   __syncthreads();
   for (int w = 128; w > 0; w >>= 1) {
@@ -550,19 +626,29 @@ __global__ __launch_bounds__(256) void counter_kernel(const unsigned* __restrict
   if (threadIdx.x == 0) { counters[0] = red[0][0]; counters[1] = red[1][0]; }
 }
 
-// One walk over a built workspace: the acceleration (acc_out), the potential (phi_out) or both.
-template <bool ACC, bool PHI>
-int tree_walk(const void* workspace, int n, float theta, float softening_sq, float g_const, int quadrupole,
-              float* acc_out, double* phi_out, unsigned long long* counters_out, nbd_stream_t stream) {
-  if (n < 0 || !(theta >= 0.f) || (n > 0 && (!workspace || (ACC && !acc_out) || (PHI && !phi_out)))) return NBD_E_BADARG;
+// One walk over a built workspace: the acceleration (acc_out), the potential (phi_out) or both. RANGED: of the target
+// groups [group_lo, group_hi) alone, the outputs in tree order with (group_hi - group_lo) 64 rows; slabs and per-group
+// counters stay where the full walk keeps them, indexed by the global body and group.
+template <bool ACC, bool PHI, bool RANGED>
+int tree_walk(const void* workspace, int n, int group_lo, int group_hi, float theta, float softening_sq, float g_const,
+              int quadrupole, float* acc_out, double* phi_out, unsigned long long* counters_out, nbd_stream_t stream) {
+  if (n < 0 || !(theta >= 0.f)) return NBD_E_BADARG;
+  if (RANGED) {                                      // the range first: an empty one asks for nothing
+    if (n > kMaxBodies) return NBD_E_UNSUPPORTED;
+    if (group_lo < 0 || group_lo > group_hi || group_hi > pad64(n) / kGroup) return NBD_E_BADARG;
+    if (group_lo == group_hi) return 0;
+  }
+  if (n > 0 && (!workspace || (ACC && !acc_out) || (PHI && !phi_out))) return NBD_E_BADARG;
   if (n == 0) return 0;
   if (n > kMaxBodies) return NBD_E_UNSUPPORTED;
   if (reinterpret_cast<uintptr_t>(workspace) & 255) return NBD_E_BADARG;
+  const int groups = pad64(n) / kGroup;
+  if (!RANGED) { group_lo = 0; group_hi = groups; }
   const Levels L = plan_levels(n);
   const Layout w = layout(n, L);
   hipStream_t st = (hipStream_t)stream;
   char* base = static_cast<char*>(const_cast<void*>(workspace));
-  typename WalkArgsOf<PHI>::type a = {};
+  typename KernelArgsOf<PHI, RANGED>::type a = {};
   a.posm = reinterpret_cast<const f4*>(base + w.posm);
   a.nodes = reinterpret_cast<const f4*>(base + w.nodes);
   a.order = reinterpret_cast<const int*>(base + w.order);
@@ -570,22 +656,74 @@ int tree_walk(const void* workspace, int n, float theta, float softening_sq, flo
   a.gcnt = reinterpret_cast<unsigned*>(base + w.gcnt);
   a.slabs = reinterpret_cast<float*>(base + w.slabs);
   if constexpr (PHI) { a.phi_out = phi_out; a.phi_slabs = reinterpret_cast<double*>(base + w.phi_slabs); }
+  if constexpr (RANGED) { a.group_lo = group_lo; a.groups = groups; }
   a.n = n; a.levels = L.levels; a.stack_cap = kStackPerLevel * L.levels;
   a.split = L.split; a.start_level = L.start_level;
   for (int l = 0; l < kMaxLevels; ++l) { a.count[l] = L.count[l]; a.off[l] = L.off[l]; }
   a.theta2 = theta * theta; a.eps2 = softening_sq; a.g = g_const;
-  const int groups = pad64(n) / kGroup;
   const size_t lds_bytes = kWalkFixedLds + (size_t)a.stack_cap * 4;
-  const dim3 grid(groups, L.split);
-  if (quadrupole) tree_walk_kernel<true, ACC, PHI><<<grid, 64, lds_bytes, st>>>(a);
-  else tree_walk_kernel<false, ACC, PHI><<<grid, 64, lds_bytes, st>>>(a);
+  const dim3 grid(group_hi - group_lo, L.split);
+  if (quadrupole) tree_walk_kernel<true, ACC, PHI, RANGED><<<grid, 64, lds_bytes, st>>>(a);
+  else tree_walk_kernel<false, ACC, PHI, RANGED><<<grid, 64, lds_bytes, st>>>(a);
   if (L.split > 1) {
-    const int blocks = (n + 255) / 256;
-    if (ACC) slab_sum_kernel<<<blocks, 256, 0, st>>>(a.slabs, L.split, n, a.order, g_const, acc_out);
-    if constexpr (PHI)
-      phi_slab_sum_kernel<<<blocks, 256, 0, st>>>(a.phi_slabs, L.split, n, a.order, (double)g_const, phi_out);
+    if (RANGED) {
+      const int first = group_lo * kGroup, rows = (group_hi - group_lo) * kGroup, blocks = (rows + 255) / 256;
+      if (ACC) slab_sum_rows_kernel<<<blocks, 256, 0, st>>>(a.slabs, L.split, n, first, rows, g_const, acc_out);
+      if constexpr (PHI)
+        phi_slab_sum_rows_kernel<<<blocks, 256, 0, st>>>(a.phi_slabs, L.split, n, first, rows, (double)g_const, phi_out);
+    } else {
+      const int blocks = (n + 255) / 256;
+      if (ACC) slab_sum_kernel<<<blocks, 256, 0, st>>>(a.slabs, L.split, n, a.order, g_const, acc_out);
+      if constexpr (PHI)
+        phi_slab_sum_kernel<<<blocks, 256, 0, st>>>(a.phi_slabs, L.split, n, a.order, (double)g_const, phi_out);
+    }
   }
-  if (counters_out) counter_kernel<<<1, 256, 0, st>>>(a.gcnt, groups * L.split, counters_out);
+  if (counters_out) counter_kernel<<<1, 256, 0, st>>>(a.gcnt, groups, L.split, group_lo, group_hi, counters_out);
+  return launch_status();
+}
+
+// Keys, sort, sorted bodies and every node from the caller's rows: pos (n,3) beside mass (n,), or STRIDE 4 packed rows
+template <int STRIDE>
+int tree_build(const float* pos, const float* mass, int n, int* order_out, void* workspace, size_t workspace_bytes,
+               nbd_stream_t stream) {
+  if (n < 0 || (n > 0 && (!pos || (STRIDE == 3 && !mass) || !order_out))) return NBD_E_BADARG;
+  if (n == 0) return 0;
+  if (n > kMaxBodies) return NBD_E_UNSUPPORTED;
+  if (!workspace) return NBD_E_BADARG;
+  if (reinterpret_cast<uintptr_t>(workspace) & 255) return NBD_E_BADARG;
+  if (STRIDE == 4 && (reinterpret_cast<uintptr_t>(pos) & 15)) return NBD_E_BADARG;
+  const Levels L = plan_levels(n);
+  const Layout w = layout(n, L);
+  if (workspace_bytes < w.total) return NBD_E_WORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  char* base = static_cast<char*>(workspace);
+  float* part = reinterpret_cast<float*>(base + w.box);
+  float* box = part + kBoxBlocks * 8;
+  uint64_t* keys_in = reinterpret_cast<uint64_t*>(base + w.keys_in);
+  uint64_t* keys_out = reinterpret_cast<uint64_t*>(base + w.keys_out);
+  int* vals_in = reinterpret_cast<int*>(base + w.vals_in);
+  int* order = reinterpret_cast<int*>(base + w.order);
+  f4* posm = reinterpret_cast<f4*>(base + w.posm);
+  f4* nodes = reinterpret_cast<f4*>(base + w.nodes);
+  double* mom = reinterpret_cast<double*>(base + w.mom);
+  float* aabb = reinterpret_cast<float*>(base + w.aabb);
+
+  box_partial_kernel<STRIDE><<<kBoxBlocks, 256, 0, st>>>(pos, n, part);
+  box_final_kernel<<<1, 256, 0, st>>>(part);
+  const int blocks = (n + 255) / 256;
+  key_kernel<STRIDE><<<blocks, 256, 0, st>>>(pos, n, box, keys_in, vals_in);
+  int rc = launch_status();
+  if (rc) return rc;
+  size_t cub_bytes = w.cub_bytes;
+  const hipError_t e = hipcub::DeviceRadixSort::SortPairs(base + w.cub, cub_bytes, keys_in, keys_out, vals_in, order, n, 0,
+                                                          63, st);
+  if (e != hipSuccess) return (int)e;
+  const int n_pad = pad64(n);
+  gather_kernel<STRIDE><<<n_pad / 256 + 1, 256, 0, st>>>(pos, mass, n, n_pad, order, posm, order_out);
+  leaf_kernel<<<(L.count[0] + 127) / 128, 128, 0, st>>>(posm, n, L.count[0], box, mom, aabb, nodes);
+  for (int l = 1; l < L.levels; ++l)
+    upper_kernel<<<(L.count[l] + 127) / 128, 128, 0, st>>>(n, l, L.count[l], L.off[l], L.count[l - 1], L.off[l - 1], box, mom,
+                                                          aabb, nodes);
   return launch_status();
 }
 
@@ -610,63 +748,66 @@ size_t nbd_tree_workspace_bytes(int n) {
 
 int nbd_tree_build_f32(const float* pos, const float* mass, int n, int* order_out, void* workspace, size_t workspace_bytes,
                        nbd_stream_t stream) {
-  if (n < 0 || (n > 0 && (!pos || !mass || !order_out))) return NBD_E_BADARG;
-  if (n == 0) return 0;
-  if (n > kMaxBodies) return NBD_E_UNSUPPORTED;
-  if (!workspace) return NBD_E_BADARG;
-  if (reinterpret_cast<uintptr_t>(workspace) & 255) return NBD_E_BADARG;
-  const Levels L = plan_levels(n);
-  const Layout w = layout(n, L);
-  if (workspace_bytes < w.total) return NBD_E_WORKSPACE;
-  hipStream_t st = (hipStream_t)stream;
-  char* base = static_cast<char*>(workspace);
-  float* part = reinterpret_cast<float*>(base + w.box);
-  float* box = part + kBoxBlocks * 8;
-  uint64_t* keys_in = reinterpret_cast<uint64_t*>(base + w.keys_in);
-  uint64_t* keys_out = reinterpret_cast<uint64_t*>(base + w.keys_out);
-  int* vals_in = reinterpret_cast<int*>(base + w.vals_in);
-  int* order = reinterpret_cast<int*>(base + w.order);
-  f4* posm = reinterpret_cast<f4*>(base + w.posm);
-  f4* nodes = reinterpret_cast<f4*>(base + w.nodes);
-  double* mom = reinterpret_cast<double*>(base + w.mom);
-  float* aabb = reinterpret_cast<float*>(base + w.aabb);
+  return tree_build<3>(pos, mass, n, order_out, workspace, workspace_bytes, stream);
+}
 
-  box_partial_kernel<<<kBoxBlocks, 256, 0, st>>>(pos, n, part);
-  box_final_kernel<<<1, 256, 0, st>>>(part);
-  const int blocks = (n + 255) / 256;
-  key_kernel<<<blocks, 256, 0, st>>>(pos, n, box, keys_in, vals_in);
-  int rc = launch_status();
-  if (rc) return rc;
-  size_t cub_bytes = w.cub_bytes;
-  const hipError_t e = hipcub::DeviceRadixSort::SortPairs(base + w.cub, cub_bytes, keys_in, keys_out, vals_in, order, n, 0,
-                                                          63, st);
-  if (e != hipSuccess) return (int)e;
-  const int n_pad = pad64(n);
-  gather_kernel<<<n_pad / 256 + 1, 256, 0, st>>>(pos, mass, n, n_pad, order, posm, order_out);
-  leaf_kernel<<<(L.count[0] + 127) / 128, 128, 0, st>>>(posm, n, L.count[0], box, mom, aabb, nodes);
-  for (int l = 1; l < L.levels; ++l)
-    upper_kernel<<<(L.count[l] + 127) / 128, 128, 0, st>>>(n, l, L.count[l], L.off[l], L.count[l - 1], L.off[l - 1], box, mom,
-                                                          aabb, nodes);
-  return launch_status();
+int nbd_tree_build_posm_f32(const float* posm, int n, int* order_out, void* workspace, size_t workspace_bytes,
+                            nbd_stream_t stream) {
+  return tree_build<4>(posm, nullptr, n, order_out, workspace, workspace_bytes, stream);
 }
 
 int nbd_tree_accel_f32(const void* workspace, int n, float theta, float softening_sq, float g_const, int quadrupole,
                        float* acc_out, unsigned long long* counters_out, nbd_stream_t stream) {
-  return tree_walk<true, false>(workspace, n, theta, softening_sq, g_const, quadrupole, acc_out, nullptr, counters_out,
+  return tree_walk<true, false, false>(workspace, n, 0, 0, theta, softening_sq, g_const, quadrupole, acc_out, nullptr, counters_out,
                                 stream);
 }
 
 int nbd_tree_potential_f32(const void* workspace, int n, float theta, float softening_sq, float g_const, int quadrupole,
                            double* phi_out, unsigned long long* counters_out, nbd_stream_t stream) {
-  return tree_walk<false, true>(workspace, n, theta, softening_sq, g_const, quadrupole, nullptr, phi_out, counters_out,
+  return tree_walk<false, true, false>(workspace, n, 0, 0, theta, softening_sq, g_const, quadrupole, nullptr, phi_out, counters_out,
                                 stream);
 }
 
 int nbd_tree_accel_potential_f32(const void* workspace, int n, float theta, float softening_sq, float g_const,
                                  int quadrupole, float* acc_out, double* phi_out, unsigned long long* counters_out,
                                  nbd_stream_t stream) {
-  return tree_walk<true, true>(workspace, n, theta, softening_sq, g_const, quadrupole, acc_out, phi_out, counters_out,
+  return tree_walk<true, true, false>(workspace, n, 0, 0, theta, softening_sq, g_const, quadrupole, acc_out, phi_out, counters_out,
                                stream);
+}
+
+int nbd_tree_accel_groups_f32(const void* workspace, int n, int group_lo, int group_hi, float theta, float softening_sq,
+                              float g_const, int quadrupole, float* acc_sorted_out, unsigned long long* counters_out,
+                              nbd_stream_t stream) {
+  return tree_walk<true, false, true>(workspace, n, group_lo, group_hi, theta, softening_sq, g_const, quadrupole,
+                                      acc_sorted_out, nullptr, counters_out, stream);
+}
+
+int nbd_tree_potential_groups_f32(const void* workspace, int n, int group_lo, int group_hi, float theta,
+                                  float softening_sq, float g_const, int quadrupole, double* phi_sorted_out,
+                                  unsigned long long* counters_out, nbd_stream_t stream) {
+  return tree_walk<false, true, true>(workspace, n, group_lo, group_hi, theta, softening_sq, g_const, quadrupole, nullptr,
+                                      phi_sorted_out, counters_out, stream);
+}
+
+int nbd_tree_accel_potential_groups_f32(const void* workspace, int n, int group_lo, int group_hi, float theta,
+                                        float softening_sq, float g_const, int quadrupole, float* acc_sorted_out,
+                                        double* phi_sorted_out, unsigned long long* counters_out, nbd_stream_t stream) {
+  return tree_walk<true, true, true>(workspace, n, group_lo, group_hi, theta, softening_sq, g_const, quadrupole,
+                                     acc_sorted_out, phi_sorted_out, counters_out, stream);
+}
+
+int nbd_tree_scatter_f32(const void* workspace, int n, int lo, int hi, const float* acc_sorted, const double* phi_sorted,
+                         float* acc_out, double* phi_out, nbd_stream_t stream) {
+  if (n < 0 || lo < 0 || lo > hi || hi > n) return NBD_E_BADARG;
+  if (n > kMaxBodies) return NBD_E_UNSUPPORTED;
+  if (lo == hi) return 0;                            // an empty range asks for nothing
+  if (!acc_sorted && !phi_sorted) return NBD_E_BADARG;
+  if (!workspace || (acc_sorted && !acc_out) || (phi_sorted && !phi_out)) return NBD_E_BADARG;
+  if (reinterpret_cast<uintptr_t>(workspace) & 255) return NBD_E_BADARG;
+  const Layout w = layout(n, plan_levels(n));
+  const int* order = reinterpret_cast<const int*>(static_cast<const char*>(workspace) + w.order);
+  scatter_kernel<<<(n + 255) / 256, 256, 0, (hipStream_t)stream>>>(order, n, lo, hi, acc_sorted, phi_sorted, acc_out, phi_out);
+  return launch_status();
 }
 
 }  // extern "C"

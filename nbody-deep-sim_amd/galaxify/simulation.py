@@ -935,8 +935,8 @@ class TreeLeapFrogSimulator(LeapFrogSimulator):
     """LeapFrogSimulator with a Barnes-Hut force in place of the all-pairs sum (csrc/tree_force.hip):
     O(N log N) per step, for softened collisionless systems where a relative force error of ~1e-3 is below the
     discreteness noise. `theta` is the opening angle (0.5; 0 opens every node and is the direct sum in tree order),
-    `quadrupole` keeps the cells' quadrupole term (True). float32 only, one GPU, no gradients: `dtype=torch.float64`,
-    `process_group` and inputs that require grad are refused.
+    `quadrupole` keeps the cells' quadrupole term (True). float32 only, no gradients: `dtype=torch.float64` and inputs
+    that require grad are refused.
 
     positions, velocities and accelerations stay in the caller's order; the bodies are re-sorted along a Morton curve
     and the tree rebuilt inside every force evaluation (`tree_order()` is that permutation, `tree_counters()` the walk's
@@ -953,7 +953,18 @@ class TreeLeapFrogSimulator(LeapFrogSimulator):
                               phi: no second build, no second walk. a and tree_counters() are the plain step's.
     compute_energies() and calc_energy keep the reference's all-pairs -G m m / (|r| + eps) kernel under either value:
     that number has to be the reference's, and its pair term is not the one the cell records expand. It is O(N^2):
-    construct large systems with calc_energy=False."""
+    construct large systems with calc_energy=False.
+
+    `process_group` ("Several ranks"): a rank owns the bodies of its RangePartition of the caller's order,
+    as in every sharded simulator here, and walks the target groups (64 consecutive bodies of the Morton order) of a
+    second RangePartition over the ceil(n/64) groups. The step is kick-drift of the own bodies, the all-gather of the
+    packed rows, sort + build of the WHOLE tree on every rank, the walk of the rank's groups, one all-gather of the
+    finished rows in tree order (two with phi) and a scatter of the own bodies' rows: the results are bit for bit those
+    of one GPU, whatever the number of ranks. compute_accelerations(), compute_potentials() and compute_invariants()
+    (potential="tree") and compute_energies() are collective; compute_potentials() returns the rank's (n_local,) phi,
+    compute_invariants() the global row on every rank, tree_order() the global order, tree_counters() the rank's own
+    walk. potential="direct" diagnostics and run() with calc_invariants stay refused as for every sharded simulator;
+    capture_step() returns False (the step stays eager)."""
 
     def __init__(self, *, theta: float = 0.5, quadrupole: bool = True, potential: str = "direct", **kw):
         name = type(self).__name__
@@ -961,8 +972,10 @@ class TreeLeapFrogSimulator(LeapFrogSimulator):
             raise ValueError(f"{name}: potential must be 'direct' or 'tree', got {potential!r}")
         if kw.get("dtype", torch.float32) != torch.float32:
             raise ValueError(f"{name}: the tree force is float32 only, got dtype={kw['dtype']!r}")
-        if kw.get("process_group") is not None:
-            raise ValueError(f"{name}: there is no range-sharded tree force; process_group is not supported")
+        group = kw.get("process_group")                  # checked here: before a device is resolved
+        if group is not None and not (torch.distributed.is_available()
+                                      and isinstance(group, torch.distributed.ProcessGroup)):
+            raise ValueError(f"{name}: process_group must be a torch.distributed.ProcessGroup, got {group!r}")
         for key in ("positions", "velocities", "masses"):
             if isinstance(kw.get(key), torch.Tensor) and kw[key].requires_grad:
                 raise ValueError(f"{name}: the tree force has no backward; {key} requires grad")
@@ -985,10 +998,79 @@ class TreeLeapFrogSimulator(LeapFrogSimulator):
         self._order = torch.empty((self.n,), dtype=torch.int32, device=self.device)
         self._counters = torch.zeros((2,), dtype=torch.int64, device=self.device)
         self._phi, self._phi_of_step = None, False       # phi of the last step's walk (potential="tree")
+        if self._sharded:
+            self._init_shard_scratch()
         self.accelerations = self.compute_accelerations()
 
+    def _init_shard_scratch(self):
+        """Several ranks: the rank's packed bodies and their gather (as BaseSimulator's), the partition of the target
+        groups, and per exchanged quantity a send buffer of the rank's groups and the array of all groups, both in tree
+        order, with the RowGather that moves one row per GROUP (192 floats of a, 64 doubles of phi) between them."""
+        from nbd import tree
+        p, dev = self.part, self.device
+        self._posm_local = direct.alloc_posm(p.max_count, dev)
+        self._posm_local.zero_()
+        self._mass_local = self.masses[p.lo:p.hi].contiguous()
+        self._gather = nbd_dist.RowGather(p, 4, torch.float32, dev, self.process_group, collective=True)
+        g = self._gpart = nbd_dist.RangePartition(tree.groups(self.n), p.world_size, p.rank)
+        self._acc_send = torch.zeros((g.max_count * tree.GROUP, 3), dtype=torch.float32, device=dev)
+        self._acc_sorted = torch.zeros((g.n * tree.GROUP, 3), dtype=torch.float32, device=dev)
+        self._acc_gather = nbd_dist.RowGather(g, 3 * tree.GROUP, torch.float32, dev, self.process_group, collective=True)
+        self._phi_send = self._phi_sorted = self._phi_gather = None      # made by the first walk that sums phi
+
+    def _phi_exchange(self):
+        from nbd import tree
+        if self._phi_gather is None:
+            g, dev = self._gpart, self.device
+            self._phi_send = torch.zeros((g.max_count * tree.GROUP,), dtype=torch.float64, device=dev)
+            self._phi_sorted = torch.zeros((g.n * tree.GROUP,), dtype=torch.float64, device=dev)
+            self._phi_gather = nbd_dist.RowGather(g, tree.GROUP, torch.float64, dev, self.process_group, collective=True)
+        return self._phi_gather
+
+    def _exchange_groups(self, gather, send, out, cols):
+        """One all-gather of the rank's group rows `send` into `out` (all groups, tree order)."""
+        g = self._gpart
+        send, out = send.view(g.max_count, cols), out.view(g.n, cols)
+        gather.finish(gather.start(send, out), out)
+
+    def _sharded_walk(self, acc: bool, phi: bool, lo: int, hi: int, ev=None) -> tuple:
+        """Several ranks, `_posm_local` already packed: all-gather of the packed rows, sort + build of the whole tree,
+        the walk of the rank's groups for a, phi or both (the fused walk), one all-gather per quantity of the finished
+        rows in tree order, and their scatter to the bodies [lo, hi) of the caller's order -> (acc or None, phi or None).
+        `ev`: events recorded after the gather's start (ev[1]), its end, the build, the walk and the scatter."""
+        from nbd import tree
+        def mark(i):
+            if ev is not None:
+                ev[i].record()
+        n, g, ws = self.n, self._gpart, self._tree_ws
+        handle = self._gather.start(self._posm_local, self._posm)
+        mark(1)
+        self._gather.finish(handle, self._posm)
+        mark(2)
+        tree.build_posm(self._posm, n, ws, self._order)
+        mark(3)
+        rows = g.n_local * tree.GROUP
+        walk = (ws, n, g.lo, g.hi, self.theta, self._eps2, self._g, self.quadrupole)
+        if phi:
+            self._phi_exchange()
+        if acc and phi:
+            tree.accel_potential_groups(*walk, out=(self._acc_send[:rows], self._phi_send[:rows]), counters=self._counters)
+        elif acc:
+            tree.accel_groups(*walk, out=self._acc_send[:rows], counters=self._counters)
+        else:
+            tree.potential_groups(*walk, out=self._phi_send[:rows])       # (the counters keep the last FORCE walk's)
+        mark(4)
+        if acc:
+            self._exchange_groups(self._acc_gather, self._acc_send, self._acc_sorted, 3 * tree.GROUP)
+        if phi:
+            self._exchange_groups(self._phi_gather, self._phi_send, self._phi_sorted, tree.GROUP)
+        out = tree.scatter(ws, n, lo, hi, self._acc_sorted if acc else None, self._phi_sorted if phi else None)
+        mark(5)
+        return out
+
     def compute_accelerations(self) -> torch.Tensor:
-        """The tree force on the current positions -> new (n,3) tensor in the caller's order."""
+        """The tree force on the current positions -> new (n_local,3) tensor in the caller's order (collective when
+        sharded)."""
         return self._tree_force(None)
 
     def _tree_force(self, phi) -> torch.Tensor:
@@ -998,6 +1080,9 @@ class TreeLeapFrogSimulator(LeapFrogSimulator):
         if self._wants_grad():
             raise ValueError(f"{type(self).__name__}.compute_accelerations(): the tree force has no backward")
         from nbd import tree
+        if self._sharded:                                # (only for a: the sharded step() walks by itself)
+            self._pack_local()
+            return self._sharded_walk(True, False, self.part.lo, self.part.hi)[0]
         tree.build(self.positions, self.masses, self._tree_ws, self._order)
         walk = (self._tree_ws, self.n, self.theta, self._eps2, self._g, self.quadrupole)
         if phi is None:
@@ -1008,12 +1093,33 @@ class TreeLeapFrogSimulator(LeapFrogSimulator):
         """potential="direct": LeapFrogSimulator.compute_potentials(). potential="tree": sort + build on the current
         positions, then the phi-only walk -> new (n,) float64 device tensor (coincident distinct bodies at softening 0
         give -inf here too). tree_counters() keeps the last FORCE evaluation's figures."""
-        if self.potential != "tree" or self.n == 0:
+        if self.potential != "tree":
             return super().compute_potentials()
+        if self.n == 0:
+            return torch.zeros((0,), dtype=torch.float64, device=self.device)
+        if self._sharded:                                # collective; the rank's own (n_local,) rows
+            return self._potentials_sharded(self.part.lo, self.part.hi)
         from nbd import tree
         self._fmt.pack(self)                             # compute_invariants() reads the packed bodies next to phi
         tree.build(self.positions, self.masses, self._tree_ws, self._order)
         return tree.potential(self._tree_ws, self.n, self.theta, self._eps2, self._g, self.quadrupole)
+
+    def _potentials_sharded(self, lo: int, hi: int) -> torch.Tensor:
+        """phi of the bodies [lo, hi) of the caller's order from the phi-only walk of the rank's groups; `_posm` is left
+        at the current positions of all bodies."""
+        self._pack_local()
+        return self._sharded_walk(False, True, lo, hi)[1]
+
+    def compute_invariants(self) -> Invariants:
+        """As BaseSimulator.compute_invariants(). Sharded with potential="tree": collective, the global row on every rank
+        (phi of all bodies from the exchanged tree-order rows, the velocities gathered for this call)."""
+        if not self._sharded or self.potential != "tree":
+            return super().compute_invariants()
+        if self.n == 0:
+            return Invariants.from_row([0.0] * direct.INVARIANT_ROW)
+        phi = self._potentials_sharded(0, self.n)
+        vel = self.gather("velocities")
+        return Invariants.from_row(direct.invariants(self._posm, vel, phi, self.n).cpu())
 
     def _invariants_into(self, out_row):
         """potential="tree": the row from the phi the step's own walk left (step() packed `_posm` in its kick-drift)."""
@@ -1042,6 +1148,9 @@ class TreeLeapFrogSimulator(LeapFrogSimulator):
         calc_invariants the force walk is the fused one and leaves phi of the new positions for the invariants."""
         if self.n == 0:
             return
+        if self._sharded:
+            self._sharded_step()
+            return
         half, dt = direct.f32(0.5 * self.dt), direct.f32(self.dt)
         direct.kick_drift(self.positions, self.velocities, self.accelerations, self.masses, half, dt, posm=self._posm)
         self._phi_of_step = self.potential == "tree" and bool(self.calc_invariants)
@@ -1049,6 +1158,43 @@ class TreeLeapFrogSimulator(LeapFrogSimulator):
             self._phi = torch.empty((self.n,), dtype=torch.float64, device=self.device)
         self.accelerations = self._tree_force(self._phi if self._phi_of_step else None)
         direct.kick(self.velocities, self.accelerations, half)
+
+    def _sharded_step(self, ev=None):
+        """The step on several ranks: kick-drift of the own bodies into `_posm_local`, `_sharded_walk` (the fused one with
+        potential="tree" and calc_invariants: `_phi` is then the rank's (n_local,) phi of the new positions), kick. Two
+        collectives (three with phi). `ev`: six events, ev[0] before the kick-drift, the others as `_sharded_walk`."""
+        p = self.part
+        half, dt = direct.f32(0.5 * self.dt), direct.f32(self.dt)
+        if ev is not None:
+            ev[0].record()
+        if p.n_local:
+            direct.kick_drift(self.positions, self.velocities, self.accelerations, self._mass_local, half, dt,
+                              posm=self._posm_local)
+        self._phi_of_step = self.potential == "tree" and bool(self.calc_invariants)
+        self.accelerations, phi = self._sharded_walk(True, self._phi_of_step, p.lo, p.hi, ev)
+        if self._phi_of_step:
+            self._phi = phi
+        if p.n_local:
+            direct.kick(self.velocities, self.accelerations, half)
+
+    def capture_step(self, warmup: int = 3) -> bool:
+        """False, and nothing is captured: the tree step stays eager, alone or sharded (out of scope)."""
+        return False
+
+    def step_phases(self):
+        """One EAGER sharded step with HIP events between its phases: {"kick_drift_ms", "gather_wait_ms" (the all-gather
+        of the packed rows: nothing overlaps it), "build_ms", "walk_ms", "exchange_ms" (the all-gathers of the finished
+        rows and the scatter), "host_enqueue_ms"}. Synchronises; collective."""
+        if not self._sharded or self.n == 0:
+            raise _lib.NbdError("step_phases(): only the range-sharded step has phases")
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(6)]
+        t0 = time.perf_counter()
+        self._sharded_step(ev)
+        host = (time.perf_counter() - t0) * 1e3
+        torch.cuda.synchronize(self.device)
+        return {"kick_drift_ms": ev[0].elapsed_time(ev[1]), "gather_wait_ms": ev[1].elapsed_time(ev[2]),
+                "build_ms": ev[2].elapsed_time(ev[3]), "walk_ms": ev[3].elapsed_time(ev[4]),
+                "exchange_ms": ev[4].elapsed_time(ev[5]), "host_enqueue_ms": host}
 
 
 class EulerSimulator(BaseSimulator):

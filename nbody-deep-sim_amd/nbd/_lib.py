@@ -397,6 +397,14 @@ SIGNATURES = {
     "nbd_tree_potential_f32": (c_int, [c_void_p, c_int, c_float, c_float, c_float, c_int, c_void_p, c_void_p, c_void_p]),
     "nbd_tree_accel_potential_f32": (c_int, [c_void_p, c_int, c_float, c_float, c_float, c_int, c_void_p, c_void_p,
                                              c_void_p, c_void_p]),
+    "nbd_tree_build_posm_f32": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "nbd_tree_accel_groups_f32": (c_int, [c_void_p, c_int, c_int, c_int, c_float, c_float, c_float, c_int, c_void_p,
+                                          c_void_p, c_void_p]),
+    "nbd_tree_potential_groups_f32": (c_int, [c_void_p, c_int, c_int, c_int, c_float, c_float, c_float, c_int, c_void_p,
+                                              c_void_p, c_void_p]),
+    "nbd_tree_accel_potential_groups_f32": (c_int, [c_void_p, c_int, c_int, c_int, c_float, c_float, c_float, c_int,
+                                                    c_void_p, c_void_p, c_void_p, c_void_p]),
+    "nbd_tree_scatter_f32": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     # --- generators on the device (csrc/generators.hip)
     "nbd_disk_workspace_bytes": (c_size_t, [c_int]),
     "nbd_disk_from_draws_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_double, c_double, c_double, c_double,

@@ -3,6 +3,10 @@
 build() orders the bodies along a Morton curve and fills a workspace with the sorted bodies and every node of the implicit
 octree-like hierarchy over that order; accel(), potential() and accel_potential() walk it. All check dtype / shape / contiguity on the host and launch on
 torch's current stream; none allocates unless the caller leaves an output out.
+
+For several ranks ("Several ranks"): build_posm() is build() from packed {x, y, z, m} rows, accel_groups(),
+potential_groups() and accel_potential_groups() walk the target groups [group_lo, group_hi) of groups(n) alone and leave
+their rows in TREE order, scatter() places tree-order rows into a range of the caller's order.
 """
 from __future__ import annotations
 
@@ -96,3 +100,111 @@ def accel_potential(ws: torch.Tensor, n: int, theta: float, softening_sq: float,
     _lib.launch("nbd_tree_accel_potential_f32", ws.device, ws.data_ptr(), int(n), float(theta), float(softening_sq),
                 float(g_const), int(bool(quadrupole)), acc.data_ptr(), phi.data_ptr(), _lib.ptr(counters))
     return acc, phi
+
+
+# ---------------------------------------------------------------- a range of the target groups (several ranks)
+GROUP = 64                       # sorted bodies per target group (one wave of the walk)
+
+
+def groups(n: int) -> int:
+    """Target groups of the walk over n bodies: ceil(n / 64)."""
+    return (int(n) + GROUP - 1) // GROUP
+
+
+def build_posm(posm: torch.Tensor, n: int, ws: torch.Tensor, order: torch.Tensor | None = None) -> torch.Tensor:
+    """build() from packed rows: posm (>= n, 4) {x, y, z, m} (what pack_posm, kick_drift and the all-gather of a sharded
+    step leave). order and everything the walks read are bit for bit build()'s for the same values."""
+    n = int(n)
+    _chk(posm, None, "posm")
+    if posm.dim() != 2 or posm.shape[1] != 4 or posm.shape[0] < n:
+        raise _lib.NbdError(f"posm: expected at least ({n}, 4) rows, got {tuple(posm.shape)}")
+    _chk(ws, None, "workspace", torch.uint8)
+    if order is None:
+        order = torch.empty((n,), dtype=torch.int32, device=posm.device)
+    _chk(order, (n,), "order", torch.int32)
+    _lib.launch("nbd_tree_build_posm_f32", posm.device, posm.data_ptr(), n, order.data_ptr(), ws.data_ptr(), _nbytes(ws))
+    return order
+
+
+def _group_checks(ws: torch.Tensor, n: int, group_lo: int, group_hi: int, counters: torch.Tensor | None) -> int:
+    """The checks of a ranged walk; returns its rows. An empty range launches nothing: its counters are zeroed here."""
+    _walk_checks(ws, n, counters)
+    if not 0 <= group_lo <= group_hi <= groups(n):
+        raise _lib.NbdError(f"groups [{group_lo}, {group_hi}) outside [0, {groups(n)}] of {n} bodies")
+    if group_lo == group_hi and counters is not None:
+        counters.zero_()
+    return (group_hi - group_lo) * GROUP
+
+
+def accel_groups(ws: torch.Tensor, n: int, group_lo: int, group_hi: int, theta: float, softening_sq: float,
+                 g_const: float, quadrupole: bool = True, out: torch.Tensor | None = None,
+                 counters: torch.Tensor | None = None) -> torch.Tensor:
+    """accel() for the target groups [group_lo, group_hi) alone -> ((group_hi - group_lo) 64, 3) in TREE order: row t is
+    sorted body 64 group_lo + t and equals accel()'s row order[64 group_lo + t] bit for bit; rows behind body n - 1 are
+    0. counters: the sums over these groups."""
+    rows = _group_checks(ws, n, group_lo, group_hi, counters)
+    if out is None:
+        out = torch.empty((rows, 3), dtype=torch.float32, device=ws.device)
+    _chk(out, (rows, 3), "acc_sorted_out")
+    _lib.launch("nbd_tree_accel_groups_f32", ws.device, ws.data_ptr(), int(n), int(group_lo), int(group_hi), float(theta),
+                float(softening_sq), float(g_const), int(bool(quadrupole)), out.data_ptr(), _lib.ptr(counters))
+    return out
+
+
+def potential_groups(ws: torch.Tensor, n: int, group_lo: int, group_hi: int, theta: float, softening_sq: float,
+                     g_const: float, quadrupole: bool = True, out: torch.Tensor | None = None,
+                     counters: torch.Tensor | None = None) -> torch.Tensor:
+    """potential() for the target groups [group_lo, group_hi) alone -> ((group_hi - group_lo) 64,) float64 in tree order."""
+    rows = _group_checks(ws, n, group_lo, group_hi, counters)
+    if out is None:
+        out = torch.empty((rows,), dtype=torch.float64, device=ws.device)
+    _chk(out, (rows,), "phi_sorted_out", torch.float64)
+    _lib.launch("nbd_tree_potential_groups_f32", ws.device, ws.data_ptr(), int(n), int(group_lo), int(group_hi),
+                float(theta), float(softening_sq), float(g_const), int(bool(quadrupole)), out.data_ptr(),
+                _lib.ptr(counters))
+    return out
+
+
+def accel_potential_groups(ws: torch.Tensor, n: int, group_lo: int, group_hi: int, theta: float, softening_sq: float,
+                           g_const: float, quadrupole: bool = True, out: tuple | None = None,
+                           counters: torch.Tensor | None = None) -> tuple:
+    """(acc, phi) of the target groups [group_lo, group_hi) from ONE walk, both in tree order. out: None or (acc, phi)."""
+    rows = _group_checks(ws, n, group_lo, group_hi, counters)
+    acc, phi = out if out is not None else (None, None)
+    if acc is None:
+        acc = torch.empty((rows, 3), dtype=torch.float32, device=ws.device)
+    if phi is None:
+        phi = torch.empty((rows,), dtype=torch.float64, device=ws.device)
+    _chk(acc, (rows, 3), "acc_sorted_out"); _chk(phi, (rows,), "phi_sorted_out", torch.float64)
+    _lib.launch("nbd_tree_accel_potential_groups_f32", ws.device, ws.data_ptr(), int(n), int(group_lo), int(group_hi),
+                float(theta), float(softening_sq), float(g_const), int(bool(quadrupole)), acc.data_ptr(), phi.data_ptr(),
+                _lib.ptr(counters))
+    return acc, phi
+
+
+def scatter(ws: torch.Tensor, n: int, lo: int, hi: int, acc_sorted: torch.Tensor | None = None,
+            phi_sorted: torch.Tensor | None = None, out: tuple | None = None) -> tuple:
+    """Tree order -> the bodies [lo, hi) of the caller's order, by the order build() left in `ws`: acc (hi - lo, 3) from
+    acc_sorted (64 groups(n), 3) and / or phi (hi - lo,) from phi_sorted (64 groups(n),). Returns (acc, phi), None for
+    what was not given. out: None or (acc, phi)."""
+    _walk_checks(ws, n, None)
+    if not 0 <= lo <= hi <= n:
+        raise _lib.NbdError(f"bodies [{lo}, {hi}) outside [0, {n}]")
+    if acc_sorted is None and phi_sorted is None:
+        raise _lib.NbdError("scatter: give acc_sorted, phi_sorted or both")
+    rows, dev = groups(n) * GROUP, ws.device
+    acc, phi = out if out is not None else (None, None)
+    if acc_sorted is not None:
+        _chk(acc_sorted, (rows, 3), "acc_sorted")
+        if acc is None:
+            acc = torch.empty((hi - lo, 3), dtype=torch.float32, device=dev)
+        _chk(acc, (hi - lo, 3), "acc_out")
+    if phi_sorted is not None:
+        _chk(phi_sorted, (rows,), "phi_sorted", torch.float64)
+        if phi is None:
+            phi = torch.empty((hi - lo,), dtype=torch.float64, device=dev)
+        _chk(phi, (hi - lo,), "phi_out", torch.float64)
+    _lib.launch("nbd_tree_scatter_f32", dev, ws.data_ptr(), int(n), int(lo), int(hi), _lib.ptr(acc_sorted),
+                _lib.ptr(phi_sorted), _lib.ptr(acc if acc_sorted is not None else None),
+                _lib.ptr(phi if phi_sorted is not None else None))
+    return (acc if acc_sorted is not None else None), (phi if phi_sorted is not None else None)

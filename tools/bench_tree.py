@@ -25,6 +25,18 @@ The tree potential next to the all-pairs potential of csrc/direct_diag.hip, same
   phi_row_error                  256 sampled rows of the tree phi, and of nbd_potential_f32, against float64 all-pairs rows:
                                  |phi - ref| / |ref|
   u_rel_diff                     |U_tree - U_direct| / |U_direct|, U = 1/2 sum m phi in float64 from the two device phi
+
+  python tools/bench_tree.py --ranks [--out FILE] [--sizes N ...] [--worlds W ...]   (default: profiles/r31_tree_ranks.json)
+
+The range-sharded tree force with its ranks EMULATED on one GPU (N = 262 144 and 524 288, theta = 0.5, world 2, 4, 8):
+  full_walk_ms                   nbd_tree_accel_f32 with the counters
+  build_ms, build_posm_ms        nbd_tree_build_f32 and nbd_tree_build_posm_f32 (every rank runs the latter on all bodies)
+  scatter_ms                     nbd_tree_scatter_f32 of rank 0's bodies from the rows of all groups
+  per rank                       the groups [lo, hi) of RangePartition(groups, world, rank), walk_ms of
+                                 nbd_tree_accel_groups_f32 over them alone on the otherwise idle GPU, its counters
+  balance                        slowest rank's walk_ms / (full_walk_ms / world): the partition balances the number of
+                                 groups, not their cost
+No collective runs here: the all-gather and exchange times of a real group are TreeLeapFrogSimulator.step_phases().
 """
 import argparse
 import json
@@ -225,8 +237,75 @@ def case(n, thetas):
     return res
 
 
+def ranks_case(n, theta, worlds):
+    from nbd.dist import RangePartition
+    p, _, m = generate_plummer(n, seed=1)
+    dev = torch.device("cuda", torch.cuda.current_device())
+    pos = torch.tensor(np.asarray(p, np.float32), device=dev)
+    mass = torch.tensor(np.asarray(m, np.float32), device=dev)
+    eps2 = direct.f32(EPS ** 2)
+    posm = direct.pack_posm(pos, mass)
+    tws = tree.workspace(n, dev)
+    order = torch.empty((n,), dtype=torch.int32, device=dev)
+    tacc = torch.empty((n, 3), dtype=torch.float32, device=dev)
+    groups = tree.groups(n)
+    sorted_acc = torch.zeros((groups * tree.GROUP, 3), dtype=torch.float32, device=dev)
+    counters = torch.zeros((2,), dtype=torch.int64, device=dev)
+    reps = max(5, min(50, int(4e6 / n) * 5))
+    own = RangePartition(n, max(worlds), 0)
+    own_acc = torch.empty((own.n_local, 3), dtype=torch.float32, device=dev)
+    runs = {"full_walk_ms": lambda: tree.accel(tws, n, theta, eps2, 1.0, True, out=tacc, counters=counters),
+            "build_ms": lambda: tree.build(pos, mass, tws, order),
+            "build_posm_ms": lambda: tree.build_posm(posm, n, tws, order),
+            "scatter_ms": lambda: tree.scatter(tws, n, own.lo, own.hi, sorted_acc, None, out=(own_acc, None))}
+    ranges = {}
+    for world in worlds:
+        for rank in range(world):
+            g = RangePartition(groups, world, rank)
+            out = sorted_acc[g.lo * tree.GROUP:g.hi * tree.GROUP]
+            ranges[(world, rank)] = (g.lo, g.hi)
+            runs[f"w{world}r{rank}"] = (lambda lo=g.lo, hi=g.hi, out=out:
+                                        tree.accel_groups(tws, n, lo, hi, theta, eps2, 1.0, True, out=out, counters=counters))
+    runs["build_posm_ms"]()
+    for fn in runs.values():
+        fn()
+    torch.cuda.synchronize()
+    t = {key: [] for key in runs}
+    for _ in range(ROUNDS):
+        for key, fn in runs.items():
+            t[key].append(_timed(fn, reps))
+    med = {key: float(np.median(vals)) for key, vals in t.items()}
+    runs["full_walk_ms"]()
+    full_counters = [int(c) for c in counters.cpu().tolist()]
+    res = {"n": n, "theta": theta, "groups": groups, "reps": reps, "plan": tree.plan(n),
+           **{key: med[key] for key in ("full_walk_ms", "build_ms", "build_posm_ms", "scatter_ms")},
+           "scatter_rows": own.n_local, "accepted_cells": full_counters[0], "rejected_level0_nodes": full_counters[1],
+           "worlds": []}
+    for world in worlds:
+        per = []
+        for rank in range(world):
+            runs[f"w{world}r{rank}"]()
+            c = [int(x) for x in counters.cpu().tolist()]
+            lo, hi = ranges[(world, rank)]
+            per.append({"rank": rank, "groups": [lo, hi], "walk_ms": med[f"w{world}r{rank}"],
+                        "walk_ms_min": float(np.min(t[f"w{world}r{rank}"])), "accepted_cells": c[0],
+                        "rejected_level0_nodes": c[1]})
+        slowest = max(r["walk_ms"] for r in per)
+        row = {"world": world, "ranks": per, "slowest_walk_ms": slowest, "sum_walk_ms": sum(r["walk_ms"] for r in per),
+               "balance": slowest / (med["full_walk_ms"] / world),
+               "counters_sum_to_the_full_walk": [sum(r["accepted_cells"] for r in per) == full_counters[0],
+                                                 sum(r["rejected_level0_nodes"] for r in per) == full_counters[1]],
+               "rank_step_ms": med["build_posm_ms"] + slowest + med["scatter_ms"],
+               "one_gpu_step_ms": med["build_ms"] + med["full_walk_ms"]}
+        res["worlds"].append(row)
+        print(json.dumps({"n": n, **{k: v for k, v in row.items() if k != "ranks"}}), flush=True)
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--ranks", action="store_true", help="the ranged walks of emulated ranks next to the full walk")
+    ap.add_argument("--worlds", type=int, nargs="+", default=[2, 4, 8])
     ap.add_argument("--potential", action="store_true", help="the tree potential next to the all-pairs potential")
     ap.add_argument("--out", default=None, help="profiles/r28_tree.json, or profiles/r30_tree_potential.json")
     ap.add_argument("--sizes", type=int, nargs="+", default=[65536, 262144, 524288])
@@ -235,6 +314,16 @@ def main():
     assert torch.cuda.is_available(), "needs the MI355X"
     if args.out is None:
         args.out = os.path.join(ROOT, "profiles", "r30_tree_potential.json" if args.potential else "r28_tree.json")
+    if args.ranks:
+        if args.out == os.path.join(ROOT, "profiles", "r28_tree.json"):
+            args.out = os.path.join(ROOT, "profiles", "r31_tree_ranks.json")
+        sizes = args.sizes if args.sizes != ap.get_default("sizes") else [262144, 524288]
+        res = {"device": torch.cuda.get_device_name(0), "softening": EPS, "quadrupole": True, "rounds": ROUNDS,
+               "cases": [ranks_case(n, 0.5, args.worlds) for n in sizes]}
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump(res, f, indent=1)
+        return
     one = potential_case if args.potential else case
     res = {"device": torch.cuda.get_device_name(0), "softening": EPS, "quadrupole": True, "sampled_rows": SAMPLED,
            "rounds": ROUNDS, "cases": [one(n, args.thetas) for n in args.sizes]}
