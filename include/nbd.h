@@ -1587,6 +1587,73 @@ int nbd_tree_accel_potential_groups_f32(const void* workspace, int n, int group_
 int nbd_tree_scatter_f32(const void* workspace, int n, int lo, int hi, const float* acc_sorted, const double* phi_sorted,
                          float* acc_out, double* phi_out, nbd_stream_t stream);
 
+/* Listed targets ("Block timesteps"): the force on a subset of the bodies, scattered along the curve,
+ * against the tree of ALL bodies, without walking every group of 64 that holds one of them.
+ *   nbd_tree_active_workspace_bytes  bytes of the workspace of nbd_tree_select_active for n bodies (0 for n <= 0 or
+ *                                 n > 2^24), 256-byte aligned: the list (n int32, at byte 0), its count (one int32 at byte
+ *                                 4 n rounded up to 256), the flags in tree order and the compaction's scratch
+ *   nbd_tree_select_active        list[0 .. n_act) = the sorted positions k, ascending, with flags[order[k]] != 0: the
+ *                                 flagged bodies in TREE order. flags (n,) int32 in the caller's order; order is the one
+ *                                 nbd_tree_build*_f32 left in `workspace` for the same n. list_out (n int32) and n_act_out
+ *                                 (one int32), both on the device; NULL: the active workspace's own. An ordered, stable
+ *                                 compaction (hipCUB DeviceSelect): the list is the same from run to run. n_act stays on
+ *                                 the device: the caller reads it back. NULL workspace / flags / active workspace or a
+ *                                 misaligned one: NBD_E_BADARG; a short active workspace: NBD_E_WORKSPACE.
+ *   nbd_tree_accel_active_f32     the walk for the n_act bodies of `list` (the host's copy of what select counted):
+ *                                 target group g is the list entries [64 g, min(n_act, 64 g + 64)), one lane each, its
+ *                                 box the AABB of those bodies alone; everything else is nbd_tree_accel_f32's walk (j == i
+ *                                 excluded by the sorted index). Written: acc_out[order[list[t]]] for t < n_act, acc_out
+ *                                 (n,3) in the CALLER's order -- NO other row -- and counters_out, the sums over the
+ *                                 listed groups. With list = 0 .. n-1 the groups are the full walk's: acc_out and
+ *                                 counters_out equal nbd_tree_accel_f32's bit for bit. An entry outside [0, n) is
+ *                                 skipped. n_act = 0 launches nothing and zeroes counters_out if given. n_act > n, a NULL
+ *                                 list, or workspace_bytes below nbd_tree_workspace_bytes(n): NBD_E_BADARG, no launch.
+ *                                 The slabs and per-group counters are the tree workspace's own, indexed by the active
+ *                                 row and group: walks of one workspace run one after another.
+ * No allocation or synchronisation inside. */
+size_t nbd_tree_active_workspace_bytes(int n);
+int nbd_tree_select_active(const void* workspace, int n, const int* flags, int* list_out, int* n_act_out,
+                           void* active_workspace, size_t active_workspace_bytes, nbd_stream_t stream);
+int nbd_tree_accel_active_f32(const void* workspace, size_t workspace_bytes, int n, const int* list, int n_act, float theta,
+                              float softening_sq, float g_const, int quadrupole, float* acc_out,
+                              unsigned long long* counters_out, nbd_stream_t stream);
+
+/* ---- block timesteps over the tree force (csrc/tree_block.hip; DESIGN.md K-T, "Block timesteps"): the O(N) stages of
+ * a hierarchical kick-drift-kick with individual power-of-two steps. One output interval dt is 2^K ticks, K = max_level
+ * in [0, 20]; body i has levels[i] = k_i in [0, K], the step h_i = dt 2^-k_i = d_i = 2^(K - k_i) ticks, and ticks[i] = the
+ * tick s_i at which its current step began. sched is a device int[NBD_TBLOCK_SCHED_INTS]: {t_next, n_act, clamped, t_cur,
+ * the min being reduced}; zero it once (clamped is cumulative); n_act is written by nbd_tree_select_active, whose
+ * n_act_out the caller points at sched + 1, so that ONE copy of sched[0..2) is the readback of a block step.
+ * Constants are (float)(0.5 dt 2^-k) and (float)(dt ticks 2^-K), formed in fp64; every update is v += c a or x += c v
+ * with product and sum rounded separately (nbd_kick_drift_f32's forms): with K = 0 a step is the shared-step tree
+ * leapfrog's bit for bit. The wanted level is the smallest k with (dt 2^-k)^4 (a.a) <= (2 eta softening)^2 in fp64 from the
+ * fp32 acceleration (a.a summed x, y, z, products and sums rounded separately); none up to K, or a NaN: K, counted in
+ * clamped.
+ *   nbd_tblock_init_levels  levels = the wanted ones of acc (n,3), ticks = 0, a new interval
+ *   nbd_tblock_open         every body: v += a h_i / 2, ticks = 0, residual (n,3) = 0
+ *   nbd_tblock_drift        t_next = min_i (ticks[i] + d_i) (an integer atomic min); every body: x += v (t_next - t_cur)
+ *                           dt / 2^K; posm (nbd_posm_padded_len(n), 4) = {x, m}, zeros in the padding. The sum is
+ *                           compensated: residual (n,3) fp32 carries the rounding of a position from one block step of
+ *                           an interval to the next (y = c v - r; t = x + y; r = (t - x) - y; x = t), because a body at a
+ *                           coarse level is drifted up to 2^K times with one velocity and its roundings repeat. With
+ *                           r = 0, the first drift of an interval, it is x += c v to the bit.
+ *   nbd_tblock_flag         flags[i] = (ticks[i] + d_i == t_next); sched[0] = t_next
+ *   nbd_tblock_close        every flagged body: v += a h_i / 2; the level deepens to the wanted one, or rises by ONE if the
+ *                           wanted one is coarser and t_next is a multiple of the coarser step's ticks; then, if t_next <
+ *                           2^K, v += a h'_i / 2 with the new step and ticks[i] = t_next, else ticks[i] = 0
+ * n <= 0 (but nbd_tblock_init_levels: n < 0), max_level outside [0, 20], dt, eta or softening not positive, a NULL array:
+ * NBD_E_BADARG. Integer atomics only: the same results from run to run. */
+#define NBD_TBLOCK_SCHED_INTS 8
+int nbd_tblock_init_levels(const float* acc, int n, double dt, double eta, double softening, int max_level, int* ticks,
+                           int* levels, int* sched, nbd_stream_t stream);
+int nbd_tblock_open(float* vel, const float* acc, const int* levels, int* ticks, float* residual, int n, int max_level,
+                    double dt, int* sched, nbd_stream_t stream);
+int nbd_tblock_drift(float* pos, const float* vel, const float* mass, const int* levels, const int* ticks, float* residual,
+                     int n, int max_level, double dt, int* sched, float* posm, nbd_stream_t stream);
+int nbd_tblock_flag(const int* levels, const int* ticks, int n, int max_level, int* sched, int* flags, nbd_stream_t stream);
+int nbd_tblock_close(float* vel, const float* acc, const int* flags, int* levels, int* ticks, int n, int max_level, double dt,
+                     double eta, double softening, int* sched, nbd_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -44,6 +44,13 @@
 //           of the last group as 0. Slabs and per-group counters stay indexed by the global body and group. A group's
 //           walk reads nothing of another group's, so a row is bit for bit the full walk's, whatever the range; the
 //           exchanged rows are placed into a range of the caller's order by scatter_kernel through `order`.
+//   active  ("Block timesteps") a block step wants the force on a subset of the bodies, scattered along
+//           the curve. select_active compacts the sorted positions k with flags[order[k]] != 0 into an ascending list
+//           (hipCUB DeviceSelect over the flags in tree order: stable, no atomics, its scratch in a workspace of its
+//           own); ACTIVE walks the whole tree for target groups of 64 consecutive LIST entries, one lane each, T the
+//           AABB of those bodies alone. Slabs and per-group counters are indexed by the active row and group; the
+//           finishing launch writes the rows order[list[t]] of the caller's array and no other. With every body listed
+//           the groups, the boxes and every sum are the full walk's: the same bits.
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 #include <math.h>
@@ -119,6 +126,25 @@ inline Layout layout(int n, const Levels& L) {
   w.cub_bytes = sort_temp_bytes(n);
   w.cub = take(w.cub_bytes);
   w.phi_slabs = take(L.split > 1 ? (size_t)L.split * n * 8 : 0);      // last: every offset above is the force's own
+  w.total = o;
+  return w;
+}
+
+// the workspace of select_active: the list first, then its count, the flags in tree order and the compaction's scratch
+struct ActiveLayout { size_t list, n_act, flags, cub, cub_bytes, total; };
+
+inline ActiveLayout active_layout(int n) {
+  ActiveLayout w = {};
+  size_t o = 0;
+  auto take = [&](size_t bytes) { const size_t at = o; o = align256(o + bytes); return at; };
+  w.list = take((size_t)n * 4);
+  w.n_act = take(sizeof(int));
+  w.flags = take((size_t)n);
+  size_t b = 0;
+  (void)hipcub::DeviceSelect::Flagged(nullptr, b, hipcub::CountingInputIterator<int>(0), (const unsigned char*)nullptr,
+                                      (int*)nullptr, (int*)nullptr, n);   // a size query: nothing runs
+  w.cub_bytes = align256(b);
+  w.cub = take(w.cub_bytes);
   w.total = o;
   return w;
 }
@@ -329,8 +355,15 @@ template <> struct WalkArgsOf<true> { typedef PhiWalkArgs type; };
 template <bool PHI> struct RangedWalkArgs : WalkArgsOf<PHI>::type {
   int group_lo, groups;    // first group of the launch; groups of the whole tree (the stride of gcnt)
 };
-template <bool PHI, bool RANGED> struct KernelArgsOf { typedef typename WalkArgsOf<PHI>::type type; };
-template <bool PHI> struct KernelArgsOf<PHI, true> { typedef RangedWalkArgs<PHI> type; };
+// what a walk of listed targets takes on top: lane t of the launch is sorted body list[t], t < n_act (an entry outside
+// [0, n) is skipped as the lanes behind n_act are); slabs are [split][n][3] by the active row t, gcnt by the active group
+template <bool PHI> struct ActiveWalkArgs : WalkArgsOf<PHI>::type {
+  const int* list;
+  int n_act;
+};
+template <bool PHI, bool RANGED, bool ACTIVE> struct KernelArgsOf { typedef typename WalkArgsOf<PHI>::type type; };
+template <bool PHI> struct KernelArgsOf<PHI, true, false> { typedef RangedWalkArgs<PHI> type; };
+template <bool PHI> struct KernelArgsOf<PHI, false, true> { typedef ActiveWalkArgs<PHI> type; };
 
 __device__ __forceinline__ int lanes_below(unsigned long long mask) {
   return __builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
@@ -354,8 +387,8 @@ __device__ __forceinline__ void add_comp(float& tot, float& comp, float s) {
 
 constexpr int kWalkFixedLds = (3 * kListCap + 64 * kLeaf) * 16 + kListCap * 4 + 2 * kMaxLevels * 4;
 
-template <bool QUAD, bool ACC, bool PHI, bool RANGED>
-__global__ __launch_bounds__(64) void tree_walk_kernel(const typename KernelArgsOf<PHI, RANGED>::type a) {
+template <bool QUAD, bool ACC, bool PHI, bool RANGED, bool ACTIVE>
+__global__ __launch_bounds__(64) void tree_walk_kernel(const typename KernelArgsOf<PHI, RANGED, ACTIVE>::type a) {
   extern __shared__ f4 lds[];
   f4* cells = lds;                                   // [kListCap][3]
   f4* stage = cells + 3 * kListCap;                  // [64][kLeaf] bodies of one pass of the level-0 list
@@ -368,9 +401,21 @@ __global__ __launch_bounds__(64) void tree_walk_kernel(const typename KernelArgs
   int group_lo = 0;                                  // the launch's first target group (its row 0 of a ranged output)
   if constexpr (RANGED) group_lo = a.group_lo;
   const int row0 = group_lo * kGroup;
-  const int i = (group_lo + blockIdx.x) * kGroup + lane;
-  const bool valid = i < a.n;
-  const f4 me = a.posm[i];
+  int target = (group_lo + blockIdx.x) * kGroup + lane;
+  bool listed = target < a.n;
+  const int row = target;                            // the lane's row of the slabs
+  f4 mine;
+  if constexpr (ACTIVE) {                            // the lane's body comes from the list
+    const int e = row < a.n_act ? a.list[row] : -1;
+    listed = (unsigned)e < (unsigned)a.n;
+    target = listed ? e : -1;                        // (no sorted index: nothing is masked for it, nothing stored)
+    mine = listed ? a.posm[e] : f4{0.f, 0.f, 0.f, 0.f};
+  } else {
+    mine = a.posm[target];
+  }
+  const int i = target;
+  const bool valid = listed;
+  const f4 me = mine;
   const float x = me.x, y = me.y, z = me.z;
   // T: the AABB of the group's real bodies
   const float tlx = wave_min(valid ? x : INFINITY), tly = wave_min(valid ? y : INFINITY), tlz = wave_min(valid ? z : INFINITY);
@@ -519,13 +564,13 @@ __global__ __launch_bounds__(64) void tree_walk_kernel(const typename KernelArgs
       const size_t o = (size_t)(RANGED ? i - row0 : a.order[i]) * 3;
       a.acc_out[o] = a.g * ax; a.acc_out[o + 1] = a.g * ay; a.acc_out[o + 2] = a.g * az;
     } else {
-      const size_t o = ((size_t)part * a.n + i) * 3;
+      const size_t o = ((size_t)part * a.n + row) * 3;
       a.slabs[o] = ax; a.slabs[o + 1] = ay; a.slabs[o + 2] = az;
     }
   }
   if constexpr (PHI) if (valid) {
     if (a.split == 1) a.phi_out[RANGED ? i - row0 : a.order[i]] = 0.0 - (double)a.g * phi;
-    else a.phi_slabs[(size_t)part * a.n + i] = phi;
+    else a.phi_slabs[(size_t)part * a.n + row] = phi;
   }
   if (RANGED && !valid && a.split == 1) {           // the rows behind body n - 1 of the last group
     const size_t t = (size_t)(i - row0);
@@ -549,6 +594,30 @@ __global__ __launch_bounds__(256) void slab_sum_kernel(const float* __restrict__
     for (int c = 0; c < 3; ++c) s[c] += slabs[((size_t)w * n + i) * 3 + c];
   const size_t o = (size_t)order[i] * 3;
   for (int c = 0; c < 3; ++c) acc_out[o + c] = g * s[c];
+}
+
+// slab_sum_kernel for the listed bodies: acc_out[order[list[t]]] = g * (slab 0 + slab 1 + ...)[t], t < n_act, the same
+// slabs added in the same order; no other row of acc_out is written
+__global__ __launch_bounds__(256) void active_slab_sum_kernel(const float* __restrict__ slabs, int split, int n,
+                                                              const int* __restrict__ list, int n_act,
+                                                              const int* __restrict__ order, float g,
+                                                              float* __restrict__ acc_out) {
+  const int t = blockIdx.x * 256 + threadIdx.x;
+  if (t >= n_act) return;
+  const int e = list[t];
+  if ((unsigned)e >= (unsigned)n) return;
+  float s[3] = {0.f, 0.f, 0.f};
+  for (int w = 0; w < split; ++w)
+    for (int c = 0; c < 3; ++c) s[c] += slabs[((size_t)w * n + t) * 3 + c];
+  const size_t o = (size_t)order[e] * 3;
+  for (int c = 0; c < 3; ++c) acc_out[o + c] = g * s[c];
+}
+
+// flags in tree order, one byte each: what the compaction of select_active reads
+__global__ __launch_bounds__(256) void tree_flags_kernel(const int* __restrict__ flags, const int* __restrict__ order, int n,
+                                                         unsigned char* __restrict__ sorted_flags) {
+  const int k = blockIdx.x * 256 + threadIdx.x;
+  if (k < n) sorted_flags[k] = flags[order[k]] != 0;
 }
 
 // phi_out[order[i]] = -g * (slab 0 + slab 1 + ...)[i], in fp64: the waves of a group in their fixed order
@@ -628,10 +697,13 @@ __global__ __launch_bounds__(256) void counter_kernel(const unsigned* __restrict
 
 // One walk over a built workspace: the acceleration (acc_out), the potential (phi_out) or both. RANGED: of the target
 // groups [group_lo, group_hi) alone, the outputs in tree order with (group_hi - group_lo) 64 rows; slabs and per-group
-// counters stay where the full walk keeps them, indexed by the global body and group.
-template <bool ACC, bool PHI, bool RANGED>
+// counters stay where the full walk keeps them, indexed by the global body and group. ACTIVE: of the n_act sorted bodies
+// of `list` (checked by the caller: non-null, 1 <= n_act <= n), acc_out in the caller's order and only its listed rows.
+template <bool ACC, bool PHI, bool RANGED, bool ACTIVE = false>
 int tree_walk(const void* workspace, int n, int group_lo, int group_hi, float theta, float softening_sq, float g_const,
-              int quadrupole, float* acc_out, double* phi_out, unsigned long long* counters_out, nbd_stream_t stream) {
+              int quadrupole, float* acc_out, double* phi_out, unsigned long long* counters_out, nbd_stream_t stream,
+              const int* list = nullptr, int n_act = 0) {
+  static_assert(!ACTIVE || (ACC && !PHI && !RANGED), "the listed walk sums the acceleration alone");
   if (n < 0 || !(theta >= 0.f)) return NBD_E_BADARG;
   if (RANGED) {                                      // the range first: an empty one asks for nothing
     if (n > kMaxBodies) return NBD_E_UNSUPPORTED;
@@ -642,13 +714,13 @@ int tree_walk(const void* workspace, int n, int group_lo, int group_hi, float th
   if (n == 0) return 0;
   if (n > kMaxBodies) return NBD_E_UNSUPPORTED;
   if (reinterpret_cast<uintptr_t>(workspace) & 255) return NBD_E_BADARG;
-  const int groups = pad64(n) / kGroup;
+  const int groups = ACTIVE ? pad64(n_act) / kGroup : pad64(n) / kGroup;
   if (!RANGED) { group_lo = 0; group_hi = groups; }
   const Levels L = plan_levels(n);
   const Layout w = layout(n, L);
   hipStream_t st = (hipStream_t)stream;
   char* base = static_cast<char*>(const_cast<void*>(workspace));
-  typename KernelArgsOf<PHI, RANGED>::type a = {};
+  typename KernelArgsOf<PHI, RANGED, ACTIVE>::type a = {};
   a.posm = reinterpret_cast<const f4*>(base + w.posm);
   a.nodes = reinterpret_cast<const f4*>(base + w.nodes);
   a.order = reinterpret_cast<const int*>(base + w.order);
@@ -657,16 +729,19 @@ int tree_walk(const void* workspace, int n, int group_lo, int group_hi, float th
   a.slabs = reinterpret_cast<float*>(base + w.slabs);
   if constexpr (PHI) { a.phi_out = phi_out; a.phi_slabs = reinterpret_cast<double*>(base + w.phi_slabs); }
   if constexpr (RANGED) { a.group_lo = group_lo; a.groups = groups; }
+  if constexpr (ACTIVE) { a.list = list; a.n_act = n_act; }
   a.n = n; a.levels = L.levels; a.stack_cap = kStackPerLevel * L.levels;
   a.split = L.split; a.start_level = L.start_level;
   for (int l = 0; l < kMaxLevels; ++l) { a.count[l] = L.count[l]; a.off[l] = L.off[l]; }
   a.theta2 = theta * theta; a.eps2 = softening_sq; a.g = g_const;
   const size_t lds_bytes = kWalkFixedLds + (size_t)a.stack_cap * 4;
   const dim3 grid(group_hi - group_lo, L.split);
-  if (quadrupole) tree_walk_kernel<true, ACC, PHI, RANGED><<<grid, 64, lds_bytes, st>>>(a);
-  else tree_walk_kernel<false, ACC, PHI, RANGED><<<grid, 64, lds_bytes, st>>>(a);
+  if (quadrupole) tree_walk_kernel<true, ACC, PHI, RANGED, ACTIVE><<<grid, 64, lds_bytes, st>>>(a);
+  else tree_walk_kernel<false, ACC, PHI, RANGED, ACTIVE><<<grid, 64, lds_bytes, st>>>(a);
   if (L.split > 1) {
-    if (RANGED) {
+    if (ACTIVE) {
+      active_slab_sum_kernel<<<(n_act + 255) / 256, 256, 0, st>>>(a.slabs, L.split, n, list, n_act, a.order, g_const, acc_out);
+    } else if (RANGED) {
       const int first = group_lo * kGroup, rows = (group_hi - group_lo) * kGroup, blocks = (rows + 255) / 256;
       if (ACC) slab_sum_rows_kernel<<<blocks, 256, 0, st>>>(a.slabs, L.split, n, first, rows, g_const, acc_out);
       if constexpr (PHI)
@@ -744,6 +819,53 @@ int nbd_tree_plan(int n, int* levels, int* nodes_total) {
 size_t nbd_tree_workspace_bytes(int n) {
   if (n <= 0 || n > kMaxBodies) return 0;
   return layout(n, plan_levels(n)).total;
+}
+
+size_t nbd_tree_active_workspace_bytes(int n) {
+  if (n <= 0 || n > kMaxBodies) return 0;
+  return active_layout(n).total;
+}
+
+int nbd_tree_select_active(const void* workspace, int n, const int* flags, int* list_out, int* n_act_out,
+                           void* active_workspace, size_t active_workspace_bytes, nbd_stream_t stream) {
+  if (n < 0 || (n > 0 && (!workspace || !flags || !active_workspace))) return NBD_E_BADARG;
+  if (n > kMaxBodies) return NBD_E_UNSUPPORTED;
+  hipStream_t st = (hipStream_t)stream;
+  if (n == 0) {
+    if (n_act_out && hipMemsetAsync(n_act_out, 0, sizeof(int), st) != hipSuccess) return (int)hipGetLastError();
+    return 0;
+  }
+  if ((reinterpret_cast<uintptr_t>(workspace) | reinterpret_cast<uintptr_t>(active_workspace)) & 255) return NBD_E_BADARG;
+  const ActiveLayout w = active_layout(n);
+  if (active_workspace_bytes < w.total) return NBD_E_WORKSPACE;
+  char* base = static_cast<char*>(active_workspace);
+  const int* order = reinterpret_cast<const int*>(static_cast<const char*>(workspace) + layout(n, plan_levels(n)).order);
+  unsigned char* sorted_flags = reinterpret_cast<unsigned char*>(base + w.flags);
+  if (!list_out) list_out = reinterpret_cast<int*>(base + w.list);
+  if (!n_act_out) n_act_out = reinterpret_cast<int*>(base + w.n_act);
+  tree_flags_kernel<<<(n + 255) / 256, 256, 0, st>>>(flags, order, n, sorted_flags);
+  const int rc = launch_status();
+  if (rc) return rc;
+  size_t cub_bytes = w.cub_bytes;
+  const hipError_t e = hipcub::DeviceSelect::Flagged(base + w.cub, cub_bytes, hipcub::CountingInputIterator<int>(0),
+                                                     sorted_flags, list_out, n_act_out, n, st);
+  return e == hipSuccess ? launch_status() : (int)e;
+}
+
+int nbd_tree_accel_active_f32(const void* workspace, size_t workspace_bytes, int n, const int* list, int n_act, float theta,
+                              float softening_sq, float g_const, int quadrupole, float* acc_out,
+                              unsigned long long* counters_out, nbd_stream_t stream) {
+  if (n < 0 || n_act < 0 || n_act > n || !(theta >= 0.f)) return NBD_E_BADARG;
+  if (n > kMaxBodies) return NBD_E_UNSUPPORTED;
+  if (n_act == 0) {                                  // nothing is listed: nothing is walked, nothing is written
+    if (counters_out && hipMemsetAsync(counters_out, 0, 2 * sizeof(unsigned long long), (hipStream_t)stream) != hipSuccess)
+      return (int)hipGetLastError();
+    return 0;
+  }
+  if (!list || !workspace || !acc_out) return NBD_E_BADARG;
+  if (workspace_bytes < layout(n, plan_levels(n)).total) return NBD_E_BADARG;
+  return tree_walk<true, false, false, true>(workspace, n, 0, 0, theta, softening_sq, g_const, quadrupole, acc_out, nullptr,
+                                             counters_out, stream, list, n_act);
 }
 
 int nbd_tree_build_f32(const float* pos, const float* mass, int n, int* order_out, void* workspace, size_t workspace_bytes,

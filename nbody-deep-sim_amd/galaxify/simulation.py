@@ -1197,6 +1197,128 @@ class TreeLeapFrogSimulator(LeapFrogSimulator):
                 "exchange_ms": ev[4].elapsed_time(ev[5]), "host_enqueue_ms": host}
 
 
+class BlockTreeLeapFrogSimulator(TreeLeapFrogSimulator):
+    """TreeLeapFrogSimulator with individual block timesteps: a hierarchical kick-drift-kick with power-of-two steps, as in
+    GADGET-2 (csrc/tree_block.hip, the listed-target walk of csrc/tree_force.hip; DESIGN.md K-T, "Block timesteps"), an
+    extension the reference does not have. `dt` is the output interval and the longest step: one step() advances every
+    body by dt, in 2^max_level ticks. Body i moves with its own step h_i = dt 2^-k_i, k_i = levels[i] in [0, max_level],
+    from the criterion of softened collisionless runs, h_i <= sqrt(2 eta softening / |a_i|) (the level may deepen at any
+    block step and rises by one where the block allows). step() gives every body the opening kick of its step and then
+    runs block steps: ALL bodies drift to the next due time (a compensated fp32 sum: within an interval a position takes
+    one rounding however many block steps drift it), the tree is sorted and rebuilt on all of them, the force is
+    walked for the due bodies alone (target groups of 64 due bodies in tree order), and those get the closing kick, a
+    new level and the opening kick of their next step. At the end of the interval every body is due and the state is
+    synchronised, so run() keeps returning one state per dt, compute_*() are TreeLeapFrogSimulator's, and with
+    potential="tree" and calc_invariants the invariants row still comes from the phi of the step's own last walk.
+    Initial levels (at construction, and after dt, eta, softening or max_level change) come from the same criterion.
+
+    Counters (cumulative Python ints): `block_steps`, `active_targets` (the sum of n_act) and `clamped` (levels the
+    criterion wanted deeper than max_level, NaN criteria included). `levels` is int32 on the device; setting
+    `level_history` to a list records a CPU copy of it after every block step. `accelerations` is updated in place.
+    tree_order() and tree_counters() are those of the last force evaluation. Eager-only: every block step reads
+    {t_next, n_act} back to the host; capture_step() returns False. With max_level=0 it is TreeLeapFrogSimulator bit for
+    bit. float32 only, no process_group, softening > 0 (the criterion needs it): each refusal is a ValueError before a
+    device is resolved."""
+
+    MAX_LEVEL_LIMIT = 20
+
+    def __init__(self, *, eta: float = 0.025, max_level: int = 10, **kw):
+        name = type(self).__name__
+        self.eta, self.max_level = eta, max_level
+        self.dt, self.softening = kw.get("dt", 0.01), kw.get("softening", 0.1)
+        self._check_block_params()
+        if kw.get("process_group") is not None:
+            raise ValueError(f"{name}: there is no range-sharded block step; process_group is not supported")
+        self.levels = None
+        self.block_steps = self.active_targets = self.clamped = 0
+        self.level_history = None
+        super().__init__(**kw)
+
+    def _check_block_params(self):
+        name = type(self).__name__
+        if not (type(self.max_level) is int and 0 <= self.max_level <= self.MAX_LEVEL_LIMIT):
+            raise ValueError(f"{name}: max_level must be an int in [0, {self.MAX_LEVEL_LIMIT}], got {self.max_level!r}")
+        if not (self.eta > 0 and self.dt > 0):
+            raise ValueError(f"{name}: dt and eta must be positive, got dt={self.dt!r}, eta={self.eta!r}")
+        if not self.softening > 0:
+            raise ValueError(f"{name}: the step criterion needs softening > 0, got {self.softening!r}")
+
+    def _init_scratch(self):
+        from nbd import tree
+        super()._init_scratch()                          # (ends with the construction-time force)
+        n, dev = self.n, self.device
+        self.levels = torch.zeros(n, dtype=torch.int32, device=dev)
+        self._ticks = torch.zeros(n, dtype=torch.int32, device=dev)
+        self._flags = torch.zeros(n, dtype=torch.int32, device=dev)
+        self._sched = torch.zeros(tree.BLOCK_SCHED_INTS, dtype=torch.int32, device=dev)
+        self._sched_host = torch.zeros(tree.BLOCK_SCHED_INTS, dtype=torch.int32).pin_memory()
+        self._act_ws = tree.active_workspace(n, dev) if n else None
+        self._act_list = torch.zeros(n, dtype=torch.int32, device=dev)
+        self._residual = torch.zeros((n, 3), dtype=torch.float32, device=dev)      # the drift's rounding, per interval
+        self._leveled_for = None
+        self._set_levels()
+
+    def _set_levels(self):
+        from nbd import tree
+        self._check_block_params()
+        self._leveled_for = (self.dt, self.eta, self.softening, self.max_level)
+        if self.n == 0:
+            return
+        tree.block_init_levels(self.accelerations, self.dt, self.eta, self.softening, self.max_level, self._ticks,
+                               self.levels, self._sched)
+        self._sched_host.copy_(self._sched)
+        self.clamped = int(self._sched_host[2])
+
+    def step(self):
+        """One output interval: the opening kick of every body, then block steps until every body is back at tick
+        2^max_level (at most 2^max_level of them)."""
+        if self.n == 0:
+            return
+        if self._leveled_for != (self.dt, self.eta, self.softening, self.max_level):
+            self._set_levels()
+        from nbd import tree
+        who = type(self).__name__
+        n, K, ws, host = self.n, self.max_level, self._tree_ws, self._sched_host
+        end, t_prev = 1 << K, 0
+        walk = (self.theta, self._eps2, self._g, self.quadrupole)
+        want_phi = self.potential == "tree" and bool(self.calc_invariants)
+        self._phi_of_step = False
+        tree.block_open(self.velocities, self.accelerations, self.levels, self._ticks, self._residual, K, self.dt,
+                        self._sched)
+        for _ in range(end):
+            tree.block_drift(self.positions, self.velocities, self.masses, self.levels, self._ticks, self._residual, K,
+                             self.dt, self._sched, self._posm)
+            tree.build_posm(self._posm, n, ws, self._order)
+            tree.block_flag(self.levels, self._ticks, K, self._sched, self._flags)
+            tree.select_active(ws, n, self._flags, self._act_list, active_ws=self._act_ws, n_act_out=self._sched[1:2])
+            host.copy_(self._sched)                      # the one readback of a block step
+            t_next, n_act = int(host[0]), int(host[1])
+            if not (t_prev < t_next <= end and 1 <= n_act <= n):
+                raise RuntimeError(f"{who}: corrupt schedule (t_next={t_next}, n_act={n_act}, previous tick {t_prev})")
+            if n_act < n:
+                tree.accel_active(ws, n, self._act_list, n_act, *walk, out=self.accelerations, counters=self._counters)
+            elif want_phi and t_next == end:             # the interval's last walk leaves phi for the invariants
+                if self._phi is None:
+                    self._phi = torch.empty((n,), dtype=torch.float64, device=self.device)
+                tree.accel_potential(ws, n, *walk, out=(self.accelerations, self._phi), counters=self._counters)
+                self._phi_of_step = True
+            else:
+                tree.accel(ws, n, *walk, out=self.accelerations, counters=self._counters)
+            tree.block_close(self.velocities, self.accelerations, self._flags, self.levels, self._ticks, K, self.dt,
+                             self.eta, self.softening, self._sched)
+            self.block_steps += 1
+            self.active_targets += n_act
+            if self.level_history is not None:
+                self.level_history.append(self.levels.cpu())
+            if t_next == end:
+                break
+            t_prev = t_next
+        else:
+            raise RuntimeError(f"{who}: interval not finished within {end} block steps")
+        host.copy_(self._sched)
+        self.clamped = int(host[2])
+
+
 class EulerSimulator(BaseSimulator):
     """The reference's Euler integrator; `dtype=torch.float64` as in LeapFrogSimulator."""
 

@@ -405,6 +405,20 @@ SIGNATURES = {
     "nbd_tree_accel_potential_groups_f32": (c_int, [c_void_p, c_int, c_int, c_int, c_float, c_float, c_float, c_int,
                                                     c_void_p, c_void_p, c_void_p, c_void_p]),
     "nbd_tree_scatter_f32": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "nbd_tree_active_workspace_bytes": (c_size_t, [c_int]),
+    "nbd_tree_select_active": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "nbd_tree_accel_active_f32": (c_int, [c_void_p, c_size_t, c_int, c_void_p, c_int, c_float, c_float, c_float, c_int,
+                                          c_void_p, c_void_p, c_void_p]),
+    # --- block timesteps over the tree force (csrc/tree_block.hip)
+    "nbd_tblock_init_levels": (c_int, [c_void_p, c_int, c_double, c_double, c_double, c_int, c_void_p, c_void_p, c_void_p,
+                                       c_void_p]),
+    "nbd_tblock_open": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_double, c_void_p,
+                                c_void_p]),
+    "nbd_tblock_drift": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_double,
+                                 c_void_p, c_void_p, c_void_p]),
+    "nbd_tblock_flag": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "nbd_tblock_close": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_double, c_double,
+                                 c_double, c_void_p, c_void_p]),
     # --- generators on the device (csrc/generators.hip)
     "nbd_disk_workspace_bytes": (c_size_t, [c_int]),
     "nbd_disk_from_draws_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_double, c_double, c_double, c_double,

@@ -7,6 +7,10 @@ torch's current stream; none allocates unless the caller leaves an output out.
 For several ranks ("Several ranks"): build_posm() is build() from packed {x, y, z, m} rows, accel_groups(),
 potential_groups() and accel_potential_groups() walk the target groups [group_lo, group_hi) of groups(n) alone and leave
 their rows in TREE order, scatter() places tree-order rows into a range of the caller's order.
+
+For block timesteps ("Block timesteps"): select_active() compacts the flagged bodies into a list of sorted
+positions, accel_active() walks the tree for the listed bodies alone and writes only their rows; block_*() are the O(N)
+stages of csrc/tree_block.hip.
 """
 from __future__ import annotations
 
@@ -208,3 +212,126 @@ def scatter(ws: torch.Tensor, n: int, lo: int, hi: int, acc_sorted: torch.Tensor
                 _lib.ptr(phi_sorted), _lib.ptr(acc if acc_sorted is not None else None),
                 _lib.ptr(phi if phi_sorted is not None else None))
     return (acc if acc_sorted is not None else None), (phi if phi_sorted is not None else None)
+
+
+# ---------------------------------------------------------------- listed targets (block timesteps)
+def active_workspace_bytes(n: int) -> int:
+    return _lib.lib().nbd_tree_active_workspace_bytes(int(n))
+
+
+def active_workspace(n: int, device) -> torch.Tensor:
+    """The buffer select_active() works in for n bodies: the list, its count, the flags in tree order and the
+    compaction's scratch."""
+    plan(n)
+    return alloc_bytes(active_workspace_bytes(n), device)
+
+
+def _active_views(active_ws: torch.Tensor, n: int) -> tuple:
+    """(list (n,), n_act (1,)) int32 views of the active workspace: the list at byte 0, the count at 4 n rounded up to 256."""
+    ints = active_ws.view(torch.int32)
+    at = (4 * n + 255) // 256 * 64
+    return ints[:n], ints[at:at + 1]
+
+
+def select_active(ws: torch.Tensor, n: int, flags: torch.Tensor, list_out: torch.Tensor | None = None, *,
+                  active_ws: torch.Tensor | None = None, n_act_out: torch.Tensor | None = None) -> tuple:
+    """(list, n_act): list[:n_act] = the sorted positions k, ascending, with flags[order[k]] != 0 -- the flagged bodies in
+    tree order, `order` the one build() left in `ws`. flags (n,) int32 in the caller's order. An ordered compaction: the
+    same list from run to run. n_act is a (1,) int32 DEVICE tensor: the caller reads it back. active_ws: the buffer of
+    active_workspace(n) (None: one is allocated here; with it given nothing is allocated and nothing synchronises).
+    list_out (n,) int32 and n_act_out (1,) int32: None for the active workspace's own."""
+    n = int(n)
+    _chk(flags, (n,), "flags", torch.int32)
+    if n == 0:
+        return (list_out if list_out is not None else torch.empty((0,), dtype=torch.int32, device=flags.device),
+                n_act_out.zero_() if n_act_out is not None else torch.zeros((1,), dtype=torch.int32, device=flags.device))
+    _walk_checks(ws, n, None)
+    if active_ws is None:
+        active_ws = active_workspace(n, ws.device)
+    _chk(active_ws, None, "active workspace", torch.uint8)
+    own_list, own_count = _active_views(active_ws, n) if _nbytes(active_ws) >= active_workspace_bytes(n) else (None, None)
+    if list_out is not None:
+        _chk(list_out, (n,), "list_out", torch.int32)
+    if n_act_out is not None:
+        _chk(n_act_out, (1,), "n_act_out", torch.int32)
+    _lib.launch("nbd_tree_select_active", ws.device, ws.data_ptr(), n, flags.data_ptr(), _lib.ptr(list_out),
+                _lib.ptr(n_act_out), active_ws.data_ptr(), _nbytes(active_ws))
+    return (list_out if list_out is not None else own_list), (n_act_out if n_act_out is not None else own_count)
+
+
+def accel_active(ws: torch.Tensor, n: int, list: torch.Tensor, n_act: int, theta: float, softening_sq: float,
+                 g_const: float, quadrupole: bool = True, out: torch.Tensor | None = None,
+                 counters: torch.Tensor | None = None) -> torch.Tensor:
+    """The tree force on the n_act bodies of `list` (select_active()'s; n_act the host's copy of its count) against the
+    tree of all n bodies in `ws`: target groups of 64 consecutive list entries, each with the box of its own bodies.
+    Written: the rows order[list[t]], t < n_act, of out (n,3) in the caller's order, and NO other row (out None: the others
+    are 0). With every body listed, out and counters equal accel()'s bit for bit. n_act = 0 launches nothing and zeroes
+    the counters."""
+    n, n_act = int(n), int(n_act)
+    _chk(ws, None, "workspace", torch.uint8)
+    if counters is not None:
+        _chk(counters, (2,), "counters", torch.int64)
+    if list is not None:
+        _chk(list, None, "list", torch.int32)
+        if list.dim() != 1 or list.shape[0] < n_act:
+            raise _lib.NbdError(f"list: {n_act} entries asked for, it holds {tuple(list.shape)}")
+    if out is None:
+        out = torch.zeros((n, 3), dtype=torch.float32, device=ws.device)
+    _chk(out, (n, 3), "acc_out")
+    _lib.launch("nbd_tree_accel_active_f32", ws.device, ws.data_ptr(), _nbytes(ws), n, _lib.ptr(list), n_act, float(theta),
+                float(softening_sq), float(g_const), int(bool(quadrupole)), out.data_ptr(), _lib.ptr(counters))
+    return out
+
+
+# ---------------------------------------------------------------- the O(N) stages of a block step (csrc/tree_block.hip)
+BLOCK_SCHED_INTS = 8             # NBD_TBLOCK_SCHED_INTS: {t_next, n_act, clamped, t_cur, the min being reduced, ...}
+
+
+def block_init_levels(acc: torch.Tensor, dt: float, eta: float, softening: float, max_level: int, ticks: torch.Tensor,
+                      levels: torch.Tensor, sched: torch.Tensor) -> None:
+    """levels = the criterion's on acc (n,3), ticks = 0; sched[2] grows by the levels wanted deeper than max_level."""
+    n = acc.shape[0]
+    _chk(acc, (n, 3), "acc"); _chk(ticks, (n,), "ticks", torch.int32); _chk(levels, (n,), "levels", torch.int32)
+    _chk(sched, (BLOCK_SCHED_INTS,), "sched", torch.int32)
+    _lib.launch("nbd_tblock_init_levels", acc.device, acc.data_ptr(), n, float(dt), float(eta), float(softening),
+                int(max_level), ticks.data_ptr(), levels.data_ptr(), sched.data_ptr())
+
+
+def block_open(vel, acc, levels, ticks, residual, max_level: int, dt: float, sched) -> None:
+    """The opening kick of an interval: v += a h_i / 2 for every body, ticks = 0, the drift's residual (n,3) = 0."""
+    n = vel.shape[0]
+    _chk(vel, (n, 3), "vel"); _chk(acc, (n, 3), "acc"); _chk(residual, (n, 3), "residual")
+    _chk(ticks, (n,), "ticks", torch.int32); _chk(levels, (n,), "levels", torch.int32)
+    _lib.launch("nbd_tblock_open", vel.device, vel.data_ptr(), acc.data_ptr(), levels.data_ptr(), ticks.data_ptr(),
+                residual.data_ptr(), n, int(max_level), float(dt), sched.data_ptr())
+
+
+def block_drift(pos, vel, mass, levels, ticks, residual, max_level: int, dt: float, sched, posm) -> None:
+    """t_next = min (ticks + d) on the device; every body drifts there (a compensated sum: `residual` (n,3) carries the
+    rounding of a position between the block steps of an interval); posm = the packed rows build_posm() takes."""
+    n = pos.shape[0]
+    _chk(pos, (n, 3), "pos"); _chk(vel, (n, 3), "vel"); _chk(mass, (n,), "mass"); _chk(residual, (n, 3), "residual")
+    _chk(ticks, (n,), "ticks", torch.int32); _chk(levels, (n,), "levels", torch.int32)
+    _chk(posm, None, "posm")
+    if posm.dim() != 2 or posm.shape[1] != 4 or posm.shape[0] < _lib.lib().nbd_posm_padded_len(n):
+        raise _lib.NbdError(f"posm: need (>= padded_len({n}), 4), got {tuple(posm.shape)}")
+    _lib.launch("nbd_tblock_drift", pos.device, pos.data_ptr(), vel.data_ptr(), mass.data_ptr(), levels.data_ptr(),
+                ticks.data_ptr(), residual.data_ptr(), n, int(max_level), float(dt), sched.data_ptr(), posm.data_ptr())
+
+
+def block_flag(levels, ticks, max_level: int, sched, flags) -> None:
+    """flags[i] = body i is due at t_next; sched[0] = t_next."""
+    n = levels.shape[0]
+    _chk(ticks, (n,), "ticks", torch.int32); _chk(levels, (n,), "levels", torch.int32)
+    _chk(flags, (n,), "flags", torch.int32)
+    _lib.launch("nbd_tblock_flag", levels.device, levels.data_ptr(), ticks.data_ptr(), n, int(max_level), sched.data_ptr(),
+                flags.data_ptr())
+
+
+def block_close(vel, acc, flags, levels, ticks, max_level: int, dt: float, eta: float, softening: float, sched) -> None:
+    """The flagged bodies: closing kick, new level, and (inside the interval) the opening kick of the next step."""
+    n = vel.shape[0]
+    _chk(vel, (n, 3), "vel"); _chk(acc, (n, 3), "acc"); _chk(flags, (n,), "flags", torch.int32)
+    _chk(ticks, (n,), "ticks", torch.int32); _chk(levels, (n,), "levels", torch.int32)
+    _lib.launch("nbd_tblock_close", vel.device, vel.data_ptr(), acc.data_ptr(), flags.data_ptr(), levels.data_ptr(),
+                ticks.data_ptr(), n, int(max_level), float(dt), float(eta), float(softening), sched.data_ptr())
