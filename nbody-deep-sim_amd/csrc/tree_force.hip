@@ -39,7 +39,7 @@
 //           accumulates at compile time; the acc-only instantiations are the force kernel unchanged.
 //   ranks   ("Several ranks") every rank builds the same tree from the gathered packed rows {x, y, z, m}
 //           (the row stride of the box / key / gather kernels is a compile-time switch: the same values, the same bits)
-//           and walks a contiguous range of the target groups: RANGED offsets the group index of the same walk and
+//           and walks a contiguous range of the target groups: kRange offsets the group index of the same walk and
 //           leaves the finished rows in TREE order, row 0 = the first body of the range's first group, the padding rows
 //           of the last group as 0. Slabs and per-group counters stay indexed by the global body and group. A group's
 //           walk reads nothing of another group's, so a row is bit for bit the full walk's, whatever the range; the
@@ -47,7 +47,7 @@
 //   active  ("Block timesteps") a block step wants the force on a subset of the bodies, scattered along
 //           the curve. select_active compacts the sorted positions k with flags[order[k]] != 0 into an ascending list
 //           (hipCUB DeviceSelect over the flags in tree order: stable, no atomics, its scratch in a workspace of its
-//           own); ACTIVE walks the whole tree for target groups of 64 consecutive LIST entries, one lane each, T the
+//           own); kList walks the whole tree for target groups of 64 consecutive LIST entries, one lane each, T the
 //           AABB of those bodies alone. Slabs and per-group counters are indexed by the active row and group; the
 //           finishing launch writes the rows order[list[t]] of the caller's array and no other. With every body listed
 //           the groups, the boxes and every sum are the full walk's: the same bits.
@@ -332,6 +332,11 @@ __global__ __launch_bounds__(128) void upper_kernel(int n, int lvl, int count, i
 
 // ---------------------------------------------------------------- the walk
 
+// which targets a launch walks: every group of the tree, the groups [group_lo, group_lo + gridDim.x) alone, or groups
+// of 64 consecutive entries of a list of sorted positions. A compile-time switch of the walk and of its finishing kernel.
+enum class Targets { kAll, kRange, kList };
+
+// One record for every instantiation; an instantiation reads the fields of its own switches and no others.
 struct WalkArgs {
   const f4* posm;          // sorted bodies, padded to a multiple of 64 with zeros
   const f4* nodes;         // 3 per node, level 0 first
@@ -342,28 +347,16 @@ struct WalkArgs {
   int n, levels, stack_cap, split, start_level;
   int count[kMaxLevels], off[kMaxLevels];
   float theta2, eps2, g;
-};
-// what a walk that sums the potential takes (the acc-only walk keeps WalkArgs: its kernel arguments do not move)
-struct PhiWalkArgs : WalkArgs {
+  // PHI
   double* phi_out;         // (n,) in the caller's order (written here when split == 1)
   double* phi_slabs;       // [split][n] partial sums in tree order (split > 1)
-};
-template <bool PHI> struct WalkArgsOf { typedef WalkArgs type; };
-template <> struct WalkArgsOf<true> { typedef PhiWalkArgs type; };
-// what a walk of the target groups [group_lo, group_lo + gridDim.x) alone takes on top: acc_out / phi_out are then in TREE
-// order, row 0 = sorted body 64 group_lo, the padding rows of the last group included (the full walks keep their structs)
-template <bool PHI> struct RangedWalkArgs : WalkArgsOf<PHI>::type {
+  // kRange: acc_out / phi_out are in TREE order, row 0 = sorted body 64 group_lo, the last group's padding rows included
   int group_lo, groups;    // first group of the launch; groups of the whole tree (the stride of gcnt)
-};
-// what a walk of listed targets takes on top: lane t of the launch is sorted body list[t], t < n_act (an entry outside
-// [0, n) is skipped as the lanes behind n_act are); slabs are [split][n][3] by the active row t, gcnt by the active group
-template <bool PHI> struct ActiveWalkArgs : WalkArgsOf<PHI>::type {
+  // kList: lane t of the launch is sorted body list[t], t < n_act (an entry outside [0, n) is skipped as the lanes behind
+  // n_act are); slabs are [split][n][3] by the active row t, gcnt by the active group
   const int* list;
   int n_act;
 };
-template <bool PHI, bool RANGED, bool ACTIVE> struct KernelArgsOf { typedef typename WalkArgsOf<PHI>::type type; };
-template <bool PHI> struct KernelArgsOf<PHI, true, false> { typedef RangedWalkArgs<PHI> type; };
-template <bool PHI> struct KernelArgsOf<PHI, false, true> { typedef ActiveWalkArgs<PHI> type; };
 
 __device__ __forceinline__ int lanes_below(unsigned long long mask) {
   return __builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
@@ -387,8 +380,9 @@ __device__ __forceinline__ void add_comp(float& tot, float& comp, float s) {
 
 constexpr int kWalkFixedLds = (3 * kListCap + 64 * kLeaf) * 16 + kListCap * 4 + 2 * kMaxLevels * 4;
 
-template <bool QUAD, bool ACC, bool PHI, bool RANGED, bool ACTIVE>
-__global__ __launch_bounds__(64) void tree_walk_kernel(const typename KernelArgsOf<PHI, RANGED, ACTIVE>::type a) {
+template <bool QUAD, bool ACC, bool PHI, Targets TG>
+__global__ __launch_bounds__(64) void tree_walk_kernel(const WalkArgs a) {
+  constexpr bool RANGED = TG == Targets::kRange, ACTIVE = TG == Targets::kList;
   extern __shared__ f4 lds[];
   f4* cells = lds;                                   // [kListCap][3]
   f4* stage = cells + 3 * kListCap;                  // [64][kLeaf] bodies of one pass of the level-0 list
@@ -584,33 +578,33 @@ __global__ __launch_bounds__(64) void tree_walk_kernel(const typename KernelArgs
   }
 }
 
-// acc_out[order[i]] = g * (slab 0 + slab 1 + ...)[i]: the waves of a group in their fixed order
-__global__ __launch_bounds__(256) void slab_sum_kernel(const float* __restrict__ slabs, int split, int n,
-                                                       const int* __restrict__ order, float g, float* __restrict__ acc_out) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  float s[3] = {0.f, 0.f, 0.f};
-  for (int w = 0; w < split; ++w)
-    for (int c = 0; c < 3; ++c) s[c] += slabs[((size_t)w * n + i) * 3 + c];
-  const size_t o = (size_t)order[i] * 3;
-  for (int c = 0; c < 3; ++c) acc_out[o + c] = g * s[c];
-}
+// what a finished row is, from the sum of its partial sums: the acceleration g s (float), the potential -g s (double)
+__device__ __forceinline__ float finish_row(float g, float s) { return g * s; }
+__device__ __forceinline__ double finish_row(double g, double s) { return 0.0 - g * s; }
 
-// slab_sum_kernel for the listed bodies: acc_out[order[list[t]]] = g * (slab 0 + slab 1 + ...)[t], t < n_act, the same
-// slabs added in the same order; no other row of acc_out is written
-__global__ __launch_bounds__(256) void active_slab_sum_kernel(const float* __restrict__ slabs, int split, int n,
-                                                              const int* __restrict__ list, int n_act,
-                                                              const int* __restrict__ order, float g,
-                                                              float* __restrict__ acc_out) {
+// The finishing launch of a split walk, for a (T = float, 3 columns) and for phi (T = double, 1 column): row t < rows adds
+// the `split` partial sums of its slab row -- the waves of a group in their fixed order, each column on its own --
+// scales by G and is placed by the walk's targets:
+//   kAll    slab row t          -> out[order[t]]
+//   kRange  slab row first + t  -> out[t], the TREE order; a row at or behind body n is written as 0
+//   kList   slab row t          -> out[order[list[t]]]; an entry outside [0, n) is skipped, no other row is written
+template <typename T, Targets TG>
+__global__ __launch_bounds__(256) void slab_sum_kernel(const T* __restrict__ slabs, int split, int n, int first, int rows,
+                                                       const int* __restrict__ order, const int* __restrict__ list, T g,
+                                                       T* __restrict__ out) {
+  constexpr int kCols = sizeof(T) == sizeof(float) ? 3 : 1;
   const int t = blockIdx.x * 256 + threadIdx.x;
-  if (t >= n_act) return;
-  const int e = list[t];
-  if ((unsigned)e >= (unsigned)n) return;
-  float s[3] = {0.f, 0.f, 0.f};
-  for (int w = 0; w < split; ++w)
-    for (int c = 0; c < 3; ++c) s[c] += slabs[((size_t)w * n + t) * 3 + c];
-  const size_t o = (size_t)order[e] * 3;
-  for (int c = 0; c < 3; ++c) acc_out[o + c] = g * s[c];
+  if (t >= rows) return;
+  const int i = TG == Targets::kRange ? first + t : t;           // the slab row
+  const int body = TG == Targets::kList ? list[t] : i;           // the sorted position it belongs to
+  const bool real = (unsigned)body < (unsigned)n;
+  if (TG != Targets::kRange && !real) return;
+  T s[kCols] = {};
+  if (real)
+    for (int w = 0; w < split; ++w)
+      for (int c = 0; c < kCols; ++c) s[c] += slabs[((size_t)w * n + i) * kCols + c];
+  const size_t o = (size_t)(TG == Targets::kRange ? t : order[body]) * kCols;
+  for (int c = 0; c < kCols; ++c) out[o + c] = real ? finish_row(g, s[c]) : T(0);
 }
 
 // flags in tree order, one byte each: what the compaction of select_active reads
@@ -618,43 +612,6 @@ __global__ __launch_bounds__(256) void tree_flags_kernel(const int* __restrict__
                                                          unsigned char* __restrict__ sorted_flags) {
   const int k = blockIdx.x * 256 + threadIdx.x;
   if (k < n) sorted_flags[k] = flags[order[k]] != 0;
-}
-
-// phi_out[order[i]] = -g * (slab 0 + slab 1 + ...)[i], in fp64: the waves of a group in their fixed order
-__global__ __launch_bounds__(256) void phi_slab_sum_kernel(const double* __restrict__ slabs, int split, int n,
-                                                           const int* __restrict__ order, double g,
-                                                           double* __restrict__ phi_out) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  double s = 0.0;
-  for (int w = 0; w < split; ++w) s += slabs[(size_t)w * n + i];
-  phi_out[order[i]] = 0.0 - g * s;
-}
-
-// The two kernels above for the sorted bodies [first, first + rows) alone and in TREE order: row t of the output is
-// sorted body first + t, the same 8 slabs added in the same order, rows at or behind body n written as 0.
-__global__ __launch_bounds__(256) void slab_sum_rows_kernel(const float* __restrict__ slabs, int split, int n, int first,
-                                                            int rows, float g, float* __restrict__ acc_sorted) {
-  const int t = blockIdx.x * 256 + threadIdx.x;
-  if (t >= rows) return;
-  const int i = first + t;
-  float s[3] = {0.f, 0.f, 0.f};
-  if (i < n)
-    for (int w = 0; w < split; ++w)
-      for (int c = 0; c < 3; ++c) s[c] += slabs[((size_t)w * n + i) * 3 + c];
-  for (int c = 0; c < 3; ++c) acc_sorted[(size_t)t * 3 + c] = i < n ? g * s[c] : 0.f;
-}
-
-__global__ __launch_bounds__(256) void phi_slab_sum_rows_kernel(const double* __restrict__ slabs, int split, int n,
-                                                                int first, int rows, double g,
-                                                                double* __restrict__ phi_sorted) {
-  const int t = blockIdx.x * 256 + threadIdx.x;
-  if (t >= rows) return;
-  const int i = first + t;
-  double s = 0.0;
-  if (i < n)
-    for (int w = 0; w < split; ++w) s += slabs[(size_t)w * n + i];
-  phi_sorted[t] = i < n ? 0.0 - g * s : 0.0;
 }
 
 // out[order[k] - lo] = sorted[k] for every sorted position k whose body the range [lo, hi) of the caller's order holds
@@ -695,65 +652,77 @@ __global__ __launch_bounds__(256) void counter_kernel(const unsigned* __restrict
   if (threadIdx.x == 0) { counters[0] = red[0][0]; counters[1] = red[1][0]; }
 }
 
-// One walk over a built workspace: the acceleration (acc_out), the potential (phi_out) or both. RANGED: of the target
+// The targets of one walk: the groups [group_lo, group_hi) of the tree (kRange; kAll walks every group and reads
+// neither), or the n_act sorted positions of `list` (kList).
+struct TargetSet {
+  int group_lo, group_hi;
+  const int* list;
+  int n_act;
+};
+
+// One walk over a built workspace: the acceleration (acc_out), the potential (phi_out) or both. kRange: of the target
 // groups [group_lo, group_hi) alone, the outputs in tree order with (group_hi - group_lo) 64 rows; slabs and per-group
-// counters stay where the full walk keeps them, indexed by the global body and group. ACTIVE: of the n_act sorted bodies
-// of `list` (checked by the caller: non-null, 1 <= n_act <= n), acc_out in the caller's order and only its listed rows.
-template <bool ACC, bool PHI, bool RANGED, bool ACTIVE = false>
-int tree_walk(const void* workspace, int n, int group_lo, int group_hi, float theta, float softening_sq, float g_const,
-              int quadrupole, float* acc_out, double* phi_out, unsigned long long* counters_out, nbd_stream_t stream,
-              const int* list = nullptr, int n_act = 0) {
-  static_assert(!ACTIVE || (ACC && !PHI && !RANGED), "the listed walk sums the acceleration alone");
+// counters stay where the full walk keeps them, indexed by the global body and group. kList: of the n_act sorted bodies
+// of `list`, acc_out in the caller's order and only its listed rows; slabs and counters by the active row and group.
+template <bool ACC, bool PHI, Targets TG>
+int tree_walk(const void* workspace, int n, TargetSet t, float theta, float softening_sq, float g_const, int quadrupole,
+              float* acc_out, double* phi_out, unsigned long long* counters_out, nbd_stream_t stream) {
+  static_assert(TG != Targets::kList || (ACC && !PHI), "the listed walk sums the acceleration alone");
+  hipStream_t st = (hipStream_t)stream;
   if (n < 0 || !(theta >= 0.f)) return NBD_E_BADARG;
-  if (RANGED) {                                      // the range first: an empty one asks for nothing
+  if (TG == Targets::kRange) {                       // the range first: an empty one asks for nothing
     if (n > kMaxBodies) return NBD_E_UNSUPPORTED;
-    if (group_lo < 0 || group_lo > group_hi || group_hi > pad64(n) / kGroup) return NBD_E_BADARG;
-    if (group_lo == group_hi) return 0;
+    if (t.group_lo < 0 || t.group_lo > t.group_hi || t.group_hi > pad64(n) / kGroup) return NBD_E_BADARG;
+    if (t.group_lo == t.group_hi) return 0;
+  }
+  if (TG == Targets::kList) {                        // the list first: an empty one is not walked, nothing is written
+    if (t.n_act < 0 || t.n_act > n) return NBD_E_BADARG;
+    if (n > kMaxBodies) return NBD_E_UNSUPPORTED;
+    if (t.n_act == 0) {
+      if (counters_out && hipMemsetAsync(counters_out, 0, 2 * sizeof(unsigned long long), st) != hipSuccess)
+        return (int)hipGetLastError();
+      return 0;
+    }
+    if (!t.list) return NBD_E_BADARG;
   }
   if (n > 0 && (!workspace || (ACC && !acc_out) || (PHI && !phi_out))) return NBD_E_BADARG;
   if (n == 0) return 0;
   if (n > kMaxBodies) return NBD_E_UNSUPPORTED;
   if (reinterpret_cast<uintptr_t>(workspace) & 255) return NBD_E_BADARG;
-  const int groups = ACTIVE ? pad64(n_act) / kGroup : pad64(n) / kGroup;
-  if (!RANGED) { group_lo = 0; group_hi = groups; }
+  const int groups = pad64(TG == Targets::kList ? t.n_act : n) / kGroup;
+  if (TG != Targets::kRange) { t.group_lo = 0; t.group_hi = groups; }
   const Levels L = plan_levels(n);
   const Layout w = layout(n, L);
-  hipStream_t st = (hipStream_t)stream;
   char* base = static_cast<char*>(const_cast<void*>(workspace));
-  typename KernelArgsOf<PHI, RANGED, ACTIVE>::type a = {};
+  WalkArgs a = {};
   a.posm = reinterpret_cast<const f4*>(base + w.posm);
   a.nodes = reinterpret_cast<const f4*>(base + w.nodes);
   a.order = reinterpret_cast<const int*>(base + w.order);
   a.acc_out = acc_out;
   a.gcnt = reinterpret_cast<unsigned*>(base + w.gcnt);
   a.slabs = reinterpret_cast<float*>(base + w.slabs);
-  if constexpr (PHI) { a.phi_out = phi_out; a.phi_slabs = reinterpret_cast<double*>(base + w.phi_slabs); }
-  if constexpr (RANGED) { a.group_lo = group_lo; a.groups = groups; }
-  if constexpr (ACTIVE) { a.list = list; a.n_act = n_act; }
+  a.phi_out = phi_out; a.phi_slabs = reinterpret_cast<double*>(base + w.phi_slabs);
+  a.group_lo = t.group_lo; a.groups = groups;
+  a.list = t.list; a.n_act = t.n_act;
   a.n = n; a.levels = L.levels; a.stack_cap = kStackPerLevel * L.levels;
   a.split = L.split; a.start_level = L.start_level;
   for (int l = 0; l < kMaxLevels; ++l) { a.count[l] = L.count[l]; a.off[l] = L.off[l]; }
   a.theta2 = theta * theta; a.eps2 = softening_sq; a.g = g_const;
   const size_t lds_bytes = kWalkFixedLds + (size_t)a.stack_cap * 4;
-  const dim3 grid(group_hi - group_lo, L.split);
-  if (quadrupole) tree_walk_kernel<true, ACC, PHI, RANGED, ACTIVE><<<grid, 64, lds_bytes, st>>>(a);
-  else tree_walk_kernel<false, ACC, PHI, RANGED, ACTIVE><<<grid, 64, lds_bytes, st>>>(a);
+  const dim3 grid(t.group_hi - t.group_lo, L.split);
+  if (quadrupole) tree_walk_kernel<true, ACC, PHI, TG><<<grid, 64, lds_bytes, st>>>(a);
+  else tree_walk_kernel<false, ACC, PHI, TG><<<grid, 64, lds_bytes, st>>>(a);
   if (L.split > 1) {
-    if (ACTIVE) {
-      active_slab_sum_kernel<<<(n_act + 255) / 256, 256, 0, st>>>(a.slabs, L.split, n, list, n_act, a.order, g_const, acc_out);
-    } else if (RANGED) {
-      const int first = group_lo * kGroup, rows = (group_hi - group_lo) * kGroup, blocks = (rows + 255) / 256;
-      if (ACC) slab_sum_rows_kernel<<<blocks, 256, 0, st>>>(a.slabs, L.split, n, first, rows, g_const, acc_out);
-      if constexpr (PHI)
-        phi_slab_sum_rows_kernel<<<blocks, 256, 0, st>>>(a.phi_slabs, L.split, n, first, rows, (double)g_const, phi_out);
-    } else {
-      const int blocks = (n + 255) / 256;
-      if (ACC) slab_sum_kernel<<<blocks, 256, 0, st>>>(a.slabs, L.split, n, a.order, g_const, acc_out);
-      if constexpr (PHI)
-        phi_slab_sum_kernel<<<blocks, 256, 0, st>>>(a.phi_slabs, L.split, n, a.order, (double)g_const, phi_out);
-    }
+    const int first = t.group_lo * kGroup;
+    const int rows = TG == Targets::kAll ? n : TG == Targets::kList ? t.n_act : (t.group_hi - t.group_lo) * kGroup;
+    const int blocks = (rows + 255) / 256;
+    if constexpr (ACC)
+      slab_sum_kernel<float, TG><<<blocks, 256, 0, st>>>(a.slabs, L.split, n, first, rows, a.order, t.list, g_const, acc_out);
+    if constexpr (PHI)
+      slab_sum_kernel<double, TG><<<blocks, 256, 0, st>>>(a.phi_slabs, L.split, n, first, rows, a.order, t.list,
+                                                          (double)g_const, phi_out);
   }
-  if (counters_out) counter_kernel<<<1, 256, 0, st>>>(a.gcnt, groups, L.split, group_lo, group_hi, counters_out);
+  if (counters_out) counter_kernel<<<1, 256, 0, st>>>(a.gcnt, groups, L.split, t.group_lo, t.group_hi, counters_out);
   return launch_status();
 }
 
@@ -855,17 +824,10 @@ int nbd_tree_select_active(const void* workspace, int n, const int* flags, int* 
 int nbd_tree_accel_active_f32(const void* workspace, size_t workspace_bytes, int n, const int* list, int n_act, float theta,
                               float softening_sq, float g_const, int quadrupole, float* acc_out,
                               unsigned long long* counters_out, nbd_stream_t stream) {
-  if (n < 0 || n_act < 0 || n_act > n || !(theta >= 0.f)) return NBD_E_BADARG;
-  if (n > kMaxBodies) return NBD_E_UNSUPPORTED;
-  if (n_act == 0) {                                  // nothing is listed: nothing is walked, nothing is written
-    if (counters_out && hipMemsetAsync(counters_out, 0, 2 * sizeof(unsigned long long), (hipStream_t)stream) != hipSuccess)
-      return (int)hipGetLastError();
-    return 0;
-  }
-  if (!list || !workspace || !acc_out) return NBD_E_BADARG;
-  if (workspace_bytes < layout(n, plan_levels(n)).total) return NBD_E_BADARG;
-  return tree_walk<true, false, false, true>(workspace, n, 0, 0, theta, softening_sq, g_const, quadrupole, acc_out, nullptr,
-                                             counters_out, stream, list, n_act);
+  // the one check tree_walk() cannot make, asked where it would launch: the size of the caller's workspace
+  if (n_act >= 1 && n_act <= n && n <= kMaxBodies && workspace_bytes < layout(n, plan_levels(n)).total) return NBD_E_BADARG;
+  return tree_walk<true, false, Targets::kList>(workspace, n, {0, 0, list, n_act}, theta, softening_sq, g_const, quadrupole,
+                                                acc_out, nullptr, counters_out, stream);
 }
 
 int nbd_tree_build_f32(const float* pos, const float* mass, int n, int* order_out, void* workspace, size_t workspace_bytes,
@@ -880,42 +842,42 @@ int nbd_tree_build_posm_f32(const float* posm, int n, int* order_out, void* work
 
 int nbd_tree_accel_f32(const void* workspace, int n, float theta, float softening_sq, float g_const, int quadrupole,
                        float* acc_out, unsigned long long* counters_out, nbd_stream_t stream) {
-  return tree_walk<true, false, false>(workspace, n, 0, 0, theta, softening_sq, g_const, quadrupole, acc_out, nullptr, counters_out,
-                                stream);
+  return tree_walk<true, false, Targets::kAll>(workspace, n, {}, theta, softening_sq, g_const, quadrupole, acc_out, nullptr,
+                                               counters_out, stream);
 }
 
 int nbd_tree_potential_f32(const void* workspace, int n, float theta, float softening_sq, float g_const, int quadrupole,
                            double* phi_out, unsigned long long* counters_out, nbd_stream_t stream) {
-  return tree_walk<false, true, false>(workspace, n, 0, 0, theta, softening_sq, g_const, quadrupole, nullptr, phi_out, counters_out,
-                                stream);
+  return tree_walk<false, true, Targets::kAll>(workspace, n, {}, theta, softening_sq, g_const, quadrupole, nullptr, phi_out,
+                                               counters_out, stream);
 }
 
 int nbd_tree_accel_potential_f32(const void* workspace, int n, float theta, float softening_sq, float g_const,
                                  int quadrupole, float* acc_out, double* phi_out, unsigned long long* counters_out,
                                  nbd_stream_t stream) {
-  return tree_walk<true, true, false>(workspace, n, 0, 0, theta, softening_sq, g_const, quadrupole, acc_out, phi_out, counters_out,
-                               stream);
+  return tree_walk<true, true, Targets::kAll>(workspace, n, {}, theta, softening_sq, g_const, quadrupole, acc_out, phi_out,
+                                              counters_out, stream);
 }
 
 int nbd_tree_accel_groups_f32(const void* workspace, int n, int group_lo, int group_hi, float theta, float softening_sq,
                               float g_const, int quadrupole, float* acc_sorted_out, unsigned long long* counters_out,
                               nbd_stream_t stream) {
-  return tree_walk<true, false, true>(workspace, n, group_lo, group_hi, theta, softening_sq, g_const, quadrupole,
-                                      acc_sorted_out, nullptr, counters_out, stream);
+  return tree_walk<true, false, Targets::kRange>(workspace, n, {group_lo, group_hi}, theta, softening_sq, g_const,
+                                                 quadrupole, acc_sorted_out, nullptr, counters_out, stream);
 }
 
 int nbd_tree_potential_groups_f32(const void* workspace, int n, int group_lo, int group_hi, float theta,
                                   float softening_sq, float g_const, int quadrupole, double* phi_sorted_out,
                                   unsigned long long* counters_out, nbd_stream_t stream) {
-  return tree_walk<false, true, true>(workspace, n, group_lo, group_hi, theta, softening_sq, g_const, quadrupole, nullptr,
-                                      phi_sorted_out, counters_out, stream);
+  return tree_walk<false, true, Targets::kRange>(workspace, n, {group_lo, group_hi}, theta, softening_sq, g_const,
+                                                 quadrupole, nullptr, phi_sorted_out, counters_out, stream);
 }
 
 int nbd_tree_accel_potential_groups_f32(const void* workspace, int n, int group_lo, int group_hi, float theta,
                                         float softening_sq, float g_const, int quadrupole, float* acc_sorted_out,
                                         double* phi_sorted_out, unsigned long long* counters_out, nbd_stream_t stream) {
-  return tree_walk<true, true, true>(workspace, n, group_lo, group_hi, theta, softening_sq, g_const, quadrupole,
-                                     acc_sorted_out, phi_sorted_out, counters_out, stream);
+  return tree_walk<true, true, Targets::kRange>(workspace, n, {group_lo, group_hi}, theta, softening_sq, g_const,
+                                                quadrupole, acc_sorted_out, phi_sorted_out, counters_out, stream);
 }
 
 int nbd_tree_scatter_f32(const void* workspace, int n, int lo, int hi, const float* acc_sorted, const double* phi_sorted,

@@ -1050,15 +1050,11 @@ class TreeLeapFrogSimulator(LeapFrogSimulator):
         tree.build_posm(self._posm, n, ws, self._order)
         mark(3)
         rows = g.n_local * tree.GROUP
-        walk = (ws, n, g.lo, g.hi, self.theta, self._eps2, self._g, self.quadrupole)
         if phi:
             self._phi_exchange()
-        if acc and phi:
-            tree.accel_potential_groups(*walk, out=(self._acc_send[:rows], self._phi_send[:rows]), counters=self._counters)
-        elif acc:
-            tree.accel_groups(*walk, out=self._acc_send[:rows], counters=self._counters)
-        else:
-            tree.potential_groups(*walk, out=self._phi_send[:rows])       # (the counters keep the last FORCE walk's)
+        tree.walk(ws, n, self.theta, self._eps2, self._g, self.quadrupole, acc=acc, phi=phi, groups=(g.lo, g.hi),
+                  out=(self._acc_send[:rows] if acc else None, self._phi_send[:rows] if phi else None),
+                  counters=self._counters if acc else None)          # (phi alone: they keep the last FORCE walk's)
         mark(4)
         if acc:
             self._exchange_groups(self._acc_gather, self._acc_send, self._acc_sorted, 3 * tree.GROUP)
@@ -1084,10 +1080,14 @@ class TreeLeapFrogSimulator(LeapFrogSimulator):
             self._pack_local()
             return self._sharded_walk(True, False, self.part.lo, self.part.hi)[0]
         tree.build(self.positions, self.masses, self._tree_ws, self._order)
-        walk = (self._tree_ws, self.n, self.theta, self._eps2, self._g, self.quadrupole)
-        if phi is None:
-            return tree.accel(*walk, counters=self._counters)
-        return tree.accel_potential(*walk, out=(None, phi), counters=self._counters)[0]
+        return tree.walk(self._tree_ws, self.n, self.theta, self._eps2, self._g, self.quadrupole, phi=phi is not None,
+                         out=(None, phi), counters=self._counters)[0]
+
+    def _phi_buffer(self) -> torch.Tensor:
+        """(n,) float64 for the phi a step's own walk leaves, made by the first step that wants it."""
+        if self._phi is None:
+            self._phi = torch.empty((self.n,), dtype=torch.float64, device=self.device)
+        return self._phi
 
     def compute_potentials(self) -> torch.Tensor:
         """potential="direct": LeapFrogSimulator.compute_potentials(). potential="tree": sort + build on the current
@@ -1102,7 +1102,7 @@ class TreeLeapFrogSimulator(LeapFrogSimulator):
         from nbd import tree
         self._fmt.pack(self)                             # compute_invariants() reads the packed bodies next to phi
         tree.build(self.positions, self.masses, self._tree_ws, self._order)
-        return tree.potential(self._tree_ws, self.n, self.theta, self._eps2, self._g, self.quadrupole)
+        return tree.walk(self._tree_ws, self.n, self.theta, self._eps2, self._g, self.quadrupole, acc=False, phi=True)[1]
 
     def _potentials_sharded(self, lo: int, hi: int) -> torch.Tensor:
         """phi of the bodies [lo, hi) of the caller's order from the phi-only walk of the rank's groups; `_posm` is left
@@ -1154,9 +1154,7 @@ class TreeLeapFrogSimulator(LeapFrogSimulator):
         half, dt = direct.f32(0.5 * self.dt), direct.f32(self.dt)
         direct.kick_drift(self.positions, self.velocities, self.accelerations, self.masses, half, dt, posm=self._posm)
         self._phi_of_step = self.potential == "tree" and bool(self.calc_invariants)
-        if self._phi_of_step and self._phi is None:
-            self._phi = torch.empty((self.n,), dtype=torch.float64, device=self.device)
-        self.accelerations = self._tree_force(self._phi if self._phi_of_step else None)
+        self.accelerations = self._tree_force(self._phi_buffer() if self._phi_of_step else None)
         direct.kick(self.velocities, self.accelerations, half)
 
     def _sharded_step(self, ev=None):
@@ -1295,15 +1293,11 @@ class BlockTreeLeapFrogSimulator(TreeLeapFrogSimulator):
             t_next, n_act = int(host[0]), int(host[1])
             if not (t_prev < t_next <= end and 1 <= n_act <= n):
                 raise RuntimeError(f"{who}: corrupt schedule (t_next={t_next}, n_act={n_act}, previous tick {t_prev})")
-            if n_act < n:
-                tree.accel_active(ws, n, self._act_list, n_act, *walk, out=self.accelerations, counters=self._counters)
-            elif want_phi and t_next == end:             # the interval's last walk leaves phi for the invariants
-                if self._phi is None:
-                    self._phi = torch.empty((n,), dtype=torch.float64, device=self.device)
-                tree.accel_potential(ws, n, *walk, out=(self.accelerations, self._phi), counters=self._counters)
-                self._phi_of_step = True
-            else:
-                tree.accel(ws, n, *walk, out=self.accelerations, counters=self._counters)
+            # the interval's last walk, of every body, leaves phi for the invariants
+            fused = want_phi and t_next == end and n_act == n
+            tree.walk(ws, n, *walk, phi=fused, active=(self._act_list, n_act) if n_act < n else None,
+                      out=(self.accelerations, self._phi_buffer() if fused else None), counters=self._counters)
+            self._phi_of_step = fused
             tree.block_close(self.velocities, self.accelerations, self._flags, self.levels, self._ticks, K, self.dt,
                              self.eta, self.softening, self._sched)
             self.block_steps += 1

@@ -1,8 +1,10 @@
 """Typed wrappers over the tree-code entry points of libnbd_hip.so (csrc/tree_force.hip).
 
 build() orders the bodies along a Morton curve and fills a workspace with the sorted bodies and every node of the implicit
-octree-like hierarchy over that order; accel(), potential() and accel_potential() walk it. All check dtype / shape / contiguity on the host and launch on
-torch's current stream; none allocates unless the caller leaves an output out.
+octree-like hierarchy over that order; walk() walks it for a, phi or both, over all target groups, a range of them or a
+list of bodies, and holds every check, allocation and launch of a walk: accel(), potential(), accel_potential() and the
+*_groups() / accel_active() names below are each one call of it. All check dtype / shape / contiguity on the host and
+launch on torch's current stream; none allocates unless the caller leaves an output out.
 
 For several ranks ("Several ranks"): build_posm() is build() from packed {x, y, z, m} rows, accel_groups(),
 potential_groups() and accel_potential_groups() walk the target groups [group_lo, group_hi) of groups(n) alone and leave
@@ -57,56 +59,6 @@ def build(pos: torch.Tensor, mass: torch.Tensor, ws: torch.Tensor, order: torch.
     return order
 
 
-def _walk_checks(ws: torch.Tensor, n: int, counters: torch.Tensor | None):
-    _chk(ws, None, "workspace", torch.uint8)
-    if _nbytes(ws) < workspace_bytes(n):
-        raise _lib.NbdError(f"workspace: {_nbytes(ws)} bytes, the tree of {n} bodies takes {workspace_bytes(n)}")
-    if counters is not None:
-        _chk(counters, (2,), "counters", torch.int64)
-
-
-def accel(ws: torch.Tensor, n: int, theta: float, softening_sq: float, g_const: float, quadrupole: bool = True,
-          out: torch.Tensor | None = None, counters: torch.Tensor | None = None) -> torch.Tensor:
-    """acc (n,3) in the caller's order from the tree build() left in `ws`. counters: None or a (2,) int64 device tensor
-    that receives {accepted cells, rejected level-0 nodes} summed over the target groups."""
-    _walk_checks(ws, n, counters)
-    if out is None:
-        out = torch.empty((n, 3), dtype=torch.float32, device=ws.device)
-    _chk(out, (n, 3), "acc_out")
-    _lib.launch("nbd_tree_accel_f32", ws.device, ws.data_ptr(), int(n), float(theta), float(softening_sq), float(g_const),
-                int(bool(quadrupole)), out.data_ptr(), _lib.ptr(counters))
-    return out
-
-
-def potential(ws: torch.Tensor, n: int, theta: float, softening_sq: float, g_const: float, quadrupole: bool = True,
-              out: torch.Tensor | None = None, counters: torch.Tensor | None = None) -> torch.Tensor:
-    """phi (n,) float64 in the caller's order from the tree build() left in `ws`: the potential whose gradient accel()
-    is, summed over the same accepted cells and rejected level-0 nodes (fp32 terms, fp64 sums). counters as in accel()."""
-    _walk_checks(ws, n, counters)
-    if out is None:
-        out = torch.empty((n,), dtype=torch.float64, device=ws.device)
-    _chk(out, (n,), "phi_out", torch.float64)
-    _lib.launch("nbd_tree_potential_f32", ws.device, ws.data_ptr(), int(n), float(theta), float(softening_sq),
-                float(g_const), int(bool(quadrupole)), out.data_ptr(), _lib.ptr(counters))
-    return out
-
-
-def accel_potential(ws: torch.Tensor, n: int, theta: float, softening_sq: float, g_const: float, quadrupole: bool = True,
-                    out: tuple | None = None, counters: torch.Tensor | None = None) -> tuple:
-    """(acc, phi) from ONE walk: acc bit for bit accel()'s, phi bit for bit potential()'s. out: None or (acc, phi)."""
-    _walk_checks(ws, n, counters)
-    acc, phi = out if out is not None else (None, None)
-    if acc is None:
-        acc = torch.empty((n, 3), dtype=torch.float32, device=ws.device)
-    if phi is None:
-        phi = torch.empty((n,), dtype=torch.float64, device=ws.device)
-    _chk(acc, (n, 3), "acc_out"); _chk(phi, (n,), "phi_out", torch.float64)
-    _lib.launch("nbd_tree_accel_potential_f32", ws.device, ws.data_ptr(), int(n), float(theta), float(softening_sq),
-                float(g_const), int(bool(quadrupole)), acc.data_ptr(), phi.data_ptr(), _lib.ptr(counters))
-    return acc, phi
-
-
-# ---------------------------------------------------------------- a range of the target groups (several ranks)
 GROUP = 64                       # sorted bodies per target group (one wave of the walk)
 
 
@@ -115,6 +67,87 @@ def groups(n: int) -> int:
     return (int(n) + GROUP - 1) // GROUP
 
 
+def _ws_checks(ws: torch.Tensor, n: int):
+    _chk(ws, None, "workspace", torch.uint8)
+    if _nbytes(ws) < workspace_bytes(n):
+        raise _lib.NbdError(f"workspace: {_nbytes(ws)} bytes, the tree of {n} bodies takes {workspace_bytes(n)}")
+
+
+def walk(ws: torch.Tensor, n: int, theta: float, softening_sq: float, g_const: float, quadrupole: bool = True, *,
+         acc: bool = True, phi: bool = False, groups: tuple | None = None, active: tuple | None = None,
+         out: tuple | None = None, counters: torch.Tensor | None = None) -> tuple:
+    """One walk of the tree build() left in `ws` -> (acc or None, phi or None): the acceleration (n,3) float32, the
+    potential (n,) float64 whose gradient it is, or both from ONE walk, in the caller's order. Every simulator and every
+    named wrapper below goes through here.
+    groups (lo, hi): of the target groups [lo, hi) of groups(n) alone; the outputs then hold (hi - lo) 64 rows in TREE
+    order, row t = sorted body 64 lo + t, the rows behind body n - 1 as 0. An empty range launches nothing.
+    active (list, n_act): of the n_act sorted positions of `list` (select_active()'s) alone; acc is in the caller's order
+    and only the rows order[list[t]] are written (an acc allocated here holds 0 elsewhere). The list has no phi.
+    out: None or (acc, phi), None for what is to be allocated. counters: None or a (2,) int64 device tensor that receives
+    {accepted cells, rejected level-0 nodes} summed over the walked groups (0 where nothing is walked)."""
+    n, acc, phi, ranged, listed = int(n), bool(acc), bool(phi), groups is not None, active is not None
+    if not (acc or phi):
+        raise _lib.NbdError("walk: nothing asked for, give acc, phi or both")
+    if ranged and listed:
+        raise _lib.NbdError("walk: give groups or active, not both")
+    if listed and phi:
+        raise _lib.NbdError("walk: the listed walk sums the acceleration alone, there is no phi of a list")
+    _ws_checks(ws, n)
+    if counters is not None:
+        _chk(counters, (2,), "counters", torch.int64)
+    rows, tag, head = n, "", (ws.data_ptr(), n)
+    if ranged:
+        (lo, hi), n_groups = (int(g) for g in groups), (n + GROUP - 1) // GROUP
+        if not 0 <= lo <= hi <= n_groups:
+            raise _lib.NbdError(f"groups [{lo}, {hi}) outside [0, {n_groups}] of {n} bodies")
+        if lo == hi and counters is not None:
+            counters.zero_()
+        rows, tag, head = (hi - lo) * GROUP, "_sorted", head + (lo, hi)
+    if listed:
+        lst, n_act = active[0], int(active[1])
+        if lst is not None:
+            _chk(lst, None, "list", torch.int32)
+            if lst.dim() != 1 or lst.shape[0] < n_act:
+                raise _lib.NbdError(f"list: {n_act} entries asked for, it holds {tuple(lst.shape)}")
+        head = (ws.data_ptr(), _nbytes(ws), n, _lib.ptr(lst), n_act)
+    a, p = out if out is not None else (None, None)
+    if acc:
+        if a is None:                            # (the unlisted rows of a listed walk are not written: they are 0)
+            a = (torch.zeros if listed else torch.empty)((rows, 3), dtype=torch.float32, device=ws.device)
+        _chk(a, (rows, 3), f"acc{tag}_out")
+    if phi:
+        if p is None:
+            p = torch.empty((rows,), dtype=torch.float64, device=ws.device)
+        _chk(p, (rows,), f"phi{tag}_out", torch.float64)
+    outs = ((a,) if acc else ()) + ((p,) if phi else ())
+    entry = "_".join(("accel",) * acc + ("potential",) * phi + ("groups",) * ranged + ("active",) * listed)
+    _lib.launch(f"nbd_tree_{entry}_f32", ws.device, *head, float(theta), float(softening_sq), float(g_const),
+                int(bool(quadrupole)), *(t.data_ptr() for t in outs), _lib.ptr(counters))
+    return (a if acc else None), (p if phi else None)
+
+
+def accel(ws: torch.Tensor, n: int, theta: float, softening_sq: float, g_const: float, quadrupole: bool = True,
+          out: torch.Tensor | None = None, counters: torch.Tensor | None = None) -> torch.Tensor:
+    """acc (n,3) in the caller's order from the tree build() left in `ws`. counters: None or a (2,) int64 device tensor
+    that receives {accepted cells, rejected level-0 nodes} summed over the target groups."""
+    return walk(ws, n, theta, softening_sq, g_const, quadrupole, out=(out, None), counters=counters)[0]
+
+
+def potential(ws: torch.Tensor, n: int, theta: float, softening_sq: float, g_const: float, quadrupole: bool = True,
+              out: torch.Tensor | None = None, counters: torch.Tensor | None = None) -> torch.Tensor:
+    """phi (n,) float64 in the caller's order from the tree build() left in `ws`: the potential whose gradient accel()
+    is, summed over the same accepted cells and rejected level-0 nodes (fp32 terms, fp64 sums). counters as in accel()."""
+    return walk(ws, n, theta, softening_sq, g_const, quadrupole, acc=False, phi=True, out=(None, out),
+                counters=counters)[1]
+
+
+def accel_potential(ws: torch.Tensor, n: int, theta: float, softening_sq: float, g_const: float, quadrupole: bool = True,
+                    out: tuple | None = None, counters: torch.Tensor | None = None) -> tuple:
+    """(acc, phi) from ONE walk: acc bit for bit accel()'s, phi bit for bit potential()'s. out: None or (acc, phi)."""
+    return walk(ws, n, theta, softening_sq, g_const, quadrupole, phi=True, out=out, counters=counters)
+
+
+# ---------------------------------------------------------------- a range of the target groups (several ranks)
 def build_posm(posm: torch.Tensor, n: int, ws: torch.Tensor, order: torch.Tensor | None = None) -> torch.Tensor:
     """build() from packed rows: posm (>= n, 4) {x, y, z, m} (what pack_posm, kick_drift and the all-gather of a sharded
     step leave). order and everything the walks read are bit for bit build()'s for the same values."""
@@ -130,60 +163,30 @@ def build_posm(posm: torch.Tensor, n: int, ws: torch.Tensor, order: torch.Tensor
     return order
 
 
-def _group_checks(ws: torch.Tensor, n: int, group_lo: int, group_hi: int, counters: torch.Tensor | None) -> int:
-    """The checks of a ranged walk; returns its rows. An empty range launches nothing: its counters are zeroed here."""
-    _walk_checks(ws, n, counters)
-    if not 0 <= group_lo <= group_hi <= groups(n):
-        raise _lib.NbdError(f"groups [{group_lo}, {group_hi}) outside [0, {groups(n)}] of {n} bodies")
-    if group_lo == group_hi and counters is not None:
-        counters.zero_()
-    return (group_hi - group_lo) * GROUP
-
-
 def accel_groups(ws: torch.Tensor, n: int, group_lo: int, group_hi: int, theta: float, softening_sq: float,
                  g_const: float, quadrupole: bool = True, out: torch.Tensor | None = None,
                  counters: torch.Tensor | None = None) -> torch.Tensor:
     """accel() for the target groups [group_lo, group_hi) alone -> ((group_hi - group_lo) 64, 3) in TREE order: row t is
     sorted body 64 group_lo + t and equals accel()'s row order[64 group_lo + t] bit for bit; rows behind body n - 1 are
     0. counters: the sums over these groups."""
-    rows = _group_checks(ws, n, group_lo, group_hi, counters)
-    if out is None:
-        out = torch.empty((rows, 3), dtype=torch.float32, device=ws.device)
-    _chk(out, (rows, 3), "acc_sorted_out")
-    _lib.launch("nbd_tree_accel_groups_f32", ws.device, ws.data_ptr(), int(n), int(group_lo), int(group_hi), float(theta),
-                float(softening_sq), float(g_const), int(bool(quadrupole)), out.data_ptr(), _lib.ptr(counters))
-    return out
+    return walk(ws, n, theta, softening_sq, g_const, quadrupole, groups=(group_lo, group_hi), out=(out, None),
+                counters=counters)[0]
 
 
 def potential_groups(ws: torch.Tensor, n: int, group_lo: int, group_hi: int, theta: float, softening_sq: float,
                      g_const: float, quadrupole: bool = True, out: torch.Tensor | None = None,
                      counters: torch.Tensor | None = None) -> torch.Tensor:
     """potential() for the target groups [group_lo, group_hi) alone -> ((group_hi - group_lo) 64,) float64 in tree order."""
-    rows = _group_checks(ws, n, group_lo, group_hi, counters)
-    if out is None:
-        out = torch.empty((rows,), dtype=torch.float64, device=ws.device)
-    _chk(out, (rows,), "phi_sorted_out", torch.float64)
-    _lib.launch("nbd_tree_potential_groups_f32", ws.device, ws.data_ptr(), int(n), int(group_lo), int(group_hi),
-                float(theta), float(softening_sq), float(g_const), int(bool(quadrupole)), out.data_ptr(),
-                _lib.ptr(counters))
-    return out
+    return walk(ws, n, theta, softening_sq, g_const, quadrupole, acc=False, phi=True, groups=(group_lo, group_hi),
+                out=(None, out), counters=counters)[1]
 
 
 def accel_potential_groups(ws: torch.Tensor, n: int, group_lo: int, group_hi: int, theta: float, softening_sq: float,
                            g_const: float, quadrupole: bool = True, out: tuple | None = None,
                            counters: torch.Tensor | None = None) -> tuple:
     """(acc, phi) of the target groups [group_lo, group_hi) from ONE walk, both in tree order. out: None or (acc, phi)."""
-    rows = _group_checks(ws, n, group_lo, group_hi, counters)
-    acc, phi = out if out is not None else (None, None)
-    if acc is None:
-        acc = torch.empty((rows, 3), dtype=torch.float32, device=ws.device)
-    if phi is None:
-        phi = torch.empty((rows,), dtype=torch.float64, device=ws.device)
-    _chk(acc, (rows, 3), "acc_sorted_out"); _chk(phi, (rows,), "phi_sorted_out", torch.float64)
-    _lib.launch("nbd_tree_accel_potential_groups_f32", ws.device, ws.data_ptr(), int(n), int(group_lo), int(group_hi),
-                float(theta), float(softening_sq), float(g_const), int(bool(quadrupole)), acc.data_ptr(), phi.data_ptr(),
-                _lib.ptr(counters))
-    return acc, phi
+    return walk(ws, n, theta, softening_sq, g_const, quadrupole, phi=True, groups=(group_lo, group_hi), out=out,
+                counters=counters)
 
 
 def scatter(ws: torch.Tensor, n: int, lo: int, hi: int, acc_sorted: torch.Tensor | None = None,
@@ -191,7 +194,7 @@ def scatter(ws: torch.Tensor, n: int, lo: int, hi: int, acc_sorted: torch.Tensor
     """Tree order -> the bodies [lo, hi) of the caller's order, by the order build() left in `ws`: acc (hi - lo, 3) from
     acc_sorted (64 groups(n), 3) and / or phi (hi - lo,) from phi_sorted (64 groups(n),). Returns (acc, phi), None for
     what was not given. out: None or (acc, phi)."""
-    _walk_checks(ws, n, None)
+    _ws_checks(ws, n)
     if not 0 <= lo <= hi <= n:
         raise _lib.NbdError(f"bodies [{lo}, {hi}) outside [0, {n}]")
     if acc_sorted is None and phi_sorted is None:
@@ -245,7 +248,7 @@ def select_active(ws: torch.Tensor, n: int, flags: torch.Tensor, list_out: torch
     if n == 0:
         return (list_out if list_out is not None else torch.empty((0,), dtype=torch.int32, device=flags.device),
                 n_act_out.zero_() if n_act_out is not None else torch.zeros((1,), dtype=torch.int32, device=flags.device))
-    _walk_checks(ws, n, None)
+    _ws_checks(ws, n)
     if active_ws is None:
         active_ws = active_workspace(n, ws.device)
     _chk(active_ws, None, "active workspace", torch.uint8)
@@ -267,20 +270,8 @@ def accel_active(ws: torch.Tensor, n: int, list: torch.Tensor, n_act: int, theta
     Written: the rows order[list[t]], t < n_act, of out (n,3) in the caller's order, and NO other row (out None: the others
     are 0). With every body listed, out and counters equal accel()'s bit for bit. n_act = 0 launches nothing and zeroes
     the counters."""
-    n, n_act = int(n), int(n_act)
-    _chk(ws, None, "workspace", torch.uint8)
-    if counters is not None:
-        _chk(counters, (2,), "counters", torch.int64)
-    if list is not None:
-        _chk(list, None, "list", torch.int32)
-        if list.dim() != 1 or list.shape[0] < n_act:
-            raise _lib.NbdError(f"list: {n_act} entries asked for, it holds {tuple(list.shape)}")
-    if out is None:
-        out = torch.zeros((n, 3), dtype=torch.float32, device=ws.device)
-    _chk(out, (n, 3), "acc_out")
-    _lib.launch("nbd_tree_accel_active_f32", ws.device, ws.data_ptr(), _nbytes(ws), n, _lib.ptr(list), n_act, float(theta),
-                float(softening_sq), float(g_const), int(bool(quadrupole)), out.data_ptr(), _lib.ptr(counters))
-    return out
+    return walk(ws, n, theta, softening_sq, g_const, quadrupole, active=(list, n_act), out=(out, None),
+                counters=counters)[0]
 
 
 # ---------------------------------------------------------------- the O(N) stages of a block step (csrc/tree_block.hip)
