@@ -1524,6 +1524,12 @@ int64_t nbd_csv_format_state(char* out, size_t cap, const char* prefix, size_t p
  *   nbd_tree_plan             host: levels and nodes over all levels for n bodies (0, 0 for n = 0); n > 2^24 is
  *                             NBD_E_UNSUPPORTED (every entry below refuses it the same way)
  *   nbd_tree_workspace_bytes  bytes of the workspace (the radix sort's scratch included; 0 for n <= 0 or n > 2^24)
+ *   nbd_tree_regions          host: the byte offsets, inside that workspace, of the three regions a build leaves and the
+ *                             walks read -- the order (n int32: sorted position -> caller's index), the sorted bodies
+ *                             (n rounded up to a multiple of 64 rows {x, y, z, m}, zeros behind body n - 1) and the node
+ *                             records (3 float4 per node, level 0 first, a level's nodes behind all nodes of the levels
+ *                             below it: {c, s}, {M, Qxx, Qxy, Qxz}, {Qyy, Qyz, Qzz, 0}). Each is 256-byte aligned. The
+ *                             refusals of nbd_tree_plan, and NBD_E_BADARG for a NULL output; n = 0 gives 0, 0, 0.
  *   nbd_tree_build_f32        keys, sort, sorted bodies and every node into `workspace` (256-byte aligned); order_out[k]
  *                             = the caller's index of the k-th sorted body. pos (n,3), mass (n,).
  *   nbd_tree_accel_f32        the walk over a workspace nbd_tree_build_f32 filled for the same n; acc_out (n,3) in the
@@ -1564,6 +1570,7 @@ int64_t nbd_csv_format_state(char* out, size_t cap, const char* prefix, size_t p
  * n = 0 is a no-op. No allocation, memset or synchronisation inside; bit-identical from run to run. */
 int nbd_tree_plan(int n, int* levels, int* nodes_total);
 size_t nbd_tree_workspace_bytes(int n);
+int nbd_tree_regions(int n, size_t* order_off, size_t* posm_off, size_t* nodes_off);
 int nbd_tree_build_f32(const float* pos, const float* mass, int n, int* order_out, void* workspace,
                        size_t workspace_bytes, nbd_stream_t stream);
 int nbd_tree_accel_f32(const void* workspace, int n, float theta, float softening_sq, float g_const, int quadrupole,

@@ -5,8 +5,12 @@
 //   tree    implicit over the sorted order: a level-L node holds the sorted bodies [i 8^(L+1), min(n, (i+1) 8^(L+1))),
 //           level 0 = ceil(n/8) nodes of up to 8 bodies, every level above groups 8 consecutive nodes until one node is
 //           left. No pointers, no atomics. Per node: mass M, centre of mass c, traceless quadrupole Q about c and the
-//           size s = longest AABB edge + max-norm of (c - AABB centre); M, c, Q are summed in fp64 (raw moments about
-//           the centre of the bounding box, kept per node so that a parent is the sum of its children) and stored fp32.
+//           size s = longest AABB edge + max-norm of (c - AABB centre); M, c, Q are summed in fp64 and stored fp32. Kept
+//           per node: the mass and the first moments about the centre of the bounding box of all bodies (a parent's are
+//           the sums of its children's) and the second moments about the node's OWN centre of mass (a parent's from its
+//           children's by the parallel-axis theorem). Second moments about the box centre would cancel down to the
+//           node's own size squared: one body far away stretches the box, and a small node far from its centre lost
+//           (distance / size)^2 2^-53 of its Q that way -- a percent with a body at 10^6 beside a cluster of size 1.
 //   walk    one wave per target group of 64 consecutive sorted bodies, one lane per body. The wave tests 32 nodes at a
 //           time against the group's AABB T: accepted when theta > 0 and s^2 < theta^2 d^2 (d = distance from c to T).
 //           Accepted cells and rejected level-0 nodes go to two LDS lists by ballot and prefix; a list is evaluated
@@ -67,7 +71,7 @@ constexpr int kMaxLevels = 8;          // 8^8 = 2^24 bodies under the top node
 constexpr int kLeaf = 8;               // bodies per level-0 node, children per node
 constexpr int kGroup = 64;             // targets per wave
 constexpr int kBoxBlocks = 256;        // partial bounding boxes
-constexpr int kMom = 13;               // doubles per node while building: M, sum m x (3), sum m x x^T (6), sum x (3)
+constexpr int kMom = 13;               // doubles per node while building: M, sum m x (3), sum m d d^T about c (6), sum x (3)
 constexpr int kListCap = 128;          // a list is flushed at >= 64 entries and grows by <= kPop per iteration
 constexpr int kPop = 32;               // stack entries tested per iteration
 constexpr int kStackPerLevel = kLeaf * kPop;
@@ -253,20 +257,27 @@ __global__ __launch_bounds__(256) void gather_kernel(const float* __restrict__ p
 
 // ---------------------------------------------------------------- nodes
 
-// The walk's record of a node from its moments about `centre` (mom: kMom doubles), its body count and its AABB:
-// nodes[3 id] = {c, s}, {M, Qxx, Qxy, Qxz}, {Qyy, Qyz, Qzz, 0}. A node without mass takes c = the mean of its bodies.
+// c - centre of a node from its mass, first moments and sum of positions about `centre` (mom: kMom doubles) and its body
+// count: the centre of mass, for a node without mass the mean of its bodies.
+__device__ inline void node_centre(const double* m, long long cnt, double* c) {
+  const double M = m[0];
+  for (int a = 0; a < 3; ++a) c[a] = M != 0.0 ? m[1 + a] / M : m[10 + a] / (double)cnt;
+}
+
+// m[4..9] += w d d^T (xx, xy, xz, yy, yz, zz)
+__device__ inline void add_second_moments(double* m, double w, const double* d) {
+  m[4] += w * d[0] * d[0]; m[5] += w * d[0] * d[1]; m[6] += w * d[0] * d[2];
+  m[7] += w * d[1] * d[1]; m[8] += w * d[1] * d[2]; m[9] += w * d[2] * d[2];
+}
+
+// The walk's record of a node from its moments (mom: kMom doubles, the second ones C_ab = sum m (x - c)_a (x - c)_b about
+// the node's own centre), its body count and its AABB: nodes[3 id] = {c, s}, {M, Qxx, Qxy, Qxz}, {Qyy, Qyz, Qzz, 0}.
 __device__ inline void finish_node(const double* m, long long cnt, const float* lo, const float* hi, const float* centre,
                                    f4* __restrict__ rec) {
   const double M = m[0];
   double c[3];
-  for (int a = 0; a < 3; ++a) c[a] = M != 0.0 ? m[1 + a] / M : m[10 + a] / (double)cnt;
-  // central second moments C_ab = sum m (x - c)_a (x - c)_b from the raw ones
-  const int ia[6] = {0, 0, 0, 1, 1, 2}, ib[6] = {0, 1, 2, 1, 2, 2};
-  double C[6];
-  for (int k = 0; k < 6; ++k) {
-    const int a = ia[k], b = ib[k];
-    C[k] = m[4 + k] - m[1 + a] * c[b] - m[1 + b] * c[a] + M * c[a] * c[b];
-  }
+  node_centre(m, cnt, c);
+  const double* C = m + 4;
   const double tr = C[0] + C[3] + C[5];
   double edge = 0.0, shift = 0.0;
   for (int a = 0; a < 3; ++a) {
@@ -299,8 +310,14 @@ __global__ __launch_bounds__(128) void leaf_kernel(const f4* __restrict__ posm, 
       m[1 + a] += w * x[a]; m[10 + a] += x[a];
     }
     m[0] += w;
-    m[4] += w * x[0] * x[0]; m[5] += w * x[0] * x[1]; m[6] += w * x[0] * x[2];
-    m[7] += w * x[1] * x[1]; m[8] += w * x[1] * x[2]; m[9] += w * x[2] * x[2];
+  }
+  double c[3];
+  node_centre(m, b1 - b0, c);
+  for (int b = b0; b < b1; ++b) {                    // the second moments about the node's own centre
+    const f4 p = posm[b];
+    const double d[3] = {((double)p.x - (double)centre[0]) - c[0], ((double)p.y - (double)centre[1]) - c[1],
+                         ((double)p.z - (double)centre[2]) - c[2]};
+    add_second_moments(m, (double)p.w, d);
   }
   for (int k = 0; k < kMom; ++k) mom[(size_t)id * kMom + k] = m[k];
   for (int a = 0; a < 3; ++a) { aabb[(size_t)id * 8 + a] = lo[a]; aabb[(size_t)id * 8 + 4 + a] = hi[a]; }
@@ -319,14 +336,26 @@ __global__ __launch_bounds__(128) void upper_kernel(int n, int lvl, int count, i
   float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
   for (int c = c0; c < c1; ++c) {
     const size_t g = (size_t)off_below + c;
-    for (int k = 0; k < kMom; ++k) m[k] += mom[g * kMom + k];
+    for (int k = 0; k < 4; ++k) m[k] += mom[g * kMom + k];
+    for (int k = 10; k < kMom; ++k) m[k] += mom[g * kMom + k];
     for (int a = 0; a < 3; ++a) { lo[a] = fminf(lo[a], aabb[g * 8 + a]); hi[a] = fmaxf(hi[a], aabb[g * 8 + 4 + a]); }
+  }
+  const long long span = 1ll << (3 * (lvl + 1));
+  const long long first = (long long)id * span, last = first + span < (long long)n ? first + span : (long long)n;
+  double cn[3];
+  node_centre(m, last - first, cn);
+  for (int c = c0; c < c1; ++c) {                    // parallel axes: a child's own second moments, and its mass at its centre
+    const double* child = mom + ((size_t)off_below + c) * kMom;
+    for (int k = 4; k < 10; ++k) m[k] += child[k];
+    const double Mk = child[0];
+    if (Mk != 0.0) {
+      const double d[3] = {child[1] / Mk - cn[0], child[2] / Mk - cn[1], child[3] / Mk - cn[2]};
+      add_second_moments(m, Mk, d);
+    }
   }
   const size_t g = (size_t)off + id;
   for (int k = 0; k < kMom; ++k) mom[g * kMom + k] = m[k];
   for (int a = 0; a < 3; ++a) { aabb[g * 8 + a] = lo[a]; aabb[g * 8 + 4 + a] = hi[a]; }
-  const long long span = 1ll << (3 * (lvl + 1));
-  const long long first = (long long)id * span, last = first + span < (long long)n ? first + span : (long long)n;
   finish_node(m, last - first, lo, hi, centre, nodes + 3 * g);
 }
 
@@ -788,6 +817,15 @@ int nbd_tree_plan(int n, int* levels, int* nodes_total) {
 size_t nbd_tree_workspace_bytes(int n) {
   if (n <= 0 || n > kMaxBodies) return 0;
   return layout(n, plan_levels(n)).total;
+}
+
+int nbd_tree_regions(int n, size_t* order_off, size_t* posm_off, size_t* nodes_off) {
+  if (n < 0 || !order_off || !posm_off || !nodes_off) return NBD_E_BADARG;
+  if (n > kMaxBodies) return NBD_E_UNSUPPORTED;
+  Layout w = {};                                     // n = 0: no workspace, every offset 0
+  if (n > 0) w = layout(n, plan_levels(n));
+  *order_off = w.order; *posm_off = w.posm; *nodes_off = w.nodes;
+  return 0;
 }
 
 size_t nbd_tree_active_workspace_bytes(int n) {

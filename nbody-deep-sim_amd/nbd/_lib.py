@@ -392,6 +392,7 @@ SIGNATURES = {
     # --- tree-code gravity (csrc/tree_force.hip)
     "nbd_tree_plan": (c_int, [c_int, POINTER(c_int), POINTER(c_int)]),
     "nbd_tree_workspace_bytes": (c_size_t, [c_int]),
+    "nbd_tree_regions": (c_int, [c_int, POINTER(c_size_t), POINTER(c_size_t), POINTER(c_size_t)]),
     "nbd_tree_build_f32": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
     "nbd_tree_accel_f32": (c_int, [c_void_p, c_int, c_float, c_float, c_float, c_int, c_void_p, c_void_p, c_void_p]),
     "nbd_tree_potential_f32": (c_int, [c_void_p, c_int, c_float, c_float, c_float, c_int, c_void_p, c_void_p, c_void_p]),

@@ -4,7 +4,8 @@ build() orders the bodies along a Morton curve and fills a workspace with the so
 octree-like hierarchy over that order; walk() walks it for a, phi or both, over all target groups, a range of them or a
 list of bodies, and holds every check, allocation and launch of a walk: accel(), potential(), accel_potential() and the
 *_groups() / accel_active() names below are each one call of it. All check dtype / shape / contiguity on the host and
-launch on torch's current stream; none allocates unless the caller leaves an output out.
+launch on torch's current stream; none allocates unless the caller leaves an output out. views() shows what a build left:
+the order, the sorted bodies and the node records, as views of the workspace.
 
 For several ranks ("Several ranks"): build_posm() is build() from packed {x, y, z, m} rows, accel_groups(),
 potential_groups() and accel_potential_groups() walk the target groups [group_lo, group_hi) of groups(n) alone and leave
@@ -124,6 +125,31 @@ def walk(ws: torch.Tensor, n: int, theta: float, softening_sq: float, g_const: f
     _lib.launch(f"nbd_tree_{entry}_f32", ws.device, *head, float(theta), float(softening_sq), float(g_const),
                 int(bool(quadrupole)), *(t.data_ptr() for t in outs), _lib.ptr(counters))
     return (a if acc else None), (p if phi else None)
+
+
+def views(ws: torch.Tensor, n: int) -> dict:
+    """What build() left in `ws` and the walks read, as zero-copy views of it (nbd_tree_regions): {"order": (n,) int32,
+    sorted position -> caller's index; "posm": (n rounded up to 64, 4) float32, the sorted rows {x, y, z, m}, zeros
+    behind body n - 1; "nodes": one (count, 12) float32 per level, level 0 first, a row {c (3), s, M, Qxx, Qxy, Qxz,
+    Qyy, Qyz, Qzz, 0}}."""
+    n = int(n)
+    offs = [ctypes.c_size_t() for _ in range(3)]
+    _lib.call("nbd_tree_regions", n, *offs)
+    if n == 0:
+        return {"order": ws[:0].view(torch.int32), "posm": ws[:0].view(torch.float32).view(0, 4), "nodes": []}
+    _ws_checks(ws, n)
+    order_off, posm_off, nodes_off = (o.value for o in offs)
+    rows = groups(n) * GROUP
+    counts = [(n + 7) // 8]
+    while counts[-1] > 1:
+        counts.append((counts[-1] + 7) // 8)
+    assert len(counts) == plan(n)["levels"] and sum(counts) == plan(n)["nodes_total"]
+    nodes, at = [], nodes_off
+    for count in counts:
+        nodes.append(ws[at:at + 48 * count].view(torch.float32).view(count, 12))
+        at += 48 * count
+    return {"order": ws[order_off:order_off + 4 * n].view(torch.int32),
+            "posm": ws[posm_off:posm_off + 16 * rows].view(torch.float32).view(rows, 4), "nodes": nodes}
 
 
 def accel(ws: torch.Tensor, n: int, theta: float, softening_sq: float, g_const: float, quadrupole: bool = True,

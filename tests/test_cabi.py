@@ -80,6 +80,15 @@ def test_host_only_queries():
     assert L.nbd_shard_workspace_bytes(65536, 3 * 8192, 8192) == (a.value + cc.value) * 8192 * 12
     assert L.nbd_shard_plan(1000, 0, 1000, a, b, cc, d) == 0 and cc.value == 0          # nothing remote
     assert L.nbd_shard_plan(1000, 990, 20, a, b, cc, d) == -1                           # range outside the system
+    # where a tree build leaves the order, the sorted bodies and the node records: 256-aligned, in this order, inside
+    # the workspace; the refusals of nbd_tree_plan, and of a NULL output
+    o, p, nd = ctypes.c_size_t(), ctypes.c_size_t(), ctypes.c_size_t()
+    assert L.nbd_tree_regions(1000, o, p, nd) == 0
+    assert 0 < o.value < p.value < nd.value < L.nbd_tree_workspace_bytes(1000) and (o.value | p.value | nd.value) % 256 == 0
+    assert p.value - o.value >= 4 * 1000 and nd.value - p.value >= 16 * 1024
+    assert L.nbd_tree_regions(0, o, p, nd) == 0 and (o.value, p.value, nd.value) == (0, 0, 0)
+    assert L.nbd_tree_regions(-1, o, p, nd) == -1 and L.nbd_tree_regions((1 << 24) + 1, o, p, nd) == -3
+    assert L.nbd_tree_regions(1000, None, p, nd) == -1
     assert L.nbd_contconv_fused_supported(128, 128, 160) == 1 and L.nbd_contconv_fused_supported(70, 40, 27) == 0
     assert L.nbd_contconv_fused_supported(128, 128, 216) == 0                            # pair-list LDS tables: <= 160 cells
     # round 3: the training-side queries

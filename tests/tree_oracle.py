@@ -66,17 +66,26 @@ def build_nodes(x, m):
     return levels
 
 
-def tree_accel(pos, mass, theta, softening, g_const=1.0, quadrupole=True, order=None, opening_dtype=np.float64):
+def tree_accel(pos, mass, theta, softening, g_const=1.0, quadrupole=True, order=None, opening_dtype=np.float64,
+               groups=None, cond=False):
     """(acc (n,3) in the caller's order, (accepted cells, rejected level-0 nodes)).
 
     opening_dtype=np.float32 makes the opening decision the way an fp32 walk does (c, s and the group boxes rounded to
-    float32, the comparison s^2 < theta^2 d^2 in float32); the forces stay float64."""
+    float32, the comparison s^2 < theta^2 d^2 in float32); the forces stay float64.
+    groups: a list of target groups (group g = the sorted bodies [64 g, min(n, 64 g + 64))) to walk alone. The result is
+    then (rows, [(cells, leaves) per listed group]): the rows of the listed groups one after another in TREE order,
+    without padding.
+    cond=True appends the condition sums (rows, 2), ordered as the rows: the sum over everything added to the row of the
+    Euclidean norm of each addend, times |g_const| -- column 0 over the pair terms m w d, column 1 over the accepted
+    cells, each the three vectors it is made of, M r u^3, (Q r) u^5 and 2.5 (r.Qr) u^7 r. S_i is the sum of the two: an
+    fp32 sum of the same addends is within a small multiple of 2^-24 S_i of the exact one, however much they cancel."""
     pos = np.asarray(pos, dtype=np.float64)
     mass = np.asarray(mass, dtype=np.float64)
     n = len(pos)
     acc = np.zeros((n, 3))
     if n == 0:
-        return acc, (0, 0)
+        empty = (np.zeros((0, 3)), []) if groups is not None else (acc, (0, 0))
+        return empty + ((np.zeros((0, 2)),) if cond else ())
     order = morton_order(pos) if order is None else np.asarray(order, dtype=np.int64)
     assert sorted(order.tolist()) == list(range(n)), "order is not a permutation"
     x, m = pos[order], mass[order]
@@ -85,12 +94,15 @@ def tree_accel(pos, mass, theta, softening, g_const=1.0, quadrupole=True, order=
     eps2 = float(softening) ** 2
     od = opening_dtype
     n_cells = n_leaves = 0
-    out = np.zeros((n, 3))
-    for g0 in range(0, n, GROUP):
+    out, cond_out, per_group = np.zeros((n, 3)), np.zeros((n, 2)), []
+    walked = range(-(-n // GROUP)) if groups is None else [int(g) for g in groups]
+    assert all(0 <= g < -(-n // GROUP) for g in walked), "group outside the tree"
+    for g0 in (g * GROUP for g in walked):
         g1 = min(n, g0 + GROUP)
         xt = x[g0:g1]
         tlo, thi = xt.min(0).astype(od), xt.max(0).astype(od)
-        a = np.zeros((g1 - g0, 3))
+        a, S = np.zeros((g1 - g0, 3)), np.zeros((g1 - g0, 2))
+        before = (n_cells, n_leaves)
         front = np.array([0])
         for lvl in range(len(levels) - 1, -1, -1):
             L = levels[lvl]
@@ -111,6 +123,11 @@ def tree_accel(pos, mass, theta, softening, g_const=1.0, quadrupole=True, order=
                     rqr = (r * qr).sum(2)
                     term += -qr * (u ** 5)[:, :, None] + 2.5 * (rqr * u ** 7)[:, :, None] * r
                 a += term.sum(1)
+                if cond:
+                    rn = np.linalg.norm(r, axis=2)
+                    S[:, 1] += (np.abs(L["M"][cells])[None, :] * rn * u ** 3).sum(1)
+                    if quadrupole:
+                        S[:, 1] += (np.linalg.norm(qr, axis=2) * u ** 5 + 2.5 * np.abs(rqr) * u ** 7 * rn).sum(1)
             if lvl > 0:
                 kids = (rest[:, None] * LEAF + np.arange(LEAF)[None, :]).ravel()
                 front = kids[kids < counts[lvl - 1]]
@@ -123,8 +140,19 @@ def tree_accel(pos, mass, theta, softening, g_const=1.0, quadrupole=True, order=
                     w = ((d * d).sum(2) + eps2) ** -1.5
                     w[np.arange(g0, g1)[:, None] == j[None, :]] = 0.0               # j == i by index
                     a += ((m[j][None, :] * w)[:, :, None] * d).sum(1)
-        out[g0:g1] = a
+                    if cond:
+                        S[:, 0] += (np.abs(m[j])[None, :] * w * np.linalg.norm(d, axis=2)).sum(1)
+        out[g0:g1], cond_out[g0:g1] = a, S
+        per_group.append((n_cells - before[0], n_leaves - before[1]))
+    if groups is not None:
+        rows = np.concatenate([np.arange(g * GROUP, min(n, g * GROUP + GROUP)) for g in walked]) if walked else \
+            np.zeros(0, dtype=np.int64)
+        return (g_const * out[rows], per_group) + ((abs(g_const) * cond_out[rows],) if cond else ())
     acc[order] = g_const * out
+    if cond:
+        S_caller = np.zeros((n, 2))
+        S_caller[order] = abs(g_const) * cond_out
+        return acc, (n_cells, n_leaves), S_caller
     return acc, (n_cells, n_leaves)
 
 

@@ -33,14 +33,17 @@ def cell_accel(x, c, M, Q, eps2, quadrupole=True):
     return a
 
 
-def tree_potential(pos, mass, theta, softening, g_const=1.0, quadrupole=True, order=None, opening_dtype=np.float64):
-    """(phi (n,) in the caller's order, (accepted cells, rejected level-0 nodes)); arguments as tree_oracle.tree_accel."""
+def tree_potential(pos, mass, theta, softening, g_const=1.0, quadrupole=True, order=None, opening_dtype=np.float64,
+                   groups=None):
+    """(phi (n,) in the caller's order, (accepted cells, rejected level-0 nodes)); arguments as tree_oracle.tree_accel.
+    groups: a list of target groups to walk alone -> (the rows of the listed groups one after another in TREE order,
+    [(cells, leaves) per listed group]), as tree_oracle.tree_accel(groups=) gives them."""
     pos = np.asarray(pos, dtype=np.float64)
     mass = np.asarray(mass, dtype=np.float64)
     n = len(pos)
     phi = np.zeros(n)
     if n == 0:
-        return phi, (0, 0)
+        return (np.zeros(0), []) if groups is not None else (phi, (0, 0))
     order = to.morton_order(pos) if order is None else np.asarray(order, dtype=np.int64)
     assert sorted(order.tolist()) == list(range(n)), "order is not a permutation"
     x, m = pos[order], mass[order]
@@ -49,12 +52,15 @@ def tree_potential(pos, mass, theta, softening, g_const=1.0, quadrupole=True, or
     eps2 = float(softening) ** 2
     od = opening_dtype
     n_cells = n_leaves = 0
-    out = np.zeros(n)
-    for g0 in range(0, n, to.GROUP):
+    out, per_group = np.zeros(n), []
+    walked = range(-(-n // to.GROUP)) if groups is None else [int(g) for g in groups]
+    assert all(0 <= g < -(-n // to.GROUP) for g in walked), "group outside the tree"
+    for g0 in (g * to.GROUP for g in walked):
         g1 = min(n, g0 + to.GROUP)
         xt = x[g0:g1]
         tlo, thi = xt.min(0).astype(od), xt.max(0).astype(od)
         f = np.zeros(g1 - g0)
+        before = (n_cells, n_leaves)
         front = np.array([0])
         for lvl in range(len(levels) - 1, -1, -1):
             L = levels[lvl]
@@ -87,6 +93,11 @@ def tree_potential(pos, mass, theta, softening, g_const=1.0, quadrupole=True, or
                     w[np.arange(g0, g1)[:, None] == j[None, :]] = 0.0               # j == i by index
                     f -= (m[j][None, :] * w).sum(1)
         out[g0:g1] = f
+        per_group.append((n_cells - before[0], n_leaves - before[1]))
+    if groups is not None:
+        rows = np.concatenate([np.arange(g * to.GROUP, min(n, g * to.GROUP + to.GROUP)) for g in walked]) if walked \
+            else np.zeros(0, dtype=np.int64)
+        return g_const * out[rows], per_group
     phi[order] = g_const * out
     return phi, (n_cells, n_leaves)
 
